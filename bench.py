@@ -3,13 +3,18 @@
 (BASELINE.json `metric`), plus achieved HBM GB/s of the embedding-gather kernel against the gfx950 roofline
 and the CPU baseline (oracle/torch_ref.py, the op-for-op TF2-CPU stand-in) timed on the same box.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" is one train_loop iteration without the optimizer (2.FM/ModelManager.py:171-177): index assembly,
 fused gather + FM, DNN part, sigmoid, Keras BCE, and every gradient materialised (dense parameters as dense
 tensors, the two tables as sorted-unique row sums).  Inputs (26 int64 [B,1] feature tensors + the label, the
 DataGenerator contract) are resident in HBM before the timed region starts.  One JSON line on rank 0.
+
+A plain run measures the headline figure alone: set-up, warm-up, the K timed steps, the outputs of the last step
+(--dump-outputs) and the line.  --full adds every secondary record after the timed steps: further timed regions, the
+rooflines, Zipf ids and other seeds, the batch sweep, the CrossNet GEMMs, the sharded DSSM, the optimizer steps, the
+replicas reference point of the sharded step and the CPU baseline.
 """
 import argparse
 import json
@@ -65,6 +70,12 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the CPU baseline sample")
     ap.add_argument("--adam-steps", type=int, default=10, help="extra: full train steps with Keras Adam as the reference applies it (dense sweep)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the secondary records after the timed steps (--repeats, --no-extras, --no-dssm, "
+                         "--adam-steps, --no-cpu-baseline and --cpu-seconds shape them)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (loss, dense gradients, the tables' row gradients) "
+                         "as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -79,6 +90,44 @@ def host_cores():
     except (OSError, ValueError):
         pass
     return n
+
+
+DUMP_BUDGET = 64 << 20          # bytes of .npy payload --dump-outputs may write
+
+
+def step_outputs(step):
+    """What a caller of the timed step receives from its last step, copied on the device: the loss, the dense gradients
+    by parameter name and the two tables' gradients as IndexedSlices (unique ids ascending, their summed rows)."""
+    if hasattr(step, "gradients"):
+        g = step.gradients()
+        ids, embed_rows, nu = g.pop("embed.embeddings")
+        w_rows = g.pop("w.embeddings")[1]
+    else:                                               # ShardedDeepFMStep: this rank's rows of the table
+        g = dict(step.g)
+        ids, embed_rows, w_rows, nu = step.table_grad
+    nu = int(nu.item()) if torch.is_tensor(nu) else int(nu)
+    out = {"loss": step.loss}
+    out.update(("grad_" + k, v) for k, v in g.items())
+    out.update(grad_table_ids=ids[:nu], grad_embed_rows=embed_rows[:nu], grad_w_rows=w_rows[:nu])
+    return {k: v.detach().clone() for k, v in out.items()}
+
+
+def dump_outputs(outputs, path):
+    """DIR/<name>.npy, float32 (ids as float64: exact below 2^53).  Beyond DUMP_BUDGET the rows of the table gradients
+    are a fixed, seeded sample (the same rows of ids, embed and w; ascending)."""
+    arrs = {k: v.cpu().numpy().astype(np.float64 if k == "grad_table_ids" else np.float32) for k, v in outputs.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_BUDGET:
+        row_keys = ("grad_table_ids", "grad_embed_rows", "grad_w_rows")
+        n = len(arrs["grad_table_ids"])
+        per_row = sum(arrs[k].nbytes for k in row_keys) / max(1, n)
+        keep = int((DUMP_BUDGET - (total - per_row * n)) // per_row)
+        idx = np.sort(np.random.Generator(np.random.PCG64(0)).choice(n, size=keep, replace=False))
+        for k in row_keys:
+            arrs[k] = arrs[k][idx]
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def cpu_baseline(args, names, seconds):
@@ -327,7 +376,7 @@ def main():
         t = torch.tensor([x], dtype=torch.float64, device="cpu" if rehearsal else "cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
-    from explicit_tf2_recommendation_amd import layers, engine, data, ops
+    from explicit_tf2_recommendation_amd import layers, engine, data
 
     V, F, E, B = args.vocab, CFG["fields"], CFG["embedding_dims"], args.batch
     names = ["C%d" % (i + 1) for i in range(F)]
@@ -431,9 +480,10 @@ def main():
     run_steps(args.steps)
     barrier()
     elapsed = time.perf_counter() - t0
+    outputs = step_outputs(step) if args.dump_outputs and rank == 0 else None
     # further regions of the same K steps (same graphs, same batches): the distribution behind the one reported number
     rep_ms = []
-    for _ in range(max(0, args.repeats)):
+    for _ in range(max(0, args.repeats) if args.full else 0):
         barrier()
         t1 = time.perf_counter()
         run_steps(args.steps)
@@ -456,7 +506,7 @@ def main():
     value = world * B * args.steps / elapsed
 
     replicas = None
-    if sharded_mode and not args.generic:
+    if args.full and sharded_mode and not args.generic:
         # reference point for the cost of the exchange: the same batches through the single-GPU fused step on a full
         # table replica per rank (no collective at all), timed the same way.  NOT the reported value.
         rstep = engine.DeepFMFusedStep(layer, B, gen.dims, gen.offsets, optimizer=None, use_graph=not args.no_graph)
@@ -485,6 +535,67 @@ def main():
         replicas = {"value": world * B * args.steps / rel, "unit": "examples/s", "ms_per_step": rel / args.steps * 1e3,
                     "note": "independent full-table replicas, no exchange (upper bound; not the reported value)"}
 
+    full = full_records(args, layer, gen, names, batches, Cy, calls_of, barrier, reduce_max, world, rank, local_rank,
+                        sharded_mode) if args.full else {}
+    extra = {}
+    if rep_ms:
+        r_ = np.array(rep_ms)
+        extra["stats"] = {"regions": len(rep_ms), "steps_per_region": args.steps,
+                          "ms_per_step_median": float(np.median(r_)), "ms_per_step_p10": float(np.percentile(r_, 10)),
+                          "ms_per_step_p90": float(np.percentile(r_, 90)), "ms_per_step_min": float(r_.min()),
+                          "value_median": world * B / (float(np.median(r_)) * 1e-3),
+                          "note": "further timed regions of the same K steps in this run (same graphs, same batches, barrier "
+                                  "+ synchronize on both sides each); `value` / `ms_per_step` are the FIRST region"}
+    if rank == 0:
+        out = {"metric": "examples/sec fwd+bwd, DeepFM 10M-vocab x16d batch 8192", "value": value,
+               "unit": "examples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+               "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+               "dtype": "f32", "data": "synthetic",
+               "config": {"workload": CFG["workload"], "vocab": V, "fields": F, "embedding_dims": E,
+                          "mlp_dims": CFG["mlp_dims"], "batch_per_gpu": B, "id_distribution": args.dist,
+                          "parallelism": ("1 process per GPU; fused table row-sharded (block partition), batch "
+                                          "data-parallel, RCCL all-to-all of ids / rows / row gradients, flat "
+                                          "all-reduce of dense gradients") if sharded_mode else
+                          ("1 process per GPU, independent full-table replicas" if world > 1 else "single GPU"),
+                          "global_batch": world * B,
+                          "hipgraph": ("one graph per %d steps incl. the RCCL collectives" % Cy
+                                       if not args.sharded_eager else False) if sharded_mode else
+                          (not args.no_graph) and
+                          ("one graph per %d steps, %d resident batches" % (Cy, n_batches) if cycle else "one per step"),
+                          "step": "sharded, de-duplicate first, fixed-capacity exchanges (constant split sizes, nothing read "
+                          "back by the host): per-column sort plan + id message + owner rank-merge for the next batch on a "
+                          "second stream (own communicator), owner gather, all-to-all of rows, fused fwd+bwd on them, "
+                          "per-id sums into the send slots, all-to-all of row gradients, owner sums"
+                          if sharded_mode else
+                          "generic" if args.generic else
+                          "fused: fwd+bwd kernel writing value rows straight to their de-duplicated slots (plan complete "
+                          "before the kernel), then reduction + remaining segment sums in one launch; de-duplication "
+                          "plan of batch k+1 (per-column sort, second stream) overlaps step k"},
+               "loss": loss}
+        if rehearsal:
+            out["config"]["rehearsal"] = ("--dist-backend gloo: %d ranks share the visible GPUs, exchanges hop through host "
+                                          "memory -- a rehearsal of the multi-rank control flow, NOT a measurement" % world)
+        if replicas is not None:
+            out["replicas_no_exchange"] = replicas
+        out.update(full)
+        out.update(extra)
+        if args.full and not args.no_cpu_baseline and world == 1:
+            out["cpu_baseline"] = cpu_baseline(args, names, args.cpu_seconds)
+        if outputs is not None:
+            dump_outputs(outputs, args.dump_outputs)
+        sys.stdout.flush()
+        os.write(json_fd, (json.dumps(out) + "\n").encode())
+    if dist.is_initialized():
+        dist.destroy_process_group()
+
+
+def full_records(args, layer, gen, names, batches, Cy, calls_of, barrier, reduce_max, world, rank, local_rank,
+                 sharded_mode):
+    """--full: the records of the line besides the headline figure, measured after the timed steps on the same layer and
+    resident batches.  Returns the keys they add to the line."""
+    from explicit_tf2_recommendation_amd import engine, data, ops
+    V, F, E, B = args.vocab, CFG["fields"], CFG["embedding_dims"], args.batch
+    n_batches = len(batches)
     # ---- rooflines.  Average launch durations are measured live with HIP events around `reps` back-to-back launches
     # replayed from a hipGraph (events and replay share torch's current stream); `traffic` = HBM bytes per launch
     # from the PMC passes committed in profiles/r01_pmc_traffic.json (separate --pmc FETCH_SIZE / WRITE_SIZE runs of
@@ -612,14 +723,6 @@ def main():
                         "latencies, then ~3 us for 27 MB of writes to leave the chip")
 
     extra = {}
-    if rep_ms:
-        r_ = np.array(rep_ms)
-        extra["stats"] = {"regions": len(rep_ms), "steps_per_region": args.steps,
-                          "ms_per_step_median": float(np.median(r_)), "ms_per_step_p10": float(np.percentile(r_, 10)),
-                          "ms_per_step_p90": float(np.percentile(r_, 90)), "ms_per_step_min": float(r_.min()),
-                          "value_median": world * B / (float(np.median(r_)) * 1e-3),
-                          "note": "further timed regions of the same K steps in this run (same graphs, same batches, barrier "
-                                  "+ synchronize on both sides each); `value` / `ms_per_step` are the FIRST region"}
     if not args.no_extras and not sharded_mode and not args.generic and world == 1:
         # the same measurement on Zipf(1.05) ids: hot ids form long runs in the de-duplication
         gz_ = data.SyntheticGenerator(names, V, dist="zipf", seed=rank)
@@ -733,45 +836,8 @@ def main():
             extra["keras_adam_lazy_exact_flush_ms"] = (time.perf_counter() - t1) * 1e3
             del fresh
 
-    if rank == 0:
-        out = {"metric": "examples/sec fwd+bwd, DeepFM 10M-vocab x16d batch 8192", "value": value,
-               "unit": "examples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-               "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-               "dtype": "f32", "data": "synthetic",
-               "config": {"workload": CFG["workload"], "vocab": V, "fields": F, "embedding_dims": E,
-                          "mlp_dims": CFG["mlp_dims"], "batch_per_gpu": B, "id_distribution": args.dist,
-                          "parallelism": ("1 process per GPU; fused table row-sharded (block partition), batch "
-                                          "data-parallel, RCCL all-to-all of ids / rows / row gradients, flat "
-                                          "all-reduce of dense gradients") if sharded_mode else
-                          ("1 process per GPU, independent full-table replicas" if world > 1 else "single GPU"),
-                          "global_batch": world * B,
-                          "hipgraph": ("one graph per %d steps incl. the RCCL collectives" % Cy
-                                       if not args.sharded_eager else False) if sharded_mode else
-                          (not args.no_graph) and
-                          ("one graph per %d steps, %d resident batches" % (Cy, n_batches) if cycle else "one per step"),
-                          "step": "sharded, de-duplicate first, fixed-capacity exchanges (constant split sizes, nothing read "
-                          "back by the host): per-column sort plan + id message + owner rank-merge for the next batch on a "
-                          "second stream (own communicator), owner gather, all-to-all of rows, fused fwd+bwd on them, "
-                          "per-id sums into the send slots, all-to-all of row gradients, owner sums"
-                          if sharded_mode else
-                          "generic" if args.generic else
-                          "fused: fwd+bwd kernel writing value rows straight to their de-duplicated slots (plan complete "
-                          "before the kernel), then reduction + remaining segment sums in one launch; de-duplication "
-                          "plan of batch k+1 (per-column sort, second stream) overlaps step k"},
-               "roofline": roofline, "roofline_gather": roofline_gather, "roofline_gather_e32": roofline_gather_e32,
-               "roofline_gather_e64": roofline_gather_e64, "loss": loss}
-        if rehearsal:
-            out["config"]["rehearsal"] = ("--dist-backend gloo: %d ranks share the visible GPUs, exchanges hop through host "
-                                          "memory -- a rehearsal of the multi-rank control flow, NOT a measurement" % world)
-        if replicas is not None:
-            out["replicas_no_exchange"] = replicas
-        out.update(extra)
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(args, names, args.cpu_seconds)
-        sys.stdout.flush()
-        os.write(json_fd, (json.dumps(out) + "\n").encode())
-    if dist.is_initialized():
-        dist.destroy_process_group()
+    return dict(roofline=roofline, roofline_gather=roofline_gather, roofline_gather_e32=roofline_gather_e32,
+                roofline_gather_e64=roofline_gather_e64, **extra)
 
 
 if __name__ == "__main__":

@@ -2,10 +2,10 @@
 """profiles/r03_pmc_traffic.json from the two rocprofv3 counter passes (FETCH_SIZE, WRITE_SIZE; separate runs, as
 MI355X_MICROARCH.md's HBM section prescribes):
 
-    rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_f -o f -- python3 bench.py --steps 20 --warmup 8 \
+    rocprofv3 --pmc FETCH_SIZE --output-format csv -d runs/pmc_f -o f -- python3 bench.py --full --steps 20 --warmup 8 \
         --no-cpu-baseline --adam-steps 0
-    rocprofv3 --pmc WRITE_SIZE ... -d gpurun_out/pmc_w -o w -- (same command)
-    python scripts/pmc_traffic.py gpurun_out/pmc_f/f_counter_collection.csv gpurun_out/pmc_w/w_counter_collection.csv [commit]
+    rocprofv3 --pmc WRITE_SIZE ... -d runs/pmc_w -o w -- (same command)
+    python scripts/pmc_traffic.py runs/pmc_f/f_counter_collection.csv runs/pmc_w/w_counter_collection.csv [commit]
 
 ``commit``: the commit of the tree the passes ran on (a GPU box has no .git: pass `git rev-parse --short HEAD` from here);
 bench.py prints it beside ``traffic`` so that a counter file older than the kernels is visible.
