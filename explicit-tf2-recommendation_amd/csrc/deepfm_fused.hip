@@ -1218,6 +1218,20 @@ __device__ __forceinline__ void fixup_body(const ColSegArgs& k_in, int bidx) {
 #endif
   const int wv = tid >> 6;
   constexpr int NWV_F = FIX_T / 64;
+  // more than one round: the list goes into ascending run order first.  The round a run falls in fixes how many waves
+  // add it (16 / nr) and so the order of its additions; taken in the order the atomics above landed, a run's sum changed
+  // in its last bits from one launch to the next.  (One round: every run gets the same 16 / nr waves wherever it sits.)
+  if (n_huge > NWV_F) {                                          // (uniform over the workgroup)
+    int hs0 = 0, hs1 = 0, hu = 0, rk = 0;
+    float hg = 0.f;
+    if (tid < n_huge) {
+      hs0 = huge_s0[tid]; hs1 = huge_s1[tid]; hu = huge_u[tid]; hg = huge_gz[tid];
+      for (int j = 0; j < n_huge; ++j) rk += huge_u[j] < hu ? 1 : 0;   // runs are distinct: ranks 0 .. n_huge-1
+    }
+    __syncthreads();
+    if (tid < n_huge) { huge_s0[rk] = hs0; huge_s1[rk] = hs1; huge_u[rk] = hu; huge_gz[rk] = hg; }
+    __syncthreads();
+  }
   for (int h0 = 0; h0 < n_huge; h0 += NWV_F) {
     const int nr = n_huge - h0 < NWV_F ? n_huge - h0 : NWV_F;    // runs of this round
     const int wpr = NWV_F / nr;                                  // waves per run

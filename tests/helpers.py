@@ -144,3 +144,103 @@ def to_torch(obj, dtype=None, requires_grad=False, device=None):
             t = t.to(device)
         return t
     return obj
+
+
+# ------------------------------------------------------------------------------------------------
+# batches with a prescribed de-duplication plan (tests/test_gpu_plan_edges.py)
+# ------------------------------------------------------------------------------------------------
+PLAN_LAYOUTS = ("scattered", "clustered", "hot", "ranked")
+
+
+def field_offsets(dims):
+    """DataGenerator id-space contract: field f owns [offsets[f], offsets[f] + dims[f]), offsets ascending."""
+    return [int(x) for x in np.concatenate([[0], np.cumsum(dims[:-1])])] if len(dims) else []
+
+
+def plan_batch(B, dims, offsets, spectra, layout="scattered", seed=0, ends=True):
+    """A DeepFM batch whose columns have exactly the runs of equal ids the caller asks for.
+
+    spectra[f] is either a sequence of run lengths summing to B (the multiset of the column's runs: one distinct key
+    per run) or "uniform" (ids drawn uniformly from the field).  Keys are distinct and lie inside the field
+    [offsets[f], offsets[f] + dims[f]); with ``ends`` (a bool, or one per column) key 0 and key dims[f]-1 are among
+    them.  Layouts:
+      scattered  runs get random keys, their members random examples;
+      clustered  runs get random keys, the members of a run are adjacent examples;
+      hot        the longest runs get the smallest keys (hot neighbours at the head of the sorted column), members
+                 at random examples;
+      ranked     spectra[f][u] is the length of the run of the u-th smallest key (places a run at a chosen plan
+                 slot), members at random examples.
+    Labels are Bernoulli(0.25) from the same seeded generator.  Returns {"f<i>": int64 [B,1], ..., "label": float32
+    [B,1]}."""
+    if layout not in PLAN_LAYOUTS:
+        raise ValueError("layout must be one of %s" % (PLAN_LAYOUTS,))
+    r = rng(seed)
+    F = len(dims)
+    if len(offsets) != F or len(spectra) != F:
+        raise ValueError("one dim, offset and spectrum per column")
+    ends_f = list(ends) if isinstance(ends, (list, tuple)) else [bool(ends)] * F
+    out = {}
+    for f in range(F):
+        dim, off, spec = int(dims[f]), int(offsets[f]), spectra[f]
+        if isinstance(spec, str):
+            if spec != "uniform":
+                raise ValueError("a spectrum is a list of run lengths or 'uniform'")
+            keys = r.integers(0, dim, size=B, dtype=np.int64)
+            if ends_f[f] and B >= 2:
+                keys[r.choice(B, 2, replace=False)] = (0, dim - 1)
+            out["f%d" % f] = (keys + off).reshape(B, 1)
+            continue
+        lens = np.asarray(spec, dtype=np.int64)
+        n = lens.size
+        if n == 0 or lens.min() < 1 or lens.sum() != B:
+            raise ValueError("column %d: run lengths must be >= 1 and sum to B=%d" % (f, B))
+        if n > dim:
+            raise ValueError("column %d: %d runs need as many distinct keys, the field has %d" % (f, n, dim))
+        # n distinct keys, ascending
+        if ends_f[f] and n >= 2:
+            inner = r.choice(dim - 2, n - 2, replace=False) + 1 if n > 2 else np.zeros(0, np.int64)
+            keys = np.sort(np.concatenate([[0, dim - 1], inner]).astype(np.int64))
+        elif ends_f[f]:
+            keys = np.zeros(1, np.int64)
+        else:
+            keys = np.sort(r.choice(dim, n, replace=False).astype(np.int64))
+        if layout == "hot":
+            lens = np.sort(lens)[::-1]                       # longest run on the smallest key
+        elif layout in ("scattered", "clustered"):
+            lens = lens[r.permutation(n)]
+        members = np.repeat(keys, lens)                      # run of keys[u] has lens[u] members
+        if layout == "clustered":
+            order = r.permutation(n)                         # runs in random example order, members adjacent
+            col = np.concatenate([np.full(lens[u], keys[u], np.int64) for u in order])
+        else:
+            col = members[r.permutation(B)]
+        out["f%d" % f] = (col + off).reshape(B, 1)
+    out["label"] = (r.random((B, 1)) < 0.25).astype(np.float32)
+    return out
+
+
+def fill_spectrum(B, runs=(), pairs=0):
+    """run lengths: the given runs, `pairs` runs of two, singles for the rest of the B examples"""
+    runs = [int(x) for x in runs]
+    rest = B - sum(runs) - 2 * pairs
+    if rest < 0:
+        raise ValueError("runs do not fit in B=%d" % B)
+    return runs + [2] * pairs + [1] * rest
+
+
+def host_plan(col, lo):
+    """The de-duplication plan of one column as the sort defines it: perm = stable order of the keys (ids - lo),
+    col_uid = the distinct ids ascending, col_seg = first sorted position of every run (then B up to index B),
+    dloc[e] = run index of example e, sign bit set unless e is the first member of its run."""
+    col = np.asarray(col, np.int64).reshape(-1)
+    B = col.size
+    perm = np.argsort(col - lo, kind="stable").astype(np.int32)
+    uid, first, inv = np.unique(col, return_index=True, return_inverse=True)
+    nu = uid.size
+    seg = np.full(B + 1, B, np.int32)
+    seg[:nu] = np.searchsorted(col[perm], uid, side="left")
+    dloc = inv.astype(np.int64)
+    head = np.zeros(B, bool)
+    head[first] = True
+    dloc = np.where(head, dloc, dloc | (1 << 31)).astype(np.uint32).view(np.int32)
+    return dict(perm=perm, col_uid=uid, col_seg=seg, col_nu=nu, dloc=dloc)
