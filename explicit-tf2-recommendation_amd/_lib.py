@@ -40,7 +40,6 @@ SIGNATURES = {
     "rec_cosine_bwd_f32": (i32, [p, p, i64, i32, p, p, p, p]),
     "rec_bce_fwd_bwd_f32": (i32, [p, p, i64, p, p, p, p]),
     "rec_adam_lr_t_f32": (f32, [f32, f32, f32, i64]),
-    "rec_adam_advance_f32": (i32, [p, p, i64, p, p]),
     "rec_adam_dense_multi_f32": (i32, [i32, p, p, p, p, p, p, f32, f32, f32, p]),
     "rec_deepfm_fused_post_direct_adam_dev_f32": (i32, [i32, i64] + [p] * 19 + [p, i64, i64, p, p, p, p, i64, i64, p, f32,
                                                                            f32, f32, p, p, p]),
@@ -73,30 +72,20 @@ SIGNATURES = {
     "rec_emb_gather_lists_f32": (i32, [p, i64, i32, i64, p, i32, i64, p, p, p]),
     "rec_block_copy": (i32, [p, i32, i64, p, p]),
     "rec_auc_hist_update_f32": (i32, [p, p, i64, p, i32, p, p, i32, p, p]),
-    "rec_shard_slab_map_i64": (i32, [p, p, p, p, i64, i64, i32, i64, p, p, p, p]),
     "rec_shard_slab_map_uslot_i64": (i32, [p, p, p, p, i64, i64, i32, i64, p, p, p, p, p]),
     "rec_dedup_plan_sorted_slabs_i64": (i32, [p, i32, i64, i64, p, p, p, p, p, sz, p]),
     "rec_deepfm_fused_post_slots_f32": (i32, [i32, i64] + [p] * 17 + [p]),
     "rec_permute_rows_f32": (i32, [p, p, i64, i32, i32, p, p]),
     "rec_deepfm_fused_workspace_bytes": (sz, [i64, i32]),
-    "rec_deepfm_fused_fwd_bwd_f32": (i32, [p, i64, i64, p, i32, i64, p, p, p, p, p, p, p, p, p, p, p, p, p, p, p, p, p,
-                                           p, p, p, p, p]),
-    "rec_deepfm_fused_step_f32": (i32, [p, i64, i64, p, i32, i64] + [p] * 21 + [p] * 8 + [i32, p]),
-    "rec_deepfm_fused_main_f32": (i32, [p, i64, i64, p, i32, i64] + [p] * 13 + [p]),
     "rec_deepfm_fused_post_f32": (i32, [i32, i64] + [p] * 19 + [i32, p]),
     "rec_colsort_workspace_bytes": (sz, [i64, i32]),
     "rec_colsort_plan_i64": (i32, [p, i32, i64, i64, p, i64, p, p, p, p, p, p, p]),
     "rec_colsort_plan_dest_i64": (i32, [p, i32, i64, i64, p, i64, p, p, p, p, p, p, p, p]),
-    "rec_deepfm_fused_main_direct_f32": (i32, [p, i64, i64, p, i32, i64] + [p] * 13 + [p, p, p] + [p]),
     "rec_deepfm_fused_post_direct_f32": (i32, [i32, i64] + [p] * 19 + [p]),
     "rec_deepfm_k0t_f32": (i32, [p, i32, p, p]),
     "rec_deepfm_fused3_main_f32": (i32, [p, i64, i64, p, i32, i64] + [p] * 14 + [p]),
     "rec_deepfm_fused3_main_direct_f32": (i32, [p, i64, i64, p, i32, i64] + [p] * 14 + [p, p, p] + [p]),
     "rec_deepfm_fused3_main_direct_adv_f32": (i32, [p, i64, i64, p, i32, i64] + [p] * 14 + [p, p, p] + [p, p, i64, p] + [p]),
-    "rec_deepfm_fused_post_direct_adam_f32": (i32, [i32, i64] + [p] * 19 + [p, i64, i64, p, p, p, p, i64, f32, f32, f32,
-                                                                          f32, p]),
-    "rec_colseg_sum_f32": (i32, [p, p, p, p, p, p, i64, i32, p, p, p, p, p]),
-    "rec_colseg_sum_packed_f32": (i32, [p, p, p, p, p, p, i64, i32, p, p, p, p]),
     "rec_din_prepare_f32": (i32, [p, p, i32, i32, p, p, p, p]),
     "rec_din_prepare_bwd_f32": (i32, [p, p, i32, i32, p, p]),
     "rec_din_attn_fwd_f32": (i32, [p, i64, i64, i32, i32, p, i64, i32, p, p, i32, i32, p, p, p, p, p, i64, i32, p, p, p,

@@ -7,15 +7,21 @@ OUT=libmi355rec.so
 FLAGS="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -I${ROOT}/include -Wno-unused-result"
 mkdir -p obj
 pids=()
+objs=()
 for f in *.hip; do
   o=obj/${f%.hip}.o
-  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ common.h -nt "$o" ] || [ ${ROOT}/include/mi355rec.h -nt "$o" ]; then
+  objs+=("$o")
+  stale=0
+  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ ${ROOT}/include/mi355rec.h -nt "$o" ]; then stale=1; fi
+  for h in *.h; do if [ "$h" -nt "$o" ]; then stale=1; fi; done     # any header of csrc/, not only common.h
+  if [ $stale = 1 ]; then
     hipcc $FLAGS -c "$f" -o "$o" &
     pids+=($!)
   fi
 done
 for p in "${pids[@]}"; do wait $p; done
-hipcc --offload-arch=gfx950 -shared -fPIC obj/*.o -o $OUT
+# only the objects of the current sources: one left behind by a removed source would still be linked
+hipcc --offload-arch=gfx950 -shared -fPIC "${objs[@]}" -o $OUT
 echo "built $(pwd)/$OUT"
 
 # TORCH_LIBRARY(mi355rec) registration of the hot operators over the same C ABI: host-only C++ (g++), linked against the

@@ -1,11 +1,11 @@
-// Fused DeepFM forward + backward kernel, third form (2.FM/CustomLayers.py:279-308 under 2.FM/ModelManager.py:171-177;
-// embedding_dims 16, mlp_dims [32, 8], fused [embed 16 | w | pad] rows).  Same inputs, outputs and workspace layout as
-// deepfm_fwd_bwd_kernel of deepfm_fused.hip (gz, IndexedSlices value rows, per-workgroup partials of the dense
-// gradients) -- the post launches of that file finish the step -- but a different schedule.
+// Main kernel of the fused DeepFM train step (2.FM/CustomLayers.py:279-308 under 2.FM/ModelManager.py:171-177;
+// embedding_dims 16, mlp_dims [32, 8], fused [embed 16 | w | pad] rows).  It writes gz, the IndexedSlices value rows and
+// the per-workgroup partials of the dense gradients into the workspace of deepfm_fused.h; the post launch of
+// deepfm_fused.hip finishes the step.
 //
 // What the B sweep of round 3 showed (profiles/r03_b_sweep.json): the chip sustains ~50 G random 128-byte lines/s, one CU
-// pulls ~25-30 GB/s from HBM (its 832 rows of a 32-example tile need ~4 us whatever the chip does), and the old kernel
-// costs ~20 us PER TILE however many tiles a CU works through: ids -> rows -> layer 1 -> head -> backward is one
+// pulls ~25-30 GB/s from HBM (its 832 rows of a 32-example tile need ~4 us whatever the chip does), and the kernel this
+// one replaced cost ~20 us PER TILE however many tiles a CU works through: ids -> rows -> layer 1 -> head -> backward is one
 // dependent chain per workgroup, with the 0.65 GFLOP of fp32 MFMA (4.2 us per CU at the f32 rate) strictly behind the
 // gather.  Here one workgroup still owns 32 examples and ONE set of dK0 accumulators, but works as two HALVES of 16
 // examples (waves 0-3 = half A, waves 4-7 = half B, every SIMD hosts one wave of each) that run one phase apart:
@@ -33,18 +33,14 @@
 //                  value row = dz (S - x) + dX needs no LDS
 //   dK0^T          [unit][dim] = dpre1^T . X_f: the only product that needs X with examples on the k axis: rows are
 //                  parked in LDS once (XT) and read back transposed, 4 bytes per lane and k-step, conflict-free
-#include "common.h"
+#include "deepfm_fused.h"
 #include <math.h>
 
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int EX = 32;        // examples per workgroup
 constexpr int HEX = 16;       // examples per half
-constexpr int E16 = 16;
-constexpr int U1 = 32, U2 = 8;
-constexpr int SMALL = 320;    // floats of small partials per workgroup (layout of deepfm_fused.hip)
 constexpr int NWV = 8, HWV = 4;
 constexpr int MAXF = 7;       // fields per wave (F <= 28 over the 4 waves of a half)
 constexpr int HS1 = 36;       // row stride of H1s / DP1 / the partial layer-1 tiles (16-byte aligned rows)
@@ -192,8 +188,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const int th_ = tid & 255;                               // thread index inside the half
   STAMP3(0);
 
-  // the device-side step counter of the optimizer (rec_adam_advance_f32's job, without its launch): this kernel does not
-  // read it; the catch-up kernel before it needs the old value, the post launch and the dense update after it the new one
+  // the device-side step counter of the optimizer, advanced here instead of in a launch of its own: this kernel does
+  // not read it; the catch-up kernel before it needs the old value, the post launch and the dense update after it the
+  // new one
   if (a.step_dev && blockIdx.x == 0 && tid == 0) {
     const int64_t s = *a.step_dev + 1;
     *a.step_dev = s;
@@ -604,34 +601,34 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     STAMP3(6);
   }
 
-  // ---- small per-workgroup partials over the 32 examples (fixed order), as in deepfm_fused.hip: after barrier 3
+  // ---- small per-workgroup partials over the 32 examples (fixed order), SMALL block of deepfm_fused.h: after barrier 3
   float* sm = a.small + (int64_t)blockIdx.x * SMALL;
   if (wave >= 4) {
     const int t2 = tid - 256, k = t2 >> 3, u = t2 & 7;
     float s = 0.f;
 #pragma unroll 8
     for (int e = 0; e < EX; ++e) s += H1s[e * HS1 + k] * dp2s[e * U2 + u];
-    sm[t2] = s;                                              // dK1 [32][8]
+    sm[SM_DK1 + t2] = s;                                     // dK1 [32][8]
   } else if (wave == 3) {
     if (lane < U1) {
       float t = 0.f;
 #pragma unroll 8
       for (int e = 0; e < EX; ++e) t += DP1[e * HS1 + lane];
-      sm[256 + lane] = t;                                    // db0
+      sm[SM_DB0 + lane] = t;                                 // db0
     }
   } else if (wave == 2) {
     if (lane < U2) {
       float t1 = 0.f, t2 = 0.f;
 #pragma unroll 8
       for (int e = 0; e < EX; ++e) { t1 += dp2s[e * U2 + lane]; t2 += h2s[e * U2 + lane] * dzs[e]; }
-      sm[288 + lane] = t1;                                   // db1
-      sm[296 + lane] = t2;                                   // dK2
+      sm[SM_DB1 + lane] = t1;                                // db1
+      sm[SM_DK2 + lane] = t2;                                // dK2
     } else if (lane == 32) {
       float t1 = 0.f, t2 = 0.f;
 #pragma unroll 8
       for (int e = 0; e < EX; ++e) { t1 += dzs[e]; t2 += lss[e]; }
-      sm[304] = t1;                                          // db2 = dbias
-      sm[305] = t2;                                          // sum of per-example BCE terms
+      sm[SM_DB2] = t1;                                       // db2 = dbias
+      sm[SM_LOSS] = t2;                                      // sum of per-example BCE terms
     }
   }
   STAMP3(7);
@@ -705,9 +702,10 @@ static int launch_fused3(const float* table, int64_t ld, int64_t V, const int64_
     if (!cols_host[f]) return REC_E_ARG;
     cp.p[f] = cols_host[f];
   }
-  const int nwg = (int)ceil_div64(B, EX);
-  float* dK0part = (float*)workspace;
-  float* small = dK0part + (size_t)nwg * F * E16 * U1;
+  const FusedWorkspace ws = fused_workspace(B, F);
+  const int nwg = ws.nwg;
+  float* dK0part = ws.dK0part(workspace);
+  float* small = ws.small(workspace);
 #ifdef REC_FUSED_STAMPS
   static unsigned long long* stamps = nullptr;
   if (!stamps && hipMalloc(&stamps, sizeof(unsigned long long) * 12 * NWV * 65536) != hipSuccess) return REC_E_ARG;
@@ -756,7 +754,7 @@ extern "C" int rec_deepfm_fused3_main_direct_f32(const float* table, int64_t ld,
                        workspace, dloc, col_nu, g_embed_rows, true, stream);
 }
 
-// rec_deepfm_fused3_main_direct_f32 + rec_adam_advance_f32 in one launch: *step_dev += 1 and *lr_t_dev =
+// rec_deepfm_fused3_main_direct_f32 that also advances the optimizer's device-side step: *step_dev += 1 and *lr_t_dev =
 // lr_table[min(*step_dev, n_table) - 1] are done by the fused kernel's first thread (the kernel itself reads neither), so the
 // post launch and the dense update behind it see the new step, the catch-up kernel before it saw the old one.
 extern "C" int rec_deepfm_fused3_main_direct_adv_f32(const float* table, int64_t ld, int64_t V,

@@ -557,16 +557,6 @@ __global__ __launch_bounds__(256) void adam_rows_lazy_kernel(float* __restrict__
   var[id * ld + d] = xx;
 }
 
-// ---- device-side step size: *step += 1, *lr_t = table[min(step, n) - 1].  The table holds Keras' bias-corrected step size
-// of steps 1..n as the host computes it (adam_lr_t: float32 pow), so a graph-replayed train step uses bit for bit the
-// values an eagerly enqueued one gets passed; beyond the table the correction factors are 1 in float32 (b2^t < 2^-24).
-__global__ void adam_advance_kernel(int64_t* __restrict__ step, const float* __restrict__ tab, int64_t n,
-                                    float* __restrict__ lr_t) {
-  const int64_t t = *step + 1;
-  *step = t;
-  *lr_t = tab[(t < n ? t : n) - 1];
-}
-
 // Adam on several small dense parameters in ONE launch (the 7 dense parameters of DeepFM were 7 launches at the launch
 // floor); arithmetic of adam_dense_kernel, step size from device memory
 constexpr int ADAM_MULTI_MAX = 16;
@@ -796,14 +786,6 @@ extern "C" int rec_adam_dense_f32(float* var, float* m, float* v, const float* g
 }
 
 extern "C" float rec_adam_lr_t_f32(float lr, float b1, float b2, int64_t t) { return adam_lr_t(lr, b1, b2, t); }
-
-extern "C" int rec_adam_advance_f32(int64_t* step_dev, const float* lr_table, int64_t n_table, float* lr_t_dev,
-                                    void* stream) {
-  if (!step_dev || !lr_table || !lr_t_dev || n_table <= 0) return REC_E_ARG;
-  hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(1), 0, as_stream(stream), step_dev, lr_table, n_table, lr_t_dev);
-  REC_LAUNCH_CHECK();
-  return REC_OK;
-}
 
 extern "C" int rec_adam_dense_multi_f32(int n_tensors, float* const* var, float* const* m, float* const* v,
                                         const float* const* g, const int64_t* numel, const float* lr_t_dev, float b1,

@@ -420,20 +420,6 @@ __global__ __launch_bounds__(256) void shard_slab_map_kernel(const int64_t* __re
 
 }  // namespace
 
-extern "C" int rec_shard_slab_map_i64(const int64_t* uniq_ids, const int64_t* n_uniq, const int32_t* seg_start,
-                                      const int32_t* perm, int64_t n, int64_t rows_per_shard, int n_shard, int64_t cap,
-                                      int64_t* msg, int64_t* slot, int* oob_flag, void* stream) {
-  if (n < 0 || rows_per_shard <= 0 || n_shard <= 0 || cap <= 0) return REC_E_ARG;
-  if (n_shard > MAX_SHARD) return REC_E_UNSUPPORTED;
-  if (n == 0) return REC_OK;
-  if (!uniq_ids || !n_uniq || !seg_start || !perm || !msg || !slot) return REC_E_ARG;
-  const int64_t threads = n > n_shard ? n : n_shard;
-  hipLaunchKernelGGL(shard_slab_map_kernel, dim3((unsigned)ceil_div64(threads, 256)), dim3(256), 0, as_stream(stream),
-                     uniq_ids, n_uniq, seg_start, perm, n, rows_per_shard, n_shard, cap, msg, slot, nullptr, oob_flag);
-  REC_LAUNCH_CHECK();
-  return REC_OK;
-}
-
 extern "C" int rec_shard_slab_map_uslot_i64(const int64_t* uniq_ids, const int64_t* n_uniq, const int32_t* seg_start,
                                             const int32_t* perm, int64_t n, int64_t rows_per_shard, int n_shard,
                                             int64_t cap, int64_t* msg, int64_t* slot, int64_t* uslot, int* oob_flag,

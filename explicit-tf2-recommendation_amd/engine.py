@@ -261,6 +261,31 @@ class DeepFMTrainStep:
         return out
 
 
+class _K0T:
+    """Transposed copy K0^T [32, F*16] of layer 1's kernel for the fused kernel (csrc/deepfm_fused3.hip reads its K0
+    operand as 16-byte pieces of K0^T), refreshed only when needed: the kernel reads it only when K0 does not fit in LDS
+    beside the rows (F > 26), and only a changed parameter needs a new transpose."""
+
+    def __init__(self, layer, F):
+        self.layer, self.F = layer, F
+        self.buf = torch.empty((32, F * 16), dtype=torch.float32, device=layer.MLP_layer1.kernel_0.device)
+        self._ver = None
+
+    def refresh(self, st=None, force=False):
+        """Re-transpose if the parameter changed by torch (its version counter) -- or, ``force``, after an in-stream
+        update through the C ABI, which the version counter does not see."""
+        if self.F <= 26:
+            return
+        K0 = self.layer.MLP_layer1.kernel_0
+        ver = (K0._version, K0.data_ptr())
+        if force or ver != self._ver:
+            if st is None:
+                st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            check(lib.rec_deepfm_k0t_f32(_p(K0), self.F, _p(self.buf), st), "rec_deepfm_k0t_f32")
+            if not force:
+                self._ver = ver
+
+
 def _bits(n):
     b = 1
     while (1 << b) < n:
@@ -269,10 +294,10 @@ def _bits(n):
 
 
 class DeepFMFusedStep:
-    """The same train_loop iteration as DeepFMTrainStep in two launches on the main stream (csrc/deepfm_fused.hip):
-    the fused forward+backward kernel, then ONE launch for the fixed-order reduction of its partials and the segment
-    sums -- plus, behind the steps of a call, the per-column LDS sort of the de-duplication plans of the batches announced
-    for the next call (they depend only on the ids).  ``many()`` runs several iterations as one captured hipGraph.
+    """The same train_loop iteration as DeepFMTrainStep in two launches on the main stream: the fused forward+backward
+    kernel (csrc/deepfm_fused3.hip), then ONE launch (csrc/deepfm_fused.hip) for the fixed-order reduction of its partials
+    and the segment sums -- plus, behind the steps of a call, the per-column LDS sort (csrc/colsort.hip) of the
+    de-duplication plans of the batches announced for the next call (they depend only on the ids).  ``many()`` runs several iterations as one captured hipGraph.
 
     Requirements (checked; otherwise use DeepFMTrainStep): embedding_dims 16, mlp_dims [32,8], fused table layout,
     F <= 28, B <= 16384, and the DataGenerator id-space contract -- ``field_offsets[f]``/``field_dims[f]`` =
@@ -285,7 +310,7 @@ class DeepFMFusedStep:
     MAX_GRAPHS = 64     # captured hipGraphs kept (least recently used beyond that are dropped with the inputs they hold)
 
     def __init__(self, layer, batch_size, field_dims, field_offsets, optimizer=None, lr=1e-3, use_graph=True,
-                 direct=True, kernel=None, want_prob=False):
+                 direct=True, want_prob=False):
         self.layer = layer
         self.direct = bool(direct)
         self.B = B = int(batch_size)
@@ -364,7 +389,6 @@ class DeepFMFusedStep:
         # priority the device offers -- the range is (0, -1), the default 0 is the lowest, and a step enqueued on a
         # priority -1 stream ran 2.5x SLOWER from its graphs: a sort workgroup cannot share a CU with a fused-kernel
         # workgroup, so concurrency only moved the wait into one fused launch in eight)
-        self._advanced = False                               # the fused launch of the step in flight advanced the step counter
         if optimizer is not None:
             self.state = {name: (torch.zeros(p.shape, **f32), torch.zeros(p.shape, **f32))
                           for name, p in layer.named_parameters()}
@@ -392,9 +416,10 @@ class DeepFMFusedStep:
                 self.state["w.embeddings"] = (fused[:, 17:18], fused[:, 18:19])
             self._last = (torch.zeros(self.V, dtype=torch.int32, device=dev)
                           if optimizer == "keras_adam_lazy" else None)    # the step every row holds
-            # the step counter and the bias-corrected step size live on the device (rec_adam_advance_f32): the train step
-            # holds no per-step host scalar, so it is captured and replayed like the gradient-only step.  The table holds
-            # lr_t of steps 1..N exactly as the host-side entry points compute it; beyond it the corrections are 1.0f
+            # the step counter and the bias-corrected step size live on the device (advanced by the fused launch): the
+            # train step holds no per-step host scalar, so it is captured and replayed like the gradient-only step.  The
+            # table holds lr_t of steps 1..N exactly as the host-side entry points compute it; beyond it the corrections
+            # are 1.0f
             N = 32768
             tab = [lib.rec_adam_lr_t_f32(lr, 0.9, 0.999, t) for t in range(1, N + 1)]
             self._lr_tab = torch.tensor(tab, **f32)
@@ -411,29 +436,9 @@ class DeepFMFusedStep:
         import collections
         self._graphs = collections.OrderedDict()            # gkey -> (graph, inputs kept alive), LRU order
         self._seen = collections.OrderedDict()              # gkeys enqueued eagerly once (addresses only: nothing is held)
-        # transposed copy of layer 1's kernel for the fused kernel (csrc/deepfm_fused3.hip reads its K0 operand as 16-byte
-        # pieces of K0^T); refreshed whenever the parameter changed -- by torch (its version counter) or by this step's
-        # own optimizer launches (which re-transpose in the same stream)
-        self.kernel_version = 3 if kernel is None else int(kernel)
-        self._k0t = torch.empty((32, D), **f32)
-        self._k0_ver = None
-
-    def _ensure_k0t(self, st=None):
-        if self.F <= 26:
-            return                                           # K0 is staged in LDS by the kernel itself: K0T is not read
-        K0 = self.layer.MLP_layer1.kernel_0
-        ver = (K0._version, K0.data_ptr())
-        if ver != self._k0_ver:
-            if st is None:
-                st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            check(lib.rec_deepfm_k0t_f32(_p(K0), self.F, _p(self._k0t), st), "rec_deepfm_k0t_f32")
-            self._k0_ver = ver
-
-    def _retranspose(self, st):
-        """after an in-stream update of the dense parameters through the C ABI (torch's version counter does not see it)"""
-        if self.F <= 26:
-            return
-        check(lib.rec_deepfm_k0t_f32(_p(self.layer.MLP_layer1.kernel_0), self.F, _p(self._k0t), st), "rec_deepfm_k0t_f32")
+        # K0^T for the fused kernel, refreshed whenever the parameter changed -- by torch or by this step's own optimizer
+        # launches (which re-transpose in the same stream)
+        self._k0t = _K0T(layer, F)
 
     def _sort(self, cols, buf, stream):
         self._sort_group([cols], buf, stream)
@@ -471,41 +476,26 @@ class DeepFMFusedStep:
                                                  _p(self._last), _p(self._step_dev), _p(self._lr_tab),
                                                  self._lr_tab.numel(), 0.9, 0.999, 1e-7, st),
                   "rec_adam_keras_catchup_f32")
-        if self.kernel_version >= 3:
-            self._ensure_k0t(st)
-            if not self.direct:
-                check(lib.rec_deepfm_fused3_main_f32(
-                    _p(emb), emb.stride(0), self.V, arr, F, self.B, _p(L.bias), _p(L.MLP_layer1.kernel_0), _p(self._k0t),
-                    _p(L.MLP_layer1.bias_0), _p(L.MLP_layer1.kernel_1), _p(L.MLP_layer1.bias_1),
-                    _p(L.MLP_layer2.kernel_0), _p(L.MLP_layer2.bias_0), _p(label), _p(self.gz), _p(self.vals),
-                    self._pprob(), _p(self.oob), _p(self.ws), st), "rec_deepfm_fused3_main_f32")
-                return
-            head = (_p(emb), emb.stride(0), self.V, arr, F, self.B, _p(L.bias), _p(L.MLP_layer1.kernel_0), _p(self._k0t),
-                    _p(L.MLP_layer1.bias_0), _p(L.MLP_layer1.kernel_1), _p(L.MLP_layer1.bias_1), _p(L.MLP_layer2.kernel_0),
-                    _p(L.MLP_layer2.bias_0), _p(label), _p(self.gz), _p(self.vals), self._pprob(), _p(self.oob), _p(self.ws),
-                    _p(pl["dloc"]), _p(pl["col_nu"]), _p(self.g_embed_rows))
-            if self._fused_lazy():
-                # the optimizer's device-side step counter advances inside this launch (the kernel reads neither word):
-                # the catch-up above saw the old step, the post launch and the dense update below see the new one
-                check(lib.rec_deepfm_fused3_main_direct_adv_f32(*head, _p(self._step_dev), _p(self._lr_tab),
-                                                                self._lr_tab.numel(), _p(self._lr_t_dev), st),
-                      "rec_deepfm_fused3_main_direct_adv_f32")
-                self._advanced = True
-            else:
-                check(lib.rec_deepfm_fused3_main_direct_f32(*head, st), "rec_deepfm_fused3_main_direct_f32")
-            return
+        self._k0t.refresh(st)
         if not self.direct:
-            check(lib.rec_deepfm_fused_main_f32(
-                _p(emb), emb.stride(0), self.V, arr, F, self.B, _p(L.bias), _p(L.MLP_layer1.kernel_0),
+            check(lib.rec_deepfm_fused3_main_f32(
+                _p(emb), emb.stride(0), self.V, arr, F, self.B, _p(L.bias), _p(L.MLP_layer1.kernel_0), _p(self._k0t.buf),
                 _p(L.MLP_layer1.bias_0), _p(L.MLP_layer1.kernel_1), _p(L.MLP_layer1.bias_1),
-                _p(L.MLP_layer2.kernel_0), _p(L.MLP_layer2.bias_0), _p(label), _p(self.gz), _p(self.vals), None,
-                _p(self.oob), _p(self.ws), st), "rec_deepfm_fused_main_f32")
+                _p(L.MLP_layer2.kernel_0), _p(L.MLP_layer2.bias_0), _p(label), _p(self.gz), _p(self.vals),
+                self._pprob(), _p(self.oob), _p(self.ws), st), "rec_deepfm_fused3_main_f32")
             return
-        check(lib.rec_deepfm_fused_main_direct_f32(
-            _p(emb), emb.stride(0), self.V, arr, F, self.B, _p(L.bias), _p(L.MLP_layer1.kernel_0),
-            _p(L.MLP_layer1.bias_0), _p(L.MLP_layer1.kernel_1), _p(L.MLP_layer1.bias_1), _p(L.MLP_layer2.kernel_0),
-            _p(L.MLP_layer2.bias_0), _p(label), _p(self.gz), _p(self.vals), None, _p(self.oob), _p(self.ws),
-            _p(pl["dloc"]), _p(pl["col_nu"]), _p(self.g_embed_rows), st), "rec_deepfm_fused_main_direct_f32")
+        head = (_p(emb), emb.stride(0), self.V, arr, F, self.B, _p(L.bias), _p(L.MLP_layer1.kernel_0), _p(self._k0t.buf),
+                _p(L.MLP_layer1.bias_0), _p(L.MLP_layer1.kernel_1), _p(L.MLP_layer1.bias_1), _p(L.MLP_layer2.kernel_0),
+                _p(L.MLP_layer2.bias_0), _p(label), _p(self.gz), _p(self.vals), self._pprob(), _p(self.oob), _p(self.ws),
+                _p(pl["dloc"]), _p(pl["col_nu"]), _p(self.g_embed_rows))
+        if self._fused_lazy():
+            # the optimizer's device-side step counter advances inside this launch (the kernel reads neither word):
+            # the catch-up above saw the old step, the post launch and the dense update below see the new one
+            check(lib.rec_deepfm_fused3_main_direct_adv_f32(*head, _p(self._step_dev), _p(self._lr_tab),
+                                                            self._lr_tab.numel(), _p(self._lr_t_dev), st),
+                  "rec_deepfm_fused3_main_direct_adv_f32")
+        else:
+            check(lib.rec_deepfm_fused3_main_direct_f32(*head, st), "rec_deepfm_fused3_main_direct_f32")
 
     def _fused_lazy(self):
         """optimizer 'lazy_adam' / 'keras_adam_lazy' in direct mode: the touched-rows update of both tables rides in the
@@ -521,10 +511,7 @@ class DeepFMFusedStep:
             params = dict(self.layer.named_parameters())
             pe = params["embed.embeddings"]
             (me, ve), (mw, vw) = self.state["embed.embeddings"], self.state["w.embeddings"]
-            if not self._advanced:                           # (the v3 fused launch has already advanced the counter)
-                check(lib.rec_adam_advance_f32(_p(self._step_dev), _p(self._lr_tab), self._lr_tab.numel(),
-                                               _p(self._lr_t_dev), st), "rec_adam_advance_f32")
-            self._advanced = False
+            # (the step counter was advanced by the fused launch in front of this one: _launch_main)
             check(lib.rec_deepfm_fused_post_direct_adam_dev_f32(
                 self.F, self.B, _p(self.gz), _p(self.vals), _p(g["MLP_layer1.kernel_0"]), _p(g["MLP_layer1.bias_0"]),
                 _p(g["MLP_layer1.kernel_1"]), _p(g["MLP_layer1.bias_1"]), _p(g["MLP_layer2.kernel_0"]),
@@ -558,14 +545,14 @@ class DeepFMFusedStep:
             k, var, m, v, g, numel = self._multi
             check(lib.rec_adam_dense_multi_f32(k, var, m, v, g, numel, _p(self._lr_t_dev), b1, b2, eps, st),
                   "rec_adam_dense_multi_f32")
-            self._retranspose(st)
+            self._k0t.refresh(st, force=True)
             return
         params = dict(self.layer.named_parameters())
         for name, grad in self.g.items():
             m, v = self.state[name]
             check(lib.rec_adam_dense_f32(_p(params[name]), _p(m), _p(v), _p(grad), grad.numel(), t, lr, b1, b2, eps, st),
                   "rec_adam_dense_f32")
-        self._retranspose(st)
+        self._k0t.refresh(st, force=True)
         n = self.B * self.F
         pe, pw = params["embed.embeddings"], params["w.embeddings"]
         if self.optimizer == "keras_adam" and _tables_share_rows(pe, pw):
@@ -700,8 +687,7 @@ class DeepFMFusedStep:
                     self._sort_group(then_cols[j:j + per], then_bufs[j], main)
 
         t_base = self.t
-        if self.kernel_version >= 3:
-            self._ensure_k0t()                                   # outside any capture: a replayed graph reads K0T
+        self._k0t.refresh()                                      # outside any capture: a replayed graph reads K0T
         if not graphed:
             enqueue_all()
         else:
@@ -935,17 +921,12 @@ class HipStepBackend:
         w = self.__dict__.get("_a_weights")
         L = st_.layer
         if w is None:                                        # parameters are updated in place: their addresses stay
-            self._k0t = torch.empty((32, st_.F * 16), dtype=torch.float32, device=st_.dev)
-            self._k0_ver = None
-            w = self._a_weights = (_p(L.bias), _p(L.MLP_layer1.kernel_0), _p(self._k0t), _p(L.MLP_layer1.bias_0),
+            self._k0t = _K0T(L, st_.F)
+            w = self._a_weights = (_p(L.bias), _p(L.MLP_layer1.kernel_0), _p(self._k0t.buf), _p(L.MLP_layer1.bias_0),
                                    _p(L.MLP_layer1.kernel_1), _p(L.MLP_layer1.bias_1), _p(L.MLP_layer2.kernel_0),
                                    _p(L.MLP_layer2.bias_0))
             self._a_tail = (_p(self.gz), _p(self.vals), None, _p(st_.oob), _p(self.ws))
-        K0 = L.MLP_layer1.kernel_0
-        ver = (K0._version, K0.data_ptr())
-        if ver != self._k0_ver and st_.F > 26:               # layer 1's kernel changed: refresh its transposed copy (only
-            check(lib.rec_deepfm_k0t_f32(_p(K0), st_.F, _p(self._k0t), self.st), "rec_deepfm_k0t_f32")   # read when K0 does
-            self._k0_ver = ver                               # not fit in LDS beside the rows)
+        self._k0t.refresh(self.st)
         check(lib.rec_deepfm_fused3_main_f32(_p(rows_local), 20, rows_local.shape[0], pl["uidx_arr"], st_.F, st_.B, *w,
                                              _p(y), *self._a_tail, self.st), "rec_deepfm_fused3_main_f32")
         return self.vals, self.gz

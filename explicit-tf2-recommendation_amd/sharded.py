@@ -222,7 +222,7 @@ class _Exchange(torch.autograd.Function):
     its backward) is a fixed program that engine.GraphedTrainStep captures in a hipGraph.
 
         plan     sorted-unique plan of the flat ids; ascending = already grouped by owner (block partition)
-        map      rec_shard_slab_map_i64: owner o's slab of the id message, every lookup's slot o*cap + rank
+        map      rec_shard_slab_map_uslot_i64: owner o's slab of the id message, every lookup's slot o*cap + rank
         C1       all-to-all of the id messages [P, 2+cap] (own communicator)          -- skipped at world size 1
                  owner-side gather of the requested rows -> [P*cap, E]
         C2       all-to-all of the rows back: row o*cap + j = the j-th id this rank asked owner o for

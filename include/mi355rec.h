@@ -181,20 +181,9 @@ int rec_bce_fwd_bwd_f32(const float* y, const float* p, int64_t n, float* loss, 
 int rec_adam_dense_f32(float* var, float* m, float* v, const float* g, int64_t n, int64_t t, float lr,
                        float b1, float b2, float eps, void* stream);
 /* Keras' bias-corrected step size lr * sqrt(1 - b2^t) / (1 - b1^t) in float32 as the entry points above compute it from
- * (t, lr, b1, b2) -- for a caller that keeps the values of steps 1..n in a device table. */
+ * (t, lr, b1, b2) -- for a caller that keeps the values of steps 1..n in a device table (beyond it the corrections are
+ * 1 in float32: b2^t < 2^-24). */
 float rec_adam_lr_t_f32(float lr, float b1, float b2, int64_t t);
-/* Device-side step counter: *step_dev += 1, *lr_t_dev = lr_table[min(*step_dev, n_table) - 1] (one tiny launch).  With it
- * a train step holds no per-step host scalar and can be captured in a hipGraph. */
-int rec_adam_advance_f32(int64_t* step_dev, const float* lr_table, int64_t n_table, float* lr_t_dev, void* stream);
-/* rec_deepfm_fused3_main_direct_f32 (below) with that advance done by the fused kernel's first thread -- the kernel reads
- * neither word, the launches behind it on the stream see the new step: one launch less per train step. */
-int rec_deepfm_fused3_main_direct_adv_f32(const float* table, int64_t ld, int64_t V, const int64_t* const* cols_host, int F,
-                                          int64_t B, const float* bias, const float* K0, const float* K0T, const float* b0,
-                                          const float* K1, const float* b1, const float* K2, const float* b2,
-                                          const float* label, float* gz, float* vals, float* prob, int* oob_flag,
-                                          void* workspace, const int32_t* dloc, const int32_t* col_nu, float* g_embed_rows,
-                                          int64_t* step_dev, const float* lr_table, int64_t n_table, float* lr_t_dev,
-                                          void* stream);
 /* rec_adam_dense_f32 on up to 16 parameters in ONE launch, step size read from device memory (host arrays of device
  * pointers, copied into the kernel arguments). */
 int rec_adam_dense_multi_f32(int n_tensors, float* const* var, float* const* m, float* const* v, const float* const* g,
@@ -266,11 +255,8 @@ int rec_colsort_shard_map_fixed_i64(const int32_t* perm, const int64_t* col_uid,
  * (uniq_ids ascending = grouped by owner under the block partition, seg_start, perm, *n_uniq on the device).
  * msg [n_shard, 2 + cap] as above (words beyond an owner's count are left alone: the caller keeps them zero);
  * slot [n] int64: row of every lookup in the [n_shard * cap, E] buffer the rows come back in.  *oob_flag is set when an
- * owner's unique ids exceed cap or an id lies outside [0, n_shard * rows_per_shard). */
-int rec_shard_slab_map_i64(const int64_t* uniq_ids, const int64_t* n_uniq, const int32_t* seg_start, const int32_t* perm,
-                           int64_t n, int64_t rows_per_shard, int n_shard, int64_t cap, int64_t* msg, int64_t* slot,
-                           int* oob_flag, void* stream);
-/* The same, and uslot [n] int64: the slot of every UNIQUE id (rank u of the plan -> owner * cap + j; ranks >= *n_uniq ->
+ * owner's unique ids exceed cap or an id lies outside [0, n_shard * rows_per_shard).
+ * uslot [n] int64: the slot of every UNIQUE id (rank u of the plan -> owner * cap + j; ranks >= *n_uniq ->
  * n_shard * cap, one row past the buffer).  The plan of the ids is then also the plan of the slots (slot is monotone in the
  * id), which is what lets the backward of the lookup reuse the forward's de-duplication: segment sums in the plan's order,
  * scattered by uslot, are the dense gradient of the [n_shard * cap, E] rows buffer. */
@@ -300,45 +286,20 @@ int rec_permute_rows_f32(const float* in, const int64_t* perm, int64_t n, int E,
                          void* stream);
 
 /* ---- Fused DeepFM train step (2.FM/CustomLayers.py:279-308 under 2.FM/ModelManager.py:171-177) for the reference's
- * default head (embedding_dims 16, mlp_dims [32,8]) on the fused 128-byte row layout (ld = 32): index assembly from the
- * F feature columns, gather, FM, MLP (fp32 MFMA), sigmoid, Keras BCE and the whole backward in ONE kernel + one
- * fixed-order reduction.  Outputs: gz [B] = dL/dz, vals [B*F,16] = IndexedSlices values of `embed` (the values of `w`
- * are gz[b]), dense gradients, loss (device scalar, mean BCE), prob [B] (optional).  F <= 28.
- * workspace: rec_deepfm_fused_workspace_bytes(B, F). */
+ * default head (embedding_dims 16, mlp_dims [32,8]) on the fused 128-byte row layout: a de-duplication plan of the
+ * batch's ids, then two launches on the stream -- the main kernel (index assembly from the F feature columns, gather,
+ * FM, MLP on fp32 MFMA, sigmoid, Keras BCE and the whole backward) and the post launch (fixed-order reduction of the
+ * main kernel's per-workgroup partials side by side with the segment sums of the de-duplicated table gradients).
+ * Outputs: gz [B] = dL/dz, vals [B*F,16] = IndexedSlices values of `embed` (the values of `w` are gz[b]), dense
+ * gradients, loss (device scalar, mean BCE), prob [B] (optional), per-unique-id gradient rows.  F <= 28.
+ * workspace (main kernel -> post launch): rec_deepfm_fused_workspace_bytes(B, F). */
 size_t rec_deepfm_fused_workspace_bytes(int64_t B, int F);
-int rec_deepfm_fused_fwd_bwd_f32(const float* table, int64_t ld, int64_t V, const int64_t* const* cols_host, int F,
-                                 int64_t B, const float* bias, const float* K0, const float* b0, const float* K1,
-                                 const float* b1, const float* K2, const float* b2, const float* label, float* gz,
-                                 float* vals, float* prob, float* dK0, float* db0, float* dK1, float* db1, float* dK2,
-                                 float* db2, float* dbias, float* loss, int* oob_flag, void* workspace, void* stream);
-/* The same iteration when the de-duplication plan of the batch (rec_colsort_plan_i64) already exists: the fused kernel,
- * then ONE launch in which the reduction of the workgroup partials and the segment sums of rec_colseg_sum_f32 (packed:
- * of rec_colseg_sum_packed_f32, g_embed_rows [B*F,20], g_w_rows unused) run side by side. */
-int rec_deepfm_fused_step_f32(const float* table, int64_t ld, int64_t V, const int64_t* const* cols_host, int F,
-                              int64_t B, const float* bias, const float* K0, const float* b0, const float* K1,
-                              const float* b1, const float* K2, const float* b2, const float* label, float* gz,
-                              float* vals, float* prob, float* dK0, float* db0, float* dK1, float* db1, float* dK2,
-                              float* db2, float* dbias, float* loss, int* oob_flag, void* workspace,
-                              const int32_t* perm, const int64_t* col_uid, const int32_t* col_seg,
-                              const int32_t* col_nu, int64_t* uniq_ids, float* g_embed_rows, float* g_w_rows,
-                              int64_t* n_uniq, int packed, void* stream);
-/* The two halves of rec_deepfm_fused_step_f32 as separate calls (fused kernel | reduction + segment sums): a caller
- * that builds the plan on another stream puts its wait between them, so that only the second half depends on it.
- * These plan-after forms take any row stride ld >= 20 that is a multiple of 4 (rows [embed 16 | w | ...]: 32 for a
- * table, 20 for the rows a sharded step received); the direct-mode form below needs ld = 32. */
-int rec_deepfm_fused_main_f32(const float* table, int64_t ld, int64_t V, const int64_t* const* cols_host, int F,
-                              int64_t B, const float* bias, const float* K0, const float* b0, const float* K1,
-                              const float* b1, const float* K2, const float* b2, const float* label, float* gz,
-                              float* vals, float* prob, int* oob_flag, void* workspace, void* stream);
-int rec_deepfm_fused_post_f32(int F, int64_t B, const float* gz, const float* vals, float* dK0, float* db0, float* dK1,
-                              float* db1, float* dK2, float* db2, float* dbias, float* loss, void* workspace,
-                              const int32_t* perm, const int64_t* col_uid, const int32_t* col_seg,
-                              const int32_t* col_nu, int64_t* uniq_ids, float* g_embed_rows, float* g_w_rows,
-                              int64_t* n_uniq, int packed, void* stream);
-/* De-duplication plan that uses the DataGenerator contract (2.FM/DataGenerator.py:76-88): column f only holds ids of
+
+/* Plan.  Uses the DataGenerator contract (2.FM/DataGenerator.py:76-88): column f only holds ids of
  * [col_lo[f], col_lo[f] + 2^key_bits) and columns are given in ascending range order, so duplicates occur only inside
  * a column and each column (B <= 16384 ids; max_key = largest id - col_lo over all columns, bits(max_key) +
- * ceil(log2 B) <= 32) is sorted on its own (chunk sort + rank merge + run detection).
+ * ceil(log2 B) <= 32) is sorted on its own (one workgroup per column: LDS radix sort + run detection; up to 256 columns
+ * per call, so one call may plan several batches).
  * perm [F,B], col_uid [F,B], col_seg [F,B+1], col_nu [F]; an id outside its column's range sets *bad_flag. */
 size_t rec_colsort_workspace_bytes(int64_t B, int F);
 int rec_colsort_plan_i64(const int64_t* const* cols_host, int F, int64_t B, int64_t V, const int64_t* col_lo,
@@ -351,53 +312,64 @@ int rec_colsort_plan_i64(const int64_t* const* cols_host, int F, int64_t B, int6
 int rec_colsort_plan_dest_i64(const int64_t* const* cols_host, int F, int64_t B, int64_t V, const int64_t* col_lo,
                               int64_t max_key, int32_t* perm, int64_t* col_uid, int32_t* col_seg, int32_t* col_nu,
                               int32_t* dloc, int* bad_flag, void* workspace, void* stream);
-/* Direct mode of the fused step: the plan of the batch (rec_colsort_plan_dest_i64) is complete before the launch.
- * rec_deepfm_fused_main_direct_f32 = rec_deepfm_fused_main_f32, except that the IndexedSlices value row of a lookup that
- * heads its run goes straight to g_embed_rows[slot] (only the other members of a run are written to vals);
- * rec_deepfm_fused_post_direct_f32 then adds the remaining members of runs longer than one in position order (sums
- * bit-identical to the plain path), writes uniq_ids / g_w_rows / n_uniq and the zero-padded tail, and reduces the dense
- * partials.  Replaces the 2.FM/ModelManager.py:176-179 IndexedSlices hand-over like the plain pair of calls does. */
-int rec_deepfm_fused_main_direct_f32(const float* table, int64_t ld, int64_t V, const int64_t* const* cols_host, int F,
-                                     int64_t B, const float* bias, const float* K0, const float* b0, const float* K1,
-                                     const float* b1, const float* K2, const float* b2, const float* label, float* gz,
-                                     float* vals, float* prob, int* oob_flag, void* workspace, const int32_t* dloc,
-                                     const int32_t* col_nu, float* g_embed_rows, void* stream);
-int rec_deepfm_fused_post_direct_f32(int F, int64_t B, const float* gz, const float* vals, float* dK0, float* db0,
-                                     float* dK1, float* db1, float* dK2, float* db2, float* dbias, float* loss,
-                                     void* workspace, const int32_t* perm, const int64_t* col_uid, const int32_t* col_seg,
-                                     const int32_t* col_nu, int64_t* uniq_ids, float* g_embed_rows, float* g_w_rows,
-                                     int64_t* n_uniq, void* stream);
-/* Third form of the fused forward+backward kernel (csrc/deepfm_fused3.hip): same inputs, outputs and workspace layout as
- * rec_deepfm_fused_main_f32 / rec_deepfm_fused_main_direct_f32 -- the post launches above finish the step -- on a schedule
- * in which the two 16-example halves of a workgroup run one phase apart (the backward of one half on the matrix cores
- * while the rows of the other are still landing).  K0T [32, F*16] = the transpose of K0 [F*16, 32], kept by the caller
- * with rec_deepfm_k0t_f32 (layer 1 then reads its K0 operand as 16-byte pieces). */
+
+/* Main kernel (csrc/deepfm_fused3.hip): the two 16-example halves of a workgroup run one phase apart (the backward of
+ * one half on the matrix cores while the rows of the other are still landing).  K0T [32, F*16] = the transpose of
+ * K0 [F*16, 32], kept by the caller with rec_deepfm_k0t_f32 (read only when F > 26: otherwise K0 is staged in LDS).
+ * rec_deepfm_fused3_main_f32 (plan-after form) takes any row stride ld >= 20 that is a multiple of 4 (rows
+ * [embed 16 | w | ...]: 32 for a table, 20 for the rows a sharded step received); the plan may be built after it. */
 int rec_deepfm_k0t_f32(const float* K0, int F, float* K0T, void* stream);
 int rec_deepfm_fused3_main_f32(const float* table, int64_t ld, int64_t V, const int64_t* const* cols_host, int F,
                                int64_t B, const float* bias, const float* K0, const float* K0T, const float* b0,
                                const float* K1, const float* b1, const float* K2, const float* b2, const float* label,
                                float* gz, float* vals, float* prob, int* oob_flag, void* workspace, void* stream);
+/* Direct mode (ld = 32): the plan of the batch (rec_colsort_plan_dest_i64) is complete before the launch, and the
+ * IndexedSlices value row of a lookup that heads its run goes straight to g_embed_rows[slot] (only the other members of
+ * a run are written to vals). */
 int rec_deepfm_fused3_main_direct_f32(const float* table, int64_t ld, int64_t V, const int64_t* const* cols_host, int F,
                                       int64_t B, const float* bias, const float* K0, const float* K0T, const float* b0,
                                       const float* K1, const float* b1, const float* K2, const float* b2,
                                       const float* label, float* gz, float* vals, float* prob, int* oob_flag,
                                       void* workspace, const int32_t* dloc, const int32_t* col_nu, float* g_embed_rows,
                                       void* stream);
-/* rec_deepfm_fused_post_direct_f32 + the lazy (touched-rows) Adam update of both tables applied to each row the moment its
- * gradient is final (optimizer in the backward; arithmetic of rec_adam_rows_f32; NOT Keras' dense-sweep
- * semantics of 2.FM/ModelManager.py:104,178-179 -- opt-in).  table: fused rows [V,32] = [embed 16 | w | pad] (ld = 32);
- * m_e, v_e [V,16]; m_w, v_w [V]; t: 1-based step. */
-int rec_deepfm_fused_post_direct_adam_f32(int F, int64_t B, const float* gz, const float* vals, float* dK0, float* db0,
-                                          float* dK1, float* db1, float* dK2, float* db2, float* dbias, float* loss,
-                                          void* workspace, const int32_t* perm, const int64_t* col_uid,
-                                          const int32_t* col_seg, const int32_t* col_nu, int64_t* uniq_ids,
-                                          float* g_embed_rows, float* g_w_rows, int64_t* n_uniq, float* table, int64_t ld,
-                                          int64_t V, float* m_e, float* v_e, float* m_w, float* v_w, int64_t t, float lr,
-                                          float b1, float b2, float eps, void* stream);
-/* ... the same with the step size read from device memory (rec_adam_advance_f32 on the same stream) and explicit row
- * strides of the optimizer state: ld_state (floats) for m_e / v_e, ld_wstate for m_w / v_w -- 16 and 1 for dense arrays,
- * 32 and 32 for state packed beside the rows ([m 16 | v 16] as one 128-byte row, m_w / v_w in the padding of the fused
- * table row: a touched row then costs two line requests instead of five or six). */
+/* ... and the optimizer's device-side step counter advanced by the kernel's first thread: *step_dev += 1,
+ * *lr_t_dev = lr_table[min(*step_dev, n_table) - 1] (lr_table: rec_adam_lr_t_f32 of steps 1..n_table).  The kernel
+ * reads neither word; the launches behind it on the stream see the new step, so a train step holds no per-step host
+ * scalar and can be captured in a hipGraph. */
+int rec_deepfm_fused3_main_direct_adv_f32(const float* table, int64_t ld, int64_t V, const int64_t* const* cols_host, int F,
+                                          int64_t B, const float* bias, const float* K0, const float* K0T, const float* b0,
+                                          const float* K1, const float* b1, const float* K2, const float* b2,
+                                          const float* label, float* gz, float* vals, float* prob, int* oob_flag,
+                                          void* workspace, const int32_t* dloc, const int32_t* col_nu, float* g_embed_rows,
+                                          int64_t* step_dev, const float* lr_table, int64_t n_table, float* lr_t_dev,
+                                          void* stream);
+
+/* Post launch (csrc/deepfm_fused.hip), after the plan-after main kernel: reduction of the workgroup partials into the
+ * dense gradients and loss, and the segment sums of (vals, gz) over the plan, compacted to the global ascending list:
+ * uniq_ids [B*F], g_embed_rows [B*F,16], g_w_rows [B*F], n_uniq; the tail is padded like rec_dedup_plan_i64's.
+ * packed: g_embed_rows [B*F,20] holds rows [embed 16 | w | 0 0 0], g_w_rows unused.  (The sharded step's form with
+ * fixed-capacity slots, rec_deepfm_fused_post_slots_f32, is declared with the exchange above.) */
+int rec_deepfm_fused_post_f32(int F, int64_t B, const float* gz, const float* vals, float* dK0, float* db0, float* dK1,
+                              float* db1, float* dK2, float* db2, float* dbias, float* loss, void* workspace,
+                              const int32_t* perm, const int64_t* col_uid, const int32_t* col_seg,
+                              const int32_t* col_nu, int64_t* uniq_ids, float* g_embed_rows, float* g_w_rows,
+                              int64_t* n_uniq, int packed, void* stream);
+/* Direct mode, after rec_deepfm_fused3_main_direct{,_adv}_f32: adds the remaining members of runs longer than one in
+ * position order (sums bit-identical to the plain path), writes uniq_ids / g_w_rows / n_uniq and the zero-padded tail,
+ * and reduces the dense partials.  Replaces the 2.FM/ModelManager.py:176-179 IndexedSlices hand-over. */
+int rec_deepfm_fused_post_direct_f32(int F, int64_t B, const float* gz, const float* vals, float* dK0, float* db0,
+                                     float* dK1, float* db1, float* dK2, float* db2, float* dbias, float* loss,
+                                     void* workspace, const int32_t* perm, const int64_t* col_uid, const int32_t* col_seg,
+                                     const int32_t* col_nu, int64_t* uniq_ids, float* g_embed_rows, float* g_w_rows,
+                                     int64_t* n_uniq, void* stream);
+/* ... + the lazy (touched-rows) Adam update of both tables applied to each row the moment its gradient is final
+ * (optimizer in the backward; arithmetic of rec_adam_rows_f32).  table: fused rows [V,32] =
+ * [embed 16 | w | pad] (ld = 32).  The step size is read from device memory (lr_t_dev, advanced by
+ * rec_deepfm_fused3_main_direct_adv_f32 on the same stream).  Explicit row strides of the optimizer state: ld_state
+ * (floats) for m_e / v_e, ld_wstate for m_w / v_w -- 16 and 1 for dense arrays, 32 and 32 for state packed beside the
+ * rows ([m 16 | v 16] as one 128-byte row, m_w / v_w in the padding of the fused table row: a touched row then costs two
+ * line requests instead of five or six).  last == NULL: plain touched-rows Adam, NOT Keras' dense-sweep semantics of
+ * 2.FM/ModelManager.py:104,178-179 (opt-in); last != NULL: the exact lazy evaluation of Keras' Adam below. */
 int rec_deepfm_fused_post_direct_adam_dev_f32(int F, int64_t B, const float* gz, const float* vals, float* dK0, float* db0,
                                               float* dK1, float* db1, float* dK2, float* db2, float* dbias, float* loss,
                                               void* workspace, const int32_t* perm, const int64_t* col_uid,
@@ -421,17 +393,6 @@ int rec_adam_keras_catchup_f32(const int64_t* col_uid, const int32_t* col_nu, in
 int rec_adam_keras_flush_f32(float* table, int64_t ld, int64_t V, float* m_e, float* v_e, int64_t ld_state, float* m_w,
                              float* v_w, int64_t ld_wstate, int32_t* last, const int64_t* step_dev, const float* lr_table,
                              int64_t n_table, float b1, float b2, float eps, void* stream);
-/* segment sums of vals [B*F,16] (embed) and gz [B] (w) over that plan + compaction to the global ascending list:
- * uniq_ids [B*F], g_embed_rows [B*F,16], g_w_rows [B*F], n_uniq; the tail is padded like rec_dedup_plan_i64's. */
-int rec_colseg_sum_f32(const float* vals, const float* gz, const int32_t* perm, const int64_t* col_uid,
-                       const int32_t* col_seg, const int32_t* col_nu, int64_t B, int F, int64_t* uniq_ids,
-                       float* g_embed_rows, float* g_w_rows, int64_t* n_uniq, void* stream);
-
-/* Same sums written as rows of 20 floats [embed 16 | w | 0 0 0] (g_rows [B*F,20]): ONE buffer to send to the shard
- * owners in the row-sharded step. */
-int rec_colseg_sum_packed_f32(const float* vals, const float* gz, const int32_t* perm, const int64_t* col_uid,
-                              const int32_t* col_seg, const int32_t* col_nu, int64_t B, int F, int64_t* uniq_ids,
-                              float* g_rows, int64_t* n_uniq, void* stream);
 
 /* ---- K8/K9  DIN ActivationUnit + masked sum pooling (5.DIN/CustomLayers.py:163-180, 256-282), factorised:
  *   pre[b,t,:] = c_b + k_t . Eff_b,  Eff_b = (W_k - W_d) + M_b,  M_b[i,o] = sum_j q_j W_o[i,j,o],

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """B sweep of the two gather-bound kernels of the headline path ("sweep B to 64 k to show the
 asymptote"): rec_emb_fm_fwd_f32 (gather + FM forward) and the fused forward+backward kernel (plan-after form, which has
-no batch limit), B = 8k .. 128k, fresh ids every launch, V = 10M x 16d fused rows.
+no batch limit: rec_deepfm_fused3_main_f32), B = 8k .. 128k, fresh ids every launch, V = 10M x 16d fused rows.
+profiles/r03_b_sweep.json was measured with the round-2 fused kernel, since removed (git show a002c2f:scripts/exp/b_sweep.py).
     python scripts/exp/b_sweep.py > gpurun_out/b_sweep.json
 """
 import ctypes as C
@@ -26,6 +27,9 @@ vp = lambda t: C.c_void_p(t.data_ptr())
 dims = [V // F] * F
 dims[-1] += V - sum(dims)
 offs = np.concatenate([[0], np.cumsum(dims[:-1])])
+K0T = torch.empty((32, F * 16), dtype=torch.float32, device="cuda")    # K0^T: the kernel reads it only when F > 26
+check(lib.rec_deepfm_k0t_f32(vp(L.MLP_layer1.kernel_0), F, vp(K0T), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+      "k0t")
 
 
 def timed(launch, reps):
@@ -70,11 +74,11 @@ for B in (8192, 16384, 32768, 65536, 131072):
     def l_fused(n):
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         for i in range(n):
-            check(lib.rec_deepfm_fused_main_f32(vp(emb), emb.stride(0), V, arrs[i % nset], F, B, vp(L.bias),
-                                                vp(L.MLP_layer1.kernel_0), vp(L.MLP_layer1.bias_0),
-                                                vp(L.MLP_layer1.kernel_1), vp(L.MLP_layer1.bias_1),
-                                                vp(L.MLP_layer2.kernel_0), vp(L.MLP_layer2.bias_0), vp(y), vp(gz),
-                                                vp(vals), None, vp(oob), vp(ws), st), "fused")
+            check(lib.rec_deepfm_fused3_main_f32(vp(emb), emb.stride(0), V, arrs[i % nset], F, B, vp(L.bias),
+                                                 vp(L.MLP_layer1.kernel_0), vp(K0T), vp(L.MLP_layer1.bias_0),
+                                                 vp(L.MLP_layer1.kernel_1), vp(L.MLP_layer1.bias_1),
+                                                 vp(L.MLP_layer2.kernel_0), vp(L.MLP_layer2.bias_0), vp(y), vp(gz),
+                                                 vp(vals), None, vp(oob), vp(ws), st), "fused")
 
     reps = 2 * nset
     ug, uf = timed(l_gather, reps), timed(l_fused, reps)

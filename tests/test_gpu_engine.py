@@ -143,7 +143,7 @@ def test_deepfm_train_steps_with_adam(opt):
 
 
 # ------------------------------------------------------------------------------------------------
-# the 4-launch fused step (csrc/deepfm_fused.hip)
+# the fused step (plan: csrc/colsort.hip, main kernel: csrc/deepfm_fused3.hip, post launch: csrc/deepfm_fused.hip)
 # ------------------------------------------------------------------------------------------------
 def make16(B, F, V, seed, dist):
     from explicit_tf2_recommendation_amd import layers, data

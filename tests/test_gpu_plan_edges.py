@@ -1,5 +1,5 @@
 """GPU tests of DeepFMFusedStep on batches whose de-duplication plans are built to reach every branch of the plan sort
-(colsort_onewg_kernel) and of the post launch (deepfm_post_direct_kernel, csrc/deepfm_fused.hip):
+(colsort_onewg_kernel, csrc/colsort.hip) and of the post launch (deepfm_post_direct_kernel, csrc/deepfm_fused.hip):
 
     run of 1 or 2 members          fast path (one lane, fix_deal mapping)
     3 .. FIX_SHORT=17              four lanes per run (skewed columns)
