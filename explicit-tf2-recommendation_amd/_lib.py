@@ -86,6 +86,11 @@ SIGNATURES = {
     "rec_deepfm_fused3_main_f32": (i32, [p, i64, i64, p, i32, i64] + [p] * 14 + [p]),
     "rec_deepfm_fused3_main_direct_f32": (i32, [p, i64, i64, p, i32, i64] + [p] * 14 + [p, p, p] + [p]),
     "rec_deepfm_fused3_main_direct_adv_f32": (i32, [p, i64, i64, p, i32, i64] + [p] * 14 + [p, p, p] + [p, p, i64, p] + [p]),
+    "rec_dssm_fused_workspace_bytes": (sz, [i64, i32, i32, i32]),
+    "rec_dssm_fused_main_f32": (i32, [p, i64, i64, p, i32, p, i64, i64, p, i32, i32, i32, i32, i32, i64, p, p, p, p, p, p,
+                                      p, p, p, sz, p, p, i64, p, p]),
+    "rec_dssm_fused_post_f32": (i32, [i64, i32, i32, i32, p, sz, p, p, p, p, p, p, p, p, p, p, p, p, p, p, p, i64, i64,
+                                      i64, i64, p, f32, f32, f32, p]),
     "rec_din_prepare_f32": (i32, [p, p, i32, i32, p, p, p, p]),
     "rec_din_prepare_bwd_f32": (i32, [p, p, i32, i32, p, p]),
     "rec_din_attn_fwd_f32": (i32, [p, i64, i64, i32, i32, p, i64, i32, p, p, i32, i32, p, p, p, p, p, i64, i32, p, p, p,

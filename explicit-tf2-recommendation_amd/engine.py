@@ -758,6 +758,303 @@ class DeepFMFusedStep:
         return out
 
 
+class DSSMFusedStep:
+    """train_loop iteration of DSSMTwoTowerRetrievalLayer (2.FM/CustomLayers.py:208-239 under 2.FM/ModelManager.py:
+    171-177) in two launches on the main stream: the fused kernel (csrc/dssm_fused.hip: gather, both tower MLPs, score,
+    Keras BCE and the whole backward) and the post launch (fixed-order reduction of its partials side by side with the
+    segment sums of both towers' gradient rows).  The de-duplication plans (rec_dedup_plan_i64 of each tower's flat
+    [B*F] ids) of the batches announced for the next call are built behind the steps of this call.  Graph policy, plan
+    prefetch and method names are those of DeepFMFusedStep.
+
+    Requirements (checked; otherwise keep GraphedTrainStep, raises NotImplementedError): plain (unsharded) tables with
+    the same embedding_dims E in {8, 16, 32, 64} in both towers, mlp_dims [64, 32], final_dim 8, 1 <= F <= 8 features
+    per tower.  optimizer: None (gradients only) or 'lazy_adam' (touched rows of both tables + Adam on the dense
+    parameters, step size on the device, so it is captured with the step; NOT the reference's dense-sweep semantics).
+    """
+
+    NBUF = 64           # plan buffers: two halves of 32, many() alternates between them
+    MAX_GRAPHS = 64     # captured hipGraphs kept (least recently used beyond that are dropped with the inputs they hold)
+    DENSE = ("mlp.kernel_0", "mlp.bias_0", "mlp.kernel_1", "mlp.bias_1", "final.kernel_0", "final.bias_0")
+
+    def __init__(self, layer, batch_size, optimizer=None, lr=1e-3, use_graph=True, want_outputs=False):
+        from . import layers as CL
+        if not isinstance(layer, CL.DSSMTwoTowerRetrievalLayer):
+            raise NotImplementedError("DSSMFusedStep covers layers.DSSMTwoTowerRetrievalLayer only")
+        if optimizer == "keras_adam":
+            raise ValueError("optimizer 'keras_adam' is Keras' dense sweep: every row of both tables moves every step "
+                             "(25.6 GB read and written per step at 100M x 64d); use 'lazy_adam' (touched rows) or "
+                             "optimizer=None with an optimizer of your own")
+        if optimizer not in (None, "lazy_adam"):
+            raise ValueError("optimizer must be None or 'lazy_adam', not %r" % (optimizer,))
+        self.layer = layer
+        self.towers = (layer.u_tower, layer.i_tower)
+        self.B = B = int(batch_size)
+        if B < 1:
+            raise ValueError("batch_size must be >= 1")
+        Es = []
+        for tw in self.towers:
+            if not isinstance(tw.embed, CL.Embedding):
+                raise NotImplementedError("the fused DSSM step needs plain (unsharded) Embedding tables")
+            if list(tw.mlp.units) != [64, 32] or list(tw.final.units) != [8]:
+                raise NotImplementedError("the fused DSSM step covers mlp_dims=[64,32] and final_dim=8 only")
+            if tw.mlp.activation != "relu" or tw.final.activation is not None or not tw.mlp.use_bias \
+                    or not tw.final.use_bias or tw.mlp.is_batch_norm or tw.final.is_batch_norm:
+                raise NotImplementedError("the fused DSSM step covers the reference's towers (relu MLP with biases)")
+            if not 1 <= len(tw.feature_names) <= 8:
+                raise NotImplementedError("the fused DSSM step covers 1 to 8 features per tower")
+            Es.append(tw.embed.embeddings.shape[1])
+        if Es[0] != Es[1]:
+            raise NotImplementedError("the fused DSSM step needs the same embedding_dims in both towers")
+        self.E = E = Es[0]
+        if E not in (8, 16, 32, 64):
+            raise NotImplementedError("the fused DSSM step covers embedding_dims in {8, 16, 32, 64}")
+        self.F = tuple(len(tw.feature_names) for tw in self.towers)
+        self.V = tuple(tw.embed.embeddings.shape[0] for tw in self.towers)
+        for tw, V in zip(self.towers, self.V):
+            t = tw.embed.embeddings
+            if not t.is_cuda or t.dtype != torch.float32 or t.stride(1) != 1 or t.stride(0) % 4 or t.data_ptr() % 16:
+                raise NotImplementedError("tables must be float32 CUDA arrays with 16-byte aligned rows")
+            if V > (1 << 32):
+                raise NotImplementedError("the de-duplication plan sorts 32-bit ids: at most 2^32 rows per table")
+        self.dev = dev = layer.u_tower.embed.embeddings.device
+        self.optimizer, self.lr, self.use_graph, self.t = optimizer, lr, use_graph, 0
+        f32 = dict(dtype=torch.float32, device=dev)
+        Fu, Fi = self.F
+        nu, ni = B * Fu, B * Fi
+        self.vals = (torch.empty((nu, E), **f32), torch.empty((ni, E), **f32))
+        self.rows = (torch.empty((nu, E), **f32), torch.empty((ni, E), **f32))
+        self.loss_steps = torch.zeros(self.NBUF // 2, **f32)
+        self.loss = self.loss_steps[0]
+        self.outputs = None
+        if want_outputs:
+            self.outputs = {"user_embedding": torch.zeros((B, 8), **f32), "item_embedding": torch.zeros((B, 8), **f32),
+                            "score": torch.zeros(B, **f32)}
+        self._row = 0
+        self.oob = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.names = ["u_tower." + n for n in self.DENSE] + ["i_tower." + n for n in self.DENSE]
+        params = dict(layer.named_parameters())
+        self.g = {n: torch.empty(params[n].shape, **f32) for n in self.names}
+        self._g_arr = (C.c_void_p * 12)(*[self.g[n].data_ptr() for n in self.names])
+        self.ws_bytes = lib.rec_dssm_fused_workspace_bytes(B, E, Fu, Fi)
+        if self.ws_bytes == 0:
+            raise NotImplementedError("rec_dssm_fused_workspace_bytes: unsupported shape")
+        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
+        # NBUF plan buffers per tower: packed ids [B*F], uniq_ids, seg_start, perm, n_uniq (rec_dedup_plan_i64).  The plan
+        # depends on the ids only, so the plans of the NEXT call's batches are built behind the steps of this call (two
+        # halves of NBUF / 2 used alternately: one is read by this call's steps while the other is filled)
+        NB = self.NBUF
+        self.plans = []
+        for n in (nu, ni):
+            self.plans.append(dict(ids=torch.empty((NB, n), dtype=torch.int64, device=dev),
+                                   uniq=torch.empty((NB, n), dtype=torch.int64, device=dev),
+                                   seg=torch.empty((NB, n + 1), dtype=torch.int32, device=dev),
+                                   perm=torch.empty((NB, n), dtype=torch.int32, device=dev),
+                                   nu=torch.zeros((NB, 1), dtype=torch.int64, device=dev)))
+        self.dedup_ws_bytes = lib.rec_dedup_workspace_bytes(max(nu, ni))
+        self.dedup_ws = torch.empty(self.dedup_ws_bytes, dtype=torch.uint8, device=dev)
+        self._last_buf = 0
+        self._prefetched, self._half = {}, 0
+        self._col_cache = {}
+        if optimizer is not None:
+            self.state = {name: (torch.zeros(p.shape, **f32), torch.zeros(p.shape, **f32))
+                          for name, p in params.items()}
+            N = 32768
+            tab = [lib.rec_adam_lr_t_f32(lr, 0.9, 0.999, t) for t in range(1, N + 1)]
+            self._lr_tab = torch.tensor(tab, **f32)
+            self._step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
+            self._lr_t_dev = torch.zeros(1, **f32)
+        import collections
+        self._graphs = collections.OrderedDict()            # gkey -> (graph, inputs kept alive), LRU order
+        self._seen = collections.OrderedDict()              # gkeys enqueued eagerly once (addresses only)
+
+    # ---- plans
+    def _plan(self, cols_uv, buf, st):
+        """rec_index_pack_i64 + rec_dedup_plan_i64 of both towers' ids into plan buffer ``buf``."""
+        for t, cols in enumerate(cols_uv):
+            F, pl = self.F[t], self.plans[t]
+            n = self.B * F
+            arr = (C.c_void_p * F)(*[c.data_ptr() for c in cols])
+            ids = pl["ids"][buf]
+            check(lib.rec_index_pack_i64(arr, F, self.B, _p(ids), F, 0, st), "rec_index_pack_i64")
+            check(lib.rec_dedup_plan_i64(_p(ids), n, self.V[t], _p(pl["uniq"][buf]), _p(pl["seg"][buf]),
+                                         _p(pl["perm"][buf]), _p(pl["nu"][buf]), _p(self.dedup_ws), self.dedup_ws_bytes,
+                                         st), "rec_dedup_plan_i64")
+
+    # ---- the two launches
+    def _launch_main(self, y, buf, st):
+        params = dict(self.layer.named_parameters())
+        w = (C.c_void_p * 12)(*[params[n].data_ptr() for n in self.names])
+        (tu, ti) = (tw.embed.embeddings for tw in self.towers)
+        o = self.outputs
+        adv = (_p(self._step_dev), _p(self._lr_tab), self._lr_tab.numel(), _p(self._lr_t_dev)) \
+            if self.optimizer is not None else (None, None, 0, None)
+        check(lib.rec_dssm_fused_main_f32(
+            _p(tu), tu.stride(0), self.V[0], _p(self.plans[0]["ids"][buf]), self.F[0],
+            _p(ti), ti.stride(0), self.V[1], _p(self.plans[1]["ids"][buf]), self.F[1],
+            self.E, 64, 32, 8, self.B, w, _p(y), _p(self.vals[0]), _p(self.vals[1]),
+            _p(o["user_embedding"]) if o else None, _p(o["item_embedding"]) if o else None, _p(o["score"]) if o else None,
+            _p(self.oob), _p(self.ws), self.ws_bytes, *adv, st), "rec_dssm_fused_main_f32")
+
+    def _launch_post(self, buf, st):
+        pu, pi = self.plans
+        adam, lr_t = None, None
+        (tu, ti) = (tw.embed.embeddings for tw in self.towers)
+        if self.optimizer is not None:
+            (mu, vu), (mi, vi) = self.state["u_tower.embed.embeddings"], self.state["i_tower.embed.embeddings"]
+            adam = (C.c_void_p * 6)(*[x.data_ptr() for x in (tu, mu, vu, ti, mi, vi)])
+            lr_t = _p(self._lr_t_dev)
+        check(lib.rec_dssm_fused_post_f32(
+            self.B, self.E, self.F[0], self.F[1], _p(self.ws), self.ws_bytes, self._g_arr,
+            C.c_void_p(self.loss_steps.data_ptr() + 4 * self._row),
+            _p(self.vals[0]), _p(pu["perm"][buf]), _p(pu["seg"][buf]), _p(pu["uniq"][buf]), _p(pu["nu"][buf]),
+            _p(self.rows[0]),
+            _p(self.vals[1]), _p(pi["perm"][buf]), _p(pi["seg"][buf]), _p(pi["uniq"][buf]), _p(pi["nu"][buf]),
+            _p(self.rows[1]),
+            adam, tu.stride(0), self.V[0], ti.stride(0), self.V[1], lr_t, 0.9, 0.999, 1e-7, st), "rec_dssm_fused_post_f32")
+        if self.optimizer is not None:
+            params = dict(self.layer.named_parameters())
+            k = len(self.names)
+            arr = lambda xs: (C.c_void_p * k)(*[x.data_ptr() for x in xs])  # noqa: E731
+            check(lib.rec_adam_dense_multi_f32(
+                k, arr([params[n] for n in self.names]), arr([self.state[n][0] for n in self.names]),
+                arr([self.state[n][1] for n in self.names]), self._g_arr,
+                (C.c_int64 * k)(*[self.g[n].numel() for n in self.names]), _p(self._lr_t_dev), 0.9, 0.999, 1e-7, st),
+                "rec_adam_dense_multi_f32")
+
+    # ---- inputs
+    def _cols(self, inputs):
+        out = []
+        for tw in self.towers:
+            cols = []
+            for name in tw.feature_names:
+                c = inputs[name]
+                if c.dtype != torch.int64 or not c.is_cuda or c.numel() != self.B or not c.is_contiguous():
+                    raise ValueError("feature %r must be a contiguous int64 CUDA tensor with %d ids" % (name, self.B))
+                cols.append(c)
+            out.append(cols)
+        return out
+
+    def _cols_key(self, inputs):
+        ent = self._col_cache.get(id(inputs))
+        names = [n for tw in self.towers for n in tw.feature_names]
+        if ent is not None and ent[2] is inputs and tuple(id(inputs[n]) for n in names) == ent[3]:
+            return ent[0], ent[1]
+        cols = self._cols(inputs)
+        if len(self._col_cache) > 256:
+            self._col_cache.clear()
+        key = tuple(c.data_ptr() for cs in cols for c in cs)
+        self._col_cache[id(inputs)] = (cols, key, inputs, tuple(id(c) for cs in cols for c in cs))
+        return cols, key
+
+    def __call__(self, inputs, label_name="label", next_inputs=None):
+        """One train_loop iteration on `inputs`; ``next_inputs`` (optional): the batch of the NEXT call, whose plans are
+        built behind this call's step."""
+        return self.many([inputs], label_name, then=next_inputs)
+
+    def many(self, batches, label_name="label", then=None):
+        """len(batches) <= 32 consecutive train_loop iterations; with ``use_graph`` as ONE hipGraph replay (captured at the
+        second sighting of the same input addresses, enqueued eagerly at the first).  ``then``: the batch, or list of
+        batches, of the NEXT call -- their plans are built behind this call's steps.  A batch of this call that no
+        earlier call announced is planned in line.  Returns the last step's loss (device scalar); ``loss_steps[i]`` holds
+        step i's."""
+        half = self.NBUF // 2
+        if then is None:
+            then_list = []
+        elif isinstance(then, dict):
+            then_list = [then]
+        else:
+            then_list = list(then)
+        if not 1 <= len(batches) <= half or len(then_list) > half:
+            raise ValueError("many(): 1 to %d batches per call (and at most %d per announcement)" % (half, half))
+        seq, keys = [], []
+        for b in batches:
+            cols, key = self._cols_key(b)
+            y = b[label_name]
+            if y.dtype != torch.float32 or not y.is_cuda or y.numel() != self.B or not y.is_contiguous():
+                raise ValueError("label must be a contiguous float32 CUDA tensor with %d entries" % self.B)
+            seq.append((cols, y))
+            keys.append(key)
+        then_cols, then_keys = [], []
+        for b in then_list:
+            cols, key = self._cols_key(b)
+            then_cols.append(cols)
+            then_keys.append(key)
+        n = len(seq)
+        cur_half = self._half
+        pre = self._prefetched
+        used = set(pre[k] for k in keys if k in pre)
+        free = [cur_half * half + j for j in range(half) if cur_half * half + j not in used]
+        bufs, inline = [], []
+        for i, k in enumerate(keys):
+            if k in pre and pre[k] not in bufs:
+                bufs.append(pre[k])
+            else:
+                bufs.append(free.pop(0))
+                inline.append(i)
+        other = (1 - cur_half) * half
+        then_bufs = [other + j for j in range(len(then_cols))]
+        gkey = (tuple(keys), tuple(y.data_ptr() for _, y in seq), tuple(then_keys), tuple(bufs), tuple(inline))
+
+        def enqueue_all():
+            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            for i in inline:                                     # not announced: planned in line
+                self._plan(seq[i][0], bufs[i], st)
+            for i in range(n):
+                self._row = i
+                self._launch_main(seq[i][1], bufs[i], st)
+                self._launch_post(bufs[i], st)
+            for cols, b in zip(then_cols, then_bufs):            # the next call's plans, behind this call's steps
+                self._plan(cols, b, st)
+
+        if not self.use_graph:
+            enqueue_all()
+        else:
+            ent = self._graphs.get(gkey)
+            if ent is not None:
+                self._graphs.move_to_end(gkey)
+                ent[0].replay()
+            elif gkey not in self._seen:
+                enqueue_all()                                    # first sighting: eager, nothing retained
+                self._seen[gkey] = True
+                if len(self._seen) > 8 * self.MAX_GRAPHS:
+                    self._seen.popitem(last=False)
+            else:
+                # second sighting: the eager enqueue IS this call's work; the capture (not run) serves the calls to come
+                enqueue_all()
+                torch.cuda.synchronize()
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, capture_error_mode=CAPTURE_MODE):
+                    enqueue_all()
+                self._graphs[gkey] = (g, seq, then_cols)         # the inputs stay alive as long as the graph does
+                del self._seen[gkey]
+                while len(self._graphs) > self.MAX_GRAPHS:
+                    self._graphs.popitem(last=False)
+        self.t += n
+        self._last_buf = bufs[n - 1]
+        self.loss = self.loss_steps[n - 1]
+        self._prefetched = dict(zip(then_keys, then_bufs))
+        self._half = 1 - cur_half if then_cols else cur_half
+        return self.loss
+
+    def release(self):
+        """Drop the captured graphs (and the inputs they hold)."""
+        self._graphs.clear()
+        self._seen.clear()
+
+    def check_flags(self):
+        if int(self.oob.item()) != 0:
+            raise IndexError("embedding id out of range [0, feature_dims)")
+
+    def gradients(self):
+        """The last step's gradients: dense tensors by parameter name; (uniq_ids, rows [n,E], n_uniq) per table."""
+        out = dict(self.g)
+        b = self._last_buf
+        for t, name in enumerate(("u_tower.embed.embeddings", "i_tower.embed.embeddings")):
+            pl = self.plans[t]
+            out[name] = (pl["uniq"][b], self.rows[t], pl["nu"][b])
+        return out
+
+
 def exchange_capacity(field_dims, field_offsets, batch_size, rows_per_shard, n_shard):
     """Slots per owner of a fixed-capacity exchange: the most unique ids ONE batch can hold for one owner =
     max over owners of the sum over the fields that intersect the owner's block of min(B, overlap) (a field contributes

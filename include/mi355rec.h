@@ -394,6 +394,37 @@ int rec_adam_keras_flush_f32(float* table, int64_t ld, int64_t V, float* m_e, fl
                              float* v_w, int64_t ld_wstate, int32_t* last, const int64_t* step_dev, const float* lr_table,
                              int64_t n_table, float b1, float b2, float eps, void* stream);
 
+/* ---- Fused DSSM two-tower train step (2.FM/CustomLayers.py:208-239 under 2.FM/ModelManager.py:171-177) for the
+ * widths mlp_dims [64,32], final_dim 8 (h1, h2, d_out; anything else: REC_E_UNSUPPORTED), E in {8,16,32,64} shared by
+ * both towers, 1 <= F_u, F_i <= 8 (csrc/dssm_fused.hip).  Two launches:
+ *   main: gather of ids [B,F] (row-major, 64-bit row offsets into table[V, ld], ld >= E a multiple of 4, table 16-byte
+ *         aligned; an id outside [0,V) reads a zero row, gets a zero gradient row and sets *oob_flag), both tower MLPs
+ *         on fp32 MFMA, score (1 - cos)/2, Keras BCE (mean over B) and the whole backward.  Writes the per-lookup
+ *         gradient rows u_vals [B*F_u,E] / i_vals [B*F_i,E] and per-workgroup dense partials + loss terms into the
+ *         workspace; user_emb / item_emb [B,8] and score [B] when non-null.  weights: host array of 12 device pointers
+ *         (user tower K0 [F_u*E,64], b0, K1 [64,32], b1, Kf [32,8], bf, then the item tower's).  step_dev != NULL: the
+ *         optimizer's device-side step counter is advanced as in rec_deepfm_fused3_main_direct_adv_f32.
+ *   post: fixed-order reduction of the partials into grads (host array of 12 device pointers, order of `weights`) and
+ *         *loss, side by side with the segment sums of u_vals / i_vals over a rec_dedup_plan_i64 of each tower's flat
+ *         ids (perm, seg_start, uniq_ids, n_uniq) -> u_rows [B*F_u,E] / i_rows [B*F_i,E] (zero on the padded tail).
+ *         adam != NULL (host array: u_table, u_m, u_v, i_table, i_m, i_v; m / v dense [V,E]): the touched-rows Adam update
+ *         of rec_adam_rows_f32 on every unique row, step size *lr_t_dev.
+ * No float atomics: bit-identical results run to run.  workspace: rec_dssm_fused_workspace_bytes (0: unsupported). */
+size_t rec_dssm_fused_workspace_bytes(int64_t B, int E, int F_u, int F_i);
+int rec_dssm_fused_main_f32(const float* u_table, int64_t u_ld, int64_t u_V, const int64_t* u_ids, int F_u,
+                            const float* i_table, int64_t i_ld, int64_t i_V, const int64_t* i_ids, int F_i, int E,
+                            int h1, int h2, int d_out, int64_t B, const float* const* weights, const float* label,
+                            float* u_vals, float* i_vals, float* user_emb, float* item_emb, float* score, int* oob_flag,
+                            void* workspace, size_t workspace_bytes, int64_t* step_dev, const float* lr_table,
+                            int64_t n_table, float* lr_t_dev, void* stream);
+int rec_dssm_fused_post_f32(int64_t B, int E, int F_u, int F_i, const void* workspace, size_t workspace_bytes,
+                            float* const* grads, float* loss, const float* u_vals, const int32_t* u_perm,
+                            const int32_t* u_seg, const int64_t* u_uniq, const int64_t* u_n_uniq, float* u_rows,
+                            const float* i_vals, const int32_t* i_perm, const int32_t* i_seg, const int64_t* i_uniq,
+                            const int64_t* i_n_uniq, float* i_rows, float* const* adam, int64_t u_ld, int64_t u_V,
+                            int64_t i_ld, int64_t i_V, const float* lr_t_dev, float b1, float b2, float eps,
+                            void* stream);
+
 /* ---- K8/K9  DIN ActivationUnit + masked sum pooling (5.DIN/CustomLayers.py:163-180, 256-282), factorised:
  *   pre[b,t,:] = c_b + k_t . Eff_b,  Eff_b = (W_k - W_d) + M_b,  M_b[i,o] = sum_j q_j W_o[i,j,o],
  *   c_b = q (W_q + W_d) + b1;  score = act(pre) . w2 + b2;  pooled[b,:] = sum_t mask[b,t] * score[b,t] * k_t.

@@ -7,6 +7,7 @@ batches, one MI355X.  Prints one JSON line per config.  Usage:  python scripts/b
   B   DeepFM, 26 fields, V=1M, E=16, B=8192                   (configs[1]; the 10M variant is bench.py)
   C   DCN matrix CrossNet, 10 cat + 3 cont, V=10M, E=32, L=3, B=16384 (D=323); C26 = 26 cat fields (D=835)
   D   DSSM two-tower, item V=100M x 64d on ONE GPU (25.6 GB table; the 8-way sharded form is sharded.py), B=8192
+  DF  config D through engine.DSSMFusedStep (fused HIP train step, gradients only), graphed cycles of 20 steps
   E   DIN, T=100, V=50M, E=32, B=4096
   R   retrieval after the towers: 10M items x 8d (L2-normalised), 1024 user vectors, top-20
   P   PNN inner product (f4), 26 fields, V=10M, E=16, B=8192      N   NFM (f4), 10 cat + 3 cont, V=10M, E=16, B=16384
@@ -160,6 +161,41 @@ def run(name):
         dt = timed(fwd_bwd(layer, batch, un + inn), 3, 20)
         return {"config": "D DSSM two-tower, item table 100M x 64d (25.6 GB) on one GPU", "B": B, "V": V,
                 "ms_per_step": dt * 1e3, "examples_per_s": B / dt}
+    if name == "DF":
+        # config D through engine.DSSMFusedStep (csrc/dssm_fused.hip, gradients only): 40 resident batches (2 x 10.5 MB of
+        # rows touched per cycle of 20 steps: no cycle finds its rows in the 256-MB memory-side cache from the previous
+        # one), graphed cycles of 20 steps, each announcing the other cycle's batches so that their plans are built behind it
+        from explicit_tf2_recommendation_amd import engine
+        un, inn = ["user_tag1", "user_tag2"], ["item_tag1", "item_tag2", "item_tag3"]
+        V, B, E, K = 100_000_000, 8192, 64, 20
+        layer = layers.DSSMTwoTowerRetrievalLayer(u_feature_names=un, i_feature_names=inn, u_feature_dims=1000,
+                                                  i_feature_dims=1000, u_embedding_dims=E, i_embedding_dims=E).cuda()
+        layer.i_tower.embed.embeddings = torch.nn.Parameter(torch.empty((V, E), device="cuda"))
+        layer.u_tower.embed.embeddings = torch.nn.Parameter(torch.empty((V // 10, E), device="cuda"))
+        big_table_(layer.i_tower.embed.embeddings)
+        big_table_(layer.u_tower.embed.embeddings)
+        gi, gu = data.SyntheticGenerator(inn, V, seed=0), data.SyntheticGenerator(un, V // 10, seed=1)
+        batches = []
+        for _ in range(2 * K):
+            bi, bu = gi.batch(B), gu.batch(B)
+            batches.append(data.to_device({**{k: bu[k] for k in un}, **{k: bi[k] for k in inn}, "label": bi["label"]}))
+        cyc = [batches[:K], batches[K:]]
+        step = engine.DSSMFusedStep(layer, B)
+        calls = [0]
+
+        def cycle():
+            c = calls[0] % 2
+            step.many(cyc[c], then=cyc[1 - c])
+            calls[0] += 1
+        dt = timed(cycle, 6, 10) / K            # 6 warm-up calls: every form of a call is captured by the 5th
+        step.check_flags()
+        Fu, Fi = len(un), len(inn)
+        nbytes = 4 * E * B * (Fu + Fi) * 4      # rows gathered, per-lookup gradient rows written + read, unique rows written
+        flop = 2.0 * B * sum(3 * K0 * 64 + 3 * 64 * 32 + 3 * 32 * 8 for K0 in (Fu * E, Fi * E))
+        return {"config": "DF DSSM two-tower, item table 100M x 64d, engine.DSSMFusedStep (graphed cycles of %d steps over "
+                          "%d resident batches)" % (K, 2 * K), "B": B, "V": V, "ms_per_step": dt * 1e3,
+                "examples_per_s": B / dt, "algorithmic_bytes_per_step": nbytes, "flop_per_step": flop,
+                "floor_ms_8TBps": nbytes / 8e12 * 1e3, "floor_ms_157TF": flop / 157e12 * 1e3}
     if name in ("DS", "ES"):
         # configs D / E with their tables ROW-SHARDED (layers.*(sharded=True): de-duplicated fixed-capacity exchange) at
         # world size 1 -- the exchange code of N > 1 with the rank's own slab kept out of RCCL; target <= 1.3 x D / E
