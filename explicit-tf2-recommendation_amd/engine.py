@@ -8,13 +8,19 @@ Nothing is allocated and nothing synchronises inside a step, so a step can be ca
 the host.  Gradients come out exactly as the autograd path of layers.py produces them (dense tensors for dense
 parameters; (uniq_ids, rows, n_uniq) for the tables) -- tests/test_gpu_engine.py holds the two paths equal.
 """
+import collections
 import ctypes as C
+import operator
+import weakref
 
 import torch
 
 from . import ops
 from ._lib import lib, check
 
+
+# Adam's constants: the defaults of tf.keras.optimizers.Adam, the reference's optimizer
+ADAM_B1, ADAM_B2, ADAM_EPS = 0.9, 0.999, 1e-7
 
 # Stream captures use the thread-local error mode: with a process group alive, ProcessGroupNCCL's watchdog thread polls
 # the events of finished collectives (hipEventQuery) whenever it likes, and in the default global mode such a call from
@@ -48,6 +54,53 @@ def _tables_share_rows(embed, w):
     E = embed.shape[1]
     return (embed.is_cuda and E % 4 == 0 and embed.stride(0) == w.stride(0) and embed.stride(0) % 4 == 0
             and embed.stride(0) >= E + 1 and w.data_ptr() == embed.data_ptr() + 4 * E and embed.data_ptr() % 16 == 0)
+
+
+class _BatchReader:
+    """The validated id columns (``names`` in order) and label of a batch dict.  ``cols_key`` caches them per dict: the
+    26 dtype / device / size / stride checks and address reads of a batch were half of the host time of a fused-step
+    call (which the GPU waits for whenever a call starts from an empty queue), so they run once per batch dict, and
+    again only when a tensor of the dict was replaced (identity of the tensor objects, compared in C: itemgetter +
+    map(id)).  ``cuda``: the tensors must live on the GPU (the kernels take raw device pointers)."""
+
+    def __init__(self, names, B, cuda=True):
+        self.names, self.B, self.cuda = list(names), int(B), cuda
+        n0 = self.names[0]
+        self._get = operator.itemgetter(*self.names) if len(self.names) > 1 else (lambda d: (d[n0],))
+        self._cache = {}
+
+    @staticmethod
+    def key(cols):
+        return tuple(c.data_ptr() for c in cols)
+
+    def cols(self, inputs):
+        """The columns of ``inputs``, validated (not cached)."""
+        cols = list(self._get(inputs))
+        for name, c in zip(self.names, cols):
+            if c.dtype != torch.int64 or c.numel() != self.B or not c.is_contiguous() or (self.cuda and not c.is_cuda):
+                raise ValueError("feature %r must be a contiguous int64 %stensor with %d ids"
+                                 % (name, "CUDA " if self.cuda else "", self.B))
+        return cols
+
+    def cols_key(self, inputs):
+        """(columns, their addresses) of ``inputs``."""
+        ent = self._cache.get(id(inputs))
+        if ent is not None and ent[2] is inputs and tuple(map(id, self._get(inputs))) == ent[3]:
+            return ent[0], ent[1]
+        cols = self.cols(inputs)
+        if len(self._cache) > 256:
+            self._cache.clear()
+        key = self.key(cols)
+        self._cache[id(inputs)] = (cols, key, inputs, tuple(map(id, cols)))
+        return cols, key
+
+    def label(self, inputs, name):
+        """The label ``inputs[name]``: a contiguous float32 tensor of B entries (the BCE kernels read it as an array)."""
+        y = inputs[name]
+        if y.dtype != torch.float32 or y.numel() != self.B or not y.is_contiguous() or (self.cuda and not y.is_cuda):
+            raise ValueError("label must be a contiguous float32 %stensor with %d entries"
+                             % ("CUDA " if self.cuda else "", self.B))
+        return y
 
 
 class DeepFMTrainStep:
@@ -118,6 +171,7 @@ class DeepFMTrainStep:
             self.side_w = torch.empty((n, 3, 1), **f32)
         self.colsum_ws = torch.empty(lib.rec_colsum_workspace_bytes(B, max(u1, u2)) // 4 + 1, **f32)
         self.segsum_ws = torch.empty(lib.rec_segment_sum_workspace_bytes(n, E) // 4, **f32)
+        self._reader = _BatchReader(layer.feature_names, B)
         self._graphs = {}
         self._static_prog = self._build_static()
 
@@ -181,7 +235,7 @@ class DeepFMTrainStep:
     def _optimizer_program(self, t):
         L = self.layer
         P = _Program()
-        lr, b1, b2, eps = self.lr, 0.9, 0.999, 1e-7
+        lr, b1, b2, eps = self.lr, ADAM_B1, ADAM_B2, ADAM_EPS
         params = dict(L.named_parameters())
         for name, grad in self.g.items():
             m, v = self.state[name]
@@ -217,21 +271,9 @@ class DeepFMTrainStep:
         if self.optimizer is not None:
             self._optimizer_program(t).run(stream)
 
-    def _check_inputs(self, inputs, label_name):
-        cols = []
-        for name in self.layer.feature_names:
-            t = inputs[name]
-            if t.dtype != torch.int64 or not t.is_cuda or t.numel() != self.B or not t.is_contiguous():
-                raise ValueError("feature %r must be a contiguous int64 CUDA tensor with %d ids" % (name, self.B))
-            cols.append(t)
-        y = inputs[label_name]
-        if y.dtype != torch.float32 or not y.is_cuda or y.numel() != self.B:
-            raise ValueError("label must be a float32 CUDA tensor with %d entries" % self.B)
-        return cols, y
-
     def __call__(self, inputs, label_name="label"):
         """One train_loop iteration.  Returns the device scalar loss (no synchronisation)."""
-        cols, y = self._check_inputs(inputs, label_name)
+        cols, y = self._reader.cols(inputs), self._reader.label(inputs, label_name)
         self.t += 1
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         if not self.use_graph or self.optimizer is not None:
@@ -293,21 +335,190 @@ def _bits(n):
     return b
 
 
-class DeepFMFusedStep:
+def _deepfm_fused_limits(B, field_dims, field_offsets, layer=None, sort_words=False):
+    """What the fused DeepFM kernels are instantiated for.  ``layer``: embedding_dims 16, mlp_dims [32, 8], F <= 28,
+    B <= 16384 and one (dim, offset) per feature (NotImplementedError).  ``sort_words``: ascending field offsets
+    (ValueError: the DataGenerator contract) and in-field keys that fit the 32-bit words of the per-column plan sort
+    beside the example index (NotImplementedError); returns the largest key."""
+    if layer is not None:
+        F = len(layer.feature_names)
+        if layer.embed.embeddings.shape[1] != 16 or list(layer.mlp_dims) != [32, 8]:
+            raise NotImplementedError("the fused DeepFM step covers embedding_dims=16, mlp_dims=[32,8]")
+        if F > 28 or B > 16384 or len(field_dims) != F or len(field_offsets) != F:
+            raise NotImplementedError("the fused DeepFM step: F <= 28, B <= 16384, one (dim, offset) per feature")
+    if not sort_words:
+        return None
+    if any(field_offsets[i] >= field_offsets[i + 1] for i in range(len(field_offsets) - 1)):
+        raise ValueError("field offsets must be ascending (DataGenerator contract)")
+    max_key = max(int(d) for d in field_dims) - 1
+    if _bits(max_key + 1) + _bits(B) > 32 or ((max_key << _bits(B)) | (B - 1)) >= 0xFFFFFFFF:
+        raise NotImplementedError("field too wide for the 32-bit sort words at this batch size")
+    return max_key
+
+
+def _assign_plan_buffers(keys, n_then, prefetched, half, nhalf):
+    """Plan buffers of one many() call.  The ring has two halves of ``nhalf`` buffers; the plans announced by the
+    previous call (``prefetched``: batch key -> buffer) live in half ``half``.  A batch of this call that was announced
+    reads its buffer (its first occurrence in the call: a repeat is planned again), every other batch takes the next
+    free buffer of the same half and is planned inline.  The ``n_then`` batches announced for the next call go to the
+    other half, which the next call then reads.
+    Returns (bufs, inline, then_bufs, next_half): a buffer per batch, the indices of the batches planned inline, the
+    announced batches' buffers and the half of the next call."""
+    used = set(prefetched[k] for k in keys if k in prefetched)
+    free = [half * nhalf + j for j in range(nhalf) if half * nhalf + j not in used]
+    bufs, inline = [], []
+    for i, k in enumerate(keys):
+        if k in prefetched and prefetched[k] not in bufs:
+            bufs.append(prefetched[k])
+        else:
+            bufs.append(free.pop(0))
+            inline.append(i)
+    other = (1 - half) * nhalf
+    return bufs, inline, [other + j for j in range(n_then)], (1 - half if n_then else half)
+
+
+class _FusedStep:
+    """Call machinery of the fused train steps (DeepFMFusedStep, DSSMFusedStep): batch reading, the ring of NBUF
+    de-duplication plan buffers with the prefetch of announced batches, ``many()`` and its graph policy, and the
+    device-side Adam clock.  A subclass sets B, calls ``super().__init__(names)`` (the id columns of a batch) and
+    supplies ``_enqueue`` (the launches of one call), and where it differs ``_graphable``, ``_before_call`` and
+    ``_after_call``."""
+
+    NBUF = 64           # plan buffers: two halves of 32, many() alternates between them (a hipGraph launch leaves the GPU
+                        # idle for ~30 us, so a call may hold up to 32 steps: ~1 us per step at that length)
+    MAX_GRAPHS = 64     # captured hipGraphs kept (least recently used beyond that are dropped with the inputs they hold)
+
+    def __init__(self, names):
+        self._reader = _BatchReader(names, self.B)
+        self._prefetched, self._half = {}, 0     # plans announced by the previous call: id-tensor addresses -> buffer
+        self._graphs = collections.OrderedDict()            # gkey -> (graph, inputs kept alive), LRU order
+        self._seen = collections.OrderedDict()              # gkeys enqueued eagerly once (addresses only: nothing is held)
+
+    def _init_device_adam(self, names):
+        """Adam with the step counter and the bias-corrected step size on the device (advanced by the fused launch): the
+        train step holds no per-step host scalar, so it is captured and replayed like the gradient-only step.  The table
+        holds lr_t of steps 1..N exactly as the host-side entry points compute it; beyond it the corrections are 1.0f.
+        The rec_adam_dense_multi_f32 arguments of the dense parameters ``names`` are built once: parameters, moments and
+        gradients are updated in place (and a captured graph holds their addresses anyway)."""
+        N = 32768
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        self._lr_tab = torch.tensor([lib.rec_adam_lr_t_f32(self.lr, ADAM_B1, ADAM_B2, t) for t in range(1, N + 1)], **f32)
+        self._step_dev = torch.zeros(1, dtype=torch.int64, device=self.dev)
+        self._lr_t_dev = torch.zeros(1, **f32)
+        params, k = dict(self.layer.named_parameters()), len(names)
+        ptrs = lambda ts: (C.c_void_p * k)(*[t.data_ptr() for t in ts])     # noqa: E731
+        self._multi = (k, ptrs(params[nm] for nm in names), ptrs(self.state[nm][0] for nm in names),
+                       ptrs(self.state[nm][1] for nm in names), ptrs(self.g[nm] for nm in names),
+                       (C.c_int64 * k)(*[self.g[nm].numel() for nm in names]))
+
+    def _adam_dense_dev(self, st):
+        """Adam on the dense parameters in ONE launch, with the step size of the device clock."""
+        check(lib.rec_adam_dense_multi_f32(*self._multi, _p(self._lr_t_dev), ADAM_B1, ADAM_B2, ADAM_EPS, st),
+              "rec_adam_dense_multi_f32")
+
+    def _cols(self, inputs):
+        return self._reader.cols(inputs)
+
+    _key = staticmethod(_BatchReader.key)
+
+    def _graphable(self):
+        return True
+
+    def _before_call(self):
+        """Runs at the start of every call, outside any capture."""
+
+    def _after_call(self, n, bufs):
+        """Bookkeeping after a call of ``n`` steps that read plan buffers ``bufs``."""
+
+    def __call__(self, inputs, label_name="label", next_inputs=None):
+        """One train_loop iteration on `inputs`.  ``next_inputs`` (optional) = the batch of the NEXT call: its
+        de-duplication plan is built behind this call's step (input-pipeline style prefetch: the plan depends on ids
+        only).  Without it, or when the previous call did not announce this batch, the plan is built inside this call,
+        in front of the fused kernel."""
+        return self.many([inputs], label_name, then=next_inputs)
+
+    def many(self, batches, label_name="label", then=None):
+        """len(batches) <= NBUF / 2 consecutive train_loop iterations; with ``use_graph`` as ONE hipGraph replay (a
+        launch-bound inner loop: one graph launch costs ~20 us of idle GPU).  ``then``: the batch, or the list of
+        batches, of the NEXT call -- their de-duplication plans are built behind this call's steps, so that no fused
+        kernel of the next call waits for a plan.  A batch of this call that no earlier call announced is planned in
+        line.  Returns the last step's loss; ``loss_steps[i]`` holds step i's.  Results left in the buffers are the last
+        step's; gradients are to be consumed by an optimizer in the same call or after single-step calls."""
+        nhalf = self.NBUF // 2
+        then_list = [] if then is None else [then] if isinstance(then, dict) else list(then)
+        if not 1 <= len(batches) <= nhalf or len(then_list) > nhalf:
+            raise ValueError("many(): 1 to %d batches per call (and at most %d per announcement)" % (nhalf, nhalf))
+        rd = self._reader
+        seq, keys = [], []
+        for b in batches:
+            cols, key = rd.cols_key(b)
+            seq.append((cols, rd.label(b, label_name)))
+            keys.append(key)
+        then_cols, then_keys = [], []
+        for b in then_list:
+            cols, key = rd.cols_key(b)
+            then_cols.append(cols)
+            then_keys.append(key)
+        bufs, inline, then_bufs, next_half = _assign_plan_buffers(keys, len(then_cols), self._prefetched, self._half,
+                                                                  nhalf)
+        gkey = (tuple(keys), tuple(y.data_ptr() for _, y in seq), tuple(then_keys), tuple(bufs), tuple(inline))
+        t_base = self.t
+        self._before_call()
+        self._run(gkey, lambda: self._enqueue(seq, bufs, inline, then_cols, then_bufs, t_base), seq, then_cols)
+        self.t = t_base + len(seq)
+        self._after_call(len(seq), bufs)
+        self._prefetched = dict(zip(then_keys, then_bufs))
+        self._half = next_half
+        return self.loss
+
+    def _run(self, gkey, enqueue_all, *keep):
+        """The graph policy of a call with input addresses ``gkey``.  First sighting: plain eager enqueue, no device
+        synchronisation, nothing retained -- an input pipeline that hands over fresh tensors every batch never gets past
+        this branch, one that cycles staging buffers is captured on the next round.  Second sighting: enqueued eagerly
+        -- that IS this call's work -- and then captured, without running, for the calls to come (with an optimizer in
+        the step a warm-up followed by a replay would apply the update twice).  After that: replayed.  The last
+        MAX_GRAPHS graphs used are kept, each with ``keep`` (the inputs whose addresses it holds)."""
+        if not (self.use_graph and self._graphable()):
+            enqueue_all()
+            return
+        ent = self._graphs.get(gkey)
+        if ent is not None:
+            self._graphs.move_to_end(gkey)
+            ent[0].replay()
+        elif gkey not in self._seen:
+            enqueue_all()
+            self._seen[gkey] = True
+            if len(self._seen) > 8 * self.MAX_GRAPHS:
+                self._seen.popitem(last=False)
+        else:
+            enqueue_all()
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, capture_error_mode=CAPTURE_MODE):
+                enqueue_all()
+            self._graphs[gkey] = (g,) + keep
+            del self._seen[gkey]
+            while len(self._graphs) > self.MAX_GRAPHS:
+                self._graphs.popitem(last=False)             # least recently used: graph and retained inputs go
+
+    def release(self):
+        """Drop the captured graphs (and the inputs they hold)."""
+        self._graphs.clear()
+        self._seen.clear()
+
+
+class DeepFMFusedStep(_FusedStep):
     """The same train_loop iteration as DeepFMTrainStep in two launches on the main stream: the fused forward+backward
     kernel (csrc/deepfm_fused3.hip), then ONE launch (csrc/deepfm_fused.hip) for the fixed-order reduction of its partials
     and the segment sums -- plus, behind the steps of a call, the per-column LDS sort (csrc/colsort.hip) of the
-    de-duplication plans of the batches announced for the next call (they depend only on the ids).  ``many()`` runs several iterations as one captured hipGraph.
+    de-duplication plans of the batches announced for the next call (they depend only on the ids).  ``many()`` runs
+    several iterations as one captured hipGraph (call forms, plan ring and graph policy: _FusedStep).
 
     Requirements (checked; otherwise use DeepFMTrainStep): embedding_dims 16, mlp_dims [32,8], fused table layout,
     F <= 28, B <= 16384, and the DataGenerator id-space contract -- ``field_offsets[f]``/``field_dims[f]`` =
     ``data_info.json``'s offsets and dims (2.FM/DataGenerator.py:126-134); an id outside its field's range sets
     ``self.bad_ids`` (checked by ``check_flags()``).
     """
-
-    NBUF = 64           # plan buffers (see __init__): two halves of 32, many() alternates between them (a hipGraph launch
-                        # leaves the GPU idle for ~30 us, so a call may hold up to 32 steps: ~1 us per step at that length)
-    MAX_GRAPHS = 64     # captured hipGraphs kept (least recently used beyond that are dropped with the inputs they hold)
 
     def __init__(self, layer, batch_size, field_dims, field_offsets, optimizer=None, lr=1e-3, use_graph=True,
                  direct=True, want_prob=False):
@@ -317,17 +528,9 @@ class DeepFMFusedStep:
         self.F = F = len(layer.feature_names)
         emb, w = layer.embed.embeddings, layer.w.embeddings
         self.V, self.E = emb.shape
-        if self.E != 16 or list(layer.mlp_dims) != [32, 8]:
-            raise NotImplementedError("the fused step covers embedding_dims=16, mlp_dims=[32,8]")
         if emb.stride(0) != 32 or w.stride(0) != 32 or w.data_ptr() != emb.data_ptr() + 64:
             raise NotImplementedError("the fused step needs the fused [embed|w|pad] table layout (layer.cuda())")
-        if F > 28 or B > 16384 or len(field_dims) != F or len(field_offsets) != F:
-            raise NotImplementedError("fused step: F <= 28, B <= 16384, one (dim, offset) per feature")
-        if any(field_offsets[i] >= field_offsets[i + 1] for i in range(F - 1)):
-            raise ValueError("field offsets must be ascending (DataGenerator contract)")
-        self.max_key = max(int(d) for d in field_dims) - 1
-        if _bits(self.max_key + 1) + _bits(B) > 32 or ((self.max_key << _bits(B)) | (B - 1)) >= 0xFFFFFFFF:
-            raise NotImplementedError("field too wide for the 32-bit sort words at this batch size")
+        self.max_key = _deepfm_fused_limits(B, field_dims, field_offsets, layer, sort_words=True)
         dev = emb.device
         self.dev = dev
         if optimizer not in (None, "keras_adam", "lazy_adam", "keras_adam_lazy"):
@@ -375,11 +578,7 @@ class DeepFMFusedStep:
         # 17 batches per launch, 442 workgroups, were measured slower than 9)
         self.GROUP = max(1, 256 // F)
         self.col_lo_rep = self.col_lo.repeat(self.GROUP).contiguous()
-        self._prefetched, self._half = {}, 0     # plans announced by the previous call: id-tensor addresses -> buffer
-        self._col_cache = {}
-        import operator
-        names_ = list(layer.feature_names)
-        self._getter = (operator.itemgetter(*names_) if len(names_) > 1 else (lambda d, n=names_[0]: (d[n],)))
+        super().__init__(layer.feature_names)
         self.uniq_ids = torch.empty(n, dtype=torch.int64, device=dev)
         self.g_embed_rows = torch.empty((n, 16), **f32)
         self.g_w_rows = torch.empty((n, 1), **f32)
@@ -408,7 +607,6 @@ class DeepFMFusedStep:
                 if owner is not None and owner() is not None and owner() is not self:
                     raise ValueError("another DeepFMFusedStep already keeps its optimizer state in this layer's table "
                                      "padding (floats 17/18 of the fused rows): one lazy-optimizer step per layer")
-                import weakref
                 layer._fused_state_owner = weakref.ref(self)
                 self._mv = torch.zeros((self.V, 32), **f32)
                 fused[:, 17:19].zero_()
@@ -416,26 +614,7 @@ class DeepFMFusedStep:
                 self.state["w.embeddings"] = (fused[:, 17:18], fused[:, 18:19])
             self._last = (torch.zeros(self.V, dtype=torch.int32, device=dev)
                           if optimizer == "keras_adam_lazy" else None)    # the step every row holds
-            # the step counter and the bias-corrected step size live on the device (advanced by the fused launch): the
-            # train step holds no per-step host scalar, so it is captured and replayed like the gradient-only step.  The
-            # table holds lr_t of steps 1..N exactly as the host-side entry points compute it; beyond it the corrections
-            # are 1.0f
-            N = 32768
-            tab = [lib.rec_adam_lr_t_f32(lr, 0.9, 0.999, t) for t in range(1, N + 1)]
-            self._lr_tab = torch.tensor(tab, **f32)
-            self._step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
-            self._lr_t_dev = torch.zeros(1, **f32)
-            params = dict(layer.named_parameters())
-            names = list(self.g)
-            k = len(names)
-            self._multi = (k, (C.c_void_p * k)(*[params[nm].data_ptr() for nm in names]),
-                           (C.c_void_p * k)(*[self.state[nm][0].data_ptr() for nm in names]),
-                           (C.c_void_p * k)(*[self.state[nm][1].data_ptr() for nm in names]),
-                           (C.c_void_p * k)(*[self.g[nm].data_ptr() for nm in names]),
-                           (C.c_int64 * k)(*[self.g[nm].numel() for nm in names]))
-        import collections
-        self._graphs = collections.OrderedDict()            # gkey -> (graph, inputs kept alive), LRU order
-        self._seen = collections.OrderedDict()              # gkeys enqueued eagerly once (addresses only: nothing is held)
+            self._init_device_adam(list(self.g))
         # K0^T for the fused kernel, refreshed whenever the parameter changed -- by torch or by this step's own optimizer
         # launches (which re-transpose in the same stream)
         self._k0t = _K0T(layer, F)
@@ -474,7 +653,7 @@ class DeepFMFusedStep:
             check(lib.rec_adam_keras_catchup_f32(_p(pl["col_uid"]), _p(pl["col_nu"]), self.B, F, _p(emb), emb.stride(0),
                                                  self.V, _p(me), _p(ve), me.stride(0), _p(mw), _p(vw), mw.stride(0),
                                                  _p(self._last), _p(self._step_dev), _p(self._lr_tab),
-                                                 self._lr_tab.numel(), 0.9, 0.999, 1e-7, st),
+                                                 self._lr_tab.numel(), ADAM_B1, ADAM_B2, ADAM_EPS, st),
                   "rec_adam_keras_catchup_f32")
         self._k0t.refresh(st)
         if not self.direct:
@@ -518,7 +697,7 @@ class DeepFMFusedStep:
                 _p(g["MLP_layer2.bias_0"]), _p(g["bias"]), self._ploss(), _p(self.ws), _p(pl["perm"]),
                 _p(pl["col_uid"]), _p(pl["col_seg"]), _p(pl["col_nu"]), _p(self.uniq_ids), _p(self.g_embed_rows),
                 _p(self.g_w_rows), _p(self.n_uniq), _p(pe), pe.stride(0), self.V, _p(me), _p(ve), _p(mw), _p(vw),
-                me.stride(0), mw.stride(0), _p(self._lr_t_dev), 0.9, 0.999, 1e-7,
+                me.stride(0), mw.stride(0), _p(self._lr_t_dev), ADAM_B1, ADAM_B2, ADAM_EPS,
                 _p(self._last) if self._last is not None else None, _p(self._step_dev), st),
                 "rec_deepfm_fused_post_direct_adam_dev_f32")
             return
@@ -538,13 +717,11 @@ class DeepFMFusedStep:
             _p(self.n_uniq), st), "rec_deepfm_fused_post_direct_f32")
 
     def _optimizer(self, t, st):
-        lr, b1, b2, eps = self.lr, 0.9, 0.999, 1e-7
+        lr, b1, b2, eps = self.lr, ADAM_B1, ADAM_B2, ADAM_EPS
         if self._fused_lazy():
             # the tables were updated inside the post launch; the dense parameters follow in ONE launch, with the
             # step size the post launch used (device memory)
-            k, var, m, v, g, numel = self._multi
-            check(lib.rec_adam_dense_multi_f32(k, var, m, v, g, numel, _p(self._lr_t_dev), b1, b2, eps, st),
-                  "rec_adam_dense_multi_f32")
+            self._adam_dense_dev(st)
             self._k0t.refresh(st, force=True)
             return
         params = dict(self.layer.named_parameters())
@@ -575,154 +752,41 @@ class DeepFMFusedStep:
                 check(lib.rec_adam_rows_f32(_p(p), p.stride(0), _p(m), _p(v), self.V, E, _p(self.uniq_ids), _p(rows),
                                             _p(self.n_uniq), n, t, lr, b1, b2, eps, st), "rec_adam_rows_f32")
 
-    def _cols(self, inputs):
-        cols = []
-        for name in self.layer.feature_names:
-            c = inputs[name]
-            if c.dtype != torch.int64 or not c.is_cuda or c.numel() != self.B or not c.is_contiguous():
-                raise ValueError("feature %r must be a contiguous int64 CUDA tensor with %d ids" % (name, self.B))
-            cols.append(c)
-        return cols
+    def _graphable(self):
+        # (the non-lazy optimizers take the step as a host scalar: enqueued eagerly)
+        return self.optimizer is None or self._fused_lazy()
 
-    def __call__(self, inputs, label_name="label", next_inputs=None):
-        """One train_loop iteration on `inputs`.  ``next_inputs`` (optional) = the batch of the NEXT call: its
-        de-duplication plan is built behind this call's step (input-pipeline style prefetch: the plan depends on ids
-        only).  Without it, or when the previous call did not announce this batch,
-        the plan is built inside this call, in front of the fused kernel."""
-        return self.many([inputs], label_name, then=next_inputs)
-
-    def _key(self, cols):
-        return tuple(c.data_ptr() for c in cols)
-
-    def _cols_key(self, inputs):
-        """(columns, their addresses) of a batch.  The 26 dtype / device / size / stride checks and address reads of a
-        batch were half of the host time of a call (which the GPU waits for whenever a call starts from an empty
-        queue): done once per batch dict, and again only when a tensor of the dict was replaced (identity of the 26
-        tensor objects, compared in C: itemgetter + map(id))."""
-        ent = self._col_cache.get(id(inputs))
-        if ent is not None and ent[2] is inputs and tuple(map(id, self._getter(inputs))) == ent[3]:
-            return ent[0], ent[1]
-        cols = self._cols(inputs)
-        if len(self._col_cache) > 256:
-            self._col_cache.clear()
-        key = self._key(cols)
-        self._col_cache[id(inputs)] = (cols, key, inputs, tuple(map(id, cols)))
-        return cols, key
-
-    def many(self, batches, label_name="label", then=None):
-        """len(batches) consecutive train_loop iterations; with ``use_graph`` as ONE hipGraph replay (a launch-bound
-        inner loop: one graph launch costs ~20 us of idle GPU).  ``then``: the batch, or the list of batches, of the NEXT
-        call -- their de-duplication plans are built behind this call's steps, several batches per sort launch, so that
-        no fused kernel of the next call waits for a sort (the plan has to be complete before the kernel starts: direct
-        mode).
-        A batch of this call that no earlier call announced is sorted in line.  Results left in the buffers are the last
-        step's; gradients are to be consumed by an optimizer in the same call or after single-step calls."""
-        half = self.NBUF // 2
-        if then is None:
-            then_list = []
-        elif isinstance(then, dict):
-            then_list = [then]
-        else:
-            then_list = list(then)
-        if len(batches) > half or len(then_list) > half:
-            raise ValueError("many(): at most %d batches per call (and per announcement)" % half)
-        seq, keys = [], []
-        for b in batches:
-            cols, key = self._cols_key(b)
-            y = b[label_name]
-            if y.dtype != torch.float32 or not y.is_cuda or y.numel() != self.B or not y.is_contiguous():
-                raise ValueError("label must be a contiguous float32 CUDA tensor with %d entries" % self.B)
-            seq.append((cols, y))
-            keys.append(key)
-        then_cols, then_keys = [], []
-        for b in then_list:
-            cols, key = self._cols_key(b)
-            then_cols.append(cols)
-            then_keys.append(key)
-        n = len(seq)
-        # plan buffers: the ring has two halves.  Plans announced by the previous call live in half `cur_half`; batches
-        # of this call that were not announced take the free slots of the same half; the announced batches of the next
-        # call go to the other half
-        cur_half = self._half
-        pre = self._prefetched
-        used = set(pre[k] for k in keys if k in pre)
-        free = [cur_half * half + j for j in range(half) if cur_half * half + j not in used]
-        bufs, inline = [], []
-        for i, k in enumerate(keys):
-            if k in pre and pre[k] not in bufs:
-                bufs.append(pre[k])
-            else:
-                bufs.append(free.pop(0))
-                inline.append(i)
-        other = (1 - cur_half) * half
-        then_bufs = [other + j for j in range(len(then_cols))]
-        graphed = self.use_graph and (self.optimizer is None or self._fused_lazy())
-        gkey = (tuple(keys), tuple(y.data_ptr() for _, y in seq), tuple(then_keys), tuple(bufs), tuple(inline))
-
-        def enqueue_all():
-            main = torch.cuda.current_stream()
-            st = C.c_void_p(main.cuda_stream)
-            for i in inline:                                     # not announced: sorted in line
-                self._sort(seq[i][0], bufs[i], main)
-            self._row = 0
-            self._launch_main(seq[0][0], seq[0][1], st, bufs[0])
-            for i in range(n):
-                self._row = i
-                if i > 0:
-                    self._launch_main(seq[i][0], seq[i][1], st, bufs[i])
-                t = t_base + i + 1                               # 1-based step (host scalar of the non-graphed optimizers)
-                self._launch_post(bufs[i], st, t)
-                if self.optimizer is not None:
-                    self._optimizer(t, st)
-            # the plans of the batches announced for the NEXT call: GROUP batches (consecutive buffers) per sort launch, on the
-            # main stream BEHIND this call's steps.  (They used to run on a second stream beside the steps -- but a sort
-            # workgroup cannot share a CU with a fused-kernel workgroup (LDS), so "beside" meant that one fused launch in
-            # eight waited for the sort: serial on one stream is 0.7 us per step faster at K = 200, the same at K = 20, and
-            # the graph has no fork / join.)
-            m_ = len(then_cols)
-            if m_:
-                nl = -(-m_ // self.GROUP)                        # as few launches as the column limit allows, evenly filled
-                per = -(-m_ // nl)
-                for j in range(0, m_, per):
-                    self._sort_group(then_cols[j:j + per], then_bufs[j], main)
-
-        t_base = self.t
+    def _before_call(self):
         self._k0t.refresh()                                      # outside any capture: a replayed graph reads K0T
-        if not graphed:
-            enqueue_all()
-        else:
-            ent = self._graphs.get(gkey)
-            if ent is not None:
-                self._graphs.move_to_end(gkey)
-                ent[0].replay()
-            elif gkey not in self._seen:
-                # first sighting of these addresses: plain eager enqueue, no device synchronisation, nothing retained.  An
-                # input pipeline that hands over fresh tensors every batch never gets past this branch (its steps run
-                # eagerly, ~0.15 ms of host time each); one that cycles staging buffers is captured on the next round
-                enqueue_all()
-                self._seen[gkey] = True
-                if len(self._seen) > 8 * self.MAX_GRAPHS:
-                    self._seen.popitem(last=False)
-            else:
-                # second sighting: enqueued eagerly -- that IS this call's work -- and then captured, without running, for
-                # the calls to come.  (With an optimizer in the step a warm-up followed by a replay would apply the update
-                # twice.)
-                enqueue_all()
-                torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, capture_error_mode=CAPTURE_MODE):
-                    enqueue_all()
-                self._graphs[gkey] = (g, seq, then_cols)         # the inputs stay alive as long as the graph does
-                del self._seen[gkey]
-                while len(self._graphs) > self.MAX_GRAPHS:
-                    self._graphs.popitem(last=False)             # least recently used: graph and retained inputs go
-        self.t = t_base + n
+
+    def _enqueue(self, seq, bufs, inline, then_cols, then_bufs, t_base):
+        main = torch.cuda.current_stream()
+        st = C.c_void_p(main.cuda_stream)
+        for i in inline:                                         # not announced: sorted in line
+            self._sort(seq[i][0], bufs[i], main)
+        for i, (cols, y) in enumerate(seq):
+            self._row = i
+            self._launch_main(cols, y, st, bufs[i])
+            t = t_base + i + 1                                   # 1-based step (host scalar of the non-graphed optimizers)
+            self._launch_post(bufs[i], st, t)
+            if self.optimizer is not None:
+                self._optimizer(t, st)
+        # the plans of the batches announced for the NEXT call: GROUP batches (consecutive buffers) per sort launch, on the
+        # main stream BEHIND this call's steps.  (They used to run on a second stream beside the steps -- but a sort
+        # workgroup cannot share a CU with a fused-kernel workgroup (LDS), so "beside" meant that one fused launch in
+        # eight waited for the sort: serial on one stream is 0.7 us per step faster at K = 200, the same at K = 20, and
+        # the graph has no fork / join.)
+        m_ = len(then_cols)
+        if m_:
+            nl = -(-m_ // self.GROUP)                            # as few launches as the column limit allows, evenly filled
+            per = -(-m_ // nl)
+            for j in range(0, m_, per):
+                self._sort_group(then_cols[j:j + per], then_bufs[j], main)
+
+    def _after_call(self, n, bufs):
         self.loss = self.loss_steps[n - 1:n]                     # the last step's
         if self.prob_steps is not None:
             self.prob = self.prob_steps[n - 1]
-        self._prefetched = dict(zip(then_keys, then_bufs))
-        self._half = 1 - cur_half if then_cols else cur_half
-        return self.loss
 
     def flush(self):
         """optimizer 'keras_adam_lazy': bring EVERY row of the tables up to the current step (the dense sweeps the rows
@@ -734,7 +798,8 @@ class DeepFMFusedStep:
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         check(lib.rec_adam_keras_flush_f32(_p(emb), emb.stride(0), self.V, _p(me), _p(ve), me.stride(0), _p(mw), _p(vw),
                                            mw.stride(0), _p(self._last), _p(self._step_dev), _p(self._lr_tab),
-                                           self._lr_tab.numel(), 0.9, 0.999, 1e-7, st), "rec_adam_keras_flush_f32")
+                                           self._lr_tab.numel(), ADAM_B1, ADAM_B2, ADAM_EPS, st),
+              "rec_adam_keras_flush_f32")
 
     def release(self):
         """Give up the optimizer state kept in the layer's table padding (lazy optimizers) and the captured graphs, so
@@ -742,8 +807,7 @@ class DeepFMFusedStep:
         owner = getattr(self.layer, "_fused_state_owner", None)
         if owner is not None and owner() is self:
             self.layer._fused_state_owner = None
-        self._graphs.clear()
-        self._seen.clear()
+        super().release()
 
     def check_flags(self):
         if int(self.oob.item()) != 0:
@@ -758,13 +822,13 @@ class DeepFMFusedStep:
         return out
 
 
-class DSSMFusedStep:
+class DSSMFusedStep(_FusedStep):
     """train_loop iteration of DSSMTwoTowerRetrievalLayer (2.FM/CustomLayers.py:208-239 under 2.FM/ModelManager.py:
     171-177) in two launches on the main stream: the fused kernel (csrc/dssm_fused.hip: gather, both tower MLPs, score,
     Keras BCE and the whole backward) and the post launch (fixed-order reduction of its partials side by side with the
     segment sums of both towers' gradient rows).  The de-duplication plans (rec_dedup_plan_i64 of each tower's flat
-    [B*F] ids) of the batches announced for the next call are built behind the steps of this call.  Graph policy, plan
-    prefetch and method names are those of DeepFMFusedStep.
+    [B*F] ids) of the batches announced for the next call are built behind the steps of this call.  Call forms, plan
+    ring and graph policy: _FusedStep.
 
     Requirements (checked; otherwise keep GraphedTrainStep, raises NotImplementedError): plain (unsharded) tables with
     the same embedding_dims E in {8, 16, 32, 64} in both towers, mlp_dims [64, 32], final_dim 8, 1 <= F <= 8 features
@@ -772,8 +836,6 @@ class DSSMFusedStep:
     parameters, step size on the device, so it is captured with the step; NOT the reference's dense-sweep semantics).
     """
 
-    NBUF = 64           # plan buffers: two halves of 32, many() alternates between them
-    MAX_GRAPHS = 64     # captured hipGraphs kept (least recently used beyond that are dropped with the inputs they hold)
     DENSE = ("mlp.kernel_0", "mlp.bias_0", "mlp.kernel_1", "mlp.bias_1", "final.kernel_0", "final.bias_0")
 
     def __init__(self, layer, batch_size, optimizer=None, lr=1e-3, use_graph=True, want_outputs=False):
@@ -853,27 +915,22 @@ class DSSMFusedStep:
         self.dedup_ws_bytes = lib.rec_dedup_workspace_bytes(max(nu, ni))
         self.dedup_ws = torch.empty(self.dedup_ws_bytes, dtype=torch.uint8, device=dev)
         self._last_buf = 0
-        self._prefetched, self._half = {}, 0
-        self._col_cache = {}
+        # a batch's columns: the user tower's features, then the item tower's
+        super().__init__([n for tw in self.towers for n in tw.feature_names])
         if optimizer is not None:
             self.state = {name: (torch.zeros(p.shape, **f32), torch.zeros(p.shape, **f32))
                           for name, p in params.items()}
-            N = 32768
-            tab = [lib.rec_adam_lr_t_f32(lr, 0.9, 0.999, t) for t in range(1, N + 1)]
-            self._lr_tab = torch.tensor(tab, **f32)
-            self._step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
-            self._lr_t_dev = torch.zeros(1, **f32)
-        import collections
-        self._graphs = collections.OrderedDict()            # gkey -> (graph, inputs kept alive), LRU order
-        self._seen = collections.OrderedDict()              # gkeys enqueued eagerly once (addresses only)
+            self._init_device_adam(self.names)
 
     # ---- plans
-    def _plan(self, cols_uv, buf, st):
-        """rec_index_pack_i64 + rec_dedup_plan_i64 of both towers' ids into plan buffer ``buf``."""
-        for t, cols in enumerate(cols_uv):
+    def _plan(self, cols, buf, st):
+        """rec_index_pack_i64 + rec_dedup_plan_i64 of both towers' ids (``cols``: user columns, then item columns) into
+        plan buffer ``buf``."""
+        Fu = self.F[0]
+        for t, tcols in enumerate((cols[:Fu], cols[Fu:])):
             F, pl = self.F[t], self.plans[t]
             n = self.B * F
-            arr = (C.c_void_p * F)(*[c.data_ptr() for c in cols])
+            arr = (C.c_void_p * F)(*[c.data_ptr() for c in tcols])
             ids = pl["ids"][buf]
             check(lib.rec_index_pack_i64(arr, F, self.B, _p(ids), F, 0, st), "rec_index_pack_i64")
             check(lib.rec_dedup_plan_i64(_p(ids), n, self.V[t], _p(pl["uniq"][buf]), _p(pl["seg"][buf]),
@@ -910,136 +967,25 @@ class DSSMFusedStep:
             _p(self.rows[0]),
             _p(self.vals[1]), _p(pi["perm"][buf]), _p(pi["seg"][buf]), _p(pi["uniq"][buf]), _p(pi["nu"][buf]),
             _p(self.rows[1]),
-            adam, tu.stride(0), self.V[0], ti.stride(0), self.V[1], lr_t, 0.9, 0.999, 1e-7, st), "rec_dssm_fused_post_f32")
+            adam, tu.stride(0), self.V[0], ti.stride(0), self.V[1], lr_t, ADAM_B1, ADAM_B2, ADAM_EPS, st),
+            "rec_dssm_fused_post_f32")
         if self.optimizer is not None:
-            params = dict(self.layer.named_parameters())
-            k = len(self.names)
-            arr = lambda xs: (C.c_void_p * k)(*[x.data_ptr() for x in xs])  # noqa: E731
-            check(lib.rec_adam_dense_multi_f32(
-                k, arr([params[n] for n in self.names]), arr([self.state[n][0] for n in self.names]),
-                arr([self.state[n][1] for n in self.names]), self._g_arr,
-                (C.c_int64 * k)(*[self.g[n].numel() for n in self.names]), _p(self._lr_t_dev), 0.9, 0.999, 1e-7, st),
-                "rec_adam_dense_multi_f32")
+            self._adam_dense_dev(st)
 
-    # ---- inputs
-    def _cols(self, inputs):
-        out = []
-        for tw in self.towers:
-            cols = []
-            for name in tw.feature_names:
-                c = inputs[name]
-                if c.dtype != torch.int64 or not c.is_cuda or c.numel() != self.B or not c.is_contiguous():
-                    raise ValueError("feature %r must be a contiguous int64 CUDA tensor with %d ids" % (name, self.B))
-                cols.append(c)
-            out.append(cols)
-        return out
+    def _enqueue(self, seq, bufs, inline, then_cols, then_bufs, t_base):
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        for i in inline:                                         # not announced: planned in line
+            self._plan(seq[i][0], bufs[i], st)
+        for i, (_, y) in enumerate(seq):
+            self._row = i
+            self._launch_main(y, bufs[i], st)
+            self._launch_post(bufs[i], st)
+        for cols, b in zip(then_cols, then_bufs):                # the next call's plans, behind this call's steps
+            self._plan(cols, b, st)
 
-    def _cols_key(self, inputs):
-        ent = self._col_cache.get(id(inputs))
-        names = [n for tw in self.towers for n in tw.feature_names]
-        if ent is not None and ent[2] is inputs and tuple(id(inputs[n]) for n in names) == ent[3]:
-            return ent[0], ent[1]
-        cols = self._cols(inputs)
-        if len(self._col_cache) > 256:
-            self._col_cache.clear()
-        key = tuple(c.data_ptr() for cs in cols for c in cs)
-        self._col_cache[id(inputs)] = (cols, key, inputs, tuple(id(c) for cs in cols for c in cs))
-        return cols, key
-
-    def __call__(self, inputs, label_name="label", next_inputs=None):
-        """One train_loop iteration on `inputs`; ``next_inputs`` (optional): the batch of the NEXT call, whose plans are
-        built behind this call's step."""
-        return self.many([inputs], label_name, then=next_inputs)
-
-    def many(self, batches, label_name="label", then=None):
-        """len(batches) <= 32 consecutive train_loop iterations; with ``use_graph`` as ONE hipGraph replay (captured at the
-        second sighting of the same input addresses, enqueued eagerly at the first).  ``then``: the batch, or list of
-        batches, of the NEXT call -- their plans are built behind this call's steps.  A batch of this call that no
-        earlier call announced is planned in line.  Returns the last step's loss (device scalar); ``loss_steps[i]`` holds
-        step i's."""
-        half = self.NBUF // 2
-        if then is None:
-            then_list = []
-        elif isinstance(then, dict):
-            then_list = [then]
-        else:
-            then_list = list(then)
-        if not 1 <= len(batches) <= half or len(then_list) > half:
-            raise ValueError("many(): 1 to %d batches per call (and at most %d per announcement)" % (half, half))
-        seq, keys = [], []
-        for b in batches:
-            cols, key = self._cols_key(b)
-            y = b[label_name]
-            if y.dtype != torch.float32 or not y.is_cuda or y.numel() != self.B or not y.is_contiguous():
-                raise ValueError("label must be a contiguous float32 CUDA tensor with %d entries" % self.B)
-            seq.append((cols, y))
-            keys.append(key)
-        then_cols, then_keys = [], []
-        for b in then_list:
-            cols, key = self._cols_key(b)
-            then_cols.append(cols)
-            then_keys.append(key)
-        n = len(seq)
-        cur_half = self._half
-        pre = self._prefetched
-        used = set(pre[k] for k in keys if k in pre)
-        free = [cur_half * half + j for j in range(half) if cur_half * half + j not in used]
-        bufs, inline = [], []
-        for i, k in enumerate(keys):
-            if k in pre and pre[k] not in bufs:
-                bufs.append(pre[k])
-            else:
-                bufs.append(free.pop(0))
-                inline.append(i)
-        other = (1 - cur_half) * half
-        then_bufs = [other + j for j in range(len(then_cols))]
-        gkey = (tuple(keys), tuple(y.data_ptr() for _, y in seq), tuple(then_keys), tuple(bufs), tuple(inline))
-
-        def enqueue_all():
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            for i in inline:                                     # not announced: planned in line
-                self._plan(seq[i][0], bufs[i], st)
-            for i in range(n):
-                self._row = i
-                self._launch_main(seq[i][1], bufs[i], st)
-                self._launch_post(bufs[i], st)
-            for cols, b in zip(then_cols, then_bufs):            # the next call's plans, behind this call's steps
-                self._plan(cols, b, st)
-
-        if not self.use_graph:
-            enqueue_all()
-        else:
-            ent = self._graphs.get(gkey)
-            if ent is not None:
-                self._graphs.move_to_end(gkey)
-                ent[0].replay()
-            elif gkey not in self._seen:
-                enqueue_all()                                    # first sighting: eager, nothing retained
-                self._seen[gkey] = True
-                if len(self._seen) > 8 * self.MAX_GRAPHS:
-                    self._seen.popitem(last=False)
-            else:
-                # second sighting: the eager enqueue IS this call's work; the capture (not run) serves the calls to come
-                enqueue_all()
-                torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, capture_error_mode=CAPTURE_MODE):
-                    enqueue_all()
-                self._graphs[gkey] = (g, seq, then_cols)         # the inputs stay alive as long as the graph does
-                del self._seen[gkey]
-                while len(self._graphs) > self.MAX_GRAPHS:
-                    self._graphs.popitem(last=False)
-        self.t += n
+    def _after_call(self, n, bufs):
         self._last_buf = bufs[n - 1]
         self.loss = self.loss_steps[n - 1]
-        self._prefetched = dict(zip(then_keys, then_bufs))
-        self._half = 1 - cur_half if then_cols else cur_half
-        return self.loss
-
-    def release(self):
-        """Drop the captured graphs (and the inputs they hold)."""
-        self._graphs.clear()
-        self._seen.clear()
 
     def check_flags(self):
         if int(self.oob.item()) != 0:
@@ -1081,15 +1027,14 @@ class HipStepBackend:
     per-plan pointer arrays are built at construction, nothing is allocated per step and nothing is read back."""
 
     def __init__(self, step, field_dims, field_offsets):
-        self.step = step
+        # the step owns its backend: a strong reference back would make the pair a reference cycle, which only the
+        # cyclic GC frees -- whenever it happens to run, in a process forked later (multiprocessing) too, where
+        # destroying the communicators, streams and graphs the step holds crashes the child
+        self.step = weakref.proxy(step)
         B, F, P, cap = step.B, step.F, step.P, step.cap
         dev = step.dev
         n = B * F
-        self.max_key = max(int(d) for d in field_dims) - 1
-        if _bits(self.max_key + 1) + _bits(B) > 32 or ((self.max_key << _bits(B)) | (B - 1)) >= 0xFFFFFFFF:
-            raise NotImplementedError("field too wide for the 32-bit sort words at this batch size")
-        if any(field_offsets[i] >= field_offsets[i + 1] for i in range(F - 1)):
-            raise ValueError("field offsets must be ascending (DataGenerator contract)")
+        self.max_key = _deepfm_fused_limits(B, field_dims, field_offsets, sort_words=True)
         f32 = dict(dtype=torch.float32, device=dev)
         i32 = dict(dtype=torch.int32, device=dev)
         i64 = dict(dtype=torch.int64, device=dev)
@@ -1294,11 +1239,8 @@ class ShardedDeepFMStep:
         self.B = B = int(batch_size)
         self.F = F = len(layer.feature_names)
         emb, w = layer.embed.embeddings, layer.w.embeddings
-        V, E = emb.shape
-        if E != 16 or list(layer.mlp_dims) != [32, 8]:
-            raise NotImplementedError("sharded step: embedding_dims=16, mlp_dims=[32,8]")
-        if F > 28 or B > 16384 or len(field_dims) != F or len(field_offsets) != F:
-            raise NotImplementedError("sharded step: F <= 28, B <= 16384, one (dim, offset) per feature")
+        V = emb.shape[0]
+        _deepfm_fused_limits(B, field_dims, field_offsets, layer)
         fused = getattr(layer, "_fused_storage", None)      # [V,32] rows = [embed | w | pad] (layers._FMTables)
         if fused is None:                                   # layer not on the GPU (CPU exchange-logic test)
             fused = torch.zeros((V, 32), dtype=torch.float32, device=emb.device)
@@ -1340,45 +1282,9 @@ class ShardedDeepFMStep:
         self.loss = views.pop("loss")
         self.g = views
         self.be = (backend or HipStepBackend)(self, field_dims, field_offsets)
+        self._reader = _BatchReader(layer.feature_names, B, cuda=isinstance(self.be, HipStepBackend))
         self._next = None               # (key, buffer, plan) announced by the previous call
         self.table_grad = None          # (local uniq ids, embed rows [.,16], w rows [.,1], n_uniq) after a step
-
-    def _cols(self, inputs):
-        cols = []
-        on_gpu = isinstance(self.be, HipStepBackend)          # the kernels take raw device pointers
-        for name in self.layer.feature_names:
-            c = inputs[name]
-            if c.dtype != torch.int64 or c.numel() != self.B or not c.is_contiguous() or (on_gpu and not c.is_cuda):
-                raise ValueError("feature %r must be a contiguous int64 %stensor with %d ids"
-                                 % (name, "CUDA " if on_gpu else "", self.B))
-            cols.append(c)
-        return cols
-
-    def _label(self, inputs, label_name):
-        y = inputs[label_name]
-        on_gpu = isinstance(self.be, HipStepBackend)
-        if y.dtype != torch.float32 or y.numel() != self.B or not y.is_contiguous() or (on_gpu and not y.is_cuda):
-            raise ValueError("label must be a contiguous float32 %stensor with %d entries" % ("CUDA " if on_gpu else "", self.B))
-        return y
-
-    def _cols_key(self, inputs):
-        """(columns, their addresses) of a batch; validated once per batch dict (the host is the bottleneck of the eager
-        step: 26 dtype / size / stride checks per call were a tenth of it) and again whenever a tensor of the dict was
-        replaced (identity of the tensor objects, as in DeepFMFusedStep._cols_key)."""
-        cache = self.__dict__.setdefault("_col_cache", {})
-        getter = self.__dict__.get("_getter")
-        if getter is None:
-            import operator
-            names_ = list(self.layer.feature_names)
-            getter = self._getter = (operator.itemgetter(*names_) if len(names_) > 1
-                                     else (lambda d, n=names_[0]: (d[n],)))
-        ent = cache.get(id(inputs))
-        if ent is None or ent[2] is not inputs or tuple(map(id, getter(inputs))) != ent[3]:
-            cols = self._cols(inputs)
-            if len(cache) > 256:
-                cache.clear()
-            ent = cache[id(inputs)] = (cols, tuple(c.data_ptr() for c in cols), inputs, tuple(map(id, cols)))
-        return ent[0], ent[1]
 
     def _plan(self, cols, buf, on_side):
         """Plan + C1 + the owner's union of what arrived: everything that depends on the ids alone."""
@@ -1390,8 +1296,8 @@ class ShardedDeepFMStep:
     def __call__(self, inputs, label_name="label", next_inputs=None):
         be, comm = self.be, self.comm
         be.begin()
-        cols, key = self._cols_key(inputs)
-        y = self._label(inputs, label_name)
+        cols, key = self._reader.cols_key(inputs)
+        y = self._reader.label(inputs, label_name)
         if self._next is not None and self._next[0] == key:
             _, buf, pl = self._next
             be.join()                                        # the plan was built on the second stream
@@ -1400,7 +1306,7 @@ class ShardedDeepFMStep:
             pl = self._plan(cols, buf, False)
         self._next = None
         if next_inputs is not None:
-            next_cols, next_key = self._cols_key(next_inputs)
+            next_cols, next_key = self._reader.cols_key(next_inputs)
             be.fork()
             with be.side_context():                          # C1 of the next batch: own communicator, second stream
                 nxt = self._plan(next_cols, 1 - buf, True)
@@ -1428,8 +1334,8 @@ class ShardedDeepFMStep:
         has constant sizes and nothing is read back, so the sequence is a fixed program).  The plan of the first batch
         is built inside the graph on the main stream, the plans of the following ones on the second stream beside the
         step before.  Every rank must call it with the same number of batches.  Returns the loss of the last step."""
-        key = (tuple(self._cols_key(b)[1] for b in batches) +
-               tuple(self._label(b, label_name).data_ptr() for b in batches))     # every column and label address
+        key = (tuple(self._reader.cols_key(b)[1] for b in batches) +
+               tuple(self._reader.label(b, label_name).data_ptr() for b in batches))     # every column and label address
         graphs = self.__dict__.setdefault("_graphs", {})
         g = graphs.get(key)
         if g is None:
@@ -1445,8 +1351,8 @@ class ShardedDeepFMStep:
                 # steps is needed), each followed by its C1 and the owner's merge; step i waits for plan i alone
                 be, comm = self.be, self.comm
                 be.begin()
-                colss = [self._cols_key(b)[0] for b in batches]
-                ys = [self._label(b, label_name) for b in batches]
+                colss = [self._reader.cols_key(b)[0] for b in batches]
+                ys = [self._reader.label(b, label_name) for b in batches]
                 be.fork()
                 evs = []
                 with be.side_context():

@@ -349,6 +349,54 @@ def test_fused_step_notices_a_replaced_column():
     assert close(rows.cpu().numpy()[:nu], ref["embed.embeddings"][touched])
 
 
+def test_steps_refuse_an_empty_call_and_a_strided_label():
+    """many([]) is refused before anything is enqueued; a strided label (a column of a [B, 2] tensor) is refused by
+    every step, whose BCE kernels read the label as a contiguous array."""
+    from explicit_tf2_recommendation_amd import engine, data
+    B, F, V = 256, 5, 5547
+    layer, names, gen = make16(B, F, V, 37, "zipf")
+    fused = engine.DeepFMFusedStep(layer, B, gen.dims, gen.offsets, use_graph=True)
+    with pytest.raises(ValueError):
+        fused.many([])
+    assert fused.t == 0
+    batch = data.to_device(gen.batch(B))
+    y2 = torch.zeros((B, 2), dtype=torch.float32, device="cuda")
+    y2[:, 0] = batch["label"].reshape(-1)
+    strided = dict(batch, label=y2[:, 0])
+    generic = engine.DeepFMTrainStep(layer, B, optimizer=None, use_graph=False)
+    for step in (generic, fused):
+        with pytest.raises(ValueError, match="contiguous"):
+            step(strided)
+    assert abs(generic(batch).item() - fused(batch).item()) <= 1e-5
+
+
+def test_steps_are_freed_by_reference_counting():
+    """A step holds captured graphs, streams and communicators: it must be freed when its last reference goes.  Left
+    in a reference cycle for the cyclic GC, it may be destroyed in a process forked later (multiprocessing's default
+    start method on Linux), where that crashes the child."""
+    import gc
+    import types
+    import weakref
+    from explicit_tf2_recommendation_amd import engine, data
+    B, F, V = 256, 5, 5547
+    layer, names, gen = make16(B, F, V, 41, "zipf")
+    batches = [data.to_device(gen.batch(B)) for _ in range(2)]
+    gc.collect()
+    gc.disable()
+    try:
+        fused = engine.DeepFMFusedStep(layer, B, gen.dims, gen.offsets, use_graph=True)
+        for _ in range(5):                                   # the plan ring alternates: two call keys, each captured
+            fused.many(batches, then=batches)
+        assert len(fused._graphs) >= 1
+        sh = engine.ShardedDeepFMStep(layer, B, gen.dims, gen.offsets, comm=types.SimpleNamespace(world=1, rank=0))
+        torch.cuda.synchronize()
+        refs = [weakref.ref(fused), weakref.ref(sh), weakref.ref(sh.be)]
+        del fused, sh
+        assert [r() is None for r in refs] == [True, True, True]
+    finally:
+        gc.enable()
+
+
 def test_fused_step_flags_contract_violation():
     from explicit_tf2_recommendation_amd import engine, data
     B, F, V = 256, 5, 5547
