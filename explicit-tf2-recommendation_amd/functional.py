@@ -486,3 +486,22 @@ class FFM(torch.autograd.Function):
         g_v = SparseRowGrad(plan.uniq_ids, rows, plan.n_uniq, (V, F, E)).to_sparse()
         g_w = _sparse_grad(plan, gz.reshape(B, 1), 1, (V, 1), row_div=F)
         return g_v, g_w, ops.colsum(gz.reshape(B, 1)), None, None
+
+
+class CIN(torch.autograd.Function):
+    """CINLayer (3.DCN/CustomLayers.py:396-417): x0 [B,F,E], W_k (1, F*H_k, H_{k+1}) -> cin_part [B, sum H].  The
+    states X^1..X^L [B, sum H, E] are saved for the backward, which writes dx0 and every dW_k (csrc/cin.hip)."""
+
+    @staticmethod
+    def forward(ctx, x0, *Ws):
+        x0 = x0.contiguous()
+        Ws = [w.contiguous() for w in Ws]
+        cin_part, states = ops.cin_fwd(x0, Ws)
+        ctx.save_for_backward(x0, states, *Ws)
+        return cin_part
+
+    @staticmethod
+    def backward(ctx, g):
+        x0, states, *Ws = ctx.saved_tensors
+        dx0, dWs = ops.cin_bwd(x0, states, g.contiguous(), Ws)
+        return (dx0, *dWs)

@@ -11,6 +11,8 @@ libmi355rec.so (through functional.py / ops.py).  Reference classes and the line
   CrossLayer                    3.DCN/CustomLayers.py:170-203
   DeepCrossNetworkLayer         3.DCN/CustomLayers.py:206-269
   MatrixCrossLayer              3.DCN/CustomLayers.py:272-305
+  XDeepFMRankingLayer           3.DCN/CustomLayers.py:308-374
+  CINLayer                      3.DCN/CustomLayers.py:377-417
 
 Parameters are named after the TF checkpoint keys (``embed.embeddings``, ``w.embeddings``, ``bias``,
 ``MLP_layer1.kernel_0`` ...), so a TensorBundle checkpoint maps onto ``state_dict()`` by name.
@@ -475,6 +477,74 @@ class DeepCrossNetworkLayer(Layer):
         dnn_output = self.dense_layer(_input)
         combine_output = ConcatCols.apply(cross_output, dnn_output)
         return {"output": self.output_layer(combine_output)}
+
+
+class CINLayer(Layer):
+    """Compressed Interaction Network (3.DCN/CustomLayers.py:377-417): weights ``w0..w{L-1}`` of the reference's shape
+    (1, F*H_k, H_{k+1}) (H_0 = F), glorot-uniform, no bias, no activation.  Built from the first input's field count
+    (or ``input_dim=F``); forward and backward are the fp32-MFMA kernels of csrc/cin.hip.  The l1_l2 regulariser of the
+    reference never reaches its loss and is not applied."""
+
+    def __init__(self, cin_size=[8, 16], input_dim=None):
+        super().__init__()
+        self.cin_size = [int(h) for h in cin_size]
+        self.built = False
+        if input_dim is not None:
+            self.build(input_dim)
+
+    def build(self, F):
+        F = int(F)
+        self.field_num = [F] + self.cin_size
+        for i in range(len(self.cin_size)):
+            a, b = self.field_num[0] * self.field_num[i], self.field_num[i + 1]
+            self.register_parameter("w%d" % i, torch.nn.Parameter(_uniform((1, a, b), math.sqrt(6.0 / (a + b)))))
+        self.built = True
+
+    def forward(self, inputs, **kwargs):
+        if not self.built:
+            self.build(inputs.shape[1])
+            self.to(inputs.device)
+        ops.cin_check_shape(inputs.shape[1], inputs.shape[2], self.cin_size)
+        return Fn.CIN.apply(inputs, *[getattr(self, "w%d" % i) for i in range(len(self.cin_size))])
+
+
+class XDeepFMRankingLayer(Layer):
+    """3.DCN/CustomLayers.py:308-374: output = Dense(1, sigmoid)(concat[linear_part, dense_part, cin_part]) with
+    linear_part = sum_f w[X_f], dense_part = DenseLayer(units, activation)(concat[X_cont, Flatten(X0)]) and
+    cin_part = CINLayer(cin_size)(X0), X0 = embedding_layer(X_cate).  The "l2" / l1_l2 regularisers are kept for the
+    signature and never reach the loss (3.DCN/ModelManager.py trains on the BCE alone)."""
+
+    def __init__(self, categorical_features=["uid", "iid", "utag1", "utag2", "utag3", "utag4", "itag1", "itag2",
+                                             "itag3", "itag4"],
+                 continuous_features=["itag4_origin", "itag4_square", "itag4_cube"], feature_dims=160000,
+                 embedding_dims=16, units=[64, 8], activation="relu", cin_size=[16, 32, 64]):
+        super().__init__()
+        self.categorical_features = list(categorical_features)
+        self.continuous_features = list(continuous_features)
+        F = len(self.categorical_features)
+        ops.cin_check_shape(F, embedding_dims, cin_size)
+        self.w = Embedding(feature_dims, 1, embeddings_regularizer="l2")
+        self.dense_layer = DenseLayer(units, activation, input_dim=len(self.continuous_features) + F * embedding_dims)
+        self.embedding_layer = Embedding(feature_dims, embedding_dims)
+        self.cin_layer = CINLayer(cin_size, input_dim=F)
+        self.output_layer = Dense(1, activation="sigmoid", input_dim=1 + list(units)[-1] + sum(cin_size))
+        # linear_part = w_rows [B,F] . ones [F,1] on the GEMM kernel (reduce_sum over the fields)
+        self.register_buffer("_field_ones", torch.ones((F, 1)), persistent=False)
+
+    def forward(self, inputs):
+        X = assemble_index(inputs, self.categorical_features)
+        B, F = X.shape
+        flag = ops.new_flag(X.device) if self.check_ids else None
+        w_rows = self.w(X, flag)                                        # [B,F,1]
+        X_emb = self.embedding_layer(X, flag)                           # [B,F,E]
+        self._raise_if_oob(flag)
+        linear_part = Fn.LinearAct.apply(w_rows.reshape(B, F), self._field_ones, None, ops.ACT_NONE)
+        cont = _cont_block(inputs, self.continuous_features, X.device)
+        dense_input = ConcatCols.apply(*cont, X_emb.reshape(B, -1))     # continuous FIRST (:357)
+        dense_part = self.dense_layer(dense_input)
+        cin_part = self.cin_layer(X_emb)
+        output = self.output_layer(ConcatCols.apply(linear_part, dense_part, cin_part))
+        return {"output": output}
 
 
 # ---------------------------------------------------------------------------------------------------

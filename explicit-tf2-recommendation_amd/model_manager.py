@@ -159,6 +159,12 @@ class ModelManager:
             p.setdefault("continuous_features", self.continuous_features)
             self.layer = CL.DeepCrossNetworkLayer(feature_dims=self.feature_dims, embedding_dims=self.embedding_dims,
                                                   **p)
+        elif layer_name == "xDeepFM":                      # 3.DCN/ModelManager.py:72-74
+            p = {k: v for k, v in model_params.items() if k in ("units", "activation")}
+            self.layer = CL.XDeepFMRankingLayer(
+                categorical_features=self.feature_names, continuous_features=self.continuous_features,
+                feature_dims=self.feature_dims, embedding_dims=self.embedding_dims, cin_size=model_params["cin_size"],
+                **p)
         elif layer_name == "din_layer":                    # 5.DIN/ModelManager.py:72-73
             p = dict(model_params)
             p.setdefault("feature_dims", self.feature_dims)

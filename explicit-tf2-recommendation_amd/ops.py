@@ -595,3 +595,56 @@ def ffm_bwd_rows(v, X, gz, plan):
     check(lib.rec_ffm_bwd_rows_f32(_ptr(v), F * E, V, E, _ptr(X), B, F, _ptr(gz), _ptr(plan.perm), _ptr(plan.seg_start),
                                    _ptr(plan.n_uniq), _ptr(rows), _stream()), "rec_ffm_bwd_rows_f32")
     return rows
+
+
+# ---- xDeepFM CIN (csrc/cin.hip)
+CIN_MAX_F, CIN_MAX_E, CIN_MAX_L, CIN_MAX_H = 64, 64, 8, 256
+
+
+def cin_check_shape(F, E, cin_size):
+    """NotImplementedError for shapes the CIN kernels do not cover (the ABI would return -2)."""
+    L = len(cin_size)
+    if not (1 <= F <= CIN_MAX_F and 1 <= E <= CIN_MAX_E and 1 <= L <= CIN_MAX_L
+            and all(1 <= int(h) <= CIN_MAX_H for h in cin_size)):
+        raise NotImplementedError(
+            "CIN kernels cover 1 <= fields <= %d, 1 <= embedding_dims <= %d, 1 <= len(cin_size) <= %d and "
+            "1 <= cin_size[k] <= %d; got fields=%d, embedding_dims=%d, cin_size=%s"
+            % (CIN_MAX_F, CIN_MAX_E, CIN_MAX_L, CIN_MAX_H, F, E, list(cin_size)))
+
+
+def _cin_args(x0, Ws):
+    B, F, E = x0.shape
+    H = [int(w.shape[-1]) for w in Ws]
+    cin_check_shape(F, E, H)
+    Hh = (C.c_int * len(H))(*H)
+    Wh = (C.c_void_p * len(Ws))(*[_f32(w, "W%d" % k).data_ptr() for k, w in enumerate(Ws)])
+    return B, F, E, H, Hh, Wh
+
+
+def cin_fwd(x0, Ws):
+    """x0 [B,F,E], Ws: the L CIN weights (1, F*H_k, H_{k+1}) -> (cin_part [B, sum H], states [B, sum H, E])."""
+    _f32(x0, "x0")
+    B, F, E, H, Hh, Wh = _cin_args(x0, Ws)
+    SH = sum(H)
+    states = torch.empty((B, SH, E), dtype=torch.float32, device=x0.device)
+    cin_part = torch.empty((B, SH), dtype=torch.float32, device=x0.device)
+    check(lib.rec_cin_fwd_f32(_ptr(x0), B, F, E, len(H), Hh, Wh, _ptr(states), _ptr(cin_part), _stream()),
+          "rec_cin_fwd_f32")
+    return cin_part, states
+
+
+def cin_bwd(x0, states, g, Ws):
+    """-> (dx0 [B,F,E], [dW_k] shaped as Ws) from g = dLoss/dcin_part [B, sum H]."""
+    B, F, E, H, Hh, Wh = _cin_args(x0, Ws)
+    _f32(states, "states")
+    _f32(g, "g")
+    dx0 = torch.empty_like(x0)
+    dWs = [torch.empty_like(w) for w in Ws]
+    dWh = (C.c_void_p * len(dWs))(*[d.data_ptr() for d in dWs])
+    nbytes = lib.rec_cin_workspace_bytes(B, F, E, len(H), Hh)
+    if nbytes == 0:
+        raise NotImplementedError("rec_cin_workspace_bytes: unsupported CIN shape")
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x0.device)
+    check(lib.rec_cin_bwd_f32(_ptr(x0), _ptr(states), _ptr(g), B, F, E, len(H), Hh, Wh, _ptr(dx0), dWh, _ptr(ws), nbytes,
+                              _stream()), "rec_cin_bwd_f32")
+    return dx0, dWs

@@ -524,6 +524,22 @@ int rec_batchnorm_fwd_f32(const float* x, int64_t ld_x, int64_t B, int N, const 
 int rec_batchnorm_bwd_f32(const float* g, const float* xhat, const float* rstd, int64_t B, int N, const float* gamma,
                           int training, float* gx, float* ggamma, float* gbeta, void* workspace, void* stream);
 
+/* ---- Compressed Interaction Network of xDeepFM (CINLayer, 3.DCN/CustomLayers.py:377-417; csrc/cin.hip).
+ * x0 [B, F, E]; L layers of H_host[k] = cin_size[k] units; W_host: HOST array of L device pointers, W_k
+ * [F * H_k, H_{k+1}] row-major (the reference's (1, F*H_k, H_{k+1}) weight; H_0 = F, row m*H_k + n):
+ *   X^{k+1}[b,h,e] = sum_{m,n} W_k[m*H_k + n, h] * x0[b,m,e] * X^k[b,n,e]     (X^0 = x0)
+ *   cin_part [B, SH] = concat_k sum_e X^{k+1}[b,:,e]      states [B, SH, E] = concat_k X^{k+1}  (SH = sum H_k)
+ * The backward takes g = dLoss/dcin_part [B, SH] and writes dx0 [B, F, E] and every dW_k (dW_host: HOST array of L
+ * device pointers, shapes of W_k).  No float atomics: bit-identical results run to run.
+ * Supported: 1 <= F, E <= 64, 1 <= L <= 8, 1 <= H_k <= 256, B >= 1; otherwise -2 (an H_k < 1 or B < 1 is -1).
+ * workspace: rec_cin_workspace_bytes (0: invalid or unsupported shape). */
+size_t rec_cin_workspace_bytes(int64_t B, int F, int E, int L, const int* H_host);
+int rec_cin_fwd_f32(const float* x0, int64_t B, int F, int E, int L, const int* H_host, const float* const* W_host,
+                    float* states, float* cin_part, void* stream);
+int rec_cin_bwd_f32(const float* x0, const float* states, const float* g, int64_t B, int F, int E, int L,
+                    const int* H_host, const float* const* W_host, float* dx0, float* const* dW_host, void* workspace,
+                    size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
