@@ -79,6 +79,7 @@ SIGNATURES = {
     "rec_deepfm_fused_workspace_bytes": (sz, [i64, i32]),
     "rec_deepfm_fused_post_f32": (i32, [i32, i64] + [p] * 19 + [i32, p]),
     "rec_colsort_workspace_bytes": (sz, [i64, i32]),
+    "rec_colsort_digits": (i32, [i64, i64, p, p]),
     "rec_colsort_plan_i64": (i32, [p, i32, i64, i64, p, i64, p, p, p, p, p, p, p]),
     "rec_colsort_plan_dest_i64": (i32, [p, i32, i64, i64, p, i64, p, p, p, p, p, p, p, p]),
     "rec_deepfm_fused_post_direct_f32": (i32, [i32, i64] + [p] * 19 + [p]),

@@ -13,7 +13,7 @@ namespace {
 constexpr uint32_t PADW = 0xFFFFFFFFu;
 
 struct ColSortArgs {
-  int64_t B; int F; int64_t V; int key_bits; int pos_bits;
+  int64_t B; int F; int64_t V; int key_bits; int pos_bits; int passes; int digit_bits;
   int32_t* perm;        // [F][B]  sorted position -> example
   int64_t* col_uid;     // [F][B]  unique ids of the column, ascending (first col_nu[f] valid)
   int32_t* col_seg;     // [F][B+1] run starts in the column's sorted order (tail = B)
@@ -23,17 +23,24 @@ struct ColSortArgs {
 };
 
 // ------------------------------------------------------------------------------------------------
-// ONE kernel: one 1024-thread workgroup per column sorts the column's <= 16384 words in LDS (stable LSD radix sort on
-// the key bits, 7 bits per pass, in place: every key is in a register between the barrier that ends the reads and the
-// one that starts the writes) and goes straight on to the run heads.  (Round 1 ran a chunk-sort / rank-merge / heads
-// chain of three latency-bound launches on ~200 CUs: 65 us for the plans of four batches against 42 us here on
-// 4 x F workgroups of 37 KB of LDS.)
+// ONE kernel: one 1024-thread workgroup per column sorts the column's <= 16384 words in LDS and goes straight on to the
+// run heads.  Columns without a hot bucket take the bucket path below; the others a stable LSD radix sort on the key
+// bits in as few passes of at most 10 bits as cover the key (19-bit keys: 10 + 9), in place: every key is in a register
+// between the barrier that ends the reads and the one that starts the writes.  (Round 1 ran a chunk-sort / rank-merge /
+// heads chain of three latency-bound launches.)
 //   ranking: element e = wave*64*KPT + round*64 + lane, so (wave, round, lane) order is array order; lanes of equal
-//   digit are matched by 7 ballots, the lowest lane of a group bumps the wave's 16-bit counter of the digit (LDS
-//   operations of one wave complete in program order); a key's new place = digit base + counts of earlier waves + its
-//   rank in the wave.
+//   digit are matched by one ballot per digit bit, the lowest lane of a group adds the group's size to the wave's 32-bit
+//   counter of the digit with an LDS atomic that returns the old count, and the group reads that count from its lowest
+//   lane.  A wave's LDS operations complete in program order, so the KPT atomics of a pass go out back to back and are
+//   waited for once.  A key's new place = digit base + counts of earlier waves + its rank in the wave.
+//   (Round 3 ran 3 passes of 7 bits, each round of a pass a dependent read-modify-write of a 16-bit counter: 5.7 us per
+//   pass at B = 8192.)
 // ------------------------------------------------------------------------------------------------
-constexpr int OW_T = 1024, OW_W = OW_T / 64, OW_BINS = 128, OW_DB = 7;
+constexpr int CS_T = 1024, CS_W = CS_T / 64, CS_DB = 10, CS_BINS = 1 << CS_DB;
+// bucket path: 2^13 buckets of the top word bits (8 per thread), taken when no bucket holds more than CS_BIG words and
+// no round of 64 words has more than CS_PROBE in lane 0's bucket
+constexpr int CS_BKB = 13, CS_NBK = 1 << CS_BKB, CS_BIG = 32, CS_PROBE = 16;
+static_assert(CS_BINS == CS_T, "the count scan gives every thread one digit");
 
 #ifdef REC_SORT_STAMPS
 __device__ unsigned long long g_sort_stamps[256 * 16];
@@ -49,74 +56,189 @@ struct SortCols {
   const int64_t* p[SORT_MAX_COLS];
 };
 
+// radix passes of key_bits-bit keys: as few passes of at most CS_DB bits as cover the key, the bits spread evenly over
+// them (the last pass takes what is left)
+static inline void colsort_digits(int key_bits, int* passes, int* digit_bits) {
+  const int p = (key_bits + CS_DB - 1) / CS_DB;
+  *passes = p;
+  *digit_bits = (key_bits + p - 1) / p;
+}
+
 template <int KPT>
-__global__ __launch_bounds__(OW_T, 4) void colsort_onewg_kernel(SortCols cols, const int64_t* __restrict__ col_lo, ColSortArgs a) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t owl[];
-  constexpr int NW = OW_T * KPT;                       // padded word count
-  uint32_t* words = owl;                               // [NW]
-  unsigned short* cnt = reinterpret_cast<unsigned short*>(owl + NW);      // [OW_W][OW_BINS]
-  uint32_t* dbase = owl + NW + OW_W * OW_BINS / 2;     // [OW_BINS]
-  uint32_t* wtot = dbase + OW_BINS;                    // [OW_W] scratch of the block scans
+__global__ __launch_bounds__(CS_T, 4) void colsort_kernel(SortCols cols, const int64_t* __restrict__ col_lo, ColSortArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t sml[];
+  constexpr int NW = CS_T * KPT;                       // padded word count
+  uint32_t* words = sml;                               // [NW]
+  uint32_t* cnt = sml + NW;                            // [CS_W][CS_BINS] per-wave digit counts, then scatter bases
+  uint32_t* wtot = cnt + CS_W * CS_BINS;               // [CS_W] scratch of the block scans
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int f = blockIdx.x;
   const int64_t B = a.B;
   const int64_t lo = col_lo[f];
   const int pb = a.pos_bits;
   const uint32_t pmask = (1u << pb) - 1u;
-  // ---- load: word = (id - lo) << pos_bits | example; pad words sort last
+  uint32_t* wcnt = cnt + wave * CS_BINS;
+  const unsigned long long lt = (1ull << lane) - 1ull;
+  // ---- load straight into the ranking layout (e = wave*64*KPT + round*64 + lane): word = (id - lo) << pos_bits | example; pad words sort last
   SSTAMP(0);
+  uint32_t w[KPT];
   bool bad = false;
+  const int64_t* col = cols.p[f];
 #pragma unroll
   for (int r = 0; r < KPT; ++r) {
-    const int e = r * OW_T + tid;
-    uint32_t w = PADW;
+    const int e = wave * (64 * KPT) + r * 64 + lane;
+    w[r] = PADW;
     if (e < B) {
-      const int64_t id = cols.p[f][e];
+      const int64_t id = col[e];
       int64_t key = id - lo;
       if (key < 0 || key >= (int64_t(1) << a.key_bits) || (uint64_t)id >= (uint64_t)a.V) {
         bad = true;
         key = key < 0 ? 0 : (int64_t(1) << a.key_bits) - 1;
       }
-      w = ((uint32_t)key << pb) | (uint32_t)e;
+      w[r] = ((uint32_t)key << pb) | (uint32_t)e;
     }
-    words[e] = w;
   }
   if (bad && a.bad) *a.bad = 1;
   SSTAMP(1);
-  const unsigned long long lt = (1ull << lane) - 1ull;
-  int pass_ = 0;
-  // ---- radix passes over the key bits
-  for (int shift = pb; shift < pb + a.key_bits; shift += OW_DB) {
-    reinterpret_cast<uint32_t*>(cnt)[tid] = 0;         // OW_W*OW_BINS/2 = 1024 words
-    __syncthreads();
-    uint32_t w[KPT];
-    unsigned short loc[KPT];
+  // ---- bucket path: the words are unique, so ANY sort of the full word gives the one sorted order, stable or not.
+  // Count the words per bucket of their top CS_BKB bits (LDS atomics), scan, scatter every word to a slot of its
+  // bucket (atomic cursor: order inside a bucket arbitrary), then rank each word inside its bucket by counting the
+  // smaller words there.  Linear in the bucket size, so a column with a bucket of more than CS_BIG words (hot ids,
+  // narrow fields) takes the radix passes below instead.  Counts, then bucket starts, then (after the scatter) bucket
+  // ends live in the counter array: bucket b = [end of b - 1, end of b).
+  const int wbits = a.key_bits + pb;
+  const int bsh = wbits > CS_BKB ? wbits - CS_BKB : 0;
+  uint32_t* bk = cnt;                                  // [CS_NBK]
+  static_assert(CS_NBK == 8 * CS_T && CS_NBK <= CS_W * CS_BINS, "8 buckets per thread, inside the counters");
 #pragma unroll
-    for (int r = 0; r < KPT; ++r) w[r] = words[wave * (64 * KPT) + r * 64 + lane];
+  for (int i = 0; i < 2; ++i) reinterpret_cast<uint4*>(bk)[i * CS_T + tid] = make_uint4(0u, 0u, 0u, 0u);
+  // probe: more than CS_PROBE words of a round share lane 0's bucket -> a hot bucket.  Such a column takes the radix
+  // passes without counting (64 lanes adding to one LDS address serialise: Zipf heads cost 1.3 us more counting)
+  int hot = 0;
+#pragma unroll
+  for (int r = 0; r < KPT; ++r) {
+    const bool real = wave * (64 * KPT) + r * 64 + lane < B;
+    const uint32_t b0 = __shfl(w[r] >> bsh, 0, 64);
+    hot |= __popcll(__ballot(real && (w[r] >> bsh) == b0)) > CS_PROBE;
+  }
+  bool fast = !__syncthreads_or(hot);                 // (uniform over the workgroup, as every test below)
+  if (fast) {
+#pragma unroll
+    for (int r = 0; r < KPT; ++r)
+      if (wave * (64 * KPT) + r * 64 + lane < B) atomicAdd(&bk[w[r] >> bsh], 1u);
+    __syncthreads();
+    // thread tid: buckets 8 tid .. 8 tid + 7 -> exclusive starts (block scan), largest count
+    const uint4 q0 = reinterpret_cast<const uint4*>(bk)[2 * tid], q1 = reinterpret_cast<const uint4*>(bk)[2 * tid + 1];
+    uint32_t c[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
+    uint32_t run = 0, mx = 0;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      run += c[q];
+      mx = max(mx, c[q]);
+    }
+    uint32_t incl = run;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t t = __shfl_up(incl, o, 64);
+      if (lane >= o) incl += t;
+    }
+    if (lane == 63) wtot[wave] = incl;
+    __syncthreads();
+    uint32_t base = incl - run;
+#pragma unroll
+    for (int q = 0; q < CS_W; ++q)
+      if (q < wave) base += wtot[q];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const uint32_t n = c[q];
+      c[q] = base;
+      base += n;
+    }
+    reinterpret_cast<uint4*>(bk)[2 * tid] = make_uint4(c[0], c[1], c[2], c[3]);
+    reinterpret_cast<uint4*>(bk)[2 * tid + 1] = make_uint4(c[4], c[5], c[6], c[7]);
+    fast = !__syncthreads_or(mx > (uint32_t)CS_BIG);  // (also the barrier before the scatter)
+  }
+  SSTAMP(2);
+  if (fast) {
 #pragma unroll
     for (int r = 0; r < KPT; ++r) {
-      const uint32_t d = (w[r] >> shift) & (OW_BINS - 1);
-      unsigned long long m = ~0ull;
-#pragma unroll
-      for (int b = 0; b < OW_DB; ++b) {
-        const bool bit = (d >> b) & 1u;
-        const unsigned long long bal = __ballot(bit);
-        m &= bit ? bal : ~bal;
-      }
-      const unsigned short old = cnt[wave * OW_BINS + d];
-      if ((m & lt) == 0) cnt[wave * OW_BINS + d] = (unsigned short)(old + __popcll(m));
-      loc[r] = (unsigned short)(old + __popcll(m & lt));
+      const int e = wave * (64 * KPT) + r * 64 + lane;
+      if (e < B) words[atomicAdd(&bk[w[r] >> bsh], 1u)] = w[r];
+      else words[e] = PADW;                            // pads keep their places at the end
     }
-    __syncthreads();                                   // every word is in a register: the array may be overwritten
-    if (tid < OW_BINS) {                               // per digit: counts -> exclusive prefix over the waves, total
+    __syncthreads();
+    SSTAMP(3);
+    uint32_t dst[KPT];
+#pragma unroll
+    for (int r = 0; r < KPT; ++r) {
+      const int e = wave * (64 * KPT) + r * 64 + lane;
+      dst[r] = (uint32_t)e;
+      if (e < B) {
+        const uint32_t b = w[r] >> bsh;
+        const uint32_t end = bk[b];
+        uint32_t j = b > 0 ? bk[b - 1] : 0u, rk = j;
+        for (; j < end; ++j) rk += words[j] < w[r] ? 1u : 0u;
+        dst[r] = rk;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < KPT; ++r) words[dst[r]] = w[r];
+    __syncthreads();
+    SSTAMP(4);
+  }
+  // ---- radix passes over the key bits (columns the bucket path does not take)
+  for (int pass = 0; pass < (fast ? 0 : a.passes); ++pass) {
+    const int shift = pb + pass * a.digit_bits;
+    const int nb = min(a.digit_bits, a.key_bits - pass * a.digit_bits);    // digit bits of this pass
+    const uint32_t dmask = (1u << nb) - 1u;
+    if (pass > 0) {
+#pragma unroll
+      for (int r = 0; r < KPT; ++r) w[r] = words[wave * (64 * KPT) + r * 64 + lane];
+    }
+    // the wave's own counters (no other wave touches them before the barrier below)
+#pragma unroll
+    for (int i = 0; i < CS_BINS / 256; ++i) reinterpret_cast<uint4*>(wcnt)[i * 64 + lane] = make_uint4(0u, 0u, 0u, 0u);
+    // rank in the wave, 8 rounds at a time (KPT = 16 would not fit 128 VGPRs in one go)
+    uint32_t below[KPT];
+#pragma unroll
+    for (int c0 = 0; c0 < KPT; c0 += 8) {
+      // peers: lanes of the same round whose digit equals this lane's, one ballot per digit bit (rounds interleaved)
+      unsigned long long m[8];
+#pragma unroll
+      for (int r = 0; r < 8; ++r) m[r] = ~0ull;
+      for (int b = 0; b < nb; ++b) {
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+          // s = the bit as 0 / ~0 (one bit-field extract); a lane keeps the lanes whose ballot bit equals its own:
+          // m &= ~(bal ^ s) -- 6 VALU instructions per round and bit (extract, compare, xor and and-not per half)
+          const uint32_t s = (uint32_t)__builtin_amdgcn_sbfe((int)w[c0 + r], shift + b, 1);
+          const unsigned long long bal = __ballot(s != 0u);
+          m[r] &= ~(bal ^ (((unsigned long long)s << 32) | s));
+        }
+      }
+      uint32_t old[8];
+      int lead[8];
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        lead[r] = __ffsll((long long)m[r]) - 1;        // lowest lane of the group
+        below[c0 + r] = (uint32_t)__popcll(m[r] & lt);
+        old[r] = 0u;
+        if (below[c0 + r] == 0u) old[r] = atomicAdd(&wcnt[(w[c0 + r] >> shift) & dmask], (uint32_t)__popcll(m[r]));
+      }
+#pragma unroll
+      for (int r = 0; r < 8; ++r) below[c0 + r] += (uint32_t)__shfl((int)old[r], lead[r], 64);
+    }
+    __syncthreads();                                   // every word is in a register, every count is in
+    {
+      // digit tid: counts of the 16 waves -> exclusive prefix over the waves; block scan of the digit totals
+      uint32_t c[CS_W];
       uint32_t run = 0;
 #pragma unroll
-      for (int q = 0; q < OW_W; ++q) {
-        const uint32_t c = cnt[q * OW_BINS + tid];
-        cnt[q * OW_BINS + tid] = (unsigned short)run;
-        run += c;
+      for (int q = 0; q < CS_W; ++q) {
+        c[q] = cnt[q * CS_BINS + tid];
+        run += c[q];
       }
-      // exclusive scan of the 128 totals (two waves)
       uint32_t incl = run;
 #pragma unroll
       for (int o = 1; o < 64; o <<= 1) {
@@ -124,19 +246,22 @@ __global__ __launch_bounds__(OW_T, 4) void colsort_onewg_kernel(SortCols cols, c
         if (lane >= o) incl += v;
       }
       if (lane == 63) wtot[wave] = incl;
-      dbase[tid] = incl - run;                         // within the wave; wave 1 adds wave 0's total below
+      __syncthreads();
+      uint32_t base = incl - run;
+#pragma unroll
+      for (int q = 0; q < CS_W; ++q)
+        if (q < wave) base += wtot[q];
+#pragma unroll
+      for (int q = 0; q < CS_W; ++q) {
+        cnt[q * CS_BINS + tid] = base;                 // first place of (wave q, digit tid)
+        base += c[q];
+      }
     }
-    __syncthreads();
-    if (tid >= 64 && tid < OW_BINS) dbase[tid] += wtot[0];
     __syncthreads();
 #pragma unroll
-    for (int r = 0; r < KPT; ++r) {
-      const uint32_t d = (w[r] >> shift) & (OW_BINS - 1);
-      words[dbase[d] + cnt[wave * OW_BINS + d] + loc[r]] = w[r];
-    }
+    for (int r = 0; r < KPT; ++r) words[wcnt[(w[r] >> shift) & dmask] + below[r]] = w[r];
     __syncthreads();
-    SSTAMP(2 + pass_);
-    ++pass_;
+    SSTAMP(2 + pass);
   }
   // ---- run heads: thread t owns the KPT consecutive sorted positions from t*KPT
   const int s0 = tid * KPT;
@@ -161,20 +286,22 @@ __global__ __launch_bounds__(OW_T, 4) void colsort_onewg_kernel(SortCols cols, c
   if (lane == 63) wtot[wave] = (uint32_t)incl;
   __syncthreads();
   int woff = 0, all = 0;
-  for (int q = 0; q < OW_W; ++q) {
+  for (int q = 0; q < CS_W; ++q) {
     const int c = (int)wtot[q];
     if (q < wave) woff += c;
     all += c;
   }
   int rank = woff + incl - heads;
+  SSTAMP(7);
   // Outputs go through LDS and leave coalesced.  (Stored straight from the registers -- a lane owns 8 consecutive sorted
   // positions -- every wave instruction wrote 64 scattered 4- or 8-byte pieces: ~32 such instructions per wave on one
-  // address path, and the last wave finished 12 us after the first, 36 us into a kernel whose sort is done at 19.)
+  // address path.)
   //   st_uq [rank]    key of the run (aliases `words`: every thread holds its words in registers behind the barrier above)
-  //   st_sg [rank]    first sorted position of the run         (16 bit: B <= 16384)
+  //   st_sg [rank]    first sorted position of the run (16 bit: B <= 16384; aliases the counters, dead since the last pass)
   //   st_dl [example] run index | 0x8000 unless head of its run (16 bit)
+  static_assert(2 * sizeof(unsigned short) * NW <= sizeof(uint32_t) * CS_W * CS_BINS, "the staging fits the counters");
   uint32_t* st_uq = words;
-  unsigned short* st_sg = reinterpret_cast<unsigned short*>(wtot + OW_W);
+  unsigned short* st_sg = reinterpret_cast<unsigned short*>(cnt);
   unsigned short* st_dl = st_sg + NW;
   int32_t* permf = a.perm + (int64_t)f * B;
   if ((B & 7) == 0 && KPT == 8) {
@@ -205,7 +332,7 @@ __global__ __launch_bounds__(OW_T, 4) void colsort_onewg_kernel(SortCols cols, c
   __syncthreads();
 #pragma unroll
   for (int r = 0; r < KPT; ++r) {
-    const int i = r * OW_T + tid;
+    const int i = r * CS_T + tid;
     if (i < B) {
       if (a.dloc) {
         const uint32_t d = st_dl[i];
@@ -229,6 +356,21 @@ __global__ __launch_bounds__(OW_T, 4) void colsort_onewg_kernel(SortCols cols, c
   if (threadIdx.x == 512) g_sort_stamps[blockIdx.x * 16 + 11] = wall_clock64();
 #endif
 }
+
+// key and position bits of the sort words: REC_OK, or the status the plan calls return
+static int colsort_widths(int64_t B, int64_t max_key, int* key_bits, int* pos_bits) {
+  if (B <= 0 || max_key < 0) return REC_E_ARG;
+  if (B > 16384) return REC_E_UNSUPPORTED;
+  int pbits = 1, kbits = 1;
+  while ((int64_t(1) << pbits) < B) ++pbits;
+  while ((int64_t(1) << kbits) <= max_key) ++kbits;
+  if (kbits + pbits > 32) return REC_E_UNSUPPORTED;
+  // the pad word 0xFFFFFFFF must be larger than every real (key, position) word
+  if ((((uint64_t)max_key << pbits) | (uint64_t)(B - 1)) >= 0xFFFFFFFFull) return REC_E_UNSUPPORTED;
+  *key_bits = kbits;
+  *pos_bits = pbits;
+  return REC_OK;
+}
 }  // namespace
 
 #ifdef REC_SORT_STAMPS
@@ -241,48 +383,48 @@ extern "C" size_t rec_colsort_workspace_bytes(int64_t B, int F) {
   return 256;      // the sort runs in LDS; the argument is kept for callers written against the three-kernel version
 }
 
+extern "C" int rec_colsort_digits(int64_t B, int64_t max_key, int* passes, int* digit_bits) {
+  if (!passes || !digit_bits) return REC_E_ARG;
+  int key_bits = 0, pos_bits = 0;
+  const int rc = colsort_widths(B, max_key, &key_bits, &pos_bits);
+  if (rc != REC_OK) return rc;
+  colsort_digits(key_bits, passes, digit_bits);
+  return REC_OK;
+}
+
 static int colsort_plan(const int64_t* const* cols_host, int F, int64_t B, int64_t V, const int64_t* col_lo,
                         int64_t max_key, int32_t* perm, int64_t* col_uid, int32_t* col_seg, int32_t* col_nu,
                         int32_t* dloc, int* bad_flag, void* workspace, void* stream) {
   if (!cols_host || !col_lo || !perm || !col_uid || !col_seg || !col_nu || !workspace || F <= 0 || B <= 0 || V <= 0 ||
       max_key < 0)
     return REC_E_ARG;
-  if (F > SORT_MAX_COLS || B > 16384) return REC_E_UNSUPPORTED;
-  int pos_bits = 1, key_bits = 1;
-  while ((int64_t(1) << pos_bits) < B) ++pos_bits;
-  while ((int64_t(1) << key_bits) <= max_key) ++key_bits;
-  if (key_bits + pos_bits > 32) return REC_E_UNSUPPORTED;
-  // the pad word 0xFFFFFFFF must be larger than every real (key, position) word
-  if ((((uint64_t)max_key << pos_bits) | (uint64_t)(B - 1)) >= 0xFFFFFFFFull) return REC_E_UNSUPPORTED;
+  if (F > SORT_MAX_COLS) return REC_E_UNSUPPORTED;
+  int key_bits = 0, pos_bits = 0;
+  const int rc = colsort_widths(B, max_key, &key_bits, &pos_bits);
+  if (rc != REC_OK) return rc;
+  int passes = 0, digit_bits = 0;
+  colsort_digits(key_bits, &passes, &digit_bits);
   SortCols cp;
   for (int f = 0; f < F; ++f) {
     if (!cols_host[f]) return REC_E_ARG;
     cp.p[f] = cols_host[f];
   }
-  ColSortArgs a{B, F, V, key_bits, pos_bits, perm, col_uid, col_seg, col_nu, bad_flag, dloc};
+  ColSortArgs a{B, F, V, key_bits, pos_bits, passes, digit_bits, perm, col_uid, col_seg, col_nu, bad_flag, dloc};
   hipStream_t st = as_stream(stream);
-  // one workgroup per column (LDS radix sort + run heads in one launch); columns longer than 16 x 1024 do not occur
-  // (B <= 16384)
-  {
-    const int kpt = B <= 8192 ? 8 : 16;
-    // words + counters + the 16-bit staging arrays of the outputs (st_sg, st_dl)
-    const size_t lds = sizeof(uint32_t) * ((size_t)OW_T * kpt + OW_W * OW_BINS / 2 + OW_BINS + OW_W) +
-                       2 * sizeof(unsigned short) * (size_t)OW_T * kpt;
-    hipError_t e;
-    if (kpt == 8) {
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(colsort_onewg_kernel<8>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return (int)e;
-      hipLaunchKernelGGL(colsort_onewg_kernel<8>, dim3(F), dim3(OW_T), lds, st, cp, col_lo, a);
-    } else {
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(colsort_onewg_kernel<16>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return (int)e;
-      hipLaunchKernelGGL(colsort_onewg_kernel<16>, dim3(F), dim3(OW_T), lds, st, cp, col_lo, a);
-    }
-    REC_LAUNCH_CHECK();
-    return REC_OK;
-  }
+  // one workgroup per column (LDS radix sort + run heads in one launch); B <= 16384 = 16 x 1024
+  const int kpt = B <= 8192 ? 8 : 16;
+  // words + per-wave counters (the 16-bit staging arrays of the outputs reuse them) + block-scan scratch
+  const size_t lds = sizeof(uint32_t) * ((size_t)CS_T * kpt + CS_W * CS_BINS + CS_W);
+  const void* fn = kpt == 8 ? reinterpret_cast<const void*>(colsort_kernel<8>)
+                            : reinterpret_cast<const void*>(colsort_kernel<16>);
+  const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return (int)e;
+  if (kpt == 8)
+    hipLaunchKernelGGL(colsort_kernel<8>, dim3(F), dim3(CS_T), lds, st, cp, col_lo, a);
+  else
+    hipLaunchKernelGGL(colsort_kernel<16>, dim3(F), dim3(CS_T), lds, st, cp, col_lo, a);
+  REC_LAUNCH_CHECK();
+  return REC_OK;
 }
 
 extern "C" int rec_colsort_plan_i64(const int64_t* const* cols_host, int F, int64_t B, int64_t V, const int64_t* col_lo,

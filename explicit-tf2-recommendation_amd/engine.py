@@ -574,7 +574,7 @@ class DeepFMFusedStep(_FusedStep):
                            col_nu=self._col_nu[b], dloc=self._dloc[b]) for b in range(NB)]
         # consecutive buffers are contiguous, so ONE sort call can build the plans of GROUP upcoming batches as
         # GROUP*F columns (the sort kernels are latency-bound at < 1 wave per SIMD: two batches cost ~1.2x one)
-        # (256 column pointers per sort launch: one workgroup per column, and a CU holds ONE sort workgroup (86 KB of LDS) --
+        # (256 column pointers per sort launch: one workgroup per column, and a CU holds ONE sort workgroup (98 KB of LDS) --
         # 17 batches per launch, 442 workgroups, were measured slower than 9)
         self.GROUP = max(1, 256 // F)
         self.col_lo_rep = self.col_lo.repeat(self.GROUP).contiguous()

@@ -302,6 +302,9 @@ size_t rec_deepfm_fused_workspace_bytes(int64_t B, int F);
  * per call, so one call may plan several batches).
  * perm [F,B], col_uid [F,B], col_seg [F,B+1], col_nu [F]; an id outside its column's range sets *bad_flag. */
 size_t rec_colsort_workspace_bytes(int64_t B, int F);
+/* Radix passes of that sort for a batch of B and a largest key max_key: *passes passes of at most *digit_bits bits
+ * (<= 10) over the key; the status the plan calls return for (B, max_key) otherwise. */
+int rec_colsort_digits(int64_t B, int64_t max_key, int* passes, int* digit_bits);
 int rec_colsort_plan_i64(const int64_t* const* cols_host, int F, int64_t B, int64_t V, const int64_t* col_lo,
                          int64_t max_key, int32_t* perm, int64_t* col_uid, int32_t* col_seg, int32_t* col_nu,
                          int* bad_flag, void* workspace, void* stream);
