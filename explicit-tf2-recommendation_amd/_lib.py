@@ -107,6 +107,9 @@ SIGNATURES = {
     "rec_cin_workspace_bytes": (sz, [i64, i32, i32, i32, p]),
     "rec_cin_fwd_f32": (i32, [p, i64, i32, i32, i32, p, p, p, p, p]),
     "rec_cin_bwd_f32": (i32, [p, p, p, i64, i32, i32, i32, p, p, p, p, p, sz, p]),
+    "rec_fibinet_workspace_bytes": (sz, [i64, i32, i32, i32, i32]),
+    "rec_fibinet_fwd_f32": (i32, [p, p, p, p, p, i64, i32, i32, i32, i32, i32, p, p, p, p]),
+    "rec_fibinet_bwd_f32": (i32, [p, p, p, p, p, p, p, i64, i32, i32, i32, i32, i32, p, p, p, p, p, sz, p]),
 }
 
 

@@ -505,3 +505,25 @@ class CIN(torch.autograd.Function):
         x0, states, *Ws = ctx.saved_tensors
         dx0, dWs = ops.cin_bwd(x0, states, g.contiguous(), Ws)
         return (dx0, *dWs)
+
+
+class FiBiNetInteraction(torch.autograd.Function):
+    """SENet + bilinear interaction of FiBiNetLayer (3.DCN/CustomLayers.py:936-1011) as one kernel each way
+    (csrc/fibinet.hip): x_emb [B,F,E], x_cont [B,C], S0 [F,mid], S1 [mid,F], W [nW,E,E] ->
+    dnn_in [B, 2PE + C] = [raw pairs | SENet pairs | x_cont].  The continuous columns get no gradient (as in
+    ConcatCols).  ``pack`` maps the trailing weight tensors to W and ``unpack`` maps dW back onto them."""
+
+    @staticmethod
+    def forward(ctx, x_emb, x_cont, S0, S1, type_code, pack, *Ws):
+        x_emb, S0, S1 = x_emb.contiguous(), S0.contiguous(), S1.contiguous()
+        W = pack(Ws)
+        dnn_in, A, H1 = ops.fibinet_fwd(x_emb, x_cont.contiguous(), S0, S1, W, type_code)
+        ctx.save_for_backward(x_emb, A, H1, S0, S1, W)
+        ctx.type_code = type_code
+        return dnn_in
+
+    @staticmethod
+    def backward(ctx, g):
+        x_emb, A, H1, S0, S1, W = ctx.saved_tensors
+        dx, dW, dS0, dS1 = ops.fibinet_bwd(x_emb, g.contiguous(), A, H1, S0, S1, W, ctx.type_code)
+        return (dx, None, dS0, dS1, None, None, *dW.unbind(0))

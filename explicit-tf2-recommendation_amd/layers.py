@@ -13,6 +13,9 @@ libmi355rec.so (through functional.py / ops.py).  Reference classes and the line
   MatrixCrossLayer              3.DCN/CustomLayers.py:272-305
   XDeepFMRankingLayer           3.DCN/CustomLayers.py:308-374
   CINLayer                      3.DCN/CustomLayers.py:377-417
+  FiBiNetLayer                  3.DCN/CustomLayers.py:888-956
+  SENetLayer                    3.DCN/CustomLayers.py:959-981
+  BilinearInteractionLayer      3.DCN/CustomLayers.py:984-1011
 
 Parameters are named after the TF checkpoint keys (``embed.embeddings``, ``w.embeddings``, ``bias``,
 ``MLP_layer1.kernel_0`` ...), so a TensorBundle checkpoint maps onto ``state_dict()`` by name.
@@ -48,10 +51,18 @@ def glorot_uniform(shape):
     return _uniform(shape, math.sqrt(6.0 / (fan_in + fan_out)))
 
 
+def glorot_normal(shape):
+    """TF2 glorot_normal: truncated normal at +-2 sigma, stddev sqrt(2 / (fan_in + fan_out)) / 0.87962566 (the stddev of
+    a unit normal truncated at +-2), so that the draws have the untruncated variance."""
+    fan_in, fan_out = (shape[-2], shape[-1]) if len(shape) >= 2 else (shape[0], shape[0])
+    std = math.sqrt(2.0 / (fan_in + fan_out)) / 0.87962566103423978
+    return torch.nn.init.trunc_normal_(torch.empty(shape), 0.0, std, -2.0 * std, 2.0 * std, generator=_init_gen)
+
+
 def _initializer(name):
     if callable(name):
         return name
-    table = {"glorot_uniform": glorot_uniform, "zeros": lambda s: torch.zeros(s),
+    table = {"glorot_uniform": glorot_uniform, "glorot_normal": glorot_normal, "zeros": lambda s: torch.zeros(s),
              "random_normal": lambda s: torch.randn(s, generator=_init_gen) * 0.05,
              "uniform": lambda s: _uniform(s, 0.05)}
     if name not in table:
@@ -545,6 +556,131 @@ class XDeepFMRankingLayer(Layer):
         cin_part = self.cin_layer(X_emb)
         output = self.output_layer(ConcatCols.apply(linear_part, dense_part, cin_part))
         return {"output": output}
+
+
+class SENetLayer(Layer):
+    """3.DCN/CustomLayers.py:959-981: A = excitation(mean_e inputs), excitation = MLPLayer([mid, F], 'relu',
+    use_bias=False) with mid = max(1, F // reduction_ratio) (``excitation.kernel_0`` [F,mid], ``excitation.kernel_1``
+    [mid,F], glorot-uniform).  Its forward runs fused with the bilinear interaction inside FiBiNetLayer
+    (csrc/fibinet.hip); there is no separate kernel for it."""
+
+    def __init__(self, reduction_ratio=3, input_dim=None):
+        super().__init__()
+        self.reduction_ratio = reduction_ratio
+        self.built = False
+        if input_dim is not None:
+            self.build(input_dim)
+
+    def build(self, field_num):
+        self.field_num = int(field_num)
+        self.mid_unit_num = max(1, self.field_num // self.reduction_ratio)
+        self.excitation = MLPLayer([self.mid_unit_num, self.field_num], activation="relu", use_bias=False,
+                                   input_dim=self.field_num)
+        self.built = True
+
+    def forward(self, inputs):
+        raise NotImplementedError("SENetLayer runs fused inside FiBiNetLayer (csrc/fibinet.hip)")
+
+
+class BilinearInteractionLayer(Layer):
+    """3.DCN/CustomLayers.py:984-1011: p_ij = (v_i W_ij) * v_j over the pairs i < j (itertools.combinations order),
+    W_ij = ``bilinear_weight`` ('all'), ``bilinear_weight{i}`` ('each'), ``bilinear_weight{i}_{j}`` ('interaction'),
+    each [E,E], TF2 glorot_normal.  The Parameters are views of one packed [nW,E,E] array, so that the kernel takes a
+    single pointer (re-packed after .to() / .cuda(); if outside code replaces one, ``packed_weight`` stacks them).
+    Its forward runs fused with SENet inside FiBiNetLayer (csrc/fibinet.hip)."""
+
+    def __init__(self, bilinear_type="interaction", input_shape=None):
+        super().__init__()
+        self.bilinear_type = bilinear_type
+        self.built = False
+        if input_shape is not None:
+            self.build(input_shape)
+
+    def build(self, input_shape):
+        F, E = int(input_shape[-2]), int(input_shape[-1])
+        self.field_num, self.embedding_size = F, E
+        pairs = [(i, j) for i in range(F) for j in range(i + 1, F)]
+        if self.bilinear_type == "all":
+            self._w_names = ["bilinear_weight"]
+        elif self.bilinear_type == "each":
+            self._w_names = ["bilinear_weight%d" % i for i in range(F - 1)]
+        elif self.bilinear_type == "interaction":
+            self._w_names = ["bilinear_weight%d_%d" % p for p in pairs]
+        else:
+            raise NotImplementedError
+        self.type_code = ops.FIBINET_TYPES[self.bilinear_type]
+        packed = torch.stack([glorot_normal((E, E)) for _ in self._w_names])
+        self._pack_into(packed)
+        self.built = True
+
+    def _pack_into(self, packed):
+        self._packed = packed
+        for k, n in enumerate(self._w_names):
+            old = getattr(self, n, None)
+            self.register_parameter(n, torch.nn.Parameter(packed[k], requires_grad=True if old is None
+                                                          else old.requires_grad))
+
+    def weights(self):
+        return [getattr(self, n) for n in self._w_names]
+
+    def _is_packed(self):
+        ws = self.weights()
+        E = self.embedding_size
+        st, off = ws[0].untyped_storage().data_ptr(), ws[0].storage_offset()
+        return all(w.is_contiguous() and w.device == ws[0].device and w.untyped_storage().data_ptr() == st
+                   and w.storage_offset() == off + E * E * k for k, w in enumerate(ws))
+
+    def packed_weight(self, ws):
+        """W [nW,E,E] for the kernel: a view of the packed array, or one torch.stack if the packing was broken."""
+        if len(ws) and self._is_packed():
+            return torch.as_strided(ws[0], (len(ws),) + tuple(ws[0].shape), (ws[0].numel(),) + tuple(ws[0].stride()))
+        return torch.stack(list(ws))
+
+    def _post_apply(self):
+        if not self.built or self._is_packed():
+            return
+        ws = self.weights()
+        packed = torch.stack([w.data for w in ws])
+        self._pack_into(packed)
+
+    def forward(self, inputs):
+        raise NotImplementedError("BilinearInteractionLayer runs fused inside FiBiNetLayer (csrc/fibinet.hip)")
+
+
+class FiBiNetLayer(Layer):
+    """3.DCN/CustomLayers.py:888-956: output = Dense(1, sigmoid)(dnn_layer(concat[Flatten(concat[Bilinear(X_emb),
+    Bilinear(SENet(X_emb))]), X_cont])), X_emb = embedding_layer(X_cate), dnn_layer = MLPLayer(units, activation).
+    The SENet, both bilinear passes and the concatenation are one kernel each way (functional.FiBiNetInteraction);
+    the MLP runs on the GEMM kernels."""
+
+    def __init__(self, categorical_features=["uid", "iid", "utag1", "utag2", "utag3", "utag4", "itag1", "itag2",
+                                             "itag3", "itag4"],
+                 continuous_features=["itag4_origin", "itag4_square", "itag4_cube"], feature_dims=160000,
+                 embedding_dims=16, units=[128, 16], activation="relu", bilinear_type="interaction", reduction_ratio=3):
+        super().__init__()
+        self.categorical_features = list(categorical_features)
+        self.continuous_features = list(continuous_features)
+        self.bilinear_type = bilinear_type
+        F, C, E = len(self.categorical_features), len(self.continuous_features), int(embedding_dims)
+        ops.fibinet_check_shape(F, E, C, max(1, F // reduction_ratio))
+        P = F * (F - 1) // 2
+        self.embedding_layer = Embedding(feature_dims, E)
+        self.dnn_layer = MLPLayer(list(units), activation=activation, input_dim=2 * P * E + C)
+        self.output_layer = Dense(1, activation="sigmoid", input_dim=list(units)[-1])
+        self.SENet = SENetLayer(reduction_ratio=reduction_ratio, input_dim=F)
+        self.Bilinear = BilinearInteractionLayer(bilinear_type=bilinear_type, input_shape=(F, E))
+
+    def forward(self, inputs):
+        X = assemble_index(inputs, self.categorical_features)
+        flag = ops.new_flag(X.device) if self.check_ids else None
+        X_emb = self.embedding_layer(X, flag)                           # [B,F,E]
+        self._raise_if_oob(flag)
+        cont = _cont_block(inputs, self.continuous_features, X.device)
+        x_cont = cont[0] if cont else torch.empty((X.shape[0], 0), dtype=torch.float32, device=X.device)
+        ex = self.SENet.excitation
+        dnn_input = Fn.FiBiNetInteraction.apply(X_emb, x_cont, ex.kernel_0, ex.kernel_1, self.Bilinear.type_code,
+                                                self.Bilinear.packed_weight, *self.Bilinear.weights())
+        return {"output": self.output_layer(self.dnn_layer(dnn_input))}
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -165,6 +165,12 @@ class ModelManager:
                 categorical_features=self.feature_names, continuous_features=self.continuous_features,
                 feature_dims=self.feature_dims, embedding_dims=self.embedding_dims, cin_size=model_params["cin_size"],
                 **p)
+        elif layer_name == "FiBiNet":                      # 3.DCN/ModelManager.py:92-93
+            p = {k: v for k, v in model_params.items()
+                 if k in ("units", "activation", "bilinear_type", "reduction_ratio")}
+            self.layer = CL.FiBiNetLayer(
+                categorical_features=self.feature_names, continuous_features=self.continuous_features,
+                feature_dims=self.feature_dims, embedding_dims=self.embedding_dims, **p)
         elif layer_name == "din_layer":                    # 5.DIN/ModelManager.py:72-73
             p = dict(model_params)
             p.setdefault("feature_dims", self.feature_dims)

@@ -648,3 +648,61 @@ def cin_bwd(x0, states, g, Ws):
     check(lib.rec_cin_bwd_f32(_ptr(x0), _ptr(states), _ptr(g), B, F, E, len(H), Hh, Wh, _ptr(dx0), dWh, _ptr(ws), nbytes,
                               _stream()), "rec_cin_bwd_f32")
     return dx0, dWs
+
+
+# ---- FiBiNet SENet + bilinear interaction (csrc/fibinet.hip)
+FIBINET_MAX_F, FIBINET_MAX_E, FIBINET_MAX_C = 32, 64, 64
+FIBINET_TYPES = {"all": 0, "each": 1, "interaction": 2}
+
+
+def fibinet_num_weights(F, bilinear_type):
+    """Bilinear matrices of one layer: 1 ('all'), F-1 ('each'), F(F-1)/2 ('interaction')."""
+    return {"all": 1, "each": F - 1, "interaction": F * (F - 1) // 2}[bilinear_type]
+
+
+def fibinet_check_shape(F, E, C, mid):
+    """NotImplementedError for shapes the FiBiNet kernels do not cover (the ABI would return -2)."""
+    if not (2 <= F <= FIBINET_MAX_F and 1 <= E <= FIBINET_MAX_E and 0 <= C <= FIBINET_MAX_C and 1 <= mid <= F):
+        raise NotImplementedError(
+            "FiBiNet kernels cover 2 <= fields <= %d, 1 <= embedding_dims <= %d, 0 <= continuous features <= %d and "
+            "1 <= SENet units <= fields; got fields=%d, embedding_dims=%d, continuous=%d, SENet units=%d"
+            % (FIBINET_MAX_F, FIBINET_MAX_E, FIBINET_MAX_C, F, E, C, mid))
+
+
+def fibinet_fwd(x_emb, x_cont, S0, S1, W, type_code):
+    """x_emb [B,F,E], x_cont [B,C], S0 [F,mid], S1 [mid,F], W [nW,E,E] -> (dnn_in [B, 2PE + C], A [B,F], H1 [B,mid])."""
+    _f32(x_emb, "x_emb"); _f32(x_cont, "x_cont"); _f32(S0, "S0"); _f32(S1, "S1"); _f32(W, "W")
+    B, F, E = x_emb.shape
+    C, mid = x_cont.shape[1], S0.shape[1]
+    fibinet_check_shape(F, E, C, mid)
+    P = F * (F - 1) // 2
+    dev = x_emb.device
+    dnn_in = torch.empty((B, 2 * P * E + C), dtype=torch.float32, device=dev)
+    A = torch.empty((B, F), dtype=torch.float32, device=dev)
+    H1 = torch.empty((B, mid), dtype=torch.float32, device=dev)
+    if B > 0:
+        check(lib.rec_fibinet_fwd_f32(_ptr(x_emb), _ptr(x_cont) if C > 0 else None, _ptr(S0), _ptr(S1), _ptr(W), B, F,
+                                      E, C, mid, type_code, _ptr(dnn_in), _ptr(A), _ptr(H1), _stream()),
+              "rec_fibinet_fwd_f32")
+    return dnn_in, A, H1
+
+
+def fibinet_bwd(x_emb, g, A, H1, S0, S1, W, type_code):
+    """-> (dx_emb [B,F,E], dW [nW,E,E], dS0, dS1) from g = dLoss/d dnn_in [B, 2PE + C]."""
+    _f32(x_emb, "x_emb"); _f32(g, "g"); _f32(A, "A"); _f32(H1, "H1"); _f32(S0, "S0"); _f32(S1, "S1"); _f32(W, "W")
+    B, F, E = x_emb.shape
+    mid = S0.shape[1]
+    C = g.shape[1] - F * (F - 1) * E
+    fibinet_check_shape(F, E, C, mid)
+    dx = torch.empty_like(x_emb)
+    if B == 0:
+        return dx, torch.zeros_like(W), torch.zeros_like(S0), torch.zeros_like(S1)
+    dW, dS0, dS1 = torch.empty_like(W), torch.empty_like(S0), torch.empty_like(S1)
+    nbytes = lib.rec_fibinet_workspace_bytes(B, F, E, mid, type_code)
+    if nbytes == 0:
+        raise NotImplementedError("rec_fibinet_workspace_bytes: unsupported FiBiNet shape")
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x_emb.device)
+    check(lib.rec_fibinet_bwd_f32(_ptr(x_emb), _ptr(g), _ptr(A), _ptr(H1), _ptr(S0), _ptr(S1), _ptr(W), B, F, E, C, mid,
+                                  type_code, _ptr(dx), _ptr(dW), _ptr(dS0), _ptr(dS1), _ptr(ws), nbytes, _stream()),
+          "rec_fibinet_bwd_f32")
+    return dx, dW, dS0, dS1

@@ -543,6 +543,27 @@ int rec_cin_bwd_f32(const float* x0, const float* states, const float* g, int64_
                     const int* H_host, const float* const* W_host, float* dx0, float* const* dW_host, void* workspace,
                     size_t workspace_bytes, void* stream);
 
+/* ---- FiBiNet SENet + bilinear interaction (FiBiNetLayer / SENetLayer / BilinearInteractionLayer,
+ * 3.DCN/CustomLayers.py:888-1011; csrc/fibinet.hip).  x_emb [B, F, E], x_cont [B, C] (may be NULL when C == 0),
+ * S0 [F, mid], S1 [mid, F], W [nW, E, E] packed (nW = 1 / F-1 / P for type 0 'all' / 1 'each' / 2 'interaction',
+ * P = F(F-1)/2 pairs i<j in itertools.combinations order; 'each' uses W[i], 'interaction' W[pair]):
+ *   Z = mean_e x_emb      H1 = relu(Z S0) [B, mid]      A = relu(H1 S1) [B, F]
+ *   p_ij = (v_i W_ij) * v_j      dnn_in [B, 2PE + C] = [p (raw pairs) | A_i A_j p_ij (SENet pairs) | x_cont],
+ *   element (s, pair, e) at column (s P + pair) E + e.  A and H1 are written for the backward.
+ * The backward reads the 2PE interaction columns of g = dLoss/d dnn_in [B, 2PE + C] and writes dx_emb [B, F, E],
+ * dW [nW, E, E] (summed over the pairs sharing a W), dS0 and dS1.  No float atomics: bit-identical results run to run.
+ * Supported: 2 <= F <= 32, 1 <= E <= 64, 0 <= C <= 64, 1 <= mid <= F, B >= 0 (B == 0: nothing is launched);
+ * otherwise -2.  A negative size, a type outside 0..2 or a NULL pointer: -1.
+ * workspace: rec_fibinet_workspace_bytes (0: invalid or unsupported shape). */
+size_t rec_fibinet_workspace_bytes(int64_t B, int F, int E, int mid, int type);
+int rec_fibinet_fwd_f32(const float* x_emb, const float* x_cont, const float* S0, const float* S1, const float* W,
+                        int64_t B, int F, int E, int C, int mid, int type, float* dnn_in, float* A, float* H1,
+                        void* stream);
+int rec_fibinet_bwd_f32(const float* x_emb, const float* g, const float* A, const float* H1, const float* S0,
+                        const float* S1, const float* W, int64_t B, int F, int E, int C, int mid, int type,
+                        float* dx_emb, float* dW, float* dS0, float* dS1, void* workspace, size_t workspace_bytes,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

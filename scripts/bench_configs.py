@@ -14,6 +14,7 @@ batches, one MI355X.  Prints one JSON line per config.  Usage:  python scripts/b
   FF  FFM (f4), 26 fields, V=10M rows of 26x16 floats (16.6 GB), B=8192
   G   SIM GSU inner-product attention (f4), T=100, V=50M, E=32, B=4096
   X   xDeepFM, 10 cat + 3 cont, V=10M, E=16, cin_size [16,32,64], units [64,8], B=16384; X26 = 26 cat fields
+  FB  FiBiNet 'interaction', 10 cat + 3 cont, V=10M, E=16, units [128,16], B=16384; FB26 = 26 cat fields, B=8192
 """
 import json
 import os
@@ -285,6 +286,20 @@ def run(name):
         cin_fwd = 2.0 * B * E * sum(ncat * hs[k] * hs[k + 1] for k in range(len(cin_size)))
         return {"config": "%s xDeepFM CIN [16,32,64], %d cat + 3 cont, 10M x 16d" % (name, ncat), "B": B, "V": V,
                 "ms_per_step": dt * 1e3, "examples_per_s": B / dt, "cin_flops_per_step": 3 * cin_fwd}
+    if name in ("FB", "FB26"):
+        ncat, B = (10, 16384) if name == "FB" else (26, 8192)
+        cat = ["c%d" % i for i in range(ncat)]
+        cont = ["x0", "x1", "x2"]
+        V, E = 10_000_000, 16
+        layer = layers.FiBiNetLayer(categorical_features=cat, continuous_features=cont, feature_dims=1000,
+                                    embedding_dims=E, units=[128, 16], bilinear_type="interaction").cuda()
+        layer.embedding_layer.embeddings = torch.nn.Parameter(torch.empty((V, E), device="cuda"))
+        big_table_(layer.embedding_layer.embeddings)
+        batch = data.to_device(data.SyntheticGenerator(cat, V, continuous=cont, seed=0).batch(B))
+        dt = timed(fwd_bwd(layer, batch, cat + cont), 5, 50)
+        P = ncat * (ncat - 1) // 2
+        return {"config": "%s FiBiNet interaction, %d cat + 3 cont, 10M x 16d, units [128,16]" % (name, ncat), "B": B,
+                "V": V, "ms_per_step": dt * 1e3, "examples_per_s": B / dt, "dnn_in_mb": B * (2 * P * E + 3) * 4 / 1e6}
     if name == "FF":
         names = ["C%d" % i for i in range(26)]
         V, B, E = 10_000_000, 8192, 16
@@ -329,7 +344,7 @@ if __name__ == "__main__":
     GRAPHED = "--graphed" in sys.argv[1:]
     for n in (argv or ["A", "B", "C", "C26", "D", "E", "R", "P", "N", "FF", "G"]):
         r = run(n)
-        if GRAPHED and n in ("B", "C", "C26", "D", "E", "DS", "ES", "P", "N", "FF", "G", "X", "X26"):
+        if GRAPHED and n in ("B", "C", "C26", "D", "E", "DS", "ES", "P", "N", "FF", "G", "X", "X26", "FB", "FB26"):
             r["config"] += " [GraphedTrainStep]"
         r["n_gpus"] = 1
         print(json.dumps(r), flush=True)
