@@ -103,7 +103,59 @@ class _BatchReader:
         return y
 
 
-class DeepFMTrainStep:
+class _GraphPolicy:
+    """When a cached train step (DeepFMTrainStep, the fused steps, ShardedDeepFMStep.many) captures a call into a
+    hipGraph, keeps it and replays it.  A subclass calls ``super().__init__()``, sets ``use_graph`` (False: every call
+    eager), overrides ``_graphable`` where some calls must stay eager, and hands each call to ``_run``."""
+
+    MAX_GRAPHS = 64     # captured hipGraphs kept (least recently used beyond that are dropped with the inputs they hold)
+    use_graph = True
+
+    def __init__(self):
+        self._graphs = collections.OrderedDict()            # gkey -> (graph, inputs kept alive), LRU order
+        self._seen = collections.OrderedDict()              # gkeys enqueued eagerly once (addresses only: nothing is held)
+
+    def _graphable(self):
+        return True
+
+    def _run(self, gkey, enqueue_all, *keep):
+        """The graph policy of a call with input addresses ``gkey``.  First sighting: plain eager enqueue, no device
+        synchronisation, nothing retained -- an input pipeline that hands over fresh tensors every batch never gets past
+        this branch, one that cycles staging buffers is captured on the next round.  Second sighting: enqueued eagerly
+        -- that IS this call's work -- and then captured, without running, for the calls to come (with an optimizer in
+        the step a warm-up followed by a replay would apply the update twice).  After that: replayed.  Every call thus
+        does its work exactly once.  The last MAX_GRAPHS graphs used are kept, each with ``keep`` (the inputs whose
+        addresses it holds)."""
+        if not (self.use_graph and self._graphable()):
+            enqueue_all()
+            return
+        ent = self._graphs.get(gkey)
+        if ent is not None:
+            self._graphs.move_to_end(gkey)
+            ent[0].replay()
+        elif gkey not in self._seen:
+            enqueue_all()
+            self._seen[gkey] = True
+            if len(self._seen) > 8 * self.MAX_GRAPHS:
+                self._seen.popitem(last=False)
+        else:
+            enqueue_all()
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, capture_error_mode=CAPTURE_MODE):
+                enqueue_all()
+            self._graphs[gkey] = (g,) + keep
+            del self._seen[gkey]
+            while len(self._graphs) > self.MAX_GRAPHS:
+                self._graphs.popitem(last=False)             # least recently used: graph and retained inputs go
+
+    def release(self):
+        """Drop the captured graphs (and the inputs they hold)."""
+        self._graphs.clear()
+        self._seen.clear()
+
+
+class DeepFMTrainStep(_GraphPolicy):
     """fwd + bwd (+ optimizer) of DeepFMRankingLayer (2.FM/CustomLayers.py:279-308) under the reference's loss.
 
     optimizer: None (gradients only -- the 'fwd+bwd' of the headline metric), 'keras_adam' (the reference's semantics:
@@ -111,6 +163,7 @@ class DeepFMTrainStep:
     """
 
     def __init__(self, layer, batch_size, optimizer=None, lr=1e-3, use_graph=True):
+        super().__init__()
         self.layer = layer
         self.B = B = int(batch_size)
         self.F = F = len(layer.feature_names)
@@ -172,7 +225,6 @@ class DeepFMTrainStep:
         self.colsum_ws = torch.empty(lib.rec_colsum_workspace_bytes(B, max(u1, u2)) // 4 + 1, **f32)
         self.segsum_ws = torch.empty(lib.rec_segment_sum_workspace_bytes(n, E) // 4, **f32)
         self._reader = _BatchReader(layer.feature_names, B)
-        self._graphs = {}
         self._static_prog = self._build_static()
 
     # -- program construction ---------------------------------------------------------------------
@@ -271,28 +323,16 @@ class DeepFMTrainStep:
         if self.optimizer is not None:
             self._optimizer_program(t).run(stream)
 
+    def _graphable(self):
+        return self.optimizer is None           # the optimizer's bias correction takes t as a host scalar: eager
+
     def __call__(self, inputs, label_name="label"):
         """One train_loop iteration.  Returns the device scalar loss (no synchronisation)."""
         cols, y = self._reader.cols(inputs), self._reader.label(inputs, label_name)
         self.t += 1
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        if not self.use_graph or self.optimizer is not None:
-            # the optimizer's bias correction depends on t: enqueue eagerly
-            self._enqueue(cols, y, stream, self.t)
-            return self.loss
-        key = tuple(c.data_ptr() for c in cols) + (y.data_ptr(),)
-        g = self._graphs.get(key)
-        if g is None:
-            # warm-up outside capture, then capture the same sequence
-            self._enqueue(cols, y, stream, self.t)
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode=CAPTURE_MODE):
-                cs = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-                self._enqueue(cols, y, cs, self.t)
-            self._graphs[key] = (g, cols, y)      # keep the inputs alive: the graph holds their addresses
-            g = self._graphs[key]
-        g[0].replay()
+        t = self.t
+        self._run(self._reader.key(cols) + (y.data_ptr(),),
+                  lambda: self._enqueue(cols, y, C.c_void_p(torch.cuda.current_stream().cuda_stream), t), cols, y)
         return self.loss
 
     def gradients(self):
@@ -377,22 +417,20 @@ def _assign_plan_buffers(keys, n_then, prefetched, half, nhalf):
     return bufs, inline, [other + j for j in range(n_then)], (1 - half if n_then else half)
 
 
-class _FusedStep:
+class _FusedStep(_GraphPolicy):
     """Call machinery of the fused train steps (DeepFMFusedStep, DSSMFusedStep): batch reading, the ring of NBUF
-    de-duplication plan buffers with the prefetch of announced batches, ``many()`` and its graph policy, and the
+    de-duplication plan buffers with the prefetch of announced batches, ``many()`` under the graph policy, and the
     device-side Adam clock.  A subclass sets B, calls ``super().__init__(names)`` (the id columns of a batch) and
     supplies ``_enqueue`` (the launches of one call), and where it differs ``_graphable``, ``_before_call`` and
     ``_after_call``."""
 
     NBUF = 64           # plan buffers: two halves of 32, many() alternates between them (a hipGraph launch leaves the GPU
                         # idle for ~30 us, so a call may hold up to 32 steps: ~1 us per step at that length)
-    MAX_GRAPHS = 64     # captured hipGraphs kept (least recently used beyond that are dropped with the inputs they hold)
 
     def __init__(self, names):
+        super().__init__()
         self._reader = _BatchReader(names, self.B)
         self._prefetched, self._half = {}, 0     # plans announced by the previous call: id-tensor addresses -> buffer
-        self._graphs = collections.OrderedDict()            # gkey -> (graph, inputs kept alive), LRU order
-        self._seen = collections.OrderedDict()              # gkeys enqueued eagerly once (addresses only: nothing is held)
 
     def _init_device_adam(self, names):
         """Adam with the step counter and the bias-corrected step size on the device (advanced by the fused launch): the
@@ -420,9 +458,6 @@ class _FusedStep:
         return self._reader.cols(inputs)
 
     _key = staticmethod(_BatchReader.key)
-
-    def _graphable(self):
-        return True
 
     def _before_call(self):
         """Runs at the start of every call, outside any capture."""
@@ -471,48 +506,13 @@ class _FusedStep:
         self._half = next_half
         return self.loss
 
-    def _run(self, gkey, enqueue_all, *keep):
-        """The graph policy of a call with input addresses ``gkey``.  First sighting: plain eager enqueue, no device
-        synchronisation, nothing retained -- an input pipeline that hands over fresh tensors every batch never gets past
-        this branch, one that cycles staging buffers is captured on the next round.  Second sighting: enqueued eagerly
-        -- that IS this call's work -- and then captured, without running, for the calls to come (with an optimizer in
-        the step a warm-up followed by a replay would apply the update twice).  After that: replayed.  The last
-        MAX_GRAPHS graphs used are kept, each with ``keep`` (the inputs whose addresses it holds)."""
-        if not (self.use_graph and self._graphable()):
-            enqueue_all()
-            return
-        ent = self._graphs.get(gkey)
-        if ent is not None:
-            self._graphs.move_to_end(gkey)
-            ent[0].replay()
-        elif gkey not in self._seen:
-            enqueue_all()
-            self._seen[gkey] = True
-            if len(self._seen) > 8 * self.MAX_GRAPHS:
-                self._seen.popitem(last=False)
-        else:
-            enqueue_all()
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode=CAPTURE_MODE):
-                enqueue_all()
-            self._graphs[gkey] = (g,) + keep
-            del self._seen[gkey]
-            while len(self._graphs) > self.MAX_GRAPHS:
-                self._graphs.popitem(last=False)             # least recently used: graph and retained inputs go
-
-    def release(self):
-        """Drop the captured graphs (and the inputs they hold)."""
-        self._graphs.clear()
-        self._seen.clear()
-
 
 class DeepFMFusedStep(_FusedStep):
     """The same train_loop iteration as DeepFMTrainStep in two launches on the main stream: the fused forward+backward
     kernel (csrc/deepfm_fused3.hip), then ONE launch (csrc/deepfm_fused.hip) for the fixed-order reduction of its partials
     and the segment sums -- plus, behind the steps of a call, the per-column LDS sort (csrc/colsort.hip) of the
     de-duplication plans of the batches announced for the next call (they depend only on the ids).  ``many()`` runs
-    several iterations as one captured hipGraph (call forms, plan ring and graph policy: _FusedStep).
+    several iterations as one captured hipGraph (call forms and plan ring: _FusedStep; graph policy: _GraphPolicy).
 
     Requirements (checked; otherwise use DeepFMTrainStep): embedding_dims 16, mlp_dims [32,8], fused table layout,
     F <= 28, B <= 16384, and the DataGenerator id-space contract -- ``field_offsets[f]``/``field_dims[f]`` =
@@ -827,8 +827,8 @@ class DSSMFusedStep(_FusedStep):
     171-177) in two launches on the main stream: the fused kernel (csrc/dssm_fused.hip: gather, both tower MLPs, score,
     Keras BCE and the whole backward) and the post launch (fixed-order reduction of its partials side by side with the
     segment sums of both towers' gradient rows).  The de-duplication plans (rec_dedup_plan_i64 of each tower's flat
-    [B*F] ids) of the batches announced for the next call are built behind the steps of this call.  Call forms, plan
-    ring and graph policy: _FusedStep.
+    [B*F] ids) of the batches announced for the next call are built behind the steps of this call.  Call forms and plan
+    ring: _FusedStep; graph policy: _GraphPolicy.
 
     Requirements (checked; otherwise keep GraphedTrainStep, raises NotImplementedError): plain (unsharded) tables with
     the same embedding_dims E in {8, 16, 32, 64} in both towers, mlp_dims [64, 32], final_dim 8, 1 <= F <= 8 features
@@ -1039,7 +1039,6 @@ class HipStepBackend:
         i32 = dict(dtype=torch.int32, device=dev)
         i64 = dict(dtype=torch.int64, device=dev)
         m = P * cap                                        # rows of every exchange buffer
-        self.col_lo = torch.tensor([int(o) for o in field_offsets], **i64)
         self.bad_ids = torch.zeros(1, **i32)
         self.o_ws_bytes = lib.rec_dedup_workspace_bytes(m)
         # NPL plan buffers.  The eager step alternates between the first two (the plan of batch k+1 is built beside step
@@ -1049,7 +1048,7 @@ class HipStepBackend:
         # on the step's critical path; eight batches per launch cost ~36)
         self.NPL = NPL = 16
         self.GROUP = max(1, min(8, 256 // F))
-        self.col_lo_rep = self.col_lo.repeat(self.GROUP).contiguous()
+        self.col_lo_rep = torch.tensor([int(o) for o in field_offsets] * self.GROUP, **i64)    # each sorted column's offset
         self._perm = torch.empty((NPL, F, B), **i32)
         self._col_uid = torch.empty((NPL, F, B), **i64)
         self._col_seg = torch.empty((NPL, F, B + 1), **i32)
@@ -1067,8 +1066,6 @@ class HipStepBackend:
         self.o_ws = [torch.empty(self.o_ws_bytes, dtype=torch.uint8, device=dev) for _ in range(NPL)]
         # every pointer below is fixed for the life of the step: the ctypes argument tuples are built once
         for buf, pl in enumerate(self.plans):
-            pl["a_sort"] = (_p(self.col_lo), self.max_key, _p(pl["perm"]), _p(pl["col_uid"]), _p(pl["col_seg"]),
-                            _p(pl["col_nu"]), _p(self.bad_ids), _p(self.sort_ws[buf]))
             pl["a_map"] = (_p(pl["perm"]), _p(pl["col_uid"]), _p(pl["col_seg"]), _p(pl["col_nu"]), B, F,
                            step.rows_per_shard, P, cap, _p(pl["msg"]), _p(pl["uidx"]), _p(pl["slot_map"]),
                            _p(pl["n_uniq"]), _p(step.oob))
@@ -1117,13 +1114,8 @@ class HipStepBackend:
     def plan(self, cols, buf, on_side=False):
         """Per-column sort + unique (rec_colsort_plan_i64), then the fixed-capacity exchange map
         (rec_colsort_shard_map_fixed_i64): the id message, the slot of every lookup and of every unique id."""
-        st_ = self.step
-        B, F = st_.B, st_.F
-        pl = self.plans[buf]
-        st = self.side_st if on_side else self.st
-        check(lib.rec_colsort_plan_i64(self._col_arr(cols), F, B, st_.V, *pl["a_sort"], st), "rec_colsort_plan_i64")
-        check(lib.rec_colsort_shard_map_fixed_i64(*pl["a_map"], st), "rec_colsort_shard_map_fixed_i64")
-        return pl
+        self.plan_group([cols], buf, on_side)
+        return self.plans[buf]
 
     def plan_group(self, cols_list, first_buf, on_side=False):
         """The plans of len(cols_list) <= GROUP batches into the consecutive buffers first_buf, first_buf + 1, ...: ONE
@@ -1132,7 +1124,7 @@ class HipStepBackend:
         B, F, k = st_.B, st_.F, len(cols_list)
         assert 1 <= k <= self.GROUP and first_buf + k <= self.NPL
         st = self.side_st if on_side else self.st
-        arr = (C.c_void_p * (k * F))(*[c.data_ptr() for cols in cols_list for c in cols])
+        arr = self._col_arr([c for cols in cols_list for c in cols])
         pl = self.plans[first_buf]
         check(lib.rec_colsort_plan_i64(arr, k * F, B, st_.V, _p(self.col_lo_rep), self.max_key, _p(pl["perm"]),
                                        _p(pl["col_uid"]), _p(pl["col_seg"]), _p(pl["col_nu"]), _p(self.bad_ids),
@@ -1205,7 +1197,7 @@ class HipStepBackend:
             raise ValueError("an id lies outside its field's [offset, offset+dim) range (DataGenerator contract)")
 
 
-class ShardedDeepFMStep:
+class ShardedDeepFMStep(_GraphPolicy):
     """DeepFM train_loop iteration with the fused [embed|w|pad] table ROW-SHARDED over the ranks of a process group
     (SURVEY.md section 8e): data-parallel batch (every rank its own B examples), block partition
     ``owner = id // ceil(V/P)``.  De-duplicate first, then exchange -- in FIXED-CAPACITY slabs: the field layout bounds
@@ -1233,6 +1225,7 @@ class ShardedDeepFMStep:
 
     def __init__(self, layer, batch_size, field_dims, field_offsets, group=None, backend=None, comm=None):
         from . import sharded
+        super().__init__()
         self.comm = comm if comm is not None else sharded.DistComm(group, separate_count_channel=True)
         self.P, self.rank = self.comm.world, self.comm.rank
         self.layer = layer
@@ -1333,54 +1326,45 @@ class ShardedDeepFMStep:
         """A cycle of steps over resident batches as ONE captured hipGraph (RCCL collectives included: every exchange
         has constant sizes and nothing is read back, so the sequence is a fixed program).  The plan of the first batch
         is built inside the graph on the main stream, the plans of the following ones on the second stream beside the
-        step before.  Every rank must call it with the same number of batches.  Returns the loss of the last step."""
-        key = (tuple(self._reader.cols_key(b)[1] for b in batches) +
-               tuple(self._reader.label(b, label_name).data_ptr() for b in batches))     # every column and label address
-        graphs = self.__dict__.setdefault("_graphs", {})
-        g = graphs.get(key)
-        if g is None:
-            grouped = isinstance(self.be, HipStepBackend) and len(batches) <= self.be.NPL
+        step before.  Every rank must call it with the same number of batches.  Under the graph policy every call runs
+        the cycle exactly once, eager or replayed, so ranks whose graph caches differ still issue the same collectives.
+        ``release()`` the graphs before the process group is destroyed: they hold RCCL kernels.  Returns the loss of the
+        last step."""
+        rd = self._reader
+        ck = [rd.cols_key(b) for b in batches]
+        colss = [cols for cols, _ in ck]
+        ys = [rd.label(b, label_name) for b in batches]
+        grouped = isinstance(self.be, HipStepBackend) and len(batches) <= self.be.NPL
 
-            def run():
-                self._next = None
-                if not grouped:
-                    for i, b in enumerate(batches):
-                        self(b, label_name, next_inputs=batches[i + 1] if i + 1 < len(batches) else None)
-                    return
-                # every plan of the cycle on the second stream, GROUP batches per sort launch (ids only: nothing of the
-                # steps is needed), each followed by its C1 and the owner's merge; step i waits for plan i alone
-                be, comm = self.be, self.comm
-                be.begin()
-                colss = [self._reader.cols_key(b)[0] for b in batches]
-                ys = [self._reader.label(b, label_name) for b in batches]
-                be.fork()
-                evs = []
-                with be.side_context():
-                    for j0 in range(0, len(batches), be.GROUP):
-                        be.plan_group(colss[j0:j0 + be.GROUP], j0, on_side=True)
-                    for i in range(len(batches)):
-                        pl = be.plans[i]
-                        pl["msg_theirs"] = comm.exchange_ids(pl["msg"], pl["msg_theirs"])
-                        be.owner_plan(pl, i, on_side=True)
-                        ev = torch.cuda.Event()
-                        ev.record(be.side)
-                        evs.append(ev)
+        def enqueue_all():
+            self._next = None
+            if not grouped:
+                for i, b in enumerate(batches):
+                    self(b, label_name, next_inputs=batches[i + 1] if i + 1 < len(batches) else None)
+                return
+            # every plan of the cycle on the second stream, GROUP batches per sort launch (ids only: nothing of the
+            # steps is needed), each followed by its C1 and the owner's merge; step i waits for plan i alone
+            be, comm = self.be, self.comm
+            be.begin()
+            be.fork()
+            evs = []
+            with be.side_context():
+                for j0 in range(0, len(batches), be.GROUP):
+                    be.plan_group(colss[j0:j0 + be.GROUP], j0, on_side=True)
                 for i in range(len(batches)):
-                    be.main.wait_event(evs[i])
-                    self._body(be.plans[i], ys[i])
-                be.join()
-            run()                                            # communicators and lazy initialisation: not captured
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode=CAPTURE_MODE):
-                run()
-            graphs[key] = g
-        g.replay()
+                    pl = be.plans[i]
+                    pl["msg_theirs"] = comm.exchange_ids(pl["msg"], pl["msg_theirs"])
+                    be.owner_plan(pl, i, on_side=True)
+                    ev = torch.cuda.Event()
+                    ev.record(be.side)
+                    evs.append(ev)
+            for i in range(len(batches)):
+                be.main.wait_event(evs[i])
+                self._body(be.plans[i], ys[i])
+            be.join()
+        key = tuple(k for _, k in ck) + tuple(y.data_ptr() for y in ys)          # every column and label address
+        self._run(key, enqueue_all, colss, ys)
         return self.loss
-
-    def release_graphs(self):
-        """Drop the captured graphs (before the process group is destroyed: they hold RCCL kernels)."""
-        self.__dict__.pop("_graphs", None)
 
     def check_flags(self):
         if int(self.oob.item()) != 0:

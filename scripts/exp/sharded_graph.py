@@ -51,7 +51,7 @@ for rep in range(3):
     t = time.perf_counter() - t0
     print("%s: %.4f ms/step (host issue %.4f)" % (mode, t / 400 * 1e3, t_issue / 400 * 1e3), flush=True)
 step.check_flags()
-step.release_graphs()
+step.release()
 torch.cuda.synchronize()
 print("destroying", flush=True)
 dist.destroy_process_group()

@@ -1,5 +1,5 @@
-"""CPU checks of the host-side pieces the fused train steps share (explicit-tf2-recommendation_amd/engine.py): the
-plan-buffer assignment of a many() call and the batch reader."""
+"""CPU checks of the host-side pieces the train steps share (explicit-tf2-recommendation_amd/engine.py): the
+plan-buffer assignment of a many() call, the batch reader and the graph policy of every cached step."""
 import pytest
 import torch
 
@@ -63,3 +63,129 @@ def test_batch_reader():
         _BatchReader(["u", "i"], B).cols_key(batch)
     with pytest.raises(ValueError, match="CUDA"):
         _BatchReader(["u", "i"], B).label(batch, "label")
+
+
+class _Recorder:
+    """Fakes of torch.cuda.CUDAGraph / graph / synchronize that log what the graph policy does.  Work enqueued inside a
+    capture is recorded into the graph, not run; a replay runs what the graph recorded."""
+
+    def __init__(self, monkeypatch):
+        import contextlib
+        from explicit_tf2_recommendation_amd import engine
+        self.events, self.done, self.capturing = [], [], None
+        rec = self
+
+        class FakeGraph:
+            def __init__(self):
+                self.nodes = []
+
+            def replay(self):
+                rec.events.append("replay")
+                rec.done.extend(self.nodes)
+
+        @contextlib.contextmanager
+        def graph(g, capture_error_mode=None):
+            assert capture_error_mode == engine.CAPTURE_MODE
+            rec.events.append("capture")
+            rec.capturing = g
+            try:
+                yield
+            finally:
+                rec.capturing = None
+
+        monkeypatch.setattr(torch.cuda, "CUDAGraph", FakeGraph)
+        monkeypatch.setattr(torch.cuda, "graph", graph)
+        monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: rec.events.append("sync"))
+
+    def enqueue(self, work):
+        if self.capturing is not None:
+            self.capturing.nodes.append(work)
+        else:
+            self.events.append("eager")
+            self.done.append(work)
+
+    def take(self):
+        ev, self.events = self.events, []
+        return ev
+
+
+def _stub(rec, graphable=True, use_graph=True):
+    from explicit_tf2_recommendation_amd.engine import _GraphPolicy
+
+    class Stub(_GraphPolicy):
+        def _graphable(self):
+            return graphable
+
+        def __call__(self, key, *keep):
+            self._run(key, lambda: rec.enqueue(key), *keep)
+
+    s = Stub()
+    s.use_graph = use_graph
+    return s
+
+
+def test_graph_policy_is_shared():
+    from explicit_tf2_recommendation_amd import engine
+    for cls in (engine.DeepFMTrainStep, engine.DeepFMFusedStep, engine.DSSMFusedStep, engine.ShardedDeepFMStep):
+        assert issubclass(cls, engine._GraphPolicy) and cls._run is engine._GraphPolicy._run, cls
+    assert not hasattr(engine.ShardedDeepFMStep, "release_graphs")
+
+
+def test_graph_policy_sightings(monkeypatch):
+    """First sighting: eager, nothing kept.  Second: eager, then captured without running.  Then: replay only.  Every
+    call does its work exactly once."""
+    rec = _Recorder(monkeypatch)
+    s = _stub(rec)
+    held = object()
+    s("a", held)
+    assert rec.take() == ["eager"] and len(s._graphs) == 0 and list(s._seen) == ["a"]
+    s("a", held)
+    assert rec.take() == ["eager", "sync", "capture"] and list(s._graphs) == ["a"] and len(s._seen) == 0
+    g, kept = s._graphs["a"]
+    assert g.nodes == ["a"] and kept is held                 # enqueued inside the capture; the inputs are held
+    for _ in range(3):
+        s("a", held)
+        assert rec.take() == ["replay"]
+    assert rec.done == ["a"] * 5                             # five calls, the work ran five times
+
+
+def test_graph_policy_lru_and_bounded_seen(monkeypatch):
+    rec = _Recorder(monkeypatch)
+    s = _stub(rec)
+    s.MAX_GRAPHS = 2
+    for k in ("a", "a", "b", "b", "a", "c", "c"):            # "a" is used after "b": "b" is the least recently used
+        s(k)
+    assert list(s._graphs) == ["a", "c"]
+    rec.take()
+    s("b")                                                   # dropped with its graph: seen afresh, eager
+    assert rec.take() == ["eager"] and "b" in s._seen
+    keys = ["k%d" % i for i in range(40)]
+    for k in keys:
+        s(k)
+    assert len(s._seen) == 8 * s.MAX_GRAPHS and list(s._seen) == keys[-8 * s.MAX_GRAPHS:]
+    rec.take()
+    s(keys[0])                                               # forgotten: a first sighting again, no capture
+    assert rec.take() == ["eager"] and len(s._graphs) == 2
+    assert len(rec.done) == 7 + 1 + 40 + 1
+
+
+@pytest.mark.parametrize("graphable,use_graph", [(False, True), (True, False)])
+def test_graph_policy_eager_when_not_graphable(monkeypatch, graphable, use_graph):
+    rec = _Recorder(monkeypatch)
+    s = _stub(rec, graphable=graphable, use_graph=use_graph)
+    for _ in range(4):
+        s("a", object())
+    assert rec.take() == ["eager"] * 4 and len(s._graphs) == 0 and len(s._seen) == 0
+
+
+def test_graph_policy_release(monkeypatch):
+    rec = _Recorder(monkeypatch)
+    s = _stub(rec)
+    for k in ("a", "a", "b"):
+        s(k)
+    assert len(s._graphs) == 1 and len(s._seen) == 1
+    s.release()
+    assert len(s._graphs) == 0 and len(s._seen) == 0
+    rec.take()
+    s("a")                                                   # after release a key starts over
+    assert rec.take() == ["eager"]

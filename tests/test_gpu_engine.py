@@ -65,8 +65,10 @@ def test_deepfm_step_gradients(use_graph, B, F, E, V, dist):
         batch = gen.batch(B)
         dbatch = data.to_device(batch)
         loss = step(dbatch)
-        if use_graph:
-            loss = step(dbatch)                            # second call on the same tensors = pure replay
+        if use_graph:                                      # eager, eager + capture, replay
+            loss = step(dbatch)
+            loss = step(dbatch)
+            assert len(step._graphs) == it + 1
         ref_loss, ref = oracle_grads(layer, names, batch)
         assert abs(loss.item() - ref_loss) <= 1e-5 * max(1, abs(ref_loss))
         g = step.gradients()
@@ -81,6 +83,41 @@ def test_deepfm_step_gradients(use_graph, B, F, E, V, dist):
             assert np.array_equal(ids, touched)            # bit exact, ascending
             assert close(rows.cpu().numpy()[:nu], ref[name][touched]), name
         assert step.oob.item() == 0
+
+
+def test_deepfm_step_fresh_batches_neither_recapture_nor_grow():
+    """DeepFMTrainStep under the shared graph policy: an input pipeline that hands over NEW tensors every batch runs
+    eagerly -- no capture, nothing retained -- and the graph cache is a bounded LRU; a ring of staging buffers refilled
+    in place is captured once per slot and replayed."""
+    from explicit_tf2_recommendation_amd import engine, data
+    B, F, E, V = 256, 5, 16, 5547
+    layer, names, gen = make(B, F, E, V, 31, "zipf")
+    step = engine.DeepFMTrainStep(layer, B, optimizer=None, use_graph=True)
+    step.MAX_GRAPHS = 4
+    keep = []                                                # keeps every batch alive: all addresses are distinct
+    for i in range(40):
+        b = data.to_device(gen.batch(B))
+        keep.append(b)
+        step(b)
+    assert len(step._graphs) == 0 and len(step._seen) <= 8 * step.MAX_GRAPHS and step.t == 40
+    torch.cuda.synchronize()
+    m0 = torch.cuda.memory_allocated()
+    ring = keep[:8]                                          # a ring of 8 staging buffers, refilled in place
+    fresh = [gen.batch(B) for _ in range(8)]
+    for rnd in range(6):
+        for slot, b in enumerate(ring):
+            src = fresh[(slot + rnd) % 8]
+            for k in b:
+                b[k].copy_(torch.from_numpy(src[k]))
+            loss = step(b)
+        assert len(step._graphs) <= step.MAX_GRAPHS
+    assert len(step._graphs) == step.MAX_GRAPHS              # 8 slots, 4 graphs: the least recently used were dropped
+    torch.cuda.synchronize()
+    assert torch.cuda.memory_allocated() - m0 < (8 << 20)    # nothing accumulates beyond the bounded cache
+    ref_loss, _ = oracle_grads(layer, names, src)            # the last call read the refilled buffers
+    assert abs(loss.item() - ref_loss) <= 1e-5 * max(1, abs(ref_loss))
+    step.release()
+    assert len(step._graphs) == 0 and len(step._seen) == 0
 
 
 def test_engine_matches_autograd_path():

@@ -379,9 +379,10 @@ def test_sharded_embedding_world1_rccl():
 
 
 @pytest.mark.gpu
-def test_sharded_deepfm_step_world1_matches_fused_step():
+def test_sharded_deepfm_step_world1_matches_fused_step_and_replays_cycles():
     """The sharded train step (bucketize -> RCCL all-to-all -> owner gather -> fused kernel on the returned rows ->
-    gradients back -> owner de-duplication) at world_size 1 against the single-GPU fused step on the same batch."""
+    gradients back -> owner de-duplication) at world_size 1 against the single-GPU fused step on the same batch; then
+    many() under the shared graph policy: a cycle is captured at its second call and its replay gives the same loss."""
     from explicit_tf2_recommendation_amd import engine, data, layers
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(_free_port())
@@ -437,11 +438,13 @@ def test_sharded_deepfm_step_world1_matches_fused_step():
         # many(): the graph key covers every column, so two cycles that differ in one inner column are two graphs
         other = dict(batch2)
         other[names[7]] = batch3[names[7]]
+        sh.many([batch3, batch2])                            # eager, then eager + capture
         la = sh.many([batch3, batch2]).item()
+        sh.many([batch3, other])
         lb = sh.many([batch3, other]).item()
         assert len(sh._graphs) == 2
         assert abs(sh.many([batch3, batch2]).item() - la) == 0 and la != lb
-        sh.release_graphs()
+        sh.release()
     finally:
         dist.destroy_process_group()
 
