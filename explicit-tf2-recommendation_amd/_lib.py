@@ -110,6 +110,10 @@ SIGNATURES = {
     "rec_fibinet_workspace_bytes": (sz, [i64, i32, i32, i32, i32]),
     "rec_fibinet_fwd_f32": (i32, [p, p, p, p, p, i64, i32, i32, i32, i32, i32, p, p, p, p]),
     "rec_fibinet_bwd_f32": (i32, [p, p, p, p, p, p, p, i64, i32, i32, i32, i32, i32, p, p, p, p, p, sz, p]),
+    "rec_autoint_workspace_bytes": (sz, [i64, i32, i32, i32, i32, i32]),
+    "rec_autoint_fwd_f32": (i32, [p, p, p, p, p, p, p, i64, i32, i32, i32, i32, i32, i32, p, p, p, p, sz, p]),
+    "rec_autoint_bwd_f32": (i32, [p, p, p, p, p, p, p, p, p, p, i64, i32, i32, i32, i32, i32, i32, p, p, p, p, p, p, p,
+                                  sz, p]),
 }
 
 

@@ -527,3 +527,31 @@ class FiBiNetInteraction(torch.autograd.Function):
         x_emb, A, H1, S0, S1, W = ctx.saved_tensors
         dx, dW, dS0, dS1 = ops.fibinet_bwd(x_emb, g.contiguous(), A, H1, S0, S1, W, ctx.type_code)
         return (dx, None, dS0, dS1, None, None, *dW.unbind(0))
+
+
+class AutoIntAttention(torch.autograd.Function):
+    """One TransformerAttentionLayer (3.DCN/CustomLayers.py:1012-1067) as one forward and one backward call of
+    csrc/autoint.hip: x [B,Fc,E] -> y = relu(O (+ X | + X Wres)) [B,F,E], the softmax over the BATCH axis.  When
+    x_cont [B,C] and cemb [C,E] are given, the C continuous fields cemb[c] * x_cont[:, c] are appended after the Fc
+    categorical ones inside the kernels (AutoIntLayer's first layer); x_cont gets no gradient.  res: 0 / 1 / 2 =
+    no residual / + X / + X Wres (Wres may be None unless res == 2)."""
+
+    @staticmethod
+    def forward(ctx, x, x_cont, cemb, Wq, Wk, Wv, Wres, num_heads, res, scaling):
+        x = x.contiguous()
+        if x_cont is not None:
+            x_cont, cemb = x_cont.contiguous(), cemb.contiguous()
+        Wq, Wk, Wv = Wq.contiguous(), Wk.contiguous(), Wv.contiguous()
+        Wres = Wres.contiguous() if res == 2 else None
+        y, stats, _ = ops.autoint_fwd(x, Wq, Wk, Wv, Wres, num_heads, res, scaling, x_cont, cemb)
+        ctx.save_for_backward(x, x_cont, cemb, Wq, Wk, Wv, Wres, y, stats)
+        ctx.cfg = (num_heads, res, scaling)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, x_cont, cemb, Wq, Wk, Wv, Wres, y, stats = ctx.saved_tensors
+        num_heads, res, scaling = ctx.cfg
+        dx, dWq, dWk, dWv, dWres, dcemb = ops.autoint_bwd(x, Wq, Wk, Wv, Wres, y, g.contiguous(), stats, num_heads, res,
+                                                          scaling, x_cont, cemb)
+        return dx, None, dcemb, dWq, dWk, dWv, dWres, None, None, None

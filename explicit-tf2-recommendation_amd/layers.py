@@ -16,6 +16,8 @@ libmi355rec.so (through functional.py / ops.py).  Reference classes and the line
   FiBiNetLayer                  3.DCN/CustomLayers.py:888-956
   SENetLayer                    3.DCN/CustomLayers.py:959-981
   BilinearInteractionLayer      3.DCN/CustomLayers.py:984-1011
+  TransformerAttentionLayer     3.DCN/CustomLayers.py:1012-1067
+  AutoIntLayer                  3.DCN/CustomLayers.py:1070-1139
 
 Parameters are named after the TF checkpoint keys (``embed.embeddings``, ``w.embeddings``, ``bias``,
 ``MLP_layer1.kernel_0`` ...), so a TensorBundle checkpoint maps onto ``state_dict()`` by name.
@@ -59,10 +61,17 @@ def glorot_normal(shape):
     return torch.nn.init.trunc_normal_(torch.empty(shape), 0.0, std, -2.0 * std, 2.0 * std, generator=_init_gen)
 
 
+def truncated_normal(shape, stddev=0.05):
+    """TF2 tf.keras.initializers.TruncatedNormal() (mean 0, stddev 0.05): a normal of that stddev, values beyond 2
+    stddev redrawn (no variance correction, unlike glorot_normal)."""
+    return torch.nn.init.trunc_normal_(torch.empty(shape), 0.0, stddev, -2.0 * stddev, 2.0 * stddev, generator=_init_gen)
+
+
 def _initializer(name):
     if callable(name):
         return name
-    table = {"glorot_uniform": glorot_uniform, "glorot_normal": glorot_normal, "zeros": lambda s: torch.zeros(s),
+    table = {"glorot_uniform": glorot_uniform, "glorot_normal": glorot_normal, "truncated_normal": truncated_normal,
+             "zeros": lambda s: torch.zeros(s),
              "random_normal": lambda s: torch.randn(s, generator=_init_gen) * 0.05,
              "uniform": lambda s: _uniform(s, 0.05)}
     if name not in table:
@@ -680,6 +689,89 @@ class FiBiNetLayer(Layer):
         ex = self.SENet.excitation
         dnn_input = Fn.FiBiNetInteraction.apply(X_emb, x_cont, ex.kernel_0, ex.kernel_1, self.Bilinear.type_code,
                                                 self.Bilinear.packed_weight, *self.Bilinear.weights())
+        return {"output": self.output_layer(self.dnn_layer(dnn_input))}
+
+
+class TransformerAttentionLayer(Layer):
+    """3.DCN/CustomLayers.py:1012-1067: multi-head self-attention over the fields, ``query``, ``key``, ``value`` (and
+    ``res`` when use_res and res_learnable) [E,E], TF2 TruncatedNormal().  Head h owns the columns [h d, (h+1) d),
+    d = E / num_heads.  The reference's softmax runs over axis 1 of (H, B, F, F), the BATCH axis, so every example's
+    output depends on the whole batch; this port keeps that.  One kernel pair per layer (functional.AutoIntAttention,
+    csrc/autoint.hip)."""
+
+    def __init__(self, num_heads=2, use_res=True, res_learnable=False, scaling=False, input_dim=None):
+        super().__init__()
+        self.num_heads = num_heads
+        self.use_res = use_res
+        self.scaling = scaling
+        self.res_learnable = res_learnable
+        self.res_code = ops.AUTOINT_RES[(bool(use_res), bool(res_learnable))]
+        self.built = False
+        if input_dim is not None:
+            self.build(input_dim)
+
+    def build(self, input_shape):
+        E = int(input_shape[-1]) if isinstance(input_shape, (tuple, list, torch.Size)) else int(input_shape)
+        self.embedding_dim = E
+        self.att_embedding_size = E // self.num_heads
+        if E % self.num_heads != 0:
+            raise ValueError("embedding_dim %d is not divisible by num_heads %d" % (E, self.num_heads))
+        self.query = torch.nn.Parameter(truncated_normal((E, E)))
+        self.key = torch.nn.Parameter(truncated_normal((E, E)))
+        self.value = torch.nn.Parameter(truncated_normal((E, E)))
+        if self.use_res and self.res_learnable:
+            self.res = torch.nn.Parameter(truncated_normal((E, E)))
+        self.built = True
+
+    def attend(self, x, x_cont=None, cemb=None):
+        """x [B,Fc,E] (+ continuous fields cemb[c] * x_cont[:, c] appended last) -> [B,F,E]."""
+        if not self.built:
+            self.build(x.shape[-1])
+            self.to(x.device)
+        return Fn.AutoIntAttention.apply(x, x_cont, cemb, self.query, self.key, self.value,
+                                         getattr(self, "res", None), self.num_heads, self.res_code, bool(self.scaling))
+
+    def forward(self, inputs):
+        return self.attend(inputs)
+
+
+class AutoIntLayer(Layer):
+    """3.DCN/CustomLayers.py:1070-1139: X_emb = concat[embedding_layer(X_cate), continuous_embedding.embeddings *
+    x_cont[..., None]] (continuous fields last), attention_layer_num TransformerAttentionLayers, Flatten, dnn_layer =
+    MLPLayer(units, activation), output_layer = Dense(1, sigmoid).  The continuous fields are assembled inside the first
+    attention layer's kernels; the MLP runs on the GEMM kernels."""
+
+    def __init__(self, categorical_features=["uid", "iid", "utag1", "utag2", "utag3", "utag4", "itag1", "itag2",
+                                             "itag3", "itag4"],
+                 continuous_features=["itag4_origin", "itag4_square", "itag4_cube"], feature_dims=160000,
+                 embedding_dims=8, units=[128, 16], activation="relu", attention_layer_num=2, num_heads=2):
+        super().__init__()
+        self.categorical_features = list(categorical_features)
+        self.continuous_features = list(continuous_features)
+        Fc, C, E = len(self.categorical_features), len(self.continuous_features), int(embedding_dims)
+        ops.autoint_check_shape(Fc + C, E, int(num_heads), C)
+        if Fc < 1 or (C > 0 and attention_layer_num < 1):
+            raise NotImplementedError("AutoIntLayer needs a categorical feature, and an attention layer to assemble "
+                                      "the continuous fields in")
+        self.embedding_dims = E
+        self.embedding_layer = Embedding(feature_dims, E)
+        self.continuous_embedding = Embedding(C, E)
+        self.attention_layers = torch.nn.ModuleList(
+            [TransformerAttentionLayer(num_heads=num_heads, input_dim=E) for _ in range(attention_layer_num)])
+        self.dnn_layer = MLPLayer(list(units), activation=activation, input_dim=(Fc + C) * E)
+        self.output_layer = Dense(1, activation="sigmoid", input_dim=list(units)[-1])
+
+    def forward(self, inputs):
+        X = assemble_index(inputs, self.categorical_features)
+        flag = ops.new_flag(X.device) if self.check_ids else None
+        att = self.embedding_layer(X, flag)                              # [B,Fc,E]
+        self._raise_if_oob(flag)
+        cont = _cont_block(inputs, self.continuous_features, X.device)
+        x_cont = cont[0] if cont else None
+        cemb = self.continuous_embedding.embeddings if cont else None
+        for k, layer in enumerate(self.attention_layers):
+            att = layer.attend(att, x_cont, cemb) if k == 0 else layer.attend(att)
+        dnn_input = att.reshape(att.shape[0], -1)                        # Flatten: field-major [B, F*E] (a view)
         return {"output": self.output_layer(self.dnn_layer(dnn_input))}
 
 

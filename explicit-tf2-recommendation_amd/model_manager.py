@@ -171,6 +171,13 @@ class ModelManager:
             self.layer = CL.FiBiNetLayer(
                 categorical_features=self.feature_names, continuous_features=self.continuous_features,
                 feature_dims=self.feature_dims, embedding_dims=self.embedding_dims, **p)
+        elif layer_name == "AutoInt":                      # 3.DCN/ModelManager.py:94-95
+            # the reference builds AutoIntLayer() with its own defaults, E = 8, whatever the manager's embedding_dims
+            p = {k: v for k, v in model_params.items()
+                 if k in ("embedding_dims", "units", "activation", "attention_layer_num", "num_heads")}
+            self.layer = CL.AutoIntLayer(
+                categorical_features=self.feature_names, continuous_features=self.continuous_features,
+                feature_dims=self.feature_dims, **p)
         elif layer_name == "din_layer":                    # 5.DIN/ModelManager.py:72-73
             p = dict(model_params)
             p.setdefault("feature_dims", self.feature_dims)

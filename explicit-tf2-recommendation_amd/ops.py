@@ -706,3 +706,83 @@ def fibinet_bwd(x_emb, g, A, H1, S0, S1, W, type_code):
                                   type_code, _ptr(dx), _ptr(dW), _ptr(dS0), _ptr(dS1), _ptr(ws), nbytes, _stream()),
           "rec_fibinet_bwd_f32")
     return dx, dW, dS0, dS1
+
+
+# ---- AutoInt multi-head field attention (csrc/autoint.hip)
+AUTOINT_MAX_F, AUTOINT_MAX_E = 64, 64
+AUTOINT_RES = {(False, False): 0, (False, True): 0, (True, False): 1, (True, True): 2}   # (use_res, res_learnable)
+
+
+def autoint_check_shape(F, E, H, C=0):
+    """NotImplementedError for shapes the AutoInt kernels do not cover (the ABI would return -2); ValueError when the
+    embedding width does not split into the heads (the reference asserts E % H == 0)."""
+    if H >= 1 and E % H != 0:
+        raise ValueError("embedding_dims=%d is not divisible by num_heads=%d" % (E, H))
+    if not (1 <= F <= AUTOINT_MAX_F and 1 <= E <= AUTOINT_MAX_E and 1 <= H <= E and 0 <= C < F):
+        raise NotImplementedError(
+            "AutoInt kernels cover 1 <= fields <= %d, 1 <= embedding_dims <= %d, 1 <= num_heads <= embedding_dims and "
+            "fewer continuous than total fields; got fields=%d, embedding_dims=%d, num_heads=%d, continuous=%d"
+            % (AUTOINT_MAX_F, AUTOINT_MAX_E, F, E, H, C))
+
+
+def _autoint_ws(B, F, E, H, C, res, dev):
+    nbytes = lib.rec_autoint_workspace_bytes(B, F, E, H, C, res)
+    if nbytes == 0:
+        raise NotImplementedError("rec_autoint_workspace_bytes: unsupported AutoInt shape")
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=dev), nbytes
+
+
+def autoint_fwd(x, Wq, Wk, Wv, Wres, num_heads, res, scaling, x_cont=None, cemb=None, want_o=False):
+    """One attention layer.  x [B,Fc,E] (plus C continuous fields cemb[c] * x_cont[:, c] appended last when x_cont
+    [B,C] and cemb [C,E] are given), W* [E,E] (Wres only for res == 2) -> (y [B,F,E], stats [2,H,F,F], o [B,F,E] or
+    None).  res: 0 none, 1 + X, 2 + X Wres.  The softmax runs over the batch axis (see csrc/autoint.hip)."""
+    for t, n in ((x, "x"), (Wq, "Wq"), (Wk, "Wk"), (Wv, "Wv")):
+        _f32(t, n)
+    B, Fc, E = x.shape
+    C = 0 if x_cont is None else x_cont.shape[1]
+    if C:
+        _f32(x_cont, "x_cont"); _f32(cemb, "cemb")
+        if tuple(cemb.shape) != (C, E) or x_cont.shape[0] != B:
+            raise ValueError("x_cont [B,C] and cemb [C,E] do not match x %s" % (tuple(x.shape),))
+    if res == 2:
+        _f32(Wres, "Wres")
+    F, H = Fc + C, int(num_heads)
+    autoint_check_shape(F, E, H, C)
+    for t in (Wq, Wk, Wv) + ((Wres,) if res == 2 else ()):
+        if tuple(t.shape) != (E, E):
+            raise ValueError("attention weights must be [E,E] = [%d,%d], got %s" % (E, E, tuple(t.shape)))
+    dev = x.device
+    y = torch.empty((B, F, E), dtype=torch.float32, device=dev)
+    o = torch.empty((B, F, E), dtype=torch.float32, device=dev) if want_o else None
+    stats = torch.empty((2, H, F, F), dtype=torch.float32, device=dev)
+    if B > 0:
+        ws, nbytes = _autoint_ws(B, F, E, H, C, res, dev)
+        check(lib.rec_autoint_fwd_f32(_ptr(x), _ptr(x_cont) if C else None, _ptr(cemb) if C else None, _ptr(Wq),
+                                      _ptr(Wk), _ptr(Wv), _ptr(Wres) if res == 2 else None, B, F, E, H, C, res,
+                                      int(bool(scaling)), _ptr(y), _ptr(o) if want_o else None, _ptr(stats), _ptr(ws),
+                                      nbytes, _stream()), "rec_autoint_fwd_f32")
+    return y, stats, o
+
+
+def autoint_bwd(x, Wq, Wk, Wv, Wres, y, dy, stats, num_heads, res, scaling, x_cont=None, cemb=None):
+    """-> (dx [B,Fc,E], dWq, dWk, dWv, dWres (res == 2, else None), dcemb [C,E] (C > 0, else None))."""
+    for t, n in ((x, "x"), (Wq, "Wq"), (Wk, "Wk"), (Wv, "Wv"), (y, "y"), (dy, "dy"), (stats, "stats")):
+        _f32(t, n)
+    B, Fc, E = x.shape
+    C = 0 if x_cont is None else x_cont.shape[1]
+    F, H = Fc + C, int(num_heads)
+    autoint_check_shape(F, E, H, C)
+    if tuple(y.shape) != (B, F, E) or tuple(dy.shape) != (B, F, E) or tuple(stats.shape) != (2, H, F, F):
+        raise ValueError("y, dy [B,F,E] and stats [2,H,F,F] do not match x %s" % (tuple(x.shape),))
+    dev = x.device
+    dx = torch.empty_like(x)
+    dW = [torch.zeros((E, E), dtype=torch.float32, device=dev) for _ in range(3 + (res == 2))]
+    dcemb = torch.zeros((C, E), dtype=torch.float32, device=dev) if C else None
+    if B > 0:
+        ws, nbytes = _autoint_ws(B, F, E, H, C, res, dev)
+        check(lib.rec_autoint_bwd_f32(_ptr(x), _ptr(x_cont) if C else None, _ptr(cemb) if C else None, _ptr(Wq),
+                                      _ptr(Wk), _ptr(Wv), _ptr(Wres) if res == 2 else None, _ptr(y), _ptr(dy),
+                                      _ptr(stats), B, F, E, H, C, res, int(bool(scaling)), _ptr(dx), _ptr(dW[0]),
+                                      _ptr(dW[1]), _ptr(dW[2]), _ptr(dW[3]) if res == 2 else None,
+                                      _ptr(dcemb) if C else None, _ptr(ws), nbytes, _stream()), "rec_autoint_bwd_f32")
+    return dx, dW[0], dW[1], dW[2], (dW[3] if res == 2 else None), dcemb

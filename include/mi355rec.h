@@ -564,6 +564,30 @@ int rec_fibinet_bwd_f32(const float* x_emb, const float* g, const float* A, cons
                         float* dx_emb, float* dW, float* dS0, float* dS1, void* workspace, size_t workspace_bytes,
                         void* stream);
 
+/* ---- AutoInt multi-head field attention (TransformerAttentionLayer / AutoIntLayer, 3.DCN/CustomLayers.py:1012-1139;
+ * csrc/autoint.hip).  One layer over X [B, F, E], F = Fc + C fields: the Fc categorical rows come from x [B, Fc, E],
+ * the C continuous rows (last) are cemb[c, :] * x_cont[b, c] (cemb [C, E], x_cont [B, C]; both may be NULL when C == 0).
+ * H heads of width d = E / H, head h owns the columns [h d, (h+1) d):
+ *   Q = X Wq, K = X Wk, V = X Wv (each [E, E])      S[h,b,i,j] = scale Q_h[b,i,:] . K_h[b,j,:], scale = 1/sqrt(d) or 1
+ *   P = softmax of S over the BATCH axis b (the reference's tf.nn.softmax(axis=1) on (H, B, F, F))
+ *   O[b,i,h d + c] = sum_j P[h,b,i,j] V[b,j,h d + c]      Z = O (res 0) | O + X (res 1) | O + X Wres (res 2)
+ *   y = relu(Z) [B, F, E];  o [B, F, E] = O before the residual (may be NULL);  stats [2, H, F, F] = (max_b S, 1/sum_b
+ *   exp(S - max)) for the backward.
+ * The backward takes dy = dLoss/dy and writes dx [B, Fc, E] (categorical rows), dWq, dWk, dWv, dWres (res 2), dcemb
+ * [C, E] (C > 0).  Every output of one call depends on the whole batch.  No float atomics: bit-identical results run
+ * to run; no host synchronisation (graph-capturable).
+ * Supported: 1 <= F <= 64, 1 <= E <= 64, 1 <= H <= E with E % H == 0, 0 <= C < F, 0 <= B < 2^31 (B == 0: nothing is
+ * launched); otherwise -2.  A negative size, res outside 0..2, scaling outside 0..1 or a NULL pointer: -1.
+ * workspace: rec_autoint_workspace_bytes (0: invalid or unsupported shape), for either direction. */
+size_t rec_autoint_workspace_bytes(int64_t B, int F, int E, int H, int C, int res);
+int rec_autoint_fwd_f32(const float* x, const float* x_cont, const float* cemb, const float* Wq, const float* Wk,
+                        const float* Wv, const float* Wres, int64_t B, int F, int E, int H, int C, int res, int scaling,
+                        float* y, float* o, float* stats, void* workspace, size_t workspace_bytes, void* stream);
+int rec_autoint_bwd_f32(const float* x, const float* x_cont, const float* cemb, const float* Wq, const float* Wk,
+                        const float* Wv, const float* Wres, const float* y, const float* dy, const float* stats,
+                        int64_t B, int F, int E, int H, int C, int res, int scaling, float* dx, float* dWq, float* dWk,
+                        float* dWv, float* dWres, float* dcemb, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,8 @@ batches, one MI355X.  Prints one JSON line per config.  Usage:  python scripts/b
   G   SIM GSU inner-product attention (f4), T=100, V=50M, E=32, B=4096
   X   xDeepFM, 10 cat + 3 cont, V=10M, E=16, cin_size [16,32,64], units [64,8], B=16384; X26 = 26 cat fields
   FB  FiBiNet 'interaction', 10 cat + 3 cont, V=10M, E=16, units [128,16], B=16384; FB26 = 26 cat fields, B=8192
+  AI  AutoInt at the reference defaults, 10 cat + 3 cont, V=10M, E=8, H=2, 2 attention layers, units [128,16], B=16384;
+      AI26 = 26 cat + 3 cont, E=16, B=8192
 """
 import json
 import os
@@ -300,6 +302,19 @@ def run(name):
         P = ncat * (ncat - 1) // 2
         return {"config": "%s FiBiNet interaction, %d cat + 3 cont, 10M x 16d, units [128,16]" % (name, ncat), "B": B,
                 "V": V, "ms_per_step": dt * 1e3, "examples_per_s": B / dt, "dnn_in_mb": B * (2 * P * E + 3) * 4 / 1e6}
+    if name in ("AI", "AI26"):
+        ncat, B, E = (10, 16384, 8) if name == "AI" else (26, 8192, 16)
+        cat = ["c%d" % i for i in range(ncat)]
+        cont = ["x0", "x1", "x2"]
+        V = 10_000_000
+        layer = layers.AutoIntLayer(categorical_features=cat, continuous_features=cont, feature_dims=1000,
+                                    embedding_dims=E, units=[128, 16], attention_layer_num=2, num_heads=2).cuda()
+        layer.embedding_layer.embeddings = torch.nn.Parameter(torch.empty((V, E), device="cuda"))
+        big_table_(layer.embedding_layer.embeddings)
+        batch = data.to_device(data.SyntheticGenerator(cat, V, continuous=cont, seed=0).batch(B))
+        dt = timed(fwd_bwd(layer, batch, cat + cont), 5, 50)
+        return {"config": "%s AutoInt, %d cat + 3 cont, 10M x %dd, 2 layers x 2 heads, units [128,16]" % (name, ncat, E),
+                "B": B, "V": V, "ms_per_step": dt * 1e3, "examples_per_s": B / dt}
     if name == "FF":
         names = ["C%d" % i for i in range(26)]
         V, B, E = 10_000_000, 8192, 16
@@ -344,7 +359,8 @@ if __name__ == "__main__":
     GRAPHED = "--graphed" in sys.argv[1:]
     for n in (argv or ["A", "B", "C", "C26", "D", "E", "R", "P", "N", "FF", "G"]):
         r = run(n)
-        if GRAPHED and n in ("B", "C", "C26", "D", "E", "DS", "ES", "P", "N", "FF", "G", "X", "X26", "FB", "FB26"):
+        if GRAPHED and n in ("B", "C", "C26", "D", "E", "DS", "ES", "P", "N", "FF", "G", "X", "X26", "FB", "FB26", "AI",
+                                "AI26"):
             r["config"] += " [GraphedTrainStep]"
         r["n_gpus"] = 1
         print(json.dumps(r), flush=True)
