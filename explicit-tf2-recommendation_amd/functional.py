@@ -555,3 +555,28 @@ class AutoIntAttention(torch.autograd.Function):
         dx, dWq, dWk, dWv, dWres, dcemb = ops.autoint_bwd(x, Wq, Wk, Wv, Wres, y, g.contiguous(), stats, num_heads, res,
                                                           scaling, x_cont, cemb)
         return dx, None, dcemb, dWq, dWk, dWv, dWres, None, None, None
+
+
+class EmbAFM(torch.autograd.Function):
+    """Attentional FM pooling fused with the lookup (3.DCN/CustomLayers.py:825-853, 870-881; csrc/afm.hip): table, X
+    [B,F], attention_w (Wa [E,A], ba [A]), attention_h (hv [A,1], bh [1]) -> o [B,E] = sum_k softmax_k(s)_k e_i * e_j.
+    Backward: the sparse row gradient of the table and the four dense ones, one launch plus the slot sum.
+    ``SAVE_ROWS``: keep the gathered rows [B,F,E] for the backward instead of gathering them again (DESIGN.md 3.2 has
+    the measurement behind the default)."""
+
+    SAVE_ROWS = False
+
+    @staticmethod
+    def forward(ctx, table, X, Wa, ba, hv, bh, oob):
+        Wa, ba, hv, bh = Wa.contiguous(), ba.contiguous(), hv.contiguous(), bh.contiguous()
+        o, stats, rows = ops.emb_afm_fwd(table, X, Wa, ba, hv, bh, oob, want_rows=EmbAFM.SAVE_ROWS)
+        ctx.save_for_backward(table, X, Wa, ba, hv, bh, o, stats, rows)
+        return o
+
+    @staticmethod
+    def backward(ctx, g):
+        table, X, Wa, ba, hv, bh, o, stats, rows = ctx.saved_tensors
+        V, E = table.shape
+        vals, dWa, dba, dhv, dbh = ops.emb_afm_bwd(table, X, Wa, ba, hv, bh, o, stats, g.contiguous(), rows)
+        plan = ops.DedupPlan(X, V)
+        return _sparse_grad(plan, vals, E, (V, E)), None, dWa, dba, dhv, dbh, None

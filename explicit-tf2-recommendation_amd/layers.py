@@ -18,6 +18,9 @@ libmi355rec.so (through functional.py / ops.py).  Reference classes and the line
   BilinearInteractionLayer      3.DCN/CustomLayers.py:984-1011
   TransformerAttentionLayer     3.DCN/CustomLayers.py:1012-1067
   AutoIntLayer                  3.DCN/CustomLayers.py:1070-1139
+  InteractionLayer              3.DCN/CustomLayers.py:825-838
+  AttentionLayer                3.DCN/CustomLayers.py:841-853
+  AttentionalFactorizationMachine  3.DCN/CustomLayers.py:856-885
 
 Parameters are named after the TF checkpoint keys (``embed.embeddings``, ``w.embeddings``, ``bias``,
 ``MLP_layer1.kernel_0`` ...), so a TensorBundle checkpoint maps onto ``state_dict()`` by name.
@@ -773,6 +776,64 @@ class AutoIntLayer(Layer):
             att = layer.attend(att, x_cont, cemb) if k == 0 else layer.attend(att)
         dnn_input = att.reshape(att.shape[0], -1)                        # Flatten: field-major [B, F*E] (a view)
         return {"output": self.output_layer(self.dnn_layer(dnn_input))}
+
+
+class InteractionLayer(Layer):
+    """3.DCN/CustomLayers.py:825-838: the F(F-1)/2 products e_i * e_j, i < j, i outer and j inner.  It has no weights;
+    its forward runs fused with the lookup and the attention inside AttentionalFactorizationMachine (csrc/afm.hip)."""
+
+    def forward(self, inputs):
+        raise NotImplementedError("InteractionLayer runs fused inside AttentionalFactorizationMachine (csrc/afm.hip)")
+
+
+class AttentionLayer(Layer):
+    """3.DCN/CustomLayers.py:841-853: ``attention_w`` = Dense(attn_size, relu), ``attention_h`` = Dense(1), a softmax
+    over the pair axis and the weighted sum of the pairs.  Its forward runs fused inside
+    AttentionalFactorizationMachine (csrc/afm.hip); there is no separate kernel for it."""
+
+    def __init__(self, attn_size, input_dim=None):
+        super().__init__()
+        self.attn_size = int(attn_size)
+        self.attention_w = Dense(self.attn_size, activation="relu")
+        self.attention_h = Dense(1, activation=None, input_dim=self.attn_size)
+        self.built = False
+        if input_dim is not None:
+            self.build(input_dim)
+
+    def build(self, embedding_dims):
+        self.attention_w.build(int(embedding_dims))
+        self.built = True
+
+    def forward(self, inputs):
+        raise NotImplementedError("AttentionLayer runs fused inside AttentionalFactorizationMachine (csrc/afm.hip)")
+
+
+class AttentionalFactorizationMachine(Layer):
+    """3.DCN/CustomLayers.py:856-885: output = MLPLayer([1], sigmoid)(attention_layer(interaction_layer(
+    embedding_layer(X)))).  Categorical features only.  The lookup, the pairwise products, the attention and the pooling
+    are one kernel each way (functional.EmbAFM); the [E,1] head runs on the GEMM kernels."""
+
+    def __init__(self, categorical_features=["uid", "iid", "utag1", "utag2", "utag3", "utag4", "itag1", "itag2",
+                                             "itag3", "itag4"],
+                 feature_dims=150000, embedding_dims=16, attn_size=3):
+        super().__init__()
+        self.categorical_features = list(categorical_features)
+        F, E = len(self.categorical_features), int(embedding_dims)
+        ops.afm_check_shape(F, E, int(attn_size))
+        self.embedding_dims = E
+        self.interaction_layer = InteractionLayer()
+        self.attention_layer = AttentionLayer(attn_size=attn_size, input_dim=E)
+        self.embedding_layer = Embedding(feature_dims, E, embeddings_regularizer="l2")
+        self.output_layer = MLPLayer(units=[1], activation="sigmoid", input_dim=E)
+
+    def forward(self, inputs):
+        X = assemble_index(inputs, self.categorical_features)
+        flag = ops.new_flag(X.device) if self.check_ids else None
+        att = self.attention_layer
+        attention_output = Fn.EmbAFM.apply(self.embedding_layer.embeddings, X, att.attention_w.kernel,
+                                           att.attention_w.bias, att.attention_h.kernel, att.attention_h.bias, flag)
+        self._raise_if_oob(flag)
+        return {"output": self.output_layer(attention_output)}
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -178,6 +178,10 @@ class ModelManager:
             self.layer = CL.AutoIntLayer(
                 categorical_features=self.feature_names, continuous_features=self.continuous_features,
                 feature_dims=self.feature_dims, **p)
+        elif layer_name == "AFM":                          # 3.DCN/ModelManager.py:89-91 (categorical features only)
+            self.layer = CL.AttentionalFactorizationMachine(
+                categorical_features=self.feature_names, feature_dims=self.feature_dims,
+                embedding_dims=self.embedding_dims, attn_size=model_params.get("attn_size", 3))
         elif layer_name == "din_layer":                    # 5.DIN/ModelManager.py:72-73
             p = dict(model_params)
             p.setdefault("feature_dims", self.feature_dims)

@@ -786,3 +786,72 @@ def autoint_bwd(x, Wq, Wk, Wv, Wres, y, dy, stats, num_heads, res, scaling, x_co
                                       _ptr(dW[1]), _ptr(dW[2]), _ptr(dW[3]) if res == 2 else None,
                                       _ptr(dcemb) if C else None, _ptr(ws), nbytes, _stream()), "rec_autoint_bwd_f32")
     return dx, dW[0], dW[1], dW[2], (dW[3] if res == 2 else None), dcemb
+
+
+# ---- Attentional FM, fused with the lookup (csrc/afm.hip)
+AFM_MAX_F, AFM_MAX_E, AFM_MAX_A = 64, 64, 16
+
+
+def afm_check_shape(F, E, A):
+    """NotImplementedError for shapes the AFM kernels do not cover (the ABI would return -2)."""
+    if not (2 <= F <= AFM_MAX_F and 1 <= E <= AFM_MAX_E and 1 <= A <= AFM_MAX_A):
+        raise NotImplementedError(
+            "AFM kernels cover 2 <= fields <= %d, 1 <= embedding_dims <= %d and 1 <= attn_size <= %d; got fields=%d, "
+            "embedding_dims=%d, attn_size=%d" % (AFM_MAX_F, AFM_MAX_E, AFM_MAX_A, F, E, A))
+
+
+def _afm_params(E, Wa, ba, hv, bh):
+    for t, n in ((Wa, "Wa"), (ba, "ba"), (hv, "hv"), (bh, "bh")):
+        _f32(t, n)
+    A = Wa.shape[1]
+    if Wa.dim() != 2 or Wa.shape[0] != E or ba.numel() != A or hv.numel() != A or bh.numel() != 1:
+        raise ValueError("attention weights must be Wa [E,A], ba [A], hv [A,1], bh [1] with E = %d, got %s %s %s %s"
+                         % (E, tuple(Wa.shape), tuple(ba.shape), tuple(hv.shape), tuple(bh.shape)))
+    return A
+
+
+def emb_afm_fwd(table, X, Wa, ba, hv, bh, oob=None, want_rows=False):
+    """Lookup + pairwise products + attention pooling in one launch: -> (o [B,E], stats [B,2] = (max, sum exp) of the
+    pair softmax, rows [B,F,E] or None)."""
+    _table(table, "table"); _i64(X, "X")
+    V, E = table.shape
+    B, F = X.shape
+    A = _afm_params(E, Wa, ba, hv, bh)
+    afm_check_shape(F, E, A)
+    dev = table.device
+    o = torch.empty((B, E), dtype=torch.float32, device=dev)
+    stats = torch.empty((B, 2), dtype=torch.float32, device=dev)
+    rows = torch.empty((B, F, E), dtype=torch.float32, device=dev) if want_rows else None
+    check(lib.rec_emb_afm_fwd_f32(_ptr(table), V, E, table.stride(0), _ptr(X), B, F, A, _ptr(Wa), _ptr(ba), _ptr(hv),
+                                  _ptr(bh), _ptr(o), _ptr(stats), _ptr(rows), _ptr(oob), _stream()),
+          "rec_emb_afm_fwd_f32")
+    return o, stats, rows
+
+
+def emb_afm_bwd(table, X, Wa, ba, hv, bh, o, stats, dout, rows=None):
+    """-> (vals [B*F,E] IndexedSlices values in the order of X, dWa [E,A], dba [A], dhv (shape of hv), dbh [1]).  With
+    the forward's ``rows`` the table is not read again."""
+    _table(table, "table"); _i64(X, "X")
+    V, E = table.shape
+    B, F = X.shape
+    A = _afm_params(E, Wa, ba, hv, bh)
+    afm_check_shape(F, E, A)
+    for t, n in ((o, "o"), (stats, "stats"), (dout, "dout")):
+        _f32(t, n)
+    if tuple(o.shape) != (B, E) or tuple(dout.shape) != (B, E) or tuple(stats.shape) != (B, 2):
+        raise ValueError("o, dout [B,E] and stats [B,2] do not match X %s" % (tuple(X.shape),))
+    if rows is not None and tuple(_f32(rows, "rows").shape) != (B, F, E):
+        raise ValueError("rows must be [B,F,E]")
+    dev = table.device
+    vals = torch.empty((B * F, E), dtype=torch.float32, device=dev)
+    dWa, dba, dhv, dbh = (torch.zeros_like(t) for t in (Wa, ba, hv, bh))
+    if B > 0:
+        nbytes = lib.rec_afm_workspace_bytes(B, F, E, A)
+        if nbytes == 0:
+            raise NotImplementedError("rec_afm_workspace_bytes: unsupported AFM shape")
+        ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+        check(lib.rec_emb_afm_bwd_f32(_ptr(table), V, E, table.stride(0), _ptr(X), B, F, A, _ptr(Wa), _ptr(ba),
+                                      _ptr(hv), _ptr(bh), _ptr(o), _ptr(stats), _ptr(rows), _ptr(dout), _ptr(vals),
+                                      _ptr(dWa), _ptr(dba), _ptr(dhv), _ptr(dbh), _ptr(ws), nbytes, _stream()),
+              "rec_emb_afm_bwd_f32")
+    return vals, dWa, dba, dhv, dbh

@@ -588,6 +588,29 @@ int rec_autoint_bwd_f32(const float* x, const float* x_cont, const float* cemb, 
                         int64_t B, int F, int E, int H, int C, int res, int scaling, float* dx, float* dWq, float* dWk,
                         float* dWv, float* dWres, float* dcemb, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Attentional Factorization Machine, fused with the lookup (InteractionLayer / AttentionLayer /
+ * AttentionalFactorizationMachine, 3.DCN/CustomLayers.py:825-885; csrc/afm.hip).  X int64 [B, F], table [V, E] with row
+ * stride ld; Wa [E, A], ba [A] (attention_w), hv [A] (attention_h kernel [A, 1]), bh [1]:
+ *   e_f = table[X[b,f]]      p_k = e_i * e_j for the P = F(F-1)/2 pairs i < j (i outer, j inner)
+ *   s_k = relu(p_k Wa + ba) . hv + bh      a = softmax over the pairs k      o [B, E] = sum_k a_k p_k
+ * The forward writes o, stats [B, 2] = (max_k s_k, sum_k exp(s_k - max)) and, when `rows` is not NULL, the gathered rows
+ * [B, F, E]; an id outside [0, V) sets *oob_flag (may be NULL) and reads as a zero row.
+ * The backward takes dout = dLoss/do [B, E] and writes vals [B*F, E], the IndexedSlices values of the lookup in the
+ * order of X, and dWa [E, A], dba [A], dhv [A], dbh [1].  With `rows` (the forward's) it does not touch the table and X
+ * (both may then be NULL); with rows == NULL it gathers again.  No float atomics: bit-identical results run to run; no
+ * host synchronisation (graph-capturable).
+ * Supported: 2 <= F <= 64, 1 <= E <= 64, 1 <= A <= 16, 0 <= B < 2^31 (B == 0: nothing is launched), V < 2^31;
+ * otherwise -2.  A negative size, V <= 0, ld < E or a NULL pointer: -1.
+ * workspace (backward only): rec_afm_workspace_bytes (0: invalid or unsupported shape). */
+size_t rec_afm_workspace_bytes(int64_t B, int F, int E, int A);
+int rec_emb_afm_fwd_f32(const float* table, int64_t V, int E, int64_t ld, const int64_t* X, int64_t B, int F, int A,
+                        const float* Wa, const float* ba, const float* hv, const float* bh, float* o, float* stats,
+                        float* rows, int* oob_flag, void* stream);
+int rec_emb_afm_bwd_f32(const float* table, int64_t V, int E, int64_t ld, const int64_t* X, int64_t B, int F, int A,
+                        const float* Wa, const float* ba, const float* hv, const float* bh, const float* o,
+                        const float* stats, const float* rows, const float* dout, float* vals, float* dWa, float* dba,
+                        float* dhv, float* dbh, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
