@@ -15,7 +15,7 @@
 //                        (dp_k = a_k do + Wa dpre_k) and writes the IndexedSlices values; then dWa = sum_k p_k (x)
 //                        dpre_k with one thread per (element, share of the pairs).  The parameter gradients stay in
 //                        registers over the tiles of a workgroup and go to a slot of its own;
-//   afm_slot_sum_kernel  adds the slots in slot order.
+//   and rec_slot_sum adds the slots in its wave order.
 // Wa, ba, hv are read with wave-uniform addresses straight from global memory (scalar loads).  No float atomics:
 // gradients are bit-identical run to run.  Scores are computed by ONE routine with explicit fmas (fp contraction is off
 // in this file), so the backward sees exactly the forward's s_k: at F = 2, a == 1, o == p_0 and dWa == dba == dhv == 0
@@ -32,7 +32,7 @@ constexpr int AFM_MAXF = 64, AFM_MAXE = 64, AFM_MAXA = 16;
 constexpr int AFM_MAXG = 1024;                  // workgroups (= workspace slots) of the backward
 constexpr int AFM_WPT = 16;                     // dWa elements per thread: E A <= 1024 over >= 64 threads
 constexpr size_t AFM_LDS_SOFT = 64 * 1024;      // what a workgroup aims for
-constexpr size_t AFM_LDS_MAX = 160 * 1024;      // LDS of one CU (gfx950)
+constexpr size_t AFM_LDS_MAX = REC_LDS_CU_BYTES;
 
 struct AfmShape {
   int64_t B, V, ld;
@@ -416,26 +416,6 @@ __global__ __launch_bounds__(AFM_NT) void emb_afm_bwd_kernel(AfmShape s, int EPW
   }
 }
 
-// out[t] = sum over the slots (stride n) in a fixed order, one wave per element; element t lands in one of four
-// destination segments of lengths len[0..3]
-struct AfmDst {
-  float* p[4];
-  int len[4];
-};
-
-__global__ __launch_bounds__(256) void afm_slot_sum_kernel(int n, int nslot, const float* __restrict__ sl, AfmDst dst) {
-  const int t = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (t >= n) return;
-  float acc = 0.f;
-  for (int k = lane; k < nslot; k += 64) acc += sl[(int64_t)k * n + t];
-  acc = group_sum<64>(acc);
-  if (lane == 0) {
-    int u = t, seg = 0;
-    while (u >= dst.len[seg]) u -= dst.len[seg++];
-    dst.p[seg][u] = acc;
-  }
-}
-
 // 0 ok (B == 0 included), REC_E_ARG, REC_E_UNSUPPORTED
 static int afm_shape(int64_t B, int F, int E, int A, int64_t V, int64_t ld, AfmShape* s) {
   if (B < 0 || F < 0 || E < 0 || A < 0 || V <= 0 || ld < E) return REC_E_ARG;
@@ -481,17 +461,8 @@ static AfmCfg afm_cfg(const AfmShape& s) {
 }
 
 static size_t afm_ws_bytes(const AfmShape& s, const AfmCfg& k) {
-  return (((size_t)k.grid[1] * (s.E * s.A + 2 * s.A + 1)) * sizeof(float) + 255) & ~(size_t)255;
+  return rec_align_up((size_t)k.grid[1] * (s.E * s.A + 2 * s.A + 1) * sizeof(float), 256);
 }
-
-#define AFM_ALLOW_LDS(KERNEL, BYTES)                                                                                 \
-  do {                                                                                                               \
-    if ((BYTES) > 65536) {             /* once per kernel, at the full budget: not again inside a capture */        \
-      static const hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL),                       \
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, AFM_LDS_MAX);    \
-      if (e_ != hipSuccess) return (int)e_;                                                                          \
-    }                                                                                                                \
-  } while (0)
 
 struct AfmFwdArgs {
   const float* table; const int64_t* X; const float *Wa, *ba, *hv, *bh;
@@ -504,7 +475,7 @@ struct AfmBwdArgs {
 
 template <bool VEC, int AC>
 static int afm_fwd_launch(const AfmShape& s, const AfmCfg& k, int gvec, const AfmFwdArgs& a, hipStream_t st) {
-  AFM_ALLOW_LDS((emb_afm_fwd_kernel<VEC, AC>), k.lds[0]);
+  if (hipError_t e = rec_allow_lds<emb_afm_fwd_kernel<VEC, AC>>(AFM_LDS_MAX)) return (int)e;
   hipLaunchKernelGGL((emb_afm_fwd_kernel<VEC, AC>), dim3(k.grid[0]), dim3(k.nthr[0]), k.lds[0], st, s, k.epw[0], gvec,
                      a.table, a.X, a.Wa, a.ba, a.hv, a.bh, a.o, a.stats, a.rows, a.oob);
   REC_LAUNCH_CHECK();
@@ -513,7 +484,7 @@ static int afm_fwd_launch(const AfmShape& s, const AfmCfg& k, int gvec, const Af
 
 template <bool VEC, int AC>
 static int afm_bwd_launch(const AfmShape& s, const AfmCfg& k, int gvec, const AfmBwdArgs& a, hipStream_t st) {
-  AFM_ALLOW_LDS((emb_afm_bwd_kernel<VEC, AC>), k.lds[1]);
+  if (hipError_t e = rec_allow_lds<emb_afm_bwd_kernel<VEC, AC>>(AFM_LDS_MAX)) return (int)e;
   hipLaunchKernelGGL((emb_afm_bwd_kernel<VEC, AC>), dim3(k.grid[1]), dim3(k.nthr[1]), k.lds[1], st, s, k.epw[1], gvec,
                      a.table, a.X, a.Wa, a.ba, a.hv, a.bh, a.o, a.stats, a.rows, a.dout, a.vals, a.slots);
   REC_LAUNCH_CHECK();
@@ -547,8 +518,6 @@ static int afm_bwd_dispatch(const AfmShape& s, const AfmCfg& k, int gvec, const 
   AFM_DISPATCH(afm_bwd_launch, s, k, gvec, a, st);
 }
 
-static inline bool afm_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 extern "C" size_t rec_afm_workspace_bytes(int64_t B, int F, int E, int A) {
@@ -568,7 +537,7 @@ extern "C" int rec_emb_afm_fwd_f32(const float* table, int64_t V, int E, int64_t
   if (!table || !X || !Wa || !ba || !hv || !bh || !o || !stats) return REC_E_ARG;
   const AfmCfg k = afm_cfg(s);
   if (k.lds[0] > AFM_LDS_MAX) return REC_E_UNSUPPORTED;
-  const int gvec = s.vec && ld % 4 == 0 && afm_al16(table) && (!rows || afm_al16(rows));
+  const int gvec = s.vec && ld % 4 == 0 && rec_is_aligned16(table) && (!rows || rec_is_aligned16(rows));
   const AfmFwdArgs a{table, X, Wa, ba, hv, bh, o, stats, rows, oob_flag};
   return afm_fwd_dispatch(s, k, gvec, a, as_stream(stream));
 }
@@ -587,20 +556,11 @@ extern "C" int rec_emb_afm_bwd_f32(const float* table, int64_t V, int E, int64_t
   const AfmCfg k = afm_cfg(s);
   if (k.lds[1] > AFM_LDS_MAX) return REC_E_UNSUPPORTED;
   if (workspace_bytes < afm_ws_bytes(s, k)) return REC_E_WORKSPACE;
-  const int gvec = s.vec && (rows ? afm_al16(rows) : (ld % 4 == 0 && afm_al16(table)));
+  const int gvec = s.vec && (rows ? rec_is_aligned16(rows) : (ld % 4 == 0 && rec_is_aligned16(table)));
   hipStream_t st = as_stream(stream);
   const AfmBwdArgs a{table, X, Wa, ba, hv, bh, o, stats, rows, dout, vals, static_cast<float*>(workspace)};
   const int r = afm_bwd_dispatch(s, k, gvec, a, st);
   if (r != REC_OK) return r;
-  const int n = E * A + 2 * A + 1;
-  AfmDst dst{};
-  float* outs[4] = {dWa, dba, dhv, dbh};
-  const int lens[4] = {E * A, A, A, 1};
-  for (int q = 0; q < 4; ++q) {
-    dst.p[q] = outs[q];
-    dst.len[q] = lens[q];
-  }
-  hipLaunchKernelGGL(afm_slot_sum_kernel, dim3((n + 3) / 4), dim3(256), 0, st, n, k.grid[1], a.slots, dst);
-  REC_LAUNCH_CHECK();
-  return REC_OK;
+  return rec_slot_sum(REC_SLOTS_WAVE, E * A + 2 * A + 1, k.grid[1], a.slots,
+                      {{dWa, dba, dhv, dbh}, {E * A, A, A, 1}}, st);
 }

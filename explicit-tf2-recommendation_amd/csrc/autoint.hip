@@ -35,7 +35,7 @@ constexpr int AI_MAXF = 64, AI_MAXE = 64;
 constexpr int AI_MAXG = 512;                   // workgroups (= workspace slots) of the persistent kernels
 constexpr int AI_TBMAX = 32;                   // examples per tile
 constexpr int AI_LDS_SOFT = 16384;             // floats of LDS a tile aims for (64 KiB: two workgroups per CU)
-constexpr int AI_LDS_MAX = 160 * 1024;         // LDS of one CU (gfx950); one example of the backward needs <= 128 KiB
+constexpr size_t AI_LDS_MAX = REC_LDS_CU_BYTES;   // one example of the backward needs <= 128 KiB
 
 struct AiShape {
   int64_t B;
@@ -147,26 +147,6 @@ __global__ __launch_bounds__(256) void autoint_ml_reduce_kernel(int HFF, int nsl
   if (lane == 0) {
     stats[t] = m;
     stats[HFF + t] = 1.f / l;
-  }
-}
-
-// out[k] = sum over the slots (stride n) in a fixed order, one wave per element; the element lands in one of up to
-// 5 destination segments of lengths len[0..4]
-struct AiDst {
-  float* p[5];
-  int len[5];
-};
-
-__global__ __launch_bounds__(256) void autoint_slot_sum_kernel(int n, int nslot, const float* __restrict__ sl, AiDst dst) {
-  const int t = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (t >= n) return;
-  float acc = 0.f;
-  for (int k = lane; k < nslot; k += 64) acc += sl[(int64_t)k * n + t];
-  acc = group_sum<64>(acc);
-  if (lane == 0) {
-    int u = t, seg = 0;
-    while (u >= dst.len[seg]) u -= dst.len[seg++];
-    dst.p[seg][u] = acc;
   }
 }
 
@@ -491,7 +471,7 @@ static AiCfg ai_cfg(const AiShape& s) {
   return k;
 }
 
-static size_t ai_align(size_t n) { return (n * sizeof(float) + 255) & ~(size_t)255; }
+static size_t ai_align(size_t n) { return rec_align_up(n * sizeof(float), 256); }
 
 // forward: ml slots [grid0][2][HFF]; backward: c slots [grid2][HFF] | c [HFF] | dW slots [grid3][nWE]
 static size_t ai_ws_bytes(const AiShape& s, const AiCfg& k) {
@@ -500,20 +480,11 @@ static size_t ai_ws_bytes(const AiShape& s, const AiCfg& k) {
   return fwd > bwd ? fwd : bwd;
 }
 
-#define AI_ALLOW_LDS(KERNEL, BYTES)                                                                                  \
-  do {                                                                                                               \
-    if ((BYTES) > 65536) {             /* once per kernel, at the full budget: not again inside a capture */        \
-      static const hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL),                       \
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, AI_LDS_MAX);     \
-      if (e_ != hipSuccess) return (int)e_;                                                                          \
-    }                                                                                                                \
-  } while (0)
-
 template <int DC>
 static int ai_fwd_out(const AiShape& s, const AiCfg& k, const float* x, const float* xc, const float* ce,
                       const float* Wq, const float* Wk, const float* Wv, const float* Wr, const float* stats, float* y,
                       float* o, hipStream_t st) {
-  AI_ALLOW_LDS(autoint_fwd_out_kernel<DC>, k.lds[1]);
+  if (hipError_t e = rec_allow_lds<autoint_fwd_out_kernel<DC>>(AI_LDS_MAX)) return (int)e;
   hipLaunchKernelGGL(autoint_fwd_out_kernel<DC>, dim3(k.grid[1]), dim3(AI_NT), k.lds[1], st, s, k.tb[1], x, xc, ce, Wq,
                      Wk, Wv, Wr, stats, y, o);
   REC_LAUNCH_CHECK();
@@ -524,7 +495,7 @@ template <int DC>
 static int ai_bwd_main(const AiShape& s, const AiCfg& k, const float* x, const float* xc, const float* ce,
                        const float* Wq, const float* Wk, const float* Wv, const float* Wr, const float* y,
                        const float* dy, const float* stats, const float* cvec, float* dx, float* dws, hipStream_t st) {
-  AI_ALLOW_LDS(autoint_bwd_main_kernel<DC>, k.lds[3]);
+  if (hipError_t e = rec_allow_lds<autoint_bwd_main_kernel<DC>>(AI_LDS_MAX)) return (int)e;
   hipLaunchKernelGGL(autoint_bwd_main_kernel<DC>, dim3(k.grid[3]), dim3(AI_NT), k.lds[3], st, s, k.tb[3], x, xc, ce,
                      Wq, Wk, Wv, Wr, y, dy, stats, cvec, dx, dws);
   REC_LAUNCH_CHECK();
@@ -552,7 +523,7 @@ extern "C" int rec_autoint_fwd_f32(const float* x, const float* x_cont, const fl
   if (workspace_bytes < ai_ws_bytes(s, k)) return REC_E_WORKSPACE;
   float* ml = static_cast<float*>(workspace);
   hipStream_t st = as_stream(stream);
-  AI_ALLOW_LDS(autoint_fwd_stats_kernel, k.lds[0]);
+  if (hipError_t e = rec_allow_lds<autoint_fwd_stats_kernel>(AI_LDS_MAX)) return (int)e;
   hipLaunchKernelGGL(autoint_fwd_stats_kernel, dim3(k.grid[0]), dim3(AI_NT), k.lds[0], st, s, k.tb[0], x, x_cont, cemb,
                      Wq, Wk, ml);
   REC_LAUNCH_CHECK();
@@ -587,16 +558,12 @@ extern "C" int rec_autoint_bwd_f32(const float* x, const float* x_cont, const fl
   float* cvec = reinterpret_cast<float*>(reinterpret_cast<char*>(cs) + ai_align((size_t)k.grid[2] * s.HFF));
   float* dws = reinterpret_cast<float*>(reinterpret_cast<char*>(cvec) + ai_align((size_t)s.HFF));
   hipStream_t st = as_stream(stream);
-  AI_ALLOW_LDS(autoint_bwd_stats_kernel, k.lds[2]);
+  if (hipError_t e = rec_allow_lds<autoint_bwd_stats_kernel>(AI_LDS_MAX)) return (int)e;
   hipLaunchKernelGGL(autoint_bwd_stats_kernel, dim3(k.grid[2]), dim3(AI_NT), k.lds[2], st, s, k.tb[2], x, x_cont, cemb,
                      Wq, Wk, Wv, y, dy, stats, cs);
   REC_LAUNCH_CHECK();
-  AiDst one{};
-  one.p[0] = cvec;
-  one.len[0] = s.HFF;
-  hipLaunchKernelGGL(autoint_slot_sum_kernel, dim3((s.HFF + 3) / 4), dim3(256), 0, st, s.HFF, k.grid[2], cs, one);
-  REC_LAUNCH_CHECK();
-  int r;
+  int r = rec_slot_sum(REC_SLOTS_WAVE, s.HFF, k.grid[2], cs, {{cvec}, {s.HFF}}, st);
+  if (r != REC_OK) return r;
   switch (s.d) {
     case 1: r = ai_bwd_main<1>(s, k, x, x_cont, cemb, Wq, Wk, Wv, Wres, y, dy, stats, cvec, dx, dws, st); break;
     case 2: r = ai_bwd_main<2>(s, k, x, x_cont, cemb, Wq, Wk, Wv, Wres, y, dy, stats, cvec, dx, dws, st); break;
@@ -614,15 +581,8 @@ extern "C" int rec_autoint_bwd_f32(const float* x, const float* x_cont, const fl
       break;
   }
   if (r != REC_OK) return r;
-  AiDst dst{};
   const int EE = E * E;
-  float* outs[5] = {dWq, dWk, dWv, res == 2 ? dWres : dcemb, dcemb};
-  int lens[5] = {EE, EE, EE, res == 2 ? EE : C * E, res == 2 ? C * E : 0};
-  for (int q = 0; q < 5; ++q) {
-    dst.p[q] = outs[q];
-    dst.len[q] = lens[q];
-  }
-  hipLaunchKernelGGL(autoint_slot_sum_kernel, dim3((s.nWE + 3) / 4), dim3(256), 0, st, s.nWE, k.grid[3], dws, dst);
-  REC_LAUNCH_CHECK();
-  return REC_OK;
+  return rec_slot_sum(REC_SLOTS_WAVE, s.nWE, k.grid[3], dws,
+                      {{dWq, dWk, dWv, res == 2 ? dWres : dcemb, dcemb},
+                       {EE, EE, EE, res == 2 ? EE : C * E, res == 2 ? C * E : 0}}, st);
 }

@@ -14,14 +14,14 @@
 //   dX^k[n] = sum_m X0[m] S[m*H_k + n]     dX0[m] += sum_n X^k[n] S[m*H_k + n]      (VALU on the MFMA result)
 //   dW_k   += A_k^T G^{k+1}                (MFMA, K = the tile's rows)
 // Each workgroup adds its tiles' dW into a slot of its own in the workspace (a fixed order of tiles), and
-// cin_dw_reduce_kernel sums the slots in slot order: no float atomics, bit-identical gradients run to run.
+// rec_slot_sum adds the slots in slot order (serial): no float atomics, bit-identical gradients run to run.
 #include "common.h"
 
 namespace {
 
 constexpr int CIN_NT = 256;                       // 4 waves
 constexpr int CIN_MAXL = 8;
-constexpr size_t CIN_LDS_BUDGET = 160 * 1024;     // LDS of one CU (gfx950)
+constexpr size_t CIN_LDS_BUDGET = REC_LDS_CU_BYTES;
 constexpr size_t CIN_WS_CAP = (size_t)512 << 20;  // bytes of dW slots the backward may ask for
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -323,20 +323,6 @@ __global__ __launch_bounds__(CIN_NT) void cin_bwd_kernel(CinShape s, const float
   }
 }
 
-// dW_k[i] = sum over the slots, in slot order
-__global__ __launch_bounds__(256) void cin_dw_reduce_kernel(CinShape s, const float* __restrict__ slots, int nslot,
-                                                            float* dw0, float* dw1, float* dw2,
-                                                            float* dw3, float* dw4, float* dw5, float* dw6, float* dw7) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= s.wsum) return;
-  float acc = 0.f;
-  for (int w = 0; w < nslot; ++w) acc += slots[(int64_t)w * s.wsum + i];
-  int k = 0;
-  while (k + 1 < s.L && i >= s.woff[k + 1]) ++k;
-  float* dst[CIN_MAXL] = {dw0, dw1, dw2, dw3, dw4, dw5, dw6, dw7};
-  dst[k][i - s.woff[k]] = acc;
-}
-
 struct CinCfg {
   int RT, ng, RP;
   size_t lds;
@@ -410,11 +396,7 @@ static bool cin_bwd_cfg(const CinShape& s, CinCfg* cfg, int* grid) {
 template <int RT>
 static int cin_launch_fwd(const CinShape& s, const CinCfg& cfg, int TB, const float* x0, float* states, float* cin,
                           hipStream_t st) {
-  if (cfg.lds > 65536) {                           // once per kernel, at the full budget: not again inside a capture
-    static const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(cin_fwd_kernel<RT>),
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)CIN_LDS_BUDGET);
-    if (e != hipSuccess) return (int)e;
-  }
+  if (hipError_t e = rec_allow_lds<cin_fwd_kernel<RT>>(CIN_LDS_BUDGET)) return (int)e;
   const int64_t grid = (s.B + TB - 1) / TB;
   hipLaunchKernelGGL(cin_fwd_kernel<RT>, dim3((unsigned)grid), dim3(CIN_NT), cfg.lds, st, s, x0, TB, cfg.RP, cfg.ng,
                      states, cin);
@@ -425,11 +407,7 @@ static int cin_launch_fwd(const CinShape& s, const CinCfg& cfg, int TB, const fl
 template <int RT>
 static int cin_launch_bwd(const CinShape& s, const CinCfg& cfg, int grid, const float* x0, const float* states,
                           const float* g, float* dx0, float* slots, hipStream_t st) {
-  if (cfg.lds > 65536) {                           // once per kernel, at the full budget: not again inside a capture
-    static const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(cin_bwd_kernel<RT>),
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)CIN_LDS_BUDGET);
-    if (e != hipSuccess) return (int)e;
-  }
+  if (hipError_t e = rec_allow_lds<cin_bwd_kernel<RT>>(CIN_LDS_BUDGET)) return (int)e;
   hipLaunchKernelGGL(cin_bwd_kernel<RT>, dim3(grid), dim3(CIN_NT), cfg.lds, st, s, x0, states, g, cfg.RP, cfg.ng, dx0,
                      slots);
   REC_LAUNCH_CHECK();
@@ -462,12 +440,8 @@ extern "C" int rec_cin_fwd_f32(const float* x0, int64_t B, int F, int E, int L, 
   if (!cin_pick((F | 1) + 2 * (cin_hmax(s, false) | 1), E, &cfg)) return REC_E_UNSUPPORTED;
   const int TB = cfg.RP / E;
   hipStream_t st = as_stream(stream);
-  switch (cfg.RT) {
-    case 1: return cin_launch_fwd<1>(s, cfg, TB, x0, states, cin_part, st);
-    case 2: return cin_launch_fwd<2>(s, cfg, TB, x0, states, cin_part, st);
-    case 3: return cin_launch_fwd<3>(s, cfg, TB, x0, states, cin_part, st);
-    default: return cin_launch_fwd<4>(s, cfg, TB, x0, states, cin_part, st);
-  }
+  return rec_dispatch_1to4(cfg.RT,
+                           [&](auto rt) { return cin_launch_fwd<rt.value>(s, cfg, TB, x0, states, cin_part, st); });
 }
 
 extern "C" int rec_cin_bwd_f32(const float* x0, const float* states, const float* g, int64_t B, int F, int E, int L,
@@ -477,11 +451,12 @@ extern "C" int rec_cin_bwd_f32(const float* x0, const float* states, const float
   const int rc = cin_shape(B, F, E, L, H_host, &s);
   if (rc != REC_OK) return rc;
   if (!x0 || !states || !g || !W_host || !dx0 || !dW_host || !workspace) return REC_E_ARG;
-  float* dw[CIN_MAXL] = {};
+  SlotDst dw{};                                      // layer k's dW is segment k of a slot
   for (int k = 0; k < L; ++k) {
     if (!W_host[k] || !dW_host[k]) return REC_E_ARG;
     s.W[k] = W_host[k];
-    dw[k] = dW_host[k];
+    dw.p[k] = dW_host[k];
+    dw.len[k] = F * s.H[k] * s.H[k + 1];
   }
   CinCfg cfg;
   int grid;
@@ -489,16 +464,8 @@ extern "C" int rec_cin_bwd_f32(const float* x0, const float* states, const float
   if (workspace_bytes < (size_t)grid * (size_t)s.wsum * sizeof(float)) return REC_E_WORKSPACE;
   hipStream_t st = as_stream(stream);
   float* slots = static_cast<float*>(workspace);
-  int r;
-  switch (cfg.RT) {
-    case 1: r = cin_launch_bwd<1>(s, cfg, grid, x0, states, g, dx0, slots, st); break;
-    case 2: r = cin_launch_bwd<2>(s, cfg, grid, x0, states, g, dx0, slots, st); break;
-    case 3: r = cin_launch_bwd<3>(s, cfg, grid, x0, states, g, dx0, slots, st); break;
-    default: r = cin_launch_bwd<4>(s, cfg, grid, x0, states, g, dx0, slots, st); break;
-  }
+  const int r = rec_dispatch_1to4(
+      cfg.RT, [&](auto rt) { return cin_launch_bwd<rt.value>(s, cfg, grid, x0, states, g, dx0, slots, st); });
   if (r != REC_OK) return r;
-  hipLaunchKernelGGL(cin_dw_reduce_kernel, dim3((unsigned)((s.wsum + 255) / 256)), dim3(256), 0, st, s, slots, grid,
-                     dw[0], dw[1], dw[2], dw[3], dw[4], dw[5], dw[6], dw[7]);
-  REC_LAUNCH_CHECK();
-  return REC_OK;
+  return rec_slot_sum(REC_SLOTS_SERIAL, (int)s.wsum, grid, slots, dw, st);   // wsum <= 8 * 64 * 256 * 256: fits int
 }

@@ -414,10 +414,8 @@ static int colsort_plan(const int64_t* const* cols_host, int F, int64_t B, int64
   // one workgroup per column (LDS radix sort + run heads in one launch); B <= 16384 = 16 x 1024
   const int kpt = B <= 8192 ? 8 : 16;
   // words + per-wave counters (the 16-bit staging arrays of the outputs reuse them) + block-scan scratch
-  const size_t lds = sizeof(uint32_t) * ((size_t)CS_T * kpt + CS_W * CS_BINS + CS_W);
-  const void* fn = kpt == 8 ? reinterpret_cast<const void*>(colsort_kernel<8>)
-                            : reinterpret_cast<const void*>(colsort_kernel<16>);
-  const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  const size_t lds = sizeof(uint32_t) * ((size_t)CS_T * kpt + CS_W * CS_BINS + CS_W);   // one size per kpt
+  const hipError_t e = kpt == 8 ? rec_allow_lds<colsort_kernel<8>>(lds) : rec_allow_lds<colsort_kernel<16>>(lds);
   if (e != hipSuccess) return (int)e;
   if (kpt == 8)
     hipLaunchKernelGGL(colsort_kernel<8>, dim3(F), dim3(CS_T), lds, st, cp, col_lo, a);

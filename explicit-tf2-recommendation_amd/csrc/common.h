@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "mi355rec.h"
 
 #define REC_WAVE 64
@@ -86,3 +87,51 @@ __device__ __forceinline__ void adam_decay(float& x, float& m, float& v, float l
   x = adam_step_x(x, m, v, lr_t, eps);
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// host-side launch support: the one copy of what every kernel file needs around a launch
+// ------------------------------------------------------------------------------------------------------------------
+constexpr size_t REC_LDS_CU_BYTES = 160 * 1024;   // LDS of one CU (gfx950)
+
+// `a` is a power of two
+static inline size_t rec_align_up(size_t x, size_t a) { return (x + a - 1) & ~(a - 1); }
+static inline bool rec_is_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// Lets Kernel be launched with up to cap_bytes of dynamic LDS; nothing to do up to 64 KiB.  cap_bytes is the most its
+// launcher can ever ask for (minus the kernel's static LDS), not the size of one launch: the attribute is set once per
+// kernel and process -- never again on the launch path or inside a graph capture -- and every later call returns what
+// that first call returned.  It bounds the launch size only; occupancy follows the size given at launch.  The once-flag
+// is per kernel VALUE (two instantiations of one template share a type).  One process drives one device everywhere
+// here, so once per process is once per device.
+template <auto Kernel>
+static hipError_t rec_allow_lds(size_t cap_bytes) {
+  if (cap_bytes <= 64 * 1024) return hipSuccess;
+  static const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel),
+                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)cap_bytes);
+  return e;
+}
+
+// f(std::integral_constant<int, c>) for c = clamp(n, 1, 4): the one spelling of a 1..4 template dispatch
+template <class Fn>
+static inline int rec_dispatch_1to4(int n, Fn&& f) {
+  switch (n) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    default: return f(std::integral_constant<int, 4>{});
+  }
+}
+
+// Deterministic sums of per-workgroup partials (slot_sum.hip): out[t] = sum_s slots[s * n + t] for t < n, where element
+// t lands in one of up to 8 destination segments of lengths len[0], len[1], ... (their sum is n).  Two orders of
+// addition, and a caller keeps the one its results were defined with:
+//   wave    one wave per element: lane l adds slots l, l + 64, ... in order, then the xor butterfly of group_sum<64>
+//   serial  one thread per element: slots 0, 1, ..., nslot - 1 in order
+struct SlotDst {
+  float* p[8];
+  int len[8];
+};
+enum RecSlotOrder { REC_SLOTS_WAVE, REC_SLOTS_SERIAL };
+
+// call as rec_slot_sum(order, n, nslot, slots, {{p0, p1, ...}, {len0, len1, ...}}, stream); REC_OK or an error code
+__attribute__((visibility("hidden"))) int rec_slot_sum(RecSlotOrder order, int n, int nslot, const float* slots,
+                                                       const SlotDst& dst, hipStream_t st);

@@ -33,18 +33,17 @@ struct Layout {
   size_t keys_tmp, keys_out, pos_tmp, hist, tot, tile_heads, total;
 };
 
-inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
 Layout make_layout(int64_t n) {
   Layout L;
   size_t off = 0;
   const size_t nb = (size_t)ceil_div64(n, RS_TILE);
-  L.keys_tmp = off; off = align256(off + sizeof(uint32_t) * n);
-  L.keys_out = off; off = align256(off + sizeof(uint32_t) * n);
-  L.pos_tmp = off; off = align256(off + sizeof(int32_t) * n);
-  L.hist = off; off = align256(off + sizeof(uint32_t) * RS_BINS * nb);
-  L.tot = off; off = align256(off + sizeof(uint32_t) * RS_BINS);
-  L.tile_heads = off; off = align256(off + sizeof(int32_t) * (size_t)(ceil_div64(n, TILE) + 1));
+  L.keys_tmp = off; off = rec_align_up(off + sizeof(uint32_t) * n, 256);
+  L.keys_out = off; off = rec_align_up(off + sizeof(uint32_t) * n, 256);
+  L.pos_tmp = off; off = rec_align_up(off + sizeof(int32_t) * n, 256);
+  L.hist = off; off = rec_align_up(off + sizeof(uint32_t) * RS_BINS * nb, 256);
+  L.tot = off; off = rec_align_up(off + sizeof(uint32_t) * RS_BINS, 256);
+  L.tile_heads = off; off = rec_align_up(off + sizeof(int32_t) * (size_t)(ceil_div64(n, TILE) + 1), 256);
   L.total = off;
   return L;
 }
@@ -678,8 +677,7 @@ extern "C" int rec_segment_sum_f32(const float* vals, int E, const int32_t* perm
   else CHUNK(256);
 #undef CHUNK
   REC_LAUNCH_CHECK();
-  bool vec = E % 4 == 0 && (reinterpret_cast<uintptr_t>(vals) & 15) == 0 &&
-             (reinterpret_cast<uintptr_t>(out) & 15) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0;
+  bool vec = E % 4 == 0 && rec_is_aligned16(vals) && rec_is_aligned16(out) && rec_is_aligned16(workspace);
   if (vec) {
     int lpr = E / 4;
     hipLaunchKernelGGL(segsum_vec_kernel, dim3((unsigned)ceil_div64(n * lpr, 256)), dim3(256), 0, st,

@@ -760,7 +760,7 @@ static int launch_post(bool direct, int F, int64_t B, const float* gz, const flo
   if (!slots && (!uniq_ids || !n_uniq)) return REC_E_ARG;
   if (slots && (direct || !packed)) return REC_E_UNSUPPORTED;
   if (direct && packed) return REC_E_UNSUPPORTED;
-  if ((reinterpret_cast<uintptr_t>(vals) & 15) != 0 || (reinterpret_cast<uintptr_t>(g_embed_rows) & 15) != 0)
+  if (!rec_is_aligned16(vals) || !rec_is_aligned16(g_embed_rows))
     return REC_E_UNSUPPORTED;
   const FusedWorkspace ws = fused_workspace(B, F);
   int D = F * E16;
@@ -842,8 +842,7 @@ extern "C" int rec_deepfm_fused_post_direct_adam_dev_f32(int F, int64_t B, const
   if (!table || !m_e || !v_e || !m_w || !v_w || !lr_t_dev || V <= 0 || ld_state < E16 || (ld_state & 3) != 0 ||
       ld_wstate < 1)
     return REC_E_ARG;
-  if (ld != LD || (reinterpret_cast<uintptr_t>(table) & 15) != 0 || (reinterpret_cast<uintptr_t>(m_e) & 15) != 0 ||
-      (reinterpret_cast<uintptr_t>(v_e) & 15) != 0)
+  if (ld != LD || !rec_is_aligned16(table) || !rec_is_aligned16(m_e) || !rec_is_aligned16(v_e))
     return REC_E_UNSUPPORTED;
   ColSegArgs a{};
   a.table = table; a.m_e = m_e; a.v_e = v_e; a.m_w = m_w; a.v_w = v_w; a.V = V;
@@ -862,8 +861,7 @@ static int catchup_args_ok(const float* table, int64_t ld, int64_t V, const floa
     return REC_E_ARG;
   if (ld != LD) return REC_E_UNSUPPORTED;
   // the rows' x / m / v travel as 16-byte pieces
-  if ((ld_state & 3) != 0 || (reinterpret_cast<uintptr_t>(table) & 15) != 0 || (reinterpret_cast<uintptr_t>(m_e) & 15) != 0 ||
-      (reinterpret_cast<uintptr_t>(v_e) & 15) != 0)
+  if ((ld_state & 3) != 0 || !rec_is_aligned16(table) || !rec_is_aligned16(m_e) || !rec_is_aligned16(v_e))
     return REC_E_UNSUPPORTED;
   return REC_OK;
 }

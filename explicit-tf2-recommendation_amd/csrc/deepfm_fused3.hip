@@ -685,18 +685,17 @@ static int launch_fused3(const float* table, int64_t ld, int64_t V, const int64_
     return REC_E_ARG;
   if (direct && (!dloc || !col_nu || !g_embed)) return REC_E_ARG;
   if (B * F * E16 * 4 >= (int64_t(1) << 31)) return REC_E_UNSUPPORTED;    // 32-bit byte offsets into vals / g_embed_rows
-  if ((reinterpret_cast<uintptr_t>(table) & 15) != 0 || (reinterpret_cast<uintptr_t>(K0) & 15) != 0 ||
-      (reinterpret_cast<uintptr_t>(K0T) & 15) != 0 || (reinterpret_cast<uintptr_t>(vals) & 15) != 0 ||
-      (direct && (reinterpret_cast<uintptr_t>(g_embed) & 15) != 0))
+  if (!rec_is_aligned16(table) || !rec_is_aligned16(K0) || !rec_is_aligned16(K0T) || !rec_is_aligned16(vals) ||
+      (direct && !rec_is_aligned16(g_embed)))
     return REC_E_UNSUPPORTED;
   // K0 in LDS whenever it fits beside the rest (F <= 26); else its fragments come from L2 (K0 and K0T)
   bool klds = F <= 26;                                   // the B waves stage 13 x 256 16-byte pieces: 8 * 16 F <= 3328
   size_t lds = (size_t)carve3_of(F, true).total * sizeof(float);
-  if (!klds || lds > 160 * 1024) {
+  if (!klds || lds > REC_LDS_CU_BYTES) {
     klds = false;
     lds = (size_t)carve3_of(F, false).total * sizeof(float);
   }
-  if (lds > 160 * 1024) return REC_E_UNSUPPORTED;
+  if (lds > REC_LDS_CU_BYTES) return REC_E_UNSUPPORTED;
   Cols3 cp;
   for (int f = 0; f < F; ++f) {
     if (!cols_host[f]) return REC_E_ARG;
@@ -719,9 +718,7 @@ static int launch_fused3(const float* table, int64_t ld, int64_t V, const int64_
   hipStream_t st = as_stream(stream);
 #define LAUNCH3(DIR, KL)                                                                                         \
   do {                                                                                                          \
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(deepfm3_kernel<DIR, KL>),                  \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                   \
-    if (e != hipSuccess) return (int)e;                                                                         \
+    if (hipError_t e = rec_allow_lds<deepfm3_kernel<DIR, KL>>(REC_LDS_CU_BYTES)) return (int)e;                 \
     hipLaunchKernelGGL((deepfm3_kernel<DIR, KL>), dim3(nwg), dim3(512), lds, st, cp, a);                        \
   } while (0)
   if (direct) {

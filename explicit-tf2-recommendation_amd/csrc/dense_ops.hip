@@ -300,16 +300,6 @@ __global__ __launch_bounds__(256) void cross_vec_bwd_layer_kernel(
   }
 }
 
-__global__ __launch_bounds__(256) void cross_vec_bwd_reduce_kernel(const float* __restrict__ part, int nslot, int D,
-                                                                   float* __restrict__ dw, float* __restrict__ db) {
-  int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= 2 * D) return;
-  int which = t / D, d = t - which * D;
-  float acc = 0.f;
-  for (int s = 0; s < nslot; ++s) acc += part[((int64_t)s * 2 + which) * D + d];
-  (which == 0 ? dw : db)[d] = acc;
-}
-
 __global__ __launch_bounds__(256) void add_inplace_kernel(float* __restrict__ y, const float* __restrict__ x,
                                                           int64_t n) {
   int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -726,9 +716,9 @@ extern "C" int rec_crossnet_vec_bwd_f32(const float* x0, int64_t B, int D, int L
     hipLaunchKernelGGL(cross_vec_bwd_layer_kernel, dim3(nchunk), dim3(256), 0, st, x0, B, D, w + (size_t)l * D,
                        xs + (size_t)l * B * D, g, gx0, part, rows_per_wg, l == L - 1 ? 1 : 0);
     REC_LAUNCH_CHECK();
-    hipLaunchKernelGGL(cross_vec_bwd_reduce_kernel, dim3((unsigned)ceil_div64(2 * D, 256)), dim3(256), 0, st, part,
-                       nchunk * 4, D, dw + (size_t)l * D, db + (size_t)l * D);
-    REC_LAUNCH_CHECK();
+    const int r = rec_slot_sum(REC_SLOTS_SERIAL, 2 * D, nchunk * 4, part,     // a slot is one wave's [dw | db]
+                               {{dw + (size_t)l * D, db + (size_t)l * D}, {D, D}}, st);
+    if (r != REC_OK) return r;
   }
   // x_0 is also the input of layer 0: gx0 += g
   hipLaunchKernelGGL(add_inplace_kernel, dim3((unsigned)ceil_div64(B * D, 256)), dim3(256), 0, st, gx0, g,
@@ -822,8 +812,7 @@ extern "C" int rec_adam_sparse_keras_f32(float* var, int64_t ld, float* m, float
     REC_LAUNCH_CHECK();
   }
   int64_t n = V * E;
-  bool vec = E % 4 == 0 && ld % 4 == 0 && (reinterpret_cast<uintptr_t>(var) & 15) == 0 &&
-             (reinterpret_cast<uintptr_t>(m) & 15) == 0 && (reinterpret_cast<uintptr_t>(v) & 15) == 0;
+  bool vec = E % 4 == 0 && ld % 4 == 0 && rec_is_aligned16(var) && rec_is_aligned16(m) && rec_is_aligned16(v);
   if (vec) {
     int64_t n4 = n / 4;
     int64_t blocks = ceil_div64(n4, 256);

@@ -900,9 +900,7 @@ static int launch_attn_fwd(const AttnArgs& a, int64_t B, int D, int H, float* sc
                            hipStream_t st) {
   constexpr size_t lds = sizeof(float) * AL<NT, ND, false>::total;
   if constexpr (lds > 150 * 1024) return REC_E_UNSUPPORTED;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(din_attn_fwd_kernel<NT, ND>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return (int)e;
+  if (hipError_t e = rec_allow_lds<din_attn_fwd_kernel<NT, ND>>(lds)) return (int)e;
   hipLaunchKernelGGL((din_attn_fwd_kernel<NT, ND>), dim3((unsigned)B), dim3(256), lds, st, a, D, H, scores, pooled, oob);
   return REC_OK;
 }
@@ -911,9 +909,7 @@ static int launch_attn_bwd(const AttnArgs& a, int64_t B, int D, int H, const flo
                            float* gkeys, float* gMext, float* gw2p, float* galphap, float* gb2p, hipStream_t st) {
   constexpr size_t lds = sizeof(float) * AL<NT, NMT * NPASS, true>::total;
   if constexpr (lds > 150 * 1024) return REC_E_UNSUPPORTED;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(din_attn_bwd_kernel<NT, NMT, NPASS>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return (int)e;
+  if (hipError_t e = rec_allow_lds<din_attn_bwd_kernel<NT, NMT, NPASS>>(lds)) return (int)e;
   hipLaunchKernelGGL((din_attn_bwd_kernel<NT, NMT, NPASS>), dim3((unsigned)B), dim3(256), lds, st, a, D, H, scores,
                      gpooled, gkeys, gMext, gw2p, galphap, gb2p);
   return REC_OK;

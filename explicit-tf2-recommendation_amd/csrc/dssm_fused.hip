@@ -23,7 +23,7 @@ constexpr int H1 = 64, H2 = 32, DO = 8;     // mlp_dims [64, 32], final_dim 8
 constexpr int LH1 = H1 + 4, LH2 = H2 + 4;   // LDS row strides (odd multiples of 4 floats: no bank conflicts on columns)
 constexpr int MAXF = 8;
 constexpr int NT = 256;                     // threads of a main-launch workgroup (4 waves)
-constexpr size_t LDS_LIMIT = 160 * 1024;
+constexpr size_t LDS_LIMIT = REC_LDS_CU_BYTES;
 
 // floats of one tower's dense partials in a workgroup block: dW0 [K0,64], db0 [64], dW1 [64,32], db1 [32], dWf [32,8], dbf [8]
 __host__ __device__ inline int64_t tower_partials(int K0) { return (int64_t)K0 * H1 + H1 + H1 * H2 + H2 + H2 * DO + DO; }
@@ -439,7 +439,6 @@ __global__ __launch_bounds__(256) void dssm_post_kernel(PostArgs a) {
 }
 
 inline bool supported_e(int E) { return E == 8 || E == 16 || E == 32 || E == 64; }
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
@@ -462,8 +461,8 @@ extern "C" int rec_dssm_fused_main_f32(const float* u_table, int64_t u_ld, int64
     return REC_E_ARG;
   if (!supported_e(E) || F_u < 1 || F_u > MAXF || F_i < 1 || F_i > MAXF || h1 != H1 || h2 != H2 || d_out != DO)
     return REC_E_UNSUPPORTED;
-  if (u_ld < E || i_ld < E || (u_ld & 3) || (i_ld & 3) || !aligned16(u_table) || !aligned16(i_table) ||
-      !aligned16(workspace))
+  if (u_ld < E || i_ld < E || (u_ld & 3) || (i_ld & 3) || !rec_is_aligned16(u_table) || !rec_is_aligned16(i_table) ||
+      !rec_is_aligned16(workspace))
     return REC_E_ARG;
   for (int j = 0; j < 12; ++j)
     if (!weights[j]) return REC_E_ARG;
@@ -491,9 +490,7 @@ extern "C" int rec_dssm_fused_main_f32(const float* u_table, int64_t u_ld, int64
   hipStream_t st = as_stream(stream);
 #define DSSM_MAIN(EE, MM)                                                                                           \
   do {                                                                                                              \
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(dssm_main_kernel<EE, MM>),                     \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                       \
-    if (e != hipSuccess) return (int)e;                                                                             \
+    if (hipError_t e = rec_allow_lds<dssm_main_kernel<EE, MM>>(LDS_LIMIT)) return (int)e;                          \
     hipLaunchKernelGGL((dssm_main_kernel<EE, MM>), dim3(nwg), dim3(NT), lds, st, a);                                \
   } while (0)
 #define DSSM_MAIN_E(EE) \
@@ -526,11 +523,12 @@ extern "C" int rec_dssm_fused_post_f32(int64_t B, int E, int F_u, int F_i, const
   if (!supported_e(E) || F_u < 1 || F_u > MAXF || F_i < 1 || F_i > MAXF) return REC_E_UNSUPPORTED;
   for (int j = 0; j < 12; ++j)
     if (!grads[j]) return REC_E_ARG;
-  if (!aligned16(u_vals) || !aligned16(i_vals) || !aligned16(u_rows) || !aligned16(i_rows)) return REC_E_ARG;
+  if (!rec_is_aligned16(u_vals) || !rec_is_aligned16(i_vals) || !rec_is_aligned16(u_rows) || !rec_is_aligned16(i_rows))
+    return REC_E_ARG;
   if (adam) {
     if (!lr_t_dev || u_V < 1 || i_V < 1 || u_ld < E || i_ld < E || (u_ld & 3) || (i_ld & 3)) return REC_E_ARG;
     for (int j = 0; j < 6; ++j)
-      if (!adam[j] || !aligned16(adam[j])) return REC_E_ARG;
+      if (!adam[j] || !rec_is_aligned16(adam[j])) return REC_E_ARG;
   }
   if (workspace_bytes < rec_dssm_fused_workspace_bytes(B, E, F_u, F_i)) return REC_E_WORKSPACE;
   const int K0u = F_u * E, K0i = F_i * E;

@@ -70,11 +70,11 @@ extern "C" int rec_block_copy(const void* const* srcs_host, int n, int64_t bytes
   for (int s0 = 0; s0 < n; s0 += 256) {
     const int ns = n - s0 < 256 ? n - s0 : 256;
     BlockSrcs b;
-    bool vec = (bytes_each & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+    bool vec = (bytes_each & 15) == 0 && rec_is_aligned16(out);
     for (int s = 0; s < ns; ++s) {
       if (!srcs_host[s0 + s]) return REC_E_ARG;
       b.p[s] = srcs_host[s0 + s];
-      vec = vec && (reinterpret_cast<uintptr_t>(b.p[s]) & 15) == 0;
+      vec = vec && rec_is_aligned16(b.p[s]);
     }
     char* o = reinterpret_cast<char*>(out) + (int64_t)s0 * bytes_each;
     if (vec) {
@@ -250,7 +250,7 @@ __global__ __launch_bounds__(256) void gather_scalar_kernel(const float* __restr
 }
 
 static inline bool vec4_ok(const void* p, int E, int64_t ld) {
-  return E % 4 == 0 && ld % 4 == 0 && (reinterpret_cast<uintptr_t>(p) & 15) == 0;
+  return E % 4 == 0 && ld % 4 == 0 && rec_is_aligned16(p);
 }
 
 extern "C" int rec_emb_gather_f32(const float* table, int64_t V, int E, int64_t ld, const int64_t* idx, int64_t n,
@@ -514,8 +514,7 @@ extern "C" int rec_emb_fm_fwd_f32(const float* embed, int64_t ld_e, const float*
   if (V >= (int64_t(1) << 31)) return REC_E_UNSUPPORTED;
   FwdArgs a{embed, ld_e, w, ld_w, bias, V, E, idx, B, F, z, prob, emb_out, sumvec, oob_flag, as_stream(stream)};
   bool done = false;
-  bool out_ok = (!emb_out || (reinterpret_cast<uintptr_t>(emb_out) & 15) == 0) &&
-                (!sumvec || (reinterpret_cast<uintptr_t>(sumvec) & 15) == 0);
+  bool out_ok = (!emb_out || rec_is_aligned16(emb_out)) && (!sumvec || rec_is_aligned16(sumvec));
   if (vec4_ok(embed, E, ld_e) && out_ok) {
     // fused layout: w is float E of the embed row and the row is a power-of-two number of float4 lanes
     bool fused = (w == embed + E) && ld_w == ld_e && ld_e > E && (ld_e & (ld_e - 1)) == 0 && ld_e <= 64;
@@ -596,9 +595,8 @@ extern "C" int rec_emb_fm_bwd_vals_f32(const float* embed, int64_t ld_e, int64_t
   if (E <= 0 || F <= 0 || B < 0 || (embed && ld_e < E)) return REC_E_ARG;
   if (B == 0) return REC_OK;
   if ((!embed && !emb_rows) || !idx || !gz || !sumvec || !dvals) return REC_E_ARG;
-  bool al = (reinterpret_cast<uintptr_t>(sumvec) & 15) == 0 && (reinterpret_cast<uintptr_t>(dvals) & 15) == 0 &&
-            (!emb_rows || (reinterpret_cast<uintptr_t>(emb_rows) & 15) == 0) &&
-            (!extra || (reinterpret_cast<uintptr_t>(extra) & 15) == 0);
+  bool al = rec_is_aligned16(sumvec) && rec_is_aligned16(dvals) && (!emb_rows || rec_is_aligned16(emb_rows)) &&
+            (!extra || rec_is_aligned16(extra));
   if (E % 4 == 0 && al && (emb_rows || vec4_ok(embed, E, ld_e))) {
     int lpr = E / 4;
     hipLaunchKernelGGL(emb_fm_bwd_vals_vec_kernel, dim3((unsigned)ceil_div64(B * F * lpr, 256)), dim3(256), 0,

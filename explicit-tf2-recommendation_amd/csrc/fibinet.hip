@@ -18,7 +18,7 @@
 //                         element to one lane, so the read-modify-writes of dx need no atomics.
 //   fibinet_bwd_w_kernel  one workgroup per (item, chunk of examples): dW_item += v_i^T (sum_j u) with K over the
 //                         chunk's examples (MFMA, accumulated in registers), the 4 waves summed in wave order into a slot.
-//   fibinet_dw_reduce_kernel / fibinet_ds_reduce_kernel sum the slots in a fixed order.
+//   rec_slot_sum adds the dW slots in chunk order (serial) and the dS slots in its wave order.
 // No float atomics: bit-identical results run to run.
 #include "common.h"
 
@@ -437,41 +437,6 @@ __global__ __launch_bounds__(FB_NT) void fibinet_bwd_w_kernel(FbShape s, const f
   for (int t = tid; t < E * E; t += FB_NT) dst[t] = red[t];
 }
 
-// dW[w] = sum over the chunks (and over the items of W for 'all'), in chunk order
-__global__ __launch_bounds__(256) void fibinet_dw_reduce_kernel(FbShape s, const float* __restrict__ wsl,
-                                                                int64_t nchunk, float* __restrict__ dW) {
-  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t EE = (int64_t)s.E * s.E;
-  if (idx >= s.nW * EE) return;
-  const int64_t w = idx / EE, k = idx - w * EE;
-  float acc = 0.f;
-  for (int64_t ch = 0; ch < nchunk; ++ch) {
-    const float* base = wsl + ch * s.nitem * EE + k;
-    if (s.type == 0) {
-      for (int it = 0; it < s.nitem; ++it) acc += base[it * EE];
-    } else {
-      acc += base[w * EE];
-    }
-  }
-  dW[idx] = acc;
-}
-
-// dS0 / dS1 element k: one wave; lane l sums the slots l, l + 64, ... in order, then a fixed butterfly over the lanes
-__global__ __launch_bounds__(64) void fibinet_ds_reduce_kernel(FbShape s, const float* __restrict__ dsl, int64_t nslot,
-                                                               float* __restrict__ dS0, float* __restrict__ dS1) {
-  const int64_t k = blockIdx.x, nsf = 2LL * s.F * s.mid;
-  const int lane = threadIdx.x;
-  float acc = 0.f;
-  for (int64_t sl = lane; sl < nslot; sl += 64) acc += dsl[sl * nsf + k];
-  acc = group_sum<64>(acc);
-  if (lane == 0) {
-    if (k < (int64_t)s.F * s.mid)
-      dS0[k] = acc;
-    else
-      dS1[k - (int64_t)s.F * s.mid] = acc;
-  }
-}
-
 // 0 ok (B == 0 included), REC_E_ARG, REC_E_UNSUPPORTED
 static int fb_shape(int64_t B, int F, int E, int C, int mid, int type, FbShape* s) {
   if (B < 0 || F < 0 || E < 0 || C < 0 || mid < 0 || type < 0 || type > 2) return REC_E_ARG;
@@ -518,7 +483,7 @@ static FbBwdCfg fb_bwd_cfg(const FbShape& s) {
 }
 
 static size_t fb_ws_bytes(const FbBwdCfg& k) {
-  return ((k.wsl_floats * sizeof(float) + 255) & ~(size_t)255) + k.dsl_floats * sizeof(float);
+  return rec_align_up(k.wsl_floats * sizeof(float), 256) + k.dsl_floats * sizeof(float);
 }
 
 template <int NTC>
@@ -559,12 +524,8 @@ extern "C" int rec_fibinet_fwd_f32(const float* x_emb, const float* x_cont, cons
   if (rc != REC_OK || B == 0) return rc;
   if (!x_emb || (C > 0 && !x_cont) || !S0 || !S1 || !W || !dnn_in || !A || !H1) return REC_E_ARG;
   hipStream_t st = as_stream(stream);
-  switch ((E + 15) / 16) {
-    case 1: return fb_fwd<1>(s, x_emb, x_cont, S0, S1, W, dnn_in, A, H1, st);
-    case 2: return fb_fwd<2>(s, x_emb, x_cont, S0, S1, W, dnn_in, A, H1, st);
-    case 3: return fb_fwd<3>(s, x_emb, x_cont, S0, S1, W, dnn_in, A, H1, st);
-    default: return fb_fwd<4>(s, x_emb, x_cont, S0, S1, W, dnn_in, A, H1, st);
-  }
+  return rec_dispatch_1to4((E + 15) / 16,
+                           [&](auto ntc) { return fb_fwd<ntc.value>(s, x_emb, x_cont, S0, S1, W, dnn_in, A, H1, st); });
 }
 
 extern "C" int rec_fibinet_bwd_f32(const float* x_emb, const float* g, const float* A, const float* H1,
@@ -578,23 +539,17 @@ extern "C" int rec_fibinet_bwd_f32(const float* x_emb, const float* g, const flo
   const FbBwdCfg k = fb_bwd_cfg(s);
   if (workspace_bytes < fb_ws_bytes(k)) return REC_E_WORKSPACE;
   float* wsl = static_cast<float*>(workspace);
-  float* dsl = reinterpret_cast<float*>(static_cast<char*>(workspace) +
-                                        ((k.wsl_floats * sizeof(float) + 255) & ~(size_t)255));
+  float* dsl =
+      reinterpret_cast<float*>(static_cast<char*>(workspace) + rec_align_up(k.wsl_floats * sizeof(float), 256));
   hipStream_t st = as_stream(stream);
-  int r;
-  switch ((E + 15) / 16) {
-    case 1: r = fb_bwd<1>(s, k, x_emb, g, A, H1, S0, S1, W, dx_emb, wsl, dsl, st); break;
-    case 2: r = fb_bwd<2>(s, k, x_emb, g, A, H1, S0, S1, W, dx_emb, wsl, dsl, st); break;
-    case 3: r = fb_bwd<3>(s, k, x_emb, g, A, H1, S0, S1, W, dx_emb, wsl, dsl, st); break;
-    default: r = fb_bwd<4>(s, k, x_emb, g, A, H1, S0, S1, W, dx_emb, wsl, dsl, st); break;
-  }
+  int r = rec_dispatch_1to4((E + 15) / 16, [&](auto ntc) {
+    return fb_bwd<ntc.value>(s, k, x_emb, g, A, H1, S0, S1, W, dx_emb, wsl, dsl, st);
+  });
   if (r != REC_OK) return r;
-  const int64_t n = s.nW * (int64_t)E * E;
-  hipLaunchKernelGGL(fibinet_dw_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, s, wsl, k.nchunk,
-                     dW);
-  REC_LAUNCH_CHECK();
-  hipLaunchKernelGGL(fibinet_ds_reduce_kernel, dim3((unsigned)(2 * F * mid)), dim3(64), 0, st, s, dsl, k.nslot, dS0,
-                     dS1);
-  REC_LAUNCH_CHECK();
-  return REC_OK;
+  // dW: the chunks in chunk order, a slot holding the chunk's nitem = nW matrices; 'all' has one W, which takes every
+  // (chunk, item) in that order
+  const int nw = s.nW * E * E, nws = (int)(type == 0 ? k.nchunk * s.nitem : k.nchunk);
+  r = rec_slot_sum(REC_SLOTS_SERIAL, nw, nws, wsl, {{dW}, {nw}}, st);
+  if (r != REC_OK) return r;
+  return rec_slot_sum(REC_SLOTS_WAVE, 2 * F * mid, (int)k.nslot, dsl, {{dS0, dS1}, {F * mid, F * mid}}, st);
 }

@@ -667,7 +667,10 @@ extern "C" int rec_gemm_f32(int transA, int transB, int64_t M, int64_t N, int64_
   if (panel_fwd) {
     const int maxb = (int)ceil_div64(ceil_div64(ncp > 0 ? ncp : N, 32), 4);   // column blocks per wave, 1..7
     constexpr int PMt = 64, PKt = 16;
-    const size_t lds = sizeof(float) * (2 * PKt * (PMt + PPAD) + 2 * PKt * ((size_t)maxb * 128 + PPAD));
+    auto panel_lds = [](int mb) {                                            // mb column blocks per wave
+      return sizeof(float) * (2 * PKt * (PMt + PPAD) + 2 * PKt * ((size_t)mb * 128 + PPAD));
+    };
+    const size_t lds = panel_lds(maxb);
     const int64_t panels = ceil_div64(M, PMt);
     // (the kernel can also take K slices of a k-major A -- blockIdx.y, partials in ws -- for the weight gradient H^T.X;
     // measured slower than the 128x128 split-K tiles, see above, so no slice is ever launched from here)
@@ -677,9 +680,7 @@ extern "C" int rec_gemm_f32(int transA, int transB, int64_t M, int64_t N, int64_
     dim3 grid((unsigned)panels, (unsigned)psplit, (unsigned)ncol_panels);
 #define PANEL(TAv, TBv, MB)                                                                                          \
   do {                                                                                                               \
-    hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f32_panel_kernel<TAv, TBv, MB, PMt, PKt>), \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                       \
-    if (e_ != hipSuccess) return (int)e_;                                                                            \
+    if (hipError_t e_ = rec_allow_lds<gemm_f32_panel_kernel<TAv, TBv, MB, PMt, PKt>>(panel_lds(7))) return (int)e_; \
     hipLaunchKernelGGL((gemm_f32_panel_kernel<TAv, TBv, MB, PMt, PKt>), grid, dim3(PMt * 8), lds, st, M, N, K, A, lda, \
                        B, ldb, C, ldc, epilogue_kind, bias, e0, lde0, e1, lde1, aux, pchunk, pws, ncp);              \
   } while (0)

@@ -200,7 +200,7 @@ extern "C" int rec_emb_ipn_fwd_f32(const float* table, int64_t V, int E, int64_t
   if (ld_out < (int64_t)F * E + (int64_t)F * (F - 1) / 2) return REC_E_ARG;
   if (B == 0) return REC_OK;
   if (!table || !X || !out) return REC_E_ARG;
-  const int vec4 = (E & 3) == 0 && (ld & 3) == 0 && (reinterpret_cast<uintptr_t>(table) & 15) == 0;
+  const int vec4 = (E & 3) == 0 && (ld & 3) == 0 && rec_is_aligned16(table);
   size_t lds;
   int EX = ipn_examples_per_group(B, F, E, false, &lds);
   if (!EX) return REC_E_ARG;
@@ -312,7 +312,7 @@ extern "C" int rec_emb_bi_fwd_f32(const float* table, int64_t V, int E, int64_t 
   if (V <= 0 || E <= 0 || ld < E || B < 0 || F <= 0 || ld_out < E) return REC_E_ARG;
   if (B == 0) return REC_OK;
   if (!table || !X || !out || !sumvec) return REC_E_ARG;
-  const bool vec = (E & 3) == 0 && (ld & 3) == 0 && (reinterpret_cast<uintptr_t>(table) & 15) == 0;
+  const bool vec = (E & 3) == 0 && (ld & 3) == 0 && rec_is_aligned16(table);
   if (vec)
     hipLaunchKernelGGL((emb_bi_fwd_kernel<true>), dim3((unsigned)ceil_div64(B * (E / 4), 256)), dim3(256), 0,
                        as_stream(stream), table, V, E, ld, X, B, F, out, ld_out, sumvec, oob_flag);
@@ -615,7 +615,7 @@ extern "C" int rec_ffm_fwd_f32(const float* v, int64_t ld_v, const float* w, int
   if (B == 0) return REC_OK;
   if (!v || !w || !bias || !X || (!z && !prob)) return REC_E_ARG;
   const size_t lds = (size_t)F * 4 + 16 + (size_t)F * (F - 1);
-  const bool vec = (E & 3) == 0 && (ld_v & 3) == 0 && (reinterpret_cast<uintptr_t>(v) & 15) == 0;
+  const bool vec = (E & 3) == 0 && (ld_v & 3) == 0 && rec_is_aligned16(v);
   if (vec)
     hipLaunchKernelGGL((ffm_fwd_kernel<true>), dim3((unsigned)B), dim3(256), lds, as_stream(stream), v, ld_v, w, ld_w,
                        bias, V, E, X, B, F, z, prob, oob_flag);

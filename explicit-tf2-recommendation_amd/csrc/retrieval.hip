@@ -224,10 +224,8 @@ extern "C" size_t rec_topk_l2_workspace_bytes(int64_t nq, int64_t n, int k) {
 template <int K, int D, int QW>
 static int launch_scan(const float* queries, int64_t nq, int d, int64_t ldq, const float* items, int64_t n, int64_t ldi,
                        int nslab, int64_t sub, float* cand_v, int* cand_i, hipStream_t st) {
-  size_t lds = sizeof(float) * ((size_t)QW * D + 4 * (size_t)QW * K * 2);
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(topk_scan_kernel<K, D, QW>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return (int)e;
+  constexpr size_t lds = sizeof(float) * ((size_t)QW * D + 4 * (size_t)QW * K * 2);
+  if (hipError_t e = rec_allow_lds<topk_scan_kernel<K, D, QW>>(lds)) return (int)e;
   dim3 grid((unsigned)nslab, (unsigned)ceil_div64(nq, QW));
   hipLaunchKernelGGL((topk_scan_kernel<K, D, QW>), grid, dim3(256), lds, st, queries, nq, d, ldq, items, n, ldi, sub,
                      cand_v, cand_i);

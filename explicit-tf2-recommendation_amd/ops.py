@@ -35,6 +35,14 @@ def _req(t, dtype, name):
     return t
 
 
+def _workspace(nbytes, what, device, dtype=torch.uint8):
+    """Scratch for one ABI call, nbytes as its rec_*_workspace_bytes answered.  `what` names that entry point where its
+    answer is 0 for a shape the kernels do not cover; None where 0 bytes only means that nothing is needed."""
+    if nbytes == 0 and what is not None:
+        raise NotImplementedError("%s: unsupported shape" % what)
+    return torch.empty(max(nbytes // dtype.itemsize, 1), dtype=dtype, device=device)
+
+
 def _f32(t, name):
     return _req(t, torch.float32, name)
 
@@ -121,7 +129,7 @@ class DedupPlan:
             self.perm = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
             self.n_uniq = torch.empty(1, dtype=torch.int64, device=dev)
             nbytes = lib.rec_dedup_workspace_bytes(n)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            ws = _workspace(nbytes, None, dev)
             lc = _i64(list_counts.reshape(-1), "list_counts")
             check(lib.rec_dedup_plan_sorted_lists_i64(_ptr(ids), n, _ptr(lc), lc.numel(), V, _ptr(self.uniq_ids),
                                                       _ptr(self.seg_start), _ptr(self.perm), _ptr(self.n_uniq),
@@ -255,7 +263,7 @@ def crossnet_vec_bwd(x0, w, xs, gy):
     dw = torch.empty_like(w)
     db = torch.empty_like(w)
     nbytes = lib.rec_crossnet_vec_bwd_workspace_bytes(B, D, L)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=x0.device)
+    ws = _workspace(nbytes, None, x0.device)
     check(lib.rec_crossnet_vec_bwd_f32(_ptr(x0), B, D, L, _ptr(w), _ptr(xs), _ptr(_f32(gy, "gy")), _ptr(gx0),
                                        _ptr(dw), _ptr(db), _ptr(ws), _stream()), "rec_crossnet_vec_bwd_f32")
     return gx0, dw, db
@@ -308,7 +316,7 @@ def shard_bucketize(ids, rows_per_shard, n_shard, oob=None):
     counts = torch.empty(n_shard, dtype=torch.int64, device=dev)
     local = torch.empty(n, dtype=torch.int64, device=dev)
     nbytes = lib.rec_shard_bucketize_workspace_bytes(n, n_shard)
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    ws = _workspace(nbytes, None, dev)
     check(lib.rec_shard_bucketize_i64(_ptr(ids), n, rows_per_shard, n_shard, _ptr(perm), _ptr(counts), _ptr(local),
                                       _ptr(oob), _ptr(ws), nbytes, _stream()), "rec_shard_bucketize_i64")
     return perm, counts, local
@@ -346,7 +354,7 @@ def topk_l2(queries, items, k):
     ind = torch.empty((nq, k), dtype=torch.int64, device=dev)
     dist = torch.empty((nq, k), dtype=torch.float32, device=dev)
     nbytes = lib.rec_topk_l2_workspace_bytes(nq, n, k)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _workspace(nbytes, None, dev)
     check(lib.rec_topk_l2_f32(_ptr(queries), nq, d, queries.stride(0), _ptr(items), n, items.stride(0), k, _ptr(ind),
                               _ptr(dist), _ptr(ws), nbytes, _stream()), "rec_topk_l2_f32")
     return dist, ind
@@ -642,9 +650,7 @@ def cin_bwd(x0, states, g, Ws):
     dWs = [torch.empty_like(w) for w in Ws]
     dWh = (C.c_void_p * len(dWs))(*[d.data_ptr() for d in dWs])
     nbytes = lib.rec_cin_workspace_bytes(B, F, E, len(H), Hh)
-    if nbytes == 0:
-        raise NotImplementedError("rec_cin_workspace_bytes: unsupported CIN shape")
-    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x0.device)
+    ws = _workspace(nbytes, "rec_cin_workspace_bytes", x0.device, torch.float32)
     check(lib.rec_cin_bwd_f32(_ptr(x0), _ptr(states), _ptr(g), B, F, E, len(H), Hh, Wh, _ptr(dx0), dWh, _ptr(ws), nbytes,
                               _stream()), "rec_cin_bwd_f32")
     return dx0, dWs
@@ -699,9 +705,7 @@ def fibinet_bwd(x_emb, g, A, H1, S0, S1, W, type_code):
         return dx, torch.zeros_like(W), torch.zeros_like(S0), torch.zeros_like(S1)
     dW, dS0, dS1 = torch.empty_like(W), torch.empty_like(S0), torch.empty_like(S1)
     nbytes = lib.rec_fibinet_workspace_bytes(B, F, E, mid, type_code)
-    if nbytes == 0:
-        raise NotImplementedError("rec_fibinet_workspace_bytes: unsupported FiBiNet shape")
-    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x_emb.device)
+    ws = _workspace(nbytes, "rec_fibinet_workspace_bytes", x_emb.device, torch.float32)
     check(lib.rec_fibinet_bwd_f32(_ptr(x_emb), _ptr(g), _ptr(A), _ptr(H1), _ptr(S0), _ptr(S1), _ptr(W), B, F, E, C, mid,
                                   type_code, _ptr(dx), _ptr(dW), _ptr(dS0), _ptr(dS1), _ptr(ws), nbytes, _stream()),
           "rec_fibinet_bwd_f32")
@@ -727,9 +731,7 @@ def autoint_check_shape(F, E, H, C=0):
 
 def _autoint_ws(B, F, E, H, C, res, dev):
     nbytes = lib.rec_autoint_workspace_bytes(B, F, E, H, C, res)
-    if nbytes == 0:
-        raise NotImplementedError("rec_autoint_workspace_bytes: unsupported AutoInt shape")
-    return torch.empty(nbytes // 4, dtype=torch.float32, device=dev), nbytes
+    return _workspace(nbytes, "rec_autoint_workspace_bytes", dev, torch.float32), nbytes
 
 
 def autoint_fwd(x, Wq, Wk, Wv, Wres, num_heads, res, scaling, x_cont=None, cemb=None, want_o=False):
@@ -847,9 +849,7 @@ def emb_afm_bwd(table, X, Wa, ba, hv, bh, o, stats, dout, rows=None):
     dWa, dba, dhv, dbh = (torch.zeros_like(t) for t in (Wa, ba, hv, bh))
     if B > 0:
         nbytes = lib.rec_afm_workspace_bytes(B, F, E, A)
-        if nbytes == 0:
-            raise NotImplementedError("rec_afm_workspace_bytes: unsupported AFM shape")
-        ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+        ws = _workspace(nbytes, "rec_afm_workspace_bytes", dev, torch.float32)
         check(lib.rec_emb_afm_bwd_f32(_ptr(table), V, E, table.stride(0), _ptr(X), B, F, A, _ptr(Wa), _ptr(ba),
                                       _ptr(hv), _ptr(bh), _ptr(o), _ptr(stats), _ptr(rows), _ptr(dout), _ptr(vals),
                                       _ptr(dWa), _ptr(dba), _ptr(dhv), _ptr(dbh), _ptr(ws), nbytes, _stream()),
