@@ -117,6 +117,9 @@ SIGNATURES = {
     "rec_afm_workspace_bytes": (sz, [i64, i32, i32, i32]),
     "rec_emb_afm_fwd_f32": (i32, [p, i64, i32, i64, p, i64, i32, i32, p, p, p, p, p, p, p, p, p]),
     "rec_emb_afm_bwd_f32": (i32, [p, i64, i32, i64, p, i64, i32, i32, p, p, p, p, p, p, p, p, p, p, p, p, p, p, sz, p]),
+    "rec_ccpm_workspace_bytes": (sz, [i64, i32, i32, i32, p, p, p]),
+    "rec_emb_ccpm_fwd_f32": (i32, [p, i64, i32, i64, p, i64, i32, i32, p, p, p, p, p, p, p, p]),
+    "rec_emb_ccpm_bwd_f32": (i32, [p, i64, i32, i64, p, i64, i32, i32, p, p, p, p, p, p, p, p, p, sz, p]),
 }
 
 

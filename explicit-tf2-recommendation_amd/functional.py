@@ -580,3 +580,37 @@ class EmbAFM(torch.autograd.Function):
         vals, dWa, dba, dhv, dbh = ops.emb_afm_bwd(table, X, Wa, ba, hv, bh, o, stats, g.contiguous(), rows)
         plan = ops.DedupPlan(X, V)
         return _sparse_grad(plan, vals, E, (V, E)), None, dWa, dba, dhv, dbh, None
+
+
+class EmbCCPM(torch.autograd.Function):
+    """CCPM's conv / k-max-pool stack fused with the lookup (3.DCN/CustomLayers.py:621-677; csrc/ccpm.hip): table, X
+    [B,F], and per layer the Conv2D kernel [kw,1,Cin,Cout] and bias [Cout] -> Flatten of the last pooling,
+    [B, 3 E C_L].  Backward: the sparse row gradient of the table and every kernel's and bias's gradient, one launch plus
+    the slot sum.  ``SAVE_ROWS``: keep the gathered rows [B,F,E] for the backward instead of gathering them again
+    (DESIGN.md 3.2 has the measurement behind the default)."""
+
+    SAVE_ROWS = False
+
+    @staticmethod
+    def forward(ctx, table, X, filters, kernel_width, oob, *weights):
+        params = torch.cat([w.reshape(-1) for w in weights])          # K_1 | b_1 | K_2 | b_2 | ...
+        out, rows = ops.emb_ccpm_fwd(table, X, params, filters, kernel_width, oob, want_rows=EmbCCPM.SAVE_ROWS)
+        ctx.save_for_backward(table, X, params, rows)
+        ctx.cfg = (list(filters), list(kernel_width), [tuple(w.shape) for w in weights])
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        table, X, params, rows = ctx.saved_tensors
+        filters, kernel_width, shapes = ctx.cfg
+        V, E = table.shape
+        vals, dparams = ops.emb_ccpm_bwd(table, X, params, filters, kernel_width, g.contiguous(), rows)
+        plan = ops.DedupPlan(X, V)
+        dws, at = [], 0
+        for shp in shapes:
+            n = 1
+            for d in shp:
+                n *= d
+            dws.append(dparams[at:at + n].reshape(shp))
+            at += n
+        return (_sparse_grad(plan, vals, E, (V, E)), None, None, None, None, *dws)

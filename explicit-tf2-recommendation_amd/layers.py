@@ -21,6 +21,9 @@ libmi355rec.so (through functional.py / ops.py).  Reference classes and the line
   InteractionLayer              3.DCN/CustomLayers.py:825-838
   AttentionLayer                3.DCN/CustomLayers.py:841-853
   AttentionalFactorizationMachine  3.DCN/CustomLayers.py:856-885
+  KMaxPool                      3.DCN/CustomLayers.py:621-637
+  CCPMBaseLayer                 3.DCN/CustomLayers.py:640-677
+  CCPMLayer                     3.DCN/CustomLayers.py:680-725
 
 Parameters are named after the TF checkpoint keys (``embed.embeddings``, ``w.embeddings``, ``bias``,
 ``MLP_layer1.kernel_0`` ...), so a TensorBundle checkpoint maps onto ``state_dict()`` by name.
@@ -52,7 +55,13 @@ def _uniform(shape, lim):
 
 
 def glorot_uniform(shape):
-    fan_in, fan_out = (shape[0], shape[1]) if len(shape) == 2 else (shape[0], shape[0])
+    """TF2 glorot_uniform.  A convolution kernel [..., Cin, Cout] counts its receptive field: fan_in = rf Cin, fan_out =
+    rf Cout with rf the product of the leading dims."""
+    if len(shape) > 2:
+        rf = math.prod(shape[:-2])
+        fan_in, fan_out = rf * shape[-2], rf * shape[-1]
+    else:
+        fan_in, fan_out = (shape[0], shape[1]) if len(shape) == 2 else (shape[0], shape[0])
     return _uniform(shape, math.sqrt(6.0 / (fan_in + fan_out)))
 
 
@@ -834,6 +843,98 @@ class AttentionalFactorizationMachine(Layer):
                                            att.attention_w.bias, att.attention_h.kernel, att.attention_h.bias, flag)
         self._raise_if_oob(flag)
         return {"output": self.output_layer(attention_output)}
+
+
+class KMaxPool(Layer):
+    """3.DCN/CustomLayers.py:621-637: per (embedding dim, channel) the k largest values over the field axis, in
+    DESCENDING order of value (tf.nn.top_k(sorted=True), not the field order of the paper), the lower field first on
+    equal values.  It has no weights; its forward runs fused inside CCPMLayer (csrc/ccpm.hip)."""
+
+    def __init__(self, k):
+        super().__init__()
+        self.k = int(k)
+
+    def forward(self, inputs):
+        raise NotImplementedError("KMaxPool runs fused inside CCPMLayer (csrc/ccpm.hip)")
+
+
+class _FieldConv(Layer):
+    """The parameters of Conv2D(filters, (kernel_width, 1), padding='same', activation='tanh'): ``kernel``
+    [kw,1,Cin,Cout] glorot-uniform, ``bias`` [Cout] zeros."""
+
+    def __init__(self, kernel_width, cin, cout):
+        super().__init__()
+        self.kernel = torch.nn.Parameter(glorot_uniform((int(kernel_width), 1, int(cin), int(cout))))
+        self.bias = torch.nn.Parameter(torch.zeros(int(cout)))
+
+    def forward(self, inputs):
+        raise NotImplementedError("the field convolution runs fused inside CCPMLayer (csrc/ccpm.hip)")
+
+
+class CCPMBaseLayer(Layer):
+    """3.DCN/CustomLayers.py:640-677: L x (Conv2D along the field axis, tanh, KMaxPool) and Flatten.  ``build`` takes
+    the input shape (fields, embedding_dims); the k of every pooling comes from ``input_shape[-1]``, the embedding
+    width, as in the reference (ops.ccpm_k).  Holds ``conv_layers.{i}.kernel`` / ``.bias``; its forward runs fused with
+    the lookup inside CCPMLayer (csrc/ccpm.hip)."""
+
+    def __init__(self, filters=[4, 6], kernel_width=[4, 2], input_shape=None):
+        super().__init__()
+        self.filters = [int(c) for c in filters]
+        self.kernel_width = [int(k) for k in kernel_width]
+        self.layers_num = len(self.filters)
+        self.built = False
+        if input_shape is not None:
+            self.build(input_shape)
+
+    def build(self, input_shape):
+        F, E = int(input_shape[-2]), int(input_shape[-1])
+        self.pool_k = ops.ccpm_check_shape(F, E, self.filters, self.kernel_width)
+        cins = [1] + self.filters[:-1]
+        self.conv_layers = torch.nn.ModuleList(
+            [_FieldConv(kw, cin, c) for kw, cin, c in zip(self.kernel_width, cins, self.filters)])
+        self.kmax_layers = torch.nn.ModuleList([KMaxPool(k) for k in self.pool_k])
+        self.output_dim = self.pool_k[-1] * E * self.filters[-1]
+        self.built = True
+
+    def weights(self):
+        return [w for c in self.conv_layers for w in (c.kernel, c.bias)]
+
+    def forward(self, inputs):
+        raise NotImplementedError("CCPMBaseLayer runs fused with the lookup inside CCPMLayer (csrc/ccpm.hip)")
+
+
+class CCPMLayer(Layer):
+    """3.DCN/CustomLayers.py:680-725: output = MLP_layer2([1], sigmoid)(MLP_layer1(units, activation, batch norm)(
+    concat[ccpm_layer(embedding_layer(X_cate)), X_cont])), the continuous columns LAST.  The lookup, the convolutions,
+    the poolings and the Flatten are one kernel each way (functional.EmbCCPM); the MLPs run on the GEMM kernels."""
+
+    def __init__(self, categorical_features=["uid", "iid", "utag1", "utag2", "utag3", "utag4", "itag1", "itag2",
+                                             "itag3", "itag4"],
+                 continuous_features=["itag4_origin", "itag4_square", "itag4_cube"], feature_dims=150000,
+                 embedding_dims=16, units=[64, 32, 8], activation="relu", is_batch_norm=True, filters=[4, 6],
+                 kernel_width=[4, 2]):
+        super().__init__()
+        self.categorical_features = list(categorical_features)
+        self.continuous_features = list(continuous_features)
+        self.units = list(units)
+        self.activation = activation
+        F, C, E = len(self.categorical_features), len(self.continuous_features), int(embedding_dims)
+        self.ccpm_layer = CCPMBaseLayer(filters, kernel_width, input_shape=(F, E))
+        self.MLP_layer1 = MLPLayer(units=self.units, activation=activation, is_batch_norm=is_batch_norm,
+                                   input_dim=self.ccpm_layer.output_dim + C)
+        self.MLP_layer2 = MLPLayer(units=[1], activation="sigmoid", input_dim=self.units[-1])
+        self.embedding_layer = Embedding(feature_dims, E, embeddings_regularizer="l2")
+
+    def forward(self, inputs):
+        X = assemble_index(inputs, self.categorical_features)
+        flag = ops.new_flag(X.device) if self.check_ids else None
+        base = self.ccpm_layer
+        ccpm_output = Fn.EmbCCPM.apply(self.embedding_layer.embeddings, X, base.filters, base.kernel_width, flag,
+                                       *base.weights())
+        self._raise_if_oob(flag)
+        cont = _cont_block(inputs, self.continuous_features, X.device)
+        _input = ConcatCols.apply(ccpm_output, *cont) if cont else ccpm_output       # continuous LAST (:720)
+        return {"output": self.MLP_layer2(self.MLP_layer1(_input))}
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -182,6 +182,12 @@ class ModelManager:
             self.layer = CL.AttentionalFactorizationMachine(
                 categorical_features=self.feature_names, feature_dims=self.feature_dims,
                 embedding_dims=self.embedding_dims, attn_size=model_params.get("attn_size", 3))
+        elif layer_name == "CCPM":                         # 3.DCN/ModelManager.py:82-84
+            self.layer = CL.CCPMLayer(
+                categorical_features=self.feature_names, continuous_features=self.continuous_features,
+                feature_dims=self.feature_dims, embedding_dims=self.embedding_dims,
+                units=model_params.get("units", [64, 32, 8]), filters=model_params.get("filters", [4, 6]),
+                kernel_width=model_params.get("kernel_width", [4, 2]))
         elif layer_name == "din_layer":                    # 5.DIN/ModelManager.py:72-73
             p = dict(model_params)
             p.setdefault("feature_dims", self.feature_dims)

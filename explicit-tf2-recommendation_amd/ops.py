@@ -855,3 +855,97 @@ def emb_afm_bwd(table, X, Wa, ba, hv, bh, o, stats, dout, rows=None):
                                       _ptr(dWa), _ptr(dba), _ptr(dhv), _ptr(dbh), _ptr(ws), nbytes, _stream()),
               "rec_emb_afm_bwd_f32")
     return vals, dWa, dba, dhv, dbh
+
+
+# ---- CCPM: field convolutions + k-max pooling, fused with the lookup (csrc/ccpm.hip)
+CCPM_MAX_F, CCPM_MAX_E, CCPM_MAX_L, CCPM_MAX_C, CCPM_MAX_KW = 64, 64, 3, 16, 8
+
+
+def ccpm_k(E, L):
+    """The k of every KMaxPool of CCPMBaseLayer.build (3.DCN/CustomLayers.py:657-667), the expression as written.  Its
+    ``fields_num`` is input_shape[-1], the EMBEDDING width, not the field count: a reference quirk that is kept."""
+    fields_num = int(E)
+    layers_num = int(L)
+    return [max(1, int((1 - pow(j / layers_num, layers_num - j)) * fields_num)) if j < layers_num else 3
+            for j in range(1, layers_num + 1)]
+
+
+def _ccpm_ints(values):
+    return (C.c_int * len(values))(*[int(v) for v in values])
+
+
+def ccpm_param_count(filters, kernel_width):
+    cin, n = 1, 0
+    for c, kw in zip(filters, kernel_width):
+        n += kw * cin * c + c
+        cin = c
+    return n
+
+
+def ccpm_check_shape(F, E, filters, kernel_width):
+    """ValueError for a configuration the reference itself cannot run (a KMaxPool whose k exceeds the height it pools:
+    tf.nn.top_k raises), NotImplementedError for shapes the CCPM kernels do not cover (the ABI would return -2)."""
+    filters, kernel_width = [int(c) for c in filters], [int(k) for k in kernel_width]
+    if len(filters) != len(kernel_width) or len(filters) < 1:
+        raise ValueError("filters and kernel_width must be lists of one length >= 1, got %r and %r"
+                         % (filters, kernel_width))
+    if min(filters) < 1 or min(kernel_width) < 1 or F < 1 or E < 1:
+        raise ValueError("fields, embedding_dims, filters and kernel_width must be positive")
+    ks, h = ccpm_k(E, len(filters)), F
+    for j, k in enumerate(ks):
+        if k > h:
+            raise ValueError("KMaxPool %d takes k = %d of %d values (k comes from embedding_dims = %d, fields = %d): "
+                             "tf.nn.top_k raises" % (j + 1, k, h, E, F))
+        h = k
+    if lib.rec_ccpm_workspace_bytes(1, F, E, len(filters), _ccpm_ints(filters), _ccpm_ints(kernel_width),
+                                    _ccpm_ints(ks)) == 0:
+        raise NotImplementedError(
+            "CCPM kernels cover fields <= %d, embedding_dims <= %d, at most %d layers, filters <= %d, kernel_width <= %d "
+            "and a column state within the LDS of a CU; got fields=%d, embedding_dims=%d, filters=%r, kernel_width=%r"
+            % (CCPM_MAX_F, CCPM_MAX_E, CCPM_MAX_L, CCPM_MAX_C, CCPM_MAX_KW, F, E, filters, kernel_width))
+    return ks
+
+
+def emb_ccpm_fwd(table, X, params, filters, kernel_width, oob=None, want_rows=False):
+    """Lookup + L x (field conv, tanh, k-max pool) + Flatten in one launch: params is the flat K_1 | b_1 | K_2 | ...
+    -> (out [B, 3 E C_L], rows [B,F,E] or None)."""
+    _table(table, "table"); _i64(X, "X"); _f32(params, "params")
+    V, E = table.shape
+    B, F = X.shape
+    ks = ccpm_check_shape(F, E, filters, kernel_width)
+    if params.numel() != ccpm_param_count(filters, kernel_width):
+        raise ValueError("params must hold %d floats for filters %r and kernel_width %r, got %d"
+                         % (ccpm_param_count(filters, kernel_width), list(filters), list(kernel_width), params.numel()))
+    dev = table.device
+    out = torch.empty((B, ks[-1] * E * int(filters[-1])), dtype=torch.float32, device=dev)
+    rows = torch.empty((B, F, E), dtype=torch.float32, device=dev) if want_rows else None
+    check(lib.rec_emb_ccpm_fwd_f32(_ptr(table), V, E, table.stride(0), _ptr(X), B, F, len(ks), _ccpm_ints(filters),
+                                   _ccpm_ints(kernel_width), _ccpm_ints(ks), _ptr(params), _ptr(out), _ptr(rows),
+                                   _ptr(oob), _stream()), "rec_emb_ccpm_fwd_f32")
+    return out, rows
+
+
+def emb_ccpm_bwd(table, X, params, filters, kernel_width, dout, rows=None):
+    """-> (vals [B*F,E] IndexedSlices values in the order of X, dparams in the layout of params).  With the forward's
+    ``rows`` the table is not read again."""
+    _table(table, "table"); _i64(X, "X"); _f32(params, "params"); _f32(dout, "dout")
+    V, E = table.shape
+    B, F = X.shape
+    ks = ccpm_check_shape(F, E, filters, kernel_width)
+    if params.numel() != ccpm_param_count(filters, kernel_width):
+        raise ValueError("params does not match filters %r and kernel_width %r" % (list(filters), list(kernel_width)))
+    if tuple(dout.shape) != (B, ks[-1] * E * int(filters[-1])):
+        raise ValueError("dout must be [B, %d], got %s" % (ks[-1] * E * int(filters[-1]), tuple(dout.shape)))
+    if rows is not None and tuple(_f32(rows, "rows").shape) != (B, F, E):
+        raise ValueError("rows must be [B,F,E]")
+    dev = table.device
+    vals = torch.empty((B * F, E), dtype=torch.float32, device=dev)
+    dparams = torch.zeros_like(params)
+    if B > 0:
+        fi, kwi, ki = _ccpm_ints(filters), _ccpm_ints(kernel_width), _ccpm_ints(ks)
+        nbytes = lib.rec_ccpm_workspace_bytes(B, F, E, len(ks), fi, kwi, ki)
+        ws = _workspace(nbytes, "rec_ccpm_workspace_bytes", dev, torch.float32)
+        check(lib.rec_emb_ccpm_bwd_f32(_ptr(table), V, E, table.stride(0), _ptr(X), B, F, len(ks), fi, kwi, ki,
+                                       _ptr(params), _ptr(rows), _ptr(dout), _ptr(vals), _ptr(dparams), _ptr(ws),
+                                       nbytes, _stream()), "rec_emb_ccpm_bwd_f32")
+    return vals, dparams

@@ -611,6 +611,36 @@ int rec_emb_afm_bwd_f32(const float* table, int64_t V, int E, int64_t ld, const 
                         const float* stats, const float* rows, const float* dout, float* vals, float* dWa, float* dba,
                         float* dhv, float* dbh, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Convolutional Click Prediction Model, fused with the lookup (KMaxPool / CCPMBaseLayer / CCPMLayer,
+ * 3.DCN/CustomLayers.py:621-725; csrc/ccpm.hip).  X int64 [B, F], table [V, E] with row stride ld.  L layers; the HOST
+ * int arrays filters_host[L] (C_j), kernel_width_host[L] (kw_j) and pool_k_host[L] (k_j) describe them; params is one
+ * flat DEVICE buffer K_1 | b_1 | K_2 | b_2 | ... with K_j [kw_j, 1, C_{j-1}, C_j] row-major (C_0 = 1) and b_j [C_j].
+ * With x_0[h, e, 0] = table[X[b,h]][e] (H_0 = F) and for j = 1..L:
+ *   y[h, e, co] = tanh(b_j[co] + sum_t sum_ci K_j[t, 0, ci, co] x_{j-1}[h - (kw_j - 1) / 2 + t, e, ci])   zeros outside
+ *                 [0, H_{j-1}) (TF's SAME padding: the extra row at the end)
+ *   x_j[r, e, co] = the r-th largest y[., e, co] over h: values in descending order, the lower h first on equal values
+ *                 (tf.nn.top_k(sorted=True)); H_j = k_j
+ * The forward writes out [B, k_L E C_L], out[b, (r E + e) C_L + c] = x_L[r, e, c] (Flatten), and, when `rows` is not
+ * NULL, the gathered rows [B, F, E]; an id outside [0, V) sets *oob_flag (may be NULL) and reads as a zero row.
+ * The backward takes dout = dLoss/dout and writes vals [B*F, E], the IndexedSlices values of the lookup in the order of
+ * X (the gradient reaches the selected positions only), and dparams in the layout of params.  With `rows` (the
+ * forward's) it does not touch the table and X (both may then be NULL); with rows == NULL it gathers again.  No float
+ * atomics: bit-identical results run to run; no host synchronisation (graph-capturable).
+ * Supported: 1 <= F <= 64, 1 <= E <= 64, 1 <= L <= 3, 1 <= C_j <= 16, 1 <= kw_j <= 8, 1 <= k_j, 0 <= B < 2^31
+ * (B == 0: nothing is launched), V < 2^31, and a column's working set within the LDS of a CU at 64 threads: with
+ * S = F + sum_j k_j C_j, (2 S + F + ceil(S / 4)) * 256 + 4 * sum_j (kw_j C_{j-1} + 1) C_j <= 160 KiB; otherwise -2.
+ * A negative size, V <= 0, ld < E, a NULL pointer or k_j > H_{j-1} (top_k over fewer values than k): -1.
+ * workspace (backward only): rec_ccpm_workspace_bytes (0: invalid or unsupported shape). */
+size_t rec_ccpm_workspace_bytes(int64_t B, int F, int E, int L, const int* filters_host, const int* kernel_width_host,
+                                const int* pool_k_host);
+int rec_emb_ccpm_fwd_f32(const float* table, int64_t V, int E, int64_t ld, const int64_t* X, int64_t B, int F, int L,
+                         const int* filters_host, const int* kernel_width_host, const int* pool_k_host,
+                         const float* params, float* out, float* rows, int* oob_flag, void* stream);
+int rec_emb_ccpm_bwd_f32(const float* table, int64_t V, int E, int64_t ld, const int64_t* X, int64_t B, int F, int L,
+                         const int* filters_host, const int* kernel_width_host, const int* pool_k_host,
+                         const float* params, const float* rows, const float* dout, float* vals, float* dparams,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,8 @@ batches, one MI355X.  Prints one JSON line per config.  Usage:  python scripts/b
   AI  AutoInt at the reference defaults, 10 cat + 3 cont, V=10M, E=8, H=2, 2 attention layers, units [128,16], B=16384;
       AI26 = 26 cat + 3 cont, E=16, B=8192
   AF  AFM, 10 categorical fields, V=10M, E=16, attn_size 3, B=16384; AF26 = 26 fields, B=8192
+  CC  CCPM, 10 cat + 3 cont, V=10M, E=16, filters [4,6], kernel_width [4,2], units [64,32,8], B=16384; CC26 = 26 cat
+      fields, B=8192
 """
 import json
 import os
@@ -329,6 +331,20 @@ def run(name):
         return {"config": "%s AFM, %d fields, 10M x 16d, attn_size 3" % (name, ncat), "B": B, "V": V,
                 "ms_per_step": dt * 1e3, "examples_per_s": B / dt,
                 "fwd_algorithmic_mb": (B * ncat * (8 + 4 * E) + B * E * 4) / 1e6}
+    if name in ("CC", "CC26"):
+        ncat, B = (10, 16384) if name == "CC" else (26, 8192)
+        cat = ["c%d" % i for i in range(ncat)]
+        cont = ["x0", "x1", "x2"]
+        V, E = 10_000_000, 16
+        layer = layers.CCPMLayer(categorical_features=cat, continuous_features=cont, feature_dims=1000,
+                                 embedding_dims=E).cuda()
+        layer.embedding_layer.embeddings = torch.nn.Parameter(torch.empty((V, E), device="cuda"))
+        big_table_(layer.embedding_layer.embeddings)
+        batch = data.to_device(data.SyntheticGenerator(cat, V, continuous=cont, seed=0).batch(B))
+        dt = timed(fwd_bwd(layer, batch, cat + cont), 5, 50)
+        return {"config": "%s CCPM, %d cat + 3 cont, 10M x 16d, filters [4,6] x kernel_width [4,2], units [64,32,8]"
+                          % (name, ncat), "B": B, "V": V, "ms_per_step": dt * 1e3, "examples_per_s": B / dt,
+                "fwd_algorithmic_mb": (B * ncat * (8 + 4 * E) + B * 3 * E * 6 * 4) / 1e6}
     if name == "FF":
         names = ["C%d" % i for i in range(26)]
         V, B, E = 10_000_000, 8192, 16
@@ -374,7 +390,7 @@ if __name__ == "__main__":
     for n in (argv or ["A", "B", "C", "C26", "D", "E", "R", "P", "N", "FF", "G"]):
         r = run(n)
         if GRAPHED and n in ("B", "C", "C26", "D", "E", "DS", "ES", "P", "N", "FF", "G", "X", "X26", "FB", "FB26", "AI",
-                                "AI26", "AF", "AF26"):
+                                "AI26", "AF", "AF26", "CC", "CC26"):
             r["config"] += " [GraphedTrainStep]"
         r["n_gpus"] = 1
         print(json.dumps(r), flush=True)
