@@ -12,6 +12,13 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libmi355rec.so")
 
 p, i32, i64, f32, sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
 
+
+class DeepFMLazyAdam(C.Structure):
+    """rec_deepfm_lazy_adam of include/mi355rec.h: the optional lazy-Adam group of rec_deepfm_fused_post_f32."""
+    _fields_ = [("table", p), ("ld", i64), ("V", i64), ("m_e", p), ("v_e", p), ("m_w", p), ("v_w", p), ("ld_state", i64),
+                ("ld_wstate", i64), ("lr_t_dev", p), ("b1", f32), ("b2", f32), ("eps", f32), ("last", p), ("step_dev", p)]
+
+
 # symbol -> (restype, argtypes); must list every function of include/mi355rec.h
 SIGNATURES = {
     "rec_version": (i32, []),
@@ -41,8 +48,6 @@ SIGNATURES = {
     "rec_bce_fwd_bwd_f32": (i32, [p, p, i64, p, p, p, p]),
     "rec_adam_lr_t_f32": (f32, [f32, f32, f32, i64]),
     "rec_adam_dense_multi_f32": (i32, [i32, p, p, p, p, p, p, f32, f32, f32, p]),
-    "rec_deepfm_fused_post_direct_adam_dev_f32": (i32, [i32, i64] + [p] * 19 + [p, i64, i64, p, p, p, p, i64, i64, p, f32,
-                                                                           f32, f32, p, p, p]),
     "rec_adam_keras_catchup_f32": (i32, [p, p, i64, i32, p, i64, i64, p, p, i64, p, p, i64, p, p, p, i64, f32, f32, f32, p]),
     "rec_adam_keras_flush_f32": (i32, [p, i64, i64, p, p, i64, p, p, i64, p, p, p, i64, f32, f32, f32, p]),
     "rec_adam_dense_f32": (i32, [p, p, p, p, i64, i64, f32, f32, f32, f32, p]),
@@ -74,19 +79,15 @@ SIGNATURES = {
     "rec_auc_hist_update_f32": (i32, [p, p, i64, p, i32, p, p, i32, p, p]),
     "rec_shard_slab_map_uslot_i64": (i32, [p, p, p, p, i64, i64, i32, i64, p, p, p, p, p]),
     "rec_dedup_plan_sorted_slabs_i64": (i32, [p, i32, i64, i64, p, p, p, p, p, sz, p]),
-    "rec_deepfm_fused_post_slots_f32": (i32, [i32, i64] + [p] * 17 + [p]),
     "rec_permute_rows_f32": (i32, [p, p, i64, i32, i32, p, p]),
     "rec_deepfm_fused_workspace_bytes": (sz, [i64, i32]),
-    "rec_deepfm_fused_post_f32": (i32, [i32, i64] + [p] * 19 + [i32, p]),
     "rec_colsort_workspace_bytes": (sz, [i64, i32]),
     "rec_colsort_digits": (i32, [i64, i64, p, p]),
     "rec_colsort_plan_i64": (i32, [p, i32, i64, i64, p, i64, p, p, p, p, p, p, p]),
     "rec_colsort_plan_dest_i64": (i32, [p, i32, i64, i64, p, i64, p, p, p, p, p, p, p, p]),
-    "rec_deepfm_fused_post_direct_f32": (i32, [i32, i64] + [p] * 19 + [p]),
     "rec_deepfm_k0t_f32": (i32, [p, i32, p, p]),
-    "rec_deepfm_fused3_main_f32": (i32, [p, i64, i64, p, i32, i64] + [p] * 14 + [p]),
-    "rec_deepfm_fused3_main_direct_f32": (i32, [p, i64, i64, p, i32, i64] + [p] * 14 + [p, p, p] + [p]),
-    "rec_deepfm_fused3_main_direct_adv_f32": (i32, [p, i64, i64, p, i32, i64] + [p] * 14 + [p, p, p] + [p, p, i64, p] + [p]),
+    "rec_deepfm_fused3_main_f32": (i32, [p, i64, i64, p, i32, i64] + [p] * 10 + [p, p, i64, p] + [p]),
+    "rec_deepfm_fused_post_f32": (i32, [i32, i64] + [p] * 14 + [i32, C.POINTER(DeepFMLazyAdam), p]),
     "rec_dssm_fused_workspace_bytes": (sz, [i64, i32, i32, i32]),
     "rec_dssm_fused_main_f32": (i32, [p, i64, i64, p, i32, p, i64, i64, p, i32, i32, i32, i32, i32, i64, p, p, p, p, p, p,
                                       p, p, p, sz, p, p, i64, p, p]),

@@ -13,6 +13,10 @@
 // Also here: the exact lazy evaluation of Keras' Adam sweep (adam_keras_catchup_kernel: the steps a row skipped are
 // replayed before a batch reads it; the flush brings every row up to date).
 //
+// ONE entry point, rec_deepfm_fused_post_f32: slot_map, direct and the lazy-Adam group are independent options and reach
+// the kernels as the ColSegArgs fields they are.  (ColSegArgs::lr_t is filled by the kernel from lr_t_dev; `packed` is
+// slot_map != null.)
+//
 // Everything is deterministic (no float atomics): per-workgroup partials + fixed-order reductions, stable sort keys.
 #include "deepfm_fused.h"
 #include <math.h>
@@ -145,25 +149,22 @@ struct ColSegArgs {
   int32_t* last; const int64_t* step_dev;
 };
 
-// m <- b1 m + (1-b1) g ; v <- b2 v + (1-b2) g^2 ; var <- var - lr_t m / (sqrt(v) + eps)   (rec_adam_rows_f32's formula)
-__device__ __forceinline__ void adam_elem(float& var, float& m, float& v, float g, float lr_t, float b1, float b2,
-                                          float eps) {
-  adam_touch(var, m, v, g, lr_t, b1, b2, eps);       // common.h: rounding pinned, the same bits in every kernel
-}
+// m <- b1 m + (1-b1) g ; v <- b2 v + (1-b2) g^2 ; var <- var - lr_t m / (sqrt(v) + eps)   (rec_adam_rows_f32's formula:
+// adam_touch of common.h, rounding pinned, the same bits in every kernel)
 __device__ __forceinline__ void adam_chunk(const ColSegArgs& k, int64_t id, int c, const float4& g) {
   float4* vp = reinterpret_cast<float4*>(k.table + id * LD) + c;
   float4* mp = reinterpret_cast<float4*>(k.m_e + id * k.ldm) + c;
   float4* qp = reinterpret_cast<float4*>(k.v_e + id * k.ldm) + c;
   float4 x = *vp, m = *mp, v = *qp;
-  adam_elem(x.x, m.x, v.x, g.x, k.lr_t, k.b1, k.b2, k.eps);
-  adam_elem(x.y, m.y, v.y, g.y, k.lr_t, k.b1, k.b2, k.eps);
-  adam_elem(x.z, m.z, v.z, g.z, k.lr_t, k.b1, k.b2, k.eps);
-  adam_elem(x.w, m.w, v.w, g.w, k.lr_t, k.b1, k.b2, k.eps);
+  adam_touch(x.x, m.x, v.x, g.x, k.lr_t, k.b1, k.b2, k.eps);
+  adam_touch(x.y, m.y, v.y, g.y, k.lr_t, k.b1, k.b2, k.eps);
+  adam_touch(x.z, m.z, v.z, g.z, k.lr_t, k.b1, k.b2, k.eps);
+  adam_touch(x.w, m.w, v.w, g.w, k.lr_t, k.b1, k.b2, k.eps);
   *vp = x; *mp = m; *qp = v;
 }
 __device__ __forceinline__ void adam_w(const ColSegArgs& k, int64_t id, float g) {
   float x = k.table[id * LD + E16], m = k.m_w[id * k.ldw], v = k.v_w[id * k.ldw];
-  adam_elem(x, m, v, g, k.lr_t, k.b1, k.b2, k.eps);
+  adam_touch(x, m, v, g, k.lr_t, k.b1, k.b2, k.eps);
   k.table[id * LD + E16] = x; k.m_w[id * k.ldw] = m; k.v_w[id * k.ldw] = v;
 }
 
@@ -747,110 +748,62 @@ extern "C" size_t rec_deepfm_fused_workspace_bytes(int64_t B, int F) {
   return fused_workspace(B, F).bytes() + 256;
 }
 
-static int launch_post(bool direct, int F, int64_t B, const float* gz, const float* vals, float* dK0, float* db0,
-                       float* dK1, float* db1, float* dK2, float* db2, float* dbias, float* loss, void* workspace,
-                       const int32_t* perm, const int64_t* col_uid, const int32_t* col_seg, const int32_t* col_nu,
-                       int64_t* uniq_ids, float* g_embed_rows, float* g_w_rows, int64_t* n_uniq, int packed,
-                       void* stream, const ColSegArgs* adam = nullptr) {
+// The one entry point of the post launch.  Three independent options:
+//   slot_map   (sharded step) packed rows [embed 16 | w | 0 0 0] go to the slots rec_colsort_shard_map_fixed_i64 gave the
+//              batch's unique ids inside g_embed_rows [owners * capacity, 20]; unused slots are not written
+//   direct     the plan (rec_colsort_plan_dest_i64) existed BEFORE the main kernel ran, which wrote the value row of every
+//              run's first member straight into g_embed_rows; this launch finishes runs with more members, fills uniq_ids /
+//              g_w_rows / n_uniq and the padded tail
+//   adam       (direct only) the lazy (touched-rows) Adam update of both tables (rec_adam_rows_f32's arithmetic) applied to
+//              every row the moment its gradient is final: no second pass over g_embed_rows / g_w_rows, no extra launch.
+//              The step size is read from device memory (lr_t_dev, advanced by the main launch on the same stream): no
+//              per-step host scalar, so a whole train step replays from a hipGraph.  last / step_dev (optional): the exact
+//              lazy evaluation of Keras' sweep
+extern "C" int rec_deepfm_fused_post_f32(int F, int64_t B, const float* gz, const float* vals, float* const* grads,
+                                         float* loss, void* workspace, const int32_t* perm, const int64_t* col_uid,
+                                         const int32_t* col_seg, const int32_t* col_nu, int64_t* uniq_ids,
+                                         float* g_embed_rows, float* g_w_rows, int64_t* n_uniq, const int32_t* slot_map,
+                                         int direct, const rec_deepfm_lazy_adam* adam, void* stream) {
+  if (adam) {
+    if (!adam->table || !adam->m_e || !adam->v_e || !adam->m_w || !adam->v_w || !adam->lr_t_dev || adam->V <= 0 ||
+        adam->ld_state < E16 || (adam->ld_state & 3) != 0 || adam->ld_wstate < 1)
+      return REC_E_ARG;
+    if (adam->ld != LD || !rec_is_aligned16(adam->table) || !rec_is_aligned16(adam->m_e) || !rec_is_aligned16(adam->v_e))
+      return REC_E_UNSUPPORTED;
+    if (adam->last && !adam->step_dev) return REC_E_ARG;
+  }
   if (B <= 0 || F <= 0 || F > 28) return REC_E_ARG;
-  if (!gz || !vals || !dK0 || !db0 || !dK1 || !db1 || !dK2 || !db2 || !dbias || !loss || !workspace || !perm ||
-      !col_uid || !col_seg || !col_nu || !g_embed_rows || (!packed && !g_w_rows))
+  if (!gz || !vals || !grads || !loss || !workspace || !perm || !col_uid || !col_seg || !col_nu || !g_embed_rows)
     return REC_E_ARG;
-  const bool slots = adam && adam->slot_map;
-  if (!slots && (!uniq_ids || !n_uniq)) return REC_E_ARG;
-  if (slots && (direct || !packed)) return REC_E_UNSUPPORTED;
-  if (direct && packed) return REC_E_UNSUPPORTED;
+  for (int i = 0; i < 7; ++i)
+    if (!grads[i]) return REC_E_ARG;
+  if (slot_map ? (uniq_ids || g_w_rows || n_uniq) : (!uniq_ids || !g_w_rows || !n_uniq)) return REC_E_ARG;
+  if ((slot_map && direct) || (adam && !direct)) return REC_E_UNSUPPORTED;
   if (!rec_is_aligned16(vals) || !rec_is_aligned16(g_embed_rows))
     return REC_E_UNSUPPORTED;
   const FusedWorkspace ws = fused_workspace(B, F);
   int D = F * E16;
   unsigned nb = (unsigned)reduce_blocks(D);
-  unsigned nbs = (unsigned)ceil_div64(B * F * 4, 1024);
-  ReduceArgs r{ws.dK0part(workspace), ws.small(workspace), ws.nwg, D, B, dK0, dK1, db0, db1, dK2, db2, dbias, loss};
-  ColSegArgs k{(const float4*)vals, gz, perm, col_uid, col_seg, col_nu, B, F, uniq_ids, (float4*)g_embed_rows,
-               packed ? (float*)nullptr : g_w_rows, n_uniq, packed ? 1 : 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0.f,
-               0.f, 0.f, 0.f, nullptr};
-  if (slots) {
-    k.slot_map = adam->slot_map;
-  } else if (adam) {
+  ReduceArgs r{ws.dK0part(workspace), ws.small(workspace), ws.nwg, D, B,
+               grads[0], grads[2], grads[1], grads[3], grads[4], grads[5], grads[6], loss};   // dK0 dK1 db0 db1 dK2 db2 dbias
+  ColSegArgs k{};                                        // (lr_t stays 0: the step size comes from lr_t_dev)
+  k.vals = (const float4*)vals; k.gz = gz; k.perm = perm; k.col_uid = col_uid; k.col_seg = col_seg; k.col_nu = col_nu;
+  k.B = B; k.F = F; k.uniq_ids = uniq_ids; k.g_embed = (float4*)g_embed_rows; k.g_w = g_w_rows; k.n_uniq = n_uniq;
+  k.packed = slot_map ? 1 : 0; k.slot_map = slot_map;
+  if (adam) {
     k.table = adam->table; k.m_e = adam->m_e; k.v_e = adam->v_e; k.m_w = adam->m_w; k.v_w = adam->v_w; k.V = adam->V;
-    k.lr_t = adam->lr_t; k.b1 = adam->b1; k.b2 = adam->b2; k.eps = adam->eps; k.lr_t_dev = adam->lr_t_dev;
-    k.ldm = adam->ldm ? adam->ldm : E16; k.ldw = adam->ldw ? adam->ldw : 1;
-    k.last = adam->last; k.step_dev = adam->step_dev;
+    k.b1 = adam->b1; k.b2 = adam->b2; k.eps = adam->eps; k.lr_t_dev = adam->lr_t_dev;
+    k.ldm = adam->ld_state; k.ldw = adam->ld_wstate; k.last = adam->last; k.step_dev = adam->step_dev;
   }
   if (direct) {
     unsigned nbf = (unsigned)F * (unsigned)ceil_div64(B, FIX_T);
     hipLaunchKernelGGL(deepfm_post_direct_kernel, dim3(nb + nbf), dim3(1024), 0, as_stream(stream), r, k, (int)nb);
   } else {
+    unsigned nbs = (unsigned)ceil_div64(B * F * 4, 1024);
     hipLaunchKernelGGL(deepfm_post_kernel, dim3(nb + nbs), dim3(1024), 0, as_stream(stream), r, k, (int)nb);
   }
   REC_LAUNCH_CHECK();
   return REC_OK;
-}
-
-extern "C" int rec_deepfm_fused_post_f32(int F, int64_t B, const float* gz, const float* vals, float* dK0, float* db0,
-                                         float* dK1, float* db1, float* dK2, float* db2, float* dbias, float* loss,
-                                         void* workspace, const int32_t* perm, const int64_t* col_uid,
-                                         const int32_t* col_seg, const int32_t* col_nu, int64_t* uniq_ids,
-                                         float* g_embed_rows, float* g_w_rows, int64_t* n_uniq, int packed,
-                                         void* stream) {
-  return launch_post(false, F, B, gz, vals, dK0, db0, dK1, db1, dK2, db2, dbias, loss, workspace, perm, col_uid, col_seg,
-                     col_nu, uniq_ids, g_embed_rows, g_w_rows, n_uniq, packed, stream);
-}
-
-// sharded step with fixed-capacity exchanges: the packed rows [embed 16 | w | 0 0 0] of the batch's unique ids go to the
-// slots rec_colsort_shard_map_fixed_i64 gave them inside g_rows [owners * capacity, 20]; unused slots are not written
-extern "C" int rec_deepfm_fused_post_slots_f32(int F, int64_t B, const float* gz, const float* vals, float* dK0,
-                                               float* db0, float* dK1, float* db1, float* dK2, float* db2, float* dbias,
-                                               float* loss, void* workspace, const int32_t* perm, const int64_t* col_uid,
-                                               const int32_t* col_seg, const int32_t* col_nu, const int32_t* slot_map,
-                                               float* g_rows, void* stream) {
-  if (!slot_map) return REC_E_ARG;
-  ColSegArgs a{};
-  a.slot_map = slot_map;
-  return launch_post(false, F, B, gz, vals, dK0, db0, dK1, db1, dK2, db2, dbias, loss, workspace, perm, col_uid, col_seg,
-                     col_nu, nullptr, g_rows, nullptr, nullptr, 1, stream, &a);
-}
-
-// direct mode: the plan (rec_colsort_plan_dest_i64) existed BEFORE the main kernel ran, which wrote the value row of
-// every run's first member straight into g_embed_rows; this launch finishes runs with more members, fills uniq_ids /
-// g_w_rows / n_uniq and the padded tail, and reduces the dense partials
-extern "C" int rec_deepfm_fused_post_direct_f32(int F, int64_t B, const float* gz, const float* vals, float* dK0,
-                                                float* db0, float* dK1, float* db1, float* dK2, float* db2, float* dbias,
-                                                float* loss, void* workspace, const int32_t* perm, const int64_t* col_uid,
-                                                const int32_t* col_seg, const int32_t* col_nu, int64_t* uniq_ids,
-                                                float* g_embed_rows, float* g_w_rows, int64_t* n_uniq, void* stream) {
-  return launch_post(true, F, B, gz, vals, dK0, db0, dK1, db1, dK2, db2, dbias, loss, workspace, perm, col_uid, col_seg,
-                     col_nu, uniq_ids, g_embed_rows, g_w_rows, n_uniq, 0, stream);
-}
-
-// ... with the lazy (touched-rows) Adam update of both tables (rec_adam_rows_f32's arithmetic) applied to every row the
-// moment its gradient is final: no second pass over g_embed_rows / g_w_rows, no extra launch.  table: the fused rows
-// [V, 32] (embed 16 | w | pad).  The step size is read from device memory (lr_t_dev, advanced by
-// rec_deepfm_fused3_main_direct_adv_f32 on the same stream): no per-step host scalar, so a whole train step -- this
-// launch included -- replays from a hipGraph.  last / step_dev (optional): the exact lazy evaluation of Keras' sweep
-extern "C" int rec_deepfm_fused_post_direct_adam_dev_f32(int F, int64_t B, const float* gz, const float* vals, float* dK0,
-                                                         float* db0, float* dK1, float* db1, float* dK2, float* db2,
-                                                         float* dbias, float* loss, void* workspace, const int32_t* perm,
-                                                         const int64_t* col_uid, const int32_t* col_seg,
-                                                         const int32_t* col_nu, int64_t* uniq_ids, float* g_embed_rows,
-                                                         float* g_w_rows, int64_t* n_uniq, float* table, int64_t ld,
-                                                         int64_t V, float* m_e, float* v_e, float* m_w, float* v_w,
-                                                         int64_t ld_state, int64_t ld_wstate,
-                                                         const float* lr_t_dev, float b1, float b2, float eps,
-                                                         int32_t* last, const int64_t* step_dev, void* stream) {
-  if (!table || !m_e || !v_e || !m_w || !v_w || !lr_t_dev || V <= 0 || ld_state < E16 || (ld_state & 3) != 0 ||
-      ld_wstate < 1)
-    return REC_E_ARG;
-  if (ld != LD || !rec_is_aligned16(table) || !rec_is_aligned16(m_e) || !rec_is_aligned16(v_e))
-    return REC_E_UNSUPPORTED;
-  ColSegArgs a{};
-  a.table = table; a.m_e = m_e; a.v_e = v_e; a.m_w = m_w; a.v_w = v_w; a.V = V;
-  if (last && !step_dev) return REC_E_ARG;
-  a.lr_t = 0.f; a.lr_t_dev = lr_t_dev; a.b1 = b1; a.b2 = b2; a.eps = eps; a.ldm = ld_state; a.ldw = ld_wstate;
-  a.last = last; a.step_dev = step_dev;
-  return launch_post(true, F, B, gz, vals, dK0, db0, dK1, db1, dK2, db2, dbias, loss, workspace, perm, col_uid, col_seg,
-                     col_nu, uniq_ids, g_embed_rows, g_w_rows, n_uniq, 0, stream, &a);
 }
 
 static int catchup_args_ok(const float* table, int64_t ld, int64_t V, const float* m_e, const float* v_e, int64_t ld_state,

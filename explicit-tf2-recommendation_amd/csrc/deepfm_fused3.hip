@@ -1,7 +1,8 @@
 // Main kernel of the fused DeepFM train step (2.FM/CustomLayers.py:279-308 under 2.FM/ModelManager.py:171-177;
 // embedding_dims 16, mlp_dims [32, 8], fused [embed 16 | w | pad] rows).  It writes gz, the IndexedSlices value rows and
 // the per-workgroup partials of the dense gradients into the workspace of deepfm_fused.h; the post launch of
-// deepfm_fused.hip finishes the step.
+// deepfm_fused.hip finishes the step.  ONE entry point, rec_deepfm_fused3_main_f32 (at the end of the file): the plan
+// pointers select the direct instantiation, the optimizer's clock is an optional group of its own.
 //
 // What the B sweep of round 3 showed (profiles/r03_b_sweep.json): the chip sustains ~50 G random 128-byte lines/s, one CU
 // pulls ~25-30 GB/s from HBM (its 832 rows of a 32-example tile need ~4 us whatever the chip does), and the kernel this
@@ -670,23 +671,28 @@ extern "C" int rec_deepfm_k0t_f32(const float* K0, int F, float* K0T, void* stre
   return REC_OK;
 }
 
-static int launch_fused3(const float* table, int64_t ld, int64_t V, const int64_t* const* cols_host, int F, int64_t B,
-                         const float* bias, const float* K0, const float* K0T, const float* b0, const float* K1,
-                         const float* b1, const float* K2, const float* b2, const float* label, float* gz, float* vals,
-                         float* prob, int* oob_flag, void* workspace, const int32_t* dloc, const int32_t* col_nu,
-                         float* g_embed, bool direct, void* stream, int64_t* step_dev = nullptr,
-                         const float* lr_tab = nullptr, int64_t n_tab = 0, float* lr_t_dev = nullptr) {
+// The one entry point of the main launch.  dloc != NULL: direct mode (the plan exists, ld = 32); step_dev != NULL: the
+// kernel's first thread also advances the optimizer's device-side clock (the kernel itself reads neither word, so the
+// catch-up kernel before it saw the old step, the post launch and the dense update behind it see the new one).
+extern "C" int rec_deepfm_fused3_main_f32(const float* table, int64_t ld, int64_t V, const int64_t* const* cols_host,
+                                          int F, int64_t B, const float* const* weights, const float* label, float* gz,
+                                          float* vals, float* prob, int* oob_flag, void* workspace, const int32_t* dloc,
+                                          const int32_t* col_nu, float* g_embed_rows, int64_t* step_dev,
+                                          const float* lr_table, int64_t n_table, float* lr_t_dev, void* stream) {
+  const bool direct = dloc != nullptr;
   if (B <= 0 || F <= 0 || V <= 0) return REC_E_ARG;
-  if (step_dev && (!lr_tab || !lr_t_dev || n_tab <= 0)) return REC_E_ARG;
+  if (step_dev && (!lr_table || !lr_t_dev || n_table <= 0)) return REC_E_ARG;
   if (F > 28 || F > REC_MAX_COLS || V >= (int64_t(1) << 31)) return REC_E_UNSUPPORTED;
   if (direct ? ld != 32 : (ld < 20 || (ld & 3) != 0)) return REC_E_UNSUPPORTED;
-  if (!table || !cols_host || !bias || !K0 || !K0T || !b0 || !K1 || !b1 || !K2 || !b2 || !label || !gz || !vals ||
-      !workspace)
-    return REC_E_ARG;
-  if (direct && (!dloc || !col_nu || !g_embed)) return REC_E_ARG;
+  if (!table || !cols_host || !weights || !label || !gz || !vals || !workspace) return REC_E_ARG;
+  for (int i = 0; i < 8; ++i)
+    if (!weights[i]) return REC_E_ARG;
+  const float *bias = weights[0], *K0 = weights[1], *K0T = weights[2], *b0 = weights[3], *K1 = weights[4],
+              *b1 = weights[5], *K2 = weights[6], *b2 = weights[7];
+  if (direct ? (!col_nu || !g_embed_rows) : (col_nu || g_embed_rows)) return REC_E_ARG;
   if (B * F * E16 * 4 >= (int64_t(1) << 31)) return REC_E_UNSUPPORTED;    // 32-bit byte offsets into vals / g_embed_rows
   if (!rec_is_aligned16(table) || !rec_is_aligned16(K0) || !rec_is_aligned16(K0T) || !rec_is_aligned16(vals) ||
-      (direct && !rec_is_aligned16(g_embed)))
+      (direct && !rec_is_aligned16(g_embed_rows)))
     return REC_E_UNSUPPORTED;
   // K0 in LDS whenever it fits beside the rest (F <= 26); else its fragments come from L2 (K0 and K0T)
   bool klds = F <= 26;                                   // the B waves stage 13 x 256 16-byte pieces: 8 * 16 F <= 3328
@@ -710,10 +716,10 @@ static int launch_fused3(const float* table, int64_t ld, int64_t V, const int64_
   if (!stamps && hipMalloc(&stamps, sizeof(unsigned long long) * 12 * NWV * 65536) != hipSuccess) return REC_E_ARG;
   g_fused3_stamps = stamps;
   F3Args a{table, V, (int)ld, bias, K0, K0T, b0, K1, b1, K2, b2, label, B, F, gz, vals, prob, dK0part, small, oob_flag,
-           dloc, col_nu, g_embed, step_dev, lr_tab, n_tab, lr_t_dev, stamps};
+           dloc, col_nu, g_embed_rows, step_dev, lr_table, n_table, lr_t_dev, stamps};
 #else
   F3Args a{table, V, (int)ld, bias, K0, K0T, b0, K1, b1, K2, b2, label, B, F, gz, vals, prob, dK0part, small, oob_flag,
-           dloc, col_nu, g_embed, step_dev, lr_tab, n_tab, lr_t_dev};
+           dloc, col_nu, g_embed_rows, step_dev, lr_table, n_table, lr_t_dev};
 #endif
   hipStream_t st = as_stream(stream);
 #define LAUNCH3(DIR, KL)                                                                                         \
@@ -729,40 +735,4 @@ static int launch_fused3(const float* table, int64_t ld, int64_t V, const int64_
 #undef LAUNCH3
   REC_LAUNCH_CHECK();
   return REC_OK;
-}
-
-extern "C" int rec_deepfm_fused3_main_f32(const float* table, int64_t ld, int64_t V, const int64_t* const* cols_host,
-                                          int F, int64_t B, const float* bias, const float* K0, const float* K0T,
-                                          const float* b0, const float* K1, const float* b1, const float* K2,
-                                          const float* b2, const float* label, float* gz, float* vals, float* prob,
-                                          int* oob_flag, void* workspace, void* stream) {
-  return launch_fused3(table, ld, V, cols_host, F, B, bias, K0, K0T, b0, K1, b1, K2, b2, label, gz, vals, prob, oob_flag,
-                       workspace, nullptr, nullptr, nullptr, false, stream);
-}
-
-extern "C" int rec_deepfm_fused3_main_direct_f32(const float* table, int64_t ld, int64_t V,
-                                                 const int64_t* const* cols_host, int F, int64_t B, const float* bias,
-                                                 const float* K0, const float* K0T, const float* b0, const float* K1,
-                                                 const float* b1, const float* K2, const float* b2, const float* label,
-                                                 float* gz, float* vals, float* prob, int* oob_flag, void* workspace,
-                                                 const int32_t* dloc, const int32_t* col_nu, float* g_embed_rows,
-                                                 void* stream) {
-  return launch_fused3(table, ld, V, cols_host, F, B, bias, K0, K0T, b0, K1, b1, K2, b2, label, gz, vals, prob, oob_flag,
-                       workspace, dloc, col_nu, g_embed_rows, true, stream);
-}
-
-// rec_deepfm_fused3_main_direct_f32 that also advances the optimizer's device-side step: *step_dev += 1 and *lr_t_dev =
-// lr_table[min(*step_dev, n_table) - 1] are done by the fused kernel's first thread (the kernel itself reads neither), so the
-// post launch and the dense update behind it see the new step, the catch-up kernel before it saw the old one.
-extern "C" int rec_deepfm_fused3_main_direct_adv_f32(const float* table, int64_t ld, int64_t V,
-                                                     const int64_t* const* cols_host, int F, int64_t B, const float* bias,
-                                                     const float* K0, const float* K0T, const float* b0, const float* K1,
-                                                     const float* b1, const float* K2, const float* b2, const float* label,
-                                                     float* gz, float* vals, float* prob, int* oob_flag, void* workspace,
-                                                     const int32_t* dloc, const int32_t* col_nu, float* g_embed_rows,
-                                                     int64_t* step_dev, const float* lr_table, int64_t n_table,
-                                                     float* lr_t_dev, void* stream) {
-  if (!step_dev || !lr_table || !lr_t_dev || n_table <= 0) return REC_E_ARG;
-  return launch_fused3(table, ld, V, cols_host, F, B, bias, K0, K0T, b0, K1, b1, K2, b2, label, gz, vals, prob, oob_flag,
-                       workspace, dloc, col_nu, g_embed_rows, true, stream, step_dev, lr_table, n_table, lr_t_dev);
 }

@@ -578,7 +578,7 @@ inline float adam_lr_t(float lr, float b1, float b2, int64_t t) {
 
 }  // namespace
 
-extern "C" int rec_version(void) { return 104; }
+extern "C" int rec_version(void) { return 105; }
 
 extern "C" int rec_act_bwd_f32(int act, const float* post, const float* dpost, float* dpre, int64_t n,
                                void* stream) {

@@ -10,13 +10,14 @@ parameters; (uniq_ids, rows, n_uniq) for the tables) -- tests/test_gpu_engine.py
 """
 import collections
 import ctypes as C
+import math
 import operator
 import weakref
 
 import torch
 
 from . import ops
-from ._lib import lib, check
+from ._lib import lib, check, DeepFMLazyAdam
 
 
 # Adam's constants: the defaults of tf.keras.optimizers.Adam, the reference's optimizer
@@ -54,6 +55,101 @@ def _tables_share_rows(embed, w):
     E = embed.shape[1]
     return (embed.is_cuda and E % 4 == 0 and embed.stride(0) == w.stride(0) and embed.stride(0) % 4 == 0
             and embed.stride(0) >= E + 1 and w.data_ptr() == embed.data_ptr() + 4 * E and embed.data_ptr() % 16 == 0)
+
+
+def _deepfm_dense(F, u1=32, u2=8, E=16):
+    """The dense parameters of DeepFMRankingLayer, (name, shape) in the order every step keeps them: the order of
+    ``g``, of the post launch's gradient array and of ShardedDeepFMStep's flat buffer."""
+    return (("MLP_layer1.kernel_0", (F * E, u1)), ("MLP_layer1.bias_0", (u1,)), ("MLP_layer1.kernel_1", (u1, u2)),
+            ("MLP_layer1.bias_1", (u2,)), ("MLP_layer2.kernel_0", (u2, 1)), ("MLP_layer2.bias_0", (1,)), ("bias", (1,)))
+
+
+def _deepfm_ptr_arrays(layer, k0t, g):
+    """The two host pointer arrays of the fused launches: the weights bias, K0, K0T, b0, K1, b1, K2, b2 of
+    rec_deepfm_fused3_main_f32 and the gradients ``g`` of rec_deepfm_fused_post_f32.  Built once per step object:
+    parameters, the transposed copy and gradients are updated in place."""
+    params, names = dict(layer.named_parameters()), list(g)
+    w = [params["bias"], params[names[0]], k0t.buf] + [params[n] for n in names[1:6]]
+    return (C.c_void_p * 8)(*[t.data_ptr() for t in w]), (C.c_void_p * 7)(*[t.data_ptr() for t in g.values()])
+
+
+def _deepfm_gradients(step):
+    """Dense grads by parameter name + the two tables' (uniq_ids, rows, n_uniq)."""
+    out = dict(step.g)
+    out["embed.embeddings"] = (step.uniq_ids, step.g_embed_rows, step.n_uniq)
+    out["w.embeddings"] = (step.uniq_ids, step.g_w_rows, step.n_uniq)
+    return out
+
+
+def _deepfm_host_adam(layer, g, state, uniq_ids, g_embed_rows, g_w_rows, n_uniq, side_e, side_w, optimizer, t, lr, st,
+                      after_dense=None):
+    """Adam on a DeepFM layer with the 1-based step ``t`` as a host scalar: the dense parameters one by one
+    (``after_dense()`` runs behind them), then both tables -- 'keras_adam': the reference's dense sweep, as ONE sweep over
+    the fused [embed | w | pad] rows where the tables share them; otherwise the touched rows only."""
+    b1, b2, eps = ADAM_B1, ADAM_B2, ADAM_EPS
+    params = dict(layer.named_parameters())
+    for name, grad in g.items():
+        m, v = state[name]
+        check(lib.rec_adam_dense_f32(_p(params[name]), _p(m), _p(v), _p(grad), grad.numel(), t, lr, b1, b2, eps, st),
+              "rec_adam_dense_f32")
+    if after_dense is not None:
+        after_dense()
+    n = uniq_ids.numel()
+    pe, pw = params["embed.embeddings"], params["w.embeddings"]
+    V, E = pe.shape
+    if optimizer == "keras_adam" and _tables_share_rows(pe, pw):
+        (me, ve), (mw, vw) = state["embed.embeddings"], state["w.embeddings"]
+        check(lib.rec_adam_sparse_keras_pair_f32(_p(pe), pe.stride(0), _p(me), _p(ve), _p(mw), _p(vw), V, E, _p(uniq_ids),
+                                                 _p(g_embed_rows), _p(g_w_rows), _p(n_uniq), n, _p(side_e), _p(side_w), t,
+                                                 lr, b1, b2, eps, st), "rec_adam_sparse_keras_pair_f32")
+        return
+    for p, rows, side in ((pe, g_embed_rows, side_e), (pw, g_w_rows, side_w)):
+        m, v = state["embed.embeddings" if p is pe else "w.embeddings"]
+        if optimizer == "keras_adam":
+            check(lib.rec_adam_sparse_keras_f32(_p(p), p.stride(0), _p(m), _p(v), V, p.shape[1], _p(uniq_ids), _p(rows),
+                                                _p(n_uniq), n, _p(side), t, lr, b1, b2, eps, st),
+                  "rec_adam_sparse_keras_f32")
+        else:
+            check(lib.rec_adam_rows_f32(_p(p), p.stride(0), _p(m), _p(v), V, p.shape[1], _p(uniq_ids), _p(rows),
+                                        _p(n_uniq), n, t, lr, b1, b2, eps, st), "rec_adam_rows_f32")
+
+
+class _ColPlanRing:
+    """``nbuf`` per-column de-duplication plans (csrc/colsort.hip): perm, col_uid [F,B], col_seg [F,B+1], col_nu [F] and
+    -- ``dloc`` -- the inverse view the direct mode of the fused step reads.  ``plans[buf]`` holds a buffer's views by
+    those names, ``a_plan[buf]`` the addresses of the first four as a ctypes tuple.  Consecutive buffers are contiguous,
+    so ONE sort call builds the plans of up to ``group`` batches as group*F columns (one workgroup per column, 256 column
+    pointers per launch; the sort kernels are latency-bound at < 1 wave per SIMD: two batches cost ~1.2x one).
+    ``ws_per_buf``: a sort workspace per buffer (sorts that run on a second stream) instead of one."""
+
+    def __init__(self, nbuf, group, B, F, V, field_offsets, max_key, dev, dloc, ws_per_buf):
+        self.nbuf, self.GROUP, self.B, self.F, self.V, self.max_key = nbuf, group, B, F, V, max_key
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.col_lo_rep = torch.tensor([int(o) for o in field_offsets] * group, dtype=torch.int64, device=dev)
+        self.bad_ids = torch.zeros(1, **i32)
+        arrays = dict(perm=torch.empty((nbuf, F, B), **i32),
+                      col_uid=torch.empty((nbuf, F, B), dtype=torch.int64, device=dev),
+                      col_seg=torch.empty((nbuf, F, B + 1), **i32), col_nu=torch.zeros((nbuf, F), **i32))
+        if dloc:
+            arrays["dloc"] = torch.empty((nbuf, F, B), **i32)
+        self.plans = [{k: a[b] for k, a in arrays.items()} for b in range(nbuf)]
+        self.a_plan = [(_p(pl["perm"]), _p(pl["col_uid"]), _p(pl["col_seg"]), _p(pl["col_nu"])) for pl in self.plans]
+        self._entry = "rec_colsort_plan_dest_i64" if dloc else "rec_colsort_plan_i64"
+        self.sort_ws = [torch.empty(lib.rec_colsort_workspace_bytes(B, F * group), dtype=torch.uint8, device=dev)
+                        for _ in range(nbuf if ws_per_buf else 1)]
+
+    def sort_group(self, cols_list, first_buf, st, arr=None):
+        """Plans of len(cols_list) <= GROUP batches into the consecutive buffers first_buf, first_buf + 1, ... as one
+        sort call over len*F columns on stream handle ``st`` (``arr``: their pointer array, where the caller keeps one)."""
+        k, F = len(cols_list), self.F
+        assert 1 <= k <= self.GROUP and first_buf + k <= self.nbuf
+        if arr is None:
+            arr = (C.c_void_p * (k * F))(*[c.data_ptr() for cols in cols_list for c in cols])
+        pl = self.plans[first_buf]
+        dloc = (_p(pl["dloc"]),) if "dloc" in pl else ()
+        ws = self.sort_ws[first_buf % len(self.sort_ws)]
+        check(getattr(lib, self._entry)(arr, k * F, self.B, self.V, _p(self.col_lo_rep), self.max_key,
+                                        *self.a_plan[first_buf], *dloc, _p(self.bad_ids), _p(ws), st), self._entry)
 
 
 class _BatchReader:
@@ -195,12 +291,7 @@ class DeepFMTrainStep(_GraphPolicy):
         self.vals = torch.empty((n, E), **f32)
         self.oob = torch.zeros(1, dtype=torch.int32, device=dev)
         # gradients
-        self.g = {
-            "MLP_layer1.kernel_0": torch.empty((D, u1), **f32), "MLP_layer1.bias_0": torch.empty(u1, **f32),
-            "MLP_layer1.kernel_1": torch.empty((u1, u2), **f32), "MLP_layer1.bias_1": torch.empty(u2, **f32),
-            "MLP_layer2.kernel_0": torch.empty((u2, 1), **f32), "MLP_layer2.bias_0": torch.empty(1, **f32),
-            "bias": torch.empty(1, **f32),
-        }
+        self.g = {name: torch.empty(shape, **f32) for name, shape in _deepfm_dense(F, u1, u2, E)}
         self.uniq_ids = torch.empty(n, dtype=torch.int64, device=dev)
         self.seg_start = torch.empty(n + 1, dtype=torch.int32, device=dev)
         self.perm = torch.empty(n, dtype=torch.int32, device=dev)
@@ -284,33 +375,6 @@ class DeepFMTrainStep(_GraphPolicy):
         P.add("rec_colsum_f32", _p(self.dz), B, 1, 1, _p(g["bias"]), _p(self.colsum_ws))
         return P
 
-    def _optimizer_program(self, t):
-        L = self.layer
-        P = _Program()
-        lr, b1, b2, eps = self.lr, ADAM_B1, ADAM_B2, ADAM_EPS
-        params = dict(L.named_parameters())
-        for name, grad in self.g.items():
-            m, v = self.state[name]
-            P.add("rec_adam_dense_f32", _p(params[name]), _p(m), _p(v), _p(grad), grad.numel(), t, lr, b1, b2, eps)
-        n = self.B * self.F
-        pe, pw = params["embed.embeddings"], params["w.embeddings"]
-        if self.optimizer == "keras_adam" and _tables_share_rows(pe, pw):
-            (me, ve), (mw, vw) = self.state["embed.embeddings"], self.state["w.embeddings"]
-            P.add("rec_adam_sparse_keras_pair_f32", _p(pe), pe.stride(0), _p(me), _p(ve), _p(mw), _p(vw), self.V, self.E,
-                  _p(self.uniq_ids), _p(self.g_embed_rows), _p(self.g_w_rows), _p(self.n_uniq), n, _p(self.side_e),
-                  _p(self.side_w), t, lr, b1, b2, eps)
-            return P
-        for name, rows, side, E in (("embed.embeddings", self.g_embed_rows, self.side_e, self.E),
-                                    ("w.embeddings", self.g_w_rows, self.side_w, 1)):
-            m, v = self.state[name]
-            if self.optimizer == "keras_adam":
-                P.add("rec_adam_sparse_keras_f32", _p(params[name]), params[name].stride(0), _p(m), _p(v), self.V, E,
-                      _p(self.uniq_ids), _p(rows), _p(self.n_uniq), n, _p(side), t, lr, b1, b2, eps)
-            else:
-                P.add("rec_adam_rows_f32", _p(params[name]), params[name].stride(0), _p(m), _p(v), self.V, E,
-                      _p(self.uniq_ids), _p(rows), _p(self.n_uniq), n, t, lr, b1, b2, eps)
-        return P
-
     # -- execution ----------------------------------------------------------------------------------
     def _enqueue(self, cols, label, stream, t):
         F = self.F
@@ -321,7 +385,8 @@ class DeepFMTrainStep(_GraphPolicy):
         calls[self._loss_call_index] = (name, fn, (_p(label),) + args[1:])
         self._static_prog.run(stream)
         if self.optimizer is not None:
-            self._optimizer_program(t).run(stream)
+            _deepfm_host_adam(self.layer, self.g, self.state, self.uniq_ids, self.g_embed_rows, self.g_w_rows,
+                              self.n_uniq, self.side_e, self.side_w, self.optimizer, t, self.lr, stream)
 
     def _graphable(self):
         return self.optimizer is None           # the optimizer's bias correction takes t as a host scalar: eager
@@ -335,12 +400,7 @@ class DeepFMTrainStep(_GraphPolicy):
                   lambda: self._enqueue(cols, y, C.c_void_p(torch.cuda.current_stream().cuda_stream), t), cols, y)
         return self.loss
 
-    def gradients(self):
-        """Dense grads by parameter name + the two tables' (uniq_ids, rows, n_uniq)."""
-        out = dict(self.g)
-        out["embed.embeddings"] = (self.uniq_ids, self.g_embed_rows, self.n_uniq)
-        out["w.embeddings"] = (self.uniq_ids, self.g_w_rows, self.n_uniq)
-        return out
+    gradients = _deepfm_gradients
 
 
 class _K0T:
@@ -541,8 +601,7 @@ class DeepFMFusedStep(_FusedStep):
             raise ValueError("optimizer 'keras_adam_lazy' applies its update inside the direct-mode post launch: direct=True")
         self.optimizer, self.lr, self.use_graph, self.t = optimizer, lr, use_graph, 0
         f32 = dict(dtype=torch.float32, device=dev)
-        n, D = B * F, F * 16
-        self.col_lo = torch.tensor([int(o) for o in field_offsets], dtype=torch.int64, device=dev)
+        n = B * F
         self.gz = torch.empty(B, **f32)
         self.vals = torch.empty((n, 16), **f32)
         # per-step results of a many() call (a caller that keeps metrics reads them after the call): loss_steps[i] and --
@@ -553,37 +612,21 @@ class DeepFMFusedStep(_FusedStep):
         self.prob = self.prob_steps[0] if want_prob else None
         self._row = 0                                                # row of the step being enqueued
         self.oob = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.bad_ids = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.g = {
-            "MLP_layer1.kernel_0": torch.empty((D, 32), **f32), "MLP_layer1.bias_0": torch.empty(32, **f32),
-            "MLP_layer1.kernel_1": torch.empty((32, 8), **f32), "MLP_layer1.bias_1": torch.empty(8, **f32),
-            "MLP_layer2.kernel_0": torch.empty((8, 1), **f32), "MLP_layer2.bias_0": torch.empty(1, **f32),
-            "bias": torch.empty(1, **f32),
-        }
+        self.g = {name: torch.empty(shape, **f32) for name, shape in _deepfm_dense(F)}
         self.ws = torch.empty(lib.rec_deepfm_fused_workspace_bytes(B, F), dtype=torch.uint8, device=dev)
         # NBUF plan buffers: the de-duplication plan depends on the ids only, so the plans of the NEXT call's batches are
         # built behind the steps of this call.  Every batch of a call has a buffer of its own (two halves of NBUF / 2 used
-        # alternately: one is read by this call's steps while the other is filled for the next call)
-        NB = self.NBUF
-        self._perm = torch.empty((NB, F, B), dtype=torch.int32, device=dev)
-        self._col_uid = torch.empty((NB, F, B), dtype=torch.int64, device=dev)
-        self._col_seg = torch.empty((NB, F, B + 1), dtype=torch.int32, device=dev)
-        self._col_nu = torch.zeros((NB, F), dtype=torch.int32, device=dev)
-        self._dloc = torch.empty((NB, F, B), dtype=torch.int32, device=dev)
-        self.plans = [dict(perm=self._perm[b], col_uid=self._col_uid[b], col_seg=self._col_seg[b],
-                           col_nu=self._col_nu[b], dloc=self._dloc[b]) for b in range(NB)]
-        # consecutive buffers are contiguous, so ONE sort call can build the plans of GROUP upcoming batches as
-        # GROUP*F columns (the sort kernels are latency-bound at < 1 wave per SIMD: two batches cost ~1.2x one)
-        # (256 column pointers per sort launch: one workgroup per column, and a CU holds ONE sort workgroup (98 KB of LDS) --
-        # 17 batches per launch, 442 workgroups, were measured slower than 9)
-        self.GROUP = max(1, 256 // F)
-        self.col_lo_rep = self.col_lo.repeat(self.GROUP).contiguous()
+        # alternately: one is read by this call's steps while the other is filled for the next call).  256 // F batches per
+        # sort launch: a CU holds ONE sort workgroup (98 KB of LDS) -- 17 batches per launch, 442 workgroups, were measured
+        # slower than 9
+        self._ring = _ColPlanRing(self.NBUF, max(1, 256 // F), B, F, self.V, field_offsets, self.max_key, dev, dloc=True,
+                                  ws_per_buf=False)
+        self.plans, self.GROUP, self.bad_ids = self._ring.plans, self._ring.GROUP, self._ring.bad_ids
         super().__init__(layer.feature_names)
         self.uniq_ids = torch.empty(n, dtype=torch.int64, device=dev)
         self.g_embed_rows = torch.empty((n, 16), **f32)
         self.g_w_rows = torch.empty((n, 1), **f32)
         self.n_uniq = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.sort_ws = torch.empty(lib.rec_colsort_workspace_bytes(B, F * self.GROUP), dtype=torch.uint8, device=dev)
         # (the plan sorts run on the caller's stream behind the steps of a call.  A second stream was tried at every
         # priority the device offers -- the range is (0, -1), the default 0 is the lowest, and a step enqueued on a
         # priority -1 stream ran 2.5x SLOWER from its graphs: a sort workgroup cannot share a CU with a fused-kernel
@@ -618,21 +661,33 @@ class DeepFMFusedStep(_FusedStep):
         # K0^T for the fused kernel, refreshed whenever the parameter changed -- by torch or by this step's own optimizer
         # launches (which re-transpose in the same stream)
         self._k0t = _K0T(layer, F)
+        # the two launches' argument lists, built once: every address in them is fixed for the life of the step.  The
+        # per-call entries (None here) are the column pointers, label and prob row of the main launch, the loss row of
+        # the post launch and the plan buffer of both
+        lazy = self._fused_lazy()
+        w_arr, g_arr = _deepfm_ptr_arrays(layer, self._k0t, self.g)
+        clock = ((_p(self._step_dev), _p(self._lr_tab), self._lr_tab.numel(), _p(self._lr_t_dev)) if lazy
+                 else (None, None, 0, None))
+        self._a_main = [_p(emb), emb.stride(0), self.V, None, F, B, w_arr, None, _p(self.gz), _p(self.vals), None,
+                        _p(self.oob), _p(self.ws), None, None, _p(self.g_embed_rows) if self.direct else None, *clock]
+        self._a_plan_main = [(_p(pl["dloc"]), a[3]) if self.direct else (None, None)
+                             for pl, a in zip(self.plans, self._ring.a_plan)]
+        self._adam = None
+        if lazy:
+            (me, ve), (mw, vw) = self.state["embed.embeddings"], self.state["w.embeddings"]
+            # (table, ld, V, m_e, v_e, ld_state, m_w, v_w, ld_wstate, last, step_dev, lr_table, n_table, b1, b2, eps)
+            self._a_catchup = (_p(emb), emb.stride(0), self.V, _p(me), _p(ve), me.stride(0), _p(mw), _p(vw), mw.stride(0),
+                               _p(self._last), *clock[:3], ADAM_B1, ADAM_B2, ADAM_EPS)
+            ptr = lambda t: t.data_ptr() if t is not None else None     # noqa: E731
+            self._adam = DeepFMLazyAdam(ptr(emb), emb.stride(0), self.V, ptr(me), ptr(ve), ptr(mw), ptr(vw), me.stride(0),
+                                        mw.stride(0), ptr(self._lr_t_dev), ADAM_B1, ADAM_B2, ADAM_EPS, ptr(self._last),
+                                        ptr(self._step_dev))
+        self._a_post = [F, B, _p(self.gz), _p(self.vals), g_arr, None, _p(self.ws), None, None, None, None,
+                        _p(self.uniq_ids), _p(self.g_embed_rows), _p(self.g_w_rows), _p(self.n_uniq), None,
+                        int(self.direct), self._adam]
 
     def _sort(self, cols, buf, stream):
-        self._sort_group([cols], buf, stream)
-
-    def _sort_group(self, cols_list, first_buf, stream):
-        """Plans of len(cols_list) <= GROUP batches into the consecutive buffers first_buf, first_buf+1, ... as one
-        rec_colsort_plan_i64 call over len*F columns."""
-        k, F = len(cols_list), self.F
-        assert 1 <= k <= self.GROUP and first_buf + k <= self.NBUF
-        arr = (C.c_void_p * (k * F))(*[c.data_ptr() for cols in cols_list for c in cols])
-        pl = self.plans[first_buf]
-        check(lib.rec_colsort_plan_dest_i64(arr, k * F, self.B, self.V, _p(self.col_lo_rep), self.max_key,
-                                            _p(pl["perm"]), _p(pl["col_uid"]), _p(pl["col_seg"]), _p(pl["col_nu"]),
-                                            _p(pl["dloc"]), _p(self.bad_ids), _p(self.sort_ws),
-                                            C.c_void_p(stream.cuda_stream)), "rec_colsort_plan_dest_i64")
+        self._ring.sort_group([cols], buf, C.c_void_p(stream.cuda_stream))
 
     def _ploss(self):
         return C.c_void_p(self.loss_steps.data_ptr() + 4 * self._row)
@@ -643,38 +698,18 @@ class DeepFMFusedStep(_FusedStep):
     def _launch_main(self, cols, label, st, buf):
         """The fused kernel.  Direct mode: the plan in buffer ``buf`` is complete, so the value row of every run's first
         member goes straight to its slot of g_embed_rows (with gz and the id)."""
-        L, F = self.layer, self.F
-        arr = (C.c_void_p * F)(*[c.data_ptr() for c in cols])
-        emb = L.embed.embeddings
-        pl = self.plans[buf]
-        if self._fused_lazy() and self._last is not None:
+        if self._adam is not None and self._last is not None:
             # Keras Adam, lazily: the rows this batch reads replay the sweeps they skipped (steps last+1 .. now)
-            (me, ve), (mw, vw) = self.state["embed.embeddings"], self.state["w.embeddings"]
-            check(lib.rec_adam_keras_catchup_f32(_p(pl["col_uid"]), _p(pl["col_nu"]), self.B, F, _p(emb), emb.stride(0),
-                                                 self.V, _p(me), _p(ve), me.stride(0), _p(mw), _p(vw), mw.stride(0),
-                                                 _p(self._last), _p(self._step_dev), _p(self._lr_tab),
-                                                 self._lr_tab.numel(), ADAM_B1, ADAM_B2, ADAM_EPS, st),
+            pl = self._ring.a_plan[buf]
+            check(lib.rec_adam_keras_catchup_f32(pl[1], pl[3], self.B, self.F, *self._a_catchup, st),
                   "rec_adam_keras_catchup_f32")
         self._k0t.refresh(st)
-        if not self.direct:
-            check(lib.rec_deepfm_fused3_main_f32(
-                _p(emb), emb.stride(0), self.V, arr, F, self.B, _p(L.bias), _p(L.MLP_layer1.kernel_0), _p(self._k0t.buf),
-                _p(L.MLP_layer1.bias_0), _p(L.MLP_layer1.kernel_1), _p(L.MLP_layer1.bias_1),
-                _p(L.MLP_layer2.kernel_0), _p(L.MLP_layer2.bias_0), _p(label), _p(self.gz), _p(self.vals),
-                self._pprob(), _p(self.oob), _p(self.ws), st), "rec_deepfm_fused3_main_f32")
-            return
-        head = (_p(emb), emb.stride(0), self.V, arr, F, self.B, _p(L.bias), _p(L.MLP_layer1.kernel_0), _p(self._k0t.buf),
-                _p(L.MLP_layer1.bias_0), _p(L.MLP_layer1.kernel_1), _p(L.MLP_layer1.bias_1), _p(L.MLP_layer2.kernel_0),
-                _p(L.MLP_layer2.bias_0), _p(label), _p(self.gz), _p(self.vals), self._pprob(), _p(self.oob), _p(self.ws),
-                _p(pl["dloc"]), _p(pl["col_nu"]), _p(self.g_embed_rows))
-        if self._fused_lazy():
-            # the optimizer's device-side step counter advances inside this launch (the kernel reads neither word):
-            # the catch-up above saw the old step, the post launch and the dense update below see the new one
-            check(lib.rec_deepfm_fused3_main_direct_adv_f32(*head, _p(self._step_dev), _p(self._lr_tab),
-                                                            self._lr_tab.numel(), _p(self._lr_t_dev), st),
-                  "rec_deepfm_fused3_main_direct_adv_f32")
-        else:
-            check(lib.rec_deepfm_fused3_main_direct_f32(*head, st), "rec_deepfm_fused3_main_direct_f32")
+        # (lazy optimizers: the optimizer's device-side step counter advances inside this launch -- the kernel reads
+        # neither word: the catch-up above saw the old step, the post launch and the dense update below see the new one)
+        a = self._a_main
+        a[3], a[7], a[10] = (C.c_void_p * self.F)(*[c.data_ptr() for c in cols]), _p(label), self._pprob()
+        a[13:15] = self._a_plan_main[buf]
+        check(lib.rec_deepfm_fused3_main_f32(*a, st), "rec_deepfm_fused3_main_f32")
 
     def _fused_lazy(self):
         """optimizer 'lazy_adam' / 'keras_adam_lazy' in direct mode: the touched-rows update of both tables rides in the
@@ -685,72 +720,21 @@ class DeepFMFusedStep(_FusedStep):
     def _launch_post(self, buf, st, t=0):
         """reduction of the workgroup partials side by side with the segment sums (direct mode: with what is left of
         them -- runs of more than one lookup and the padded tail) in ONE launch"""
-        g, pl = self.g, self.plans[buf]
-        if self._fused_lazy():
-            params = dict(self.layer.named_parameters())
-            pe = params["embed.embeddings"]
-            (me, ve), (mw, vw) = self.state["embed.embeddings"], self.state["w.embeddings"]
-            # (the step counter was advanced by the fused launch in front of this one: _launch_main)
-            check(lib.rec_deepfm_fused_post_direct_adam_dev_f32(
-                self.F, self.B, _p(self.gz), _p(self.vals), _p(g["MLP_layer1.kernel_0"]), _p(g["MLP_layer1.bias_0"]),
-                _p(g["MLP_layer1.kernel_1"]), _p(g["MLP_layer1.bias_1"]), _p(g["MLP_layer2.kernel_0"]),
-                _p(g["MLP_layer2.bias_0"]), _p(g["bias"]), self._ploss(), _p(self.ws), _p(pl["perm"]),
-                _p(pl["col_uid"]), _p(pl["col_seg"]), _p(pl["col_nu"]), _p(self.uniq_ids), _p(self.g_embed_rows),
-                _p(self.g_w_rows), _p(self.n_uniq), _p(pe), pe.stride(0), self.V, _p(me), _p(ve), _p(mw), _p(vw),
-                me.stride(0), mw.stride(0), _p(self._lr_t_dev), ADAM_B1, ADAM_B2, ADAM_EPS,
-                _p(self._last) if self._last is not None else None, _p(self._step_dev), st),
-                "rec_deepfm_fused_post_direct_adam_dev_f32")
-            return
-        if not self.direct:
-            check(lib.rec_deepfm_fused_post_f32(
-                self.F, self.B, _p(self.gz), _p(self.vals), _p(g["MLP_layer1.kernel_0"]), _p(g["MLP_layer1.bias_0"]),
-                _p(g["MLP_layer1.kernel_1"]), _p(g["MLP_layer1.bias_1"]), _p(g["MLP_layer2.kernel_0"]),
-                _p(g["MLP_layer2.bias_0"]), _p(g["bias"]), self._ploss(), _p(self.ws), _p(pl["perm"]),
-                _p(pl["col_uid"]), _p(pl["col_seg"]), _p(pl["col_nu"]), _p(self.uniq_ids), _p(self.g_embed_rows),
-                _p(self.g_w_rows), _p(self.n_uniq), 0, st), "rec_deepfm_fused_post_f32")
-            return
-        check(lib.rec_deepfm_fused_post_direct_f32(
-            self.F, self.B, _p(self.gz), _p(self.vals), _p(g["MLP_layer1.kernel_0"]), _p(g["MLP_layer1.bias_0"]),
-            _p(g["MLP_layer1.kernel_1"]), _p(g["MLP_layer1.bias_1"]), _p(g["MLP_layer2.kernel_0"]),
-            _p(g["MLP_layer2.bias_0"]), _p(g["bias"]), self._ploss(), _p(self.ws), _p(pl["perm"]), _p(pl["col_uid"]),
-            _p(pl["col_seg"]), _p(pl["col_nu"]), _p(self.uniq_ids), _p(self.g_embed_rows), _p(self.g_w_rows),
-            _p(self.n_uniq), st), "rec_deepfm_fused_post_direct_f32")
+        a = self._a_post
+        a[5] = self._ploss()
+        a[7:11] = self._ring.a_plan[buf]
+        check(lib.rec_deepfm_fused_post_f32(*a, st), "rec_deepfm_fused_post_f32")
 
     def _optimizer(self, t, st):
-        lr, b1, b2, eps = self.lr, ADAM_B1, ADAM_B2, ADAM_EPS
         if self._fused_lazy():
             # the tables were updated inside the post launch; the dense parameters follow in ONE launch, with the
             # step size the post launch used (device memory)
             self._adam_dense_dev(st)
             self._k0t.refresh(st, force=True)
             return
-        params = dict(self.layer.named_parameters())
-        for name, grad in self.g.items():
-            m, v = self.state[name]
-            check(lib.rec_adam_dense_f32(_p(params[name]), _p(m), _p(v), _p(grad), grad.numel(), t, lr, b1, b2, eps, st),
-                  "rec_adam_dense_f32")
-        self._k0t.refresh(st, force=True)
-        n = self.B * self.F
-        pe, pw = params["embed.embeddings"], params["w.embeddings"]
-        if self.optimizer == "keras_adam" and _tables_share_rows(pe, pw):
-            # one sweep over the fused [embed | w | pad] rows instead of one per table
-            (me, ve), (mw, vw) = self.state["embed.embeddings"], self.state["w.embeddings"]
-            check(lib.rec_adam_sparse_keras_pair_f32(_p(pe), pe.stride(0), _p(me), _p(ve), _p(mw), _p(vw), self.V, 16,
-                                                     _p(self.uniq_ids), _p(self.g_embed_rows), _p(self.g_w_rows),
-                                                     _p(self.n_uniq), n, _p(self.side_e), _p(self.side_w), t, lr, b1,
-                                                     b2, eps, st), "rec_adam_sparse_keras_pair_f32")
-            return
-        for name, rows, side, E in (("embed.embeddings", self.g_embed_rows, self.side_e, 16),
-                                    ("w.embeddings", self.g_w_rows, self.side_w, 1)):
-            m, v = self.state[name]
-            p = params[name]
-            if self.optimizer == "keras_adam":
-                check(lib.rec_adam_sparse_keras_f32(_p(p), p.stride(0), _p(m), _p(v), self.V, E, _p(self.uniq_ids),
-                                                    _p(rows), _p(self.n_uniq), n, _p(side), t, lr, b1, b2, eps, st),
-                      "rec_adam_sparse_keras_f32")
-            else:
-                check(lib.rec_adam_rows_f32(_p(p), p.stride(0), _p(m), _p(v), self.V, E, _p(self.uniq_ids), _p(rows),
-                                            _p(self.n_uniq), n, t, lr, b1, b2, eps, st), "rec_adam_rows_f32")
+        _deepfm_host_adam(self.layer, self.g, self.state, self.uniq_ids, self.g_embed_rows, self.g_w_rows, self.n_uniq,
+                          self.side_e, self.side_w, self.optimizer, t, self.lr, st,
+                          after_dense=lambda: self._k0t.refresh(st, force=True))
 
     def _graphable(self):
         # (the non-lazy optimizers take the step as a host scalar: enqueued eagerly)
@@ -760,10 +744,9 @@ class DeepFMFusedStep(_FusedStep):
         self._k0t.refresh()                                      # outside any capture: a replayed graph reads K0T
 
     def _enqueue(self, seq, bufs, inline, then_cols, then_bufs, t_base):
-        main = torch.cuda.current_stream()
-        st = C.c_void_p(main.cuda_stream)
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         for i in inline:                                         # not announced: sorted in line
-            self._sort(seq[i][0], bufs[i], main)
+            self._ring.sort_group([seq[i][0]], bufs[i], st)
         for i, (cols, y) in enumerate(seq):
             self._row = i
             self._launch_main(cols, y, st, bufs[i])
@@ -781,7 +764,7 @@ class DeepFMFusedStep(_FusedStep):
             nl = -(-m_ // self.GROUP)                            # as few launches as the column limit allows, evenly filled
             per = -(-m_ // nl)
             for j in range(0, m_, per):
-                self._sort_group(then_cols[j:j + per], then_bufs[j], main)
+                self._ring.sort_group(then_cols[j:j + per], then_bufs[j], st)
 
     def _after_call(self, n, bufs):
         self.loss = self.loss_steps[n - 1:n]                     # the last step's
@@ -793,13 +776,8 @@ class DeepFMFusedStep(_FusedStep):
         skipped) -- before the parameters are read from outside the step (evaluation, checkpoint)."""
         if not (self._fused_lazy() and self._last is not None):
             return
-        emb = self.layer.embed.embeddings
-        (me, ve), (mw, vw) = self.state["embed.embeddings"], self.state["w.embeddings"]
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        check(lib.rec_adam_keras_flush_f32(_p(emb), emb.stride(0), self.V, _p(me), _p(ve), me.stride(0), _p(mw), _p(vw),
-                                           mw.stride(0), _p(self._last), _p(self._step_dev), _p(self._lr_tab),
-                                           self._lr_tab.numel(), ADAM_B1, ADAM_B2, ADAM_EPS, st),
-              "rec_adam_keras_flush_f32")
+        check(lib.rec_adam_keras_flush_f32(*self._a_catchup, st), "rec_adam_keras_flush_f32")
 
     def release(self):
         """Give up the optimizer state kept in the layer's table padding (lazy optimizers) and the captured graphs, so
@@ -815,11 +793,7 @@ class DeepFMFusedStep(_FusedStep):
         if int(self.bad_ids.item()) != 0:
             raise ValueError("an id lies outside its field's [offset, offset+dim) range (DataGenerator contract)")
 
-    def gradients(self):
-        out = dict(self.g)
-        out["embed.embeddings"] = (self.uniq_ids, self.g_embed_rows, self.n_uniq)
-        out["w.embeddings"] = (self.uniq_ids, self.g_w_rows, self.n_uniq)
-        return out
+    gradients = _deepfm_gradients
 
 
 class DSSMFusedStep(_FusedStep):
@@ -1034,44 +1008,36 @@ class HipStepBackend:
         B, F, P, cap = step.B, step.F, step.P, step.cap
         dev = step.dev
         n = B * F
-        self.max_key = _deepfm_fused_limits(B, field_dims, field_offsets, sort_words=True)
         f32 = dict(dtype=torch.float32, device=dev)
         i32 = dict(dtype=torch.int32, device=dev)
         i64 = dict(dtype=torch.int64, device=dev)
         m = P * cap                                        # rows of every exchange buffer
-        self.bad_ids = torch.zeros(1, **i32)
         self.o_ws_bytes = lib.rec_dedup_workspace_bytes(m)
         # NPL plan buffers.  The eager step alternates between the first two (the plan of batch k+1 is built beside step
-        # k); many() gives every batch of its cycle a buffer of its own and sorts GROUP batches per launch -- the sort
-        # arrays of consecutive buffers are contiguous, so ONE rec_colsort_plan_i64 call over GROUP*F columns fills them
-        # (a sort workgroup cannot share a CU with a fused-kernel workgroup -- LDS --, so a 32-us sort per step was 32 us
-        # on the step's critical path; eight batches per launch cost ~36)
+        # k); many() gives every batch of its cycle a buffer of its own and sorts GROUP batches per launch (a sort
+        # workgroup cannot share a CU with a fused-kernel workgroup -- LDS --, so a 32-us sort per step was 32 us on the
+        # step's critical path; eight batches per launch cost ~36).  A sort workspace per buffer: the sorts run on a
+        # second stream
         self.NPL = NPL = 16
-        self.GROUP = max(1, min(8, 256 // F))
-        self.col_lo_rep = torch.tensor([int(o) for o in field_offsets] * self.GROUP, **i64)    # each sorted column's offset
-        self._perm = torch.empty((NPL, F, B), **i32)
-        self._col_uid = torch.empty((NPL, F, B), **i64)
-        self._col_seg = torch.empty((NPL, F, B + 1), **i32)
-        self._col_nu = torch.zeros((NPL, F), **i32)
-        self.plans = [dict(perm=self._perm[b], col_uid=self._col_uid[b], col_seg=self._col_seg[b], col_nu=self._col_nu[b],
-                           msg=torch.zeros((P, cap + 2), **i64), msg_theirs=torch.zeros((P, cap + 2), **i64),
-                           uidx=torch.empty((F, B), **i64), slot_map=torch.zeros(n, **i32), n_uniq=torch.zeros(1, **i64),
-                           # owner side: union of the P lists that arrive (depends on ids only: built with the plan)
-                           o_uniq=torch.empty(m, **i64), o_seg=torch.empty(m + 1, **i32), o_perm=torch.empty(m, **i32),
-                           o_nu=torch.zeros(1, **i64)) for b in range(NPL)]
-        for pl in self.plans:
-            pl["uidx_arr"] = (C.c_void_p * F)(*[pl["uidx"][f].data_ptr() for f in range(F)])
-        self.sort_ws = [torch.empty(lib.rec_colsort_workspace_bytes(B, F * self.GROUP), dtype=torch.uint8, device=dev)
-                        for _ in range(NPL)]
+        self._ring = _ColPlanRing(NPL, max(1, min(8, 256 // F)), B, F, step.V, field_offsets,
+                                  _deepfm_fused_limits(B, field_dims, field_offsets, sort_words=True), dev, dloc=False,
+                                  ws_per_buf=True)
+        self.plans, self.GROUP, self.bad_ids = self._ring.plans, self._ring.GROUP, self._ring.bad_ids
         self.o_ws = [torch.empty(self.o_ws_bytes, dtype=torch.uint8, device=dev) for _ in range(NPL)]
-        # every pointer below is fixed for the life of the step: the ctypes argument tuples are built once
+        # the exchange fields of a plan; every pointer below is fixed for the life of the step: the ctypes argument
+        # tuples are built once
         for buf, pl in enumerate(self.plans):
-            pl["a_map"] = (_p(pl["perm"]), _p(pl["col_uid"]), _p(pl["col_seg"]), _p(pl["col_nu"]), B, F,
-                           step.rows_per_shard, P, cap, _p(pl["msg"]), _p(pl["uidx"]), _p(pl["slot_map"]),
-                           _p(pl["n_uniq"]), _p(step.oob))
+            pl.update(msg=torch.zeros((P, cap + 2), **i64), msg_theirs=torch.zeros((P, cap + 2), **i64),
+                      uidx=torch.empty((F, B), **i64), slot_map=torch.zeros(n, **i32), n_uniq=torch.zeros(1, **i64),
+                      # owner side: union of the P lists that arrive (depends on ids only: built with the plan)
+                      o_uniq=torch.empty(m, **i64), o_seg=torch.empty(m + 1, **i32), o_perm=torch.empty(m, **i32),
+                      o_nu=torch.zeros(1, **i64))
+            pl["uidx_arr"] = (C.c_void_p * F)(*[pl["uidx"][f].data_ptr() for f in range(F)])
+            pl["a_plan"] = self._ring.a_plan[buf]
+            pl["a_map"] = (*pl["a_plan"], B, F, step.rows_per_shard, P, cap, _p(pl["msg"]), _p(pl["uidx"]),
+                           _p(pl["slot_map"]), _p(pl["n_uniq"]), _p(step.oob))
             pl["a_owner"] = (P, cap, step.rows_per_shard, _p(pl["o_uniq"]), _p(pl["o_seg"]), _p(pl["o_perm"]),
                              _p(pl["o_nu"]), _p(self.o_ws[buf]), self.o_ws_bytes)
-            pl["a_plan4"] = (_p(pl["perm"]), _p(pl["col_uid"]), _p(pl["col_seg"]), _p(pl["col_nu"]), _p(pl["slot_map"]))
         self.gz = torch.empty(B, **f32)
         self.vals = torch.empty((n, 16), **f32)
         # rows travel as [embed 16 | w | pad 3] = 80 bytes, not as the 128-byte lines they are stored in (C2 -37 %)
@@ -1087,6 +1053,9 @@ class HipStepBackend:
         self.side_st = C.c_void_p(self.side.cuda_stream)
         self.main, self.st = None, None
         self._arr_cache = {}
+        # the fused launches' pointer arrays: parameters and gradients are updated in place, their addresses stay
+        self._k0t = _K0T(step.layer, F)
+        self._w_arr, self._g_arr = _deepfm_ptr_arrays(step.layer, self._k0t, step.g)
 
     # -- streams: the plan of the next batch depends on ids only and is built beside the current step
     def begin(self):
@@ -1120,16 +1089,9 @@ class HipStepBackend:
     def plan_group(self, cols_list, first_buf, on_side=False):
         """The plans of len(cols_list) <= GROUP batches into the consecutive buffers first_buf, first_buf + 1, ...: ONE
         per-column sort over all their columns, then the exchange map of each."""
-        st_ = self.step
-        B, F, k = st_.B, st_.F, len(cols_list)
-        assert 1 <= k <= self.GROUP and first_buf + k <= self.NPL
         st = self.side_st if on_side else self.st
-        arr = self._col_arr([c for cols in cols_list for c in cols])
-        pl = self.plans[first_buf]
-        check(lib.rec_colsort_plan_i64(arr, k * F, B, st_.V, _p(self.col_lo_rep), self.max_key, _p(pl["perm"]),
-                                       _p(pl["col_uid"]), _p(pl["col_seg"]), _p(pl["col_nu"]), _p(self.bad_ids),
-                                       _p(self.sort_ws[first_buf]), st), "rec_colsort_plan_i64")
-        for j in range(k):
+        self._ring.sort_group(cols_list, first_buf, st, self._col_arr([c for cols in cols_list for c in cols]))
+        for j in range(len(cols_list)):
             check(lib.rec_colsort_shard_map_fixed_i64(*self.plans[first_buf + j]["a_map"], st),
                   "rec_colsort_shard_map_fixed_i64")
 
@@ -1152,31 +1114,20 @@ class HipStepBackend:
         the ids are the slots uidx.  Returns (vals [n,16], gz [B]); the dense gradients follow in local_grad (the
         reduction shares its launch with the segment sums)."""
         st_ = self.step
-        w = self.__dict__.get("_a_weights")
-        L = st_.layer
-        if w is None:                                        # parameters are updated in place: their addresses stay
-            self._k0t = _K0T(L, st_.F)
-            w = self._a_weights = (_p(L.bias), _p(L.MLP_layer1.kernel_0), _p(self._k0t.buf), _p(L.MLP_layer1.bias_0),
-                                   _p(L.MLP_layer1.kernel_1), _p(L.MLP_layer1.bias_1), _p(L.MLP_layer2.kernel_0),
-                                   _p(L.MLP_layer2.bias_0))
-            self._a_tail = (_p(self.gz), _p(self.vals), None, _p(st_.oob), _p(self.ws))
         self._k0t.refresh(self.st)
-        check(lib.rec_deepfm_fused3_main_f32(_p(rows_local), 20, rows_local.shape[0], pl["uidx_arr"], st_.F, st_.B, *w,
-                                             _p(y), *self._a_tail, self.st), "rec_deepfm_fused3_main_f32")
+        check(lib.rec_deepfm_fused3_main_f32(_p(rows_local), 20, rows_local.shape[0], pl["uidx_arr"], st_.F, st_.B,
+                                             self._w_arr, _p(y), _p(self.gz), _p(self.vals), None, _p(st_.oob),
+                                             _p(self.ws), None, None, None, None, None, 0, None, self.st),
+              "rec_deepfm_fused3_main_f32")
         return self.vals, self.gz
 
     def local_grad(self, pl, vals, gz):
         """Reduction of the workgroup partials (fills step.g / step.loss) and, in the same launch, this batch's
         gradient per unique id as rows [embed 16 | w | 0 0 0] in the id's slot of the [P*cap,20] send buffer."""
         st_ = self.step
-        a = self.__dict__.get("_a_post")
-        if a is None:
-            g = st_.g
-            a = self._a_post = (_p(g["MLP_layer1.kernel_0"]), _p(g["MLP_layer1.bias_0"]), _p(g["MLP_layer1.kernel_1"]),
-                                _p(g["MLP_layer1.bias_1"]), _p(g["MLP_layer2.kernel_0"]), _p(g["MLP_layer2.bias_0"]),
-                                _p(g["bias"]), _p(st_.loss), _p(self.ws))
-        check(lib.rec_deepfm_fused_post_slots_f32(st_.F, st_.B, _p(gz), _p(vals), *a, *pl["a_plan4"], _p(self.grows),
-                                                  self.st), "rec_deepfm_fused_post_slots_f32")
+        check(lib.rec_deepfm_fused_post_f32(st_.F, st_.B, _p(gz), _p(vals), self._g_arr, _p(st_.loss), _p(self.ws),
+                                            *pl["a_plan"], None, _p(self.grows), None, None, _p(pl["slot_map"]), 0, None,
+                                            self.st), "rec_deepfm_fused_post_f32")
         return self.grows
 
     def owner_reduce(self, pl, rows_theirs, scale):
@@ -1252,26 +1203,14 @@ class ShardedDeepFMStep(_GraphPolicy):
         self.table_shard[: hi - lo].copy_(fused[lo:hi])
         self.n = B * F
         self.oob = torch.zeros(1, dtype=torch.int32, device=dev)
-        D = F * 16
         # the dense gradients and the loss are views of ONE flat buffer: C4 is a single in-place all-reduce, no
         # concatenation before it and no copies after it (every view starts on a 16-byte boundary)
-        shapes = [("MLP_layer1.kernel_0", (D, 32)), ("MLP_layer1.bias_0", (32,)), ("MLP_layer1.kernel_1", (32, 8)),
-                  ("MLP_layer1.bias_1", (8,)), ("MLP_layer2.kernel_0", (8, 1)), ("MLP_layer2.bias_0", (1,)),
-                  ("bias", (1,)), ("loss", (1,))]
-        offs, total = [], 0
-        for _, shp in shapes:
-            offs.append(total)
-            k = 1
-            for d in shp:
-                k *= d
-            total += (k + 3) // 4 * 4
+        views, total = {}, 0
+        for name, shp in _deepfm_dense(F) + (("loss", (1,)),):
+            views[name] = (total, shp)
+            total += (math.prod(shp) + 3) // 4 * 4
         self.flat = torch.zeros(total, **f32)
-        views = {}
-        for (name, shp), off in zip(shapes, offs):
-            k = 1
-            for d in shp:
-                k *= d
-            views[name] = self.flat[off:off + k].view(shp)
+        views = {name: self.flat[off:off + math.prod(shp)].view(shp) for name, (off, shp) in views.items()}
         self.loss = views.pop("loss")
         self.g = views
         self.be = (backend or HipStepBackend)(self, field_dims, field_offsets)

@@ -275,12 +275,8 @@ int rec_emb_gather_lists_f32(const float* table, int64_t V, int E, int64_t ld, c
 int rec_dedup_plan_sorted_slabs_i64(const int64_t* msg, int n_lists, int64_t cap, int64_t V, int64_t* uniq_ids,
                                     int32_t* seg_start, int32_t* perm, int64_t* n_uniq, void* workspace,
                                     size_t workspace_bytes, void* stream);
-/* Post launch of the fused step for that layout: dense-gradient reduction + per-unique-id sums of (vals, gz) written as
- * packed rows [embed 16 | w | 0 0 0] to g_rows [n_shard * cap, 20] at slot_map[rank]; unused slots are left alone. */
-int rec_deepfm_fused_post_slots_f32(int F, int64_t B, const float* gz, const float* vals, float* dK0, float* db0,
-                                    float* dK1, float* db1, float* dK2, float* db2, float* dbias, float* loss,
-                                    void* workspace, const int32_t* perm, const int64_t* col_uid, const int32_t* col_seg,
-                                    const int32_t* col_nu, const int32_t* slot_map, float* g_rows, void* stream);
+/* (The post launch of the fused step writes the row gradients into that layout: rec_deepfm_fused_post_f32 with
+ * slot_map, below.) */
 /* out[perm[i], :] = in[i, :]   (inverse permutation of received rows) and its transpose */
 int rec_permute_rows_f32(const float* in, const int64_t* perm, int64_t n, int E, int scatter, float* out,
                          void* stream);
@@ -316,71 +312,55 @@ int rec_colsort_plan_dest_i64(const int64_t* const* cols_host, int F, int64_t B,
                               int64_t max_key, int32_t* perm, int64_t* col_uid, int32_t* col_seg, int32_t* col_nu,
                               int32_t* dloc, int* bad_flag, void* workspace, void* stream);
 
-/* Main kernel (csrc/deepfm_fused3.hip): the two 16-example halves of a workgroup run one phase apart (the backward of
- * one half on the matrix cores while the rows of the other are still landing).  K0T [32, F*16] = the transpose of
- * K0 [F*16, 32], kept by the caller with rec_deepfm_k0t_f32 (read only when F > 26: otherwise K0 is staged in LDS).
- * rec_deepfm_fused3_main_f32 (plan-after form) takes any row stride ld >= 20 that is a multiple of 4 (rows
- * [embed 16 | w | ...]: 32 for a table, 20 for the rows a sharded step received); the plan may be built after it. */
+/* Main launch (csrc/deepfm_fused3.hip): the two 16-example halves of a workgroup run one phase apart (the backward of
+ * one half on the matrix cores while the rows of the other are still landing).  weights: HOST array of 8 device
+ * pointers bias, K0 [F*16,32], K0T, b0, K1 [32,8], b1, K2 [8,1], b2; K0T [32, F*16] = the transpose of K0, kept by the
+ * caller with rec_deepfm_k0t_f32 (read only when F > 26: otherwise K0 is staged in LDS).  Two optional groups:
+ *   dloc, col_nu, g_embed_rows   all NULL: the plan-after form -- any row stride ld >= 20 that is a multiple of 4 (rows
+ *       [embed 16 | w | ...]: 32 for a table, 20 for the rows a sharded step received); the plan may be built after
+ *       the launch.  All given: direct mode (ld = 32) -- the plan of the batch (rec_colsort_plan_dest_i64) is complete
+ *       before the launch, and the IndexedSlices value row of a lookup that heads its run goes straight to
+ *       g_embed_rows[slot] (only the other members of a run are written to vals).  Anything else: REC_E_ARG.
+ *   step_dev, lr_table, n_table, lr_t_dev   step_dev NULL: off.  Otherwise the optimizer's device-side step counter is
+ *       advanced by the kernel's first thread: *step_dev += 1, *lr_t_dev = lr_table[min(*step_dev, n_table) - 1]
+ *       (lr_table: rec_adam_lr_t_f32 of steps 1..n_table).  The kernel reads neither word; the launches behind it on the
+ *       stream see the new step, so a train step holds no per-step host scalar and can be captured in a hipGraph. */
 int rec_deepfm_k0t_f32(const float* K0, int F, float* K0T, void* stream);
 int rec_deepfm_fused3_main_f32(const float* table, int64_t ld, int64_t V, const int64_t* const* cols_host, int F,
-                               int64_t B, const float* bias, const float* K0, const float* K0T, const float* b0,
-                               const float* K1, const float* b1, const float* K2, const float* b2, const float* label,
-                               float* gz, float* vals, float* prob, int* oob_flag, void* workspace, void* stream);
-/* Direct mode (ld = 32): the plan of the batch (rec_colsort_plan_dest_i64) is complete before the launch, and the
- * IndexedSlices value row of a lookup that heads its run goes straight to g_embed_rows[slot] (only the other members of
- * a run are written to vals). */
-int rec_deepfm_fused3_main_direct_f32(const float* table, int64_t ld, int64_t V, const int64_t* const* cols_host, int F,
-                                      int64_t B, const float* bias, const float* K0, const float* K0T, const float* b0,
-                                      const float* K1, const float* b1, const float* K2, const float* b2,
-                                      const float* label, float* gz, float* vals, float* prob, int* oob_flag,
-                                      void* workspace, const int32_t* dloc, const int32_t* col_nu, float* g_embed_rows,
-                                      void* stream);
-/* ... and the optimizer's device-side step counter advanced by the kernel's first thread: *step_dev += 1,
- * *lr_t_dev = lr_table[min(*step_dev, n_table) - 1] (lr_table: rec_adam_lr_t_f32 of steps 1..n_table).  The kernel
- * reads neither word; the launches behind it on the stream see the new step, so a train step holds no per-step host
- * scalar and can be captured in a hipGraph. */
-int rec_deepfm_fused3_main_direct_adv_f32(const float* table, int64_t ld, int64_t V, const int64_t* const* cols_host, int F,
-                                          int64_t B, const float* bias, const float* K0, const float* K0T, const float* b0,
-                                          const float* K1, const float* b1, const float* K2, const float* b2,
-                                          const float* label, float* gz, float* vals, float* prob, int* oob_flag,
-                                          void* workspace, const int32_t* dloc, const int32_t* col_nu, float* g_embed_rows,
-                                          int64_t* step_dev, const float* lr_table, int64_t n_table, float* lr_t_dev,
-                                          void* stream);
+                               int64_t B, const float* const* weights, const float* label, float* gz, float* vals,
+                               float* prob, int* oob_flag, void* workspace, const int32_t* dloc, const int32_t* col_nu,
+                               float* g_embed_rows, int64_t* step_dev, const float* lr_table, int64_t n_table,
+                               float* lr_t_dev, void* stream);
 
-/* Post launch (csrc/deepfm_fused.hip), after the plan-after main kernel: reduction of the workgroup partials into the
- * dense gradients and loss, and the segment sums of (vals, gz) over the plan, compacted to the global ascending list:
- * uniq_ids [B*F], g_embed_rows [B*F,16], g_w_rows [B*F], n_uniq; the tail is padded like rec_dedup_plan_i64's.
- * packed: g_embed_rows [B*F,20] holds rows [embed 16 | w | 0 0 0], g_w_rows unused.  (The sharded step's form with
- * fixed-capacity slots, rec_deepfm_fused_post_slots_f32, is declared with the exchange above.) */
-int rec_deepfm_fused_post_f32(int F, int64_t B, const float* gz, const float* vals, float* dK0, float* db0, float* dK1,
-                              float* db1, float* dK2, float* db2, float* dbias, float* loss, void* workspace,
-                              const int32_t* perm, const int64_t* col_uid, const int32_t* col_seg,
+/* The lazy (touched-rows) Adam of the post launch (optimizer in the backward; arithmetic of
+ * rec_adam_rows_f32), applied to each row of both tables the moment its gradient is final.  table: fused rows [V,32] =
+ * [embed 16 | w | pad] (ld = 32).  The step size is read from device memory (lr_t_dev, advanced by the main launch on
+ * the same stream).  Row strides of the optimizer state: ld_state (floats) for m_e / v_e, ld_wstate for m_w / v_w -- 16
+ * and 1 for dense arrays, 32 and 32 for state packed beside the rows ([m 16 | v 16] as one 128-byte row, m_w / v_w in
+ * the padding of the fused table row: a touched row then costs two line requests instead of five or six).
+ * last == NULL: plain touched-rows Adam, NOT Keras' dense-sweep semantics of 2.FM/ModelManager.py:104,178-179 (opt-in);
+ * last != NULL (then step_dev too): the exact lazy evaluation of Keras' Adam below. */
+typedef struct rec_deepfm_lazy_adam {
+  float* table; int64_t ld, V;
+  float *m_e, *v_e, *m_w, *v_w; int64_t ld_state, ld_wstate;
+  const float* lr_t_dev; float b1, b2, eps;
+  int32_t* last; const int64_t* step_dev;
+} rec_deepfm_lazy_adam;
+/* Post launch (csrc/deepfm_fused.hip): reduction of the workgroup partials into the dense gradients (grads: HOST array
+ * of 7 device pointers dK0, db0, dK1, db1, dK2, db2, dbias) and *loss, side by side with the segment sums of (vals, gz)
+ * over the plan, compacted to the global ascending list: uniq_ids [B*F], g_embed_rows [B*F,16], g_w_rows [B*F], n_uniq;
+ * the tail is padded like rec_dedup_plan_i64's.  Replaces the 2.FM/ModelManager.py:176-179 IndexedSlices hand-over.
+ *   slot_map != NULL (the sharded step; uniq_ids, g_w_rows, n_uniq NULL): per-unique-id sums written as packed rows
+ *       [embed 16 | w | 0 0 0] to g_embed_rows [n_shard * cap, 20] at slot_map[rank]; unused slots are left alone.
+ *   direct != 0, after a direct-mode main launch: adds the remaining members of runs longer than one in position order
+ *       (sums bit-identical to the plain form), writes uniq_ids / g_w_rows / n_uniq and the zero-padded tail.
+ *   adam != NULL (direct only): the lazy Adam above on every finished row.
+ * slot_map with direct, adam without direct: REC_E_UNSUPPORTED. */
+int rec_deepfm_fused_post_f32(int F, int64_t B, const float* gz, const float* vals, float* const* grads, float* loss,
+                              void* workspace, const int32_t* perm, const int64_t* col_uid, const int32_t* col_seg,
                               const int32_t* col_nu, int64_t* uniq_ids, float* g_embed_rows, float* g_w_rows,
-                              int64_t* n_uniq, int packed, void* stream);
-/* Direct mode, after rec_deepfm_fused3_main_direct{,_adv}_f32: adds the remaining members of runs longer than one in
- * position order (sums bit-identical to the plain path), writes uniq_ids / g_w_rows / n_uniq and the zero-padded tail,
- * and reduces the dense partials.  Replaces the 2.FM/ModelManager.py:176-179 IndexedSlices hand-over. */
-int rec_deepfm_fused_post_direct_f32(int F, int64_t B, const float* gz, const float* vals, float* dK0, float* db0,
-                                     float* dK1, float* db1, float* dK2, float* db2, float* dbias, float* loss,
-                                     void* workspace, const int32_t* perm, const int64_t* col_uid, const int32_t* col_seg,
-                                     const int32_t* col_nu, int64_t* uniq_ids, float* g_embed_rows, float* g_w_rows,
-                                     int64_t* n_uniq, void* stream);
-/* ... + the lazy (touched-rows) Adam update of both tables applied to each row the moment its gradient is final
- * (optimizer in the backward; arithmetic of rec_adam_rows_f32).  table: fused rows [V,32] =
- * [embed 16 | w | pad] (ld = 32).  The step size is read from device memory (lr_t_dev, advanced by
- * rec_deepfm_fused3_main_direct_adv_f32 on the same stream).  Explicit row strides of the optimizer state: ld_state
- * (floats) for m_e / v_e, ld_wstate for m_w / v_w -- 16 and 1 for dense arrays, 32 and 32 for state packed beside the
- * rows ([m 16 | v 16] as one 128-byte row, m_w / v_w in the padding of the fused table row: a touched row then costs two
- * line requests instead of five or six).  last == NULL: plain touched-rows Adam, NOT Keras' dense-sweep semantics of
- * 2.FM/ModelManager.py:104,178-179 (opt-in); last != NULL: the exact lazy evaluation of Keras' Adam below. */
-int rec_deepfm_fused_post_direct_adam_dev_f32(int F, int64_t B, const float* gz, const float* vals, float* dK0, float* db0,
-                                              float* dK1, float* db1, float* dK2, float* db2, float* dbias, float* loss,
-                                              void* workspace, const int32_t* perm, const int64_t* col_uid,
-                                              const int32_t* col_seg, const int32_t* col_nu, int64_t* uniq_ids,
-                                              float* g_embed_rows, float* g_w_rows, int64_t* n_uniq, float* table,
-                                              int64_t ld, int64_t V, float* m_e, float* v_e, float* m_w, float* v_w,
-                                              int64_t ld_state, int64_t ld_wstate, const float* lr_t_dev, float b1,
-                                              float b2, float eps, int32_t* last, const int64_t* step_dev, void* stream);
+                              int64_t* n_uniq, const int32_t* slot_map, int direct, const rec_deepfm_lazy_adam* adam,
+                              void* stream);
 /* Keras Adam evaluated lazily and exactly (2.FM/ModelManager.py:178-179: the sparse apply of IndexedSlices gradients is
  * a dense sweep over every row).  An untouched row's update at step j depends only on the row and lr_j, so rows may skip
  * the sweeps and replay them later with the sweep's own arithmetic: last [V] int32 = the step each row holds (zero at
@@ -406,7 +386,7 @@ int rec_adam_keras_flush_f32(float* table, int64_t ld, int64_t V, float* m_e, fl
  *         gradient rows u_vals [B*F_u,E] / i_vals [B*F_i,E] and per-workgroup dense partials + loss terms into the
  *         workspace; user_emb / item_emb [B,8] and score [B] when non-null.  weights: host array of 12 device pointers
  *         (user tower K0 [F_u*E,64], b0, K1 [64,32], b1, Kf [32,8], bf, then the item tower's).  step_dev != NULL: the
- *         optimizer's device-side step counter is advanced as in rec_deepfm_fused3_main_direct_adv_f32.
+ *         optimizer's device-side step counter is advanced as in rec_deepfm_fused3_main_f32.
  *   post: fixed-order reduction of the partials into grads (host array of 12 device pointers, order of `weights`) and
  *         *loss, side by side with the segment sums of u_vals / i_vals over a rec_dedup_plan_i64 of each tower's flat
  *         ids (perm, seg_start, uniq_ids, n_uniq) -> u_rows [B*F_u,E] / i_rows [B*F_i,E] (zero on the padded tail).

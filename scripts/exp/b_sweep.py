@@ -30,6 +30,9 @@ offs = np.concatenate([[0], np.cumsum(dims[:-1])])
 K0T = torch.empty((32, F * 16), dtype=torch.float32, device="cuda")    # K0^T: the kernel reads it only when F > 26
 check(lib.rec_deepfm_k0t_f32(vp(L.MLP_layer1.kernel_0), F, vp(K0T), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
       "k0t")
+# the weights of the main launch: bias, K0, K0T, b0, K1, b1, K2, b2
+W = (C.c_void_p * 8)(*[t.data_ptr() for t in (L.bias, L.MLP_layer1.kernel_0, K0T, L.MLP_layer1.bias_0, L.MLP_layer1.kernel_1,
+                                               L.MLP_layer1.bias_1, L.MLP_layer2.kernel_0, L.MLP_layer2.bias_0)])
 
 
 def timed(launch, reps):
@@ -74,11 +77,9 @@ for B in (8192, 16384, 32768, 65536, 131072):
     def l_fused(n):
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         for i in range(n):
-            check(lib.rec_deepfm_fused3_main_f32(vp(emb), emb.stride(0), V, arrs[i % nset], F, B, vp(L.bias),
-                                                 vp(L.MLP_layer1.kernel_0), vp(K0T), vp(L.MLP_layer1.bias_0),
-                                                 vp(L.MLP_layer1.kernel_1), vp(L.MLP_layer1.bias_1),
-                                                 vp(L.MLP_layer2.kernel_0), vp(L.MLP_layer2.bias_0), vp(y), vp(gz),
-                                                 vp(vals), None, vp(oob), vp(ws), st), "fused")
+            check(lib.rec_deepfm_fused3_main_f32(vp(emb), emb.stride(0), V, arrs[i % nset], F, B, W, vp(y), vp(gz),
+                                                 vp(vals), None, vp(oob), vp(ws), None, None, None, None, None, 0, None,
+                                                 st), "fused")
 
     reps = 2 * nset
     ug, uf = timed(l_gather, reps), timed(l_fused, reps)

@@ -14,6 +14,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 from explicit_tf2_recommendation_amd import layers, data, engine  # noqa: E402
+from explicit_tf2_recommendation_amd._lib import lib  # noqa: E402
 
 V, F, E, B = 10_000_000, 26, 16, int(os.environ.get("B", "8192"))
 names = ["C%d" % (i + 1) for i in range(F)]
@@ -38,7 +39,7 @@ dbg = C.CDLL(OUT)
 fs = engine.DeepFMFusedStep(L, B, gen.dims, gen.offsets, optimizer=None, use_graph=False)
 fs._k0t.refresh()
 fn = dbg.rec_deepfm_fused3_main_f32
-fn.restype = C.c_int
+fn.restype, fn.argtypes = C.c_int, lib.rec_deepfm_fused3_main_f32.argtypes
 nwg = (B + 31) // 32
 st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
 emb = L.embed.embeddings
@@ -49,10 +50,9 @@ def dbg_launch(n):
     for it in range(n):
         bt = batches[it % NB]
         arr = (C.c_void_p * F)(*[bt[k].data_ptr() for k in names])
-        rc = fn(vp(emb), C.c_int64(emb.stride(0)), C.c_int64(V), arr, C.c_int(F), C.c_int64(B), vp(L.bias),
-                vp(L.MLP_layer1.kernel_0), vp(fs._k0t.buf), vp(L.MLP_layer1.bias_0), vp(L.MLP_layer1.kernel_1),
-                vp(L.MLP_layer1.bias_1), vp(L.MLP_layer2.kernel_0), vp(L.MLP_layer2.bias_0), vp(bt["label"]), vp(fs.gz),
-                vp(fs.vals), None, vp(fs.oob), vp(fs.ws), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        rc = fn(vp(emb), emb.stride(0), V, arr, F, B, fs._a_main[6], vp(bt["label"]), vp(fs.gz), vp(fs.vals), None,
+                vp(fs.oob), vp(fs.ws), None, None, None, None, None, 0, None,       # plan-after form, no clock
+                C.c_void_p(torch.cuda.current_stream().cuda_stream))
         assert rc == 0, rc
 
 

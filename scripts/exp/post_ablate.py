@@ -30,7 +30,7 @@ for i in range(NB):
     fs._launch_main(colss[i], batches[i]["label"], st(), i)
 torch.cuda.synchronize()
 CS = os.path.join(ROOT, "explicit-tf2-recommendation_amd", "csrc")
-NAME = "rec_deepfm_fused_post_direct_f32"
+NAME = "rec_deepfm_fused_post_f32"
 VARIANTS = ([], ["-DABL_NOSHORT"], ["-DABL_NOLONG"], ["-DABL_NOHUGE"], ["-DABL_NOSHORT", "-DABL_NOLONG", "-DABL_NOHUGE"])
 if os.environ.get("VARIANTS"):
     VARIANTS = [v.split() for v in os.environ["VARIANTS"].split(";")]

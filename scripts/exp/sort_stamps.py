@@ -51,8 +51,8 @@ for it in range(10):
     arr = (C.c_void_p * (k * F))(*[c.data_ptr() for cols in cl for c in cols])
     pl = fs.plans[0]
     for rep in range(3):     # back to back: the last one is measured warm
-        rc = fn(arr, C.c_int(k * F), C.c_int64(B), C.c_int64(V), vp(fs.col_lo_rep), C.c_int64(fs.max_key), vp(pl["perm"]),
-                vp(pl["col_uid"]), vp(pl["col_seg"]), vp(pl["col_nu"]), vp(pl["dloc"]), vp(fs.bad_ids), vp(fs.sort_ws),
+        rc = fn(arr, C.c_int(k * F), C.c_int64(B), C.c_int64(V), vp(fs._ring.col_lo_rep), C.c_int64(fs.max_key), vp(pl["perm"]),
+                vp(pl["col_uid"]), vp(pl["col_seg"]), vp(pl["col_nu"]), vp(pl["dloc"]), vp(fs.bad_ids), vp(fs._ring.sort_ws[0]),
                 C.c_void_p(torch.cuda.current_stream().cuda_stream))
         assert rc == 0
     torch.cuda.synchronize()

@@ -17,9 +17,9 @@ for V in (26 * 100, 26 * 16000, 10_000_000):
     cols = [fs._cols(b) for b in bs]
     for k in (1, 2, 4):
         def launch(n):
-            st = torch.cuda.current_stream()
+            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
             for i in range(n):
-                fs._sort_group(cols[(i * k) % 8:(i * k) % 8 + k] if (i * k) % 8 + k <= 8 else cols[:k], 0, st)
+                fs._ring.sort_group(cols[(i * k) % 8:(i * k) % 8 + k] if (i * k) % 8 + k <= 8 else cols[:k], 0, st)
         launch(4); torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, capture_error_mode=engine.CAPTURE_MODE):

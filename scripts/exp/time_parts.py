@@ -72,13 +72,13 @@ def l_sort1(n):
 def l_sort4(n):
     for i in range(n):
         j = (4 * i) % NB
-        fs._sort_group([cols[j], cols[j + 1], cols[j + 2], cols[j + 3]], j, torch.cuda.current_stream())
+        fs._ring.sort_group([cols[j], cols[j + 1], cols[j + 2], cols[j + 3]], j, st())
 
 
 def l_sort2(n):
     for i in range(n):
         j = (2 * i) % NB
-        fs._sort_group([cols[j], cols[j + 1]], j, torch.cuda.current_stream())
+        fs._ring.sort_group([cols[j], cols[j + 1]], j, st())
 
 
 print("id distribution: %s, %s mode" % (dist, "direct" if direct else "classic"))

@@ -44,6 +44,42 @@ def test_argument_errors_do_not_need_a_gpu():
         check(-2, "x")
 
 
+def test_fused_deepfm_entry_points_validate_their_option_groups():
+    """The merged entry points of the fused DeepFM step (one per launch): which optional groups go together is decided on
+    the host, before anything is launched.  Every required pointer is a non-NULL dummy: validation reads only values."""
+    from explicit_tf2_recommendation_amd._lib import lib, DeepFMLazyAdam
+    d = ctypes.c_void_p(4096)                                           # 16-byte aligned, never dereferenced
+    F, B, V = 3, 64, 1000
+    cols = (ctypes.c_void_p * F)(*[4096] * F)
+    w = (ctypes.c_void_p * 8)(*[4096] * 8)
+
+    def main(ld=32, dloc=None, col_nu=None, g_rows=None, clock=(None, None, 0, None)):
+        return lib.rec_deepfm_fused3_main_f32(d, ld, V, cols, F, B, w, d, d, d, None, d, d, dloc, col_nu, g_rows, *clock,
+                                              None)
+    assert main(dloc=d, col_nu=None, g_rows=d) == -1                    # a partial direct group
+    assert main(dloc=None, col_nu=d) == -1 and main(dloc=None, g_rows=d) == -1
+    assert main(clock=(d, None, 4, d)) == -1                            # a partial clock group
+    assert main(clock=(d, d, 0, d)) == -1 and main(clock=(d, d, 4, None)) == -1
+    assert main(ld=18) == -2 and main(ld=22) == -2                      # plain: ld >= 20, a multiple of 4
+    assert main(ld=20, dloc=d, col_nu=d, g_rows=d) == -2                # direct: ld = 32
+    assert main(ld=20, dloc=d, col_nu=None, g_rows=d) == -2             # (the ld rule is judged before the pointers)
+
+    g = (ctypes.c_void_p * 7)(*[4096] * 7)
+    adam = DeepFMLazyAdam(4096, 32, V, 4096, 4096, 4096, 4096, 16, 1, 4096, 0.9, 0.999, 1e-7, None, None)
+
+    def post(uniq=d, g_w=d, n_uniq=d, slot_map=None, direct=0, adam=None):
+        return lib.rec_deepfm_fused_post_f32(F, B, d, d, g, d, d, d, d, d, d, uniq, d, g_w, n_uniq, slot_map, direct,
+                                             adam, None)
+    assert post(uniq=None, g_w=None, n_uniq=None, slot_map=d, direct=1) == -2
+    assert post(direct=0, adam=adam) == -2
+    assert post(uniq=None) == -1 and post(n_uniq=None) == -1 and post(g_w=None) == -1
+    assert post(slot_map=d) == -1                                       # packed rows: uniq_ids / g_w_rows / n_uniq stay NULL
+    adam.ld = 20
+    assert post(direct=1, adam=adam) == -2                              # the table must be the fused [V,32] rows
+    adam.ld, adam.m_e = 32, None
+    assert post(direct=1, adam=adam) == -1
+
+
 def test_layer_signatures_match_the_reference():
     """Constructor keywords of 2.FM/CustomLayers.py:117,167,220-222,255-256; 3.DCN/CustomLayers.py:171,220-224,273;
     5.DIN/CustomLayers.py:164,200-205 (reference spelling kept, e.g. `is_dropput`)."""

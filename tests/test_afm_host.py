@@ -129,8 +129,8 @@ def _ABI():
     return lib
 
 
-def test_rec_version_is_104():
-    assert _ABI().rec_version() == 104
+def test_rec_version_is_105():
+    assert _ABI().rec_version() == 105
 
 
 def test_afm_abi_rejects_bad_arguments_without_a_gpu():
