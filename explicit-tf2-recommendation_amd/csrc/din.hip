@@ -44,7 +44,8 @@ __device__ __forceinline__ float feat_act(int kind, float x, float alpha, float 
       da = (1.f - p) * x;
       break;
     }
-    case DACT_PRELU: y = x > 0.f ? x : alpha * x; dx = x > 0.f ? 1.f : alpha; da = x > 0.f ? 0.f : x; break;
+    // Keras PReLU = relu(x) - alpha * relu(-x): at x == 0 both ReLUs have gradient 0, so dy/dx(0) = 0, not alpha
+    case DACT_PRELU: y = x > 0.f ? x : alpha * x; dx = x > 0.f ? 1.f : (x < 0.f ? alpha : 0.f); da = x > 0.f ? 0.f : x; break;
     default: break;
   }
   if (dydx) *dydx = dx;
@@ -74,7 +75,8 @@ __device__ __forceinline__ float feat_act_hw(int kind, float x, float alpha, flo
       }
       break;
     }
-    case DACT_PRELU: y = x > 0.f ? x : alpha * x; dx = x > 0.f ? 1.f : alpha; da = x > 0.f ? 0.f : x; break;
+    // Keras PReLU = relu(x) - alpha * relu(-x): at x == 0 both ReLUs have gradient 0, so dy/dx(0) = 0, not alpha
+    case DACT_PRELU: y = x > 0.f ? x : alpha * x; dx = x > 0.f ? 1.f : (x < 0.f ? alpha : 0.f); da = x > 0.f ? 0.f : x; break;
     default: break;
   }
   if (GRAD) { dydx = dx; dyda = da; }

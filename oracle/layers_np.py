@@ -193,15 +193,21 @@ def two_tower_score(u, i, dt=np.float32):
 
 
 def two_tower_score_backward(u, i, gout, dt=np.float32):
-    """d out/d u, d out/d i for out=(1-cos)/2: dc/du = (i_hat - c*u_hat)/|u| (|u|^2 > 1e-12)."""
+    """d out/d u, d out/d i for out=(1-cos)/2: dc/du = (i_hat - c*u_hat)/|u| where |u|^2 > 1e-12.  Where the clamp of
+    l2_normalize is active (|u|^2 < 1e-12) u_hat = u * 1e6 is LINEAR in u: dc/du = i_hat * 1e6, no projection term --
+    for u = 0 the two forms coincide (c = 0), for 0 < |u|^2 < 1e-12 they do not."""
     u = u.astype(dt)
     i = i.astype(dt)
-    nu = np.sqrt(np.maximum(np.square(u).sum(1, keepdims=True), dt(1e-12)))
-    ni = np.sqrt(np.maximum(np.square(i).sum(1, keepdims=True), dt(1e-12)))
+    su = np.square(u).sum(1, keepdims=True)
+    si = np.square(i).sum(1, keepdims=True)
+    nu = np.sqrt(np.maximum(su, dt(1e-12)))
+    ni = np.sqrt(np.maximum(si, dt(1e-12)))
     uh, ih = u / nu, i / ni
     c = (uh * ih).sum(1, keepdims=True)
     gc = -dt(0.5) * gout.astype(dt).reshape(-1, 1)
-    return gc * (ih - c * uh) / nu, gc * (uh - c * ih) / ni
+    pu = np.where(su < dt(1e-12), dt(0), c)         # clamp active: the norm does not depend on the vector
+    pi = np.where(si < dt(1e-12), dt(0), c)
+    return gc * (ih - pu * uh) / nu, gc * (uh - pi * ih) / ni
 
 
 # --------------------------------------------------------------------------------------------
