@@ -121,6 +121,9 @@ SIGNATURES = {
     "rec_ccpm_workspace_bytes": (sz, [i64, i32, i32, i32, p, p, p]),
     "rec_emb_ccpm_fwd_f32": (i32, [p, i64, i32, i64, p, i64, i32, i32, p, p, p, p, p, p, p, p]),
     "rec_emb_ccpm_bwd_f32": (i32, [p, i64, i32, i64, p, i64, i32, i32, p, p, p, p, p, p, p, p, p, sz, p]),
+    "rec_fgcnn_workspace_bytes": (sz, [i64, i32, i32, i32, p, p, p]),
+    "rec_emb_fgcnn_fwd_f32": (i32, [p, i64, i32, i64, p, i64, i32, i32, p, p, p, p, p, p, p, p]),
+    "rec_emb_fgcnn_bwd_f32": (i32, [i32, i64, i32, i32, p, p, p, p, p, p, p, p, p, p, sz, p]),
 }
 
 

@@ -400,10 +400,13 @@ __global__ __launch_bounds__(AFM_NT) void emb_afm_bwd_kernel(AfmShape s, int EPW
   }
   __syncthreads();
   if (nparts == 1) {
+    // part == 0 only: with E A < nthr < 2 E A the threads beyond E A hold no share (part == 1, accW == 0) but their ea0
+    // wraps onto the elements 0 .. nthr - E A - 1, whose sums they would overwrite with zeros in whichever order the
+    // waves arrive
 #pragma unroll
     for (int u = 0; u < AFM_WPT; ++u) {
       const int ea = ea0 + u * EAs;
-      if (ea < EA) slot[ea] = accW[u];
+      if (part == 0 && ea < EA) slot[ea] = accW[u];
     }
   } else {
     if (part < nparts) red[part * EA + ea0] = accW[0];

@@ -614,3 +614,39 @@ class EmbCCPM(torch.autograd.Function):
             dws.append(dparams[at:at + n].reshape(shp))
             at += n
         return (_sparse_grad(plan, vals, E, (V, E)), None, None, None, None, *dws)
+
+
+class EmbFGCNN(torch.autograd.Function):
+    """FGCNN's conv / max-pool stack fused with the lookup (3.DCN/CustomLayers.py:757-767; csrc/fgcnn.hip): table, X
+    [B,F], and per layer the Conv2D kernel [kw,1,Cin,Cout] and bias [Cout] -> (rows [B,F,E], p_1, ..., p_L) with p_j
+    [B, H_j E C_j] the Flatten of the j-th pooled map.  Every output has consumers of its own (the rows go into the MLP
+    input, each p_j into its recombination Dense), so the backward takes a gradient per output, None read as zeros:
+    the sparse row gradient of the table and every kernel's and bias's gradient, one launch plus the slot sum."""
+
+    @staticmethod
+    def forward(ctx, table, X, filters, kernel_width, pooling_width, oob, *weights):
+        params = torch.cat([w.reshape(-1) for w in weights])          # K_1 | b_1 | K_2 | b_2 | ...
+        rows, pooled = ops.emb_fgcnn_fwd(table, X, params, filters, kernel_width, pooling_width, oob)
+        ctx.save_for_backward(X, params, rows)
+        ctx.cfg = (list(filters), list(kernel_width), list(pooling_width), [tuple(w.shape) for w in weights],
+                   tuple(table.shape), [tuple(p.shape) for p in pooled])
+        ctx.set_materialize_grads(False)
+        return (rows, *pooled)
+
+    @staticmethod
+    def backward(ctx, grows, *gpooled):
+        X, params, rows = ctx.saved_tensors
+        filters, kernel_width, pooling_width, shapes, (V, E), pshapes = ctx.cfg
+        dps = [g.contiguous() if g is not None else torch.zeros(shp, dtype=torch.float32, device=rows.device)
+               for g, shp in zip(gpooled, pshapes)]
+        vals, dparams = ops.emb_fgcnn_bwd(rows, params, filters, kernel_width, pooling_width, dps,
+                                          grows.contiguous() if grows is not None else None)
+        plan = ops.DedupPlan(X, V)
+        dws, at = [], 0
+        for shp in shapes:
+            n = 1
+            for d in shp:
+                n *= d
+            dws.append(dparams[at:at + n].reshape(shp))
+            at += n
+        return (_sparse_grad(plan, vals, E, (V, E)), None, None, None, None, None, *dws)

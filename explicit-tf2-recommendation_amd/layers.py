@@ -24,6 +24,8 @@ libmi355rec.so (through functional.py / ops.py).  Reference classes and the line
   KMaxPool                      3.DCN/CustomLayers.py:621-637
   CCPMBaseLayer                 3.DCN/CustomLayers.py:640-677
   CCPMLayer                     3.DCN/CustomLayers.py:680-725
+  FGCNNBaseLayer                3.DCN/CustomLayers.py:728-772
+  FGCNNLayer                    3.DCN/CustomLayers.py:775-822
 
 Parameters are named after the TF checkpoint keys (``embed.embeddings``, ``w.embeddings``, ``bias``,
 ``MLP_layer1.kernel_0`` ...), so a TensorBundle checkpoint maps onto ``state_dict()`` by name.
@@ -934,6 +936,86 @@ class CCPMLayer(Layer):
         self._raise_if_oob(flag)
         cont = _cont_block(inputs, self.continuous_features, X.device)
         _input = ConcatCols.apply(ccpm_output, *cont) if cont else ccpm_output       # continuous LAST (:720)
+        return {"output": self.MLP_layer2(self.MLP_layer1(_input))}
+
+
+class FGCNNBaseLayer(Layer):
+    """3.DCN/CustomLayers.py:728-772: L x (Conv2D along the field axis, tanh, MaxPool2D((pooling_width, 1))), and after
+    every pooling a Dense "recombination" of its Flatten, reshaped to [N_j, E]; the output is their concat along the
+    field axis, [B, sum N_j, E].  ``build`` takes the input shape (fields, embedding_dims).  As in the reference every
+    Dense has dnn_maps x fields x embedding_dims // pooling_width units, from the ORIGINAL field count and not from the
+    height its layer pools (ops.fgcnn_dense_units).  Holds ``conv_layers.{i}.kernel`` / ``.bias`` and
+    ``dense_layers.{i}.kernel`` / ``.bias``.  The convolutions and poolings run fused with the lookup inside FGCNNLayer
+    (csrc/fgcnn.hip); ``recombine`` is the part after them, on the GEMM kernels."""
+
+    def __init__(self, filters=[14, 16], kernel_width=[7, 7], dnn_maps=[3, 3], pooling_width=[2, 2], input_shape=None):
+        super().__init__()
+        self.filters = [int(c) for c in filters]
+        self.kernel_width = [int(k) for k in kernel_width]
+        self.dnn_maps = [int(m) for m in dnn_maps]
+        self.pooling_width = [int(w) for w in pooling_width]
+        self.built = False
+        if input_shape is not None:
+            self.build(input_shape)
+
+    def build(self, input_shape):
+        F, E = int(input_shape[-2]), int(input_shape[-1])
+        self.heights = ops.fgcnn_check_shape(F, E, self.filters, self.kernel_width, self.pooling_width, self.dnn_maps)
+        self.dense_units = ops.fgcnn_dense_units(F, E, self.dnn_maps, self.pooling_width)
+        self.new_fields = [u // E for u in self.dense_units]
+        cins = [1] + self.filters[:-1]
+        self.conv_layers = torch.nn.ModuleList(
+            [_FieldConv(kw, cin, c) for kw, cin, c in zip(self.kernel_width, cins, self.filters)])
+        self.dense_layers = torch.nn.ModuleList(
+            [Dense(u, input_dim=h * E * c) for u, h, c in zip(self.dense_units, self.heights, self.filters)])
+        self.output_dim = sum(self.dense_units)
+        self.built = True
+
+    def weights(self):
+        return [w for c in self.conv_layers for w in (c.kernel, c.bias)]
+
+    def recombine(self, pooled):
+        """[p_1 .. p_L] -> [d_1 .. d_L], d_j = Dense_j(p_j) [B, N_j E]: row-major, the reshape to [N_j, E] and the
+        Flatten that follows the concat leave the bytes where they are."""
+        return [dense(p) for dense, p in zip(self.dense_layers, pooled)]
+
+    def forward(self, inputs):
+        raise NotImplementedError("FGCNNBaseLayer's convolutions run fused with the lookup inside FGCNNLayer "
+                                  "(csrc/fgcnn.hip)")
+
+
+class FGCNNLayer(Layer):
+    """3.DCN/CustomLayers.py:775-822: output = MLP_layer2([1], sigmoid)(MLP_layer1(units, activation, batch norm)(
+    concat[Flatten(concat[X_emb, fgcnn_layer(X_emb)], axis=1), X_cont])): the embeddings first, then every layer's
+    recombined maps in order, the continuous columns LAST.  The lookup, the convolutions and the poolings are one kernel
+    each way (functional.EmbFGCNN); the recombinations and the MLPs run on the GEMM kernels."""
+
+    def __init__(self, categorical_features=["uid", "iid", "utag1", "utag2", "utag3", "utag4", "itag1", "itag2",
+                                             "itag3", "itag4"],
+                 continuous_features=["itag4_origin", "itag4_square", "itag4_cube"], feature_dims=150000,
+                 embedding_dims=16, units=[64, 8], activation="relu", is_batch_norm=True, filters=[14, 16],
+                 kernel_width=[7, 7], dnn_maps=[3, 3], pooling_width=[2, 2]):
+        super().__init__()
+        self.categorical_features = list(categorical_features)
+        self.continuous_features = list(continuous_features)
+        self.units = list(units)
+        self.activation = activation
+        F, C, E = len(self.categorical_features), len(self.continuous_features), int(embedding_dims)
+        self.fgcnn_layer = FGCNNBaseLayer(filters, kernel_width, dnn_maps, pooling_width, input_shape=(F, E))
+        self.MLP_layer1 = MLPLayer(units=self.units, activation=activation, is_batch_norm=is_batch_norm,
+                                   input_dim=F * E + self.fgcnn_layer.output_dim + C)
+        self.MLP_layer2 = MLPLayer(units=[1], activation="sigmoid", input_dim=self.units[-1])
+        self.embedding_layer = Embedding(feature_dims, E, embeddings_regularizer="l2")
+
+    def forward(self, inputs):
+        X = assemble_index(inputs, self.categorical_features)
+        flag = ops.new_flag(X.device) if self.check_ids else None
+        base = self.fgcnn_layer
+        rows, *pooled = Fn.EmbFGCNN.apply(self.embedding_layer.embeddings, X, base.filters, base.kernel_width,
+                                          base.pooling_width, flag, *base.weights())
+        self._raise_if_oob(flag)
+        cont = _cont_block(inputs, self.continuous_features, X.device)
+        _input = ConcatCols.apply(rows.reshape(rows.shape[0], -1), *base.recombine(pooled), *cont)   # :815-817
         return {"output": self.MLP_layer2(self.MLP_layer1(_input))}
 
 

@@ -188,6 +188,13 @@ class ModelManager:
                 feature_dims=self.feature_dims, embedding_dims=self.embedding_dims,
                 units=model_params.get("units", [64, 32, 8]), filters=model_params.get("filters", [4, 6]),
                 kernel_width=model_params.get("kernel_width", [4, 2]))
+        elif layer_name == "FGCNN":                        # 3.DCN/ModelManager.py:85-88
+            self.layer = CL.FGCNNLayer(
+                categorical_features=self.feature_names, continuous_features=self.continuous_features,
+                feature_dims=self.feature_dims, embedding_dims=self.embedding_dims,
+                units=model_params.get("units", [64, 8]), filters=model_params.get("filters", [14, 16]),
+                kernel_width=model_params.get("kernel_width", [7, 7]), dnn_maps=model_params.get("dnn_maps", [3, 3]),
+                pooling_width=model_params.get("pooling_width", [2, 2]))
         elif layer_name == "din_layer":                    # 5.DIN/ModelManager.py:72-73
             p = dict(model_params)
             p.setdefault("feature_dims", self.feature_dims)

@@ -949,3 +949,114 @@ def emb_ccpm_bwd(table, X, params, filters, kernel_width, dout, rows=None):
                                        _ptr(params), _ptr(rows), _ptr(dout), _ptr(vals), _ptr(dparams), _ptr(ws),
                                        nbytes, _stream()), "rec_emb_ccpm_bwd_f32")
     return vals, dparams
+
+
+# ---- FGCNN: field convolutions + max pooling, every pooled map an output, fused with the lookup (csrc/fgcnn.hip)
+FGCNN_MAX_F, FGCNN_MAX_E, FGCNN_MAX_L, FGCNN_MAX_C, FGCNN_MAX_KW, FGCNN_MAX_PW = 64, 64, 3, 16, 8, 8
+FGCNN_BWD_GRID = 1024          # workgroups of the backward (FG_MAXG_BWD): beyond it a workgroup takes a second tile
+
+
+def fgcnn_heights(F, pooling_width):
+    """H_1..H_L of the pooled maps: MaxPool2D((pw, 1)) with stride pw and VALID padding keeps H // pw rows."""
+    out, h = [], int(F)
+    for pw in pooling_width:
+        h = h // int(pw)
+        out.append(h)
+    return out
+
+
+def fgcnn_dense_units(F, E, dnn_maps, pooling_width):
+    """The units of every recombination Dense of FGCNNBaseLayer.build (3.DCN/CustomLayers.py:752-754), the expression
+    as written: from the ORIGINAL field count at every layer, not from the height that layer pools: a reference quirk
+    that is kept."""
+    return [int(m) * int(F) * int(E) // int(pw) for m, pw in zip(dnn_maps, pooling_width)]
+
+
+def fgcnn_check_shape(F, E, filters, kernel_width, pooling_width, dnn_maps=None):
+    """ValueError for a configuration the reference itself cannot run (a pooling that leaves no row; with ``dnn_maps``, a
+    Dense whose units the reshape to [-1, N, E] cannot split), NotImplementedError for shapes the FGCNN kernels do not
+    cover (the ABI would return -2).  -> the heights H_1..H_L."""
+    filters, kernel_width = [int(c) for c in filters], [int(k) for k in kernel_width]
+    pooling_width = [int(w) for w in pooling_width]
+    L = len(filters)
+    if L < 1 or len(kernel_width) != L or len(pooling_width) != L or (dnn_maps is not None and len(dnn_maps) != L):
+        raise ValueError("filters, kernel_width, dnn_maps and pooling_width must be lists of one length >= 1, got %r, "
+                         "%r, %r and %r" % (filters, kernel_width, dnn_maps, pooling_width))
+    if min(filters) < 1 or min(kernel_width) < 1 or min(pooling_width) < 1 or F < 1 or E < 1:
+        raise ValueError("fields, embedding_dims, filters, kernel_width and pooling_width must be positive")
+    heights = fgcnn_heights(F, pooling_width)
+    for j, h in enumerate(heights):
+        if h < 1:
+            raise ValueError("MaxPool2D %d (pooling_width %d) leaves no row of %d: heights %r from %d fields"
+                             % (j + 1, pooling_width[j], ([F] + heights)[j], heights, F))
+    if dnn_maps is not None:
+        for j, u in enumerate(fgcnn_dense_units(F, E, dnn_maps, pooling_width)):
+            if u < 1 or u % E:
+                raise ValueError("Dense %d has %d units (dnn_maps %d x %d fields x %d // pooling_width %d), which the "
+                                 "reshape to [-1, N, %d] cannot split" % (j + 1, u, dnn_maps[j], F, E, pooling_width[j], E))
+    if lib.rec_fgcnn_workspace_bytes(1, F, E, L, _ccpm_ints(filters), _ccpm_ints(kernel_width),
+                                     _ccpm_ints(pooling_width)) == 0:
+        raise NotImplementedError(
+            "FGCNN kernels cover fields <= %d, embedding_dims <= %d, at most %d layers, filters <= %d, kernel_width <= "
+            "%d, pooling_width <= %d and a column state within the LDS of a CU; got fields=%d, embedding_dims=%d, "
+            "filters=%r, kernel_width=%r, pooling_width=%r"
+            % (FGCNN_MAX_F, FGCNN_MAX_E, FGCNN_MAX_L, FGCNN_MAX_C, FGCNN_MAX_KW, FGCNN_MAX_PW, F, E, filters,
+               kernel_width, pooling_width))
+    return heights
+
+
+def _ptr_array(tensors):
+    return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def _fgcnn_params(params, filters, kernel_width):
+    if _f32(params, "params").numel() != ccpm_param_count(filters, kernel_width):
+        raise ValueError("params must hold %d floats for filters %r and kernel_width %r, got %d"
+                         % (ccpm_param_count(filters, kernel_width), list(filters), list(kernel_width), params.numel()))
+
+
+def emb_fgcnn_fwd(table, X, params, filters, kernel_width, pooling_width, oob=None):
+    """Lookup + L x (field conv, tanh, max pool) in one launch: params is the flat K_1 | b_1 | K_2 | ... -> (rows
+    [B,F,E], [p_1 .. p_L]) with p_j [B, H_j E C_j] the Flatten of the j-th pooled map."""
+    _table(table, "table"); _i64(X, "X")
+    V, E = table.shape
+    B, F = X.shape
+    hs = fgcnn_check_shape(F, E, filters, kernel_width, pooling_width)
+    _fgcnn_params(params, filters, kernel_width)
+    dev = table.device
+    rows = torch.empty((B, F, E), dtype=torch.float32, device=dev)
+    pooled = [torch.empty((B, h * E * int(c)), dtype=torch.float32, device=dev) for h, c in zip(hs, filters)]
+    check(lib.rec_emb_fgcnn_fwd_f32(_ptr(table), V, E, table.stride(0), _ptr(X), B, F, len(hs), _ccpm_ints(filters),
+                                    _ccpm_ints(kernel_width), _ccpm_ints(pooling_width), _ptr(params), _ptr(rows),
+                                    _ptr_array(pooled), _ptr(oob), _stream()), "rec_emb_fgcnn_fwd_f32")
+    return rows, pooled
+
+
+def emb_fgcnn_bwd(rows, params, filters, kernel_width, pooling_width, dpooled, drows_direct=None):
+    """rows [B,F,E] as the forward gathered them, dpooled = [dLoss/dp_1 .. dLoss/dp_L], drows_direct = dLoss/drows from
+    the other consumers of the rows (None: zeros) -> (vals [B*F,E] IndexedSlices values in the order of X, the direct
+    gradient included, dparams in the layout of params)."""
+    _f32(rows, "rows")
+    if rows.dim() != 3:
+        raise ValueError("rows must be [B,F,E]")
+    B, F, E = rows.shape
+    hs = fgcnn_check_shape(F, E, filters, kernel_width, pooling_width)
+    _fgcnn_params(params, filters, kernel_width)
+    if len(dpooled) != len(hs):
+        raise ValueError("dpooled must hold %d tensors, got %d" % (len(hs), len(dpooled)))
+    for j, (d, h, c) in enumerate(zip(dpooled, hs, filters)):
+        if tuple(_f32(d, "dpooled[%d]" % j).shape) != (B, h * E * int(c)):
+            raise ValueError("dpooled[%d] must be [B, %d], got %s" % (j, h * E * int(c), tuple(d.shape)))
+    if drows_direct is not None and tuple(_f32(drows_direct, "drows_direct").shape) != (B, F, E):
+        raise ValueError("drows_direct must be [B,F,E]")
+    dev = rows.device
+    vals = torch.empty((B * F, E), dtype=torch.float32, device=dev)
+    dparams = torch.zeros_like(params)
+    if B > 0:
+        fi, kwi, pwi = _ccpm_ints(filters), _ccpm_ints(kernel_width), _ccpm_ints(pooling_width)
+        nbytes = lib.rec_fgcnn_workspace_bytes(B, F, E, len(hs), fi, kwi, pwi)
+        ws = _workspace(nbytes, "rec_fgcnn_workspace_bytes", dev, torch.float32)
+        check(lib.rec_emb_fgcnn_bwd_f32(E, B, F, len(hs), fi, kwi, pwi, _ptr(params), _ptr(rows), _ptr_array(dpooled),
+                                        _ptr(drows_direct), _ptr(vals), _ptr(dparams), _ptr(ws), nbytes, _stream()),
+              "rec_emb_fgcnn_bwd_f32")
+    return vals, dparams

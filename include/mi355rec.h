@@ -621,6 +621,39 @@ int rec_emb_ccpm_bwd_f32(const float* table, int64_t V, int E, int64_t ld, const
                          const float* params, const float* rows, const float* dout, float* vals, float* dparams,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Feature Generation by CNN, fused with the lookup (FGCNNBaseLayer / FGCNNLayer, 3.DCN/CustomLayers.py:728-822;
+ * csrc/fgcnn.hip).  X int64 [B, F], table [V, E] with row stride ld.  L layers; the HOST int arrays filters_host[L]
+ * (C_j), kernel_width_host[L] (kw_j) and pooling_width_host[L] (pw_j) describe them; params is one flat DEVICE buffer
+ * K_1 | b_1 | K_2 | b_2 | ... with K_j [kw_j, 1, C_{j-1}, C_j] row-major (C_0 = 1) and b_j [C_j].
+ * With x_0[h, e, 0] = table[X[b,h]][e] (H_0 = F) and for j = 1..L:
+ *   y[h, e, co] = tanh(b_j[co] + sum_t sum_ci K_j[t, 0, ci, co] x_{j-1}[h - (kw_j - 1) / 2 + t, e, ci])   zeros outside
+ *                 [0, H_{j-1}) (TF's SAME padding: the extra row at the end)
+ *   x_j[r, e, co] = max_{q < pw_j} y[r pw_j + q, e, co]      MaxPool2D((pw_j, 1)), stride pw_j, VALID:
+ *                 H_j = H_{j-1} / pw_j, the trailing H_{j-1} mod pw_j rows are dropped
+ * The forward writes the gathered rows [B, F, E] and EVERY pooled map, pooled_out_host_ptrs[j-1] -> p_j
+ * [B, H_j E C_j] with p_j[b, (r E + e) C_j + c] = x_j[r, e, c] (Flatten); pooled_out_host_ptrs is a HOST array of L
+ * device pointers.  An id outside [0, V) sets *oob_flag (may be NULL) and reads as a zero row.
+ * The backward takes the saved rows, dpooled_host_ptrs[j-1] -> dLoss/dp_j for every j (a HOST array of L device
+ * pointers) and drows_direct [B, F, E] = dLoss/drows from the rows' other consumers (may be NULL: zeros).  It writes
+ * vals [B*F, E] = drows_direct + dLoss/dx_0, the IndexedSlices values of the lookup in the order of X, and dparams in
+ * the layout of params.  The gradient of a pooling goes to the maximum of its window, on equal values to the LOWER
+ * row; dropped rows get none.  It reads neither the table nor X, so it takes only the shape.  No float atomics:
+ * bit-identical results run to run; no host synchronisation (graph-capturable).
+ * Supported: 1 <= F <= 64, 1 <= E <= 64, 1 <= L <= 3, 1 <= C_j <= 16, 1 <= kw_j <= 8, pw_j <= 8, 0 <= B < 2^31
+ * (B == 0: nothing is launched), V < 2^31, and the state of one column within the LDS of a CU; otherwise -2.
+ * A negative size, V <= 0, ld < E, a NULL pointer, pw_j < 1 or H_j == 0: -1.
+ * workspace (backward only): rec_fgcnn_workspace_bytes (0: invalid or unsupported shape). */
+size_t rec_fgcnn_workspace_bytes(int64_t B, int F, int E, int L, const int* filters_host, const int* kernel_width_host,
+                                 const int* pooling_width_host);
+int rec_emb_fgcnn_fwd_f32(const float* table, int64_t V, int E, int64_t ld, const int64_t* X, int64_t B, int F, int L,
+                          const int* filters_host, const int* kernel_width_host, const int* pooling_width_host,
+                          const float* params, float* rows_out, float* const* pooled_out_host_ptrs, int* oob_flag,
+                          void* stream);
+int rec_emb_fgcnn_bwd_f32(int E, int64_t B, int F, int L, const int* filters_host, const int* kernel_width_host,
+                          const int* pooling_width_host, const float* params, const float* rows,
+                          const float* const* dpooled_host_ptrs, const float* drows_direct, float* vals, float* dparams,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

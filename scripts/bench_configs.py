@@ -20,6 +20,8 @@ batches, one MI355X.  Prints one JSON line per config.  Usage:  python scripts/b
   AF  AFM, 10 categorical fields, V=10M, E=16, attn_size 3, B=16384; AF26 = 26 fields, B=8192
   CC  CCPM, 10 cat + 3 cont, V=10M, E=16, filters [4,6], kernel_width [4,2], units [64,32,8], B=16384; CC26 = 26 cat
       fields, B=8192
+  FG  FGCNN, 10 cat + 3 cont, V=10M, E=16, filters [14,16], kernel_width [7,7], dnn_maps [3,3], pooling_width [2,2],
+      units [64,8], B=16384; FG26 = 26 cat fields, B=8192
 """
 import json
 import os
@@ -345,6 +347,22 @@ def run(name):
         return {"config": "%s CCPM, %d cat + 3 cont, 10M x 16d, filters [4,6] x kernel_width [4,2], units [64,32,8]"
                           % (name, ncat), "B": B, "V": V, "ms_per_step": dt * 1e3, "examples_per_s": B / dt,
                 "fwd_algorithmic_mb": (B * ncat * (8 + 4 * E) + B * 3 * E * 6 * 4) / 1e6}
+    if name in ("FG", "FG26"):
+        ncat, B = (10, 16384) if name == "FG" else (26, 8192)
+        cat = ["c%d" % i for i in range(ncat)]
+        cont = ["x0", "x1", "x2"]
+        V, E = 10_000_000, 16
+        layer = layers.FGCNNLayer(categorical_features=cat, continuous_features=cont, feature_dims=1000,
+                                  embedding_dims=E).cuda()
+        layer.embedding_layer.embeddings = torch.nn.Parameter(torch.empty((V, E), device="cuda"))
+        big_table_(layer.embedding_layer.embeddings)
+        batch = data.to_device(data.SyntheticGenerator(cat, V, continuous=cont, seed=0).batch(B))
+        dt = timed(fwd_bwd(layer, batch, cat + cont), 5, 50)
+        hs = layer.fgcnn_layer.heights
+        return {"config": "%s FGCNN, %d cat + 3 cont, 10M x 16d, filters [14,16] x kernel_width [7,7], pooling_width "
+                          "[2,2], dnn_maps [3,3], units [64,8]" % (name, ncat), "B": B, "V": V, "ms_per_step": dt * 1e3,
+                "examples_per_s": B / dt,
+                "fwd_algorithmic_mb": (B * ncat * (8 + 8 * E) + B * E * (hs[0] * 14 + hs[1] * 16) * 4) / 1e6}
     if name == "FF":
         names = ["C%d" % i for i in range(26)]
         V, B, E = 10_000_000, 8192, 16
@@ -390,7 +408,7 @@ if __name__ == "__main__":
     for n in (argv or ["A", "B", "C", "C26", "D", "E", "R", "P", "N", "FF", "G"]):
         r = run(n)
         if GRAPHED and n in ("B", "C", "C26", "D", "E", "DS", "ES", "P", "N", "FF", "G", "X", "X26", "FB", "FB26", "AI",
-                                "AI26", "AF", "AF26", "CC", "CC26"):
+                                "AI26", "AF", "AF26", "CC", "CC26", "FG", "FG26"):
             r["config"] += " [GraphedTrainStep]"
         r["n_gpus"] = 1
         print(json.dumps(r), flush=True)
