@@ -24,37 +24,25 @@
 // skipped, for every position alike), so equal inputs give bit-equal outputs and the tie rule is observable; tanhf is
 // the accurate one.  The conv weights are read with wave-uniform addresses straight from global memory.
 #include <math.h>
-#include "common.h"
+#include "field_conv.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int CCPM_MAXL = 3, CCPM_MAXF = 64, CCPM_MAXE = 64, CCPM_MAXC = 16, CCPM_MAXKW = 8;
-constexpr int CCPM_MAXG = 1024;                  // workgroups (= workspace slots) of the backward
-constexpr size_t CCPM_LDS_SOFT = 64 * 1024;      // what a workgroup aims for
-constexpr size_t CCPM_LDS_MAX = REC_LDS_CU_BYTES;
-
-struct CcpmShape {
-  int64_t B, V, ld, ncol;                        // ncol = B E columns
-  int F, E, L, NW;                               // NW: all weights, K_1 | b_1 | K_2 | b_2 | ...
-  int C[CCPM_MAXL + 1], H[CCPM_MAXL + 1];        // channels and height of state j (C[0] = 1, H[0] = F, H[j] = k_j)
-  int KW[CCPM_MAXL], woff[CCPM_MAXL], boff[CCPM_MAXL];
-  int soff[CCPM_MAXL + 2];                       // state j starts at soff[j] (floats per column); soff[L+1] = all states
-  int smax;                                      // the largest state
-};
+// In the FieldConvShape of this file H[j] = k_j, and span is the largest state: the size of each of the forward's two
+// ping-pong buffers.
 
 struct CcpmCfg {
   int nthr[2], grid[2];                          // forward, backward
   size_t lds[2];
 };
 
-__host__ __device__ inline int ccpm_r4(int n) { return (n + 3) & ~3; }
 // floats of LDS per column.  forward: two states (ping-pong) | y [F]; backward: every state | its gradient | y [F] |
 // the selected positions, one byte each
-__host__ __device__ inline int ccpm_col_floats(const CcpmShape& s, int bwd) {
+__host__ __device__ inline int ccpm_col_floats(const FieldConvShape& s, int bwd) {
   const int all = s.soff[s.L + 1];
-  return bwd ? 2 * all + s.F + ccpm_r4(all) / 4 : 2 * s.smax + s.F;
+  return bwd ? 2 * all + s.F + fc_r4(all) / 4 : 2 * s.span + s.F;
 }
 
 // One conv + tanh + k-max-pool layer of one column.  xin [Hin, Cin] and xout [k, Cout] are LDS arrays of stride `st`
@@ -97,7 +85,7 @@ __device__ __forceinline__ void ccpm_conv_pool(const float* __restrict__ Kw, con
 }
 
 // the rows of column (b, e) -> x [F] (stride st); true when an id was out of range (it reads as a zero row)
-__device__ __forceinline__ bool ccpm_load_col(const CcpmShape& s, const float* __restrict__ table,
+__device__ __forceinline__ bool ccpm_load_col(const FieldConvShape& s, const float* __restrict__ table,
                                               const int64_t* __restrict__ X, const float* __restrict__ rows_in, bool valid,
                                               int64_t b, int e, int st, float* x, float* __restrict__ rows_out) {
   bool bad = false;
@@ -123,19 +111,17 @@ __device__ __forceinline__ bool ccpm_load_col(const CcpmShape& s, const float* _
 // ------------------------------------------------------------------------------------------------------------------
 // forward: grid = ceil(B E / blockDim)
 // ------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void emb_ccpm_fwd_kernel(CcpmShape s, const float* __restrict__ table,
+__global__ __launch_bounds__(256) void emb_ccpm_fwd_kernel(FieldConvShape s, const float* __restrict__ table,
                                                            const int64_t* __restrict__ X,
                                                            const float* __restrict__ par, float* __restrict__ out,
                                                            float* __restrict__ rows_out, int* oob) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int st = blockDim.x;
   float* cur = lds + threadIdx.x;
-  float* nxt = cur + s.smax * st;
-  float* y = nxt + s.smax * st;
+  float* nxt = cur + s.span * st;
+  float* y = nxt + s.span * st;
   const int64_t col = (int64_t)blockIdx.x * st + threadIdx.x;
-  const bool valid = col < s.ncol;
-  const int64_t b = col / s.E;
-  const int e = (int)(col - b * s.E);
+  const auto [b, e, valid] = fc_col(s, col);
   if (ccpm_load_col(s, table, X, nullptr, valid, b, e, st, cur, rows_out) && oob) *oob = 1;
   for (int j = 0; j < s.L; ++j) {
     ccpm_conv_pool(par + s.woff[j], par + s.boff[j], s.H[j], s.C[j], s.C[j + 1], s.KW[j], s.H[j + 1], st, cur, nxt, y,
@@ -154,7 +140,7 @@ __global__ __launch_bounds__(256) void emb_ccpm_fwd_kernel(CcpmShape s, const fl
 // ------------------------------------------------------------------------------------------------------------------
 // backward: persistent grid, blockDim a multiple of 64; slot of workgroup g [NW] in the layout of the weights
 // ------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void emb_ccpm_bwd_kernel(CcpmShape s, const float* __restrict__ table,
+__global__ __launch_bounds__(256) void emb_ccpm_bwd_kernel(FieldConvShape s, const float* __restrict__ table,
                                                            const int64_t* __restrict__ X,
                                                            const float* __restrict__ par,
                                                            const float* __restrict__ rows_in,
@@ -175,9 +161,7 @@ __global__ __launch_bounds__(256) void emb_ccpm_bwd_kernel(CcpmShape s, const fl
   const int64_t ntiles = (s.ncol + st - 1) / st;
   for (int64_t tl = blockIdx.x; tl < ntiles; tl += gridDim.x) {
     const int64_t col = tl * st + threadIdx.x;
-    const bool valid = col < s.ncol;
-    const int64_t b = col / s.E;
-    const int e = (int)(col - b * s.E);
+    const auto [b, e, valid] = fc_col(s, col);
     ccpm_load_col(s, table, X, rows_in, valid, b, e, st, xs, nullptr);
     for (int j = 0; j < L; ++j)
       ccpm_conv_pool(par + s.woff[j], par + s.boff[j], s.H[j], s.C[j], s.C[j + 1], s.KW[j], s.H[j + 1], st,
@@ -245,91 +229,60 @@ __global__ __launch_bounds__(256) void emb_ccpm_bwd_kernel(CcpmShape s, const fl
 
 // 0 ok (B == 0 included), REC_E_ARG, REC_E_UNSUPPORTED
 static int ccpm_shape(int64_t B, int F, int E, int L, const int* filters, const int* kernel_width, const int* pool_k,
-                      int64_t V, int64_t ld, CcpmShape* s) {
-  if (B < 0 || F < 0 || E < 0 || L < 0 || V <= 0 || ld < E || !filters || !kernel_width || !pool_k) return REC_E_ARG;
-  for (int j = 0; j < L && j < CCPM_MAXL; ++j)
-    if (filters[j] < 0 || kernel_width[j] < 0 || pool_k[j] < 0) return REC_E_ARG;
-  if (F < 1 || F > CCPM_MAXF || E < 1 || E > CCPM_MAXE || L < 1 || L > CCPM_MAXL) return REC_E_UNSUPPORTED;
-  if (B > 0x7fffffffLL || V >= ((int64_t)1 << 31)) return REC_E_UNSUPPORTED;
-  *s = CcpmShape{};
-  s->B = B;
-  s->V = V;
-  s->ld = ld;
-  s->ncol = B * E;
-  s->F = F;
-  s->E = E;
-  s->L = L;
-  s->C[0] = 1;
-  s->H[0] = F;
-  s->soff[0] = 0;
-  s->soff[1] = F;
-  s->smax = F;
-  int off = 0;
+                      int64_t V, int64_t ld, FieldConvShape* s) {
+  if (int rc = fc_begin(s, B, F, E, L, filters, kernel_width, pool_k, 0, V, ld)) return rc;
+  s->span = F;
   for (int j = 0; j < L; ++j) {
-    const int c = filters[j], kw = kernel_width[j], k = pool_k[j];
+    const int k = pool_k[j];
     if (k > s->H[j]) return REC_E_ARG;                         // top_k over fewer values than k: the reference raises
-    if (c < 1 || c > CCPM_MAXC || kw < 1 || kw > CCPM_MAXKW || k < 1) return REC_E_UNSUPPORTED;
-    s->C[j + 1] = c;
-    s->H[j + 1] = k;
-    s->KW[j] = kw;
-    s->woff[j] = off;
-    off += kw * s->C[j] * c;
-    s->boff[j] = off;
-    off += c;
-    s->soff[j + 2] = s->soff[j + 1] + k * c;
-    if (k * c > s->smax) s->smax = k * c;
+    if (k < 1) return REC_E_UNSUPPORTED;
+    if (int rc = fc_layer(s, j, filters[j], kernel_width[j], k)) return rc;
+    if (k * filters[j] > s->span) s->span = k * filters[j];
   }
-  s->NW = off;
   return REC_OK;
 }
 
 // nthr[d] == 0: the column state does not fit the LDS of a CU
-static CcpmCfg ccpm_cfg(const CcpmShape& s) {
+static CcpmCfg ccpm_cfg(const FieldConvShape& s) {
   CcpmCfg k{};
   for (int d = 0; d < 2; ++d) {
     int nthr = 256;
     size_t bytes;
     for (;;) {
       bytes = ((size_t)ccpm_col_floats(s, d) * nthr + (d ? (size_t)(nthr / 64) * s.NW : 0)) * 4;
-      if (bytes <= CCPM_LDS_SOFT || nthr == 64) break;
+      if (bytes <= FC_LDS_SOFT || nthr == 64) break;
       nthr >>= 1;
     }
-    if (bytes > CCPM_LDS_MAX) continue;
-    const int64_t ntiles = (s.ncol + nthr - 1) / nthr;
+    if (bytes > FC_LDS_MAX) continue;
     k.nthr[d] = nthr;
     k.lds[d] = bytes;
-    k.grid[d] = (int)(d == 0 ? ntiles : (ntiles < CCPM_MAXG ? ntiles : CCPM_MAXG));
-    if (k.grid[d] < 1) k.grid[d] = 1;
+    k.grid[d] = d ? fc_grid(s, nthr, FC_MAXG_BWD) : fc_grid(s, nthr);
   }
   return k;
-}
-
-static size_t ccpm_ws_bytes(const CcpmShape& s, const CcpmCfg& k) {
-  return rec_align_up((size_t)k.grid[1] * s.NW * sizeof(float), 256);
 }
 
 }  // namespace
 
 extern "C" size_t rec_ccpm_workspace_bytes(int64_t B, int F, int E, int L, const int* filters, const int* kernel_width,
                                            const int* pool_k) {
-  CcpmShape s;
+  FieldConvShape s;
   if (ccpm_shape(B, F, E, L, filters, kernel_width, pool_k, 1, E, &s) != REC_OK) return 0;
   const CcpmCfg k = ccpm_cfg(s);
   if (!k.nthr[0] || !k.nthr[1]) return 0;
-  return ccpm_ws_bytes(s, k);
+  return fc_ws_bytes(s, k.grid[1]);
 }
 
 extern "C" int rec_emb_ccpm_fwd_f32(const float* table, int64_t V, int E, int64_t ld, const int64_t* X, int64_t B, int F,
                                     int L, const int* filters, const int* kernel_width, const int* pool_k,
                                     const float* params, float* out, float* rows, int* oob_flag, void* stream) {
-  CcpmShape s;
+  FieldConvShape s;
   const int rc = ccpm_shape(B, F, E, L, filters, kernel_width, pool_k, V, ld, &s);
   if (rc != REC_OK) return rc;
   const CcpmCfg k = ccpm_cfg(s);
   if (!k.nthr[0] || !k.nthr[1]) return REC_E_UNSUPPORTED;
   if (B == 0) return REC_OK;
   if (!table || !X || !params || !out) return REC_E_ARG;
-  if (hipError_t e = rec_allow_lds<emb_ccpm_fwd_kernel>(CCPM_LDS_MAX)) return (int)e;
+  if (hipError_t e = rec_allow_lds<emb_ccpm_fwd_kernel>(FC_LDS_MAX)) return (int)e;
   hipLaunchKernelGGL(emb_ccpm_fwd_kernel, dim3(k.grid[0]), dim3(k.nthr[0]), k.lds[0], as_stream(stream), s, table, X,
                      params, out, rows, oob_flag);
   REC_LAUNCH_CHECK();
@@ -340,17 +293,17 @@ extern "C" int rec_emb_ccpm_bwd_f32(const float* table, int64_t V, int E, int64_
                                     int L, const int* filters, const int* kernel_width, const int* pool_k,
                                     const float* params, const float* rows, const float* dout, float* vals,
                                     float* dparams, void* workspace, size_t workspace_bytes, void* stream) {
-  CcpmShape s;
+  FieldConvShape s;
   const int rc = ccpm_shape(B, F, E, L, filters, kernel_width, pool_k, V, ld, &s);
   if (rc != REC_OK) return rc;
   const CcpmCfg k = ccpm_cfg(s);
   if (!k.nthr[0] || !k.nthr[1]) return REC_E_UNSUPPORTED;
   if (B == 0) return REC_OK;
   if ((!rows && (!table || !X)) || !params || !dout || !vals || !dparams || !workspace) return REC_E_ARG;
-  if (workspace_bytes < ccpm_ws_bytes(s, k)) return REC_E_WORKSPACE;
+  if (workspace_bytes < fc_ws_bytes(s, k.grid[1])) return REC_E_WORKSPACE;
   hipStream_t st = as_stream(stream);
   float* slots = static_cast<float*>(workspace);
-  if (hipError_t e = rec_allow_lds<emb_ccpm_bwd_kernel>(CCPM_LDS_MAX)) return (int)e;
+  if (hipError_t e = rec_allow_lds<emb_ccpm_bwd_kernel>(FC_LDS_MAX)) return (int)e;
   hipLaunchKernelGGL(emb_ccpm_bwd_kernel, dim3(k.grid[1]), dim3(k.nthr[1]), k.lds[1], st, s, table, X, params, rows,
                      dout, vals, slots);
   REC_LAUNCH_CHECK();

@@ -30,30 +30,21 @@
 // blockDim floats and wave-uniform weights from global memory, here a lane group walks a contiguous column with the
 // weights in LDS and pools inside the loop; one routine for both would change what either compiles to.
 #include <math.h>
-#include "common.h"
+#include "field_conv.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int FG_MAXL = 3, FG_MAXF = 64, FG_MAXE = 64, FG_MAXC = 16, FG_MAXKW = 8, FG_MAXPW = 8;
+constexpr int FG_MAXPW = 8;
 constexpr int FG_NTHR = 256, FG_MING = 16;
 constexpr int FG_MAXG_FWD = 2048;                // workgroups of the forward
-constexpr int FG_MAXG_BWD = 1024;                // workgroups (= workspace slots) of the backward
-constexpr size_t FG_LDS_SOFT = 64 * 1024;        // what a workgroup aims for
-constexpr size_t FG_LDS_MAX = REC_LDS_CU_BYTES;
 
-struct FgShape {
-  int64_t B, V, ld, ncol;                        // ncol = B E columns
-  int F, E, L, NW;                               // NW: all weights, K_1 | b_1 | K_2 | b_2 | ...
-  int C[FG_MAXL + 1], H[FG_MAXL + 1];            // channels and height of state j (C[0] = 1, H[0] = F)
-  int KW[FG_MAXL], PW[FG_MAXL], woff[FG_MAXL], boff[FG_MAXL];
-  int soff[FG_MAXL + 2];                         // state j starts at soff[j] (floats per column); soff[L+1] = all states
-  int S;                                         // the stride of a column: soff[L+1] rounded up to an odd multiple of 4
-};
+// In the FieldConvShape of this file PW[j-1] = pw_j, H[j] = H[j-1] / pw_j, and span = S, the stride of a column:
+// soff[L+1] rounded up to an odd multiple of 4.
 
 struct FgPtrs {
-  float* p[FG_MAXL];
+  float* p[FC_MAXL];
 };
 
 struct FgCfg {
@@ -61,12 +52,12 @@ struct FgCfg {
   size_t lds[2];
 };
 
-__host__ __device__ inline int fg_r4(int n) { return (n + 3) & ~3; }
 // floats of LDS of a workgroup.  forward: weights | cols x states; backward: weights | their gradients | cols x
 // (states | gradients | selected rows, one byte each)
-__host__ __device__ inline size_t fg_lds_floats(const FgShape& s, int G, int bwd) {
+__host__ __device__ inline size_t fg_lds_floats(const FieldConvShape& s, int G, int bwd) {
   const size_t cols = FG_NTHR / G;
-  return bwd ? 2 * (size_t)fg_r4(s.NW) + cols * (2 * (size_t)s.S + s.S / 4) : (size_t)fg_r4(s.NW) + cols * s.S;
+  return bwd ? 2 * (size_t)fc_r4(s.NW) + cols * (2 * (size_t)s.span + s.span / 4)
+             : (size_t)fc_r4(s.NW) + cols * s.span;
 }
 
 // One conv + max-pool + tanh layer of one column, by the G lanes of its group: lane g computes the pooled values
@@ -101,32 +92,17 @@ __device__ __forceinline__ void fg_conv_pool(const float* W, const float* bias, 
   }
 }
 
-// tile geometry: column slot c of tile tl is column tl cols + c = (b, e)
-struct FgCol {
-  int64_t b;
-  int e;
-  bool valid;
-};
-__device__ __forceinline__ FgCol fg_col(const FgShape& s, int64_t tl, int cols, int c) {
-  const int64_t col = tl * cols + c;
-  FgCol k;
-  k.valid = col < s.ncol;
-  k.b = col / s.E;
-  k.e = (int)(col - k.b * s.E);
-  return k;
-}
-
 // ------------------------------------------------------------------------------------------------------------------
 // forward: persistent over tiles of 256 / G columns
 // ------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(FG_NTHR) void emb_fgcnn_fwd_kernel(FgShape s, int G, const float* __restrict__ table,
+__global__ __launch_bounds__(FG_NTHR) void emb_fgcnn_fwd_kernel(FieldConvShape s, int G, const float* __restrict__ table,
                                                                 const int64_t* __restrict__ X,
                                                                 const float* __restrict__ par,
                                                                 float* __restrict__ rows_out, FgPtrs pooled, int* oob) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int tid = threadIdx.x, cols = FG_NTHR / G, L = s.L, S = s.S;
+  const int tid = threadIdx.x, cols = FG_NTHR / G, L = s.L, S = s.span;
   float* wl = lds;                                             // [NW]
-  float* xs = wl + fg_r4(s.NW);                                // [cols][S]
+  float* xs = wl + fc_r4(s.NW);                                // [cols][S]
   for (int t = tid; t < s.NW; t += FG_NTHR) wl[t] = par[t];
   const int myc = tid / G, g = tid - myc * G;
   float* mx = xs + myc * S;
@@ -137,7 +113,7 @@ __global__ __launch_bounds__(FG_NTHR) void emb_fgcnn_fwd_kernel(FgShape s, int G
     __syncthreads();                                           // the weights; the previous tile's readers
     for (int i = tid; i < s.F * cols; i += FG_NTHR) {          // gather: [h][c], the lanes along e
       const int h = i / cols, c = i - h * cols;
-      const FgCol k = fg_col(s, tl, cols, c);
+      const FcCol k = fc_col(s, tl * cols + c);                // column slot c of tile tl
       float v = 0.f;
       if (k.valid) {
         const int64_t id = X[k.b * s.F + h];
@@ -160,7 +136,7 @@ __global__ __launch_bounds__(FG_NTHR) void emb_fgcnn_fwd_kernel(FgShape s, int G
       float* __restrict__ out = pooled.p[j - 1];
       for (int i = tid; i < n; i += FG_NTHR) {
         const int r = i / per, rem = i - r * per, c = rem / Cj, ch = rem - c * Cj;
-        const FgCol k = fg_col(s, tl, cols, c);
+        const FcCol k = fc_col(s, tl * cols + c);
         if (k.valid) out[k.b * ((int64_t)s.H[j] * s.E * Cj) + (r * s.E + k.e) * Cj + ch] = xs[c * S + s.soff[j] + r * Cj + ch];
       }
     }
@@ -171,15 +147,15 @@ __global__ __launch_bounds__(FG_NTHR) void emb_fgcnn_fwd_kernel(FgShape s, int G
 // ------------------------------------------------------------------------------------------------------------------
 // backward: persistent over tiles of 256 / G columns; slot of workgroup w [NW] in the layout of the weights
 // ------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(FG_NTHR) void emb_fgcnn_bwd_kernel(FgShape s, int G, const float* __restrict__ par,
+__global__ __launch_bounds__(FG_NTHR) void emb_fgcnn_bwd_kernel(FieldConvShape s, int G, const float* __restrict__ par,
                                                                 const float* __restrict__ rows, FgPtrs dpooled,
                                                                 const float* __restrict__ ddirect,
                                                                 float* __restrict__ vals, float* __restrict__ slots) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int tid = threadIdx.x, cols = FG_NTHR / G, L = s.L, S = s.S;
+  const int tid = threadIdx.x, cols = FG_NTHR / G, L = s.L, S = s.span;
   float* wl = lds;                                             // [NW]
-  float* wacc = wl + fg_r4(s.NW);                              // [NW]: element w has ONE writer, thread w mod 256
-  float* xs = wacc + fg_r4(s.NW);                              // [cols][S] states
+  float* wacc = wl + fc_r4(s.NW);                              // [NW]: element w has ONE writer, thread w mod 256
+  float* xs = wacc + fc_r4(s.NW);                              // [cols][S] states
   float* gs = xs + cols * S;                                   // [cols][S] their gradients
   unsigned char* sl = reinterpret_cast<unsigned char*>(gs + cols * S);   // [cols][S] selected rows
   for (int t = tid; t < s.NW; t += FG_NTHR) {
@@ -196,7 +172,7 @@ __global__ __launch_bounds__(FG_NTHR) void emb_fgcnn_bwd_kernel(FgShape s, int G
     __syncthreads();
     for (int i = tid; i < s.F * cols; i += FG_NTHR) {
       const int h = i / cols, c = i - h * cols;
-      const FgCol k = fg_col(s, tl, cols, c);
+      const FcCol k = fc_col(s, tl * cols + c);
       xs[c * S + h] = k.valid ? rows[(k.b * s.F + h) * s.E + k.e] : 0.f;
     }
     for (int j = 1; j <= L; ++j) {                             // g(x_j) starts as dp_j
@@ -204,7 +180,7 @@ __global__ __launch_bounds__(FG_NTHR) void emb_fgcnn_bwd_kernel(FgShape s, int G
       const float* __restrict__ d = dpooled.p[j - 1];
       for (int i = tid; i < n; i += FG_NTHR) {
         const int r = i / per, rem = i - r * per, c = rem / Cj, ch = rem - c * Cj;
-        const FgCol k = fg_col(s, tl, cols, c);
+        const FcCol k = fc_col(s, tl * cols + c);
         gs[c * S + s.soff[j] + r * Cj + ch] =
             k.valid ? d[k.b * ((int64_t)s.H[j] * s.E * Cj) + (r * s.E + k.e) * Cj + ch] : 0.f;
       }
@@ -267,7 +243,7 @@ __global__ __launch_bounds__(FG_NTHR) void emb_fgcnn_bwd_kernel(FgShape s, int G
     }
     for (int i = tid; i < s.F * cols; i += FG_NTHR) {
       const int h = i / cols, c = i - h * cols;
-      const FgCol k = fg_col(s, tl, cols, c);
+      const FcCol k = fc_col(s, tl * cols + c);
       if (k.valid) {
         const int64_t at = (k.b * s.F + h) * s.E + k.e;
         vals[at] = ddirect ? ddirect[at] + gs[c * S + h] : gs[c * S + h];
@@ -281,88 +257,55 @@ __global__ __launch_bounds__(FG_NTHR) void emb_fgcnn_bwd_kernel(FgShape s, int G
 
 // 0 ok (B == 0 included), REC_E_ARG, REC_E_UNSUPPORTED
 static int fg_shape(int64_t B, int F, int E, int L, const int* filters, const int* kernel_width, const int* pooling_width,
-                    int64_t V, int64_t ld, FgShape* s) {
-  if (B < 0 || F < 0 || E < 0 || L < 0 || V <= 0 || ld < E || !filters || !kernel_width || !pooling_width)
-    return REC_E_ARG;
-  for (int j = 0; j < L && j < FG_MAXL; ++j)
-    if (filters[j] < 0 || kernel_width[j] < 0 || pooling_width[j] < 1) return REC_E_ARG;
-  if (F < 1 || F > FG_MAXF || E < 1 || E > FG_MAXE || L < 1 || L > FG_MAXL) return REC_E_UNSUPPORTED;
-  if (B > 0x7fffffffLL || V >= ((int64_t)1 << 31)) return REC_E_UNSUPPORTED;
-  *s = FgShape{};
-  s->B = B;
-  s->V = V;
-  s->ld = ld;
-  s->ncol = B * E;
-  s->F = F;
-  s->E = E;
-  s->L = L;
-  s->C[0] = 1;
-  s->H[0] = F;
-  s->soff[0] = 0;
-  s->soff[1] = F;
-  int off = 0;
+                    int64_t V, int64_t ld, FieldConvShape* s) {
+  if (int rc = fc_begin(s, B, F, E, L, filters, kernel_width, pooling_width, 1, V, ld)) return rc;
   for (int j = 0; j < L; ++j) {
-    const int c = filters[j], kw = kernel_width[j], pw = pooling_width[j];
+    const int pw = pooling_width[j];
     if (s->H[j] / pw < 1) return REC_E_ARG;                    // a pooling wider than what it pools: nothing is left
-    if (c < 1 || c > FG_MAXC || kw < 1 || kw > FG_MAXKW || pw > FG_MAXPW) return REC_E_UNSUPPORTED;
-    s->C[j + 1] = c;
-    s->H[j + 1] = s->H[j] / pw;
-    s->KW[j] = kw;
+    if (pw > FG_MAXPW) return REC_E_UNSUPPORTED;
+    if (int rc = fc_layer(s, j, filters[j], kernel_width[j], s->H[j] / pw)) return rc;
     s->PW[j] = pw;
-    s->woff[j] = off;
-    off += kw * s->C[j] * c;
-    s->boff[j] = off;
-    off += c;
-    s->soff[j + 2] = s->soff[j + 1] + s->H[j + 1] * c;
   }
-  s->NW = off;
-  s->S = fg_r4(s->soff[L + 1]);
-  if (!(s->S & 4)) s->S += 4;                                  // an odd number of 16-byte units: columns spread over banks
+  s->span = fc_r4(s->soff[L + 1]);
+  if (!(s->span & 4)) s->span += 4;                            // an odd number of 16-byte units: columns spread over banks
   return REC_OK;
 }
 
 // G[d] == 0: the state of one column does not fit the LDS of a CU
-static FgCfg fg_cfg(const FgShape& s) {
+static FgCfg fg_cfg(const FieldConvShape& s) {
   FgCfg k{};
   for (int d = 0; d < 2; ++d) {
     int G = FG_MING;
     size_t bytes;
     for (;;) {
       bytes = fg_lds_floats(s, G, d) * 4;
-      if (bytes <= FG_LDS_SOFT || G == 64) break;
+      if (bytes <= FC_LDS_SOFT || G == 64) break;
       G <<= 1;
     }
-    if (bytes > FG_LDS_MAX) continue;
-    const int cols = FG_NTHR / G, cap = d ? FG_MAXG_BWD : FG_MAXG_FWD;
-    const int64_t ntiles = (s.ncol + cols - 1) / cols;
+    if (bytes > FC_LDS_MAX) continue;
     k.G[d] = G;
     k.lds[d] = bytes;
-    k.grid[d] = (int)(ntiles < cap ? ntiles : cap);
-    if (k.grid[d] < 1) k.grid[d] = 1;
+    k.grid[d] = fc_grid(s, FG_NTHR / G, d ? FC_MAXG_BWD : FG_MAXG_FWD);
   }
   return k;
-}
-
-static size_t fg_ws_bytes(const FgShape& s, const FgCfg& k) {
-  return rec_align_up((size_t)k.grid[1] * s.NW * sizeof(float), 256);
 }
 
 }  // namespace
 
 extern "C" size_t rec_fgcnn_workspace_bytes(int64_t B, int F, int E, int L, const int* filters, const int* kernel_width,
                                             const int* pooling_width) {
-  FgShape s;
+  FieldConvShape s;
   if (fg_shape(B, F, E, L, filters, kernel_width, pooling_width, 1, E, &s) != REC_OK) return 0;
   const FgCfg k = fg_cfg(s);
   if (!k.G[0] || !k.G[1]) return 0;
-  return fg_ws_bytes(s, k);
+  return fc_ws_bytes(s, k.grid[1]);
 }
 
 extern "C" int rec_emb_fgcnn_fwd_f32(const float* table, int64_t V, int E, int64_t ld, const int64_t* X, int64_t B, int F,
                                      int L, const int* filters, const int* kernel_width, const int* pooling_width,
                                      const float* params, float* rows, float* const* pooled, int* oob_flag,
                                      void* stream) {
-  FgShape s;
+  FieldConvShape s;
   const int rc = fg_shape(B, F, E, L, filters, kernel_width, pooling_width, V, ld, &s);
   if (rc != REC_OK) return rc;
   const FgCfg k = fg_cfg(s);
@@ -374,7 +317,7 @@ extern "C" int rec_emb_fgcnn_fwd_f32(const float* table, int64_t V, int E, int64
     if (!pooled[j]) return REC_E_ARG;
     pp.p[j] = pooled[j];
   }
-  if (hipError_t e = rec_allow_lds<emb_fgcnn_fwd_kernel>(FG_LDS_MAX)) return (int)e;
+  if (hipError_t e = rec_allow_lds<emb_fgcnn_fwd_kernel>(FC_LDS_MAX)) return (int)e;
   hipLaunchKernelGGL(emb_fgcnn_fwd_kernel, dim3(k.grid[0]), dim3(FG_NTHR), k.lds[0], as_stream(stream), s, k.G[0], table,
                      X, params, rows, pp, oob_flag);
   REC_LAUNCH_CHECK();
@@ -385,7 +328,7 @@ extern "C" int rec_emb_fgcnn_bwd_f32(int E, int64_t B, int F, int L, const int* 
                                      const int* pooling_width, const float* params, const float* rows,
                                      const float* const* dpooled, const float* drows_direct, float* vals, float* dparams,
                                      void* workspace, size_t workspace_bytes, void* stream) {
-  FgShape s;
+  FieldConvShape s;
   const int rc = fg_shape(B, F, E, L, filters, kernel_width, pooling_width, 1, E, &s);
   if (rc != REC_OK) return rc;
   const FgCfg k = fg_cfg(s);
@@ -397,10 +340,10 @@ extern "C" int rec_emb_fgcnn_bwd_f32(int E, int64_t B, int F, int L, const int* 
     if (!dpooled[j]) return REC_E_ARG;
     pp.p[j] = const_cast<float*>(dpooled[j]);
   }
-  if (workspace_bytes < fg_ws_bytes(s, k)) return REC_E_WORKSPACE;
+  if (workspace_bytes < fc_ws_bytes(s, k.grid[1])) return REC_E_WORKSPACE;
   hipStream_t st = as_stream(stream);
   float* slots = static_cast<float*>(workspace);
-  if (hipError_t e = rec_allow_lds<emb_fgcnn_bwd_kernel>(FG_LDS_MAX)) return (int)e;
+  if (hipError_t e = rec_allow_lds<emb_fgcnn_bwd_kernel>(FC_LDS_MAX)) return (int)e;
   hipLaunchKernelGGL(emb_fgcnn_bwd_kernel, dim3(k.grid[1]), dim3(FG_NTHR), k.lds[1], st, s, k.G[1], params, rows, pp,
                      drows_direct, vals, slots);
   REC_LAUNCH_CHECK();

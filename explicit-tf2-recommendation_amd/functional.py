@@ -4,6 +4,8 @@ IndexedSlices-like sparse gradient -- here already de-duplicated (sorted unique 
 as an uncoalesced torch sparse COO tensor whose padded tail points at a valid id with zero rows, so no
 host synchronisation is needed to learn the unique count.
 """
+import math
+
 import torch
 
 from . import ops
@@ -582,6 +584,21 @@ class EmbAFM(torch.autograd.Function):
         return _sparse_grad(plan, vals, E, (V, E)), None, dWa, dba, dhv, dbh, None
 
 
+def _flatten_weights(weights):
+    """[K_1, b_1, K_2, b_2, ...] -> (the flat params K_1 | b_1 | K_2 | b_2 | ..., their shapes)."""
+    return torch.cat([w.reshape(-1) for w in weights]), [tuple(w.shape) for w in weights]
+
+
+def _split_like(flat, shapes):
+    """The inverse of _flatten_weights: views of ``flat`` in the weights' shapes."""
+    out, at = [], 0
+    for shp in shapes:
+        n = math.prod(shp)
+        out.append(flat[at:at + n].reshape(shp))
+        at += n
+    return out
+
+
 class EmbCCPM(torch.autograd.Function):
     """CCPM's conv / k-max-pool stack fused with the lookup (3.DCN/CustomLayers.py:621-677; csrc/ccpm.hip): table, X
     [B,F], and per layer the Conv2D kernel [kw,1,Cin,Cout] and bias [Cout] -> Flatten of the last pooling,
@@ -593,10 +610,10 @@ class EmbCCPM(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, table, X, filters, kernel_width, oob, *weights):
-        params = torch.cat([w.reshape(-1) for w in weights])          # K_1 | b_1 | K_2 | b_2 | ...
+        params, shapes = _flatten_weights(weights)
         out, rows = ops.emb_ccpm_fwd(table, X, params, filters, kernel_width, oob, want_rows=EmbCCPM.SAVE_ROWS)
         ctx.save_for_backward(table, X, params, rows)
-        ctx.cfg = (list(filters), list(kernel_width), [tuple(w.shape) for w in weights])
+        ctx.cfg = (list(filters), list(kernel_width), shapes)
         return out
 
     @staticmethod
@@ -606,14 +623,7 @@ class EmbCCPM(torch.autograd.Function):
         V, E = table.shape
         vals, dparams = ops.emb_ccpm_bwd(table, X, params, filters, kernel_width, g.contiguous(), rows)
         plan = ops.DedupPlan(X, V)
-        dws, at = [], 0
-        for shp in shapes:
-            n = 1
-            for d in shp:
-                n *= d
-            dws.append(dparams[at:at + n].reshape(shp))
-            at += n
-        return (_sparse_grad(plan, vals, E, (V, E)), None, None, None, None, *dws)
+        return (_sparse_grad(plan, vals, E, (V, E)), None, None, None, None, *_split_like(dparams, shapes))
 
 
 class EmbFGCNN(torch.autograd.Function):
@@ -625,11 +635,11 @@ class EmbFGCNN(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, table, X, filters, kernel_width, pooling_width, oob, *weights):
-        params = torch.cat([w.reshape(-1) for w in weights])          # K_1 | b_1 | K_2 | b_2 | ...
+        params, shapes = _flatten_weights(weights)
         rows, pooled = ops.emb_fgcnn_fwd(table, X, params, filters, kernel_width, pooling_width, oob)
         ctx.save_for_backward(X, params, rows)
-        ctx.cfg = (list(filters), list(kernel_width), list(pooling_width), [tuple(w.shape) for w in weights],
-                   tuple(table.shape), [tuple(p.shape) for p in pooled])
+        ctx.cfg = (list(filters), list(kernel_width), list(pooling_width), shapes, tuple(table.shape),
+                   [tuple(p.shape) for p in pooled])
         ctx.set_materialize_grads(False)
         return (rows, *pooled)
 
@@ -642,11 +652,4 @@ class EmbFGCNN(torch.autograd.Function):
         vals, dparams = ops.emb_fgcnn_bwd(rows, params, filters, kernel_width, pooling_width, dps,
                                           grows.contiguous() if grows is not None else None)
         plan = ops.DedupPlan(X, V)
-        dws, at = [], 0
-        for shp in shapes:
-            n = 1
-            for d in shp:
-                n *= d
-            dws.append(dparams[at:at + n].reshape(shp))
-            at += n
-        return (_sparse_grad(plan, vals, E, (V, E)), None, None, None, None, None, *dws)
+        return (_sparse_grad(plan, vals, E, (V, E)), None, None, None, None, None, *_split_like(dparams, shapes))

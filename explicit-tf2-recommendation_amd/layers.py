@@ -870,7 +870,20 @@ class _FieldConv(Layer):
         self.bias = torch.nn.Parameter(torch.zeros(int(cout)))
 
     def forward(self, inputs):
-        raise NotImplementedError("the field convolution runs fused inside CCPMLayer (csrc/ccpm.hip)")
+        raise NotImplementedError("the field convolution runs fused inside CCPMLayer (csrc/ccpm.hip) and FGCNNLayer "
+                                  "(csrc/fgcnn.hip)")
+
+
+def _field_convs(filters, kernel_width):
+    """The ``conv_layers`` of CCPMBaseLayer and FGCNNBaseLayer: layer i reads the channels of layer i - 1, the first one
+    a single channel."""
+    cins = [1] + list(filters[:-1])
+    return torch.nn.ModuleList([_FieldConv(kw, cin, c) for kw, cin, c in zip(kernel_width, cins, filters)])
+
+
+def _field_conv_weights(conv_layers):
+    """K_1, b_1, K_2, b_2, ...: the order of the kernels' flat params."""
+    return [w for c in conv_layers for w in (c.kernel, c.bias)]
 
 
 class CCPMBaseLayer(Layer):
@@ -891,15 +904,13 @@ class CCPMBaseLayer(Layer):
     def build(self, input_shape):
         F, E = int(input_shape[-2]), int(input_shape[-1])
         self.pool_k = ops.ccpm_check_shape(F, E, self.filters, self.kernel_width)
-        cins = [1] + self.filters[:-1]
-        self.conv_layers = torch.nn.ModuleList(
-            [_FieldConv(kw, cin, c) for kw, cin, c in zip(self.kernel_width, cins, self.filters)])
+        self.conv_layers = _field_convs(self.filters, self.kernel_width)
         self.kmax_layers = torch.nn.ModuleList([KMaxPool(k) for k in self.pool_k])
         self.output_dim = self.pool_k[-1] * E * self.filters[-1]
         self.built = True
 
     def weights(self):
-        return [w for c in self.conv_layers for w in (c.kernel, c.bias)]
+        return _field_conv_weights(self.conv_layers)
 
     def forward(self, inputs):
         raise NotImplementedError("CCPMBaseLayer runs fused with the lookup inside CCPMLayer (csrc/ccpm.hip)")
@@ -963,16 +974,14 @@ class FGCNNBaseLayer(Layer):
         self.heights = ops.fgcnn_check_shape(F, E, self.filters, self.kernel_width, self.pooling_width, self.dnn_maps)
         self.dense_units = ops.fgcnn_dense_units(F, E, self.dnn_maps, self.pooling_width)
         self.new_fields = [u // E for u in self.dense_units]
-        cins = [1] + self.filters[:-1]
-        self.conv_layers = torch.nn.ModuleList(
-            [_FieldConv(kw, cin, c) for kw, cin, c in zip(self.kernel_width, cins, self.filters)])
+        self.conv_layers = _field_convs(self.filters, self.kernel_width)
         self.dense_layers = torch.nn.ModuleList(
             [Dense(u, input_dim=h * E * c) for u, h, c in zip(self.dense_units, self.heights, self.filters)])
         self.output_dim = sum(self.dense_units)
         self.built = True
 
     def weights(self):
-        return [w for c in self.conv_layers for w in (c.kernel, c.bias)]
+        return _field_conv_weights(self.conv_layers)
 
     def recombine(self, pooled):
         """[p_1 .. p_L] -> [d_1 .. d_L], d_j = Dense_j(p_j) [B, N_j E]: row-major, the reshape to [N_j, E] and the

@@ -857,10 +857,31 @@ def emb_afm_bwd(table, X, Wa, ba, hv, bh, o, stats, dout, rows=None):
     return vals, dWa, dba, dhv, dbh
 
 
+# ---- field-conv stacks: what CCPM and FGCNN share (csrc/field_conv.h): the limits and the flat K_1 | b_1 | K_2 | ...
+CCPM_MAX_F = FGCNN_MAX_F = 64                  # fields
+CCPM_MAX_E = FGCNN_MAX_E = 64                  # embedding_dims
+CCPM_MAX_L = FGCNN_MAX_L = 3                   # layers
+CCPM_MAX_C = FGCNN_MAX_C = 16                  # filters
+CCPM_MAX_KW = FGCNN_MAX_KW = 8                 # kernel_width
+
+
+def _ints(values):
+    return (C.c_int * len(values))(*[int(v) for v in values])
+
+
+def field_conv_param_count(filters, kernel_width):
+    cins = [1] + list(filters[:-1])
+    return sum(kw * cin * c + c for kw, cin, c in zip(kernel_width, cins, filters))
+
+
+def _field_conv_params(params, filters, kernel_width):
+    n = field_conv_param_count(filters, kernel_width)
+    if _f32(params, "params").numel() != n:
+        raise ValueError("params must hold %d floats for filters %r and kernel_width %r, got %d"
+                         % (n, list(filters), list(kernel_width), params.numel()))
+
+
 # ---- CCPM: field convolutions + k-max pooling, fused with the lookup (csrc/ccpm.hip)
-CCPM_MAX_F, CCPM_MAX_E, CCPM_MAX_L, CCPM_MAX_C, CCPM_MAX_KW = 64, 64, 3, 16, 8
-
-
 def ccpm_k(E, L):
     """The k of every KMaxPool of CCPMBaseLayer.build (3.DCN/CustomLayers.py:657-667), the expression as written.  Its
     ``fields_num`` is input_shape[-1], the EMBEDDING width, not the field count: a reference quirk that is kept."""
@@ -868,18 +889,6 @@ def ccpm_k(E, L):
     layers_num = int(L)
     return [max(1, int((1 - pow(j / layers_num, layers_num - j)) * fields_num)) if j < layers_num else 3
             for j in range(1, layers_num + 1)]
-
-
-def _ccpm_ints(values):
-    return (C.c_int * len(values))(*[int(v) for v in values])
-
-
-def ccpm_param_count(filters, kernel_width):
-    cin, n = 1, 0
-    for c, kw in zip(filters, kernel_width):
-        n += kw * cin * c + c
-        cin = c
-    return n
 
 
 def ccpm_check_shape(F, E, filters, kernel_width):
@@ -897,8 +906,7 @@ def ccpm_check_shape(F, E, filters, kernel_width):
             raise ValueError("KMaxPool %d takes k = %d of %d values (k comes from embedding_dims = %d, fields = %d): "
                              "tf.nn.top_k raises" % (j + 1, k, h, E, F))
         h = k
-    if lib.rec_ccpm_workspace_bytes(1, F, E, len(filters), _ccpm_ints(filters), _ccpm_ints(kernel_width),
-                                    _ccpm_ints(ks)) == 0:
+    if lib.rec_ccpm_workspace_bytes(1, F, E, len(filters), _ints(filters), _ints(kernel_width), _ints(ks)) == 0:
         raise NotImplementedError(
             "CCPM kernels cover fields <= %d, embedding_dims <= %d, at most %d layers, filters <= %d, kernel_width <= %d "
             "and a column state within the LDS of a CU; got fields=%d, embedding_dims=%d, filters=%r, kernel_width=%r"
@@ -913,15 +921,13 @@ def emb_ccpm_fwd(table, X, params, filters, kernel_width, oob=None, want_rows=Fa
     V, E = table.shape
     B, F = X.shape
     ks = ccpm_check_shape(F, E, filters, kernel_width)
-    if params.numel() != ccpm_param_count(filters, kernel_width):
-        raise ValueError("params must hold %d floats for filters %r and kernel_width %r, got %d"
-                         % (ccpm_param_count(filters, kernel_width), list(filters), list(kernel_width), params.numel()))
+    _field_conv_params(params, filters, kernel_width)
     dev = table.device
     out = torch.empty((B, ks[-1] * E * int(filters[-1])), dtype=torch.float32, device=dev)
     rows = torch.empty((B, F, E), dtype=torch.float32, device=dev) if want_rows else None
-    check(lib.rec_emb_ccpm_fwd_f32(_ptr(table), V, E, table.stride(0), _ptr(X), B, F, len(ks), _ccpm_ints(filters),
-                                   _ccpm_ints(kernel_width), _ccpm_ints(ks), _ptr(params), _ptr(out), _ptr(rows),
-                                   _ptr(oob), _stream()), "rec_emb_ccpm_fwd_f32")
+    check(lib.rec_emb_ccpm_fwd_f32(_ptr(table), V, E, table.stride(0), _ptr(X), B, F, len(ks), _ints(filters),
+                                   _ints(kernel_width), _ints(ks), _ptr(params), _ptr(out), _ptr(rows), _ptr(oob),
+                                   _stream()), "rec_emb_ccpm_fwd_f32")
     return out, rows
 
 
@@ -932,8 +938,7 @@ def emb_ccpm_bwd(table, X, params, filters, kernel_width, dout, rows=None):
     V, E = table.shape
     B, F = X.shape
     ks = ccpm_check_shape(F, E, filters, kernel_width)
-    if params.numel() != ccpm_param_count(filters, kernel_width):
-        raise ValueError("params does not match filters %r and kernel_width %r" % (list(filters), list(kernel_width)))
+    _field_conv_params(params, filters, kernel_width)
     if tuple(dout.shape) != (B, ks[-1] * E * int(filters[-1])):
         raise ValueError("dout must be [B, %d], got %s" % (ks[-1] * E * int(filters[-1]), tuple(dout.shape)))
     if rows is not None and tuple(_f32(rows, "rows").shape) != (B, F, E):
@@ -942,7 +947,7 @@ def emb_ccpm_bwd(table, X, params, filters, kernel_width, dout, rows=None):
     vals = torch.empty((B * F, E), dtype=torch.float32, device=dev)
     dparams = torch.zeros_like(params)
     if B > 0:
-        fi, kwi, ki = _ccpm_ints(filters), _ccpm_ints(kernel_width), _ccpm_ints(ks)
+        fi, kwi, ki = _ints(filters), _ints(kernel_width), _ints(ks)
         nbytes = lib.rec_ccpm_workspace_bytes(B, F, E, len(ks), fi, kwi, ki)
         ws = _workspace(nbytes, "rec_ccpm_workspace_bytes", dev, torch.float32)
         check(lib.rec_emb_ccpm_bwd_f32(_ptr(table), V, E, table.stride(0), _ptr(X), B, F, len(ks), fi, kwi, ki,
@@ -952,8 +957,8 @@ def emb_ccpm_bwd(table, X, params, filters, kernel_width, dout, rows=None):
 
 
 # ---- FGCNN: field convolutions + max pooling, every pooled map an output, fused with the lookup (csrc/fgcnn.hip)
-FGCNN_MAX_F, FGCNN_MAX_E, FGCNN_MAX_L, FGCNN_MAX_C, FGCNN_MAX_KW, FGCNN_MAX_PW = 64, 64, 3, 16, 8, 8
-FGCNN_BWD_GRID = 1024          # workgroups of the backward (FG_MAXG_BWD): beyond it a workgroup takes a second tile
+FGCNN_MAX_PW = 8
+FGCNN_BWD_GRID = 1024          # workgroups of the backward (FC_MAXG_BWD): beyond it a workgroup takes a second tile
 
 
 def fgcnn_heights(F, pooling_width):
@@ -994,8 +999,7 @@ def fgcnn_check_shape(F, E, filters, kernel_width, pooling_width, dnn_maps=None)
             if u < 1 or u % E:
                 raise ValueError("Dense %d has %d units (dnn_maps %d x %d fields x %d // pooling_width %d), which the "
                                  "reshape to [-1, N, %d] cannot split" % (j + 1, u, dnn_maps[j], F, E, pooling_width[j], E))
-    if lib.rec_fgcnn_workspace_bytes(1, F, E, L, _ccpm_ints(filters), _ccpm_ints(kernel_width),
-                                     _ccpm_ints(pooling_width)) == 0:
+    if lib.rec_fgcnn_workspace_bytes(1, F, E, L, _ints(filters), _ints(kernel_width), _ints(pooling_width)) == 0:
         raise NotImplementedError(
             "FGCNN kernels cover fields <= %d, embedding_dims <= %d, at most %d layers, filters <= %d, kernel_width <= "
             "%d, pooling_width <= %d and a column state within the LDS of a CU; got fields=%d, embedding_dims=%d, "
@@ -1009,12 +1013,6 @@ def _ptr_array(tensors):
     return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
 
-def _fgcnn_params(params, filters, kernel_width):
-    if _f32(params, "params").numel() != ccpm_param_count(filters, kernel_width):
-        raise ValueError("params must hold %d floats for filters %r and kernel_width %r, got %d"
-                         % (ccpm_param_count(filters, kernel_width), list(filters), list(kernel_width), params.numel()))
-
-
 def emb_fgcnn_fwd(table, X, params, filters, kernel_width, pooling_width, oob=None):
     """Lookup + L x (field conv, tanh, max pool) in one launch: params is the flat K_1 | b_1 | K_2 | ... -> (rows
     [B,F,E], [p_1 .. p_L]) with p_j [B, H_j E C_j] the Flatten of the j-th pooled map."""
@@ -1022,12 +1020,12 @@ def emb_fgcnn_fwd(table, X, params, filters, kernel_width, pooling_width, oob=No
     V, E = table.shape
     B, F = X.shape
     hs = fgcnn_check_shape(F, E, filters, kernel_width, pooling_width)
-    _fgcnn_params(params, filters, kernel_width)
+    _field_conv_params(params, filters, kernel_width)
     dev = table.device
     rows = torch.empty((B, F, E), dtype=torch.float32, device=dev)
     pooled = [torch.empty((B, h * E * int(c)), dtype=torch.float32, device=dev) for h, c in zip(hs, filters)]
-    check(lib.rec_emb_fgcnn_fwd_f32(_ptr(table), V, E, table.stride(0), _ptr(X), B, F, len(hs), _ccpm_ints(filters),
-                                    _ccpm_ints(kernel_width), _ccpm_ints(pooling_width), _ptr(params), _ptr(rows),
+    check(lib.rec_emb_fgcnn_fwd_f32(_ptr(table), V, E, table.stride(0), _ptr(X), B, F, len(hs), _ints(filters),
+                                    _ints(kernel_width), _ints(pooling_width), _ptr(params), _ptr(rows),
                                     _ptr_array(pooled), _ptr(oob), _stream()), "rec_emb_fgcnn_fwd_f32")
     return rows, pooled
 
@@ -1041,7 +1039,7 @@ def emb_fgcnn_bwd(rows, params, filters, kernel_width, pooling_width, dpooled, d
         raise ValueError("rows must be [B,F,E]")
     B, F, E = rows.shape
     hs = fgcnn_check_shape(F, E, filters, kernel_width, pooling_width)
-    _fgcnn_params(params, filters, kernel_width)
+    _field_conv_params(params, filters, kernel_width)
     if len(dpooled) != len(hs):
         raise ValueError("dpooled must hold %d tensors, got %d" % (len(hs), len(dpooled)))
     for j, (d, h, c) in enumerate(zip(dpooled, hs, filters)):
@@ -1053,7 +1051,7 @@ def emb_fgcnn_bwd(rows, params, filters, kernel_width, pooling_width, dpooled, d
     vals = torch.empty((B * F, E), dtype=torch.float32, device=dev)
     dparams = torch.zeros_like(params)
     if B > 0:
-        fi, kwi, pwi = _ccpm_ints(filters), _ccpm_ints(kernel_width), _ccpm_ints(pooling_width)
+        fi, kwi, pwi = _ints(filters), _ints(kernel_width), _ints(pooling_width)
         nbytes = lib.rec_fgcnn_workspace_bytes(B, F, E, len(hs), fi, kwi, pwi)
         ws = _workspace(nbytes, "rec_fgcnn_workspace_bytes", dev, torch.float32)
         check(lib.rec_emb_fgcnn_bwd_f32(E, B, F, len(hs), fi, kwi, pwi, _ptr(params), _ptr(rows), _ptr_array(dpooled),

@@ -189,6 +189,23 @@ def test_ccpm_workspace_is_positive_for_the_bench_configs(B, F):
     assert lib.rec_ccpm_workspace_bytes(1, 3, 1, 1, _ints([1]), _ints([1]), _ints([3])) > 0
 
 
+@pytest.mark.parametrize("filters,kw", [([1], [1]), ([4, 6], [4, 2]), ([4, 6, 5], [4, 3, 2])])
+def test_flat_params_round_trip_through_the_weights_shapes(filters, kw):
+    """The pair CCPM and FGCNN share: _flatten_weights lays [K_1, b_1, K_2, ...] out as the kernels read them,
+    field_conv_param_count counts that layout, and _split_like gives every weight back in its own shape."""
+    from explicit_tf2_recommendation_amd import functional as Fn, ops
+    params = CR.make_params(filters, kw, 7)
+    weights = [torch.from_numpy(a) for kb in params for a in kb]
+    flat, shapes = Fn._flatten_weights(weights)
+    assert flat.dim() == 1 and flat.numel() == ops.field_conv_param_count(filters, kw)
+    assert shapes == [s for k, cin, c in zip(kw, [1] + filters[:-1], filters) for s in ((k, 1, cin, c), (c,))]
+    np.testing.assert_array_equal(flat.numpy(), CR.flat_params(params))
+    back = Fn._split_like(flat, shapes)
+    assert len(back) == len(weights)
+    for got, want in zip(back, weights):
+        assert got.shape == want.shape and torch.equal(got, want)
+
+
 def test_signatures_keep_the_reference_keywords():
     """3.DCN/CustomLayers.py:622, :646 and :681-684."""
     from explicit_tf2_recommendation_amd import layers as CL
