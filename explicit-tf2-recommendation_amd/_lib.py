@@ -1,4 +1,8 @@
-"""ctypes binding of csrc/libmi355rec.so (the C ABI declared in include/mi355rec.h).
+"""ctypes binding of csrc/libmi355rec.so, generated from the C ABI's own declaration, include/mi355rec.h.
+
+The header is the one description of the boundary: this module reads it at import and derives the signature of every
+entry point, the fields of ``DeepFMLazyAdam`` and the ``REC_*`` constants (``LIMITS``) from it.  The type spellings it
+accepts are a closed set (the header's preamble lists them); any other fails the import and names the declaration.
 
 The HIP library is the product: there is NO fallback.  If the shared object is missing or a symbol the
 header declares cannot be resolved, importing this module raises -- build it with
@@ -6,125 +10,85 @@ header declares cannot be resolved, importing this module raises -- build it wit
 """
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libmi355rec.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mi355rec.h")   # what csrc/build.sh compiles against
 
-p, i32, i64, f32, sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double,
+            "size_t": C.c_size_t}
 
 
 class DeepFMLazyAdam(C.Structure):
-    """rec_deepfm_lazy_adam of include/mi355rec.h: the optional lazy-Adam group of rec_deepfm_fused_post_f32."""
-    _fields_ = [("table", p), ("ld", i64), ("V", i64), ("m_e", p), ("v_e", p), ("m_w", p), ("v_w", p), ("ld_state", i64),
-                ("ld_wstate", i64), ("lr_t_dev", p), ("b1", f32), ("b2", f32), ("eps", f32), ("last", p), ("step_dev", p)]
+    """rec_deepfm_lazy_adam of include/mi355rec.h: the optional lazy-Adam group of rec_deepfm_fused_post_f32 (its
+    _fields_ are set from the header below)."""
 
 
-# symbol -> (restype, argtypes); must list every function of include/mi355rec.h
-SIGNATURES = {
-    "rec_version": (i32, []),
-    "rec_index_pack_i64": (i32, [p, i32, i64, p, i64, i64, p]),
-    "rec_emb_gather_f32": (i32, [p, i64, i32, i64, p, i64, p, p, p]),
-    "rec_emb_fm_fwd_f32": (i32, [p, i64, p, i64, p, i64, i32, p, i64, i32, p, p, p, p, p, p]),
-    "rec_emb_fm_bwd_vals_f32": (i32, [p, i64, i64, i32, p, i64, i32, p, p, p, p, p, p]),
-    "rec_dedup_workspace_bytes": (sz, [i64]),
-    "rec_dedup_plan_i64": (i32, [p, i64, i64, p, p, p, p, p, sz, p]),
-    "rec_dedup_plan_sorted_lists_i64": (i32, [p, i64, p, i32, i64, p, p, p, p, p, sz, p]),
-    "rec_segment_sum_workspace_bytes": (sz, [i64, i32]),
-    "rec_segment_sum_f32": (i32, [p, i32, p, p, i64, i32, p, p, p]),
-    "rec_gemm_f32": (i32, [i32, i32, i64, i64, i64, p, i64, p, i64, p, i64, i32, p, p, i64, p, i64, i32, p, p, p]),
-    "rec_act_fwd_f32": (i32, [i32, p, p, p, i64, p]),
-    "rec_crossnet_mat_bwd_elem_f32": (i32, [p, p, p, p, p, i32, i64, p]),
-    "rec_act_bwd_f32": (i32, [i32, p, p, p, i64, p]),
-    "rec_colsum_workspace_bytes": (sz, [i64, i64]),
-    "rec_colsum_fused_f32": (i32, [p, i64, i64, i64, p, p, p, p]),
-    "rec_colsum_f32": (i32, [p, i64, i64, i64, p, p, p]),
-    "rec_axpby_f32": (i32, [f32, p, f32, p, i64, p]),
-    "rec_copy_cols_f32": (i32, [p, i64, p, i64, i64, i64, p]),
-    "rec_crossnet_vec_fwd_f32": (i32, [p, i64, i32, i32, p, p, p, p, p]),
-    "rec_crossnet_vec_bwd_workspace_bytes": (sz, [i64, i32, i32]),
-    "rec_crossnet_vec_bwd_f32": (i32, [p, i64, i32, i32, p, p, p, p, p, p, p, p]),
-    "rec_cosine_fwd_f32": (i32, [p, p, i64, i32, p, p]),
-    "rec_cosine_bwd_f32": (i32, [p, p, i64, i32, p, p, p, p]),
-    "rec_bce_fwd_bwd_f32": (i32, [p, p, i64, p, p, p, p]),
-    "rec_adam_lr_t_f32": (f32, [f32, f32, f32, i64]),
-    "rec_adam_dense_multi_f32": (i32, [i32, p, p, p, p, p, p, f32, f32, f32, p]),
-    "rec_adam_keras_catchup_f32": (i32, [p, p, i64, i32, p, i64, i64, p, p, i64, p, p, i64, p, p, p, i64, f32, f32, f32, p]),
-    "rec_adam_keras_flush_f32": (i32, [p, i64, i64, p, p, i64, p, p, i64, p, p, p, i64, f32, f32, f32, p]),
-    "rec_adam_dense_f32": (i32, [p, p, p, p, i64, i64, f32, f32, f32, f32, p]),
-    "rec_adam_sparse_keras_f32": (i32, [p, i64, p, p, i64, i32, p, p, p, i64, p, i64, f32, f32, f32, f32, p]),
-    "rec_adam_sparse_keras_pair_f32": (i32, [p, i64, p, p, p, p, i64, i32, p, p, p, p, i64, p, p, i64, f32, f32, f32, f32, p]),
-    "rec_adam_rows_f32": (i32, [p, i64, p, p, i64, i32, p, p, p, i64, i64, f32, f32, f32, f32, p]),
-    "rec_l2_rows_workspace_bytes": (sz, [i64, i32]),
-    "rec_l2_rows_f32": (i32, [p, i64, i64, i32, p, p, i64, f32, p, p, p, p]),
-    "rec_l2_normalize_rows_f32": (i32, [p, i64, i32, i64, p, i64, p]),
-    "rec_topk_l2_workspace_bytes": (sz, [i64, i64, i32]),
-    "rec_topk_l2_f32": (i32, [p, i64, i32, i64, p, i64, i64, i32, p, p, p, sz, p]),
-    "rec_emb_ipn_fwd_f32": (i32, [p, i64, i32, i64, p, i64, i32, p, i64, p, p]),
-    "rec_emb_ipn_bwd_vals_f32": (i32, [p, i64, p, i64, i64, i32, i32, p, p]),
-    "rec_emb_bi_fwd_f32": (i32, [p, i64, i32, i64, p, i64, i32, p, i64, p, p, p]),
-    "rec_emb_bi_bwd_vals_f32": (i32, [p, i64, i32, i64, p, i64, i32, p, i64, p, p, p]),
-    "rec_ip_attn_fwd_f32": (i32, [p, i64, i64, i32, i32, p, i64, i32, p, i64, i64, p, p, i64, p, p]),
-    "rec_ip_attn_bwd_f32": (i32, [p, i64, i64, i32, i32, p, i64, i32, p, i64, i64, p, p, i64, p, p, p]),
-    "rec_ffm_fwd_f32": (i32, [p, i64, p, i64, p, i64, i32, p, i64, i32, p, p, p, p]),
-    "rec_ffm_bwd_rows_f32": (i32, [p, i64, i64, i32, p, i64, i32, p, p, p, p, p, p]),
-    "rec_batchnorm_workspace_bytes": (sz, [i64, i32]),
-    "rec_batchnorm_fwd_f32": (i32, [p, i64, i64, i32, p, p, f32, f32, i32, p, p, p, p, p, p, p]),
-    "rec_batchnorm_bwd_f32": (i32, [p, p, p, i64, i32, p, i32, p, p, p, p, p]),
-    "rec_shard_bucketize_workspace_bytes": (sz, [i64, i32]),
-    "rec_shard_bucketize_i64": (i32, [p, i64, i64, i32, p, p, p, p, p, sz, p]),
-    "rec_colsort_shard_map_i64": (i32, [p, p, p, p, i64, i32, i64, i32, p, p, p, p, p, p]),
-    "rec_colsort_shard_map_fixed_i64": (i32, [p, p, p, p, i64, i32, i64, i32, i64, p, p, p, p, p, p]),
-    "rec_emb_gather_lists_f32": (i32, [p, i64, i32, i64, p, i32, i64, p, p, p]),
-    "rec_block_copy": (i32, [p, i32, i64, p, p]),
-    "rec_auc_hist_update_f32": (i32, [p, p, i64, p, i32, p, p, i32, p, p]),
-    "rec_shard_slab_map_uslot_i64": (i32, [p, p, p, p, i64, i64, i32, i64, p, p, p, p, p]),
-    "rec_dedup_plan_sorted_slabs_i64": (i32, [p, i32, i64, i64, p, p, p, p, p, sz, p]),
-    "rec_permute_rows_f32": (i32, [p, p, i64, i32, i32, p, p]),
-    "rec_deepfm_fused_workspace_bytes": (sz, [i64, i32]),
-    "rec_colsort_workspace_bytes": (sz, [i64, i32]),
-    "rec_colsort_digits": (i32, [i64, i64, p, p]),
-    "rec_colsort_plan_i64": (i32, [p, i32, i64, i64, p, i64, p, p, p, p, p, p, p]),
-    "rec_colsort_plan_dest_i64": (i32, [p, i32, i64, i64, p, i64, p, p, p, p, p, p, p, p]),
-    "rec_deepfm_k0t_f32": (i32, [p, i32, p, p]),
-    "rec_deepfm_fused3_main_f32": (i32, [p, i64, i64, p, i32, i64] + [p] * 10 + [p, p, i64, p] + [p]),
-    "rec_deepfm_fused_post_f32": (i32, [i32, i64] + [p] * 14 + [i32, C.POINTER(DeepFMLazyAdam), p]),
-    "rec_dssm_fused_workspace_bytes": (sz, [i64, i32, i32, i32]),
-    "rec_dssm_fused_main_f32": (i32, [p, i64, i64, p, i32, p, i64, i64, p, i32, i32, i32, i32, i32, i64, p, p, p, p, p, p,
-                                      p, p, p, sz, p, p, i64, p, p]),
-    "rec_dssm_fused_post_f32": (i32, [i64, i32, i32, i32, p, sz, p, p, p, p, p, p, p, p, p, p, p, p, p, p, p, i64, i64,
-                                      i64, i64, p, f32, f32, f32, p]),
-    "rec_din_prepare_f32": (i32, [p, p, i32, i32, p, p, p, p]),
-    "rec_din_prepare_bwd_f32": (i32, [p, p, i32, i32, p, p]),
-    "rec_din_attn_fwd_f32": (i32, [p, i64, i64, i32, i32, p, i64, i32, p, p, i32, i32, p, p, p, p, p, i64, i32, p, p, p,
-                                   p]),
-    "rec_din_attn_bwd_f32": (i32, [p, i64, i64, i32, i32, p, i64, i32, p, p, i32, i32, p, p, p, p, p, i64, i32, p, p, p,
-                                   p, p, p, p, p]),
-    "rec_feat_act_fwd_f32": (i32, [i32, p, p, p, p, p, i64, i32, p]),
-    "rec_feat_act_bwd_f32": (i32, [i32, p, p, p, p, p, p, p, i64, i32, p]),
-    "rec_layernorm_fwd_f32": (i32, [p, p, p, i64, i32, p, p, p, p]),
-    "rec_layernorm_bwd_f32": (i32, [p, p, p, p, i64, i32, p, p, p]),
-    "rec_softmax_fwd_f32": (i32, [p, i64, i32, p, p]),
-    "rec_softmax_bwd_f32": (i32, [p, p, i64, i32, p, p]),
-    "rec_cin_workspace_bytes": (sz, [i64, i32, i32, i32, p]),
-    "rec_cin_fwd_f32": (i32, [p, i64, i32, i32, i32, p, p, p, p, p]),
-    "rec_cin_bwd_f32": (i32, [p, p, p, i64, i32, i32, i32, p, p, p, p, p, sz, p]),
-    "rec_fibinet_workspace_bytes": (sz, [i64, i32, i32, i32, i32]),
-    "rec_fibinet_fwd_f32": (i32, [p, p, p, p, p, i64, i32, i32, i32, i32, i32, p, p, p, p]),
-    "rec_fibinet_bwd_f32": (i32, [p, p, p, p, p, p, p, i64, i32, i32, i32, i32, i32, p, p, p, p, p, sz, p]),
-    "rec_autoint_workspace_bytes": (sz, [i64, i32, i32, i32, i32, i32]),
-    "rec_autoint_fwd_f32": (i32, [p, p, p, p, p, p, p, i64, i32, i32, i32, i32, i32, i32, p, p, p, p, sz, p]),
-    "rec_autoint_bwd_f32": (i32, [p, p, p, p, p, p, p, p, p, p, i64, i32, i32, i32, i32, i32, i32, p, p, p, p, p, p, p,
-                                  sz, p]),
-    "rec_afm_workspace_bytes": (sz, [i64, i32, i32, i32]),
-    "rec_emb_afm_fwd_f32": (i32, [p, i64, i32, i64, p, i64, i32, i32, p, p, p, p, p, p, p, p, p]),
-    "rec_emb_afm_bwd_f32": (i32, [p, i64, i32, i64, p, i64, i32, i32, p, p, p, p, p, p, p, p, p, p, p, p, p, p, sz, p]),
-    "rec_ccpm_workspace_bytes": (sz, [i64, i32, i32, i32, p, p, p]),
-    "rec_emb_ccpm_fwd_f32": (i32, [p, i64, i32, i64, p, i64, i32, i32, p, p, p, p, p, p, p, p]),
-    "rec_emb_ccpm_bwd_f32": (i32, [p, i64, i32, i64, p, i64, i32, i32, p, p, p, p, p, p, p, p, p, sz, p]),
-    "rec_fgcnn_workspace_bytes": (sz, [i64, i32, i32, i32, p, p, p]),
-    "rec_emb_fgcnn_fwd_f32": (i32, [p, i64, i32, i64, p, i64, i32, i32, p, p, p, p, p, p, p, p]),
-    "rec_emb_fgcnn_bwd_f32": (i32, [i32, i64, i32, i32, p, p, p, p, p, p, p, p, p, p, sz, p]),
-}
+def _ctype(decl, where, named=False):
+    """'const float* const*' -> c_void_p, 'int64_t' -> c_int64, ...; with `named`, decl ends in the parameter's name.
+    `where` names the declaration in the error."""
+    words = decl.replace("*", " * ").split()
+    stars = "*" in words
+    words = [w for w in words if w not in ("const", "*")]
+    base = words[0] if len(words) == 1 + named else None
+    if stars and base == "rec_deepfm_lazy_adam":
+        return C.POINTER(DeepFMLazyAdam)
+    if stars and (base in _SCALARS or base == "void"):
+        return C.c_void_p
+    if not stars and base in _SCALARS:
+        return _SCALARS[base]
+    raise ImportError("include/mi355rec.h, %s: the bindings know no type like %r (the header's preamble lists the "
+                      "spellings)" % (where, decl.strip()))
+
+
+def strip_comments(text):
+    return re.sub(r"/\*.*?\*/|//[^\n]*", "", text, flags=re.S)
+
+
+def constants(text):
+    """{name: value} of every `#define REC_<NAME> <integer>` (the value may stand in parentheses)."""
+    found = re.findall(r"^[ \t]*#[ \t]*define[ \t]+(REC_\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$", text, flags=re.M)
+    return {name: int(value) for name, value in found}
+
+
+def struct_fields(text, struct):
+    """ctypes _fields_ of `struct <struct> { ... }`: statements `type declarator, declarator;`, * on the declarator."""
+    body = re.search(r"struct\s+%s\s*\{(.*?)\}" % struct, text, flags=re.S)
+    if not body:
+        raise ImportError("include/mi355rec.h does not define struct %s" % struct)
+    fields = []
+    for stmt in filter(None, (s.strip() for s in body.group(1).split(";"))):
+        base, declarators = re.fullmatch(r"((?:const\s+)?\w+)\s*(.*)", stmt, flags=re.S).groups()
+        for d in declarators.split(","):
+            name = d.replace("*", "").strip()
+            fields.append((name, _ctype(base + "*" * d.count("*"), "struct %s, field %s" % (struct, name))))
+    return fields
+
+
+def prototypes(text):
+    """{symbol: (restype, argtypes)} of every prototype `ret rec_name(type name, ...);`."""
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    table = {}
+    for ret, name, args in re.findall(r"(?:^|(?<=[;{}]))\s*([\w\s*]+?)\s*\b(rec_\w+)\s*\(([^()]*)\)\s*;", text):
+        args = [] if args.strip() == "void" else args.split(",")
+        table[name] = (_ctype(ret, name), [_ctype(a, name, named=True) for a in args])
+    return table
+
+
+def _read_header():
+    if not os.path.exists(HEADER_PATH):
+        raise ImportError(
+            "%s not found: the ctypes bindings of the HIP extension are generated from it (the package is used from "
+            "its source tree, next to include/)" % HEADER_PATH)
+    with open(HEADER_PATH) as f:
+        return strip_comments(f.read())
+
+
+_header = _read_header()
+LIMITS = constants(_header)                    # REC_OK, REC_E_*, REC_MAX_COLS and the kernel families' shape limits
+DeepFMLazyAdam._fields_ = struct_fields(_header, "rec_deepfm_lazy_adam")
+SIGNATURES = prototypes(_header)               # symbol -> (restype, argtypes), every function of include/mi355rec.h
 
 
 def _load():

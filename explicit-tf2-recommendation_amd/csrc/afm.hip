@@ -28,7 +28,7 @@
 namespace {
 
 constexpr int AFM_NT = 256;
-constexpr int AFM_MAXF = 64, AFM_MAXE = 64, AFM_MAXA = 16;
+constexpr int AFM_MAXF = REC_AFM_MAX_F, AFM_MAXE = REC_AFM_MAX_E, AFM_MAXA = REC_AFM_MAX_A;
 constexpr int AFM_MAXG = 1024;                  // workgroups (= workspace slots) of the backward
 constexpr int AFM_WPT = 16;                     // dWa elements per thread: E A <= 1024 over >= 64 threads
 constexpr size_t AFM_LDS_SOFT = 64 * 1024;      // what a workgroup aims for

@@ -31,7 +31,7 @@
 namespace {
 
 constexpr int AI_NT = 256;
-constexpr int AI_MAXF = 64, AI_MAXE = 64;
+constexpr int AI_MAXF = REC_AUTOINT_MAX_F, AI_MAXE = REC_AUTOINT_MAX_E;
 constexpr int AI_MAXG = 512;                   // workgroups (= workspace slots) of the persistent kernels
 constexpr int AI_TBMAX = 32;                   // examples per tile
 constexpr int AI_LDS_SOFT = 16384;             // floats of LDS a tile aims for (64 KiB: two workgroups per CU)

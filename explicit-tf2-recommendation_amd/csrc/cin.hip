@@ -20,7 +20,7 @@
 namespace {
 
 constexpr int CIN_NT = 256;                       // 4 waves
-constexpr int CIN_MAXL = 8;
+constexpr int CIN_MAXF = REC_CIN_MAX_F, CIN_MAXE = REC_CIN_MAX_E, CIN_MAXL = REC_CIN_MAX_L, CIN_MAXH = REC_CIN_MAX_H;
 constexpr size_t CIN_LDS_BUDGET = REC_LDS_CU_BYTES;
 constexpr size_t CIN_WS_CAP = (size_t)512 << 20;  // bytes of dW slots the backward may ask for
 
@@ -352,9 +352,9 @@ static int cin_shape(int64_t B, int F, int E, int L, const int* H_host, CinShape
   if (B < 1 || F < 1 || E < 1 || L < 1 || !H_host) return REC_E_ARG;
   for (int k = 0; k < L && k < CIN_MAXL; ++k)
     if (H_host[k] < 1) return REC_E_ARG;
-  if (F > 64 || E > 64 || L > CIN_MAXL) return REC_E_UNSUPPORTED;
+  if (F > CIN_MAXF || E > CIN_MAXE || L > CIN_MAXL) return REC_E_UNSUPPORTED;
   for (int k = 0; k < L; ++k)
-    if (H_host[k] > 256) return REC_E_UNSUPPORTED;
+    if (H_host[k] > CIN_MAXH) return REC_E_UNSUPPORTED;
   if (B > ((int64_t)1 << 40) / 64) return REC_E_UNSUPPORTED;
   *s = CinShape{};
   s->B = B;

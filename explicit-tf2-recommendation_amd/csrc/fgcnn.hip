@@ -36,7 +36,7 @@
 
 namespace {
 
-constexpr int FG_MAXPW = 8;
+constexpr int FG_MAXPW = REC_FGCNN_MAX_PW;
 constexpr int FG_NTHR = 256, FG_MING = 16;
 constexpr int FG_MAXG_FWD = 2048;                // workgroups of the forward
 

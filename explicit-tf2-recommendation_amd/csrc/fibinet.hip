@@ -25,7 +25,7 @@
 namespace {
 
 constexpr int FB_NT = 256;                       // 4 waves
-constexpr int FB_MAXF = 32, FB_MAXE = 64, FB_MAXC = 64;
+constexpr int FB_MAXF = REC_FIBINET_MAX_F, FB_MAXE = REC_FIBINET_MAX_E, FB_MAXC = REC_FIBINET_MAX_C;
 constexpr int FB_MAXX_BLOCKS = 1024;             // persistent grid of the dx kernel: at most 4096 dS slots
 constexpr int FB_TARGET_W_BLOCKS = 2048;         // workgroups of the dW kernel (items x chunks)
 constexpr int FB_MAX_CHUNKS = 64;

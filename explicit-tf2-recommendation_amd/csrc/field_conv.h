@@ -12,8 +12,9 @@
 #include <limits.h>
 #include "common.h"
 
-constexpr int FC_MAXL = 3, FC_MAXF = 64, FC_MAXE = 64, FC_MAXC = 16, FC_MAXKW = 8;
-constexpr int FC_MAXG_BWD = 1024;                // workgroups (= workspace slots) of a backward
+constexpr int FC_MAXL = REC_FIELD_CONV_MAX_L, FC_MAXF = REC_FIELD_CONV_MAX_F, FC_MAXE = REC_FIELD_CONV_MAX_E;
+constexpr int FC_MAXC = REC_FIELD_CONV_MAX_C, FC_MAXKW = REC_FIELD_CONV_MAX_KW;
+constexpr int FC_MAXG_BWD = REC_FIELD_CONV_BWD_GRID;   // workgroups (= workspace slots) of a backward
 constexpr size_t FC_LDS_SOFT = 64 * 1024;        // what a workgroup aims for
 constexpr size_t FC_LDS_MAX = REC_LDS_CU_BYTES;
 

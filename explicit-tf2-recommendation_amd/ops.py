@@ -8,7 +8,7 @@ import ctypes as C
 
 import torch
 
-from ._lib import lib, check, tops
+from ._lib import lib, check, tops, LIMITS
 
 EPI_NONE, EPI_BIAS, EPI_BIAS_RELU, EPI_BIAS_SIGMOID, EPI_BIAS_TANH, EPI_CROSS, EPI_ADD = range(7)
 ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH = range(4)
@@ -606,7 +606,7 @@ def ffm_bwd_rows(v, X, gz, plan):
 
 
 # ---- xDeepFM CIN (csrc/cin.hip)
-CIN_MAX_F, CIN_MAX_E, CIN_MAX_L, CIN_MAX_H = 64, 64, 8, 256
+CIN_MAX_F, CIN_MAX_E, CIN_MAX_L, CIN_MAX_H = (LIMITS["REC_CIN_MAX_" + d] for d in "FELH")
 
 
 def cin_check_shape(F, E, cin_size):
@@ -657,7 +657,7 @@ def cin_bwd(x0, states, g, Ws):
 
 
 # ---- FiBiNet SENet + bilinear interaction (csrc/fibinet.hip)
-FIBINET_MAX_F, FIBINET_MAX_E, FIBINET_MAX_C = 32, 64, 64
+FIBINET_MAX_F, FIBINET_MAX_E, FIBINET_MAX_C = (LIMITS["REC_FIBINET_MAX_" + d] for d in "FEC")
 FIBINET_TYPES = {"all": 0, "each": 1, "interaction": 2}
 
 
@@ -713,7 +713,7 @@ def fibinet_bwd(x_emb, g, A, H1, S0, S1, W, type_code):
 
 
 # ---- AutoInt multi-head field attention (csrc/autoint.hip)
-AUTOINT_MAX_F, AUTOINT_MAX_E = 64, 64
+AUTOINT_MAX_F, AUTOINT_MAX_E = (LIMITS["REC_AUTOINT_MAX_" + d] for d in "FE")
 AUTOINT_RES = {(False, False): 0, (False, True): 0, (True, False): 1, (True, True): 2}   # (use_res, res_learnable)
 
 
@@ -791,7 +791,7 @@ def autoint_bwd(x, Wq, Wk, Wv, Wres, y, dy, stats, num_heads, res, scaling, x_co
 
 
 # ---- Attentional FM, fused with the lookup (csrc/afm.hip)
-AFM_MAX_F, AFM_MAX_E, AFM_MAX_A = 64, 64, 16
+AFM_MAX_F, AFM_MAX_E, AFM_MAX_A = (LIMITS["REC_AFM_MAX_" + d] for d in "FEA")
 
 
 def afm_check_shape(F, E, A):
@@ -858,11 +858,9 @@ def emb_afm_bwd(table, X, Wa, ba, hv, bh, o, stats, dout, rows=None):
 
 
 # ---- field-conv stacks: what CCPM and FGCNN share (csrc/field_conv.h): the limits and the flat K_1 | b_1 | K_2 | ...
-CCPM_MAX_F = FGCNN_MAX_F = 64                  # fields
-CCPM_MAX_E = FGCNN_MAX_E = 64                  # embedding_dims
-CCPM_MAX_L = FGCNN_MAX_L = 3                   # layers
-CCPM_MAX_C = FGCNN_MAX_C = 16                  # filters
-CCPM_MAX_KW = FGCNN_MAX_KW = 8                 # kernel_width
+_FIELD_CONV_MAX = [LIMITS["REC_FIELD_CONV_MAX_" + d] for d in ("F", "E", "L", "C", "KW")]
+CCPM_MAX_F, CCPM_MAX_E, CCPM_MAX_L, CCPM_MAX_C, CCPM_MAX_KW = _FIELD_CONV_MAX       # fields, embedding_dims, layers,
+FGCNN_MAX_F, FGCNN_MAX_E, FGCNN_MAX_L, FGCNN_MAX_C, FGCNN_MAX_KW = _FIELD_CONV_MAX  # filters, kernel_width
 
 
 def _ints(values):
@@ -957,8 +955,8 @@ def emb_ccpm_bwd(table, X, params, filters, kernel_width, dout, rows=None):
 
 
 # ---- FGCNN: field convolutions + max pooling, every pooled map an output, fused with the lookup (csrc/fgcnn.hip)
-FGCNN_MAX_PW = 8
-FGCNN_BWD_GRID = 1024          # workgroups of the backward (FC_MAXG_BWD): beyond it a workgroup takes a second tile
+FGCNN_MAX_PW = LIMITS["REC_FGCNN_MAX_PW"]
+FGCNN_BWD_GRID = LIMITS["REC_FIELD_CONV_BWD_GRID"]   # workgroups of the backward: beyond it a workgroup takes a second tile
 
 
 def fgcnn_heights(F, pooling_width):

@@ -1,6 +1,7 @@
 """CPU checks of the drop-in boundary: the C-ABI shared library loads without a GPU, exports every symbol that
-include/mi355rec.h declares, the ctypes table binds exactly that set, and the host-side mirror keeps the reference's
-constructor keywords and error behaviour (no compute calls here: there is no GPU in this container)."""
+include/mi355rec.h declares, the ctypes table generated from the header binds exactly that set with the types the header
+spells, the shape limits the header defines are the ones the compiled library enforces, and the host-side mirror keeps
+the reference's constructor keywords and error behaviour (no compute calls here: nothing in this file needs a GPU)."""
 import ctypes
 import inspect
 import os
@@ -27,6 +28,132 @@ def test_library_exports_every_declared_symbol():
     assert not missing, missing
     assert sorted(_lib.SIGNATURES) == syms           # the binding table and the header agree, symbol for symbol
     assert _lib.lib.rec_version() >= 100
+
+
+def test_generated_signatures_match_frozen_literals():
+    """The bindings are generated from the header; these literals are not.  They are the hand-written table's entries
+    for the longest and the oddest signatures, so a parser that quietly changes a type, drops an argument or a return
+    type does not pass."""
+    from explicit_tf2_recommendation_amd import _lib
+    p, i32, i64, f32, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
+    frozen = {
+        "rec_gemm_f32": (i32, [i32, i32, i64, i64, i64, p, i64, p, i64, p, i64, i32, p, p, i64, p, i64, i32, p, p, p]),
+        "rec_emb_afm_bwd_f32": (i32, [p, i64, i32, i64, p, i64, i32, i32, p, p, p, p, p, p, p, p, p, p, p, p, p, p, sz,
+                                      p]),
+        "rec_emb_fgcnn_bwd_f32": (i32, [i32, i64, i32, i32, p, p, p, p, p, p, p, p, p, p, sz, p]),
+        "rec_dssm_fused_post_f32": (i32, [i64, i32, i32, i32, p, sz, p, p, p, p, p, p, p, p, p, p, p, p, p, p, p, i64,
+                                          i64, i64, i64, p, f32, f32, f32, p]),
+        "rec_adam_lr_t_f32": (f32, [f32, f32, f32, i64]),
+        "rec_version": (i32, []),
+        "rec_dedup_workspace_bytes": (sz, [i64]),
+    }
+    for name, want in frozen.items():
+        assert _lib.SIGNATURES[name] == want, name
+        fn = getattr(_lib.lib, name)
+        assert (fn.restype, list(fn.argtypes)) == want, name
+    res, args = _lib.SIGNATURES["rec_deepfm_fused_post_f32"]
+    assert res is i32 and len(args) == 19 and args[17] is ctypes.POINTER(_lib.DeepFMLazyAdam)
+    assert args[:17] == [i32, i64] + [p] * 14 + [i32] and args[18] is p
+    assert _lib.DeepFMLazyAdam._fields_ == [
+        ("table", p), ("ld", i64), ("V", i64), ("m_e", p), ("v_e", p), ("m_w", p), ("v_w", p), ("ld_state", i64),
+        ("ld_wstate", i64), ("lr_t_dev", p), ("b1", f32), ("b2", f32), ("eps", f32), ("last", p), ("step_dev", p)]
+
+
+def test_header_parser_is_closed_over_its_type_map():
+    """A spelling outside the header's list is an error that names the declaration, never a silent pointer or int."""
+    from explicit_tf2_recommendation_amd import _lib
+    ok = _lib.prototypes("int rec_x(const float* const* a, int32_t n, double d, size_t s); size_t rec_y(void);")
+    assert ok == {"rec_x": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_size_t]),
+                  "rec_y": (ctypes.c_size_t, [])}
+    for bad in ("int rec_x(unsigned n);", "int rec_x(long long n);", "int rec_x(hipStream_t stream);",
+                "int rec_x(my_struct* q);", "int rec_x(int);", "char* rec_x(int n);", "static int rec_x(int n);"):
+        with pytest.raises(ImportError, match="rec_x"):
+            _lib.prototypes(bad)
+    with pytest.raises(ImportError, match="field n"):
+        _lib.struct_fields("struct s { float* a; unsigned n; };", "s")
+    text = _lib.strip_comments("#define REC_A 3 // x\n/* #define REC_B 4 */\n#define REC_C (-2)\n#define REC_D 1.5\n")
+    assert _lib.constants(text) == {"REC_A": 3, "REC_C": -2}
+    assert {"REC_OK": 0, "REC_E_ARG": -1, "REC_E_UNSUPPORTED": -2, "REC_E_WORKSPACE": -3,
+            "REC_MAX_COLS": 128}.items() <= _lib.LIMITS.items()
+
+
+def _ints(*values):
+    return (ctypes.c_int * len(values))(*values)
+
+
+def _limit_cases():
+    """(define, f): f(v) = the family's rec_*_workspace_bytes with the limited size set to v and the others small."""
+    from explicit_tf2_recommendation_amd._lib import lib
+    fc = {"ccpm": lib.rec_ccpm_workspace_bytes, "fgcnn": lib.rec_fgcnn_workspace_bytes}
+    cases = [
+        ("REC_AFM_MAX_F", lambda v: lib.rec_afm_workspace_bytes(4, v, 4, 2)),
+        ("REC_AFM_MAX_E", lambda v: lib.rec_afm_workspace_bytes(4, 3, v, 2)),
+        ("REC_AFM_MAX_A", lambda v: lib.rec_afm_workspace_bytes(4, 3, 4, v)),
+        ("REC_AUTOINT_MAX_F", lambda v: lib.rec_autoint_workspace_bytes(4, v, 4, 1, 0, 0)),
+        ("REC_AUTOINT_MAX_E", lambda v: lib.rec_autoint_workspace_bytes(4, 3, v, 1, 0, 0)),
+        ("REC_FIBINET_MAX_F", lambda v: lib.rec_fibinet_workspace_bytes(4, v, 4, 2, 0)),
+        ("REC_FIBINET_MAX_E", lambda v: lib.rec_fibinet_workspace_bytes(4, 3, v, 2, 0)),
+        ("REC_CIN_MAX_F", lambda v: lib.rec_cin_workspace_bytes(4, v, 4, 1, _ints(2))),
+        ("REC_CIN_MAX_E", lambda v: lib.rec_cin_workspace_bytes(4, 3, v, 1, _ints(2))),
+        ("REC_CIN_MAX_L", lambda v: lib.rec_cin_workspace_bytes(4, 3, 4, v, _ints(*[2] * v))),
+        ("REC_CIN_MAX_H", lambda v: lib.rec_cin_workspace_bytes(4, 3, 4, 2, _ints(2, v))),
+    ]
+    for fam, ws in fc.items():            # pool = 1 is a k of CCPM's k-max pooling and a width of FGCNN's max pooling
+        cases += [
+            ("REC_FIELD_CONV_MAX_F:" + fam, lambda v, ws=ws: ws(4, v, 4, 1, _ints(2), _ints(2), _ints(1))),
+            ("REC_FIELD_CONV_MAX_E:" + fam, lambda v, ws=ws: ws(4, 3, v, 1, _ints(2), _ints(2), _ints(1))),
+            ("REC_FIELD_CONV_MAX_L:" + fam, lambda v, ws=ws: ws(4, 3, 4, v, _ints(*[2] * v), _ints(*[2] * v),
+                                                                _ints(*[1] * v))),
+            ("REC_FIELD_CONV_MAX_C:" + fam, lambda v, ws=ws: ws(4, 3, 4, 1, _ints(v), _ints(2), _ints(1))),
+            ("REC_FIELD_CONV_MAX_KW:" + fam, lambda v, ws=ws: ws(4, 3, 4, 1, _ints(2), _ints(v), _ints(1))),
+        ]
+    # 20 fields: a pooling width one past the limit still leaves two rows, so only the limit can refuse it
+    cases.append(("REC_FGCNN_MAX_PW",
+                  lambda v: lib.rec_fgcnn_workspace_bytes(4, 20, 4, 1, _ints(2), _ints(2), _ints(v))))
+    return cases
+
+
+def test_header_limits_are_the_compiled_library_s():
+    """Every shape limit include/mi355rec.h defines, against the library the kernel files were compiled into: at the
+    limit the family's workspace query answers a size, one past it 0 (unsupported).  Fails when a kernel file and the
+    header disagree, in either direction."""
+    from explicit_tf2_recommendation_amd._lib import lib, LIMITS
+    seen = set()
+    for key, f in _limit_cases():
+        name = key.split(":")[0]
+        seen.add(name)
+        limit = LIMITS[name]
+        assert f(limit) > 0, (key, limit)
+        assert f(limit + 1) == 0, (key, limit + 1)
+    # FiBiNet's workspace does not depend on the continuous features: with B == 0 the forward checks the shape and
+    # returns before it looks at a pointer or launches anything
+    def fibinet_c(c):
+        return lib.rec_fibinet_fwd_f32(None, None, None, None, None, 0, 3, 4, c, 2, 0, None, None, None, None)
+    assert fibinet_c(LIMITS["REC_FIBINET_MAX_C"]) == 0 and fibinet_c(LIMITS["REC_FIBINET_MAX_C"] + 1) == -2
+    # the backward grid of the field-conv stacks: a slot of NW = kw C + C floats per workgroup, and no more slots than
+    # the limit however many columns there are (B E / 16 columns per workgroup at the least)
+    grid = LIMITS["REC_FIELD_CONV_BWD_GRID"]
+    for ws in (lib.rec_ccpm_workspace_bytes, lib.rec_fgcnn_workspace_bytes):
+        sizes = [ws(B, 3, 16, 1, _ints(2), _ints(2), _ints(1)) for B in (1, 64 * grid, 128 * grid)]
+        assert sizes[0] < sizes[1] == sizes[2] == -(-grid * (2 * 2 + 2) * 4 // 256) * 256, sizes
+    seen |= {"REC_FIBINET_MAX_C", "REC_FIELD_CONV_BWD_GRID"}
+    status = {"REC_OK", "REC_E_ARG", "REC_E_UNSUPPORTED", "REC_E_WORKSPACE", "REC_MAX_COLS"}
+    assert seen == set(LIMITS) - status                                # a limit added to the header gets a case here
+
+
+def test_ops_limits_are_the_header_s():
+    """ops.py keeps its public names and no literal of its own: each is the header's define."""
+    from explicit_tf2_recommendation_amd import ops
+    from explicit_tf2_recommendation_amd._lib import LIMITS
+    for prefix, family, dims in (("AFM", "AFM", "FEA"), ("AUTOINT", "AUTOINT", "FE"), ("FIBINET", "FIBINET", "FEC"),
+                                 ("CIN", "CIN", "FELH"), ("CCPM", "FIELD_CONV", ("F", "E", "L", "C", "KW")),
+                                 ("FGCNN", "FIELD_CONV", ("F", "E", "L", "C", "KW")), ("FGCNN", "FGCNN", ("PW",))):
+        for d in dims:
+            assert getattr(ops, "%s_MAX_%s" % (prefix, d)) == LIMITS["REC_%s_MAX_%s" % (family, d)], (prefix, d)
+    assert ops.FGCNN_BWD_GRID == LIMITS["REC_FIELD_CONV_BWD_GRID"]
+    with pytest.raises(NotImplementedError, match="fields <= %d" % LIMITS["REC_AFM_MAX_F"]):
+        ops.afm_check_shape(LIMITS["REC_AFM_MAX_F"] + 1, 4, 2)
+    ops.afm_check_shape(LIMITS["REC_AFM_MAX_F"], 4, 2)
 
 
 def test_argument_errors_do_not_need_a_gpu():
