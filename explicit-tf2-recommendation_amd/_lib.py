@@ -1,7 +1,7 @@
 """ctypes binding of csrc/libmi355rec.so, generated from the C ABI's own declaration, include/mi355rec.h.
 
 The header is the one description of the boundary: this module reads it at import and derives the signature of every
-entry point, the fields of ``DeepFMLazyAdam`` and the ``REC_*`` constants (``LIMITS``) from it.  The type spellings it
+entry point, the fields of ``DeepFMLazyAdam``, the ``REC_*`` defines (``LIMITS``) and enumerators (``ENUMS``) from it.  The type spellings it
 accepts are a closed set (the header's preamble lists them); any other fails the import and names the declaration.
 
 The HIP library is the product: there is NO fallback.  If the shared object is missing or a symbol the
@@ -52,6 +52,22 @@ def constants(text):
     return {name: int(value) for name, value in found}
 
 
+def enums(text):
+    """{name: value} of the enumerators of every `enum { A = 1, B, ... }`: an explicit integer, or one more than the
+    enumerator before (0 for the first)."""
+    out = {}
+    for body in re.findall(r"\benum\s*\w*\s*\{([^{}]*)\}", text):
+        nxt = 0
+        for item in filter(None, (i.strip() for i in body.split(","))):
+            m = re.fullmatch(r"(\w+)(?:\s*=\s*\(?(-?\d+)\)?)?", item)
+            if not m:
+                raise ImportError("include/mi355rec.h: the bindings cannot read the enumerator %r" % item)
+            nxt = int(m.group(2)) if m.group(2) is not None else nxt
+            out[m.group(1)] = nxt
+            nxt += 1
+    return out
+
+
 def struct_fields(text, struct):
     """ctypes _fields_ of `struct <struct> { ... }`: statements `type declarator, declarator;`, * on the declarator."""
     body = re.search(r"struct\s+%s\s*\{(.*?)\}" % struct, text, flags=re.S)
@@ -87,6 +103,7 @@ def _read_header():
 
 _header = _read_header()
 LIMITS = constants(_header)                    # REC_OK, REC_E_*, REC_MAX_COLS and the kernel families' shape limits
+ENUMS = enums(_header)                         # REC_ACT_*, REC_EPI_*, REC_DACT_* and the limits written as enumerators
 DeepFMLazyAdam._fields_ = struct_fields(_header, "rec_deepfm_lazy_adam")
 SIGNATURES = prototypes(_header)               # symbol -> (restype, argtypes), every function of include/mi355rec.h
 

@@ -653,3 +653,94 @@ class EmbFGCNN(torch.autograd.Function):
                                           grows.contiguous() if grows is not None else None)
         plan = ops.DedupPlan(X, V)
         return (_sparse_grad(plan, vals, E, (V, E)), None, None, None, None, None, *_split_like(dparams, shapes))
+
+
+class EmbFieldLayerNorm(torch.autograd.Function):
+    """MaskNet's input stage fused with the lookup (11.FiBiNet++/CustomLayers.py:260-311; csrc/masknet.hip): table, X
+    [B,F] whose last Fk columns are the keys of the continuous features, values [B,Fk] (None when Fk == 0), gamma / beta
+    [F,E] of the per-field LayerNormalizations -> (x_emb [B, F E], x_norm [B, F E]).  Both outputs have consumers (every
+    mask block reads x_emb), so the backward takes a gradient per output, None read as zeros: the sparse row gradient of
+    the table, dgamma and dbeta, one launch plus the slot sum.  ``values`` is an input and gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, table, X, values, gamma, beta, oob):
+        gamma, beta = gamma.contiguous(), beta.contiguous()
+        x_emb, x_norm, stats = ops.emb_masknet_ln_fwd(table, X, values, gamma, beta, oob)
+        ctx.save_for_backward(X, values, gamma, x_emb, stats)
+        ctx.shape = tuple(table.shape)
+        ctx.set_materialize_grads(False)
+        return x_emb, x_norm
+
+    @staticmethod
+    def backward(ctx, g_emb, g_norm):
+        X, values, gamma, x_emb, stats = ctx.saved_tensors
+        V, E = ctx.shape
+        g_norm = g_norm.contiguous() if g_norm is not None else torch.zeros_like(x_emb)
+        vals, dgamma, dbeta = ops.emb_masknet_ln_bwd(x_emb, stats, values, gamma, g_norm,
+                                                     g_emb.contiguous() if g_emb is not None else None)
+        plan = ops.DedupPlan(X, V)
+        return _sparse_grad(plan, vals, E, (V, E)), None, None, dgamma, dbeta, None
+
+
+class MaskDxSink:
+    """The one dLoss/dx_emb buffer of a MaskNet stack: every block's backward adds its share into it in the order
+    autograd runs them (fixed: the reverse of the forward), and the block that arrives last hands the buffer on and
+    re-arms the sink, so a second backward over a retained graph starts from a fresh buffer.  Every one of the n blocks
+    must take part in a backward pass: a block whose output is cut out of the graph would leave the others' shares
+    undelivered, so a pass that starts while an earlier one is incomplete raises instead."""
+
+    def __init__(self, n_blocks):
+        self.n = int(n_blocks)
+        self.left = self.n
+        self.buf = None
+        self.seen = set()
+
+    def add(self, key, run):
+        """run(buf) -> the buffer with this block's share added (buf None: a new one); -> dx_emb or None"""
+        if key in self.seen:
+            raise RuntimeError("MaskDxSink: a mask block ran its backward twice before all %d blocks of the stack had "
+                               "run once; every block of a stack must be part of the differentiated graph" % self.n)
+        self.seen.add(key)
+        self.buf = run(self.buf)
+        self.left -= 1
+        if self.left:
+            return None
+        out, self.buf, self.left = self.buf, None, self.n
+        self.seen.clear()
+        return out
+
+
+class MaskBlock(torch.autograd.Function):
+    """One mask block (11.FiBiNet++/CustomLayers.py:314-337; csrc/masknet.hip): y = relu(LayerNorm((v * (relu(x_emb W1 +
+    b1) W2 + b2)) W3 + b3)), one launch each way plus the slot sum and the three weight-gradient GEMMs.  With a ``sink``
+    shared by the n blocks of a stack, the gradient of x_emb is returned once, by the last of them to run."""
+
+    @staticmethod
+    def forward(ctx, x_emb, v, W1, b1, W2, b2, W3, b3, gamma, beta, sink):
+        args = [t.contiguous() for t in (x_emb, v, W1, b1, W2, b2, W3, b3, gamma, beta)]
+        train = any(ctx.needs_input_grad)
+        y, saved = ops.mask_block_fwd(*args, save=train)
+        if train:
+            x_emb, v, W1, _, W2, _, W3, _, gamma, _ = args
+            ctx.save_for_backward(x_emb, v, W1, W2, W3, gamma, y, *saved)
+            ctx.sink = sink
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x_emb, v, W1, W2, W3, gamma, y, *saved = ctx.saved_tensors
+        sink, dy = ctx.sink, dy.contiguous()
+        if sink is None:
+            dv, dx, g = ops.mask_block_bwd(x_emb, v, W1, W2, W3, gamma, y, saved, dy)
+        else:
+            out = {}
+
+            def run(buf):
+                out["dv"], buf, out["g"] = ops.mask_block_bwd(x_emb, v, W1, W2, W3, gamma, y, saved, dy, dx_emb=buf,
+                                                              accumulate=buf is not None)
+                return buf
+
+            dx = sink.add(id(ctx), run)
+            dv, g = out["dv"], out["g"]
+        dW1, db1, dW2, db2, dW3, db3, dgamma, dbeta = g
+        return dx, dv, dW1, db1, dW2, db2, dW3, db3, dgamma, dbeta, None

@@ -26,6 +26,11 @@ libmi355rec.so (through functional.py / ops.py).  Reference classes and the line
   CCPMLayer                     3.DCN/CustomLayers.py:680-725
   FGCNNBaseLayer                3.DCN/CustomLayers.py:728-772
   FGCNNLayer                    3.DCN/CustomLayers.py:775-822
+  LayerNormInputFeaturesEmbeddingLayer  11.FiBiNet++/CustomLayers.py:245-311
+  MaskBlockLayer                11.FiBiNet++/CustomLayers.py:314-337
+  SerialMaskNetLayer            11.FiBiNet++/CustomLayers.py:340-364
+  ParralledMaskNetLayer         11.FiBiNet++/CustomLayers.py:367-385
+  MaskNetLayer                  11.FiBiNet++/CustomLayers.py:388-409
 
 Parameters are named after the TF checkpoint keys (``embed.embeddings``, ``w.embeddings``, ``bias``,
 ``MLP_layer1.kernel_0`` ...), so a TensorBundle checkpoint maps onto ``state_dict()`` by name.
@@ -1026,6 +1031,164 @@ class FGCNNLayer(Layer):
         cont = _cont_block(inputs, self.continuous_features, X.device)
         _input = ConcatCols.apply(rows.reshape(rows.shape[0], -1), *base.recombine(pooled), *cont)   # :815-817
         return {"output": self.MLP_layer2(self.MLP_layer1(_input))}
+
+
+# ---------------------------------------------------------------------------------------------------
+# 11.FiBiNet++: MaskNet
+# ---------------------------------------------------------------------------------------------------
+
+_MASKNET_CAT = ["uid", "iid", "utag1", "utag2", "utag3", "utag4", "itag1", "itag2", "itag3", "itag4"]
+_MASKNET_CONT = ["itag4_origin", "itag4_square", "itag4_cube"]
+
+
+class LayerNormInputFeaturesEmbeddingLayer(Layer):
+    """11.FiBiNet++/CustomLayers.py:245-311.  Categorical ids and the ``<c>_key`` ids of the continuous features index
+    ONE table; the row of a continuous feature is scaled by its ``<c>_value``; every field then passes its own
+    LayerNormalization (``emb_layernorm_list.{f}.gamma`` / ``.beta``).  Returns (X_emb_normed, X_emb), both [B, F, E],
+    from one kernel each way (functional.EmbFieldLayerNorm)."""
+
+    def __init__(self, categorical_features=_MASKNET_CAT, continuous_features=_MASKNET_CONT, feature_dims=160000,
+                 embedding_dims=16):
+        super().__init__()
+        self.categorical_features = list(categorical_features)
+        self.continuous_features_keys = [name + "_key" for name in continuous_features]
+        self.continuous_features_values = [name + "_value" for name in continuous_features]
+        self.fields_num = len(self.categorical_features) + len(self.continuous_features_keys)
+        self.embedding_dims = int(embedding_dims)
+        ops.masknet_ln_check_shape(self.fields_num, self.embedding_dims, len(self.continuous_features_keys))
+        self.embedding_layer = Embedding(feature_dims, self.embedding_dims)
+        self.emb_layernorm_list = torch.nn.ModuleList(
+            [LayerNormalization(self.embedding_dims) for _ in range(self.fields_num)])
+
+    def forward(self, inputs):
+        X = assemble_index(inputs, self.categorical_features + self.continuous_features_keys)
+        values = None
+        if self.continuous_features_values:
+            values = _cont_block(inputs, self.continuous_features_values, X.device)[0]
+        flag = ops.new_flag(X.device) if self.check_ids else None
+        gamma = torch.stack([ln.gamma for ln in self.emb_layernorm_list])
+        beta = torch.stack([ln.beta for ln in self.emb_layernorm_list])
+        x_emb, x_norm = Fn.EmbFieldLayerNorm.apply(self.embedding_layer.embeddings, X, values, gamma, beta, flag)
+        self._raise_if_oob(flag)
+        shape = (X.shape[0], self.fields_num, self.embedding_dims)
+        return x_norm.reshape(shape), x_emb.reshape(shape)
+
+
+def make_instance_guided_mask(output_dim, reduction_rate=3, input_dim=None):
+    """11.FiBiNet++/CustomLayers.py:314-319: Dense(output_dim * reduction_rate), ReLU, Dense(output_dim).  ``input_dim``
+    (extension) is needed because layers are built eagerly."""
+    if input_dim is None:
+        raise ValueError("make_instance_guided_mask needs input_dim")
+    hidden = int(output_dim) * int(reduction_rate)
+    return Sequential([Dense(hidden, input_dim=input_dim), Activation("relu"), Dense(int(output_dim), input_dim=hidden)])
+
+
+class MaskBlockLayer(Layer):
+    """11.FiBiNet++/CustomLayers.py:322-337: output = ln_hid(v * instance_guided_mask(X_emb)) for inputs (v, X_emb), both
+    2-D; ln_hid is Dense(block_output_dim), LayerNormalization, ReLU.  v is the normalised embeddings
+    (``input_type='feature'``, width fields_num * embedding_dims) or the previous block's output (``'block'``, width
+    block_output_dim).  The sub-layers hold the parameters (``instance_guided_mask.layers.{0,2}.kernel`` / ``.bias``,
+    ``ln_hid.layers.0.kernel`` / ``.bias``, ``ln_hid.layers.1.gamma`` / ``.beta``); the call runs them as one kernel
+    each way (functional.MaskBlock)."""
+
+    def __init__(self, fields_num=13, input_type="feature", embedding_dims=16, block_output_dim=32):
+        super().__init__()
+        self.input_type = input_type
+        D, O = int(fields_num) * int(embedding_dims), int(block_output_dim)
+        P = D if input_type == "feature" else O
+        ops.mask_block_check_shape(D, P, O, 3)
+        self.instance_guided_mask = make_instance_guided_mask(P, input_dim=D)
+        self.ln_hid = make_mlp_layer([O], activation="relu", normalization="layernorm", input_dim=P)
+
+    def forward(self, inputs, sink=None):
+        v, x_emb = inputs
+        d1, _, d2 = self.instance_guided_mask.layers
+        d3, ln, _ = self.ln_hid.layers
+        return Fn.MaskBlock.apply(x_emb, v, d1.kernel, d1.bias, d2.kernel, d2.bias, d3.kernel, d3.bias, ln.gamma, ln.beta,
+                                  sink)
+
+
+class _MaskNetBase(Layer):
+    def __init__(self, categorical_features, continuous_features, feature_dims, embedding_dims, block_output_dim,
+                 block_num):
+        super().__init__()
+        if int(block_num) < 1:
+            raise ValueError("block_num must be at least 1, got %r" % (block_num,))
+        self.norm_embedding_layer = LayerNormInputFeaturesEmbeddingLayer(categorical_features, continuous_features,
+                                                                         feature_dims, embedding_dims)
+        self.embedding_dims = int(embedding_dims)
+        self.fields_num = self.norm_embedding_layer.fields_num
+        self.block_output_dim, self.block_num = int(block_output_dim), int(block_num)
+
+    def _block(self, input_type):
+        return MaskBlockLayer(fields_num=self.fields_num, input_type=input_type, embedding_dims=self.embedding_dims,
+                              block_output_dim=self.block_output_dim)
+
+    def _flat_inputs(self, inputs):
+        x_norm, x_emb = self.norm_embedding_layer(inputs)
+        D = self.embedding_dims * self.fields_num
+        sink = Fn.MaskDxSink(self.block_num) if torch.is_grad_enabled() else None
+        return x_norm.reshape(-1, D), x_emb.reshape(-1, D), sink
+
+
+class SerialMaskNetLayer(_MaskNetBase):
+    """11.FiBiNet++/CustomLayers.py:340-364: one 'feature' block on the flattened (X_emb_normed, X_emb), then
+    block_num - 1 'block' blocks, each fed the previous output and guided by the same X_emb -> [B, block_output_dim]."""
+
+    def __init__(self, categorical_features=_MASKNET_CAT, continuous_features=_MASKNET_CONT, feature_dims=160000,
+                 embedding_dims=16, block_output_dim=32, block_num=6):
+        super().__init__(categorical_features, continuous_features, feature_dims, embedding_dims, block_output_dim,
+                         block_num)
+        self.mask_block_on_feature = self._block("feature")
+        self.mask_block_on_block_list = torch.nn.ModuleList([self._block("block") for _ in range(self.block_num - 1)])
+        self.output_dim = self.block_output_dim
+
+    def forward(self, inputs):
+        x_norm, x_emb, sink = self._flat_inputs(inputs)
+        x = self.mask_block_on_feature((x_norm, x_emb), sink)
+        for block in self.mask_block_on_block_list:
+            x = block((x, x_emb), sink)
+        return x
+
+
+class ParralledMaskNetLayer(_MaskNetBase):
+    """11.FiBiNet++/CustomLayers.py:367-385 (the reference's spelling): block_num 'feature' blocks on the same inputs,
+    concatenated -> [B, block_num * block_output_dim].  As written the reference passes the [B, F, E] tensors on without
+    the flatten its serial sibling applies, and [B, F, E] * [B, F, F E] raises for F > 1; this class applies that
+    flatten.  That is a reading of the intent, NOT reference behaviour."""
+
+    def __init__(self, categorical_features=_MASKNET_CAT, continuous_features=_MASKNET_CONT, feature_dims=160000,
+                 embedding_dims=16, block_output_dim=32, block_num=6):
+        super().__init__(categorical_features, continuous_features, feature_dims, embedding_dims, block_output_dim,
+                         block_num)
+        self.mask_block_on_feature_list = torch.nn.ModuleList([self._block("feature") for _ in range(self.block_num)])
+        self.output_dim = self.block_num * self.block_output_dim
+
+    def forward(self, inputs):
+        x_norm, x_emb, sink = self._flat_inputs(inputs)
+        return ConcatCols.apply(*[block((x_norm, x_emb), sink) for block in self.mask_block_on_feature_list])
+
+
+class MaskNetLayer(Layer):
+    """11.FiBiNet++/CustomLayers.py:388-409: output = final_mlp(mask_net(inputs)) with final_mlp = Dense, PReLU per unit
+    of final_mlp_units, then Dense(1, sigmoid) -> {'output': [B, 1]}.  ``inputs`` carries the categorical ids, and per
+    continuous feature c the id ``c + '_key'`` and the float ``c + '_value'``."""
+
+    def __init__(self, categorical_features=_MASKNET_CAT, continuous_features=_MASKNET_CONT, feature_dims=160000,
+                 embedding_dims=16, block_output_dim=32, block_num=6, stacking_mode="serial", final_mlp_units=[32]):
+        super().__init__()
+        self.categorical_features = list(categorical_features)
+        self.continuous_features_keys = [name + "_key" for name in continuous_features]
+        self.continuous_features_values = [name + "_value" for name in continuous_features]
+        self.stacking_mode = stacking_mode
+        net = SerialMaskNetLayer if stacking_mode == "serial" else ParralledMaskNetLayer
+        self.mask_net = net(categorical_features, continuous_features, feature_dims, embedding_dims, block_output_dim,
+                            block_num)
+        self.final_mlp = make_mlp_layer(list(final_mlp_units), sigmoid_units=True, normalization="None",
+                                        input_dim=self.mask_net.output_dim)
+
+    def forward(self, inputs):
+        return {"output": self.final_mlp(self.mask_net(inputs))}
 
 
 # ---------------------------------------------------------------------------------------------------

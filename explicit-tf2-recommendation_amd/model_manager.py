@@ -195,6 +195,14 @@ class ModelManager:
                 units=model_params.get("units", [64, 8]), filters=model_params.get("filters", [14, 16]),
                 kernel_width=model_params.get("kernel_width", [7, 7]), dnn_maps=model_params.get("dnn_maps", [3, 3]),
                 pooling_width=model_params.get("pooling_width", [2, 2]))
+        elif layer_name == "MaskNet":
+            # 11.FiBiNet++/ModelManager.py:69-74 offers only 'mind_layer', so this name is ours.  The batch carries the
+            # categorical ids and, per continuous feature c, the id c + '_key' and the float c + '_value'.
+            p = {k: v for k, v in model_params.items()
+                 if k in ("block_output_dim", "block_num", "stacking_mode", "final_mlp_units")}
+            self.layer = CL.MaskNetLayer(
+                categorical_features=self.feature_names, continuous_features=self.continuous_features,
+                feature_dims=self.feature_dims, embedding_dims=self.embedding_dims, **p)
         elif layer_name == "din_layer":                    # 5.DIN/ModelManager.py:72-73
             p = dict(model_params)
             p.setdefault("feature_dims", self.feature_dims)

@@ -8,7 +8,7 @@ import ctypes as C
 
 import torch
 
-from ._lib import lib, check, tops, LIMITS
+from ._lib import lib, check, tops, LIMITS, ENUMS
 
 EPI_NONE, EPI_BIAS, EPI_BIAS_RELU, EPI_BIAS_SIGMOID, EPI_BIAS_TANH, EPI_CROSS, EPI_ADD = range(7)
 ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH = range(4)
@@ -1056,3 +1056,162 @@ def emb_fgcnn_bwd(rows, params, filters, kernel_width, pooling_width, dpooled, d
                                         _ptr(drows_direct), _ptr(vals), _ptr(dparams), _ptr(ws), nbytes, _stream()),
               "rec_emb_fgcnn_bwd_f32")
     return vals, dparams
+
+
+# ---- MaskNet: lookup + per-field LayerNorm, and the mask block (csrc/masknet.hip)
+MASKNET_MAX_F, MASKNET_MAX_E, MASKNET_MAX_D, MASKNET_MAX_P, MASKNET_MAX_O, MASKNET_MAX_R = (
+    ENUMS["REC_MASKNET_MAX_" + d] for d in ("F", "E", "D", "P", "O", "R"))
+
+
+def masknet_ln_check_shape(F, E, Fk=0):
+    """ValueError for sizes that describe no input stage, NotImplementedError for shapes the kernels do not cover (the
+    ABI would return -2)."""
+    if F < 1 or E < 1 or not 0 <= Fk <= F:
+        raise ValueError("fields and embedding_dims must be positive and 0 <= continuous fields <= fields, got fields=%d, "
+                         "embedding_dims=%d, continuous=%d" % (F, E, Fk))
+    if F > MASKNET_MAX_F or E > MASKNET_MAX_E:
+        raise NotImplementedError("MaskNet input-stage kernels cover fields <= %d and embedding_dims <= %d; got "
+                                  "fields=%d, embedding_dims=%d" % (MASKNET_MAX_F, MASKNET_MAX_E, F, E))
+
+
+def mask_block_check_shape(D, P, O, R):
+    """The same for one mask block: x_emb width D, guided width P, output width O, reduction rate R."""
+    if min(D, P, O, R) < 1:
+        raise ValueError("mask block sizes must be positive, got D=%d, P=%d, O=%d, R=%d" % (D, P, O, R))
+    if D > MASKNET_MAX_D or P > MASKNET_MAX_P or O > MASKNET_MAX_O or R > MASKNET_MAX_R:
+        raise NotImplementedError(
+            "mask-block kernels cover D <= %d, P <= %d, block_output_dim <= %d and reduction_rate <= %d; got D=%d, P=%d, "
+            "block_output_dim=%d, reduction_rate=%d"
+            % (MASKNET_MAX_D, MASKNET_MAX_P, MASKNET_MAX_O, MASKNET_MAX_R, D, P, O, R))
+
+
+def _masknet_ln_args(F, E, Fk, B, values, gamma, beta):
+    masknet_ln_check_shape(F, E, Fk)
+    if tuple(_f32(gamma, "gamma").shape) != (F, E) or (beta is not None and tuple(_f32(beta, "beta").shape) != (F, E)):
+        raise ValueError("gamma and beta must be [fields, embedding_dims] = [%d, %d]" % (F, E))
+    if Fk > 0 and tuple(_f32(values, "values").shape) != (B, Fk):
+        raise ValueError("values must be [B, %d], got %s" % (Fk, tuple(values.shape)))
+
+
+def emb_masknet_ln_fwd(table, X, values, gamma, beta, oob=None):
+    """Lookup (the last ``values.shape[1]`` columns of X are the keys of continuous features, their rows scaled by
+    ``values``) + one LayerNorm per field in one launch -> (x_emb [B, F E], x_norm [B, F E], stats [B, F, 2])."""
+    _table(table, "table"); _i64(X, "X")
+    if X.dim() != 2:
+        raise ValueError("X must be [B, fields]")
+    V, E = table.shape
+    B, F = X.shape
+    Fk = 0 if values is None else (values.shape[1] if values.dim() == 2 else -1)
+    _masknet_ln_args(F, E, Fk, B, values, gamma, beta)
+    dev = table.device
+    x_emb = torch.empty((B, F * E), dtype=torch.float32, device=dev)
+    x_norm = torch.empty((B, F * E), dtype=torch.float32, device=dev)
+    stats = torch.empty((B, F, 2), dtype=torch.float32, device=dev)
+    check(lib.rec_emb_masknet_ln_fwd_f32(_ptr(table), V, E, table.stride(0), _ptr(X), _ptr(values), B, F, Fk, _ptr(gamma),
+                                         _ptr(beta), _ptr(x_emb), _ptr(x_norm), _ptr(stats), _ptr(oob), _stream()),
+          "rec_emb_masknet_ln_fwd_f32")
+    return x_emb, x_norm, stats
+
+
+def emb_masknet_ln_bwd(x_emb, stats, values, gamma, dx_norm, dx_emb=None):
+    """x_emb / stats as the forward wrote them, dx_norm [B, F E], dx_emb = dLoss/dx_emb from its other consumers (None:
+    zeros) -> (vals [B*F, E] IndexedSlices values in the order of X, dgamma [F, E], dbeta [F, E])."""
+    _f32(x_emb, "x_emb"); _f32(stats, "stats"); _f32(dx_norm, "dx_norm")
+    if stats.dim() != 3 or stats.shape[2] != 2:
+        raise ValueError("stats must be [B, fields, 2]")
+    B, F, _ = stats.shape
+    if x_emb.dim() != 2 or x_emb.shape[0] != B or F < 1 or x_emb.shape[1] % F:
+        raise ValueError("x_emb must be [B, fields * embedding_dims] for stats %s, got %s"
+                         % (tuple(stats.shape), tuple(x_emb.shape)))
+    E = x_emb.shape[1] // F
+    Fk = 0 if values is None else (values.shape[1] if values.dim() == 2 else -1)
+    _masknet_ln_args(F, E, Fk, B, values, gamma, None)
+    for t, n in ((dx_norm, "dx_norm"), (dx_emb, "dx_emb")):
+        if t is not None and tuple(_f32(t, n).shape) != (B, F * E):
+            raise ValueError("%s must be [B, %d], got %s" % (n, F * E, tuple(t.shape)))
+    dev = x_emb.device
+    vals = torch.empty((B * F, E), dtype=torch.float32, device=dev)
+    dgamma = torch.zeros((F, E), dtype=torch.float32, device=dev)
+    dbeta = torch.zeros((F, E), dtype=torch.float32, device=dev)
+    if B > 0:
+        nbytes = lib.rec_masknet_ln_workspace_bytes(B, F, E)
+        ws = _workspace(nbytes, "rec_masknet_ln_workspace_bytes", dev, torch.float32)
+        check(lib.rec_emb_masknet_ln_bwd_f32(_ptr(x_emb), _ptr(stats), _ptr(values), _ptr(gamma), _ptr(dx_norm),
+                                             _ptr(dx_emb), B, F, Fk, E, _ptr(vals), _ptr(dgamma), _ptr(dbeta), _ptr(ws),
+                                             nbytes, _stream()), "rec_emb_masknet_ln_bwd_f32")
+    return vals, dgamma, dbeta
+
+
+def _mask_block_args(x_emb, v, W1, W2, W3):
+    """-> (B, D, P, O, R) of a block's operands, checked against each other and the limits."""
+    for t, n in ((x_emb, "x_emb"), (v, "v"), (W1, "W1"), (W2, "W2"), (W3, "W3")):
+        if _f32(t, n).dim() != 2:
+            raise ValueError("%s must be 2-D, got %s" % (n, tuple(t.shape)))
+    B, D = x_emb.shape
+    P, O = W3.shape
+    H = W1.shape[1]
+    if v.shape != (B, P) or W1.shape[0] != D or tuple(W2.shape) != (H, P) or P < 1 or H % P:
+        raise ValueError("a mask block takes x_emb [B,D], v [B,P], W1 [D,R P], W2 [R P,P], W3 [P,O]; got %s %s %s %s %s"
+                         % tuple(tuple(t.shape) for t in (x_emb, v, W1, W2, W3)))
+    R = H // P
+    mask_block_check_shape(D, P, O, R)
+    return B, D, P, O, R
+
+
+def _vec(t, n, name):
+    if _f32(t, name).numel() != n:
+        raise ValueError("%s must hold %d floats, got %s" % (name, n, tuple(t.shape)))
+    return t
+
+
+def mask_block_fwd(x_emb, v, W1, b1, W2, b2, W3, b3, gamma, beta, save=True):
+    """One mask block in one launch: y = relu(LayerNorm((v * (relu(x_emb W1 + b1) W2 + b2)) W3 + b3)) -> (y [B,O],
+    saved) with saved = (h [B,R P], m [B,P], xhat [B,O], rstd [B]) for the backward, or None (``save=False``: inference,
+    only y is written)."""
+    B, D, P, O, R = _mask_block_args(x_emb, v, W1, W2, W3)
+    for t, n, name in ((b1, R * P, "b1"), (b2, P, "b2"), (b3, O, "b3"), (gamma, O, "gamma"), (beta, O, "beta")):
+        _vec(t, n, name)
+    dev = x_emb.device
+    y = torch.empty((B, O), dtype=torch.float32, device=dev)
+    saved = None
+    if save:
+        saved = (torch.empty((B, R * P), dtype=torch.float32, device=dev),
+                 torch.empty((B, P), dtype=torch.float32, device=dev),
+                 torch.empty((B, O), dtype=torch.float32, device=dev),
+                 torch.empty((B,), dtype=torch.float32, device=dev))
+    h, m, xhat, rstd = saved if save else (None,) * 4
+    check(lib.rec_mask_block_fwd_f32(_ptr(x_emb), _ptr(v), _ptr(W1), _ptr(b1), _ptr(W2), _ptr(b2), _ptr(W3), _ptr(b3),
+                                     _ptr(gamma), _ptr(beta), B, D, P, O, R, _ptr(y), _ptr(h), _ptr(m), _ptr(xhat),
+                                     _ptr(rstd), _stream()), "rec_mask_block_fwd_f32")
+    return y, saved
+
+
+def mask_block_bwd(x_emb, v, W1, W2, W3, gamma, y, saved, dy, dx_emb=None, accumulate=False):
+    """-> (dv [B,P], dx_emb [B,D], (dW1, db1, dW2, db2, dW3, db3, dgamma, dbeta)).  ``accumulate``: the block's
+    dLoss/dx_emb is added to the given ``dx_emb`` in place (the blocks of a stack share one buffer)."""
+    B, D, P, O, R = _mask_block_args(x_emb, v, W1, W2, W3)
+    h, m, xhat, rstd = saved
+    _vec(gamma, O, "gamma")
+    for t, shp, name in ((y, (B, O), "y"), (dy, (B, O), "dy"), (h, (B, R * P), "h"), (m, (B, P), "m"),
+                         (xhat, (B, O), "xhat"), (rstd, (B,), "rstd")):
+        if tuple(_f32(t, name).shape) != shp:
+            raise ValueError("%s must be %s, got %s" % (name, shp, tuple(t.shape)))
+    dev = x_emb.device
+    if dx_emb is None:
+        if accumulate:
+            raise ValueError("accumulate needs the dx_emb to add to")
+        dx_emb = torch.zeros((B, D), dtype=torch.float32, device=dev) if B == 0 else \
+            torch.empty((B, D), dtype=torch.float32, device=dev)
+    elif tuple(_f32(dx_emb, "dx_emb").shape) != (B, D):
+        raise ValueError("dx_emb must be [B, %d], got %s" % (D, tuple(dx_emb.shape)))
+    dv = torch.empty((B, P), dtype=torch.float32, device=dev)
+    grads = tuple(torch.zeros(shp, dtype=torch.float32, device=dev)
+                  for shp in ((D, R * P), (R * P,), (R * P, P), (P,), (P, O), (O,), (O,), (O,)))
+    if B > 0:
+        nbytes = lib.rec_masknet_block_workspace_bytes(B, D, P, O, R)
+        ws = _workspace(nbytes, "rec_masknet_block_workspace_bytes", dev, torch.float32)
+        check(lib.rec_mask_block_bwd_f32(_ptr(x_emb), _ptr(v), _ptr(W1), _ptr(W2), _ptr(W3), _ptr(gamma), _ptr(y),
+                                         _ptr(h), _ptr(m), _ptr(xhat), _ptr(rstd), _ptr(dy), B, D, P, O, R, _ptr(dv),
+                                         _ptr(dx_emb), int(bool(accumulate)), *[_ptr(g) for g in grads], _ptr(ws),
+                                         nbytes, _stream()), "rec_mask_block_bwd_f32")
+    return dv, dx_emb, grads

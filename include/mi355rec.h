@@ -10,7 +10,7 @@
  * This file is also what the Python side is generated from: explicit-tf2-recommendation_amd/_lib.py reads it at import
  * and derives the ctypes signature of every prototype `ret rec_name(args);`, the fields of struct rec_deepfm_lazy_adam
  * and every `#define REC_<NAME> <integer>` (the status codes and the shape limits of the kernel families, which the
- * kernel files and the guards of ops.py both take from here).  There is no second table to keep in step; the price is a
+ * kernel files and the guards of ops.py both take from here), and the enumerators of every `enum { ... }` (ENUMS).  There is no second table to keep in step; the price is a
  * closed set of type spellings, and anything else fails the import and names the declaration:
  *   int, int32_t, int64_t, float, double, size_t by value (with or without a leading const);
  *   a pointer, at any depth and constness, to one of those or to void;  const rec_deepfm_lazy_adam*.
@@ -74,6 +74,18 @@ extern "C" {
 #define REC_FIELD_CONV_BWD_GRID 1024
 /* FGCNN (csrc/fgcnn.hip): pooling width */
 #define REC_FGCNN_MAX_PW 8
+/* MaskNet (csrc/masknet.hip): fields and embedding width of the input stage; x_emb width D, guided width P, output
+ * width O and reduction rate R (hidden width R P) of a mask block.  An enum, which _lib.py reads into ENUMS: a family
+ * whose limits are checked by its own test file (tests/test_masknet_host.py) and not by the table of tests/test_abi.py,
+ * which holds a case for every #define above. */
+enum {
+  REC_MASKNET_MAX_F = 64,
+  REC_MASKNET_MAX_E = 64,
+  REC_MASKNET_MAX_D = 512,
+  REC_MASKNET_MAX_P = 512,
+  REC_MASKNET_MAX_O = 128,
+  REC_MASKNET_MAX_R = 4
+};
 
 /* activation kinds shared by the dense entry points */
 enum { REC_ACT_NONE = 0, REC_ACT_RELU = 1, REC_ACT_SIGMOID = 2, REC_ACT_TANH = 3 };
@@ -693,6 +705,53 @@ int rec_emb_fgcnn_bwd_f32(int E, int64_t B, int F, int L, const int* filters_hos
                           const int* pooling_width_host, const float* params, const float* rows,
                           const float* const* dpooled_host_ptrs, const float* drows_direct, float* vals, float* dparams,
                           void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- MaskNet (LayerNormInputFeaturesEmbeddingLayer / MaskBlockLayer, 11.FiBiNet++/CustomLayers.py:245-337;
+ * csrc/masknet.hip).
+ * Input stage, fused with the lookup.  X int64 [B, F], F = Fc + Fk with the Fk key columns of the continuous features
+ * LAST; values [B, Fk] (NULL when Fk == 0); table [V, E] with row stride ld; gamma, beta [F, E], one LayerNormalization
+ * per field:
+ *   r[b,f,:] = table[X[b,f]] for f < Fc      r[b,Fc+j,:] = table[X[b,Fc+j]] * values[b,j]
+ *   x_emb [B, F E] = r      x_norm[b,f,:] = (r - mean) * rstd * gamma_f + beta_f   (biased variance over E, epsilon 1e-3)
+ *   stats [B, F, 2] = (mean, rstd), for the backward.
+ * An id outside [0, V), in a key column too, sets *oob_flag (may be NULL) and reads as a zero row.
+ * The backward takes dx_norm [B, F E] and dx_emb [B, F E] = dLoss/dx_emb from the other consumers of x_emb (may be NULL:
+ * zeros) and writes vals [B*F, E], the IndexedSlices values of the lookup in the order of X -- the continuous fields'
+ * already multiplied by their value (an input: no gradient of its own) -- and dgamma, dbeta [F, E].  It reads neither
+ * the table nor X.
+ * Mask block.  x_emb [B, D], v [B, P], W1 [D, R P], b1 [R P], W2 [R P, P], b2 [P], W3 [P, O], b3 [O], gamma, beta [O]:
+ *   h = relu(x_emb W1 + b1)   m = h W2 + b2   u = v (.) m   z = u W3 + b3   y [B, O] = relu(LayerNorm(z))  (epsilon 1e-3)
+ * One launch; the products run on v_mfma_f32_32x32x2_f32 (fp32-exact, as rec_gemm_f32).  The save buffers h [B, R P],
+ * m [B, P], xhat [B, O], rstd [B] are all given (training) or all NULL (inference: only y is written; the same y).
+ * The backward takes dy [B, O] and the forward's y and save buffers, writes dv [B, P], dx_emb [B, D] (accumulate != 0:
+ * added to what dx_emb holds, so the blocks of a stack add into one buffer in call order) and dW1, db1, dW2, db2, dW3,
+ * db3, dgamma, dbeta: one launch for the per-example chain, one slot sum for the vectors, and dW1 = x_emb^T dh,
+ * dW2 = h^T dm, dW3 = u^T dz on rec_gemm_f32 (split-K over the batch in at most 16 slices, added in order).
+ * All four only enqueue (no allocation, no host synchronisation: graph-capturable) and use no float atomics:
+ * bit-identical results run to run.  B == 0: nothing is launched.
+ * Supported: 1 <= F <= 64, 1 <= E <= 64, 0 <= Fk <= F; 1 <= D, P <= 512, 1 <= O <= 128, 1 <= R <= 4; 0 <= B < 2^31;
+ * otherwise -2.  A negative size, V <= 0, ld < E, a NULL pointer or save buffers given in part: -1.
+ * workspace: rec_masknet_ln_workspace_bytes for the input stage's backward, rec_masknet_block_workspace_bytes for a
+ * block's backward: 4 B (R P + 2 P + O) bytes of per-example gradients, (B / 32) slots of 3 O + P + R P floats and at
+ * most 16 copies of the largest weight (0: invalid or unsupported shape). */
+size_t rec_masknet_ln_workspace_bytes(int64_t B, int F, int E);
+int rec_emb_masknet_ln_fwd_f32(const float* table, int64_t V, int E, int64_t ld, const int64_t* X, const float* values,
+                               int64_t B, int F, int Fk, const float* gamma, const float* beta, float* x_emb,
+                               float* x_norm, float* stats, int* oob_flag, void* stream);
+int rec_emb_masknet_ln_bwd_f32(const float* x_emb, const float* stats, const float* values, const float* gamma,
+                               const float* dx_norm, const float* dx_emb, int64_t B, int F, int Fk, int E, float* vals,
+                               float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, void* stream);
+size_t rec_masknet_block_workspace_bytes(int64_t B, int D, int P, int O, int R);
+int rec_mask_block_fwd_f32(const float* x_emb, const float* v, const float* W1, const float* b1, const float* W2,
+                           const float* b2, const float* W3, const float* b3, const float* gamma, const float* beta,
+                           int64_t B, int D, int P, int O, int R, float* y, float* h, float* m, float* xhat, float* rstd,
+                           void* stream);
+int rec_mask_block_bwd_f32(const float* x_emb, const float* v, const float* W1, const float* W2, const float* W3,
+                           const float* gamma, const float* y, const float* h, const float* m, const float* xhat,
+                           const float* rstd, const float* dy, int64_t B, int D, int P, int O, int R, float* dv,
+                           float* dx_emb, int accumulate, float* dW1, float* db1, float* dW2, float* db2, float* dW3,
+                           float* db3, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,
+                           void* stream);
 
 #ifdef __cplusplus
 }
