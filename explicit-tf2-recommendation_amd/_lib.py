@@ -1,8 +1,9 @@
 """ctypes binding of csrc/libmi355rec.so, generated from the C ABI's own declaration, include/mi355rec.h.
 
 The header is the one description of the boundary: this module reads it at import and derives the signature of every
-entry point, the fields of ``DeepFMLazyAdam``, the ``REC_*`` defines (``LIMITS``) and enumerators (``ENUMS``) from it.  The type spellings it
-accepts are a closed set (the header's preamble lists them); any other fails the import and names the declaration.
+entry point, the fields of ``DeepFMLazyAdam``, the ``REC_*`` defines (``LIMITS``: status codes and shape limits) and the
+enumerators (``ENUMS``: operation codes) from it.  The type spellings it accepts are a closed set (the header's preamble
+lists them); any other fails the import and names the declaration.
 
 The HIP library is the product: there is NO fallback.  If the shared object is missing or a symbol the
 header declares cannot be resolved, importing this module raises -- build it with
@@ -103,7 +104,7 @@ def _read_header():
 
 _header = _read_header()
 LIMITS = constants(_header)                    # REC_OK, REC_E_*, REC_MAX_COLS and the kernel families' shape limits
-ENUMS = enums(_header)                         # REC_ACT_*, REC_EPI_*, REC_DACT_* and the limits written as enumerators
+ENUMS = enums(_header)                         # the operation codes REC_ACT_*, REC_EPI_*, REC_DACT_* that ops.py binds
 DeepFMLazyAdam._fields_ = struct_fields(_header, "rec_deepfm_lazy_adam")
 SIGNATURES = prototypes(_header)               # symbol -> (restype, argtypes), every function of include/mi355rec.h
 

@@ -10,8 +10,9 @@ import torch
 
 from ._lib import lib, check, tops, LIMITS, ENUMS
 
-EPI_NONE, EPI_BIAS, EPI_BIAS_RELU, EPI_BIAS_SIGMOID, EPI_BIAS_TANH, EPI_CROSS, EPI_ADD = range(7)
-ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH = range(4)
+EPI_NONE, EPI_BIAS, EPI_BIAS_RELU, EPI_BIAS_SIGMOID, EPI_BIAS_TANH, EPI_CROSS, EPI_ADD = (
+    ENUMS["REC_EPI_" + k] for k in ("NONE", "BIAS", "BIAS_RELU", "BIAS_SIGMOID", "BIAS_TANH", "CROSS", "ADD"))
+ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH = (ENUMS["REC_ACT_" + k] for k in ("NONE", "RELU", "SIGMOID", "TANH"))
 ACT_CODE = {None: ACT_NONE, "linear": ACT_NONE, "relu": ACT_RELU, "sigmoid": ACT_SIGMOID, "tanh": ACT_TANH}
 EPI_OF_ACT = {ACT_NONE: EPI_BIAS, ACT_RELU: EPI_BIAS_RELU, ACT_SIGMOID: EPI_BIAS_SIGMOID, ACT_TANH: EPI_BIAS_TANH}
 
@@ -363,7 +364,8 @@ def topk_l2(queries, items, k):
 # ---------------------------------------------------------------------------------------------------
 # DIN
 # ---------------------------------------------------------------------------------------------------
-DACT_NONE, DACT_RELU, DACT_SIGMOID, DACT_TANH, DACT_DICE, DACT_PRELU = range(6)
+DACT_NONE, DACT_RELU, DACT_SIGMOID, DACT_TANH, DACT_DICE, DACT_PRELU = (
+    ENUMS["REC_DACT_" + k] for k in ("NONE", "RELU", "SIGMOID", "TANH", "DICE", "PRELU"))
 DACT_CODE = {None: DACT_NONE, "linear": DACT_NONE, "relu": DACT_RELU, "sigmoid": DACT_SIGMOID, "tanh": DACT_TANH,
              "dice": DACT_DICE, "prelu": DACT_PRELU}
 
@@ -1060,7 +1062,7 @@ def emb_fgcnn_bwd(rows, params, filters, kernel_width, pooling_width, dpooled, d
 
 # ---- MaskNet: lookup + per-field LayerNorm, and the mask block (csrc/masknet.hip)
 MASKNET_MAX_F, MASKNET_MAX_E, MASKNET_MAX_D, MASKNET_MAX_P, MASKNET_MAX_O, MASKNET_MAX_R = (
-    ENUMS["REC_MASKNET_MAX_" + d] for d in ("F", "E", "D", "P", "O", "R"))
+    LIMITS["REC_MASKNET_MAX_" + d] for d in "FEDPOR")
 
 
 def masknet_ln_check_shape(F, E, Fk=0):

@@ -9,8 +9,10 @@
  *
  * This file is also what the Python side is generated from: explicit-tf2-recommendation_amd/_lib.py reads it at import
  * and derives the ctypes signature of every prototype `ret rec_name(args);`, the fields of struct rec_deepfm_lazy_adam
- * and every `#define REC_<NAME> <integer>` (the status codes and the shape limits of the kernel families, which the
- * kernel files and the guards of ops.py both take from here), and the enumerators of every `enum { ... }` (ENUMS).  There is no second table to keep in step; the price is a
+ * and the two tables of constants.  Every `#define REC_<NAME> <integer>` goes to LIMITS: the status codes and the shape
+ * limits of the kernel families, which the kernel files and the guards of ops.py both take from here.  The enumerators
+ * of every `enum { ... }` go to ENUMS: the operation codes (REC_ACT_*, REC_EPI_*, REC_DACT_*), which the kernels switch
+ * on and ops.py binds its names to.  There is no second table to keep in step; the price is a
  * closed set of type spellings, and anything else fails the import and names the declaration:
  *   int, int32_t, int64_t, float, double, size_t by value (with or without a leading const);
  *   a pointer, at any depth and constness, to one of those or to void;  const rec_deepfm_lazy_adam*.
@@ -74,18 +76,13 @@ extern "C" {
 #define REC_FIELD_CONV_BWD_GRID 1024
 /* FGCNN (csrc/fgcnn.hip): pooling width */
 #define REC_FGCNN_MAX_PW 8
-/* MaskNet (csrc/masknet.hip): fields and embedding width of the input stage; x_emb width D, guided width P, output
- * width O and reduction rate R (hidden width R P) of a mask block.  An enum, which _lib.py reads into ENUMS: a family
- * whose limits are checked by its own test file (tests/test_masknet_host.py) and not by the table of tests/test_abi.py,
- * which holds a case for every #define above. */
-enum {
-  REC_MASKNET_MAX_F = 64,
-  REC_MASKNET_MAX_E = 64,
-  REC_MASKNET_MAX_D = 512,
-  REC_MASKNET_MAX_P = 512,
-  REC_MASKNET_MAX_O = 128,
-  REC_MASKNET_MAX_R = 4
-};
+/* MaskNet (csrc/masknet.hip): fields, embedding width; a mask block's x_emb, guided and output widths, reduction rate */
+#define REC_MASKNET_MAX_F 64
+#define REC_MASKNET_MAX_E 64
+#define REC_MASKNET_MAX_D 512
+#define REC_MASKNET_MAX_P 512
+#define REC_MASKNET_MAX_O 128
+#define REC_MASKNET_MAX_R 4
 
 /* activation kinds shared by the dense entry points */
 enum { REC_ACT_NONE = 0, REC_ACT_RELU = 1, REC_ACT_SIGMOID = 2, REC_ACT_TANH = 3 };

@@ -1,7 +1,8 @@
 """CPU checks of the drop-in boundary: the C-ABI shared library loads without a GPU, exports every symbol that
 include/mi355rec.h declares, the ctypes table generated from the header binds exactly that set with the types the header
-spells, the shape limits the header defines are the ones the compiled library enforces, and the host-side mirror keeps
-the reference's constructor keywords and error behaviour (no compute calls here: nothing in this file needs a GPU)."""
+spells, the shape limits the header defines are the ones the compiled library enforces, the operation codes ops.py binds
+are the header's enumerators, and the host-side mirror keeps the reference's constructor keywords and error behaviour (no
+compute calls here: nothing in this file needs a GPU)."""
 import ctypes
 import inspect
 import os
@@ -75,6 +76,7 @@ def test_header_parser_is_closed_over_its_type_map():
     assert _lib.constants(text) == {"REC_A": 3, "REC_C": -2}
     assert {"REC_OK": 0, "REC_E_ARG": -1, "REC_E_UNSUPPORTED": -2, "REC_E_WORKSPACE": -3,
             "REC_MAX_COLS": 128}.items() <= _lib.LIMITS.items()
+    assert _lib.enums("enum { A = 3, B, C = (-2), D };") == {"A": 3, "B": 4, "C": -2, "D": -1}
 
 
 def _ints(*values):
@@ -110,6 +112,15 @@ def _limit_cases():
     # 20 fields: a pooling width one past the limit still leaves two rows, so only the limit can refuse it
     cases.append(("REC_FGCNN_MAX_PW",
                   lambda v: lib.rec_fgcnn_workspace_bytes(4, 20, 4, 1, _ints(2), _ints(2), _ints(v))))
+    ln, blk = lib.rec_masknet_ln_workspace_bytes, lib.rec_masknet_block_workspace_bytes
+    cases += [
+        ("REC_MASKNET_MAX_F", lambda v: ln(4, v, 4)),
+        ("REC_MASKNET_MAX_E", lambda v: ln(4, 3, v)),
+        ("REC_MASKNET_MAX_D", lambda v: blk(4, v, 8, 4, 2)),
+        ("REC_MASKNET_MAX_P", lambda v: blk(4, 8, v, 4, 2)),
+        ("REC_MASKNET_MAX_O", lambda v: blk(4, 8, 8, v, 2)),
+        ("REC_MASKNET_MAX_R", lambda v: blk(4, 8, 8, 4, v)),
+    ]
     return cases
 
 
@@ -147,13 +158,36 @@ def test_ops_limits_are_the_header_s():
     from explicit_tf2_recommendation_amd._lib import LIMITS
     for prefix, family, dims in (("AFM", "AFM", "FEA"), ("AUTOINT", "AUTOINT", "FE"), ("FIBINET", "FIBINET", "FEC"),
                                  ("CIN", "CIN", "FELH"), ("CCPM", "FIELD_CONV", ("F", "E", "L", "C", "KW")),
-                                 ("FGCNN", "FIELD_CONV", ("F", "E", "L", "C", "KW")), ("FGCNN", "FGCNN", ("PW",))):
+                                 ("FGCNN", "FIELD_CONV", ("F", "E", "L", "C", "KW")), ("FGCNN", "FGCNN", ("PW",)),
+                                 ("MASKNET", "MASKNET", "FEDPOR")):
         for d in dims:
             assert getattr(ops, "%s_MAX_%s" % (prefix, d)) == LIMITS["REC_%s_MAX_%s" % (family, d)], (prefix, d)
     assert ops.FGCNN_BWD_GRID == LIMITS["REC_FIELD_CONV_BWD_GRID"]
     with pytest.raises(NotImplementedError, match="fields <= %d" % LIMITS["REC_AFM_MAX_F"]):
         ops.afm_check_shape(LIMITS["REC_AFM_MAX_F"] + 1, 4, 2)
     ops.afm_check_shape(LIMITS["REC_AFM_MAX_F"], 4, 2)
+
+
+def test_ops_codes_are_the_header_s_and_the_header_s_are_frozen():
+    """The operation codes are the header's enumerators, and ops.py binds its names to them.  The literal below is
+    deliberate: saved graphs, recorded profiles and outside callers hold these numbers, so renumbering the header fails
+    here.  Shape limits are defines (LIMITS, the tables above): none may come in as an enumerator."""
+    from explicit_tf2_recommendation_amd import ops
+    from explicit_tf2_recommendation_amd._lib import ENUMS
+    frozen = {"REC_EPI_NONE": 0, "REC_EPI_BIAS": 1, "REC_EPI_BIAS_RELU": 2, "REC_EPI_BIAS_SIGMOID": 3,
+              "REC_EPI_BIAS_TANH": 4, "REC_EPI_CROSS": 5, "REC_EPI_ADD": 6,
+              "REC_ACT_NONE": 0, "REC_ACT_RELU": 1, "REC_ACT_SIGMOID": 2, "REC_ACT_TANH": 3,
+              "REC_DACT_NONE": 0, "REC_DACT_RELU": 1, "REC_DACT_SIGMOID": 2, "REC_DACT_TANH": 3, "REC_DACT_DICE": 4,
+              "REC_DACT_PRELU": 5}
+    codes = {k: v for k, v in ENUMS.items() if k.startswith(("REC_EPI_", "REC_ACT_", "REC_DACT_"))}
+    assert codes == frozen
+    bound = {n: getattr(ops, n) for n in dir(ops)
+             if n.startswith(("EPI_", "ACT_", "DACT_")) and isinstance(getattr(ops, n), int)}
+    assert bound == {k[len("REC_"):]: v for k, v in frozen.items()}    # every code has its name in ops.py, and no other
+    for n, v in bound.items():
+        assert v == ENUMS["REC_" + n], n
+    assert not [k for k in ENUMS if k.startswith("REC_MASKNET_") or re.search(r"_MAX_\w+$", k)]
+    assert set(ENUMS) == set(frozen)                                   # an enumerator added to the header gets a line here
 
 
 def test_argument_errors_do_not_need_a_gpu():
