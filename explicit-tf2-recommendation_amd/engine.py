@@ -9,7 +9,9 @@ the host.  Gradients come out exactly as the autograd path of layers.py produces
 parameters; (uniq_ids, rows, n_uniq) for the tables) -- tests/test_gpu_engine.py holds the two paths equal.
 """
 import collections
+import contextlib
 import ctypes as C
+import gc
 import math
 import operator
 import weakref
@@ -28,6 +30,39 @@ ADAM_B1, ADAM_B2, ADAM_EPS = 0.9, 0.999, 1e-7
 # ANOTHER thread during a capture invalidates the capture and terminates the process ("operation not permitted when
 # stream is capturing") -- seen in bench.py --sharded, where graphs are captured after collectives have run.
 CAPTURE_MODE = "thread_local"
+
+
+@contextlib.contextmanager
+def _no_cyclic_gc():
+    """Collect what is dead now, then keep Python's cyclic collector off until the block ends.  For stream captures: a
+    step that is no longer used is usually part of a reference cycle (a ModelManager and the closures it hands to its
+    step), so its CUDAGraph dies whenever the collector happens to run -- in whichever thread allocates the object that
+    trips its threshold, the autograd thread of a captured backward included.  Destroying a CUDAGraph is not a
+    capture-safe operation (the ROCm build waits for the device in the destructor): with the collector firing inside
+    the captured backward of a GraphedTrainStep, built after a few managers had been dropped, the process aborts.
+    (torch.cuda.graph used to collect before every capture; it no longer does.)  Objects that die by reference
+    counting inside the block are not affected.  A caller that has switched the collector off itself (a benchmark
+    around its timed region) has already excluded the hazard: nothing is collected and nothing is changed then.
+    gc.disable() / gc.enable() act on the whole process: the collector is off for every thread while a capture runs, and
+    a thread that switches it off in the meantime finds it on again afterwards.  The train loops of this package drive
+    their steps from one thread; a program that manages the collector from several must serialise that itself."""
+    if not gc.isenabled():
+        yield
+        return
+    gc.collect()
+    gc.disable()
+    try:
+        yield
+    finally:
+        gc.enable()
+
+
+@contextlib.contextmanager
+def _capture(graph):
+    """torch.cuda.graph(graph) in this module's capture mode, with the cyclic collector out of the way."""
+    with _no_cyclic_gc():
+        with torch.cuda.graph(graph, capture_error_mode=CAPTURE_MODE):
+            yield
 
 
 def _p(t):
@@ -238,7 +273,7 @@ class _GraphPolicy:
             enqueue_all()
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode=CAPTURE_MODE):
+            with _capture(g):
                 enqueue_all()
             self._graphs[gkey] = (g,) + keep
             del self._seen[gkey]
@@ -1341,6 +1376,14 @@ class GraphedTrainStep:
             if isinstance(m, CL.Layer):
                 m.check_ids = False                          # a host read of the bounds flag cannot be captured
         self.params = [p for p in layer.parameters() if p.requires_grad]
+        # the warm-up passes run the layer in its training mode, and a module may update a buffer in place on every
+        # forward (BatchNormalization folds the batch statistics into its moving averages): building the step must leave
+        # the layer as it found it, so the buffers are saved here and written back -- in place, the capture records
+        # their addresses -- before the capture.  Capturing executes nothing: the first replay is the first fold.
+        # (This takes the layer to be BUILT: a module that registers a buffer on its first forward would have it created
+        # and folded by the warm-up with nothing to restore it from -- checked below.)
+        buffers = list(layer.buffers())
+        saved = [b.clone() for b in buffers]
         cur = torch.cuda.current_stream()
         side = torch.cuda.Stream()
         side.wait_stream(cur)
@@ -1348,11 +1391,17 @@ class GraphedTrainStep:
             for _ in range(warmup):
                 self._fwd_bwd()
         cur.wait_stream(side)
+        if [id(b) for b in layer.buffers()] != [id(b) for b in buffers]:
+            raise RuntimeError("GraphedTrainStep: the layer registered or replaced a buffer during the warm-up passes; "
+                               "build every module (input_dim=...) or run one forward before the step is built")
+        with torch.no_grad():
+            for b, s in zip(buffers, saved):
+                b.copy_(s)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
         for p in self.params:
             p.grad = None
-        with torch.cuda.graph(self.graph, capture_error_mode=CAPTURE_MODE):
+        with _capture(self.graph):
             self.loss = self._fwd_bwd()
         self.grads = [p.grad for p in self.params]           # tensors of the graph's pool: refreshed by every replay
 

@@ -408,7 +408,11 @@ class ModelManager:
         """One iteration of 2.FM/ModelManager.py:171-181 (DIN: 5.DIN/ModelManager.py:170-197, which adds the L2 term
         on the embedding rows the batch used).  Returns the loss as a DEVICE scalar (no synchronisation).
         ``next_inputs``: the batch of the next call, if the caller already has it -- its de-duplication plan is then built
-        beside this iteration (compiled DeepFM step)."""
+        beside this iteration (compiled DeepFM step).
+        This call stays lazy: with the compiled DeepFM step, table rows outside the batch keep their pending Adam
+        sweeps.  ``train_step`` and ``eval_step`` bring the tables up to date themselves; a caller that drives
+        ``train_loop`` directly must call ``sync_parameters()`` before it reads parameters (``state_dict()``,
+        checkpoint, export)."""
         if self.engine == "auto" and str(self.device).startswith("cuda"):
             pend = self.__dict__.get("_pending")
             if pend is not None and pend[0] is inputs:       # staged (and its plan prefetched) by the previous call
@@ -537,10 +541,12 @@ class ModelManager:
                 order = order[1:]
             if self._eng[0] == "fused" and order:
                 self._train_chunks(order)
+                self.sync_parameters()                       # an epoch ends with current tables: one flush launch
                 return self._metric_result()
         for i, batch_data in enumerate(order):
             nxt = order[i + 1] if i + 1 < len(order) else None                # the input pipeline knows what comes next
             self.train_loop(batch_data, next_inputs=nxt)
+        self.sync_parameters()
         return self._metric_result()
 
     @torch.no_grad()

@@ -189,3 +189,52 @@ def test_graph_policy_release(monkeypatch):
     rec.take()
     s("a")                                                   # after release a key starts over
     assert rec.take() == ["eager"]
+
+
+def test_captures_run_without_the_cyclic_collector(monkeypatch):
+    """A dead reference cycle may hold a CUDAGraph, and destroying one waits for the device -- not allowed while a
+    stream captures.  So every capture of this module first collects what is dead and keeps the cyclic collector off
+    until the capture has ended, whatever thread the captured work runs in; afterwards the collector is as it was."""
+    import gc
+    import weakref
+    from explicit_tf2_recommendation_amd import engine
+
+    class Node:
+        pass
+
+    def dead_cycle():
+        a, b = Node(), Node()
+        a.other, b.other = b, a
+        return weakref.ref(a)
+
+    rec = _Recorder(monkeypatch)
+    seen = []
+
+    class Stub(engine._GraphPolicy):
+        def __call__(self, key):
+            self._run(key, lambda: seen.append((rec.capturing is not None, gc.isenabled(), ref() is None)))
+
+    assert gc.isenabled()
+    s = Stub()
+    ref = dead_cycle()
+    s("b")
+    s("b")
+    # first sighting and the second one's own run: eager, collector untouched; inside the capture: collector off, and
+    # the cycle was collected before the capture began
+    assert [x[:2] for x in seen] == [(False, True), (False, True), (True, False)] and seen[-1][2] and gc.isenabled()
+    # a caller that keeps the collector off itself (a benchmark around its timed region) is left alone: no collection
+    del seen[:]
+    gc.disable()
+    try:
+        ref = dead_cycle()
+        s("a")
+        s("a")
+        assert gc.isenabled() is False
+    finally:
+        gc.enable()
+    assert seen == [(False, False, False)] * 2 + [(True, False, False)]
+    with pytest.raises(RuntimeError):
+        with engine._no_cyclic_gc():
+            assert not gc.isenabled()
+            raise RuntimeError("a failed capture")
+    assert gc.isenabled()

@@ -536,6 +536,77 @@ def test_keras_adam_evaluated_lazily_equals_the_dense_sweep_bit_for_bit(dist, us
     assert a(batches[2]).item() == b(batches[2]).item()
 
 
+@pytest.mark.parametrize("use_graph,multi", [(False, False), (True, False), (True, True)])
+def test_keras_adam_lazy_flush_continue_flush_equals_the_dense_sweep(use_graph, multi):
+    """flush() is what ends every epoch of the compiled DeepFM loop, so steps -> flush -> steps -> flush is the normal
+    path: after EVERY flush both tables, both moment arrays of both tables and every dense parameter must equal the
+    dense-sweep step's bit for bit, and every step's loss must be the same number.  A flush before the first step and a
+    second flush in a row change nothing.  ``multi``: the segments after the first flush run through
+    many(cur, then=nxt), four rounds of them (the first round plans its middle chunk in line; with announced plans the
+    call form is then seen once eagerly, captured at the second sighting and replayed from the third), so that in the
+    last round a flush lands between two replayed multi-step graphs.  All comparisons are exact: the lazy path replays
+    the sweep's own arithmetic (see the test above)."""
+    from explicit_tf2_recommendation_amd import engine, data
+    B, F, V = 512, 6, 6000
+    la, names, gen = make16(B, F, V, 41, "zipf")
+    lb, _, _ = make16(B, F, V, 41, "zipf")
+    lb.load_state_dict(la.state_dict())
+    a = engine.DeepFMFusedStep(la, B, gen.dims, gen.offsets, optimizer="keras_adam", lr=0.01, use_graph=False)
+    b = engine.DeepFMFusedStep(lb, B, gen.dims, gen.offsets, optimizer="keras_adam_lazy", lr=0.01, use_graph=use_graph)
+    batches = [data.to_device(gen.batch(B)) for _ in range(5)]
+
+    def same_state(where):
+        for (k, p), (_, q) in zip(la.named_parameters(), lb.named_parameters()):     # both tables and the dense ones
+            assert torch.equal(p, q), (where, k)
+        for k in ("embed.embeddings", "w.embeddings"):
+            assert torch.equal(a.state[k][0], b.state[k][0].contiguous()), (where, k, "m")
+            assert torch.equal(a.state[k][1], b.state[k][1].contiguous()), (where, k, "v")
+
+    def single(seq, where):
+        for n, i in enumerate(seq):
+            assert a(batches[i]).item() == b(batches[i]).item(), (where, n, i)
+
+    def chunk(seq, then, where):
+        want = [a(batches[i]).item() for i in seq]
+        b.many([batches[i] for i in seq], then=[batches[i] for i in then])
+        assert b.loss_steps[:len(seq)].tolist() == want, where
+
+    before = {k: p.detach().clone() for k, p in lb.named_parameters()}
+    b.flush()                                                # nothing is pending before the first step
+    for k, p in lb.named_parameters():
+        assert torch.equal(p, before[k]), k
+    assert b.t == 0 and int(b._last.max().item()) == 0
+    single([0, 1, 2], "first")
+    b.flush()
+    same_state("flush 1")
+    b.flush()                                                # idempotent
+    same_state("flush 1 again")
+    done = 3
+    for rnd in range(4 if multi else 1):
+        if multi:
+            chunk([0, 3, 3], [4, 1, 0], ("middle", rnd))
+        else:
+            single([0, 3, 3], "middle")
+        done += 3
+        stale = b._last.cpu().numpy()
+        assert ((stale > 0) & (stale < done)).any()          # the flush below has rows to bring up to date
+        b.flush()
+        assert int(b._last.min().item()) == done
+        same_state(("flush 2", rnd))
+        if multi:
+            chunk([4, 1, 0], [0, 3, 3], ("last", rnd))
+        else:
+            single([4, 1, 0], "last")
+        done += 3
+        b.flush()
+        assert int(b._last.min().item()) == done
+        same_state(("flush 3", rnd))
+    assert a.t == b.t == done and int(b._step_dev.item()) == done
+    if multi:
+        assert len(b._graphs) >= 2                           # the replay path was exercised
+    b.check_flags()
+
+
 def test_fused_lazy_adam_train_steps_replayed_from_graphs_equal_eager_ones():
     """The whole train step with the lazy Adam inside the post launch holds no per-step host scalar (the step counter and
     the bias-corrected step size live on the device), so cycles of steps are captured and replayed: parameters and
