@@ -744,3 +744,49 @@ class MaskBlock(torch.autograd.Function):
             dv, g = out["dv"], out["g"]
         dW1, db1, dW2, db2, dW3, db3, dgamma, dbeta = g
         return dx, dv, dW1, db1, dW2, db2, dW3, db3, dgamma, dbeta, None
+
+
+class EmbScaledLookup(torch.autograd.Function):
+    """ContextNet's input stage fused with the lookup (11.FiBiNet++/CustomLayers.py:492-523; csrc/contextnet.hip): table,
+    X [B,F] whose last Fk columns are the keys of the continuous features, values [B,Fk] (None when Fk == 0) -> x
+    [B, F E], the key rows multiplied by their value.  Backward: the sparse row gradient of the table, one launch plus
+    the dedup + segment sum.  ``values`` is an input and gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, table, X, values, oob):
+        x = ops.emb_contextnet_in_fwd(table, X, values, oob)
+        ctx.save_for_backward(X, values)
+        ctx.shape = tuple(table.shape)
+        return x
+
+    @staticmethod
+    def backward(ctx, g):
+        X, values = ctx.saved_tensors
+        V, E = ctx.shape
+        vals = ops.emb_contextnet_in_bwd(g.contiguous(), values, X.shape[1])
+        plan = ops.DedupPlan(X, V)
+        return _sparse_grad(plan, vals, E, (V, E)), None, None, None
+
+
+class ContextNetBlock(torch.autograd.Function):
+    """One ContextNet block (11.FiBiNet++/CustomLayers.py:412-471; csrc/contextnet.hip): x [B, F E], the contextual
+    embedding MLP Wa, ba, Wb, bb, the fields' W1 [F,E,E], W2 [F,E,E] (None: the single-matrix mode) and LayerNorm gamma,
+    beta [F,E] -> y [B, F E], one launch each way plus the slot sums, the batched per-field weight gradients and the two
+    weight-gradient GEMMs."""
+
+    @staticmethod
+    def forward(ctx, x, Wa, ba, Wb, bb, W1, W2, gamma, beta):
+        args = [t.contiguous() if t is not None else None for t in (x, Wa, ba, Wb, bb, W1, W2, gamma, beta)]
+        train = any(ctx.needs_input_grad)
+        y, saved = ops.contextnet_block_fwd(*args, save=train)
+        if train:
+            x, Wa, _, Wb, _, W1, W2, gamma, _ = args
+            ctx.save_for_backward(x, Wa, Wb, W1, W2, gamma, *saved)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, Wa, Wb, W1, W2, gamma, *saved = ctx.saved_tensors
+        dx, (dWa, dba, dWb, dbb, dW1, dW2, dgamma, dbeta) = ops.contextnet_block_bwd(x, Wa, Wb, W1, W2, gamma, saved,
+                                                                                     dy.contiguous())
+        return dx, dWa, dba, dWb, dbb, dW1, dW2, dgamma, dbeta

@@ -31,6 +31,10 @@ libmi355rec.so (through functional.py / ops.py).  Reference classes and the line
   SerialMaskNetLayer            11.FiBiNet++/CustomLayers.py:340-364
   ParralledMaskNetLayer         11.FiBiNet++/CustomLayers.py:367-385
   MaskNetLayer                  11.FiBiNet++/CustomLayers.py:388-409
+  ContextualEmbeddingLayer      11.FiBiNet++/CustomLayers.py:412-425
+  NonLinearFeedforwardLayer     11.FiBiNet++/CustomLayers.py:428-446
+  ContextNetBlockLayer          11.FiBiNet++/CustomLayers.py:449-471
+  ContextNetLayer               11.FiBiNet++/CustomLayers.py:474-531
 
 Parameters are named after the TF checkpoint keys (``embed.embeddings``, ``w.embeddings``, ``bias``,
 ``MLP_layer1.kernel_0`` ...), so a TensorBundle checkpoint maps onto ``state_dict()`` by name.
@@ -1189,6 +1193,114 @@ class MaskNetLayer(Layer):
 
     def forward(self, inputs):
         return {"output": self.final_mlp(self.mask_net(inputs))}
+
+
+# ---------------------------------------------------------------------------------------------------
+# 11.FiBiNet++: ContextNet
+# ---------------------------------------------------------------------------------------------------
+
+class ContextualEmbeddingLayer(Layer):
+    """11.FiBiNet++/CustomLayers.py:412-425: mask = reshape(contextual_embedding_transform(flatten(inputs))) with the
+    transform make_instance_guided_mask(fields_num * embedding_dims).  It holds the parameters
+    (``contextual_embedding_transform.layers.{0,2}.kernel`` / ``.bias``); ContextNetBlockLayer runs them inside its one
+    kernel, and a direct call composes the same Dense layers."""
+
+    def __init__(self, fields_num=13, embedding_dims=16):
+        super().__init__()
+        D = int(fields_num) * int(embedding_dims)
+        self.contextual_embedding_transform = make_instance_guided_mask(D, input_dim=D)
+
+    def forward(self, inputs):
+        return self.contextual_embedding_transform(inputs.reshape(inputs.shape[0], -1)).reshape(inputs.shape)
+
+
+class NonLinearFeedforwardLayer(Layer):
+    """11.FiBiNet++/CustomLayers.py:428-446: ln(relu(x W1) W2 + x) in 'pointwise' mode, ln(x W1) in any other; W1, W2
+    [E,E] TF2 glorot_normal, W2 only in pointwise mode; ``ln.gamma`` / ``ln.beta``.  It holds one field's parameters;
+    ContextNetBlockLayer runs all fields inside its one kernel; a direct call composes the same arithmetic from the GEMM,
+    activation and LayerNorm kernels."""
+
+    def __init__(self, embedding_dims=16, mode="pointwise"):
+        super().__init__()
+        E = int(embedding_dims)
+        self.W1 = torch.nn.Parameter(glorot_normal((E, E)))
+        self.ln = LayerNormalization(E)
+        self.mode = mode
+        if mode == "pointwise":
+            self.W2 = torch.nn.Parameter(glorot_normal((E, E)))
+
+    def forward(self, inputs):
+        out = Fn.LinearAct.apply(inputs, self.W1, None, ops.ACT_NONE)
+        if self.mode == "pointwise":
+            out = Fn.LinearAct.apply(Fn.FeatAct.apply(out, ops.DACT_RELU, None, None, None), self.W2, None,
+                                     ops.ACT_NONE) + inputs
+        return self.ln(out)
+
+
+class ContextNetBlockLayer(Layer):
+    """11.FiBiNet++/CustomLayers.py:449-471: mask = ce_layer(x); per field f, nonlinear_layer_list[f](x_f * mask_f);
+    stacked -> [B, F, E].  The reference builds ``ce_layer`` and ``nonlinear_layer_list`` from the first input's shape;
+    layers are built eagerly here, so ``fields_num`` and ``embedding_dims`` are extension keywords.  The sub-layers hold
+    the parameters under the reference's names; the call stacks the per-field weights and runs the block as one kernel
+    each way (functional.ContextNetBlock)."""
+
+    def __init__(self, nonlinear_type="pointwise", fields_num=13, embedding_dims=16):
+        super().__init__()
+        self.nonlinear_type = nonlinear_type
+        self.fields_num, self.embedding_dims = int(fields_num), int(embedding_dims)
+        ops.contextnet_check_shape(self.fields_num, self.embedding_dims, 3)
+        self.nonlinear_layer_list = torch.nn.ModuleList(
+            [NonLinearFeedforwardLayer(embedding_dims=self.embedding_dims, mode=nonlinear_type)
+             for _ in range(self.fields_num)])
+        self.ce_layer = ContextualEmbeddingLayer(fields_num=self.fields_num, embedding_dims=self.embedding_dims)
+
+    def forward(self, inputs):
+        F, E = self.fields_num, self.embedding_dims
+        d1, _, d2 = self.ce_layer.contextual_embedding_transform.layers
+        nl = self.nonlinear_layer_list
+        W1 = torch.stack([l.W1 for l in nl])
+        W2 = torch.stack([l.W2 for l in nl]) if self.nonlinear_type == "pointwise" else None
+        gamma, beta = torch.stack([l.ln.gamma for l in nl]), torch.stack([l.ln.beta for l in nl])
+        y = Fn.ContextNetBlock.apply(inputs.reshape(-1, F * E), d1.kernel, d1.bias, d2.kernel, d2.bias, W1, W2, gamma, beta)
+        return y.reshape(-1, F, E)
+
+
+class ContextNetLayer(Layer):
+    """11.FiBiNet++/CustomLayers.py:474-531: X = rows of the categorical ids and of the ``<c>_key`` ids out of ONE table,
+    the key rows scaled by their ``<c>_value`` (no LayerNorm, unlike MaskNet); block_num ContextNet blocks; output =
+    final_mlp(flatten(X)) with final_mlp = Dense, PReLU per unit of final_mlp_units, then Dense(1, sigmoid) ->
+    {'output': [B, 1]}."""
+
+    def __init__(self, categorical_features=_MASKNET_CAT, continuous_features=_MASKNET_CONT, feature_dims=160000,
+                 embedding_dims=16, block_num=6, final_mlp_units=[32], nonlinear_type="pointwise"):
+        super().__init__()
+        self.categorical_features = list(categorical_features)
+        self.continuous_features_keys = [name + "_key" for name in continuous_features]
+        self.continuous_features_values = [name + "_value" for name in continuous_features]
+        self.fields_num = len(self.categorical_features) + len(self.continuous_features_keys)
+        self.embedding_dims = int(embedding_dims)
+        if int(block_num) < 1:
+            raise ValueError("block_num must be at least 1, got %r" % (block_num,))
+        ops.contextnet_check_shape(self.fields_num, self.embedding_dims, 3, len(self.continuous_features_keys))
+        self.embedding_layer = Embedding(feature_dims, self.embedding_dims)
+        self.context_block_list = torch.nn.ModuleList(
+            [ContextNetBlockLayer(nonlinear_type=nonlinear_type, fields_num=self.fields_num,
+                                  embedding_dims=self.embedding_dims) for _ in range(int(block_num))])
+        self.final_mlp = make_mlp_layer(list(final_mlp_units), sigmoid_units=True, normalization="None",
+                                        input_dim=self.fields_num * self.embedding_dims)
+
+    def forward(self, inputs):
+        X = assemble_index(inputs, self.categorical_features + self.continuous_features_keys)
+        values = None
+        if self.continuous_features_values:
+            values = _cont_block(inputs, self.continuous_features_values, X.device)[0]
+        flag = ops.new_flag(X.device) if self.check_ids else None
+        x = Fn.EmbScaledLookup.apply(self.embedding_layer.embeddings, X, values, flag)
+        self._raise_if_oob(flag)
+        x = x.reshape(X.shape[0], self.fields_num, self.embedding_dims)
+        for block in self.context_block_list:
+            x = block(x)
+        return {"output": self.final_mlp(x.reshape(X.shape[0], -1))}
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -203,6 +203,12 @@ class ModelManager:
             self.layer = CL.MaskNetLayer(
                 categorical_features=self.feature_names, continuous_features=self.continuous_features,
                 feature_dims=self.feature_dims, embedding_dims=self.embedding_dims, **p)
+        elif layer_name == "ContextNet":
+            # as with MaskNet the name is ours (11.FiBiNet++/ModelManager.py offers neither) and the batch is the same
+            p = {k: v for k, v in model_params.items() if k in ("block_num", "final_mlp_units", "nonlinear_type")}
+            self.layer = CL.ContextNetLayer(
+                categorical_features=self.feature_names, continuous_features=self.continuous_features,
+                feature_dims=self.feature_dims, embedding_dims=self.embedding_dims, **p)
         elif layer_name == "din_layer":                    # 5.DIN/ModelManager.py:72-73
             p = dict(model_params)
             p.setdefault("feature_dims", self.feature_dims)

@@ -1217,3 +1217,120 @@ def mask_block_bwd(x_emb, v, W1, W2, W3, gamma, y, saved, dy, dx_emb=None, accum
                                          _ptr(dx_emb), int(bool(accumulate)), *[_ptr(g) for g in grads], _ptr(ws),
                                          nbytes, _stream()), "rec_mask_block_bwd_f32")
     return dv, dx_emb, grads
+
+
+# ---- ContextNet: lookup x value, and the block (csrc/contextnet.hip).  The limits are MaskNet's.
+def contextnet_check_shape(F, E, R=3, Fk=0):
+    """ValueError for sizes that describe no ContextNet block, NotImplementedError for shapes the kernels do not cover
+    (the ABI would return -2): fields F, embedding_dims E, reduction rate R of the contextual-embedding MLP."""
+    if F < 1 or E < 1 or R < 1 or not 0 <= Fk <= F:
+        raise ValueError("fields, embedding_dims and the reduction rate must be positive and 0 <= continuous fields <= "
+                         "fields, got fields=%d, embedding_dims=%d, reduction_rate=%d, continuous=%d" % (F, E, R, Fk))
+    if F > MASKNET_MAX_F or E > MASKNET_MAX_E or F * E > MASKNET_MAX_D or R > MASKNET_MAX_R:
+        raise NotImplementedError(
+            "ContextNet kernels cover fields <= %d, embedding_dims <= %d, fields * embedding_dims <= %d and "
+            "reduction_rate <= %d; got fields=%d, embedding_dims=%d, fields * embedding_dims=%d, reduction_rate=%d"
+            % (MASKNET_MAX_F, MASKNET_MAX_E, MASKNET_MAX_D, MASKNET_MAX_R, F, E, F * E, R))
+
+
+def _contextnet_values(values, B, F):
+    Fk = 0 if values is None else (values.shape[1] if values.dim() == 2 else -1)
+    if Fk > 0 and tuple(_f32(values, "values").shape) != (B, Fk):
+        raise ValueError("values must be [B, %d], got %s" % (Fk, tuple(values.shape)))
+    return Fk
+
+
+def emb_contextnet_in_fwd(table, X, values, oob=None):
+    """Lookup with the rows of the last ``values.shape[1]`` columns of X (the keys of continuous features) scaled by
+    ``values``, one launch -> x [B, F E]."""
+    _table(table, "table"); _i64(X, "X")
+    if X.dim() != 2:
+        raise ValueError("X must be [B, fields]")
+    V, E = table.shape
+    B, F = X.shape
+    Fk = _contextnet_values(values, B, F)
+    contextnet_check_shape(F, E, 1, Fk)
+    x = torch.empty((B, F * E), dtype=torch.float32, device=table.device)
+    check(lib.rec_emb_contextnet_in_fwd_f32(_ptr(table), V, E, table.stride(0), _ptr(X), _ptr(values), B, F, Fk, _ptr(x),
+                                            _ptr(oob), _stream()), "rec_emb_contextnet_in_fwd_f32")
+    return x
+
+
+def emb_contextnet_in_bwd(dx, values, F):
+    """dx [B, F E] = dLoss/dx -> vals [B*F, E], the IndexedSlices values in the order of X, the key fields' multiplied by
+    their value."""
+    _f32(dx, "dx")
+    if dx.dim() != 2 or F < 1 or dx.shape[1] % F:
+        raise ValueError("dx must be [B, fields * embedding_dims] with fields=%d, got %s" % (F, tuple(dx.shape)))
+    B, E = dx.shape[0], dx.shape[1] // F
+    Fk = _contextnet_values(values, B, F)
+    contextnet_check_shape(F, E, 1, Fk)
+    vals = torch.empty((B * F, E), dtype=torch.float32, device=dx.device)
+    check(lib.rec_emb_contextnet_in_bwd_f32(_ptr(values), _ptr(dx), B, F, Fk, E, _ptr(vals), _stream()),
+          "rec_emb_contextnet_in_bwd_f32")
+    return vals
+
+
+def _contextnet_block_args(x, Wa, Wb, W1, W2, gamma):
+    """-> (B, F, E, R, pointwise) of a block's operands, checked against each other and the limits.  W2 None: single
+    mode."""
+    for t, n, d in ((x, "x", 2), (Wa, "Wa", 2), (Wb, "Wb", 2), (W1, "W1", 3), (W2, "W2", 3), (gamma, "gamma", 2)):
+        if t is not None and _f32(t, n).dim() != d:
+            raise ValueError("%s must be %d-D, got %s" % (n, d, tuple(t.shape)))
+    B, D = x.shape
+    F, E = W1.shape[0], W1.shape[2]
+    H = Wa.shape[1]
+    if (F * E != D or W1.shape[1] != E or Wa.shape[0] != D or tuple(Wb.shape) != (H, D) or D < 1 or H % D
+            or (W2 is not None and W2.shape != W1.shape) or tuple(gamma.shape) != (F, E)):
+        raise ValueError("a ContextNet block takes x [B,F E], Wa [F E,R F E], Wb [R F E,F E], W1 (and W2) [F,E,E], gamma "
+                         "[F,E]; got %s" % ", ".join(str(None if t is None else tuple(t.shape))
+                                                      for t in (x, Wa, Wb, W1, W2, gamma)))
+    R = H // D
+    contextnet_check_shape(F, E, R)
+    return B, F, E, R, int(W2 is not None)
+
+
+def contextnet_block_fwd(x, Wa, ba, Wb, bb, W1, W2, gamma, beta, save=True):
+    """One ContextNet block in one launch: u = x * (relu(x Wa + ba) Wb + bb), per field r_f = relu(u_f W1_f) W2_f + u_f
+    (``W2`` None: r_f = u_f W1_f), y_f = LayerNorm_f(r_f) -> (y [B, F E], saved) with saved = (h [B,R F E], m [B,F E],
+    xhat [B,F E], rstd [B,F], a [B,F E] or None) for the backward, or None (``save=False``: inference, only y is
+    written)."""
+    B, F, E, R, pw = _contextnet_block_args(x, Wa, Wb, W1, W2, gamma)
+    D = F * E
+    for t, n, name in ((ba, R * D, "ba"), (bb, D, "bb"), (beta, D, "beta")):
+        _vec(t, n, name)
+    dev = x.device
+    new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+    y = new(B, D)
+    saved = (new(B, R * D), new(B, D), new(B, D), new(B, F), new(B, D) if pw else None) if save else None
+    h, m, xhat, rstd, a = saved if save else (None,) * 5
+    check(lib.rec_contextnet_block_fwd_f32(_ptr(x), _ptr(Wa), _ptr(ba), _ptr(Wb), _ptr(bb), _ptr(W1), _ptr(W2),
+                                           _ptr(gamma), _ptr(beta), B, F, E, R, pw, _ptr(y), _ptr(h), _ptr(m), _ptr(xhat),
+                                           _ptr(rstd), _ptr(a), _stream()), "rec_contextnet_block_fwd_f32")
+    return y, saved
+
+
+def contextnet_block_bwd(x, Wa, Wb, W1, W2, gamma, saved, dy):
+    """-> (dx [B, F E], (dWa, dba, dWb, dbb, dW1, dW2 or None, dgamma, dbeta))."""
+    B, F, E, R, pw = _contextnet_block_args(x, Wa, Wb, W1, W2, gamma)
+    D = F * E
+    h, m, xhat, rstd, a = saved
+    for t, shp, name in ((dy, (B, D), "dy"), (h, (B, R * D), "h"), (m, (B, D), "m"), (xhat, (B, D), "xhat"),
+                         (rstd, (B, F), "rstd")) + (((a, (B, D), "a"),) if pw else ()):
+        if t is None or tuple(_f32(t, name).shape) != shp:
+            raise ValueError("%s must be %s, got %s" % (name, shp, None if t is None else tuple(t.shape)))
+    dev = x.device
+    dx = torch.zeros((B, D), dtype=torch.float32, device=dev) if B == 0 else \
+        torch.empty((B, D), dtype=torch.float32, device=dev)
+    z = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)
+    dWa, dba, dWb, dbb, dW1, dW2, dg, db = (z(D, R * D), z(R * D), z(R * D, D), z(D), z(F, E, E),
+                                            z(F, E, E) if pw else None, z(F, E), z(F, E))
+    if B > 0:
+        nbytes = lib.rec_contextnet_block_workspace_bytes(B, F, E, R, pw)
+        ws = _workspace(nbytes, "rec_contextnet_block_workspace_bytes", dev, torch.float32)
+        check(lib.rec_contextnet_block_bwd_f32(_ptr(x), _ptr(Wa), _ptr(Wb), _ptr(W1), _ptr(W2), _ptr(gamma), _ptr(h),
+                                               _ptr(m), _ptr(xhat), _ptr(rstd), _ptr(a), _ptr(dy), B, F, E, R, pw,
+                                               _ptr(dx), _ptr(dWa), _ptr(dba), _ptr(dWb), _ptr(dbb), _ptr(dW1), _ptr(dW2),
+                                               _ptr(dg), _ptr(db), _ptr(ws), nbytes, _stream()),
+              "rec_contextnet_block_bwd_f32")
+    return dx, (dWa, dba, dWb, dbb, dW1, dW2, dg, db)

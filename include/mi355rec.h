@@ -750,6 +750,52 @@ int rec_mask_block_bwd_f32(const float* x_emb, const float* v, const float* W1, 
                            float* db3, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,
                            void* stream);
 
+/* ---- ContextNet (ContextualEmbeddingLayer / NonLinearFeedforwardLayer / ContextNetBlockLayer,
+ * 11.FiBiNet++/CustomLayers.py:412-531; csrc/contextnet.hip).
+ * Input stage, fused with the lookup: MaskNet's without the LayerNorm.  X int64 [B, F], F = Fc + Fk with the Fk key
+ * columns LAST; values [B, Fk] (NULL when Fk == 0); table [V, E] with row stride ld:
+ *   x[b,f,:] = table[X[b,f]] for f < Fc      x[b,Fc+j,:] = table[X[b,Fc+j]] * values[b,j]      x [B, F E]
+ * An id outside [0, V), in a key column too, sets *oob_flag (may be NULL) and reads as a zero row.  The backward takes
+ * dx [B, F E] and writes vals [B*F, E], the IndexedSlices values of the lookup in the order of X, the key fields'
+ * multiplied by their value (an input: no gradient of its own).  It reads neither the table nor X.
+ * Block.  x [B, F E], D = F E, H = R D; Wa [D, H], ba [H], Wb [H, D], bb [D]; per field W1, W2 [F, E, E] and gamma,
+ * beta [F, E]:
+ *   h = relu(x Wa + ba)   m = h Wb + bb   u = x (.) m
+ *   pointwise != 0:  a_f = relu(u_f W1_f)   r_f = a_f W2_f + u_f        pointwise == 0:  r_f = u_f W1_f   (W2 unused: NULL)
+ *   y[b,f,:] = LayerNorm(r_f) gamma_f + beta_f   (biased variance over E, epsilon 1e-3)        y [B, F E]
+ * One launch; h and m run on v_mfma_f32_32x32x2_f32 (fp32-exact, as rec_gemm_f32), the per-field products out of LDS.
+ * The save buffers h [B, H], m [B, D], xhat [B, D], rstd [B, F] and, when pointwise, a [B, D] (ignored otherwise) are
+ * all given (training) or all NULL (inference: only y is written; the same y).
+ * The backward takes dy [B, D] and the forward's save buffers and writes dx [B, D] (written, never added to) and dWa,
+ * dba, dWb, dbb, dW1, dW2 (pointwise only, else may be NULL), dgamma, dbeta: one launch for the per-example chain, one
+ * slot sum for the vectors, ONE launch for all per-field weight gradients (dW1_f = u_f^T da_f, dW2_f = a_f^T dr_f over
+ * at most 16 batch slices added in order by a second slot sum), and dWa = x^T dh, dWb = h^T dm on rec_gemm_f32 (split-K
+ * over the batch in at most 16 slices, added in order): the number of launches does not depend on F.
+ * All four only enqueue (no allocation, no host synchronisation: graph-capturable) and use no float atomics:
+ * bit-identical results run to run.  B == 0: nothing is launched.
+ * Supported: the limits are MaskNet's, this family has no constants of its own: 1 <= F <= REC_MASKNET_MAX_F,
+ * 1 <= E <= REC_MASKNET_MAX_E, F E <= REC_MASKNET_MAX_D (the input stage too: it feeds the blocks),
+ * 1 <= R <= REC_MASKNET_MAX_R, 0 <= Fk <= F, 0 <= B < 2^31; otherwise -2.  A negative size, V <= 0, ld < E, pointwise other than 0 / 1, a NULL pointer or save buffers given in
+ * part: -1.
+ * workspace (block backward only): rec_contextnet_block_workspace_bytes: 4 B (R D + 3 D, + D when pointwise) bytes of
+ * per-example gradients, (B / 32) slots of 3 D + R D floats, at most 16 copies of the per-field weights and at most 16
+ * of Wa (0: invalid or unsupported shape). */
+int rec_emb_contextnet_in_fwd_f32(const float* table, int64_t V, int E, int64_t ld, const int64_t* X,
+                                  const float* values, int64_t B, int F, int Fk, float* x, int* oob_flag, void* stream);
+int rec_emb_contextnet_in_bwd_f32(const float* values, const float* dx, int64_t B, int F, int Fk, int E, float* vals,
+                                  void* stream);
+size_t rec_contextnet_block_workspace_bytes(int64_t B, int F, int E, int R, int pointwise);
+int rec_contextnet_block_fwd_f32(const float* x, const float* Wa, const float* ba, const float* Wb, const float* bb,
+                                 const float* W1, const float* W2, const float* gamma, const float* beta, int64_t B,
+                                 int F, int E, int R, int pointwise, float* y, float* h, float* m, float* xhat,
+                                 float* rstd, float* a, void* stream);
+int rec_contextnet_block_bwd_f32(const float* x, const float* Wa, const float* Wb, const float* W1, const float* W2,
+                                 const float* gamma, const float* h, const float* m, const float* xhat,
+                                 const float* rstd, const float* a, const float* dy, int64_t B, int F, int E, int R,
+                                 int pointwise, float* dx, float* dWa, float* dba, float* dWb, float* dbb, float* dW1,
+                                 float* dW2, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,
+                                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif
