@@ -790,3 +790,62 @@ class ContextNetBlock(torch.autograd.Function):
         dx, (dWa, dba, dWb, dbb, dW1, dW2, dgamma, dbeta) = ops.contextnet_block_bwd(x, Wa, Wb, W1, W2, gamma, saved,
                                                                                      dy.contiguous())
         return dx, dWa, dba, dWb, dbb, dW1, dW2, dgamma, dbeta
+
+
+class EmbNormLookup(torch.autograd.Function):
+    """FiBiNet++'s input stage fused with the lookup (11.FiBiNet++/CustomLayers.py:78-145; csrc/fibinetplus.hip): table,
+    X [B,F] whose last Fk columns are the keys of the continuous features, values [B,Fk] (None when Fk == 0), the ONE
+    BatchNormalization of the categorical rows (gamma, beta, moving mean / variance [E]; ``training``: batch statistics,
+    the moving averages updated in place) and the key fields' LayerNormalizations (gamma, beta [Fk,E]) -> x [B, F E].
+    Backward: the sparse row gradient of the table and the four norm gradients.  ``values`` gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, table, X, values, gamma_bn, beta_bn, gamma_ln, beta_ln, moving_mean, moving_var, training, oob):
+        cg = lambda t: t.contiguous() if t is not None else None
+        gamma_bn, beta_bn, gamma_ln, beta_ln = cg(gamma_bn), cg(beta_bn), cg(gamma_ln), cg(beta_ln)
+        x, saved = ops.emb_fibinetplus_in_fwd(table, X, values, gamma_bn, beta_bn, gamma_ln, beta_ln, moving_mean,
+                                              moving_var, training, oob)
+        ctx.save_for_backward(X, values, gamma_bn, gamma_ln, *saved)
+        ctx.shape = tuple(table.shape)
+        ctx.training = bool(training)
+        ctx.has = (gamma_bn is not None, gamma_ln is not None)
+        return x
+
+    @staticmethod
+    def backward(ctx, g):
+        X, values, gamma_bn, gamma_ln, *saved = ctx.saved_tensors
+        V, E = ctx.shape
+        vals, dg_bn, db_bn, dg_ln, db_ln = ops.emb_fibinetplus_in_bwd(g.contiguous(), values, saved, gamma_bn, gamma_ln,
+                                                                      X.shape[1], ctx.training)
+        plan = ops.DedupPlan(X, V)
+        bn, ln = ctx.has
+        return (_sparse_grad(plan, vals, E, (V, E)), None, None, dg_bn if bn else None, db_bn if bn else None,
+                dg_ln if ln else None, db_ln if ln else None, None, None, None, None)
+
+
+class FiBiNetPlusBlock(torch.autograd.Function):
+    """The FiBiNet++ body (11.FiBiNet++/CustomLayers.py:170-242; csrc/fibinetplus.hip): x [B, F E], the bilinear+
+    matrices W [nW,E,E] with their reducing Dense + LayerNorm (Wr, br, gamma_q, beta_q) and SENet+'s excitation (S0, b0,
+    gamma0, beta0, S1, b1, gamma1, beta1) -> [q | x * A] [B, O + F E], one launch each way plus the slot sums, one launch
+    for all bilinear weight gradients and three weight-gradient GEMMs.  ``packed`` maps the matrices' Parameters onto one
+    [nW,E,E] array (BilinearInteractionPlusLayer.packed_weight)."""
+
+    @staticmethod
+    def forward(ctx, x, Wr, br, gq, bq, S0, b0, g0, be0, S1, b1, g1, be1, G, type_code, packed, *ws):
+        W = packed(ws).contiguous()
+        args = [t.contiguous() for t in (x, W, Wr, br, gq, bq, S0, b0, g0, be0, S1, b1, g1, be1)]
+        train = any(ctx.needs_input_grad)
+        out, saved = ops.fibinetplus_block_fwd(*args, G, type_code, save=train)
+        if train:
+            x, W, Wr, _, gq, _, S0, _, g0, be0, S1, _, g1, be1 = args
+            ctx.save_for_backward(x, W, Wr, gq, S0, g0, be0, S1, g1, be1, *saved)
+        ctx.G, ctx.type_code = G, type_code
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, W, Wr, gq, S0, g0, be0, S1, g1, be1, *saved = ctx.saved_tensors
+        dx, g = ops.fibinetplus_block_bwd(x, W, Wr, gq, S0, g0, be0, S1, g1, be1, ctx.G, ctx.type_code, saved,
+                                          dout.contiguous())
+        dW, dWr, dbr, dgq, dbq, dS0, db0, dg0, dbe0, dS1, db1, dg1, dbe1 = g
+        return (dx, dWr, dbr, dgq, dbq, dS0, db0, dg0, dbe0, dS1, db1, dg1, dbe1, None, None, None) + tuple(dW.unbind(0))

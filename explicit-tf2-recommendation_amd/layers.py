@@ -35,6 +35,10 @@ libmi355rec.so (through functional.py / ops.py).  Reference classes and the line
   NonLinearFeedforwardLayer     11.FiBiNet++/CustomLayers.py:428-446
   ContextNetBlockLayer          11.FiBiNet++/CustomLayers.py:449-471
   ContextNetLayer               11.FiBiNet++/CustomLayers.py:474-531
+  NormInputFeaturesEmbeddingLayer  11.FiBiNet++/CustomLayers.py:78-145
+  FiBiNetPlusLayer              11.FiBiNet++/CustomLayers.py:148-178
+  SENetPlusLayer                11.FiBiNet++/CustomLayers.py:181-205
+  BilinearInteractionPlusLayer  11.FiBiNet++/CustomLayers.py:208-242
 
 Parameters are named after the TF checkpoint keys (``embed.embeddings``, ``w.embeddings``, ``bias``,
 ``MLP_layer1.kernel_0`` ...), so a TensorBundle checkpoint maps onto ``state_dict()`` by name.
@@ -1304,6 +1308,154 @@ class ContextNetLayer(Layer):
 
 
 # ---------------------------------------------------------------------------------------------------
+# 11.FiBiNet++: FiBiNet++
+# ---------------------------------------------------------------------------------------------------
+
+class NormInputFeaturesEmbeddingLayer(Layer):
+    """11.FiBiNet++/CustomLayers.py:78-145.  Categorical ids and the ``<c>_key`` ids of the continuous features index ONE
+    table.  The categorical rows pass ONE BatchNormalization over the last axis of [B, Fc, E] (``emb_batchnorm.gamma`` /
+    ``.beta`` / ``.moving_mean`` / ``.moving_variance`` [E]; batch statistics and the moving-average update in training
+    mode, the moving statistics in eval mode); the row of a continuous feature is scaled by its ``<c>_value`` and passes
+    its own LayerNormalization (``emb_layernorm_list.{j}.gamma`` / ``.beta``).  Returns [B, F, E], categorical fields
+    first, from one fused call each way (functional.EmbNormLookup)."""
+
+    def __init__(self, categorical_features=_MASKNET_CAT, continuous_features=_MASKNET_CONT, feature_dims=160000,
+                 embedding_dims=16):
+        super().__init__()
+        self.categorical_features = list(categorical_features)
+        self.continuous_features_keys = [name + "_key" for name in continuous_features]
+        self.continuous_features_values = [name + "_value" for name in continuous_features]
+        self.fields_num = len(self.categorical_features) + len(self.continuous_features_keys)
+        self.embedding_dims = int(embedding_dims)
+        ops.fibinetplus_check_shape(self.fields_num, self.embedding_dims, Fk=len(self.continuous_features_keys),
+                                    min_fields=1)
+        self.embedding_layer = Embedding(feature_dims, self.embedding_dims)
+        self.emb_batchnorm = BatchNormalization(input_dim=self.embedding_dims)
+        self.emb_layernorm_list = torch.nn.ModuleList(
+            [LayerNormalization(self.embedding_dims) for _ in self.continuous_features_keys])
+
+    def forward(self, inputs):
+        X = assemble_index(inputs, self.categorical_features + self.continuous_features_keys)
+        values = gamma_ln = beta_ln = None
+        if self.continuous_features_values:
+            values = _cont_block(inputs, self.continuous_features_values, X.device)[0]
+            gamma_ln = torch.stack([ln.gamma for ln in self.emb_layernorm_list])
+            beta_ln = torch.stack([ln.beta for ln in self.emb_layernorm_list])
+        flag = ops.new_flag(X.device) if self.check_ids else None
+        bn = self.emb_batchnorm
+        x = Fn.EmbNormLookup.apply(self.embedding_layer.embeddings, X, values, bn.gamma, bn.beta, gamma_ln, beta_ln,
+                                   bn.moving_mean, bn.moving_variance, self.training, flag)
+        self._raise_if_oob(flag)
+        return x.reshape(X.shape[0], self.fields_num, self.embedding_dims)
+
+
+class SENetPlusLayer(Layer):
+    """11.FiBiNet++/CustomLayers.py:181-205: the embedding axis is split into group_num groups; per field the group
+    means then the group maxima (width 2 G F) feed excitation = make_mlp_layer([mid, F E], 'relu') with mid = max(1,
+    2 G F // reduction_ratio) (``excitation.layers.{0,3}.kernel`` / ``.bias``, ``.{1,4}.gamma`` / ``.beta``); V = inputs
+    * A, no residual and no final LayerNorm.  The reference builds the excitation from the first input's shape; layers
+    are built eagerly here, so ``input_shape`` (F, E) is an extension keyword.  FiBiNetPlusLayer runs the parameters
+    inside its one kernel; a direct call composes the same arithmetic from the GEMM, LayerNorm and activation kernels
+    plus torch for the grouping."""
+
+    def __init__(self, reduction_ratio=3, group_num=4, input_shape=None):
+        super().__init__()
+        self.reduction_ratio = reduction_ratio
+        self.group_num = group_num
+        self.built = False
+        if input_shape is not None:
+            self.build(input_shape)
+
+    def build(self, input_shape):
+        F, E, G = int(input_shape[-2]), int(input_shape[-1]), int(self.group_num)
+        self.field_num, self.embedding_size = F, E
+        if G < 1 or E % G:
+            raise ValueError("group_num must divide embedding_dims, got group_num=%r, embedding_dims=%d" % (G, E))
+        self.mid_unit_num = ops.fibinetplus_mid(F, G, self.reduction_ratio)
+        self.excitation = make_mlp_layer([self.mid_unit_num, F * E], activation="relu", input_dim=2 * G * F)
+        self.built = True
+
+    def forward(self, inputs):
+        if not self.built:
+            self.build(inputs.shape)
+            self.to(inputs.device)
+        B, F, E = inputs.shape
+        G = int(self.group_num)
+        grouped = inputs.reshape(B, F, G, E // G)
+        info = torch.cat([grouped.mean(dim=-1), grouped.max(dim=-1).values], dim=-1).reshape(B, 2 * G * F)
+        return inputs * self.excitation(info.contiguous()).reshape(B, F, E)
+
+
+class BilinearInteractionPlusLayer(BilinearInteractionLayer):
+    """11.FiBiNet++/CustomLayers.py:208-242: ONE scalar per pair, p_ij = sum((v_i W_ij) * v_j) over the pairs i < j
+    (itertools.combinations order), then reducing_layer = make_mlp_layer([output_dim], 'None'): Dense + LayerNormalization
+    and no activation (``reducing_layer.layers.0.kernel`` / ``.bias``, ``.1.gamma`` / ``.beta``).  The matrices are named
+    and packed as BilinearInteractionLayer's.  ``input_shape`` (F, E) is an extension keyword (eager build).
+    FiBiNetPlusLayer runs the parameters inside its one kernel; a direct call composes the same arithmetic from the GEMM
+    and LayerNorm kernels plus torch elementwise operations."""
+
+    def __init__(self, bilinear_type="interaction", output_dim=16, input_shape=None):
+        super().__init__(bilinear_type=bilinear_type, input_shape=None)
+        self.output_dim = int(output_dim)
+        if input_shape is not None:
+            self.build(input_shape)
+
+    def build(self, input_shape):
+        super().build(input_shape)
+        F = self.field_num
+        self.reducing_layer = make_mlp_layer([self.output_dim], activation="None", input_dim=F * (F - 1) // 2)
+
+    def forward(self, inputs):
+        if not self.built:
+            self.build(inputs.shape)
+            self.to(inputs.device)
+        F = self.field_num
+        ws = self.weights()
+        p = []
+        for t, (i, j) in enumerate((i, j) for i in range(F) for j in range(i + 1, F)):
+            w = ws[{"all": 0, "each": i, "interaction": t}[self.bilinear_type]]
+            vi = Fn.LinearAct.apply(inputs[:, i].contiguous(), w, None, ops.ACT_NONE)
+            p.append((vi * inputs[:, j]).sum(dim=1))
+        return self.reducing_layer(torch.stack(p, dim=1).contiguous())
+
+
+class FiBiNetPlusLayer(Layer):
+    """11.FiBiNet++/CustomLayers.py:148-178: X = norm_embedding_layer(inputs); output = final_mlp(concat[bilinear+(X),
+    flatten(SENet+(X))]) with final_mlp = Dense, LayerNormalization, activation per unit of final_mlp_units, then
+    Dense(1, sigmoid) -> {'output': [B, 1]}.  The input stage is one fused call each way (functional.EmbNormLookup), the
+    two sub-layers and the concatenation one kernel each way (functional.FiBiNetPlusBlock); the head runs on the GEMM,
+    LayerNorm and activation kernels."""
+
+    def __init__(self, categorical_features=_MASKNET_CAT, continuous_features=_MASKNET_CONT, feature_dims=160000,
+                 embedding_dims=16, bilinear_type="interaction", bilinear_output_dim=16, senet_reduction_ratio=3,
+                 senet_group_num=2, final_mlp_units=[32], final_mlp_activation="ReLU"):
+        super().__init__()
+        F = len(categorical_features) + len(continuous_features)
+        E, G, O = int(embedding_dims), int(senet_group_num), int(bilinear_output_dim)
+        if bilinear_type not in ops.FIBINET_TYPES:
+            raise NotImplementedError
+        ops.fibinetplus_check_shape(F, E, G, ops.fibinetplus_mid(F, max(G, 1), senet_reduction_ratio) if G >= 1 else 1,
+                                    O, len(continuous_features))
+        self.norm_embedding_layer = NormInputFeaturesEmbeddingLayer(categorical_features, continuous_features,
+                                                                    feature_dims, E)
+        self.bilinear_interaction_plus_layer = BilinearInteractionPlusLayer(bilinear_type, O, input_shape=(F, E))
+        self.senet_plus_layer = SENetPlusLayer(senet_reduction_ratio, G, input_shape=(F, E))
+        # Keras spells the layer class 'ReLU'; the activation kernels know it as 'relu'
+        act = "relu" if final_mlp_activation == "ReLU" else final_mlp_activation
+        self.final_mlp = make_mlp_layer(list(final_mlp_units), activation=act, sigmoid_units=True, input_dim=O + F * E)
+
+    def forward(self, inputs):
+        x = self.norm_embedding_layer(inputs)
+        bil, se = self.bilinear_interaction_plus_layer, self.senet_plus_layer
+        red, ex = bil.reducing_layer.layers, se.excitation.layers
+        out = Fn.FiBiNetPlusBlock.apply(x.reshape(x.shape[0], -1), red[0].kernel, red[0].bias, red[1].gamma, red[1].beta,
+                                        ex[0].kernel, ex[0].bias, ex[1].gamma, ex[1].beta, ex[3].kernel, ex[3].bias,
+                                        ex[4].gamma, ex[4].beta, int(se.group_num), bil.type_code, bil.packed_weight,
+                                        *bil.weights())
+        return {"output": self.final_mlp(out)}
+
+
+# ---------------------------------------------------------------------------------------------------
 # 5.DIN
 # ---------------------------------------------------------------------------------------------------
 
@@ -1428,7 +1580,7 @@ def make_mlp_layer(units, activation="PReLU", normalization="layernorm", softmax
             if isinstance(activation, (Dice, PReLU)) and not activation.built:
                 activation.build(d)
             seq.append(Activation(activation))
-        else:
+        elif activation != "None":                       # the reference's spelling of "no activation layer"
             seq.append(Activation(activation))
     if softmax_units > 0:
         seq.append(SoftmaxDense(softmax_units, d))

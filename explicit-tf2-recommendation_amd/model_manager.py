@@ -209,6 +209,14 @@ class ModelManager:
             self.layer = CL.ContextNetLayer(
                 categorical_features=self.feature_names, continuous_features=self.continuous_features,
                 feature_dims=self.feature_dims, embedding_dims=self.embedding_dims, **p)
+        elif layer_name == "FiBiNetPlus":
+            # the third model of 11.FiBiNet++/CustomLayers.py (148-178); the name is ours and the batch is MaskNet's
+            p = {k: v for k, v in model_params.items()
+                 if k in ("bilinear_type", "bilinear_output_dim", "senet_reduction_ratio", "senet_group_num",
+                          "final_mlp_units", "final_mlp_activation")}
+            self.layer = CL.FiBiNetPlusLayer(
+                categorical_features=self.feature_names, continuous_features=self.continuous_features,
+                feature_dims=self.feature_dims, embedding_dims=self.embedding_dims, **p)
         elif layer_name == "din_layer":                    # 5.DIN/ModelManager.py:72-73
             p = dict(model_params)
             p.setdefault("feature_dims", self.feature_dims)

@@ -1334,3 +1334,171 @@ def contextnet_block_bwd(x, Wa, Wb, W1, W2, gamma, saved, dy):
                                                _ptr(dg), _ptr(db), _ptr(ws), nbytes, _stream()),
               "rec_contextnet_block_bwd_f32")
     return dx, (dWa, dba, dWb, dbb, dW1, dW2, dg, db)
+
+
+# ---- FiBiNet++: lookup x value + BatchNorm / per-field LayerNorm, and the SENet+ / bilinear+ block (csrc/fibinetplus.hip).
+# The limits are FiBiNet's and MaskNet's.
+def fibinetplus_check_shape(F, E, G=1, mid=1, O=1, Fk=0, min_fields=2):
+    """ValueError for sizes that describe no FiBiNet++ layer, NotImplementedError for shapes the kernels do not cover
+    (the ABI would return -2): fields F, embedding_dims E, SENet+ groups G and hidden units mid, bilinear+ output
+    width O, continuous fields Fk.  The body needs a pair of fields (``min_fields`` 2), the input stage one."""
+    if min(F, E, G, mid, O) < 1 or not 0 <= Fk <= F or E % G:
+        raise ValueError("fields, embedding_dims, groups, SENet units and the bilinear output width must be positive, the "
+                         "groups divide embedding_dims and 0 <= continuous fields <= fields; got fields=%d, "
+                         "embedding_dims=%d, groups=%d, SENet units=%d, output width=%d, continuous=%d"
+                         % (F, E, G, mid, O, Fk))
+    if not (min_fields <= F <= FIBINET_MAX_F and E <= FIBINET_MAX_E and F * E <= MASKNET_MAX_D and O <= MASKNET_MAX_O
+            and mid <= MASKNET_MAX_P):
+        raise NotImplementedError(
+            "FiBiNet++ kernels cover %d <= fields <= %d, embedding_dims <= %d, fields * embedding_dims <= %d, bilinear "
+            "output width <= %d and SENet units <= %d; got fields=%d, embedding_dims=%d, fields * embedding_dims=%d, "
+            "output width=%d, SENet units=%d"
+            % (min_fields, FIBINET_MAX_F, FIBINET_MAX_E, MASKNET_MAX_D, MASKNET_MAX_O, MASKNET_MAX_P, F, E, F * E, O, mid))
+
+
+def fibinetplus_mid(F, G, reduction_ratio):
+    """SENetPlusLayer's hidden width (11.FiBiNet++/CustomLayers.py:191)."""
+    return max(1, 2 * G * F // reduction_ratio)
+
+
+def _fibinetplus_in_args(B, F, E, values, gamma_bn, gamma_ln):
+    Fk = _contextnet_values(values, B, F)
+    if not 0 <= Fk <= F:
+        raise ValueError("values must be [B, continuous fields <= %d], got %s" % (F, tuple(values.shape)))
+    fibinetplus_check_shape(F, E, Fk=Fk, min_fields=1)
+    if Fk < F:
+        _vec(gamma_bn, E, "gamma_bn")
+    if Fk > 0 and tuple(_f32(gamma_ln, "gamma_ln").shape) != (Fk, E):
+        raise ValueError("gamma_ln must be [%d, %d], got %s" % (Fk, E, tuple(gamma_ln.shape)))
+    return Fk
+
+
+def emb_fibinetplus_in_fwd(table, X, values, gamma_bn, beta_bn, gamma_ln, beta_ln, moving_mean, moving_var, training,
+                           oob=None, save=True):
+    """Lookup, x value on the last ``values.shape[1]`` columns of X, ONE BatchNorm over the categorical rows (training:
+    batch statistics and the moving averages updated on the device; else the moving statistics) and a LayerNorm per key
+    field -> (x [B, F E], saved) with saved = (xhat [B, F E], rstd_bn [E], rstd_ln [B, Fk]) or None (``save=False``)."""
+    _table(table, "table"); _i64(X, "X")
+    if X.dim() != 2:
+        raise ValueError("X must be [B, fields]")
+    V, E = table.shape
+    B, F = X.shape
+    Fk = _fibinetplus_in_args(B, F, E, values, gamma_bn, gamma_ln)
+    if Fk < F:
+        for t, name in ((beta_bn, "beta_bn"), (moving_mean, "moving_mean"), (moving_var, "moving_var")):
+            _vec(t, E, name)
+    if Fk > 0:
+        _vec(beta_ln, Fk * E, "beta_ln")
+    dev = table.device
+    new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+    x = new(B, F * E)
+    saved = (new(B, F * E), new(E), new(B, max(Fk, 1))) if save else None
+    xhat, rstd_bn, rstd_ln = saved if save else (None,) * 3
+    if B > 0:
+        nbytes = lib.rec_emb_fibinetplus_in_workspace_bytes(B, F, Fk, E)
+        ws = _workspace(nbytes, "rec_emb_fibinetplus_in_workspace_bytes", dev, torch.float32)
+        check(lib.rec_emb_fibinetplus_in_fwd_f32(_ptr(table), V, E, table.stride(0), _ptr(X), _ptr(values),
+                                                 _ptr(gamma_bn), _ptr(beta_bn), _ptr(gamma_ln), _ptr(beta_ln), B, F, Fk,
+                                                 int(bool(training)), _ptr(moving_mean), _ptr(moving_var), _ptr(x),
+                                                 _ptr(xhat), _ptr(rstd_bn), _ptr(rstd_ln), _ptr(oob), _ptr(ws), nbytes,
+                                                 _stream()), "rec_emb_fibinetplus_in_fwd_f32")
+    return x, saved
+
+
+def emb_fibinetplus_in_bwd(dx, values, saved, gamma_bn, gamma_ln, F, training):
+    """dx [B, F E] = dLoss/dx -> (vals [B*F, E], the IndexedSlices values in the order of X with the key fields'
+    multiplied by their value, dgamma_bn [E], dbeta_bn [E], dgamma_ln [Fk, E], dbeta_ln [Fk, E])."""
+    _f32(dx, "dx")
+    if dx.dim() != 2 or F < 1 or dx.shape[1] % F:
+        raise ValueError("dx must be [B, fields * embedding_dims] with fields=%d, got %s" % (F, tuple(dx.shape)))
+    B, E = dx.shape[0], dx.shape[1] // F
+    Fk = _fibinetplus_in_args(B, F, E, values, gamma_bn, gamma_ln)
+    xhat, rstd_bn, rstd_ln = saved
+    if tuple(_f32(xhat, "xhat").shape) != (B, F * E):
+        raise ValueError("xhat must be %s, got %s" % ((B, F * E), tuple(xhat.shape)))
+    _vec(rstd_bn, E, "rstd_bn"); _vec(rstd_ln, B * max(Fk, 1), "rstd_ln")
+    dev = dx.device
+    z = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)
+    # every output the call writes in full starts uninitialised; what it leaves alone (an empty batch, no field of a
+    # kind) is zeros
+    e = lambda on, *s: torch.empty(s, dtype=torch.float32, device=dev) if on and B > 0 else z(*s)
+    vals = e(True, B * F, E)
+    dg_bn, db_bn, dg_ln, db_ln = e(Fk < F, E), e(Fk < F, E), e(Fk > 0, Fk, E), e(Fk > 0, Fk, E)
+    if B > 0:
+        nbytes = lib.rec_emb_fibinetplus_in_workspace_bytes(B, F, Fk, E)
+        ws = _workspace(nbytes, "rec_emb_fibinetplus_in_workspace_bytes", dev, torch.float32)
+        check(lib.rec_emb_fibinetplus_in_bwd_f32(_ptr(dx), _ptr(values), _ptr(xhat), _ptr(rstd_bn), _ptr(rstd_ln),
+                                                 _ptr(gamma_bn), _ptr(gamma_ln), B, F, Fk, E, int(bool(training)),
+                                                 _ptr(vals), _ptr(dg_bn), _ptr(db_bn), _ptr(dg_ln), _ptr(db_ln), _ptr(ws),
+                                                 nbytes, _stream()), "rec_emb_fibinetplus_in_bwd_f32")
+    return vals, dg_bn, db_bn, dg_ln, db_ln
+
+
+def _fibinetplus_block_args(x, W, Wr, S0, S1, G, type_code):
+    """-> (B, F, E, G, mid, O, type) of a block's operands, checked against each other and the limits."""
+    for t, n, d in ((x, "x", 2), (W, "W", 3), (Wr, "Wr", 2), (S0, "S0", 2), (S1, "S1", 2)):
+        if _f32(t, n).dim() != d:
+            raise ValueError("%s must be %d-D, got %s" % (n, d, tuple(t.shape)))
+    B, D = x.shape
+    nW, E = W.shape[0], W.shape[2]
+    P, O = Wr.shape
+    mid = S0.shape[1]
+    F = D // E if E > 0 and D % E == 0 else -1
+    G = int(G)
+    if type_code not in FIBINET_TYPES.values():
+        raise ValueError("type_code must be one of %s, got %r" % (sorted(FIBINET_TYPES.values()), type_code))
+    name = [k for k, v in FIBINET_TYPES.items() if v == type_code][0]
+    if (F < 2 or W.shape[1] != E or P != F * (F - 1) // 2 or nW != fibinet_num_weights(F, name) or G < 1 or E % G
+            or S0.shape[0] != 2 * G * F or tuple(S1.shape) != (mid, D) or min(mid, O) < 1):
+        raise ValueError("a FiBiNet++ block takes x [B,F E], W [nW,E,E], Wr [F(F-1)/2,O], S0 [2 G F,mid], S1 [mid,F E] "
+                         "with G dividing E; got %s, G=%d" % (", ".join(str(tuple(t.shape)) for t in (x, W, Wr, S0, S1)),
+                                                              G))
+    fibinetplus_check_shape(F, E, G, mid, O)
+    return B, F, E, G, mid, O, int(type_code)
+
+
+def fibinetplus_block_fwd(x, W, Wr, br, gq, bq, S0, b0, g0, be0, S1, b1, g1, be1, G, type_code, save=True):
+    """The FiBiNet++ body in one launch: q = LN(p Wr + br) with p the pair scalars x_i W x_j^T, v = x * relu(LN(relu(LN(
+    s S0 + b0)) S1 + b1)) with s the group means and maxima -> (out [B, O + F E] = [q | v], saved) with saved = (p,
+    xhat_q, s, xhat0, h, xhat1, rstd [B,3]) for the backward, or None (``save=False``: inference, only out is
+    written)."""
+    B, F, E, G, mid, O, tc = _fibinetplus_block_args(x, W, Wr, S0, S1, G, type_code)
+    D, P = F * E, F * (F - 1) // 2
+    for t, n, name in ((br, O, "br"), (gq, O, "gamma_q"), (bq, O, "beta_q"), (b0, mid, "b0"), (g0, mid, "gamma0"),
+                       (be0, mid, "beta0"), (b1, D, "b1"), (g1, D, "gamma1"), (be1, D, "beta1")):
+        _vec(t, n, name)
+    dev = x.device
+    new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+    out = new(B, O + D)
+    saved = (new(B, P), new(B, O), new(B, 2 * G * F), new(B, mid), new(B, mid), new(B, D), new(B, 3)) if save else None
+    sv = saved if save else (None,) * 7
+    check(lib.rec_fibinetplus_block_fwd_f32(_ptr(x), _ptr(W), _ptr(Wr), _ptr(br), _ptr(gq), _ptr(bq), _ptr(S0), _ptr(b0),
+                                            _ptr(g0), _ptr(be0), _ptr(S1), _ptr(b1), _ptr(g1), _ptr(be1), B, F, E, G, mid,
+                                            O, tc, _ptr(out), *[_ptr(t) for t in sv], _stream()),
+          "rec_fibinetplus_block_fwd_f32")
+    return out, saved
+
+
+def fibinetplus_block_bwd(x, W, Wr, gq, S0, g0, be0, S1, g1, be1, G, type_code, saved, dout):
+    """-> (dx [B, F E], (dW, dWr, dbr, dgamma_q, dbeta_q, dS0, db0, dgamma0, dbeta0, dS1, db1, dgamma1, dbeta1))."""
+    B, F, E, G, mid, O, tc = _fibinetplus_block_args(x, W, Wr, S0, S1, G, type_code)
+    D, P = F * E, F * (F - 1) // 2
+    shapes = ((B, P), (B, O), (B, 2 * G * F), (B, mid), (B, mid), (B, D), (B, 3))
+    names = ("p", "xhat_q", "s", "xhat0", "h", "xhat1", "rstd")
+    for t, shp, name in tuple(zip(saved, shapes, names)) + ((dout, (B, O + D), "dout"),):
+        if t is None or tuple(_f32(t, name).shape) != shp:
+            raise ValueError("%s must be %s, got %s" % (name, shp, None if t is None else tuple(t.shape)))
+    dev = x.device
+    # the call writes every output in full; an empty batch launches nothing and leaves zeros
+    z = lambda *s: (torch.zeros if B == 0 else torch.empty)(s, dtype=torch.float32, device=dev)
+    dx = z(B, D)
+    grads = (z(*W.shape), z(P, O), z(O), z(O), z(O), z(2 * G * F, mid), z(mid), z(mid), z(mid), z(mid, D), z(D), z(D),
+             z(D))
+    if B > 0:
+        nbytes = lib.rec_fibinetplus_block_workspace_bytes(B, F, E, G, mid, O, tc)
+        ws = _workspace(nbytes, "rec_fibinetplus_block_workspace_bytes", dev, torch.float32)
+        check(lib.rec_fibinetplus_block_bwd_f32(_ptr(x), _ptr(W), _ptr(Wr), _ptr(gq), _ptr(S0), _ptr(g0), _ptr(be0),
+                                                _ptr(S1), _ptr(g1), _ptr(be1), *[_ptr(t) for t in saved], _ptr(dout), B,
+                                                F, E, G, mid, O, tc, _ptr(dx), *[_ptr(t) for t in grads], _ptr(ws),
+                                                nbytes, _stream()), "rec_fibinetplus_block_bwd_f32")
+    return dx, grads

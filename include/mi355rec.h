@@ -796,6 +796,76 @@ int rec_contextnet_block_bwd_f32(const float* x, const float* Wa, const float* W
                                  float* dW2, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,
                                  void* stream);
 
+/* ---- FiBiNet++ (NormInputFeaturesEmbeddingLayer / SENetPlusLayer / BilinearInteractionPlusLayer / FiBiNetPlusLayer,
+ * 11.FiBiNet++/CustomLayers.py:78-242; csrc/fibinetplus.hip).
+ * Input stage, fused with the lookup.  X int64 [B, F], F = Fc + Fk with the Fk key columns LAST; values [B, Fk] (NULL
+ * when Fk == 0); table [V, E] with row stride ld:
+ *   f < Fc:   x[b,f,:] = BatchNorm(table[X[b,f]])  ONE Keras BatchNormalization over the B Fc rows, per channel e: gamma_bn,
+ *             beta_bn, moving_mean, moving_var [E], biased variance, epsilon 1e-3, momentum 0.99
+ *   j < Fk:   x[b,Fc+j,:] = LayerNorm_j(table[X[b,Fc+j]] * values[b,j])  over E, epsilon 1e-3; gamma_ln, beta_ln [Fk, E]
+ * training != 0: batch statistics, and moving <- 0.99 moving + 0.01 batch (the biased batch variance) on the device;
+ * training == 0: the moving statistics, nothing updated.  The channel sums are per-workgroup partials in workspace slots
+ * added in a fixed order, the variance a second pass over (x - mean)^2.  An id outside [0, V), in a key column too, sets
+ * *oob_flag (may be NULL) and reads as a zero row, which takes part in the statistics.  The save buffers xhat [B, F E],
+ * rstd_bn [E] (Fc > 0) and rstd_ln [B, Fk] (Fk > 0) are all given or all NULL.
+ * The backward takes dx [B, F E] and the save buffers and writes vals [B*F, E], the IndexedSlices values of the lookup in
+ * the order of X, the key fields' already multiplied by their value, and dgamma_bn, dbeta_bn [E], dgamma_ln, dbeta_ln
+ * [Fk, E]; training != 0: the full BatchNorm backward across the B Fc rows, else g gamma rstd.  It reads neither the
+ * table nor X.  workspace (both ways): rec_emb_fibinetplus_in_workspace_bytes.
+ * Body.  x [B, F E], D = F E, P = F (F - 1) / 2 pairs (i < j) in itertools.combinations order; W [nW, E, E] with nW = 1
+ * (type 0 'all'), F - 1 (type 1 'each': W[i]) or P (type 2 'interaction': W[pair]); Wr [P, O], br, gamma_q, beta_q [O];
+ * G groups of width E / G; S0 [2 G F, mid], b0, gamma0, beta0 [mid]; S1 [mid, D], b1, gamma1, beta1 [D]:
+ *   p[b,pair] = x_i W x_j^T      q = LayerNorm(p Wr + br)
+ *   s[b, f 2G + g] = mean of group g of field f      s[b, f 2G + G + g] = its maximum
+ *   h = relu(LayerNorm(s S0 + b0))      A = relu(LayerNorm(h S1 + b1))      out = [q | x (.) A]      out [B, O + D]
+ * (every LayerNorm: biased variance, epsilon 1e-3).  One launch: a workgroup owns 16 examples whose x, p, s, h and A live
+ * in LDS; nothing between x and out goes to global memory except the save buffers p [B, P], xhat_q [B, O], s [B, 2 G F],
+ * xhat0 [B, mid], h [B, mid], xhat1 [B, D], rstd [B, 3] (q, h, A), all given (training) or all NULL (inference: only out
+ * is written; the same out).
+ * The backward takes dout [B, O + D] and the save buffers and writes dx [B, D] (written, never added to), dW [nW, E, E],
+ * dWr, dbr, dgamma_q, dbeta_q, dS0, db0, dgamma0, dbeta0, dS1, db1, dgamma1, dbeta1: one launch for the per-example
+ * chain (the gradient of a group maximum goes to its first arg-max element), two slot sums for the vectors, ONE launch
+ * for all of dW over at most 16 batch slices added in order by a third slot sum, and dWr = p^T dzq, dS0 = s^T dz0,
+ * dS1 = h^T dz1 on rec_gemm_f32 (split-K over the batch in at most 16 slices, added in order): the number of launches
+ * does not depend on F or P.
+ * All four only enqueue (no allocation, no host synchronisation: graph-capturable) and use no float atomics:
+ * bit-identical results run to run.  B == 0: nothing is launched.  A norm over one element returns exactly beta and
+ * exactly zero input gradients.
+ * Supported: the limits are FiBiNet's and MaskNet's, this family has no constants of its own: 2 <= F <= REC_FIBINET_MAX_F
+ * (the input stage alone: 1 <= F),
+ * 1 <= E <= REC_FIBINET_MAX_E, F E <= REC_MASKNET_MAX_D, 1 <= O <= REC_MASKNET_MAX_O, 1 <= mid <= REC_MASKNET_MAX_P,
+ * G >= 1, 0 <= Fk <= F, type 0 / 1 / 2, 0 <= B < 2^31; otherwise -2.  A negative size, G not dividing E, V <= 0, ld < E,
+ * a NULL pointer or save buffers given in part: -1.  A workspace that is too small: -3.
+ * workspace (block backward only): rec_fibinetplus_block_workspace_bytes: 4 B (D + mid + O + P) bytes of per-example
+ * gradients, (B / 16) slots of 3 (D + mid + O) floats, at most 16 copies of W and at most 16 of the largest of Wr, S0,
+ * S1 (0: invalid or unsupported shape). */
+size_t rec_emb_fibinetplus_in_workspace_bytes(int64_t B, int F, int Fk, int E);
+int rec_emb_fibinetplus_in_fwd_f32(const float* table, int64_t V, int E, int64_t ld, const int64_t* X,
+                                   const float* values, const float* gamma_bn, const float* beta_bn,
+                                   const float* gamma_ln, const float* beta_ln, int64_t B, int F, int Fk, int training,
+                                   float* moving_mean, float* moving_var, float* x, float* xhat, float* rstd_bn,
+                                   float* rstd_ln, int* oob_flag, void* workspace, size_t workspace_bytes, void* stream);
+int rec_emb_fibinetplus_in_bwd_f32(const float* dx, const float* values, const float* xhat, const float* rstd_bn,
+                                   const float* rstd_ln, const float* gamma_bn, const float* gamma_ln, int64_t B, int F,
+                                   int Fk, int E, int training, float* vals, float* dgamma_bn, float* dbeta_bn,
+                                   float* dgamma_ln, float* dbeta_ln, void* workspace, size_t workspace_bytes,
+                                   void* stream);
+size_t rec_fibinetplus_block_workspace_bytes(int64_t B, int F, int E, int G, int mid, int O, int type);
+int rec_fibinetplus_block_fwd_f32(const float* x, const float* W, const float* Wr, const float* br,
+                                  const float* gamma_q, const float* beta_q, const float* S0, const float* b0,
+                                  const float* gamma0, const float* beta0, const float* S1, const float* b1,
+                                  const float* gamma1, const float* beta1, int64_t B, int F, int E, int G, int mid, int O,
+                                  int type, float* out, float* p, float* xhat_q, float* s, float* xhat0, float* h,
+                                  float* xhat1, float* rstd, void* stream);
+int rec_fibinetplus_block_bwd_f32(const float* x, const float* W, const float* Wr, const float* gamma_q, const float* S0,
+                                  const float* gamma0, const float* beta0, const float* S1, const float* gamma1,
+                                  const float* beta1, const float* p, const float* xhat_q, const float* s,
+                                  const float* xhat0, const float* h, const float* xhat1, const float* rstd,
+                                  const float* dout, int64_t B, int F, int E, int G, int mid, int O, int type, float* dx,
+                                  float* dW, float* dWr, float* dbr, float* dgamma_q, float* dbeta_q, float* dS0,
+                                  float* db0, float* dgamma0, float* dbeta0, float* dS1, float* db1, float* dgamma1,
+                                  float* dbeta1, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
