@@ -1359,15 +1359,21 @@ class GraphedTrainStep:
                                       # is a tensor of the graph (dense, or sparse COO rows for tables) valid until the
                                       # next replay
 
+    ``label_name`` may be a sequence of names (a multi-task layer): the target is then [B, T], one column per name.
+    ``output_fn(layer, inputs) -> tensor`` replaces ``layer(inputs)["output"]`` for a layer whose result has no such key.
+
     The debug-mode bounds check of the layers (one host read per call) is switched off on this layer's modules: a host
     read cannot be captured.  Out-of-range ids then read as zero rows, as the kernels guarantee (no fault).
     """
 
-    def __init__(self, layer, example_batch, label_name="label", loss_fn=None, warmup=3, extra_loss_fn=None):
+    def __init__(self, layer, example_batch, label_name="label", loss_fn=None, warmup=3, extra_loss_fn=None,
+                 output_fn=None):
         from . import functional as Fn
         from . import layers as CL
         self.layer = layer
         self.label_name = label_name
+        self.label_names = (label_name,) if isinstance(label_name, str) else tuple(label_name)
+        self.output_fn = output_fn
         self.extra_loss_fn = extra_loss_fn                   # (inputs dict) -> scalar added to the loss (DIN's L2 term)
         self.out = None                                      # the layer's output of the last replay (graph pool tensor)
         self.static = {k: v.clone() for k, v in example_batch.items() if isinstance(v, torch.Tensor)}
@@ -1406,6 +1412,8 @@ class GraphedTrainStep:
         self.grads = [p.grad for p in self.params]           # tensors of the graph's pool: refreshed by every replay
 
     def _target(self, out):
+        if not isinstance(self.label_name, str):             # one column per task
+            return torch.stack([self.static[n].to(torch.float32).reshape(-1) for n in self.label_names], dim=1)
         y = self.static[self.label_name].to(torch.float32)
         if out.dim() == 2 and out.shape[1] > 1 and y.reshape(-1).numel() == out.shape[0]:
             y = y.reshape(-1, 1).expand(-1, out.shape[1])
@@ -1414,8 +1422,8 @@ class GraphedTrainStep:
     def _fwd_bwd(self):
         for p in self.params:
             p.grad = None
-        ins = {k: v for k, v in self.static.items() if k != self.label_name}
-        out = self.layer(ins)["output"]
+        ins = {k: v for k, v in self.static.items() if k not in self.label_names}
+        out = self.output_fn(self.layer, ins) if self.output_fn is not None else self.layer(ins)["output"]
         loss = self.loss_fn(out, self._target(out))
         if self.extra_loss_fn is not None:
             loss = loss + self.extra_loss_fn(ins)

@@ -849,3 +849,27 @@ class FiBiNetPlusBlock(torch.autograd.Function):
                                           dout.contiguous())
         dW, dWr, dbr, dgq, dbq, dS0, db0, dg0, dbe0, dS1, db1, dg1, dbe1 = g
         return (dx, dWr, dbr, dgq, dbq, dS0, db0, dg0, dbe0, dS1, db1, dg1, dbe1, None, None, None) + tuple(dW.unbind(0))
+
+
+class MMOEBody(torch.autograd.Function):
+    """The MMOE / ESMM body (4.MMOE/CustomLayers.py:152-172, 221-244; csrc/mmoe.hip): x [B, D] and the packed weights W1,
+    b1, We2, be2, Wg2, bg2, Wt1, bt1, Wt2, bt2, Wt3, bt3 (include/mi355rec.h) -> out [B, T], one launch each way plus the
+    slot sums, one launch for all small weight gradients and one weight-gradient GEMM."""
+
+    @staticmethod
+    def forward(ctx, x, gate_softmax_passes, ctcvr, *weights):
+        x = x.contiguous()
+        weights = [t.contiguous() for t in weights]
+        train = any(ctx.needs_input_grad)
+        out, saved = ops.mmoe_fwd(x, weights, gate_softmax_passes, ctcvr, save=train)
+        if train:
+            ctx.save_for_backward(x, *weights, *saved)
+        ctx.flags = (gate_softmax_passes, ctcvr)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, *rest = ctx.saved_tensors
+        weights, saved = rest[:12], rest[12:]
+        dx, grads = ops.mmoe_bwd(x, weights, saved, dout.contiguous(), *ctx.flags)
+        return (dx, None, None) + tuple(grads)

@@ -39,6 +39,8 @@ libmi355rec.so (through functional.py / ops.py).  Reference classes and the line
   FiBiNetPlusLayer              11.FiBiNet++/CustomLayers.py:148-178
   SENetPlusLayer                11.FiBiNet++/CustomLayers.py:181-205
   BilinearInteractionPlusLayer  11.FiBiNet++/CustomLayers.py:208-242
+  MMOELayer                     4.MMOE/CustomLayers.py:107-173
+  ESMMLayer                     4.MMOE/CustomLayers.py:175-245
 
 Parameters are named after the TF checkpoint keys (``embed.embeddings``, ``w.embeddings``, ``bias``,
 ``MLP_layer1.kernel_0`` ...), so a TensorBundle checkpoint maps onto ``state_dict()`` by name.
@@ -1938,3 +1940,82 @@ class FFMRankingLayer(FFMLayer):
 
 class PNNRankingLayer(PNNLayer):
     """2.FM/CustomLayers.py:536-598 (the loop form, InnerProductNetwork :601-624): same numbers as PNNLayer."""
+
+
+# ---------------------------------------------------------------------------------------------------
+# 4.MMOE: MMOE, ESMM
+# ---------------------------------------------------------------------------------------------------
+
+_MMOE_CAT = ["sdk_type", "remote_host", "device_type", "dtu", "click_goods_num", "buy_click_num", "goods_show_num",
+             "goods_click_num", "brand_name"]
+_MMOE_CONT = ["click_goods_num_origin", "click_goods_num_square", "click_goods_num_cube"]
+
+
+class MMOELayer(Layer):
+    """4.MMOE/CustomLayers.py:107-173: the flattened rows of the categorical ids feed ``expert_num`` expert MLPs [64, 8]
+    and one gate MLP [64, expert_num] per task (relu on every layer, the gate's last one too, then a softmax); each
+    task's tower, MLP [64, 8] then a sigmoid unit, reads the expert outputs scaled by its gate and FLATTENED (not summed)
+    -> {'ctr_output': [B, 1], 'cvr_output': [B, 1]}.  ``continuous_features`` is accepted and unused, as in the
+    reference.  The sub-layers hold the parameters under the reference's names; the call packs them and runs everything
+    after the lookup as one kernel each way (functional.MMOEBody)."""
+
+    task_names = ("ctr", "cvr")
+    gate_softmax_passes = 1
+    ctcvr = False
+
+    def __init__(self, categorical_features=_MMOE_CAT, continuous_features=_MMOE_CONT, feature_dims=160000,
+                 embedding_dims=16, expert_num=3):
+        super().__init__()
+        self.categorical_features = list(categorical_features)
+        self.continuous_features = list(continuous_features)
+        self.embedding_dims = int(embedding_dims)
+        self.expert_num = int(expert_num)
+        D, n = len(self.categorical_features) * self.embedding_dims, self.expert_num
+        ops.mmoe_check_shape(D, n, len(self.task_names), 64, 8, 64, 8)
+        self.embedding_layer = Embedding(feature_dims, self.embedding_dims)
+        self.expert_model = torch.nn.ModuleList(
+            [MLPLayer(units=[64, 8], activation="relu", input_dim=D) for _ in range(n)])
+        self.ctr_gate = MLPLayer(units=[64, n], activation="relu", input_dim=D)
+        self.cvr_gate = MLPLayer(units=[64, n], activation="relu", input_dim=D)
+        tower = lambda: torch.nn.ModuleList([MLPLayer(units=[64, 8], activation="relu", input_dim=n * 8),
+                                             MLPLayer(units=[1], activation="sigmoid", input_dim=8)])
+        self.ctr_output = tower()
+        self.cvr_output = tower()
+
+    def packed_weights(self):
+        """The sub-layers' parameters in the packed layout of include/mi355rec.h (W1, b1, We2, be2, Wg2, bg2, Wt1, bt1,
+        Wt2, bt2, Wt3, bt3); gradients flow back through the concatenations."""
+        first = list(self.expert_model) + [self.ctr_gate, self.cvr_gate]
+        gates, towers = [self.ctr_gate, self.cvr_gate], [self.ctr_output, self.cvr_output]
+        cat, stack = torch.cat, torch.stack
+        return (cat([m.kernel_0 for m in first], dim=1), cat([m.bias_0 for m in first]),
+                stack([m.kernel_1 for m in self.expert_model]), stack([m.bias_1 for m in self.expert_model]),
+                stack([m.kernel_1 for m in gates]), stack([m.bias_1 for m in gates]),
+                stack([t[0].kernel_0 for t in towers]), stack([t[0].bias_0 for t in towers]),
+                stack([t[0].kernel_1 for t in towers]), stack([t[0].bias_1 for t in towers]),
+                stack([t[1].kernel_0.reshape(-1) for t in towers]), cat([t[1].bias_0 for t in towers]))
+
+    def task_outputs(self, inputs):
+        """[B, 2]: column 0 is 'ctr_output', column 1 'cvr_output' (the dict entries are views of it)."""
+        X = assemble_index(inputs, self.categorical_features)
+        flag = ops.new_flag(X.device) if self.check_ids else None
+        x = self.embedding_layer(X, flag)
+        self._raise_if_oob(flag)
+        return Fn.MMOEBody.apply(x.reshape(X.shape[0], -1), self.gate_softmax_passes, self.ctcvr,
+                                 *self.packed_weights())
+
+    def forward(self, inputs):
+        out = self.task_outputs(inputs)
+        return {"ctr_output": out[:, 0:1], "cvr_output": out[:, 1:2]}
+
+
+class ESMMLayer(MMOELayer):
+    """4.MMOE/CustomLayers.py:175-245: MMOE's structure with the gate's softmax applied twice (227-233) and
+    'cvr_output' = ctr * cvr (243-244)."""
+
+    gate_softmax_passes = 2
+    ctcvr = True
+
+    def __init__(self, categorical_features=_MMOE_CAT, continuous_features=_MMOE_CONT, feature_dims=160000,
+                 embedding_dims=16, expert_num=3):
+        super().__init__(categorical_features, continuous_features, feature_dims, embedding_dims, expert_num)

@@ -7,6 +7,9 @@ data.py).
 
     mm = ModelManager(layer='deepfm_ranking', feature_names=[...], data_info=data.data_info(V, F), batch=8192)
     result = mm.train_step(batches)          # -> {'auc': ..., 'loss': ...}
+
+The two-label models of 4.MMOE (``layer='mmoe_layer'``, ``'esmm_layer'``; 4.MMOE/ModelManager.py:68-73, 95-107, 174-190,
+229-240) take batches with a ``ctr`` and a ``cvr`` label and report {'ctr_auc', 'cvr_auc', 'loss'}.
 """
 import json
 import random
@@ -106,6 +109,7 @@ class ModelManager:
         self.regularization_factor = regularization_factor   # 5.DIN/ModelManager.py:20,38 (used by the DIN loop only)
         self.continuous_features = list(continuous_features or [])
         self.behavior_series_features = list(behavior_series_features or [])
+        self.task_labels = None                              # the label names of a multi-task layer, one per output column
         self.set_feature_names(feature_names, label_name)
         self.load_json_info(json_path, data_info)
         self.feature_dims = self.feature_info[-1]          # total vocabulary (2.FM/ModelManager.py:38)
@@ -217,6 +221,16 @@ class ModelManager:
             self.layer = CL.FiBiNetPlusLayer(
                 categorical_features=self.feature_names, continuous_features=self.continuous_features,
                 feature_dims=self.feature_dims, embedding_dims=self.embedding_dims, **p)
+        elif layer_name in ("mmoe_layer", "esmm_layer"):   # 4.MMOE/ModelManager.py:68-73
+            cls = CL.MMOELayer if layer_name == "mmoe_layer" else CL.ESMMLayer
+            self.layer = cls(categorical_features=self.feature_names, continuous_features=self.continuous_features,
+                             feature_dims=self.feature_dims, embedding_dims=self.embedding_dims,
+                             expert_num=model_params.get("expert_num", 3))
+            # the reference pops 'ctr' and 'cvr' off the batch (ModelManager.py:176-177) whatever its label_name says
+            names = self.layer.task_names if isinstance(self.label_name, str) else tuple(self.label_name)
+            if len(names) != len(self.layer.task_names):
+                raise ValueError("%s takes %d label names, got %r" % (layer_name, len(self.layer.task_names), names))
+            self.task_labels = tuple(names)
         elif layer_name == "din_layer":                    # 5.DIN/ModelManager.py:72-73
             p = dict(model_params)
             p.setdefault("feature_dims", self.feature_dims)
@@ -255,6 +269,8 @@ class ModelManager:
     def init_metric(self):
         self._loss_sum, self._loss_n = 0.0, 0
         self._auc_hist = np.zeros((2, self.AUC_THRESHOLDS + 1), np.float64)      # [negatives | positives] per bucket (host)
+        if self.task_labels:                                                    # one histogram per task (4.MMOE:104-107)
+            self._auc_hist = np.zeros((len(self.task_labels), 2, self.AUC_THRESHOLDS + 1), np.float64)
         self._dev_metric = None                                                 # device accumulators of the compiled loop
 
     def _metric_reset(self):
@@ -287,6 +303,39 @@ class ModelManager:
                                                   ops._ptr(d["loss"]), ops._stream()), "rec_auc_hist_update_f32")
         d["n"] += n_steps
 
+    def _task_target(self, inputs, pop=False):
+        """[B, T] float32: the task labels of a batch, one column per task."""
+        cols = [(inputs.pop(n) if pop else inputs[n]).to(torch.float32).reshape(-1) for n in self.task_labels]
+        return torch.stack(cols, dim=1)
+
+    def _metric_update_dev_tasks(self, loss, target, out):
+        """The multi-task form of _metric_update_dev: rec_auc_hist_update_f32 once per task on its own histogram, the
+        loss added by the first call alone."""
+        d = self._dev_metric
+        T = len(self.task_labels)
+        if d is None:
+            dev = loss.device
+            d = self._dev_metric = {"thr": torch.from_numpy(self._auc_thresholds().astype(np.float32)).to(dev),
+                                    "hist": torch.zeros((T, 2 * (self.AUC_THRESHOLDS + 1)), dtype=torch.int64, device=dev),
+                                    "loss": torch.zeros(1, dtype=torch.float64, device=dev), "n": 0}
+        ls = loss.reshape(-1).to(torch.float32).contiguous()
+        for t in range(T):
+            p, y = out[:, t].to(torch.float32).contiguous(), target[:, t].to(torch.float32).contiguous()
+            ops.check(ops.lib.rec_auc_hist_update_f32(ops._ptr(p), ops._ptr(y), p.numel(), ops._ptr(d["thr"]),
+                                                      self.AUC_THRESHOLDS, ops._ptr(d["hist"][t]), ops._ptr(ls),
+                                                      1 if t == 0 else 0, ops._ptr(d["loss"]), ops._stream()),
+                      "rec_auc_hist_update_f32")
+        d["n"] += 1
+
+    def _metric_update_tasks(self, loss, target, out):
+        self._loss_sum += float(loss)
+        self._loss_n += 1
+        thr = self._auc_thresholds().astype(np.float32)
+        y, p = target.detach().cpu().numpy(), out.detach().cpu().numpy().astype(np.float32)
+        for t in range(len(self.task_labels)):
+            k = np.searchsorted(thr, p[:, t], side="left")
+            np.add.at(self._auc_hist[t], ((y[:, t] > 0.5).astype(np.int64), k), 1.0)
+
     def _metric_update(self, loss, target, output):
         self._loss_sum += float(loss)
         self._loss_n += 1
@@ -300,13 +349,24 @@ class ModelManager:
     def _metric_result(self):
         d = self._dev_metric
         if d is not None and d["n"] > 0:                     # ONE device -> host read
-            self._auc_hist += d["hist"].cpu().numpy().astype(np.float64).reshape(2, -1)
+            self._auc_hist += d["hist"].cpu().numpy().astype(np.float64).reshape(self._auc_hist.shape)
             self._loss_sum += float(d["loss"].item())
             self._loss_n += d["n"]
             d["hist"].zero_(); d["loss"].zero_(); d["n"] = 0
+        if self.task_labels:
+            names = [n + "_auc" for n in self.layer.task_names]
+            if self._loss_n == 0:
+                return dict.fromkeys(names + ["loss"], float("nan"))
+            res = {n: self._auc_of(h) for n, h in zip(names, self._auc_hist)}
+            res["loss"] = self._loss_sum / max(1, self._loss_n)
+            return res
         if self._loss_n == 0:
             return {"auc": float("nan"), "loss": float("nan")}
-        neg, pos = self._auc_hist
+        return {"auc": self._auc_of(self._auc_hist), "loss": self._loss_sum / max(1, self._loss_n)}
+
+    @staticmethod
+    def _auc_of(hist):
+        neg, pos = hist
         # counts above threshold i = buckets i+1 ..: reverse cumulative sums
         tp = np.cumsum(pos[::-1])[::-1][1:]
         fp = np.cumsum(neg[::-1])[::-1][1:]
@@ -316,7 +376,7 @@ class ModelManager:
         else:
             tpr, fpr = tp / n_pos, fp / n_neg
             auc = float(np.sum((fpr[:-1] - fpr[1:]) * (tpr[:-1] + tpr[1:]) / 2.0))
-        return {"auc": auc, "loss": self._loss_sum / max(1, self._loss_n)}
+        return auc
 
     def _to_device(self, inputs):
         out = {}
@@ -392,7 +452,7 @@ class ModelManager:
         from . import engine as EN
         lay = self.model
         info = self.feature_info
-        B = slot[self.label_name].numel()
+        B = slot[self.task_labels[0] if self.task_labels else self.label_name].numel()
         fused_ok = (isinstance(lay, CL.DeepFMRankingLayer) and lay.embedding_dims == 16 and
                     list(lay.mlp_dims) == [32, 8] and len(lay.feature_names) <= 28 and B <= 16384 and
                     isinstance(info, (list, tuple)) and len(info) >= 2 and
@@ -407,6 +467,11 @@ class ModelManager:
         extra = None
         if isinstance(lay, CL.DINLayer) and self.regularization_factor and hasattr(lay.embed, "embeddings"):
             extra = lambda ins: self.used_rows_l2(ins)
+        if self.task_labels:                                 # BCE over [B, T]: the mean of the tasks' losses
+            step = EN.GraphedTrainStep(lay, slot, label_name=self.task_labels,
+                                       loss_fn=lambda out, y: Fn.KerasBCE.apply(out, y),
+                                       output_fn=lambda layer, ins: layer.task_outputs(ins))
+            return ("graphed", step)
         step = EN.GraphedTrainStep(lay, slot, label_name=self.label_name,
                                    loss_fn=lambda out, y: Fn.KerasBCE.apply(out, y), extra_loss_fn=extra)
         return ("graphed", step)
@@ -437,6 +502,11 @@ class ModelManager:
             if self._eng is None:
                 self._eng = self._build_engine(slot)
             kind, step = self._eng
+            if self.task_labels:                             # 4.MMOE/ModelManager.py:174-190
+                loss = step(slot).clone()
+                self.opt.apply_gradients()
+                self._metric_update_dev_tasks(loss, self._task_target(slot), step.out)
+                return loss
             target = slot[self.label_name]
             if kind == "fused":
                 nxt = None
@@ -453,6 +523,15 @@ class ModelManager:
             self._metric_update_dev(loss, target, prob)
             return loss
         inputs = self._to_device(inputs)
+        if self.task_labels:
+            # 0.5 BCE(ctr) + 0.5 BCE(cvr) is the mean of the element-wise cross-entropy over [B, 2]
+            target = self._task_target(inputs, pop=True)
+            out = self.model.task_outputs(inputs)
+            scaled_loss = Fn.KerasBCE.apply(out, target)
+            scaled_loss.backward()
+            self.opt.apply_gradients()
+            self._metric_update_tasks(scaled_loss.item(), target, out)
+            return scaled_loss
         target = inputs.pop(self.label_name)
         logits = self.model(inputs)
         scaled_loss = self.loss(target, logits["output"])
@@ -469,7 +548,8 @@ class ModelManager:
         from . import tfrecord
         assert mode in ("train", "test")
         self.set_feature_names(feature_names, label_name)
-        return tfrecord.TFRecordDataset(data_dir, mode, self.feature_names, self.label_name, self.batch)
+        return tfrecord.TFRecordDataset(data_dir, mode, self.feature_names, self.task_labels or self.label_name,
+                                        self.batch)
 
     def _train_chunks(self, order):
         """The epoch of the compiled DeepFM loop, `steps_per_call` iterations per call: a hipGraph launch leaves the GPU
@@ -569,6 +649,12 @@ class ModelManager:
         self._metric_reset()
         for batch_data in ds:
             inputs = self._to_device(dict(batch_data))
+            if self.task_labels:                             # 4.MMOE/ModelManager.py:229-240
+                target = self._task_target(inputs, pop=True)
+                out = self.model.task_outputs(inputs)
+                loss, _, _ = ops.bce_fwd_bwd(target, out.contiguous(), want_dp=False)
+                self._metric_update_tasks(loss.item(), target, out)
+                continue
             target = inputs.pop(self.label_name)
             logits = self.model(inputs)
             loss, _, _ = ops.bce_fwd_bwd(self._match_target(target, logits["output"]), logits["output"].contiguous(),

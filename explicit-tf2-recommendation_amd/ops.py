@@ -1502,3 +1502,91 @@ def fibinetplus_block_bwd(x, W, Wr, gq, S0, g0, be0, S1, g1, be1, G, type_code, 
                                                 F, E, G, mid, O, tc, _ptr(dx), *[_ptr(t) for t in grads], _ptr(ws),
                                                 nbytes, _stream()), "rec_fibinetplus_block_bwd_f32")
     return dx, grads
+
+
+# ---- MMOE / ESMM: experts, gates, gate mixture and towers in one launch each way (csrc/mmoe.hip).  The limits are
+# MaskNet's.
+def mmoe_check_shape(D, n, T=2, H1=64, O=8, H2=64, O2=8):
+    """ValueError for sizes that describe no MMOE body, NotImplementedError for shapes the kernel does not cover (the ABI
+    would return -2): input width D, n experts, T tasks, hidden width H1 of experts and gates, expert output width O,
+    tower widths H2 and O2."""
+    if min(D, n, T, H1, O, H2, O2) < 1:
+        raise ValueError("every size of an MMOE body must be positive, got D=%d, experts=%d, tasks=%d, H1=%d, O=%d, "
+                         "H2=%d, O2=%d" % (D, n, T, H1, O, H2, O2))
+    N1 = (n + T) * H1
+    if (D > MASKNET_MAX_D or N1 > MASKNET_MAX_P or T > MASKNET_MAX_R
+            or max(H1, H2, O2, n * O, n * T) > MASKNET_MAX_O):
+        raise NotImplementedError(
+            "MMOE kernels cover fields * embedding_dims <= %d, (experts + tasks) * H1 <= %d, tasks <= %d and each of H1, "
+            "H2, O2, experts * O and experts * tasks <= %d; got fields * embedding_dims=%d, (experts + tasks) * H1=%d, "
+            "tasks=%d, H1=%d, H2=%d, O2=%d, experts * O=%d, experts * tasks=%d"
+            % (MASKNET_MAX_D, MASKNET_MAX_P, MASKNET_MAX_R, MASKNET_MAX_O, D, N1, T, H1, H2, O2, n * O, n * T))
+
+
+_MMOE_WEIGHTS = ("W1", "b1", "We2", "be2", "Wg2", "bg2", "Wt1", "bt1", "Wt2", "bt2", "Wt3", "bt3")
+
+
+def _mmoe_args(x, w, passes, ctcvr):
+    """-> (B, D, n, T, H1, O, H2, O2) of the packed weights ``w`` (a dict or sequence in the order of _MMOE_WEIGHTS),
+    checked against each other, the flags and the limits."""
+    W1, b1, We2, be2, Wg2, bg2, Wt1, bt1, Wt2, bt2, Wt3, bt3 = w
+    for t, name, dim in ((x, "x", 2), (W1, "W1", 2), (We2, "We2", 3), (Wg2, "Wg2", 3), (Wt1, "Wt1", 3), (Wt2, "Wt2", 3),
+                         (Wt3, "Wt3", 2)):
+        if _f32(t, name).dim() != dim:
+            raise ValueError("%s must be %d-D, got %s" % (name, dim, tuple(t.shape)))
+    B, D = x.shape
+    n, H1, O = We2.shape
+    T, H2, O2 = Wt2.shape
+    if (tuple(W1.shape) != (D, (n + T) * H1) or tuple(Wg2.shape) != (T, H1, n) or tuple(Wt1.shape) != (T, n * O, H2)
+            or tuple(Wt3.shape) != (T, O2)):
+        raise ValueError("an MMOE body takes x [B,D], W1 [D,(n+T) H1], We2 [n,H1,O], Wg2 [T,H1,n], Wt1 [T,n O,H2], Wt2 "
+                         "[T,H2,O2], Wt3 [T,O2]; got %s" % ", ".join(str(tuple(t.shape))
+                                                                      for t in (x, W1, We2, Wg2, Wt1, Wt2, Wt3)))
+    if passes not in (1, 2) or ctcvr not in (0, 1, False, True) or (ctcvr and T != 2):
+        raise ValueError("gate_softmax_passes is 1 or 2 and ctcvr needs two tasks, got passes=%r, ctcvr=%r, tasks=%d"
+                         % (passes, ctcvr, T))
+    mmoe_check_shape(D, n, T, H1, O, H2, O2)
+    for t, cnt, name in ((b1, (n + T) * H1, "b1"), (be2, n * O, "be2"), (bg2, T * n, "bg2"), (bt1, T * H2, "bt1"),
+                         (bt2, T * O2, "bt2"), (bt3, T, "bt3")):
+        _vec(t, cnt, name)
+    return B, D, n, T, H1, O, H2, O2
+
+
+def mmoe_fwd(x, weights, gate_softmax_passes=1, ctcvr=False, save=True):
+    """The MMOE / ESMM body in one launch: experts and gates over x [B, D], softmax gates (``gate_softmax_passes`` 1 or
+    2), the gate-weighted expert outputs flattened into the towers -> (out [B, T], saved) with out[:, t] the task
+    probability (``ctcvr``: out[:, 1] = p_0 p_1) and saved = (h [B,(n+T) H1], e [B,n O], z [B,T n], g [B,T n], a1
+    [B,T H2], a2 [B,T O2], p [B,T]) for the backward, or None (``save=False``: inference, only out is written).
+    ``weights``: W1, b1, We2, be2, Wg2, bg2, Wt1, bt1, Wt2, bt2, Wt3, bt3 as include/mi355rec.h packs them."""
+    B, D, n, T, H1, O, H2, O2 = _mmoe_args(x, weights, gate_softmax_passes, ctcvr)
+    dev = x.device
+    new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+    out = new(B, T)
+    saved = (new(B, (n + T) * H1), new(B, n * O), new(B, T * n), new(B, T * n), new(B, T * H2), new(B, T * O2),
+             new(B, T)) if save else None
+    check(lib.rec_mmoe_fwd_f32(_ptr(x), *[_ptr(t) for t in weights], B, D, n, T, H1, O, H2, O2, int(gate_softmax_passes),
+                               int(bool(ctcvr)), _ptr(out), *[_ptr(t) for t in (saved or (None,) * 7)], _stream()),
+          "rec_mmoe_fwd_f32")
+    return out, saved
+
+
+def mmoe_bwd(x, weights, saved, dout, gate_softmax_passes=1, ctcvr=False):
+    """-> (dx [B, D], grads) with grads the gradient of every packed weight, in the order of ``weights``."""
+    B, D, n, T, H1, O, H2, O2 = _mmoe_args(x, weights, gate_softmax_passes, ctcvr)
+    shapes = ((B, (n + T) * H1), (B, n * O), (B, T * n), (B, T * n), (B, T * H2), (B, T * O2), (B, T))
+    for t, shp, name in zip(tuple(saved) + (dout,), shapes + ((B, T),), ("h", "e", "z", "g", "a1", "a2", "p", "dout")):
+        if t is None or tuple(_f32(t, name).shape) != shp:
+            raise ValueError("%s must be %s, got %s" % (name, shp, None if t is None else tuple(t.shape)))
+    dev = x.device
+    dx = torch.zeros((B, D), dtype=torch.float32, device=dev) if B == 0 else \
+        torch.empty((B, D), dtype=torch.float32, device=dev)
+    grads = [torch.zeros_like(t) if B == 0 else torch.empty_like(t) for t in weights]   # written in full when B > 0
+    if B > 0:
+        nbytes = lib.rec_mmoe_workspace_bytes(B, D, n, T, H1, O, H2, O2)
+        ws = _workspace(nbytes, "rec_mmoe_workspace_bytes", dev, torch.float32)
+        W1, _, We2, _, Wg2, _, Wt1, _, Wt2, _, Wt3, _ = weights
+        check(lib.rec_mmoe_bwd_f32(_ptr(x), *[_ptr(t) for t in (W1, We2, Wg2, Wt1, Wt2, Wt3)],
+                                   *[_ptr(t) for t in saved], _ptr(dout), B, D, n, T, H1, O, H2, O2,
+                                   int(gate_softmax_passes), int(bool(ctcvr)), _ptr(dx), *[_ptr(g) for g in grads],
+                                   _ptr(ws), nbytes, _stream()), "rec_mmoe_bwd_f32")
+    return dx, grads

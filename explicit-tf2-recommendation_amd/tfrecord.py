@@ -257,23 +257,28 @@ def write_dataset(output_path, data_name, encoded, labels, data_type, feature_na
 class TFRecordDataset:
     """init_dataset (2.FM/ModelManager.py:122-153): every file of data_dir whose name contains `mode`, each record
     parsed as FixedLenFeature([1]) (float32 label, int64 features), batched; the last batch may be short.  Iterating
-    yields {name: int64 [b,1], label_name: float32 [b,1]} numpy batches (data.to_device moves them to the GPU)."""
+    yields {name: int64 [b,1], label_name: float32 [b,1]} numpy batches (data.to_device moves them to the GPU).
+    ``label_name`` may be a sequence of names (4.MMOE/ModelManager.py:125-128: 'ctr' and 'cvr'), each one float per
+    example and one [b,1] entry of the batch."""
 
     def __init__(self, data_dir, mode, feature_names, label_name="label", batch=100):
         assert mode in ("train", "test")
         self.files = sorted(os.path.join(data_dir, f) for f in os.listdir(data_dir) if mode in f)
         self.feature_names, self.label_name, self.batch = list(feature_names), label_name, int(batch)
+        self.label_names = [label_name] if isinstance(label_name, str) else list(label_name)
 
     def __iter__(self):
         cols = {n: [] for n in self.feature_names}
-        lab = []
+        labs = {n: [] for n in self.label_names}
+        first = self.label_names[0]
 
         def flush():
             out = {n: np.array(cols[n], np.int64).reshape(-1, 1) for n in self.feature_names}
-            out[self.label_name] = np.array(lab, np.float32).reshape(-1, 1)
+            for n in self.label_names:
+                out[n] = np.array(labs[n], np.float32).reshape(-1, 1)
+                labs[n].clear()
             for n in cols:
                 cols[n].clear()
-            lab.clear()
             return out
 
         for path in self.files:
@@ -284,11 +289,12 @@ class TFRecordDataset:
                     if v is None or len(v) != 1:
                         raise ValueError("feature %r: expected exactly one int64 (FixedLenFeature([1]))" % n)
                     cols[n].append(int(v[0]))
-                v = ex.get(self.label_name)
-                if v is None or len(v) != 1:
-                    raise ValueError("label %r: expected exactly one float" % self.label_name)
-                lab.append(float(v[0]))
-                if len(lab) == self.batch:
+                for n in self.label_names:
+                    v = ex.get(n)
+                    if v is None or len(v) != 1:
+                        raise ValueError("label %r: expected exactly one float" % n)
+                    labs[n].append(float(v[0]))
+                if len(labs[first]) == self.batch:
                     yield flush()
-        if lab:
+        if labs[first]:
             yield flush()

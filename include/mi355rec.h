@@ -866,6 +866,51 @@ int rec_fibinetplus_block_bwd_f32(const float* x, const float* W, const float* W
                                   float* db0, float* dgamma0, float* dbeta0, float* dS1, float* db1, float* dgamma1,
                                   float* dbeta1, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- MMOE / ESMM (MMOELayer / ESMMLayer, 4.MMOE/CustomLayers.py:107-245; csrc/mmoe.hip): n expert MLPs and T gate
+ * MLPs over one input, the gate-weighted expert outputs flattened into T towers.
+ * x [B, D]; n experts, T tasks, hidden width H1 of experts and gates, expert output width O, tower widths H2 and O2,
+ * N1 = (n + T) H1.  Packed weights, all row-major:
+ *   W1 [D, N1], b1 [N1]   the first layers side by side: column block i < n (H1 columns) is expert i's, block n + t gate t's
+ *   We2 [n, H1, O], be2 [n, O]      Wg2 [T, H1, n], bg2 [T, n]
+ *   Wt1 [T, n O, H2], bt1 [T, H2]   Wt2 [T, H2, O2], bt2 [T, O2]   Wt3 [T, O2], bt3 [T]
+ * Per example (relu'(0) = 0):
+ *   h = relu(x W1 + b1)   e_i = relu(h_i We2[i] + be2[i])   z_t = relu(h_{n+t} Wg2[t] + bg2[t])
+ *   g_t = softmax(z_t), applied gate_softmax_passes times (1: MMOE, 2: ESMM)
+ *   u_t = concat_i(e_i g_t[i])  [n O]  (flattened, not summed over the experts)
+ *   a1_t = relu(u_t Wt1[t] + bt1[t])   a2_t = relu(a1_t Wt2[t] + bt2[t])   p_t = sigmoid(a2_t Wt3[t] + bt3[t])
+ *   out[:, t] = p_t;  ctcvr != 0 (T == 2): out[:, 1] = p_0 p_1                                            out [B, T]
+ * One launch: a workgroup owns 32 examples, x W1 runs on v_mfma_f32_32x32x2_f32 (fp32-exact, as rec_gemm_f32), everything
+ * after h out of LDS.  The save buffers h [B, N1], e [B, n O], z [B, T n], g [B, T n] (the gate after the last softmax),
+ * a1 [B, T H2], a2 [B, T O2] and p [B, T] are all given (training) or all NULL (inference: only out is written; the
+ * same out).
+ * The backward takes dout [B, T] and the save buffers and writes dx [B, D] (written, never added to) and the gradient of
+ * every packed weight: one launch for the per-example chain and dx, one slot sum for the bias gradients, ONE launch for
+ * dWe2, dWg2, dWt1, dWt2 and dWt3 over at most 16 batch slices added in order by a second slot sum, and dW1 = x^T dZ1
+ * on rec_gemm_f32 (split-K over the batch in at most 16 slices, added in order): the number of launches does not depend
+ * on n, T or B.
+ * Both only enqueue (no allocation, no host synchronisation: graph-capturable) and use no float atomics: bit-identical
+ * results run to run.  B == 0: nothing is launched.  With n == 1 the gate is exactly 1 and its gradients exactly 0.
+ * Supported: the limits are MaskNet's, this family has no constants of its own: 1 <= D <= REC_MASKNET_MAX_D,
+ * N1 <= REC_MASKNET_MAX_P, each of H1, H2, O2, n O and n T <= REC_MASKNET_MAX_O, 1 <= T <= REC_MASKNET_MAX_R, n >= 1,
+ * 0 <= B < 2^31; otherwise -2.  A size below 1 (B below 0), gate_softmax_passes other than 1 / 2, ctcvr other than
+ * 0 / 1, ctcvr with T != 2, a NULL pointer or save buffers given in part: -1.  A workspace that is too small: -3.
+ * workspace (backward only): rec_mmoe_workspace_bytes: 4 B (N1 + n O + T n + T H2 + T O2 + T) bytes of per-example
+ * gradients, (B / 32) slots of as many floats, at most 16 copies of the small weights and at most 16 of W1 (0: invalid
+ * or unsupported shape). */
+size_t rec_mmoe_workspace_bytes(int64_t B, int D, int n, int T, int H1, int O, int H2, int O2);
+int rec_mmoe_fwd_f32(const float* x, const float* W1, const float* b1, const float* We2, const float* be2,
+                     const float* Wg2, const float* bg2, const float* Wt1, const float* bt1, const float* Wt2,
+                     const float* bt2, const float* Wt3, const float* bt3, int64_t B, int D, int n, int T, int H1, int O,
+                     int H2, int O2, int gate_softmax_passes, int ctcvr, float* out, float* h, float* e, float* z,
+                     float* g, float* a1, float* a2, float* p, void* stream);
+int rec_mmoe_bwd_f32(const float* x, const float* W1, const float* We2, const float* Wg2, const float* Wt1,
+                     const float* Wt2, const float* Wt3, const float* h, const float* e, const float* z, const float* g,
+                     const float* a1, const float* a2, const float* p, const float* dout, int64_t B, int D, int n, int T,
+                     int H1, int O, int H2, int O2, int gate_softmax_passes, int ctcvr, float* dx, float* dW1,
+                     float* db1, float* dWe2, float* dbe2, float* dWg2, float* dbg2, float* dWt1, float* dbt1,
+                     float* dWt2, float* dbt2, float* dWt3, float* dbt3, void* workspace, size_t workspace_bytes,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif
