@@ -19,12 +19,15 @@ struct ColSortArgs {
   int32_t* col_seg;     // [F][B+1] run starts in the column's sorted order (tail = B)
   int32_t* col_nu;      // [F]
   int* bad;
+  int64_t max_key;      // largest key of the launch (the widest field's dim - 1)
+  int bm_words;         // bitmap path: 32-bit words that cover keys 0 .. max_key; 0 = the launch does not take it
   int32_t* dloc;        // [F][B] or null: run index of lookup (f, example) inside its column, sign bit = not the run's head
 };
 
 // ------------------------------------------------------------------------------------------------
 // ONE kernel: one 1024-thread workgroup per column sorts the column's <= 16384 words in LDS and goes straight on to the
-// run heads.  Columns without a hot bucket take the bucket path below; the others a stable LSD radix sort on the key
+// run heads.  Columns without a hot bucket take the bitmap path (no sort at all: CS_BM_WORDS below) when the launch's key
+// range fits it, else the bucket path below; the others a stable LSD radix sort on the key
 // bits in as few passes of at most 10 bits as cover the key (19-bit keys: 10 + 9), in place: every key is in a register
 // between the barrier that ends the reads and the one that starts the writes.  (Round 1 ran a chunk-sort / rank-merge /
 // heads chain of three latency-bound launches.)
@@ -41,12 +44,44 @@ constexpr int CS_T = 1024, CS_W = CS_T / 64, CS_DB = 10, CS_BINS = 1 << CS_DB;
 // no round of 64 words has more than CS_PROBE in lane 0's bucket
 constexpr int CS_BKB = 13, CS_NBK = 1 << CS_BKB, CS_BIG = 32, CS_PROBE = 16;
 static_assert(CS_BINS == CS_T, "the count scan gives every thread one digit");
+// bitmap path (8 words per thread only: B <= 8192): a launch whose keys 0 .. max_key fit CS_BM_WORDS 32-bit words ranks
+// a column without sorting it.  One bit per distinct key; the popcount prefix over the words is the ascending rank of
+// every distinct id.  A lookup whose word holds no duplicated id has its sorted position from two prefixes and one
+// popcount; the lookups of the other words ("slow") go to a list, every such word to a segment of its own.
+//   LDS, inside the other paths' arrays (32-bit word offsets; `wtot` behind them is shared):
+//     bm   [CS_BM_WORDS]          the bitmap                                            4 bytes per word
+//     xc   [CS_BM_WORDS] 16 bit   lookups - distinct keys of the word; after the scan the lookups beyond the distinct
+//                                 keys in all earlier words, or 0x8000 | index of the word's record   2 bytes per word
+//     pu   [CS_BM_WORDS / 2] 16 bit  distinct keys before the PAIR of words (one 8-byte read gives a lookup its pair of
+//                                 the bitmap: the odd word adds the even word's popcount)             1 byte per word
+//     list [CS_BM_CAP]            sort words of the slow lookups, one segment per slow word
+//     rec  [CS_BM_CAP / 2] x 2    per slow word: (extras before | segment start << 16, append cursor -> segment end)
+//   7 bytes per word + 8 per list entry inside the 98 KB the kernel has at 8 words per thread: 13 x 1024 words =
+//   425,984 keys (the headline's widest field: 384,625 keys = 12,020 words).  The widest legal key at B = 8192
+//   (2^19 - 2: 16,384 words) would need 112 KB and stays on the bucket path, as does B > 8192 (16 words per thread, keys
+//   of at most 18 bits: a uniform column there has more than a thousand slow lookups, see CS_BM_CAP).
+// CS_BM_CAP: a word's segment is scanned by each of its members, so the work does not grow with the list, only the LDS
+// does (8 bytes per entry).  512 = the largest power of two that leaves the bitmap its 13 K words; uniform headline
+// columns have 229 slow lookups on average and 329 at most in 2000 draws.  The stamps put the bitmap's own work (set,
+// scan: ~6 us) in front of the test, which a column over the cap pays before it starts the bucket path.
+constexpr int CS_BM_WORDS = 13 * CS_T, CS_BM_CAP = 512, CS_BM_PPT = 7;
+constexpr int CS_BM_XC = CS_BM_WORDS, CS_BM_PU = CS_BM_XC + CS_BM_WORDS / 2, CS_BM_LIST = CS_BM_PU + CS_BM_WORDS / 4,
+              CS_BM_REC = CS_BM_LIST + CS_BM_CAP, CS_BM_WTOT = CS_BM_REC + CS_BM_CAP, CS_BM_END = CS_BM_WTOT + CS_W;
+static_assert(CS_BM_PPT * CS_T * 2 >= CS_BM_WORDS && CS_BM_WORDS % 8 == 0, "the scan covers the bitmap, 16-byte zeroing");
+static_assert(CS_BM_END <= CS_T * 8 + CS_W * CS_BINS, "the bitmap path fits the LDS of the other paths at 8 words per thread");
+static_assert(CS_BM_REC % 2 == 0 && CS_BM_XC % 4 == 0, "8-byte records, 16-byte zeroing of xc");
+// its output staging: 32-bit keys [8192], 16-bit run starts [8192], 16-bit perm [8192] -- below the list and the records
+static_assert(CS_T * 8 * 2 <= CS_BM_PU, "the staging leaves pu, list and records alone");
 
 #ifdef REC_SORT_STAMPS
 __device__ unsigned long long g_sort_stamps[256 * 16];
 #define SSTAMP(k) do { if (threadIdx.x == 0) g_sort_stamps[blockIdx.x * 16 + (k)] = wall_clock64(); } while (0)
+#define SSTAMP_END() do { SSTAMP(8); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); SSTAMP(9); \
+    if (threadIdx.x == 1023) g_sort_stamps[blockIdx.x * 16 + 10] = wall_clock64(); \
+    if (threadIdx.x == 512) g_sort_stamps[blockIdx.x * 16 + 11] = wall_clock64(); } while (0)
 #else
 #define SSTAMP(k) do {} while (0)
+#define SSTAMP_END() do {} while (0)
 #endif
 
 // up to 256 columns per launch (8 batches of 26..32 columns: ONE launch per 8 upcoming batches -- every sort launch holds
@@ -83,18 +118,33 @@ __global__ __launch_bounds__(CS_T, 4) void colsort_kernel(SortCols cols, const i
   SSTAMP(0);
   uint32_t w[KPT];
   bool bad = false;
+  const int nw = KPT == 8 ? a.bm_words : 0;            // bitmap words of the launch (0: no bitmap path)
+  int hot = 0;
   const int64_t* col = cols.p[f];
+  int64_t id[KPT];
+#pragma unroll
+  for (int r = 0; r < KPT; ++r) {
+    const int e = wave * (64 * KPT) + r * 64 + lane;
+    id[r] = e < B ? col[e] : lo;
+  }
+  // bitmap and per-word counts are cleared while the ids are in flight (words and counts are read in pairs: both
+  // arrays in 16-byte pieces, past an odd last word)
+  uint32_t* bm = sml;
+  uint32_t* xc32 = sml + CS_BM_XC;
+  for (int i = tid; i < (nw + 3) / 4; i += CS_T) reinterpret_cast<uint4*>(bm)[i] = make_uint4(0u, 0u, 0u, 0u);
+  for (int i = tid; i < (nw + 7) / 8; i += CS_T) reinterpret_cast<uint4*>(xc32)[i] = make_uint4(0u, 0u, 0u, 0u);
 #pragma unroll
   for (int r = 0; r < KPT; ++r) {
     const int e = wave * (64 * KPT) + r * 64 + lane;
     w[r] = PADW;
     if (e < B) {
-      const int64_t id = col[e];
-      int64_t key = id - lo;
-      if (key < 0 || key >= (int64_t(1) << a.key_bits) || (uint64_t)id >= (uint64_t)a.V) {
+      int64_t key = id[r] - lo;
+      if (key < 0 || key >= (int64_t(1) << a.key_bits) || (uint64_t)id[r] >= (uint64_t)a.V) {
         bad = true;
         key = key < 0 ? 0 : (int64_t(1) << a.key_bits) - 1;
       }
+      // a key beyond the launch's largest (a clamped id, an id of a neighbouring field) has no bit: radix passes
+      if (nw && key > a.max_key) hot = 1;
       w[r] = ((uint32_t)key << pb) | (uint32_t)e;
     }
   }
@@ -110,11 +160,12 @@ __global__ __launch_bounds__(CS_T, 4) void colsort_kernel(SortCols cols, const i
   const int bsh = wbits > CS_BKB ? wbits - CS_BKB : 0;
   uint32_t* bk = cnt;                                  // [CS_NBK]
   static_assert(CS_NBK == 8 * CS_T && CS_NBK <= CS_W * CS_BINS, "8 buckets per thread, inside the counters");
+  if (!nw) {
 #pragma unroll
-  for (int i = 0; i < 2; ++i) reinterpret_cast<uint4*>(bk)[i * CS_T + tid] = make_uint4(0u, 0u, 0u, 0u);
+    for (int i = 0; i < 2; ++i) reinterpret_cast<uint4*>(bk)[i * CS_T + tid] = make_uint4(0u, 0u, 0u, 0u);
+  }
   // probe: more than CS_PROBE words of a round share lane 0's bucket -> a hot bucket.  Such a column takes the radix
   // passes without counting (64 lanes adding to one LDS address serialise: Zipf heads cost 1.3 us more counting)
-  int hot = 0;
 #pragma unroll
   for (int r = 0; r < KPT; ++r) {
     const bool real = wave * (64 * KPT) + r * 64 + lane < B;
@@ -122,6 +173,235 @@ __global__ __launch_bounds__(CS_T, 4) void colsort_kernel(SortCols cols, const i
     hot |= __popcll(__ballot(real && (w[r] >> bsh) == b0)) > CS_PROBE;
   }
   bool fast = !__syncthreads_or(hot);                 // (uniform over the workgroup, as every test below)
+  if (KPT == 8 && nw && fast) {
+    // ---- bitmap path.  Set the bits; a lookup that finds its bit set is one more than the distinct keys of its word
+    // (the total per word does not depend on the order of arrival).  Here and below every loop issues its LDS
+    // operations back to back and uses the results in a loop of its own: a wave's LDS operations complete in order, so
+    // the 8 of a loop are waited for once.
+    uint32_t was[KPT];
+#pragma unroll
+    for (int r = 0; r < KPT; ++r) {
+      const uint32_t key = w[r] >> pb, bit = 1u << (key & 31u);
+      was[r] = 0u;
+      if (wave * (64 * KPT) + r * 64 + lane < B) was[r] = atomicOr(&bm[key >> 5], bit) & bit;
+    }
+#pragma unroll
+    for (int r = 0; r < KPT; ++r) {
+      const uint32_t wd = w[r] >> (pb + 5);
+      if (was[r]) atomicAdd(&xc32[wd >> 1], (wd & 1u) ? 0x10000u : 1u);
+    }
+    __syncthreads();
+    SSTAMP(12);
+    // scan: thread tid owns the pairs of words CS_BM_PPT tid ...  A = distinct keys | extras << 16 and
+    // S = slow words | slow lookups << 16 (a slow word: one with extras; all of its lookups are slow); no field passes
+    // B <= 8192
+    const int npairs = (nw + 1) >> 1;
+    const uint2* bm2 = reinterpret_cast<const uint2*>(bm);
+    uint2 bw[CS_BM_PPT];
+    uint32_t xw[CS_BM_PPT];
+#pragma unroll
+    for (int i = 0; i < CS_BM_PPT; ++i) {
+      const int p = min(tid * CS_BM_PPT + i, npairs - 1);
+      bw[i] = bm2[p];
+      xw[i] = xc32[p];
+    }
+    uint32_t accA = 0, accS = 0;
+#pragma unroll
+    for (int i = 0; i < CS_BM_PPT; ++i) {
+      if (tid * CS_BM_PPT + i >= npairs) {
+        bw[i] = make_uint2(0u, 0u);
+        xw[i] = 0u;
+      }
+      const uint32_t x0 = xw[i] & 0xFFFFu, x1 = xw[i] >> 16;
+      const uint32_t c0 = (uint32_t)__popc(bw[i].x), c1 = (uint32_t)__popc(bw[i].y);
+      accA += c0 + c1 + ((x0 + x1) << 16);
+      accS += (x0 ? 1u + ((c0 + x0) << 16) : 0u) + (x1 ? 1u + ((c1 + x1) << 16) : 0u);
+    }
+    uint32_t inA = accA, inS = accS;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t tA = __shfl_up(inA, o, 64), tS = __shfl_up(inS, o, 64);
+      if (lane >= o) {
+        inA += tA;
+        inS += tS;
+      }
+    }
+    uint32_t* wtotS = sml + CS_BM_WTOT;
+    if (lane == 63) {
+      wtot[wave] = inA;
+      wtotS[wave] = inS;
+    }
+    __syncthreads();
+    uint32_t A = inA - accA, S = inS - accS, allA = 0, allS = 0;
+#pragma unroll
+    for (int q = 0; q < CS_W; ++q) {
+      const uint32_t tA = wtot[q], tS = wtotS[q];
+      if (q < wave) {
+        A += tA;
+        S += tS;
+      }
+      allA += tA;
+      allS += tS;
+    }
+    const uint32_t nslow = allS >> 16;                   // (uniform: every thread sums the same totals)
+    if (nslow <= (uint32_t)CS_BM_CAP) {
+      const int all = (int)(allA & 0xFFFFu);
+      unsigned short* pu = reinterpret_cast<unsigned short*>(sml + CS_BM_PU);
+      uint32_t* list = sml + CS_BM_LIST;
+      uint2* rec = reinterpret_cast<uint2*>(sml + CS_BM_REC);
+      // the prefixes take the places of the counts
+#pragma unroll
+      for (int i = 0; i < CS_BM_PPT; ++i) {
+        const int p = tid * CS_BM_PPT + i;
+        if (p < npairs) {
+          const uint32_t xs[2] = {xw[i] & 0xFFFFu, xw[i] >> 16};
+          const uint32_t cs[2] = {(uint32_t)__popc(bw[i].x), (uint32_t)__popc(bw[i].y)};
+          uint32_t o[2];
+          pu[p] = (unsigned short)(A & 0xFFFFu);
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            o[h] = A >> 16;                              // extras before this word (< 8192)
+            if (xs[h]) {
+              o[h] = 0x8000u | (S & 0xFFFFu);
+              rec[S & 0xFFFFu] = make_uint2((A >> 16) | (S & 0xFFFF0000u), S >> 16);
+              S += 1u + ((cs[h] + xs[h]) << 16);
+            }
+            A += cs[h] + (xs[h] << 16);
+          }
+          xc32[p] = o[0] | (o[1] << 16);
+        }
+      }
+      __syncthreads();
+      SSTAMP(13);
+      // rank: run = distinct keys below the lookup's; a fast lookup is its run's head at run + the extras before its
+      // word.  A slow lookup only appends its sort word to its word's segment of the list (order arbitrary).
+      const unsigned short* xc16 = reinterpret_cast<const unsigned short*>(xc32);
+      uint32_t xv[KPT], run[KPT], pos[KPT];
+#pragma unroll
+      for (int c0 = 0; c0 < KPT; c0 += 4) {              // (4 rounds at a time, as the radix passes take 8: registers)
+        uint32_t b0[4], b1[4];                           // the pair of bitmap words (two scalars: no indexed struct)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int r = c0 + q;
+          const bool real = wave * (64 * KPT) + r * 64 + lane < B;
+          const uint32_t wd = real ? w[r] >> (pb + 5) : 0u;
+          const uint2 t = bm2[wd >> 1];
+          b0[q] = t.x;
+          b1[q] = t.y;
+          xv[r] = real ? (uint32_t)xc16[wd] : 0u;
+          run[r] = pu[wd >> 1];
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int r = c0 + q;
+          pos[r] = 0u;
+          if (xv[r] & 0x8000u) pos[r] = atomicAdd(&rec[xv[r] & 0x7FFFu].y, 1u);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int r = c0 + q;
+          if (xv[r] & 0x8000u) {
+            list[pos[r]] = w[r];
+          } else {
+            const uint32_t key = w[r] >> pb, wd = key >> 5, below = (1u << (key & 31u)) - 1u;
+            const uint32_t odd = 0u - (wd & 1u);          // all ones for the pair's second word
+            run[r] += (uint32_t)__popc(b0[q] & odd) + (uint32_t)__popc(((b1[q] & odd) | (b0[q] & ~odd)) & below);
+            pos[r] = run[r] + xv[r];
+          }
+        }
+      }
+      __syncthreads();                                   // the segments are complete
+      // slow lookups, one per thread from the list: sorted position = keys and extras before its word + the smaller sort
+      // words of its segment; head iff none of those has its key.  Both are counts over a complete segment: the order
+      // of the appends does not show.
+      uint32_t s_w = 0, s_pos = 0, s_run = 0;
+      bool s_hd = false;
+      if ((uint32_t)tid < nslow) {
+        s_w = list[tid];
+        const uint32_t key = s_w >> pb, wd = key >> 5, below = (1u << (key & 31u)) - 1u;
+        const uint2 b = bm2[wd >> 1];
+        const uint32_t odd = 0u - (wd & 1u), bx = b.x, by = b.y;
+        const uint32_t base = pu[wd >> 1] + (uint32_t)__popc(bx & odd);
+        const uint2 t = rec[xc16[wd] & 0x7FFFu];
+        const uint32_t sb = t.x >> 16, end = min(t.y, (uint32_t)CS_BM_CAP);   // (the segment; never past the list)
+        uint32_t v[4], c = 0, same = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[q] = list[min(sb + q, (uint32_t)CS_BM_CAP - 1u)];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const bool lt = sb + q < end && v[q] < s_w;
+          c += lt ? 1u : 0u;
+          same += (lt && (v[q] >> pb) == key) ? 1u : 0u;
+        }
+        for (uint32_t j = sb + 4; j < end; ++j) {
+          const uint32_t u = list[j];
+          c += u < s_w ? 1u : 0u;
+          same += (u < s_w && (u >> pb) == key) ? 1u : 0u;
+        }
+        s_run = base + (uint32_t)__popc(((by & odd) | (bx & ~odd)) & below);
+        s_pos = base + (t.x & 0xFFFFu) + c;
+        s_hd = same == 0u;
+      }
+      __syncthreads();                                   // bitmap, xc and pu are dead: the staging takes their place
+      uint32_t* st_uq = sml;
+      unsigned short* st_sg = reinterpret_cast<unsigned short*>(sml + NW);
+      unsigned short* st_pm = st_sg + NW;
+      int32_t* permf = a.perm + (int64_t)f * B;
+#pragma unroll
+      for (int r = 0; r < KPT; ++r) {
+        const int e = wave * (64 * KPT) + r * 64 + lane;
+        if (e < B && !(xv[r] & 0x8000u)) {
+          st_pm[pos[r]] = (unsigned short)e;
+          st_uq[run[r]] = w[r] >> pb;
+          st_sg[run[r]] = (unsigned short)pos[r];
+          if (a.dloc) a.dloc[(int64_t)f * B + e] = (int32_t)run[r];
+        }
+      }
+      if ((uint32_t)tid < nslow) {
+        const uint32_t e = s_w & pmask;
+        st_pm[s_pos] = (unsigned short)e;
+        if (s_hd) {
+          st_uq[s_run] = s_w >> pb;
+          st_sg[s_run] = (unsigned short)s_pos;
+        }
+        if (a.dloc) a.dloc[(int64_t)f * B + e] = (int32_t)(s_run | (s_hd ? 0u : 0x80000000u));
+      }
+      __syncthreads();
+      SSTAMP(14);
+      if ((B & 7) == 0) {
+        if (tid * 8 < B) {
+          const uint4 q = reinterpret_cast<const uint4*>(st_pm)[tid];
+          *reinterpret_cast<int4*>(permf + tid * 8) = make_int4((int)(q.x & 0xFFFFu), (int)(q.x >> 16), (int)(q.y & 0xFFFFu), (int)(q.y >> 16));
+          *reinterpret_cast<int4*>(permf + tid * 8 + 4) = make_int4((int)(q.z & 0xFFFFu), (int)(q.z >> 16), (int)(q.w & 0xFFFFu), (int)(q.w >> 16));
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < KPT; ++r)
+          if (r * CS_T + tid < B) permf[r * CS_T + tid] = (int32_t)st_pm[r * CS_T + tid];
+      }
+#pragma unroll
+      for (int r = 0; r < KPT; ++r) {
+        const int i = r * CS_T + tid;
+        if (i < B) {
+          if (i < all) {
+            a.col_uid[(int64_t)f * B + i] = lo + (int64_t)st_uq[i];
+            a.col_seg[(int64_t)f * (B + 1) + i] = (int32_t)st_sg[i];
+          } else {
+            a.col_seg[(int64_t)f * (B + 1) + i] = (int32_t)B;
+          }
+        }
+      }
+      if (tid == 0) a.col_seg[(int64_t)f * (B + 1) + B] = (int32_t)B;
+      if (tid == 0) a.col_nu[f] = all;
+      SSTAMP_END();
+      return;
+    }
+    // more slow lookups than the list holds: the bucket path from its start (every thread is past its reads of the
+    // bitmap: the barrier of the scan)
+#pragma unroll
+    for (int i = 0; i < 2; ++i) reinterpret_cast<uint4*>(bk)[i * CS_T + tid] = make_uint4(0u, 0u, 0u, 0u);
+    __syncthreads();
+  }
   if (fast) {
 #pragma unroll
     for (int r = 0; r < KPT; ++r)
@@ -348,13 +628,7 @@ __global__ __launch_bounds__(CS_T, 4) void colsort_kernel(SortCols cols, const i
   }
   if (tid == 0) a.col_seg[(int64_t)f * (B + 1) + B] = (int32_t)B;
   if (tid == 0) a.col_nu[f] = all;
-  SSTAMP(8);
-#ifdef REC_SORT_STAMPS
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  SSTAMP(9);
-  if (threadIdx.x == 1023) g_sort_stamps[blockIdx.x * 16 + 10] = wall_clock64();
-  if (threadIdx.x == 512) g_sort_stamps[blockIdx.x * 16 + 11] = wall_clock64();
-#endif
+  SSTAMP_END();
 }
 
 // key and position bits of the sort words: REC_OK, or the status the plan calls return
@@ -383,6 +657,22 @@ extern "C" size_t rec_colsort_workspace_bytes(int64_t B, int F) {
   return 256;      // the sort runs in LDS; the argument is kept for callers written against the three-kernel version
 }
 
+// bitmap words of a launch: ceil((max_key + 1) / 32) when the bitmap path takes it, else 0
+static inline int colsort_bitmap_words(int64_t B, int64_t max_key) {
+  const int64_t nw = (max_key + 32) / 32;
+  return B <= 8192 && nw <= CS_BM_WORDS ? (int)nw : 0;
+}
+
+extern "C" int rec_colsort_bitmap_limits(int64_t B, int64_t max_key, int* words, int* slow_cap) {
+  if (!words || !slow_cap) return REC_E_ARG;
+  int key_bits = 0, pos_bits = 0;
+  const int rc = colsort_widths(B, max_key, &key_bits, &pos_bits);
+  if (rc != REC_OK) return rc;
+  *words = colsort_bitmap_words(B, max_key);
+  *slow_cap = CS_BM_CAP;
+  return REC_OK;
+}
+
 extern "C" int rec_colsort_digits(int64_t B, int64_t max_key, int* passes, int* digit_bits) {
   if (!passes || !digit_bits) return REC_E_ARG;
   int key_bits = 0, pos_bits = 0;
@@ -409,7 +699,8 @@ static int colsort_plan(const int64_t* const* cols_host, int F, int64_t B, int64
     if (!cols_host[f]) return REC_E_ARG;
     cp.p[f] = cols_host[f];
   }
-  ColSortArgs a{B, F, V, key_bits, pos_bits, passes, digit_bits, perm, col_uid, col_seg, col_nu, bad_flag, dloc};
+  ColSortArgs a{B, F, V, key_bits, pos_bits, passes, digit_bits, perm, col_uid, col_seg, col_nu, bad_flag, max_key,
+                colsort_bitmap_words(B, max_key), dloc};
   hipStream_t st = as_stream(stream);
   // one workgroup per column (LDS radix sort + run heads in one launch); B <= 16384 = 16 x 1024
   const int kpt = B <= 8192 ? 8 : 16;

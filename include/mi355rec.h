@@ -350,6 +350,12 @@ size_t rec_colsort_workspace_bytes(int64_t B, int F);
 /* Radix passes of that sort for a batch of B and a largest key max_key: *passes passes of at most *digit_bits bits
  * (<= 10) over the key; the status the plan calls return for (B, max_key) otherwise. */
 int rec_colsort_digits(int64_t B, int64_t max_key, int* passes, int* digit_bits);
+/* Bitmap path of that sort (columns without a hot bucket are ranked through an LDS bitmap of the launch's key range
+ * instead of being sorted): *words = 32-bit bitmap words a launch of (B, max_key) uses = ceil((max_key + 1) / 32), or 0
+ * when the launch does not take the path (B > 8192, or a key range beyond 425,984 keys); *slow_cap = the most lookups
+ * of a column that may share a 32-key word with a duplicated id (a column with more takes the bucket path).  Statuses
+ * as rec_colsort_digits. */
+int rec_colsort_bitmap_limits(int64_t B, int64_t max_key, int* words, int* slow_cap);
 int rec_colsort_plan_i64(const int64_t* const* cols_host, int F, int64_t B, int64_t V, const int64_t* col_lo,
                          int64_t max_key, int32_t* perm, int64_t* col_uid, int32_t* col_seg, int32_t* col_nu,
                          int* bad_flag, void* workspace, void* stream);

@@ -6,13 +6,15 @@ of its own), at the bench's launch shape: GROUP batches of 26 columns per launch
     python scripts/exp/sort_stamps.py [--dist zipf] [--k 9] [--lib PATH]
 
 Stamps are wall_clock64 ticks (100 MHz) of thread 0 of every workgroup, relative to the earliest start in the launch;
-slots a kernel does not write are not printed."""
+slots a kernel does not write are not printed (a column on the bitmap path writes the "bitmap:" slots and none of the
+sorted paths' phases)."""
 import argparse, ctypes as C, os, subprocess, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 SRC = os.path.join(ROOT, "explicit-tf2-recommendation_amd", "csrc", "colsort.hip")
-NAMES = {0: "start", 1: "ids loaded", 2: "counted / pass 1", 3: "scattered / pass 2", 4: "ranked / pass 3", 5: "pass 4",
+NAMES = {0: "start", 1: "ids loaded", 12: "bitmap: bits set", 13: "bitmap: words scanned", 14: "bitmap: ranked and staged",
+         2: "counted / pass 1", 3: "scattered / pass 2", 4: "ranked / pass 3", 5: "pass 4",
          7: "run heads found", 8: "outputs issued", 9: "outputs drained", 10: "thread 1023 end", 11: "thread 512 end"}
 
 ap = argparse.ArgumentParser()
