@@ -25,12 +25,37 @@ namespace {
 
 constexpr int LD = 32;        // fused row stride (floats)
 
+// Phase stamps of the direct-mode post launch (diagnostic builds, -DREC_POST_STAMPS; scripts/exp/post_stamps.py reads
+// them): lane 0 of every wave writes the wall clock (100 MHz) at the phases of its job, 8 words per wave; the reduce
+// workgroups come first in the buffer, then the fix-up workgroups, wherever they sit in the grid (PSTAMP_WG).  PSTAMP_WAIT
+// makes "landed" mean what it says: the wave waits for its outstanding loads before it stamps.  Off: all are nothing.
+#ifdef REC_POST_STAMPS
+#define PSTAMP_WG(wg_) const int pstamp_wg = (wg_)
+#define PSTAMP(A, k_)                                                                                          \
+  do {                                                                                                         \
+    if ((threadIdx.x & 63) == 0)                                                                               \
+      (A).stamps[((int64_t)pstamp_wg * 16 + (threadIdx.x >> 6)) * 8 + (k_)] = wall_clock64();                  \
+  } while (0)
+#ifdef REC_POST_STAMPS_NOWAIT                            // (stamps where the waves are anyway: no wait added)
+#define PSTAMP_WAIT() do {} while (0)
+#else
+#define PSTAMP_WAIT() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
+#endif
+#else
+#define PSTAMP_WG(wg_) do {} while (0)
+#define PSTAMP(A, k_) do {} while (0)
+#define PSTAMP_WAIT() do {} while (0)
+#endif
+
 // fixed-order sum of the per-workgroup partials.  1024 threads = 16 slices x 64 lanes; lane owns 4 consecutive
 // outputs (float4), slice q adds workgroups q, q+16, q+32, ... (independent 16-B loads), then the 16 slices are
 // added in slice order through LDS.
 struct ReduceArgs {
   const float* dK0part; const float* small; int nwg; int D; int64_t B;
   float* dK0; float* dK1; float* db0; float* db1; float* dK2; float* db2; float* dbias; float* loss;
+#ifdef REC_POST_STAMPS
+  unsigned long long* stamps;
+#endif
 };
 
 // 1024 threads = 64 slices x 16 lanes; a lane owns 4 consecutive outputs (float4), slice q adds the partials of
@@ -54,6 +79,8 @@ __device__ __forceinline__ void reduce_body(const ReduceArgs& r, int bidx) {
   __shared__ float4 red[RS][RC];
   __shared__ float4 red2[8][RC];
   const int lane = threadIdx.x & (RC - 1), q = threadIdx.x / RC;
+  PSTAMP_WG(bidx);
+  PSTAMP(r, 0);
   const int64_t n0 = (int64_t)D * U1;                  // multiple of 4
   const int nb0 = (int)((n0 / 4 + RC - 1) / RC);       // blocks that cover dK0
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -87,8 +114,11 @@ __device__ __forceinline__ void reduce_body(const ReduceArgs& r, int bidx) {
       acc.x += x.x; acc.y += x.y; acc.z += x.z; acc.w += x.w;
     }
   }
+  PSTAMP_WAIT();
+  PSTAMP(r, 1);                                        // partials landed (and added)
   red[q][lane] = acc;
   __syncthreads();
+  PSTAMP(r, 2);
   if (q < 8) {                                         // slices 8q .. 8q+7, in order
     float4 s = red[8 * q][lane];
 #pragma unroll
@@ -108,6 +138,7 @@ __device__ __forceinline__ void reduce_body(const ReduceArgs& r, int bidx) {
   }
   if (!is_small) {
     if (e4 * 4 < n0) *reinterpret_cast<float4*>(dK0 + e4 * 4) = s;
+    PSTAMP(r, 3);
     return;
   }
   if (e4 * 4 >= SMALL) return;
@@ -122,6 +153,7 @@ __device__ __forceinline__ void reduce_body(const ReduceArgs& r, int bidx) {
     else if (k == SM_DB2) { db2[0] = sv[i]; dbias[0] = sv[i]; }
     else if (k == SM_LOSS) loss[0] = sv[i] / (float)B;
   }
+  PSTAMP(r, 3);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -147,6 +179,9 @@ struct ColSegArgs {
   // exact lazy evaluation of Keras' dense sweep (rec_adam_keras_catchup_f32): last[row] = the step whose update the row
   // holds; a touched row holds step *step_dev afterwards.  null: plain touched-rows Adam
   int32_t* last; const int64_t* step_dev;
+#ifdef REC_POST_STAMPS
+  unsigned long long* stamps;
+#endif
 };
 
 // m <- b1 m + (1-b1) g ; v <- b2 v + (1-b2) g^2 ; var <- var - lr_t m / (sqrt(v) + eps)   (rec_adam_rows_f32's formula:
@@ -279,7 +314,9 @@ __device__ __forceinline__ void colseg_body(const ColSegArgs& k, int bidx) {
 }
 
 
-// ---- direct mode: what is left for the launch after the fused kernel.  ONE LANE per run (slot) of the plan:
+// ---- direct mode: what is left for the launch after the fused kernel.  One lane per run (slot) of the plan
+// (fixup_body), or four consecutive runs per lane where B is a multiple of 1024 and no lazy Adam rides along
+// (fixq_body, further down); in both:
 //   a run of one lookup (almost all of them with uniform ids): g_w = gz of that lookup, uniq_ids = its id -- coalesced
 //     stores, the value row is already in place;
 //   a pair: the lane adds the second member's value row to the head's row itself;
@@ -289,8 +326,8 @@ __device__ __forceinline__ void colseg_body(const ColSegArgs& k, int bidx) {
 //   slots beyond the column's runs: the zero-padded tail.
 constexpr int FIX_T = 1024, FIX_HUGE = 128, FIX_SHORT = 17, FIX_SKEW = 256;
 // slot t of a column (thread order) -> run u, twice.
-// fix_deal: the mapping of the FAST path (ids, single lookups, pairs, the padded tail -- nearly everything, and all of it
-// coalesced stores): a wave takes 4 consecutive runs from each sixteenth of the column, so that plan words arrive and ids
+// fix_deal: the mapping of fixup_body's FAST path (ids, single lookups, pairs, the padded tail -- nearly everything, and
+// all of it coalesced stores): a wave takes 4 consecutive runs from each sixteenth of the column, so that plan words arrive and ids
 // leave as 16-byte pieces, and a workgroup owns whole lines of uniq_ids / g_w.  (Interleaving the waves of different
 // workgroups here cost 2.3 us with uniform ids: every line of the outputs was then written in pieces by four CUs.)
 // fix_spread: the mapping under which the runs of MORE THAN TWO members are looked at a second time and summed: lane l of
@@ -317,6 +354,230 @@ __device__ __forceinline__ int fix_group_src(unsigned long long mask, int lane) 
   }
   return src;
 }
+// what the paths for runs of more than two members keep in LDS.  Runs of more than FIX_HUGE members (Zipf heads: the
+// hottest id of a column holds ~10 % of its lookups) are left to the WHOLE workgroup: at most B / FIX_HUGE <= 128 of them
+// exist in a column
+struct FixShared {
+  int huge_n, huge_s0[128], huge_s1[128], huge_u[128];
+  float huge_gz[128];
+  float4 hpart[FIX_T / 64][4];
+  float hw_s[FIX_T / 64];
+};
+
+// The runs of `longm` (one bit per owning lane: members s0b+1 .. s1b-1 of perm, slot ub, gz of the head accwb), one at a
+// time, by the whole wave: lane = (member slot r of 16, chunk c of 4).  IX: the integer the offsets are formed in.
+// HEADGZ: the wave reads gz of the run's head itself, beside the members (accwb is not used).  The head's row is asked
+// for before the members: it is only needed after the butterfly, and asked for there it was a round trip of its own
+template <typename IX, bool HEADGZ = false>
+__device__ __forceinline__ void fix_wave_runs(const ColSegArgs& k, const int32_t* __restrict__ pf, int f, IX before,
+                                              unsigned long long longm, int s0b, int s1b, int ub, float accwb) {
+  const float4* __restrict__ vals = k.vals;
+  const float* __restrict__ gz = k.gz;
+  float4* __restrict__ g_embed = k.g_embed;
+  const int F = k.F;
+  const int lane = threadIdx.x & 63, r = lane >> 2, c = lane & 3;
+#ifdef ABL_NOLONG
+  longm = 0;
+#endif
+  while (longm) {
+    const int src = __ffsll((long long)longm) - 1;
+    longm &= longm - 1;
+    const int rs0 = __shfl(s0b, src, 64), rs1 = __shfl(s1b, src, 64);
+    const int ru = __shfl(ub, src, 64);
+    float rgz = __shfl(accwb, src, 64);
+    const IX rdst = before + ru;
+    float4 h = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (r == 0) h = g_embed[rdst * 4 + c];
+    if (HEADGZ) rgz = gz[pf[rs0]];
+    float4 pa = make_float4(0.f, 0.f, 0.f, 0.f);
+    float pw = 0.f;
+#pragma unroll 4
+    for (int s = rs0 + 1 + r; s < rs1; s += 16) {              // independent loads: several rounds in flight
+      const IX b = pf[s];
+      const float4 x = vals[(b * F + f) * 4 + c];
+      pa.x += x.x; pa.y += x.y; pa.z += x.z; pa.w += x.w;
+      pw += gz[b];
+    }
+#pragma unroll
+    for (int o = 4; o < 64; o <<= 1) {                         // fixed butterfly over the 16 member slots
+      pa.x += __shfl_xor(pa.x, o, 64); pa.y += __shfl_xor(pa.y, o, 64);
+      pa.z += __shfl_xor(pa.z, o, 64); pa.w += __shfl_xor(pa.w, o, 64);
+      pw += __shfl_xor(pw, o, 64);
+    }
+    if (r == 0) {
+      h.x += pa.x; h.y += pa.y; h.z += pa.z; h.w += pa.w;
+      g_embed[rdst * 4 + c] = h;
+      const float wsum = rgz + pw;
+      if (c == 0) k.g_w[rdst] = wsum;
+    }
+  }
+}
+
+// ---- runs of more than two members of a SKEWED column (more than FIX_SKEW lookups beyond the first of their runs): the
+// second look, under fix_spread.  Slot t of the column (this workgroup's 1024, one per thread; sh.huge_n was zeroed
+// before a barrier).  (A column without skew -- uniform ids: ~90 pairs -- has next to nothing to balance, and the second
+// look costs 1.3 us of scattered plan-word loads: its few longer runs are added where the fast path found them.)
+template <typename IX>
+__device__ __forceinline__ void fix_skew_runs(const ColSegArgs& k, FixShared& sh, const int32_t* __restrict__ pf, int f,
+                                              IX before, int nu, bool in_col, int t) {
+  const float4* __restrict__ vals = k.vals;
+  const float* __restrict__ gz = k.gz;
+  float4* __restrict__ g_embed = k.g_embed;
+  const int64_t B = k.B;
+  const int F = k.F;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int ub = fix_spread(t, B);
+  int s0b = 0, s1b = 0;
+  if (in_col && ub < nu) {
+    s0b = k.col_seg[(IX)f * (IX)(B + 1) + ub];
+    s1b = k.col_seg[(IX)f * (IX)(B + 1) + ub + 1];
+  }
+  const int lenb = s1b - s0b;
+  float accwb = 0.f;                                            // gz of the run's head
+  if (lenb > 2) accwb = gz[pf[s0b]];
+  if (lenb > FIX_HUGE) {                                         // (which entry a run gets does not matter: every run is
+    const int i = atomicAdd(&sh.huge_n, 1);                      // summed on its own, in a fixed order)
+    if (i < 128) { sh.huge_s0[i] = s0b; sh.huge_s1[i] = s1b; sh.huge_u[i] = ub; sh.huge_gz[i] = accwb; }
+  }
+  const int r = lane >> 2, c = lane & 3;
+  // runs of 3..FIX_SHORT members: FOUR lanes per run (one 16-byte chunk of the row each), 16 runs per round; head + member
+  // 2 + member 3 ... in member order, four members' loads in flight at a time.  (One lane per run walking its members
+  // paid two dependent round trips per member: up to 14 in a row for a run of 8 -- with Zipf ids every wave has a few.)
+  {
+    unsigned long long shortm = __ballot(lenb > 2 && lenb <= FIX_SHORT);
+#ifdef ABL_NOSHORT
+    shortm = 0;
+#endif
+    while (shortm) {                                            // wave-uniform
+      const int src = fix_group_src(shortm, lane);
+      const bool has = src >= 0;
+      const int sl = has ? src : 0;
+      const int gs0 = __shfl(s0b, sl, 64), gs1_ = __shfl(s1b, sl, 64), gu = __shfl(ub, sl, 64);
+      float wsum = __shfl(accwb, sl, 64);
+      const int gs1 = has ? gs1_ : 0;                            // (the shuffles themselves need every lane)
+      const IX gdst = before + gu;
+      float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (has) acc = g_embed[gdst * 4 + c];
+      for (int sp = gs0 + 1; __any(sp < gs1); sp += 4) {
+        if (sp < gs1) {
+          int e[4];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) e[j] = pf[sp + j < gs1 ? sp + j : gs1 - 1];
+          float4 xm[4];
+          float gm[4];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            xm[j] = vals[((IX)e[j] * F + f) * 4 + c];
+            gm[j] = gz[e[j]];
+          }
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            if (sp + j < gs1) {
+              acc.x += xm[j].x; acc.y += xm[j].y; acc.z += xm[j].z; acc.w += xm[j].w;
+              wsum += gm[j];
+            }
+          }
+        }
+      }
+      if (has) {
+        g_embed[gdst * 4 + c] = acc;
+        if (c == 0) k.g_w[gdst] = wsum;
+      }
+      for (int i = 0; i < 16 && shortm; ++i) shortm &= shortm - 1;
+    }
+  }
+  fix_wave_runs<IX>(k, pf, f, before, __ballot(lenb > FIX_SHORT && lenb <= FIX_HUGE), s0b, s1b, ub, accwb);
+  // huge runs, up to 16 at a time, by the whole workgroup: with n of them in a round, 16 / n waves share a run (wave of run
+  // h, sub-index sw: member slots 16 sw + r, stride 16 * waves-per-run, four members per lane in flight); the waves'
+  // partial rows meet in LDS and the run's first wave adds them in wave order.  (One wave walking the 848 members of a
+  // Zipf head 64 at a time was a 13-round dependent chain; the whole workgroup taking the huge runs one after the other
+  // still paid ~5 round trips per run: 16 us of the 34-us launch with Zipf ids.)
+  __syncthreads();
+#ifdef ABL_NOHUGE
+  const int n_huge = 0;
+#else
+  const int n_huge = sh.huge_n < 128 ? sh.huge_n : 128;
+#endif
+  const int wv = tid >> 6;
+  constexpr int NWV_F = FIX_T / 64;
+  // more than one round: the list goes into ascending run order first.  The round a run falls in fixes how many waves
+  // add it (16 / nr) and so the order of its additions; taken in the order the atomics above landed, a run's sum changed
+  // in its last bits from one launch to the next.  (One round: every run gets the same 16 / nr waves wherever it sits.)
+  if (n_huge > NWV_F) {                                          // (uniform over the workgroup)
+    int hs0 = 0, hs1 = 0, hu = 0, rk = 0;
+    float hg = 0.f;
+    if (tid < n_huge) {
+      hs0 = sh.huge_s0[tid]; hs1 = sh.huge_s1[tid]; hu = sh.huge_u[tid]; hg = sh.huge_gz[tid];
+      for (int j = 0; j < n_huge; ++j) rk += sh.huge_u[j] < hu ? 1 : 0;   // runs are distinct: ranks 0 .. n_huge-1
+    }
+    __syncthreads();
+    if (tid < n_huge) { sh.huge_s0[rk] = hs0; sh.huge_s1[rk] = hs1; sh.huge_u[rk] = hu; sh.huge_gz[rk] = hg; }
+    __syncthreads();
+  }
+  for (int h0 = 0; h0 < n_huge; h0 += NWV_F) {
+    const int nr = n_huge - h0 < NWV_F ? n_huge - h0 : NWV_F;    // runs of this round
+    const int wpr = NWV_F / nr;                                  // waves per run
+    const int hl = wv / wpr, sw = wv - hl * wpr;
+    const bool mine = hl < nr;
+    const int h = h0 + (mine ? hl : 0);
+    const int rs0 = sh.huge_s0[h], rs1 = mine ? sh.huge_s1[h] : 0;
+    float4 pa = make_float4(0.f, 0.f, 0.f, 0.f);
+    float pw = 0.f;
+    const int stride = 16 * wpr;
+    // four members per lane and round in flight (eight cost 25 more registers: at 81 the launch dropped to one workgroup
+    // per CU and the uniform step lost 0.7 us)
+    for (int base = rs0 + 1 + 16 * sw + r; base < rs1; base += 4 * stride) {
+      int bm[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int sidx = base + j * stride;
+        bm[j] = pf[sidx < rs1 ? sidx : rs1 - 1];
+      }
+      float4 xm[4];
+      float gm[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        xm[j] = vals[((IX)bm[j] * F + f) * 4 + c];
+        gm[j] = gz[bm[j]];
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (base + j * stride < rs1) {
+          pa.x += xm[j].x; pa.y += xm[j].y; pa.z += xm[j].z; pa.w += xm[j].w;
+          pw += gm[j];
+        }
+      }
+    }
+#pragma unroll
+    for (int o = 4; o < 64; o <<= 1) {
+      pa.x += __shfl_xor(pa.x, o, 64); pa.y += __shfl_xor(pa.y, o, 64);
+      pa.z += __shfl_xor(pa.z, o, 64); pa.w += __shfl_xor(pa.w, o, 64);
+      pw += __shfl_xor(pw, o, 64);
+    }
+    float4 hsum = make_float4(0.f, 0.f, 0.f, 0.f);
+    const IX rdst = before + sh.huge_u[h];
+    const bool fin = mine && sw == 0 && r == 0;                  // the run's first wave, one lane per chunk
+    if (fin) hsum = g_embed[rdst * 4 + c];                       // (in flight across the barrier)
+    if (r == 0) {
+      sh.hpart[wv][c] = pa;
+      if (c == 0) sh.hw_s[wv] = pw;
+    }
+    __syncthreads();
+    if (fin) {
+      float wsum = sh.huge_gz[h];
+      for (int q = 0; q < wpr; ++q) {
+        const float4 x = sh.hpart[wv + q][c];
+        hsum.x += x.x; hsum.y += x.y; hsum.z += x.z; hsum.w += x.w;
+        wsum += sh.hw_s[wv + q];
+      }
+      g_embed[rdst * 4 + c] = hsum;
+      if (c == 0) k.g_w[rdst] = wsum;
+    }
+    __syncthreads();
+  }
+}
+
+// The one-run-per-lane body: every B that is no multiple of 1024, and every launch with the lazy Adam.
 __device__ __forceinline__ void fixup_body(const ColSegArgs& k_in, int bidx) {
   ColSegArgs k = k_in;
   if (k.lr_t_dev) k.lr_t = *k.lr_t_dev;
@@ -325,21 +586,19 @@ __device__ __forceinline__ void fixup_body(const ColSegArgs& k_in, int bidx) {
   const int64_t B = k.B;
   const int F = k.F;
   float4* __restrict__ g_embed = k.g_embed;
-  const int tid = threadIdx.x, lane = tid & 63;
+  const int tid = threadIdx.x;
   const int per_col = (int)((B + FIX_T - 1) / FIX_T);           // workgroups per column
+  PSTAMP_WG((int)gridDim.x - F * per_col + bidx);
+  PSTAMP(k, 0);
   const int f = bidx / per_col;
   const int t = (bidx - f * per_col) * FIX_T + tid;             // slot of the column before the deal
   const int u = fix_deal(t, B);
   __shared__ int nu_s[REC_MAX_COLS];
-  // runs of more than FIX_HUGE members (Zipf heads: the hottest id of a column holds ~10 % of its lookups) are left to
-  // the WHOLE workgroup: at most B / FIX_HUGE <= 128 of them exist in a column
-  __shared__ int huge_n, huge_s0[128], huge_s1[128], huge_u[128];
-  __shared__ float huge_gz[128];
-  __shared__ float4 hpart[FIX_T / 64][4];
-  __shared__ float hw_s[FIX_T / 64];
+  __shared__ FixShared sh;
   if (tid < F) nu_s[tid] = k.col_nu[tid];
-  if (tid == 0) huge_n = 0;
+  if (tid == 0) sh.huge_n = 0;
   __syncthreads();
+  PSTAMP(k, 1);
   int64_t before = 0, total = 0;
   for (int q = 0; q < F; ++q) {
     const int nq = nu_s[q];
@@ -360,8 +619,15 @@ __device__ __forceinline__ void fixup_body(const ColSegArgs& k_in, int bidx) {
   const bool adam = k.table != nullptr;
   float accw = 0.f;                                             // gz of the run's head
   if (live) {
-    accw = gz[pf[s0]];
+    PSTAMP_WAIT();
+    PSTAMP(k, 2);
+    const int hb = pf[s0];
+    PSTAMP_WAIT();
+    PSTAMP(k, 3);
+    accw = gz[hb];
     const int64_t id = k.col_uid[(int64_t)f * B + u];
+    PSTAMP_WAIT();
+    PSTAMP(k, 4);
     if (len == 2) {                                             // a pair (nearly every multi-member run of a uniform batch):
       const int64_t b2 = pf[s0 + 1];                            // this lane alone, two dependent round trips
       const float4* r2 = vals + (b2 * F + f) * 4;
@@ -384,197 +650,12 @@ __device__ __forceinline__ void fixup_body(const ColSegArgs& k_in, int bidx) {
     k.g_w[d2] = 0.f;
     k.uniq_ids[d2] = k.col_uid[0];
   }
-  // ---- runs of more than two members: the second look (fix_spread) -- for a column with more than FIX_SKEW lookups
-  // beyond the first of their runs; a column without (uniform ids: ~90 pairs) has next to nothing to balance, and the
-  // second look costs 1.3 us of scattered plan-word loads: its few longer runs are added where the fast path found them
+  PSTAMP(k, 5);
+  // ---- runs of more than two members: a skewed column looks at them a second time (fix_skew_runs); the few of a column
+  // without skew all take the whole-wave path where the fast path found them: no list, no barrier
   const bool skew = B - nu > FIX_SKEW;                           // uniform over the workgroup
-  const int ub = skew ? fix_spread(t, B) : u;
-  int s0b = s0, s1b = s1;
-  if (skew) {
-    s0b = 0; s1b = 0;
-    if (in_col && ub < nu) {
-      s0b = k.col_seg[(int64_t)f * (B + 1) + ub];
-      s1b = k.col_seg[(int64_t)f * (B + 1) + ub + 1];
-    }
-  }
-  const int lenb = s1b - s0b;
-  float accwb = 0.f;                                            // gz of the run's head
-  if (lenb > 2) accwb = skew ? gz[pf[s0b]] : accw;
-  // (without skew the few runs of more than two members all take the whole-wave path below: no list, no barrier)
-  if (skew && lenb > FIX_HUGE) {                                 // (which entry a run gets does not matter: every run is
-    const int i = atomicAdd(&huge_n, 1);                         // summed on its own, in a fixed order)
-    if (i < 128) { huge_s0[i] = s0b; huge_s1[i] = s1b; huge_u[i] = ub; huge_gz[i] = accwb; }
-  }
-  const int r = lane >> 2, c = lane & 3;
-  // runs of 3..FIX_SHORT members: FOUR lanes per run (one 16-byte chunk of the row each), 16 runs per round; head + member
-  // 2 + member 3 ... in member order, four members' loads in flight at a time.  (One lane per run walking its members
-  // paid two dependent round trips per member: up to 14 in a row for a run of 8 -- with Zipf ids every wave has a few.)
-  {
-    unsigned long long shortm = __ballot(skew && lenb > 2 && lenb <= FIX_SHORT);
-#ifdef ABL_NOSHORT
-    shortm = 0;
-#endif
-    while (shortm) {                                            // wave-uniform
-      const int src = fix_group_src(shortm, lane);
-      const bool has = src >= 0;
-      const int sl = has ? src : 0;
-      const int gs0 = __shfl(s0b, sl, 64), gs1_ = __shfl(s1b, sl, 64), gu = __shfl(ub, sl, 64);
-      float wsum = __shfl(accwb, sl, 64);
-      const int gs1 = has ? gs1_ : 0;                            // (the shuffles themselves need every lane)
-      const int64_t gdst = before + gu;
-      float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (has) acc = g_embed[gdst * 4 + c];
-      for (int sp = gs0 + 1; __any(sp < gs1); sp += 4) {
-        if (sp < gs1) {
-          int e[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) e[j] = pf[sp + j < gs1 ? sp + j : gs1 - 1];
-          float4 xm[4];
-          float gm[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            xm[j] = vals[((int64_t)e[j] * F + f) * 4 + c];
-            gm[j] = gz[e[j]];
-          }
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            if (sp + j < gs1) {
-              acc.x += xm[j].x; acc.y += xm[j].y; acc.z += xm[j].z; acc.w += xm[j].w;
-              wsum += gm[j];
-            }
-          }
-        }
-      }
-      if (has) {
-        g_embed[gdst * 4 + c] = acc;
-        if (c == 0) k.g_w[gdst] = wsum;
-      }
-      for (int i = 0; i < 16 && shortm; ++i) shortm &= shortm - 1;
-    }
-  }
-  // long runs, one at a time, by the whole wave: lane = (member slot r of 16, chunk c of 4)
-  unsigned long long longm = __ballot(skew ? (lenb > FIX_SHORT && lenb <= FIX_HUGE) : lenb > 2);
-#ifdef ABL_NOLONG
-  longm = 0;
-#endif
-  while (longm) {
-    const int src = __ffsll((long long)longm) - 1;
-    longm &= longm - 1;
-    const int rs0 = __shfl(s0b, src, 64), rs1 = __shfl(s1b, src, 64);
-    const int ru = __shfl(ub, src, 64);
-    const float rgz = __shfl(accwb, src, 64);
-    const int64_t rdst = before + ru;
-    float4 pa = make_float4(0.f, 0.f, 0.f, 0.f);
-    float pw = 0.f;
-#pragma unroll 4
-    for (int s = rs0 + 1 + r; s < rs1; s += 16) {              // independent loads: several rounds in flight
-      const int64_t b = pf[s];
-      const float4 x = vals[(b * F + f) * 4 + c];
-      pa.x += x.x; pa.y += x.y; pa.z += x.z; pa.w += x.w;
-      pw += gz[b];
-    }
-#pragma unroll
-    for (int o = 4; o < 64; o <<= 1) {                         // fixed butterfly over the 16 member slots
-      pa.x += __shfl_xor(pa.x, o, 64); pa.y += __shfl_xor(pa.y, o, 64);
-      pa.z += __shfl_xor(pa.z, o, 64); pa.w += __shfl_xor(pa.w, o, 64);
-      pw += __shfl_xor(pw, o, 64);
-    }
-    if (r == 0) {
-      float4 h = g_embed[rdst * 4 + c];
-      h.x += pa.x; h.y += pa.y; h.z += pa.z; h.w += pa.w;
-      g_embed[rdst * 4 + c] = h;
-      const float wsum = rgz + pw;
-      if (c == 0) k.g_w[rdst] = wsum;
-    }
-  }
-  // huge runs, up to 16 at a time, by the whole workgroup: with n of them in a round, 16 / n waves share a run (wave of run
-  // h, sub-index sw: member slots 16 sw + r, stride 16 * waves-per-run, four members per lane in flight); the waves'
-  // partial rows meet in LDS and the run's first wave adds them in wave order.  (One wave walking the 848 members of a
-  // Zipf head 64 at a time was a 13-round dependent chain; the whole workgroup taking the huge runs one after the other
-  // still paid ~5 round trips per run: 16 us of the 34-us launch with Zipf ids.)
-  if (skew) __syncthreads();                                     // (uniform over the workgroup)
-#ifdef ABL_NOHUGE
-  const int n_huge = 0;
-#else
-  const int n_huge = skew ? (huge_n < 128 ? huge_n : 128) : 0;
-#endif
-  const int wv = tid >> 6;
-  constexpr int NWV_F = FIX_T / 64;
-  // more than one round: the list goes into ascending run order first.  The round a run falls in fixes how many waves
-  // add it (16 / nr) and so the order of its additions; taken in the order the atomics above landed, a run's sum changed
-  // in its last bits from one launch to the next.  (One round: every run gets the same 16 / nr waves wherever it sits.)
-  if (n_huge > NWV_F) {                                          // (uniform over the workgroup)
-    int hs0 = 0, hs1 = 0, hu = 0, rk = 0;
-    float hg = 0.f;
-    if (tid < n_huge) {
-      hs0 = huge_s0[tid]; hs1 = huge_s1[tid]; hu = huge_u[tid]; hg = huge_gz[tid];
-      for (int j = 0; j < n_huge; ++j) rk += huge_u[j] < hu ? 1 : 0;   // runs are distinct: ranks 0 .. n_huge-1
-    }
-    __syncthreads();
-    if (tid < n_huge) { huge_s0[rk] = hs0; huge_s1[rk] = hs1; huge_u[rk] = hu; huge_gz[rk] = hg; }
-    __syncthreads();
-  }
-  for (int h0 = 0; h0 < n_huge; h0 += NWV_F) {
-    const int nr = n_huge - h0 < NWV_F ? n_huge - h0 : NWV_F;    // runs of this round
-    const int wpr = NWV_F / nr;                                  // waves per run
-    const int hl = wv / wpr, sw = wv - hl * wpr;
-    const bool mine = hl < nr;
-    const int h = h0 + (mine ? hl : 0);
-    const int rs0 = huge_s0[h], rs1 = mine ? huge_s1[h] : 0;
-    float4 pa = make_float4(0.f, 0.f, 0.f, 0.f);
-    float pw = 0.f;
-    const int stride = 16 * wpr;
-    // four members per lane and round in flight (eight cost 25 more registers: at 81 the launch dropped to one workgroup
-    // per CU and the uniform step lost 0.7 us)
-    for (int base = rs0 + 1 + 16 * sw + r; base < rs1; base += 4 * stride) {
-      int bm[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int sidx = base + j * stride;
-        bm[j] = pf[sidx < rs1 ? sidx : rs1 - 1];
-      }
-      float4 xm[4];
-      float gm[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        xm[j] = vals[((int64_t)bm[j] * F + f) * 4 + c];
-        gm[j] = gz[bm[j]];
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if (base + j * stride < rs1) {
-          pa.x += xm[j].x; pa.y += xm[j].y; pa.z += xm[j].z; pa.w += xm[j].w;
-          pw += gm[j];
-        }
-      }
-    }
-#pragma unroll
-    for (int o = 4; o < 64; o <<= 1) {
-      pa.x += __shfl_xor(pa.x, o, 64); pa.y += __shfl_xor(pa.y, o, 64);
-      pa.z += __shfl_xor(pa.z, o, 64); pa.w += __shfl_xor(pa.w, o, 64);
-      pw += __shfl_xor(pw, o, 64);
-    }
-    float4 hsum = make_float4(0.f, 0.f, 0.f, 0.f);
-    const int64_t rdst = before + huge_u[h];
-    const bool fin = mine && sw == 0 && r == 0;                  // the run's first wave, one lane per chunk
-    if (fin) hsum = g_embed[rdst * 4 + c];                       // (in flight across the barrier)
-    if (r == 0) {
-      hpart[wv][c] = pa;
-      if (c == 0) hw_s[wv] = pw;
-    }
-    __syncthreads();
-    if (fin) {
-      float wsum = huge_gz[h];
-      for (int q = 0; q < wpr; ++q) {
-        const float4 x = hpart[wv + q][c];
-        hsum.x += x.x; hsum.y += x.y; hsum.z += x.z; hsum.w += x.w;
-        wsum += hw_s[wv + q];
-      }
-      g_embed[rdst * 4 + c] = hsum;
-      if (c == 0) k.g_w[rdst] = wsum;
-    }
-    __syncthreads();
-  }
+  if (skew) fix_skew_runs<int64_t>(k, sh, pf, f, before, nu, in_col, t);
+  else fix_wave_runs<int64_t>(k, pf, f, before, __ballot(len > 2), s0, s1, u, accw);
   if (bidx == 0 && tid == 0) *k.n_uniq = total;
   // The optimizer, once every row sum of this workgroup's slots is final: 8 lanes per row -- lanes 0..3 one 16-byte
   // chunk of the embedding row and of its moments, lane 4 the first-order weight -- so that a wave instruction covers 8
@@ -609,9 +690,198 @@ __device__ __forceinline__ void fixup_body(const ColSegArgs& k_in, int bidx) {
       }
     }
   }
+  PSTAMP(k, 6);
 }
 
+// ---- the body for B % 1024 == 0 without the lazy Adam: FOUR CONSECUTIVE RUNS PER LANE.  A workgroup still owns 1024
+// consecutive slots of one column (whole lines of uniq_ids / g_w / g_embed), but its fast path is the work of waves
+// 0..3 only: lane L of wave w owns runs u0 = 1024 wg + 256 w + 4 L .. u0 + 3, so the plan words arrive as one 16-byte and
+// one 4-byte piece of col_seg and two 16-byte pieces of col_uid, four perm and four gz gathers are in flight per lane,
+// and the ids and first-order rows leave as 16-byte pieces.  Every plan word is asked for BEFORE col_nu is waited for
+// (u0 + 4 <= B: the addresses need no clamp), and before / total come from one col_nu[lane] load and a wave scan: no LDS
+// and no barrier ahead of the plan loads.  Waves 4..7 read the col_seg words of waves 0..3 a second time and add the
+// few runs of more than two members of a column without skew BESIDE the fast path (behind it, in the same wave, they
+// were three more round trips at the very end of the launch, profiles/r09_post_stamps.txt); waves 8..15 of such a
+// column leave at once.  In a skewed column all 16 waves take the second look of fix_skew_runs, as in
+// the other body: every run of more than two members is summed by the same code in the same order of additions,
+// whichever wave does it.  32-bit offsets (the entry point checks the sizes).
+constexpr int FIXQ_WV = FIX_T / 256;                             // waves of a workgroup on the fast path
+typedef int32_t fixq_seg4 __attribute__((ext_vector_type(4), aligned(4)));   // col_seg + f (B + 1) + u0: 4-byte aligned
+typedef long long fixq_id2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void fixq_body(const ColSegArgs& k, int bidx) {
+  const float4* __restrict__ vals = k.vals;
+  const float* __restrict__ gz = k.gz;
+  float4* __restrict__ g_embed = k.g_embed;
+  const int B = (int)k.B, F = k.F;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);       // (scalar: the branches on it are wave-uniform)
+  const int per_col = B >> 10;                                   // workgroups per column
+  PSTAMP_WG((int)gridDim.x - F * per_col + bidx);
+  PSTAMP(k, 0);
+  const int f = bidx / per_col;
+  const int wgc = bidx - f * per_col;
+  const bool fast = wv < FIXQ_WV;                                // wave-uniform
+  const bool helper = !fast && wv < 2 * FIXQ_WV;                 // the long runs of wave wv - 4's slots
+  const int u0 = wgc * FIX_T + (fast || helper ? 256 * (wv & (FIXQ_WV - 1)) + 4 * lane : 0);
+  __shared__ FixShared sh;
+  const int nu_l = k.col_nu[lane < F ? lane : 0];
+  fixq_seg4 sg4 = {0, 0, 0, 0};
+  int sg4e = 0;
+  fixq_id2 id01 = {0, 0}, id23 = {0, 0};
+  int64_t id_pad = 0;
+  if (fast || helper) {
+    const int32_t* segp = k.col_seg + (f * (B + 1) + u0);
+    sg4 = *reinterpret_cast<const fixq_seg4*>(segp);
+    sg4e = segp[4];
+  }
+  if (fast) {
+    const fixq_id2* idp = reinterpret_cast<const fixq_id2*>(k.col_uid + (f * B + u0));
+    id01 = idp[0];
+    id23 = idp[1];
+    id_pad = k.col_uid[0];
+  }
+  // runs per column: lane c holds col_nu[c]; the prefix over the columns is a wave scan
+  int incl = lane < F ? nu_l : 0;
+#pragma unroll
+  for (int o = 1; o < 32; o <<= 1) {
+    const int x = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += x;
+  }
+  // (read as scalars: everything that only depends on them is wave-uniform)
+  const int before = __builtin_amdgcn_readlane(incl - (lane < F ? nu_l : 0), f);   // unique ids in earlier columns
+  const int total = __builtin_amdgcn_readlane(incl, F - 1);                         // ... in all columns
+  const int nu = __builtin_amdgcn_readlane(nu_l, f);
+  PSTAMP(k, 1);
+  const bool skew = B - nu > FIX_SKEW;                           // uniform over the workgroup
+  const int32_t* pf = k.perm + f * B;
+  if (fast) {
+    const int nl = nu - u0;                                      // runs u0 + j with j < nl are live
+    const int sg[5] = {sg4.x, sg4.y, sg4.z, sg4.w, sg4e};
+    PSTAMP_WAIT();
+    PSTAMP(k, 2);
+    // ids and the padded tail first: they need nothing but the plan words, and their registers are free afterwards
+    {
+    const int dst = before + u0;
+    if (nl >= 4) {
+      if ((dst & 1) == 0) {                                      // (wave-uniform: u0 is a multiple of 4)
+        fixq_id2* op = reinterpret_cast<fixq_id2*>(k.uniq_ids + dst);
+        op[0] = id01;
+        op[1] = id23;
+      } else {
+        k.uniq_ids[dst] = id01.x; k.uniq_ids[dst + 1] = id01.y; k.uniq_ids[dst + 2] = id23.x; k.uniq_ids[dst + 3] = id23.y;
+      }
+    } else {
+      // the column's last live runs and / or its share of the padded tail: slot = total + rank among the column's
+      // unused slots; id = the smallest id of column 0, zero rows
+      const int64_t idv[4] = {id01.x, id01.y, id23.x, id23.y};
+      const int d2 = total + (f * B - before) + (u0 - nu);       // slot of u0 if it were unused
+      const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (nl <= 0 && (d2 & 3) == 0) {                            // (total, before, nu: wave-uniform)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) g_embed[d2 * 4 + i] = z;
+        *reinterpret_cast<float4*>(k.g_w + d2) = z;
+        const fixq_id2 p2 = {id_pad, id_pad};
+        fixq_id2* op = reinterpret_cast<fixq_id2*>(k.uniq_ids + d2);
+        op[0] = p2;
+        op[1] = p2;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          if (j < nl) {
+            k.uniq_ids[dst + j] = idv[j];
+          } else {
+            g_embed[(d2 + j) * 4] = z; g_embed[(d2 + j) * 4 + 1] = z; g_embed[(d2 + j) * 4 + 2] = z;
+            g_embed[(d2 + j) * 4 + 3] = z;
+            k.g_w[d2 + j] = 0.f;
+            k.uniq_ids[d2 + j] = id_pad;
+          }
+        }
+      }
+    }
+    }
+    int ln[4], hb[4], hb2[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ln[j] = j < nl ? sg[j + 1] - sg[j] : 0;
+    // head of every run, and the member behind it (the head again for a run of one): a pair's second member is then
+    // one round trip away, not two
+#pragma unroll
+    for (int j = 0; j < 4; ++j) hb[j] = pf[j < nl ? sg[j] : 0];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) hb2[j] = pf[j < nl ? sg[j] + (ln[j] > 1 ? 1 : 0) : 0];
+    PSTAMP_WAIT();
+    PSTAMP(k, 3);
+    float gw[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) gw[j] = gz[hb[j]];
+    // (keeps the second members' loads up here: sunk into the pair branch they would be a round trip of their own)
+    asm volatile("" : "+v"(hb2[0]), "+v"(hb2[1]), "+v"(hb2[2]), "+v"(hb2[3]));
+    PSTAMP_WAIT();
+    PSTAMP(k, 4);
+    const int dst = before + u0;
+    // pairs (nearly every multi-member run of a uniform batch): the owning lane, head row + second member.  A lane takes
+    // its pairs one after the other, the lanes of a wave theirs at the same time: a wave (2.7 pairs on average with
+    // uniform ids) is one round trip behind its slowest lane, not one per position of the quadruple that holds a pair
+    // (taken position by position the launch measured 8.9 us, so 7.8)
+    const bool anylong = ln[0] > 2 || ln[1] > 2 || ln[2] > 2 || ln[3] > 2;
+    unsigned pm = (ln[0] == 2 ? 1u : 0u) | (ln[1] == 2 ? 2u : 0u) | (ln[2] == 2 ? 4u : 0u) | (ln[3] == 2 ? 8u : 0u);
+    while (pm) {
+      const int j = __ffs((int)pm) - 1;
+      pm &= pm - 1;
+      const int b2 = j == 0 ? hb2[0] : j == 1 ? hb2[1] : j == 2 ? hb2[2] : hb2[3];
+      const float4* r2 = vals + (b2 * F + f) * 4;
+      float4* hr = g_embed + (dst + j) * 4;
+      float4 a0 = hr[0], a1 = hr[1], a2 = hr[2], a3 = hr[3];
+      const float4 x0 = r2[0], x1 = r2[1], x2 = r2[2], x3 = r2[3];
+      const float g2 = gz[b2];
+      a0.x += x0.x; a0.y += x0.y; a0.z += x0.z; a0.w += x0.w;
+      a1.x += x1.x; a1.y += x1.y; a1.z += x1.z; a1.w += x1.w;
+      a2.x += x2.x; a2.y += x2.y; a2.z += x2.z; a2.w += x2.w;
+      a3.x += x3.x; a3.y += x3.y; a3.z += x3.z; a3.w += x3.w;
+      hr[0] = a0; hr[1] = a1; hr[2] = a2; hr[3] = a3;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) gw[i] = i == j ? gw[i] + g2 : gw[i];
+    }
+    // first-order rows of the runs of one and two members (a longer run's is written by whoever sums the run -- in a
+    // skewed column another workgroup: a quadruple that holds one leaves its g_w element by element)
+    if (nl >= 4 && !anylong && (dst & 3) == 0) {
+      *reinterpret_cast<float4*>(k.g_w + dst) = make_float4(gw[0], gw[1], gw[2], gw[3]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (ln[j] == 1 || ln[j] == 2) k.g_w[dst + j] = gw[j];
+    }
+    PSTAMP(k, 5);
+  }
+  // a column without skew: its few runs of more than two members
+  if (helper && !skew) {
+    const int nl = nu - u0;
+    const int sg[5] = {sg4.x, sg4.y, sg4.z, sg4.w, sg4e};
+    PSTAMP_WAIT();
+    PSTAMP(k, 2);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      fix_wave_runs<int, true>(k, pf, f, before, __ballot(j < nl && sg[j + 1] - sg[j] > 2), sg[j], sg[j + 1], u0 + j, 0.f);
+  }
+  if (bidx == 0 && tid == 0) *k.n_uniq = total;
+  if (skew) {
+    if (tid == 0) sh.huge_n = 0;
+    __syncthreads();
+    fix_skew_runs<int>(k, sh, pf, f, before, nu, true, wgc * FIX_T + tid);
+  }
+  PSTAMP(k, 6);
+}
+
+// QUADS: the fix-up workgroups come FIRST in the grid.  Their job is a chain of dependent round trips (col_nu, plan
+// words, perm, rows of the pairs), the reduction a 2.5-us flood of independent loads that ends at 4 us either way: with
+// the plan words asked for ahead of the flood the launch measured 7.5 us against 7.8 (profiles/r09_post_stamps.txt)
+template <bool QUADS>
 __global__ __launch_bounds__(1024, 8) void deepfm_post_direct_kernel(ReduceArgs r, ColSegArgs k, int nb_reduce) {
+  if (QUADS) {
+    const int nbf = (int)gridDim.x - nb_reduce;
+    if ((int)blockIdx.x < nbf) fixq_body(k, (int)blockIdx.x);
+    else reduce_body(r, (int)blockIdx.x - nbf);
+    return;
+  }
   if ((int)blockIdx.x < nb_reduce) reduce_body(r, (int)blockIdx.x);
   else fixup_body(k, (int)blockIdx.x - nb_reduce);
 }
@@ -743,6 +1013,17 @@ __global__ __launch_bounds__(256) void fill_last_kernel(int32_t* __restrict__ la
 
 }  // namespace
 
+#ifdef REC_POST_STAMPS
+static unsigned long long* g_post_stamps = nullptr;
+constexpr size_t POST_STAMP_WGS = 4096;
+// stamps of the last direct-mode launch: [workgroup][wave 16][8] wall-clock words (a wave leaves the words of phases
+// it did not reach as an earlier launch left them)
+extern "C" int rec_debug_post_stamps(unsigned long long* host_out, int n_wg) {
+  if (!g_post_stamps || n_wg < 0 || (size_t)n_wg > POST_STAMP_WGS) return REC_E_ARG;
+  return (int)hipMemcpy(host_out, g_post_stamps, sizeof(unsigned long long) * 8 * 16 * (size_t)n_wg, hipMemcpyDeviceToHost);
+}
+#endif
+
 extern "C" size_t rec_deepfm_fused_workspace_bytes(int64_t B, int F) {
   if (B <= 0 || F <= 0) return 0;
   return fused_workspace(B, F).bytes() + 256;
@@ -781,6 +1062,7 @@ extern "C" int rec_deepfm_fused_post_f32(int F, int64_t B, const float* gz, cons
   if ((slot_map && direct) || (adam && !direct)) return REC_E_UNSUPPORTED;
   if (!rec_is_aligned16(vals) || !rec_is_aligned16(g_embed_rows))
     return REC_E_UNSUPPORTED;
+  if (B > (((int64_t)1 << 31) - 1) / ((int64_t)F * E16)) return REC_E_UNSUPPORTED;   // 32-bit offsets into the row arrays
   const FusedWorkspace ws = fused_workspace(B, F);
   int D = F * E16;
   unsigned nb = (unsigned)reduce_blocks(D);
@@ -797,7 +1079,26 @@ extern "C" int rec_deepfm_fused_post_f32(int F, int64_t B, const float* gz, cons
   }
   if (direct) {
     unsigned nbf = (unsigned)F * (unsigned)ceil_div64(B, FIX_T);
-    hipLaunchKernelGGL(deepfm_post_direct_kernel, dim3(nb + nbf), dim3(1024), 0, as_stream(stream), r, k, (int)nb);
+#ifdef REC_POST_STAMPS
+    if (nb + nbf > POST_STAMP_WGS) return REC_E_UNSUPPORTED;
+    if (!g_post_stamps &&
+        (hipMalloc(&g_post_stamps, sizeof(unsigned long long) * 8 * 16 * POST_STAMP_WGS) != hipSuccess ||
+         hipMemset(g_post_stamps, 0, sizeof(unsigned long long) * 8 * 16 * POST_STAMP_WGS) != hipSuccess))
+      return REC_E_ARG;
+    r.stamps = g_post_stamps;
+    k.stamps = g_post_stamps;
+#endif
+    // four runs per lane (fixq_body) where a workgroup's 1024 slots are whole quadruples and the 16-byte pieces of the
+    // plan and of the outputs are aligned; the lazy Adam stays with the one-run-per-lane body
+    bool quads = !adam && (B % FIX_T) == 0 && rec_is_aligned16(col_uid) && rec_is_aligned16(uniq_ids) &&
+                 rec_is_aligned16(g_w_rows);
+#ifdef REC_POST_NO_QUADS
+    quads = false;                                       // (diagnostic builds: the one-run-per-lane body everywhere)
+#endif
+    if (quads)
+      hipLaunchKernelGGL(deepfm_post_direct_kernel<true>, dim3(nb + nbf), dim3(1024), 0, as_stream(stream), r, k, (int)nb);
+    else
+      hipLaunchKernelGGL(deepfm_post_direct_kernel<false>, dim3(nb + nbf), dim3(1024), 0, as_stream(stream), r, k, (int)nb);
   } else {
     unsigned nbs = (unsigned)ceil_div64(B * F * 4, 1024);
     hipLaunchKernelGGL(deepfm_post_kernel, dim3(nb + nbs), dim3(1024), 0, as_stream(stream), r, k, (int)nb);
