@@ -519,6 +519,7 @@ __global__ __launch_bounds__(256, 3) void din_attn_fwd_kernel(AttnArgs a, int D,
 template <int NT, int NMT, int NPASS>
 __global__ __launch_bounds__(256, 2) void din_attn_bwd_kernel(AttnArgs a, int D, int H, const float* __restrict__ scores,
                                                               const float* __restrict__ gpooled,
+                                                              const float* __restrict__ gscores /* [B,T] or null */,
                                                               float* __restrict__ gkeys /* [B,T,D] */,
                                                               float* __restrict__ gMext /* [B, D*H+H] */,
                                                               float* __restrict__ gw2p /* [B,H] */,
@@ -597,7 +598,9 @@ __global__ __launch_bounds__(256, 2) void din_attn_bwd_kernel(AttnArgs a, int D,
       dot += __shfl_xor(dot, 16, 64);
       dot += __shfl_xor(dot, 32, 64);
       if (g == 0) {                                        // lanes 0..15 = rows 0..15
-        gsw[l15] = m_row * dot;
+        // a gradient at the raw score itself (the single-key path returns the scores) bypasses the mask
+        const float gs_in = (gscores && t0 + l15 < a.T) ? gscores[b * a.T + t0 + l15] : 0.f;
+        gsw[l15] = m_row * dot + gs_in;
         msw[l15] = m_row * sc_row;                         // (mask*score) for the keys' gradient
       }
       wave_lds_sync();
@@ -871,9 +874,23 @@ __global__ __launch_bounds__(256) void softmax_bwd_kernel(const float* __restric
   for (int n = lane; n < N; n += 64) gx[row * N + n] = y[row * N + n] * (gy[row * N + n] - s);
 }
 
-bool attn_args_ok(int D, int H, int E, int C, int T) {
-  return D > 0 && H > 0 && E > 0 && C > 0 && T > 0 && D == E * C && H <= 64 && D <= 256;
+// The shapes BOTH directions take (include/mi355rec.h): the backward's LDS (AL<NT, ND, true>) is the larger one, so its
+// cap decides for the forward too -- a forward that ran would leave a graph whose backward cannot.
+int attn_shape_status(int H, int E, int C, int T) {
+  if (H <= 0 || E <= 0 || C <= 0 || T <= 0) return REC_E_ARG;
+  const int64_t D = (int64_t)E * C;
+  if (D > REC_DIN_MAX_D || H > REC_DIN_MAX_H) return REC_E_UNSUPPORTED;
+  if (D > REC_DIN_WIDE_D && H > REC_DIN_WIDE_MAX_H) return REC_E_UNSUPPORTED;
+  return REC_OK;
 }
+constexpr size_t ATTN_LDS_CAP = 150 * 1024;
+// every class attn_shape_status admits fits, the refused corner <4, 16> does not
+static_assert(sizeof(float) * AL<3, 16, true>::total <= ATTN_LDS_CAP &&
+                  sizeof(float) * AL<4, 8, true>::total <= ATTN_LDS_CAP &&
+                  sizeof(float) * AL<4, 16, true>::total > ATTN_LDS_CAP,
+              "REC_DIN_WIDE_D / REC_DIN_WIDE_MAX_H of mi355rec.h must be the LDS envelope of the backward");
+static_assert(REC_DIN_MAX_D == 256 && REC_DIN_MAX_H == 64 && REC_DIN_WIDE_D == 128 && REC_DIN_WIDE_MAX_H == 48,
+              "the dispatch below is written for these classes");
 
 }  // namespace
 
@@ -901,19 +918,20 @@ template <int NT, int ND>
 static int launch_attn_fwd(const AttnArgs& a, int64_t B, int D, int H, float* scores, float* pooled, int* oob,
                            hipStream_t st) {
   constexpr size_t lds = sizeof(float) * AL<NT, ND, false>::total;
-  if constexpr (lds > 150 * 1024) return REC_E_UNSUPPORTED;
+  if constexpr (lds > ATTN_LDS_CAP || sizeof(float) * AL<NT, ND, true>::total > ATTN_LDS_CAP) return REC_E_UNSUPPORTED;
   if (hipError_t e = rec_allow_lds<din_attn_fwd_kernel<NT, ND>>(lds)) return (int)e;
   hipLaunchKernelGGL((din_attn_fwd_kernel<NT, ND>), dim3((unsigned)B), dim3(256), lds, st, a, D, H, scores, pooled, oob);
   return REC_OK;
 }
 template <int NT, int NMT, int NPASS>
 static int launch_attn_bwd(const AttnArgs& a, int64_t B, int D, int H, const float* scores, const float* gpooled,
-                           float* gkeys, float* gMext, float* gw2p, float* galphap, float* gb2p, hipStream_t st) {
+                           const float* gscores, float* gkeys, float* gMext, float* gw2p, float* galphap,
+                           float* gb2p, hipStream_t st) {
   constexpr size_t lds = sizeof(float) * AL<NT, NMT * NPASS, true>::total;
-  if constexpr (lds > 150 * 1024) return REC_E_UNSUPPORTED;
+  if constexpr (lds > ATTN_LDS_CAP) return REC_E_UNSUPPORTED;
   if (hipError_t e = rec_allow_lds<din_attn_bwd_kernel<NT, NMT, NPASS>>(lds)) return (int)e;
   hipLaunchKernelGGL((din_attn_bwd_kernel<NT, NMT, NPASS>), dim3((unsigned)B), dim3(256), lds, st, a, D, H, scores,
-                     gpooled, gkeys, gMext, gw2p, galphap, gb2p);
+                     gpooled, gscores, gkeys, gMext, gw2p, galphap, gb2p);
   return REC_OK;
 }
 
@@ -922,8 +940,9 @@ extern "C" int rec_din_attn_fwd_f32(const float* embed, int64_t ld, int64_t V, i
                                     const float* alpha, const float* mean, const float* var, const float* w2,
                                     const float* b2, int64_t padding_index, int mask_valid, float* scores,
                                     float* pooled, int* oob_flag, void* stream) {
+  if (int rc = attn_shape_status(H, E, C, T)) return rc;
   int D = E * C;
-  if (B < 0 || !attn_args_ok(D, H, E, C, T) || ld < E || V <= 0) return REC_E_ARG;
+  if (B < 0 || ld < E || V <= 0) return REC_E_ARG;
   if (act < DACT_NONE || act > DACT_PRELU) return REC_E_ARG;
   if (B == 0) return REC_OK;
   if (!embed || !series || !Mext || !Wkd || !w2 || !b2 || !scores || !pooled) return REC_E_ARG;
@@ -953,10 +972,11 @@ extern "C" int rec_din_attn_bwd_f32(const float* embed, int64_t ld, int64_t V, i
                                     int64_t B, int T, const float* Mext, const float* Wkd, int H, int act,
                                     const float* alpha, const float* mean, const float* var, const float* w2,
                                     const float* b2, int64_t padding_index, int mask_valid, const float* scores,
-                                    const float* gpooled, float* gkeys, float* gMext, float* gw2p, float* galphap,
-                                    float* gb2p, void* stream) {
+                                    const float* gpooled, const float* gscores, float* gkeys, float* gMext,
+                                    float* gw2p, float* galphap, float* gb2p, void* stream) {
+  if (int rc = attn_shape_status(H, E, C, T)) return rc;
   int D = E * C;
-  if (B < 0 || !attn_args_ok(D, H, E, C, T) || ld < E || V <= 0) return REC_E_ARG;
+  if (B < 0 || ld < E || V <= 0) return REC_E_ARG;
   if (act < DACT_NONE || act > DACT_PRELU) return REC_E_ARG;
   if (B == 0) return REC_OK;
   if (!embed || !series || !Mext || !Wkd || !w2 || !b2 || !scores || !gpooled || !gkeys || !gMext || !gw2p ||
@@ -966,11 +986,12 @@ extern "C" int rec_din_attn_bwd_f32(const float* embed, int64_t ld, int64_t V, i
   hipStream_t st = as_stream(stream);
   const int nd = (D + 15) / 16;
   int rc;
-#define BWD_ND(NT)                                                                                                   \
-  (nd <= 2 ? launch_attn_bwd<NT, 2, 1>(a, B, D, H, scores, gpooled, gkeys, gMext, gw2p, galphap, gb2p, st)            \
-   : nd <= 6 ? launch_attn_bwd<NT, 6, 1>(a, B, D, H, scores, gpooled, gkeys, gMext, gw2p, galphap, gb2p, st)          \
-   : nd <= 8 ? launch_attn_bwd<NT, 8, 1>(a, B, D, H, scores, gpooled, gkeys, gMext, gw2p, galphap, gb2p, st)          \
-             : launch_attn_bwd<NT, 8, 2>(a, B, D, H, scores, gpooled, gkeys, gMext, gw2p, galphap, gb2p, st))
+#define BWD_ARGS a, B, D, H, scores, gpooled, gscores, gkeys, gMext, gw2p, galphap, gb2p, st
+#define BWD_ND(NT)                                     \
+  (nd <= 2 ? launch_attn_bwd<NT, 2, 1>(BWD_ARGS)        \
+   : nd <= 6 ? launch_attn_bwd<NT, 6, 1>(BWD_ARGS)      \
+   : nd <= 8 ? launch_attn_bwd<NT, 8, 1>(BWD_ARGS)      \
+             : launch_attn_bwd<NT, 8, 2>(BWD_ARGS))
   switch ((H + 15) / 16) {
     case 1: rc = BWD_ND(1); break;
     case 2: rc = BWD_ND(2); break;
@@ -978,6 +999,7 @@ extern "C" int rec_din_attn_bwd_f32(const float* embed, int64_t ld, int64_t V, i
     default: rc = BWD_ND(4); break;
   }
 #undef BWD_ND
+#undef BWD_ARGS
   if (rc != REC_OK) return rc;
   REC_LAUNCH_CHECK();
   return REC_OK;

@@ -320,11 +320,12 @@ class DinAttention(torch.autograd.Function):
     """DinActivationLayer over every time step + mask + weighted sum pooling (5.DIN/CustomLayers.py:173-180,
     256-282), bilinear-factorised.  Inputs: table, q = flattened candidate-item embedding [B,D], series ids
     [B,T,C], the Dense(H) kernel W1 [3D+D*D,H] / bias b1, the activation's parameters, the Dense(1) kernel W2 [H,1]
-    / bias b2.  Returns pooled [B,D] and the raw scores [B,T] (not differentiable)."""
+    / bias b2.  Returns pooled [B,D] and the raw scores [B,T]; the scores are differentiable only with ``score_grad``
+    (the single-key path, whose result they are): DINLayer consumes pooled alone."""
 
     @staticmethod
     def forward(ctx, embed, q, series, W1, b1, kind, alpha, mean, var, W2, b2, padding_index, mask_valid, oob,
-                sink=None):
+                sink=None, score_grad=False):
         q = q.contiguous()
         B, D = q.shape
         H = W1.shape[1]
@@ -336,15 +337,22 @@ class DinAttention(torch.autograd.Function):
         ctx.save_for_backward(embed, q, series, Wcat, Wkd, Mext, alpha, mean, var, w2, b2, scores)
         ctx.cfg = (kind, padding_index, mask_valid, D, H)
         ctx.sink = sink
-        ctx.mark_non_differentiable(scores)
+        if score_grad:
+            ctx.set_materialize_grads(False)                 # an output nobody used arrives as None, not as zeros
+        else:
+            ctx.mark_non_differentiable(scores)
         return pooled, scores
 
     @staticmethod
-    def backward(ctx, gpooled, _gscores):
+    def backward(ctx, gpooled, gscores):
         embed, q, series, Wcat, Wkd, Mext, alpha, mean, var, w2, b2, scores = ctx.saved_tensors
         kind, padding_index, mask_valid, D, H = ctx.cfg
         V, E = embed.shape
         B = q.shape[0]
+        if gpooled is None:                                  # only the scores were used (score_grad)
+            gpooled = torch.zeros((B, D), dtype=torch.float32, device=q.device)
+        if gscores is not None:
+            gscores = gscores.contiguous()
         sink, buf, dst = ctx.sink, None, None
         if sink is not None:                                 # values land behind the Gather's rows in one shared buffer
             n_ser = series.numel()
@@ -352,7 +360,7 @@ class DinAttention(torch.autograd.Function):
             dst = buf[sink.n_head:sink.n_head + n_ser].view(series.shape[0], series.shape[1], D)
         gkeys, gMext, gw2p, galphap, gb2p = ops.din_attn_bwd(embed, series, Mext, Wkd, kind, alpha, mean, var, w2, b2,
                                                              padding_index, mask_valid, scores, gpooled.contiguous(),
-                                                             gkeys=dst)
+                                                             gkeys=dst, gscores=gscores)
         gq = ops.gemm(gMext, Wcat, transB=True)                                          # [B,D]
         gWcat = ops.gemm(q, gMext, transA=True, split_k=ops.split_k_for(B, D, D * H + H, True, False))  # [D, D*H+H]
         gbext = ops.colsum(gMext)
@@ -369,7 +377,7 @@ class DinAttention(torch.autograd.Function):
         else:
             plan = ops.DedupPlan(series, V)
             gembed = _sparse_grad(plan, gkeys.reshape(-1, E), E, (V, E))
-        return gembed, gq, None, gW1, gb1, None, galpha, None, None, gW2, gb2, None, None, None, None
+        return gembed, gq, None, gW1, gb1, None, galpha, None, None, gW2, gb2, None, None, None, None, None
 
 
 class EmbIpn(torch.autograd.Function):

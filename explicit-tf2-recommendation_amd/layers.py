@@ -1643,9 +1643,10 @@ class DinActivationLayer(Layer):
     def attend_rows(self, q, keys2d, ids):
         dense = self.mlp_layer.layers[0]
         kind, alpha, mean, var = self.act_params()
-        # mask_valid=1 with padding_index=-1: no position is masked
+        # mask_valid=1 with padding_index=-1: no position is masked; the scores are this path's result, so they carry
+        # a gradient (to q, to the keys as the rows of the identity table, and to the unit's parameters)
         return Fn.DinAttention.apply(keys2d.contiguous(), q, ids, dense.kernel, dense.bias, kind, alpha, mean, var,
-                                     self.output_layer.kernel, self.output_layer.bias, -1, 1, None)
+                                     self.output_layer.kernel, self.output_layer.bias, -1, 1, None, None, True)
 
 
 class DINLayer(Layer):

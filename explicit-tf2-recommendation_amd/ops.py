@@ -389,11 +389,25 @@ def din_prepare_bwd(gWcat, gWkd, D, H):
     return gW1
 
 
+DIN_MAX_D, DIN_MAX_H, DIN_WIDE_D, DIN_WIDE_MAX_H = (LIMITS["REC_DIN_" + k] for k in ("MAX_D", "MAX_H", "WIDE_D",
+                                                                                     "WIDE_MAX_H"))
+
+
+def din_attn_check_shape(D, H):
+    """Raises what rec_din_attn_fwd_f32 / _bwd_f32 would answer with -2, before anything is allocated or launched: key
+    width D = E * C and hidden units H.  The envelope is the backward's and holds for the forward too."""
+    if D > DIN_MAX_D or H > DIN_MAX_H or (D > DIN_WIDE_D and H > DIN_WIDE_MAX_H):
+        raise NotImplementedError(
+            "DIN attention kernels cover key width <= %d and hidden units <= %d, and beyond key width %d only hidden "
+            "units <= %d; got key width=%d, hidden units=%d" % (DIN_MAX_D, DIN_MAX_H, DIN_WIDE_D, DIN_WIDE_MAX_H, D, H))
+
+
 def _attn_common(embed, series, Mext, Wkd, act, alpha, mean, var, w2, b2, padding_index, mask_valid):
     _table(embed, "embed"); _i64(series, "series")
     V, E = embed.shape
     B, T, Cn = series.shape
     H = Wkd.shape[1]
+    din_attn_check_shape(Cn * E, H)
     return [_ptr(embed), embed.stride(0), V, E, Cn, _ptr(series), B, T, _ptr(_f32(Mext, "Mext")), _ptr(_f32(Wkd, "Wkd")),
             H, act, _ptr(alpha), _ptr(mean), _ptr(var), _ptr(_f32(w2, "w2")), _ptr(_f32(b2, "b2")), int(padding_index),
             int(bool(mask_valid))], (B, T, Cn * E, H)
@@ -409,8 +423,9 @@ def din_attn_fwd(embed, series, Mext, Wkd, act, alpha, mean, var, w2, b2, paddin
 
 
 def din_attn_bwd(embed, series, Mext, Wkd, act, alpha, mean, var, w2, b2, padding_index, mask_valid, scores, gpooled,
-                 gkeys=None):
-    """``gkeys``: optional preallocated contiguous [B,T,D] destination (the tail of a shared value buffer)."""
+                 gkeys=None, gscores=None):
+    """``gkeys``: optional preallocated contiguous [B,T,D] destination (the tail of a shared value buffer).
+    ``gscores``: optional [B,T] gradient at the raw scores, added to the one that arrives through pooled."""
     args, (B, T, D, H) = _attn_common(embed, series, Mext, Wkd, act, alpha, mean, var, w2, b2, padding_index,
                                       mask_valid)
     dev = embed.device
@@ -422,8 +437,10 @@ def din_attn_bwd(embed, series, Mext, Wkd, act, alpha, mean, var, w2, b2, paddin
     gw2p = torch.empty((B, H), **f32)
     galphap = torch.empty((B, H), **f32)
     gb2p = torch.empty((B, 1), **f32)
-    check(lib.rec_din_attn_bwd_f32(*args, _ptr(_f32(scores, "scores")), _ptr(_f32(gpooled, "gpooled")), _ptr(gkeys),
-                                   _ptr(gMext), _ptr(gw2p), _ptr(galphap), _ptr(gb2p), _stream()),
+    if gscores is not None and tuple(_f32(gscores, "gscores").shape) != (B, T):
+        raise ValueError("gscores must be [B,T] = [%d, %d], got %s" % (B, T, tuple(gscores.shape)))
+    check(lib.rec_din_attn_bwd_f32(*args, _ptr(_f32(scores, "scores")), _ptr(_f32(gpooled, "gpooled")), _ptr(gscores),
+                                   _ptr(gkeys), _ptr(gMext), _ptr(gw2p), _ptr(galphap), _ptr(gb2p), _stream()),
           "rec_din_attn_bwd_f32")
     return gkeys, gMext, gw2p, galphap, gb2p
 

@@ -83,6 +83,12 @@ extern "C" {
 #define REC_MASKNET_MAX_P 512
 #define REC_MASKNET_MAX_O 128
 #define REC_MASKNET_MAX_R 4
+/* DIN attention (csrc/din.hip), forward and backward alike: key width D = E C, hidden units H; beyond D = WIDE_D only
+ * H <= WIDE_MAX_H (the backward keeps Eff, the key slabs and the gpre slabs of a workgroup in the LDS of one CU) */
+#define REC_DIN_MAX_D 256
+#define REC_DIN_MAX_H 64
+#define REC_DIN_WIDE_D 128
+#define REC_DIN_WIDE_MAX_H 48
 
 /* activation kinds shared by the dense entry points */
 enum { REC_ACT_NONE = 0, REC_ACT_RELU = 1, REC_ACT_SIGMOID = 2, REC_ACT_TANH = 3 };
@@ -478,19 +484,26 @@ int rec_din_prepare_f32(const float* W1, const float* b1, int D, int H, float* W
 int rec_din_prepare_bwd_f32(const float* gWcat, const float* gWkd, int D, int H, float* gW1, void* stream);
 /* series: int64 [B,T,C] (the tf.stack(axis=2) of the behaviour series, :258); key k_t = concat_r embed[series[b,t,r]].
  * mask: reference behaviour (mask_valid = 0) keeps PADDED positions (series[b,t,0] == padding_index, :256,277-278);
- * mask_valid = 1 is the intended form.  scores [B,T] are the raw (unmasked) scores; pooled [B,D]. */
+ * mask_valid = 1 is the intended form.  scores [B,T] are the raw (unmasked) scores; pooled [B,D].
+ * Supported, the same for the forward and the backward: 1 <= D = E C <= REC_DIN_MAX_D (256), 1 <= H <= REC_DIN_MAX_H
+ * (64), and D > REC_DIN_WIDE_D (128) only with H <= REC_DIN_WIDE_MAX_H (48): at 129 <= D <= 256 with 49 <= H <= 64 the
+ * backward's LDS (156 KiB) is above its 150 KiB launch cap, so both directions refuse that corner.  Outside: -2
+ * (REC_E_UNSUPPORTED), answered from the sizes alone before a pointer is looked at, also with B == 0.  A size <= 0,
+ * ld < E, V <= 0, an unknown act or a NULL pointer: -1. */
 int rec_din_attn_fwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* series, int64_t B,
                          int T, const float* Mext, const float* Wkd, int H, int act, const float* alpha,
                          const float* mean, const float* var, const float* w2, const float* b2,
                          int64_t padding_index, int mask_valid, float* scores, float* pooled, int* oob_flag,
                          void* stream);
 /* backward: gkeys [B,T,D] (IndexedSlices values of the series lookups), gMext [B, D*H+H], and per-example partials
- * gw2p [B,H], galphap [B,H], gb2p [B] (column sums of these are the parameter gradients). */
+ * gw2p [B,H], galphap [B,H], gb2p [B] (column sums of these are the parameter gradients).  gscores (optional, [B,T]):
+ * a gradient that arrives at the raw scores themselves, added to the one that comes through pooled; NULL = none. */
 int rec_din_attn_bwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* series, int64_t B,
                          int T, const float* Mext, const float* Wkd, int H, int act, const float* alpha,
                          const float* mean, const float* var, const float* w2, const float* b2,
                          int64_t padding_index, int mask_valid, const float* scores, const float* gpooled,
-                         float* gkeys, float* gMext, float* gw2p, float* galphap, float* gb2p, void* stream);
+                         const float* gscores, float* gkeys, float* gMext, float* gw2p, float* galphap, float* gb2p,
+                         void* stream);
 
 /* ---- rows of DIN's final MLP (make_mlp_layer, 5.DIN/CustomLayers.py:142-160) */
 /* y = act(x) on [M,N] with per-feature parameters; bwd also returns gy * dy/dalpha per element (column-sum it) */

@@ -147,6 +147,18 @@ def test_header_limits_are_the_compiled_library_s():
     for ws in (lib.rec_ccpm_workspace_bytes, lib.rec_fgcnn_workspace_bytes):
         sizes = [ws(B, 3, 16, 1, _ints(2), _ints(2), _ints(1)) for B in (1, 64 * grid, 128 * grid)]
         assert sizes[0] < sizes[1] == sizes[2] == -(-grid * (2 * 2 + 2) * 4 // 256) * 256, sizes
+    # DIN attention has no workspace either: with B == 0 both directions answer from the sizes alone.  Key width D = E C
+    # and hidden units H; beyond D = WIDE_D only H <= WIDE_MAX_H
+    def din(D, H):
+        head = (None, D, 10, D, 1, None, 0, 5, None, None, H, 0, None, None, None, None, None, 0, 1)
+        fwd = lib.rec_din_attn_fwd_f32(*head, None, None, None, None)
+        assert fwd == lib.rec_din_attn_bwd_f32(*head, *[None] * 9), (D, H)
+        return fwd
+    max_d, max_h, wide_d, wide_h = (LIMITS["REC_DIN_" + k] for k in ("MAX_D", "MAX_H", "WIDE_D", "WIDE_MAX_H"))
+    assert din(max_d, wide_h) == 0 and din(max_d + 1, 1) == -2
+    assert din(wide_d, max_h) == 0 and din(1, max_h + 1) == -2
+    assert din(wide_d + 1, wide_h) == 0 and din(wide_d + 1, wide_h + 1) == -2 and din(max_d, max_h) == -2
+    seen |= {"REC_DIN_MAX_D", "REC_DIN_MAX_H", "REC_DIN_WIDE_D", "REC_DIN_WIDE_MAX_H"}
     seen |= {"REC_FIBINET_MAX_C", "REC_FIELD_CONV_BWD_GRID"}
     status = {"REC_OK", "REC_E_ARG", "REC_E_UNSUPPORTED", "REC_E_WORKSPACE", "REC_MAX_COLS"}
     assert seen == set(LIMITS) - status                                # a limit added to the header gets a case here

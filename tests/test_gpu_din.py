@@ -9,6 +9,7 @@ import torch
 
 from oracle import layers_np as L
 from oracle import torch_ref as T
+from tests import din_classes_ref as DR
 from tests import helpers as H
 
 pytestmark = pytest.mark.gpu
@@ -110,11 +111,7 @@ def test_din_attention_kernel_vs_literal_activation_unit(R, act, E, T_, mask_val
     ta = H.to_torch(a, torch.float64, True)
     emb_t = torch.from_numpy(pr["embed"]).double().requires_grad_()
     qt = torch.from_numpy(q).double().requires_grad_()
-    keys = T.lookup(emb_t, torch.from_numpy(series.reshape(B, T_ * C))).reshape(B, T_, D)
-    sc = torch.stack([T.din_activation_unit(qt, keys[:, t, :], ta) for t in range(T_)], dim=1).squeeze(-1)
-    pad = torch.from_numpy(series[:, :, 0] == 0)
-    m = (~pad if mask_valid else pad).double()
-    pooled_t = (keys * (sc * m).unsqueeze(-1)).sum(1)
+    sc, pooled_t, _ = DR.literal_attention(emb_t, qt, series, ta, 0, mask_valid)
     g = r.normal(size=(B, D)).astype(np.float32)
     (pooled_t * torch.from_numpy(g).double()).sum().backward()
     # HIP
