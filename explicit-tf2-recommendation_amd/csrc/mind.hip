@@ -1,0 +1,649 @@
+// MIND (MultiInterestExtractorLayer, LabelAwareAttention and MINDLayer.call, 6.MIND/CustomLayers.py:62-158, 263-285) on
+// gfx950, fp32: the capsule routing and the label-aware attention with its sampled-softmax loss.
+//
+// Capsule routing, per example b (series int64 [B, T, C] as rec_din_attn_*; D = E C):
+//   x_t = concat_r embed[series[b,t,r]]  [T, D]     valid_t = series[b,t,0] != padding_index     u = x S  [T, Dc]
+//   L = B0 [K, T];  R times:  W = softmax_t(valid_t ? L : -FLT_MAX),  c = squash(W u),  (but the last)  L += c u^T
+//   out[b] = c  [K, Dc]
+// squash(s) = s n / (1 + n^2) with n = |s|: the reference's n^2 / ((1 + n^2) n) is 0/0 at n = 0, this form gives 0 there
+// and the backward gives a zero gradient there, which is the limit.  An example with no valid position has every logit
+// at -FLT_MAX and so the uniform weights 1 / T over ALL positions, padded ones included; nothing becomes NaN.
+// Forward, one launch.  A workgroup of 4 waves holds ONE example at a time: its rows are gathered once into LDS
+// ([T][D | 1]: the odd stride serves the row-per-lane reads of x S and the column-per-lane reads of x^T du alike),
+// u = x S runs on v_mfma_f32_32x32x2_f32, one (32 rows, 32 columns) block per wave and step, S read from global memory
+// (every workgroup reads the same few KiB), and lands in LDS ([T][Dc | 1]).  A capsule row k depends on no other row,
+// so wave k & 3 owns it through all R rounds with nothing but wave-level ordering: the softmax with lanes over t, W u
+// with lanes over the capsule dims (the weight is a broadcast read), the squash with one wave sum, c u^T with lanes
+// over t.  K <= 16 rows of T <= ~100 and Dc <= 256 are VALU work; an MFMA tile would be padding.  u, L, W and c never
+// leave LDS; the forward saves nothing but out.
+// Backward.  It gathers the rows and runs the rounds again, keeping the weights W of every round in LDS; then, from the
+// last round to the first (dL is the gradient of the logits that leave round r, zero after the last):
+//   s = W_r u   dc = last ? gout : dL u   ds = squash'(s) dc   c = squash(s)          (the row's wave)
+//   du += W_r^T ds + dL^T c                                                            (all threads, over (t, dim))
+//   dW = ds u^T   dL += valid_t ? W_r (dW - sum_t dW W_r) : 0                          (the row's wave)
+// with no stop_gradient anywhere; B0 gets nothing.  gkeys[b] = du S^T and dS += x^T du run on the MFMA again.  dS stays in
+// the accumulators of the workgroup over all its examples (the grid is capped, so the number of partials does not grow
+// with B), goes to the workgroup's slot and the slots are added by rec_slot_sum in wave order.
+//
+// Label-aware attention + sampled-softmax loss, per example b (items int64 [B, Ns, C]; Dc = E C):
+//   x_s = concat_r embed[items[b,s,r]]   sc[k,s] = m_k . x_s   w[:,s] = softmax_k(k < kv ? sc[k,s] : -FLT_MAX)
+//   out[s] = sum_k w[k,s] sc[k,s]   loss = logsumexp_s(out) - out[0]
+// One wave owns an example (its m, its rows and the K Ns scores in LDS); a workgroup has 4, 2 or 1 waves, as many as
+// fit the launch cap.  The backward recomputes the forward from the ids and m and returns gm and gitems in one launch:
+//   g[s] = gout[s] + gloss (softmax_s(out)[s] - [s == 0])
+//   dsc[k,s] = g[s] (w[k,s] + (k < kv ? w[k,s] (sc[k,s] - out[s]) : 0))     a masked capsule's score is a constant inside
+//   the softmax and keeps the direct term alone, zero unless every capsule is masked
+//   gm_k = sum_s dsc[k,s] x_s   gitems_s = sum_k dsc[k,s] m_k
+// Neither family uses a float atomic or scratch; every launch only enqueues.  An id outside [0, V) reads as a zero row and
+// sets the flag.
+#include <float.h>
+#include <math.h>
+#include "common.h"
+#include "mfma_tile.h"
+
+namespace {
+
+// the limits are DIN's and AFM's: the header gains no constant for this family
+constexpr int MI_MAXD = REC_DIN_MAX_D, MI_MAXK = REC_AFM_MAX_A, MI_MAXR = 8;
+constexpr int MI_NTHR = 256;
+constexpr size_t MI_LDS_CAP = 150 * 1024;
+constexpr int MI_GRID = 1024;                   // workgroups (= dS partials) of the routing backward, at the most
+static_assert(MI_LDS_CAP <= REC_LDS_CU_BYTES, "the launch cap fits the LDS of a CU");
+
+__host__ __device__ inline int mi_odd(int n) { return n | 1; }
+
+// floats of LDS of the routing backward, which is what both directions are held to:
+//   xs [T][D | 1], u and du [T][Dc | 1], W of every round [R][K][T], dL and dW [K][T], ds and c [K][Dc | 1], valid [T]
+__host__ __device__ inline size_t rt_lds_floats(int T, int D, int Dc, int K, int R) {
+  return (size_t)T * mi_odd(D) + 2 * (size_t)T * mi_odd(Dc) + (size_t)(R + 2) * K * T + 2 * (size_t)K * mi_odd(Dc) + T;
+}
+// and of the forward: xs, u, W [K][T], L [K][T], c [K][Dc | 1], valid [T]
+__host__ __device__ inline size_t rt_fwd_lds_floats(int T, int D, int Dc, int K) {
+  return (size_t)T * mi_odd(D) + (size_t)T * mi_odd(Dc) + 2 * (size_t)K * T + (size_t)K * mi_odd(Dc) + T;
+}
+// floats of LDS of one example of the attention: m [K][Dc | 1], x [Ns][Dc | 1], sc and w [K][Ns], out and g [Ns]
+__host__ __device__ inline size_t la_lds_floats(int Ns, int Dc, int K) {
+  return ((size_t)K + Ns) * mi_odd(Dc) + 2 * (size_t)K * Ns + 2 * (size_t)Ns;
+}
+
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+// what one lane of a wave wrote to LDS is read by another lane of the SAME wave after it
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// sum_i a[i] b[i sb] over i < n, in that order; the operands of 8 terms are requested together so that the LDS latency is
+// paid once per 8, not once per term (a is read at the same address by every lane: a broadcast)
+__device__ __forceinline__ float mi_dot(const float* a, const float* b, int sb, int n) {
+  float acc = 0.f;
+  int i = 0;
+  for (; i + 8 <= n; i += 8) {
+    float x[8], y[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      x[j] = a[i + j];
+      y[j] = b[(i + j) * sb];
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc = fmaf(x[j], y[j], acc);
+  }
+  for (; i < n; ++i) acc = fmaf(a[i], b[i * sb], acc);
+  return acc;
+}
+// two sums over the same b: r1 = sum a1[i] b[i sb], r2 = sum a2[i] b[i sb]
+__device__ __forceinline__ void mi_dot2(const float* a1, const float* a2, const float* b, int sb, int n, float& r1,
+                                        float& r2) {
+  float s1 = 0.f, s2 = 0.f;
+  int i = 0;
+  for (; i + 8 <= n; i += 8) {
+    float x[8], z[8], y[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      x[j] = a1[i + j];
+      z[j] = a2[i + j];
+      y[j] = b[(i + j) * sb];
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      s1 = fmaf(x[j], y[j], s1);
+      s2 = fmaf(z[j], y[j], s2);
+    }
+  }
+  for (; i < n; ++i) {
+    const float y = b[i * sb];
+    s1 = fmaf(a1[i], y, s1);
+    s2 = fmaf(a2[i], y, s2);
+  }
+  r1 = s1;
+  r2 = s2;
+}
+
+struct RtArgs {
+  const float* embed;
+  int64_t ld, V;
+  const int64_t* series;
+  int64_t B;
+  const float *S, *B0;
+  int64_t padding_index;
+  int T, C, E, D, Dc, K, R;
+};
+
+// one 32 x 32 block of acc += A Bm over k < Kd: fa(k) is A[row lo][k], fb(k) is Bm[k][column lo], both already masked.
+// The operands of U k-steps are requested together (an operand may come from global memory: one latency per U steps).
+template <class FA, class FB>
+__device__ __forceinline__ void mi_mma(f32x16& acc, int Kd, int hi, FA fa, FB fb) {
+  constexpr int U = 8;
+  for (int k = 0; k < Kd; k += 2 * U) {
+    float av[U], bv[U];
+#pragma unroll
+    for (int s = 0; s < U; ++s) {
+      const int kk = k + 2 * s + hi;
+      const bool kok = kk < Kd;
+      const int kc = kok ? kk : Kd - 1;
+      const float x = fa(kc), y = fb(kc);
+      av[s] = kok ? x : 0.f;
+      bv[s] = kok ? y : 0.f;
+    }
+#pragma unroll
+    for (int s = 0; s < U; ++s)
+      if (k + 2 * s < Kd) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s], bv[s], acc, 0, 0, 0);   // uniform
+  }
+}
+
+// rows x (C E) looked-up values of ids [rows][C] into xs [rows][stride], by NT threads (this one is tid): the ids of U
+// elements are requested together, then their values, with no branch between them (an id outside [0, V) reads row 0 and
+// keeps a zero); valid != NULL: valid[row] = ids[row][0] != pad, taken from the id the element (row, 0) has read anyway
+template <int NT>
+__device__ __forceinline__ void mi_gather(const float* __restrict__ embed, int64_t ld, int64_t V,
+                                          const int64_t* __restrict__ ids, int rows, int C, int E, float* xs, int stride,
+                                          int tid, bool& bad, int64_t pad = 0, int* valid = nullptr) {
+  constexpr int U = 4;
+  const int D = C * E, n = rows * D;
+  for (int i0 = tid; i0 < n; i0 += NT * U) {
+    int64_t id[U];
+    int at[U], e[U], row[U];
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+      const int i = i0 + j * NT, ic = i < n ? i : n - 1;
+      const int t = ic / D, d = ic - t * D, r = d / E;
+      e[j] = d - r * E;
+      at[j] = t * stride + d;
+      row[j] = d == 0 ? t : -1;
+      id[j] = ids[(int64_t)t * C + r];
+    }
+    float v[U];
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+      const bool ok = id[j] >= 0 && id[j] < V;
+      const float x = embed[(ok ? id[j] : 0) * ld + e[j]];
+      v[j] = ok ? x : 0.f;
+      bad |= !ok;
+    }
+#pragma unroll
+    for (int j = 0; j < U; ++j)
+      if (i0 + j * NT < n) {
+        xs[at[j]] = v[j];
+        if (valid && row[j] >= 0) valid[row[j]] = id[j] != pad;
+      }
+  }
+}
+
+// The rows of example b into xs, valid, L <- B0, u = x S, and the R rounds.  KEEP: W of round r goes to Wall[r] (the
+// backward), otherwise every round uses Wall[0].  out (may be NULL): c of the last round.  Ends with every wave done
+// with its own rows only: the caller synchronises.
+template <bool KEEP>
+__device__ __forceinline__ void rt_forward(const RtArgs& a, int64_t b, float* xs, float* u, float* Wall, float* L,
+                                           float* c, int* valid, float* __restrict__ out, int tid, bool& bad) {
+  const int lane = tid & 63, lo = lane & 31, hi = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int T = a.T, C = a.C, E = a.E, D = a.D, Dc = a.Dc, K = a.K, R = a.R, Dp = mi_odd(D), Dcp = mi_odd(Dc);
+  const int64_t* __restrict__ ids = a.series + b * T * C;
+  const float l0 = tid < K * T ? a.B0[tid] : 0.f;                // in flight beside the rows
+  mi_gather<MI_NTHR>(a.embed, a.ld, a.V, ids, T, C, E, xs, Dp, tid, bad, a.padding_index, valid);
+  if (tid < K * T) L[tid] = l0;
+  for (int i = tid + MI_NTHR; i < K * T; i += MI_NTHR) L[i] = a.B0[i];
+  __syncthreads();
+
+  const int ncb = (Dc + 31) / 32, ntile = (T + 31) / 32;
+  for (int task = wave; task < ntile * ncb; task += 4) {        // u = x S
+    const int tile = task / ncb, cb = task - tile * ncb;
+    const int t = tile * 32 + lo, n = cb * 32 + lo;
+    const bool tok = t < T, nok = n < Dc;
+    const float* xr = xs + (tok ? t : T - 1) * Dp;
+    const float* __restrict__ Sc = a.S + (nok ? n : Dc - 1);
+    f32x16 acc;
+    mb_zero(acc);
+    mi_mma(acc, D, hi, [&](int k) { return tok ? xr[k] : 0.f; },
+           [&](int k) { const float v = Sc[(int64_t)k * Dc]; return nok ? v : 0.f; });
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int row = tile * 32 + mb_row(r, hi);
+      if (row < T && nok) u[row * Dcp + n] = acc[r];
+    }
+  }
+  __syncthreads();
+
+  for (int k = wave; k < K; k += 4) {                            // a row needs no other row
+    float* Lk = L + k * T;
+    float* ck = c + k * Dcp;
+    for (int r = 0; r < R; ++r) {
+      float* Wk = (KEEP ? Wall + (size_t)r * K * T : Wall) + k * T;
+      float m = -FLT_MAX;
+      for (int t = lane; t < T; t += 64) m = fmaxf(m, valid[t] ? Lk[t] : -FLT_MAX);
+      m = wave_max(m);
+      float sum = 0.f;
+      for (int t = lane; t < T; t += 64) {
+        const float ex = expf((valid[t] ? Lk[t] : -FLT_MAX) - m);
+        Wk[t] = ex;
+        sum += ex;
+      }
+      sum = group_sum<64>(sum);
+      for (int t = lane; t < T; t += 64) Wk[t] = Wk[t] / sum;
+      wave_sync();
+      float n2 = 0.f;
+      for (int d = lane; d < Dc; d += 64) {                      // s = W u
+        const float acc = mi_dot(Wk, u + d, Dcp, T);
+        ck[d] = acc;
+        n2 = fmaf(acc, acc, n2);
+      }
+      n2 = group_sum<64>(n2);
+      const float f = sqrtf(n2) / (1.f + n2);
+      for (int d = lane; d < Dc; d += 64) {
+        const float cv = ck[d] * f;
+        ck[d] = cv;
+        if (out && r == R - 1) out[((int64_t)b * K + k) * Dc + d] = cv;
+      }
+      wave_sync();
+      if (r < R - 1) {
+        for (int t = lane; t < T; t += 64) {                     // L += c u^T
+          Lk[t] = Lk[t] + mi_dot(ck, u + t * Dcp, 1, Dc);
+        }
+        wave_sync();
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(MI_NTHR) void mind_routing_fwd_kernel(RtArgs a, float* __restrict__ out,
+                                                                   int* __restrict__ oob) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int T = a.T, K = a.K, Dp = mi_odd(a.D), Dcp = mi_odd(a.Dc);
+  float* xs = lds;
+  float* u = xs + T * Dp;
+  float* W = u + T * Dcp;
+  float* L = W + K * T;
+  float* c = L + K * T;
+  int* valid = reinterpret_cast<int*>(c + K * Dcp);
+  bool bad = false;
+  for (int64_t b = blockIdx.x; b < a.B; b += gridDim.x) {
+    rt_forward<false>(a, b, xs, u, W, L, c, valid, out, threadIdx.x, bad);
+    __syncthreads();                                             // the next example overwrites all of it
+  }
+  if (bad && oob) *oob = 1;
+}
+
+// NB: 32 x 32 blocks of dS per wave (block w, w + 4, ...): 1, 4 or 16
+template <int NB>
+__global__ __launch_bounds__(MI_NTHR, NB == 1 ? 4 : 1) void mind_routing_bwd_kernel(RtArgs a, const float* __restrict__ gout,
+                                                                   float* __restrict__ gkeys,
+                                                                   float* __restrict__ slots) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int tid = threadIdx.x, lane = tid & 63, lo = lane & 31, hi = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int T = a.T, D = a.D, Dc = a.Dc, K = a.K, R = a.R, Dp = mi_odd(D), Dcp = mi_odd(Dc);
+  float* xs = lds;
+  float* u = xs + T * Dp;
+  float* du = u + T * Dcp;
+  float* Wall = du + T * Dcp;                                    // [R][K][T]
+  float* dL = Wall + (size_t)R * K * T;                          // [K][T]: L going forward, dL coming back
+  float* dW = dL + K * T;                                        // [K][T]
+  float* ds = dW + K * T;                                        // [K][Dcp]
+  float* c = ds + K * Dcp;                                       // [K][Dcp]: s, then c
+  int* valid = reinterpret_cast<int*>(c + K * Dcp);
+  const int ncb = (Dc + 31) / 32, ndb = (D + 31) / 32, ntile = (T + 31) / 32;
+  f32x16 sacc[NB];
+#pragma unroll
+  for (int j = 0; j < NB; ++j) mb_zero(sacc[j]);
+  bool bad = false;
+
+  for (int64_t b = blockIdx.x; b < a.B; b += gridDim.x) {
+    rt_forward<true>(a, b, xs, u, Wall, dL, c, valid, nullptr, tid, bad);
+    __syncthreads();
+    for (int i = tid; i < K * T; i += MI_NTHR) dL[i] = 0.f;
+    __syncthreads();
+
+    for (int r = R - 1; r >= 0; --r) {
+      const bool last = r == R - 1;
+      const float* Wr = Wall + (size_t)r * K * T;
+      for (int k = wave; k < K; k += 4) {                        // s, dc -> ds, c of the row
+        const float* Wk = Wr + k * T;
+        const float* dLk = dL + k * T;
+        float *dsk = ds + k * Dcp, *ck = c + k * Dcp;
+        float n2 = 0.f, sd = 0.f;
+        for (int d = lane; d < Dc; d += 64) {
+          float acc = 0.f, dc = 0.f;
+          if (last) {
+            dc = gout[((int64_t)b * K + k) * Dc + d];
+            acc = mi_dot(Wk, u + d, Dcp, T);
+          } else {
+            mi_dot2(Wk, dLk, u + d, Dcp, T, acc, dc);
+          }
+          ck[d] = acc;
+          dsk[d] = dc;
+          n2 = fmaf(acc, acc, n2);
+          sd = fmaf(acc, dc, sd);
+        }
+        n2 = group_sum<64>(n2);
+        sd = group_sum<64>(sd);
+        const float n = sqrtf(n2), den = 1.f + n2, f = n / den;
+        const float g = n > 0.f ? (1.f - n2) / (den * den * n) * sd : 0.f;     // f'(n) / n (s . dc)
+        for (int d = lane; d < Dc; d += 64) {
+          const float sv = ck[d];
+          dsk[d] = fmaf(sv, g, f * dsk[d]);
+          ck[d] = sv * f;
+        }
+      }
+      __syncthreads();
+      for (int i = tid; i < T * Dc; i += MI_NTHR) {              // du += W_r^T ds + dL^T c
+        const int t = i / Dc, d = i - t * Dc;
+        float acc = last ? 0.f : du[t * Dcp + d];
+        for (int k = 0; k < K; ++k) {
+          acc = fmaf(Wr[k * T + t], ds[k * Dcp + d], acc);
+          if (!last) acc = fmaf(dL[k * T + t], c[k * Dcp + d], acc);
+        }
+        du[t * Dcp + d] = acc;
+      }
+      __syncthreads();
+      for (int k = wave; k < K; k += 4) {                        // dW = ds u^T and the softmax, back
+        const float* Wk = Wr + k * T;
+        const float* dsk = ds + k * Dcp;
+        float *dLk = dL + k * T, *dWk = dW + k * T;
+        float dot = 0.f;
+        for (int t = lane; t < T; t += 64) {
+          const float acc = mi_dot(dsk, u + t * Dcp, 1, Dc);
+          dWk[t] = acc;
+          dot = fmaf(acc, Wk[t], dot);
+        }
+        dot = group_sum<64>(dot);
+        for (int t = lane; t < T; t += 64)
+          if (valid[t]) dLk[t] = dLk[t] + Wk[t] * (dWk[t] - dot);
+      }
+      __syncthreads();
+    }
+
+    for (int task = wave; task < ntile * ndb; task += 4) {       // gkeys[b] = du S^T
+      const int tile = task / ndb, db = task - tile * ndb;
+      const int t = tile * 32 + lo, n = db * 32 + lo;
+      const bool tok = t < T, nok = n < D;
+      const float* dr = du + (tok ? t : T - 1) * Dcp;
+      const float* __restrict__ Sr = a.S + (int64_t)(nok ? n : D - 1) * Dc;
+      f32x16 acc;
+      mb_zero(acc);
+      mi_mma(acc, Dc, hi, [&](int k) { return tok ? dr[k] : 0.f; },
+             [&](int k) { const float v = Sr[k]; return nok ? v : 0.f; });
+#pragma unroll
+      for (int rr = 0; rr < 16; ++rr) {
+        const int row = tile * 32 + mb_row(rr, hi);
+        if (row < T && nok) gkeys[((int64_t)b * T + row) * D + n] = acc[rr];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {                               // dS += x^T du
+      const int blk = wave + 4 * j;
+      if (blk < ndb * ncb) {
+        const int db = blk / ncb, cb = blk - db * ncb;
+        const int m = db * 32 + lo, n = cb * 32 + lo;
+        const bool mok = m < D, nok = n < Dc;
+        const float* xc = xs + (mok ? m : D - 1);
+        const float* dcn = du + (nok ? n : Dc - 1);
+        mi_mma(sacc[j], T, hi, [&](int k) { const float v = xc[k * Dp]; return mok ? v : 0.f; },
+               [&](int k) { const float v = dcn[k * Dcp]; return nok ? v : 0.f; });
+      }
+    }
+    __syncthreads();                                             // the next example overwrites all of it
+  }
+
+  float* __restrict__ slot = slots + (int64_t)blockIdx.x * D * Dc;
+#pragma unroll
+  for (int j = 0; j < NB; ++j) {
+    const int blk = wave + 4 * j;
+    if (blk < ndb * ncb) {
+      const int db = blk / ncb, cb = blk - db * ncb, n = cb * 32 + lo;
+#pragma unroll
+      for (int rr = 0; rr < 16; ++rr) {
+        const int m = db * 32 + mb_row(rr, hi);
+        if (m < D && n < Dc) slot[m * Dc + n] = sacc[j][rr];
+      }
+    }
+  }
+}
+
+struct LaArgs {
+  const float* embed;
+  int64_t ld, V;
+  const int64_t* items;
+  int64_t B;
+  const float* m;
+  const int32_t* kv;
+  int Ns, C, E, Dc, K;
+};
+
+// One wave per example; blockDim.x / 64 examples per workgroup.  A wave past the batch computes on zeros and writes nothing.
+template <bool BWD>
+__global__ __launch_bounds__(MI_NTHR) void mind_laa_kernel(LaArgs a, float* __restrict__ out, float* __restrict__ loss,
+                                                           const float* __restrict__ gout,
+                                                           const float* __restrict__ gloss, float* __restrict__ gm,
+                                                           float* __restrict__ gitems, int* __restrict__ oob) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int Ns = a.Ns, C = a.C, E = a.E, Dc = a.Dc, K = a.K, Dcp = mi_odd(Dc);
+  const int64_t b = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;
+  const bool live = b < a.B;
+  float* ms = lds + (size_t)wave * la_lds_floats(Ns, Dc, K);     // [K][Dcp]
+  float* xs = ms + K * Dcp;                                      // [Ns][Dcp]
+  float* sc = xs + Ns * Dcp;                                     // [K][Ns]: the scores, then dsc
+  float* w = sc + K * Ns;                                        // [K][Ns]
+  float* o = w + K * Ns;                                         // [Ns]
+  float* go = o + Ns;                                            // [Ns]
+  const int kv = live ? a.kv[b] : 0;
+  bool bad = false;
+
+  for (int i = lane; i < K * Dc; i += 64) {
+    const int k = i / Dc, d = i - k * Dc;
+    ms[k * Dcp + d] = live ? a.m[((int64_t)b * K + k) * Dc + d] : 0.f;
+  }
+  if (live) {
+    mi_gather<64>(a.embed, a.ld, a.V, a.items + b * Ns * C, Ns, C, E, xs, Dcp, lane, bad);
+  } else {
+    for (int i = lane; i < Ns * Dcp; i += 64) xs[i] = 0.f;
+  }
+  wave_sync();
+  for (int i = lane; i < K * Ns; i += 64) {
+    const int k = i / Ns, sI = i - k * Ns;
+    float acc = 0.f;
+    for (int d = 0; d < Dc; ++d) acc = fmaf(ms[k * Dcp + d], xs[sI * Dcp + d], acc);
+    sc[i] = acc;
+  }
+  wave_sync();
+  for (int sI = lane; sI < Ns; sI += 64) {
+    float mx = -FLT_MAX;
+    for (int k = 0; k < K; ++k) mx = fmaxf(mx, k < kv ? sc[k * Ns + sI] : -FLT_MAX);
+    float sum = 0.f;
+    for (int k = 0; k < K; ++k) {
+      const float ex = expf((k < kv ? sc[k * Ns + sI] : -FLT_MAX) - mx);
+      w[k * Ns + sI] = ex;
+      sum += ex;
+    }
+    float ov = 0.f;
+    for (int k = 0; k < K; ++k) {
+      const float wv = w[k * Ns + sI] / sum;
+      w[k * Ns + sI] = wv;
+      ov = fmaf(wv, sc[k * Ns + sI], ov);
+    }
+    o[sI] = ov;
+    if (!BWD && live) out[b * Ns + sI] = ov;
+  }
+  wave_sync();
+  float mx = -FLT_MAX;
+  for (int sI = lane; sI < Ns; sI += 64) mx = fmaxf(mx, o[sI]);
+  mx = wave_max(mx);
+  float sum = 0.f;
+  for (int sI = lane; sI < Ns; sI += 64) sum += expf(o[sI] - mx);
+  sum = group_sum<64>(sum);
+  const float lse = mx + logf(sum);
+  if (!BWD) {
+    if (lane == 0 && live) loss[b] = lse - o[0];
+  } else {
+    const float gl = (gloss && live) ? gloss[b] : 0.f;
+    for (int sI = lane; sI < Ns; sI += 64) {
+      float g = (gout && live) ? gout[b * Ns + sI] : 0.f;
+      g = fmaf(gl, expf(o[sI] - lse) - (sI == 0 ? 1.f : 0.f), g);
+      go[sI] = g;
+    }
+    wave_sync();
+    for (int i = lane; i < K * Ns; i += 64) {
+      const int k = i / Ns, sI = i - k * Ns;
+      const float wv = w[i];
+      sc[i] = go[sI] * (k < kv ? fmaf(wv, sc[i] - o[sI], wv) : wv);
+    }
+    wave_sync();
+    for (int i = lane; i < K * Dc; i += 64) {
+      const int k = i / Dc, d = i - k * Dc;
+      float acc = 0.f;
+      for (int sI = 0; sI < Ns; ++sI) acc = fmaf(sc[k * Ns + sI], xs[sI * Dcp + d], acc);
+      if (live) gm[((int64_t)b * K + k) * Dc + d] = acc;
+    }
+    for (int i = lane; i < Ns * Dc; i += 64) {
+      const int sI = i / Dc, d = i - sI * Dc;
+      float acc = 0.f;
+      for (int k = 0; k < K; ++k) acc = fmaf(sc[k * Ns + sI], ms[k * Dcp + d], acc);
+      if (live) gitems[((int64_t)b * Ns + sI) * Dc + d] = acc;
+    }
+  }
+  if (!BWD && bad && oob) *oob = 1;
+}
+
+static int rt_shape(int64_t B, int T, int E, int C, int Dc, int K, int R) {
+  if (B < 0 || T < 1 || E < 1 || C < 1 || Dc < 1 || K < 1 || R < 1) return REC_E_ARG;
+  if ((int64_t)E * C > MI_MAXD || Dc > MI_MAXD || K > MI_MAXK || R > MI_MAXR || B >= ((int64_t)1 << 31) ||
+      T > (int)(MI_LDS_CAP / sizeof(float)))
+    return REC_E_UNSUPPORTED;
+  if (sizeof(float) * rt_lds_floats(T, E * C, Dc, K, R) > MI_LDS_CAP) return REC_E_UNSUPPORTED;
+  return REC_OK;
+}
+// as many workgroups as the chip holds at once: 4, 2 or 1 per CU by the registers of the instantiation (1, 4 or 16 blocks
+// of dS per wave), 256 CUs
+static int rt_grid(int64_t B, int D, int Dc) {
+  const int nblk = ((D + 31) / 32) * ((Dc + 31) / 32);
+  const int cap = nblk <= 4 ? MI_GRID : (nblk <= 16 ? MI_GRID / 2 : MI_GRID / 4);
+  return B < cap ? (int)B : cap;
+}
+
+// waves (= examples) of a workgroup of the attention: 4, 2 or 1, as many as fit; 0: not even one
+static int la_waves(int Ns, int Dc, int K) {
+  const size_t one = sizeof(float) * la_lds_floats(Ns, Dc, K);
+  return 4 * one <= MI_LDS_CAP ? 4 : (2 * one <= MI_LDS_CAP ? 2 : (one <= MI_LDS_CAP ? 1 : 0));
+}
+static int la_shape(int64_t B, int Ns, int E, int C, int K) {
+  if (B < 0 || Ns < 1 || E < 1 || C < 1 || K < 1) return REC_E_ARG;
+  if ((int64_t)E * C > MI_MAXD || K > MI_MAXK || B >= ((int64_t)1 << 31) || Ns > (int)(MI_LDS_CAP / sizeof(float)))
+    return REC_E_UNSUPPORTED;
+  if (la_waves(Ns, E * C, K) == 0) return REC_E_UNSUPPORTED;
+  return REC_OK;
+}
+
+template <int NB>
+static int rt_launch_bwd(const RtArgs& a, int grid, size_t lds, const float* gout, float* gkeys, float* slots,
+                         hipStream_t st) {
+  if (hipError_t err = rec_allow_lds<mind_routing_bwd_kernel<NB>>(MI_LDS_CAP)) return (int)err;
+  hipLaunchKernelGGL(mind_routing_bwd_kernel<NB>, dim3(grid), dim3(MI_NTHR), lds, st, a, gout, gkeys, slots);
+  REC_LAUNCH_CHECK();
+  return REC_OK;
+}
+
+}  // namespace
+
+extern "C" size_t rec_mind_routing_workspace_bytes(int64_t B, int T, int E, int C, int Dc, int K, int R) {
+  if (rt_shape(B, T, E, C, Dc, K, R) != REC_OK) return 0;
+  return sizeof(float) * ((size_t)rt_grid(B, E * C, Dc) * E * C * Dc + 4);
+}
+
+extern "C" int rec_mind_routing_fwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* series,
+                                        int64_t B, int T, const float* S, const float* B0, int Dc, int K, int R,
+                                        int64_t padding_index, float* out, int* oob_flag, void* stream) {
+  if (int rc = rt_shape(B, T, E, C, Dc, K, R)) return rc;
+  if (ld < E || V <= 0 || !embed || !series || !S || !B0 || !out) return REC_E_ARG;
+  if (B == 0) return REC_OK;
+  const RtArgs a{embed, ld, V, series, B, S, B0, padding_index, T, C, E, E * C, Dc, K, R};
+  if (hipError_t err = rec_allow_lds<mind_routing_fwd_kernel>(MI_LDS_CAP)) return (int)err;
+  const size_t lds = sizeof(float) * rt_fwd_lds_floats(T, E * C, Dc, K);
+  const int grid = B < 65536 ? (int)B : 65536;
+  hipLaunchKernelGGL(mind_routing_fwd_kernel, dim3(grid), dim3(MI_NTHR), lds, as_stream(stream), a, out, oob_flag);
+  REC_LAUNCH_CHECK();
+  return REC_OK;
+}
+
+extern "C" int rec_mind_routing_bwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* series,
+                                        int64_t B, int T, const float* S, const float* B0, int Dc, int K, int R,
+                                        int64_t padding_index, const float* gout, float* gkeys, float* dS,
+                                        void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = rt_shape(B, T, E, C, Dc, K, R)) return rc;
+  if (ld < E || V <= 0 || !embed || !series || !S || !B0 || !gout || !gkeys || !dS || !workspace) return REC_E_ARG;
+  const int D = E * C, grid = rt_grid(B, D, Dc);
+  if (workspace_bytes < sizeof(float) * (size_t)grid * D * Dc) return REC_E_WORKSPACE;
+  hipStream_t st = as_stream(stream);
+  if (B == 0) return REC_OK;                                     // nothing is launched and nothing written
+  const RtArgs a{embed, ld, V, series, B, S, B0, padding_index, T, C, E, D, Dc, K, R};
+  const size_t lds = sizeof(float) * rt_lds_floats(T, D, Dc, K, R);
+  float* slots = static_cast<float*>(workspace);
+  const int nblk = ((D + 31) / 32) * ((Dc + 31) / 32), nb = (nblk + 3) / 4;
+  const int rc = nb <= 1   ? rt_launch_bwd<1>(a, grid, lds, gout, gkeys, slots, st)
+                 : nb <= 4 ? rt_launch_bwd<4>(a, grid, lds, gout, gkeys, slots, st)
+                           : rt_launch_bwd<16>(a, grid, lds, gout, gkeys, slots, st);
+  if (rc) return rc;
+  return rec_slot_sum(REC_SLOTS_WAVE, D * Dc, grid, slots, {{dS}, {D * Dc}}, st);
+}
+
+extern "C" size_t rec_mind_laa_lds_bytes(int Ns, int E, int C, int K) {
+  if (la_shape(0, Ns, E, C, K) != REC_OK) return 0;
+  return sizeof(float) * la_waves(Ns, E * C, K) * la_lds_floats(Ns, E * C, K);
+}
+
+extern "C" int rec_mind_laa_fwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* items,
+                                    int64_t B, int Ns, const float* m, const int32_t* kv, int K, float* out,
+                                    float* loss, int* oob_flag, void* stream) {
+  if (int rc = la_shape(B, Ns, E, C, K)) return rc;
+  if (ld < E || V <= 0 || !embed || !items || !m || !kv || !out || !loss) return REC_E_ARG;
+  if (B == 0) return REC_OK;
+  const int Dc = E * C, wpb = la_waves(Ns, Dc, K);
+  const LaArgs a{embed, ld, V, items, B, m, kv, Ns, C, E, Dc, K};
+  if (hipError_t err = rec_allow_lds<mind_laa_kernel<false>>(MI_LDS_CAP)) return (int)err;
+  const size_t lds = sizeof(float) * wpb * la_lds_floats(Ns, Dc, K);
+  hipLaunchKernelGGL(mind_laa_kernel<false>, dim3((unsigned)ceil_div64(B, wpb)), dim3(64 * wpb), lds, as_stream(stream),
+                     a, out, loss, nullptr, nullptr, nullptr, nullptr, oob_flag);
+  REC_LAUNCH_CHECK();
+  return REC_OK;
+}
+
+extern "C" int rec_mind_laa_bwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* items,
+                                    int64_t B, int Ns, const float* m, const int32_t* kv, int K, const float* gout,
+                                    const float* gloss, float* gm, float* gitems, void* stream) {
+  if (int rc = la_shape(B, Ns, E, C, K)) return rc;
+  if (ld < E || V <= 0 || !embed || !items || !m || !kv || (!gout && !gloss) || !gm || !gitems) return REC_E_ARG;
+  if (B == 0) return REC_OK;
+  const int Dc = E * C, wpb = la_waves(Ns, Dc, K);
+  const LaArgs a{embed, ld, V, items, B, m, kv, Ns, C, E, Dc, K};
+  if (hipError_t err = rec_allow_lds<mind_laa_kernel<true>>(MI_LDS_CAP)) return (int)err;
+  const size_t lds = sizeof(float) * wpb * la_lds_floats(Ns, Dc, K);
+  hipLaunchKernelGGL(mind_laa_kernel<true>, dim3((unsigned)ceil_div64(B, wpb)), dim3(64 * wpb), lds, as_stream(stream),
+                     a, nullptr, nullptr, gout, gloss, gm, gitems, nullptr);
+  REC_LAUNCH_CHECK();
+  return REC_OK;
+}

@@ -881,3 +881,56 @@ class MMOEBody(torch.autograd.Function):
         weights, saved = rest[:12], rest[12:]
         dx, grads = ops.mmoe_bwd(x, weights, saved, dout.contiguous(), *ctx.flags)
         return (dx, None, None) + tuple(grads)
+
+
+class CapsuleRouting(torch.autograd.Function):
+    """MultiInterestExtractorLayer.call fused with the series lookup (6.MIND/CustomLayers.py:111-138, 204-212;
+    csrc/mind.hip): table, series ids [B,T,C], S [C E, Dc], the non-trainable logits B0 [K,T] -> the capsules [B,K,Dc].
+    One launch forward, which saves nothing but its inputs; the backward runs the rounds again and differentiates
+    through all of them.  The table's gradient is a sparse COO tensor of de-duplicated rows; B0 gets none."""
+
+    @staticmethod
+    def forward(ctx, embed, series, S, B0, routing_rounds, padding_index, oob):
+        S, B0 = S.contiguous(), B0.contiguous()
+        out = ops.mind_routing_fwd(embed, series, S, B0, routing_rounds, padding_index, oob)
+        ctx.save_for_backward(embed, series, S, B0)
+        ctx.cfg = (routing_rounds, padding_index)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        embed, series, S, B0 = ctx.saved_tensors
+        V, E = embed.shape
+        gkeys, dS = ops.mind_routing_bwd(embed, series, S, B0, gout.contiguous(), *ctx.cfg)
+        gembed = None
+        if ctx.needs_input_grad[0]:
+            plan = ops.DedupPlan(series, V)
+            gembed = _sparse_grad(plan, gkeys.reshape(-1, E), E, (V, E))
+        return gembed, None, dS, None, None, None, None
+
+
+class LabelAwareAttention(torch.autograd.Function):
+    """LabelAwareAttention, the inner products with the sampled items and the sampled-softmax loss, fused with the item
+    lookup (6.MIND/CustomLayers.py:141-158, 252-285; csrc/mind.hip): table, item ids [B,Ns,C], capsules m [B,K,C E],
+    valid capsule counts kv int32 [B] -> (out [B,Ns], loss [B]).  One launch each way; an output nobody used arrives as
+    None in the backward, not as zeros."""
+
+    @staticmethod
+    def forward(ctx, embed, items, m, kv, oob):
+        m = m.contiguous()
+        out, loss = ops.mind_laa_fwd(embed, items, m, kv, oob)
+        ctx.save_for_backward(embed, items, m, kv)
+        ctx.set_materialize_grads(False)
+        return out, loss
+
+    @staticmethod
+    def backward(ctx, gout, gloss):
+        embed, items, m, kv = ctx.saved_tensors
+        V, E = embed.shape
+        gm, gitems = ops.mind_laa_bwd(embed, items, m, kv, None if gout is None else gout.contiguous(),
+                                      None if gloss is None else gloss.contiguous())
+        gembed = None
+        if ctx.needs_input_grad[0] and (gout is not None or gloss is not None):
+            plan = ops.DedupPlan(items, V)
+            gembed = _sparse_grad(plan, gitems.reshape(-1, E), E, (V, E))
+        return gembed, None, gm, None, None

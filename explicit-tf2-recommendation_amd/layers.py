@@ -41,6 +41,9 @@ libmi355rec.so (through functional.py / ops.py).  Reference classes and the line
   BilinearInteractionPlusLayer  11.FiBiNet++/CustomLayers.py:208-242
   MMOELayer                     4.MMOE/CustomLayers.py:107-173
   ESMMLayer                     4.MMOE/CustomLayers.py:175-245
+  MultiInterestExtractorLayer   6.MIND/CustomLayers.py:62-138   (takes the table and the ids: the lookup is fused)
+  LabelAwareAttention           6.MIND/CustomLayers.py:141-158  (with the inner products and the loss of :267-285)
+  MINDLayer                     6.MIND/CustomLayers.py:161-285
 
 Parameters are named after the TF checkpoint keys (``embed.embeddings``, ``w.embeddings``, ``bias``,
 ``MLP_layer1.kernel_0`` ...), so a TensorBundle checkpoint maps onto ``state_dict()`` by name.
@@ -2020,3 +2023,156 @@ class ESMMLayer(MMOELayer):
     def __init__(self, categorical_features=_MMOE_CAT, continuous_features=_MMOE_CONT, feature_dims=160000,
                  embedding_dims=16, expert_num=3):
         super().__init__(categorical_features, continuous_features, feature_dims, embedding_dims, expert_num)
+
+
+# ---------------------------------------------------------------------------------------------------
+# MIND: multi-interest retrieval (6.MIND/CustomLayers.py:62-285)
+# ---------------------------------------------------------------------------------------------------
+
+def _stack_ids(inputs, names, device):
+    """tf.stack(axis=2) of 2-D id features: [B,T] each -> int64 [B,T,len(names)] on ``device``."""
+    cols = []
+    for name in names:
+        t = inputs[name]
+        if not isinstance(t, torch.Tensor):
+            t = torch.as_tensor(t)
+        t = t.to(device=device, dtype=torch.int64).contiguous()
+        if t.dim() != 2:
+            raise ValueError("feature %r must have shape [B,T], got %s" % (name, tuple(t.shape)))
+        cols.append(t)
+    B, T = cols[0].shape
+    return ops.index_pack(cols).reshape(B, T, len(cols))
+
+
+def mind_capsule_count_table(max_length, capsules_num):
+    """int32 [max_length + 1]: the number of valid capsules of an example with n valid behaviours.  The reference computes
+    ``log(n) / log(2.)`` in fp32, clips it at capsules_num and masks capsule k where ``k + 1 >`` it
+    (6.MIND/CustomLayers.py:214-218).  This is the numpy-float32 reading of those lines, in that order of operations, built
+    once on the host (nobody here can run TensorFlow); n = 0 gives -inf and so 0 capsules."""
+    import numpy as np
+    n = np.arange(int(max_length) + 1, dtype=np.float32)
+    with np.errstate(divide="ignore"):
+        v = np.log(n) / np.log(np.float32(2.))
+    v = np.minimum(v, np.float32(capsules_num))
+    k1 = np.arange(int(capsules_num), dtype=np.float32) + np.float32(1)
+    assert v.dtype == np.float32 and k1.dtype == np.float32
+    return torch.from_numpy((~(k1[None, :] > v[:, None])).sum(axis=1).astype(np.int32))
+
+
+class MultiInterestExtractorLayer(Layer):
+    """6.MIND/CustomLayers.py:62-138: B2I dynamic routing of a behaviour series into ``capsules_num`` interest capsules.
+    ``S`` [D, capsules_dim] is trained, the routing logits ``B`` [capsules_num, T] are a buffer (the reference's
+    non-trainable weight); both random_normal(stddev 0.05).  squash is evaluated as c n / (1 + n^2), zero with a zero
+    gradient at n = 0 where the reference's n^2 / ((1 + n^2) n) is 0/0.
+    The lookup is part of the kernel, so the call takes ``(table, series)`` -- the embedding matrix [V,E] and the stacked
+    ids [B,T,C] -- where the reference takes the looked-up behaviours and their mask; the mask is
+    ``series[:, :, 0] != padding_index``, as MINDLayer computes it.  ``input_shape=(T, D)`` (extension) builds eagerly."""
+
+    def __init__(self, capsules_num, capsules_dim, routing_rounds=3, input_shape=None):
+        super().__init__()
+        self.capsules_num = capsules_num
+        self.capsules_dim = capsules_dim
+        self.routing_rounds = routing_rounds
+        self.built = False
+        if input_shape is not None:
+            self.build(input_shape)
+
+    def build(self, input_shape):
+        T, D = (int(v) for v in tuple(input_shape)[-2:])
+        ops.mind_check_shape(D, self.capsules_dim, self.capsules_num, self.routing_rounds, T=T)
+        init = _initializer("random_normal")
+        self.S = torch.nn.Parameter(init((D, self.capsules_dim)))
+        self.register_buffer("B", init((self.capsules_num, T)))
+        self.built = True
+
+    def forward(self, inputs, padding_index=0, oob=None):
+        table, series = inputs
+        if not self.built:
+            self.build((series.shape[1], series.shape[2] * table.shape[1]))
+            self.to(table.device)
+        return Fn.CapsuleRouting.apply(table, series, self.S, self.B, self.routing_rounds, padding_index, oob)
+
+
+class LabelAwareAttention(Layer):
+    """6.MIND/CustomLayers.py:141-158 together with the inner products and the loss of MINDLayer.call (:267-285), which is
+    where its output goes: the capsule weights are a masked softmax over the capsules' scores against every sampled item,
+    ``output[b,s]`` the weighted capsule's inner product with item s, ``loss[b]`` the softmax cross entropy with the label
+    at sample 0.  The item lookup is part of the kernel: the call takes the table, the stacked item ids [B,Ns,C], the
+    capsules [B,K,C E] and the number of valid capsules int32 [B] (capsule k is masked iff k >= that number)."""
+
+    def forward(self, table, items, mlped_capsules, valid_capsules_num, oob=None):
+        return Fn.LabelAwareAttention.apply(table, items, mlped_capsules, valid_capsules_num, oob)
+
+
+class MINDLayer(Layer):
+    """6.MIND/CustomLayers.py:161-285.  ``seq_length`` (extension): the length T of the behaviour series; given, the
+    extractor's ``S`` / ``B`` exist from construction (a state dict can be loaded), otherwise they are built by the first
+    call.  ``generate_interest_capsules`` returns the capsule COUNT int32 [B] as ``valid_capsules_num`` (what
+    save_interest_capsules casts the reference's fp32 log2 to; 0 where that is -inf), see mind_capsule_count_table."""
+
+    def __init__(self, user_and_context_categorical_features=["uid", "utag1", "utag2", "utag3", "utag4"],
+                 item_categorical_features=["label_goods_ids", "label_shop_ids", "label_cate_ids"],
+                 behavior_series_features=["visited_goods_ids", "visited_shop_ids", "visited_cate_ids"],
+                 feature_dims=160000, embedding_dims=16, activation="ReLU", padding_index=0, capsules_num=4,
+                 seq_length=None):
+        super().__init__()
+        self.user_and_context_categorical_features = user_and_context_categorical_features
+        self.item_categorical_features = item_categorical_features
+        assert len(item_categorical_features) == len(behavior_series_features), \
+            "Features to be interacted should match in item and behavior series"
+        self.behavior_series_features = behavior_series_features
+        self.feature_dims = feature_dims
+        self.embedding_dims = embedding_dims
+        self.embed = Embedding(feature_dims, embedding_dims)
+        capsules_dim = embedding_dims * len(item_categorical_features)
+        ops.mind_check_shape(capsules_dim, capsules_dim, capsules_num)
+        self.context_mlp = Dense(capsules_dim // 2, activation="sigmoid",
+                                 input_dim=len(user_and_context_categorical_features) * embedding_dims)
+        self.context_bn = BatchNormalization(input_dim=capsules_dim // 2)
+        if isinstance(activation, str) and activation not in ("PReLU", "Dice", "None"):
+            activation = activation.lower()              # Keras resolves 'ReLU' and 'relu' to the same function
+        self.final_mlp = make_mlp_layer([capsules_dim * 4, capsules_dim], activation=activation,
+                                        input_dim=capsules_dim // 2 + capsules_dim)
+        self.padding_index = padding_index
+        self.capsules_num = capsules_num
+        self.MIE_layer = MultiInterestExtractorLayer(
+            capsules_num=capsules_num, capsules_dim=capsules_dim,
+            input_shape=None if seq_length is None else (seq_length, capsules_dim))
+        self.LAA_layer = LabelAwareAttention()
+        self._count_table = None
+
+    def _capsule_counts(self, series):
+        T = series.shape[1]
+        if self._count_table is None or self._count_table.numel() != T + 1 or self._count_table.device != series.device:
+            self._count_table = mind_capsule_count_table(T, self.capsules_num).to(series.device)
+        n_valid = (series[:, :, 0] != self.padding_index).sum(dim=1)
+        return self._count_table[n_valid]
+
+    def _capsules(self, inputs, flag):
+        device = self._device()
+        series = _stack_ids(inputs, self.behavior_series_features, device)
+        interest_capsules = self.MIE_layer((self.embed.embeddings, series), self.padding_index, flag)
+        valid_capsules_num = self._capsule_counts(series)
+        K = self.capsules_num
+        capsules_mask = torch.arange(K, device=device)[None, :] >= valid_capsules_num[:, None]
+        X_cate = assemble_index(inputs, self.user_and_context_categorical_features)
+        profile = self.embed(X_cate, flag)
+        profile_output = self.context_bn(self.context_mlp(profile.reshape(profile.shape[0], -1)))
+        B, half = profile_output.shape
+        concated = torch.cat([profile_output[:, None, :].expand(B, K, half), interest_capsules], dim=2)
+        mlped_capsules = self.final_mlp(concated.reshape(B * K, -1)).reshape(B, K, -1)
+        return mlped_capsules, capsules_mask, valid_capsules_num
+
+    def generate_interest_capsules(self, inputs):
+        flag = ops.new_flag(self._device()) if self.check_ids else None
+        result = self._capsules(inputs, flag)
+        self._raise_if_oob(flag)
+        return result
+
+    def forward(self, inputs):
+        flag = ops.new_flag(self._device()) if self.check_ids else None
+        mlped_capsules, _, valid_capsules_num = self._capsules(inputs, flag)
+        items = _stack_ids(inputs, self.item_categorical_features, mlped_capsules.device)
+        output, loss = self.LAA_layer(self.embed.embeddings, items, mlped_capsules, valid_capsules_num, flag)
+        self._raise_if_oob(flag)
+        return {"output": output, "loss": loss}

@@ -1607,3 +1607,138 @@ def mmoe_bwd(x, weights, saved, dout, gate_softmax_passes=1, ctcvr=False):
                                    int(gate_softmax_passes), int(bool(ctcvr)), _ptr(dx), *[_ptr(g) for g in grads],
                                    _ptr(ws), nbytes, _stream()), "rec_mmoe_bwd_f32")
     return dx, grads
+
+
+# ---- MIND: capsule routing and label-aware attention + sampled-softmax loss, one launch each way (csrc/mind.hip).  The
+# limits are DIN's key width and AFM's attention size, the rounds and the LDS fit are the header's formulas.
+MIND_MAX_ROUNDS = 8
+_MIND_LDS_CAP = 150 * 1024
+
+
+def _odd(n):
+    return n | 1
+
+
+def mind_routing_lds_bytes(T, D, Dc, K, R):
+    """LDS of one workgroup of the routing backward (include/mi355rec.h): what both directions are held to."""
+    return 4 * (T * _odd(D) + 2 * T * _odd(Dc) + (R + 2) * K * T + 2 * K * _odd(Dc) + T)
+
+
+def mind_laa_lds_bytes(Ns, Dc, K):
+    """LDS of one example of the label-aware attention (include/mi355rec.h)."""
+    return 4 * ((K + Ns) * _odd(Dc) + 2 * K * Ns + 2 * Ns)
+
+
+def mind_check_shape(D, Dc, K, R=3, T=None, Ns=None):
+    """ValueError for sizes that describe no MIND body, NotImplementedError naming the limit for shapes the kernels do
+    not cover (the ABI would return -2): key width D = E C, capsule width Dc, K capsules, R routing rounds, and -- where
+    given -- the series length T (routing) and the number of sampled items Ns (attention: its rows have Dc columns)."""
+    sizes = [D, Dc, K, R] + [v for v in (T, Ns) if v is not None]
+    if min(sizes) < 1:
+        raise ValueError("every size of a MIND body must be positive, got D=%d, Dc=%d, capsules=%d, rounds=%d, T=%r, "
+                         "Ns=%r" % (D, Dc, K, R, T, Ns))
+    if D > DIN_MAX_D or Dc > DIN_MAX_D or K > AFM_MAX_A or R > MIND_MAX_ROUNDS:
+        raise NotImplementedError(
+            "MIND kernels cover key width and capsule width <= %d, capsules <= %d and routing rounds <= %d; got key "
+            "width=%d, capsule width=%d, capsules=%d, rounds=%d" % (DIN_MAX_D, AFM_MAX_A, MIND_MAX_ROUNDS, D, Dc, K, R))
+    if T is not None and mind_routing_lds_bytes(T, D, Dc, K, R) > _MIND_LDS_CAP:
+        raise NotImplementedError(
+            "MIND routing holds one example in LDS: 4 (T (D|1) + 2 T (Dc|1) + (R + 2) K T + 2 K (Dc|1) + T) <= %d bytes; "
+            "got %d at T=%d, key width=%d, capsule width=%d, capsules=%d, rounds=%d"
+            % (_MIND_LDS_CAP, mind_routing_lds_bytes(T, D, Dc, K, R), T, D, Dc, K, R))
+    if Ns is not None and mind_laa_lds_bytes(Ns, Dc, K) > _MIND_LDS_CAP:
+        raise NotImplementedError(
+            "MIND label-aware attention holds one example in LDS: 4 ((K + Ns) (Dc|1) + 2 K Ns + 2 Ns) <= %d bytes; got "
+            "%d at Ns=%d, capsule width=%d, capsules=%d" % (_MIND_LDS_CAP, mind_laa_lds_bytes(Ns, Dc, K), Ns, Dc, K))
+
+
+def _mind_routing_args(embed, series, S, B0, R, padding_index):
+    _table(embed, "embed"); _i64(series, "series"); _f32(S, "S"); _f32(B0, "B0")
+    if series.dim() != 3 or S.dim() != 2 or B0.dim() != 2:
+        raise ValueError("capsule routing takes series [B,T,C], S [D,Dc] and B0 [K,T]; got %s, %s, %s"
+                         % (tuple(series.shape), tuple(S.shape), tuple(B0.shape)))
+    V, E = embed.shape
+    B, T, Cn = series.shape
+    D, Dc = S.shape
+    K = B0.shape[0]
+    if D != Cn * E or B0.shape[1] != T:
+        raise ValueError("capsule routing: S must have C E = %d rows and B0 T = %d columns; got S %s, B0 %s"
+                         % (Cn * E, T, tuple(S.shape), tuple(B0.shape)))
+    mind_check_shape(D, Dc, K, int(R), T=T)
+    return [_ptr(embed), embed.stride(0), V, E, Cn, _ptr(series), B, T, _ptr(S), _ptr(B0), Dc, K, int(R),
+            int(padding_index)], (B, T, Cn, E, D, Dc, K)
+
+
+def mind_routing_fwd(embed, series, S, B0, routing_rounds=3, padding_index=0, oob=None):
+    """Capsule routing of MultiInterestExtractorLayer over the looked-up series in one launch: series ids [B,T,C] into
+    ``embed``, S [C E, Dc], B0 [K, T] -> the squashed capsules of the last round [B, K, Dc].  Nothing else is saved."""
+    args, (B, T, Cn, E, D, Dc, K) = _mind_routing_args(embed, series, S, B0, routing_rounds, padding_index)
+    out = torch.empty((B, K, Dc), dtype=torch.float32, device=embed.device)
+    if B > 0:                                            # an empty batch answers from the sizes alone
+        check(lib.rec_mind_routing_fwd_f32(*args, _ptr(out), _ptr(oob), _stream()), "rec_mind_routing_fwd_f32")
+    return out
+
+
+def mind_routing_bwd(embed, series, S, B0, gout, routing_rounds=3, padding_index=0):
+    """-> (gkeys [B,T,C E], the IndexedSlices values of the series lookups, dS [C E, Dc]) from gout [B,K,Dc]; the rounds
+    are run again from the ids and differentiated through, all of them.  B0 has no gradient."""
+    args, (B, T, Cn, E, D, Dc, K) = _mind_routing_args(embed, series, S, B0, routing_rounds, padding_index)
+    if tuple(_f32(gout, "gout").shape) != (B, K, Dc):
+        raise ValueError("gout must be [B,K,Dc] = %s, got %s" % ((B, K, Dc), tuple(gout.shape)))
+    dev = embed.device
+    gkeys = torch.empty((B, T, D), dtype=torch.float32, device=dev)
+    dS = torch.zeros((D, Dc), dtype=torch.float32, device=dev) if B == 0 else \
+        torch.empty((D, Dc), dtype=torch.float32, device=dev)
+    if B > 0:
+        nbytes = lib.rec_mind_routing_workspace_bytes(B, T, E, Cn, Dc, K, int(routing_rounds))
+        ws = _workspace(nbytes, "rec_mind_routing_workspace_bytes", dev, torch.float32)
+        check(lib.rec_mind_routing_bwd_f32(*args, _ptr(gout), _ptr(gkeys), _ptr(dS), _ptr(ws), nbytes, _stream()),
+              "rec_mind_routing_bwd_f32")
+    return gkeys, dS
+
+
+def _mind_laa_args(embed, items, m, kv):
+    _table(embed, "embed"); _i64(items, "items"); _f32(m, "m"); _req(kv, torch.int32, "kv")
+    if items.dim() != 3 or m.dim() != 3 or kv.dim() != 1:
+        raise ValueError("label-aware attention takes items [B,Ns,C], m [B,K,Dc] and kv [B]; got %s, %s, %s"
+                         % (tuple(items.shape), tuple(m.shape), tuple(kv.shape)))
+    V, E = embed.shape
+    B, Ns, Cn = items.shape
+    K, Dc = m.shape[1:]
+    if m.shape[0] != B or kv.shape[0] != B or Dc != Cn * E:
+        raise ValueError("label-aware attention: m must be [B, K, C E] = [%d, K, %d] and kv [%d]; got m %s, kv %s"
+                         % (B, Cn * E, B, tuple(m.shape), tuple(kv.shape)))
+    mind_check_shape(Dc, Dc, K, 1, Ns=Ns)
+    return [_ptr(embed), embed.stride(0), V, E, Cn, _ptr(items), B, Ns, _ptr(m), _ptr(kv), K], (B, Ns, Dc, K)
+
+
+def mind_laa_fwd(embed, items, m, kv, oob=None):
+    """LabelAwareAttention over the looked-up sampled items, the inner products and the sampled-softmax loss in one
+    launch: item ids [B,Ns,C] into ``embed``, capsules m [B,K,C E], valid capsule counts kv int32 [B] -> (out [B,Ns],
+    loss [B]) with the label at sample 0."""
+    args, (B, Ns, Dc, K) = _mind_laa_args(embed, items, m, kv)
+    out = torch.empty((B, Ns), dtype=torch.float32, device=embed.device)
+    loss = torch.empty((B,), dtype=torch.float32, device=embed.device)
+    if B > 0:
+        check(lib.rec_mind_laa_fwd_f32(*args, _ptr(out), _ptr(loss), _ptr(oob), _stream()), "rec_mind_laa_fwd_f32")
+    return out, loss
+
+
+def mind_laa_bwd(embed, items, m, kv, gout=None, gloss=None):
+    """-> (gm [B,K,C E], gitems [B,Ns,C E], the IndexedSlices values of the item lookups) from gout [B,Ns] and / or
+    gloss [B] in one launch; with neither, zeros."""
+    args, (B, Ns, Dc, K) = _mind_laa_args(embed, items, m, kv)
+    dev = embed.device
+    if gout is None and gloss is None:
+        return (torch.zeros((B, K, Dc), dtype=torch.float32, device=dev),
+                torch.zeros((B, Ns, Dc), dtype=torch.float32, device=dev))
+    if gout is not None and tuple(_f32(gout, "gout").shape) != (B, Ns):
+        raise ValueError("gout must be [B,Ns] = %s, got %s" % ((B, Ns), tuple(gout.shape)))
+    if gloss is not None and tuple(_f32(gloss, "gloss").shape) != (B,):
+        raise ValueError("gloss must be [B] = [%d], got %s" % (B, tuple(gloss.shape)))
+    gm = torch.empty((B, K, Dc), dtype=torch.float32, device=dev)
+    gitems = torch.empty((B, Ns, Dc), dtype=torch.float32, device=dev)
+    if B > 0:
+        check(lib.rec_mind_laa_bwd_f32(*args, _ptr(gout), _ptr(gloss), _ptr(gm), _ptr(gitems), _stream()),
+              "rec_mind_laa_bwd_f32")
+    return gm, gitems

@@ -930,6 +930,66 @@ int rec_mmoe_bwd_f32(const float* x, const float* W1, const float* We2, const fl
                      float* dWt2, float* dbt2, float* dWt3, float* dbt3, void* workspace, size_t workspace_bytes,
                      void* stream);
 
+/* ---- MIND (MultiInterestExtractorLayer, LabelAwareAttention, MINDLayer.call, 6.MIND/CustomLayers.py:62-158, 263-285;
+ * csrc/mind.hip): capsule routing over a behaviour series, and label-aware attention with the sampled-softmax loss.
+ * Both families gather from embed [V, E] with row stride ld >= E; an id outside [0, V) reads as a zero row and sets
+ * *oob_flag (may be NULL).
+ *
+ * Capsule routing.  series int64 [B, T, C] as rec_din_attn_*, D = E C, S [D, Dc], B0 [K, T] (the layer's non-trainable
+ * logits, the same for every example), R rounds.  Per example b:
+ *   x_t = concat_r embed[series[b,t,r]]  [T, D]    valid_t = series[b,t,0] != padding_index    u = x S  [T, Dc]
+ *   L = B0;  R times:  W = softmax_t(valid_t ? L : -FLT_MAX)  [K, T],  c = squash(W u)  [K, Dc],
+ *                      and in every round but the last  L += c u^T
+ *   out[b] = c                                                                                    out [B, K, Dc]
+ * squash(s) = s n / (1 + n^2), n = |s|: at n = 0 it is 0 with a zero gradient, the limit of the reference's
+ * n^2 / ((1 + n^2) n), which is 0/0 there.  -FLT_MAX is the lowest finite float: an example with no valid position gets
+ * the uniform weights 1 / T over all T positions, padded ones included, and never NaN.  Padding may sit anywhere.
+ * The forward is one launch and saves nothing but out.  The backward takes gout [B, K, Dc], runs the rounds again from
+ * the ids and differentiates through all of them (no stop_gradient; B0 gets nothing): gkeys [B, T, D], the
+ * IndexedSlices values of the series lookups as rec_din_attn_bwd_f32's, and dS [D, Dc], both written, never added to.
+ * dS is reduced through one partial per workgroup of a capped grid and a slot sum in wave order.
+ * Supported, the same both ways: D = E C <= REC_DIN_MAX_D (256), Dc <= REC_DIN_MAX_D, K <= REC_AFM_MAX_A (16),
+ * 1 <= R <= 8, 0 <= B < 2^31 and the backward's LDS within the 150 KiB launch cap:
+ *   4 (T (D|1) + 2 T (Dc|1) + (R + 2) K T + 2 K (Dc|1) + T) <= 153600          (x|1: x made odd)
+ * e.g. T <= 226 at D = Dc = 48, K = 4, R = 3 and T <= 35 at D = Dc = 256, K = 16, R = 3.
+ * workspace (backward only): rec_mind_routing_workspace_bytes: min(B, 1024) partials of D Dc floats (at most 512 when dS
+ * has more than four 32 x 32 blocks, 256 when more than sixteen); 0: invalid or unsupported shape.
+ *
+ * Label-aware attention + loss.  items int64 [B, Ns, C], Dc = E C, m [B, K, Dc] (the capsules after the final MLP),
+ * kv int32 [B]: capsule k of example b is valid iff k < kv[b].  Per example:
+ *   x_s = concat_r embed[items[b,s,r]]  [Ns, Dc]      sc[k,s] = m_k . x_s
+ *   w[:,s] = softmax_k(k < kv ? sc[k,s] : -FLT_MAX)   (kv <= 0: uniform 1 / K)
+ *   out[s] = sum_k w[k,s] sc[k,s]   (the unmasked scores: equal to (sum_k w[k,s] m_k) . x_s)          out [B, Ns]
+ *   loss = logsumexp_s(out) - out[0]   (softmax cross entropy with the label at sample 0)            loss [B]
+ * The forward is one launch for both.  The backward is one launch from gout [B, Ns] and gloss [B], either of which may
+ * be NULL (not both): it recomputes the forward and writes gm [B, K, Dc] and gitems [B, Ns, Dc], the IndexedSlices
+ * values of the item lookups.  A masked capsule's score is a constant inside the softmax: it receives the direct term
+ * w[k,s] alone, which is zero unless every capsule is masked.
+ * Supported: Dc = E C <= REC_DIN_MAX_D, K <= REC_AFM_MAX_A, 0 <= B < 2^31 and one example's LDS within the launch cap:
+ *   4 ((K + Ns) (Dc|1) + 2 K Ns + 2 Ns) <= 153600
+ * (a workgroup holds 4, 2 or 1 examples, as many as fit).  rec_mind_laa_lds_bytes: the dynamic LDS of a launch; 0:
+ * invalid or unsupported shape.  There is no workspace.
+ *
+ * All four only enqueue (no allocation, no host synchronisation: graph-capturable) and use no float atomics:
+ * bit-identical results run to run.  Return codes, answered in this order: a size below 1 (B below 0): -1; a shape
+ * outside the limits: -2, from the sizes alone; ld < E, V < 1 or a NULL pointer other than oob_flag / one of gout and
+ * gloss: -1; a workspace that is too small: -3; then B == 0: 0, nothing is launched or written. */
+size_t rec_mind_routing_workspace_bytes(int64_t B, int T, int E, int C, int Dc, int K, int R);
+int rec_mind_routing_fwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* series, int64_t B,
+                             int T, const float* S, const float* B0, int Dc, int K, int R, int64_t padding_index,
+                             float* out, int* oob_flag, void* stream);
+int rec_mind_routing_bwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* series, int64_t B,
+                             int T, const float* S, const float* B0, int Dc, int K, int R, int64_t padding_index,
+                             const float* gout, float* gkeys, float* dS, void* workspace, size_t workspace_bytes,
+                             void* stream);
+size_t rec_mind_laa_lds_bytes(int Ns, int E, int C, int K);
+int rec_mind_laa_fwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* items, int64_t B,
+                         int Ns, const float* m, const int32_t* kv, int K, float* out, float* loss, int* oob_flag,
+                         void* stream);
+int rec_mind_laa_bwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* items, int64_t B,
+                         int Ns, const float* m, const int32_t* kv, int K, const float* gout, const float* gloss,
+                         float* gm, float* gitems, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
