@@ -883,6 +883,34 @@ class MMOEBody(torch.autograd.Function):
         return (dx, None, None) + tuple(grads)
 
 
+class PLELevel(torch.autograd.Function):
+    """One CGC level of PLE (4.MMOE/CustomLayers.py:315-358 and the towers :380-382; csrc/ple.hip): xin [B, Gin, Din]
+    (Gin = 1 for the first level, tasks + 1 afterwards) and the packed weights W1, b1, We2, be2, Wg2, bg2, Wg3s, Wg3h,
+    Wtw, btw (include/mi355rec.h; None for the shared gate of the last level and for the towers of the others) ->
+    y [B, Gout, O], and for the last level (y, out [B, T]).  One launch each way plus the slot sums, one launch for all
+    small weight gradients and, for the first level, one weight-gradient GEMM.  Saves only under grad."""
+
+    @staticmethod
+    def forward(ctx, xin, T, S, Sh, last, *weights):
+        xin = xin.contiguous()
+        weights = [None if t is None else t.contiguous() for t in weights]
+        train = any(ctx.needs_input_grad)
+        y, out, saved = ops.ple_cgc_fwd(xin, weights, T, S, Sh, last, save=train)
+        if train:
+            ctx.save_for_backward(xin, *weights, *saved, y, out)
+        ctx.cfg = (T, S, Sh, bool(last))
+        return (y, out) if last else y
+
+    @staticmethod
+    def backward(ctx, dy, dout=None):
+        xin, *rest = ctx.saved_tensors
+        weights, saved, y, out = rest[:10], rest[10:14], rest[14], rest[15]
+        last = ctx.cfg[3]
+        dxin, grads = ops.ple_cgc_bwd(xin, weights, saved, y, out, None if dy is None else dy.contiguous(),
+                                      dout.contiguous() if last else None, *ctx.cfg)
+        return (dxin, None, None, None, None) + tuple(grads)
+
+
 class CapsuleRouting(torch.autograd.Function):
     """MultiInterestExtractorLayer.call fused with the series lookup (6.MIND/CustomLayers.py:111-138, 204-212;
     csrc/mind.hip): table, series ids [B,T,C], S [C E, Dc], the non-trainable logits B0 [K,T] -> the capsules [B,K,Dc].

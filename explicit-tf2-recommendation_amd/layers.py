@@ -41,6 +41,7 @@ libmi355rec.so (through functional.py / ops.py).  Reference classes and the line
   BilinearInteractionPlusLayer  11.FiBiNet++/CustomLayers.py:208-242
   MMOELayer                     4.MMOE/CustomLayers.py:107-173
   ESMMLayer                     4.MMOE/CustomLayers.py:175-245
+  PLELayer                      4.MMOE/CustomLayers.py:248-384
   MultiInterestExtractorLayer   6.MIND/CustomLayers.py:62-138   (takes the table and the ids: the lookup is fused)
   LabelAwareAttention           6.MIND/CustomLayers.py:141-158  (with the inner products and the loss of :267-285)
   MINDLayer                     6.MIND/CustomLayers.py:161-285
@@ -1947,7 +1948,7 @@ class PNNRankingLayer(PNNLayer):
 
 
 # ---------------------------------------------------------------------------------------------------
-# 4.MMOE: MMOE, ESMM
+# 4.MMOE: MMOE, ESMM, PLE
 # ---------------------------------------------------------------------------------------------------
 
 _MMOE_CAT = ["sdk_type", "remote_host", "device_type", "dtu", "click_goods_num", "buy_click_num", "goods_show_num",
@@ -2023,6 +2024,82 @@ class ESMMLayer(MMOELayer):
     def __init__(self, categorical_features=_MMOE_CAT, continuous_features=_MMOE_CONT, feature_dims=160000,
                  embedding_dims=16, expert_num=3):
         super().__init__(categorical_features, continuous_features, feature_dims, embedding_dims, expert_num)
+
+
+class PLELayer(Layer):
+    """4.MMOE/CustomLayers.py:248-384: progressive layered extraction.  ``level_num`` CGC levels; a level has
+    ``specific_expert_num`` expert MLPs [64, 8] per task and ``shared_expert_num`` shared ones, one gate per task (MLP
+    [64, 8], then a bias-free dense layer whose softmax the reference applies TWICE) over the task's experts and the
+    shared ones, and, except the last level, a shared gate (softmax once) over all experts; a gate's output is the
+    weighted SUM of its experts.  The first level reads the flattened embedding rows for every branch, a later one the
+    previous level's outputs, one per task and one shared.  A sigmoid unit per task reads the last level ->
+    {'task_0': [B, 1], 'task_1': [B, 1], 'task_2': [B, 1]}.  ``continuous_features`` is accepted and unused, as in the
+    reference.  The sub-layers hold the parameters under the reference's names (the gates' dense layers are holders
+    of ``kernel_0``: their softmax runs inside the kernel); a call packs them level by level and runs each level as one
+    kernel each way (functional.PLELevel)."""
+
+    num_tasks = 3               # the reference fixes it (:271)
+
+    def __init__(self, categorical_features=_MMOE_CAT, continuous_features=_MMOE_CONT, feature_dims=160000,
+                 embedding_dims=8, specific_expert_num=3, shared_expert_num=3, level_num=2):
+        super().__init__()
+        self.categorical_features = list(categorical_features)
+        self.continuous_features = list(continuous_features)
+        self.embedding_dims = int(embedding_dims)
+        self.specific_expert_num = int(specific_expert_num)
+        self.shared_expert_num = int(shared_expert_num)
+        self.level_num = int(level_num)
+        if self.level_num < 1:
+            raise ValueError("level_num must be at least 1, got %d" % self.level_num)
+        T, S, Sh, L = self.num_tasks, self.specific_expert_num, self.shared_expert_num, self.level_num
+        D = len(self.categorical_features) * self.embedding_dims
+        H1, O, Og = 64, 8, 8
+        dins = [D] + [O] * (L - 1)
+        for level, din in enumerate(dins):
+            ops.ple_check_shape(din, 1 if level == 0 else T + 1, T, S, Sh, H1, O, Og, level == L - 1)
+        self.embedding_layer = Embedding(feature_dims, self.embedding_dims)
+        ML = torch.nn.ModuleList
+        mlp = lambda din: MLPLayer(units=[H1, O], activation="relu", input_dim=din)
+        gate = lambda din, width: ML([MLPLayer(units=[H1, Og], activation="relu", input_dim=din),
+                                      MLPLayer(units=[width], use_bias=False, activation=None, input_dim=Og)])
+        self.specific_expert_networks = ML([ML([mlp(din) for _ in range(T * S)]) for din in dins])
+        self.shared_expert_networks = ML([ML([mlp(din) for _ in range(Sh)]) for din in dins])
+        self.specific_gates = ML([ML([gate(din, S + Sh) for _ in range(T)]) for din in dins])
+        self.shared_gates = ML([gate(din, T * S + Sh) for din in dins[:-1]])       # the last level has no shared output
+        self.tower_outputs = ML([MLPLayer(units=[1], activation="sigmoid", input_dim=O) for _ in range(T)])
+
+    def packed_weights(self, level):
+        """Level ``level``'s parameters in the packed layout of include/mi355rec.h (W1, b1, We2, be2, Wg2, bg2, Wg3s,
+        Wg3h, Wtw, btw; None for the shared gate of the last level and the towers of the others); gradients flow back
+        through the concatenations."""
+        last = level == self.level_num - 1
+        experts = list(self.specific_expert_networks[level]) + list(self.shared_expert_networks[level])
+        gates = list(self.specific_gates[level]) + ([] if last else [self.shared_gates[level]])
+        first = experts + [gt[0] for gt in gates]
+        cat, stack = torch.cat, torch.stack
+        return (cat([m.kernel_0 for m in first], dim=1), cat([m.bias_0 for m in first]),
+                stack([m.kernel_1 for m in experts]), stack([m.bias_1 for m in experts]),
+                stack([gt[0].kernel_1 for gt in gates]), stack([gt[0].bias_1 for gt in gates]),
+                stack([gt[1].kernel_0 for gt in self.specific_gates[level]]),
+                None if last else self.shared_gates[level][1].kernel_0,
+                stack([t.kernel_0.reshape(-1) for t in self.tower_outputs]) if last else None,
+                cat([t.bias_0 for t in self.tower_outputs]) if last else None)
+
+    def task_outputs(self, inputs):
+        """[B, 3]: column i is 'task_i' (the dict entries are views of it)."""
+        X = assemble_index(inputs, self.categorical_features)
+        flag = ops.new_flag(X.device) if self.check_ids else None
+        x = self.embedding_layer(X, flag)
+        self._raise_if_oob(flag)
+        cfg = (self.num_tasks, self.specific_expert_num, self.shared_expert_num)
+        y = x.reshape(X.shape[0], 1, -1)
+        for level in range(self.level_num - 1):
+            y = Fn.PLELevel.apply(y, *cfg, False, *self.packed_weights(level))
+        return Fn.PLELevel.apply(y, *cfg, True, *self.packed_weights(self.level_num - 1))[1]
+
+    def forward(self, inputs):
+        out = self.task_outputs(inputs)
+        return {"task_%d" % i: out[:, i:i + 1] for i in range(self.num_tasks)}
 
 
 # ---------------------------------------------------------------------------------------------------

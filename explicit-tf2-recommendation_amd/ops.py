@@ -1609,6 +1609,122 @@ def mmoe_bwd(x, weights, saved, dout, gate_softmax_passes=1, ctcvr=False):
     return dx, grads
 
 
+# ---- PLE: one CGC level (experts, task gates, the shared gate, the gated sums, the towers of the last level) in one
+# launch each way (csrc/ple.hip).  The limits are MaskNet's.
+def ple_check_shape(Din, Gin, T, S, Sh, H1=64, O=8, Og=8, last=False):
+    """ValueError for sizes that describe no CGC level, NotImplementedError for shapes the kernels do not cover (the ABI
+    would return -2): input width Din of each of Gin in {1, T + 1} input groups, T tasks, S specific experts per task, Sh
+    shared experts, hidden width H1, expert output width O, gate MLP output width Og."""
+    if min(Din, Gin, T, S, Sh, H1, O, Og) < 1:
+        raise ValueError("every size of a PLE level must be positive, got Din=%d, Gin=%d, tasks=%d, specific=%d, "
+                         "shared=%d, H1=%d, O=%d, Og=%d" % (Din, Gin, T, S, Sh, H1, O, Og))
+    if Gin not in (1, T + 1):
+        raise ValueError("a PLE level reads one input group or tasks + 1 = %d of them, got %d" % (T + 1, Gin))
+    ne = T * S + Sh
+    GW = T * (S + Sh) + (0 if last else ne)
+    if (Din > MASKNET_MAX_D or T > MASKNET_MAX_R or max(H1, ne * O, (T + 1) * Og, GW) > MASKNET_MAX_O
+            or (Gin > 1 and Gin * Din > MASKNET_MAX_O)):
+        raise NotImplementedError(
+            "PLE kernels cover Din <= %d, tasks <= %d, each of H1, experts * O, (tasks + 1) * Og and the gate columns "
+            "tasks * (specific + shared) [+ experts] <= %d, and Gin * Din <= %d for a grouped level; got Din=%d, Gin=%d, "
+            "tasks=%d, H1=%d, experts * O=%d, (tasks + 1) * Og=%d, gate columns=%d"
+            % (MASKNET_MAX_D, MASKNET_MAX_R, MASKNET_MAX_O, MASKNET_MAX_O, Din, Gin, T, H1, ne * O, (T + 1) * Og, GW))
+
+
+def _ple_args(xin, w, T, S, Sh, last):
+    """-> (B, Din, Gin, H1, O, Og) of xin [B, Gin, Din] and the packed weights ``w`` = (W1, b1, We2, be2, Wg2, bg2, Wg3s,
+    Wg3h, Wtw, btw) (Wg3h None iff last; Wtw, btw None unless last), checked against each other and the limits."""
+    if len(w) != 10:
+        raise ValueError("a PLE level takes ten packed weights (None for the absent ones), got %d" % len(w))
+    W1, b1, We2, be2, Wg2, bg2, Wg3s, Wg3h, Wtw, btw = w
+    last = bool(last)
+    if last and (Wg3h is not None or Wtw is None or btw is None):
+        raise ValueError("the last level has towers (Wtw, btw) and no shared gate (Wg3h)")
+    if not last and (Wg3h is None or Wtw is not None or btw is not None):
+        raise ValueError("a level before the last has a shared gate (Wg3h) and no towers (Wtw, btw)")
+    for t, name, dim in ((xin, "xin", 3), (W1, "W1", 2), (We2, "We2", 3), (Wg2, "Wg2", 3), (Wg3s, "Wg3s", 3)):
+        if _f32(t, name).dim() != dim:
+            raise ValueError("%s must be %d-D, got %s" % (name, dim, tuple(t.shape)))
+    T, S, Sh = int(T), int(S), int(Sh)
+    B, Gin, Din = xin.shape
+    _, H1, O = We2.shape
+    Og = Wg2.shape[2]
+    ple_check_shape(Din, Gin, T, S, Sh, H1, O, Og, last)
+    ne, ns, Gout = T * S + Sh, S + Sh, T if last else T + 1
+    want = [(Din, (ne + Gout) * H1), (ne, H1, O), (Gout, H1, Og), (T, Og, ns)]
+    got = [tuple(t.shape) for t in (W1, We2, Wg2, Wg3s)]
+    if last:
+        want.append((T, O))
+        got.append(tuple(_f32(Wtw, "Wtw").shape))
+    else:
+        want.append((Og, ne))
+        got.append(tuple(_f32(Wg3h, "Wg3h").shape))
+    if want != got:
+        raise ValueError("a PLE level takes W1 [Din,(ne+Gout) H1], We2 [ne,H1,O], Wg2 [Gout,H1,Og], Wg3s [T,Og,S+Sh] and "
+                         "Wg3h [Og,ne] or Wtw [T,O]: expected %s, got %s" % (want, got))
+    for t, cnt, name in ((b1, (ne + Gout) * H1, "b1"), (be2, ne * O, "be2"), (bg2, Gout * Og, "bg2")) + \
+            (((btw, T, "btw"),) if last else ()):
+        _vec(t, cnt, name)
+    return B, Din, Gin, H1, O, Og
+
+
+def ple_cgc_fwd(xin, weights, T, S, Sh, last=False, save=True):
+    """One CGC level in one launch: xin [B, Gin, Din] (Gin = 1: one input for every MLP; Gin = T + 1: each task and the
+    shared branch reads its own) -> (y [B, Gout, O], out [B, T] or None, saved) with Gout = T (``last``) or T + 1, out
+    the tower probabilities of the last level, and saved = (h [B, N1], e [B, ne O], q [B, Gout Og], g [B, GW]) for the
+    backward, or None (``save=False``: inference, the same y and out).  ``weights``: W1, b1, We2, be2, Wg2, bg2, Wg3s,
+    Wg3h, Wtw, btw as include/mi355rec.h packs them, None for Wg3h of the last level and for Wtw, btw of the others."""
+    B, Din, Gin, H1, O, Og = _ple_args(xin, weights, T, S, Sh, last)
+    last = int(bool(last))
+    ne, Gout = T * S + Sh, T if last else T + 1
+    GW = T * (S + Sh) + (0 if last else ne)
+    dev = xin.device
+    new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+    y = new(B, Gout, O)
+    out = new(B, T) if last else None
+    saved = (new(B, (ne + Gout) * H1), new(B, ne * O), new(B, Gout * Og), new(B, GW)) if save else None
+    check(lib.rec_ple_cgc_fwd_f32(_ptr(xin), *[_ptr(t) for t in weights], B, Din, Gin, T, S, Sh, H1, O, Og, last,
+                                  _ptr(y), _ptr(out), *[_ptr(t) for t in (saved or (None,) * 4)], _stream()),
+          "rec_ple_cgc_fwd_f32")
+    return y, out, saved
+
+
+def ple_cgc_bwd(xin, weights, saved, y, out, dy, dout, T, S, Sh, last=False):
+    """-> (dxin [B, Gin, Din], grads) with grads the gradient of every packed weight in the order of ``weights`` (None
+    where the weight is None).  ``dy`` [B, Gout, O] may be None for the last level; ``dout`` [B, T] and ``out`` belong to
+    the last level alone."""
+    B, Din, Gin, H1, O, Og = _ple_args(xin, weights, T, S, Sh, last)
+    last = int(bool(last))
+    ne, Gout = T * S + Sh, T if last else T + 1
+    GW = T * (S + Sh) + (0 if last else ne)
+    if saved is None or len(saved) != 4:
+        raise ValueError("the backward of a PLE level needs the four save buffers h, e, q, g")
+    named = list(zip(tuple(saved) + (y,), ((B, (ne + Gout) * H1), (B, ne * O), (B, Gout * Og), (B, GW), (B, Gout, O)),
+                     ("h", "e", "q", "g", "y")))
+    if last:
+        named += [(out, (B, T), "out"), (dout, (B, T), "dout")]
+    elif out is not None or dout is not None:
+        raise ValueError("out and dout belong to the last level")
+    if dy is not None or not last:
+        named.append((dy, (B, Gout, O), "dy"))
+    for t, shp, name in named:
+        if t is None or tuple(_f32(t, name).shape) != shp:
+            raise ValueError("%s must be %s, got %s" % (name, shp, None if t is None else tuple(t.shape)))
+    dev = xin.device
+    mk = torch.zeros if B == 0 else torch.empty                      # written in full when B > 0
+    dxin = mk((B, Gin, Din), dtype=torch.float32, device=dev)
+    grads = [None if t is None else mk(tuple(t.shape), dtype=torch.float32, device=dev) for t in weights]
+    if B > 0:
+        nbytes = lib.rec_ple_cgc_workspace_bytes(B, Din, Gin, T, S, Sh, H1, O, Og, last)
+        ws = _workspace(nbytes, "rec_ple_cgc_workspace_bytes", dev, torch.float32)
+        W1, _, We2, _, Wg2, _, Wg3s, Wg3h, Wtw, _ = weights
+        check(lib.rec_ple_cgc_bwd_f32(_ptr(xin), *[_ptr(t) for t in (W1, We2, Wg2, Wg3s, Wg3h, Wtw)],
+                                      *[_ptr(t) for t in saved], _ptr(y), _ptr(out), _ptr(dy), _ptr(dout), B, Din, Gin,
+                                      T, S, Sh, H1, O, Og, last, _ptr(dxin), *[_ptr(g) for g in grads], _ptr(ws), nbytes,
+                                      _stream()), "rec_ple_cgc_bwd_f32")
+    return dxin, grads
+
+
 # ---- MIND: capsule routing and label-aware attention + sampled-softmax loss, one launch each way (csrc/mind.hip).  The
 # limits are DIN's key width and AFM's attention size, the rounds and the LDS fit are the header's formulas.
 MIND_MAX_ROUNDS = 8

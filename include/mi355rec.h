@@ -930,6 +930,62 @@ int rec_mmoe_bwd_f32(const float* x, const float* W1, const float* We2, const fl
                      float* dWt2, float* dbt2, float* dWt3, float* dbt3, void* workspace, size_t workspace_bytes,
                      void* stream);
 
+/* ---- PLE (PLELayer, 4.MMOE/CustomLayers.py:248-384; csrc/ple.hip): one CGC level (customized gate control, one stage
+ * of progressive layered extraction) per call each way.
+ * T tasks, S specific experts per task, Sh shared experts, ne = T S + Sh experts, ns = S + Sh; hidden width H1 of every
+ * MLP, expert output width O, gate MLP output width Og; last != 0: the last level (T outputs and the towers, no shared
+ * gate), else a level with a shared output.  Gout = last ? T : T + 1 gates, M = ne + Gout first layers, N1 = M H1,
+ * GW = T ns + (last ? 0 : ne) gate columns.
+ * xin [B, Gin, Din] with Gin = 1 (level 0: every MLP reads the same row) or Gin = T + 1 (every MLP reads the row of its
+ * group: task t is group t, the shared branch group T; Din is the previous level's O).  group(m): expert m < T S reads
+ * group m / S, a shared expert and the shared gate read group T, task gate t reads group t.
+ * Packed weights, all row-major:
+ *   W1 [Din, N1], b1 [N1]   the first layers side by side: column block m < ne is expert m's, block ne + g gate g's
+ *   We2 [ne, H1, O], be2 [ne, O]        Wg2 [Gout, H1, Og], bg2 [Gout, Og]
+ *   Wg3s [T, Og, ns] (no bias)          Wg3h [Og, ne] (no bias; NULL iff last)
+ *   Wtw [T, O], btw [T]                 the sigmoid towers (NULL unless last)
+ * Per example (relu'(0) = 0):
+ *   h_m = relu(in_group(m) W1_m + b1_m)   e_i = relu(h_i We2[i] + be2[i])   q_g = relu(h_{ne+g} Wg2[g] + bg2[g])
+ *   g_t = softmax(softmax(q_t Wg3s[t]))  (twice, as the reference applies it)
+ *   y_t = sum_{j<S} g_t[j] e_{t S+j} + sum_{k<Sh} g_t[S+k] e_{T S+k}         (a sum over the experts, not a flatten)
+ *   not last:  g_T = softmax(q_T Wg3h) (once),  y_T = sum_i g_T[i] e_i over all experts in order
+ *   last:      out[:, t] = sigmoid(y_t . Wtw[t] + btw[t])
+ * y [B, Gout, O] is always written; out [B, T] iff last (NULL otherwise).
+ * One launch: a workgroup owns 32 examples; the first layers run on v_mfma_f32_32x32x2_f32 (fp32-exact) in chunks of
+ * whole MLPs whose second layers are finished before the next chunk, everything narrower out of LDS.  The save buffers
+ * h [B, N1], e [B, ne O], q [B, Gout Og] and g [B, GW] (the gates after their last softmax, task gates first) are all
+ * given (training) or all NULL (inference: the same y and out).
+ * The backward takes the save buffers, y and out as the forward wrote them, dy [B, Gout, O] (may be NULL when last: read
+ * as zero) and dout [B, T] (iff last), and writes dxin [B, Gin, Din] (written, never added to) and the gradient of every
+ * packed weight (dWg3h iff not last, dWtw and dbtw iff last; NULL otherwise).  Gate logits are not saved: the first
+ * softmax of a task gate is recomputed from q with the forward's code.  One launch for the per-example chain and dxin,
+ * one slot sum for the bias gradients, ONE launch for dWe2, dWg2, dWg3s, dWg3h, dWtw (and dW1 when Gin > 1) over at most
+ * 16 batch slices added in order by a second slot sum; with Gin = 1, dW1 = xin^T dZ1 on rec_gemm_f32 (split-K, slices
+ * added in order).
+ * All only enqueue (no allocation, no host synchronisation: graph-capturable) and use no float atomics: bit-identical
+ * results run to run.  B == 0: nothing is launched.
+ * Supported: the limits are MaskNet's, this family has no constants of its own: 1 <= Din <= REC_MASKNET_MAX_D,
+ * H1 <= REC_MASKNET_MAX_O, ne O <= REC_MASKNET_MAX_O, (T + 1) Og <= REC_MASKNET_MAX_O, 1 <= T <= REC_MASKNET_MAX_R,
+ * S >= 1, Sh >= 1, 0 <= B < 2^31, and two that keep every shape inside the 156 KB of LDS of a workgroup: the gate
+ * columns GW <= REC_MASKNET_MAX_O (the gates, their first softmax and their gradients live in LDS next to e and q), and
+ * Gin Din <= REC_MASKNET_MAX_O when Gin > 1 (the width of a previous level's y); otherwise -2.  A size below 1 (B below
+ * 0), Gin other than 1 / T + 1, last other than 0 / 1, a NULL pointer that must be given or a pointer that must be
+ * NULL, or save buffers given in part: -1.  A workspace that is too small: -3.
+ * workspace (backward only): rec_ple_cgc_workspace_bytes: 4 B (N1 + ne O + Gout Og + GW + T) bytes of per-example
+ * gradients, (B / 32) slots of bias gradients, at most 16 copies of the small weights and, with Gin = 1, at most 16 of
+ * W1 (0: invalid or unsupported shape). */
+size_t rec_ple_cgc_workspace_bytes(int64_t B, int Din, int Gin, int T, int S, int Sh, int H1, int O, int Og, int last);
+int rec_ple_cgc_fwd_f32(const float* xin, const float* W1, const float* b1, const float* We2, const float* be2,
+                        const float* Wg2, const float* bg2, const float* Wg3s, const float* Wg3h, const float* Wtw,
+                        const float* btw, int64_t B, int Din, int Gin, int T, int S, int Sh, int H1, int O, int Og,
+                        int last, float* y, float* out, float* h, float* e, float* q, float* g, void* stream);
+int rec_ple_cgc_bwd_f32(const float* xin, const float* W1, const float* We2, const float* Wg2, const float* Wg3s,
+                        const float* Wg3h, const float* Wtw, const float* h, const float* e, const float* q,
+                        const float* g, const float* y, const float* out, const float* dy, const float* dout, int64_t B,
+                        int Din, int Gin, int T, int S, int Sh, int H1, int O, int Og, int last, float* dxin, float* dW1,
+                        float* db1, float* dWe2, float* dbe2, float* dWg2, float* dbg2, float* dWg3s, float* dWg3h,
+                        float* dWtw, float* dbtw, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- MIND (MultiInterestExtractorLayer, LabelAwareAttention, MINDLayer.call, 6.MIND/CustomLayers.py:62-158, 263-285;
  * csrc/mind.hip): capsule routing over a behaviour series, and label-aware attention with the sampled-softmax loss.
  * Both families gather from embed [V, E] with row stride ld >= E; an id outside [0, V) reads as a zero row and sets
