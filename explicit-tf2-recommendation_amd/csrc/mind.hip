@@ -36,21 +36,11 @@
 //   gm_k = sum_s dsc[k,s] x_s   gitems_s = sum_k dsc[k,s] m_k
 // Neither family uses a float atomic or scratch; every launch only enqueues.  An id outside [0, V) reads as a zero row and
 // sets the flag.
-#include <float.h>
-#include <math.h>
-#include "common.h"
-#include "mfma_tile.h"
+#include "capsule.h"
 
 namespace {
 
-// the limits are DIN's and AFM's: the header gains no constant for this family
-constexpr int MI_MAXD = REC_DIN_MAX_D, MI_MAXK = REC_AFM_MAX_A, MI_MAXR = 8;
-constexpr int MI_NTHR = 256;
-constexpr size_t MI_LDS_CAP = 150 * 1024;
 constexpr int MI_GRID = 1024;                   // workgroups (= dS partials) of the routing backward, at the most
-static_assert(MI_LDS_CAP <= REC_LDS_CU_BYTES, "the launch cap fits the LDS of a CU");
-
-__host__ __device__ inline int mi_odd(int n) { return n | 1; }
 
 // floats of LDS of the routing backward, which is what both directions are held to:
 //   xs [T][D | 1], u and du [T][Dc | 1], W of every round [R][K][T], dL and dW [K][T], ds and c [K][Dc | 1], valid [T]
@@ -60,68 +50,6 @@ __host__ __device__ inline size_t rt_lds_floats(int T, int D, int Dc, int K, int
 // and of the forward: xs, u, W [K][T], L [K][T], c [K][Dc | 1], valid [T]
 __host__ __device__ inline size_t rt_fwd_lds_floats(int T, int D, int Dc, int K) {
   return (size_t)T * mi_odd(D) + (size_t)T * mi_odd(Dc) + 2 * (size_t)K * T + (size_t)K * mi_odd(Dc) + T;
-}
-// floats of LDS of one example of the attention: m [K][Dc | 1], x [Ns][Dc | 1], sc and w [K][Ns], out and g [Ns]
-__host__ __device__ inline size_t la_lds_floats(int Ns, int Dc, int K) {
-  return ((size_t)K + Ns) * mi_odd(Dc) + 2 * (size_t)K * Ns + 2 * (size_t)Ns;
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-// what one lane of a wave wrote to LDS is read by another lane of the SAME wave after it
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// sum_i a[i] b[i sb] over i < n, in that order; the operands of 8 terms are requested together so that the LDS latency is
-// paid once per 8, not once per term (a is read at the same address by every lane: a broadcast)
-__device__ __forceinline__ float mi_dot(const float* a, const float* b, int sb, int n) {
-  float acc = 0.f;
-  int i = 0;
-  for (; i + 8 <= n; i += 8) {
-    float x[8], y[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      x[j] = a[i + j];
-      y[j] = b[(i + j) * sb];
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc = fmaf(x[j], y[j], acc);
-  }
-  for (; i < n; ++i) acc = fmaf(a[i], b[i * sb], acc);
-  return acc;
-}
-// two sums over the same b: r1 = sum a1[i] b[i sb], r2 = sum a2[i] b[i sb]
-__device__ __forceinline__ void mi_dot2(const float* a1, const float* a2, const float* b, int sb, int n, float& r1,
-                                        float& r2) {
-  float s1 = 0.f, s2 = 0.f;
-  int i = 0;
-  for (; i + 8 <= n; i += 8) {
-    float x[8], z[8], y[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      x[j] = a1[i + j];
-      z[j] = a2[i + j];
-      y[j] = b[(i + j) * sb];
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      s1 = fmaf(x[j], y[j], s1);
-      s2 = fmaf(z[j], y[j], s2);
-    }
-  }
-  for (; i < n; ++i) {
-    const float y = b[i * sb];
-    s1 = fmaf(a1[i], y, s1);
-    s2 = fmaf(a2[i], y, s2);
-  }
-  r1 = s1;
-  r2 = s2;
 }
 
 struct RtArgs {
@@ -133,66 +61,6 @@ struct RtArgs {
   int64_t padding_index;
   int T, C, E, D, Dc, K, R;
 };
-
-// one 32 x 32 block of acc += A Bm over k < Kd: fa(k) is A[row lo][k], fb(k) is Bm[k][column lo], both already masked.
-// The operands of U k-steps are requested together (an operand may come from global memory: one latency per U steps).
-template <class FA, class FB>
-__device__ __forceinline__ void mi_mma(f32x16& acc, int Kd, int hi, FA fa, FB fb) {
-  constexpr int U = 8;
-  for (int k = 0; k < Kd; k += 2 * U) {
-    float av[U], bv[U];
-#pragma unroll
-    for (int s = 0; s < U; ++s) {
-      const int kk = k + 2 * s + hi;
-      const bool kok = kk < Kd;
-      const int kc = kok ? kk : Kd - 1;
-      const float x = fa(kc), y = fb(kc);
-      av[s] = kok ? x : 0.f;
-      bv[s] = kok ? y : 0.f;
-    }
-#pragma unroll
-    for (int s = 0; s < U; ++s)
-      if (k + 2 * s < Kd) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s], bv[s], acc, 0, 0, 0);   // uniform
-  }
-}
-
-// rows x (C E) looked-up values of ids [rows][C] into xs [rows][stride], by NT threads (this one is tid): the ids of U
-// elements are requested together, then their values, with no branch between them (an id outside [0, V) reads row 0 and
-// keeps a zero); valid != NULL: valid[row] = ids[row][0] != pad, taken from the id the element (row, 0) has read anyway
-template <int NT>
-__device__ __forceinline__ void mi_gather(const float* __restrict__ embed, int64_t ld, int64_t V,
-                                          const int64_t* __restrict__ ids, int rows, int C, int E, float* xs, int stride,
-                                          int tid, bool& bad, int64_t pad = 0, int* valid = nullptr) {
-  constexpr int U = 4;
-  const int D = C * E, n = rows * D;
-  for (int i0 = tid; i0 < n; i0 += NT * U) {
-    int64_t id[U];
-    int at[U], e[U], row[U];
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-      const int i = i0 + j * NT, ic = i < n ? i : n - 1;
-      const int t = ic / D, d = ic - t * D, r = d / E;
-      e[j] = d - r * E;
-      at[j] = t * stride + d;
-      row[j] = d == 0 ? t : -1;
-      id[j] = ids[(int64_t)t * C + r];
-    }
-    float v[U];
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-      const bool ok = id[j] >= 0 && id[j] < V;
-      const float x = embed[(ok ? id[j] : 0) * ld + e[j]];
-      v[j] = ok ? x : 0.f;
-      bad |= !ok;
-    }
-#pragma unroll
-    for (int j = 0; j < U; ++j)
-      if (i0 + j * NT < n) {
-        xs[at[j]] = v[j];
-        if (valid && row[j] >= 0) valid[row[j]] = id[j] != pad;
-      }
-  }
-}
 
 // The rows of example b into xs, valid, L <- B0, u = x S, and the R rounds.  KEEP: W of round r goes to Wall[r] (the
 // backward), otherwise every round uses Wall[0].  out (may be NULL): c of the last round.  Ends with every wave done
@@ -210,23 +78,7 @@ __device__ __forceinline__ void rt_forward(const RtArgs& a, int64_t b, float* xs
   for (int i = tid + MI_NTHR; i < K * T; i += MI_NTHR) L[i] = a.B0[i];
   __syncthreads();
 
-  const int ncb = (Dc + 31) / 32, ntile = (T + 31) / 32;
-  for (int task = wave; task < ntile * ncb; task += 4) {        // u = x S
-    const int tile = task / ncb, cb = task - tile * ncb;
-    const int t = tile * 32 + lo, n = cb * 32 + lo;
-    const bool tok = t < T, nok = n < Dc;
-    const float* xr = xs + (tok ? t : T - 1) * Dp;
-    const float* __restrict__ Sc = a.S + (nok ? n : Dc - 1);
-    f32x16 acc;
-    mb_zero(acc);
-    mi_mma(acc, D, hi, [&](int k) { return tok ? xr[k] : 0.f; },
-           [&](int k) { const float v = Sc[(int64_t)k * Dc]; return nok ? v : 0.f; });
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = tile * 32 + mb_row(r, hi);
-      if (row < T && nok) u[row * Dcp + n] = acc[r];
-    }
-  }
+  caps_project<false>(xs, Dp, a.S, T, D, Dc, u, Dcp, wave, lo, hi);        // u = x S
   __syncthreads();
 
   for (int k = wave; k < K; k += 4) {                            // a row needs no other row
@@ -234,38 +86,9 @@ __device__ __forceinline__ void rt_forward(const RtArgs& a, int64_t b, float* xs
     float* ck = c + k * Dcp;
     for (int r = 0; r < R; ++r) {
       float* Wk = (KEEP ? Wall + (size_t)r * K * T : Wall) + k * T;
-      float m = -FLT_MAX;
-      for (int t = lane; t < T; t += 64) m = fmaxf(m, valid[t] ? Lk[t] : -FLT_MAX);
-      m = wave_max(m);
-      float sum = 0.f;
-      for (int t = lane; t < T; t += 64) {
-        const float ex = expf((valid[t] ? Lk[t] : -FLT_MAX) - m);
-        Wk[t] = ex;
-        sum += ex;
-      }
-      sum = group_sum<64>(sum);
-      for (int t = lane; t < T; t += 64) Wk[t] = Wk[t] / sum;
-      wave_sync();
-      float n2 = 0.f;
-      for (int d = lane; d < Dc; d += 64) {                      // s = W u
-        const float acc = mi_dot(Wk, u + d, Dcp, T);
-        ck[d] = acc;
-        n2 = fmaf(acc, acc, n2);
-      }
-      n2 = group_sum<64>(n2);
-      const float f = sqrtf(n2) / (1.f + n2);
-      for (int d = lane; d < Dc; d += 64) {
-        const float cv = ck[d] * f;
-        ck[d] = cv;
-        if (out && r == R - 1) out[((int64_t)b * K + k) * Dc + d] = cv;
-      }
-      wave_sync();
-      if (r < R - 1) {
-        for (int t = lane; t < T; t += 64) {                     // L += c u^T
-          Lk[t] = Lk[t] + mi_dot(ck, u + t * Dcp, 1, Dc);
-        }
-        wave_sync();
-      }
+      caps_softmax_row(Lk, valid, Wk, T, lane);
+      caps_squash_row(Wk, u, Dcp, T, Dc, ck, (out && r == R - 1) ? out + ((int64_t)b * K + k) * Dc : nullptr, lane);
+      if (r < R - 1) caps_logit_update(Lk, ck, u, Dcp, T, Dc, lane);     // L += c u^T
     }
   }
 }
@@ -306,7 +129,6 @@ __global__ __launch_bounds__(MI_NTHR, NB == 1 ? 4 : 1) void mind_routing_bwd_ker
   float* ds = dW + K * T;                                        // [K][Dcp]
   float* c = ds + K * Dcp;                                       // [K][Dcp]: s, then c
   int* valid = reinterpret_cast<int*>(c + K * Dcp);
-  const int ncb = (Dc + 31) / 32, ndb = (D + 31) / 32, ntile = (T + 31) / 32;
   f32x16 sacc[NB];
 #pragma unroll
   for (int j = 0; j < NB; ++j) mb_zero(sacc[j]);
@@ -377,51 +199,12 @@ __global__ __launch_bounds__(MI_NTHR, NB == 1 ? 4 : 1) void mind_routing_bwd_ker
       __syncthreads();
     }
 
-    for (int task = wave; task < ntile * ndb; task += 4) {       // gkeys[b] = du S^T
-      const int tile = task / ndb, db = task - tile * ndb;
-      const int t = tile * 32 + lo, n = db * 32 + lo;
-      const bool tok = t < T, nok = n < D;
-      const float* dr = du + (tok ? t : T - 1) * Dcp;
-      const float* __restrict__ Sr = a.S + (int64_t)(nok ? n : D - 1) * Dc;
-      f32x16 acc;
-      mb_zero(acc);
-      mi_mma(acc, Dc, hi, [&](int k) { return tok ? dr[k] : 0.f; },
-             [&](int k) { const float v = Sr[k]; return nok ? v : 0.f; });
-#pragma unroll
-      for (int rr = 0; rr < 16; ++rr) {
-        const int row = tile * 32 + mb_row(rr, hi);
-        if (row < T && nok) gkeys[((int64_t)b * T + row) * D + n] = acc[rr];
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {                               // dS += x^T du
-      const int blk = wave + 4 * j;
-      if (blk < ndb * ncb) {
-        const int db = blk / ncb, cb = blk - db * ncb;
-        const int m = db * 32 + lo, n = cb * 32 + lo;
-        const bool mok = m < D, nok = n < Dc;
-        const float* xc = xs + (mok ? m : D - 1);
-        const float* dcn = du + (nok ? n : Dc - 1);
-        mi_mma(sacc[j], T, hi, [&](int k) { const float v = xc[k * Dp]; return mok ? v : 0.f; },
-               [&](int k) { const float v = dcn[k * Dcp]; return nok ? v : 0.f; });
-      }
-    }
+    caps_keys_grad(du, Dcp, a.S, T, D, Dc, gkeys + b * T * D, wave, lo, hi);       // gkeys[b] = du S^T
+    caps_weight_grad<NB>(sacc, xs, Dp, du, Dcp, T, D, Dc, wave, lo, hi);           // dS += x^T du
     __syncthreads();                                             // the next example overwrites all of it
   }
 
-  float* __restrict__ slot = slots + (int64_t)blockIdx.x * D * Dc;
-#pragma unroll
-  for (int j = 0; j < NB; ++j) {
-    const int blk = wave + 4 * j;
-    if (blk < ndb * ncb) {
-      const int db = blk / ncb, cb = blk - db * ncb, n = cb * 32 + lo;
-#pragma unroll
-      for (int rr = 0; rr < 16; ++rr) {
-        const int m = db * 32 + mb_row(rr, hi);
-        if (m < D && n < Dc) slot[m * Dc + n] = sacc[j][rr];
-      }
-    }
-  }
+  caps_weight_store<NB>(sacc, slots + (int64_t)blockIdx.x * D * Dc, D, Dc, wave, lo, hi);
 }
 
 struct LaArgs {
@@ -538,26 +321,7 @@ static int rt_shape(int64_t B, int T, int E, int C, int Dc, int K, int R) {
   if (sizeof(float) * rt_lds_floats(T, E * C, Dc, K, R) > MI_LDS_CAP) return REC_E_UNSUPPORTED;
   return REC_OK;
 }
-// as many workgroups as the chip holds at once: 4, 2 or 1 per CU by the registers of the instantiation (1, 4 or 16 blocks
-// of dS per wave), 256 CUs
-static int rt_grid(int64_t B, int D, int Dc) {
-  const int nblk = ((D + 31) / 32) * ((Dc + 31) / 32);
-  const int cap = nblk <= 4 ? MI_GRID : (nblk <= 16 ? MI_GRID / 2 : MI_GRID / 4);
-  return B < cap ? (int)B : cap;
-}
-
-// waves (= examples) of a workgroup of the attention: 4, 2 or 1, as many as fit; 0: not even one
-static int la_waves(int Ns, int Dc, int K) {
-  const size_t one = sizeof(float) * la_lds_floats(Ns, Dc, K);
-  return 4 * one <= MI_LDS_CAP ? 4 : (2 * one <= MI_LDS_CAP ? 2 : (one <= MI_LDS_CAP ? 1 : 0));
-}
-static int la_shape(int64_t B, int Ns, int E, int C, int K) {
-  if (B < 0 || Ns < 1 || E < 1 || C < 1 || K < 1) return REC_E_ARG;
-  if ((int64_t)E * C > MI_MAXD || K > MI_MAXK || B >= ((int64_t)1 << 31) || Ns > (int)(MI_LDS_CAP / sizeof(float)))
-    return REC_E_UNSUPPORTED;
-  if (la_waves(Ns, E * C, K) == 0) return REC_E_UNSUPPORTED;
-  return REC_OK;
-}
+static int rt_grid(int64_t B, int D, int Dc) { return caps_grid(B, D, Dc, MI_GRID); }
 
 template <int NB>
 static int rt_launch_bwd(const RtArgs& a, int grid, size_t lds, const float* gout, float* gkeys, float* slots,
@@ -603,9 +367,9 @@ extern "C" int rec_mind_routing_bwd_f32(const float* embed, int64_t ld, int64_t 
   const RtArgs a{embed, ld, V, series, B, S, B0, padding_index, T, C, E, D, Dc, K, R};
   const size_t lds = sizeof(float) * rt_lds_floats(T, D, Dc, K, R);
   float* slots = static_cast<float*>(workspace);
-  const int nblk = ((D + 31) / 32) * ((Dc + 31) / 32), nb = (nblk + 3) / 4;
-  const int rc = nb <= 1   ? rt_launch_bwd<1>(a, grid, lds, gout, gkeys, slots, st)
-                 : nb <= 4 ? rt_launch_bwd<4>(a, grid, lds, gout, gkeys, slots, st)
+  const int nb = caps_weight_nb(D, Dc);
+  const int rc = nb == 1   ? rt_launch_bwd<1>(a, grid, lds, gout, gkeys, slots, st)
+                 : nb == 4 ? rt_launch_bwd<4>(a, grid, lds, gout, gkeys, slots, st)
                            : rt_launch_bwd<16>(a, grid, lds, gout, gkeys, slots, st);
   if (rc) return rc;
   return rec_slot_sum(REC_SLOTS_WAVE, D * Dc, grid, slots, {{dS}, {D * Dc}}, st);

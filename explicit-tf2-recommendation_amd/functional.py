@@ -962,3 +962,82 @@ class LabelAwareAttention(torch.autograd.Function):
             plan = ops.DedupPlan(items, V)
             gembed = _sparse_grad(plan, gitems.reshape(-1, E), E, (V, E))
         return gembed, None, gm, None, None
+
+
+def _series_grad(ctx, series, gkeys, V, E):
+    """the table's gradient of a fused series / item lookup: sparse COO, rows de-duplicated"""
+    if not ctx.needs_input_grad[0]:
+        return None
+    return _sparse_grad(ops.DedupPlan(series, V), gkeys.reshape(-1, E), E, (V, E))
+
+
+class ComiRecRouting(torch.autograd.Function):
+    """ComiRecDynamicRoutingLayer.call fused with the series lookup (6.MIND/CustomLayers.py:562-594, 714-724;
+    csrc/comirec.hip): table, series ids [B,T,C], W [K,T,C E,Dc], the non-trainable logits B0 [K,T] -> the capsules
+    [B,K,Dc].  The forward saves nothing but its inputs; the backward projects and routes again and differentiates
+    through every round.  The table's gradient is a sparse COO tensor of de-duplicated rows; B0 gets none."""
+
+    @staticmethod
+    def forward(ctx, embed, series, W, B0, routing_rounds, padding_index, keep_padding, oob):
+        W, B0 = W.contiguous(), B0.contiguous()
+        out = ops.comirec_dr_fwd(embed, series, W, B0, routing_rounds, padding_index, keep_padding, oob)
+        ctx.save_for_backward(embed, series, W, B0)
+        ctx.cfg = (routing_rounds, padding_index, keep_padding)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        embed, series, W, B0 = ctx.saved_tensors
+        V, E = embed.shape
+        gkeys, dW = ops.comirec_dr_bwd(embed, series, W, B0, gout.contiguous(), *ctx.cfg)
+        return _series_grad(ctx, series, gkeys, V, E), None, dW, None, None, None, None, None
+
+
+class ComiRecSelfAttention(torch.autograd.Function):
+    """ComiRecSelfAttentiveLayer.call fused with the series lookup (6.MIND/CustomLayers.py:644-665; csrc/comirec.hip):
+    table, series ids [B,T,C], W1 [C E,Dc], W2 [K,Dc], the constant positional table pos [T,C E] or None -> [B,K,Dc].
+    One launch forward; the backward recomputes it."""
+
+    @staticmethod
+    def forward(ctx, embed, series, W1, W2, pos, padding_index, keep_padding, oob):
+        W1, W2 = W1.contiguous(), W2.contiguous()
+        out = ops.comirec_sa_fwd(embed, series, W1, W2, pos, padding_index, keep_padding, oob)
+        ctx.save_for_backward(embed, series, W1, W2)
+        ctx.pos, ctx.cfg = pos, (padding_index, keep_padding)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        embed, series, W1, W2 = ctx.saved_tensors
+        V, E = embed.shape
+        gkeys, dW1, dW2 = ops.comirec_sa_bwd(embed, series, W1, W2, gout.contiguous(), ctx.pos, *ctx.cfg)
+        return _series_grad(ctx, series, gkeys, V, E), None, dW1, dW2, None, None, None, None
+
+
+class ComiRecSelect(torch.autograd.Function):
+    """The hard attention of ComiRecLayer.manually_negative_sampled_call fused with the item lookup and the loss
+    (6.MIND/CustomLayers.py:768-810; csrc/comirec.hip): table, item ids [B,Ns,C], capsules m [B,K,C E] -> (selected
+    [B,Ns,C E], the capsule with the largest inner product per item, smallest index on a tie; inner [B,Ns]; loss [B];
+    chosen int32 [B,Ns], not differentiable).  The backward uses the forward's ``chosen``; an output nobody used arrives
+    as None, not as zeros."""
+
+    @staticmethod
+    def forward(ctx, embed, items, m, oob):
+        m = m.contiguous()
+        chosen, inner, loss = ops.comirec_select_fwd(embed, items, m, oob)
+        selected = torch.gather(m, 1, chosen.long()[:, :, None].expand(-1, -1, m.shape[2]))
+        ctx.save_for_backward(embed, items, m, chosen)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(chosen)
+        return selected, inner, loss, chosen
+
+    @staticmethod
+    def backward(ctx, gsel, ginner, gloss, _gchosen):
+        embed, items, m, chosen = ctx.saved_tensors
+        V, E = embed.shape
+        c = lambda g: None if g is None else g.contiguous()
+        gm, gitems = ops.comirec_select_bwd(embed, items, m, chosen, c(ginner), c(gloss), c(gsel))
+        gembed = None
+        if gsel is not None or ginner is not None or gloss is not None:
+            gembed = _series_grad(ctx, items, gitems, V, E)
+        return gembed, None, gm, None

@@ -45,6 +45,9 @@ libmi355rec.so (through functional.py / ops.py).  Reference classes and the line
   MultiInterestExtractorLayer   6.MIND/CustomLayers.py:62-138   (takes the table and the ids: the lookup is fused)
   LabelAwareAttention           6.MIND/CustomLayers.py:141-158  (with the inner products and the loss of :267-285)
   MINDLayer                     6.MIND/CustomLayers.py:161-285
+  ComiRecDynamicRoutingLayer    6.MIND/CustomLayers.py:528-594  (takes the table and the ids, as the MIND extractor)
+  ComiRecSelfAttentiveLayer     6.MIND/CustomLayers.py:597-665  (the same)
+  ComiRecLayer                  6.MIND/CustomLayers.py:668-810  (negative_sample_type='manual')
 
 Parameters are named after the TF checkpoint keys (``embed.embeddings``, ``w.embeddings``, ``bias``,
 ``MLP_layer1.kernel_0`` ...), so a TensorBundle checkpoint maps onto ``state_dict()`` by name.
@@ -2253,3 +2256,160 @@ class MINDLayer(Layer):
         output, loss = self.LAA_layer(self.embed.embeddings, items, mlped_capsules, valid_capsules_num, flag)
         self._raise_if_oob(flag)
         return {"output": output, "loss": loss}
+
+
+# ---------------------------------------------------------------------------------------------------
+# ComiRec: multi-interest retrieval with hard attention (6.MIND/CustomLayers.py:528-866)
+# ---------------------------------------------------------------------------------------------------
+
+def comirec_positional_table(seq_length, d_model):
+    """float32 [seq_length, d_model]: ComiRecSelfAttentiveLayer.positional_encoding (6.MIND/CustomLayers.py:625-642) as
+    numpy float32 reads it, in that order of operations -- pos * (1 / 10000 ** (2 (i // 2) / d_model)), sin on the even
+    columns and cos on the odd ones -- built once on the host (nobody here can run TensorFlow)."""
+    import numpy as np
+    pos = np.arange(int(seq_length), dtype=np.float32)[:, None]
+    i = np.arange(int(d_model), dtype=np.float32)[None, :]
+    rates = np.float32(1) / np.power(np.float32(10000.0), (np.float32(2) * np.floor_divide(i, np.float32(2)))
+                                     / np.float32(d_model))
+    angle = pos * rates
+    assert angle.dtype == np.float32
+    even = (np.arange(int(d_model)) % 2 == 0)[None, :]
+    return torch.from_numpy(np.where(even, np.sin(angle), np.cos(angle)).astype(np.float32))
+
+
+class ComiRecDynamicRoutingLayer(Layer):
+    """6.MIND/CustomLayers.py:528-594: dynamic routing with one projection per capsule and position.  ``W``
+    [capsules_num, T, D, capsules_dim] random_normal(stddev 0.05), trained; the routing logits ``B`` [capsules_num, T]
+    zeros, a buffer (the reference's non-trainable weight).  squash as in MultiInterestExtractorLayer.
+    The lookup is part of the kernel, so the call is ``layer((table, series), padding_index, keep_padding)`` with the
+    embedding matrix [V,E] and the stacked ids [B,T,C] where the reference takes the looked-up behaviours and a mask in
+    which True means "takes part": position t takes part iff ``(series[b,t,0] == padding_index) == keep_padding``.
+    ``seq_length`` and ``embedding_dims`` (extensions; the latter is D = C E) build at construction."""
+
+    def __init__(self, capsules_num, capsules_dim, routing_rounds=3, *, seq_length=None, embedding_dims=None):
+        super().__init__()
+        self.capsules_num = capsules_num
+        self.capsules_dim = capsules_dim
+        self.routing_rounds = routing_rounds
+        self.built = False
+        if seq_length is not None and embedding_dims is not None:
+            self.build((seq_length, embedding_dims))
+
+    def build(self, input_shape):
+        T, D = (int(v) for v in tuple(input_shape)[-2:])
+        ops.comirec_check_shape(D, self.capsules_dim, self.capsules_num, self.routing_rounds, T=T, mode="DR")
+        self.W = torch.nn.Parameter(_initializer("random_normal")((self.capsules_num, T, D, self.capsules_dim)))
+        self.register_buffer("B", torch.zeros(self.capsules_num, T))
+        self.built = True
+
+    def forward(self, inputs, padding_index=0, keep_padding=True, oob=None):
+        table, series = inputs
+        if not self.built:
+            self.build((series.shape[1], series.shape[2] * table.shape[1]))
+            self.to(table.device)
+        return Fn.ComiRecRouting.apply(table, series, self.W, self.B, self.routing_rounds, padding_index,
+                                       bool(keep_padding), oob)
+
+
+class ComiRecSelfAttentiveLayer(Layer):
+    """6.MIND/CustomLayers.py:597-665: ``tanh((behaviours + positional encoding) W1)``, ``capsules_num`` attention heads
+    from ``W2``, a masked softmax over the positions and the weighted sum of the TRANSFORMED behaviours (the reference's
+    choice, so that both extractors return [B, capsules_num, capsules_dim]).  ``W1`` [D, capsules_dim] and ``W2``
+    [capsules_num, capsules_dim] glorot_normal; the positional table is a constant built once on the host
+    (comirec_positional_table).  Called as ComiRecDynamicRoutingLayer."""
+
+    def __init__(self, capsules_num, capsules_dim, add_pos_emb=True, *, seq_length=None, embedding_dims=None):
+        super().__init__()
+        self.capsules_num = capsules_num
+        self.capsules_dim = capsules_dim
+        self.add_pos_emb = add_pos_emb
+        self.built = False
+        self._pos = None
+        if embedding_dims is not None:
+            self.build((seq_length, embedding_dims))
+
+    def build(self, input_shape):
+        T, D = tuple(input_shape)[-2:]
+        ops.comirec_check_shape(int(D), self.capsules_dim, self.capsules_num, T=None if T is None else int(T), mode="SA")
+        self.W1 = torch.nn.Parameter(glorot_normal((int(D), self.capsules_dim)))
+        self.W2 = torch.nn.Parameter(glorot_normal((self.capsules_num, self.capsules_dim)))
+        self.built = True
+
+    def _positions(self, T, D, device):
+        if not self.add_pos_emb:
+            return None
+        if self._pos is None or tuple(self._pos.shape) != (T, D) or self._pos.device != device:
+            self._pos = comirec_positional_table(T, D).to(device)
+        return self._pos
+
+    def forward(self, inputs, padding_index=0, keep_padding=True, oob=None):
+        table, series = inputs
+        T, D = series.shape[1], series.shape[2] * table.shape[1]
+        if not self.built:
+            self.build((T, D))
+            self.to(table.device)
+        return Fn.ComiRecSelfAttention.apply(table, series, self.W1, self.W2, self._positions(T, D, table.device),
+                                             padding_index, bool(keep_padding), oob)
+
+
+class ComiRecLayer(Layer):
+    """6.MIND/CustomLayers.py:668-810.  ``forward`` returns ``{'output': the selected capsules [B,Ns,Dc], 'loss': [B]}``:
+    every sampled item picks the capsule with the largest inner product (smallest index on a tie, tf.argmax) and the
+    softmax cross entropy with the label at sample 0 runs over those inner products.
+    Extensions, keyword-only: ``seq_length``, as in MINDLayer, builds the extractor's weights at construction;
+    ``reference_mask``: the reference hands ``series == padding_index`` to an extractor whose mask means "takes part"
+    (:714, :724), so read literally it routes over the PADDED positions -- True keeps that, False routes over the
+    behaviours, which is what the paper and MINDLayer mean.
+    ``negative_sample_type='auto'`` is tf.nn.sampled_softmax_loss with a random log-uniform sampler: nothing
+    deterministic to mirror, NotImplementedError.  The greedy_search_inference methods and save_interest_capsules are
+    host-side serving code and are not ported."""
+
+    def __init__(self, item_categorical_features=["label_goods_ids", "label_shop_ids", "label_cate_ids"],
+                 behavior_series_features=["visited_goods_ids", "visited_shop_ids", "visited_cate_ids"],
+                 feature_dims=160000, embedding_dims=16, activation="ReLU", padding_index=0, capsules_num=4, mode="DR",
+                 routing_rounds=3, add_pos_emb=True, negative_sample_type="manual", *, seq_length=None,
+                 reference_mask=True):
+        super().__init__()
+        if negative_sample_type not in ("auto", "manual"):
+            raise ValueError("negative_sample_type must be in ('auto','manual')")
+        if negative_sample_type == "auto":
+            raise NotImplementedError("negative_sample_type='auto' draws its negatives from tf.nn.sampled_softmax_loss' "
+                                      "random log-uniform sampler; only 'manual' is implemented")
+        self.item_categorical_features = item_categorical_features
+        assert len(item_categorical_features) == len(behavior_series_features), \
+            "Features to be interacted should match in item and behavior series"
+        self.behavior_series_features = behavior_series_features
+        self.feature_dims = feature_dims
+        self.embedding_dims = embedding_dims
+        self.embed = Embedding(feature_dims, embedding_dims)
+        capsules_dim = embedding_dims * len(item_categorical_features)
+        self.padding_index = padding_index
+        self.capsules_num = capsules_num
+        self.reference_mask = bool(reference_mask)
+        ops.comirec_check_shape(capsules_dim, capsules_dim, capsules_num)
+        built = dict(seq_length=seq_length, embedding_dims=None if seq_length is None else capsules_dim)
+        if mode == "DR":
+            self.interest_extractor = ComiRecDynamicRoutingLayer(capsules_num, capsules_dim, routing_rounds, **built)
+        elif mode == "SA":
+            self.interest_extractor = ComiRecSelfAttentiveLayer(capsules_num, capsules_dim, add_pos_emb, **built)
+        else:
+            raise ValueError("mode must be in ('DR','SA')")
+        self.negative_sample_type = negative_sample_type
+
+    def _capsules(self, inputs, flag):
+        series = _stack_ids(inputs, self.behavior_series_features, self._device())
+        return self.interest_extractor((self.embed.embeddings, series), self.padding_index, self.reference_mask, flag)
+
+    def generate_interest_capsules(self, inputs):
+        flag = ops.new_flag(self._device()) if self.check_ids else None
+        interest_capsules = self._capsules(inputs, flag)
+        self._raise_if_oob(flag)
+        return interest_capsules
+
+    def forward(self, inputs):
+        flag = ops.new_flag(self._device()) if self.check_ids else None
+        interest_capsules = self._capsules(inputs, flag)
+        items = _stack_ids(inputs, self.item_categorical_features, interest_capsules.device)
+        selected, _, loss, _ = Fn.ComiRecSelect.apply(self.embed.embeddings, items, interest_capsules, flag)
+        self._raise_if_oob(flag)
+        return {"output": selected, "loss": loss}

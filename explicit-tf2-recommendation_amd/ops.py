@@ -1858,3 +1858,191 @@ def mind_laa_bwd(embed, items, m, kv, gout=None, gloss=None):
         check(lib.rec_mind_laa_bwd_f32(*args, _ptr(gout), _ptr(gloss), _ptr(gm), _ptr(gitems), _stream()),
               "rec_mind_laa_bwd_f32")
     return gm, gitems
+
+
+# ---- ComiRec: dynamic routing with unshared weights, the self-attentive extractor and hard attention + sampled-softmax
+# loss (csrc/comirec.hip).  The limits are MIND's, the LDS fits are the header's formulas.
+def comirec_dr_lds_bytes(T, Dc, R):
+    """LDS of one row (b, k) of the dynamic-routing backward (include/mi355rec.h): what both directions are held to."""
+    return 4 * (T * _odd(Dc) + (2 * R + 3) * T + 2 * R * _odd(Dc))
+
+
+def comirec_sa_lds_bytes(T, D, Dc, K):
+    """LDS of one workgroup of the self-attentive backward (include/mi355rec.h)."""
+    return 4 * (T * _odd(D) + 2 * T * _odd(Dc) + 2 * K * T + 3 * K * _odd(Dc) + T)
+
+
+def comirec_check_shape(D, Dc, K, R=None, T=None, mode="DR", Ns=None):
+    """ValueError for sizes that describe no ComiRec body, NotImplementedError naming the limit for shapes the kernels do
+    not cover (the ABI would return -2): key width D = E C, capsule width Dc, K capsules and -- where given -- R routing
+    rounds and the series length T of mode 'DR' or 'SA', or the number of sampled items Ns of the hard attention."""
+    sizes = [D, Dc, K] + [v for v in (R, T, Ns) if v is not None]
+    if min(sizes) < 1:
+        raise ValueError("every size of a ComiRec body must be positive, got D=%d, Dc=%d, capsules=%d, rounds=%r, T=%r, "
+                         "Ns=%r" % (D, Dc, K, R, T, Ns))
+    if D > DIN_MAX_D or Dc > DIN_MAX_D or K > AFM_MAX_A or (R is not None and R > MIND_MAX_ROUNDS):
+        raise NotImplementedError(
+            "ComiRec kernels cover key width and capsule width <= %d, capsules <= %d and routing rounds <= %d; got key "
+            "width=%d, capsule width=%d, capsules=%d, rounds=%r" % (DIN_MAX_D, AFM_MAX_A, MIND_MAX_ROUNDS, D, Dc, K, R))
+    if T is not None and mode == "DR" and comirec_dr_lds_bytes(T, Dc, R) > _MIND_LDS_CAP:
+        raise NotImplementedError(
+            "ComiRec dynamic routing holds one row (b, k) in LDS: 4 (T (Dc|1) + (2 R + 3) T + 2 R (Dc|1)) <= %d bytes; "
+            "got %d at T=%d, capsule width=%d, rounds=%d" % (_MIND_LDS_CAP, comirec_dr_lds_bytes(T, Dc, R), T, Dc, R))
+    if T is not None and mode == "SA" and comirec_sa_lds_bytes(T, D, Dc, K) > _MIND_LDS_CAP:
+        raise NotImplementedError(
+            "ComiRec self-attention holds one example in LDS: 4 (T (D|1) + 2 T (Dc|1) + 2 K T + 3 K (Dc|1) + T) <= %d "
+            "bytes; got %d at T=%d, key width=%d, capsule width=%d, capsules=%d"
+            % (_MIND_LDS_CAP, comirec_sa_lds_bytes(T, D, Dc, K), T, D, Dc, K))
+    if Ns is not None and mind_laa_lds_bytes(Ns, Dc, K) > _MIND_LDS_CAP:
+        raise NotImplementedError(
+            "ComiRec hard attention holds one example in LDS: 4 ((K + Ns) (Dc|1) + 2 K Ns + 2 Ns) <= %d bytes; got %d at "
+            "Ns=%d, capsule width=%d, capsules=%d" % (_MIND_LDS_CAP, mind_laa_lds_bytes(Ns, Dc, K), Ns, Dc, K))
+
+
+def _comirec_dr_args(embed, series, W, B0, R, padding_index, keep_padding):
+    _table(embed, "embed"); _i64(series, "series"); _f32(W, "W"); _f32(B0, "B0")
+    if series.dim() != 3 or W.dim() != 4 or B0.dim() != 2:
+        raise ValueError("dynamic routing takes series [B,T,C], W [K,T,D,Dc] and B0 [K,T]; got %s, %s, %s"
+                         % (tuple(series.shape), tuple(W.shape), tuple(B0.shape)))
+    V, E = embed.shape
+    B, T, Cn = series.shape
+    K, Tw, D, Dc = W.shape
+    if D != Cn * E or Tw != T or tuple(B0.shape) != (K, T):
+        raise ValueError("dynamic routing: W must be [K, T = %d, C E = %d, Dc] and B0 [K, T]; got W %s, B0 %s"
+                         % (T, Cn * E, tuple(W.shape), tuple(B0.shape)))
+    comirec_check_shape(D, Dc, K, int(R), T=T, mode="DR")
+    return [_ptr(embed), embed.stride(0), V, E, Cn, _ptr(series), B, T, _ptr(W), _ptr(B0), Dc, K, int(R),
+            int(padding_index), int(bool(keep_padding))], (B, T, Cn, E, D, Dc, K)
+
+
+def comirec_dr_fwd(embed, series, W, B0, routing_rounds=3, padding_index=0, keep_padding=True, oob=None):
+    """ComiRecDynamicRoutingLayer over the looked-up series: series ids [B,T,C] into ``embed``, W [K,T,C E,Dc], B0 [K,T]
+    -> the squashed capsules of the last round [B,K,Dc].  Position t takes part iff (series[b,t,0] == padding_index) ==
+    keep_padding.  Nothing else is saved."""
+    args, (B, T, Cn, E, D, Dc, K) = _comirec_dr_args(embed, series, W, B0, routing_rounds, padding_index, keep_padding)
+    out = torch.empty((B, K, Dc), dtype=torch.float32, device=embed.device)
+    if B > 0:                                            # an empty batch answers from the sizes alone
+        nbytes = lib.rec_comirec_dr_workspace_bytes(B, T, E, Cn, Dc, K, int(routing_rounds))
+        ws = _workspace(nbytes, "rec_comirec_dr_workspace_bytes", embed.device, torch.float32)
+        check(lib.rec_comirec_dr_fwd_f32(*args, _ptr(out), _ptr(oob), _ptr(ws), nbytes, _stream()),
+              "rec_comirec_dr_fwd_f32")
+    return out
+
+
+def comirec_dr_bwd(embed, series, W, B0, gout, routing_rounds=3, padding_index=0, keep_padding=True):
+    """-> (gkeys [B,T,C E], the IndexedSlices values of the series lookups, dW [K,T,C E,Dc]) from gout [B,K,Dc]; the
+    projection and the rounds are run again and differentiated through, all of them.  B0 has no gradient."""
+    args, (B, T, Cn, E, D, Dc, K) = _comirec_dr_args(embed, series, W, B0, routing_rounds, padding_index, keep_padding)
+    if tuple(_f32(gout, "gout").shape) != (B, K, Dc):
+        raise ValueError("gout must be [B,K,Dc] = %s, got %s" % ((B, K, Dc), tuple(gout.shape)))
+    dev = embed.device
+    gkeys = torch.empty((B, T, D), dtype=torch.float32, device=dev)
+    dW = (torch.zeros if B == 0 else torch.empty)((K, T, D, Dc), dtype=torch.float32, device=dev)
+    if B > 0:
+        nbytes = lib.rec_comirec_dr_workspace_bytes(B, T, E, Cn, Dc, K, int(routing_rounds))
+        ws = _workspace(nbytes, "rec_comirec_dr_workspace_bytes", dev, torch.float32)
+        check(lib.rec_comirec_dr_bwd_f32(*args, _ptr(gout), _ptr(gkeys), _ptr(dW), _ptr(ws), nbytes, _stream()),
+              "rec_comirec_dr_bwd_f32")
+    return gkeys, dW
+
+
+def _comirec_sa_args(embed, series, W1, W2, pos, padding_index, keep_padding):
+    _table(embed, "embed"); _i64(series, "series"); _f32(W1, "W1"); _f32(W2, "W2")
+    if series.dim() != 3 or W1.dim() != 2 or W2.dim() != 2:
+        raise ValueError("self-attention takes series [B,T,C], W1 [D,Dc] and W2 [K,Dc]; got %s, %s, %s"
+                         % (tuple(series.shape), tuple(W1.shape), tuple(W2.shape)))
+    V, E = embed.shape
+    B, T, Cn = series.shape
+    D, Dc = W1.shape
+    K = W2.shape[0]
+    if D != Cn * E or W2.shape[1] != Dc:
+        raise ValueError("self-attention: W1 must have C E = %d rows and W2 Dc = %d columns; got W1 %s, W2 %s"
+                         % (Cn * E, Dc, tuple(W1.shape), tuple(W2.shape)))
+    if pos is not None and tuple(_f32(pos, "pos").shape) != (T, D):
+        raise ValueError("pos must be [T,D] = %s, got %s" % ((T, D), tuple(pos.shape)))
+    comirec_check_shape(D, Dc, K, T=T, mode="SA")
+    return [_ptr(embed), embed.stride(0), V, E, Cn, _ptr(series), B, T, _ptr(W1), _ptr(W2), _ptr(pos), Dc, K,
+            int(padding_index), int(bool(keep_padding))], (B, T, Cn, E, D, Dc, K)
+
+
+def comirec_sa_fwd(embed, series, W1, W2, pos=None, padding_index=0, keep_padding=True, oob=None):
+    """ComiRecSelfAttentiveLayer over the looked-up series in one launch: h = tanh((x + pos) W1), K heads h W2^T, masked
+    softmax over the positions -> the weighted sums of h [B,K,Dc].  ``pos`` [T,C E] or None."""
+    args, (B, T, Cn, E, D, Dc, K) = _comirec_sa_args(embed, series, W1, W2, pos, padding_index, keep_padding)
+    out = torch.empty((B, K, Dc), dtype=torch.float32, device=embed.device)
+    if B > 0:
+        check(lib.rec_comirec_sa_fwd_f32(*args, _ptr(out), _ptr(oob), _stream()), "rec_comirec_sa_fwd_f32")
+    return out
+
+
+def comirec_sa_bwd(embed, series, W1, W2, gout, pos=None, padding_index=0, keep_padding=True):
+    """-> (gkeys [B,T,C E], dW1 [C E,Dc], dW2 [K,Dc]) from gout [B,K,Dc]; ``pos`` is a constant."""
+    args, (B, T, Cn, E, D, Dc, K) = _comirec_sa_args(embed, series, W1, W2, pos, padding_index, keep_padding)
+    if tuple(_f32(gout, "gout").shape) != (B, K, Dc):
+        raise ValueError("gout must be [B,K,Dc] = %s, got %s" % ((B, K, Dc), tuple(gout.shape)))
+    dev = embed.device
+    make = torch.zeros if B == 0 else torch.empty
+    gkeys = torch.empty((B, T, D), dtype=torch.float32, device=dev)
+    dW1, dW2 = make((D, Dc), dtype=torch.float32, device=dev), make((K, Dc), dtype=torch.float32, device=dev)
+    if B > 0:
+        nbytes = lib.rec_comirec_sa_workspace_bytes(B, T, E, Cn, Dc, K)
+        ws = _workspace(nbytes, "rec_comirec_sa_workspace_bytes", dev, torch.float32)
+        check(lib.rec_comirec_sa_bwd_f32(*args, _ptr(gout), _ptr(gkeys), _ptr(dW1), _ptr(dW2), _ptr(ws), nbytes,
+                                         _stream()), "rec_comirec_sa_bwd_f32")
+    return gkeys, dW1, dW2
+
+
+def _comirec_select_args(embed, items, m):
+    _table(embed, "embed"); _i64(items, "items"); _f32(m, "m")
+    if items.dim() != 3 or m.dim() != 3:
+        raise ValueError("hard attention takes items [B,Ns,C] and m [B,K,Dc]; got %s, %s"
+                         % (tuple(items.shape), tuple(m.shape)))
+    V, E = embed.shape
+    B, Ns, Cn = items.shape
+    K, Dc = m.shape[1:]
+    if m.shape[0] != B or Dc != Cn * E:
+        raise ValueError("hard attention: m must be [B, K, C E] = [%d, K, %d]; got %s" % (B, Cn * E, tuple(m.shape)))
+    comirec_check_shape(Dc, Dc, K, Ns=Ns)
+    return [_ptr(embed), embed.stride(0), V, E, Cn, _ptr(items), B, Ns, _ptr(m), K], (B, Ns, Dc, K)
+
+
+def comirec_select_fwd(embed, items, m, oob=None):
+    """Hard attention of ComiRecLayer over the looked-up sampled items and the sampled-softmax loss in one launch: item
+    ids [B,Ns,C] into ``embed``, capsules m [B,K,C E] -> (chosen int32 [B,Ns], the smallest index of the largest inner
+    product; inner [B,Ns], that product; loss [B]) with the label at sample 0."""
+    args, (B, Ns, Dc, K) = _comirec_select_args(embed, items, m)
+    dev = embed.device
+    chosen = torch.empty((B, Ns), dtype=torch.int32, device=dev)
+    inner = torch.empty((B, Ns), dtype=torch.float32, device=dev)
+    loss = torch.empty((B,), dtype=torch.float32, device=dev)
+    if B > 0:
+        check(lib.rec_comirec_select_fwd_f32(*args, _ptr(chosen), _ptr(inner), _ptr(loss), _ptr(oob), _stream()),
+              "rec_comirec_select_fwd_f32")
+    return chosen, inner, loss
+
+
+def comirec_select_bwd(embed, items, m, chosen, ginner=None, gloss=None, gsel=None):
+    """-> (gm [B,K,C E], gitems [B,Ns,C E], the IndexedSlices values of the item lookups) from ginner [B,Ns] and / or
+    gloss [B] and, optionally, gsel [B,Ns,C E], the gradient of the selected capsules, in one launch; ``chosen`` is the
+    forward's.  With no gradient at all, zeros."""
+    args, (B, Ns, Dc, K) = _comirec_select_args(embed, items, m)
+    dev = embed.device
+    if tuple(_req(chosen, torch.int32, "chosen").shape) != (B, Ns):
+        raise ValueError("chosen must be [B,Ns] = %s, got %s" % ((B, Ns), tuple(chosen.shape)))
+    if ginner is None and gloss is None and gsel is None:
+        return (torch.zeros((B, K, Dc), dtype=torch.float32, device=dev),
+                torch.zeros((B, Ns, Dc), dtype=torch.float32, device=dev))
+    if ginner is not None and tuple(_f32(ginner, "ginner").shape) != (B, Ns):
+        raise ValueError("ginner must be [B,Ns] = %s, got %s" % ((B, Ns), tuple(ginner.shape)))
+    if gloss is not None and tuple(_f32(gloss, "gloss").shape) != (B,):
+        raise ValueError("gloss must be [B] = [%d], got %s" % (B, tuple(gloss.shape)))
+    if gsel is not None and tuple(_f32(gsel, "gsel").shape) != (B, Ns, Dc):
+        raise ValueError("gsel must be [B,Ns,Dc] = %s, got %s" % ((B, Ns, Dc), tuple(gsel.shape)))
+    if ginner is None and gloss is None:                 # the ABI wants one of the two: an all-zero gloss adds nothing
+        gloss = torch.zeros((B,), dtype=torch.float32, device=dev)
+    gm = torch.empty((B, K, Dc), dtype=torch.float32, device=dev)
+    gitems = torch.empty((B, Ns, Dc), dtype=torch.float32, device=dev)
+    if B > 0:
+        check(lib.rec_comirec_select_bwd_f32(*args, _ptr(chosen), _ptr(ginner), _ptr(gloss), _ptr(gsel), _ptr(gm),
+                                             _ptr(gitems), _stream()), "rec_comirec_select_bwd_f32")
+    return gm, gitems

@@ -1046,6 +1046,84 @@ int rec_mind_laa_bwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C
                          int Ns, const float* m, const int32_t* kv, int K, const float* gout, const float* gloss,
                          float* gm, float* gitems, void* stream);
 
+/* ---- ComiRec (ComiRecDynamicRoutingLayer, ComiRecSelfAttentiveLayer, ComiRecLayer.manually_negative_sampled_call,
+ * 6.MIND/CustomLayers.py:528-810; csrc/comirec.hip): dynamic routing with unshared weights, the self-attentive
+ * extractor, and hard attention with the sampled-softmax loss.  All three gather from embed [V, E] with row stride
+ * ld >= E; an id outside [0, V) reads as a zero row and sets *oob_flag (may be NULL).  series int64 [B, T, C], D = E C.
+ * Position t of example b TAKES PART iff (series[b,t,0] == padding_index) == (keep_padding != 0): keep_padding = 1 is
+ * the reference read literally (ComiRecLayer hands `series == padding_index` to a mask in which True means "takes
+ * part"), keep_padding = 0 routes over the behaviours, as MIND does.  Padding may sit anywhere.  -FLT_MAX is the lowest
+ * finite float: a row with no participating position gets the uniform weights 1 / T over all T positions, never NaN.
+ * squash(s) = s n / (1 + n^2), n = |s|, 0 with a zero gradient at n = 0, as for MIND.
+ *
+ * (a) Dynamic routing.  W [K, T, D, Dc] (one matrix per capsule and position), B0 [K, T] (the layer's non-trainable
+ * logits), R rounds.  Per example b:
+ *   x_t = concat_r embed[series[b,t,r]]      u[k,t,:] = x_t W[k,t]      L = B0
+ *   R times:  C = softmax_t(part_t ? L : -FLT_MAX)  [K, T],   c_k = squash(sum_t C[k,t] u[k,t,:]),
+ *             and in every round but the last  L[k,t] += c_k . u[k,t,:]
+ *   out[b] = c                                                                                    out [B, K, Dc]
+ * The backward takes gout [B, K, Dc], recomputes u and the rounds and differentiates through all of them (no
+ * stop_gradient; B0 gets nothing): gkeys [B, T, D], the IndexedSlices values of the series lookups, and dW [K, T, D, Dc],
+ * both written, never added to.  The batch goes through in slabs of min(2048, max(32, 64 MiB / (4 K T Dc) rounded down
+ * to 32)) examples; u [slab, K, T, Dc] lives in the workspace (du overwrites it), the projection and the two backward
+ * products run on v_mfma_f32_32x32x2_f32 over 32-example tiles with W[k,t] read once per tile, and dW is reduced through
+ * one partial per batch slice (at most 16) and a slot sum in serial order.  One wave owns a row (b, k) through the rounds.
+ * Supported, the same both ways: D = E C <= REC_DIN_MAX_D (256), Dc <= REC_DIN_MAX_D, K <= REC_AFM_MAX_A (16),
+ * 1 <= R <= 8, 0 <= B < 2^31 and one row's LDS within the 150 KiB launch cap:
+ *   4 (T (Dc|1) + (2 R + 3) T + 2 R (Dc|1)) <= 153600                          (x|1: x made odd)
+ * e.g. T <= 657 at Dc = 48, R = 3 and T <= 124 at Dc = 256, R = 8.
+ * workspace (BOTH directions): rec_comirec_dr_workspace_bytes: u of a slab plus, for the backward, slices K T D Dc
+ * floats; the forward accepts one that holds u alone; 0: invalid or unsupported shape.
+ *
+ * (b) Self-attentive extractor.  W1 [D, Dc], W2 [K, Dc], pos [T, D] or NULL (no positional encoding).  Per example:
+ *   h_t = tanh((x_t + pos_t) W1)   sc[k,t] = h_t . W2[k]   A = softmax_t(part_t ? sc : -FLT_MAX)
+ *   out[b,k] = sum_t A[k,t] h_t     (the reference weights h, not the raw behaviours)             out [B, K, Dc]
+ * One launch forward, one example per workgroup; the backward recomputes it and writes gkeys [B, T, D], dW1 [D, Dc] and
+ * dW2 [K, Dc] (pos is a constant), the weight gradients through one partial per workgroup of a capped grid and a slot
+ * sum in wave order.  Supported: D, Dc, K, B as above and the backward's LDS within the launch cap:
+ *   4 (T (D|1) + 2 T (Dc|1) + 2 K T + 3 K (Dc|1) + T) <= 153600
+ * e.g. T <= 242 at D = Dc = 48, K = 4.  workspace (backward only): rec_comirec_sa_workspace_bytes: min(B, 1024)
+ * partials of (D + K) Dc floats (at most 512 / 256 when dW1 has more than four / sixteen 32 x 32 blocks).
+ *
+ * (c) Hard attention + loss.  items int64 [B, Ns, C], Dc = E C, m [B, K, Dc] (the capsules).  Per example:
+ *   x_s = concat_r embed[items[b,s,r]]   p[s,k] = m_k . x_s
+ *   chosen[s] = the smallest k with p[s,k] = max_k p[s,k]  (tf.argmax)   inner[s] = p[s, chosen[s]]
+ *   loss = logsumexp_s(inner) - inner[0]   (softmax cross entropy with the label at sample 0)
+ * Forward, one launch: chosen int32 [B, Ns], inner [B, Ns], loss [B].  Backward, one launch, from ginner [B, Ns] and
+ * gloss [B], either of which may be NULL (not both), and gsel [B, Ns, Dc] or NULL, the gradient of the selected
+ * capsules m[b, chosen[s]] themselves: gm [B, K, Dc] and gitems [B, Ns, Dc].  It reads chosen as the forward wrote it
+ * (a value outside [0, K) is clamped) and never recomputes the argmax.  Supported: as rec_mind_laa_*, the same LDS
+ * inequality; rec_comirec_select_lds_bytes: the dynamic LDS of a launch; 0: invalid or unsupported.  No workspace.
+ *
+ * All entry points only enqueue (no allocation, no host synchronisation: graph-capturable) and use no float atomics:
+ * bit-identical results run to run.  Return codes, answered in this order: a size below 1 (B below 0): -1; a shape
+ * outside the limits: -2, from the sizes alone; ld < E, V < 1 or a NULL pointer other than oob_flag, pos, gsel / one of
+ * ginner and gloss: -1; a workspace that is too small: -3; then B == 0: 0, nothing is launched or written. */
+size_t rec_comirec_dr_workspace_bytes(int64_t B, int T, int E, int C, int Dc, int K, int R);
+int rec_comirec_dr_fwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* series, int64_t B,
+                           int T, const float* W, const float* B0, int Dc, int K, int R, int64_t padding_index,
+                           int keep_padding, float* out, int* oob_flag, void* workspace, size_t workspace_bytes,
+                           void* stream);
+int rec_comirec_dr_bwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* series, int64_t B,
+                           int T, const float* W, const float* B0, int Dc, int K, int R, int64_t padding_index,
+                           int keep_padding, const float* gout, float* gkeys, float* dW, void* workspace,
+                           size_t workspace_bytes, void* stream);
+size_t rec_comirec_sa_workspace_bytes(int64_t B, int T, int E, int C, int Dc, int K);
+int rec_comirec_sa_fwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* series, int64_t B,
+                           int T, const float* W1, const float* W2, const float* pos, int Dc, int K,
+                           int64_t padding_index, int keep_padding, float* out, int* oob_flag, void* stream);
+int rec_comirec_sa_bwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* series, int64_t B,
+                           int T, const float* W1, const float* W2, const float* pos, int Dc, int K,
+                           int64_t padding_index, int keep_padding, const float* gout, float* gkeys, float* dW1,
+                           float* dW2, void* workspace, size_t workspace_bytes, void* stream);
+size_t rec_comirec_select_lds_bytes(int Ns, int E, int C, int K);
+int rec_comirec_select_fwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* items, int64_t B,
+                               int Ns, const float* m, int K, int32_t* chosen, float* inner, float* loss, int* oob_flag,
+                               void* stream);
+int rec_comirec_select_bwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* items, int64_t B,
+                               int Ns, const float* m, int K, const int32_t* chosen, const float* ginner,
+                               const float* gloss, const float* gsel, float* gm, float* gitems, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
