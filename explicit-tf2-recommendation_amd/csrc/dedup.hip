@@ -532,6 +532,30 @@ __global__ __launch_bounds__(256) void segsum_scalar_kernel(const float* __restr
   out[t] = acc;
 }
 
+// Rows wider than 256 columns (CAN's induction rows: 816 floats and more): one workgroup per output row, a thread per
+// column and every 256th after it, the rows of the run added in sorted (= position) order with four loads in flight.
+// A workgroup beyond the unique count finds an empty run and writes zeros.
+__global__ __launch_bounds__(256) void segsum_wide_kernel(const float* __restrict__ vals, int E,
+                                                          const int32_t* __restrict__ perm,
+                                                          const int32_t* __restrict__ seg_start, int32_t row_div,
+                                                          float* __restrict__ out) {
+  const int64_t u = blockIdx.x;
+  const int s0 = seg_start[u], s1 = seg_start[u + 1];
+  for (int d = threadIdx.x; d < E; d += 256) {
+    float acc = 0.f;
+    int s = s0;
+    for (; s + 4 <= s1; s += 4) {
+      float r[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) r[q] = vals[(int64_t)(perm[s + q] / row_div) * E + d];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc += r[q];
+    }
+    for (; s < s1; ++s) acc += vals[(int64_t)(perm[s] / row_div) * E + d];
+    out[u * E + d] = acc;
+  }
+}
+
 // ---- union of P ascending, duplicate-free id lists (what P requesters that de-duplicated their own batch send to
 // the owner of a table shard).  Final position of an element = its index in its own list + for every other list the
 // number of ids that sort before it (ties: the lower list first) -- binary searches, no sort.
@@ -661,8 +685,12 @@ extern "C" int rec_segment_sum_f32(const float* vals, int E, const int32_t* perm
   if (E <= 0 || n < 0 || row_div <= 0) return REC_E_ARG;
   if (n == 0) return REC_OK;
   if (!vals || !perm || !seg_start || !out || !workspace) return REC_E_ARG;
-  if (E > 256) return REC_E_UNSUPPORTED;
   hipStream_t st = as_stream(stream);
+  if (E > 256) {                                   // wide rows: their own kernel, no workspace use
+    hipLaunchKernelGGL(segsum_wide_kernel, dim3((unsigned)n), dim3(256), 0, st, vals, E, perm, seg_start, row_div, out);
+    REC_LAUNCH_CHECK();
+    return REC_OK;
+  }
   unsigned n_chunks = (unsigned)ceil_div64(n, CH);
 #define CHUNK(GE) hipLaunchKernelGGL(segsum_chunk_kernel<GE>, dim3(n_chunks), dim3(256), 0, st, vals, E, perm, \
                                      seg_start, n, row_div, workspace)

@@ -21,8 +21,8 @@ class SparseRowGrad:
         return torch.sparse_coo_tensor(self.uniq_ids[: self.rows.shape[0]].unsqueeze(0), self.rows, self.shape)
 
 
-def _sparse_grad(plan, vals, E, shape, row_div=1):
-    rows = plan.segment_sum(vals, E, row_div)
+def _sparse_grad(plan, vals, E, shape, row_div=1, wide=False):
+    rows = plan.segment_sum(vals, E, row_div, wide)
     return SparseRowGrad(plan.uniq_ids, rows, plan.n_uniq, shape).to_sparse()
 
 
@@ -1041,3 +1041,38 @@ class ComiRecSelect(torch.autograd.Function):
         if gsel is not None or ginner is not None or gloss is not None:
             gembed = _series_grad(ctx, items, gitems, V, E)
         return gembed, None, gm, None
+
+
+class CoAction(torch.autograd.Function):
+    """CoActionUnit.call fused with both lookups (7.SIM/CustomLayers.py:339-378; csrc/can.hip): the feed table [Vf,E],
+    target ids iid [B], feed ids fid [B,T] and the induction tables [Vi,P] -- one per order, or ONE that every order reads
+    -> out [order,B,T,Eo], or with ``pooled`` its sum over orders and positions [B,Eo].  Nothing but the inputs is saved;
+    the backward runs the forward again.  Every table's gradient is a sparse COO tensor of de-duplicated rows: the feed
+    table's over the B T feed ids, an induction table's over the B target ids (one plan serves all orders), and a shared
+    table gets ONE gradient, the order * B value rows under one plan over the ids tiled ``order`` times."""
+
+    @staticmethod
+    def forward(ctx, feed, iid, fid, coefs, order, act, padding_index, pooled, oob, *inds):
+        res = ops.can_fwd(feed, inds, iid, fid, coefs, order, act, padding_index, pooled, oob)
+        ctx.save_for_backward(feed, iid, fid, *inds)
+        ctx.cfg = (tuple(coefs), order, act)
+        ctx.tail = (padding_index, pooled)
+        return res
+
+    @staticmethod
+    def backward(ctx, g):
+        feed, iid, fid, *inds = ctx.saved_tensors
+        coefs, order, act = ctx.cfg
+        gfeed, gind = ops.can_bwd(feed, inds, iid, fid, coefs, order, act, g.contiguous(), *ctx.tail)
+        Vf, E = feed.shape
+        Vi, P = inds[0].shape
+        dfeed = _series_grad(ctx, fid, gfeed, Vf, E)
+        dinds = [None] * len(inds)
+        if len(inds) == 1 and ctx.needs_input_grad[9]:
+            plan = ops.DedupPlan(iid.repeat(order), Vi)
+            dinds[0] = _sparse_grad(plan, gind.reshape(-1, P), P, (Vi, P), wide=True)
+        elif any(ctx.needs_input_grad[9:]):
+            plan = ops.DedupPlan(iid, Vi)
+            dinds = [_sparse_grad(plan, gind[o], P, (Vi, P), wide=True) if ctx.needs_input_grad[9 + o] else None
+                     for o in range(order)]
+        return (dfeed,) + (None,) * 8 + tuple(dinds)

@@ -2413,3 +2413,70 @@ class ComiRecLayer(Layer):
         selected, _, loss, _ = Fn.ComiRecSelect.apply(self.embed.embeddings, items, interest_capsules, flag)
         self._raise_if_oob(flag)
         return {"output": selected, "loss": loss}
+
+
+class CoActionUnit(Layer):
+    """7.SIM/CustomLayers.py:285-378, the CAN co-action: the induction row of the target item IS the weights and biases of
+    a small MLP (layer l maps feed_feature_dim * coef_l to feed_feature_dim * coef_l+1 columns) that is applied to every
+    feed feature of the example raised to the powers 1..order; a feed id equal to ``padding_index`` gives zeros.
+    ``forward([induction_feature, feed_feature])`` returns the reference's list of ``order`` tensors: induction_feature
+    [B] or [B,1]; feed_feature [B] (outputs [B, Eo]) or [B,T] (outputs [B,T,Eo]).  Both lookups and the MLP of every order
+    are one launch (csrc/can.hip).  A reference quirk that is kept: the layers are zipped with a list of ``order``
+    activations, so only min(len(layer_unit_coef), order) layers are applied and Eo is the width of the last one applied;
+    the induction rows still hold every layer, the unused tail gets a zero gradient.  With ``order_independent=False``
+    every order reads ONE table (state dict: only ``induction_embedding.0.embeddings``) and its gradient is the sum over
+    the orders.  Activations: 'tanh', 'relu', 'sigmoid', 'linear' / None; anything else Keras knows: NotImplementedError.
+    Extension: ``pooled([induction_feature, feed_feature])`` -> [B, Eo], the sum of the list over orders and positions
+    (what CANLayer takes from its series co-action), fused: the list is never materialised."""
+
+    def __init__(self, induction_feature_num=1000, feed_feature_num=1000, feed_feature_dim=16, layer_unit_coef=None,
+                 order=3, order_independent=True, activation="tanh", padding_index=0):
+        super().__init__()
+        if layer_unit_coef is None:
+            layer_unit_coef = [1, 1, 1]
+        if activation not in ops.ACT_CODE:
+            raise NotImplementedError("CoActionUnit implements the activations 'tanh', 'relu', 'sigmoid' and 'linear' / "
+                                      "None, got %r" % (activation,))
+        self.layer_unit_coef = [int(c) for c in layer_unit_coef]
+        self.order = int(order)
+        self.order_independent = bool(order_independent)
+        self.act = ops.ACT_CODE[activation]
+        self.padding_index = padding_index
+        self.feed_feature_dim = int(feed_feature_dim)
+        ops.can_check_shape(self.feed_feature_dim, self.layer_unit_coef, self.order)
+        self.feed_embedding = Embedding(feed_feature_num, feed_feature_dim)
+        induction_feature_dim = ops.can_row_floats(feed_feature_dim, self.layer_unit_coef)
+        self.induction_embedding = torch.nn.ModuleList(
+            [Embedding(induction_feature_num, induction_feature_dim)
+             for _ in range(self.order if self.order_independent else 1)])    # not independent: one table, every order
+        applied = min(len(self.layer_unit_coef), self.order)
+        self.output_dim = ops.can_widths(feed_feature_dim, self.layer_unit_coef)[applied]
+
+    def _ids(self, inputs):
+        induction_feature, feed_feature = inputs
+        dev = self._device()
+        as_ids = lambda t: (t if isinstance(t, torch.Tensor) else torch.as_tensor(t)).to(device=dev, dtype=torch.int64)
+        iid, fid = as_ids(induction_feature), as_ids(feed_feature)
+        if iid.dim() == 2 and iid.shape[1] == 1:
+            iid = iid.squeeze(1)
+        if fid.dim() not in (1, 2):
+            raise ValueError("feed_vector维度必须是2维或者3维")
+        if iid.dim() != 1 or iid.shape[0] != fid.shape[0]:
+            raise ValueError("induction_feature must be [B] or [B,1] with the batch of feed_feature, got %s and %s"
+                             % (tuple(iid.shape), tuple(fid.shape)))
+        return iid.contiguous(), fid.reshape(fid.shape[0], -1).contiguous(), fid.dim() == 1
+
+    def _run(self, inputs, pooled):
+        iid, fid, flat = self._ids(inputs)
+        flag = ops.new_flag(iid.device) if self.check_ids else None
+        res = Fn.CoAction.apply(self.feed_embedding.embeddings, iid, fid, self.layer_unit_coef, self.order, self.act,
+                                self.padding_index, pooled, flag, *[e.embeddings for e in self.induction_embedding])
+        self._raise_if_oob(flag)
+        return res, flat
+
+    def forward(self, inputs):
+        out, flat = self._run(inputs, False)
+        return [o[:, 0] if flat else o for o in out.unbind(0)]
+
+    def pooled(self, inputs):
+        return self._run(inputs, True)[0]

@@ -137,9 +137,10 @@ class DedupPlan:
                                                       _ptr(ws), nbytes, _stream()),
                   "rec_dedup_plan_sorted_lists_i64")
 
-    def segment_sum(self, vals, E, row_div=1):
-        """vals [n/row_div, E] -> [n, E]; rows >= n_uniq are zero."""
-        if E > 256:      # wide rows (FFM's F*E): the kernel takes up to 256 columns at a time
+    def segment_sum(self, vals, E, row_div=1, wide=False):
+        """vals [n/row_div, E] -> [n, E]; rows >= n_uniq are zero.  ``wide``: rows of more than 256 columns go through
+        the wide-row kernel in one launch (a workgroup per unique id) instead of 256-column slices."""
+        if E > 256 and not wide:      # wide rows (FFM's F*E): the kernel takes up to 256 columns at a time
             out = torch.empty((max(self.n, 1), E), dtype=torch.float32, device=vals.device)
             for c0 in range(0, E, 256):
                 c1 = min(E, c0 + 256)
@@ -2046,3 +2047,105 @@ def comirec_select_bwd(embed, items, m, chosen, ginner=None, gloss=None, gsel=No
         check(lib.rec_comirec_select_bwd_f32(*args, _ptr(chosen), _ptr(ginner), _ptr(gloss), _ptr(gsel), _ptr(gm),
                                              _ptr(gitems), _stream()), "rec_comirec_select_bwd_f32")
     return gm, gitems
+
+
+# ---- CAN co-action: both lookups and the per-example micro-MLP in one launch each way (csrc/can.hip).  The widest layer
+# is AFM's embedding limit; layers, orders and the LDS fit are the header's.
+CAN_MAX_W = AFM_MAX_E
+CAN_MAX_LAYERS = CAN_MAX_ORDER = 4
+
+
+def can_widths(E, coefs):
+    """[E, E c_1, ..., E c_n]: the layer widths of a co-action MLP"""
+    return [int(E)] + [int(E) * int(c) for c in coefs]
+
+
+def can_row_floats(E, coefs):
+    """P: the floats of an induction row, W_l [w_l, w_l+1] then B_l, layer after layer"""
+    w = can_widths(E, coefs)
+    return sum(a * b + b for a, b in zip(w[:-1], w[1:]))
+
+
+def can_lds_bytes(T, E, coefs, order):
+    """LDS of one example of the co-action backward (include/mi355rec.h): what both directions are held to."""
+    w = can_widths(E, coefs)
+    w = w[:min(len(coefs), order) + 1]                   # the layers applied
+    pv = sum(a * _odd(b) + b for a, b in zip(w[:-1], w[1:]))
+    return 4 * (2 * T * E + pv + T * sum(_odd(x) for x in w) + 2 * T * _odd(max(w)) + T + 256)
+
+
+def can_check_shape(E, coefs, order, T=None):
+    """ValueError for sizes that describe no co-action unit, NotImplementedError naming the limit for shapes the kernels
+    do not cover (the ABI would return -2): feed width E, layer_unit_coef, order and -- where given -- the number of feed
+    positions T of an example."""
+    coefs = [int(c) for c in coefs]
+    sizes = [E, order, len(coefs)] + coefs + ([T] if T is not None else [])
+    if min(sizes) < 1:
+        raise ValueError("every size of a co-action unit must be positive (and layer_unit_coef not empty), got "
+                         "feed_feature_dim=%d, layer_unit_coef=%r, order=%d, T=%r" % (E, coefs, order, T))
+    if max(can_widths(E, coefs)) > CAN_MAX_W or len(coefs) > CAN_MAX_LAYERS or order > CAN_MAX_ORDER:
+        raise NotImplementedError(
+            "CAN kernels cover layer widths feed_feature_dim * coef <= %d, at most %d layers and order <= %d; got "
+            "feed_feature_dim=%d, layer_unit_coef=%r, order=%d" % (CAN_MAX_W, CAN_MAX_LAYERS, CAN_MAX_ORDER, E, coefs, order))
+    if T is not None and can_lds_bytes(T, E, coefs, order) > _MIND_LDS_CAP:
+        raise NotImplementedError(
+            "the CAN co-action holds one example in LDS: 4 (2 T E + Pv + T sum (w_l|1) + 2 T (wmax|1) + T + 256) <= %d "
+            "bytes; got %d at T=%d, feed_feature_dim=%d, layer_unit_coef=%r, order=%d"
+            % (_MIND_LDS_CAP, can_lds_bytes(T, E, coefs, order), T, E, coefs, order))
+
+
+def _can_args(feed, inds, iid, fid, coefs, order, act, padding_index):
+    _table(feed, "feed"); _i64(iid, "iid"); _i64(fid, "fid")
+    inds = list(inds)
+    if len(inds) not in (1, int(order)):
+        raise ValueError("co-action takes one induction table per order (%d) or one shared table; got %d"
+                         % (order, len(inds)))
+    for t in inds:
+        _table(t, "induction table")
+    if iid.dim() != 1 or fid.dim() != 2 or fid.shape[0] != iid.shape[0]:
+        raise ValueError("co-action takes iid [B] and fid [B,T]; got %s, %s" % (tuple(iid.shape), tuple(fid.shape)))
+    Vf, E = feed.shape
+    Vi, P = inds[0].shape
+    B, T = fid.shape
+    if any(tuple(t.shape) != (Vi, P) or t.stride(0) != inds[0].stride(0) for t in inds) or P != can_row_floats(E, coefs):
+        raise ValueError("co-action: every induction table must be [Vi, P = %d] with one row stride for feed width %d "
+                         "and layer_unit_coef %r; got %s" % (can_row_floats(E, coefs), E, list(coefs),
+                                                             [tuple(t.shape) for t in inds]))
+    if act not in (ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH):
+        raise ValueError("co-action: unknown activation code %r" % (act,))
+    if T < 1:
+        raise ValueError("co-action: fid must have at least one position, got %s" % (tuple(fid.shape),))
+    can_check_shape(E, coefs, int(order), T=T)
+    shared = int(len(inds) == 1 and int(order) > 1)
+    La = min(len(coefs), int(order))
+    return [_ptr(feed), feed.stride(0), Vf, E, _ptr_array(inds), shared, inds[0].stride(0), Vi, len(coefs),
+            _ints(coefs), int(order), int(act), _ptr(iid), _ptr(fid), B, T, int(padding_index)], \
+        (B, T, E, P, can_widths(E, coefs)[La])
+
+
+def can_fwd(feed, inds, iid, fid, coefs, order, act, padding_index=0, pooled=False, oob=None):
+    """CoActionUnit over both lookups in one launch: feed table [Vf,E], ``inds`` the induction tables [Vi,P] (one per
+    order, or one shared), iid [B], fid [B,T] -> out [order,B,T,Eo], or with ``pooled`` its sum over orders and positions
+    [B,Eo].  min(len(coefs), order) layers are applied; a position whose feed id is ``padding_index`` is zero."""
+    args, (B, T, E, P, Eo) = _can_args(feed, inds, iid, fid, coefs, order, act, padding_index)
+    shape = (B, Eo) if pooled else (int(order), B, T, Eo)
+    res = torch.empty(shape, dtype=torch.float32, device=feed.device)
+    if B > 0:                                            # an empty batch answers from the sizes alone
+        check(lib.rec_can_fwd_f32(*args, None if pooled else _ptr(res), _ptr(res) if pooled else None, _ptr(oob),
+                                  _stream()), "rec_can_fwd_f32")
+    return res
+
+
+def can_bwd(feed, inds, iid, fid, coefs, order, act, g, padding_index=0, pooled=False):
+    """-> (gfeed [B,T,E], the IndexedSlices values of the feed lookups summed over the orders, gind [order,B,P], those of
+    each order's induction lookup) from gout [order,B,T,Eo] or, with ``pooled``, gpool [B,Eo]; the forward is run again."""
+    args, (B, T, E, P, Eo) = _can_args(feed, inds, iid, fid, coefs, order, act, padding_index)
+    shape = (B, Eo) if pooled else (int(order), B, T, Eo)
+    if tuple(_f32(g, "g").shape) != shape:
+        raise ValueError("the upstream gradient must be %s, got %s" % (shape, tuple(g.shape)))
+    gfeed = torch.empty((B, T, E), dtype=torch.float32, device=feed.device)
+    gind = torch.empty((int(order), B, P), dtype=torch.float32, device=feed.device)
+    if B > 0:
+        check(lib.rec_can_bwd_f32(*args, None if pooled else _ptr(g), _ptr(g) if pooled else None, _ptr(gfeed),
+                                  _ptr(gind), _stream()), "rec_can_bwd_f32")
+    return gfeed, gind

@@ -160,7 +160,9 @@ int rec_dedup_plan_i64(const int64_t* ids, int64_t n, int64_t V, int64_t* uniq_i
                        void* stream);
 /* out[u,:] = sum over s in [seg_start[u], seg_start[u+1]) of vals[perm[s] / row_div, :]   for u in [0,n).
  * row_div = 1 for per-lookup values; row_div = F broadcasts a per-example value (the w table, whose
- * per-lookup gradient is gz[b]). */
+ * per-lookup gradient is gz[b]).  E <= 256 goes through chunk partials (long runs are finished by a whole workgroup);
+ * E > 256 (CAN's induction rows) takes one workgroup per output row, a thread per column and every 256th after it, the
+ * rows of a run added in sorted order, and does not touch the workspace. */
 /* Same outputs as rec_dedup_plan_i64 for ids that arrive as n_lists ascending, duplicate-free lists laid end to end
  * (list_counts [n_lists], int64, on the device; their sum must be n): the owner-side union of what P requesters
  * send after de-duplicating their own batches.  Rank merge by binary search instead of a sort; rows of one id are
@@ -1123,6 +1125,56 @@ int rec_comirec_select_fwd_f32(const float* embed, int64_t ld, int64_t V, int E,
 int rec_comirec_select_bwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* items, int64_t B,
                                int Ns, const float* m, int K, const int32_t* chosen, const float* ginner,
                                const float* gloss, const float* gsel, float* gm, float* gitems, void* stream);
+
+/* ---- CAN co-action (CoActionUnit, 7.SIM/CustomLayers.py:285-378; csrc/can.hip): for every example the target item's
+ * induction row IS the weights and biases of a small MLP, which is applied to every feed feature of the example raised
+ * to the powers 1..O.  Both lookups happen inside the kernel.
+ *   feed [Vf, E], row stride ld_f >= E;   ind_host: O pointers (a HOST array of device pointers; one pointer with
+ *   shared = 1, read by every order) to tables [Vi, P], row stride ld_i >= P;   iid int64 [B];   fid int64 [B, T].
+ * An id outside its table reads as a zero row and sets *oob_flag (may be NULL).  widths[0] = E, widths[l] = E c_l with
+ * c_1..c_n = coefs_host (n = n_layers); P = sum_{l<n} (widths[l] widths[l+1] + widths[l+1]); a row holds layer after
+ * layer, W_l row-major [widths[l], widths[l+1]] and then B_l.  Per example b, order o = 1..O and position t:
+ *   x_0 = feed[fid[b,t]] ** o (elementwise, by repeated multiplication)        v = ind_o[iid[b]]
+ *   x_{l+1} = act(x_l W_l + B_l)  for l < La                                  act: REC_ACT_NONE / RELU / SIGMOID / TANH
+ *   out[o-1,b,t,:] = (fid[b,t] == padding_index) ? 0 : x_La                    out [O, B, T, Eo], Eo = widths[La]
+ * La = min(n_layers, order) is the number of layers APPLIED: the reference zips its layers with a list of `order`
+ * activations and so silently drops the layers beyond `order`; that is kept.  The row still has all P floats; the tail
+ * no layer reads gets a zero gradient.  Padding may sit anywhere; a padded position still goes through the MLP in the
+ * reference and is zeroed afterwards, so it contributes nothing to any gradient.
+ * Two output modes, exactly one of out and pool is non-NULL:
+ *   out  [O, B, T, Eo]  each order a contiguous [B, T, Eo], as the reference's list;
+ *   pool [B, Eo] = sum_o sum_t out[o,b,t,:]  (concat(axis=1) + reduce_sum(axis=1) of CANLayer), added in a fixed order:
+ *                 per order min(16, 256 / Eo) interleaved partial sums over t, these in ascending order onto the running
+ *                 sum, orders ascending; out is never written.
+ * The backward takes gout [O, B, T, Eo] or gpool [B, Eo] (exactly one non-NULL), runs the forward again (nothing is
+ * saved) and writes, never adds:
+ *   gfeed [B, T, E] = sum_o o feed^(o-1) dx_0(o), feed^0 = 1 exactly; orders ascending; zero at padded positions;
+ *   gind [O, B, P]: the IndexedSlices values of each order's induction lookup: dW_l = sum_t x_l^T dz_l and
+ *                   dB_l = sum_t dz_l added in position order, the tail beyond the La applied layers written as zeros.
+ * One workgroup of 256 threads owns an example through all orders: the feed rows are read once, each induction row once
+ * per (example, order), coalesced, into LDS (W_l rows padded to an odd stride); the products are f32 FMA chains out of
+ * LDS, four positions per thread forward; dW is accumulated in registers over the positions and each gind row is
+ * written once.  Supported, the same both ways: every widths[l] <= REC_AFM_MAX_E (64), 1 <= n_layers <= 4,
+ * 1 <= order <= 4, T >= 1, 0 <= B < 2^31 and one example's working set within the 150 KiB launch cap:
+ *   4 (2 T E + Pv + T sum_{l<=La} (widths[l]|1) + 2 T (wmax|1) + T + 256) <= 153600                (x|1: x made odd)
+ *   Pv = sum_{l<La} (widths[l] (widths[l+1]|1) + widths[l+1]),  wmax = max_{l<=La} widths[l]
+ * e.g. T <= 276 at E = 16, coefs (1,1,1), order 3 (Pv = 864) and T <= 65 at E = 64, coefs (1,1), order 2 (Pv = 8448).
+ * rec_can_lds_bytes: the left-hand side, the dynamic LDS of a backward launch; 0: invalid or unsupported.  No workspace.
+ *
+ * Both entry points only enqueue (no allocation, no host synchronisation: graph-capturable) and use no float atomics:
+ * bit-identical results run to run.  Return codes, answered in this order: a size below 1 (B below 0, a coefficient
+ * below 1, coefs_host NULL): -1; a shape outside the limits: -2, from the sizes alone; ld_f < E, ld_i < P, Vf < 1,
+ * Vi < 1, an unknown act, a NULL pointer other than oob_flag, or not exactly one of out / pool (gout / gpool): -1; then
+ * B == 0: 0, nothing is launched or written. */
+size_t rec_can_lds_bytes(int T, int E, int n_layers, const int* coefs_host, int order);
+int rec_can_fwd_f32(const float* feed, int64_t ld_f, int64_t Vf, int E, const float* const* ind_host, int shared,
+                    int64_t ld_i, int64_t Vi, int n_layers, const int* coefs_host, int order, int act,
+                    const int64_t* iid, const int64_t* fid, int64_t B, int T, int64_t padding_index, float* out,
+                    float* pool, int* oob_flag, void* stream);
+int rec_can_bwd_f32(const float* feed, int64_t ld_f, int64_t Vf, int E, const float* const* ind_host, int shared,
+                    int64_t ld_i, int64_t Vi, int n_layers, const int* coefs_host, int order, int act,
+                    const int64_t* iid, const int64_t* fid, int64_t B, int T, int64_t padding_index, const float* gout,
+                    const float* gpool, float* gfeed, float* gind, void* stream);
 
 #ifdef __cplusplus
 }
