@@ -28,11 +28,14 @@
 // run to run; no host synchronisation.
 // Contraction is off in this file as in masknet.hip: a LayerNorm over ONE element (E = 1) must return exactly zero
 // gradients, which g gamma - mean(g gamma) only does when both are the same rounded product.
+// Shared with the other tile kernels, in tile_ops.h: the row pass out of an LDS operand (TileOps), the batch slices of
+// the per-field weight-gradient launch, the workspace carving and the split-K weight-gradient GEMM; the MFMA tile itself
+// is mfma_tile.h.
 #include <math.h>
 #include "common.h"
 
 #pragma clang fp contract(off)
-#include "mfma_tile.h"
+#include "tile_ops.h"
 
 namespace {
 
@@ -120,14 +123,7 @@ __device__ __forceinline__ float cn_dot(const float* src, int col0, const float*
   return acc;
 }
 
-// rows of consecutive columns out of a k-major LDS operand: dst[(r0 + row) D + c0 + c] = src[c][row], c < nc
-__device__ __forceinline__ void cn_rows_out(float* __restrict__ dst, const float* src, int64_t r0, int64_t B, int D,
-                                            int c0, int nc, int tid) {
-  for (int i = tid; i < MB_T * nc; i += CN_NTHR) {
-    const int row = i / nc, c = i - row * nc;
-    if (r0 + row < B) dst[(r0 + row) * D + c0 + c] = src[c * MB_LD + row];
-  }
-}
+using Tile = TileOps<MB_T, MB_LD, CN_NTHR>;
 
 // floats of LDS: forward  xs / us [even(D)][33] | hs [128][33]
 //                backward two tiles [even(D)][33] | chunk [128][33]
@@ -214,7 +210,7 @@ __global__ __launch_bounds__(CN_NTHR) void contextnet_block_fwd_kernel(
         const int f = (c0 + c) / E, j = c0 + c - f * E;
         xs[(c0 + c) * MB_LD + b] = cn_dot<false>(hs, c0, W2, f, j, E, b) + xs[(c0 + c) * MB_LD + b];
       }
-      if (save_a) cn_rows_out(save_a, hs, r0, B, D, c0, nc, tid);
+      if (save_a) Tile::rows_out(save_a, hs, r0, B, D, c0, nc, tid);
       __syncthreads();                                        // hs is rewritten by the next pass
     } else {
       for (int c = g; c < nc; c += CN_G) {
@@ -325,7 +321,7 @@ __global__ __launch_bounds__(CN_NTHR) void contextnet_block_bwd_kernel(
   const int fpp = MB_HC / E;
   for (int f0 = 0; f0 < F; f0 += fpp) {
     const int c0 = f0 * E, nc = (F - f0 < fpp ? F - f0 : fpp) * E;
-    cn_rows_out(ws_dr, ga + c0 * MB_LD, r0, B, D, c0, nc, tid);
+    Tile::rows_out(ws_dr, ga + c0 * MB_LD, r0, B, D, c0, nc, tid);
     if (pointwise) {
       for (int c = g; c < nc; c += CN_G) {                    // da = (dr W2^T) (.) [a > 0]
         const int f = (c0 + c) / E, e = c0 + c - f * E;
@@ -337,7 +333,7 @@ __global__ __launch_bounds__(CN_NTHR) void contextnet_block_bwd_kernel(
         const int f = (c0 + c) / E, e = c0 + c - f * E;
         ga[(c0 + c) * MB_LD + b] = ga[(c0 + c) * MB_LD + b] + cn_dot<true>(cs, c0, W1, f, e, E, b);
       }
-      cn_rows_out(ws_da, cs, r0, B, D, c0, nc, tid);
+      Tile::rows_out(ws_da, cs, r0, B, D, c0, nc, tid);
       __syncthreads();
     } else {
       for (int c = g; c < nc; c += CN_G) {                    // du = dr W1^T
@@ -416,7 +412,9 @@ __global__ __launch_bounds__(CN_NTHR) void contextnet_block_bwd_kernel(
 
 // Per-field weight gradients, all of them in one launch: workgroup (f and a block of 256 outputs, q, s) adds the examples
 // of batch slice s, in order, into part[s][q][f] [E][E] = A_q[:, f]^T G_q[:, f], one output per thread; the slices are
-// added by rec_slot_sum in slice order.
+// added by rec_slot_sum in slice order.  It is small_dw_kernel (tile_ops.h) with M = N = E and stays a kernel of its own:
+// through the shared kernel it took 240 us against 170 at the default shape, most likely because it stages A and G in
+// ONE loop with both loads in flight together where the shared kernel waits for each in turn.
 __global__ __launch_bounds__(CN_NTHR) void contextnet_field_dw_kernel(const float* __restrict__ A0,
                                                                       const float* __restrict__ G0,
                                                                       const float* __restrict__ A1,
@@ -454,31 +452,23 @@ static int cn_shape(int64_t B, int F, int E, int R, int pointwise) {
   return REC_OK;
 }
 
-// slices of the per-field weight gradients over the batch: at most 16, at least 256 examples each
-static int cn_field_split(int64_t B) {
-  const int64_t s = B / 256;
-  return s < 1 ? 1 : (s > 16 ? 16 : (int)s);
-}
-
 struct CnWs {
   size_t dr, da, u, dm, dh, slots, part, gemm, total;          // offsets in floats
 };
 static CnWs cn_ws(int64_t B, int F, int E, int H, int pointwise) {
   CnWs w{};
   const size_t b = (size_t)B, tiles = (size_t)ceil_div64(B, MB_T), D = (size_t)F * E;
-  auto r4 = [](size_t v) { return (v + 3) & ~(size_t)3; };
-  size_t at = 0;
-  w.dr = at; at += r4(b * D);
-  w.da = at; at += pointwise ? r4(b * D) : 0;
-  w.u = at; at += r4(b * D);
-  w.dm = at; at += r4(b * D);
-  w.dh = at; at += r4(b * H);
-  w.slots = at; at += r4(tiles * (3 * D + (size_t)H));
-  w.part = at; at += r4((size_t)cn_field_split(B) * (pointwise ? 2 : 1) * D * E);
-  w.gemm = at;
-  const size_t g1 = (size_t)mb_split(B, (int)D, H) * D * H, g2 = (size_t)mb_split(B, H, (int)D) * H * D;
-  at += r4(g1 > g2 ? g1 : g2);
-  w.total = at;
+  WsCarve c;
+  w.dr = c.take(b * D);
+  w.da = c.take(pointwise ? b * D : 0);
+  w.u = c.take(b * D);
+  w.dm = c.take(b * D);
+  w.dh = c.take(b * H);
+  w.slots = c.take(tiles * (3 * D + (size_t)H));
+  w.part = c.take((size_t)mb_small_split(B) * (pointwise ? 2 : 1) * D * E);
+  const size_t g1 = mb_dw_gemm_floats(B, (int)D, H), g2 = mb_dw_gemm_floats(B, H, (int)D);
+  w.gemm = c.take(g1 > g2 ? g1 : g2);
+  w.total = c.at;
   return w;
 }
 
@@ -561,7 +551,7 @@ extern "C" int rec_contextnet_block_bwd_f32(const float* x, const float* Wa, con
   if (int rc = rec_slot_sum(REC_SLOTS_WAVE, 3 * D + H, tiles, slots, {{dgamma, dbeta, dbb, dba}, {D, D, D, H}}, st))
     return rc;
   // pointwise: dW1_f = u_f^T da_f, dW2_f = a_f^T dr_f; single: dW1_f = u_f^T dr_f
-  const int S = cn_field_split(B), nq = pointwise ? 2 : 1;
+  const int S = mb_small_split(B), nq = pointwise ? 2 : 1;
   const int64_t per = ceil_div64(ceil_div64(B, S), CN_DW_ROWS) * CN_DW_ROWS;
   const int nblk = (E * E + CN_NTHR - 1) / CN_NTHR;
   hipLaunchKernelGGL(contextnet_field_dw_kernel, dim3(F * nblk, nq, S), dim3(CN_NTHR), 0, st, u, pointwise ? da : dr, a,
@@ -569,10 +559,6 @@ extern "C" int rec_contextnet_block_bwd_f32(const float* x, const float* Wa, con
   REC_LAUNCH_CHECK();
   if (int rc = rec_slot_sum(REC_SLOTS_SERIAL, nq * D * E, S, part, {{dW1, dW2}, {D * E, pointwise ? D * E : 0}}, st))
     return rc;
-  // dW = A^T G with A, G stored [B, .]: transA, K = B
-  if (int rc = rec_gemm_f32(1, 0, D, H, B, x, D, dh, H, dWa, H, REC_EPI_NONE, nullptr, nullptr, 0, nullptr, 0,
-                            mb_split(B, D, H), gws, nullptr, stream))
-    return rc;
-  return rec_gemm_f32(1, 0, H, D, B, h, H, dm, D, dWb, D, REC_EPI_NONE, nullptr, nullptr, 0, nullptr, 0,
-                      mb_split(B, H, D), gws, nullptr, stream);
+  if (int rc = mb_dw_gemm(D, H, B, x, dh, dWa, gws, stream)) return rc;        // dWa = x^T dh
+  return mb_dw_gemm(H, D, B, h, dm, dWb, gws, stream);                           // dWb = h^T dm
 }

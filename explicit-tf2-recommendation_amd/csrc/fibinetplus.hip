@@ -37,11 +37,14 @@
 // No float atomics and no value with two writers: bit-identical results run to run; no host synchronisation.
 // Contraction is off in this file as in masknet.hip: a norm over ONE element must return exactly beta and exactly zero
 // gradients, which x - mean and g gamma - mean(g gamma) only do when both sides are the same rounded value.
+// Shared with the other tile kernels, in tile_ops.h: the row / column passes over an LDS operand (TileOps, here on the
+// 16-example tile), the batch slices of the weight-gradient launch, the workspace carving and the split-K weight-gradient
+// GEMM.  The bilinear weight gradients sum over field pairs inside the accumulation and keep a kernel of their own.
 #include <math.h>
 #include "common.h"
 
 #pragma clang fp contract(off)
-#include "mfma_tile.h"
+#include "tile_ops.h"
 
 namespace {
 
@@ -372,30 +375,7 @@ __device__ __forceinline__ void fp_ln_bwd(float* Gd, const float* XH, const floa
   __syncthreads();
 }
 
-// rows of consecutive columns: dst[(r0 + row) ldd + c] = src[c][row], c < n
-__device__ __forceinline__ void fp_rows_out(float* __restrict__ dst, int64_t ldd, const float* src, int n, int64_t r0,
-                                            int64_t B, int tid) {
-  for (int i = tid; i < FP_T * n; i += FP_NTHR) {
-    const int row = i / n, c = i - row * n;
-    if (r0 + row < B) dst[(r0 + row) * ldd + c] = src[c * FP_LD + row];
-  }
-}
-// dst[c][row] = src[(r0 + row) lds + c], zero beyond the batch
-__device__ __forceinline__ void fp_rows_in(float* dst, const float* __restrict__ src, int64_t lds_, int n, int64_t r0,
-                                           int64_t B, int tid) {
-  for (int i = tid; i < FP_T * n; i += FP_NTHR) {
-    const int row = i / n, c = i - row * n;
-    dst[c * FP_LD + row] = r0 + row < B ? src[(r0 + row) * lds_ + c] : 0.f;
-  }
-}
-// column sums of the tile, rows in order: out[c] = sum_row A[c][row] (* Bm[c][row])
-__device__ __forceinline__ void fp_colsum(float* __restrict__ out, const float* A, const float* Bm, int n, int tid) {
-  for (int c = tid; c < n; c += FP_NTHR) {
-    float s = 0.f;
-    for (int r = 0; r < FP_T; ++r) s += Bm ? A[c * FP_LD + r] * Bm[c * FP_LD + r] : A[c * FP_LD + r];
-    out[c] = s;
-  }
-}
+using Tile = TileOps<FP_T, FP_LD, FP_NTHR>;
 
 struct FpFwdArgs {
   const float *x, *W, *Wr, *br, *gq, *bq, *S0, *b0, *g0, *be0, *S1, *b1, *g1, *be1;
@@ -411,11 +391,12 @@ __global__ __launch_bounds__(FP_NTHR) void fibinetplus_block_fwd_kernel(FpFwdArg
   float* r2 = r1 + fp_r1(d) * FP_LD;             // [max(P, mid)]: p, then z_0 / h
   float* sc = r2 + fp_r2(d) * FP_LD;             // [16][16]
   int* pij = reinterpret_cast<int*>(sc + FP_G * FP_T);
-  const int64_t r0 = (int64_t)blockIdx.x * FP_T, ldo = O + D;
+  const int64_t r0 = (int64_t)blockIdx.x * FP_T;
+  const int ldo = O + D;
   const bool mine = r0 + b < B;
 
   fp_pair_table(pij, F, P, tid);
-  fp_rows_in(xs, a.x, D, D, r0, B, tid);
+  Tile::rows_in(xs, a.x, r0, B, D, 0, D, tid);
   __syncthreads();
 
   // bilinear+: one scalar per pair
@@ -440,7 +421,7 @@ __global__ __launch_bounds__(FP_NTHR) void fibinetplus_block_fwd_kernel(FpFwdArg
     r2[t * FP_LD + b] = acc;
   }
   __syncthreads();
-  if (a.p) fp_rows_out(a.p, P, r2, P, r0, B, tid);
+  if (a.p) Tile::rows_out(a.p, r2, r0, B, P, 0, P, tid);
   for (int o = g; o < O; o += FP_G) r1[o * FP_LD + b] = fp_dot(r2, P, a.Wr, O, o, b) + a.br[o];
   __syncthreads();
   {
@@ -472,18 +453,18 @@ __global__ __launch_bounds__(FP_NTHR) void fibinetplus_block_fwd_kernel(FpFwdArg
     r1[(f * 2 * G + G + gg) * FP_LD + b] = m;
   }
   __syncthreads();
-  if (a.s) fp_rows_out(a.s, S2, r1, S2, r0, B, tid);
+  if (a.s) Tile::rows_out(a.s, r1, r0, B, S2, 0, S2, tid);
   for (int m = g; m < mid; m += FP_G) r2[m * FP_LD + b] = fp_dot(r1, S2, a.S0, mid, m, b) + a.b0[m];
   __syncthreads();
   {
     const float rs = fp_ln(r2, mid, sc, b, g);
     if (a.rstd && mine && g == 0) a.rstd[(r0 + b) * 3 + 1] = rs;
   }
-  if (a.xhat0) fp_rows_out(a.xhat0, mid, r2, mid, r0, B, tid);
+  if (a.xhat0) Tile::rows_out(a.xhat0, r2, r0, B, mid, 0, mid, tid);
   __syncthreads();
   for (int m = g; m < mid; m += FP_G) r2[m * FP_LD + b] = fmaxf(r2[m * FP_LD + b] * a.g0[m] + a.be0[m], 0.f);
   __syncthreads();
-  if (a.h) fp_rows_out(a.h, mid, r2, mid, r0, B, tid);
+  if (a.h) Tile::rows_out(a.h, r2, r0, B, mid, 0, mid, tid);
   for (int c = g; c < D; c += FP_G) r1[c * FP_LD + b] = fp_dot(r2, mid, a.S1, D, c, b) + a.b1[c];
   __syncthreads();
   {
@@ -516,7 +497,8 @@ __global__ __launch_bounds__(FP_NTHR) void fibinetplus_block_bwd_kernel(FpBwdArg
   float* rc = rb + fp_rb(d) * FP_LD;             // [mid]: dy0 -> dz0
   float* sc = rc + mid * FP_LD;
   int* pij = reinterpret_cast<int*>(sc + FP_G * FP_T);
-  const int64_t r0 = (int64_t)blockIdx.x * FP_T, ldo = O + D;
+  const int64_t r0 = (int64_t)blockIdx.x * FP_T;
+  const int ldo = O + D;
   const bool mine = r0 + b < B;
   float* __restrict__ sa = a.slot_a + (int64_t)blockIdx.x * 3 * (O + mid);
   float* __restrict__ sb = a.slot_b + (int64_t)blockIdx.x * 3 * D;
@@ -524,9 +506,9 @@ __global__ __launch_bounds__(FP_NTHR) void fibinetplus_block_bwd_kernel(FpBwdArg
               rs1 = mine ? a.rstd[(r0 + b) * 3 + 2] : 0.f;
 
   fp_pair_table(pij, F, P, tid);
-  fp_rows_in(xs, a.x, D, D, r0, B, tid);
-  fp_rows_in(ra, a.dout + O, ldo, D, r0, B, tid);
-  fp_rows_in(rb, a.xhat1, D, D, r0, B, tid);
+  Tile::rows_in(xs, a.x, r0, B, D, 0, D, tid);
+  Tile::rows_in(ra, a.dout + O, r0, B, ldo, 0, D, tid);
+  Tile::rows_in(rb, a.xhat1, r0, B, D, 0, D, tid);
   __syncthreads();
 
   // v = x (.) A, A = relu(xhat1 g1 + be1): dy1 = dv x [A > 0]
@@ -535,15 +517,15 @@ __global__ __launch_bounds__(FP_NTHR) void fibinetplus_block_bwd_kernel(FpBwdArg
     ra[c * FP_LD + b] = pre > 0.f ? ra[c * FP_LD + b] * xs[c * FP_LD + b] : 0.f;
   }
   __syncthreads();
-  fp_colsum(sb, ra, rb, D, tid);
-  fp_colsum(sb + D, ra, nullptr, D, tid);
+  Tile::col_sums(sb, ra, D, tid, rb);
+  Tile::col_sums(sb + D, ra, D, tid);
   fp_ln_bwd(ra, rb, a.g1, D, rs1, sc, b, g);
-  fp_rows_out(a.ws_dz1, D, ra, D, r0, B, tid);
-  fp_colsum(sb + 2 * D, ra, nullptr, D, tid);
+  Tile::rows_out(a.ws_dz1, ra, r0, B, D, 0, D, tid);
+  Tile::col_sums(sb + 2 * D, ra, D, tid);
   __syncthreads();                                             // rb (xhat1) is rewritten
 
   // h = relu(xhat0 g0 + be0): dy0 = (dz1 S1^T) [h > 0]
-  fp_rows_in(rb, a.xhat0, mid, mid, r0, B, tid);
+  Tile::rows_in(rb, a.xhat0, r0, B, mid, 0, mid, tid);
   __syncthreads();
   for (int m = g; m < mid; m += FP_G) {
     const float pre = rb[m * FP_LD + b] * a.g0[m] + a.be0[m];
@@ -551,25 +533,25 @@ __global__ __launch_bounds__(FP_NTHR) void fibinetplus_block_bwd_kernel(FpBwdArg
     rc[m * FP_LD + b] = pre > 0.f ? dh : 0.f;
   }
   __syncthreads();
-  fp_colsum(sa + 3 * O, rc, rb, mid, tid);
-  fp_colsum(sa + 3 * O + mid, rc, nullptr, mid, tid);
+  Tile::col_sums(sa + 3 * O, rc, mid, tid, rb);
+  Tile::col_sums(sa + 3 * O + mid, rc, mid, tid);
   fp_ln_bwd(rc, rb, a.g0, mid, rs0, sc, b, g);
-  fp_rows_out(a.ws_dz0, mid, rc, mid, r0, B, tid);
-  fp_colsum(sa + 3 * O + 2 * mid, rc, nullptr, mid, tid);
+  Tile::rows_out(a.ws_dz0, rc, r0, B, mid, 0, mid, tid);
+  Tile::col_sums(sa + 3 * O + 2 * mid, rc, mid, tid);
   __syncthreads();                                             // ra (dz1) and rb (xhat0) are rewritten
 
   // q = LN(p Wr + br): dzq, dp = dzq Wr^T
-  fp_rows_in(ra, a.dout, ldo, O, r0, B, tid);
-  fp_rows_in(rb, a.xhatq, O, O, r0, B, tid);
+  Tile::rows_in(ra, a.dout, r0, B, ldo, 0, O, tid);
+  Tile::rows_in(rb, a.xhatq, r0, B, O, 0, O, tid);
   __syncthreads();
-  fp_colsum(sa, ra, rb, O, tid);
-  fp_colsum(sa + O, ra, nullptr, O, tid);
+  Tile::col_sums(sa, ra, O, tid, rb);
+  Tile::col_sums(sa + O, ra, O, tid);
   fp_ln_bwd(ra, rb, a.gq, O, rsq, sc, b, g);
-  fp_rows_out(a.ws_dzq, O, ra, O, r0, B, tid);
-  fp_colsum(sa + 2 * O, ra, nullptr, O, tid);
+  Tile::rows_out(a.ws_dzq, ra, r0, B, O, 0, O, tid);
+  Tile::col_sums(sa + 2 * O, ra, O, tid);
   for (int t = g; t < P; t += FP_G) rb[t * FP_LD + b] = fp_dot_t(ra, O, a.Wr, O, t, b);
   __syncthreads();
-  fp_rows_out(a.ws_dp, P, rb, P, r0, B, tid);
+  Tile::rows_out(a.ws_dp, rb, r0, B, P, 0, P, tid);
 
   // dx: the direct part dv (.) A in rows, then every thread adds the squeeze and the bilinear parts of its columns
   for (int i = tid; i < FP_T * D; i += FP_NTHR) {
@@ -626,7 +608,7 @@ __global__ __launch_bounds__(FP_NTHR) void fibinetplus_block_bwd_kernel(FpBwdArg
     ra[c * FP_LD + b] = val;
   }
   __syncthreads();
-  fp_rows_out(a.dx, D, ra, D, r0, B, tid);
+  Tile::rows_out(a.dx, ra, r0, B, D, 0, D, tid);
 }
 
 // Bilinear weight gradients, all of them in one launch: workgroup (matrix wi and a block of 256 outputs, slice s) adds,
@@ -689,12 +671,6 @@ static int fp_shape(int64_t B, const FpDims& d) {
 }
 static int fp_num_weights(const FpDims& d) { return d.type == 0 ? 1 : (d.type == 1 ? d.F - 1 : fp_pairs(d.F)); }
 
-// slices of the bilinear weight gradients over the batch: at most 16, at least 256 examples each
-static int fp_dw_split(int64_t B) {
-  const int64_t s = B / 256;
-  return s < 1 ? 1 : (s > 16 ? 16 : (int)s);
-}
-
 struct FpWs {
   size_t dz1, dz0, dzq, dp, slot_a, slot_b, part, gemm, total;   // offsets in floats
 };
@@ -702,20 +678,18 @@ static FpWs fp_ws(int64_t B, const FpDims& d) {
   FpWs w{};
   const size_t b = (size_t)B, tiles = (size_t)ceil_div64(B, FP_T), D = (size_t)d.F * d.E, P = (size_t)fp_pairs(d.F);
   const size_t mid = (size_t)d.mid, O = (size_t)d.O, S2 = (size_t)2 * d.G * d.F;
-  auto r4 = [](size_t v) { return (v + 3) & ~(size_t)3; };
-  size_t at = 0;
-  w.dz1 = at; at += r4(b * D);
-  w.dz0 = at; at += r4(b * mid);
-  w.dzq = at; at += r4(b * O);
-  w.dp = at; at += r4(b * P);
-  w.slot_a = at; at += r4(tiles * 3 * (O + mid));
-  w.slot_b = at; at += r4(tiles * 3 * D);
-  w.part = at; at += r4((size_t)fp_dw_split(B) * fp_num_weights(d) * d.E * d.E);
-  w.gemm = at;
-  const size_t g1 = (size_t)mb_split(B, (int)P, d.O) * P * O, g2 = (size_t)mb_split(B, (int)S2, d.mid) * S2 * mid,
-               g3 = (size_t)mb_split(B, d.mid, (int)D) * mid * D;
-  at += r4(g1 > g2 ? (g1 > g3 ? g1 : g3) : (g2 > g3 ? g2 : g3));
-  w.total = at;
+  WsCarve c;
+  w.dz1 = c.take(b * D);
+  w.dz0 = c.take(b * mid);
+  w.dzq = c.take(b * O);
+  w.dp = c.take(b * P);
+  w.slot_a = c.take(tiles * 3 * (O + mid));
+  w.slot_b = c.take(tiles * 3 * D);
+  w.part = c.take((size_t)mb_small_split(B) * fp_num_weights(d) * d.E * d.E);
+  const size_t g1 = mb_dw_gemm_floats(B, (int)P, d.O), g2 = mb_dw_gemm_floats(B, (int)S2, d.mid),
+               g3 = mb_dw_gemm_floats(B, d.mid, (int)D);
+  w.gemm = c.take(g1 > g2 ? (g1 > g3 ? g1 : g3) : (g2 > g3 ? g2 : g3));
+  w.total = c.at;
   return w;
 }
 
@@ -859,20 +833,14 @@ extern "C" int rec_fibinetplus_block_bwd_f32(const float* x, const float* W, con
                             {{dgamma_q, dbeta_q, dbr, dgamma0, dbeta0, db0}, {O, O, O, mid, mid, mid}}, st))
     return rc;
   if (int rc = rec_slot_sum(REC_SLOTS_WAVE, 3 * D, tiles, slot_b, {{dgamma1, dbeta1, db1}, {D, D, D}}, st)) return rc;
-  const int S = fp_dw_split(B), nW = fp_num_weights(d);
+  const int S = mb_small_split(B), nW = fp_num_weights(d);
   const int64_t per = ceil_div64(ceil_div64(B, S), FP_DW_ROWS) * FP_DW_ROWS;
   const int nblk = (E * E + FP_NTHR - 1) / FP_NTHR;
   hipLaunchKernelGGL(fibinetplus_dw_kernel, dim3(nW * nblk, S), dim3(FP_NTHR), 0, st, x, dp, B, F, E, type, nW, nblk,
                      per, part);
   REC_LAUNCH_CHECK();
   if (int rc = rec_slot_sum(REC_SLOTS_SERIAL, nW * E * E, S, part, {{dW}, {nW * E * E}}, st)) return rc;
-  // dWr = p^T dzq, dS0 = s^T dz0, dS1 = h^T dz1 with the operands stored [B, .]: transA, K = B
-  if (int rc = rec_gemm_f32(1, 0, P, O, B, p, P, dzq, O, dWr, O, REC_EPI_NONE, nullptr, nullptr, 0, nullptr, 0,
-                            mb_split(B, P, O), gws, nullptr, stream))
-    return rc;
-  if (int rc = rec_gemm_f32(1, 0, S2, mid, B, s, S2, dz0, mid, dS0, mid, REC_EPI_NONE, nullptr, nullptr, 0, nullptr, 0,
-                            mb_split(B, S2, mid), gws, nullptr, stream))
-    return rc;
-  return rec_gemm_f32(1, 0, mid, D, B, h, mid, dz1, D, dS1, D, REC_EPI_NONE, nullptr, nullptr, 0, nullptr, 0,
-                      mb_split(B, mid, D), gws, nullptr, stream);
+  if (int rc = mb_dw_gemm(P, O, B, p, dzq, dWr, gws, stream)) return rc;         // dWr = p^T dzq
+  if (int rc = mb_dw_gemm(S2, mid, B, s, dz0, dS0, gws, stream)) return rc;      // dS0 = s^T dz0
+  return mb_dw_gemm(mid, D, B, h, dz1, dS1, gws, stream);                        // dS1 = h^T dz1
 }

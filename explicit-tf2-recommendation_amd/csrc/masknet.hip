@@ -25,11 +25,13 @@
 // Contraction is off in this file: the LayerNorm backward forms g gamma twice, for the sums and for the result, and a
 // LayerNorm over ONE element (E = 1, O = 1) must return exactly zero, which g gamma - mean(g gamma) only does when both
 // are the same rounded product.  Where a fused multiply-add is wanted it is written fmaf.
+// Shared with the other tile kernels: the MFMA tile is mfma_tile.h; the workspace carving and the split-K
+// weight-gradient GEMM are tile_ops.h.
 #include <math.h>
 #include "common.h"
 
 #pragma clang fp contract(off)
-#include "mfma_tile.h"
+#include "tile_ops.h"
 
 namespace {
 
@@ -451,18 +453,15 @@ struct MbWs {
 static MbWs mb_ws(int64_t B, int D, int P, int O, int H) {
   MbWs w{};
   const size_t b = (size_t)B, tiles = (size_t)ceil_div64(B, MB_T);
-  auto r4 = [](size_t x) { return (x + 3) & ~(size_t)3; };
-  size_t at = 0;
-  w.dz = at; at += r4(b * O);
-  w.dm = at; at += r4(b * P);
-  w.u = at; at += r4(b * P);
-  w.dh = at; at += r4(b * H);
-  w.slots = at; at += r4(tiles * (size_t)(3 * O + P + H));
-  w.gemm = at;
-  size_t g = (size_t)mb_split(B, D, H) * D * H, g2 = (size_t)mb_split(B, H, P) * H * P,
-         g3 = (size_t)mb_split(B, P, O) * P * O;
-  at += r4(g > g2 ? (g > g3 ? g : g3) : (g2 > g3 ? g2 : g3));
-  w.total = at;
+  WsCarve c;
+  w.dz = c.take(b * O);
+  w.dm = c.take(b * P);
+  w.u = c.take(b * P);
+  w.dh = c.take(b * H);
+  w.slots = c.take(tiles * (size_t)(3 * O + P + H));
+  const size_t g = mb_dw_gemm_floats(B, D, H), g2 = mb_dw_gemm_floats(B, H, P), g3 = mb_dw_gemm_floats(B, P, O);
+  w.gemm = c.take(g > g2 ? (g > g3 ? g : g3) : (g2 > g3 ? g2 : g3));
+  w.total = c.at;
   return w;
 }
 
@@ -555,13 +554,7 @@ extern "C" int rec_mask_block_bwd_f32(const float* x_emb, const float* v, const 
   if (int rc = rec_slot_sum(REC_SLOTS_WAVE, 3 * O + P + H, tiles, slots,
                             {{dgamma, dbeta, db3, db2, db1}, {O, O, O, P, H}}, st))
     return rc;
-  // dW = A^T G with A, G stored [B, .]: transA, K = B
-  if (int rc = rec_gemm_f32(1, 0, D, H, B, x_emb, D, dh, H, dW1, H, REC_EPI_NONE, nullptr, nullptr, 0, nullptr, 0,
-                            mb_split(B, D, H), gws, nullptr, stream))
-    return rc;
-  if (int rc = rec_gemm_f32(1, 0, H, P, B, h, H, dm, P, dW2, P, REC_EPI_NONE, nullptr, nullptr, 0, nullptr, 0,
-                            mb_split(B, H, P), gws, nullptr, stream))
-    return rc;
-  return rec_gemm_f32(1, 0, P, O, B, u, P, dz, O, dW3, O, REC_EPI_NONE, nullptr, nullptr, 0, nullptr, 0,
-                      mb_split(B, P, O), gws, nullptr, stream);
+  if (int rc = mb_dw_gemm(D, H, B, x_emb, dh, dW1, gws, stream)) return rc;     // dW1 = x_emb^T dh
+  if (int rc = mb_dw_gemm(H, P, B, h, dm, dW2, gws, stream)) return rc;         // dW2 = h^T dm
+  return mb_dw_gemm(P, O, B, u, dz, dW3, gws, stream);                           // dW3 = u^T dz
 }

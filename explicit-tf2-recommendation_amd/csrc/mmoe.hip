@@ -27,11 +27,14 @@
 // No float atomics and no value with two writers: bit-identical results run to run; no host synchronisation.
 // Contraction is off: a softmax over ONE expert must return exactly zero gradients, which g (dg - dg g) only does when
 // both terms are the same rounded product.
+// Shared with the other tile kernels, in tile_ops.h: the row / column / softmax passes over an LDS operand (TileOps), the
+// small weight-gradient kernel and its launch (this file supplies the matrices: MmSmall), the workspace carving and the
+// split-K weight-gradient GEMM; the MFMA tile itself is mfma_tile.h.
 #include <math.h>
 #include "common.h"
 
 #pragma clang fp contract(off)
-#include "mfma_tile.h"
+#include "tile_ops.h"
 
 namespace {
 
@@ -40,7 +43,6 @@ constexpr int MM_MAXD = REC_MASKNET_MAX_D, MM_MAXN1 = REC_MASKNET_MAX_P, MM_MAXO
 constexpr int MM_MAXT = REC_MASKNET_MAX_R;
 constexpr int MM_NTHR = 256;
 constexpr int MM_G = MM_NTHR / MB_T;             // column groups of the VALU stages
-constexpr int MM_DW_ROWS = 32;                   // examples of one step of the small weight gradients
 
 static_assert(MM_MAXN1 <= 128 * MB_NJ && MM_MAXD <= 128 * MB_NJ, "accumulator blocks per wave");
 static_assert(MM_MAXT <= MM_G - 1, "one thread per (example, task), and one more");
@@ -69,62 +71,7 @@ static_assert(sizeof(float) * (MM_MAXN1 + 5 * MM_MAXO + MM_MAXT) * MB_LD <= MM_L
                   MM_LDS_CAP <= REC_LDS_CU_BYTES,
               "both directions of the largest shape fit the LDS of a CU");
 
-// rows of consecutive columns out of a k-major LDS operand: dst[(r0 + row) ld + c0 + c] = src[c][row], c < nc
-__device__ __forceinline__ void mm_rows_out(float* __restrict__ dst, const float* src, int64_t r0, int64_t B, int ld,
-                                            int c0, int nc, int tid) {
-  for (int i = tid; i < MB_T * nc; i += MM_NTHR) {
-    const int row = i / nc, c = i - row * nc;
-    if (r0 + row < B) dst[(r0 + row) * ld + c0 + c] = src[c * MB_LD + row];
-  }
-}
-// and into one; rows past the batch read as zero
-__device__ __forceinline__ void mm_rows_in(float* dst, const float* __restrict__ src, int64_t r0, int64_t B, int ld,
-                                           int c0, int nc, int tid) {
-  for (int i = tid; i < MB_T * nc; i += MM_NTHR) {
-    const int row = i / nc, c = i - row * nc;
-    dst[c * MB_LD + row] = r0 + row < B ? src[(r0 + row) * ld + c0 + c] : 0.f;
-  }
-}
-// buf <- buf (.) [act > 0] in place, and its copy to the workspace; rows past the batch become zero
-__device__ __forceinline__ void mm_mask_out(float* buf, const float* __restrict__ act, float* __restrict__ ws,
-                                            int64_t r0, int64_t B, int ld, int c0, int nc, int tid) {
-  for (int i = tid; i < MB_T * nc; i += MM_NTHR) {
-    const int row = i / nc, c = i - row * nc;
-    float v = 0.f;
-    if (r0 + row < B) {
-      const int64_t at = (r0 + row) * ld + c0 + c;
-      v = act[at] > 0.f ? buf[c * MB_LD + row] : 0.f;
-      ws[at] = v;
-    }
-    buf[c * MB_LD + row] = v;
-  }
-}
-// column sums of a k-major LDS operand, rows in order
-__device__ __forceinline__ void mm_col_sums(float* __restrict__ slot, const float* buf, int nc, int tid) {
-  for (int c = tid; c < nc; c += MM_NTHR) {
-    float s = 0.f;
-    for (int r = 0; r < MB_T; ++r) s += buf[c * MB_LD + r];
-    slot[c] = s;
-  }
-}
-// softmax over n elements of stride MB_LD; dst may be src
-__device__ __forceinline__ void mm_softmax(const float* src, float* dst, int n) {
-  float m = src[0];
-  for (int i = 1; i < n; ++i) m = fmaxf(m, src[i * MB_LD]);
-  float s = 0.f;
-  for (int i = 0; i < n; ++i) {
-    const float ex = expf(src[i * MB_LD] - m);
-    dst[i * MB_LD] = ex;
-    s += ex;
-  }
-  for (int i = 0; i < n; ++i) dst[i * MB_LD] = dst[i * MB_LD] / s;
-}
-// dz over dg in place: dz = g (.) (dg - sum(dg (.) g))
-__device__ __forceinline__ void mm_softmax_bwd(const float* gp, float* dp, int n) {
-  float s = 0.f;
-  for (int i = 0; i < n; ++i) s += dp[i * MB_LD] * gp[i * MB_LD];
-  for (int i = 0; i < n; ++i) dp[i * MB_LD] = gp[i * MB_LD] * (dp[i * MB_LD] - s);
-}
+using Tile = TileOps<MB_T, MB_LD, MM_NTHR>;
 
 __global__ __launch_bounds__(MM_NTHR) void mmoe_fwd_kernel(
     const float* __restrict__ x, const float* __restrict__ W1, const float* __restrict__ b1,
@@ -202,15 +149,15 @@ __global__ __launch_bounds__(MM_NTHR) void mmoe_fwd_kernel(
   }
   __syncthreads();
   if (se) {
-    mm_rows_out(se, es, r0, B, nO, 0, nO, tid);
-    mm_rows_out(sz, zs, r0, B, Tn, 0, Tn, tid);
+    Tile::rows_out(se, es, r0, B, nO, 0, nO, tid);
+    Tile::rows_out(sz, zs, r0, B, Tn, 0, Tn, tid);
   }
   if (g < T) {
-    mm_softmax(zs + g * n * MB_LD + b, gs + g * n * MB_LD + b, n);
-    if (passes == 2) mm_softmax(gs + g * n * MB_LD + b, gs + g * n * MB_LD + b, n);
+    Tile::softmax(zs + g * n * MB_LD + b, gs + g * n * MB_LD + b, n);
+    if (passes == 2) Tile::softmax(gs + g * n * MB_LD + b, gs + g * n * MB_LD + b, n);
   }
   __syncthreads();
-  if (sg) mm_rows_out(sg, gs, r0, B, Tn, 0, Tn, tid);
+  if (sg) Tile::rows_out(sg, gs, r0, B, Tn, 0, Tn, tid);
 
   for (int t = 0; t < T; ++t) {                  // the towers, one task at a time
     for (int c = g; c < H2; c += MM_G) {
@@ -232,14 +179,14 @@ __global__ __launch_bounds__(MM_NTHR) void mmoe_fwd_kernel(
       for (int k = 0; k < H2; ++k) acc = fmaf(a1s[k * MB_LD + b], W[k * O2], acc);
       a2s[c * MB_LD + b] = fmaxf(acc + bt2[t * O2 + c], 0.f);
     }
-    if (sa1) mm_rows_out(sa1, a1s, r0, B, T * H2, t * H2, H2, tid);
+    if (sa1) Tile::rows_out(sa1, a1s, r0, B, T * H2, t * H2, H2, tid);
     __syncthreads();
     if (g == 0) {
       float acc = 0.f;
       for (int k = 0; k < O2; ++k) acc = fmaf(a2s[k * MB_LD + b], Wt3[t * O2 + k], acc);
       ps[t * MB_LD + b] = sigmoid_acc(acc + bt3[t]);
     }
-    if (sa2) mm_rows_out(sa2, a2s, r0, B, T * O2, t * O2, O2, tid);
+    if (sa2) Tile::rows_out(sa2, a2s, r0, B, T * O2, t * O2, O2, tid);
     __syncthreads();                             // a1s and a2s are rewritten by the next task
   }
   for (int i = tid; i < MB_T * T; i += MM_NTHR) {
@@ -290,11 +237,11 @@ __global__ __launch_bounds__(MM_NTHR) void mmoe_bwd_kernel(
   float* __restrict__ slot_2 = slot_1 + T * H2;
   float* __restrict__ slot_l = slot_2 + T * O2;
 
-  mm_rows_in(es, e, r0, B, nO, 0, nO, tid);
-  mm_rows_in(gs, gt, r0, B, Tn, 0, Tn, tid);
-  if (passes == 2) mm_rows_in(g1s, z, r0, B, Tn, 0, Tn, tid);
-  mm_rows_in(ps, p, r0, B, T, 0, T, tid);
-  mm_rows_in(dls, dout, r0, B, T, 0, T, tid);
+  Tile::rows_in(es, e, r0, B, nO, 0, nO, tid);
+  Tile::rows_in(gs, gt, r0, B, Tn, 0, Tn, tid);
+  if (passes == 2) Tile::rows_in(g1s, z, r0, B, Tn, 0, Tn, tid);
+  Tile::rows_in(ps, p, r0, B, T, 0, T, tid);
+  Tile::rows_in(dls, dout, r0, B, T, 0, T, tid);
   for (int c = g; c < nO; c += MM_G) des[c * MB_LD + b] = 0.f;     // by the thread that adds to it below
   __syncthreads();
 
@@ -308,18 +255,18 @@ __global__ __launch_bounds__(MM_NTHR) void mmoe_bwd_kernel(
       dls[t * MB_LD + b] = dp * (pv * (1.f - pv));
     }
   } else if (passes == 2 && g - 1 < T) {         // the first softmax again, by the other threads of the example
-    mm_softmax(g1s + (g - 1) * n * MB_LD + b, g1s + (g - 1) * n * MB_LD + b, n);
+    Tile::softmax(g1s + (g - 1) * n * MB_LD + b, g1s + (g - 1) * n * MB_LD + b, n);
   }
   __syncthreads();
-  mm_rows_out(ws_dl, dls, r0, B, T, 0, T, tid);
-  mm_col_sums(slot_l, dls, T, tid);
+  Tile::rows_out(ws_dl, dls, r0, B, T, 0, T, tid);
+  Tile::col_sums(slot_l, dls, T, tid);
 
   for (int t = 0; t < T; ++t) {
     for (int c = g; c < O2; c += MM_G) d2s[c * MB_LD + b] = dls[t * MB_LD + b] * Wt3[t * O2 + c];
     __syncthreads();
-    mm_mask_out(d2s, a2, ws_d2, r0, B, T * O2, t * O2, O2, tid);
+    Tile::mask_out(d2s, a2, ws_d2, r0, B, T * O2, t * O2, O2, tid);
     __syncthreads();
-    mm_col_sums(slot_2 + t * O2, d2s, O2, tid);
+    Tile::col_sums(slot_2 + t * O2, d2s, O2, tid);
     for (int c = g; c < H2; c += MM_G) {         // da2 Wt2^T
       const float* W = Wt2 + ((int64_t)t * H2 + c) * O2;
       float acc = 0.f;
@@ -327,9 +274,9 @@ __global__ __launch_bounds__(MM_NTHR) void mmoe_bwd_kernel(
       d1s[c * MB_LD + b] = acc;
     }
     __syncthreads();
-    mm_mask_out(d1s, a1, ws_d1, r0, B, T * H2, t * H2, H2, tid);
+    Tile::mask_out(d1s, a1, ws_d1, r0, B, T * H2, t * H2, H2, tid);
     __syncthreads();
-    mm_col_sums(slot_1 + t * H2, d1s, H2, tid);
+    Tile::col_sums(slot_1 + t * H2, d1s, H2, tid);
     for (int k = g; k < nO; k += MM_G) {         // du = da1 Wt1^T; de += du g
       const float* W = Wt1 + ((int64_t)t * nO + k) * H2;
       float acc = 0.f;
@@ -347,15 +294,15 @@ __global__ __launch_bounds__(MM_NTHR) void mmoe_bwd_kernel(
   }
 
   if (g < T) {
-    mm_softmax_bwd(gs + g * n * MB_LD + b, dzs + g * n * MB_LD + b, n);
-    if (passes == 2) mm_softmax_bwd(g1s + g * n * MB_LD + b, dzs + g * n * MB_LD + b, n);
+    Tile::softmax_bwd(gs + g * n * MB_LD + b, dzs + g * n * MB_LD + b, n);
+    if (passes == 2) Tile::softmax_bwd(g1s + g * n * MB_LD + b, dzs + g * n * MB_LD + b, n);
   }
   __syncthreads();
-  mm_mask_out(dzs, z, ws_dzz, r0, B, Tn, 0, Tn, tid);
-  mm_mask_out(des, e, ws_dze, r0, B, nO, 0, nO, tid);
+  Tile::mask_out(dzs, z, ws_dzz, r0, B, Tn, 0, Tn, tid);
+  Tile::mask_out(des, e, ws_dze, r0, B, nO, 0, nO, tid);
   __syncthreads();                               // and every read of es .. ps lies before it: zt may be written
-  mm_col_sums(slot_e, des, nO, tid);
-  mm_col_sums(slot_g, dzs, Tn, tid);
+  Tile::col_sums(slot_e, des, nO, tid);
+  Tile::col_sums(slot_g, dzs, Tn, tid);
 
   for (int c = g; c < N1e; c += MM_G) {          // dh = dze We2^T | dzz Wg2^T
     float acc = 0.f;
@@ -373,9 +320,9 @@ __global__ __launch_bounds__(MM_NTHR) void mmoe_bwd_kernel(
     zt[c * MB_LD + b] = acc;
   }
   __syncthreads();
-  mm_mask_out(zt, h, ws_dz1, r0, B, N1, 0, N1, tid);
+  Tile::mask_out(zt, h, ws_dz1, r0, B, N1, 0, N1, tid);
   __syncthreads();
-  mm_col_sums(slot, zt, N1, tid);
+  Tile::col_sums(slot, zt, N1, tid);
 
   f32x16 xacc[MB_NJ];
 #pragma unroll
@@ -394,65 +341,26 @@ __global__ __launch_bounds__(MM_NTHR) void mmoe_bwd_kernel(
   }
 }
 
-// The small weight gradients, all of them in one launch.  Matrix q of the n + 4 T is A_q^T G_q over the batch with
+// The small weight gradients, all of them in one launch (small_dw_kernel, tile_ops.h).  Matrix q of the n + 4 T is
+// A_q^T G_q over the batch with
 //   q < n          dWe2[i]  = h_i^T dze_i            then  dWg2[t] = h_{n+t}^T dzz_t,   dWt1[t] = u_t^T da1_t (u_t = e (.) g_t
-//   recomputed),   dWt2[t]  = a1_t^T da2_t           and   dWt3[t] = a2_t^T dl_t,
-// laid out one after the other in that order (the order of the packed gradients).  Workgroup (q and a block of 256
-// outputs, s) adds the examples of batch slice s, in order, into part[s], one output per thread; the slices are added by
-// rec_slot_sum in slice order.
-__global__ __launch_bounds__(MM_NTHR) void mmoe_small_dw_kernel(
-    const float* __restrict__ h, const float* __restrict__ e, const float* __restrict__ gt,
-    const float* __restrict__ a1, const float* __restrict__ a2, const float* __restrict__ dze,
-    const float* __restrict__ dzz, const float* __restrict__ d1, const float* __restrict__ d2,
-    const float* __restrict__ dl, int64_t B, MmDims d, int maxblk, int64_t per, int wtot, float* __restrict__ part) {
-  __shared__ float as[MM_DW_ROWS * MM_MAXO], gsh[MM_DW_ROWS * MM_MAXO];
-  const int tid = threadIdx.x, blk = blockIdx.x % maxblk;
-  int q = blockIdx.x / maxblk;
-  const int n = d.n, T = d.T, H1 = d.H1, O = d.O, H2 = d.H2, O2 = d.O2, N1 = d.N1(), nO = d.nO(), Tn = d.Tn();
-  const float *A, *G;
-  int lda, a0, M, ldg, g0, N, off, ut = -1;
-  if (q < n) {
-    A = h; lda = N1; a0 = q * H1; M = H1; G = dze; ldg = nO; g0 = q * O; N = O; off = q * H1 * O;
-  } else if ((q -= n) < T) {
-    A = h; lda = N1; a0 = (n + q) * H1; M = H1; G = dzz; ldg = Tn; g0 = q * n; N = n; off = n * H1 * O + q * H1 * n;
-  } else if ((q -= T) < T) {
-    A = e; lda = nO; a0 = 0; M = nO; G = d1; ldg = T * H2; g0 = q * H2; N = H2; ut = q;
-    off = n * H1 * O + T * H1 * n + q * nO * H2;
-  } else if ((q -= T) < T) {
-    A = a1; lda = T * H2; a0 = q * H2; M = H2; G = d2; ldg = T * O2; g0 = q * O2; N = O2;
-    off = n * H1 * O + T * H1 * n + T * nO * H2 + q * H2 * O2;
-  } else {
+//   recomputed: the row scale),   dWt2[t]  = a1_t^T da2_t           and   dWt3[t] = a2_t^T dl_t,
+// laid out one after the other in that order (the order of the packed gradients).
+struct MmSmall {
+  static constexpr int MAXK = MM_MAXO;
+  MmDims d;
+  const float *h, *e, *gt, *a1, *a2, *dze, *dzz, *d1, *d2, *dl;
+  __device__ SmallMat mat(int q) const {
+    const int n = d.n, T = d.T, H1 = d.H1, O = d.O, H2 = d.H2, O2 = d.O2, N1 = d.N1(), nO = d.nO(), Tn = d.Tn();
+    const int oG = n * H1 * O, o1 = oG + T * H1 * n, o2 = o1 + T * nO * H2, o3 = o2 + T * H2 * O2;
+    if (q < n) return {h, N1, q * H1, H1, dze, nO, q * O, O, q * H1 * O, O};
+    if ((q -= n) < T) return {h, N1, (n + q) * H1, H1, dzz, Tn, q * n, n, oG + q * H1 * n, n};
+    if ((q -= T) < T) return {e, nO, 0, nO, d1, T * H2, q * H2, H2, o1 + q * nO * H2, H2, gt, Tn, q * n, O};
+    if ((q -= T) < T) return {a1, T * H2, q * H2, H2, d2, T * O2, q * O2, O2, o2 + q * H2 * O2, O2};
     q -= T;
-    A = a2; lda = T * O2; a0 = q * O2; M = O2; G = dl; ldg = T; g0 = q; N = 1;
-    off = n * H1 * O + T * H1 * n + T * nO * H2 + T * H2 * O2 + q * O2;
+    return {a2, T * O2, q * O2, O2, dl, T, q, 1, o3 + q * O2, 1};
   }
-  if (blk * MM_NTHR >= M * N) return;            // uniform over the workgroup
-  const int o = blk * MM_NTHR + tid;
-  const bool own = o < M * N;
-  const int om = own ? o / N : 0, on = own ? o - om * N : 0;
-  const int64_t b0 = (int64_t)blockIdx.y * per, b1 = b0 + per < B ? b0 + per : B;
-  float acc = 0.f;
-  for (int64_t bb = b0; bb < b1; bb += MM_DW_ROWS) {
-    for (int i = tid; i < MM_DW_ROWS * M; i += MM_NTHR) {
-      const int r = i / M, m = i - r * M;
-      float v = 0.f;
-      if (bb + r < b1) {
-        v = A[(bb + r) * lda + a0 + m];
-        if (ut >= 0) v = v * gt[(bb + r) * Tn + ut * n + m / O];
-      }
-      as[i] = v;
-    }
-    for (int i = tid; i < MM_DW_ROWS * N; i += MM_NTHR) {
-      const int r = i / N, c = i - r * N;
-      gsh[i] = bb + r < b1 ? G[(bb + r) * ldg + g0 + c] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll 8
-    for (int r = 0; r < MM_DW_ROWS; ++r) acc = fmaf(as[r * M + om], gsh[r * N + on], acc);
-    __syncthreads();
-  }
-  if (own) part[(int64_t)blockIdx.y * wtot + off + o] = acc;
-}
+};
 
 static int mm_shape(int64_t B, int D, int n, int T, int H1, int O, int H2, int O2, int passes, int ctcvr) {
   if (B < 0 || D < 1 || n < 1 || T < 1 || H1 < 1 || O < 1 || H2 < 1 || O2 < 1) return REC_E_ARG;
@@ -463,11 +371,6 @@ static int mm_shape(int64_t B, int D, int n, int T, int H1, int O, int H2, int O
   return REC_OK;
 }
 
-// slices of the small weight gradients over the batch: at most 16, at least 256 examples each
-static int mm_small_split(int64_t B) {
-  const int64_t s = B / 256;
-  return s < 1 ? 1 : (s > 16 ? 16 : (int)s);
-}
 static int mm_small_floats(const MmDims& d) {
   return d.n * d.H1 * d.O + d.T * d.H1 * d.n + d.T * d.nO() * d.H2 + d.T * d.H2 * d.O2 + d.T * d.O2;
 }
@@ -478,18 +381,17 @@ struct MmWs {
 static MmWs mm_ws(int64_t B, const MmDims& d) {
   MmWs w{};
   const size_t b = (size_t)B, tiles = (size_t)ceil_div64(B, MB_T);
-  auto r4 = [](size_t v) { return (v + 3) & ~(size_t)3; };
-  size_t at = 0;
-  w.dz1 = at; at += r4(b * d.N1());
-  w.dze = at; at += r4(b * d.nO());
-  w.dzz = at; at += r4(b * d.Tn());
-  w.d1 = at; at += r4(b * d.T * d.H2);
-  w.d2 = at; at += r4(b * d.T * d.O2);
-  w.dl = at; at += r4(b * d.T);
-  w.slots = at; at += r4(tiles * (size_t)mm_slot_floats(d));
-  w.part = at; at += r4((size_t)mm_small_split(B) * mm_small_floats(d));
-  w.gemm = at; at += r4((size_t)mb_split(B, d.D, d.N1()) * d.D * d.N1());
-  w.total = at;
+  WsCarve c;
+  w.dz1 = c.take(b * d.N1());
+  w.dze = c.take(b * d.nO());
+  w.dzz = c.take(b * d.Tn());
+  w.d1 = c.take(b * d.T * d.H2);
+  w.d2 = c.take(b * d.T * d.O2);
+  w.dl = c.take(b * d.T);
+  w.slots = c.take(tiles * (size_t)mm_slot_floats(d));
+  w.part = c.take((size_t)mb_small_split(B) * mm_small_floats(d));
+  w.gemm = c.take(mb_dw_gemm_floats(B, d.D, d.N1()));
+  w.total = c.at;
   return w;
 }
 
@@ -551,20 +453,15 @@ extern "C" int rec_mmoe_bwd_f32(const float* x, const float* W1, const float* We
   if (int rc = rec_slot_sum(REC_SLOTS_WAVE, mm_slot_floats(d), tiles, slots,
                             {{db1, dbe2, dbg2, dbt1, dbt2, dbt3}, {N1, nO, Tn, T * H2, T * O2, T}}, st))
     return rc;
-  const int S = mm_small_split(B), wtot = mm_small_floats(d);
-  const int64_t per = ceil_div64(ceil_div64(B, S), MM_DW_ROWS) * MM_DW_ROWS;
+  const int S = mb_small_split(B), wtot = mm_small_floats(d);
   int big = H1 * (O > n ? O : n);
   if (nO * H2 > big) big = nO * H2;
   if (H2 * O2 > big) big = H2 * O2;
-  const int maxblk = (big + MM_NTHR - 1) / MM_NTHR;
-  hipLaunchKernelGGL(mmoe_small_dw_kernel, dim3((n + 4 * T) * maxblk, S), dim3(MM_NTHR), 0, st, h, e, g, a1, a2, dze, dzz,
-                     d1, d2, dl, B, d, maxblk, per, wtot, part);
-  REC_LAUNCH_CHECK();
+  if (int rc = small_dw_launch(MmSmall{d, h, e, g, a1, a2, dze, dzz, d1, d2, dl}, n + 4 * T, big, wtot, B, part, st))
+    return rc;
   if (int rc = rec_slot_sum(REC_SLOTS_SERIAL, wtot, S, part,
                             {{dWe2, dWg2, dWt1, dWt2, dWt3}, {n * H1 * O, T * H1 * n, T * nO * H2, T * H2 * O2, T * O2}},
                             st))
     return rc;
-  // dW1 = x^T dZ1 with both stored [B, .]: transA, K = B
-  return rec_gemm_f32(1, 0, D, N1, B, x, D, dz1, N1, dW1, N1, REC_EPI_NONE, nullptr, nullptr, 0, nullptr, 0,
-                      mb_split(B, D, N1), gws, nullptr, stream);
+  return mb_dw_gemm(D, N1, B, x, dz1, dW1, gws, stream);        // dW1 = x^T dZ1
 }

@@ -17,8 +17,8 @@
 // operand being the tile of the MLP's group.  N1 is 1024 at the default level 0 and 1920 at the limits, so the first
 // layer runs in CHUNKS of whole MLPs (at most 512 / H1, fewer where LDS is short) and the second layers of a chunk are
 // finished before the next chunk overwrites h: LDS holds one h chunk, e, q, the gates and y, never the whole h.  The
-// narrow stages (e, q, the gate logits, the softmax, the mixture, the towers) run on the VALU out of LDS as in mmoe.hip:
-// thread t owns example t & 31 and the columns t / 32, t / 32 + 8, ...
+// narrow stages (e, q, the gate logits, the softmax, the mixture, the towers) run on the VALU out of LDS: thread t owns
+// example t & 31 and the columns t / 32, t / 32 + 8, ...
 // Grouped levels (K = Din = 8 at the defaults) keep the MFMA for the first layer: K is even, so no k step is padding, and
 // a block of H1 = 64 columns is two full 32-column tiles.  Their dxin has N = Din = 8 columns per group, a quarter of a
 // tile, and runs on the VALU; their dW1 is a few KB and joins the batched small weight gradients.
@@ -32,12 +32,16 @@
 // level, dW1) is one launch over (matrix, block of 256 outputs, batch slice) whose at most 16 slices a second slot sum
 // adds in order; with Gin = 1, dW1 = xin^T dZ1 goes to rec_gemm_f32 (split-K, slices added in order).
 // No float atomics and no value with two writers: bit-identical results run to run; no host synchronisation.
-// Contraction is off, as in mmoe.hip: a softmax over one column must return exactly zero gradients.
+// Contraction is off: a softmax over one column must return exactly zero gradients, which g (dg - dg g) only does when
+// both terms are the same rounded product.
+// Shared with the other tile kernels, in tile_ops.h: the row / column / softmax passes over an LDS operand (TileOps), the
+// small weight-gradient kernel and its launch (this file supplies the matrices: PlSmall), the workspace carving and the
+// split-K weight-gradient GEMM; the MFMA tile itself is mfma_tile.h.
 #include <math.h>
 #include "common.h"
 
 #pragma clang fp contract(off)
-#include "mfma_tile.h"
+#include "tile_ops.h"
 
 namespace {
 
@@ -46,7 +50,6 @@ constexpr int PL_MAXD = REC_MASKNET_MAX_D, PL_MAXO = REC_MASKNET_MAX_O, PL_MAXT 
 constexpr int PL_MAXCH = 128 * MB_NJ;            // columns of an h chunk at most: the accumulator columns of mb_mma
 constexpr int PL_NTHR = 256;
 constexpr int PL_G = PL_NTHR / MB_T;             // column groups of the VALU stages
-constexpr int PL_DW_ROWS = 32;                   // examples of one step of the small weight gradients
 constexpr size_t PL_LDS_CAP = 156 * 1024;
 constexpr int PL_LDS_ROWS = (int)(PL_LDS_CAP / (sizeof(float) * MB_LD));
 
@@ -94,62 +97,8 @@ static_assert(PL_MAXD + 4 * PL_MAXO + PL_MAXO + 1 <= PL_LDS_ROWS, "forward at th
 static_assert(8 * PL_MAXO + PL_MAXT + PL_MAXO + 1 <= PL_LDS_ROWS, "backward at the limits");
 static_assert(PL_LDS_CAP <= REC_LDS_CU_BYTES, "the LDS of a CU");
 
-// rows of consecutive columns out of a k-major LDS operand: dst[(r0 + row) ld + c0 + c] = src[c][row], c < nc
-__device__ __forceinline__ void pl_rows_out(float* __restrict__ dst, const float* src, int64_t r0, int64_t B, int ld,
-                                            int c0, int nc, int tid) {
-  for (int i = tid; i < MB_T * nc; i += PL_NTHR) {
-    const int row = i / nc, c = i - row * nc;
-    if (r0 + row < B) dst[(r0 + row) * ld + c0 + c] = src[c * MB_LD + row];
-  }
-}
-// and into one; rows past the batch read as zero, and so does all of it when src is NULL
-__device__ __forceinline__ void pl_rows_in(float* dst, const float* __restrict__ src, int64_t r0, int64_t B, int ld,
-                                           int c0, int nc, int tid) {
-  for (int i = tid; i < MB_T * nc; i += PL_NTHR) {
-    const int row = i / nc, c = i - row * nc;
-    dst[c * MB_LD + row] = (src && r0 + row < B) ? src[(r0 + row) * ld + c0 + c] : 0.f;
-  }
-}
-// buf <- buf (.) [act > 0] in place, and its copy to the workspace; rows past the batch become zero
-__device__ __forceinline__ void pl_mask_out(float* buf, const float* __restrict__ act, float* __restrict__ ws,
-                                            int64_t r0, int64_t B, int ld, int c0, int nc, int tid) {
-  for (int i = tid; i < MB_T * nc; i += PL_NTHR) {
-    const int row = i / nc, c = i - row * nc;
-    float v = 0.f;
-    if (r0 + row < B) {
-      const int64_t at = (r0 + row) * ld + c0 + c;
-      v = act[at] > 0.f ? buf[c * MB_LD + row] : 0.f;
-      ws[at] = v;
-    }
-    buf[c * MB_LD + row] = v;
-  }
-}
-// column sums of a k-major LDS operand, rows in order
-__device__ __forceinline__ void pl_col_sums(float* __restrict__ slot, const float* buf, int nc, int tid) {
-  for (int c = tid; c < nc; c += PL_NTHR) {
-    float s = 0.f;
-    for (int r = 0; r < MB_T; ++r) s += buf[c * MB_LD + r];
-    slot[c] = s;
-  }
-}
-// softmax over n elements of stride MB_LD; dst may be src
-__device__ __forceinline__ void pl_softmax(const float* src, float* dst, int n) {
-  float m = src[0];
-  for (int i = 1; i < n; ++i) m = fmaxf(m, src[i * MB_LD]);
-  float s = 0.f;
-  for (int i = 0; i < n; ++i) {
-    const float ex = expf(src[i * MB_LD] - m);
-    dst[i * MB_LD] = ex;
-    s += ex;
-  }
-  for (int i = 0; i < n; ++i) dst[i * MB_LD] = dst[i * MB_LD] / s;
-}
-// dz over dg in place: dz = g (.) (dg - sum(dg (.) g))
-__device__ __forceinline__ void pl_softmax_bwd(const float* gp, float* dp, int n) {
-  float s = 0.f;
-  for (int i = 0; i < n; ++i) s += dp[i * MB_LD] * gp[i * MB_LD];
-  for (int i = 0; i < n; ++i) dp[i * MB_LD] = gp[i * MB_LD] * (dp[i * MB_LD] - s);
-}
+using Tile = TileOps<MB_T, MB_LD, PL_NTHR>;
+
 // acc + sum_k a[k][example] w[k ldw], k ascending.  The weights of eight steps are requested together: a workgroup is one
 // wave per SIMD, so nothing else hides the latency of a weight load, and one wait per step was a third of the forward.
 __device__ __forceinline__ float pl_dot(const float* a, const float* __restrict__ w, int ldw, int K, float acc) {
@@ -283,19 +232,19 @@ __global__ __launch_bounds__(PL_NTHR) void ple_cgc_fwd_kernel(
     __syncthreads();                             // the next chunk overwrites hs
   }
   if (se) {
-    pl_rows_out(se, es, r0, B, neO, 0, neO, tid);
-    pl_rows_out(sq, qs, r0, B, GQ, 0, GQ, tid);
+    Tile::rows_out(se, es, r0, B, neO, 0, neO, tid);
+    Tile::rows_out(sq, qs, r0, B, GQ, 0, GQ, tid);
   }
   pl_logits(d, qs, Wg3s, Wg3h, gs, GW, b, g);
   __syncthreads();
   if (g < T) {
-    pl_softmax(gs + g * ns * MB_LD + b, gs + g * ns * MB_LD + b, ns);
-    pl_softmax(gs + g * ns * MB_LD + b, gs + g * ns * MB_LD + b, ns);
+    Tile::softmax(gs + g * ns * MB_LD + b, gs + g * ns * MB_LD + b, ns);
+    Tile::softmax(gs + g * ns * MB_LD + b, gs + g * ns * MB_LD + b, ns);
   } else if (g == T && !d.last) {
-    pl_softmax(gs + Tns * MB_LD + b, gs + Tns * MB_LD + b, ne);
+    Tile::softmax(gs + Tns * MB_LD + b, gs + Tns * MB_LD + b, ne);
   }
   __syncthreads();
-  if (sg) pl_rows_out(sg, gs, r0, B, GW, 0, GW, tid);
+  if (sg) Tile::rows_out(sg, gs, r0, B, GW, 0, GW, tid);
 
   for (int c = g; c < GO; c += PL_G) {           // the mixture: a gated SUM over the experts a gate reads
     const int gi = c / O, o = c - gi * O;
@@ -311,7 +260,7 @@ __global__ __launch_bounds__(PL_NTHR) void ple_cgc_fwd_kernel(
     ys[c * MB_LD + b] = acc;
   }
   __syncthreads();
-  pl_rows_out(y, ys, r0, B, GO, 0, GO, tid);
+  Tile::rows_out(y, ys, r0, B, GO, 0, GO, tid);
   if (d.last && g < T && r0 + b < B) {           // the towers: one sigmoid unit per task
     float acc = 0.f;
     for (int o = 0; o < O; ++o) acc = fmaf(ys[(g * O + o) * MB_LD + b], Wtw[g * O + o], acc);
@@ -353,10 +302,10 @@ __global__ __launch_bounds__(PL_NTHR) void ple_cgc_bwd_kernel(
   float* __restrict__ slot_g = slot_e + neO;
   float* __restrict__ slot_l = slot_g + GQ;
 
-  pl_rows_in(es, e, r0, B, neO, 0, neO, tid);
-  pl_rows_in(gs, gt, r0, B, GW, 0, GW, tid);
-  pl_rows_in(qs, q, r0, B, GQ, 0, GQ, tid);
-  pl_rows_in(dys, dy, r0, B, GO, 0, GO, tid);
+  Tile::rows_in(es, e, r0, B, neO, 0, neO, tid);
+  Tile::rows_in(gs, gt, r0, B, GW, 0, GW, tid);
+  Tile::rows_in(qs, q, r0, B, GQ, 0, GQ, tid);
+  Tile::rows_in(dys, dy, r0, B, GO, 0, GO, tid);
   if (last) {
     for (int i = tid; i < MB_T * T; i += PL_NTHR) {
       const int row = i / T, t = i - row * T;
@@ -375,12 +324,12 @@ __global__ __launch_bounds__(PL_NTHR) void ple_cgc_bwd_kernel(
 
   pl_logits(d, qs, Wg3s, Wg3h, g1s, Tns, b, g);  // the task gates' logits again
   if (last) {
-    pl_col_sums(slot_l, dls, T, tid);
+    Tile::col_sums(slot_l, dls, T, tid);
     for (int c = g; c < GO; c += PL_G)           // dy of the towers
       dys[c * MB_LD + b] = dys[c * MB_LD + b] + dls[(c / O) * MB_LD + b] * Wtw[c];
   }
   __syncthreads();
-  if (g < T) pl_softmax(g1s + g * ns * MB_LD + b, g1s + g * ns * MB_LD + b, ns);
+  if (g < T) Tile::softmax(g1s + g * ns * MB_LD + b, g1s + g * ns * MB_LD + b, ns);
 
   for (int c = g; c < GW; c += PL_G) {           // dg[i] = dy . e_i
     int gi, ei;
@@ -412,24 +361,24 @@ __global__ __launch_bounds__(PL_NTHR) void ple_cgc_bwd_kernel(
   __syncthreads();
 
   if (g < T) {                                   // through both softmax passes of a task gate, one of the shared gate
-    pl_softmax_bwd(gs + g * ns * MB_LD + b, dgs + g * ns * MB_LD + b, ns);
-    pl_softmax_bwd(g1s + g * ns * MB_LD + b, dgs + g * ns * MB_LD + b, ns);
+    Tile::softmax_bwd(gs + g * ns * MB_LD + b, dgs + g * ns * MB_LD + b, ns);
+    Tile::softmax_bwd(g1s + g * ns * MB_LD + b, dgs + g * ns * MB_LD + b, ns);
   } else if (g == T && !last) {
-    pl_softmax_bwd(gs + Tns * MB_LD + b, dgs + Tns * MB_LD + b, ne);
+    Tile::softmax_bwd(gs + Tns * MB_LD + b, dgs + Tns * MB_LD + b, ne);
   }
   __syncthreads();                               // and every read of q lies before it: qs becomes dq
-  pl_rows_out(ws_dlg, dgs, r0, B, GW, 0, GW, tid);
+  Tile::rows_out(ws_dlg, dgs, r0, B, GW, 0, GW, tid);
   for (int c = g; c < GQ; c += PL_G) {           // dq = dlogits Wg3^T
     const int gi = c / Og, k = c - gi * Og;
     qs[c * MB_LD + b] = gi < T ? pl_dot(dgs + gi * ns * MB_LD + b, Wg3s + ((int64_t)gi * Og + k) * ns, 1, ns, 0.f)
                                : pl_dot(dgs + Tns * MB_LD + b, Wg3h + (int64_t)k * ne, 1, ne, 0.f);
   }
   __syncthreads();
-  pl_mask_out(qs, q, ws_dzq, r0, B, GQ, 0, GQ, tid);
-  pl_mask_out(des, e, ws_dze, r0, B, neO, 0, neO, tid);
+  Tile::mask_out(qs, q, ws_dzq, r0, B, GQ, 0, GQ, tid);
+  Tile::mask_out(des, e, ws_dze, r0, B, neO, 0, neO, tid);
   __syncthreads();
-  pl_col_sums(slot_e, des, neO, tid);
-  pl_col_sums(slot_g, qs, GQ, tid);
+  Tile::col_sums(slot_e, des, neO, tid);
+  Tile::col_sums(slot_g, qs, GQ, tid);
 
   f32x16 xacc[MB_NJ];
 #pragma unroll
@@ -476,10 +425,10 @@ __global__ __launch_bounds__(PL_NTHR) void ple_cgc_bwd_kernel(
         zt[c * MB_LD + b] = acc;
       }
       __syncthreads();
-      pl_mask_out(zt, h, ws_dz1, r0, B, N1, m0 * H1, nc, tid);
+      Tile::mask_out(zt, h, ws_dz1, r0, B, N1, m0 * H1, nc, tid);
       __syncthreads();
     }
-    pl_col_sums(slot + m0 * H1, zt, nc, tid);
+    Tile::col_sums(slot + m0 * H1, zt, nc, tid);
     if (Gin == 1) {                              // dxin += dZ1 W1^T over the chunk's columns
       mb_mma<true>(xacc, zt, nc, W1, N1, m0 * H1, Din, wave, lo, hi);
     } else {                                     // each group's dxin sums its own MLPs' blocks only
@@ -508,69 +457,35 @@ __global__ __launch_bounds__(PL_NTHR) void ple_cgc_bwd_kernel(
       }
     }
   } else {
-    pl_rows_out(dxin, dxs, r0, B, XD, 0, XD, tid);
+    Tile::rows_out(dxin, dxs, r0, B, XD, 0, XD, tid);
   }
 }
 
-// The small weight gradients, all of them in one launch.  Every matrix is A^T G over the batch:
+// The small weight gradients, all of them in one launch (small_dw_kernel, tile_ops.h).  Every matrix is A^T G over the
+// batch:
 //   dWe2[i] = h_i^T dze_i   dWg2[g] = h_{ne+g}^T dzq_g   dWg3s[t] = q_t^T dlg_t   dWg3h = q_T^T dlg_T (not last)
 //   dWtw[t] = y_t^T dl_t (last)   and for a grouped level dW1 block m = xin_group(m)^T dZ1_m, written in place in the
 //   [Din, N1] layout of dW1,
-// laid out one after the other in that order.  Workgroup (matrix and a block of 256 outputs, s) adds the examples of
-// batch slice s, in order, into part[s], one output per thread; the slices are added by rec_slot_sum in slice order.
-__global__ __launch_bounds__(PL_NTHR) void ple_small_dw_kernel(
-    const float* __restrict__ xin, const float* __restrict__ h, const float* __restrict__ q,
-    const float* __restrict__ y, const float* __restrict__ dz1, const float* __restrict__ dze,
-    const float* __restrict__ dzq, const float* __restrict__ dlg, const float* __restrict__ dl, int64_t B, PlDims d,
-    int maxblk, int64_t per, int wtot, float* __restrict__ part) {
-  __shared__ float as[PL_DW_ROWS * PL_MAXO], gsh[PL_DW_ROWS * PL_MAXO];
-  const int tid = threadIdx.x, blk = blockIdx.x % maxblk;
-  int mq = blockIdx.x / maxblk;
-  const int T = d.T, H1 = d.H1, O = d.O, Og = d.Og, ne = d.ne(), ns = d.ns(), Gout = d.Gout(), N1 = d.N1();
-  const int neO = d.neO(), GQ = d.GQ(), GW = d.GW(), GO = d.GO(), Tns = d.Tns();
-  const int oG = ne * H1 * O, oS = oG + Gout * H1 * Og, oH = oS + T * Og * ns, oT = oH + (d.last ? 0 : Og * ne);
-  const int oW = oT + (d.last ? T * O : 0);
-  const int nH = d.last ? 0 : 1, nT = d.last ? T : 0;            // shared-gate and tower matrices
-  const float *A, *G;
-  int lda, a0, M, ldg, g0, N, off, ldo;
-  if (mq < ne) {
-    A = h; lda = N1; a0 = mq * H1; M = H1; G = dze; ldg = neO; g0 = mq * O; N = O; off = mq * H1 * O; ldo = O;
-  } else if ((mq -= ne) < Gout) {
-    A = h; lda = N1; a0 = (ne + mq) * H1; M = H1; G = dzq; ldg = GQ; g0 = mq * Og; N = Og; off = oG + mq * H1 * Og;
-    ldo = Og;
-  } else if ((mq -= Gout) < T) {
-    A = q; lda = GQ; a0 = mq * Og; M = Og; G = dlg; ldg = GW; g0 = mq * ns; N = ns; off = oS + mq * Og * ns; ldo = ns;
-  } else if ((mq -= T) < nH) {
-    A = q; lda = GQ; a0 = T * Og; M = Og; G = dlg; ldg = GW; g0 = Tns; N = ne; off = oH; ldo = ne;
-  } else if ((mq -= nH) < nT) {
-    A = y; lda = GO; a0 = mq * O; M = O; G = dl; ldg = T; g0 = mq; N = 1; off = oT + mq * O; ldo = 1;
-  } else {
+// laid out one after the other in that order.
+struct PlSmall {
+  static constexpr int MAXK = PL_MAXO;
+  PlDims d;
+  const float *xin, *h, *q, *y, *dz1, *dze, *dzq, *dlg, *dl;
+  __device__ SmallMat mat(int mq) const {
+    const int T = d.T, H1 = d.H1, O = d.O, Og = d.Og, ne = d.ne(), ns = d.ns(), Gout = d.Gout(), N1 = d.N1();
+    const int neO = d.neO(), GQ = d.GQ(), GW = d.GW(), GO = d.GO(), Tns = d.Tns();
+    const int oG = ne * H1 * O, oS = oG + Gout * H1 * Og, oH = oS + T * Og * ns, oT = oH + (d.last ? 0 : Og * ne);
+    const int oW = oT + (d.last ? T * O : 0);
+    const int nH = d.last ? 0 : 1, nT = d.last ? T : 0;          // shared-gate and tower matrices
+    if (mq < ne) return {h, N1, mq * H1, H1, dze, neO, mq * O, O, mq * H1 * O, O};
+    if ((mq -= ne) < Gout) return {h, N1, (ne + mq) * H1, H1, dzq, GQ, mq * Og, Og, oG + mq * H1 * Og, Og};
+    if ((mq -= Gout) < T) return {q, GQ, mq * Og, Og, dlg, GW, mq * ns, ns, oS + mq * Og * ns, ns};
+    if ((mq -= T) < nH) return {q, GQ, T * Og, Og, dlg, GW, Tns, ne, oH, ne};
+    if ((mq -= nH) < nT) return {y, GO, mq * O, O, dl, T, mq, 1, oT + mq * O, 1};
     mq -= nT;                                    // a first layer of a grouped level
-    A = xin; lda = d.XD(); a0 = d.grp(mq) * d.Din; M = d.Din; G = dz1; ldg = N1; g0 = mq * H1; N = H1;
-    off = oW + mq * H1; ldo = N1;
+    return {xin, d.XD(), d.grp(mq) * d.Din, d.Din, dz1, N1, mq * H1, H1, oW + mq * H1, N1};
   }
-  if (blk * PL_NTHR >= M * N) return;            // uniform over the workgroup
-  const int o = blk * PL_NTHR + tid;
-  const bool own = o < M * N;
-  const int om = own ? o / N : 0, on = own ? o - om * N : 0;
-  const int64_t b0 = (int64_t)blockIdx.y * per, b1 = b0 + per < B ? b0 + per : B;
-  float acc = 0.f;
-  for (int64_t bb = b0; bb < b1; bb += PL_DW_ROWS) {
-    for (int i = tid; i < PL_DW_ROWS * M; i += PL_NTHR) {
-      const int r = i / M, m = i - r * M;
-      as[i] = bb + r < b1 ? A[(bb + r) * lda + a0 + m] : 0.f;
-    }
-    for (int i = tid; i < PL_DW_ROWS * N; i += PL_NTHR) {
-      const int r = i / N, c = i - r * N;
-      gsh[i] = bb + r < b1 ? G[(bb + r) * ldg + g0 + c] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll 8
-    for (int r = 0; r < PL_DW_ROWS; ++r) acc = fmaf(as[r * M + om], gsh[r * N + on], acc);
-    __syncthreads();
-  }
-  if (own) part[(int64_t)blockIdx.y * wtot + off + om * ldo + on] = acc;
-}
+};
 
 static int pl_shape(int64_t B, int Din, int Gin, int T, int S, int Sh, int H1, int O, int Og, int last) {
   if (B < 0 || Din < 1 || T < 1 || S < 1 || Sh < 1 || H1 < 1 || O < 1 || Og < 1) return REC_E_ARG;
@@ -582,11 +497,6 @@ static int pl_shape(int64_t B, int Din, int Gin, int T, int S, int Sh, int H1, i
   return REC_OK;
 }
 
-// slices of the small weight gradients over the batch: at most 16, at least 256 examples each
-static int pl_small_split(int64_t B) {
-  const int64_t s = B / 256;
-  return s < 1 ? 1 : (s > 16 ? 16 : (int)s);
-}
 static int pl_small_floats(const PlDims& d) {
   return d.ne() * d.H1 * d.O + d.Gout() * d.H1 * d.Og + d.T * d.Og * d.ns() + (d.last ? d.T * d.O : d.Og * d.ne()) +
          (d.Gin > 1 ? d.Din * d.N1() : 0);
@@ -598,17 +508,16 @@ struct PlWs {
 static PlWs pl_ws(int64_t B, const PlDims& d) {
   PlWs w{};
   const size_t b = (size_t)B, tiles = (size_t)ceil_div64(B, MB_T);
-  auto r4 = [](size_t v) { return (v + 3) & ~(size_t)3; };
-  size_t at = 0;
-  w.dz1 = at; at += r4(b * d.N1());
-  w.dze = at; at += r4(b * d.neO());
-  w.dzq = at; at += r4(b * d.GQ());
-  w.dlg = at; at += r4(b * d.GW());
-  w.dl = at; at += r4(b * d.T);
-  w.slots = at; at += r4(tiles * (size_t)pl_slot_floats(d));
-  w.part = at; at += r4((size_t)pl_small_split(B) * pl_small_floats(d));
-  w.gemm = at; at += d.Gin == 1 ? r4((size_t)mb_split(B, d.Din, d.N1()) * d.Din * d.N1()) : 0;
-  w.total = at;
+  WsCarve c;
+  w.dz1 = c.take(b * d.N1());
+  w.dze = c.take(b * d.neO());
+  w.dzq = c.take(b * d.GQ());
+  w.dlg = c.take(b * d.GW());
+  w.dl = c.take(b * d.T);
+  w.slots = c.take(tiles * (size_t)pl_slot_floats(d));
+  w.part = c.take((size_t)mb_small_split(B) * pl_small_floats(d));
+  w.gemm = c.take(d.Gin == 1 ? mb_dw_gemm_floats(B, d.Din, d.N1()) : 0);
+  w.total = c.at;
   return w;
 }
 
@@ -671,16 +580,12 @@ extern "C" int rec_ple_cgc_bwd_f32(const float* xin, const float* W1, const floa
   if (int rc = rec_slot_sum(REC_SLOTS_WAVE, pl_slot_floats(d), tiles, slots,
                             {{db1, dbe2, dbg2, dbtw}, {N1, d.neO(), d.GQ(), last ? T : 0}}, st))
     return rc;
-  const int Sl = pl_small_split(B), wtot = pl_small_floats(d);
-  const int64_t per = ceil_div64(ceil_div64(B, Sl), PL_DW_ROWS) * PL_DW_ROWS;
+  const int Sl = mb_small_split(B), wtot = pl_small_floats(d);
   int big = H1 * (O > Og ? O : Og);
   if (Og * (ne > ns ? ne : ns) > big) big = Og * (ne > ns ? ne : ns);
   if (Gin > 1 && Din * H1 > big) big = Din * H1;
-  const int maxblk = (big + PL_NTHR - 1) / PL_NTHR;
   const int mats = ne + Gout + T + (last ? T : 1) + (Gin > 1 ? d.M() : 0);
-  hipLaunchKernelGGL(ple_small_dw_kernel, dim3(mats * maxblk, Sl), dim3(PL_NTHR), 0, st, xin, h, q, y, dz1, dze, dzq,
-                     dlg, dl, B, d, maxblk, per, wtot, part);
-  REC_LAUNCH_CHECK();
+  if (int rc = small_dw_launch(PlSmall{d, xin, h, q, y, dz1, dze, dzq, dlg, dl}, mats, big, wtot, B, part, st)) return rc;
   if (int rc = rec_slot_sum(REC_SLOTS_SERIAL, wtot, Sl, part,
                             {{dWe2, dWg2, dWg3s, dWg3h, dWtw, dW1},
                              {ne * H1 * O, Gout * H1 * Og, T * Og * ns, last ? 0 : Og * ne, last ? T * O : 0,
@@ -688,7 +593,5 @@ extern "C" int rec_ple_cgc_bwd_f32(const float* xin, const float* W1, const floa
                             st))
     return rc;
   if (Gin > 1) return REC_OK;
-  // dW1 = xin^T dZ1 with both stored [B, .]: transA, K = B
-  return rec_gemm_f32(1, 0, Din, N1, B, xin, Din, dz1, N1, dW1, N1, REC_EPI_NONE, nullptr, nullptr, 0, nullptr, 0,
-                      mb_split(B, Din, N1), gws, nullptr, stream);
+  return mb_dw_gemm(Din, N1, B, xin, dz1, dW1, gws, stream);   // dW1 = xin^T dZ1
 }
