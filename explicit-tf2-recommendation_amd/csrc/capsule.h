@@ -1,7 +1,9 @@
 // What the multi-interest kernels share (mind.hip, comirec.hip): the limits and the launch cap, wave-level helpers, the
-// series / item gather into LDS, the lambda-operand MFMA block, the steps of a routing row (masked softmax over the
-// positions, weighted sum + squash, logit update), the three products around an example held in LDS (x S, du S^T and
-// x^T du with its per-workgroup slot) and the LDS bookkeeping of the one-wave-per-example item kernels.
+// series / item gather into LDS, the lambda-operand MFMA block, one routing row both ways (the forward rounds: masked
+// softmax over the positions, weighted sum + squash, logit update; the backward of a round: the squash and the softmax),
+// the three products around an example held in LDS (x S, du S^T and x^T du with its per-workgroup slot), the frame of the
+// one-wave-per-example item kernels (LDS carve, load, scores, log-sum-exp loss and its gradient) and the host side: the
+// head of the series arguments, the item arguments, the shape checks, the 4/2/1 wave ladder and the launches.
 #pragma once
 #include <float.h>
 #include <math.h>
@@ -185,6 +187,61 @@ __device__ __forceinline__ void caps_logit_update(float* Lk, const float* ck, co
   wave_sync();
 }
 
+// the R rounds of one row: the weights of round r go to W0 + r wstep with KEEP (the backward), to W0 otherwise; orow (may
+// be NULL): the row of out that c of the last round also goes to
+template <bool KEEP>
+__device__ __forceinline__ void caps_route_rounds(float* Lk, const int* part, float* W0, int wstep, const float* u, int Dcp,
+                                                  int T, int Dc, int R, float* ck, float* __restrict__ orow, int lane) {
+  for (int r = 0; r < R; ++r) {
+    float* Wk = KEEP ? W0 + (size_t)r * wstep : W0;
+    caps_softmax_row(Lk, part, Wk, T, lane);
+    caps_squash_row(Wk, u, Dcp, T, Dc, ck, r == R - 1 ? orow : nullptr, lane);
+    if (r < R - 1) caps_logit_update(Lk, ck, u, Dcp, T, Dc, lane);         // L += c u^T
+  }
+}
+// A round, back.  Neither step ends in an ordering of its own: the callers differ there.
+// s = Wk u, dc = grow (the last round: the row of gout) or dLk u  ->  dsk = squash'(s) dc, ck = squash(s)
+__device__ __forceinline__ void caps_squash_bwd_row(const float* Wk, const float* dLk, const float* u, int Dcp, int T,
+                                                    int Dc, const float* __restrict__ grow, float* dsk, float* ck,
+                                                    int lane) {
+  float n2 = 0.f, sd = 0.f;
+  for (int d = lane; d < Dc; d += 64) {
+    float acc = 0.f, dc = 0.f;
+    if (grow) {
+      dc = grow[d];
+      acc = mi_dot(Wk, u + d, Dcp, T);
+    } else {
+      mi_dot2(Wk, dLk, u + d, Dcp, T, acc, dc);
+    }
+    ck[d] = acc;
+    dsk[d] = dc;
+    n2 = fmaf(acc, acc, n2);
+    sd = fmaf(acc, dc, sd);
+  }
+  n2 = group_sum<64>(n2);
+  sd = group_sum<64>(sd);
+  const float n = sqrtf(n2), den = 1.f + n2, f = n / den;
+  const float g = n > 0.f ? (1.f - n2) / (den * den * n) * sd : 0.f;       // f'(n) / n (s . dc)
+  for (int d = lane; d < Dc; d += 64) {
+    const float sv = ck[d];
+    dsk[d] = fmaf(sv, g, f * dsk[d]);
+    ck[d] = sv * f;
+  }
+}
+// dWk = dsk u^T, dLk += part ? Wk (dWk - sum_t dWk Wk) : 0
+__device__ __forceinline__ void caps_softmax_bwd_row(const float* dsk, const float* u, int Dcp, int T, int Dc,
+                                                     const float* Wk, const int* part, float* dWk, float* dLk, int lane) {
+  float dot = 0.f;
+  for (int t = lane; t < T; t += 64) {
+    const float acc = mi_dot(dsk, u + t * Dcp, 1, Dc);
+    dWk[t] = acc;
+    dot = fmaf(acc, Wk[t], dot);
+  }
+  dot = group_sum<64>(dot);
+  for (int t = lane; t < T; t += 64)
+    if (part[t]) dLk[t] = dLk[t] + Wk[t] * (dWk[t] - dot);
+}
+
 // ---- the products around one example in LDS, by a workgroup of 4 waves ------------------------------------------------
 // u [T][Dcp] = act(xs [T][Dp] S [D, Dc]) on v_mfma_f32_32x32x2_f32, one (32 rows, 32 columns) block per wave and step, S
 // read from global memory (every workgroup reads the same few KiB); act is tanh or nothing
@@ -268,10 +325,115 @@ __device__ __forceinline__ void caps_weight_store(const f32x16 (&sacc)[NB], floa
     }
   }
 }
+
+// ---- the item kernels: one wave per example, blockDim.x / 64 examples per workgroup, no workgroup-level barrier -----
+struct ItemArgs {
+  const float* embed;
+  int64_t ld, V;
+  const int64_t* items;
+  int64_t B;
+  const float* m;
+  const int32_t* kv;                                             // NULL for the hard attention
+  int Ns, C, E, Dc, K;
+};
+// the LDS of the wave's example (la_lds_floats): m [K][Dcp], x [Ns][Dcp], the scores [K][Ns], a second [K][Ns], two [Ns]
+struct ItemLds {
+  float *ms, *xs, *sc, *w, *o, *go;
+};
+__device__ __forceinline__ ItemLds la_carve(float* lds, int wave, int Ns, int Dc, int K) {
+  ItemLds f;
+  f.ms = lds + (size_t)wave * la_lds_floats(Ns, Dc, K);
+  f.xs = f.ms + K * mi_odd(Dc);
+  f.sc = f.xs + Ns * mi_odd(Dc);
+  f.w = f.sc + K * Ns;
+  f.o = f.w + K * Ns;
+  f.go = f.o + Ns;
+  return f;
+}
+// m of example b and its looked-up items into LDS; the caller orders
+__device__ __forceinline__ void la_load(const ItemArgs& a, int64_t b, const ItemLds& f, int lane, bool& bad) {
+  const int Dc = a.Dc, Dcp = mi_odd(Dc);
+  for (int i = lane; i < a.K * Dc; i += 64) {
+    const int k = i / Dc, d = i - k * Dc;
+    f.ms[k * Dcp + d] = a.m[b * a.K * Dc + i];
+  }
+  mi_gather<64>(a.embed, a.ld, a.V, a.items + b * a.Ns * a.C, a.Ns, a.C, a.E, f.xs, Dcp, lane, bad);
+}
+// sc[k][s] = m_k . x_s
+__device__ __forceinline__ void la_scores(const ItemLds& f, int Ns, int Dc, int K, int lane) {
+  const int Dcp = mi_odd(Dc);
+  for (int i = lane; i < K * Ns; i += 64) {
+    const int k = i / Ns, s = i - k * Ns;
+    float acc = 0.f;
+    for (int d = 0; d < Dc; ++d) acc = fmaf(f.ms[k * Dcp + d], f.xs[s * Dcp + d], acc);
+    f.sc[i] = acc;
+  }
+  wave_sync();
+}
+// logsumexp_s o[s]; the loss is that minus o[0]
+__device__ __forceinline__ float la_logsumexp(const float* o, int Ns, int lane) {
+  float mx = -FLT_MAX;
+  for (int s = lane; s < Ns; s += 64) mx = fmaxf(mx, o[s]);
+  mx = wave_max(mx);
+  float sum = 0.f;
+  for (int s = lane; s < Ns; s += 64) sum += expf(o[s] - mx);
+  sum = group_sum<64>(sum);
+  return mx + logf(sum);
+}
+// go[s] = grow[s] + gl (softmax_s(o)[s] - [s == 0]); grow (may be NULL): the example's row of the gradient of o
+__device__ __forceinline__ void la_loss_grad(const ItemLds& f, float lse, float gl, const float* __restrict__ grow, int Ns,
+                                             int lane) {
+  for (int s = lane; s < Ns; s += 64) {
+    const float g = grow ? grow[s] : 0.f;
+    f.go[s] = fmaf(gl, expf(f.o[s] - lse) - (s == 0 ? 1.f : 0.f), g);
+  }
+  wave_sync();
+}
+
+// ---- the host side ---------------------------------------------------------------------------------------------------
+// what every series kernel is given first: the table, the ids [B, T, C] and the sizes (D = E C)
+struct CapsSeries {
+  const float* embed;
+  int64_t ld, V;
+  const int64_t* series;
+  int64_t B, padding_index;
+  int T, C, E, D, Dc, K;
+};
+static inline int caps_fits(size_t lds_bytes) { return lds_bytes <= MI_LDS_CAP ? REC_OK : REC_E_UNSUPPORTED; }
+// the sizes of a series family (R = 1 where it has no rounds); its LDS fit is the family's own
+static inline int caps_series_shape(int64_t B, int T, int E, int C, int Dc, int K, int R) {
+  if (B < 0 || T < 1 || E < 1 || C < 1 || Dc < 1 || K < 1 || R < 1) return REC_E_ARG;
+  if ((int64_t)E * C > MI_MAXD || Dc > MI_MAXD || K > MI_MAXK || R > MI_MAXR || B >= ((int64_t)1 << 31) ||
+      T > (int)(MI_LDS_CAP / sizeof(float)))
+    return REC_E_UNSUPPORTED;
+  return REC_OK;
+}
+// waves of a workgroup when each holds `one` bytes of LDS: 4, 2 or 1, as many as fit; 0: not even one
+static inline int caps_waves(size_t one) {
+  return 4 * one <= MI_LDS_CAP ? 4 : (2 * one <= MI_LDS_CAP ? 2 : (one <= MI_LDS_CAP ? 1 : 0));
+}
+// one launch of a kernel whose dynamic LDS may go up to the cap
+template <auto Kernel, class... Args>
+static int caps_launch(dim3 grid, int nthr, size_t lds, hipStream_t st, Args... args) {
+  if (hipError_t err = rec_allow_lds<Kernel>(MI_LDS_CAP)) return (int)err;
+  hipLaunchKernelGGL(Kernel, grid, dim3(nthr), lds, st, args...);
+  REC_LAUNCH_CHECK();
+  return REC_OK;
+}
+// workgroups of a persistent forward: one example at a time each
+static inline int caps_fwd_grid(int64_t B) { return B < 65536 ? (int)B : 65536; }
+
 // 32 x 32 blocks of the weight gradient per wave: 1, 4 or 16
 static inline int caps_weight_nb(int D, int Dc) {
   const int nblk = ((D + 31) / 32) * ((Dc + 31) / 32), nb = (nblk + 3) / 4;
   return nb <= 1 ? 1 : (nb <= 4 ? 4 : 16);
+}
+// f(std::integral_constant<int, NB>) for that NB: the one spelling of the 1 / 4 / 16 template dispatch
+template <class Fn>
+static inline int caps_launch_nb(int nb, Fn&& f) {
+  return nb == 1   ? f(std::integral_constant<int, 1>{})
+         : nb == 4 ? f(std::integral_constant<int, 4>{})
+                   : f(std::integral_constant<int, 16>{});
 }
 // as many workgroups as the chip holds at once: 4, 2 or 1 per CU by the registers of the instantiation (1, 4 or 16 blocks
 // of the weight gradient per wave), 256 CUs; `most` workgroups at 4 per CU
@@ -281,18 +443,22 @@ static inline int caps_grid(int64_t B, int D, int Dc, int most) {
   return B < cap ? (int)B : cap;
 }
 
-// ---- the item kernels: one wave per example ------------------------------------------------------------------------
-// waves (= examples) of a workgroup: 4, 2 or 1, as many as fit; 0: not even one
-static inline int la_waves(int Ns, int Dc, int K) {
-  const size_t one = sizeof(float) * la_lds_floats(Ns, Dc, K);
-  return 4 * one <= MI_LDS_CAP ? 4 : (2 * one <= MI_LDS_CAP ? 2 : (one <= MI_LDS_CAP ? 1 : 0));
+// the item kernels: examples of a workgroup, LDS of a launch, shape check and launch
+static inline int la_waves(int Ns, int Dc, int K) { return caps_waves(sizeof(float) * la_lds_floats(Ns, Dc, K)); }
+static inline size_t la_lds_bytes(int Ns, int Dc, int K) {
+  return sizeof(float) * la_waves(Ns, Dc, K) * la_lds_floats(Ns, Dc, K);
 }
 static inline int la_shape(int64_t B, int Ns, int E, int C, int K) {
   if (B < 0 || Ns < 1 || E < 1 || C < 1 || K < 1) return REC_E_ARG;
   if ((int64_t)E * C > MI_MAXD || K > MI_MAXK || B >= ((int64_t)1 << 31) || Ns > (int)(MI_LDS_CAP / sizeof(float)))
     return REC_E_UNSUPPORTED;
-  if (la_waves(Ns, E * C, K) == 0) return REC_E_UNSUPPORTED;
-  return REC_OK;
+  return caps_fits(sizeof(float) * la_lds_floats(Ns, E * C, K));
+}
+template <auto Kernel, class... Args>
+static int la_launch(const ItemArgs& a, void* stream, Args... args) {
+  const int wpb = la_waves(a.Ns, a.Dc, a.K);
+  return caps_launch<Kernel>(dim3((unsigned)ceil_div64(a.B, wpb)), 64 * wpb, la_lds_bytes(a.Ns, a.Dc, a.K),
+                             as_stream(stream), a, args...);
 }
 
 }  // namespace

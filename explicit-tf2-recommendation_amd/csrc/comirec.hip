@@ -44,15 +44,9 @@ constexpr int CR_SLAB_MAX = 2048;               // examples of a slab of the dyn
 constexpr int64_t CR_SLAB_BYTES = 64 << 20;     // and bytes of its u [slab, K, T, Dc] (never fewer than 32 examples)
 
 // ---- (a) dynamic routing -------------------------------------------------------------------------------------------
-struct DrArgs {
-  const float* embed;
-  int64_t ld, V;
-  const int64_t* series;
-  int64_t B;
+struct DrArgs : CapsSeries {
   const float *W, *B0;
-  int64_t padding_index;
-  int keep;
-  int T, C, E, D, Dc, K, R;
+  int keep, R;
 };
 
 // floats of LDS of one row (b, k) of the routing backward, which is what both directions are held to:
@@ -61,17 +55,10 @@ __host__ __device__ inline size_t dr_row_floats(int T, int Dc, int R) {
   return (size_t)T * mi_odd(Dc) + (size_t)(2 * R + 3) * T + 2 * (size_t)R * mi_odd(Dc);
 }
 // rows (= waves) of a workgroup: 4, 2 or 1, as many as fit; 0: not even one
-static int dr_waves(int T, int Dc, int R) {
-  const size_t one = sizeof(float) * dr_row_floats(T, Dc, R);
-  return 4 * one <= MI_LDS_CAP ? 4 : (2 * one <= MI_LDS_CAP ? 2 : (one <= MI_LDS_CAP ? 1 : 0));
-}
-static int dr_shape(int64_t B, int T, int E, int C, int Dc, int K, int R) {
-  if (B < 0 || T < 1 || E < 1 || C < 1 || Dc < 1 || K < 1 || R < 1) return REC_E_ARG;
-  if ((int64_t)E * C > MI_MAXD || Dc > MI_MAXD || K > MI_MAXK || R > MI_MAXR || B >= ((int64_t)1 << 31) ||
-      T > (int)(MI_LDS_CAP / sizeof(float)))
-    return REC_E_UNSUPPORTED;
-  if (dr_waves(T, Dc, R) == 0) return REC_E_UNSUPPORTED;
-  return REC_OK;
+static int dr_waves(int T, int Dc, int R) { return caps_waves(sizeof(float) * dr_row_floats(T, Dc, R)); }
+static int dr_check(int64_t B, int T, int E, int C, int Dc, int K, int R) {
+  const int rc = caps_series_shape(B, T, E, C, Dc, K, R);
+  return rc ? rc : caps_fits(sizeof(float) * dr_row_floats(T, Dc, R));
 }
 // examples of a slab, slices of the weight gradient, floats of u and of the slots
 struct DrPlan {
@@ -187,12 +174,7 @@ __global__ __launch_bounds__(MI_NTHR) void comirec_dr_route_kernel(DrArgs a, int
     L[t] = a.B0[k * T + t];
   }
   wave_sync();
-  for (int r = 0; r < R; ++r) {
-    float* Wk = Call + (BWD ? r : 0) * T;
-    caps_softmax_row(L, part, Wk, T, lane);
-    caps_squash_row(Wk, u, Dcp, T, Dc, call, (!BWD && r == R - 1) ? out + (b * K + k) * Dc : nullptr, lane);
-    if (r < R - 1) caps_logit_update(L, call, u, Dcp, T, Dc, lane);
-  }
+  caps_route_rounds<BWD>(L, part, Call, T, u, Dcp, T, Dc, R, call, BWD ? nullptr : out + (b * K + k) * Dc, lane);
   if (!BWD) return;
 
   float* dL = L;
@@ -202,40 +184,10 @@ __global__ __launch_bounds__(MI_NTHR) void comirec_dr_route_kernel(DrArgs a, int
     const bool last = r == R - 1;
     const float* Wk = Call + r * T;
     float *dsr = dsall + r * Dcp, *cr = call + r * Dcp;
-    float n2 = 0.f, sd = 0.f;
-    for (int d = lane; d < Dc; d += 64) {                        // s, dc
-      float acc = 0.f, dc = 0.f;
-      if (last) {
-        dc = gout[(b * K + k) * Dc + d];
-        acc = mi_dot(Wk, u + d, Dcp, T);
-      } else {
-        mi_dot2(Wk, dL, u + d, Dcp, T, acc, dc);
-      }
-      cr[d] = acc;
-      dsr[d] = dc;
-      n2 = fmaf(acc, acc, n2);
-      sd = fmaf(acc, dc, sd);
-    }
-    n2 = group_sum<64>(n2);
-    sd = group_sum<64>(sd);
-    const float n = sqrtf(n2), den = 1.f + n2, f = n / den;
-    const float gs = n > 0.f ? (1.f - n2) / (den * den * n) * sd : 0.f;      // f'(n) / n (s . dc)
-    for (int d = lane; d < Dc; d += 64) {
-      const float sv = cr[d];
-      dsr[d] = fmaf(sv, gs, f * dsr[d]);
-      cr[d] = sv * f;
-    }
+    caps_squash_bwd_row(Wk, dL, u, Dcp, T, Dc, last ? gout + (b * K + k) * Dc : nullptr, dsr, cr, lane);   // s, dc
     for (int t = lane; t < T; t += 64) dLall[r * T + t] = dL[t];
     wave_sync();
-    float dot = 0.f;
-    for (int t = lane; t < T; t += 64) {                         // dW = ds u^T and the softmax, back
-      const float acc = mi_dot(dsr, u + t * Dcp, 1, Dc);
-      dW[t] = acc;
-      dot = fmaf(acc, Wk[t], dot);
-    }
-    dot = group_sum<64>(dot);
-    for (int t = lane; t < T; t += 64)
-      if (part[t]) dL[t] = dL[t] + Wk[t] * (dW[t] - dot);
+    caps_softmax_bwd_row(dsr, u, Dcp, T, Dc, Wk, part, dW, dL, lane);      // dW = ds u^T and the softmax, back
     wave_sync();
   }
   for (int i = lane; i < T * Dc; i += 64) {                      // du = sum_r C_r^T ds_r + dL_r^T c_r
@@ -341,25 +293,16 @@ static int dr_project(const DrArgs& a, int64_t s0, int ns, float* u, int* oob, h
 
 template <bool BWD>
 static int dr_route(const DrArgs& a, int64_t s0, int ns, float* ws, const float* gout, float* out, hipStream_t st) {
-  if (hipError_t err = rec_allow_lds<comirec_dr_route_kernel<BWD>>(MI_LDS_CAP)) return (int)err;
   const int wpb = dr_waves(a.T, a.Dc, a.R);
-  const size_t lds = sizeof(float) * wpb * dr_row_floats(a.T, a.Dc, a.R);
-  hipLaunchKernelGGL(comirec_dr_route_kernel<BWD>, dim3((unsigned)ceil_div64((int64_t)ns * a.K, wpb)), dim3(64 * wpb), lds,
-                     st, a, s0, ns, ws, gout, out);
-  REC_LAUNCH_CHECK();
-  return REC_OK;
+  return caps_launch<comirec_dr_route_kernel<BWD>>(dim3((unsigned)ceil_div64((int64_t)ns * a.K, wpb)), 64 * wpb,
+                                                   sizeof(float) * wpb * dr_row_floats(a.T, a.Dc, a.R), st, a, s0, ns, ws,
+                                                   gout, out);
 }
 
 // ---- (b) self-attentive extractor ------------------------------------------------------------------------------------
-struct SaArgs {
-  const float* embed;
-  int64_t ld, V;
-  const int64_t* series;
-  int64_t B;
+struct SaArgs : CapsSeries {
   const float *W1, *W2, *pos;
-  int64_t padding_index;
   int keep;
-  int T, C, E, D, Dc, K;
 };
 
 // floats of LDS of the backward, which is what both directions are held to:
@@ -371,13 +314,9 @@ __host__ __device__ inline size_t sa_lds_floats(int T, int D, int Dc, int K) {
 __host__ __device__ inline size_t sa_fwd_lds_floats(int T, int D, int Dc, int K) {
   return (size_t)T * mi_odd(D) + (size_t)T * mi_odd(Dc) + 2 * (size_t)K * T + (size_t)K * mi_odd(Dc) + T;
 }
-static int sa_shape(int64_t B, int T, int E, int C, int Dc, int K) {
-  if (B < 0 || T < 1 || E < 1 || C < 1 || Dc < 1 || K < 1) return REC_E_ARG;
-  if ((int64_t)E * C > MI_MAXD || Dc > MI_MAXD || K > MI_MAXK || B >= ((int64_t)1 << 31) ||
-      T > (int)(MI_LDS_CAP / sizeof(float)))
-    return REC_E_UNSUPPORTED;
-  if (sizeof(float) * sa_lds_floats(T, E * C, Dc, K) > MI_LDS_CAP) return REC_E_UNSUPPORTED;
-  return REC_OK;
+static int sa_check(int64_t B, int T, int E, int C, int Dc, int K) {
+  const int rc = caps_series_shape(B, T, E, C, Dc, K, 1);
+  return rc ? rc : caps_fits(sizeof(float) * sa_lds_floats(T, E * C, Dc, K));
 }
 
 __device__ __forceinline__ void sa_load_w2(const SaArgs& a, float* w2s, int tid) {
@@ -505,30 +444,11 @@ __global__ __launch_bounds__(MI_NTHR, NB == 1 ? 4 : 1) void comirec_sa_bwd_kerne
   }
 }
 
-template <int NB>
-static int sa_launch_bwd(const SaArgs& a, int grid, size_t lds, const float* gout, float* gkeys, float* slots,
-                         hipStream_t st) {
-  if (hipError_t err = rec_allow_lds<comirec_sa_bwd_kernel<NB>>(MI_LDS_CAP)) return (int)err;
-  hipLaunchKernelGGL(comirec_sa_bwd_kernel<NB>, dim3(grid), dim3(MI_NTHR), lds, st, a, gout, gkeys, slots);
-  REC_LAUNCH_CHECK();
-  return REC_OK;
-}
-
 // ---- (c) hard attention + loss ---------------------------------------------------------------------------------------
-struct SelArgs {
-  const float* embed;
-  int64_t ld, V;
-  const int64_t* items;
-  int64_t B;
-  const float* m;
-  int Ns, C, E, Dc, K;
-};
-
-// One wave per example; blockDim.x / 64 examples per workgroup.  A wave past the batch leaves: there is no workgroup-level
-// barrier.  The LDS of an example is the label-aware attention's: m, x, p [K][Ns], chosen [Ns] (of the second [K][Ns]),
-// inner and g [Ns].
+// One wave per example.  A wave past the batch leaves: there is no workgroup-level barrier.  The LDS of an example is
+// the label-aware attention's: m, x, p [K][Ns], chosen [Ns] (of the second [K][Ns]), inner and g [Ns].
 template <bool BWD>
-__global__ __launch_bounds__(MI_NTHR) void comirec_select_kernel(SelArgs a, int32_t* __restrict__ chosen,
+__global__ __launch_bounds__(MI_NTHR) void comirec_select_kernel(ItemArgs a, int32_t* __restrict__ chosen,
                                                                  float* __restrict__ inner, float* __restrict__ loss,
                                                                  const float* __restrict__ ginner,
                                                                  const float* __restrict__ gloss,
@@ -540,19 +460,12 @@ __global__ __launch_bounds__(MI_NTHR) void comirec_select_kernel(SelArgs a, int3
   const int Ns = a.Ns, Dc = a.Dc, K = a.K, Dcp = mi_odd(Dc);
   const int64_t b = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;
   if (b >= a.B) return;
-  float* ms = lds + (size_t)wave * la_lds_floats(Ns, Dc, K);     // [K][Dcp]
-  float* xs = ms + K * Dcp;                                      // [Ns][Dcp]
-  float* p = xs + Ns * Dcp;                                      // [K][Ns]
-  int* ch = reinterpret_cast<int*>(p + K * Ns);                  // [Ns]
-  float* o = p + 2 * K * Ns;                                     // [Ns]
-  float* go = o + Ns;                                            // [Ns]
+  const ItemLds f = la_carve(lds, wave, Ns, Dc, K);
+  float *ms = f.ms, *xs = f.xs, *p = f.sc, *o = f.o, *go = f.go;
+  int* ch = reinterpret_cast<int*>(f.w);                         // [Ns]
   bool bad = false;
 
-  for (int i = lane; i < K * Dc; i += 64) {
-    const int k = i / Dc, d = i - k * Dc;
-    ms[k * Dcp + d] = a.m[b * K * Dc + i];
-  }
-  mi_gather<64>(a.embed, a.ld, a.V, a.items + b * Ns * a.C, Ns, a.C, a.E, xs, Dcp, lane, bad);
+  la_load(a, b, f, lane, bad);
   if (BWD)
     for (int s = lane; s < Ns; s += 64) {
       const int c = chosen[b * Ns + s];
@@ -560,13 +473,7 @@ __global__ __launch_bounds__(MI_NTHR) void comirec_select_kernel(SelArgs a, int3
     }
   wave_sync();
   if (!BWD) {
-    for (int i = lane; i < K * Ns; i += 64) {
-      const int k = i / Ns, s = i - k * Ns;
-      float acc = 0.f;
-      for (int d = 0; d < Dc; ++d) acc = fmaf(ms[k * Dcp + d], xs[s * Dcp + d], acc);
-      p[i] = acc;
-    }
-    wave_sync();
+    la_scores(f, Ns, Dc, K, lane);
     for (int s = lane; s < Ns; s += 64) {
       int best = 0;
       float bv = p[s];
@@ -590,24 +497,13 @@ __global__ __launch_bounds__(MI_NTHR) void comirec_select_kernel(SelArgs a, int3
     }
   }
   wave_sync();
-  float mx = -FLT_MAX;
-  for (int s = lane; s < Ns; s += 64) mx = fmaxf(mx, o[s]);
-  mx = wave_max(mx);
-  float sum = 0.f;
-  for (int s = lane; s < Ns; s += 64) sum += expf(o[s] - mx);
-  sum = group_sum<64>(sum);
-  const float lse = mx + logf(sum);
+  const float lse = la_logsumexp(o, Ns, lane);
   if (!BWD) {
     if (lane == 0) loss[b] = lse - o[0];
     if (bad && oob) *oob = 1;
     return;
   }
-  const float gl = gloss ? gloss[b] : 0.f;
-  for (int s = lane; s < Ns; s += 64) {
-    const float g = ginner ? ginner[b * Ns + s] : 0.f;
-    go[s] = fmaf(gl, expf(o[s] - lse) - (s == 0 ? 1.f : 0.f), g);
-  }
-  wave_sync();
+  la_loss_grad(f, lse, gloss ? gloss[b] : 0.f, ginner ? ginner + b * Ns : nullptr, Ns, lane);
   for (int i = lane; i < K * Dc; i += 64) {
     const int k = i / Dc, d = i - k * Dc;
     float acc = 0.f;
@@ -627,7 +523,7 @@ __global__ __launch_bounds__(MI_NTHR) void comirec_select_kernel(SelArgs a, int3
 }  // namespace
 
 extern "C" size_t rec_comirec_dr_workspace_bytes(int64_t B, int T, int E, int C, int Dc, int K, int R) {
-  if (dr_shape(B, T, E, C, Dc, K, R) != REC_OK) return 0;
+  if (dr_check(B, T, E, C, Dc, K, R) != REC_OK) return 0;
   const DrPlan p = dr_plan(B, T, E * C, Dc, K);
   return sizeof(float) * (p.u_floats + p.slot_floats + 4);
 }
@@ -636,14 +532,14 @@ extern "C" int rec_comirec_dr_fwd_f32(const float* embed, int64_t ld, int64_t V,
                                       int64_t B, int T, const float* W, const float* B0, int Dc, int K, int R,
                                       int64_t padding_index, int keep_padding, float* out, int* oob_flag, void* workspace,
                                       size_t workspace_bytes, void* stream) {
-  if (int rc = dr_shape(B, T, E, C, Dc, K, R)) return rc;
+  if (int rc = dr_check(B, T, E, C, Dc, K, R)) return rc;
   if (ld < E || V <= 0 || !embed || !series || !W || !B0 || !out || !workspace) return REC_E_ARG;
   const int D = E * C;
   const DrPlan p = dr_plan(B, T, D, Dc, K);
   if (workspace_bytes < sizeof(float) * p.u_floats) return REC_E_WORKSPACE;
   if (B == 0) return REC_OK;
   hipStream_t st = as_stream(stream);
-  const DrArgs a{embed, ld, V, series, B, W, B0, padding_index, keep_padding, T, C, E, D, Dc, K, R};
+  const DrArgs a{{embed, ld, V, series, B, padding_index, T, C, E, D, Dc, K}, W, B0, keep_padding, R};
   float* u = static_cast<float*>(workspace);
   for (int64_t s0 = 0; s0 < B; s0 += p.slab) {
     const int ns = (int)(B - s0 < p.slab ? B - s0 : p.slab);
@@ -657,14 +553,14 @@ extern "C" int rec_comirec_dr_bwd_f32(const float* embed, int64_t ld, int64_t V,
                                       int64_t B, int T, const float* W, const float* B0, int Dc, int K, int R,
                                       int64_t padding_index, int keep_padding, const float* gout, float* gkeys, float* dW,
                                       void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = dr_shape(B, T, E, C, Dc, K, R)) return rc;
+  if (int rc = dr_check(B, T, E, C, Dc, K, R)) return rc;
   if (ld < E || V <= 0 || !embed || !series || !W || !B0 || !gout || !gkeys || !dW || !workspace) return REC_E_ARG;
   const int D = E * C;
   const DrPlan p = dr_plan(B, T, D, Dc, K);
   if (workspace_bytes < sizeof(float) * (p.u_floats + p.slot_floats)) return REC_E_WORKSPACE;
   if (B == 0) return REC_OK;                                     // nothing is launched and nothing written
   hipStream_t st = as_stream(stream);
-  const DrArgs a{embed, ld, V, series, B, W, B0, padding_index, keep_padding, T, C, E, D, Dc, K, R};
+  const DrArgs a{{embed, ld, V, series, B, padding_index, T, C, E, D, Dc, K}, W, B0, keep_padding, R};
   float* u = static_cast<float*>(workspace);
   float* slots = u + p.u_floats;
   for (int64_t s0 = 0; s0 < B; s0 += p.slab) {
@@ -683,50 +579,45 @@ extern "C" int rec_comirec_dr_bwd_f32(const float* embed, int64_t ld, int64_t V,
 }
 
 extern "C" size_t rec_comirec_sa_workspace_bytes(int64_t B, int T, int E, int C, int Dc, int K) {
-  if (sa_shape(B, T, E, C, Dc, K) != REC_OK) return 0;
+  if (sa_check(B, T, E, C, Dc, K) != REC_OK) return 0;
   return sizeof(float) * ((size_t)caps_grid(B, E * C, Dc, CR_GRID) * (E * C + K) * Dc + 4);
 }
 
 extern "C" int rec_comirec_sa_fwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* series,
                                       int64_t B, int T, const float* W1, const float* W2, const float* pos, int Dc, int K,
                                       int64_t padding_index, int keep_padding, float* out, int* oob_flag, void* stream) {
-  if (int rc = sa_shape(B, T, E, C, Dc, K)) return rc;
+  if (int rc = sa_check(B, T, E, C, Dc, K)) return rc;
   if (ld < E || V <= 0 || !embed || !series || !W1 || !W2 || !out) return REC_E_ARG;
   if (B == 0) return REC_OK;
-  const SaArgs a{embed, ld, V, series, B, W1, W2, pos, padding_index, keep_padding, T, C, E, E * C, Dc, K};
-  if (hipError_t err = rec_allow_lds<comirec_sa_fwd_kernel>(MI_LDS_CAP)) return (int)err;
-  const size_t lds = sizeof(float) * sa_fwd_lds_floats(T, E * C, Dc, K);
-  const int grid = B < 65536 ? (int)B : 65536;
-  hipLaunchKernelGGL(comirec_sa_fwd_kernel, dim3(grid), dim3(MI_NTHR), lds, as_stream(stream), a, out, oob_flag);
-  REC_LAUNCH_CHECK();
-  return REC_OK;
+  const SaArgs a{{embed, ld, V, series, B, padding_index, T, C, E, E * C, Dc, K}, W1, W2, pos, keep_padding};
+  return caps_launch<comirec_sa_fwd_kernel>(dim3(caps_fwd_grid(B)), MI_NTHR,
+                                            sizeof(float) * sa_fwd_lds_floats(T, E * C, Dc, K), as_stream(stream), a, out,
+                                            oob_flag);
 }
 
 extern "C" int rec_comirec_sa_bwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* series,
                                       int64_t B, int T, const float* W1, const float* W2, const float* pos, int Dc, int K,
                                       int64_t padding_index, int keep_padding, const float* gout, float* gkeys,
                                       float* dW1, float* dW2, void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = sa_shape(B, T, E, C, Dc, K)) return rc;
+  if (int rc = sa_check(B, T, E, C, Dc, K)) return rc;
   if (ld < E || V <= 0 || !embed || !series || !W1 || !W2 || !gout || !gkeys || !dW1 || !dW2 || !workspace)
     return REC_E_ARG;
   const int D = E * C, grid = caps_grid(B, D, Dc, CR_GRID);
   if (workspace_bytes < sizeof(float) * (size_t)grid * (D + K) * Dc) return REC_E_WORKSPACE;
   if (B == 0) return REC_OK;                                     // nothing is launched and nothing written
   hipStream_t st = as_stream(stream);
-  const SaArgs a{embed, ld, V, series, B, W1, W2, pos, padding_index, keep_padding, T, C, E, D, Dc, K};
+  const SaArgs a{{embed, ld, V, series, B, padding_index, T, C, E, D, Dc, K}, W1, W2, pos, keep_padding};
   const size_t lds = sizeof(float) * sa_lds_floats(T, D, Dc, K);
   float* slots = static_cast<float*>(workspace);
-  const int nb = caps_weight_nb(D, Dc);
-  const int rc = nb == 1   ? sa_launch_bwd<1>(a, grid, lds, gout, gkeys, slots, st)
-                 : nb == 4 ? sa_launch_bwd<4>(a, grid, lds, gout, gkeys, slots, st)
-                           : sa_launch_bwd<16>(a, grid, lds, gout, gkeys, slots, st);
+  const int rc = caps_launch_nb(caps_weight_nb(D, Dc), [&](auto nb) {
+    return caps_launch<comirec_sa_bwd_kernel<nb.value>>(dim3(grid), MI_NTHR, lds, st, a, gout, gkeys, slots);
+  });
   if (rc) return rc;
   return rec_slot_sum(REC_SLOTS_WAVE, (D + K) * Dc, grid, slots, {{dW1, dW2}, {D * Dc, K * Dc}}, st);
 }
 
 extern "C" size_t rec_comirec_select_lds_bytes(int Ns, int E, int C, int K) {
-  if (la_shape(0, Ns, E, C, K) != REC_OK) return 0;
-  return sizeof(float) * la_waves(Ns, E * C, K) * la_lds_floats(Ns, E * C, K);
+  return la_shape(0, Ns, E, C, K) == REC_OK ? la_lds_bytes(Ns, E * C, K) : 0;
 }
 
 extern "C" int rec_comirec_select_fwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* items,
@@ -735,14 +626,8 @@ extern "C" int rec_comirec_select_fwd_f32(const float* embed, int64_t ld, int64_
   if (int rc = la_shape(B, Ns, E, C, K)) return rc;
   if (ld < E || V <= 0 || !embed || !items || !m || !chosen || !inner || !loss) return REC_E_ARG;
   if (B == 0) return REC_OK;
-  const int Dc = E * C, wpb = la_waves(Ns, Dc, K);
-  const SelArgs a{embed, ld, V, items, B, m, Ns, C, E, Dc, K};
-  if (hipError_t err = rec_allow_lds<comirec_select_kernel<false>>(MI_LDS_CAP)) return (int)err;
-  const size_t lds = sizeof(float) * wpb * la_lds_floats(Ns, Dc, K);
-  hipLaunchKernelGGL(comirec_select_kernel<false>, dim3((unsigned)ceil_div64(B, wpb)), dim3(64 * wpb), lds,
-                     as_stream(stream), a, chosen, inner, loss, nullptr, nullptr, nullptr, nullptr, nullptr, oob_flag);
-  REC_LAUNCH_CHECK();
-  return REC_OK;
+  return la_launch<comirec_select_kernel<false>>({embed, ld, V, items, B, m, nullptr, Ns, C, E, E * C, K}, stream, chosen,
+                                                 inner, loss, nullptr, nullptr, nullptr, nullptr, nullptr, oob_flag);
 }
 
 extern "C" int rec_comirec_select_bwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* items,
@@ -752,13 +637,7 @@ extern "C" int rec_comirec_select_bwd_f32(const float* embed, int64_t ld, int64_
   if (int rc = la_shape(B, Ns, E, C, K)) return rc;
   if (ld < E || V <= 0 || !embed || !items || !m || !chosen || (!ginner && !gloss) || !gm || !gitems) return REC_E_ARG;
   if (B == 0) return REC_OK;
-  const int Dc = E * C, wpb = la_waves(Ns, Dc, K);
-  const SelArgs a{embed, ld, V, items, B, m, Ns, C, E, Dc, K};
-  if (hipError_t err = rec_allow_lds<comirec_select_kernel<true>>(MI_LDS_CAP)) return (int)err;
-  const size_t lds = sizeof(float) * wpb * la_lds_floats(Ns, Dc, K);
-  hipLaunchKernelGGL(comirec_select_kernel<true>, dim3((unsigned)ceil_div64(B, wpb)), dim3(64 * wpb), lds,
-                     as_stream(stream), a, const_cast<int32_t*>(chosen), nullptr, nullptr, ginner, gloss, gsel, gm,
-                     gitems, nullptr);
-  REC_LAUNCH_CHECK();
-  return REC_OK;
+  return la_launch<comirec_select_kernel<true>>({embed, ld, V, items, B, m, nullptr, Ns, C, E, E * C, K}, stream,
+                                                const_cast<int32_t*>(chosen), nullptr, nullptr, ginner, gloss, gsel, gm,
+                                                gitems, nullptr);
 }

@@ -52,14 +52,9 @@ __host__ __device__ inline size_t rt_fwd_lds_floats(int T, int D, int Dc, int K)
   return (size_t)T * mi_odd(D) + (size_t)T * mi_odd(Dc) + 2 * (size_t)K * T + (size_t)K * mi_odd(Dc) + T;
 }
 
-struct RtArgs {
-  const float* embed;
-  int64_t ld, V;
-  const int64_t* series;
-  int64_t B;
+struct RtArgs : CapsSeries {
   const float *S, *B0;
-  int64_t padding_index;
-  int T, C, E, D, Dc, K, R;
+  int R;
 };
 
 // The rows of example b into xs, valid, L <- B0, u = x S, and the R rounds.  KEEP: W of round r goes to Wall[r] (the
@@ -81,16 +76,9 @@ __device__ __forceinline__ void rt_forward(const RtArgs& a, int64_t b, float* xs
   caps_project<false>(xs, Dp, a.S, T, D, Dc, u, Dcp, wave, lo, hi);        // u = x S
   __syncthreads();
 
-  for (int k = wave; k < K; k += 4) {                            // a row needs no other row
-    float* Lk = L + k * T;
-    float* ck = c + k * Dcp;
-    for (int r = 0; r < R; ++r) {
-      float* Wk = (KEEP ? Wall + (size_t)r * K * T : Wall) + k * T;
-      caps_softmax_row(Lk, valid, Wk, T, lane);
-      caps_squash_row(Wk, u, Dcp, T, Dc, ck, (out && r == R - 1) ? out + ((int64_t)b * K + k) * Dc : nullptr, lane);
-      if (r < R - 1) caps_logit_update(Lk, ck, u, Dcp, T, Dc, lane);     // L += c u^T
-    }
-  }
+  for (int k = wave; k < K; k += 4)                              // a row needs no other row
+    caps_route_rounds<KEEP>(L + k * T, valid, Wall + k * T, K * T, u, Dcp, T, Dc, R, c + k * Dcp,
+                            out ? out + ((int64_t)b * K + k) * Dc : nullptr, lane);
 }
 
 __global__ __launch_bounds__(MI_NTHR) void mind_routing_fwd_kernel(RtArgs a, float* __restrict__ out,
@@ -143,34 +131,9 @@ __global__ __launch_bounds__(MI_NTHR, NB == 1 ? 4 : 1) void mind_routing_bwd_ker
     for (int r = R - 1; r >= 0; --r) {
       const bool last = r == R - 1;
       const float* Wr = Wall + (size_t)r * K * T;
-      for (int k = wave; k < K; k += 4) {                        // s, dc -> ds, c of the row
-        const float* Wk = Wr + k * T;
-        const float* dLk = dL + k * T;
-        float *dsk = ds + k * Dcp, *ck = c + k * Dcp;
-        float n2 = 0.f, sd = 0.f;
-        for (int d = lane; d < Dc; d += 64) {
-          float acc = 0.f, dc = 0.f;
-          if (last) {
-            dc = gout[((int64_t)b * K + k) * Dc + d];
-            acc = mi_dot(Wk, u + d, Dcp, T);
-          } else {
-            mi_dot2(Wk, dLk, u + d, Dcp, T, acc, dc);
-          }
-          ck[d] = acc;
-          dsk[d] = dc;
-          n2 = fmaf(acc, acc, n2);
-          sd = fmaf(acc, dc, sd);
-        }
-        n2 = group_sum<64>(n2);
-        sd = group_sum<64>(sd);
-        const float n = sqrtf(n2), den = 1.f + n2, f = n / den;
-        const float g = n > 0.f ? (1.f - n2) / (den * den * n) * sd : 0.f;     // f'(n) / n (s . dc)
-        for (int d = lane; d < Dc; d += 64) {
-          const float sv = ck[d];
-          dsk[d] = fmaf(sv, g, f * dsk[d]);
-          ck[d] = sv * f;
-        }
-      }
+      for (int k = wave; k < K; k += 4)                          // s, dc -> ds, c of the row
+        caps_squash_bwd_row(Wr + k * T, dL + k * T, u, Dcp, T, Dc, last ? gout + ((int64_t)b * K + k) * Dc : nullptr,
+                            ds + k * Dcp, c + k * Dcp, lane);
       __syncthreads();
       for (int i = tid; i < T * Dc; i += MI_NTHR) {              // du += W_r^T ds + dL^T c
         const int t = i / Dc, d = i - t * Dc;
@@ -182,20 +145,8 @@ __global__ __launch_bounds__(MI_NTHR, NB == 1 ? 4 : 1) void mind_routing_bwd_ker
         du[t * Dcp + d] = acc;
       }
       __syncthreads();
-      for (int k = wave; k < K; k += 4) {                        // dW = ds u^T and the softmax, back
-        const float* Wk = Wr + k * T;
-        const float* dsk = ds + k * Dcp;
-        float *dLk = dL + k * T, *dWk = dW + k * T;
-        float dot = 0.f;
-        for (int t = lane; t < T; t += 64) {
-          const float acc = mi_dot(dsk, u + t * Dcp, 1, Dc);
-          dWk[t] = acc;
-          dot = fmaf(acc, Wk[t], dot);
-        }
-        dot = group_sum<64>(dot);
-        for (int t = lane; t < T; t += 64)
-          if (valid[t]) dLk[t] = dLk[t] + Wk[t] * (dWk[t] - dot);
-      }
+      for (int k = wave; k < K; k += 4)                          // dW = ds u^T and the softmax, back
+        caps_softmax_bwd_row(ds + k * Dcp, u, Dcp, T, Dc, Wr + k * T, valid, dW + k * T, dL + k * T, lane);
       __syncthreads();
     }
 
@@ -207,54 +158,26 @@ __global__ __launch_bounds__(MI_NTHR, NB == 1 ? 4 : 1) void mind_routing_bwd_ker
   caps_weight_store<NB>(sacc, slots + (int64_t)blockIdx.x * D * Dc, D, Dc, wave, lo, hi);
 }
 
-struct LaArgs {
-  const float* embed;
-  int64_t ld, V;
-  const int64_t* items;
-  int64_t B;
-  const float* m;
-  const int32_t* kv;
-  int Ns, C, E, Dc, K;
-};
-
-// One wave per example; blockDim.x / 64 examples per workgroup.  A wave past the batch computes on zeros and writes nothing.
+// One wave per example.  A wave past the batch leaves: there is no workgroup-level barrier.
 template <bool BWD>
-__global__ __launch_bounds__(MI_NTHR) void mind_laa_kernel(LaArgs a, float* __restrict__ out, float* __restrict__ loss,
+__global__ __launch_bounds__(MI_NTHR) void mind_laa_kernel(ItemArgs a, float* __restrict__ out, float* __restrict__ loss,
                                                            const float* __restrict__ gout,
                                                            const float* __restrict__ gloss, float* __restrict__ gm,
                                                            float* __restrict__ gitems, int* __restrict__ oob) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int Ns = a.Ns, C = a.C, E = a.E, Dc = a.Dc, K = a.K, Dcp = mi_odd(Dc);
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int Ns = a.Ns, Dc = a.Dc, K = a.K, Dcp = mi_odd(Dc);
   const int64_t b = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;
-  const bool live = b < a.B;
-  float* ms = lds + (size_t)wave * la_lds_floats(Ns, Dc, K);     // [K][Dcp]
-  float* xs = ms + K * Dcp;                                      // [Ns][Dcp]
-  float* sc = xs + Ns * Dcp;                                     // [K][Ns]: the scores, then dsc
-  float* w = sc + K * Ns;                                        // [K][Ns]
-  float* o = w + K * Ns;                                         // [Ns]
-  float* go = o + Ns;                                            // [Ns]
-  const int kv = live ? a.kv[b] : 0;
+  if (b >= a.B) return;
+  const ItemLds f = la_carve(lds, wave, Ns, Dc, K);
+  float *ms = f.ms, *xs = f.xs, *sc = f.sc, *w = f.w, *o = f.o;  // sc: the scores, then dsc
+  const int kv = a.kv[b];
   bool bad = false;
 
-  for (int i = lane; i < K * Dc; i += 64) {
-    const int k = i / Dc, d = i - k * Dc;
-    ms[k * Dcp + d] = live ? a.m[((int64_t)b * K + k) * Dc + d] : 0.f;
-  }
-  if (live) {
-    mi_gather<64>(a.embed, a.ld, a.V, a.items + b * Ns * C, Ns, C, E, xs, Dcp, lane, bad);
-  } else {
-    for (int i = lane; i < Ns * Dcp; i += 64) xs[i] = 0.f;
-  }
+  la_load(a, b, f, lane, bad);
   wave_sync();
-  for (int i = lane; i < K * Ns; i += 64) {
-    const int k = i / Ns, sI = i - k * Ns;
-    float acc = 0.f;
-    for (int d = 0; d < Dc; ++d) acc = fmaf(ms[k * Dcp + d], xs[sI * Dcp + d], acc);
-    sc[i] = acc;
-  }
-  wave_sync();
+  la_scores(f, Ns, Dc, K, lane);
   for (int sI = lane; sI < Ns; sI += 64) {
     float mx = -FLT_MAX;
     for (int k = 0; k < K; ++k) mx = fmaxf(mx, k < kv ? sc[k * Ns + sI] : -FLT_MAX);
@@ -271,113 +194,84 @@ __global__ __launch_bounds__(MI_NTHR) void mind_laa_kernel(LaArgs a, float* __re
       ov = fmaf(wv, sc[k * Ns + sI], ov);
     }
     o[sI] = ov;
-    if (!BWD && live) out[b * Ns + sI] = ov;
+    if (!BWD) out[b * Ns + sI] = ov;
   }
   wave_sync();
-  float mx = -FLT_MAX;
-  for (int sI = lane; sI < Ns; sI += 64) mx = fmaxf(mx, o[sI]);
-  mx = wave_max(mx);
-  float sum = 0.f;
-  for (int sI = lane; sI < Ns; sI += 64) sum += expf(o[sI] - mx);
-  sum = group_sum<64>(sum);
-  const float lse = mx + logf(sum);
+  const float lse = la_logsumexp(o, Ns, lane);
   if (!BWD) {
-    if (lane == 0 && live) loss[b] = lse - o[0];
-  } else {
-    const float gl = (gloss && live) ? gloss[b] : 0.f;
-    for (int sI = lane; sI < Ns; sI += 64) {
-      float g = (gout && live) ? gout[b * Ns + sI] : 0.f;
-      g = fmaf(gl, expf(o[sI] - lse) - (sI == 0 ? 1.f : 0.f), g);
-      go[sI] = g;
-    }
-    wave_sync();
-    for (int i = lane; i < K * Ns; i += 64) {
-      const int k = i / Ns, sI = i - k * Ns;
-      const float wv = w[i];
-      sc[i] = go[sI] * (k < kv ? fmaf(wv, sc[i] - o[sI], wv) : wv);
-    }
-    wave_sync();
-    for (int i = lane; i < K * Dc; i += 64) {
-      const int k = i / Dc, d = i - k * Dc;
-      float acc = 0.f;
-      for (int sI = 0; sI < Ns; ++sI) acc = fmaf(sc[k * Ns + sI], xs[sI * Dcp + d], acc);
-      if (live) gm[((int64_t)b * K + k) * Dc + d] = acc;
-    }
-    for (int i = lane; i < Ns * Dc; i += 64) {
-      const int sI = i / Dc, d = i - sI * Dc;
-      float acc = 0.f;
-      for (int k = 0; k < K; ++k) acc = fmaf(sc[k * Ns + sI], ms[k * Dcp + d], acc);
-      if (live) gitems[((int64_t)b * Ns + sI) * Dc + d] = acc;
-    }
+    if (lane == 0) loss[b] = lse - o[0];
+    if (bad && oob) *oob = 1;
+    return;
   }
-  if (!BWD && bad && oob) *oob = 1;
+  la_loss_grad(f, lse, gloss ? gloss[b] : 0.f, gout ? gout + b * Ns : nullptr, Ns, lane);
+  for (int i = lane; i < K * Ns; i += 64) {
+    const int k = i / Ns, sI = i - k * Ns;
+    const float wv = w[i];
+    sc[i] = f.go[sI] * (k < kv ? fmaf(wv, sc[i] - o[sI], wv) : wv);
+  }
+  wave_sync();
+  for (int i = lane; i < K * Dc; i += 64) {
+    const int k = i / Dc, d = i - k * Dc;
+    float acc = 0.f;
+    for (int sI = 0; sI < Ns; ++sI) acc = fmaf(sc[k * Ns + sI], xs[sI * Dcp + d], acc);
+    gm[((int64_t)b * K + k) * Dc + d] = acc;
+  }
+  for (int i = lane; i < Ns * Dc; i += 64) {
+    const int sI = i / Dc, d = i - sI * Dc;
+    float acc = 0.f;
+    for (int k = 0; k < K; ++k) acc = fmaf(sc[k * Ns + sI], ms[k * Dcp + d], acc);
+    gitems[((int64_t)b * Ns + sI) * Dc + d] = acc;
+  }
 }
 
-static int rt_shape(int64_t B, int T, int E, int C, int Dc, int K, int R) {
-  if (B < 0 || T < 1 || E < 1 || C < 1 || Dc < 1 || K < 1 || R < 1) return REC_E_ARG;
-  if ((int64_t)E * C > MI_MAXD || Dc > MI_MAXD || K > MI_MAXK || R > MI_MAXR || B >= ((int64_t)1 << 31) ||
-      T > (int)(MI_LDS_CAP / sizeof(float)))
-    return REC_E_UNSUPPORTED;
-  if (sizeof(float) * rt_lds_floats(T, E * C, Dc, K, R) > MI_LDS_CAP) return REC_E_UNSUPPORTED;
-  return REC_OK;
+// the sizes and the LDS fit of the routing
+static int rt_check(int64_t B, int T, int E, int C, int Dc, int K, int R) {
+  const int rc = caps_series_shape(B, T, E, C, Dc, K, R);
+  return rc ? rc : caps_fits(sizeof(float) * rt_lds_floats(T, E * C, Dc, K, R));
 }
 static int rt_grid(int64_t B, int D, int Dc) { return caps_grid(B, D, Dc, MI_GRID); }
-
-template <int NB>
-static int rt_launch_bwd(const RtArgs& a, int grid, size_t lds, const float* gout, float* gkeys, float* slots,
-                         hipStream_t st) {
-  if (hipError_t err = rec_allow_lds<mind_routing_bwd_kernel<NB>>(MI_LDS_CAP)) return (int)err;
-  hipLaunchKernelGGL(mind_routing_bwd_kernel<NB>, dim3(grid), dim3(MI_NTHR), lds, st, a, gout, gkeys, slots);
-  REC_LAUNCH_CHECK();
-  return REC_OK;
-}
 
 }  // namespace
 
 extern "C" size_t rec_mind_routing_workspace_bytes(int64_t B, int T, int E, int C, int Dc, int K, int R) {
-  if (rt_shape(B, T, E, C, Dc, K, R) != REC_OK) return 0;
+  if (rt_check(B, T, E, C, Dc, K, R) != REC_OK) return 0;
   return sizeof(float) * ((size_t)rt_grid(B, E * C, Dc) * E * C * Dc + 4);
 }
 
 extern "C" int rec_mind_routing_fwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* series,
                                         int64_t B, int T, const float* S, const float* B0, int Dc, int K, int R,
                                         int64_t padding_index, float* out, int* oob_flag, void* stream) {
-  if (int rc = rt_shape(B, T, E, C, Dc, K, R)) return rc;
+  if (int rc = rt_check(B, T, E, C, Dc, K, R)) return rc;
   if (ld < E || V <= 0 || !embed || !series || !S || !B0 || !out) return REC_E_ARG;
   if (B == 0) return REC_OK;
-  const RtArgs a{embed, ld, V, series, B, S, B0, padding_index, T, C, E, E * C, Dc, K, R};
-  if (hipError_t err = rec_allow_lds<mind_routing_fwd_kernel>(MI_LDS_CAP)) return (int)err;
-  const size_t lds = sizeof(float) * rt_fwd_lds_floats(T, E * C, Dc, K);
-  const int grid = B < 65536 ? (int)B : 65536;
-  hipLaunchKernelGGL(mind_routing_fwd_kernel, dim3(grid), dim3(MI_NTHR), lds, as_stream(stream), a, out, oob_flag);
-  REC_LAUNCH_CHECK();
-  return REC_OK;
+  const RtArgs a{{embed, ld, V, series, B, padding_index, T, C, E, E * C, Dc, K}, S, B0, R};
+  return caps_launch<mind_routing_fwd_kernel>(dim3(caps_fwd_grid(B)), MI_NTHR,
+                                              sizeof(float) * rt_fwd_lds_floats(T, E * C, Dc, K), as_stream(stream), a, out,
+                                              oob_flag);
 }
 
 extern "C" int rec_mind_routing_bwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* series,
                                         int64_t B, int T, const float* S, const float* B0, int Dc, int K, int R,
                                         int64_t padding_index, const float* gout, float* gkeys, float* dS,
                                         void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = rt_shape(B, T, E, C, Dc, K, R)) return rc;
+  if (int rc = rt_check(B, T, E, C, Dc, K, R)) return rc;
   if (ld < E || V <= 0 || !embed || !series || !S || !B0 || !gout || !gkeys || !dS || !workspace) return REC_E_ARG;
   const int D = E * C, grid = rt_grid(B, D, Dc);
   if (workspace_bytes < sizeof(float) * (size_t)grid * D * Dc) return REC_E_WORKSPACE;
   hipStream_t st = as_stream(stream);
   if (B == 0) return REC_OK;                                     // nothing is launched and nothing written
-  const RtArgs a{embed, ld, V, series, B, S, B0, padding_index, T, C, E, D, Dc, K, R};
+  const RtArgs a{{embed, ld, V, series, B, padding_index, T, C, E, D, Dc, K}, S, B0, R};
   const size_t lds = sizeof(float) * rt_lds_floats(T, D, Dc, K, R);
   float* slots = static_cast<float*>(workspace);
-  const int nb = caps_weight_nb(D, Dc);
-  const int rc = nb == 1   ? rt_launch_bwd<1>(a, grid, lds, gout, gkeys, slots, st)
-                 : nb == 4 ? rt_launch_bwd<4>(a, grid, lds, gout, gkeys, slots, st)
-                           : rt_launch_bwd<16>(a, grid, lds, gout, gkeys, slots, st);
+  const int rc = caps_launch_nb(caps_weight_nb(D, Dc), [&](auto nb) {
+    return caps_launch<mind_routing_bwd_kernel<nb.value>>(dim3(grid), MI_NTHR, lds, st, a, gout, gkeys, slots);
+  });
   if (rc) return rc;
   return rec_slot_sum(REC_SLOTS_WAVE, D * Dc, grid, slots, {{dS}, {D * Dc}}, st);
 }
 
 extern "C" size_t rec_mind_laa_lds_bytes(int Ns, int E, int C, int K) {
-  if (la_shape(0, Ns, E, C, K) != REC_OK) return 0;
-  return sizeof(float) * la_waves(Ns, E * C, K) * la_lds_floats(Ns, E * C, K);
+  return la_shape(0, Ns, E, C, K) == REC_OK ? la_lds_bytes(Ns, E * C, K) : 0;
 }
 
 extern "C" int rec_mind_laa_fwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* items,
@@ -386,14 +280,8 @@ extern "C" int rec_mind_laa_fwd_f32(const float* embed, int64_t ld, int64_t V, i
   if (int rc = la_shape(B, Ns, E, C, K)) return rc;
   if (ld < E || V <= 0 || !embed || !items || !m || !kv || !out || !loss) return REC_E_ARG;
   if (B == 0) return REC_OK;
-  const int Dc = E * C, wpb = la_waves(Ns, Dc, K);
-  const LaArgs a{embed, ld, V, items, B, m, kv, Ns, C, E, Dc, K};
-  if (hipError_t err = rec_allow_lds<mind_laa_kernel<false>>(MI_LDS_CAP)) return (int)err;
-  const size_t lds = sizeof(float) * wpb * la_lds_floats(Ns, Dc, K);
-  hipLaunchKernelGGL(mind_laa_kernel<false>, dim3((unsigned)ceil_div64(B, wpb)), dim3(64 * wpb), lds, as_stream(stream),
-                     a, out, loss, nullptr, nullptr, nullptr, nullptr, oob_flag);
-  REC_LAUNCH_CHECK();
-  return REC_OK;
+  return la_launch<mind_laa_kernel<false>>({embed, ld, V, items, B, m, kv, Ns, C, E, E * C, K}, stream, out, loss, nullptr,
+                                           nullptr, nullptr, nullptr, oob_flag);
 }
 
 extern "C" int rec_mind_laa_bwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* items,
@@ -402,12 +290,6 @@ extern "C" int rec_mind_laa_bwd_f32(const float* embed, int64_t ld, int64_t V, i
   if (int rc = la_shape(B, Ns, E, C, K)) return rc;
   if (ld < E || V <= 0 || !embed || !items || !m || !kv || (!gout && !gloss) || !gm || !gitems) return REC_E_ARG;
   if (B == 0) return REC_OK;
-  const int Dc = E * C, wpb = la_waves(Ns, Dc, K);
-  const LaArgs a{embed, ld, V, items, B, m, kv, Ns, C, E, Dc, K};
-  if (hipError_t err = rec_allow_lds<mind_laa_kernel<true>>(MI_LDS_CAP)) return (int)err;
-  const size_t lds = sizeof(float) * wpb * la_lds_floats(Ns, Dc, K);
-  hipLaunchKernelGGL(mind_laa_kernel<true>, dim3((unsigned)ceil_div64(B, wpb)), dim3(64 * wpb), lds, as_stream(stream),
-                     a, nullptr, nullptr, gout, gloss, gm, gitems, nullptr);
-  REC_LAUNCH_CHECK();
-  return REC_OK;
+  return la_launch<mind_laa_kernel<true>>({embed, ld, V, items, B, m, kv, Ns, C, E, E * C, K}, stream, nullptr, nullptr,
+                                          gout, gloss, gm, gitems, nullptr);
 }

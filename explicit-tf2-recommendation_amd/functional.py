@@ -911,6 +911,13 @@ class PLELevel(torch.autograd.Function):
         return (dxin, None, None, None, None) + tuple(grads)
 
 
+def _series_grad(ctx, series, gkeys, V, E):
+    """the table's gradient of a fused series / item lookup: sparse COO, rows de-duplicated"""
+    if not ctx.needs_input_grad[0]:
+        return None
+    return _sparse_grad(ops.DedupPlan(series, V), gkeys.reshape(-1, E), E, (V, E))
+
+
 class CapsuleRouting(torch.autograd.Function):
     """MultiInterestExtractorLayer.call fused with the series lookup (6.MIND/CustomLayers.py:111-138, 204-212;
     csrc/mind.hip): table, series ids [B,T,C], S [C E, Dc], the non-trainable logits B0 [K,T] -> the capsules [B,K,Dc].
@@ -930,11 +937,7 @@ class CapsuleRouting(torch.autograd.Function):
         embed, series, S, B0 = ctx.saved_tensors
         V, E = embed.shape
         gkeys, dS = ops.mind_routing_bwd(embed, series, S, B0, gout.contiguous(), *ctx.cfg)
-        gembed = None
-        if ctx.needs_input_grad[0]:
-            plan = ops.DedupPlan(series, V)
-            gembed = _sparse_grad(plan, gkeys.reshape(-1, E), E, (V, E))
-        return gembed, None, dS, None, None, None, None
+        return _series_grad(ctx, series, gkeys, V, E), None, dS, None, None, None, None
 
 
 class LabelAwareAttention(torch.autograd.Function):
@@ -958,17 +961,9 @@ class LabelAwareAttention(torch.autograd.Function):
         gm, gitems = ops.mind_laa_bwd(embed, items, m, kv, None if gout is None else gout.contiguous(),
                                       None if gloss is None else gloss.contiguous())
         gembed = None
-        if ctx.needs_input_grad[0] and (gout is not None or gloss is not None):
-            plan = ops.DedupPlan(items, V)
-            gembed = _sparse_grad(plan, gitems.reshape(-1, E), E, (V, E))
+        if gout is not None or gloss is not None:
+            gembed = _series_grad(ctx, items, gitems, V, E)
         return gembed, None, gm, None, None
-
-
-def _series_grad(ctx, series, gkeys, V, E):
-    """the table's gradient of a fused series / item lookup: sparse COO, rows de-duplicated"""
-    if not ctx.needs_input_grad[0]:
-        return None
-    return _sparse_grad(ops.DedupPlan(series, V), gkeys.reshape(-1, E), E, (V, E))
 
 
 class ComiRecRouting(torch.autograd.Function):

@@ -1736,6 +1736,76 @@ def _odd(n):
     return n | 1
 
 
+# what the MIND, ComiRec and CAN wrappers share
+def _caps_limits(family, D, Dc, K, R, rounds):
+    """NotImplementedError past the limits of the capsule kernels; ``rounds`` is the format R is shown with"""
+    if D > DIN_MAX_D or Dc > DIN_MAX_D or K > AFM_MAX_A or (R is not None and R > MIND_MAX_ROUNDS):
+        raise NotImplementedError(
+            "%s kernels cover key width and capsule width <= %d, capsules <= %d and routing rounds <= %d; got key "
+            "width=%d, capsule width=%d, capsules=%d, rounds=%s"
+            % (family, DIN_MAX_D, AFM_MAX_A, MIND_MAX_ROUNDS, D, Dc, K, rounds % (R,)))
+
+
+def _lds_fit(nbytes, holds, formula, at):
+    """NotImplementedError where what a kernel holds in LDS (``nbytes`` = 4 (``formula``)) passes the launch cap"""
+    if nbytes > _MIND_LDS_CAP:
+        raise NotImplementedError("%s in LDS: 4 (%s) <= %d bytes; got %d at %s"
+                                  % (holds, formula, _MIND_LDS_CAP, nbytes, at))
+
+
+def _items_fit(family, Ns, Dc, K):
+    _lds_fit(mind_laa_lds_bytes(Ns, Dc, K), "%s attention holds one example" % family,
+             "(K + Ns) (Dc|1) + 2 K Ns + 2 Ns", "Ns=%d, capsule width=%d, capsules=%d" % (Ns, Dc, K))
+
+
+def _caps_head(what, embed, *named):
+    """The checks and the arguments every capsule entry point starts with: the table, then ``named``, (tensor, "name
+    [a,b,..]", dtype if not fp32) each -- the int64 ids [B, n, C] first -- of that dtype and with as many dimensions as
+    its label.  -> the leading ABI arguments (table, stride, V, E, C, ids, B, n) and (V, E, B, n, C)."""
+    _table(embed, "embed")
+    for t, label, *dtype in named:
+        _req(t, dtype[0] if dtype else torch.float32, label.split()[0])
+    if any(t.dim() != label.count(",") + 1 for t, label, *_ in named):
+        raise ValueError("%s takes %s and %s; got %s" % (what, ", ".join(x[1] for x in named[:-1]), named[-1][1],
+                                                         ", ".join(str(tuple(x[0].shape)) for x in named)))
+    (V, E), (B, n, Cn) = embed.shape, named[0][0].shape
+    return [_ptr(embed), embed.stride(0), V, E, Cn, _ptr(named[0][0]), B, n], (V, E, B, n, Cn)
+
+
+def _series_head(embed, series, what, *weights):
+    return _caps_head(what, embed, (series, "series [B,T,C]", torch.int64), *weights)
+
+
+def _items_head(embed, items, m, what, *more):
+    return _caps_head(what, embed, (items, "items [B,Ns,C]", torch.int64), (m, "m [B,K,Dc]"), *more)
+
+
+def _expect(t, shape, name, label, dtype=torch.float32, optional=False):
+    """``t`` is a contiguous tensor of ``dtype`` and ``shape`` on the device (or, with ``optional``, None); ``label``
+    spells the shape in the error, which shows a one-dimensional shape as [n]"""
+    if t is None and optional:
+        return
+    if tuple(_req(t, dtype, name).shape) != shape:
+        raise ValueError("%s must be %s = %s, got %s"
+                         % (name, label, "[%d]" % shape if len(shape) == 1 else shape, tuple(t.shape)))
+
+
+def _new(shape, dev, B=1, dtype=torch.float32):
+    """an output the launch writes in full; zeros where the batch ``B`` is empty and nothing is launched"""
+    return (torch.zeros if B == 0 else torch.empty)(shape, dtype=dtype, device=dev)
+
+
+def _call(fn, *args):
+    check(getattr(lib, fn)(*args, _stream()), fn)
+
+
+def _call_ws(query, query_args, fn, dev, *args):
+    """``fn`` with the workspace that ``query`` asks for at ``query_args``"""
+    nbytes = getattr(lib, query)(*query_args)
+    ws = _workspace(nbytes, query, dev, torch.float32)
+    _call(fn, *args, _ptr(ws), nbytes)
+
+
 def mind_routing_lds_bytes(T, D, Dc, K, R):
     """LDS of one workgroup of the routing backward (include/mi355rec.h): what both directions are held to."""
     return 4 * (T * _odd(D) + 2 * T * _odd(Dc) + (R + 2) * K * T + 2 * K * _odd(Dc) + T)
@@ -1754,45 +1824,33 @@ def mind_check_shape(D, Dc, K, R=3, T=None, Ns=None):
     if min(sizes) < 1:
         raise ValueError("every size of a MIND body must be positive, got D=%d, Dc=%d, capsules=%d, rounds=%d, T=%r, "
                          "Ns=%r" % (D, Dc, K, R, T, Ns))
-    if D > DIN_MAX_D or Dc > DIN_MAX_D or K > AFM_MAX_A or R > MIND_MAX_ROUNDS:
-        raise NotImplementedError(
-            "MIND kernels cover key width and capsule width <= %d, capsules <= %d and routing rounds <= %d; got key "
-            "width=%d, capsule width=%d, capsules=%d, rounds=%d" % (DIN_MAX_D, AFM_MAX_A, MIND_MAX_ROUNDS, D, Dc, K, R))
-    if T is not None and mind_routing_lds_bytes(T, D, Dc, K, R) > _MIND_LDS_CAP:
-        raise NotImplementedError(
-            "MIND routing holds one example in LDS: 4 (T (D|1) + 2 T (Dc|1) + (R + 2) K T + 2 K (Dc|1) + T) <= %d bytes; "
-            "got %d at T=%d, key width=%d, capsule width=%d, capsules=%d, rounds=%d"
-            % (_MIND_LDS_CAP, mind_routing_lds_bytes(T, D, Dc, K, R), T, D, Dc, K, R))
-    if Ns is not None and mind_laa_lds_bytes(Ns, Dc, K) > _MIND_LDS_CAP:
-        raise NotImplementedError(
-            "MIND label-aware attention holds one example in LDS: 4 ((K + Ns) (Dc|1) + 2 K Ns + 2 Ns) <= %d bytes; got "
-            "%d at Ns=%d, capsule width=%d, capsules=%d" % (_MIND_LDS_CAP, mind_laa_lds_bytes(Ns, Dc, K), Ns, Dc, K))
+    _caps_limits("MIND", D, Dc, K, R, "%d")
+    if T is not None:
+        _lds_fit(mind_routing_lds_bytes(T, D, Dc, K, R), "MIND routing holds one example",
+                 "T (D|1) + 2 T (Dc|1) + (R + 2) K T + 2 K (Dc|1) + T",
+                 "T=%d, key width=%d, capsule width=%d, capsules=%d, rounds=%d" % (T, D, Dc, K, R))
+    if Ns is not None:
+        _items_fit("MIND label-aware", Ns, Dc, K)
 
 
 def _mind_routing_args(embed, series, S, B0, R, padding_index):
-    _table(embed, "embed"); _i64(series, "series"); _f32(S, "S"); _f32(B0, "B0")
-    if series.dim() != 3 or S.dim() != 2 or B0.dim() != 2:
-        raise ValueError("capsule routing takes series [B,T,C], S [D,Dc] and B0 [K,T]; got %s, %s, %s"
-                         % (tuple(series.shape), tuple(S.shape), tuple(B0.shape)))
-    V, E = embed.shape
-    B, T, Cn = series.shape
+    args, (V, E, B, T, Cn) = _series_head(embed, series, "capsule routing", (S, "S [D,Dc]"), (B0, "B0 [K,T]"))
     D, Dc = S.shape
     K = B0.shape[0]
     if D != Cn * E or B0.shape[1] != T:
         raise ValueError("capsule routing: S must have C E = %d rows and B0 T = %d columns; got S %s, B0 %s"
                          % (Cn * E, T, tuple(S.shape), tuple(B0.shape)))
     mind_check_shape(D, Dc, K, int(R), T=T)
-    return [_ptr(embed), embed.stride(0), V, E, Cn, _ptr(series), B, T, _ptr(S), _ptr(B0), Dc, K, int(R),
-            int(padding_index)], (B, T, Cn, E, D, Dc, K)
+    return args + [_ptr(S), _ptr(B0), Dc, K, int(R), int(padding_index)], (B, T, Cn, E, D, Dc, K)
 
 
 def mind_routing_fwd(embed, series, S, B0, routing_rounds=3, padding_index=0, oob=None):
     """Capsule routing of MultiInterestExtractorLayer over the looked-up series in one launch: series ids [B,T,C] into
     ``embed``, S [C E, Dc], B0 [K, T] -> the squashed capsules of the last round [B, K, Dc].  Nothing else is saved."""
     args, (B, T, Cn, E, D, Dc, K) = _mind_routing_args(embed, series, S, B0, routing_rounds, padding_index)
-    out = torch.empty((B, K, Dc), dtype=torch.float32, device=embed.device)
+    out = _new((B, K, Dc), embed.device)
     if B > 0:                                            # an empty batch answers from the sizes alone
-        check(lib.rec_mind_routing_fwd_f32(*args, _ptr(out), _ptr(oob), _stream()), "rec_mind_routing_fwd_f32")
+        _call("rec_mind_routing_fwd_f32", *args, _ptr(out), _ptr(oob))
     return out
 
 
@@ -1800,33 +1858,23 @@ def mind_routing_bwd(embed, series, S, B0, gout, routing_rounds=3, padding_index
     """-> (gkeys [B,T,C E], the IndexedSlices values of the series lookups, dS [C E, Dc]) from gout [B,K,Dc]; the rounds
     are run again from the ids and differentiated through, all of them.  B0 has no gradient."""
     args, (B, T, Cn, E, D, Dc, K) = _mind_routing_args(embed, series, S, B0, routing_rounds, padding_index)
-    if tuple(_f32(gout, "gout").shape) != (B, K, Dc):
-        raise ValueError("gout must be [B,K,Dc] = %s, got %s" % ((B, K, Dc), tuple(gout.shape)))
+    _expect(gout, (B, K, Dc), "gout", "[B,K,Dc]")
     dev = embed.device
-    gkeys = torch.empty((B, T, D), dtype=torch.float32, device=dev)
-    dS = torch.zeros((D, Dc), dtype=torch.float32, device=dev) if B == 0 else \
-        torch.empty((D, Dc), dtype=torch.float32, device=dev)
+    gkeys, dS = _new((B, T, D), dev), _new((D, Dc), dev, B)
     if B > 0:
-        nbytes = lib.rec_mind_routing_workspace_bytes(B, T, E, Cn, Dc, K, int(routing_rounds))
-        ws = _workspace(nbytes, "rec_mind_routing_workspace_bytes", dev, torch.float32)
-        check(lib.rec_mind_routing_bwd_f32(*args, _ptr(gout), _ptr(gkeys), _ptr(dS), _ptr(ws), nbytes, _stream()),
-              "rec_mind_routing_bwd_f32")
+        _call_ws("rec_mind_routing_workspace_bytes", (B, T, E, Cn, Dc, K, int(routing_rounds)),
+                 "rec_mind_routing_bwd_f32", dev, *args, _ptr(gout), _ptr(gkeys), _ptr(dS))
     return gkeys, dS
 
 
 def _mind_laa_args(embed, items, m, kv):
-    _table(embed, "embed"); _i64(items, "items"); _f32(m, "m"); _req(kv, torch.int32, "kv")
-    if items.dim() != 3 or m.dim() != 3 or kv.dim() != 1:
-        raise ValueError("label-aware attention takes items [B,Ns,C], m [B,K,Dc] and kv [B]; got %s, %s, %s"
-                         % (tuple(items.shape), tuple(m.shape), tuple(kv.shape)))
-    V, E = embed.shape
-    B, Ns, Cn = items.shape
+    args, (V, E, B, Ns, Cn) = _items_head(embed, items, m, "label-aware attention", (kv, "kv [B]", torch.int32))
     K, Dc = m.shape[1:]
     if m.shape[0] != B or kv.shape[0] != B or Dc != Cn * E:
         raise ValueError("label-aware attention: m must be [B, K, C E] = [%d, K, %d] and kv [%d]; got m %s, kv %s"
                          % (B, Cn * E, B, tuple(m.shape), tuple(kv.shape)))
     mind_check_shape(Dc, Dc, K, 1, Ns=Ns)
-    return [_ptr(embed), embed.stride(0), V, E, Cn, _ptr(items), B, Ns, _ptr(m), _ptr(kv), K], (B, Ns, Dc, K)
+    return args + [_ptr(m), _ptr(kv), K], (B, Ns, Dc, K)
 
 
 def mind_laa_fwd(embed, items, m, kv, oob=None):
@@ -1834,10 +1882,9 @@ def mind_laa_fwd(embed, items, m, kv, oob=None):
     launch: item ids [B,Ns,C] into ``embed``, capsules m [B,K,C E], valid capsule counts kv int32 [B] -> (out [B,Ns],
     loss [B]) with the label at sample 0."""
     args, (B, Ns, Dc, K) = _mind_laa_args(embed, items, m, kv)
-    out = torch.empty((B, Ns), dtype=torch.float32, device=embed.device)
-    loss = torch.empty((B,), dtype=torch.float32, device=embed.device)
+    out, loss = _new((B, Ns), embed.device), _new((B,), embed.device)
     if B > 0:
-        check(lib.rec_mind_laa_fwd_f32(*args, _ptr(out), _ptr(loss), _ptr(oob), _stream()), "rec_mind_laa_fwd_f32")
+        _call("rec_mind_laa_fwd_f32", *args, _ptr(out), _ptr(loss), _ptr(oob))
     return out, loss
 
 
@@ -1847,17 +1894,12 @@ def mind_laa_bwd(embed, items, m, kv, gout=None, gloss=None):
     args, (B, Ns, Dc, K) = _mind_laa_args(embed, items, m, kv)
     dev = embed.device
     if gout is None and gloss is None:
-        return (torch.zeros((B, K, Dc), dtype=torch.float32, device=dev),
-                torch.zeros((B, Ns, Dc), dtype=torch.float32, device=dev))
-    if gout is not None and tuple(_f32(gout, "gout").shape) != (B, Ns):
-        raise ValueError("gout must be [B,Ns] = %s, got %s" % ((B, Ns), tuple(gout.shape)))
-    if gloss is not None and tuple(_f32(gloss, "gloss").shape) != (B,):
-        raise ValueError("gloss must be [B] = [%d], got %s" % (B, tuple(gloss.shape)))
-    gm = torch.empty((B, K, Dc), dtype=torch.float32, device=dev)
-    gitems = torch.empty((B, Ns, Dc), dtype=torch.float32, device=dev)
+        return _new((B, K, Dc), dev, B=0), _new((B, Ns, Dc), dev, B=0)
+    _expect(gout, (B, Ns), "gout", "[B,Ns]", optional=True)
+    _expect(gloss, (B,), "gloss", "[B]", optional=True)
+    gm, gitems = _new((B, K, Dc), dev), _new((B, Ns, Dc), dev)
     if B > 0:
-        check(lib.rec_mind_laa_bwd_f32(*args, _ptr(gout), _ptr(gloss), _ptr(gm), _ptr(gitems), _stream()),
-              "rec_mind_laa_bwd_f32")
+        _call("rec_mind_laa_bwd_f32", *args, _ptr(gout), _ptr(gloss), _ptr(gm), _ptr(gitems))
     return gm, gitems
 
 
@@ -1881,39 +1923,27 @@ def comirec_check_shape(D, Dc, K, R=None, T=None, mode="DR", Ns=None):
     if min(sizes) < 1:
         raise ValueError("every size of a ComiRec body must be positive, got D=%d, Dc=%d, capsules=%d, rounds=%r, T=%r, "
                          "Ns=%r" % (D, Dc, K, R, T, Ns))
-    if D > DIN_MAX_D or Dc > DIN_MAX_D or K > AFM_MAX_A or (R is not None and R > MIND_MAX_ROUNDS):
-        raise NotImplementedError(
-            "ComiRec kernels cover key width and capsule width <= %d, capsules <= %d and routing rounds <= %d; got key "
-            "width=%d, capsule width=%d, capsules=%d, rounds=%r" % (DIN_MAX_D, AFM_MAX_A, MIND_MAX_ROUNDS, D, Dc, K, R))
-    if T is not None and mode == "DR" and comirec_dr_lds_bytes(T, Dc, R) > _MIND_LDS_CAP:
-        raise NotImplementedError(
-            "ComiRec dynamic routing holds one row (b, k) in LDS: 4 (T (Dc|1) + (2 R + 3) T + 2 R (Dc|1)) <= %d bytes; "
-            "got %d at T=%d, capsule width=%d, rounds=%d" % (_MIND_LDS_CAP, comirec_dr_lds_bytes(T, Dc, R), T, Dc, R))
-    if T is not None and mode == "SA" and comirec_sa_lds_bytes(T, D, Dc, K) > _MIND_LDS_CAP:
-        raise NotImplementedError(
-            "ComiRec self-attention holds one example in LDS: 4 (T (D|1) + 2 T (Dc|1) + 2 K T + 3 K (Dc|1) + T) <= %d "
-            "bytes; got %d at T=%d, key width=%d, capsule width=%d, capsules=%d"
-            % (_MIND_LDS_CAP, comirec_sa_lds_bytes(T, D, Dc, K), T, D, Dc, K))
-    if Ns is not None and mind_laa_lds_bytes(Ns, Dc, K) > _MIND_LDS_CAP:
-        raise NotImplementedError(
-            "ComiRec hard attention holds one example in LDS: 4 ((K + Ns) (Dc|1) + 2 K Ns + 2 Ns) <= %d bytes; got %d at "
-            "Ns=%d, capsule width=%d, capsules=%d" % (_MIND_LDS_CAP, mind_laa_lds_bytes(Ns, Dc, K), Ns, Dc, K))
+    _caps_limits("ComiRec", D, Dc, K, R, "%r")
+    if T is not None and mode == "DR":
+        _lds_fit(comirec_dr_lds_bytes(T, Dc, R), "ComiRec dynamic routing holds one row (b, k)",
+                 "T (Dc|1) + (2 R + 3) T + 2 R (Dc|1)", "T=%d, capsule width=%d, rounds=%d" % (T, Dc, R))
+    if T is not None and mode == "SA":
+        _lds_fit(comirec_sa_lds_bytes(T, D, Dc, K), "ComiRec self-attention holds one example",
+                 "T (D|1) + 2 T (Dc|1) + 2 K T + 3 K (Dc|1) + T",
+                 "T=%d, key width=%d, capsule width=%d, capsules=%d" % (T, D, Dc, K))
+    if Ns is not None:
+        _items_fit("ComiRec hard", Ns, Dc, K)
 
 
 def _comirec_dr_args(embed, series, W, B0, R, padding_index, keep_padding):
-    _table(embed, "embed"); _i64(series, "series"); _f32(W, "W"); _f32(B0, "B0")
-    if series.dim() != 3 or W.dim() != 4 or B0.dim() != 2:
-        raise ValueError("dynamic routing takes series [B,T,C], W [K,T,D,Dc] and B0 [K,T]; got %s, %s, %s"
-                         % (tuple(series.shape), tuple(W.shape), tuple(B0.shape)))
-    V, E = embed.shape
-    B, T, Cn = series.shape
+    args, (V, E, B, T, Cn) = _series_head(embed, series, "dynamic routing", (W, "W [K,T,D,Dc]"), (B0, "B0 [K,T]"))
     K, Tw, D, Dc = W.shape
     if D != Cn * E or Tw != T or tuple(B0.shape) != (K, T):
         raise ValueError("dynamic routing: W must be [K, T = %d, C E = %d, Dc] and B0 [K, T]; got W %s, B0 %s"
                          % (T, Cn * E, tuple(W.shape), tuple(B0.shape)))
     comirec_check_shape(D, Dc, K, int(R), T=T, mode="DR")
-    return [_ptr(embed), embed.stride(0), V, E, Cn, _ptr(series), B, T, _ptr(W), _ptr(B0), Dc, K, int(R),
-            int(padding_index), int(bool(keep_padding))], (B, T, Cn, E, D, Dc, K)
+    return args + [_ptr(W), _ptr(B0), Dc, K, int(R), int(padding_index), int(bool(keep_padding))], \
+        (B, T, Cn, E, D, Dc, K)
 
 
 def comirec_dr_fwd(embed, series, W, B0, routing_rounds=3, padding_index=0, keep_padding=True, oob=None):
@@ -1921,12 +1951,10 @@ def comirec_dr_fwd(embed, series, W, B0, routing_rounds=3, padding_index=0, keep
     -> the squashed capsules of the last round [B,K,Dc].  Position t takes part iff (series[b,t,0] == padding_index) ==
     keep_padding.  Nothing else is saved."""
     args, (B, T, Cn, E, D, Dc, K) = _comirec_dr_args(embed, series, W, B0, routing_rounds, padding_index, keep_padding)
-    out = torch.empty((B, K, Dc), dtype=torch.float32, device=embed.device)
+    out = _new((B, K, Dc), embed.device)
     if B > 0:                                            # an empty batch answers from the sizes alone
-        nbytes = lib.rec_comirec_dr_workspace_bytes(B, T, E, Cn, Dc, K, int(routing_rounds))
-        ws = _workspace(nbytes, "rec_comirec_dr_workspace_bytes", embed.device, torch.float32)
-        check(lib.rec_comirec_dr_fwd_f32(*args, _ptr(out), _ptr(oob), _ptr(ws), nbytes, _stream()),
-              "rec_comirec_dr_fwd_f32")
+        _call_ws("rec_comirec_dr_workspace_bytes", (B, T, E, Cn, Dc, K, int(routing_rounds)), "rec_comirec_dr_fwd_f32",
+                 embed.device, *args, _ptr(out), _ptr(oob))
     return out
 
 
@@ -1934,77 +1962,57 @@ def comirec_dr_bwd(embed, series, W, B0, gout, routing_rounds=3, padding_index=0
     """-> (gkeys [B,T,C E], the IndexedSlices values of the series lookups, dW [K,T,C E,Dc]) from gout [B,K,Dc]; the
     projection and the rounds are run again and differentiated through, all of them.  B0 has no gradient."""
     args, (B, T, Cn, E, D, Dc, K) = _comirec_dr_args(embed, series, W, B0, routing_rounds, padding_index, keep_padding)
-    if tuple(_f32(gout, "gout").shape) != (B, K, Dc):
-        raise ValueError("gout must be [B,K,Dc] = %s, got %s" % ((B, K, Dc), tuple(gout.shape)))
+    _expect(gout, (B, K, Dc), "gout", "[B,K,Dc]")
     dev = embed.device
-    gkeys = torch.empty((B, T, D), dtype=torch.float32, device=dev)
-    dW = (torch.zeros if B == 0 else torch.empty)((K, T, D, Dc), dtype=torch.float32, device=dev)
+    gkeys, dW = _new((B, T, D), dev), _new((K, T, D, Dc), dev, B)
     if B > 0:
-        nbytes = lib.rec_comirec_dr_workspace_bytes(B, T, E, Cn, Dc, K, int(routing_rounds))
-        ws = _workspace(nbytes, "rec_comirec_dr_workspace_bytes", dev, torch.float32)
-        check(lib.rec_comirec_dr_bwd_f32(*args, _ptr(gout), _ptr(gkeys), _ptr(dW), _ptr(ws), nbytes, _stream()),
-              "rec_comirec_dr_bwd_f32")
+        _call_ws("rec_comirec_dr_workspace_bytes", (B, T, E, Cn, Dc, K, int(routing_rounds)), "rec_comirec_dr_bwd_f32",
+                 dev, *args, _ptr(gout), _ptr(gkeys), _ptr(dW))
     return gkeys, dW
 
 
 def _comirec_sa_args(embed, series, W1, W2, pos, padding_index, keep_padding):
-    _table(embed, "embed"); _i64(series, "series"); _f32(W1, "W1"); _f32(W2, "W2")
-    if series.dim() != 3 or W1.dim() != 2 or W2.dim() != 2:
-        raise ValueError("self-attention takes series [B,T,C], W1 [D,Dc] and W2 [K,Dc]; got %s, %s, %s"
-                         % (tuple(series.shape), tuple(W1.shape), tuple(W2.shape)))
-    V, E = embed.shape
-    B, T, Cn = series.shape
+    args, (V, E, B, T, Cn) = _series_head(embed, series, "self-attention", (W1, "W1 [D,Dc]"), (W2, "W2 [K,Dc]"))
     D, Dc = W1.shape
     K = W2.shape[0]
     if D != Cn * E or W2.shape[1] != Dc:
         raise ValueError("self-attention: W1 must have C E = %d rows and W2 Dc = %d columns; got W1 %s, W2 %s"
                          % (Cn * E, Dc, tuple(W1.shape), tuple(W2.shape)))
-    if pos is not None and tuple(_f32(pos, "pos").shape) != (T, D):
-        raise ValueError("pos must be [T,D] = %s, got %s" % ((T, D), tuple(pos.shape)))
+    _expect(pos, (T, D), "pos", "[T,D]", optional=True)
     comirec_check_shape(D, Dc, K, T=T, mode="SA")
-    return [_ptr(embed), embed.stride(0), V, E, Cn, _ptr(series), B, T, _ptr(W1), _ptr(W2), _ptr(pos), Dc, K,
-            int(padding_index), int(bool(keep_padding))], (B, T, Cn, E, D, Dc, K)
+    return args + [_ptr(W1), _ptr(W2), _ptr(pos), Dc, K, int(padding_index), int(bool(keep_padding))], \
+        (B, T, Cn, E, D, Dc, K)
 
 
 def comirec_sa_fwd(embed, series, W1, W2, pos=None, padding_index=0, keep_padding=True, oob=None):
     """ComiRecSelfAttentiveLayer over the looked-up series in one launch: h = tanh((x + pos) W1), K heads h W2^T, masked
     softmax over the positions -> the weighted sums of h [B,K,Dc].  ``pos`` [T,C E] or None."""
     args, (B, T, Cn, E, D, Dc, K) = _comirec_sa_args(embed, series, W1, W2, pos, padding_index, keep_padding)
-    out = torch.empty((B, K, Dc), dtype=torch.float32, device=embed.device)
+    out = _new((B, K, Dc), embed.device)
     if B > 0:
-        check(lib.rec_comirec_sa_fwd_f32(*args, _ptr(out), _ptr(oob), _stream()), "rec_comirec_sa_fwd_f32")
+        _call("rec_comirec_sa_fwd_f32", *args, _ptr(out), _ptr(oob))
     return out
 
 
 def comirec_sa_bwd(embed, series, W1, W2, gout, pos=None, padding_index=0, keep_padding=True):
     """-> (gkeys [B,T,C E], dW1 [C E,Dc], dW2 [K,Dc]) from gout [B,K,Dc]; ``pos`` is a constant."""
     args, (B, T, Cn, E, D, Dc, K) = _comirec_sa_args(embed, series, W1, W2, pos, padding_index, keep_padding)
-    if tuple(_f32(gout, "gout").shape) != (B, K, Dc):
-        raise ValueError("gout must be [B,K,Dc] = %s, got %s" % ((B, K, Dc), tuple(gout.shape)))
+    _expect(gout, (B, K, Dc), "gout", "[B,K,Dc]")
     dev = embed.device
-    make = torch.zeros if B == 0 else torch.empty
-    gkeys = torch.empty((B, T, D), dtype=torch.float32, device=dev)
-    dW1, dW2 = make((D, Dc), dtype=torch.float32, device=dev), make((K, Dc), dtype=torch.float32, device=dev)
+    gkeys, dW1, dW2 = _new((B, T, D), dev), _new((D, Dc), dev, B), _new((K, Dc), dev, B)
     if B > 0:
-        nbytes = lib.rec_comirec_sa_workspace_bytes(B, T, E, Cn, Dc, K)
-        ws = _workspace(nbytes, "rec_comirec_sa_workspace_bytes", dev, torch.float32)
-        check(lib.rec_comirec_sa_bwd_f32(*args, _ptr(gout), _ptr(gkeys), _ptr(dW1), _ptr(dW2), _ptr(ws), nbytes,
-                                         _stream()), "rec_comirec_sa_bwd_f32")
+        _call_ws("rec_comirec_sa_workspace_bytes", (B, T, E, Cn, Dc, K), "rec_comirec_sa_bwd_f32", dev, *args,
+                 _ptr(gout), _ptr(gkeys), _ptr(dW1), _ptr(dW2))
     return gkeys, dW1, dW2
 
 
 def _comirec_select_args(embed, items, m):
-    _table(embed, "embed"); _i64(items, "items"); _f32(m, "m")
-    if items.dim() != 3 or m.dim() != 3:
-        raise ValueError("hard attention takes items [B,Ns,C] and m [B,K,Dc]; got %s, %s"
-                         % (tuple(items.shape), tuple(m.shape)))
-    V, E = embed.shape
-    B, Ns, Cn = items.shape
+    args, (V, E, B, Ns, Cn) = _items_head(embed, items, m, "hard attention")
     K, Dc = m.shape[1:]
     if m.shape[0] != B or Dc != Cn * E:
         raise ValueError("hard attention: m must be [B, K, C E] = [%d, K, %d]; got %s" % (B, Cn * E, tuple(m.shape)))
     comirec_check_shape(Dc, Dc, K, Ns=Ns)
-    return [_ptr(embed), embed.stride(0), V, E, Cn, _ptr(items), B, Ns, _ptr(m), K], (B, Ns, Dc, K)
+    return args + [_ptr(m), K], (B, Ns, Dc, K)
 
 
 def comirec_select_fwd(embed, items, m, oob=None):
@@ -2013,12 +2021,9 @@ def comirec_select_fwd(embed, items, m, oob=None):
     product; inner [B,Ns], that product; loss [B]) with the label at sample 0."""
     args, (B, Ns, Dc, K) = _comirec_select_args(embed, items, m)
     dev = embed.device
-    chosen = torch.empty((B, Ns), dtype=torch.int32, device=dev)
-    inner = torch.empty((B, Ns), dtype=torch.float32, device=dev)
-    loss = torch.empty((B,), dtype=torch.float32, device=dev)
+    chosen, inner, loss = _new((B, Ns), dev, dtype=torch.int32), _new((B, Ns), dev), _new((B,), dev)
     if B > 0:
-        check(lib.rec_comirec_select_fwd_f32(*args, _ptr(chosen), _ptr(inner), _ptr(loss), _ptr(oob), _stream()),
-              "rec_comirec_select_fwd_f32")
+        _call("rec_comirec_select_fwd_f32", *args, _ptr(chosen), _ptr(inner), _ptr(loss), _ptr(oob))
     return chosen, inner, loss
 
 
@@ -2028,24 +2033,18 @@ def comirec_select_bwd(embed, items, m, chosen, ginner=None, gloss=None, gsel=No
     forward's.  With no gradient at all, zeros."""
     args, (B, Ns, Dc, K) = _comirec_select_args(embed, items, m)
     dev = embed.device
-    if tuple(_req(chosen, torch.int32, "chosen").shape) != (B, Ns):
-        raise ValueError("chosen must be [B,Ns] = %s, got %s" % ((B, Ns), tuple(chosen.shape)))
+    _expect(chosen, (B, Ns), "chosen", "[B,Ns]", torch.int32)
     if ginner is None and gloss is None and gsel is None:
-        return (torch.zeros((B, K, Dc), dtype=torch.float32, device=dev),
-                torch.zeros((B, Ns, Dc), dtype=torch.float32, device=dev))
-    if ginner is not None and tuple(_f32(ginner, "ginner").shape) != (B, Ns):
-        raise ValueError("ginner must be [B,Ns] = %s, got %s" % ((B, Ns), tuple(ginner.shape)))
-    if gloss is not None and tuple(_f32(gloss, "gloss").shape) != (B,):
-        raise ValueError("gloss must be [B] = [%d], got %s" % (B, tuple(gloss.shape)))
-    if gsel is not None and tuple(_f32(gsel, "gsel").shape) != (B, Ns, Dc):
-        raise ValueError("gsel must be [B,Ns,Dc] = %s, got %s" % ((B, Ns, Dc), tuple(gsel.shape)))
+        return _new((B, K, Dc), dev, B=0), _new((B, Ns, Dc), dev, B=0)
+    _expect(ginner, (B, Ns), "ginner", "[B,Ns]", optional=True)
+    _expect(gloss, (B,), "gloss", "[B]", optional=True)
+    _expect(gsel, (B, Ns, Dc), "gsel", "[B,Ns,Dc]", optional=True)
     if ginner is None and gloss is None:                 # the ABI wants one of the two: an all-zero gloss adds nothing
-        gloss = torch.zeros((B,), dtype=torch.float32, device=dev)
-    gm = torch.empty((B, K, Dc), dtype=torch.float32, device=dev)
-    gitems = torch.empty((B, Ns, Dc), dtype=torch.float32, device=dev)
+        gloss = _new((B,), dev, B=0)
+    gm, gitems = _new((B, K, Dc), dev), _new((B, Ns, Dc), dev)
     if B > 0:
-        check(lib.rec_comirec_select_bwd_f32(*args, _ptr(chosen), _ptr(ginner), _ptr(gloss), _ptr(gsel), _ptr(gm),
-                                             _ptr(gitems), _stream()), "rec_comirec_select_bwd_f32")
+        _call("rec_comirec_select_bwd_f32", *args, _ptr(chosen), _ptr(ginner), _ptr(gloss), _ptr(gsel), _ptr(gm),
+              _ptr(gitems))
     return gm, gitems
 
 
@@ -2087,11 +2086,10 @@ def can_check_shape(E, coefs, order, T=None):
         raise NotImplementedError(
             "CAN kernels cover layer widths feed_feature_dim * coef <= %d, at most %d layers and order <= %d; got "
             "feed_feature_dim=%d, layer_unit_coef=%r, order=%d" % (CAN_MAX_W, CAN_MAX_LAYERS, CAN_MAX_ORDER, E, coefs, order))
-    if T is not None and can_lds_bytes(T, E, coefs, order) > _MIND_LDS_CAP:
-        raise NotImplementedError(
-            "the CAN co-action holds one example in LDS: 4 (2 T E + Pv + T sum (w_l|1) + 2 T (wmax|1) + T + 256) <= %d "
-            "bytes; got %d at T=%d, feed_feature_dim=%d, layer_unit_coef=%r, order=%d"
-            % (_MIND_LDS_CAP, can_lds_bytes(T, E, coefs, order), T, E, coefs, order))
+    if T is not None:
+        _lds_fit(can_lds_bytes(T, E, coefs, order), "the CAN co-action holds one example",
+                 "2 T E + Pv + T sum (w_l|1) + 2 T (wmax|1) + T + 256",
+                 "T=%d, feed_feature_dim=%d, layer_unit_coef=%r, order=%d" % (T, E, coefs, order))
 
 
 def _can_args(feed, inds, iid, fid, coefs, order, act, padding_index):
@@ -2129,10 +2127,9 @@ def can_fwd(feed, inds, iid, fid, coefs, order, act, padding_index=0, pooled=Fal
     [B,Eo].  min(len(coefs), order) layers are applied; a position whose feed id is ``padding_index`` is zero."""
     args, (B, T, E, P, Eo) = _can_args(feed, inds, iid, fid, coefs, order, act, padding_index)
     shape = (B, Eo) if pooled else (int(order), B, T, Eo)
-    res = torch.empty(shape, dtype=torch.float32, device=feed.device)
+    res = _new(shape, feed.device)
     if B > 0:                                            # an empty batch answers from the sizes alone
-        check(lib.rec_can_fwd_f32(*args, None if pooled else _ptr(res), _ptr(res) if pooled else None, _ptr(oob),
-                                  _stream()), "rec_can_fwd_f32")
+        _call("rec_can_fwd_f32", *args, None if pooled else _ptr(res), _ptr(res) if pooled else None, _ptr(oob))
     return res
 
 
@@ -2143,9 +2140,7 @@ def can_bwd(feed, inds, iid, fid, coefs, order, act, g, padding_index=0, pooled=
     shape = (B, Eo) if pooled else (int(order), B, T, Eo)
     if tuple(_f32(g, "g").shape) != shape:
         raise ValueError("the upstream gradient must be %s, got %s" % (shape, tuple(g.shape)))
-    gfeed = torch.empty((B, T, E), dtype=torch.float32, device=feed.device)
-    gind = torch.empty((int(order), B, P), dtype=torch.float32, device=feed.device)
+    gfeed, gind = _new((B, T, E), feed.device), _new((int(order), B, P), feed.device)
     if B > 0:
-        check(lib.rec_can_bwd_f32(*args, None if pooled else _ptr(g), _ptr(g) if pooled else None, _ptr(gfeed),
-                                  _ptr(gind), _stream()), "rec_can_bwd_f32")
+        _call("rec_can_bwd_f32", *args, None if pooled else _ptr(g), _ptr(g) if pooled else None, _ptr(gfeed), _ptr(gind))
     return gfeed, gind
