@@ -25,7 +25,10 @@ TASKS = ("ctr", "cvr")
 BODY_CASES = [(1, 1, 1, 1, 1, 1, 1, 1, 1, 0), (2, 15, 3, 2, 5, 3, 7, 2, 1, 0), (33, 144, 3, 2, 64, 8, 64, 8, 1, 0),
               (33, 144, 3, 2, 64, 8, 64, 8, 2, 1), (17, 144, 1, 2, 64, 8, 64, 8, 1, 0), (17, 64, 4, 4, 64, 8, 32, 4, 1, 0),
               (17, 512, 2, 1, 32, 16, 128, 8, 1, 0), (2049, 144, 3, 2, 64, 8, 64, 8, 1, 0),
-              (2049, 144, 3, 2, 64, 8, 64, 8, 2, 1)]
+              (2049, 144, 3, 2, 64, 8, 64, 8, 2, 1),
+              # the slice edges of the small weight-gradient launch (csrc/tile_ops.h), at the smallest non-trivial widths:
+              # B = 513 two slices of unequal length, B = 4097 sixteen of 288 examples, the last one empty
+              (513, 15, 3, 2, 5, 3, 7, 2, 1, 0), (4097, 15, 3, 2, 5, 3, 7, 2, 1, 0), (4097, 15, 3, 2, 5, 3, 7, 2, 2, 1)]
 
 
 def f32_exact(a):

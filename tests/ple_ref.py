@@ -28,7 +28,12 @@ SAVED = ["h", "e", "q", "g"]
 LEVEL_CASES = [(1, 1, 1, 1, 1, 1, 1, 1, 1, 1), (2, 15, 1, 2, 2, 1, 5, 3, 2, 0), (33, 72, 1, 3, 3, 3, 64, 8, 8, 0),
                (33, 8, 4, 3, 3, 3, 64, 8, 8, 1), (17, 8, 4, 3, 3, 3, 64, 8, 8, 0), (17, 72, 1, 3, 3, 3, 64, 8, 8, 1),
                (17, 40, 1, 2, 3, 2, 48, 4, 6, 0), (17, 512, 1, 4, 2, 2, 128, 12, 8, 0),
-               (2049, 72, 1, 3, 3, 3, 64, 8, 8, 0), (2049, 8, 4, 3, 3, 3, 64, 8, 8, 1)]
+               (2049, 72, 1, 3, 3, 3, 64, 8, 8, 0), (2049, 8, 4, 3, 3, 3, 64, 8, 8, 1),
+               # the slice edges of the small weight-gradient launch (csrc/tile_ops.h), at the smallest non-trivial
+               # widths, a level before the last and a last one with Gin = T + 1: B = 513 two slices of unequal length,
+               # B = 4097 sixteen of 288 examples, the last one empty
+               (513, 15, 1, 2, 2, 1, 5, 3, 2, 0), (4097, 15, 1, 2, 2, 1, 5, 3, 2, 0), (513, 3, 3, 2, 2, 1, 5, 3, 2, 1),
+               (4097, 3, 3, 2, 2, 1, 5, 3, 2, 1)]
 # (B, D, T, S, Sh, L): whole bodies at the reference's widths H1 = 64, O = Og = 8
 BODY_CASES = [(33, 72, 3, 3, 3, 1), (33, 72, 3, 3, 3, 2), (33, 72, 3, 3, 3, 3)]
 H1_REF, O_REF, OG_REF = 64, 8, 8

@@ -222,7 +222,9 @@ def run_block(c, save=True):
 
 BLOCK_CASES = [(1, 1, 1, 1, PW), (2, 3, 5, 2, PW), (5, 13, 10, 3, PW), (17, 13, 16, 3, PW), (17, 13, 16, 3, SINGLE),
                (33, 7, 33, 1, PW), (17, 8, 64, 4, PW), (17, 64, 8, 4, SINGLE), (33, 64, 1, 3, PW), (4099, 13, 16, 3, PW),
-               (4099, 13, 16, 3, SINGLE), (2049, 26, 16, 3, PW)]
+               (4099, 13, 16, 3, SINGLE), (2049, 26, 16, 3, PW),
+               # slice edges of the small weight-gradient launch (csrc/tile_ops.h): two unequal slices; sixteen, the last empty
+               (513, 3, 5, 2, PW), (4097, 3, 5, 2, PW), (4097, 3, 5, 2, SINGLE)]
 GRAD_NAMES = ["dWa", "dba", "dWb", "dbb", "dW1", "dW2", "dgamma", "dbeta"]
 
 

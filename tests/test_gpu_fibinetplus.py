@@ -325,7 +325,9 @@ BLOCK_CASES = [(1, 2, 1, 1, 3, 1, ALL), (2, 3, 6, 3, 2, 4, EACH), (5, 13, 10, 5,
                (17, 13, 16, 2, 3, 16, ALL), (17, 13, 16, 2, 3, 16, EACH), (17, 13, 16, 2, 3, 16, INTER),
                (17, 13, 16, 16, 3, 16, INTER), (17, 13, 16, 1, 3, 16, INTER), (33, 7, 33, 3, 1, 5, EACH),
                (17, 8, 64, 4, 4, 128, INTER), (17, 32, 16, 2, 3, 16, INTER), (4099, 13, 16, 2, 3, 16, INTER),
-               (2049, 26, 16, 2, 3, 16, ALL)]
+               (2049, 26, 16, 2, 3, 16, ALL),
+               # slice edges of the small weight-gradient launch (csrc/tile_ops.h): two unequal slices; sixteen, the last empty
+               (513, 3, 6, 3, 2, 4, EACH), (4097, 3, 6, 3, 2, 4, EACH), (4097, 3, 6, 3, 2, 4, INTER)]
 GRAD_NAMES = ["dW", "dWr", "dbr", "dgamma_q", "dbeta_q", "dS0", "db0", "dgamma0", "dbeta0", "dS1", "db1", "dgamma1",
               "dbeta1"]
 
