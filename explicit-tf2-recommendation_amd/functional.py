@@ -1038,6 +1038,47 @@ class ComiRecSelect(torch.autograd.Function):
         return gembed, None, gm, None
 
 
+class SineInterest(torch.autograd.Function):
+    """SINELayer.generate_user_interest fused with the series lookup (6.MIND/CustomLayers.py:1000-1130; csrc/sine.hip):
+    table, series ids [B,T,C], the concept pool [L,C E], W1, W2, Wk1 [L,C E,C E], Wk2 [L,C E], W3, W4 -> (user_interest
+    [B,C E], chosen int32 [B,K], every example's top-K concepts, not differentiable).  One launch forward, which saves
+    nothing but its inputs and ``chosen``; the backward runs the forward again with that ``chosen`` and differentiates
+    through all of it.  The table's gradient is a sparse COO tensor of de-duplicated rows."""
+
+    @staticmethod
+    def forward(ctx, embed, series, pool, W1, W2, Wk1, Wk2, W3, W4, K, tau, padding_index, oob):
+        weights = tuple(w.contiguous() for w in (pool, W1, W2, Wk1, Wk2, W3, W4))
+        out, chosen = ops.sine_interest_fwd(embed, series, *weights, K, tau, ops.SINE_LN_EPS, padding_index, oob)
+        ctx.save_for_backward(embed, series, chosen, *weights)
+        ctx.cfg = (tau, ops.SINE_LN_EPS, padding_index)
+        ctx.mark_non_differentiable(chosen)
+        return out, chosen
+
+    @staticmethod
+    def backward(ctx, gout, _gchosen):
+        embed, series, chosen, *weights = ctx.saved_tensors
+        V, E = embed.shape
+        gkeys, *grads = ops.sine_interest_bwd(embed, series, *weights, chosen, gout.contiguous(), *ctx.cfg)
+        return (_series_grad(ctx, series, gkeys, V, E), None, *grads, None, None, None, None)
+
+
+class SineAux(torch.autograd.Function):
+    """SINELayer.compute_auxiliary_loss (6.MIND/CustomLayers.py:1143-1157; csrc/sine.hip): the concept pool [L,D] -> the
+    scalar 0.5 sum_{i != j} M_ij^2 of the centred pool's Gram matrix M.  Its gradient is zero where the off-diagonal is
+    zero throughout (the reference's 0.5 square(norm) gives NaN there)."""
+
+    @staticmethod
+    def forward(ctx, pool):
+        pool = pool.contiguous()
+        ctx.save_for_backward(pool)
+        return ops.sine_aux_fwd(pool)
+
+    @staticmethod
+    def backward(ctx, gloss):
+        pool, = ctx.saved_tensors
+        return ops.sine_aux_bwd(pool, gloss.reshape(1).contiguous())
+
+
 class CoAction(torch.autograd.Function):
     """CoActionUnit.call fused with both lookups (7.SIM/CustomLayers.py:339-378; csrc/can.hip): the feed table [Vf,E],
     target ids iid [B], feed ids fid [B,T] and the induction tables [Vi,P] -- one per order, or ONE that every order reads

@@ -2415,6 +2415,68 @@ class ComiRecLayer(Layer):
         return {"output": selected, "loss": loss}
 
 
+class SINELayer(Layer):
+    """6.MIND/CustomLayers.py:966-1176, the sparse-interest network: every example selects the K of L concepts of
+    ``interest_pool`` closest to its attention-pooled series (tf.math.top_k: descending, the lower index first on equal
+    values), each selection brings its own matrix ``Wk1[l]`` into a tanh-attention over the series, and the K interests are
+    mixed by a softmax at temperature ``tau``.  ``forward`` returns ``{'user_interest': [B,D], 'main_loss': [B],
+    'aux_loss': scalar}``; ``main_loss`` is the softmax cross entropy with the label at sample 0 over the inner products of
+    the looked-up items with ``user_interest`` (the hard-attention kernel of ComiRec with one capsule).  Only the first
+    attention masks padded positions, as in the reference; its LayerNormalization layers are built inside ``call`` and so
+    never trained: no gamma, no beta, eps 1e-3.  The whole extractor is one launch each way (csrc/sine.hip).
+    The one deliberate deviation: the reference writes the auxiliary loss as 0.5 square(norm), whose TF gradient is NaN
+    when the off-diagonal of the pool's covariance is zero throughout (L = 1, say); here that gradient is zero."""
+
+    def __init__(self, item_categorical_features=["label_goods_ids", "label_shop_ids", "label_cate_ids"],
+                 behavior_series_features=["visited_goods_ids", "visited_shop_ids", "visited_cate_ids"],
+                 feature_dims=160000, embedding_dims=16, padding_index=0, L=100, K=5, tau=0.1):
+        super().__init__()
+        assert len(item_categorical_features) == len(behavior_series_features)
+        self.item_categorical_features = item_categorical_features
+        self.behavior_series_features = behavior_series_features
+        self.feature_dims = feature_dims
+        self.embedding_dims = embedding_dims
+        self.L = L
+        self.K = K
+        self.D = D = len(item_categorical_features) * embedding_dims
+        self.tau = tau
+        ops.sine_check_shape(D, L, K)
+        if not tau > 0:
+            raise ValueError("tau must be positive, got %r" % (tau,))
+        self.embed = Embedding(feature_dims, embedding_dims)
+        normal = _initializer("random_normal")
+        self.interest_pool = torch.nn.Parameter(normal((L, D)))
+        self.W1 = torch.nn.Parameter(normal((D, D)))
+        self.W2 = torch.nn.Parameter(normal((D,)))
+        self.Wk1 = torch.nn.Parameter(normal((L, D, D)))
+        self.Wk2 = torch.nn.Parameter(normal((L, D)))
+        self.W3 = torch.nn.Parameter(normal((D, D)))
+        self.W4 = torch.nn.Parameter(normal((D,)))
+        self.padding_index = padding_index
+
+    def _interest(self, inputs, flag):
+        series = _stack_ids(inputs, self.behavior_series_features, self._device())
+        return Fn.SineInterest.apply(self.embed.embeddings, series, self.interest_pool, self.W1, self.W2, self.Wk1,
+                                     self.Wk2, self.W3, self.W4, self.K, self.tau, self.padding_index, flag)[0]
+
+    def generate_user_interest(self, inputs):
+        flag = ops.new_flag(self._device()) if self.check_ids else None
+        user_interest = self._interest(inputs, flag)
+        self._raise_if_oob(flag)
+        return user_interest
+
+    def compute_auxiliary_loss(self):
+        return Fn.SineAux.apply(self.interest_pool)
+
+    def forward(self, inputs):
+        flag = ops.new_flag(self._device()) if self.check_ids else None
+        user_interest = self._interest(inputs, flag)
+        items = _stack_ids(inputs, self.item_categorical_features, user_interest.device)
+        _, _, main_loss, _ = Fn.ComiRecSelect.apply(self.embed.embeddings, items, user_interest[:, None, :], flag)
+        self._raise_if_oob(flag)
+        return {"user_interest": user_interest, "main_loss": main_loss, "aux_loss": self.compute_auxiliary_loss()}
+
+
 class CoActionUnit(Layer):
     """7.SIM/CustomLayers.py:285-378, the CAN co-action: the induction row of the target item IS the weights and biases of
     a small MLP (layer l maps feed_feature_dim * coef_l to feed_feature_dim * coef_l+1 columns) that is applied to every

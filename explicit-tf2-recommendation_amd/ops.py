@@ -2048,6 +2048,110 @@ def comirec_select_bwd(embed, items, m, chosen, ginner=None, gloss=None, gsel=No
     return gm, gitems
 
 
+# ---- SINE: the sparse-interest extractor with its per-example top-K of L concepts, and the auxiliary loss of the concept
+# pool (csrc/sine.hip).  Key width and K are MIND's limits, L and the LDS fit are the header's.
+SINE_MAX_L = 1024
+SINE_LN_EPS = 1e-3
+
+
+def sine_lds_bytes(T, D, L, K):
+    """LDS of one example of either direction (include/mi355rec.h)."""
+    return 4 * (4 * T * _odd(D) + 4 * K * T + L + 5 * K * _odd(D) + 6 * T + 8 * _odd(D) + 128)
+
+
+def sine_check_shape(D, L, K, T=None):
+    """ValueError for sizes that describe no SINE body, NotImplementedError naming the limit for shapes the kernels do
+    not cover (the ABI would return -2): key width D = E C, L concepts of which every example selects K and -- where
+    given -- the series length T."""
+    sizes = [D, L, K] + ([] if T is None else [T])
+    if min(sizes) < 1:
+        raise ValueError("every size of a SINE body must be positive, got D=%d, L=%d, K=%d, T=%r" % (D, L, K, T))
+    if D > DIN_MAX_D or L > SINE_MAX_L or K > min(L, AFM_MAX_A):
+        raise NotImplementedError("SINE kernels cover key width <= %d, concepts L <= %d and selected concepts K <= "
+                                  "min(L, %d); got key width=%d, L=%d, K=%d" % (DIN_MAX_D, SINE_MAX_L, AFM_MAX_A, D, L, K))
+    if T is not None:
+        _lds_fit(sine_lds_bytes(T, D, L, K), "SINE holds one example",
+                 "4 T (D|1) + 4 K T + L + 5 K (D|1) + 6 T + 8 (D|1) + 128", "T=%d, key width=%d, L=%d, K=%d" % (T, D, L, K))
+
+
+def _sine_args(embed, series, pool, W1, W2, Wk1, Wk2, W3, W4, K, tau, ln_eps, padding_index):
+    args, (V, E, B, T, Cn) = _series_head(embed, series, "sparse interest", (pool, "pool [L,D]"), (W1, "W1 [D,D]"),
+                                          (W2, "W2 [D]"), (Wk1, "Wk1 [L,D,D]"), (Wk2, "Wk2 [L,D]"), (W3, "W3 [D,D]"),
+                                          (W4, "W4 [D]"))
+    L, D = pool.shape
+    want = {"W1": (D, D), "W2": (D,), "Wk1": (L, D, D), "Wk2": (L, D), "W3": (D, D), "W4": (D,)}
+    got = {"W1": W1, "W2": W2, "Wk1": Wk1, "Wk2": Wk2, "W3": W3, "W4": W4}
+    if D != Cn * E or any(tuple(got[k].shape) != s for k, s in want.items()):
+        raise ValueError("sparse interest: pool must be [L, C E = %d] and the weights %s; got pool %s, %s"
+                         % (Cn * E, want, tuple(pool.shape), {k: tuple(t.shape) for k, t in got.items()}))
+    if not (tau > 0 and ln_eps > 0):
+        raise ValueError("sparse interest: tau and ln_eps must be positive, got %r and %r" % (tau, ln_eps))
+    sine_check_shape(D, L, int(K), T=T)
+    return args + [_ptr(pool), _ptr(W1), _ptr(W2), _ptr(Wk1), _ptr(Wk2), _ptr(W3), _ptr(W4), L, int(K), float(tau),
+                   float(ln_eps), int(padding_index)], (B, T, Cn, E, D, L)
+
+
+def sine_interest_fwd(embed, series, pool, W1, W2, Wk1, Wk2, W3, W4, K, tau=0.1, ln_eps=SINE_LN_EPS, padding_index=0,
+                      oob=None):
+    """SINELayer.generate_user_interest over the looked-up series in one launch: series ids [B,T,C] into ``embed``, the
+    concept pool [L,C E] and the six weights -> (user_interest [B,C E], chosen int32 [B,K]: every example's top-K concepts
+    in descending-similarity order, the lower index first on equal values).  Nothing else is saved."""
+    args, (B, T, Cn, E, D, L) = _sine_args(embed, series, pool, W1, W2, Wk1, Wk2, W3, W4, K, tau, ln_eps, padding_index)
+    dev = embed.device
+    out, chosen = _new((B, D), dev), _new((B, int(K)), dev, B, dtype=torch.int32)
+    if B > 0:
+        _call("rec_sine_interest_fwd_f32", *args, _ptr(out), _ptr(chosen), _ptr(oob))
+    return out, chosen
+
+
+def sine_interest_bwd(embed, series, pool, W1, W2, Wk1, Wk2, W3, W4, chosen, gout, tau=0.1, ln_eps=SINE_LN_EPS,
+                      padding_index=0):
+    """-> (gkeys [B,T,C E], the IndexedSlices values of the series lookups, dpool, dW1, dW2, dWk1, dWk2, dW3, dW4) from
+    gout [B,C E]; ``chosen`` is the forward's and is never re-selected.  Every gradient is written in full: the rows of
+    dpool, dWk1 and dWk2 that no example chose are zero."""
+    K = chosen.shape[1] if isinstance(chosen, torch.Tensor) and chosen.dim() == 2 else 0
+    args, (B, T, Cn, E, D, L) = _sine_args(embed, series, pool, W1, W2, Wk1, Wk2, W3, W4, K, tau, ln_eps, padding_index)
+    _expect(chosen, (B, K), "chosen", "[B,K]", torch.int32)
+    _expect(gout, (B, D), "gout", "[B,D]")
+    dev = embed.device
+    gkeys = _new((B, T, D), dev)
+    grads = [_new(tuple(t.shape), dev, B) for t in (pool, W1, W2, Wk1, Wk2, W3, W4)]
+    if B > 0:
+        nbytes = lib.rec_sine_scratch_bytes(B, T, E, Cn, L, K)
+        scratch = _workspace(nbytes, "rec_sine_scratch_bytes", dev, torch.float32)
+        _call("rec_sine_interest_bwd_f32", *args, _ptr(chosen), _ptr(gout), _ptr(gkeys), *[_ptr(g) for g in grads],
+              _ptr(scratch), nbytes)
+    return (gkeys, *grads)
+
+
+def _sine_pool(pool):
+    _req(pool, torch.float32, "pool")
+    if pool.dim() != 2:
+        raise ValueError("the auxiliary loss takes pool [L,D]; got %s" % (tuple(pool.shape),))
+    L, D = pool.shape
+    sine_check_shape(D, L, 1)
+    return L, D
+
+
+def sine_aux_fwd(pool):
+    """SINELayer.compute_auxiliary_loss: 0.5 sum_{i != j} M_ij^2 of M = Cc Cc^T, Cc the centred pool -> a scalar tensor."""
+    L, D = _sine_pool(pool)
+    loss = _new((1,), pool.device)
+    _call("rec_sine_aux_fwd_f32", _ptr(pool), L, D, _ptr(loss))
+    return loss.reshape(())
+
+
+def sine_aux_bwd(pool, gloss):
+    """-> dpool [L,D] = gloss (2 offdiag(M) Cc) pushed back through the centring; gloss a one-element device tensor"""
+    L, D = _sine_pool(pool)
+    _req(gloss, torch.float32, "gloss")
+    if gloss.numel() != 1:
+        raise ValueError("gloss must hold one element, got %s" % (tuple(gloss.shape),))
+    dpool = _new((L, D), pool.device)
+    _call("rec_sine_aux_bwd_f32", _ptr(pool), L, D, _ptr(gloss), _ptr(dpool))
+    return dpool
+
+
 # ---- CAN co-action: both lookups and the per-example micro-MLP in one launch each way (csrc/can.hip).  The widest layer
 # is AFM's embedding limit; layers, orders and the LDS fit are the header's.
 CAN_MAX_W = AFM_MAX_E

@@ -1176,6 +1176,62 @@ int rec_can_bwd_f32(const float* feed, int64_t ld_f, int64_t Vf, int E, const fl
                     const int64_t* iid, const int64_t* fid, int64_t B, int T, int64_t padding_index, const float* gout,
                     const float* gpool, float* gfeed, float* gind, void* stream);
 
+/* ---- SINE (SINELayer, 6.MIND/CustomLayers.py:966-1176; csrc/sine.hip): the sparse-interest extractor, whose examples
+ * each select K of the L concepts of a pool, and the auxiliary loss of the pool.  The extractor gathers from embed [V, E]
+ * with row stride ld >= E; an id outside [0, V) reads as a zero row and sets *oob_flag (may be NULL).  series int64
+ * [B, T, C], D = E C, pool [L, D], W1 [D, D], W2 [D], Wk1 [L, D, D], Wk2 [L, D], W3 [D, D], W4 [D].
+ * LN(r) = (r - mean) / sqrt(var + ln_eps) over the last axis with the population variance, no gamma, no beta (the
+ * reference builds its LayerNormalization inside call: never trained, ln_eps = 1e-3).  Per example b:
+ *   x_t = concat_r embed[series[b,t,r]]   pad_t = series[b,t,0] == padding_index
+ *   (a) s_t = tanh(x_t W1) . W2 + (pad_t ? -1e9f : 0)    a = softmax_t(s)    z = sum_t a_t x_t
+ *   (b) sim_l = z . pool_l    idx = top-K of sim: descending, the lower index first on equal values (tf.math.top_k)
+ *       g_k = sigmoid(sim[idx_k])    Cu_k = g_k pool[idx_k]                                                     [K, D]
+ *   (c) P[t,:] = softmax_k(LN(x_t W3) . LN(Cu_k))                                                               [T, K]
+ *   (d) A[k,:] = softmax_t(tanh(x_t Wk1[idx_k]) . Wk2[idx_k])                                                   [K, T]
+ *   (e) Z_k = LN(sum_t P[t,k] A[k,t] x_t)                                                                       [K, D]
+ *   (f) Xh_t = sum_k P[t,k] Cu_k    b = softmax_t(tanh(Xh_t W3) . W4)    cap = LN(sum_t b_t Xh_t)
+ *   (g) e = softmax_k(cap . Z_k / tau)    out[b] = sum_k e_k Z_k                                          out [B, D]
+ * Only (a) masks padded positions; (c), (d) and (f) run over all T, as the reference does.  The mask is the additive
+ * -1e9f in fp32: a row padded throughout gets the uniform 1 / T, never NaN.  Padding may sit anywhere.
+ * The forward is one launch, one example per workgroup at a time; the 3 + K products [T, D] x [D, D] run on
+ * v_mfma_f32_32x32x2_f32, the top-K is K rounds of an arg-max inside the workgroup.  It writes out and chosen int32
+ * [B, K] (idx, in descending-similarity order) and saves nothing else.  The backward takes chosen as the forward wrote
+ * it (a value outside [0, L) is clamped) and never re-selects; it recomputes (a)-(g) and differentiates through all of
+ * it with idx constant, from gout [B, D]: gkeys [B, T, D], the IndexedSlices values of the series lookups, dpool [L, D]
+ * (through Cu and through sim), dW1, dW2, dWk1 [L, D, D], dWk2 [L, D], dW3 (both uses) and dW4, every one written, never
+ * added to; the rows of dpool, dWk1 and dWk2 that no example chose are zero.  The batch goes through in slabs of
+ * min(2048, max(1, 64 MiB / (4 K (D D + 2 D)))) examples: an example-major launch keeps dW1 .. dW4 per workgroup (at most
+ * 1024 workgroups; 256 where [D, D] has more than four 32 x 32 blocks) and writes x^T dpre_k, the row of dWk2 and the row
+ * of dpool of every pair (b, k) to the scratch; a concept-major launch adds the pairs with chosen == l in ascending
+ * (b, k) order, one thread per element (the first slab writes, later slabs add); a slot sum in wave order finishes
+ * dW1 .. dW4.  Supported, the same both ways: D = E C <= REC_DIN_MAX_D (256), 1 <= K <= min(L, REC_AFM_MAX_A (16)),
+ * L <= 1024 (SN_MAX_L of csrc/sine.hip), 0 <= B < 2^31 and one example's LDS within the 150 KiB launch cap:
+ *   4 (4 T (D|1) + 4 K T + L + 5 K (D|1) + 6 T + 8 (D|1) + 128) <= 153600                     (x|1: x made odd)
+ * e.g. T <= 164 at D = 48, K = 5, L = 100.  rec_sine_lds_bytes: the left-hand side, the dynamic LDS of a launch; 0:
+ * invalid or unsupported.  scratch (backward only): rec_sine_scratch_bytes: the pairs of a slab plus the slots; 0 likewise.
+ *
+ * aux.  Cc = pool - mean_l(pool), M = Cc Cc^T [L, L]: loss[0] = 0.5 sum_{i != j} M_ij^2; the backward takes gloss [1] ON
+ * THE DEVICE and writes dpool = gloss (2 offdiag(M) Cc), pushed back through the centring.  L <= 1024, D <= 256.
+ *
+ * All entry points only enqueue (no allocation, no host synchronisation: graph-capturable) and use no float atomics:
+ * bit-identical results run to run.  Return codes, answered in this order: a size below 1 (B below 0), tau <= 0 or
+ * ln_eps <= 0: -1; a shape outside the limits: -2, from the sizes alone; ld < E, V < 1 or a NULL pointer other than
+ * oob_flag: -1; a scratch that is too small: -3; then B == 0: 0, nothing is launched or written. */
+size_t rec_sine_lds_bytes(int T, int E, int C, int L, int K);
+size_t rec_sine_scratch_bytes(int64_t B, int T, int E, int C, int L, int K);
+int rec_sine_interest_fwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* series, int64_t B,
+                              int T, const float* pool, const float* W1, const float* W2, const float* Wk1,
+                              const float* Wk2, const float* W3, const float* W4, int L, int K, float tau, float ln_eps,
+                              int64_t padding_index, float* out, int32_t* chosen, int* oob_flag, void* stream);
+int rec_sine_interest_bwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* series, int64_t B,
+                              int T, const float* pool, const float* W1, const float* W2, const float* Wk1,
+                              const float* Wk2, const float* W3, const float* W4, int L, int K, float tau, float ln_eps,
+                              int64_t padding_index, const int32_t* chosen, const float* gout, float* gkeys,
+                              float* dpool, float* dW1, float* dW2, float* dWk1, float* dWk2, float* dW3, float* dW4,
+                              void* scratch, size_t scratch_bytes, void* stream);
+int rec_sine_aux_fwd_f32(const float* pool, int L, int D, float* loss, void* stream);
+int rec_sine_aux_bwd_f32(const float* pool, int L, int D, const float* gloss, float* dpool, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
