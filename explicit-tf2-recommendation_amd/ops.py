@@ -3,6 +3,14 @@
 torch is plumbing here: it owns device memory and the current HIP stream; every function below hands raw
 device pointers and the stream handle to libmi355rec.so and returns torch tensors that view the results.
 Nothing in this file computes on the CPU or through torch ops -- a non-CUDA tensor is an error.
+
+A wrapper of a kernel family is five steps, each with its policy in one helper below: (1) check the operands against
+each other (_req, _expect, _expect_all, _vec, _keyed_head, _caps_head) and against the family's limits (its own
+*_check_shape); (2) allocate the outputs -- _new / _new_like for what the launch writes in full, which is zeros where
+the batch is empty and nothing is launched, torch.zeros / torch.zeros_like for what kernels add into or leave alone;
+(3) launch nothing for an empty batch; (4) make one _call, or one _call_ws where the entry point ends in (workspace,
+nbytes, stream): _call alone appends the stream and checks the status, _workspace alone turns the answer of a
+rec_*_workspace_bytes query into memory; (5) return the tensors.
 """
 import ctypes as C
 
@@ -36,20 +44,102 @@ def _req(t, dtype, name):
     return t
 
 
-def _workspace(nbytes, what, device, dtype=torch.uint8):
-    """Scratch for one ABI call, nbytes as its rec_*_workspace_bytes answered.  `what` names that entry point where its
-    answer is 0 for a shape the kernels do not cover; None where 0 bytes only means that nothing is needed."""
-    if nbytes == 0 and what is not None:
-        raise NotImplementedError("%s: unsupported shape" % what)
-    return torch.empty(max(nbytes // dtype.itemsize, 1), dtype=dtype, device=device)
-
-
 def _f32(t, name):
     return _req(t, torch.float32, name)
 
 
 def _i64(t, name):
     return _req(t, torch.int64, name)
+
+
+def _expect(t, shape, name, label=None, dtype=torch.float32, optional=False):
+    """``t`` is a contiguous tensor of ``dtype`` and ``shape`` on the device (or, with ``optional``, None); ``label``
+    spells the shape in the error, which shows a one-dimensional shape as [n]"""
+    if t is None and optional:
+        return
+    if tuple(_req(t, dtype, name).shape) != tuple(shape):
+        want = "[%d]" % tuple(shape) if len(shape) == 1 else tuple(shape)
+        raise ValueError("%s must be %s, got %s"
+                         % (name, want if label is None else "%s = %s" % (label, want), tuple(t.shape)))
+
+
+def _expect_all(named):
+    """_expect over (tensor, shape, name) each: the saved tensors and upstream gradients of a backward, of which a
+    missing one is a shape error"""
+    for t, shape, name in named:
+        if t is None:
+            raise ValueError("%s must be %s, got None" % (name, tuple(shape)))
+        _expect(t, shape, name)
+
+
+def _vec(t, n, name):
+    """``t`` holds n floats in any shape"""
+    if _f32(t, name).numel() != n:
+        raise ValueError("%s must hold %d floats, got %s" % (name, n, tuple(t.shape)))
+    return t
+
+
+def _keyed_head(x, values, E=None, F=None, name="dx"):
+    """The head of a keyed input stage, whose last ``values.shape[1]`` of F fields are scaled by ``values``: ``x`` is X
+    [B,F] int64 beside a table of width ``E`` (the forward) or, with ``F`` given, the fp32 [B, F E] called ``name`` (the
+    backward); ``values`` is None or fp32 [B,Fk] with 0 <= Fk <= F.  -> (B, F, E, Fk); the limits are the family's."""
+    if F is None:
+        if _i64(x, "X").dim() != 2:
+            raise ValueError("X must be [B, fields]")
+        B, F = x.shape
+    else:
+        if _f32(x, name).dim() != 2 or F < 1 or x.shape[1] % F:
+            raise ValueError("%s must be [B, fields * embedding_dims] with fields=%d, got %s" % (name, F, tuple(x.shape)))
+        B, E = x.shape[0], x.shape[1] // F
+    Fk = 0 if values is None else (values.shape[1] if values.dim() == 2 else -1)
+    if not 0 <= Fk <= F:
+        raise ValueError("values must be [B, continuous fields <= %d], got %s" % (F, tuple(values.shape)))
+    if Fk > 0:
+        _expect(values, (B, Fk), "values", "[B,Fk]")
+    return B, F, E, Fk
+
+
+def _new(shape, dev, B=1, dtype=torch.float32):
+    """an output the launch writes in full; zeros where the batch ``B`` is empty and nothing is launched"""
+    return (torch.zeros if B == 0 else torch.empty)(shape, dtype=dtype, device=dev)
+
+
+def _new_like(t, B=1):
+    """_new in the shape of the contiguous ``t``: the gradient of a weight, the result of a row-wise op"""
+    return (torch.zeros_like if B == 0 else torch.empty_like)(t)
+
+
+def _ptrs(tensors):
+    return [_ptr(t) for t in tensors]
+
+
+def _ptr_array(tensors):
+    """a host array of device pointers, for the entry points that take a list of tensors"""
+    return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def _ints(values):
+    return (C.c_int * len(values))(*[int(v) for v in values])
+
+
+def _call(fn, *args):
+    check(getattr(lib, fn)(*args, _stream()), fn)
+
+
+def _workspace(nbytes, what, device):
+    """Scratch for one ABI call, nbytes as its rec_*_workspace_bytes answered.  `what` names that entry point where its
+    answer is 0 for a shape the kernels do not cover; None where 0 bytes only means that nothing is needed."""
+    if nbytes == 0 and what is not None:
+        raise NotImplementedError("%s: unsupported shape" % what)
+    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
+
+
+def _call_ws(query, query_args, fn, dev, *args, may_need_none=False):
+    """``fn`` with the workspace that ``query`` asks for at ``query_args``, for the entry points that end in (workspace,
+    nbytes, stream); ``may_need_none``: 0 bytes is an answer, not an uncovered shape"""
+    nbytes = getattr(lib, query)(*query_args)
+    ws = _workspace(nbytes, None if may_need_none else query, dev)
+    _call(fn, *args, _ptr(ws), nbytes)
 
 
 def _table(t, name):
@@ -125,23 +215,20 @@ class DedupPlan:
         if list_counts is None:
             self.uniq_ids, self.seg_start, self.perm, self.n_uniq = tops.dedup_plan(ids, V)
         else:
-            self.uniq_ids = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
-            self.seg_start = torch.empty(n + 1, dtype=torch.int32, device=dev)
-            self.perm = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-            self.n_uniq = torch.empty(1, dtype=torch.int64, device=dev)
-            nbytes = lib.rec_dedup_workspace_bytes(n)
-            ws = _workspace(nbytes, None, dev)
             lc = _i64(list_counts.reshape(-1), "list_counts")
-            check(lib.rec_dedup_plan_sorted_lists_i64(_ptr(ids), n, _ptr(lc), lc.numel(), V, _ptr(self.uniq_ids),
-                                                      _ptr(self.seg_start), _ptr(self.perm), _ptr(self.n_uniq),
-                                                      _ptr(ws), nbytes, _stream()),
-                  "rec_dedup_plan_sorted_lists_i64")
+            self.uniq_ids = _new(max(n, 1), dev, dtype=torch.int64)
+            self.seg_start = _new(n + 1, dev, dtype=torch.int32)
+            self.perm = _new(max(n, 1), dev, dtype=torch.int32)
+            self.n_uniq = _new(1, dev, dtype=torch.int64)
+            _call_ws("rec_dedup_workspace_bytes", (n,), "rec_dedup_plan_sorted_lists_i64", dev, _ptr(ids), n, _ptr(lc),
+                     lc.numel(), V, _ptr(self.uniq_ids), _ptr(self.seg_start), _ptr(self.perm), _ptr(self.n_uniq),
+                     may_need_none=True)
 
     def segment_sum(self, vals, E, row_div=1, wide=False):
         """vals [n/row_div, E] -> [n, E]; rows >= n_uniq are zero.  ``wide``: rows of more than 256 columns go through
         the wide-row kernel in one launch (a workgroup per unique id) instead of 256-column slices."""
         if E > 256 and not wide:      # wide rows (FFM's F*E): the kernel takes up to 256 columns at a time
-            out = torch.empty((max(self.n, 1), E), dtype=torch.float32, device=vals.device)
+            out = _new((max(self.n, 1), E), vals.device)
             for c0 in range(0, E, 256):
                 c1 = min(E, c0 + 256)
                 out[:, c0:c1] = self.segment_sum(vals[:, c0:c1].contiguous(), c1 - c0, row_div)
@@ -156,11 +243,10 @@ def l2_used_rows(table, plan, factor):
     V, E = table.shape
     n = plan.n
     dev = table.device
-    rows = torch.empty((max(n, 1), E), dtype=torch.float32, device=dev)
-    loss = torch.empty(1, dtype=torch.float32, device=dev)
-    ws = torch.empty(lib.rec_l2_rows_workspace_bytes(n, E) // 4 + 1, dtype=torch.float32, device=dev)
-    check(lib.rec_l2_rows_f32(_ptr(table), table.stride(0), V, E, _ptr(plan.uniq_ids), _ptr(plan.n_uniq), n,
-                              float(factor), _ptr(rows), _ptr(loss), _ptr(ws), _stream()), "rec_l2_rows_f32")
+    rows, loss = _new((max(n, 1), E), dev), _new(1, dev)
+    ws = _workspace(lib.rec_l2_rows_workspace_bytes(n, E), None, dev)
+    _call("rec_l2_rows_f32", _ptr(table), table.stride(0), V, E, _ptr(plan.uniq_ids), _ptr(plan.n_uniq), n,
+          float(factor), _ptr(rows), _ptr(loss), _ptr(ws))
     return loss, rows
 
 
@@ -181,7 +267,7 @@ def gemm(A, B, transA=False, transB=False, epi=EPI_NONE, bias=None, e0=None, e1=
     if K != K2:
         raise ValueError("gemm inner dimensions differ: %d vs %d" % (K, K2))
     if out is None:
-        out = torch.empty((M, N), dtype=torch.float32, device=A.device)
+        out = _new((M, N), A.device)
     if out.dim() != 2 or tuple(out.shape) != (M, N) or out.stride(1) != 1 or out.dtype != torch.float32:
         raise ValueError("out must be a 2-D fp32 [%d,%d] tensor with unit inner stride" % (M, N))
     if aux is not None:
@@ -222,8 +308,7 @@ def axpby(a, x, b, y):
 def copy_cols(src, dst_view):
     """dst_view[:, :] = src, both 2-D with unit inner stride (dst may be a column block of a wider buffer)."""
     rows, w = src.shape
-    check(lib.rec_copy_cols_f32(_ptr(src), src.stride(0), _ptr(dst_view), dst_view.stride(0), rows, w, _stream()),
-          "rec_copy_cols_f32")
+    _call("rec_copy_cols_f32", _ptr(src), src.stride(0), _ptr(dst_view), dst_view.stride(0), rows, w)
     return dst_view
 
 
@@ -251,23 +336,21 @@ def split_k_for(K, M, N, transA=False, transB=False):
 def crossnet_vec_fwd(x0, w, b, save=True):
     B, D = x0.shape
     L = w.shape[0]
-    y = torch.empty_like(x0)
-    xs = torch.empty((L, B, D), dtype=torch.float32, device=x0.device) if save else None
-    check(lib.rec_crossnet_vec_fwd_f32(_ptr(_f32(x0, "x0")), B, D, L, _ptr(_f32(w, "w")), _ptr(_f32(b, "b")),
-                                       _ptr(y), _ptr(xs), _stream()), "rec_crossnet_vec_fwd_f32")
+    _f32(x0, "x0"); _f32(w, "w"); _f32(b, "b")
+    y = _new_like(x0)
+    xs = _new((L, B, D), x0.device) if save else None
+    _call("rec_crossnet_vec_fwd_f32", _ptr(x0), B, D, L, _ptr(w), _ptr(b), _ptr(y), _ptr(xs))
     return y, xs
 
 
 def crossnet_vec_bwd(x0, w, xs, gy):
     B, D = x0.shape
     L = w.shape[0]
-    gx0 = torch.empty_like(x0)
-    dw = torch.empty_like(w)
-    db = torch.empty_like(w)
-    nbytes = lib.rec_crossnet_vec_bwd_workspace_bytes(B, D, L)
-    ws = _workspace(nbytes, None, x0.device)
-    check(lib.rec_crossnet_vec_bwd_f32(_ptr(x0), B, D, L, _ptr(w), _ptr(xs), _ptr(_f32(gy, "gy")), _ptr(gx0),
-                                       _ptr(dw), _ptr(db), _ptr(ws), _stream()), "rec_crossnet_vec_bwd_f32")
+    _f32(gy, "gy")
+    gx0, dw, db = _new_like(x0), _new_like(w, B), _new_like(w, B)
+    ws = _workspace(lib.rec_crossnet_vec_bwd_workspace_bytes(B, D, L), None, x0.device)
+    _call("rec_crossnet_vec_bwd_f32", _ptr(x0), B, D, L, _ptr(w), _ptr(xs), _ptr(gy), _ptr(gx0), _ptr(dw), _ptr(db),
+          _ptr(ws))
     return gx0, dw, db
 
 
@@ -286,24 +369,22 @@ def bce_fwd_bwd(y, p, want_dp=True, want_dz=False):
 
 
 def adam_dense(var, m, v, g, t, lr, b1=0.9, b2=0.999, eps=1e-7):
-    check(lib.rec_adam_dense_f32(_ptr(_f32(var, "var")), _ptr(m), _ptr(v), _ptr(_f32(g, "g")), var.numel(), t, lr,
-                                 b1, b2, eps, _stream()), "rec_adam_dense_f32")
+    _call("rec_adam_dense_f32", _ptr(_f32(var, "var")), _ptr(m), _ptr(v), _ptr(_f32(g, "g")), var.numel(), t, lr, b1, b2,
+          eps)
 
 
 def adam_sparse_keras(var, m, v, uniq_ids, g_rows, n_uniq, t, lr, b1=0.9, b2=0.999, eps=1e-7):
-    V, E = var.shape
+    V, E = _table(var, "var").shape
     cap = g_rows.shape[0]
-    side = torch.empty((cap, 3, E), dtype=torch.float32, device=var.device)
-    check(lib.rec_adam_sparse_keras_f32(_ptr(_table(var, "var")), var.stride(0), _ptr(m), _ptr(v), V, E, _ptr(uniq_ids),
-                                        _ptr(g_rows), _ptr(n_uniq), cap, _ptr(side), t, lr, b1, b2, eps, _stream()),
-          "rec_adam_sparse_keras_f32")
+    side = _new((cap, 3, E), var.device)                 # the touched rows' new (var, m, v), patched in after the sweep
+    _call("rec_adam_sparse_keras_f32", _ptr(var), var.stride(0), _ptr(m), _ptr(v), V, E, _ptr(uniq_ids), _ptr(g_rows),
+          _ptr(n_uniq), cap, _ptr(side), t, lr, b1, b2, eps)
 
 
 def adam_rows(var, m, v, uniq_ids, g_rows, n_uniq, t, lr, b1=0.9, b2=0.999, eps=1e-7):
-    V, E = var.shape
-    check(lib.rec_adam_rows_f32(_ptr(_table(var, "var")), var.stride(0), _ptr(m), _ptr(v), V, E, _ptr(uniq_ids),
-                                _ptr(g_rows), _ptr(n_uniq), g_rows.shape[0], t, lr, b1, b2, eps, _stream()),
-          "rec_adam_rows_f32")
+    V, E = _table(var, "var").shape
+    _call("rec_adam_rows_f32", _ptr(var), var.stride(0), _ptr(m), _ptr(v), V, E, _ptr(uniq_ids), _ptr(g_rows),
+          _ptr(n_uniq), g_rows.shape[0], t, lr, b1, b2, eps)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -314,22 +395,17 @@ def shard_bucketize(ids, rows_per_shard, n_shard, oob=None):
     ids = _i64(ids.reshape(-1), "ids")
     n = ids.numel()
     dev = ids.device
-    perm = torch.empty(n, dtype=torch.int64, device=dev)
-    counts = torch.empty(n_shard, dtype=torch.int64, device=dev)
-    local = torch.empty(n, dtype=torch.int64, device=dev)
-    nbytes = lib.rec_shard_bucketize_workspace_bytes(n, n_shard)
-    ws = _workspace(nbytes, None, dev)
-    check(lib.rec_shard_bucketize_i64(_ptr(ids), n, rows_per_shard, n_shard, _ptr(perm), _ptr(counts), _ptr(local),
-                                      _ptr(oob), _ptr(ws), nbytes, _stream()), "rec_shard_bucketize_i64")
+    perm, counts, local = (_new(k, dev, dtype=torch.int64) for k in (n, n_shard, n))
+    _call_ws("rec_shard_bucketize_workspace_bytes", (n, n_shard), "rec_shard_bucketize_i64", dev, _ptr(ids), n,
+             rows_per_shard, n_shard, _ptr(perm), _ptr(counts), _ptr(local), _ptr(oob), may_need_none=True)
     return perm, counts, local
 
 
 def permute_rows(x, perm, scatter):
     """scatter=True: out[perm[i]] = x[i];  scatter=False: out[i] = x[perm[i]]."""
-    n, E = x.shape
-    out = torch.empty_like(x)
-    check(lib.rec_permute_rows_f32(_ptr(_f32(x, "x")), _ptr(_i64(perm, "perm")), n, E, int(scatter), _ptr(out),
-                                   _stream()), "rec_permute_rows_f32")
+    n, E = _f32(x, "x").shape
+    out = _new_like(x)
+    _call("rec_permute_rows_f32", _ptr(x), _ptr(_i64(perm, "perm")), n, E, int(scatter), _ptr(out))
     return out
 
 
@@ -339,9 +415,8 @@ def permute_rows(x, perm, scatter):
 def l2_normalize_rows(x):
     """x / ||x||_2 per row (2.FM/OfflineLoader.py:140)."""
     _table(x, "x")                                       # 2-D fp32 CUDA, unit inner stride, any row stride
-    y = torch.empty((x.shape[0], x.shape[1]), dtype=torch.float32, device=x.device)
-    check(lib.rec_l2_normalize_rows_f32(_ptr(x), x.shape[0], x.shape[1], x.stride(0), _ptr(y), y.stride(0), _stream()),
-          "rec_l2_normalize_rows_f32")
+    y = _new(tuple(x.shape), x.device)
+    _call("rec_l2_normalize_rows_f32", _ptr(x), x.shape[0], x.shape[1], x.stride(0), _ptr(y), y.stride(0))
     return y
 
 
@@ -353,12 +428,9 @@ def topk_l2(queries, items, k):
     nq, d = queries.shape
     n = items.shape[0]
     dev = queries.device
-    ind = torch.empty((nq, k), dtype=torch.int64, device=dev)
-    dist = torch.empty((nq, k), dtype=torch.float32, device=dev)
-    nbytes = lib.rec_topk_l2_workspace_bytes(nq, n, k)
-    ws = _workspace(nbytes, None, dev)
-    check(lib.rec_topk_l2_f32(_ptr(queries), nq, d, queries.stride(0), _ptr(items), n, items.stride(0), k, _ptr(ind),
-                              _ptr(dist), _ptr(ws), nbytes, _stream()), "rec_topk_l2_f32")
+    ind, dist = _new((nq, k), dev, dtype=torch.int64), _new((nq, k), dev)
+    _call_ws("rec_topk_l2_workspace_bytes", (nq, n, k), "rec_topk_l2_f32", dev, _ptr(queries), nq, d, queries.stride(0),
+             _ptr(items), n, items.stride(0), k, _ptr(ind), _ptr(dist), may_need_none=True)
     return dist, ind
 
 
@@ -375,18 +447,14 @@ def din_prepare(W1, b1, D, H):
     """W1 [3D+D*D, H], b1 [H] -> Wcat [D, D*H+H], Wkd [D,H], bext [D*H+H]."""
     dev = W1.device
     N = D * H + H
-    Wcat = torch.empty((D, N), dtype=torch.float32, device=dev)
-    Wkd = torch.empty((D, H), dtype=torch.float32, device=dev)
-    bext = torch.empty(N, dtype=torch.float32, device=dev)
-    check(lib.rec_din_prepare_f32(_ptr(_f32(W1, "W1")), _ptr(_f32(b1, "b1")), D, H, _ptr(Wcat), _ptr(Wkd), _ptr(bext),
-                                  _stream()), "rec_din_prepare_f32")
+    Wcat, Wkd, bext = _new((D, N), dev), _new((D, H), dev), _new(N, dev)
+    _call("rec_din_prepare_f32", _ptr(_f32(W1, "W1")), _ptr(_f32(b1, "b1")), D, H, _ptr(Wcat), _ptr(Wkd), _ptr(bext))
     return Wcat, Wkd, bext
 
 
 def din_prepare_bwd(gWcat, gWkd, D, H):
-    gW1 = torch.empty((3 * D + D * D, H), dtype=torch.float32, device=gWcat.device)
-    check(lib.rec_din_prepare_bwd_f32(_ptr(_f32(gWcat, "gWcat")), _ptr(_f32(gWkd, "gWkd")), D, H, _ptr(gW1), _stream()),
-          "rec_din_prepare_bwd_f32")
+    gW1 = _new((3 * D + D * D, H), gWcat.device)
+    _call("rec_din_prepare_bwd_f32", _ptr(_f32(gWcat, "gWcat")), _ptr(_f32(gWkd, "gWkd")), D, H, _ptr(gW1))
     return gW1
 
 
@@ -417,9 +485,8 @@ def _attn_common(embed, series, Mext, Wkd, act, alpha, mean, var, w2, b2, paddin
 def din_attn_fwd(embed, series, Mext, Wkd, act, alpha, mean, var, w2, b2, padding_index, mask_valid, oob=None):
     args, (B, T, D, H) = _attn_common(embed, series, Mext, Wkd, act, alpha, mean, var, w2, b2, padding_index,
                                       mask_valid)
-    scores = torch.empty((B, T), dtype=torch.float32, device=embed.device)
-    pooled = torch.empty((B, D), dtype=torch.float32, device=embed.device)
-    check(lib.rec_din_attn_fwd_f32(*args, _ptr(scores), _ptr(pooled), _ptr(oob), _stream()), "rec_din_attn_fwd_f32")
+    scores, pooled = _new((B, T), embed.device), _new((B, D), embed.device)
+    _call("rec_din_attn_fwd_f32", *args, _ptr(scores), _ptr(pooled), _ptr(oob))
     return scores, pooled
 
 
@@ -430,67 +497,60 @@ def din_attn_bwd(embed, series, Mext, Wkd, act, alpha, mean, var, w2, b2, paddin
     args, (B, T, D, H) = _attn_common(embed, series, Mext, Wkd, act, alpha, mean, var, w2, b2, padding_index,
                                       mask_valid)
     dev = embed.device
-    f32 = dict(dtype=torch.float32, device=dev)
+    _f32(scores, "scores"); _f32(gpooled, "gpooled")
+    _expect(gscores, (B, T), "gscores", "[B,T]", optional=True)
     if gkeys is None:
-        gkeys = torch.empty((B, T, D), **f32)
+        gkeys = _new((B, T, D), dev)
     _f32(gkeys, "gkeys")
-    gMext = torch.empty((B, D * H + H), **f32)
-    gw2p = torch.empty((B, H), **f32)
-    galphap = torch.empty((B, H), **f32)
-    gb2p = torch.empty((B, 1), **f32)
-    if gscores is not None and tuple(_f32(gscores, "gscores").shape) != (B, T):
-        raise ValueError("gscores must be [B,T] = [%d, %d], got %s" % (B, T, tuple(gscores.shape)))
-    check(lib.rec_din_attn_bwd_f32(*args, _ptr(_f32(scores, "scores")), _ptr(_f32(gpooled, "gpooled")), _ptr(gscores),
-                                   _ptr(gkeys), _ptr(gMext), _ptr(gw2p), _ptr(galphap), _ptr(gb2p), _stream()),
-          "rec_din_attn_bwd_f32")
+    gMext, gw2p, galphap, gb2p = _new((B, D * H + H), dev), _new((B, H), dev), _new((B, H), dev), _new((B, 1), dev)
+    _call("rec_din_attn_bwd_f32", *args, _ptr(scores), _ptr(gpooled), _ptr(gscores), _ptr(gkeys), _ptr(gMext),
+          _ptr(gw2p), _ptr(galphap), _ptr(gb2p))
     return gkeys, gMext, gw2p, galphap, gb2p
 
 
 def feat_act_fwd(kind, x, alpha=None, mean=None, var=None):
-    M, N = x.shape
-    y = torch.empty_like(x)
-    check(lib.rec_feat_act_fwd_f32(kind, _ptr(_f32(x, "x")), _ptr(alpha), _ptr(mean), _ptr(var), _ptr(y), M, N,
-                                   _stream()), "rec_feat_act_fwd_f32")
+    M, N = _f32(x, "x").shape
+    y = _new_like(x)
+    _call("rec_feat_act_fwd_f32", kind, _ptr(x), _ptr(alpha), _ptr(mean), _ptr(var), _ptr(y), M, N)
     return y
 
 
 def feat_act_bwd(kind, x, gy, alpha=None, mean=None, var=None, want_alpha=False):
     M, N = x.shape
-    gx = torch.empty_like(x)
-    ga = torch.empty_like(x) if want_alpha else None
-    check(lib.rec_feat_act_bwd_f32(kind, _ptr(x), _ptr(_f32(gy, "gy")), _ptr(alpha), _ptr(mean), _ptr(var), _ptr(gx),
-                                   _ptr(ga), M, N, _stream()), "rec_feat_act_bwd_f32")
+    _f32(gy, "gy")
+    gx = _new_like(x)
+    ga = _new_like(x) if want_alpha else None
+    _call("rec_feat_act_bwd_f32", kind, _ptr(x), _ptr(gy), _ptr(alpha), _ptr(mean), _ptr(var), _ptr(gx), _ptr(ga), M, N)
     return gx, ga
 
 
 def layernorm_fwd(x, gamma, beta):
-    M, N = x.shape
-    y, xhat = torch.empty_like(x), torch.empty_like(x)
-    rstd = torch.empty(M, dtype=torch.float32, device=x.device)
-    check(lib.rec_layernorm_fwd_f32(_ptr(_f32(x, "x")), _ptr(_f32(gamma, "gamma")), _ptr(_f32(beta, "beta")), M, N,
-                                    _ptr(y), _ptr(xhat), _ptr(rstd), _stream()), "rec_layernorm_fwd_f32")
+    M, N = _f32(x, "x").shape
+    _f32(gamma, "gamma"); _f32(beta, "beta")
+    y, xhat, rstd = _new_like(x), _new_like(x), _new(M, x.device)
+    _call("rec_layernorm_fwd_f32", _ptr(x), _ptr(gamma), _ptr(beta), M, N, _ptr(y), _ptr(xhat), _ptr(rstd))
     return y, xhat, rstd
 
 
 def layernorm_bwd(gy, xhat, rstd, gamma):
-    M, N = gy.shape
-    gx, gg = torch.empty_like(gy), torch.empty_like(gy)
-    check(lib.rec_layernorm_bwd_f32(_ptr(_f32(gy, "gy")), _ptr(xhat), _ptr(rstd), _ptr(gamma), M, N, _ptr(gx), _ptr(gg),
-                                    _stream()), "rec_layernorm_bwd_f32")
+    M, N = _f32(gy, "gy").shape
+    gx, gg = _new_like(gy), _new_like(gy)
+    _call("rec_layernorm_bwd_f32", _ptr(gy), _ptr(xhat), _ptr(rstd), _ptr(gamma), M, N, _ptr(gx), _ptr(gg))
     return gx, gg
 
 
 def softmax_fwd(x):
-    M, N = x.shape
-    y = torch.empty_like(x)
-    check(lib.rec_softmax_fwd_f32(_ptr(_f32(x, "x")), M, N, _ptr(y), _stream()), "rec_softmax_fwd_f32")
+    M, N = _f32(x, "x").shape
+    y = _new_like(x)
+    _call("rec_softmax_fwd_f32", _ptr(x), M, N, _ptr(y))
     return y
 
 
 def softmax_bwd(y, gy):
     M, N = y.shape
-    gx = torch.empty_like(y)
-    check(lib.rec_softmax_bwd_f32(_ptr(y), _ptr(_f32(gy, "gy")), M, N, _ptr(gx), _stream()), "rec_softmax_bwd_f32")
+    _f32(gy, "gy")
+    gx = _new_like(y)
+    _call("rec_softmax_bwd_f32", _ptr(y), _ptr(gy), M, N, _ptr(gx))
     return gx
 
 
@@ -504,18 +564,16 @@ def emb_ipn_fwd(table, X, oob=None):
     V, E = table.shape
     B, F = X.shape
     W = F * E + F * (F - 1) // 2
-    out = torch.empty((B, W), dtype=torch.float32, device=table.device)
-    check(lib.rec_emb_ipn_fwd_f32(_ptr(table), V, E, table.stride(0), _ptr(X), B, F, _ptr(out), W, _ptr(oob), _stream()),
-          "rec_emb_ipn_fwd_f32")
+    out = _new((B, W), table.device)
+    _call("rec_emb_ipn_fwd_f32", _ptr(table), V, E, table.stride(0), _ptr(X), B, F, _ptr(out), W, _ptr(oob))
     return out
 
 
 def emb_ipn_bwd_vals(out, g, F, E):
     _f32(out, "out"); _f32(g, "g")
     B, W = out.shape
-    vals = torch.empty((B * F, E), dtype=torch.float32, device=out.device)
-    check(lib.rec_emb_ipn_bwd_vals_f32(_ptr(out), W, _ptr(g), g.shape[1], B, F, E, _ptr(vals), _stream()),
-          "rec_emb_ipn_bwd_vals_f32")
+    vals = _new((B * F, E), out.device)
+    _call("rec_emb_ipn_bwd_vals_f32", _ptr(out), W, _ptr(g), g.shape[1], B, F, E, _ptr(vals))
     return vals
 
 
@@ -526,11 +584,11 @@ def emb_bi_fwd(table, X, out=None, oob=None):
     V, E = table.shape
     B, F = X.shape
     if out is None:
-        out = torch.empty((B, E), dtype=torch.float32, device=table.device)
+        out = _new((B, E), table.device)
     _f32(out, "out")
-    S = torch.empty((B, E), dtype=torch.float32, device=table.device)
-    check(lib.rec_emb_bi_fwd_f32(_ptr(table), V, E, table.stride(0), _ptr(X), B, F, _ptr(out), out.shape[1], _ptr(S),
-                                 _ptr(oob), _stream()), "rec_emb_bi_fwd_f32")
+    S = _new((B, E), table.device)
+    _call("rec_emb_bi_fwd_f32", _ptr(table), V, E, table.stride(0), _ptr(X), B, F, _ptr(out), out.shape[1], _ptr(S),
+          _ptr(oob))
     return out, S
 
 
@@ -539,9 +597,9 @@ def emb_bi_bwd_vals(table, X, g, S):
     _table(table, "table"); _i64(X, "X"); _f32(g, "g"); _f32(S, "S")
     V, E = table.shape
     B, F = X.shape
-    vals = torch.empty((B * F, E), dtype=torch.float32, device=table.device)
-    check(lib.rec_emb_bi_bwd_vals_f32(_ptr(table), V, E, table.stride(0), _ptr(X), B, F, _ptr(g), g.shape[1], _ptr(S),
-                                      _ptr(vals), _stream()), "rec_emb_bi_bwd_vals_f32")
+    vals = _new((B * F, E), table.device)
+    _call("rec_emb_bi_bwd_vals_f32", _ptr(table), V, E, table.stride(0), _ptr(X), B, F, _ptr(g), g.shape[1], _ptr(S),
+          _ptr(vals))
     return vals
 
 
@@ -551,11 +609,9 @@ def ip_attn_fwd(embed, series, q, padding_index, oob=None):
     V, E = embed.shape
     B, T, C = series.shape
     D = C * E
-    scores = torch.empty((B, T), dtype=torch.float32, device=embed.device)
-    pooled = torch.empty((B, D), dtype=torch.float32, device=embed.device)
-    check(lib.rec_ip_attn_fwd_f32(_ptr(embed), embed.stride(0), V, E, C, _ptr(series), B, T, _ptr(q), q.shape[1],
-                                  int(padding_index), _ptr(scores), _ptr(pooled), D, _ptr(oob), _stream()),
-          "rec_ip_attn_fwd_f32")
+    scores, pooled = _new((B, T), embed.device), _new((B, D), embed.device)
+    _call("rec_ip_attn_fwd_f32", _ptr(embed), embed.stride(0), V, E, C, _ptr(series), B, T, _ptr(q), q.shape[1],
+          int(padding_index), _ptr(scores), _ptr(pooled), D, _ptr(oob))
     return scores, pooled
 
 
@@ -565,12 +621,11 @@ def ip_attn_bwd(embed, series, q, padding_index, scores, gpooled, gkeys=None):
     B, T, C = series.shape
     D = C * E
     if gkeys is None:
-        gkeys = torch.empty((B, T, D), dtype=torch.float32, device=embed.device)
+        gkeys = _new((B, T, D), embed.device)
     _f32(gkeys, "gkeys")
-    gq = torch.empty((B, D), dtype=torch.float32, device=embed.device)
-    check(lib.rec_ip_attn_bwd_f32(_ptr(embed), embed.stride(0), V, E, C, _ptr(series), B, T, _ptr(q), q.shape[1],
-                                  int(padding_index), _ptr(scores), _ptr(gpooled), gpooled.shape[1], _ptr(gkeys),
-                                  _ptr(gq), _stream()), "rec_ip_attn_bwd_f32")
+    gq = _new((B, D), embed.device)
+    _call("rec_ip_attn_bwd_f32", _ptr(embed), embed.stride(0), V, E, C, _ptr(series), B, T, _ptr(q), q.shape[1],
+          int(padding_index), _ptr(scores), _ptr(gpooled), gpooled.shape[1], _ptr(gkeys), _ptr(gq))
     return gkeys, gq
 
 
@@ -578,25 +633,22 @@ def batchnorm_fwd(x, gamma, beta, moving_mean, moving_var, training, eps=1e-3, m
     """Keras BatchNormalization on [B,N]; moving statistics are updated in place when training."""
     _f32(x, "x")
     B, N = x.shape
-    y = torch.empty_like(x)
-    xhat = torch.empty_like(x) if save else None
-    rstd = torch.empty(N, dtype=torch.float32, device=x.device) if save else None
-    ws = torch.empty(lib.rec_batchnorm_workspace_bytes(B, N) // 4, dtype=torch.float32, device=x.device)
-    check(lib.rec_batchnorm_fwd_f32(_ptr(x), N, B, N, _ptr(gamma), _ptr(beta), float(eps), float(momentum),
-                                    1 if training else 0, _ptr(moving_mean), _ptr(moving_var), _ptr(y), _ptr(xhat),
-                                    _ptr(rstd), _ptr(ws), _stream()), "rec_batchnorm_fwd_f32")
+    y = _new_like(x)
+    xhat = _new_like(x) if save else None
+    rstd = _new(N, x.device) if save else None
+    ws = _workspace(lib.rec_batchnorm_workspace_bytes(B, N), None, x.device)
+    _call("rec_batchnorm_fwd_f32", _ptr(x), N, B, N, _ptr(gamma), _ptr(beta), float(eps), float(momentum),
+          1 if training else 0, _ptr(moving_mean), _ptr(moving_var), _ptr(y), _ptr(xhat), _ptr(rstd), _ptr(ws))
     return y, xhat, rstd
 
 
 def batchnorm_bwd(g, xhat, rstd, gamma, training):
     _f32(g, "g")
     B, N = g.shape
-    gx = torch.empty_like(g)
-    ggamma = torch.empty(N, dtype=torch.float32, device=g.device)
-    gbeta = torch.empty(N, dtype=torch.float32, device=g.device)
-    ws = torch.empty(lib.rec_batchnorm_workspace_bytes(B, N) // 4, dtype=torch.float32, device=g.device)
-    check(lib.rec_batchnorm_bwd_f32(_ptr(g), _ptr(xhat), _ptr(rstd), B, N, _ptr(gamma), 1 if training else 0, _ptr(gx),
-                                    _ptr(ggamma), _ptr(gbeta), _ptr(ws), _stream()), "rec_batchnorm_bwd_f32")
+    gx, ggamma, gbeta = _new_like(g), _new(N, g.device, B), _new(N, g.device, B)
+    ws = _workspace(lib.rec_batchnorm_workspace_bytes(B, N), None, g.device)
+    _call("rec_batchnorm_bwd_f32", _ptr(g), _ptr(xhat), _ptr(rstd), B, N, _ptr(gamma), 1 if training else 0, _ptr(gx),
+          _ptr(ggamma), _ptr(gbeta), _ptr(ws))
     return gx, ggamma, gbeta
 
 
@@ -607,10 +659,10 @@ def ffm_fwd(v, w, bias, X, want_prob=False, oob=None):
     B = X.shape[0]
     if X.shape[1] != F:
         raise ValueError("X has %d fields, the table %d" % (X.shape[1], F))
-    z = torch.empty(B, dtype=torch.float32, device=v.device)
-    prob = torch.empty(B, dtype=torch.float32, device=v.device) if want_prob else None
-    check(lib.rec_ffm_fwd_f32(_ptr(v), F * E, _ptr(w), w.stride(0), _ptr(bias), V, E, _ptr(X), B, F, _ptr(z), _ptr(prob),
-                              _ptr(oob), _stream()), "rec_ffm_fwd_f32")
+    z = _new(B, v.device)
+    prob = _new(B, v.device) if want_prob else None
+    _call("rec_ffm_fwd_f32", _ptr(v), F * E, _ptr(w), w.stride(0), _ptr(bias), V, E, _ptr(X), B, F, _ptr(z), _ptr(prob),
+          _ptr(oob))
     return z, prob
 
 
@@ -619,9 +671,9 @@ def ffm_bwd_rows(v, X, gz, plan):
     _f32(v, "v"); _i64(X, "X"); _f32(gz, "gz")
     V, F, E = v.shape
     B = X.shape[0]
-    rows = torch.empty((max(B * F, 1), F, E), dtype=torch.float32, device=v.device)
-    check(lib.rec_ffm_bwd_rows_f32(_ptr(v), F * E, V, E, _ptr(X), B, F, _ptr(gz), _ptr(plan.perm), _ptr(plan.seg_start),
-                                   _ptr(plan.n_uniq), _ptr(rows), _stream()), "rec_ffm_bwd_rows_f32")
+    rows = _new((max(B * F, 1), F, E), v.device)
+    _call("rec_ffm_bwd_rows_f32", _ptr(v), F * E, V, E, _ptr(X), B, F, _ptr(gz), _ptr(plan.perm), _ptr(plan.seg_start),
+          _ptr(plan.n_uniq), _ptr(rows))
     return rows
 
 
@@ -644,20 +696,19 @@ def _cin_args(x0, Ws):
     B, F, E = x0.shape
     H = [int(w.shape[-1]) for w in Ws]
     cin_check_shape(F, E, H)
-    Hh = (C.c_int * len(H))(*H)
-    Wh = (C.c_void_p * len(Ws))(*[_f32(w, "W%d" % k).data_ptr() for k, w in enumerate(Ws)])
-    return B, F, E, H, Hh, Wh
+    for k, w in enumerate(Ws):
+        _f32(w, "W%d" % k)
+    return B, F, E, H, _ints(H), _ptr_array(Ws)
 
 
 def cin_fwd(x0, Ws):
-    """x0 [B,F,E], Ws: the L CIN weights (1, F*H_k, H_{k+1}) -> (cin_part [B, sum H], states [B, sum H, E])."""
+    """x0 [B,F,E], Ws: the L CIN weights (1, F*H_k, H_{k+1}) -> (cin_part [B, sum H], states [B, sum H, E]).  An empty
+    batch is an error of the entry point (REC_E_ARG), unlike every other family's."""
     _f32(x0, "x0")
     B, F, E, H, Hh, Wh = _cin_args(x0, Ws)
     SH = sum(H)
-    states = torch.empty((B, SH, E), dtype=torch.float32, device=x0.device)
-    cin_part = torch.empty((B, SH), dtype=torch.float32, device=x0.device)
-    check(lib.rec_cin_fwd_f32(_ptr(x0), B, F, E, len(H), Hh, Wh, _ptr(states), _ptr(cin_part), _stream()),
-          "rec_cin_fwd_f32")
+    states, cin_part = _new((B, SH, E), x0.device), _new((B, SH), x0.device)
+    _call("rec_cin_fwd_f32", _ptr(x0), B, F, E, len(H), Hh, Wh, _ptr(states), _ptr(cin_part))
     return cin_part, states
 
 
@@ -666,13 +717,10 @@ def cin_bwd(x0, states, g, Ws):
     B, F, E, H, Hh, Wh = _cin_args(x0, Ws)
     _f32(states, "states")
     _f32(g, "g")
-    dx0 = torch.empty_like(x0)
-    dWs = [torch.empty_like(w) for w in Ws]
-    dWh = (C.c_void_p * len(dWs))(*[d.data_ptr() for d in dWs])
-    nbytes = lib.rec_cin_workspace_bytes(B, F, E, len(H), Hh)
-    ws = _workspace(nbytes, "rec_cin_workspace_bytes", x0.device, torch.float32)
-    check(lib.rec_cin_bwd_f32(_ptr(x0), _ptr(states), _ptr(g), B, F, E, len(H), Hh, Wh, _ptr(dx0), dWh, _ptr(ws), nbytes,
-                              _stream()), "rec_cin_bwd_f32")
+    dx0 = _new_like(x0)
+    dWs = [_new_like(w) for w in Ws]
+    _call_ws("rec_cin_workspace_bytes", (B, F, E, len(H), Hh), "rec_cin_bwd_f32", x0.device, _ptr(x0), _ptr(states),
+             _ptr(g), B, F, E, len(H), Hh, Wh, _ptr(dx0), _ptr_array(dWs))
     return dx0, dWs
 
 
@@ -703,13 +751,10 @@ def fibinet_fwd(x_emb, x_cont, S0, S1, W, type_code):
     fibinet_check_shape(F, E, C, mid)
     P = F * (F - 1) // 2
     dev = x_emb.device
-    dnn_in = torch.empty((B, 2 * P * E + C), dtype=torch.float32, device=dev)
-    A = torch.empty((B, F), dtype=torch.float32, device=dev)
-    H1 = torch.empty((B, mid), dtype=torch.float32, device=dev)
+    dnn_in, A, H1 = _new((B, 2 * P * E + C), dev), _new((B, F), dev), _new((B, mid), dev)
     if B > 0:
-        check(lib.rec_fibinet_fwd_f32(_ptr(x_emb), _ptr(x_cont) if C > 0 else None, _ptr(S0), _ptr(S1), _ptr(W), B, F,
-                                      E, C, mid, type_code, _ptr(dnn_in), _ptr(A), _ptr(H1), _stream()),
-              "rec_fibinet_fwd_f32")
+        _call("rec_fibinet_fwd_f32", _ptr(x_emb), _ptr(x_cont) if C > 0 else None, _ptr(S0), _ptr(S1), _ptr(W), B, F, E,
+              C, mid, type_code, _ptr(dnn_in), _ptr(A), _ptr(H1))
     return dnn_in, A, H1
 
 
@@ -720,15 +765,11 @@ def fibinet_bwd(x_emb, g, A, H1, S0, S1, W, type_code):
     mid = S0.shape[1]
     C = g.shape[1] - F * (F - 1) * E
     fibinet_check_shape(F, E, C, mid)
-    dx = torch.empty_like(x_emb)
-    if B == 0:
-        return dx, torch.zeros_like(W), torch.zeros_like(S0), torch.zeros_like(S1)
-    dW, dS0, dS1 = torch.empty_like(W), torch.empty_like(S0), torch.empty_like(S1)
-    nbytes = lib.rec_fibinet_workspace_bytes(B, F, E, mid, type_code)
-    ws = _workspace(nbytes, "rec_fibinet_workspace_bytes", x_emb.device, torch.float32)
-    check(lib.rec_fibinet_bwd_f32(_ptr(x_emb), _ptr(g), _ptr(A), _ptr(H1), _ptr(S0), _ptr(S1), _ptr(W), B, F, E, C, mid,
-                                  type_code, _ptr(dx), _ptr(dW), _ptr(dS0), _ptr(dS1), _ptr(ws), nbytes, _stream()),
-          "rec_fibinet_bwd_f32")
+    dx, dW, dS0, dS1 = _new_like(x_emb), _new_like(W, B), _new_like(S0, B), _new_like(S1, B)
+    if B > 0:
+        _call_ws("rec_fibinet_workspace_bytes", (B, F, E, mid, type_code), "rec_fibinet_bwd_f32", x_emb.device,
+                 _ptr(x_emb), _ptr(g), _ptr(A), _ptr(H1), _ptr(S0), _ptr(S1), _ptr(W), B, F, E, C, mid, type_code,
+                 _ptr(dx), _ptr(dW), _ptr(dS0), _ptr(dS1))
     return dx, dW, dS0, dS1
 
 
@@ -749,11 +790,6 @@ def autoint_check_shape(F, E, H, C=0):
             % (AUTOINT_MAX_F, AUTOINT_MAX_E, F, E, H, C))
 
 
-def _autoint_ws(B, F, E, H, C, res, dev):
-    nbytes = lib.rec_autoint_workspace_bytes(B, F, E, H, C, res)
-    return _workspace(nbytes, "rec_autoint_workspace_bytes", dev, torch.float32), nbytes
-
-
 def autoint_fwd(x, Wq, Wk, Wv, Wres, num_heads, res, scaling, x_cont=None, cemb=None, want_o=False):
     """One attention layer.  x [B,Fc,E] (plus C continuous fields cemb[c] * x_cont[:, c] appended last when x_cont
     [B,C] and cemb [C,E] are given), W* [E,E] (Wres only for res == 2) -> (y [B,F,E], stats [2,H,F,F], o [B,F,E] or
@@ -763,51 +799,50 @@ def autoint_fwd(x, Wq, Wk, Wv, Wres, num_heads, res, scaling, x_cont=None, cemb=
     B, Fc, E = x.shape
     C = 0 if x_cont is None else x_cont.shape[1]
     if C:
-        _f32(x_cont, "x_cont"); _f32(cemb, "cemb")
-        if tuple(cemb.shape) != (C, E) or x_cont.shape[0] != B:
-            raise ValueError("x_cont [B,C] and cemb [C,E] do not match x %s" % (tuple(x.shape),))
+        _expect(x_cont, (B, C), "x_cont", "[B,C]"); _expect(cemb, (C, E), "cemb", "[C,E]")
+    else:
+        x_cont = cemb = None
     if res == 2:
         _f32(Wres, "Wres")
+    else:
+        Wres = None
     F, H = Fc + C, int(num_heads)
     autoint_check_shape(F, E, H, C)
-    for t in (Wq, Wk, Wv) + ((Wres,) if res == 2 else ()):
-        if tuple(t.shape) != (E, E):
-            raise ValueError("attention weights must be [E,E] = [%d,%d], got %s" % (E, E, tuple(t.shape)))
+    _expect_all([(t, (E, E), n) for t, n in ((Wq, "Wq"), (Wk, "Wk"), (Wv, "Wv"), (Wres, "Wres")) if t is not None])
     dev = x.device
-    y = torch.empty((B, F, E), dtype=torch.float32, device=dev)
-    o = torch.empty((B, F, E), dtype=torch.float32, device=dev) if want_o else None
-    stats = torch.empty((2, H, F, F), dtype=torch.float32, device=dev)
+    y = _new((B, F, E), dev)
+    o = _new((B, F, E), dev) if want_o else None
+    stats = _new((2, H, F, F), dev, B)
     if B > 0:
-        ws, nbytes = _autoint_ws(B, F, E, H, C, res, dev)
-        check(lib.rec_autoint_fwd_f32(_ptr(x), _ptr(x_cont) if C else None, _ptr(cemb) if C else None, _ptr(Wq),
-                                      _ptr(Wk), _ptr(Wv), _ptr(Wres) if res == 2 else None, B, F, E, H, C, res,
-                                      int(bool(scaling)), _ptr(y), _ptr(o) if want_o else None, _ptr(stats), _ptr(ws),
-                                      nbytes, _stream()), "rec_autoint_fwd_f32")
+        _call_ws("rec_autoint_workspace_bytes", (B, F, E, H, C, res), "rec_autoint_fwd_f32", dev, _ptr(x), _ptr(x_cont),
+                 _ptr(cemb), _ptr(Wq), _ptr(Wk), _ptr(Wv), _ptr(Wres), B, F, E, H, C, res, int(bool(scaling)), _ptr(y),
+                 _ptr(o), _ptr(stats))
     return y, stats, o
 
 
 def autoint_bwd(x, Wq, Wk, Wv, Wres, y, dy, stats, num_heads, res, scaling, x_cont=None, cemb=None):
     """-> (dx [B,Fc,E], dWq, dWk, dWv, dWres (res == 2, else None), dcemb [C,E] (C > 0, else None))."""
-    for t, n in ((x, "x"), (Wq, "Wq"), (Wk, "Wk"), (Wv, "Wv"), (y, "y"), (dy, "dy"), (stats, "stats")):
+    for t, n in ((x, "x"), (Wq, "Wq"), (Wk, "Wk"), (Wv, "Wv")):
         _f32(t, n)
     B, Fc, E = x.shape
     C = 0 if x_cont is None else x_cont.shape[1]
+    if not C:
+        x_cont = cemb = None
+    if res != 2:
+        Wres = None
     F, H = Fc + C, int(num_heads)
     autoint_check_shape(F, E, H, C)
-    if tuple(y.shape) != (B, F, E) or tuple(dy.shape) != (B, F, E) or tuple(stats.shape) != (2, H, F, F):
-        raise ValueError("y, dy [B,F,E] and stats [2,H,F,F] do not match x %s" % (tuple(x.shape),))
+    _expect_all([(y, (B, F, E), "y"), (dy, (B, F, E), "dy"), (stats, (2, H, F, F), "stats")])
     dev = x.device
-    dx = torch.empty_like(x)
-    dW = [torch.zeros((E, E), dtype=torch.float32, device=dev) for _ in range(3 + (res == 2))]
+    dx = _new_like(x)
+    dWq, dWk, dWv = (torch.zeros((E, E), dtype=torch.float32, device=dev) for _ in range(3))
+    dWres = torch.zeros((E, E), dtype=torch.float32, device=dev) if res == 2 else None
     dcemb = torch.zeros((C, E), dtype=torch.float32, device=dev) if C else None
     if B > 0:
-        ws, nbytes = _autoint_ws(B, F, E, H, C, res, dev)
-        check(lib.rec_autoint_bwd_f32(_ptr(x), _ptr(x_cont) if C else None, _ptr(cemb) if C else None, _ptr(Wq),
-                                      _ptr(Wk), _ptr(Wv), _ptr(Wres) if res == 2 else None, _ptr(y), _ptr(dy),
-                                      _ptr(stats), B, F, E, H, C, res, int(bool(scaling)), _ptr(dx), _ptr(dW[0]),
-                                      _ptr(dW[1]), _ptr(dW[2]), _ptr(dW[3]) if res == 2 else None,
-                                      _ptr(dcemb) if C else None, _ptr(ws), nbytes, _stream()), "rec_autoint_bwd_f32")
-    return dx, dW[0], dW[1], dW[2], (dW[3] if res == 2 else None), dcemb
+        _call_ws("rec_autoint_workspace_bytes", (B, F, E, H, C, res), "rec_autoint_bwd_f32", dev, _ptr(x), _ptr(x_cont),
+                 _ptr(cemb), _ptr(Wq), _ptr(Wk), _ptr(Wv), _ptr(Wres), _ptr(y), _ptr(dy), _ptr(stats), B, F, E, H, C,
+                 res, int(bool(scaling)), _ptr(dx), _ptr(dWq), _ptr(dWk), _ptr(dWv), _ptr(dWres), _ptr(dcemb))
+    return dx, dWq, dWk, dWv, dWres, dcemb
 
 
 # ---- Attentional FM, fused with the lookup (csrc/afm.hip)
@@ -841,12 +876,10 @@ def emb_afm_fwd(table, X, Wa, ba, hv, bh, oob=None, want_rows=False):
     A = _afm_params(E, Wa, ba, hv, bh)
     afm_check_shape(F, E, A)
     dev = table.device
-    o = torch.empty((B, E), dtype=torch.float32, device=dev)
-    stats = torch.empty((B, 2), dtype=torch.float32, device=dev)
-    rows = torch.empty((B, F, E), dtype=torch.float32, device=dev) if want_rows else None
-    check(lib.rec_emb_afm_fwd_f32(_ptr(table), V, E, table.stride(0), _ptr(X), B, F, A, _ptr(Wa), _ptr(ba), _ptr(hv),
-                                  _ptr(bh), _ptr(o), _ptr(stats), _ptr(rows), _ptr(oob), _stream()),
-          "rec_emb_afm_fwd_f32")
+    o, stats = _new((B, E), dev), _new((B, 2), dev)
+    rows = _new((B, F, E), dev) if want_rows else None
+    _call("rec_emb_afm_fwd_f32", _ptr(table), V, E, table.stride(0), _ptr(X), B, F, A, _ptr(Wa), _ptr(ba), _ptr(hv),
+          _ptr(bh), _ptr(o), _ptr(stats), _ptr(rows), _ptr(oob))
     return o, stats, rows
 
 
@@ -858,22 +891,15 @@ def emb_afm_bwd(table, X, Wa, ba, hv, bh, o, stats, dout, rows=None):
     B, F = X.shape
     A = _afm_params(E, Wa, ba, hv, bh)
     afm_check_shape(F, E, A)
-    for t, n in ((o, "o"), (stats, "stats"), (dout, "dout")):
-        _f32(t, n)
-    if tuple(o.shape) != (B, E) or tuple(dout.shape) != (B, E) or tuple(stats.shape) != (B, 2):
-        raise ValueError("o, dout [B,E] and stats [B,2] do not match X %s" % (tuple(X.shape),))
-    if rows is not None and tuple(_f32(rows, "rows").shape) != (B, F, E):
-        raise ValueError("rows must be [B,F,E]")
+    _expect_all([(o, (B, E), "o"), (stats, (B, 2), "stats"), (dout, (B, E), "dout")])
+    _expect(rows, (B, F, E), "rows", "[B,F,E]", optional=True)
     dev = table.device
-    vals = torch.empty((B * F, E), dtype=torch.float32, device=dev)
+    vals = _new((B * F, E), dev)
     dWa, dba, dhv, dbh = (torch.zeros_like(t) for t in (Wa, ba, hv, bh))
     if B > 0:
-        nbytes = lib.rec_afm_workspace_bytes(B, F, E, A)
-        ws = _workspace(nbytes, "rec_afm_workspace_bytes", dev, torch.float32)
-        check(lib.rec_emb_afm_bwd_f32(_ptr(table), V, E, table.stride(0), _ptr(X), B, F, A, _ptr(Wa), _ptr(ba),
-                                      _ptr(hv), _ptr(bh), _ptr(o), _ptr(stats), _ptr(rows), _ptr(dout), _ptr(vals),
-                                      _ptr(dWa), _ptr(dba), _ptr(dhv), _ptr(dbh), _ptr(ws), nbytes, _stream()),
-              "rec_emb_afm_bwd_f32")
+        _call_ws("rec_afm_workspace_bytes", (B, F, E, A), "rec_emb_afm_bwd_f32", dev, _ptr(table), V, E, table.stride(0),
+                 _ptr(X), B, F, A, _ptr(Wa), _ptr(ba), _ptr(hv), _ptr(bh), _ptr(o), _ptr(stats), _ptr(rows), _ptr(dout),
+                 _ptr(vals), _ptr(dWa), _ptr(dba), _ptr(dhv), _ptr(dbh))
     return vals, dWa, dba, dhv, dbh
 
 
@@ -881,10 +907,6 @@ def emb_afm_bwd(table, X, Wa, ba, hv, bh, o, stats, dout, rows=None):
 _FIELD_CONV_MAX = [LIMITS["REC_FIELD_CONV_MAX_" + d] for d in ("F", "E", "L", "C", "KW")]
 CCPM_MAX_F, CCPM_MAX_E, CCPM_MAX_L, CCPM_MAX_C, CCPM_MAX_KW = _FIELD_CONV_MAX       # fields, embedding_dims, layers,
 FGCNN_MAX_F, FGCNN_MAX_E, FGCNN_MAX_L, FGCNN_MAX_C, FGCNN_MAX_KW = _FIELD_CONV_MAX  # filters, kernel_width
-
-
-def _ints(values):
-    return (C.c_int * len(values))(*[int(v) for v in values])
 
 
 def field_conv_param_count(filters, kernel_width):
@@ -941,11 +963,10 @@ def emb_ccpm_fwd(table, X, params, filters, kernel_width, oob=None, want_rows=Fa
     ks = ccpm_check_shape(F, E, filters, kernel_width)
     _field_conv_params(params, filters, kernel_width)
     dev = table.device
-    out = torch.empty((B, ks[-1] * E * int(filters[-1])), dtype=torch.float32, device=dev)
-    rows = torch.empty((B, F, E), dtype=torch.float32, device=dev) if want_rows else None
-    check(lib.rec_emb_ccpm_fwd_f32(_ptr(table), V, E, table.stride(0), _ptr(X), B, F, len(ks), _ints(filters),
-                                   _ints(kernel_width), _ints(ks), _ptr(params), _ptr(out), _ptr(rows), _ptr(oob),
-                                   _stream()), "rec_emb_ccpm_fwd_f32")
+    out = _new((B, ks[-1] * E * int(filters[-1])), dev)
+    rows = _new((B, F, E), dev) if want_rows else None
+    _call("rec_emb_ccpm_fwd_f32", _ptr(table), V, E, table.stride(0), _ptr(X), B, F, len(ks), _ints(filters),
+          _ints(kernel_width), _ints(ks), _ptr(params), _ptr(out), _ptr(rows), _ptr(oob))
     return out, rows
 
 
@@ -957,20 +978,15 @@ def emb_ccpm_bwd(table, X, params, filters, kernel_width, dout, rows=None):
     B, F = X.shape
     ks = ccpm_check_shape(F, E, filters, kernel_width)
     _field_conv_params(params, filters, kernel_width)
-    if tuple(dout.shape) != (B, ks[-1] * E * int(filters[-1])):
-        raise ValueError("dout must be [B, %d], got %s" % (ks[-1] * E * int(filters[-1]), tuple(dout.shape)))
-    if rows is not None and tuple(_f32(rows, "rows").shape) != (B, F, E):
-        raise ValueError("rows must be [B,F,E]")
+    _expect(dout, (B, ks[-1] * E * int(filters[-1])), "dout", "[B, k_L E C_L]")
+    _expect(rows, (B, F, E), "rows", "[B,F,E]", optional=True)
     dev = table.device
-    vals = torch.empty((B * F, E), dtype=torch.float32, device=dev)
+    vals = _new((B * F, E), dev)
     dparams = torch.zeros_like(params)
     if B > 0:
-        fi, kwi, ki = _ints(filters), _ints(kernel_width), _ints(ks)
-        nbytes = lib.rec_ccpm_workspace_bytes(B, F, E, len(ks), fi, kwi, ki)
-        ws = _workspace(nbytes, "rec_ccpm_workspace_bytes", dev, torch.float32)
-        check(lib.rec_emb_ccpm_bwd_f32(_ptr(table), V, E, table.stride(0), _ptr(X), B, F, len(ks), fi, kwi, ki,
-                                       _ptr(params), _ptr(rows), _ptr(dout), _ptr(vals), _ptr(dparams), _ptr(ws),
-                                       nbytes, _stream()), "rec_emb_ccpm_bwd_f32")
+        stack = (len(ks), _ints(filters), _ints(kernel_width), _ints(ks))
+        _call_ws("rec_ccpm_workspace_bytes", (B, F, E, *stack), "rec_emb_ccpm_bwd_f32", dev, _ptr(table), V, E,
+                 table.stride(0), _ptr(X), B, F, *stack, _ptr(params), _ptr(rows), _ptr(dout), _ptr(vals), _ptr(dparams))
     return vals, dparams
 
 
@@ -1027,10 +1043,6 @@ def fgcnn_check_shape(F, E, filters, kernel_width, pooling_width, dnn_maps=None)
     return heights
 
 
-def _ptr_array(tensors):
-    return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
-
-
 def emb_fgcnn_fwd(table, X, params, filters, kernel_width, pooling_width, oob=None):
     """Lookup + L x (field conv, tanh, max pool) in one launch: params is the flat K_1 | b_1 | K_2 | ... -> (rows
     [B,F,E], [p_1 .. p_L]) with p_j [B, H_j E C_j] the Flatten of the j-th pooled map."""
@@ -1040,11 +1052,10 @@ def emb_fgcnn_fwd(table, X, params, filters, kernel_width, pooling_width, oob=No
     hs = fgcnn_check_shape(F, E, filters, kernel_width, pooling_width)
     _field_conv_params(params, filters, kernel_width)
     dev = table.device
-    rows = torch.empty((B, F, E), dtype=torch.float32, device=dev)
-    pooled = [torch.empty((B, h * E * int(c)), dtype=torch.float32, device=dev) for h, c in zip(hs, filters)]
-    check(lib.rec_emb_fgcnn_fwd_f32(_ptr(table), V, E, table.stride(0), _ptr(X), B, F, len(hs), _ints(filters),
-                                    _ints(kernel_width), _ints(pooling_width), _ptr(params), _ptr(rows),
-                                    _ptr_array(pooled), _ptr(oob), _stream()), "rec_emb_fgcnn_fwd_f32")
+    rows = _new((B, F, E), dev)
+    pooled = [_new((B, h * E * int(c)), dev) for h, c in zip(hs, filters)]
+    _call("rec_emb_fgcnn_fwd_f32", _ptr(table), V, E, table.stride(0), _ptr(X), B, F, len(hs), _ints(filters),
+          _ints(kernel_width), _ints(pooling_width), _ptr(params), _ptr(rows), _ptr_array(pooled), _ptr(oob))
     return rows, pooled
 
 
@@ -1060,21 +1071,15 @@ def emb_fgcnn_bwd(rows, params, filters, kernel_width, pooling_width, dpooled, d
     _field_conv_params(params, filters, kernel_width)
     if len(dpooled) != len(hs):
         raise ValueError("dpooled must hold %d tensors, got %d" % (len(hs), len(dpooled)))
-    for j, (d, h, c) in enumerate(zip(dpooled, hs, filters)):
-        if tuple(_f32(d, "dpooled[%d]" % j).shape) != (B, h * E * int(c)):
-            raise ValueError("dpooled[%d] must be [B, %d], got %s" % (j, h * E * int(c), tuple(d.shape)))
-    if drows_direct is not None and tuple(_f32(drows_direct, "drows_direct").shape) != (B, F, E):
-        raise ValueError("drows_direct must be [B,F,E]")
+    _expect_all([(d, (B, h * E * int(c)), "dpooled[%d]" % j) for j, (d, h, c) in enumerate(zip(dpooled, hs, filters))])
+    _expect(drows_direct, (B, F, E), "drows_direct", "[B,F,E]", optional=True)
     dev = rows.device
-    vals = torch.empty((B * F, E), dtype=torch.float32, device=dev)
+    vals = _new((B * F, E), dev)
     dparams = torch.zeros_like(params)
     if B > 0:
-        fi, kwi, pwi = _ints(filters), _ints(kernel_width), _ints(pooling_width)
-        nbytes = lib.rec_fgcnn_workspace_bytes(B, F, E, len(hs), fi, kwi, pwi)
-        ws = _workspace(nbytes, "rec_fgcnn_workspace_bytes", dev, torch.float32)
-        check(lib.rec_emb_fgcnn_bwd_f32(E, B, F, len(hs), fi, kwi, pwi, _ptr(params), _ptr(rows), _ptr_array(dpooled),
-                                        _ptr(drows_direct), _ptr(vals), _ptr(dparams), _ptr(ws), nbytes, _stream()),
-              "rec_emb_fgcnn_bwd_f32")
+        stack = (len(hs), _ints(filters), _ints(kernel_width), _ints(pooling_width))
+        _call_ws("rec_fgcnn_workspace_bytes", (B, F, E, *stack), "rec_emb_fgcnn_bwd_f32", dev, E, B, F, *stack,
+                 _ptr(params), _ptr(rows), _ptr_array(dpooled), _ptr(drows_direct), _ptr(vals), _ptr(dparams))
     return vals, dparams
 
 
@@ -1105,60 +1110,40 @@ def mask_block_check_shape(D, P, O, R):
             % (MASKNET_MAX_D, MASKNET_MAX_P, MASKNET_MAX_O, MASKNET_MAX_R, D, P, O, R))
 
 
-def _masknet_ln_args(F, E, Fk, B, values, gamma, beta):
-    masknet_ln_check_shape(F, E, Fk)
-    if tuple(_f32(gamma, "gamma").shape) != (F, E) or (beta is not None and tuple(_f32(beta, "beta").shape) != (F, E)):
-        raise ValueError("gamma and beta must be [fields, embedding_dims] = [%d, %d]" % (F, E))
-    if Fk > 0 and tuple(_f32(values, "values").shape) != (B, Fk):
-        raise ValueError("values must be [B, %d], got %s" % (Fk, tuple(values.shape)))
-
-
 def emb_masknet_ln_fwd(table, X, values, gamma, beta, oob=None):
     """Lookup (the last ``values.shape[1]`` columns of X are the keys of continuous features, their rows scaled by
     ``values``) + one LayerNorm per field in one launch -> (x_emb [B, F E], x_norm [B, F E], stats [B, F, 2])."""
-    _table(table, "table"); _i64(X, "X")
-    if X.dim() != 2:
-        raise ValueError("X must be [B, fields]")
-    V, E = table.shape
-    B, F = X.shape
-    Fk = 0 if values is None else (values.shape[1] if values.dim() == 2 else -1)
-    _masknet_ln_args(F, E, Fk, B, values, gamma, beta)
+    V, E = _table(table, "table").shape
+    B, F, E, Fk = _keyed_head(X, values, E)
+    masknet_ln_check_shape(F, E, Fk)
+    _expect(gamma, (F, E), "gamma", "[fields, embedding_dims]")
+    _expect(beta, (F, E), "beta", "[fields, embedding_dims]", optional=True)
     dev = table.device
-    x_emb = torch.empty((B, F * E), dtype=torch.float32, device=dev)
-    x_norm = torch.empty((B, F * E), dtype=torch.float32, device=dev)
-    stats = torch.empty((B, F, 2), dtype=torch.float32, device=dev)
-    check(lib.rec_emb_masknet_ln_fwd_f32(_ptr(table), V, E, table.stride(0), _ptr(X), _ptr(values), B, F, Fk, _ptr(gamma),
-                                         _ptr(beta), _ptr(x_emb), _ptr(x_norm), _ptr(stats), _ptr(oob), _stream()),
-          "rec_emb_masknet_ln_fwd_f32")
+    x_emb, x_norm, stats = _new((B, F * E), dev), _new((B, F * E), dev), _new((B, F, 2), dev)
+    _call("rec_emb_masknet_ln_fwd_f32", _ptr(table), V, E, table.stride(0), _ptr(X), _ptr(values), B, F, Fk, _ptr(gamma),
+          _ptr(beta), _ptr(x_emb), _ptr(x_norm), _ptr(stats), _ptr(oob))
     return x_emb, x_norm, stats
 
 
 def emb_masknet_ln_bwd(x_emb, stats, values, gamma, dx_norm, dx_emb=None):
     """x_emb / stats as the forward wrote them, dx_norm [B, F E], dx_emb = dLoss/dx_emb from its other consumers (None:
     zeros) -> (vals [B*F, E] IndexedSlices values in the order of X, dgamma [F, E], dbeta [F, E])."""
-    _f32(x_emb, "x_emb"); _f32(stats, "stats"); _f32(dx_norm, "dx_norm")
-    if stats.dim() != 3 or stats.shape[2] != 2:
+    if _f32(stats, "stats").dim() != 3 or stats.shape[2] != 2:
         raise ValueError("stats must be [B, fields, 2]")
-    B, F, _ = stats.shape
-    if x_emb.dim() != 2 or x_emb.shape[0] != B or F < 1 or x_emb.shape[1] % F:
-        raise ValueError("x_emb must be [B, fields * embedding_dims] for stats %s, got %s"
-                         % (tuple(stats.shape), tuple(x_emb.shape)))
-    E = x_emb.shape[1] // F
-    Fk = 0 if values is None else (values.shape[1] if values.dim() == 2 else -1)
-    _masknet_ln_args(F, E, Fk, B, values, gamma, None)
-    for t, n in ((dx_norm, "dx_norm"), (dx_emb, "dx_emb")):
-        if t is not None and tuple(_f32(t, n).shape) != (B, F * E):
-            raise ValueError("%s must be [B, %d], got %s" % (n, F * E, tuple(t.shape)))
+    B, F, E, Fk = _keyed_head(x_emb, values, F=stats.shape[1], name="x_emb")
+    masknet_ln_check_shape(F, E, Fk)
+    _expect(stats, (B, F, 2), "stats", "[B, fields, 2]")
+    _expect(gamma, (F, E), "gamma", "[fields, embedding_dims]")
+    _expect(dx_norm, (B, F * E), "dx_norm", "[B, F E]")
+    _expect(dx_emb, (B, F * E), "dx_emb", "[B, F E]", optional=True)
     dev = x_emb.device
-    vals = torch.empty((B * F, E), dtype=torch.float32, device=dev)
+    vals = _new((B * F, E), dev)
     dgamma = torch.zeros((F, E), dtype=torch.float32, device=dev)
     dbeta = torch.zeros((F, E), dtype=torch.float32, device=dev)
     if B > 0:
-        nbytes = lib.rec_masknet_ln_workspace_bytes(B, F, E)
-        ws = _workspace(nbytes, "rec_masknet_ln_workspace_bytes", dev, torch.float32)
-        check(lib.rec_emb_masknet_ln_bwd_f32(_ptr(x_emb), _ptr(stats), _ptr(values), _ptr(gamma), _ptr(dx_norm),
-                                             _ptr(dx_emb), B, F, Fk, E, _ptr(vals), _ptr(dgamma), _ptr(dbeta), _ptr(ws),
-                                             nbytes, _stream()), "rec_emb_masknet_ln_bwd_f32")
+        _call_ws("rec_masknet_ln_workspace_bytes", (B, F, E), "rec_emb_masknet_ln_bwd_f32", dev, _ptr(x_emb), _ptr(stats),
+                 _ptr(values), _ptr(gamma), _ptr(dx_norm), _ptr(dx_emb), B, F, Fk, E, _ptr(vals), _ptr(dgamma),
+                 _ptr(dbeta))
     return vals, dgamma, dbeta
 
 
@@ -1178,12 +1163,6 @@ def _mask_block_args(x_emb, v, W1, W2, W3):
     return B, D, P, O, R
 
 
-def _vec(t, n, name):
-    if _f32(t, name).numel() != n:
-        raise ValueError("%s must hold %d floats, got %s" % (name, n, tuple(t.shape)))
-    return t
-
-
 def mask_block_fwd(x_emb, v, W1, b1, W2, b2, W3, b3, gamma, beta, save=True):
     """One mask block in one launch: y = relu(LayerNorm((v * (relu(x_emb W1 + b1) W2 + b2)) W3 + b3)) -> (y [B,O],
     saved) with saved = (h [B,R P], m [B,P], xhat [B,O], rstd [B]) for the backward, or None (``save=False``: inference,
@@ -1192,17 +1171,10 @@ def mask_block_fwd(x_emb, v, W1, b1, W2, b2, W3, b3, gamma, beta, save=True):
     for t, n, name in ((b1, R * P, "b1"), (b2, P, "b2"), (b3, O, "b3"), (gamma, O, "gamma"), (beta, O, "beta")):
         _vec(t, n, name)
     dev = x_emb.device
-    y = torch.empty((B, O), dtype=torch.float32, device=dev)
-    saved = None
-    if save:
-        saved = (torch.empty((B, R * P), dtype=torch.float32, device=dev),
-                 torch.empty((B, P), dtype=torch.float32, device=dev),
-                 torch.empty((B, O), dtype=torch.float32, device=dev),
-                 torch.empty((B,), dtype=torch.float32, device=dev))
-    h, m, xhat, rstd = saved if save else (None,) * 4
-    check(lib.rec_mask_block_fwd_f32(_ptr(x_emb), _ptr(v), _ptr(W1), _ptr(b1), _ptr(W2), _ptr(b2), _ptr(W3), _ptr(b3),
-                                     _ptr(gamma), _ptr(beta), B, D, P, O, R, _ptr(y), _ptr(h), _ptr(m), _ptr(xhat),
-                                     _ptr(rstd), _stream()), "rec_mask_block_fwd_f32")
+    y = _new((B, O), dev)
+    saved = (_new((B, R * P), dev), _new((B, P), dev), _new((B, O), dev), _new((B,), dev)) if save else None
+    _call("rec_mask_block_fwd_f32", _ptr(x_emb), _ptr(v), _ptr(W1), _ptr(b1), _ptr(W2), _ptr(b2), _ptr(W3), _ptr(b3),
+          _ptr(gamma), _ptr(beta), B, D, P, O, R, _ptr(y), *_ptrs(saved or (None,) * 4))
     return y, saved
 
 
@@ -1212,28 +1184,22 @@ def mask_block_bwd(x_emb, v, W1, W2, W3, gamma, y, saved, dy, dx_emb=None, accum
     B, D, P, O, R = _mask_block_args(x_emb, v, W1, W2, W3)
     h, m, xhat, rstd = saved
     _vec(gamma, O, "gamma")
-    for t, shp, name in ((y, (B, O), "y"), (dy, (B, O), "dy"), (h, (B, R * P), "h"), (m, (B, P), "m"),
-                         (xhat, (B, O), "xhat"), (rstd, (B,), "rstd")):
-        if tuple(_f32(t, name).shape) != shp:
-            raise ValueError("%s must be %s, got %s" % (name, shp, tuple(t.shape)))
+    _expect_all([(y, (B, O), "y"), (dy, (B, O), "dy"), (h, (B, R * P), "h"), (m, (B, P), "m"), (xhat, (B, O), "xhat"),
+                 (rstd, (B,), "rstd")])
     dev = x_emb.device
     if dx_emb is None:
         if accumulate:
             raise ValueError("accumulate needs the dx_emb to add to")
-        dx_emb = torch.zeros((B, D), dtype=torch.float32, device=dev) if B == 0 else \
-            torch.empty((B, D), dtype=torch.float32, device=dev)
-    elif tuple(_f32(dx_emb, "dx_emb").shape) != (B, D):
-        raise ValueError("dx_emb must be [B, %d], got %s" % (D, tuple(dx_emb.shape)))
-    dv = torch.empty((B, P), dtype=torch.float32, device=dev)
+        dx_emb = _new((B, D), dev, B)
+    else:
+        _expect(dx_emb, (B, D), "dx_emb", "[B,D]")
+    dv = _new((B, P), dev)
     grads = tuple(torch.zeros(shp, dtype=torch.float32, device=dev)
                   for shp in ((D, R * P), (R * P,), (R * P, P), (P,), (P, O), (O,), (O,), (O,)))
     if B > 0:
-        nbytes = lib.rec_masknet_block_workspace_bytes(B, D, P, O, R)
-        ws = _workspace(nbytes, "rec_masknet_block_workspace_bytes", dev, torch.float32)
-        check(lib.rec_mask_block_bwd_f32(_ptr(x_emb), _ptr(v), _ptr(W1), _ptr(W2), _ptr(W3), _ptr(gamma), _ptr(y),
-                                         _ptr(h), _ptr(m), _ptr(xhat), _ptr(rstd), _ptr(dy), B, D, P, O, R, _ptr(dv),
-                                         _ptr(dx_emb), int(bool(accumulate)), *[_ptr(g) for g in grads], _ptr(ws),
-                                         nbytes, _stream()), "rec_mask_block_bwd_f32")
+        _call_ws("rec_masknet_block_workspace_bytes", (B, D, P, O, R), "rec_mask_block_bwd_f32", dev, _ptr(x_emb),
+                 _ptr(v), _ptr(W1), _ptr(W2), _ptr(W3), _ptr(gamma), _ptr(y), _ptr(h), _ptr(m), _ptr(xhat), _ptr(rstd),
+                 _ptr(dy), B, D, P, O, R, _ptr(dv), _ptr(dx_emb), int(bool(accumulate)), *_ptrs(grads))
     return dv, dx_emb, grads
 
 
@@ -1251,41 +1217,25 @@ def contextnet_check_shape(F, E, R=3, Fk=0):
             % (MASKNET_MAX_F, MASKNET_MAX_E, MASKNET_MAX_D, MASKNET_MAX_R, F, E, F * E, R))
 
 
-def _contextnet_values(values, B, F):
-    Fk = 0 if values is None else (values.shape[1] if values.dim() == 2 else -1)
-    if Fk > 0 and tuple(_f32(values, "values").shape) != (B, Fk):
-        raise ValueError("values must be [B, %d], got %s" % (Fk, tuple(values.shape)))
-    return Fk
-
-
 def emb_contextnet_in_fwd(table, X, values, oob=None):
     """Lookup with the rows of the last ``values.shape[1]`` columns of X (the keys of continuous features) scaled by
     ``values``, one launch -> x [B, F E]."""
-    _table(table, "table"); _i64(X, "X")
-    if X.dim() != 2:
-        raise ValueError("X must be [B, fields]")
-    V, E = table.shape
-    B, F = X.shape
-    Fk = _contextnet_values(values, B, F)
+    V, E = _table(table, "table").shape
+    B, F, E, Fk = _keyed_head(X, values, E)
     contextnet_check_shape(F, E, 1, Fk)
-    x = torch.empty((B, F * E), dtype=torch.float32, device=table.device)
-    check(lib.rec_emb_contextnet_in_fwd_f32(_ptr(table), V, E, table.stride(0), _ptr(X), _ptr(values), B, F, Fk, _ptr(x),
-                                            _ptr(oob), _stream()), "rec_emb_contextnet_in_fwd_f32")
+    x = _new((B, F * E), table.device)
+    _call("rec_emb_contextnet_in_fwd_f32", _ptr(table), V, E, table.stride(0), _ptr(X), _ptr(values), B, F, Fk, _ptr(x),
+          _ptr(oob))
     return x
 
 
 def emb_contextnet_in_bwd(dx, values, F):
     """dx [B, F E] = dLoss/dx -> vals [B*F, E], the IndexedSlices values in the order of X, the key fields' multiplied by
     their value."""
-    _f32(dx, "dx")
-    if dx.dim() != 2 or F < 1 or dx.shape[1] % F:
-        raise ValueError("dx must be [B, fields * embedding_dims] with fields=%d, got %s" % (F, tuple(dx.shape)))
-    B, E = dx.shape[0], dx.shape[1] // F
-    Fk = _contextnet_values(values, B, F)
+    B, F, E, Fk = _keyed_head(dx, values, F=F)
     contextnet_check_shape(F, E, 1, Fk)
-    vals = torch.empty((B * F, E), dtype=torch.float32, device=dx.device)
-    check(lib.rec_emb_contextnet_in_bwd_f32(_ptr(values), _ptr(dx), B, F, Fk, E, _ptr(vals), _stream()),
-          "rec_emb_contextnet_in_bwd_f32")
+    vals = _new((B * F, E), dx.device)
+    _call("rec_emb_contextnet_in_bwd_f32", _ptr(values), _ptr(dx), B, F, Fk, E, _ptr(vals))
     return vals
 
 
@@ -1318,13 +1268,11 @@ def contextnet_block_fwd(x, Wa, ba, Wb, bb, W1, W2, gamma, beta, save=True):
     for t, n, name in ((ba, R * D, "ba"), (bb, D, "bb"), (beta, D, "beta")):
         _vec(t, n, name)
     dev = x.device
-    new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
-    y = new(B, D)
-    saved = (new(B, R * D), new(B, D), new(B, D), new(B, F), new(B, D) if pw else None) if save else None
-    h, m, xhat, rstd, a = saved if save else (None,) * 5
-    check(lib.rec_contextnet_block_fwd_f32(_ptr(x), _ptr(Wa), _ptr(ba), _ptr(Wb), _ptr(bb), _ptr(W1), _ptr(W2),
-                                           _ptr(gamma), _ptr(beta), B, F, E, R, pw, _ptr(y), _ptr(h), _ptr(m), _ptr(xhat),
-                                           _ptr(rstd), _ptr(a), _stream()), "rec_contextnet_block_fwd_f32")
+    y = _new((B, D), dev)
+    saved = (_new((B, R * D), dev), _new((B, D), dev), _new((B, D), dev), _new((B, F), dev),
+             _new((B, D), dev) if pw else None) if save else None
+    _call("rec_contextnet_block_fwd_f32", _ptr(x), _ptr(Wa), _ptr(ba), _ptr(Wb), _ptr(bb), _ptr(W1), _ptr(W2),
+          _ptr(gamma), _ptr(beta), B, F, E, R, pw, _ptr(y), *_ptrs(saved or (None,) * 5))
     return y, saved
 
 
@@ -1333,25 +1281,17 @@ def contextnet_block_bwd(x, Wa, Wb, W1, W2, gamma, saved, dy):
     B, F, E, R, pw = _contextnet_block_args(x, Wa, Wb, W1, W2, gamma)
     D = F * E
     h, m, xhat, rstd, a = saved
-    for t, shp, name in ((dy, (B, D), "dy"), (h, (B, R * D), "h"), (m, (B, D), "m"), (xhat, (B, D), "xhat"),
-                         (rstd, (B, F), "rstd")) + (((a, (B, D), "a"),) if pw else ()):
-        if t is None or tuple(_f32(t, name).shape) != shp:
-            raise ValueError("%s must be %s, got %s" % (name, shp, None if t is None else tuple(t.shape)))
+    _expect_all([(dy, (B, D), "dy"), (h, (B, R * D), "h"), (m, (B, D), "m"), (xhat, (B, D), "xhat"),
+                 (rstd, (B, F), "rstd")] + ([(a, (B, D), "a")] if pw else []))
     dev = x.device
-    dx = torch.zeros((B, D), dtype=torch.float32, device=dev) if B == 0 else \
-        torch.empty((B, D), dtype=torch.float32, device=dev)
-    z = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)
-    dWa, dba, dWb, dbb, dW1, dW2, dg, db = (z(D, R * D), z(R * D), z(R * D, D), z(D), z(F, E, E),
-                                            z(F, E, E) if pw else None, z(F, E), z(F, E))
+    dx = _new((B, D), dev, B)
+    shapes = ((D, R * D), (R * D,), (R * D, D), (D,), (F, E, E), (F, E, E) if pw else None, (F, E), (F, E))
+    grads = tuple(None if s is None else torch.zeros(s, dtype=torch.float32, device=dev) for s in shapes)
     if B > 0:
-        nbytes = lib.rec_contextnet_block_workspace_bytes(B, F, E, R, pw)
-        ws = _workspace(nbytes, "rec_contextnet_block_workspace_bytes", dev, torch.float32)
-        check(lib.rec_contextnet_block_bwd_f32(_ptr(x), _ptr(Wa), _ptr(Wb), _ptr(W1), _ptr(W2), _ptr(gamma), _ptr(h),
-                                               _ptr(m), _ptr(xhat), _ptr(rstd), _ptr(a), _ptr(dy), B, F, E, R, pw,
-                                               _ptr(dx), _ptr(dWa), _ptr(dba), _ptr(dWb), _ptr(dbb), _ptr(dW1), _ptr(dW2),
-                                               _ptr(dg), _ptr(db), _ptr(ws), nbytes, _stream()),
-              "rec_contextnet_block_bwd_f32")
-    return dx, (dWa, dba, dWb, dbb, dW1, dW2, dg, db)
+        _call_ws("rec_contextnet_block_workspace_bytes", (B, F, E, R, pw), "rec_contextnet_block_bwd_f32", dev, _ptr(x),
+                 _ptr(Wa), _ptr(Wb), _ptr(W1), _ptr(W2), _ptr(gamma), _ptr(h), _ptr(m), _ptr(xhat), _ptr(rstd), _ptr(a),
+                 _ptr(dy), B, F, E, R, pw, _ptr(dx), *_ptrs(grads))
+    return dx, grads
 
 
 # ---- FiBiNet++: lookup x value + BatchNorm / per-field LayerNorm, and the SENet+ / bilinear+ block (csrc/fibinetplus.hip).
@@ -1379,16 +1319,13 @@ def fibinetplus_mid(F, G, reduction_ratio):
     return max(1, 2 * G * F // reduction_ratio)
 
 
-def _fibinetplus_in_args(B, F, E, values, gamma_bn, gamma_ln):
-    Fk = _contextnet_values(values, B, F)
-    if not 0 <= Fk <= F:
-        raise ValueError("values must be [B, continuous fields <= %d], got %s" % (F, tuple(values.shape)))
+def _fibinetplus_in_gammas(F, E, Fk, gamma_bn, gamma_ln):
+    """what both directions of the input stage check after the keyed head: the limits and the two scales"""
     fibinetplus_check_shape(F, E, Fk=Fk, min_fields=1)
     if Fk < F:
         _vec(gamma_bn, E, "gamma_bn")
-    if Fk > 0 and tuple(_f32(gamma_ln, "gamma_ln").shape) != (Fk, E):
-        raise ValueError("gamma_ln must be [%d, %d], got %s" % (Fk, E, tuple(gamma_ln.shape)))
-    return Fk
+    if Fk > 0:
+        _expect(gamma_ln, (Fk, E), "gamma_ln", "[Fk,E]")
 
 
 def emb_fibinetplus_in_fwd(table, X, values, gamma_bn, beta_bn, gamma_ln, beta_ln, moving_mean, moving_var, training,
@@ -1396,59 +1333,42 @@ def emb_fibinetplus_in_fwd(table, X, values, gamma_bn, beta_bn, gamma_ln, beta_l
     """Lookup, x value on the last ``values.shape[1]`` columns of X, ONE BatchNorm over the categorical rows (training:
     batch statistics and the moving averages updated on the device; else the moving statistics) and a LayerNorm per key
     field -> (x [B, F E], saved) with saved = (xhat [B, F E], rstd_bn [E], rstd_ln [B, Fk]) or None (``save=False``)."""
-    _table(table, "table"); _i64(X, "X")
-    if X.dim() != 2:
-        raise ValueError("X must be [B, fields]")
-    V, E = table.shape
-    B, F = X.shape
-    Fk = _fibinetplus_in_args(B, F, E, values, gamma_bn, gamma_ln)
+    V, E = _table(table, "table").shape
+    B, F, E, Fk = _keyed_head(X, values, E)
+    _fibinetplus_in_gammas(F, E, Fk, gamma_bn, gamma_ln)
     if Fk < F:
         for t, name in ((beta_bn, "beta_bn"), (moving_mean, "moving_mean"), (moving_var, "moving_var")):
             _vec(t, E, name)
     if Fk > 0:
         _vec(beta_ln, Fk * E, "beta_ln")
     dev = table.device
-    new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
-    x = new(B, F * E)
-    saved = (new(B, F * E), new(E), new(B, max(Fk, 1))) if save else None
-    xhat, rstd_bn, rstd_ln = saved if save else (None,) * 3
+    x = _new((B, F * E), dev)
+    saved = (_new((B, F * E), dev), _new((E,), dev), _new((B, max(Fk, 1)), dev)) if save else None
     if B > 0:
-        nbytes = lib.rec_emb_fibinetplus_in_workspace_bytes(B, F, Fk, E)
-        ws = _workspace(nbytes, "rec_emb_fibinetplus_in_workspace_bytes", dev, torch.float32)
-        check(lib.rec_emb_fibinetplus_in_fwd_f32(_ptr(table), V, E, table.stride(0), _ptr(X), _ptr(values),
-                                                 _ptr(gamma_bn), _ptr(beta_bn), _ptr(gamma_ln), _ptr(beta_ln), B, F, Fk,
-                                                 int(bool(training)), _ptr(moving_mean), _ptr(moving_var), _ptr(x),
-                                                 _ptr(xhat), _ptr(rstd_bn), _ptr(rstd_ln), _ptr(oob), _ptr(ws), nbytes,
-                                                 _stream()), "rec_emb_fibinetplus_in_fwd_f32")
+        _call_ws("rec_emb_fibinetplus_in_workspace_bytes", (B, F, Fk, E), "rec_emb_fibinetplus_in_fwd_f32", dev,
+                 _ptr(table), V, E, table.stride(0), _ptr(X), _ptr(values), _ptr(gamma_bn), _ptr(beta_bn), _ptr(gamma_ln),
+                 _ptr(beta_ln), B, F, Fk, int(bool(training)), _ptr(moving_mean), _ptr(moving_var), _ptr(x),
+                 *_ptrs(saved or (None,) * 3), _ptr(oob))
     return x, saved
 
 
 def emb_fibinetplus_in_bwd(dx, values, saved, gamma_bn, gamma_ln, F, training):
     """dx [B, F E] = dLoss/dx -> (vals [B*F, E], the IndexedSlices values in the order of X with the key fields'
     multiplied by their value, dgamma_bn [E], dbeta_bn [E], dgamma_ln [Fk, E], dbeta_ln [Fk, E])."""
-    _f32(dx, "dx")
-    if dx.dim() != 2 or F < 1 or dx.shape[1] % F:
-        raise ValueError("dx must be [B, fields * embedding_dims] with fields=%d, got %s" % (F, tuple(dx.shape)))
-    B, E = dx.shape[0], dx.shape[1] // F
-    Fk = _fibinetplus_in_args(B, F, E, values, gamma_bn, gamma_ln)
+    B, F, E, Fk = _keyed_head(dx, values, F=F)
+    _fibinetplus_in_gammas(F, E, Fk, gamma_bn, gamma_ln)
     xhat, rstd_bn, rstd_ln = saved
-    if tuple(_f32(xhat, "xhat").shape) != (B, F * E):
-        raise ValueError("xhat must be %s, got %s" % ((B, F * E), tuple(xhat.shape)))
+    _expect(xhat, (B, F * E), "xhat", "[B, F E]")
     _vec(rstd_bn, E, "rstd_bn"); _vec(rstd_ln, B * max(Fk, 1), "rstd_ln")
     dev = dx.device
-    z = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)
-    # every output the call writes in full starts uninitialised; what it leaves alone (an empty batch, no field of a
-    # kind) is zeros
-    e = lambda on, *s: torch.empty(s, dtype=torch.float32, device=dev) if on and B > 0 else z(*s)
-    vals = e(True, B * F, E)
-    dg_bn, db_bn, dg_ln, db_ln = e(Fk < F, E), e(Fk < F, E), e(Fk > 0, Fk, E), e(Fk > 0, Fk, E)
+    # the gradients of a kind of field the batch does not have are left alone by the call: zeros, as for an empty batch
+    Bc, Bk = (B if Fk < F else 0), (B if Fk > 0 else 0)
+    vals = _new((B * F, E), dev, B)
+    dg_bn, db_bn, dg_ln, db_ln = _new((E,), dev, Bc), _new((E,), dev, Bc), _new((Fk, E), dev, Bk), _new((Fk, E), dev, Bk)
     if B > 0:
-        nbytes = lib.rec_emb_fibinetplus_in_workspace_bytes(B, F, Fk, E)
-        ws = _workspace(nbytes, "rec_emb_fibinetplus_in_workspace_bytes", dev, torch.float32)
-        check(lib.rec_emb_fibinetplus_in_bwd_f32(_ptr(dx), _ptr(values), _ptr(xhat), _ptr(rstd_bn), _ptr(rstd_ln),
-                                                 _ptr(gamma_bn), _ptr(gamma_ln), B, F, Fk, E, int(bool(training)),
-                                                 _ptr(vals), _ptr(dg_bn), _ptr(db_bn), _ptr(dg_ln), _ptr(db_ln), _ptr(ws),
-                                                 nbytes, _stream()), "rec_emb_fibinetplus_in_bwd_f32")
+        _call_ws("rec_emb_fibinetplus_in_workspace_bytes", (B, F, Fk, E), "rec_emb_fibinetplus_in_bwd_f32", dev,
+                 _ptr(dx), _ptr(values), _ptr(xhat), _ptr(rstd_bn), _ptr(rstd_ln), _ptr(gamma_bn), _ptr(gamma_ln), B, F,
+                 Fk, E, int(bool(training)), _ptr(vals), _ptr(dg_bn), _ptr(db_bn), _ptr(dg_ln), _ptr(db_ln))
     return vals, dg_bn, db_bn, dg_ln, db_ln
 
 
@@ -1486,14 +1406,10 @@ def fibinetplus_block_fwd(x, W, Wr, br, gq, bq, S0, b0, g0, be0, S1, b1, g1, be1
                        (be0, mid, "beta0"), (b1, D, "b1"), (g1, D, "gamma1"), (be1, D, "beta1")):
         _vec(t, n, name)
     dev = x.device
-    new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
-    out = new(B, O + D)
-    saved = (new(B, P), new(B, O), new(B, 2 * G * F), new(B, mid), new(B, mid), new(B, D), new(B, 3)) if save else None
-    sv = saved if save else (None,) * 7
-    check(lib.rec_fibinetplus_block_fwd_f32(_ptr(x), _ptr(W), _ptr(Wr), _ptr(br), _ptr(gq), _ptr(bq), _ptr(S0), _ptr(b0),
-                                            _ptr(g0), _ptr(be0), _ptr(S1), _ptr(b1), _ptr(g1), _ptr(be1), B, F, E, G, mid,
-                                            O, tc, _ptr(out), *[_ptr(t) for t in sv], _stream()),
-          "rec_fibinetplus_block_fwd_f32")
+    out = _new((B, O + D), dev)
+    saved = tuple(_new((B, w), dev) for w in (P, O, 2 * G * F, mid, mid, D, 3)) if save else None
+    _call("rec_fibinetplus_block_fwd_f32", *_ptrs((x, W, Wr, br, gq, bq, S0, b0, g0, be0, S1, b1, g1, be1)), B, F, E, G,
+          mid, O, tc, _ptr(out), *_ptrs(saved or (None,) * 7))
     return out, saved
 
 
@@ -1503,22 +1419,15 @@ def fibinetplus_block_bwd(x, W, Wr, gq, S0, g0, be0, S1, g1, be1, G, type_code, 
     D, P = F * E, F * (F - 1) // 2
     shapes = ((B, P), (B, O), (B, 2 * G * F), (B, mid), (B, mid), (B, D), (B, 3))
     names = ("p", "xhat_q", "s", "xhat0", "h", "xhat1", "rstd")
-    for t, shp, name in tuple(zip(saved, shapes, names)) + ((dout, (B, O + D), "dout"),):
-        if t is None or tuple(_f32(t, name).shape) != shp:
-            raise ValueError("%s must be %s, got %s" % (name, shp, None if t is None else tuple(t.shape)))
+    _expect_all(list(zip(saved, shapes, names)) + [(dout, (B, O + D), "dout")])
     dev = x.device
-    # the call writes every output in full; an empty batch launches nothing and leaves zeros
-    z = lambda *s: (torch.zeros if B == 0 else torch.empty)(s, dtype=torch.float32, device=dev)
-    dx = z(B, D)
-    grads = (z(*W.shape), z(P, O), z(O), z(O), z(O), z(2 * G * F, mid), z(mid), z(mid), z(mid), z(mid, D), z(D), z(D),
-             z(D))
+    dx = _new((B, D), dev, B)
+    grads = tuple(_new(s, dev, B) for s in (tuple(W.shape), (P, O), (O,), (O,), (O,), (2 * G * F, mid), (mid,), (mid,),
+                                            (mid,), (mid, D), (D,), (D,), (D,)))
     if B > 0:
-        nbytes = lib.rec_fibinetplus_block_workspace_bytes(B, F, E, G, mid, O, tc)
-        ws = _workspace(nbytes, "rec_fibinetplus_block_workspace_bytes", dev, torch.float32)
-        check(lib.rec_fibinetplus_block_bwd_f32(_ptr(x), _ptr(W), _ptr(Wr), _ptr(gq), _ptr(S0), _ptr(g0), _ptr(be0),
-                                                _ptr(S1), _ptr(g1), _ptr(be1), *[_ptr(t) for t in saved], _ptr(dout), B,
-                                                F, E, G, mid, O, tc, _ptr(dx), *[_ptr(t) for t in grads], _ptr(ws),
-                                                nbytes, _stream()), "rec_fibinetplus_block_bwd_f32")
+        _call_ws("rec_fibinetplus_block_workspace_bytes", (B, F, E, G, mid, O, tc), "rec_fibinetplus_block_bwd_f32", dev,
+                 *_ptrs((x, W, Wr, gq, S0, g0, be0, S1, g1, be1)), *_ptrs(saved), _ptr(dout), B, F, E, G, mid, O, tc,
+                 _ptr(dx), *_ptrs(grads))
     return dx, grads
 
 
@@ -1578,13 +1487,10 @@ def mmoe_fwd(x, weights, gate_softmax_passes=1, ctcvr=False, save=True):
     ``weights``: W1, b1, We2, be2, Wg2, bg2, Wt1, bt1, Wt2, bt2, Wt3, bt3 as include/mi355rec.h packs them."""
     B, D, n, T, H1, O, H2, O2 = _mmoe_args(x, weights, gate_softmax_passes, ctcvr)
     dev = x.device
-    new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
-    out = new(B, T)
-    saved = (new(B, (n + T) * H1), new(B, n * O), new(B, T * n), new(B, T * n), new(B, T * H2), new(B, T * O2),
-             new(B, T)) if save else None
-    check(lib.rec_mmoe_fwd_f32(_ptr(x), *[_ptr(t) for t in weights], B, D, n, T, H1, O, H2, O2, int(gate_softmax_passes),
-                               int(bool(ctcvr)), _ptr(out), *[_ptr(t) for t in (saved or (None,) * 7)], _stream()),
-          "rec_mmoe_fwd_f32")
+    out = _new((B, T), dev)
+    saved = tuple(_new((B, w), dev) for w in ((n + T) * H1, n * O, T * n, T * n, T * H2, T * O2, T)) if save else None
+    _call("rec_mmoe_fwd_f32", _ptr(x), *_ptrs(weights), B, D, n, T, H1, O, H2, O2, int(gate_softmax_passes),
+          int(bool(ctcvr)), _ptr(out), *_ptrs(saved or (None,) * 7))
     return out, saved
 
 
@@ -1592,21 +1498,15 @@ def mmoe_bwd(x, weights, saved, dout, gate_softmax_passes=1, ctcvr=False):
     """-> (dx [B, D], grads) with grads the gradient of every packed weight, in the order of ``weights``."""
     B, D, n, T, H1, O, H2, O2 = _mmoe_args(x, weights, gate_softmax_passes, ctcvr)
     shapes = ((B, (n + T) * H1), (B, n * O), (B, T * n), (B, T * n), (B, T * H2), (B, T * O2), (B, T))
-    for t, shp, name in zip(tuple(saved) + (dout,), shapes + ((B, T),), ("h", "e", "z", "g", "a1", "a2", "p", "dout")):
-        if t is None or tuple(_f32(t, name).shape) != shp:
-            raise ValueError("%s must be %s, got %s" % (name, shp, None if t is None else tuple(t.shape)))
+    _expect_all(zip(tuple(saved) + (dout,), shapes + ((B, T),), ("h", "e", "z", "g", "a1", "a2", "p", "dout")))
     dev = x.device
-    dx = torch.zeros((B, D), dtype=torch.float32, device=dev) if B == 0 else \
-        torch.empty((B, D), dtype=torch.float32, device=dev)
-    grads = [torch.zeros_like(t) if B == 0 else torch.empty_like(t) for t in weights]   # written in full when B > 0
+    dx = _new((B, D), dev, B)
+    grads = [_new_like(t, B) for t in weights]
     if B > 0:
-        nbytes = lib.rec_mmoe_workspace_bytes(B, D, n, T, H1, O, H2, O2)
-        ws = _workspace(nbytes, "rec_mmoe_workspace_bytes", dev, torch.float32)
         W1, _, We2, _, Wg2, _, Wt1, _, Wt2, _, Wt3, _ = weights
-        check(lib.rec_mmoe_bwd_f32(_ptr(x), *[_ptr(t) for t in (W1, We2, Wg2, Wt1, Wt2, Wt3)],
-                                   *[_ptr(t) for t in saved], _ptr(dout), B, D, n, T, H1, O, H2, O2,
-                                   int(gate_softmax_passes), int(bool(ctcvr)), _ptr(dx), *[_ptr(g) for g in grads],
-                                   _ptr(ws), nbytes, _stream()), "rec_mmoe_bwd_f32")
+        _call_ws("rec_mmoe_workspace_bytes", (B, D, n, T, H1, O, H2, O2), "rec_mmoe_bwd_f32", dev, _ptr(x),
+                 *_ptrs((W1, We2, Wg2, Wt1, Wt2, Wt3)), *_ptrs(saved), _ptr(dout), B, D, n, T, H1, O, H2, O2,
+                 int(gate_softmax_passes), int(bool(ctcvr)), _ptr(dx), *_ptrs(grads))
     return dx, grads
 
 
@@ -1680,13 +1580,11 @@ def ple_cgc_fwd(xin, weights, T, S, Sh, last=False, save=True):
     ne, Gout = T * S + Sh, T if last else T + 1
     GW = T * (S + Sh) + (0 if last else ne)
     dev = xin.device
-    new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
-    y = new(B, Gout, O)
-    out = new(B, T) if last else None
-    saved = (new(B, (ne + Gout) * H1), new(B, ne * O), new(B, Gout * Og), new(B, GW)) if save else None
-    check(lib.rec_ple_cgc_fwd_f32(_ptr(xin), *[_ptr(t) for t in weights], B, Din, Gin, T, S, Sh, H1, O, Og, last,
-                                  _ptr(y), _ptr(out), *[_ptr(t) for t in (saved or (None,) * 4)], _stream()),
-          "rec_ple_cgc_fwd_f32")
+    y = _new((B, Gout, O), dev)
+    out = _new((B, T), dev) if last else None
+    saved = tuple(_new((B, w), dev) for w in ((ne + Gout) * H1, ne * O, Gout * Og, GW)) if save else None
+    _call("rec_ple_cgc_fwd_f32", _ptr(xin), *_ptrs(weights), B, Din, Gin, T, S, Sh, H1, O, Og, last, _ptr(y), _ptr(out),
+          *_ptrs(saved or (None,) * 4))
     return y, out, saved
 
 
@@ -1708,21 +1606,15 @@ def ple_cgc_bwd(xin, weights, saved, y, out, dy, dout, T, S, Sh, last=False):
         raise ValueError("out and dout belong to the last level")
     if dy is not None or not last:
         named.append((dy, (B, Gout, O), "dy"))
-    for t, shp, name in named:
-        if t is None or tuple(_f32(t, name).shape) != shp:
-            raise ValueError("%s must be %s, got %s" % (name, shp, None if t is None else tuple(t.shape)))
+    _expect_all(named)
     dev = xin.device
-    mk = torch.zeros if B == 0 else torch.empty                      # written in full when B > 0
-    dxin = mk((B, Gin, Din), dtype=torch.float32, device=dev)
-    grads = [None if t is None else mk(tuple(t.shape), dtype=torch.float32, device=dev) for t in weights]
+    dxin = _new((B, Gin, Din), dev, B)
+    grads = [None if t is None else _new_like(t, B) for t in weights]
     if B > 0:
-        nbytes = lib.rec_ple_cgc_workspace_bytes(B, Din, Gin, T, S, Sh, H1, O, Og, last)
-        ws = _workspace(nbytes, "rec_ple_cgc_workspace_bytes", dev, torch.float32)
         W1, _, We2, _, Wg2, _, Wg3s, Wg3h, Wtw, _ = weights
-        check(lib.rec_ple_cgc_bwd_f32(_ptr(xin), *[_ptr(t) for t in (W1, We2, Wg2, Wg3s, Wg3h, Wtw)],
-                                      *[_ptr(t) for t in saved], _ptr(y), _ptr(out), _ptr(dy), _ptr(dout), B, Din, Gin,
-                                      T, S, Sh, H1, O, Og, last, _ptr(dxin), *[_ptr(g) for g in grads], _ptr(ws), nbytes,
-                                      _stream()), "rec_ple_cgc_bwd_f32")
+        _call_ws("rec_ple_cgc_workspace_bytes", (B, Din, Gin, T, S, Sh, H1, O, Og, last), "rec_ple_cgc_bwd_f32", dev,
+                 _ptr(xin), *_ptrs((W1, We2, Wg2, Wg3s, Wg3h, Wtw)), *_ptrs(saved), _ptr(y), _ptr(out), _ptr(dy),
+                 _ptr(dout), B, Din, Gin, T, S, Sh, H1, O, Og, last, _ptr(dxin), *_ptrs(grads))
     return dxin, grads
 
 
@@ -1778,32 +1670,6 @@ def _series_head(embed, series, what, *weights):
 
 def _items_head(embed, items, m, what, *more):
     return _caps_head(what, embed, (items, "items [B,Ns,C]", torch.int64), (m, "m [B,K,Dc]"), *more)
-
-
-def _expect(t, shape, name, label, dtype=torch.float32, optional=False):
-    """``t`` is a contiguous tensor of ``dtype`` and ``shape`` on the device (or, with ``optional``, None); ``label``
-    spells the shape in the error, which shows a one-dimensional shape as [n]"""
-    if t is None and optional:
-        return
-    if tuple(_req(t, dtype, name).shape) != shape:
-        raise ValueError("%s must be %s = %s, got %s"
-                         % (name, label, "[%d]" % shape if len(shape) == 1 else shape, tuple(t.shape)))
-
-
-def _new(shape, dev, B=1, dtype=torch.float32):
-    """an output the launch writes in full; zeros where the batch ``B`` is empty and nothing is launched"""
-    return (torch.zeros if B == 0 else torch.empty)(shape, dtype=dtype, device=dev)
-
-
-def _call(fn, *args):
-    check(getattr(lib, fn)(*args, _stream()), fn)
-
-
-def _call_ws(query, query_args, fn, dev, *args):
-    """``fn`` with the workspace that ``query`` asks for at ``query_args``"""
-    nbytes = getattr(lib, query)(*query_args)
-    ws = _workspace(nbytes, query, dev, torch.float32)
-    _call(fn, *args, _ptr(ws), nbytes)
 
 
 def mind_routing_lds_bytes(T, D, Dc, K, R):
@@ -2117,10 +1983,8 @@ def sine_interest_bwd(embed, series, pool, W1, W2, Wk1, Wk2, W3, W4, chosen, gou
     gkeys = _new((B, T, D), dev)
     grads = [_new(tuple(t.shape), dev, B) for t in (pool, W1, W2, Wk1, Wk2, W3, W4)]
     if B > 0:
-        nbytes = lib.rec_sine_scratch_bytes(B, T, E, Cn, L, K)
-        scratch = _workspace(nbytes, "rec_sine_scratch_bytes", dev, torch.float32)
-        _call("rec_sine_interest_bwd_f32", *args, _ptr(chosen), _ptr(gout), _ptr(gkeys), *[_ptr(g) for g in grads],
-              _ptr(scratch), nbytes)
+        _call_ws("rec_sine_scratch_bytes", (B, T, E, Cn, L, K), "rec_sine_interest_bwd_f32", dev, *args, _ptr(chosen),
+                 _ptr(gout), _ptr(gkeys), *_ptrs(grads))
     return (gkeys, *grads)
 
 
@@ -2242,8 +2106,7 @@ def can_bwd(feed, inds, iid, fid, coefs, order, act, g, padding_index=0, pooled=
     each order's induction lookup) from gout [order,B,T,Eo] or, with ``pooled``, gpool [B,Eo]; the forward is run again."""
     args, (B, T, E, P, Eo) = _can_args(feed, inds, iid, fid, coefs, order, act, padding_index)
     shape = (B, Eo) if pooled else (int(order), B, T, Eo)
-    if tuple(_f32(g, "g").shape) != shape:
-        raise ValueError("the upstream gradient must be %s, got %s" % (shape, tuple(g.shape)))
+    _expect(g, shape, "g", "the upstream gradient")
     gfeed, gind = _new((B, T, E), feed.device), _new((int(order), B, P), feed.device)
     if B > 0:
         _call("rec_can_bwd_f32", *args, None if pooled else _ptr(g), _ptr(g) if pooled else None, _ptr(gfeed), _ptr(gind))
