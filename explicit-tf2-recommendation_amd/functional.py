@@ -1112,3 +1112,30 @@ class CoAction(torch.autograd.Function):
             dinds = [_sparse_grad(plan, gind[o], P, (Vi, P), wide=True) if ctx.needs_input_grad[9 + o] else None
                      for o in range(order)]
         return (dfeed,) + (None,) * 8 + tuple(dinds)
+
+
+class FinalMLPBody(torch.autograd.Function):
+    """The FinalMLP body (8.DMR/CustomLayers.py:379-385, 406-442; csrc/finalmlp.hip): the shared rows xs [B, D], the rows
+    x1 / x2 of the two gates and ONE packed parameter buffer (ops.finalmlp_param_shapes) -> out [B, o].  ``moving`` is the
+    list of the 2 L moving means followed by the 2 L moving variances; in training they move in place on the device.
+    Forward: 2 L + 1 launches in training, one in evaluation; the gradient of the packed buffer comes back as one tensor
+    that autograd splits by the views the caller concatenated."""
+
+    @staticmethod
+    def forward(ctx, xs, x1, x2, params, moving, dims, training, eps, momentum):
+        xs, x1, x2, params = (t.contiguous() for t in (xs, x1, x2, params))
+        half = len(moving) // 2
+        save = training or any(ctx.needs_input_grad)
+        out, saved = ops.finalmlp_fwd(xs, x1, x2, params, moving[:half], moving[half:], dims, training, eps, momentum,
+                                      save=save)
+        if save:
+            ctx.save_for_backward(xs, x1, x2, params, out, *saved)
+        ctx.dims, ctx.training = dims, training
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        xs, x1, x2, params, out, *saved = ctx.saved_tensors
+        dxs, dx1, dx2, dparams = ops.finalmlp_bwd(xs, x1, x2, params, saved, out, dout.contiguous(), ctx.dims,
+                                                  ctx.training)
+        return dxs, dx1, dx2, dparams, None, None, None, None, None

@@ -48,6 +48,9 @@ libmi355rec.so (through functional.py / ops.py).  Reference classes and the line
   ComiRecDynamicRoutingLayer    6.MIND/CustomLayers.py:528-594  (takes the table and the ids, as the MIND extractor)
   ComiRecSelfAttentiveLayer     6.MIND/CustomLayers.py:597-665  (the same)
   ComiRecLayer                  6.MIND/CustomLayers.py:668-810  (negative_sample_type='manual')
+  FinalMLPLayer                 8.DMR/CustomLayers.py:319-387
+  FeatureSelectionLayer         8.DMR/CustomLayers.py:390-414
+  DualPartsInteractionLayer     8.DMR/CustomLayers.py:416-442
 
 Parameters are named after the TF checkpoint keys (``embed.embeddings``, ``w.embeddings``, ``bias``,
 ``MLP_layer1.kernel_0`` ...), so a TensorBundle checkpoint maps onto ``state_dict()`` by name.
@@ -1577,7 +1580,7 @@ def make_mlp_layer(units, activation="PReLU", normalization="layernorm", softmax
         seq.append(Dense(unit, input_dim=d))
         d = unit
         if normalization == "batchnorm":
-            raise NotImplementedError("normalization='batchnorm' is not on the hot path")
+            seq.append(BatchNormalization(input_dim=d))
         elif normalization == "layernorm":
             seq.append(LayerNormalization(d))
         if activation == "PReLU":
@@ -2542,3 +2545,175 @@ class CoActionUnit(Layer):
 
     def pooled(self, inputs):
         return self._run(inputs, True)[0]
+
+
+# ---------------------------------------------------------------------------------------------------
+# 8.DMR: FinalMLP
+# ---------------------------------------------------------------------------------------------------
+
+def _keras_name(name):
+    """Keras resolves 'ReLU' and 'relu' alike; the 8.DMR chapter spells the former.  'None' stays the chapter's "no such
+    layer"."""
+    return name.lower() if isinstance(name, str) and name.lower() in ops.DACT_CODE else name
+
+
+class FeatureSelectionLayer(Layer):
+    """8.DMR/CustomLayers.py:390-414.  ``forward([X_shared, X_item, X_user])``: gate 1 reads the ITEM ids through
+    ``fs1_embedding``, gate 2 the USER ids through ``fs2_embedding``; a gate is g = 2 sigmoid(Dense(hidden(rows))), with
+    ``hidden`` = make_mlp_layer(units[:-1], activation, norm) and units[-1] the width of X_shared -> (g1 (.) X_shared,
+    g2 (.) X_shared).  ``input_dims`` = (item fields, user fields) (extension: layers are built eagerly)."""
+
+    def __init__(self, fs1_feature_dims=160000, fs2_feature_dims=160000, fs1_emd_dim=16, fs2_emd_dim=16, fs1_units=None,
+                 fs2_units=None, fs1_activation="ReLU", fs2_activation="ReLU", fs1_norm="None", fs2_norm="None",
+                 input_dims=(5, 5)):
+        super().__init__()
+        fs1_units = [64, 160] if fs1_units is None else list(fs1_units)
+        fs2_units = [64, 160] if fs2_units is None else list(fs2_units)
+        self.fs1_embedding = Embedding(fs1_feature_dims, fs1_emd_dim)
+        self.fs2_embedding = Embedding(fs2_feature_dims, fs2_emd_dim)
+        d1, d2 = int(input_dims[0]) * int(fs1_emd_dim), int(input_dims[1]) * int(fs2_emd_dim)
+        a1, a2 = _keras_name(fs1_activation), _keras_name(fs2_activation)
+        self.mlp_gate1_hidden = make_mlp_layer(fs1_units[:-1], a1, fs1_norm, input_dim=d1)
+        self.mlp_gate2_hidden = make_mlp_layer(fs2_units[:-1], a2, fs2_norm, input_dim=d2)
+        self.mlp_gate1_output = make_mlp_layer(fs1_units[-1:], "sigmoid", fs1_norm, input_dim=(fs1_units[:-1] or [d1])[-1])
+        self.mlp_gate2_output = make_mlp_layer(fs2_units[-1:], "sigmoid", fs2_norm, input_dim=(fs2_units[:-1] or [d2])[-1])
+
+    def gate_rows(self, X_item, X_user, flag=None):
+        """the flattened rows the two gates read: ([B, Fi fs1_emd_dim], [B, Fu fs2_emd_dim])"""
+        return (self.fs1_embedding(X_item, flag).reshape(X_item.shape[0], -1),
+                self.fs2_embedding(X_user, flag).reshape(X_user.shape[0], -1))
+
+    def forward(self, inputs):
+        X_shared, X_item, X_user = inputs
+        flag = ops.new_flag(X_shared.device) if self.check_ids else None
+        x1, x2 = self.gate_rows(X_item, X_user, flag)
+        self._raise_if_oob(flag)
+        g1 = self.mlp_gate1_output(self.mlp_gate1_hidden(x1)) * 2
+        g2 = self.mlp_gate2_output(self.mlp_gate2_hidden(x2)) * 2
+        return g1 * X_shared, g2 * X_shared
+
+
+class DualPartsInteractionLayer(Layer):
+    """8.DMR/CustomLayers.py:416-442: out = m1 W_1 + c_1 + m2 W_2 + c_2 + sum over heads of m1_h^T W_12[h] m2_h, no
+    activation -> [B, output_dim].  ``W_12`` [num_heads, d1 / num_heads, d2 / num_heads, output_dim], glorot-uniform
+    with Keras' rank-4 fans.  ``input_dims`` = (d1, d2) builds it eagerly; otherwise the first call does."""
+
+    def __init__(self, num_heads=8, output_dim=1, input_dims=None):
+        super().__init__()
+        self.num_heads, self.output_dim = int(num_heads), int(output_dim)
+        self.built = False
+        if input_dims is not None:
+            self.build(*input_dims)
+
+    def build(self, dim1, dim2):
+        dim1, dim2, n = int(dim1), int(dim2), self.num_heads
+        if dim1 % n or dim2 % n:
+            raise ValueError("输入维度必须被num_heads整除")
+        self.head_dim1, self.head_dim2 = dim1 // n, dim2 // n
+        self.W_1 = Dense(self.output_dim, input_dim=dim1)
+        self.W_2 = Dense(self.output_dim, input_dim=dim2)
+        self.W_12 = torch.nn.Parameter(glorot_uniform((n, self.head_dim1, self.head_dim2, self.output_dim)))
+        self.built = True
+
+    def forward(self, inputs):
+        m1, m2 = inputs
+        if not self.built:
+            self.build(m1.shape[-1], m2.shape[-1])
+            self.to(m1.device)
+        n = self.num_heads
+        t = torch.einsum("bnx,nxyo->bnyo", m1.reshape(-1, n, self.head_dim1), self.W_12)
+        t = torch.einsum("bnyo,bny->bno", t, m2.reshape(-1, n, self.head_dim2)).sum(dim=1)
+        return self.W_1(m1) + self.W_2(m2) + t
+
+
+class FinalMLPLayer(Layer):
+    """8.DMR/CustomLayers.py:319-387: the flattened shared rows of the user and item ids (users first) are gated twice
+    (FeatureSelectionLayer: gate 1 from the item ids, gate 2 from the user ids), each gated copy runs through its own
+    Dense -> BatchNormalization -> activation stream, and DualPartsInteractionLayer joins the two -> {'output': [B,
+    output_dim]} after a sigmoid.  The constructor arguments and defaults are the reference's.
+
+    ``fused`` ('auto' | True | False; extension): the fused path runs everything behind the three lookups on the kernels
+    of csrc/finalmlp.hip (functional.FinalMLPBody).  It needs one ReLU hidden layer without a norm in both gates, ReLU +
+    'batchnorm' streams of the same depth 1..4 and sizes inside the kernel limits; 'auto' takes it where that holds, True
+    raises NotImplementedError where it does not.  The composed path strings the earlier entry points together (Dense,
+    BatchNormalization, Activation, torch for the head's einsum) and serves every argument combination."""
+
+    def __init__(self, user_features=["uid", "utag1", "utag2", "utag3", "utag4"],
+                 item_features=["iid", "itag1", "itag2", "itag3", "itag4"], feature_dims=160000, embedding_dims=16,
+                 fs1_feature_dims=160000, fs2_feature_dims=160000, fs1_emd_dim=16, fs2_emd_dim=16, fs1_hidden_units=[64],
+                 fs2_hidden_units=[64], fs1_activation="ReLU", fs2_activation="ReLU", fs1_norm="None", fs2_norm="None",
+                 mlp1_hidden_units=[64, 64, 64], mlp2_hidden_units=[64, 64, 64], mlp1_activation="ReLU",
+                 mlp2_activation="ReLU", mlp1_norm="batchnorm", mlp2_norm="batchnorm", num_heads=8, output_dim=1,
+                 fused="auto"):
+        super().__init__()
+        if fused not in ("auto", True, False):
+            raise ValueError("fused is 'auto', True or False, got %r" % (fused,))
+        self.user_features, self.item_features = list(user_features), list(item_features)
+        Fu, Fi = len(self.user_features), len(self.item_features)
+        D = (Fu + Fi) * int(embedding_dims)
+        w1, w2 = [int(w) for w in mlp1_hidden_units], [int(w) for w in mlp2_hidden_units]
+        if not w1 or not w2:
+            raise ValueError("mlp1_hidden_units and mlp2_hidden_units must not be empty")
+        if w1[-1] % int(num_heads) or w2[-1] % int(num_heads):
+            raise ValueError("输入维度必须被num_heads整除")
+        self.shared_embedding = Embedding(feature_dims, embedding_dims)
+        self.fs_layer = FeatureSelectionLayer(
+            fs1_feature_dims=fs1_feature_dims, fs2_feature_dims=fs2_feature_dims, fs1_emd_dim=fs1_emd_dim,
+            fs2_emd_dim=fs2_emd_dim, fs1_units=list(fs1_hidden_units) + [D], fs2_units=list(fs2_hidden_units) + [D],
+            fs1_activation=fs1_activation, fs2_activation=fs2_activation, fs1_norm=fs1_norm, fs2_norm=fs2_norm,
+            input_dims=(Fi, Fu))
+        self.mlp1 = make_mlp_layer(w1, _keras_name(mlp1_activation), mlp1_norm, input_dim=D)
+        self.mlp2 = make_mlp_layer(w2, _keras_name(mlp2_activation), mlp2_norm, input_dim=D)
+        self.interaction_layer = DualPartsInteractionLayer(num_heads, output_dim, input_dims=(w1[-1], w2[-1]))
+
+        why = None                                           # what keeps this configuration off the fused path
+        gates = [(list(fs1_hidden_units), fs1_activation, fs1_norm), (list(fs2_hidden_units), fs2_activation, fs2_norm)]
+        streams = [(mlp1_activation, mlp1_norm), (mlp2_activation, mlp2_norm)]
+        if any(len(u) != 1 or _keras_name(a) != "relu" or n != "None" for u, a, n in gates):
+            why = "the fused FinalMLP path takes gates with exactly one hidden layer, ReLU and norm 'None'"
+        elif any(_keras_name(a) != "relu" or n != "batchnorm" for a, n in streams) or len(w1) != len(w2):
+            why = "the fused FinalMLP path takes ReLU + 'batchnorm' streams of the same depth"
+        else:
+            self._dims = (int(fs1_hidden_units[0]), int(fs2_hidden_units[0]), w1, w2, int(num_heads), int(output_dim))
+            try:
+                ops.finalmlp_check_shape(D, Fi * int(fs1_emd_dim), Fu * int(fs2_emd_dim), *self._dims)
+            except NotImplementedError as e:
+                why = str(e)
+        if fused is True and why is not None:
+            raise NotImplementedError(why)
+        self.fused = why is None and fused is not False
+
+    def _streams(self):
+        """[(Dense, BatchNormalization)] of stream 1, then of stream 2 (fused configurations)"""
+        return [(m.layers[i], m.layers[i + 1]) for m in (self.mlp1, self.mlp2) for i in range(0, len(m.layers), 3)]
+
+    def packed_params(self):
+        """The sub-layers' parameters laid end to end in the order of include/mi355rec.h (one concatenation per call;
+        gradients flow back through its views)."""
+        fs, il = self.fs_layer, self.interaction_layer
+        ts = []
+        for hid, outp in ((fs.mlp_gate1_hidden, fs.mlp_gate1_output), (fs.mlp_gate2_hidden, fs.mlp_gate2_output)):
+            ts += [hid.layers[0].kernel, hid.layers[0].bias, outp.layers[0].kernel, outp.layers[0].bias]
+        for dense, bn in self._streams():
+            ts += [dense.kernel, dense.bias, bn.gamma, bn.beta]
+        ts += [il.W_1.kernel, il.W_1.bias, il.W_2.kernel, il.W_2.bias, il.W_12]
+        return torch.cat([t.reshape(-1) for t in ts])
+
+    def forward(self, inputs):
+        X_user = assemble_index(inputs, self.user_features)
+        X_item = assemble_index(inputs, self.item_features)
+        X_shared = torch.cat([X_user, X_item], dim=1)
+        flag = ops.new_flag(X_shared.device) if self.check_ids else None
+        xs = self.shared_embedding(X_shared, flag).reshape(X_shared.shape[0], -1)
+        if self.fused:
+            x1, x2 = self.fs_layer.gate_rows(X_item, X_user, flag)
+            self._raise_if_oob(flag)
+            bns = [bn for _, bn in self._streams()]
+            moving = [bn.moving_mean for bn in bns] + [bn.moving_variance for bn in bns]
+            out = Fn.FinalMLPBody.apply(xs, x1, x2, self.packed_params(), moving, self._dims, self.training,
+                                        bns[0].epsilon, bns[0].momentum)
+            return {"output": out}
+        self._raise_if_oob(flag)
+        part1, part2 = self.fs_layer([xs, X_item, X_user])
+        out = self.interaction_layer((self.mlp1(part1), self.mlp2(part2)))
+        return {"output": Fn.FeatAct.apply(out.contiguous(), ops.DACT_SIGMOID, None, None, None)}

@@ -221,6 +221,18 @@ class ModelManager:
             self.layer = CL.FiBiNetPlusLayer(
                 categorical_features=self.feature_names, continuous_features=self.continuous_features,
                 feature_dims=self.feature_dims, embedding_dims=self.embedding_dims, **p)
+        elif layer_name == "FinalMLP":
+            # 8.DMR/ModelManager.py offers no FinalMLPLayer, so this name is ours; model_params carry user_features /
+            # item_features (default: the manager's feature names split in half, users first) and the layer's other
+            # arguments.  One sigmoid output, BCE: the plain train loop.
+            p = dict(model_params)
+            half = len(self.feature_names) // 2
+            p.setdefault("user_features", list(self.feature_names[:half]))
+            p.setdefault("item_features", list(self.feature_names[half:]))
+            for k in ("feature_dims", "fs1_feature_dims", "fs2_feature_dims"):
+                p.setdefault(k, self.feature_dims)
+            p.setdefault("embedding_dims", self.embedding_dims)
+            self.layer = CL.FinalMLPLayer(**p)
         elif layer_name in ("mmoe_layer", "esmm_layer"):   # 4.MMOE/ModelManager.py:68-73
             cls = CL.MMOELayer if layer_name == "mmoe_layer" else CL.ESMMLayer
             self.layer = cls(categorical_features=self.feature_names, continuous_features=self.continuous_features,

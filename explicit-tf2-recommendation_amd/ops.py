@@ -2111,3 +2111,104 @@ def can_bwd(feed, inds, iid, fid, coefs, order, act, g, padding_index=0, pooled=
     if B > 0:
         _call("rec_can_bwd_f32", *args, None if pooled else _ptr(g), _ptr(g) if pooled else None, _ptr(gfeed), _ptr(gind))
     return gfeed, gind
+
+
+# ---- FinalMLP: the two gates, the gating, both BatchNorm-MLP streams and the bilinear head over ONE packed parameter
+# buffer (csrc/finalmlp.hip).  The limits are MaskNet's.
+def finalmlp_check_shape(D, D1, D2, Hg1, Hg2, widths1, widths2, n, o):
+    """ValueError for sizes that describe no FinalMLP body, NotImplementedError naming the limit for shapes the kernels do
+    not cover (the ABI would return -2): shared width D, gate input widths D1 / D2 and hidden widths Hg1 / Hg2, the
+    stream widths, n heads, o outputs."""
+    widths1, widths2 = [int(w) for w in widths1], [int(w) for w in widths2]
+    if len(widths1) != len(widths2) or not widths1 or min([D, D1, D2, Hg1, Hg2, n, o] + widths1 + widths2) < 1:
+        raise ValueError("a FinalMLP body has positive sizes and two streams of the same depth >= 1, got D=%d, D1=%d, "
+                         "D2=%d, Hg1=%d, Hg2=%d, mlp1=%r, mlp2=%r, num_heads=%d, output_dim=%d"
+                         % (D, D1, D2, Hg1, Hg2, widths1, widths2, n, o))
+    if widths1[-1] % n or widths2[-1] % n:
+        raise ValueError("num_heads=%d must divide the last width of both streams, got %d and %d"
+                         % (n, widths1[-1], widths2[-1]))
+    if (max(D, D1, D2) > MASKNET_MAX_D or max([Hg1, Hg2] + widths1 + widths2) > MASKNET_MAX_O
+            or len(widths1) > MASKNET_MAX_R or o > MASKNET_MAX_R or widths2[-1] // n * o > MASKNET_MAX_O):
+        raise NotImplementedError(
+            "FinalMLP kernels cover fields * embedding_dims and both gate inputs <= %d, gate hidden and stream widths <= "
+            "%d, 1..%d stream layers, output_dim <= %d and (mlp2 width / num_heads) * output_dim <= %d; got D=%d, D1=%d, "
+            "D2=%d, Hg1=%d, Hg2=%d, mlp1=%r, mlp2=%r, num_heads=%d, output_dim=%d"
+            % (MASKNET_MAX_D, MASKNET_MAX_O, MASKNET_MAX_R, MASKNET_MAX_R, MASKNET_MAX_O, D, D1, D2, Hg1, Hg2, widths1,
+               widths2, n, o))
+
+
+def finalmlp_param_shapes(D, D1, D2, Hg1, Hg2, widths1, widths2, n, o):
+    """[(name, shape)] of the packed parameters, in the order include/mi355rec.h lays them end to end"""
+    out = []
+    for s, (Dx, Hg) in enumerate(((D1, Hg1), (D2, Hg2)), 1):
+        out += [("Wh_%d" % s, (Dx, Hg)), ("bh_%d" % s, (Hg,)), ("Wo_%d" % s, (Hg, D)), ("bo_%d" % s, (D,))]
+    for s, widths in enumerate((widths1, widths2), 1):
+        d = D
+        for l, w in enumerate(widths):
+            out += [("W_%d_%d" % (s, l), (d, w))] + [("%s_%d_%d" % (k, s, l), (w,)) for k in ("b", "gamma", "beta")]
+            d = w
+    d1, d2 = widths1[-1], widths2[-1]
+    return out + [("W_1", (d1, o)), ("c_1", (o,)), ("W_2", (d2, o)), ("c_2", (o,)), ("W_12", (n, d1 // n, d2 // n, o))]
+
+
+def _finalmlp_args(xs, x1, x2, params, dims):
+    Hg1, Hg2, widths1, widths2, n, o = dims
+    for t, name in ((xs, "xs"), (x1, "x1"), (x2, "x2")):
+        if _f32(t, name).dim() != 2 or t.shape[0] != xs.shape[0]:
+            raise ValueError("a FinalMLP body takes xs [B,D], x1 [B,D1], x2 [B,D2]; got %s"
+                             % ", ".join(str(tuple(t.shape)) for t in (xs, x1, x2)))
+    (B, D), D1, D2 = xs.shape, x1.shape[1], x2.shape[1]
+    finalmlp_check_shape(D, D1, D2, Hg1, Hg2, widths1, widths2, n, o)
+    shapes = finalmlp_param_shapes(D, D1, D2, Hg1, Hg2, widths1, widths2, n, o)
+    total = 0
+    for _, shape in shapes:
+        cnt = 1
+        for v in shape:
+            cnt *= v
+        total += cnt
+    _expect(params, (total,), "params", "the packed parameters")
+    sizes = (B, D, D1, D2, int(Hg1), int(Hg2), len(widths1), _ints(widths1), _ints(widths2), int(n), int(o))
+    return sizes, sum(widths1) + sum(widths2)
+
+
+def finalmlp_fwd(xs, x1, x2, params, moving_mean, moving_var, dims, training, eps=1e-3, momentum=0.99, save=True):
+    """The FinalMLP body: xs [B,D] the shared rows, x1 / x2 the rows of the two gates, ``params`` the packed parameters
+    (finalmlp_param_shapes), ``moving_mean`` / ``moving_var`` the 2 L moving statistics (stream 1 layer 0 .., then stream
+    2), ``dims`` = (Hg1, Hg2, widths1, widths2, num_heads, output_dim) -> (out [B,o], saved) with saved = (hg [B,Hg1+Hg2],
+    g [B,2 D], z [B,Z], a [B,Z], stats [2,Z]) or None.  ``training``: batch statistics in 2 L + 1 launches, and the moving
+    statistics move in place on the device; else the moving statistics in one launch."""
+    sizes, Z = _finalmlp_args(xs, x1, x2, params, dims)
+    B, D, L, o = sizes[0], sizes[1], sizes[6], sizes[10]
+    widths = list(dims[2]) + list(dims[3])
+    if len(moving_mean) != 2 * L or len(moving_var) != 2 * L:
+        raise ValueError("a FinalMLP body takes %d moving means and variances, got %d and %d"
+                         % (2 * L, len(moving_mean), len(moving_var)))
+    for t, w in zip(list(moving_mean) + list(moving_var), widths + widths):
+        _expect(t, (w,), "moving statistic")
+    if training and not save:
+        raise ValueError("the batch-statistics forward keeps its save buffers: z carries the chain between launches")
+    dev = xs.device
+    out = _new((B, o), dev)
+    saved = tuple(_new(s, dev, B) for s in ((B, dims[0] + dims[1]), (B, 2 * D), (B, Z), (B, Z), (2, Z))) if save else None
+    if B > 0:
+        args = (_ptr(xs), _ptr(x1), _ptr(x2), _ptr(params), _ptr_array(moving_mean), _ptr_array(moving_var), *sizes,
+                int(bool(training)), float(eps), float(momentum), _ptr(out), *_ptrs(saved or (None,) * 5))
+        if training:
+            _call_ws("rec_finalmlp_scratch_bytes", sizes, "rec_finalmlp_fwd_f32", dev, *args)
+        else:
+            _call("rec_finalmlp_fwd_f32", *args, None, 0)
+    return out, saved
+
+
+def finalmlp_bwd(xs, x1, x2, params, saved, out, dout, dims, training):
+    """-> (dxs [B,D], dx1 [B,D1], dx2 [B,D2], dparams in the layout of ``params``)"""
+    sizes, Z = _finalmlp_args(xs, x1, x2, params, dims)
+    B, D, o = sizes[0], sizes[1], sizes[10]
+    shapes = ((B, dims[0] + dims[1]), (B, 2 * D), (B, Z), (B, Z), (2, Z), (B, o), (B, o))
+    _expect_all(zip(tuple(saved) + (out, dout), shapes, ("hg", "g", "z", "a", "stats", "out", "dout")))
+    dxs, dx1, dx2, dparams = (_new_like(t, B) for t in (xs, x1, x2, params))
+    if B > 0:
+        _call_ws("rec_finalmlp_scratch_bytes", sizes, "rec_finalmlp_bwd_f32", xs.device, _ptr(xs), _ptr(x1), _ptr(x2),
+                 _ptr(params), *_ptrs(saved), _ptr(out), _ptr(dout), *sizes, int(bool(training)), _ptr(dxs), _ptr(dx1),
+                 _ptr(dx2), _ptr(dparams))
+    return dxs, dx1, dx2, dparams

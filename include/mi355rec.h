@@ -1232,6 +1232,64 @@ int rec_sine_interest_bwd_f32(const float* embed, int64_t ld, int64_t V, int E, 
 int rec_sine_aux_fwd_f32(const float* pool, int L, int D, float* loss, void* stream);
 int rec_sine_aux_bwd_f32(const float* pool, int L, int D, const float* gloss, float* dpool, void* stream);
 
+/* ---- FinalMLP (FinalMLPLayer / FeatureSelectionLayer / DualPartsInteractionLayer, 8.DMR/CustomLayers.py:319-442;
+ * csrc/finalmlp.hip): everything between the three lookups and the output.
+ * xs [B, D]: the shared rows, user fields first.  x1 [B, D1]: the rows of gate 1 (fs1_embedding of the ITEM ids),
+ * x2 [B, D2]: those of gate 2 (fs2_embedding of the USER ids).  Hg1, Hg2: the hidden width of each gate.  L layers per
+ * stream of widths widths1_host / widths2_host (HOST arrays of L ints); n heads, o outputs; d1, d2: the last widths.
+ *   hg_s = relu(x_s Wh_s + bh_s)   g_s = 2 sigmoid(hg_s Wo_s + bo_s)   part_s = g_s (.) xs                      s = 1, 2
+ *   z_s^0 = part_s W_s^0 + b_s^0   a_s^l = relu(xhat_s^l gamma_s^l + beta_s^l)   z_s^(l+1) = a_s^l W_s^(l+1) + b_s^(l+1)
+ *   xhat = (z - mean) rstd, rstd = 1 / sqrt(var + eps), per column: training != 0 the batch mean and the biased batch
+ *   variance, and moving <- momentum moving + (1 - momentum) batch on the device (eps and momentum are doubles so that
+ *   1 - momentum is rounded to fp32 once, as Keras rounds it); training == 0 the moving statistics,
+ *   nothing updated (Keras BatchNormalization; relu'(0) = 0)
+ *   out = sigmoid(m_1 W_1 + c_1 + m_2 W_2 + c_2 + sum_h m_1h^T W_12[h] m_2h)      m_s = a_s^(L-1), head h its columns
+ *   [h d_s / n, (h + 1) d_s / n)                                                                           out [B, o]
+ * params: ONE buffer, row-major tensors laid end to end without padding, in this order:
+ *   Wh_1 [D1, Hg1], bh_1 [Hg1], Wo_1 [Hg1, D], bo_1 [D],   Wh_2 [D2, Hg2], bh_2 [Hg2], Wo_2 [Hg2, D], bo_2 [D],
+ *   stream 1, l = 0 .. L-1: W [in, w], b [w], gamma [w], beta [w] (in = D, then the width before),   stream 2 likewise,
+ *   W_1 [d1, o], c_1 [o], W_2 [d2, o], c_2 [o], W_12 [n, d1 / n, d2 / n, o]
+ * dparams: the gradients in the same layout, every float written, never added to.
+ * moving_mean_host, moving_var_host: HOST arrays of 2 L device pointers (stream 1 layer 0 .. L-1, then stream 2), each
+ * to the [w] floats of that layer; read at enqueue time.
+ * Save buffers hg [B, Hg1 + Hg2], g [B, 2 D] (g_1 | g_2), z and a [B, Z] with Z = sum_l (w1_l + w2_l) and the columns
+ * layer-major (layer 0: stream 1, stream 2; layer 1: ...), stats [2, Z] (mean row, rstd row): all given or all NULL;
+ * training != 0 needs them (z carries the chain from launch to launch).  Inference without them writes out alone, the
+ * same out.
+ * Forward, training == 0: one launch.  training != 0: 2 L + 1 launches whatever B: a launch ends where the next batch
+ * statistic is needed and leaves z^l and, per 32-example tile and column, (count, mean, M2 about that mean); a merge
+ * launch folds the tiles in a fixed order with the pairwise update of Chan, Golub and LeVeque (the variance is never
+ * formed as E[x^2] - mean^2), writes mean and rstd and moves the moving averages; the last launch runs the head.
+ * Every product runs on v_mfma_f32_32x32x2_f32 (fp32-exact, as rec_gemm_f32), the head on the VALU out of LDS.
+ * Backward: takes dout [B, o], out and the save buffers, writes dxs [B, D], dx1 [B, D1], dx2 [B, D2] (written, never
+ * added to) and dparams.  L + 1 stage launches (head, then layer L-1 .. 0 and the gates), each followed by a slot sum
+ * that lands the stage's column sums in dparams (dgamma / dbeta of a layer are the batch sums the next stage's full
+ * BatchNorm backward reads); one launch for dW_1, dW_2, dW_12 over at most 16 batch slices added in order by a slot
+ * sum; every other weight gradient on rec_gemm_f32 (split-K over the batch in at most 16 slices, added in order).
+ * training != 0: the gradient of a bias b_s^l is sum_b dz = 0 identically and is written as exact zeros.
+ * All three only enqueue (no allocation, no host synchronisation: graph-capturable) and use no float atomics:
+ * bit-identical results run to run.  B == 0: nothing is launched.  B == 1, training: xhat is exactly 0.
+ * Supported: the limits are MaskNet's, this family has no constants of its own: each of D, D1, D2
+ * <= REC_MASKNET_MAX_D, each of Hg1, Hg2 and every stream width <= REC_MASKNET_MAX_O, 1 <= L <= REC_MASKNET_MAX_R,
+ * 1 <= o <= REC_MASKNET_MAX_R, (d2 / n) o <= REC_MASKNET_MAX_O, 0 <= B < 2^31; otherwise -2.  A size below 1 (B below
+ * 0), n not dividing d1 and d2, a NULL widths array, training other than 0 / 1, eps <= 0, momentum outside [0, 1], a
+ * NULL pointer or save buffers given in part: -1.  A workspace that is too small: -3.
+ * workspace (forward when training != 0, and backward): rec_finalmlp_scratch_bytes: 4 B (Z + o + d2 o + 4 D + Hg1 +
+ * Hg2) bytes of per-example gradients and operands, (B / 32) slots, at most 16 copies of the head weights and at most
+ * 16 of the largest other weight (0: invalid or unsupported shape). */
+size_t rec_finalmlp_scratch_bytes(int64_t B, int D, int D1, int D2, int Hg1, int Hg2, int L, const int* widths1_host,
+                                    const int* widths2_host, int n, int o);
+int rec_finalmlp_fwd_f32(const float* xs, const float* x1, const float* x2, const float* params,
+                         float* const* moving_mean_host, float* const* moving_var_host, int64_t B, int D, int D1, int D2,
+                         int Hg1, int Hg2, int L, const int* widths1_host, const int* widths2_host, int n, int o,
+                         int training, double eps, double momentum, float* out, float* hg, float* g, float* z, float* a,
+                         float* stats, void* workspace, size_t workspace_bytes, void* stream);
+int rec_finalmlp_bwd_f32(const float* xs, const float* x1, const float* x2, const float* params, const float* hg,
+                         const float* g, const float* z, const float* a, const float* stats, const float* out,
+                         const float* dout, int64_t B, int D, int D1, int D2, int Hg1, int Hg2, int L,
+                         const int* widths1_host, const int* widths2_host, int n, int o, int training, float* dxs,
+                         float* dx1, float* dx2, float* dparams, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
