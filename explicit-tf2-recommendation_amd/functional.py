@@ -1139,3 +1139,59 @@ class FinalMLPBody(torch.autograd.Function):
         dxs, dx1, dx2, dparams = ops.finalmlp_bwd(xs, x1, x2, params, saved, out, dout.contiguous(), ctx.dims,
                                                   ctx.training)
         return dxs, dx1, dx2, dparams, None, None, None, None, None
+
+
+class DmrMatch(torch.autograd.Function):
+    """DMRI2INetworkLayer, DMRU2INetworkLayer and compute_auxiliary_loss fused with the series and negative lookups
+    (8.DMR/CustomLayers.py:203-316; csrc/dmr.hip): table, the candidate's rows xi [B,C E], series ids [B,T,C], negative
+    ids [B,Nn,C], the positional table pos [T,C E], the i2i unit's Wc, Wp, We [C E,H] and z [H], the u2i unit's Wp, We
+    and z -> (i2i [B,C E + 1], u2i [B,C E + 1], aux [B]).  P = pos [Wp_i2i | Wp_u2i] and q = xi Wc are GEMMs here; the
+    rest is one launch each way, the backward recomputing from the ids.  An output nobody used arrives as None, not as
+    zeros.  With ``sink`` (functional.GradSink) the values of both lookups ride along with the profile lookup's
+    de-duplication and the table's gradient is returned there."""
+
+    @staticmethod
+    def forward(ctx, embed, xi, series, negatives, pos, Wc, Wp_i, We_i, z_i, Wp_u, We_u, z_u, padding_index, oob,
+                sink=None):
+        xi, pos, Wc = xi.contiguous(), pos.contiguous(), Wc.contiguous()
+        Wp = torch.cat([Wp_i, Wp_u], dim=1)
+        We = torch.cat([We_i, We_u], dim=1)
+        z = torch.stack([z_i, z_u])
+        P = ops.gemm(pos, Wp)
+        q = ops.gemm(xi, Wc)
+        i2i, u2i, aux = ops.dmr_fwd(embed, series, negatives, xi, q, P, We, z, padding_index, oob)
+        ctx.save_for_backward(embed, xi, series, negatives, pos, Wc, Wp, We, z, P, q)
+        ctx.padding_index, ctx.sink = padding_index, sink
+        ctx.set_materialize_grads(False)
+        return i2i, u2i, aux
+
+    @staticmethod
+    def backward(ctx, g_i2i, g_u2i, g_aux):
+        embed, xi, series, negatives, pos, Wc, Wp, We, z, P, q = ctx.saved_tensors
+        V, E = embed.shape
+        B, D = xi.shape
+        H = Wc.shape[1]
+        c = lambda g: None if g is None else g.contiguous()
+        sink, buf, dk, dn = ctx.sink, None, None, None
+        n_ser, n_neg = series.numel(), negatives.numel()
+        if sink is not None:                                 # values land behind the Gather's rows in one shared buffer
+            buf = sink.new_buf(n_ser + n_neg, E, embed.device)
+            dk = buf[sink.n_head:sink.n_head + n_ser].view(B, series.shape[1], D)
+            dn = buf[sink.n_head + n_ser:sink.n_head + n_ser + n_neg].view(B, negatives.shape[1], D)
+        gkeys, gneg, gitem, gq, dP, dWe, dz = ops.dmr_bwd(embed, series, negatives, xi, q, P, We, z, c(g_i2i), c(g_u2i),
+                                                          c(g_aux), ctx.padding_index, gkeys=dk, gneg=dn)
+        gxi = ops.gemm(gq, Wc, transB=True, epi=ops.EPI_ADD, e1=gitem)       # through u . xi and through q = xi Wc
+        dWc = ops.gemm(xi, gq, transA=True)
+        dWp = ops.gemm(pos, dP, transA=True)
+        dpos = ops.gemm(dP, Wp, transB=True)
+        ids = torch.cat([series.reshape(-1), negatives.reshape(-1)])
+        if sink is not None:
+            sink.ids, sink.buf = ids, buf
+            gembed = None
+        elif ctx.needs_input_grad[0]:
+            vals = torch.cat([gkeys.reshape(-1, E), gneg.reshape(-1, E)])
+            gembed = _sparse_grad(ops.DedupPlan(ids, V), vals, E, (V, E))
+        else:
+            gembed = None
+        return (gembed, gxi, None, None, dpos, dWc, dWp[:, :H], dWe[:, :H], dz[0], dWp[:, H:], dWe[:, H:], dz[1],
+                None, None, None)

@@ -2717,3 +2717,179 @@ class FinalMLPLayer(Layer):
         part1, part2 = self.fs_layer([xs, X_item, X_user])
         out = self.interaction_layer((self.mlp1(part1), self.mlp2(part2)))
         return {"output": Fn.FeatAct.apply(out.contiguous(), ops.DACT_SIGMOID, None, None, None)}
+
+
+# ---------------------------------------------------------------------------------------------------
+# DMR (8.DMR/CustomLayers.py:76-316): item-to-item and user-to-item attention with an auxiliary match loss
+# ---------------------------------------------------------------------------------------------------
+
+def _dmr_attention(scores, valid):
+    """softmax of ``scores`` [B,T] over the valid positions, 0 elsewhere (where(valid, s, -inf) then softmax, :243-244
+    and :305-306); an example without a valid position gets zeros, where the reference's softmax of all -inf is NaN"""
+    has = valid.any(dim=1, keepdim=True)
+    masked = torch.where(valid, scores, torch.full_like(scores, -math.inf))
+    masked = torch.where(has, masked, torch.zeros_like(scores))
+    return torch.softmax(masked, dim=-1) * (valid & has).to(scores.dtype)
+
+
+class DMRI2INetworkLayer(Layer):
+    """8.DMR/CustomLayers.py:203-248: s_t = z . tanh(xi Wc + x_t We + pos_t Wp), softmax over the valid positions ->
+    [sum_t a_t x_t, sum over the valid t of s_t], [B, D + 1].  ``input_dim`` (extension) is needed because layers are
+    built eagerly.  ``b`` is created and never used, as in the reference (:219): it stays in the state dict and its
+    gradient is None.  ``forward`` is the composed path in the reference's operation order."""
+
+    def __init__(self, hidden_dim=48, input_dim=None):
+        super().__init__()
+        if input_dim is None:
+            raise ValueError("DMRI2INetworkLayer needs input_dim")
+        self.hidden_dim = hidden_dim
+        self.Wc = torch.nn.Parameter(glorot_uniform((input_dim, hidden_dim)))
+        self.Wp = torch.nn.Parameter(glorot_uniform((input_dim, hidden_dim)))
+        self.We = torch.nn.Parameter(glorot_uniform((input_dim, hidden_dim)))
+        self.b = torch.nn.Parameter(glorot_uniform((hidden_dim,)))
+        self.z = torch.nn.Parameter(glorot_uniform((hidden_dim,)))
+
+    def forward(self, inputs):
+        X_series, pos_series, X_item, valid_mask = inputs
+        pre = (X_item @ self.Wc)[:, None, :] + X_series @ self.We + (pos_series @ self.Wp)[None, :, :]
+        scores = (self.z[None, None, :] * torch.tanh(pre)).sum(-1)                       # [B,T]
+        score_sum = torch.where(valid_mask, scores, torch.zeros_like(scores)).sum(-1, keepdim=True)
+        attention = _dmr_attention(scores, valid_mask)
+        attention_output = (attention[:, :, None] * X_series).sum(1)
+        return torch.cat([attention_output, score_sum], dim=1)
+
+
+class DMRU2INetworkLayer(Layer):
+    """8.DMR/CustomLayers.py:251-316: s_t = z . tanh(x_t We + pos_t Wp), av_t = a_t x_t, u = sum_t av_t -> ([u, u . xi]
+    [B, D + 1], auxiliary_loss [B]).  The loss is always computed: ``stage == 'train' or 'eval'`` (:312) is always true
+    in the reference, and so it is here whatever ``stage`` says.  With last = (number of valid positions) - 1 it sets
+    av[last] against ov = sum_{t < last} av_t (the mask is range(T) < last, not validity, :277) and every negative
+    against ov; tf.keras.losses.CosineSimilarity returns MINUS the cosine (:281-284), so the logits are (1 - cos) / 2,
+    into the sigmoid cross entropy with label 1 and 0.  ``b`` is created and never used (:264).  An example without a
+    valid position gives zeros (the reference fails there: gather_nd at -1)."""
+
+    def __init__(self, hidden_dim=48, input_dim=None):
+        super().__init__()
+        if input_dim is None:
+            raise ValueError("DMRU2INetworkLayer needs input_dim")
+        self.hidden_dim = hidden_dim
+        self.Wp = torch.nn.Parameter(glorot_uniform((input_dim, hidden_dim)))
+        self.We = torch.nn.Parameter(glorot_uniform((input_dim, hidden_dim)))
+        self.b = torch.nn.Parameter(glorot_uniform((hidden_dim,)))
+        self.z = torch.nn.Parameter(glorot_uniform((hidden_dim,)))
+
+    @staticmethod
+    def _neg_cosine(p, q):
+        """tf.keras.losses.CosineSimilarity(axis=-1): -sum(l2_normalize(p) l2_normalize(q)), epsilon 1e-12"""
+        nrm = lambda v: v * torch.rsqrt(torch.clamp((v * v).sum(-1, keepdim=True), min=1e-12))
+        return -(nrm(p) * nrm(q)).sum(-1)
+
+    def compute_auxiliary_loss(self, attentioned_vectors, valid_mask, X_negative):
+        B, T = valid_mask.shape
+        n = valid_mask.sum(1)
+        last = n - 1
+        lv = attentioned_vectors[torch.arange(B, device=last.device), last.clamp(min=0)]
+        new_mask = torch.arange(T, device=last.device)[None, :] < last[:, None]
+        ov = (attentioned_vectors * new_mask[:, :, None].to(attentioned_vectors.dtype)).sum(1)
+        pos_logits = (self._neg_cosine(lv, ov) + 1) / 2
+        neg_logits = (self._neg_cosine(X_negative, ov[:, None, :].expand_as(X_negative)) + 1) / 2
+        softplus = torch.nn.functional.softplus      # sigmoid CE: label 1 -> softplus(-x), label 0 -> softplus(x)
+        loss = softplus(-pos_logits) + softplus(neg_logits).sum(-1)
+        return torch.where(n > 0, loss, torch.zeros_like(loss))
+
+    def forward(self, inputs):
+        X_series, pos_series, X_item, valid_mask, stage, X_negative = inputs
+        pre = X_series @ self.We + (pos_series @ self.Wp)[None, :, :]
+        scores = (self.z[None, None, :] * torch.tanh(pre)).sum(-1)
+        attention = _dmr_attention(scores, valid_mask)
+        attentioned_vectors = attention[:, :, None] * X_series
+        attention_output = attentioned_vectors.sum(1)
+        inner_product = (attention_output * X_item).sum(-1, keepdim=True)
+        auxiliary_loss = self.compute_auxiliary_loss(attentioned_vectors, valid_mask, X_negative)
+        return torch.cat([attention_output, inner_product], dim=1), auxiliary_loss
+
+
+class DMRLayer(Layer):
+    """8.DMR/CustomLayers.py:76-200, Deep Match to Rank: the profile rows, an item-to-item attention of the candidate
+    over the behaviour series and a user-to-item attention of the series alone, both with a trained positional table,
+    into make_mlp_layer([200, 80], sigmoid_units=True); the u2i unit also yields the auxiliary match loss over the sampled
+    negatives.  ``forward`` returns ``{'output': [B,1], 'auxiliary_loss': [B]}``; the reference nowhere says how the loss
+    enters training.  The series length must equal ``max_length`` (pos_embed(tf.range(max_length)) is added to it, :181).
+    ``fused=True`` (extension): everything behind the lookups of both units and of the loss is one launch each way
+    (csrc/dmr.hip), and one profile lookup serves ``profile`` and the candidate's rows, its de-duplication shared with
+    the series and negative lookups; ``fused=False`` composes the two sub-layers in torch.  The loss is computed in
+    every stage, as in the reference (:312).  Padding in the middle of a series is not an error: last is still the
+    number of valid positions minus one.
+    The one deliberate deviation: an example whose series has no valid position makes the reference fail (gather_nd at
+    index -1, a softmax of all -inf); here it yields zero attention vectors, score sum 0, inner product 0 and
+    auxiliary loss 0, with zero gradients, and no row is read at position -1."""
+
+    def __init__(self, user_and_context_categorical_features=["uid", "utag1", "utag2", "utag3", "utag4"],
+                 item_categorical_features=["i_goods_id", "i_shop_id", "i_cate_id"],
+                 behavior_series_features=["visited_goods_ids", "visited_shop_ids", "visited_cate_ids"],
+                 negative_sample_features=["negative_goods_ids", "negative_shop_ids", "negative_cate_ids"],
+                 feature_dims=160000, embedding_dims=16, activation="PReLU", padding_index=0, stage="train",
+                 max_length=10, fused=True):
+        super().__init__()
+        self.user_and_context_categorical_features = user_and_context_categorical_features
+        self.item_categorical_features = item_categorical_features
+        assert len(item_categorical_features) == len(behavior_series_features) == len(negative_sample_features), \
+            "Features to be interacted should match in item and behavior/negative series"
+        self.behavior_series_features = behavior_series_features
+        self.negative_sample_features = negative_sample_features
+        self.feature_dims = feature_dims
+        self.embedding_dims = embedding_dims
+        D = len(item_categorical_features) * embedding_dims
+        ops.dmr_check_shape(D, D, T=max_length, Nn=1)
+        self.id_embed = Embedding(feature_dims, embedding_dims)
+        self.max_length = max_length
+        self.pos_embed = Embedding(max_length, D)
+        n_profile = len(user_and_context_categorical_features) + len(item_categorical_features)
+        self.mlp = make_mlp_layer([200, 80], activation=activation, sigmoid_units=True,
+                                  input_dim=n_profile * embedding_dims + 2 * (D + 1))
+        self.padding_index = padding_index
+        self.stage = stage
+        self.i2i_network = DMRI2INetworkLayer(D, input_dim=D)
+        self.u2i_network = DMRU2INetworkLayer(D, input_dim=D)
+        self.fused = fused
+
+    def set_stage(self, stage):
+        assert stage in ("train", "valid", "inference")
+        self.stage = stage
+
+    def forward(self, inputs):
+        shape = tuple(getattr(inputs[self.behavior_series_features[0]], "shape", ()))
+        if len(shape) == 2 and shape[1] != self.max_length:      # before anything is moved or launched
+            raise ValueError("the behaviour series must have max_length = %d positions, got %d"
+                             % (self.max_length, shape[1]))
+        prof_names = self.user_and_context_categorical_features + self.item_categorical_features
+        X_cate = assemble_index(inputs, prof_names)
+        dev = X_cate.device
+        series = _stack_ids(inputs, self.behavior_series_features, dev)
+        negatives = _stack_ids(inputs, self.negative_sample_features, dev)
+        B, T, Cn = series.shape
+        if T != self.max_length:
+            raise ValueError("the behaviour series must have max_length = %d positions, got %d" % (self.max_length, T))
+        flag = ops.new_flag(dev) if self.check_ids else None
+        n_item = len(self.item_categorical_features)
+        i2i_net, u2i_net = self.i2i_network, self.u2i_network
+        # one lookup serves both: the candidate item's rows are the tail of the profile rows (the reference looks the item
+        # ids up a second time, :165-172 -- same values)
+        sink = self.id_embed.grad_sink(X_cate) if self.fused else None
+        profile = self.id_embed(X_cate, flag, sink)
+        profile_output = profile.reshape(B, -1)
+        X_item = profile[:, profile.shape[1] - n_item:, :].reshape(B, -1)
+        pos_series = self.pos_embed.embeddings                   # pos_embed(tf.range(max_length)): the whole table
+        if self.fused:
+            i2i_vector, u2i_vector, auxiliary_loss = Fn.DmrMatch.apply(
+                self.id_embed.embeddings, X_item, series, negatives, pos_series, i2i_net.Wc, i2i_net.Wp, i2i_net.We,
+                i2i_net.z, u2i_net.Wp, u2i_net.We, u2i_net.z, self.padding_index, flag, sink)
+        else:
+            X_series = self.id_embed(series.reshape(B, T * Cn), flag).reshape(B, T, -1)
+            X_negative = self.id_embed(negatives.reshape(B, -1), flag).reshape(B, negatives.shape[1], -1)
+            valid_mask = series[:, :, 0] != self.padding_index
+            i2i_vector = i2i_net([X_series, pos_series, X_item, valid_mask])
+            u2i_vector, auxiliary_loss = u2i_net([X_series, pos_series, X_item, valid_mask, self.stage, X_negative])
+        self._raise_if_oob(flag)
+        X_combined = ConcatCols.apply(profile_output, i2i_vector, u2i_vector)
+        return {"output": self.mlp(X_combined), "auxiliary_loss": auxiliary_loss}

@@ -2212,3 +2212,80 @@ def finalmlp_bwd(xs, x1, x2, params, saved, out, dout, dims, training):
                  _ptr(params), *_ptrs(saved), _ptr(out), _ptr(dout), *sizes, int(bool(training)), _ptr(dxs), _ptr(dx1),
                  _ptr(dx2), _ptr(dparams))
     return dxs, dx1, dx2, dparams
+
+
+# ---- DMR: both attention units over the behaviour series and the auxiliary match loss, one launch each way
+# (csrc/dmr.hip).  Key width and hidden width share DIN's key-width limit; the LDS fit is the header's formula.
+def dmr_lds_bytes(T, D, H, Nn):
+    """LDS of one example of either direction (include/mi355rec.h)."""
+    return 4 * (T * (_odd(D) + _odd(2 * H) + 7) + Nn * (_odd(D) + 3) + 8 * _odd(D) + 5 * H + 16)
+
+
+def dmr_check_shape(D, H, T=None, Nn=None):
+    """ValueError for sizes that describe no DMR body, NotImplementedError naming the limit for shapes the kernels do not
+    cover (the ABI would return -2): key width D = E C, hidden width H of both units and -- where both are given -- the
+    series length T and the number of negatives Nn per example."""
+    sizes = [D, H] + [v for v in (T, Nn) if v is not None]
+    if min(sizes) < 1:
+        raise ValueError("every size of a DMR body must be positive, got D=%d, H=%d, T=%r, Nn=%r" % (D, H, T, Nn))
+    if D > DIN_MAX_D or H > DIN_MAX_D:
+        raise NotImplementedError("DMR kernels cover key width and hidden width <= %d; got key width=%d, hidden width=%d"
+                                  % (DIN_MAX_D, D, H))
+    if T is not None and Nn is not None:
+        _lds_fit(dmr_lds_bytes(T, D, H, Nn), "DMR holds one example",
+                 "T ((D|1) + (2H|1) + 7) + Nn ((D|1) + 3) + 8 (D|1) + 5 H + 16",
+                 "T=%d, key width=%d, hidden width=%d, Nn=%d" % (T, D, H, Nn))
+
+
+def _dmr_args(embed, series, negatives, xi, q, P, We, z, padding_index):
+    args, (V, E, B, T, Cn) = _series_head(embed, series, "DMR match", (negatives, "negatives [B,Nn,C]", torch.int64),
+                                          (xi, "xi [B,D]"), (q, "q [B,H]"), (P, "P [T,2H]"), (We, "We [D,2H]"),
+                                          (z, "z [2,H]"))
+    D, H, Nn = Cn * E, z.shape[1], negatives.shape[1]
+    want = {"negatives": (B, Nn, Cn), "xi": (B, D), "q": (B, H), "P": (T, 2 * H), "We": (D, 2 * H), "z": (2, H)}
+    got = {"negatives": negatives, "xi": xi, "q": q, "P": P, "We": We, "z": z}
+    if any(tuple(got[k].shape) != s for k, s in want.items()):
+        raise ValueError("DMR match: with series %s and z %s the operands must be %s; got %s"
+                         % (tuple(series.shape), tuple(z.shape), want, {k: tuple(t.shape) for k, t in got.items()}))
+    dmr_check_shape(D, H, T=T, Nn=Nn)
+    return args + [_ptr(negatives), Nn, _ptr(xi), _ptr(q), _ptr(P), _ptr(We), _ptr(z), H, int(padding_index)], \
+        (B, T, Cn, E, D, H, Nn)
+
+
+def dmr_fwd(embed, series, negatives, xi, q, P, We, z, padding_index=0, oob=None):
+    """DMRI2INetworkLayer, DMRU2INetworkLayer and compute_auxiliary_loss over the looked-up series and negatives in one
+    launch: series ids [B,T,C] and negative ids [B,Nn,C] into ``embed``, the candidate's rows xi [B,C E], q = xi Wc [B,H],
+    P = pos [Wp_i2i | Wp_u2i] [T,2H], We = [We_i2i | We_u2i] [C E,2H], z = [z_i2i; z_u2i] [2,H] -> (i2i [B,C E + 1]:
+    pooled series | score sum, u2i [B,C E + 1]: pooled series | its inner product with xi, aux [B]).  An example with no
+    valid position gives zeros.  Nothing else is saved."""
+    args, (B, T, Cn, E, D, H, Nn) = _dmr_args(embed, series, negatives, xi, q, P, We, z, padding_index)
+    dev = embed.device
+    i2i, u2i, aux = _new((B, D + 1), dev, B), _new((B, D + 1), dev, B), _new((B,), dev, B)
+    if B > 0:                                            # an empty batch answers from the sizes alone
+        _call("rec_dmr_fwd_f32", *args, _ptr(i2i), _ptr(u2i), _ptr(aux), _ptr(oob))
+    return i2i, u2i, aux
+
+
+def dmr_bwd(embed, series, negatives, xi, q, P, We, z, g_i2i=None, g_u2i=None, g_aux=None, padding_index=0, gkeys=None,
+            gneg=None):
+    """-> (gkeys [B,T,C E] and gneg [B,Nn,C E], the IndexedSlices values of the two lookups, gitem [B,C E] (through the
+    inner product alone), gq [B,H], dP [T,2H], dWe [C E,2H], dz [2,H]) from g_i2i [B,C E + 1], g_u2i [B,C E + 1] and
+    g_aux [B], each of which may be None (exact zeros); the forward is run again from the ids.  ``gkeys`` / ``gneg``:
+    optional preallocated contiguous destinations (the tail of a shared value buffer)."""
+    args, (B, T, Cn, E, D, H, Nn) = _dmr_args(embed, series, negatives, xi, q, P, We, z, padding_index)
+    dev = embed.device
+    _expect(g_i2i, (B, D + 1), "g_i2i", "[B,D+1]", optional=True)
+    _expect(g_u2i, (B, D + 1), "g_u2i", "[B,D+1]", optional=True)
+    _expect(g_aux, (B,), "g_aux", "[B]", optional=True)
+    if gkeys is None:
+        gkeys = _new((B, T, D), dev, B)
+    if gneg is None:
+        gneg = _new((B, Nn, D), dev, B)
+    _expect(gkeys, (B, T, D), "gkeys", "[B,T,D]")
+    _expect(gneg, (B, Nn, D), "gneg", "[B,Nn,D]")
+    gitem, gq = _new((B, D), dev, B), _new((B, H), dev, B)
+    dP, dWe, dz = _new((T, 2 * H), dev, B), _new((D, 2 * H), dev, B), _new((2, H), dev, B)
+    if B > 0:
+        _call_ws("rec_dmr_scratch_bytes", (B, T, E, Cn, H, Nn), "rec_dmr_bwd_f32", dev, *args, _ptr(g_i2i), _ptr(g_u2i),
+                 _ptr(g_aux), _ptr(gkeys), _ptr(gneg), _ptr(gitem), _ptr(gq), _ptr(dP), _ptr(dWe), _ptr(dz))
+    return gkeys, gneg, gitem, gq, dP, dWe, dz

@@ -1290,6 +1290,46 @@ int rec_finalmlp_bwd_f32(const float* xs, const float* x1, const float* x2, cons
                          const int* widths1_host, const int* widths2_host, int n, int o, int training, float* dxs,
                          float* dx1, float* dx2, float* dparams, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- DMR (DMRI2INetworkLayer / DMRU2INetworkLayer / compute_auxiliary_loss, 8.DMR/CustomLayers.py:203-316;
+ * csrc/dmr.hip): both attention units over the looked-up behaviour series and the auxiliary match loss, one launch each
+ * way.  series int64 [B, T, C], negatives int64 [B, Nn, C], D = E C; xi [B, D] the candidate item's rows; q [B, H] =
+ * xi Wc and P [T, 2H] = pos [Wp_i2i | Wp_u2i], both made by the caller (rec_gemm_f32); We [D, 2H] = [We_i2i | We_u2i];
+ * z [2, H] = z_i2i, z_u2i.  Unit 0 is i2i, unit 1 u2i.  Per example, x_t = concat_r embed[series[b,t,r]]:
+ *   valid_t = series[b,t,0] != padding_index   n = sum_t valid_t   last = n - 1
+ *   h_t = tanh(([q | 0] + x_t We) + P_t)       s[u,t] = z_u . h_t[uH : (u+1)H]
+ *   A_u = softmax over the valid t of s[u], 0 elsewhere (all 0 where n = 0)
+ *   i2i = [sum_t A_0[t] x_t, sum_valid s[0,t]]                                                         i2i [B, D + 1]
+ *   u = sum_t A_1[t] x_t    u2i = [u, u . xi]                                                           u2i [B, D + 1]
+ *   lv = A_1[last] x_last   ov = sum_{t < last} A_1[t] x_t   nrm(v) = v / sqrt(max(sum v^2, 1e-12))
+ *   cos(p, q) = sum nrm(p) nrm(q)   pos = (1 - cos(lv, ov)) / 2   neg_j = (1 - cos(xneg_j, ov)) / 2
+ *   aux = softplus(-pos) + sum_j softplus(neg_j)   (0 where n = 0: the reference fails there)             aux [B]
+ * Nothing is saved.  The backward takes g_i2i [B, D + 1], g_u2i [B, D + 1] and g_aux [B], each of which may be NULL
+ * (exact zeros), recomputes the forward from the ids and writes, never adds to: gkeys [B, T, D] and gneg [B, Nn, D],
+ * the IndexedSlices values of the two lookups; gitem [B, D] (through u . xi only); gq [B, H]; dP [T, 2H], dWe [D, 2H],
+ * dz [2, H], summed over the batch through one slot per workgroup of a capped grid and a slot sum in wave order.  The
+ * clamp inside nrm has TF's gradient (a constant factor 1e6 where sum v^2 < 1e-12).  One example per workgroup; x We,
+ * dh We^T and x^T dh run on v_mfma_f32_32x32x2_f32.  Both only enqueue (no allocation, no host synchronisation:
+ * graph-capturable) and use no float atomics: bit-identical results run to run.
+ * Supported, the same both ways: D = E C <= REC_DIN_MAX_D (256), H <= REC_DIN_MAX_D, 0 <= B < 2^31 and one example's
+ * LDS within the 150 KiB launch cap (rec_dmr_lds_bytes; 0: invalid or unsupported):
+ *   4 (T ((D|1) + (2H|1) + 7) + Nn ((D|1) + 3) + 8 (D|1) + 5 H + 16) <= 153600                (x|1: x made odd)
+ * e.g. T <= 244 at D = H = 48, Nn = 6.  scratch (backward only): rec_dmr_scratch_bytes: min(B, 1024) slots of
+ * (D + T + 1) 2H floats (at most 512 / 256 slots when dWe has more than eight / sixteen 32 x 32 blocks); 0: invalid or
+ * unsupported.  Return codes, answered in this order: a size below 1 (B below 0): -1; a shape outside the limits: -2,
+ * from the sizes alone; ld < E, V < 1 or a NULL pointer other than oob_flag, g_i2i, g_u2i, g_aux: -1; a scratch that is
+ * too small: -3; then B == 0: 0, nothing is launched or written. */
+size_t rec_dmr_lds_bytes(int T, int E, int C, int H, int Nn);
+size_t rec_dmr_scratch_bytes(int64_t B, int T, int E, int C, int H, int Nn);
+int rec_dmr_fwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* series, int64_t B, int T,
+                    const int64_t* negatives, int Nn, const float* xi, const float* q, const float* P, const float* We,
+                    const float* z, int H, int64_t padding_index, float* i2i, float* u2i, float* aux, int* oob_flag,
+                    void* stream);
+int rec_dmr_bwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* series, int64_t B, int T,
+                    const int64_t* negatives, int Nn, const float* xi, const float* q, const float* P, const float* We,
+                    const float* z, int H, int64_t padding_index, const float* g_i2i, const float* g_u2i,
+                    const float* g_aux, float* gkeys, float* gneg, float* gitem, float* gq, float* dP, float* dWe,
+                    float* dz, void* scratch, size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
