@@ -1195,3 +1195,59 @@ class DmrMatch(torch.autograd.Function):
             gembed = None
         return (gembed, gxi, None, None, dpos, dWc, dWp[:, :H], dWe[:, :H], dz[0], dWp[:, H:], dWe[:, H:], dz[1],
                 None, None, None)
+
+
+class EmbEPNetLookup(torch.autograd.Function):
+    """PEPNet's embedding stage fused with the EPNet gates (10.POSO/CustomLayers.py:415-457; csrc/epnet.hip): table, ids
+    [B, F + P] (F main ids, then the P personalisation ids) and the stacked GateNU weights A [F, P E, Hg], a [F, Hg], Bm
+    [F, Hg, E], bm [F, E] -> u [B, (F + P) E]: the main rows times their gate, then the personalisation rows raw.
+    Nothing but the ids is saved; the backward computes the gates again, returns the gate weights' gradients and hands
+    the row gradients (the personalisation rows' from both of their uses) to the de-duplicated sparse path."""
+
+    @staticmethod
+    def forward(ctx, table, ids, F, oob, A, a, Bm, bm):
+        weights = [t.contiguous() for t in (A, a, Bm, bm)]
+        u = ops.epnet_lookup_fwd(table, ids, F, *weights, oob)
+        ctx.save_for_backward(table, ids, *weights)
+        ctx.F = F
+        return u
+
+    @staticmethod
+    def backward(ctx, du):
+        table, ids, *weights = ctx.saved_tensors
+        V, E = table.shape
+        vals, grads = ops.epnet_lookup_bwd(table, ids, ctx.F, *weights, du.contiguous())
+        gtable = _sparse_grad(ops.DedupPlan(ids, V), vals, E, (V, E)) if ctx.needs_input_grad[0] else None
+        return (gtable, None, None, None) + tuple(grads)
+
+
+class PosoMLP(torch.autograd.Function):
+    """T stacked POSO-MLPs of chained layers (10.POSO/CustomLayers.py:92-119; csrc/poso.hip): x [B, Dm], g [B, Dg] and
+    the packed weights Wg1, bg1, Wg2, bg2, W, b, C (include/mi355rec.h) -> out [B, T, units[-1]]; one launch each way
+    plus the slot sums, one launch for all small weight gradients and one weight-gradient GEMM.
+    ``shared_cols`` > 0 is PEPNet's arrangement: ``x`` is None and the main input is the leading ``shared_cols`` columns
+    of ``g`` (nothing is copied), which as part of the gate input stand behind a stop_gradient -- the gradient of ``g``
+    is then dx in those columns and dg in the others."""
+
+    @staticmethod
+    def forward(ctx, x, g, units, acts, m, shared_cols, *weights):
+        g = g.contiguous()
+        x = g[:, :shared_cols] if shared_cols else x.contiguous()
+        weights = [t.contiguous() for t in weights]
+        train = any(ctx.needs_input_grad)
+        out, saved = ops.poso_mlp_fwd(x, g, weights, units, acts, m, save=train)
+        if train:
+            ctx.save_for_backward(x, g, *weights, *saved)
+        ctx.cfg = (list(units), list(acts), m)
+        ctx.shared_cols = shared_cols
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, g, *rest = ctx.saved_tensors
+        weights, saved = rest[:7], rest[7:]
+        dx, dg, grads = ops.poso_mlp_bwd(x, g, weights, saved, dout.contiguous(), *ctx.cfg)
+        if ctx.shared_cols:
+            dg[:, :ctx.shared_cols].copy_(dx)             # stop_gradient: the gate path's share of these columns is dropped
+            dx = None
+        return (dx, dg, None, None, None, None) + tuple(grads)

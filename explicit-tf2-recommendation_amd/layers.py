@@ -42,6 +42,9 @@ libmi355rec.so (through functional.py / ops.py).  Reference classes and the line
   MMOELayer                     4.MMOE/CustomLayers.py:107-173
   ESMMLayer                     4.MMOE/CustomLayers.py:175-245
   PLELayer                      4.MMOE/CustomLayers.py:248-384
+  GateNULayer                   10.POSO/CustomLayers.py:76-89
+  PosoForMLPLayer               10.POSO/CustomLayers.py:92-119   (chain_layers=True: an extension, see the class)
+  PEPNetLayer                   10.POSO/CustomLayers.py:371-462  (returns a tensor [B, tasks, units], as the reference)
   MultiInterestExtractorLayer   6.MIND/CustomLayers.py:62-138   (takes the table and the ids: the lookup is fused)
   LabelAwareAttention           6.MIND/CustomLayers.py:141-158  (with the inner products and the loss of :267-285)
   MINDLayer                     6.MIND/CustomLayers.py:161-285
@@ -2106,6 +2109,191 @@ class PLELayer(Layer):
     def forward(self, inputs):
         out = self.task_outputs(inputs)
         return {"task_%d" % i: out[:, i:i + 1] for i in range(self.num_tasks)}
+
+
+# ---------------------------------------------------------------------------------------------------
+# 10.POSO: GateNU, POSO-MLP, PEPNet
+# ---------------------------------------------------------------------------------------------------
+
+_POSO_ACTS = ("relu", "sigmoid", "linear")
+
+
+class _Sequential(Layer):
+    """tf.keras.models.Sequential of Dense layers: ``layers.{i}.{kernel,bias}``."""
+
+    def __init__(self, layers):
+        super().__init__()
+        self.layers = torch.nn.ModuleList(layers)
+
+    def forward(self, x):
+        for layer in self.layers:
+            x = layer(x)
+        return x
+
+
+class GateNULayer(Layer):
+    """10.POSO/CustomLayers.py:76-89: 2 * sigmoid(relu(x A + a) Bm + bm), parameters ``gate.layers.{0,1}.{kernel,bias}``.
+    ``input_dim`` builds the parameters at construction (the fused layers below read them; they never call this layer).
+    A direct call runs the two Dense layers on their own kernels."""
+
+    def __init__(self, hidden_unit=16, output_unit=16, input_dim=None):
+        super().__init__()
+        self.hidden_unit, self.output_unit = int(hidden_unit), int(output_unit)
+        self.gate = _Sequential([Dense(self.hidden_unit, activation="relu", input_dim=input_dim),
+                                 Dense(self.output_unit, activation="sigmoid", input_dim=self.hidden_unit)])
+
+    def forward(self, inputs):
+        shape = inputs.shape
+        return (2.0 * self.gate(inputs.reshape(-1, shape[-1]))).reshape(*shape[:-1], self.output_unit)
+
+
+class _Holder(Layer):
+    """``kernel`` / ``bias`` of a Dense layer that only a fused kernel reads."""
+
+    def __init__(self, input_dim, units):
+        super().__init__()
+        self.kernel = torch.nn.Parameter(glorot_uniform((int(input_dim), int(units))))
+        self.bias = torch.nn.Parameter(torch.zeros(int(units)))
+
+
+class PosoForMLPLayer(Layer):
+    """10.POSO/CustomLayers.py:92-119: an MLP whose every layer is scaled by a GateNU of a second input and a trainable
+    scalar, act_i(C_i (in W_i + b_i) (.) GateNU_i(gate input)), called as ``layer(main, gate)`` -> [B, units[-1]].
+    Parameters under the reference's names: ``dense_layers.{i}.{kernel,bias}``, ``gates.{i}.gate.layers.{0,1}.{kernel,
+    bias}``, ``C_list.{i}``.  Activations: 'relu', 'sigmoid', 'linear'; 'PReLU' and ``norm`` (which the reference builds
+    as a fresh, untrained Keras layer inside every call: nothing stable to mirror) raise NotImplementedError.
+
+    ``chain_layers=False`` (the default) is the reference AS WRITTEN: every layer reads ``main`` (:109), the loop keeps
+    only the last layer's activation (:118-119), so the output is the last layer applied to ``main``; the layers before
+    it hold parameters of input width ``main_dim``, are not computed and get no gradient (None, as in TF).
+    ``chain_layers=True`` is an EXTENSION, not reference behaviour (in the sense of DINLayer(mask_mode='valid')): the
+    MLP the loop's ``inputs=`` assignment and the POSO paper mean, layer i reading layer i-1's activation, so W_i is
+    [units[i-1], units[i]].  Both run on one kernel each way (functional.PosoMLP): literal mode is that kernel with one
+    layer."""
+
+    def __init__(self, units=[32, 16, 8], activations=["relu", "relu", "relu"], gate_hidden_multiple=2, norm=None,
+                 main_dim=None, gate_dim=None, chain_layers=False):
+        super().__init__()
+        if norm is not None:
+            raise NotImplementedError("PosoForMLPLayer(norm=%r): the reference constructs an untrained normalisation "
+                                      "layer inside every call; only norm=None is built" % (norm,))
+        self.units = [int(u) for u in units]
+        self.activations = list(activations)
+        if len(self.activations) != len(self.units) or not self.units:
+            raise ValueError("units and activations must have the same, positive length, got %d and %d"
+                             % (len(self.units), len(self.activations)))
+        for act in self.activations:
+            if act not in _POSO_ACTS:
+                raise NotImplementedError("PosoForMLPLayer covers the activations %s, got %r" % (_POSO_ACTS, act))
+        if main_dim is None or gate_dim is None:
+            raise ValueError("PosoForMLPLayer needs main_dim and gate_dim: its kernel reads parameters built at "
+                             "construction")
+        self.gate_hidden_multiple = int(gate_hidden_multiple)
+        self.main_dim, self.gate_dim, self.chain_layers = int(main_dim), int(gate_dim), bool(chain_layers)
+        self.norm = None
+        self.layer_depth = len(self.units)
+        ops.poso_mlp_check_shape(self.main_dim, self.gate_dim, 1, self.live_units(), self.gate_hidden_multiple)
+        dims = [self.main_dim] + (self.units[:-1] if self.chain_layers else [self.main_dim] * (self.layer_depth - 1))
+        self.dense_layers = torch.nn.ModuleList([_Holder(k, u) for k, u in zip(dims, self.units)])
+        self.gates = torch.nn.ModuleList(
+            [GateNULayer(self.gate_hidden_multiple * u, u, input_dim=self.gate_dim) for u in self.units])
+        self.C_list = torch.nn.ParameterList([torch.nn.Parameter(torch.ones(())) for _ in self.units])
+
+    def live_layers(self):
+        """indices of the layers that reach the output: all of them when chained, the last one as written"""
+        return list(range(self.layer_depth)) if self.chain_layers else [self.layer_depth - 1]
+
+    def live_units(self):
+        return [self.units[i] for i in self.live_layers()]
+
+    def live_activations(self):
+        return [self.activations[i] for i in self.live_layers()]
+
+    def forward(self, inputs_for_main, inputs_for_gate):
+        weights = pack_poso_weights([self])
+        out = Fn.PosoMLP.apply(inputs_for_main, inputs_for_gate, self.live_units(), self.live_activations(),
+                               self.gate_hidden_multiple, 0, *weights)
+        return out[:, 0, :]
+
+
+def pack_poso_weights(towers):
+    """The live layers' parameters of T PosoForMLPLayers of one shape in the packed layout of include/mi355rec.h (Wg1,
+    bg1, Wg2, bg2, W, b, C); gradients flow back through the concatenations."""
+    cat = torch.cat
+    pairs = [(t, i) for t in towers for i in t.live_layers()]
+    g0 = lambda t, i: t.gates[i].gate.layers[0]
+    g1 = lambda t, i: t.gates[i].gate.layers[1]
+    return (cat([g0(t, i).kernel for t, i in pairs], dim=1), cat([g0(t, i).bias for t, i in pairs]),
+            cat([g1(t, i).kernel.reshape(-1) for t, i in pairs]), cat([g1(t, i).bias for t, i in pairs]),
+            cat([t.dense_layers[i].kernel.reshape(-1) for t, i in pairs]),
+            cat([t.dense_layers[i].bias for t, i in pairs]),
+            torch.stack([t.C_list[i] for t, i in pairs]).reshape(len(towers), -1))
+
+
+_PEPNET_PP = ["ppnet_cate1", "ppnet_cate2"]
+_PEPNET_EP = ["epnet_cate1", "epnet_cate2"]
+
+
+class PEPNetLayer(Layer):
+    """10.POSO/CustomLayers.py:371-462: parameter- and embedding-personalised network.  ONE table serves the
+    ``categorical_features`` (main rows [B, F, E]) and the ``ppnet_input_features`` (pp [B, P E]).  EPNet: field f's
+    rows are multiplied by GateNU_f(pp).  PPNet: ``num_tasks`` PosoForMLPLayers (units ``poso_mlp_units``, relu, relu,
+    sigmoid) read the flattened gated rows c, gated by concat(stop_gradient(c), pp) -> a TENSOR [B, num_tasks,
+    poso_mlp_units[-1]] (tf.stack(axis=1)), not a dict.
+    Kept as the reference has it: the EPNet input is built from ``ppnet_input_features`` a second time (:439), so
+    ``epnet_input_features`` is stored and never read (a batch needs no such keys); no gradient reaches c, the main
+    ids' rows or the EPNet gates through the towers' gate input; with ``chain_layers=False`` every tower layer reads c
+    and only the last one reaches the output (see PosoForMLPLayer; ``chain_layers=True`` is the extension described
+    there).  The lookup, the EPNet gates and the product are one kernel each way (functional.EmbEPNetLookup), whose
+    output is both the towers' main input (its leading F E columns) and their gate input; the towers are one kernel
+    each way (functional.PosoMLP)."""
+
+    def __init__(self, categorical_features=_MMOE_CAT, ppnet_input_features=_PEPNET_PP,
+                 epnet_input_features=_PEPNET_EP, feature_dims=160000, embedding_dims=8, gate_hidden_dim=16,
+                 num_tasks=3, poso_mlp_units=[64, 16, 1], chain_layers=False):
+        super().__init__()
+        self.categorical_features = list(categorical_features)
+        self.ppnet_input_features = list(ppnet_input_features)
+        self.epnet_input_features = list(epnet_input_features)      # stored, never read: as the reference
+        self.embedding_dims, self.gate_hidden_dim = int(embedding_dims), int(gate_hidden_dim)
+        self.num_tasks, self.chain_layers = int(num_tasks), bool(chain_layers)
+        self.poso_mlp_units = [int(u) for u in poso_mlp_units]
+        if len(self.poso_mlp_units) != 3:
+            raise ValueError("PEPNetLayer fixes three activations (relu, relu, sigmoid): poso_mlp_units needs three "
+                             "widths, got %s" % (self.poso_mlp_units,))
+        F, P, E = len(self.categorical_features), len(self.ppnet_input_features), self.embedding_dims
+        ops.pepnet_check_shape(F, P, E, self.gate_hidden_dim, self.num_tasks, self.poso_mlp_units, 2, self.chain_layers)
+        self.embedding_layer = Embedding(feature_dims, E)
+        self.poso_gate_for_embedding = torch.nn.ModuleList(
+            [GateNULayer(self.gate_hidden_dim, E, input_dim=P * E) for _ in range(F)])
+        self.poso_mlp_layers = torch.nn.ModuleList(
+            [PosoForMLPLayer(units=self.poso_mlp_units, activations=["relu", "relu", "sigmoid"], gate_hidden_multiple=2,
+                             norm=None, main_dim=F * E, gate_dim=(F + P) * E, chain_layers=self.chain_layers)
+             for _ in range(self.num_tasks)])
+
+    def packed_epnet_weights(self):
+        """The EPNet gates' parameters stacked over the fields: A [F, P E, Hg], a [F, Hg], Bm [F, Hg, E], bm [F, E]."""
+        gates = [gt.gate.layers for gt in self.poso_gate_for_embedding]
+        stack = torch.stack
+        return (stack([g[0].kernel for g in gates]), stack([g[0].bias for g in gates]),
+                stack([g[1].kernel for g in gates]), stack([g[1].bias for g in gates]))
+
+    def forward(self, inputs):
+        F = len(self.categorical_features)
+        ids = assemble_index(inputs, self.categorical_features + self.ppnet_input_features)
+        flag = ops.new_flag(ids.device) if self.check_ids else None
+        u = Fn.EmbEPNetLookup.apply(self.embedding_layer.embeddings, ids, F, flag, *self.packed_epnet_weights())
+        self._raise_if_oob(flag)
+        tower = self.poso_mlp_layers[0]
+        return Fn.PosoMLP.apply(None, u, tower.live_units(), tower.live_activations(), tower.gate_hidden_multiple,
+                                F * self.embedding_dims, *pack_poso_weights(self.poso_mlp_layers))
+
+    def task_outputs(self, inputs):
+        """[B, num_tasks]: column t is task t's output (a view of forward's tensor); needs poso_mlp_units[-1] == 1."""
+        if self.poso_mlp_units[-1] != 1:
+            raise ValueError("task_outputs needs one output unit per task, poso_mlp_units ends in %d"
+                             % self.poso_mlp_units[-1])
+        return self.forward(inputs)[:, :, 0]
 
 
 # ---------------------------------------------------------------------------------------------------

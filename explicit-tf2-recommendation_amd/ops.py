@@ -2289,3 +2289,184 @@ def dmr_bwd(embed, series, negatives, xi, q, P, We, z, g_i2i=None, g_u2i=None, g
         _call_ws("rec_dmr_scratch_bytes", (B, T, E, Cn, H, Nn), "rec_dmr_bwd_f32", dev, *args, _ptr(g_i2i), _ptr(g_u2i),
                  _ptr(g_aux), _ptr(gkeys), _ptr(gneg), _ptr(gitem), _ptr(gq), _ptr(dP), _ptr(dWe), _ptr(dz))
     return gkeys, gneg, gitem, gq, dP, dWe, dz
+
+
+# ---- PEPNet: the lookup fused with the EPNet gates (csrc/epnet.hip) and the T gated MLPs of the towers, one launch each
+# way (csrc/poso.hip).  The limits are MaskNet's: a gate's hidden width is held to MAX_E, tasks and chained layers to
+# MAX_R.
+EPNET_MAX_HG, POSO_MAX_T, POSO_MAX_L = MASKNET_MAX_E, MASKNET_MAX_R, MASKNET_MAX_R
+_POSO_LDS_CAP = 156 * 1024
+_POSO_ACTS = (ACT_NONE, ACT_RELU, ACT_SIGMOID)
+
+
+def _even(n):
+    return (n + 1) & ~1
+
+
+def epnet_check_shape(F, P, E, Hg=16):
+    """ValueError for sizes that describe no EPNet lookup, NotImplementedError for shapes the kernel does not cover (the
+    ABI would return -2): F main fields, P personalisation fields, embedding width E, gate hidden width Hg."""
+    if min(F, P, E, Hg) < 1:
+        raise ValueError("every size of an EPNet lookup must be positive, got fields=%d, ppnet fields=%d, "
+                         "embedding_dims=%d, gate_hidden_dim=%d" % (F, P, E, Hg))
+    if (F > MASKNET_MAX_F or E > MASKNET_MAX_E or Hg > EPNET_MAX_HG or P * E > MASKNET_MAX_O
+            or (F + P) * E > MASKNET_MAX_D):
+        raise NotImplementedError(
+            "EPNet kernels cover fields <= %d, embedding_dims <= %d, gate_hidden_dim <= %d, ppnet fields * embedding_dims "
+            "<= %d and (fields + ppnet fields) * embedding_dims <= %d; got fields=%d, embedding_dims=%d, "
+            "gate_hidden_dim=%d, ppnet fields * embedding_dims=%d, (fields + ppnet fields) * embedding_dims=%d"
+            % (MASKNET_MAX_F, MASKNET_MAX_E, EPNET_MAX_HG, MASKNET_MAX_O, MASKNET_MAX_D, F, E, Hg, P * E, (F + P) * E))
+
+
+def poso_mlp_check_shape(Dm, Dg, T, units, m=2):
+    """ValueError for sizes that describe no POSO-MLP, NotImplementedError for shapes the kernel does not cover (the ABI
+    would return -2): main and gate input widths, T tasks, the widths of the chained layers, gate_hidden_multiple."""
+    units = [int(u) for u in units]
+    if min([Dm, Dg, T, m, len(units)] + units) < 1:
+        raise ValueError("every size of a POSO-MLP must be positive, got main=%d, gate=%d, tasks=%d, units=%s, "
+                         "gate_hidden_multiple=%d" % (Dm, Dg, T, units, m))
+    L, Um = len(units), max(units)
+    lds = 132 * (_even(Dg) + max(_even(m * Um), _even(Dm)) + (2 if L > 1 else 1) * _even(Um))
+    if (T > POSO_MAX_T or L > POSO_MAX_L or Um > MASKNET_MAX_O or m * Um > MASKNET_MAX_P
+            or max(Dm, Dg) > MASKNET_MAX_D or lds > _POSO_LDS_CAP):
+        raise NotImplementedError(
+            "POSO-MLP kernels cover tasks <= %d, layers <= %d, units <= %d, gate_hidden_multiple * units <= %d, input "
+            "widths <= %d and a tile of %d bytes of LDS; got tasks=%d, units=%s, gate_hidden_multiple=%d, main=%d, "
+            "gate=%d, a tile of %d bytes" % (POSO_MAX_T, POSO_MAX_L, MASKNET_MAX_O, MASKNET_MAX_P, MASKNET_MAX_D,
+                                            _POSO_LDS_CAP, T, units, m, Dm, Dg, lds))
+
+
+def pepnet_check_shape(F, P, E, Hg=16, T=3, units=(64, 16, 1), m=2, chain_layers=False):
+    """Both kernels of a PEPNet of F main and P personalisation fields of width E: the EPNet lookup and the T towers
+    (the last layer alone unless ``chain_layers``) over its output."""
+    epnet_check_shape(F, P, E, Hg)
+    poso_mlp_check_shape(F * E, (F + P) * E, T, list(units) if chain_layers else list(units)[-1:], m)
+
+
+def _epnet_args(table, ids, F, A, a, Bm, bm):
+    _table(table, "table")
+    if _i64(ids, "ids").dim() != 2:
+        raise ValueError("ids must be [B, fields + ppnet fields], got %s" % (tuple(ids.shape),))
+    for t, name, dim in ((A, "A", 3), (a, "a", 2), (Bm, "Bm", 3), (bm, "bm", 2)):
+        if _f32(t, name).dim() != dim:
+            raise ValueError("%s must be %d-D, got %s" % (name, dim, tuple(t.shape)))
+    B, FP = ids.shape
+    V, E = table.shape
+    P = FP - int(F)
+    Hg = A.shape[2]
+    if (P < 1 or tuple(A.shape) != (F, P * E, Hg) or tuple(a.shape) != (F, Hg) or tuple(Bm.shape) != (F, Hg, E)
+            or tuple(bm.shape) != (F, E)):
+        raise ValueError("an EPNet lookup takes ids [B,F+P] with P >= 1, A [F,P E,Hg], a [F,Hg], Bm [F,Hg,E], bm [F,E]; "
+                         "got F=%d and %s" % (F, ", ".join(str(tuple(t.shape)) for t in (ids, A, a, Bm, bm))))
+    epnet_check_shape(F, P, E, Hg)
+    return B, V, E, P, Hg
+
+
+def epnet_lookup_fwd(table, ids, F, A, a, Bm, bm, oob=None):
+    """ids [B, F + P] into one table [V, E] -> u [B, (F + P) E]: the F main rows scaled by their GateNU of the P
+    personalisation rows, then those rows raw (include/mi355rec.h).  An id out of range reads row 0 and sets ``oob``."""
+    B, V, E, P, Hg = _epnet_args(table, ids, F, A, a, Bm, bm)
+    u = _new((B, (F + P) * E), table.device, B)
+    if B > 0:
+        _call("rec_epnet_lookup_fwd_f32", _ptr(table), V, table.stride(0), _ptr(ids), *_ptrs((A, a, Bm, bm)), B, F, P, E,
+              Hg, _ptr(u), _ptr(oob))
+    return u
+
+
+def epnet_lookup_bwd(table, ids, F, A, a, Bm, bm, du):
+    """-> (drows [B (F + P), E], the IndexedSlices values of the lookup, (dA, da, dBm, dbm)) from du [B, (F + P) E]; the
+    gates are computed again from the ids."""
+    B, V, E, P, Hg = _epnet_args(table, ids, F, A, a, Bm, bm)
+    _expect_all(((du, (B, (F + P) * E), "du"),))
+    dev = table.device
+    drows = _new((B * (F + P), E), dev, B)
+    grads = [_new_like(t, B) for t in (A, a, Bm, bm)]
+    if B > 0:
+        _call_ws("rec_epnet_lookup_scratch_bytes", (B, F, P, E, Hg), "rec_epnet_lookup_bwd_f32", dev, _ptr(table), V,
+                 table.stride(0), _ptr(ids), *_ptrs((A, a, Bm, bm)), _ptr(du), B, F, P, E, Hg, _ptr(drows),
+                 *_ptrs(grads))
+    return drows, grads
+
+
+_POSO_WEIGHTS = ("Wg1", "bg1", "Wg2", "bg2", "W", "b", "C")
+
+
+def _rows(t, name):
+    """a 2-D fp32 operand on the device whose rows may be strided (a column block of a wider buffer)"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError("%s must be a tensor on the MI355X (got %r): the HIP path has no CPU fallback"
+                           % (name, getattr(t, "device", type(t))))
+    if t.dtype != torch.float32 or t.dim() != 2 or (t.shape[0] > 1 and (t.stride(1) != 1 or t.stride(0) < t.shape[1])):
+        raise ValueError("%s must be a 2-D fp32 tensor with unit inner stride, got %s" % (name, tuple(t.shape)))
+    return t
+
+
+def _poso_args(x, g, w, units, acts, m):
+    """-> (B, Dm, Dg, T, L, units, act codes) of the packed weights ``w`` (in the order of _POSO_WEIGHTS), checked against
+    each other and the limits."""
+    Wg1, bg1, Wg2, bg2, W, b, Cc = w
+    _rows(x, "x"); _rows(g, "g")
+    units = [int(u) for u in units]
+    L = len(units)
+    if len(acts) != L:
+        raise ValueError("a POSO-MLP needs one activation per layer, got %d for %d layers" % (len(acts), L))
+    codes = []
+    for act in acts:
+        code = ACT_CODE.get(act, act) if not isinstance(act, int) else act
+        if code not in _POSO_ACTS:
+            raise NotImplementedError("POSO-MLP kernels cover the activations 'relu', 'sigmoid' and 'linear', got %r"
+                                      % (act,))
+        codes.append(code)
+    if _f32(Cc, "C").dim() != 2 or Cc.shape[1] != L or _f32(Wg1, "Wg1").dim() != 2:
+        raise ValueError("a POSO-MLP takes C [T,L] and Wg1 [Dg,NG]; got %s, %s for %d layers"
+                         % (tuple(Cc.shape), tuple(Wg1.shape), L))
+    B, Dm = x.shape
+    Dg, T = g.shape[1], Cc.shape[0]
+    if g.shape[0] != B:
+        raise ValueError("x and g differ in batch: %s, %s" % (tuple(x.shape), tuple(g.shape)))
+    poso_mlp_check_shape(Dm, Dg, T, units, m)
+    sumU = sum(units)
+    ks = [Dm] + units[:-1]
+    if tuple(Wg1.shape) != (Dg, T * m * sumU):
+        raise ValueError("Wg1 must be [Dg, T m sum(units)] = %s, got %s" % ((Dg, T * m * sumU), tuple(Wg1.shape)))
+    for t, cnt, name in ((bg1, T * m * sumU, "bg1"), (Wg2, T * sum(m * u * u for u in units), "Wg2"),
+                         (bg2, T * sumU, "bg2"), (W, T * sum(k * u for k, u in zip(ks, units)), "W"),
+                         (b, T * sumU, "b")):
+        _vec(t, cnt, name)
+    return B, Dm, Dg, T, L, units, codes
+
+
+def _ld(t):
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+
+def poso_mlp_fwd(x, g, weights, units, acts, m=2, save=True):
+    """T stacked POSO-MLPs of chained layers in one launch: x [B, Dm] and g [B, Dg] (rows may be strided: column blocks
+    of one buffer) -> (out [B, T, units[-1]], saved) with saved = (h [B, NG], gate, d, a [B, T sum(units)]) for the
+    backward, or None (``save=False``: inference, only out is written).  ``weights``: Wg1, bg1, Wg2, bg2, W, b, C as
+    include/mi355rec.h packs them."""
+    B, Dm, Dg, T, L, units, codes = _poso_args(x, g, weights, units, acts, m)
+    dev, sumU = x.device, sum(units)
+    out = _new((B, T, units[-1]), dev, B)
+    saved = tuple(_new((B, w), dev, B) for w in (T * m * sumU, T * sumU, T * sumU, T * sumU)) if save else None
+    if B > 0:
+        _call("rec_poso_mlp_fwd_f32", _ptr(x), _ld(x), _ptr(g), _ld(g), *_ptrs(weights), B, Dm, Dg, T, L, _ints(units),
+              _ints(codes), int(m), _ptr(out), *_ptrs(saved or (None,) * 4))
+    return out, saved
+
+
+def poso_mlp_bwd(x, g, weights, saved, dout, units, acts, m=2):
+    """-> (dx [B, Dm], dg [B, Dg], grads) with grads the gradient of every packed weight, in the order of ``weights``."""
+    B, Dm, Dg, T, L, units, codes = _poso_args(x, g, weights, units, acts, m)
+    sumU = sum(units)
+    shapes = ((B, T * m * sumU),) + ((B, T * sumU),) * 3 + ((B, T, units[-1]),)
+    _expect_all(zip(tuple(saved) + (dout,), shapes, ("h", "gate", "d", "a", "dout")))
+    dev = x.device
+    dx, dg = _new((B, Dm), dev, B), _new((B, Dg), dev, B)
+    grads = [_new_like(t, B) for t in weights]
+    if B > 0:
+        Wg1, _, Wg2, _, W, _, Cc = weights
+        _call_ws("rec_poso_mlp_scratch_bytes", (B, Dm, Dg, T, L, _ints(units), int(m)), "rec_poso_mlp_bwd_f32", dev,
+                 _ptr(x), _ld(x), _ptr(g), _ld(g), *_ptrs((Wg1, Wg2, W, Cc)), *_ptrs(saved), _ptr(dout), B, Dm, Dg, T, L,
+                 _ints(units), _ints(codes), int(m), _ptr(dx), _ptr(dg), *_ptrs(grads))
+    return dx, dg, grads

@@ -1330,6 +1330,71 @@ int rec_dmr_bwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, con
                     const float* g_aux, float* gkeys, float* gneg, float* gitem, float* gq, float* dP, float* dWe,
                     float* dz, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- PEPNet (PEPNetLayer / PosoForMLPLayer / GateNULayer, 10.POSO/CustomLayers.py:76-119, 371-462; csrc/epnet.hip,
+ * csrc/poso.hip).  GateNU(v) = 2 sigmoid(relu(v A + a) Bm + bm).
+ * EPNet lookup.  ids int64 [B, F + P] into ONE table [V, E] with row stride ld: F main ids, then P personalisation ids.
+ * Packed gate weights, row-major: A [F, P E, Hg], a [F, Hg], Bm [F, Hg, E], bm [F, E].  Per example:
+ *   pp = concat_p table[ids[F + p]]  [P E]        gate_f = GateNU_f(pp)  [E]
+ *   u[f E + e] = gate_f[e] table[ids[f]][e]  (f < F)      u[F E + k] = pp[k]                            u [B, (F + P) E]
+ * u is the gate input of the towers below and its leading F E columns their main input.  An id outside [0, V) reads row
+ * 0 and sets *oob_flag (may be NULL).  Nothing is saved: the backward takes du [B, (F + P) E], recomputes the gates from
+ * the ids and writes, never adds to: drows [B, F + P, E], the IndexedSlices values of the lookup (main rows du (.) gate,
+ * pp rows du plus the gradient through all F gates), and dA, da, dBm, dbm, summed over the batch through one slot per
+ * workgroup (at most 256, each walking its tiles of 32 examples in order) and a slot sum in wave order.
+ * Supported (the limits are MaskNet's, this family has no constants of its own): 1 <= F <= REC_MASKNET_MAX_F,
+ * 1 <= E <= REC_MASKNET_MAX_E, 1 <= Hg <= REC_MASKNET_MAX_E, 1 <= P,
+ * P E <= REC_MASKNET_MAX_O, (F + P) E <= REC_MASKNET_MAX_D, 0 <= B < 2^31; otherwise -2.  A size below 1 (B below 0),
+ * V < 1, ld < E or a NULL pointer other than oob_flag: -1.  A workspace that is too small: -3.  workspace (backward
+ * only): rec_epnet_lookup_scratch_bytes: min(ceil(B / 32), 256) slots of F (P E Hg + Hg + Hg E + E) floats (0: invalid
+ * or unsupported shape).
+ * POSO-MLP.  x [B, Dm] with row stride ldx and g [B, Dg] with row stride ldg (both may point into one u); T tasks of L
+ * chained layers of widths U_i = units_host[i] (a HOST int array, as acts_host: REC_ACT_NONE / _RELU / _SIGMOID);
+ * m = gate_hidden_multiple, H_i = m U_i, sumU = sum_i U_i, NG = T m sumU, K_0 = Dm, K_i = U_{i-1}.  Packed weights,
+ * row-major, (t, i) task-major:
+ *   Wg1 [Dg, NG], bg1 [NG]   the first gate layers side by side; the H_i columns of (t, i) start at m (t sumU + sum_{j<i} U_j)
+ *   Wg2   the [H_i, U_i] of every (t, i) one after the other     bg2 [T, sumU]
+ *   W     the [K_i, U_i] of every (t, i) one after the other     b [T, sumU]     C [T, L]
+ * Per example (relu'(0) = 0), a_t,-1 = x:
+ *   h_ti = relu(g Wg1_ti + bg1_ti)   gate_ti = 2 sigmoid(h_ti Wg2_ti + bg2_ti)   d_ti = a_t,i-1 W_ti + b_ti
+ *   a_ti = act_i(C_ti (d_ti (.) gate_ti))          out[:, t, :] = a_t,L-1                            out [B, T, U_{L-1}]
+ * The reference as written (every layer reads x, only the last one is returned) is L = 1 on the last layer's
+ * parameters.  One launch: a workgroup owns 32 examples, every product runs on v_mfma_f32_32x32x2_f32 (fp32-exact).  The
+ * save buffers h [B, NG], gate, d_out, a [B, T sumU] are all given (training) or all NULL (inference: only out is
+ * written; the same out).  The backward takes dout [B, T, U_{L-1}] and the save buffers and writes, never adds to:
+ * dx [B, Dm] and dg [B, Dg] (contiguous, separately: the caller decides what reaches a shared buffer) and the gradient
+ * of every packed weight: one launch for the per-example chain, one slot sum (dbg1, dbg2, db, dC), ONE launch for all dW
+ * and dWg2 over at most 16 batch slices added in order by a second slot sum, and dWg1 = g^T dZ on rec_gemm_f32 (split-K,
+ * slices added in order).  Both only enqueue (no allocation, no host synchronisation: graph-capturable) and use no
+ * float atomics: bit-identical results run to run.  B == 0: nothing is launched.
+ * Supported: 1 <= T <= REC_MASKNET_MAX_R, 1 <= L <= REC_MASKNET_MAX_R, U_i <= REC_MASKNET_MAX_O, m U_i <= REC_MASKNET_MAX_P,
+ * Dm, Dg <= REC_MASKNET_MAX_D, an activation of the three above, 0 <= B < 2^31, and the forward's tile within the LDS of
+ * a CU: 132 (even(Dg) + max(even(m Umax), even(Dm)) + (L > 1 ? 2 : 1) even(Umax)) <= 159744 (every L = 1 shape inside
+ * the limits does; L > 1 with Dg and max(Dm, m Umax) both near 512 does not); otherwise -2.  A size below 1 (B below 0),
+ * ldx < Dm, ldg < Dg, a NULL pointer or save buffers given in part: -1.  A workspace that is too small: -3.  workspace
+ * (backward only): rec_poso_mlp_scratch_bytes: 4 B (NG + 2 T sumU) bytes of per-example gradients, (B / 32) slots of
+ * NG + 2 T sumU + T L floats, at most 16 copies of W and Wg2 and at most 16 of Wg1 (0: invalid or unsupported shape). */
+size_t rec_epnet_lookup_scratch_bytes(int64_t B, int F, int P, int E, int Hg);
+int rec_epnet_lookup_fwd_f32(const float* table, int64_t V, int64_t ld, const int64_t* ids, const float* A,
+                             const float* a, const float* Bm, const float* bm, int64_t B, int F, int P, int E, int Hg,
+                             float* u, int* oob_flag, void* stream);
+int rec_epnet_lookup_bwd_f32(const float* table, int64_t V, int64_t ld, const int64_t* ids, const float* A,
+                             const float* a, const float* Bm, const float* bm, const float* du, int64_t B, int F, int P,
+                             int E, int Hg, float* drows, float* dA, float* da, float* dBm, float* dbm, void* workspace,
+                             size_t workspace_bytes, void* stream);
+size_t rec_poso_mlp_scratch_bytes(int64_t B, int Dm, int Dg, int T, int L, const int* units_host,
+                                    int gate_hidden_multiple);
+int rec_poso_mlp_fwd_f32(const float* x, int64_t ldx, const float* g, int64_t ldg, const float* Wg1, const float* bg1,
+                         const float* Wg2, const float* bg2, const float* W, const float* b, const float* C, int64_t B,
+                         int Dm, int Dg, int T, int L, const int* units_host, const int* acts_host,
+                         int gate_hidden_multiple, float* out, float* h, float* gate, float* d_out, float* a,
+                         void* stream);
+int rec_poso_mlp_bwd_f32(const float* x, int64_t ldx, const float* g, int64_t ldg, const float* Wg1, const float* Wg2,
+                         const float* W, const float* C, const float* h, const float* gate, const float* d_out,
+                         const float* a, const float* dout, int64_t B, int Dm, int Dg, int T, int L,
+                         const int* units_host, const int* acts_host, int gate_hidden_multiple, float* dx, float* dg,
+                         float* dWg1, float* dbg1, float* dWg2, float* dbg2, float* dW, float* db, float* dC,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
