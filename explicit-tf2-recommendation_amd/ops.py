@@ -369,22 +369,41 @@ def bce_fwd_bwd(y, p, want_dp=True, want_dz=False):
 
 
 def adam_dense(var, m, v, g, t, lr, b1=0.9, b2=0.999, eps=1e-7):
-    _call("rec_adam_dense_f32", _ptr(_f32(var, "var")), _ptr(m), _ptr(v), _ptr(_f32(g, "g")), var.numel(), t, lr, b1, b2,
-          eps)
+    """Keras' dense Adam apply on a contiguous parameter of any shape; m, v and g have that shape"""
+    shape = tuple(_f32(var, "var").shape)
+    for x, name in ((m, "m"), (v, "v"), (g, "g")):
+        _expect(x, shape, name, "the shape of var")
+    _call("rec_adam_dense_f32", _ptr(var), _ptr(m), _ptr(v), _ptr(g), var.numel(), t, lr, b1, b2, eps)
+
+
+def _adam_rows_head(var, m, v, uniq_ids, g_rows, n_uniq):
+    """The operands of a sparse Adam step: var a table [V,E] (a strided row view of the fused layout may be), m and v
+    contiguous [V,E], g_rows [cap,E] the gradient rows of the int64 uniq_ids (cap ids or more), of which the int64
+    device scalar n_uniq counts the used ones.  -> (V, E, cap)"""
+    V, E = _table(var, "var").shape
+    _expect(m, (V, E), "m", "[V,E]")
+    _expect(v, (V, E), "v", "[V,E]")
+    if _f32(g_rows, "g_rows").dim() != 2 or g_rows.shape[1] != E:
+        raise ValueError("g_rows must be [cap,E] = (cap, %d), got %s" % (E, tuple(g_rows.shape)))
+    cap = g_rows.shape[0]
+    if _i64(uniq_ids, "uniq_ids").dim() != 1 or uniq_ids.numel() < cap:
+        raise ValueError("uniq_ids must hold the [%d] ids of g_rows or more, got %s" % (cap, tuple(uniq_ids.shape)))
+    if _i64(n_uniq, "n_uniq").numel() != 1:
+        raise ValueError("n_uniq must be one int64 on the device, got %s" % (tuple(n_uniq.shape),))
+    return V, E, cap
 
 
 def adam_sparse_keras(var, m, v, uniq_ids, g_rows, n_uniq, t, lr, b1=0.9, b2=0.999, eps=1e-7):
-    V, E = _table(var, "var").shape
-    cap = g_rows.shape[0]
+    V, E, cap = _adam_rows_head(var, m, v, uniq_ids, g_rows, n_uniq)
     side = _new((cap, 3, E), var.device)                 # the touched rows' new (var, m, v), patched in after the sweep
     _call("rec_adam_sparse_keras_f32", _ptr(var), var.stride(0), _ptr(m), _ptr(v), V, E, _ptr(uniq_ids), _ptr(g_rows),
           _ptr(n_uniq), cap, _ptr(side), t, lr, b1, b2, eps)
 
 
 def adam_rows(var, m, v, uniq_ids, g_rows, n_uniq, t, lr, b1=0.9, b2=0.999, eps=1e-7):
-    V, E = _table(var, "var").shape
+    V, E, cap = _adam_rows_head(var, m, v, uniq_ids, g_rows, n_uniq)
     _call("rec_adam_rows_f32", _ptr(var), var.stride(0), _ptr(m), _ptr(v), V, E, _ptr(uniq_ids), _ptr(g_rows),
-          _ptr(n_uniq), g_rows.shape[0], t, lr, b1, b2, eps)
+          _ptr(n_uniq), cap, t, lr, b1, b2, eps)
 
 
 # ---------------------------------------------------------------------------------------------------
