@@ -1251,3 +1251,106 @@ class PosoMLP(torch.autograd.Function):
             dg[:, :ctx.shared_cols].copy_(dx)             # stop_gradient: the gate path's share of these columns is dropped
             dx = None
         return (dx, dg, None, None, None, None) + tuple(grads)
+
+
+class DienGru(torch.autograd.Function):
+    """DIEN's interest extractor (5.DIN/CustomLayers.py:412, 434-453, 480-502; csrc/dien.hip): the masked
+    tf.keras.layers.GRU (reset_after=True; ``kernel`` [H,3H], ``recurrent_kernel`` [H,3H], ``bias`` [2,3H], gate order
+    z, r, h) fused with the series lookup and, with ``negatives``, the auxiliary loss -> (gru_output [B,T,H], h_final,
+    aux).  Table mode: ``embed`` [V,E], ``series`` and ``negatives`` ids [B,T,C]; gru_output and aux (a scalar; None
+    without negatives) are returned, h_final is None.  Dense mode (``embed`` None): ``x`` [B,T,H] with ``mask_ids``
+    [B,T], DienGRU's AIGRU; only h_final is returned.  One recurrence launch each way; the backward recomputes the gates
+    from the saved gru_output.  With ``sink`` (functional.GradSink) the values of both lookups ride along with the
+    profile lookup's de-duplication and the table's gradient is returned there; ``after`` is then a tensor out of that
+    lookup (the candidate's rows): it is not read and gets no gradient, the edge only makes autograd run this backward
+    before the lookup's, which collects what the sink holds."""
+
+    @staticmethod
+    def forward(ctx, embed, series, negatives, x, mask_ids, kernel, recurrent_kernel, bias, padding_index, oob=None,
+                sink=None, after=None):
+        kernel, recurrent_kernel, bias = kernel.contiguous(), recurrent_kernel.contiguous(), bias.contiguous()
+        table = embed is not None
+        if not table:
+            x = x.contiguous()
+        out, fin, aux = ops.dien_gru_fwd(kernel, recurrent_kernel, bias, embed, series, negatives, x, mask_ids,
+                                         padding_index, oob, want_output=True, want_final=not table)
+        ctx.save_for_backward(embed, series, negatives, x, mask_ids, kernel, recurrent_kernel, bias, out)
+        ctx.padding_index, ctx.sink = padding_index, sink
+        ctx.set_materialize_grads(False)
+        if table:
+            return out, None, (aux.reshape(()) if aux is not None else None)
+        ctx.mark_non_differentiable(out)
+        return out, fin, None
+
+    @staticmethod
+    def backward(ctx, dout, dfin, gaux):
+        embed, series, negatives, x, mask_ids, kernel, recurrent_kernel, bias, out = ctx.saved_tensors
+        c = lambda g: None if g is None else g.contiguous()
+        table = embed is not None
+        sink, buf, dk, dn = ctx.sink, None, None, None
+        if table:
+            V, E = embed.shape
+            B, T, H = out.shape
+            n_ser = series.numel()
+            n_neg = negatives.numel() if negatives is not None else 0
+            if sink is not None:                             # values land behind the Gather's rows in one shared buffer
+                buf = sink.new_buf(n_ser + n_neg, E, embed.device)
+                dk = buf[sink.n_head:sink.n_head + n_ser].view(B, T, H)
+                if n_neg:
+                    dn = buf[sink.n_head + n_ser:sink.n_head + n_ser + n_neg].view(B, T, H)
+        gaux = None if gaux is None else c(gaux).reshape(1)
+        dx, dneg, dK, dU, db = ops.dien_gru_bwd(kernel, recurrent_kernel, bias, out, None if not table else c(dout),
+                                                c(dfin), gaux, embed, series, negatives, x, mask_ids,
+                                                ctx.padding_index, dx=dk, dneg=dn)
+        gembed = None
+        if table:
+            ids = series.reshape(-1) if negatives is None else torch.cat([series.reshape(-1), negatives.reshape(-1)])
+            if sink is not None:
+                sink.ids, sink.buf = ids, buf
+            elif ctx.needs_input_grad[0]:
+                vals = dx.reshape(-1, E) if negatives is None else torch.cat([dx.reshape(-1, E), dneg.reshape(-1, E)])
+                gembed = _sparse_grad(ops.DedupPlan(ids, V), vals, E, (V, E))
+        return gembed, None, None, (None if table else dx), None, dK, dU, db, None, None, None, None
+
+
+class DienAugru(torch.autograd.Function):
+    """DienActivationLayer and DienGRU's AGRU / AUGRU (5.DIN/CustomLayers.py:292-386; csrc/dien.hip): gru_output
+    [B,T,H], the candidate's rows X_item [B,H], the bilinear W [H,H], the mask ids ([B,T] or the series ids [B,T,C]) and
+    CustomGRUCell's weights -> (evolved interest [B,H], scores [B,T]).  q = X_item W^T is a GEMM here, the scores and
+    the recurrence one launch each way; the backward recomputes the gates from the saved states.  The scores are
+    returned for inspection and carry no gradient of their own."""
+
+    @staticmethod
+    def forward(ctx, gru_output, X_item, W, mask_ids, mode, padding_index, mask_valid, W_r, U_r, b_r, W_h, U_h, b_h,
+                W_z=None, U_z=None, b_z=None):
+        gru_output, X_item, W = gru_output.contiguous(), X_item.contiguous(), W.contiguous()
+        if mode == ops.DIEN_AUGRU:
+            Wx, Uh, bx = torch.cat([W_z, W_r, W_h], 1), torch.cat([U_z, U_r, U_h], 1), torch.cat([b_z, b_r, b_h])
+        else:
+            Wx, Uh, bx = torch.cat([W_r, W_h], 1), torch.cat([U_r, U_h], 1), torch.cat([b_r, b_h])
+        q = ops.gemm(X_item, W, transB=True)
+        train = any(ctx.needs_input_grad)
+        scores, states, fin = ops.dien_augru_fwd(gru_output, q, mask_ids, mode, Wx, Uh, bx, padding_index, mask_valid,
+                                                 save=train)
+        if train:
+            ctx.save_for_backward(gru_output, X_item, W, mask_ids, Wx, Uh, bx, q, scores, states)
+        ctx.cfg = (mode, padding_index, mask_valid)
+        ctx.mark_non_differentiable(scores)
+        return fin, scores
+
+    @staticmethod
+    def backward(ctx, dfin, _dscores):
+        gru_output, X_item, W, mask_ids, Wx, Uh, bx, q, scores, states = ctx.saved_tensors
+        mode, padding_index, mask_valid = ctx.cfg
+        H = X_item.shape[1]
+        dg, dq, dWx, dUh, dbx = ops.dien_augru_bwd(gru_output, q, mask_ids, mode, Wx, Uh, bx, scores, states,
+                                                   dfin.contiguous(), padding_index, mask_valid)
+        dX_item = ops.gemm(dq, W)
+        dW = ops.gemm(dq, X_item, transA=True)
+        o = H if mode == ops.DIEN_AUGRU else 0               # the packed blocks: [z | r | h], AGRU [r | h]
+        cell = (dWx[:, o:o + H], dUh[:, o:o + H], dbx[o:o + H], dWx[:, o + H:], dUh[:, o + H:], dbx[o + H:])
+        if mode == ops.DIEN_AUGRU:
+            cell = cell + (dWx[:, :H], dUh[:, :H], dbx[:H])
+        else:
+            cell = cell + (None, None, None)
+        return (dg, dX_item, dW, None, None, None, None) + cell

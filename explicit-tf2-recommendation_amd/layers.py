@@ -54,6 +54,10 @@ libmi355rec.so (through functional.py / ops.py).  Reference classes and the line
   FinalMLPLayer                 8.DMR/CustomLayers.py:319-387
   FeatureSelectionLayer         8.DMR/CustomLayers.py:390-414
   DualPartsInteractionLayer     8.DMR/CustomLayers.py:416-442
+  DienActivationLayer           5.DIN/CustomLayers.py:292-317
+  CustomGRUCell                 5.DIN/CustomLayers.py:320-359
+  DienGRU                       5.DIN/CustomLayers.py:362-386
+  DIENLayer                     5.DIN/CustomLayers.py:389-517   (GRU: the Keras-named weights of tf.keras.layers.GRU)
 
 Parameters are named after the TF checkpoint keys (``embed.embeddings``, ``w.embeddings``, ``bias``,
 ``MLP_layer1.kernel_0`` ...), so a TensorBundle checkpoint maps onto ``state_dict()`` by name.
@@ -3081,3 +3085,254 @@ class DMRLayer(Layer):
         self._raise_if_oob(flag)
         X_combined = ConcatCols.apply(profile_output, i2i_vector, u2i_vector)
         return {"output": self.mlp(X_combined), "auxiliary_loss": auxiliary_loss}
+
+
+# ---------------------------------------------------------------------------------------------------
+# DIEN (5.DIN/CustomLayers.py:292-517): interest extractor, auxiliary loss, attention scores, interest evolution
+# ---------------------------------------------------------------------------------------------------
+
+def orthogonal(shape):
+    """tf.keras.initializers.Orthogonal(): the Q of a normal matrix's QR decomposition, signs fixed by R's diagonal"""
+    rows, cols = shape
+    a = torch.randn((max(rows, cols), min(rows, cols)), generator=_init_gen)
+    qm, r = torch.linalg.qr(a)
+    qm = qm * torch.sign(torch.diagonal(r))[None, :]
+    return (qm if rows >= cols else qm.t()).contiguous()
+
+
+class GRU(Layer):
+    """The weights of tf.keras.layers.GRU(units) under their Keras names -- ``kernel`` [input_dim, 3 units] (Glorot
+    uniform), ``recurrent_kernel`` [units, 3 units] (orthogonal), ``bias`` [2, 3 units] (zeros; reset_after=True), gate
+    order z, r, h -- and the composed recurrence in torch: ``forward(x, mask)`` returns every state [B,T,units]; where
+    the mask is false the state is carried and is the output of that step (zero before the first valid step).
+    DIENLayer runs these weights through csrc/dien.hip instead."""
+
+    def __init__(self, units, input_dim=None):
+        super().__init__()
+        if input_dim is None:
+            raise ValueError("GRU needs input_dim")
+        self.units = units
+        self.kernel = torch.nn.Parameter(glorot_uniform((input_dim, 3 * units)))
+        self.recurrent_kernel = torch.nn.Parameter(orthogonal((units, 3 * units)))
+        self.bias = torch.nn.Parameter(torch.zeros((2, 3 * units)))
+
+    def forward(self, x, mask=None):
+        B, T, _ = x.shape
+        H = self.units
+        h = x.new_zeros((B, H))
+        outs = []
+        for t in range(T):
+            xi = x[:, t] @ self.kernel + self.bias[0]
+            hi = h @ self.recurrent_kernel + self.bias[1]
+            z = torch.sigmoid(xi[:, :H] + hi[:, :H])
+            r = torch.sigmoid(xi[:, H:2 * H] + hi[:, H:2 * H])
+            hh = torch.tanh(xi[:, 2 * H:] + r * hi[:, 2 * H:])
+            hn = z * h + (1 - z) * hh
+            h = hn if mask is None else torch.where(mask[:, t, None], hn, h)
+            outs.append(h)
+        return torch.stack(outs, 1)
+
+
+class DienActivationLayer(Layer):
+    """5.DIN/CustomLayers.py:292-317: scores = exp((gru_output W) . X_item) (.) ~mask over their row sum, NaN -> 0 -- as
+    written the positions the mask passed in marks FALSE score, and DIENLayer passes the valid mask (see its
+    ``mask_mode``).  A row with nothing selected scores zeros and sends no gradient through the scores (TensorFlow's
+    gradient of the 0 / 0 would be NaN).  ``forward`` is the composed path; DIENLayer fuses it with the evolution."""
+
+    def __init__(self, embedding_dims1, embedding_dims2=None, **kwargs):
+        super().__init__()
+        if not embedding_dims2:
+            embedding_dims2 = embedding_dims1
+        self.W = torch.nn.Parameter(torch.randn((embedding_dims2, embedding_dims1), generator=_init_gen) * 0.05)
+
+    def forward(self, inputs):
+        gru_output, X_item, mask = inputs
+        product = ((gru_output @ self.W) * X_item[:, None, :]).sum(-1)
+        masked = torch.exp(product) * (~mask).to(product.dtype)
+        denominator = masked.sum(-1, keepdim=True)
+        return masked / torch.where(denominator > 0, denominator, torch.ones_like(denominator))
+
+
+class CustomGRUCell(Layer):
+    """5.DIN/CustomLayers.py:320-359: one step of the attention GRU on inputs [x | a].  The inner GRUCell the reference
+    creates is never built and owns no weights: it has no counterpart here.  ``units`` doubles as the input width."""
+
+    def __init__(self, units, mode, **kwargs):
+        super().__init__()
+        self.units = units
+        self.mode = mode
+        self.state_size = units
+        for g in ("r", "h") + (("z",) if mode == "AUGRU" else ()):
+            setattr(self, "W_" + g, torch.nn.Parameter(glorot_uniform((units, units))))
+            setattr(self, "U_" + g, torch.nn.Parameter(glorot_uniform((units, units))))
+            setattr(self, "b_" + g, torch.nn.Parameter(torch.zeros(units)))
+
+    def forward(self, inputs, states):
+        h_prev = states[0]
+        x = inputs[:, :self.units]
+        a = inputs[:, self.units:]
+        r = torch.sigmoid(x @ self.W_r + h_prev @ self.U_r + self.b_r)
+        h_tilda = torch.tanh(x @ self.W_h + r * (h_prev @ self.U_h) + self.b_h)
+        if self.mode == "AGRU":
+            h = (1 - a) * h_prev + a * h_tilda
+        elif self.mode == "AUGRU":
+            u = torch.sigmoid(x @ self.W_z + h_prev @ self.U_z + self.b_z)
+            u_hat = a * u
+            h = (1 - u_hat) * h_prev + u_hat * h_tilda
+        return h, [h]
+
+    def weights(self):
+        names = ("W_r", "U_r", "b_r", "W_h", "U_h", "b_h") + (("W_z", "U_z", "b_z") if self.mode == "AUGRU" else ())
+        return [getattr(self, n) for n in names]
+
+
+class DienGRU(Layer):
+    """5.DIN/CustomLayers.py:362-386: the interest evolution over (gru_output, activation_scores) under the valid mask
+    (a masked step carries the state) -> the final state [B, units].  AIGRU: a second Keras GRU on gru_output (.) scores;
+    AGRU / AUGRU: CustomGRUCell.  ``forward`` is the composed path in torch; ``evolve`` is the fused one: scores and
+    recurrence in one launch each way (csrc/dien.hip; AIGRU: the scores composed from the existing ops, then the dense
+    mode of the GRU kernels)."""
+
+    def __init__(self, units, mode, **kwargs):
+        super().__init__()
+        self.units = units
+        self.mode = mode
+        if mode == "AIGRU":
+            self.gru = GRU(units, input_dim=units)
+        elif mode in ["AGRU", "AUGRU"]:
+            self.gru_cell = CustomGRUCell(units, mode)
+
+    def forward(self, inputs, valid_mask):
+        gru_input, activation_scores = inputs
+        if self.mode == "AIGRU":
+            return self.gru(gru_input * activation_scores[:, :, None], mask=valid_mask)[:, -1]
+        x = torch.cat([gru_input, activation_scores[:, :, None]], dim=-1)
+        h = gru_input.new_zeros((gru_input.shape[0], self.units))
+        for t in range(gru_input.shape[1]):
+            hn, _ = self.gru_cell(x[:, t], [h])
+            h = torch.where(valid_mask[:, t, None], hn, h)
+        return h
+
+    def evolve(self, gru_output, X_item, activation, series, padding_index, mask_valid):
+        """gru_output [B,T,H], the candidate's rows [B,H], the DienActivationLayer and the series ids [B,T,C]"""
+        if self.mode == "AIGRU":
+            valid = series[:, :, 0] != padding_index
+            scores = activation((gru_output, X_item, valid if mask_valid == 0 else ~valid))
+            _, final, _ = Fn.DienGru.apply(None, None, None, gru_output * scores[:, :, None],
+                                           series[:, :, 0].contiguous(), self.gru.kernel, self.gru.recurrent_kernel,
+                                           self.gru.bias, padding_index)
+            return final
+        final, _ = Fn.DienAugru.apply(gru_output, X_item, activation.W, series, ops.DIEN_MODE[self.mode], padding_index,
+                                      mask_valid, *self.gru_cell.weights())
+        return final
+
+
+class DIENLayer(Layer):
+    """5.DIN/CustomLayers.py:389-517, Deep Interest Evolution Network: the profile rows and the evolved interest into
+    make_mlp_layer([200, 80], softmax_units=2).  The interest extractor is a masked Keras GRU over the looked-up
+    behaviour series (``gru``); in stage 'train' its states are scored against the next behaviour and a sampled negative
+    (``auxiliary_loss``, a scalar summed over the batch, oddities kept: p and n pass through a sigmoid BEFORE the
+    sigmoid cross entropy; 0, a Python number, in stage 'inference', which never reads the negative features);
+    DienActivationLayer scores the states against the candidate and DienGRU evolves them.  ``forward`` returns
+    ``{'X_combined', 'output', 'auxiliary_loss'}``; the reference nowhere adds the auxiliary loss to its training loss
+    (INTEGRATION.md shows how to).
+    ``mask_mode`` (extension, as DINLayer's): 'reference' keeps the activation's mask as written -- only PADDED positions
+    score.  With AGRU / AUGRU every valid step then has a = 0 and every padded step is skipped, so the evolved interest
+    is exactly zero whatever the weights, and ``dien_activation_layer.W`` and the cell get exactly zero gradient;
+    'valid' scores the valid positions.  ``fused`` (extension): True runs csrc/dien.hip -- series lookup + GRU + auxiliary
+    loss in one launch each way, scores + AGRU / AUGRU in another -- and one profile lookup serves ``profile`` and the
+    candidate's rows, its de-duplication shared with the series and negative lookups; False composes the sub-layers in
+    torch."""
+
+    def __init__(self, user_and_context_categorical_features=["uid", "utag1", "utag2", "utag3", "utag4"],
+                 item_categorical_features=["i_goods_id", "i_shop_id", "i_cate_id"],
+                 behavior_series_features=["visited_goods_ids", "visited_shop_ids", "visited_cate_ids"],
+                 negative_sample_features=["negative_goods_ids", "negative_shop_ids", "negative_cate_ids"],
+                 feature_dims=160000, embedding_dims=16, activation="Dice", padding_index=0, mode="AUGRU", stage="train",
+                 mask_mode="reference", fused=True):
+        super().__init__()
+        self.user_and_context_categorical_features = user_and_context_categorical_features
+        self.item_categorical_features = item_categorical_features
+        assert len(item_categorical_features) == len(behavior_series_features) == len(negative_sample_features), \
+            "Features to be interacted should match in item and behavior/negative series"
+        self.behavior_series_features = behavior_series_features
+        self.negative_sample_features = negative_sample_features
+        self.feature_dims = feature_dims
+        self.embedding_dims = embedding_dims
+        if mask_mode not in ("reference", "valid"):
+            raise ValueError("mask_mode must be 'reference' or 'valid'")
+        self.mask_mode = mask_mode
+        H = len(behavior_series_features) * embedding_dims
+        ops.dien_check_shape(H)
+        self.embed = Embedding(feature_dims, embedding_dims)
+        self.gru = GRU(H, input_dim=H)
+        self.dien_activation_layer = DienActivationLayer(embedding_dims1=H)
+        assert mode in ("AIGRU", "AGRU", "AUGRU")
+        self.mode = mode
+        self.dien_gru = DienGRU(H, mode)
+        n_profile = len(user_and_context_categorical_features) + len(item_categorical_features)
+        self.mlp = make_mlp_layer([200, 80], activation=activation, softmax_units=2,
+                                  input_dim=n_profile * embedding_dims + H)
+        self.padding_index = padding_index
+        self.stage = stage
+        self.fused = fused
+
+    def set_stage(self, stage):
+        assert stage in ("train", "inference")
+        self.stage = stage
+
+    def get_auxiliary_loss(self, X_series, gru_output, X_negative, valid_mask):
+        X_series, gru_output, X_negative = X_series[:, :-1], gru_output[:, 1:], X_negative[:, 1:]
+        pos_logits = torch.sigmoid((X_series * gru_output).sum(-1))
+        neg_logits = torch.sigmoid((X_series * X_negative).sum(-1))
+        sce = lambda v, label: torch.clamp(v, min=0) - v * label + torch.log1p(torch.exp(-v.abs()))
+        mask = valid_mask[:, 1:].to(X_series.dtype)
+        return (sce(pos_logits, 1.0) * mask).sum() + (sce(neg_logits, 0.0) * mask).sum()
+
+    def body(self, X_series, X_negative, X_item, valid_mask):
+        """The composed layer between the lookups and the MLP, in torch (any device): X_series [B,T,H], X_negative
+        [B,T,H] or None (stage 'inference'), X_item [B,H], valid_mask [B,T] -> (evolved interest [B,H], auxiliary loss)"""
+        gru_output = self.gru(X_series, mask=valid_mask)
+        if self.stage == "train":
+            auxiliary_loss = self.get_auxiliary_loss(X_series, gru_output, X_negative, valid_mask)
+        else:
+            auxiliary_loss = 0
+        mask = valid_mask if self.mask_mode == "reference" else ~valid_mask
+        activation_scores = self.dien_activation_layer((gru_output, X_item, mask))
+        return self.dien_gru((gru_output, activation_scores), valid_mask), auxiliary_loss
+
+    def forward(self, inputs):
+        prof_names = self.user_and_context_categorical_features + self.item_categorical_features
+        X_cate = assemble_index(inputs, prof_names)
+        dev = X_cate.device
+        series = _stack_ids(inputs, self.behavior_series_features, dev)
+        train = self.stage == "train"
+        negatives = _stack_ids(inputs, self.negative_sample_features, dev) if train else None
+        B, T, Cn = series.shape
+        if negatives is not None and tuple(negatives.shape) != (B, T, Cn):
+            raise ValueError("the negative samples must have the behaviour series' shape %s, got %s"
+                             % ((B, T), tuple(negatives.shape[:2])))
+        ops.dien_check_shape(Cn * self.embedding_dims, T, ops.DIEN_MODE.get(self.mode))
+        flag = ops.new_flag(dev) if self.check_ids else None
+        n_item = len(self.item_categorical_features)
+        # one lookup serves both: the candidate item's rows are the tail of the profile rows (the reference looks the item
+        # ids up a second time, :471-478 -- same values)
+        sink = self.embed.grad_sink(X_cate) if self.fused else None
+        profile = self.embed(X_cate, flag, sink)
+        profile_output = profile.reshape(B, -1)
+        X_item = profile[:, profile.shape[1] - n_item:, :].reshape(B, -1)
+        if self.fused:
+            mask_valid = 1 if self.mask_mode == "valid" else 0
+            gru_output, _, aux = Fn.DienGru.apply(self.embed.embeddings, series, negatives, None, None, self.gru.kernel,
+                                                  self.gru.recurrent_kernel, self.gru.bias, self.padding_index, flag,
+                                                  sink, X_item)
+            auxiliary_loss = aux if train else 0
+            evolved = self.dien_gru.evolve(gru_output, X_item, self.dien_activation_layer, series, self.padding_index,
+                                           mask_valid)
+        else:
+            X_series = self.embed(series.reshape(B, T * Cn), flag).reshape(B, T, -1)
+            X_negative = self.embed(negatives.reshape(B, T * Cn), flag).reshape(B, T, -1) if train else None
+            evolved, auxiliary_loss = self.body(X_series, X_negative, X_item, series[:, :, 0] != self.padding_index)
+        self._raise_if_oob(flag)
+        X_combined = ConcatCols.apply(profile_output, evolved)
+        return {"X_combined": X_combined, "output": self.mlp(X_combined), "auxiliary_loss": auxiliary_loss}

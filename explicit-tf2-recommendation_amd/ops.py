@@ -2489,3 +2489,154 @@ def poso_mlp_bwd(x, g, weights, saved, dout, units, acts, m=2):
                  _ptr(x), _ld(x), _ptr(g), _ld(g), *_ptrs((Wg1, Wg2, W, Cc)), *_ptrs(saved), _ptr(dout), B, Dm, Dg, T, L,
                  _ints(units), _ints(codes), int(m), _ptr(dx), _ptr(dg), *_ptrs(grads))
     return dx, dg, grads
+
+
+# ---- DIEN: the masked Keras GRU of the interest extractor fused with the series / negative lookups and the auxiliary
+# loss, and the attention scores fused with the AGRU / AUGRU of the interest evolution (csrc/dien.hip).  Every width is
+# H = E C, held to DIN's wide key width; the LDS fit is the header's formula.
+DIEN_AUGRU, DIEN_AGRU = 1, 2
+DIEN_MODE = {"AUGRU": DIEN_AUGRU, "AGRU": DIEN_AGRU}
+
+
+def dien_lds_bytes(T, H, mode=None):
+    """LDS of a tile of 32 examples (include/mi355rec.h): the extractor (``mode`` None) or the evolution"""
+    He = _even(H)
+    if mode is None:
+        return 132 * 8 * He + 512
+    return 132 * ((7 if mode == DIEN_AUGRU else 6) * He + 2 * T) + 512
+
+
+def dien_check_shape(H, T=None, mode=None):
+    """ValueError for sizes that describe no DIEN body, NotImplementedError naming the limit for shapes the kernels do
+    not cover (the ABI would return -2): the width H = E C of the series rows and of both recurrences, the series length
+    T and -- for the evolution -- ``mode`` (DIEN_AUGRU / DIEN_AGRU)."""
+    if min([H] + ([T] if T is not None else [])) < 1:
+        raise ValueError("every size of a DIEN body must be positive, got H=%d, T=%r" % (H, T))
+    if mode not in (None, DIEN_AUGRU, DIEN_AGRU):
+        raise ValueError("the evolution's mode must be DIEN_AUGRU or DIEN_AGRU, got %r" % (mode,))
+    if H > DIN_WIDE_D:
+        raise NotImplementedError("DIEN kernels cover a width embedding_dims * series features <= %d; got %d"
+                                  % (DIN_WIDE_D, H))
+    if T is not None:
+        _lds_fit(dien_lds_bytes(T, H, mode), "DIEN holds a tile of 32 examples",
+                 "33 (8 He)" if mode is None else "33 ((7 or 6) He + 2 T) + 128", "T=%d, H=%d" % (T, H))
+
+
+def _dien_gru_args(embed, series, negatives, x, mask_ids, kernel, recurrent_kernel, bias, padding_index):
+    """the leading ABI arguments of rec_dien_gru_* and (B, T, H, V, E, C): table mode (embed, series [B,T,C] and
+    optionally negatives [B,T,C]) or dense mode (x [B,T,H], mask_ids [B,T])"""
+    if (embed is None) == (x is None):
+        raise ValueError("a DIEN GRU takes a table with series ids, or dense rows x with mask ids, not both")
+    if embed is not None:
+        head, (V, E, B, T, Cn) = _series_head(embed, series, "DIEN GRU")
+        H = Cn * E
+        if negatives is not None:
+            _expect(negatives, (B, T, Cn), "negatives", "[B,T,C]", dtype=torch.int64)
+        lead = head[:6] + [_ptr(negatives), None, None, B, T, H]
+    else:
+        if negatives is not None or series is not None:
+            raise ValueError("the dense mode of a DIEN GRU takes no series or negative ids")
+        if _f32(x, "x").dim() != 3:
+            raise ValueError("x must be [B,T,H], got %s" % (tuple(x.shape),))
+        B, T, H = x.shape
+        _expect(mask_ids, (B, T), "mask_ids", "[B,T]", dtype=torch.int64)
+        V, E, Cn = 0, 1, 1
+        lead = [None, 0, 0, 1, 1, None, None, _ptr(x), _ptr(mask_ids), B, T, H]
+    _expect_all(((kernel, (H, 3 * H), "kernel"), (recurrent_kernel, (H, 3 * H), "recurrent_kernel"),
+                 (bias, (2, 3 * H), "bias")))
+    dien_check_shape(H, T)
+    return lead + [_ptr(kernel), _ptr(recurrent_kernel), _ptr(bias), int(padding_index)], (B, T, H, V, E, Cn)
+
+
+def dien_gru_fwd(kernel, recurrent_kernel, bias, embed=None, series=None, negatives=None, x=None, mask_ids=None,
+                 padding_index=0, oob=None, want_output=True, want_final=False):
+    """The masked Keras GRU (reset_after=True, gate order z, r, h; the state is carried where the mask id equals
+    ``padding_index``) over the looked-up series (``embed`` [V,E], ``series`` ids [B,T,C]) or over dense rows ``x``
+    [B,T,H] with ``mask_ids`` [B,T] -> (gru_output [B,T,H] or None, h_final [B,H] or None, aux [1] or None); with
+    ``negatives`` [B,T,C] aux is the auxiliary loss summed over the batch.  One launch (plus the slot sum of aux)."""
+    args, (B, T, H, V, E, Cn) = _dien_gru_args(embed, series, negatives, x, mask_ids, kernel, recurrent_kernel, bias,
+                                               padding_index)
+    if not (want_output or want_final):
+        raise ValueError("a DIEN GRU returns gru_output, h_final or both")
+    dev = kernel.device
+    out = _new((B, T, H), dev, B) if want_output else None
+    fin = _new((B, H), dev, B) if want_final else None
+    aux = torch.zeros((1,), dtype=torch.float32, device=dev) if negatives is not None else None
+    if B > 0:
+        tail = (_ptr(out), _ptr(fin), _ptr(aux), _ptr(oob))
+        if negatives is not None:
+            _call_ws("rec_dien_gru_scratch_bytes", (B, T, H, 0), "rec_dien_gru_fwd_f32", dev, *args, *tail)
+        else:
+            _call("rec_dien_gru_fwd_f32", *args, *tail, None, 0)
+    return out, fin, aux
+
+
+def dien_gru_bwd(kernel, recurrent_kernel, bias, gru_output, dgru_output=None, dh_final=None, gaux=None, embed=None,
+                 series=None, negatives=None, x=None, mask_ids=None, padding_index=0, dx=None, dneg=None):
+    """-> (dx [B,T,H]: the IndexedSlices values of the series lookup or the gradient of x, dneg [B,T,H] or None: the
+    values of the negative lookup, dkernel, drecurrent_kernel, dbias) from dgru_output [B,T,H], dh_final [B,H] and gaux
+    [1], each of which may be None (exact zeros); the gates are computed again from ``gru_output``.  ``dx`` / ``dneg``:
+    optional preallocated contiguous destinations (the tail of a shared value buffer)."""
+    args, (B, T, H, V, E, Cn) = _dien_gru_args(embed, series, negatives, x, mask_ids, kernel, recurrent_kernel, bias,
+                                               padding_index)
+    dev = kernel.device
+    _expect(gru_output, (B, T, H), "gru_output", "[B,T,H]")
+    _expect(dgru_output, (B, T, H), "dgru_output", "[B,T,H]", optional=True)
+    _expect(dh_final, (B, H), "dh_final", "[B,H]", optional=True)
+    _expect(gaux, (1,), "gaux", optional=True)
+    if dx is None:
+        dx = _new((B, T, H), dev, B)
+    _expect(dx, (B, T, H), "dx", "[B,T,H]")
+    if negatives is not None:
+        if dneg is None:
+            dneg = _new((B, T, H), dev, B)
+        _expect(dneg, (B, T, H), "dneg", "[B,T,H]")
+    grads = [_new_like(t, B) for t in (kernel, recurrent_kernel, bias)]
+    if B > 0:
+        _call_ws("rec_dien_gru_scratch_bytes", (B, T, H, 1), "rec_dien_gru_bwd_f32", dev, *args, _ptr(gru_output),
+                 _ptr(dgru_output), _ptr(dh_final), _ptr(gaux), _ptr(dx), _ptr(dneg), *_ptrs(grads))
+    return (dx, dneg if negatives is not None else None) + tuple(grads)
+
+
+def _dien_augru_args(gru_output, q, mask_ids, mode, Wx, Uh, bx, padding_index, mask_valid):
+    if _f32(gru_output, "gru_output").dim() != 3:
+        raise ValueError("gru_output must be [B,T,H], got %s" % (tuple(gru_output.shape),))
+    B, T, H = gru_output.shape
+    if mode not in (DIEN_AUGRU, DIEN_AGRU):
+        raise ValueError("the evolution's mode must be DIEN_AUGRU or DIEN_AGRU, got %r" % (mode,))
+    ng = 3 if mode == DIEN_AUGRU else 2
+    _req(mask_ids, torch.int64, "mask_ids")
+    if mask_ids.dim() not in (2, 3) or tuple(mask_ids.shape[:2]) != (B, T):
+        raise ValueError("mask_ids must be [B,T] or the series ids [B,T,C], got %s" % (tuple(mask_ids.shape),))
+    stride = mask_ids.shape[2] if mask_ids.dim() == 3 else 1
+    _expect_all(((q, (B, H), "q"), (Wx, (H, ng * H), "Wx"), (Uh, (H, ng * H), "Uh"), (bx, (ng * H,), "bx")))
+    dien_check_shape(H, T, mode)
+    return [_ptr(gru_output), _ptr(q), _ptr(mask_ids), stride, B, T, H, mode, _ptr(Wx), _ptr(Uh), _ptr(bx),
+            int(padding_index), int(bool(mask_valid))], (B, T, H)
+
+
+def dien_augru_fwd(gru_output, q, mask_ids, mode, Wx, Uh, bx, padding_index=0, mask_valid=0, save=True):
+    """DienActivationLayer's scores and the AGRU / AUGRU over them in one launch: gru_output [B,T,H], q = X_item W^T
+    [B,H], the mask ids ([B,T], or the series ids [B,T,C] whose first feature decides), the packed cell weights Wx, Uh
+    [H, ng H] and bx [ng H] (AUGRU [z | r | h], AGRU [r | h]) -> (scores [B,T], states [B,T,H] or None, h_final [B,H]).
+    ``mask_valid`` = 0 scores the PADDED positions (the reference), 1 the valid ones."""
+    args, (B, T, H) = _dien_augru_args(gru_output, q, mask_ids, mode, Wx, Uh, bx, padding_index, mask_valid)
+    dev = gru_output.device
+    scores, fin = _new((B, T), dev, B), _new((B, H), dev, B)
+    states = _new((B, T, H), dev, B) if save else None
+    if B > 0:
+        _call("rec_dien_augru_fwd_f32", *args, _ptr(scores), _ptr(states), _ptr(fin))
+    return scores, states, fin
+
+
+def dien_augru_bwd(gru_output, q, mask_ids, mode, Wx, Uh, bx, scores, states, dh_final, padding_index=0, mask_valid=0):
+    """-> (dgru_output [B,T,H], dq [B,H], dWx, dUh, dbx) from dh_final [B,H] and the forward's scores and states"""
+    args, (B, T, H) = _dien_augru_args(gru_output, q, mask_ids, mode, Wx, Uh, bx, padding_index, mask_valid)
+    _expect_all(((scores, (B, T), "scores"), (states, (B, T, H), "states"), (dh_final, (B, H), "dh_final")))
+    dev = gru_output.device
+    dg, dq = _new((B, T, H), dev, B), _new((B, H), dev, B)
+    grads = [_new_like(t, B) for t in (Wx, Uh, bx)]
+    if B > 0:
+        _call_ws("rec_dien_augru_scratch_bytes", (B, T, H, mode), "rec_dien_augru_bwd_f32", dev, *args, _ptr(scores),
+                 _ptr(states), _ptr(dh_final), _ptr(dg), _ptr(dq), *_ptrs(grads))
+    return (dg, dq) + tuple(grads)

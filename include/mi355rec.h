@@ -1395,6 +1395,74 @@ int rec_poso_mlp_bwd_f32(const float* x, int64_t ldx, const float* g, int64_t ld
                          float* dWg1, float* dbg1, float* dWg2, float* dbg2, float* dW, float* db, float* dC,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- DIEN (DIENLayer / DienGRU / CustomGRUCell / DienActivationLayer, 5.DIN/CustomLayers.py:292-517; csrc/dien.hip):
+ * the interest extractor (a masked tf.keras.layers.GRU fused with the series and negative lookups and the auxiliary
+ * loss) and the interest evolution (attention scores fused with an AGRU / AUGRU).  H = D = E C everywhere.  One cell
+ * serves all three recurrences: gate blocks [z | r | h] of H columns each, Wx [H, 3H] on the input, Uh [H, 3H] on the
+ * state (AGRU: [r | h], [H, 2H]); valid[b,t] = (mask id != padding_index); where it is false h_t = h_{t-1} (h_{-1} = 0),
+ * anywhere in the row:
+ *   pre = x_t Wx + bx   rec = h Uh + bh   z = sigmoid(pre_z + rec_z)   r = sigmoid(pre_r + rec_r)
+ *   hh = tanh(pre_h + r (.) rec_h)
+ *   GRU     h_t = z h + (1 - z) hh        kernel = Wx, recurrent_kernel = Uh, bias [2, 3H] = [bx ; bh] (reset_after=True)
+ *   AUGRU   h_t = (1 - a z) h + a z hh    Wx = [W_z | W_r | W_h], Uh = [U_z | U_r | U_h], bx = [b_z | b_r | b_h], bh = 0
+ *   AGRU    h_t = (1 - a) h + a hh        Wx = [W_r | W_h], Uh = [U_r | U_h], bx = [b_r | b_h]
+ * rec_dien_gru_*.  Table mode (embed != NULL; x and mask_ids NULL): x_t = concat_r embed[series[b,t,r]], series int64
+ * [B, T, C], the mask ids are series[b,t,0]; an id outside [0, V) reads a zero row and sets *oob_flag (may be NULL).
+ * Dense mode (embed NULL): x [B, T, H] and mask_ids int64 [B, T]; negatives must be NULL.  The forward writes
+ * gru_output [B, T, H] (every h_t) and / or h_final [B, H]: either may be NULL, not both.  negatives int64 [B, T, C]
+ * (table mode, may be NULL): aux [1] = sum over b and t >= 1 of valid[b,t] (ce(sigmoid(x_{t-1} . h_t), 1) +
+ * ce(sigmoid(x_{t-1} . neg_t), 0)), ce(v, l) = max(v, 0) - v l + log1p(exp(-|v|)); T = 1 gives 0.  It is summed
+ * through one slot per workgroup in the scratch, which only this case needs (the others accept NULL).
+ * The backward takes gru_output (the forward's, always [B, T, H]), dgru_output [B, T, H], dh_final [B, H] and gaux [1]
+ * (each may be NULL: exact zeros), recomputes the gates and writes, never adds to: dx [B, T, H], the IndexedSlices
+ * values of the series lookup (table mode) or the gradient of x; dneg [B, T, H] the values of the negative lookup (with
+ * negatives; position 0 is zero); dkernel, drecurrent_kernel [H, 3H], dbias [2, 3H].
+ * rec_dien_augru_*.  mode 1 = AUGRU, 2 = AGRU.  gru_output [B, T, H] is the input, q [B, H] = X_item W^T (made by the
+ * caller, rec_gemm_f32), mask_ids[(b T + t) mask_stride] the mask ids.  product[b,t] = gru_output[b,t] . q[b],
+ * e = sel ? exp(product) : 0 with sel = !valid (mask_valid = 0, the reference: only PADDED positions score) or valid
+ * (mask_valid = 1), scores = e / sum_t e with NaN -> 0 (a row with nothing selected scores zeros) [B, T], always
+ * written; a = scores.  states [B, T, H] (every h_t; may be NULL in inference) and h_final [B, H].  The backward takes
+ * scores, states and dh_final and writes dgru_output [B, T, H] (through the cell and through the scores), dq [B, H],
+ * dWx, dUh, dbx in the packed layout; rows whose scores were NaN -> 0 get zero through the scores.
+ * All four: one recurrence launch that walks t inside the kernel, a workgroup of 4 waves per 32 examples, products on
+ * v_mfma_f32_32x32x2_f32 (fp32-exact); the backward adds one slot sum for the bias gradients and three rec_gemm_f32
+ * (split-K over B T, slices added in order) for dWx = X^T dpre and dUh = Hprev^T drec out of the scratch.  They only
+ * enqueue (graph-capturable) and use no float atomics: bit-identical results run to run.
+ * Supported, the same both ways: 1 <= H <= REC_DIN_WIDE_D (128), T >= 1, 0 <= B < 2^31 and the tile's LDS within the
+ * 150 KiB launch cap (rec_dien_gru_lds_bytes, rec_dien_augru_lds_bytes; 0: invalid or unsupported), He = H made even:
+ *   GRU     132 * 8 He + 512 <= 153600                       (every H up to 128, any T)
+ *   AUGRU   132 * (7 He + 2 T) + 512, AGRU 132 * (6 He + 2 T) + 512 <= 153600      (T <= 131 at H = 128, <= 243 at 96)
+ * scratch: rec_dien_gru_scratch_bytes (backward = 0: the forward's aux slots; 1: the backward's) and
+ * rec_dien_augru_scratch_bytes (backward only): B T (6 H or 5 H) floats of per-step gradients and operands, at most
+ * 2048 slots of 2 ng H floats, 16 split-K slices of [H, ng H]; 0: invalid or unsupported.
+ * Return codes, in this order: a size below 1 (B below 0) or an unknown mode: -1; a shape outside the limits: -2, from
+ * the sizes alone; ld < E, V < 1, E C != H, a pointer that must (not) be NULL: -1; a scratch that is too small: -3; then
+ * B == 0: 0, nothing is launched or written. */
+size_t rec_dien_gru_lds_bytes(int T, int H);
+size_t rec_dien_augru_lds_bytes(int T, int H, int mode);
+size_t rec_dien_gru_scratch_bytes(int64_t B, int T, int H, int backward);
+size_t rec_dien_augru_scratch_bytes(int64_t B, int T, int H, int mode);
+int rec_dien_gru_fwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* series,
+                         const int64_t* negatives, const float* x, const int64_t* mask_ids, int64_t B, int T, int H,
+                         const float* kernel, const float* recurrent_kernel, const float* bias, int64_t padding_index,
+                         float* gru_output, float* h_final, float* aux, int* oob_flag, void* scratch,
+                         size_t scratch_bytes, void* stream);
+int rec_dien_gru_bwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* series,
+                         const int64_t* negatives, const float* x, const int64_t* mask_ids, int64_t B, int T, int H,
+                         const float* kernel, const float* recurrent_kernel, const float* bias, int64_t padding_index,
+                         const float* gru_output, const float* dgru_output, const float* dh_final, const float* gaux,
+                         float* dx, float* dneg, float* dkernel, float* drecurrent_kernel, float* dbias, void* scratch,
+                         size_t scratch_bytes, void* stream);
+int rec_dien_augru_fwd_f32(const float* gru_output, const float* q, const int64_t* mask_ids, int64_t mask_stride,
+                           int64_t B, int T, int H, int mode, const float* Wx, const float* Uh, const float* bx,
+                           int64_t padding_index, int mask_valid, float* scores, float* states, float* h_final,
+                           void* stream);
+int rec_dien_augru_bwd_f32(const float* gru_output, const float* q, const int64_t* mask_ids, int64_t mask_stride,
+                           int64_t B, int T, int H, int mode, const float* Wx, const float* Uh, const float* bx,
+                           int64_t padding_index, int mask_valid, const float* scores, const float* states,
+                           const float* dh_final, float* dgru_output, float* dq, float* dWx, float* dUh, float* dbx,
+                           void* scratch, size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
