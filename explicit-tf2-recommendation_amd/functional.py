@@ -1354,3 +1354,74 @@ class DienAugru(torch.autograd.Function):
         else:
             cell = cell + (None, None, None)
         return (dg, dX_item, dW, None, None, None, None) + cell
+
+
+class SimSearch(torch.autograd.Function):
+    """SIM's soft search fused with the GSU pooling and the series lookup (7.SIM/CustomLayers.py:88-96, 236-260;
+    csrc/sim.hip): ``embed`` [V,E], the candidate's rows ``q`` [B,D], ``series`` ids [B,T,C] -> (pooled [B,D], sel
+    [B,K,D], sel_valid int32 [B,K], chosen int32 [B,K], scores [B,T]) with K = min(k, T); the last three carry no
+    gradient.  One launch each way; the gradient that arrives through ``sel`` joins the pooling's in the one [B,T,D]
+    buffer of IndexedSlices values, so ONE de-duplication plan serves the series.  ``sink``: as IpAttention's."""
+
+    @staticmethod
+    def forward(ctx, embed, q, series, padding_index, k, oob=None, sink=None):
+        q = q.contiguous()
+        K = min(int(k), series.shape[1])
+        scores, pooled, chosen, sel, sel_valid = ops.sim_search_fwd(embed, series, q, padding_index, K, oob)
+        ctx.save_for_backward(embed, q, series, scores, chosen)
+        ctx.padding_index, ctx.sink = padding_index, sink
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(sel_valid, chosen, scores)
+        return pooled, sel, sel_valid, chosen, scores
+
+    @staticmethod
+    def backward(ctx, gpooled, gsel, _gvalid, _gchosen, _gscores):
+        embed, q, series, scores, chosen = ctx.saved_tensors
+        V, E = embed.shape
+        gpooled = torch.zeros_like(q) if gpooled is None else gpooled.contiguous()
+        gsel = None if gsel is None else gsel.contiguous()
+        sink, dst = ctx.sink, None
+        if sink is not None:
+            buf = sink.new_buf(series.numel(), E, embed.device)
+            dst = buf[sink.n_head:sink.n_head + series.numel()].view(series.shape[0], series.shape[1], -1)
+        gkeys, gq = ops.sim_search_bwd(embed, series, q, ctx.padding_index, scores, gpooled, chosen, gsel, gkeys=dst)
+        if sink is not None:
+            sink.ids, sink.buf = series, buf
+            return None, gq, None, None, None, None, None
+        gembed = None
+        if ctx.needs_input_grad[0]:
+            gembed = _sparse_grad(ops.DedupPlan(series, V), gkeys.reshape(-1, E), E, (V, E))
+        return gembed, gq, None, None, None, None, None
+
+
+class EsuAttention(torch.autograd.Function):
+    """Keras MultiHeadAttention with one query over K dense keys (7.SIM/CustomLayers.py:159, 191-196; csrc/sim.hip):
+    q [B,D], x [B,K,D] (keys and values), mask [B,K] (True / non-zero = attend; Keras' additive -1e9 in fp32), the
+    kernels Wq, Wk, Wv [D,H,dk], Wo [H,dk,D] and their biases -> out [B,D].  One launch forward; the backward recomputes
+    the forward's stages and sums the weight gradients over the batch in a fixed order."""
+
+    @staticmethod
+    def forward(ctx, q, x, mask, Wq, bq, Wk, bk, Wv, bv, Wo, bo):
+        q, x = q.contiguous(), x.contiguous()
+        mask = mask.to(torch.int32).contiguous()
+        weights = tuple(w.contiguous() for w in (Wq, bq, Wk, bk, Wv, bv, Wo, bo))
+        out, _ = ops.esu_attn_fwd(q, x, mask, weights)
+        ctx.save_for_backward(q, x, mask, *weights)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        q, x, mask, *weights = ctx.saved_tensors
+        grads = ops.esu_attn_bwd(q, x, mask, tuple(weights), gout.contiguous())
+        return (grads[0], grads[1], None) + tuple(grads[2:])
+
+
+def sim_loss(gsu_logits, esu_logits, label, alpha=0.2, beta=0.8):
+    """The loss of SIM's train loop (7.SIM/ModelManager.py:173-180): tf.nn.softmax_cross_entropy_with_logits on the two
+    heads' outputs -- which are softmax outputs already; the double softmax is the reference's and is kept -- weighted
+    alpha, beta and summed over the batch.  ``label``: [B] 0/1 or one-hot [B,2].  Composed of torch ops."""
+    if label.dim() == 1:
+        label = torch.stack([1 - label, label], 1)
+    label = label.to(gsu_logits.dtype)
+    ce = lambda logits: -(label * torch.log_softmax(logits, -1)).sum(-1)
+    return (alpha * ce(gsu_logits) + beta * ce(esu_logits)).sum()

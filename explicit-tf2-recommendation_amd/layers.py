@@ -3336,3 +3336,200 @@ class DIENLayer(Layer):
         self._raise_if_oob(flag)
         X_combined = ConcatCols.apply(profile_output, evolved)
         return {"X_combined": X_combined, "output": self.mlp(X_combined), "auxiliary_loss": auxiliary_loss}
+
+
+class _EinsumDense(Layer):
+    """One projection of Keras' MultiHeadAttention: ``kernel`` (rank 3, glorot_uniform) and ``bias`` (zeros)"""
+
+    def __init__(self, kernel_shape, bias_shape):
+        super().__init__()
+        self.kernel = torch.nn.Parameter(glorot_uniform(tuple(kernel_shape)))
+        self.bias = torch.nn.Parameter(torch.zeros(tuple(bias_shape)))
+
+
+class MultiHeadAttention(Layer):
+    """tf.keras.layers.MultiHeadAttention(num_heads, key_dim) of Keras 2.x with value_dim = key_dim, no dropout and the
+    output width of the query, built eagerly for ``input_dim``-wide queries, keys and values.  Sub-modules
+    ``_query_dense``, ``_key_dense``, ``_value_dense`` (kernel [D,H,dk], bias [H,dk]) and ``_output_dense`` (kernel
+    [H,dk,D], bias [D]): Keras' checkpoint names with '/' -> '.'.  ``forward(query [B,1,D], value [B,K,D], key=None,
+    attention_mask=[B,1,K] bool)`` -> [B,1,D]: one query over K keys, the case the reference uses.  The mask is Keras'
+    additive one, float32(logit + (1 - mask) * -1e9) -- a row with every position masked attends uniformly.  GPU
+    tensors with key = value run csrc/sim.hip; anything else runs ``composed``, the einsum form of Keras in torch."""
+
+    def __init__(self, num_heads, key_dim, input_dim):
+        super().__init__()
+        self.num_heads, self.key_dim, self.input_dim = num_heads, key_dim, input_dim
+        D, H, dk = input_dim, num_heads, key_dim
+        self._query_dense = _EinsumDense((D, H, dk), (H, dk))
+        self._key_dense = _EinsumDense((D, H, dk), (H, dk))
+        self._value_dense = _EinsumDense((D, H, dk), (H, dk))
+        self._output_dense = _EinsumDense((H, dk, D), (D,))
+
+    def weights(self):
+        return tuple(t for m in (self._query_dense, self._key_dense, self._value_dense, self._output_dense)
+                     for t in (m.kernel, m.bias))
+
+    def composed(self, query, value, key=None, attention_mask=None):
+        key = value if key is None else key
+        Wq, bq, Wk, bk, Wv, bv, Wo, bo = self.weights()
+        q = torch.einsum("bqd,dhk->bqhk", query, Wq) + bq
+        k = torch.einsum("bjd,dhk->bjhk", key, Wk) + bk
+        v = torch.einsum("bjd,dhk->bjhk", value, Wv) + bv
+        q = q * (1.0 / math.sqrt(float(self.key_dim)))
+        logits = torch.einsum("bjhk,bqhk->bhqj", k, q)
+        if attention_mask is not None:
+            logits = logits + (1.0 - attention_mask[:, None].to(logits.dtype)) * -1e9
+        p = torch.softmax(logits, -1)
+        o = torch.einsum("bhqj,bjhk->bqhk", p, v)
+        return torch.einsum("bqhk,hkd->bqd", o, Wo) + bo
+
+    def forward(self, query, value, key=None, attention_mask=None, fused=True):
+        if query.dim() != 3 or query.shape[1] != 1 or value.dim() != 3:
+            raise ValueError("MultiHeadAttention takes one query [B,1,D] over value [B,K,D], got %s and %s"
+                             % (tuple(query.shape), tuple(value.shape)))
+        if not (fused and query.is_cuda and (key is None or key is value)):
+            return self.composed(query, value, key, attention_mask)
+        B, K, D = value.shape
+        ops.sim_check_shape(D, None, K, self.num_heads, self.key_dim)
+        if attention_mask is None:
+            mask = torch.ones((B, K), dtype=torch.int32, device=value.device)
+        else:
+            mask = attention_mask.reshape(B, K)
+        return Fn.EsuAttention.apply(query[:, 0], value, mask, *self.weights()).unsqueeze(1)
+
+
+class ESULayer(Layer):
+    """7.SIM/CustomLayers.py:130-201 (exact search unit): a frozen DIENLayer's ``X_combined`` beside a multi-head
+    attention of the candidate item over the K extracted behaviours, into make_mlp_layer([200, 80], softmax_units=2).
+    ``forward`` reads ``inputs['extracted_series']`` [B,K,D] and ``inputs['series_mask']`` [B,K] (True = padded), as the
+    reference does, and returns ``{'output'}``.
+    Extensions, after the reference's arguments: ``dien_layer`` -- a trained DIENLayer to embed (what the reference's
+    commented load_weights line intends); None builds DIENLayer(stage='inference') with its own defaults.  It is frozen
+    (requires_grad False, run under no_grad and in eval mode, absent from ``trainable_variables``, present in
+    ``state_dict()``).  ``mask_mode``: 'reference' passes series_mask as Keras' attention_mask as written, so only PADDED
+    selections are attended (with all K selections valid every logit is masked and the attention is the uniform mean of
+    the values); 'valid' attends the valid selections.  ``fused``: True runs csrc/sim.hip, False the torch composition."""
+
+    def __init__(self, user_and_context_categorical_features=["uid", "utag1", "utag2", "utag3", "utag4"],
+                 item_categorical_features=["i_goods_id", "i_shop_id", "i_cate_id"],
+                 behavior_series_features=["visited_goods_ids", "visited_shop_ids", "visited_cate_ids"],
+                 feature_dims=1000, embedding_dims=16, activation="Dice", padding_index=0, num_heads=8,
+                 embedding_layer=None, l2_reg=0.01, dien_layer=None, mask_mode="reference", fused=True):
+        super().__init__()
+        self.user_and_context_categorical_features = user_and_context_categorical_features
+        self.item_categorical_features = item_categorical_features
+        assert len(item_categorical_features) == len(behavior_series_features), \
+            "Features to be interacted should match in item and behavior series"
+        self.behavior_series_features = behavior_series_features
+        self.feature_dims = feature_dims
+        self.embedding_dims = embedding_dims
+        self.l2_reg = l2_reg
+        if mask_mode not in ("reference", "valid"):
+            raise ValueError("mask_mode must be 'reference' or 'valid'")
+        self.mask_mode = mask_mode
+        self.fused = fused
+        self.embed = embedding_layer if embedding_layer is not None else Embedding(feature_dims, embedding_dims)
+        D = len(behavior_series_features) * embedding_dims
+        if fused:
+            ops.sim_check_shape(D, None, None, num_heads, D)
+        self.dien_layer = dien_layer if dien_layer is not None else DIENLayer(stage="inference")
+        self.dien_layer.set_stage("inference")
+        self.dien_layer.requires_grad_(False)
+        self.dien_layer.eval()
+        dien_width = self.dien_layer.mlp.layers[0].kernel.shape[0]          # the width of DIEN's X_combined
+        self.mlp = make_mlp_layer([200, 80], activation=activation, softmax_units=2, input_dim=dien_width + D)
+        self.padding_index = padding_index
+        self.mha = MultiHeadAttention(num_heads=num_heads, key_dim=D, input_dim=D)
+
+    def train(self, mode=True):
+        super().train(mode)
+        self.dien_layer.eval()                               # Keras: trainable = False also means inference mode
+        return self
+
+    def head(self, inputs, X_item, extracted_series, series_mask):
+        """everything after the item lookup: X_item [B,D] -> the layer's output"""
+        with torch.no_grad():
+            dien_output = self.dien_layer(inputs)["X_combined"]
+        attend = series_mask if self.mask_mode == "reference" else ~series_mask
+        mha_interest = self.mha(X_item.unsqueeze(1), extracted_series, attention_mask=attend.unsqueeze(1),
+                                fused=self.fused).squeeze(1)
+        X_combined = ConcatCols.apply(dien_output, mha_interest)
+        return self.mlp(X_combined)
+
+    def forward(self, inputs):
+        X_item = assemble_index(inputs, self.item_categorical_features)
+        flag = ops.new_flag(X_item.device) if self.check_ids else None
+        q = self.embed(X_item, flag)
+        self._raise_if_oob(flag)
+        series_mask = inputs["series_mask"].to(device=X_item.device, dtype=torch.bool)
+        x = inputs["extracted_series"].to(device=X_item.device, dtype=torch.float32)
+        return {"output": self.head(inputs, q.reshape(q.shape[0], -1), x, series_mask)}
+
+
+class SIMLayer(Layer):
+    """7.SIM/CustomLayers.py:203-282, search-based interest model: the general search unit's pooling head, the soft
+    search for the ``k`` behaviours that score highest against the candidate (a padded step ranks as -inf; ties go to the
+    lower index, tf.argsort's order), and the exact search unit over them.  One shared table: ``embed``,
+    ``gsu_layer.embed`` and ``esu_layer.embed`` are the same module.  ``forward`` returns ``{'gsu_logits',
+    'esu_logits'}``, both [B,2] tensors -- in the reference 'esu_logits' is the ESU's result dict, which its own train
+    loop cannot consume -- and does not write 'extracted_series' / 'series_mask' into the caller's ``inputs``, as the
+    reference does.
+    Extensions, after the reference's arguments: ``mask_mode`` and ``dien_layer`` are ESULayer's; ``fused`` = True makes
+    ONE item lookup (the reference's three read the same rows), ONE search launch each way that yields the GSU pooling,
+    the top k and their rows, and ONE attention launch; the series' gradient -- through the pooling and through the
+    selected rows -- leaves through one buffer and one de-duplication plan shared with the item lookup.  False composes
+    GSULayer(return_series=True), torch.sort(stable=True, descending=True), a gather and the composed attention."""
+
+    def __init__(self, user_and_context_categorical_features=["uid", "utag1", "utag2", "utag3", "utag4"],
+                 item_categorical_features=["i_goods_id", "i_shop_id", "i_cate_id"],
+                 behavior_series_features=["visited_goods_ids", "visited_shop_ids", "visited_cate_ids"],
+                 feature_dims=1000, embedding_dims=16, activation="Dice", padding_index=0, k=3, l2_reg=0.01,
+                 mask_mode="reference", fused=True, dien_layer=None):
+        super().__init__()
+        assert len(item_categorical_features) == len(behavior_series_features), \
+            "Features to be interacted should match in item and behavior series"
+        self.user_and_context_categorical_features = user_and_context_categorical_features
+        self.item_categorical_features = item_categorical_features
+        self.behavior_series_features = behavior_series_features
+        self.embedding_dims = embedding_dims
+        self.padding_index = padding_index
+        self.fused = fused
+        self.embed = Embedding(feature_dims, embedding_dims)
+        self.gsu_layer = GSULayer(item_categorical_features=item_categorical_features,
+                                  behavior_series_features=behavior_series_features, feature_dims=feature_dims,
+                                  embedding_dims=embedding_dims, activation=activation, padding_index=padding_index,
+                                  embedding_layer=self.embed, return_series=True)
+        self.esu_layer = ESULayer(user_and_context_categorical_features=user_and_context_categorical_features,
+                                  item_categorical_features=item_categorical_features,
+                                  behavior_series_features=behavior_series_features, feature_dims=feature_dims,
+                                  embedding_dims=embedding_dims, activation=activation, padding_index=padding_index,
+                                  embedding_layer=self.embed, dien_layer=dien_layer, mask_mode=mask_mode, fused=fused)
+        self.k = k
+
+    def soft_index_search(self, X_item, X_series, valid_mask):
+        inner_products = torch.einsum("be,ble->bl", X_item, X_series)
+        inner_products = torch.where(valid_mask, inner_products, torch.full_like(inner_products, -math.inf))
+        order = torch.sort(inner_products, dim=-1, descending=True, stable=True).indices[:, :self.k]
+        top_k_embeddings = torch.gather(X_series, 1, order.unsqueeze(-1).expand(-1, -1, X_series.shape[2]))
+        return top_k_embeddings, torch.gather(valid_mask, 1, order)
+
+    def forward(self, inputs):
+        X_item = assemble_index(inputs, self.item_categorical_features)
+        flag = ops.new_flag(X_item.device) if self.check_ids else None
+        if not self.fused:
+            gsu_output = self.gsu_layer(inputs)
+            q = self.embed(X_item, flag)
+            q = q.reshape(q.shape[0], -1)
+            self._raise_if_oob(flag)
+            sel, sel_valid = self.soft_index_search(q, gsu_output["X_series"], gsu_output["valid_mask"])
+            return {"gsu_logits": gsu_output["output"], "esu_logits": self.esu_layer.head(inputs, q, sel, ~sel_valid)}
+        sink = self.embed.grad_sink(X_item)                  # the series lookup shares the item lookup's de-duplication
+        q = self.embed(X_item, flag, sink)
+        q = q.reshape(q.shape[0], -1)
+        series = _stack_ids(inputs, self.behavior_series_features, X_item.device)
+        ops.sim_check_shape(q.shape[1], series.shape[1], min(self.k, series.shape[1]), C=series.shape[2])
+        pooled, sel, sel_valid, _, _ = Fn.SimSearch.apply(self.embed.embeddings, q, series, self.padding_index, self.k,
+                                                          flag, sink)
+        self._raise_if_oob(flag)
+        gsu_logits = self.gsu_layer.mlp(ConcatCols.apply(q, pooled))
+        return {"gsu_logits": gsu_logits, "esu_logits": self.esu_layer.head(inputs, q, sel, sel_valid == 0)}

@@ -2640,3 +2640,140 @@ def dien_augru_bwd(gru_output, q, mask_ids, mode, Wx, Uh, bx, scores, states, dh
         _call_ws("rec_dien_augru_scratch_bytes", (B, T, H, mode), "rec_dien_augru_bwd_f32", dev, *args, _ptr(scores),
                  _ptr(states), _ptr(dh_final), _ptr(dg), _ptr(dq), *_ptrs(grads))
     return (dg, dq) + tuple(grads)
+
+
+# ---------------------------------------------------------------------------------------------------
+# SIM (7.SIM/CustomLayers.py:130-282; csrc/sim.hip): the soft search fused with the GSU pooling, and the one-query
+# multi-head attention of the exact search unit.  The limits are the .hip file's and show through its size queries.
+# ---------------------------------------------------------------------------------------------------
+SIM_MAX_D, SIM_MAX_K, SIM_MAX_H = 64, 16, 8         # the attention's; the search alone covers a key width of 256
+_SIM_SEARCH_LDS_CAP = 64 * 1024
+
+
+def sim_search_lds_bytes(T, C, D, K=1):
+    """LDS of one example of the search (include/mi355rec.h)"""
+    return 4 * (T * C + 4 * D + T + 16)
+
+
+def esu_attn_lds_bytes(K, D, H, dk):
+    """LDS of a tile of 32 examples of the attention (include/mi355rec.h)"""
+    return 132 * (_even(max(H * dk, H * D, D)) + 2 + 2 * H * K + H)
+
+
+def sim_check_shape(D, T=None, K=None, H=None, dk=None, C=1):
+    """ValueError for sizes that describe no SIM body, NotImplementedError naming the limit for shapes the kernels do not
+    cover (the ABI would return -2): the key width D = E C, the series length T, the K selected positions, and -- for the
+    attention -- the heads H and their width dk (None: dk = D, the reference's)."""
+    given = [v for v in (D, T, K, H, dk, C) if v is not None]
+    if min(given) < 1:
+        raise ValueError("every size of a SIM body must be positive, got D=%r, T=%r, K=%r, H=%r, dk=%r"
+                         % (D, T, K, H, dk))
+    if D > DIN_WIDE_D * 2:
+        raise NotImplementedError("the SIM search covers a key width embedding_dims * series features <= %d; got %d"
+                                  % (DIN_WIDE_D * 2, D))
+    if K is not None and K > SIM_MAX_K:
+        raise NotImplementedError("SIM kernels cover k <= %d selected positions; got %d" % (SIM_MAX_K, K))
+    if T is not None and sim_search_lds_bytes(T, C, D) > _SIM_SEARCH_LDS_CAP:
+        raise NotImplementedError("the SIM search holds one example's ids and scores in LDS: 4 (T C + 4 D + T + 16) <= "
+                                  "%d bytes; got %d at T=%d, C=%d, D=%d"
+                                  % (_SIM_SEARCH_LDS_CAP, sim_search_lds_bytes(T, C, D), T, C, D))
+    if H is not None:
+        dk = D if dk is None else dk
+        if D > SIM_MAX_D or dk > SIM_MAX_D or H > SIM_MAX_H or D % 2 or dk % 2:
+            raise NotImplementedError("the ESU attention covers even widths D, key_dim <= %d and num_heads <= %d; got "
+                                      "D=%d, key_dim=%d, num_heads=%d" % (SIM_MAX_D, SIM_MAX_H, D, dk, H))
+        if K is not None:
+            _lds_fit(esu_attn_lds_bytes(K, D, H, dk), "the ESU attention holds a tile of 32 examples",
+                     "33 (max(H dk, H D) + 2 + 2 H K + H)", "K=%d, D=%d, H=%d, key_dim=%d" % (K, D, H, dk))
+
+
+def _sim_search_args(embed, series, q, padding_index, K):
+    head, (V, E, B, T, Cn) = _series_head(embed, series, "the SIM search")
+    D = Cn * E
+    _expect(q, (B, D), "q", "[B, C E]")
+    if not 1 <= K <= T:
+        raise ValueError("the SIM search selects 1 <= K <= T positions, got K=%d at T=%d" % (K, T))
+    sim_check_shape(D, T, K, C=Cn)
+    return head + [_ptr(q), D, int(padding_index), int(K)], (V, E, B, T, Cn, D)
+
+
+def sim_search_fwd(embed, series, q, padding_index, K, oob=None):
+    """series [B,T,C] int64, q [B, C E] -> (scores [B,T], pooled [B,D], chosen int32 [B,K], sel [B,K,D], sel_valid int32
+    [B,K]): rec_ip_attn's scores and pooling, the K best positions by <q, k_t> (padded steps rank as -inf, ties go to the
+    lower index) and their rows  (7.SIM/CustomLayers.py:88-96, 236-260).  One launch."""
+    args, (V, E, B, T, Cn, D) = _sim_search_args(embed, series, q, padding_index, K)
+    dev = embed.device
+    scores, pooled, sel = _new((B, T), dev, B), _new((B, D), dev, B), _new((B, K, D), dev, B)
+    chosen, sel_valid = _new((B, K), dev, B, torch.int32), _new((B, K), dev, B, torch.int32)
+    if B > 0:
+        _call("rec_sim_search_fwd_f32", *args, _ptr(scores), _ptr(pooled), D, _ptr(chosen), _ptr(sel), _ptr(sel_valid),
+              _ptr(oob))
+    return scores, pooled, chosen, sel, sel_valid
+
+
+def sim_search_bwd(embed, series, q, padding_index, scores, gpooled, chosen, gsel=None, gkeys=None):
+    """-> (gkeys [B,T,D]: the IndexedSlices values of the series lookup, gq [B,D]) from gpooled [B,D] and gsel [B,K,D]
+    (None: nothing arrives through the selected rows).  ``gkeys``: optional preallocated contiguous destination."""
+    if _req(chosen, torch.int32, "chosen").dim() != 2:
+        raise ValueError("chosen must be [B,K], got %s" % (tuple(chosen.shape),))
+    K = chosen.shape[1]
+    args, (V, E, B, T, Cn, D) = _sim_search_args(embed, series, q, padding_index, K)
+    _expect(chosen, (B, K), "chosen", "[B,K]", dtype=torch.int32)
+    _expect_all(((scores, (B, T), "scores"), (gpooled, (B, D), "gpooled")))
+    _expect(gsel, (B, K, D), "gsel", "[B,K,D]", optional=True)
+    dev = embed.device
+    if gkeys is None:
+        gkeys = _new((B, T, D), dev, B)
+    _expect(gkeys, (B, T, D), "gkeys", "[B,T,D]")
+    gq = _new((B, D), dev, B)
+    if B > 0:
+        _call("rec_sim_search_bwd_f32", *args, _ptr(scores), _ptr(gpooled), D, _ptr(chosen), _ptr(gsel), _ptr(gkeys),
+              _ptr(gq))
+    return gkeys, gq
+
+
+_ESU_WEIGHTS = ("Wq", "bq", "Wk", "bk", "Wv", "bv", "Wo", "bo")
+
+
+def _esu_attn_args(q, x, mask, weights):
+    """``weights``: (Wq, bq, Wk, bk, Wv, bv, Wo, bo), Keras' kernels [D,H,dk] / [H,dk,D] and biases [H,dk] / [D]"""
+    if _f32(x, "x").dim() != 3:
+        raise ValueError("x must be [B,K,D], got %s" % (tuple(x.shape),))
+    B, K, D = x.shape
+    if len(weights) != 8 or _f32(weights[0], "Wq").dim() != 3 or weights[0].shape[0] != D:
+        raise ValueError("the ESU attention takes (Wq, bq, Wk, bk, Wv, bv, Wo, bo) with Wq [D,H,dk]")
+    H, dk = weights[0].shape[1:]
+    _expect(q, (B, D), "q", "[B,D]")
+    _expect(mask, (B, K), "mask", "[B,K]", dtype=torch.int32)
+    shapes = ((D, H, dk), (H, dk), (D, H, dk), (H, dk), (D, H, dk), (H, dk), (H, dk, D), (D,))
+    for t, shape, name in zip(weights, shapes, _ESU_WEIGHTS):
+        _expect(t, shape, name)
+    sim_check_shape(D, None, K, H, dk)
+    return [_ptr(q), D, _ptr(x), _ptr(mask), B, K, D, H, dk], (B, K, D, H, dk)
+
+
+def esu_attn_fwd(q, x, mask, weights, want_probs=False):
+    """Keras MultiHeadAttention with one query: q [B,D], x [B,K,D] (keys and values), mask int32 [B,K] (non-zero =
+    attend, applied additively as -1e9 in fp32) -> (out [B,D], probs [B,H,K] or None).  One launch."""
+    args, (B, K, D, H, dk) = _esu_attn_args(q, x, mask, weights)
+    dev = x.device
+    out = _new((B, D), dev, B)
+    probs = _new((B, H, K), dev, B) if want_probs else None
+    if B > 0:
+        _call_ws("rec_esu_attn_scratch_bytes", (B, K, D, H, dk), "rec_esu_attn_fwd_f32", dev, *args, *_ptrs(weights),
+                 _ptr(out), _ptr(probs))
+    return out, probs
+
+
+def esu_attn_bwd(q, x, mask, weights, gout):
+    """-> (gq [B,D], gx [B,K,D], dWq, dbq, dWk, dbk, dWv, dbv, dWo, dbo) from gout [B,D]; the forward's stages are
+    computed again"""
+    args, (B, K, D, H, dk) = _esu_attn_args(q, x, mask, weights)
+    _expect_all(((gout, (B, D), "gout"),))
+    dev = x.device
+    gq, gx = _new((B, D), dev, B), _new((B, K, D), dev, B)
+    grads = [_new_like(t, B) for t in weights]
+    if B > 0:
+        _call_ws("rec_esu_attn_scratch_bytes", (B, K, D, H, dk), "rec_esu_attn_bwd_f32", dev, *args,
+                 *_ptrs(weights[:7]), _ptr(gout), D, _ptr(gq), _ptr(gx), *_ptrs(grads))
+    return (gq, gx) + tuple(grads)

@@ -1463,6 +1463,61 @@ int rec_dien_augru_bwd_f32(const float* gru_output, const float* q, const int64_
                            const float* dh_final, float* dgru_output, float* dq, float* dWx, float* dUh, float* dbx,
                            void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- SIM (SIMLayer / ESULayer, 7.SIM/CustomLayers.py:130-282; csrc/sim.hip): the soft search fused with the GSU
+ * pooling, and the one-query multi-head attention of the exact search unit.  D = E C.
+ * rec_sim_search_*.  key k_t = concat_r embed[series[b,t,r]], valid[b,t] = series[b,t,0] != padding_index.  scores
+ * [B,T] = valid <q, k_t> and pooled [B,D] = sum_t scores_t k_t are those of rec_ip_attn_fwd_f32.  The ranked value is
+ * <q, k_t> for a valid step and -inf for a padded one (a NaN ranks as -inf); chosen int32 [B,K] holds the K <= T
+ * positions in descending order, on equal values the lower index first (tf.argsort(direction='DESCENDING')[:, :K]; it
+ * also orders the -inf entries when fewer than K steps are valid).  A score depends on the values of its key and of q
+ * only, so steps with the same ids tie bit for bit.  sel [B,K,D] is the key at chosen[b,j], read for padded positions
+ * too; sel_valid int32 [B,K] = valid[b, chosen[b,j]].  An id outside [0, V) reads a zero row and sets *oob_flag (may be
+ * NULL).  The backward writes, never adds to, gkeys [B,T,D] = scores_t gpooled + valid <gpooled, k_t> q, plus gsel[b,j,:]
+ * (may be NULL: none) where chosen[b,j] == t -- the IndexedSlices values of the one series lookup -- and gq [B,D] as
+ * rec_ip_attn_bwd_f32 does (the selection sends nothing to q).  One launch each way, one workgroup per example.
+ * Supported: D <= 256, K <= 16, V and B < 2^31, 4 (T C + 4 D + T + 16) <= 65536 bytes of LDS (rec_sim_search_lds_bytes:
+ * that sum, 0: invalid or unsupported).
+ * rec_esu_attn_*.  Keras 2.x MultiHeadAttention (value_dim = key_dim, no dropout) with one query q [B,D] over K dense
+ * keys x [B,K,D], mask int32 [B,K] (non-zero = attend), Wq, Wk, Wv [D,H,dk], bq, bk, bv [H,dk], Wo [H,dk,D], bo [D]:
+ *   Q_h  = (q Wq_h + bq_h) / sqrt(dk)          K_jh = x_j Wk_h + bk_h          V_jh = x_j Wv_h + bv_h
+ *   l_hj = <Q_h, K_jh>      a_hj = float32(l_hj + (1 - mask_j) * (-1e9))       p_h = softmax_j(a_h)
+ *   out  = sum_h (sum_j p_hj V_jh) Wo_h + bo
+ * The mask is additive in fp32, not a select: a row with every position masked has a_hj = -1e9 exactly for |l| < 32,
+ * hence p = 1/K, and the backward is the softmax Jacobian dl_hj = p_hj (g_hj - <p_h, g_h>) for every j, masked or not.
+ * out [B,D]; probs [B,H,K] = p (may be NULL).  The kernels use the collapsed form u_h = Wk_h Q_h, l_hj = <x_j, u_h> +
+ * <bk_h, Q_h>, sum_j p_hj V_jh = (sum_j p_hj x_j) Wv_h + bv_h; dbk, zero in exact arithmetic, comes out as rounding
+ * residue of sum_j dl_hj.  The backward takes gout [B,D] and writes, never adds to, gq [B,D], gx [B,K,D] and the eight
+ * weight gradients: one launch for the chain (a workgroup of 4 waves per 32 examples, products on
+ * v_mfma_f32_32x32x2_f32), a slot sum for dbq, dbv, dbo and one launch plus a slot sum for the 5 H per-head matrices of
+ * dWq, dWk, dWv, dWo, dbk over at most 16 batch slices added in order.  No float atomics: bit-identical run to run.
+ * Supported: D, dk <= 64 and even, H <= 8, K <= 16, B < 2^31 and 132 (max(H dk, H D) + 2 + 2 H K + H) <= 153600 bytes
+ * of LDS (rec_esu_attn_lds_bytes: that product, 0: invalid or unsupported).  scratch: rec_esu_attn_scratch_bytes,
+ * what the backward needs (the forward needs less): 4 B (4 H dk + 4 H D + H) bytes of per-example operands, (B / 32)
+ * slots and at most 16 copies of the weights; 0: invalid or unsupported.
+ * Return codes, in this order: a size below 1 (B below 0): -1; a shape outside the limits: -2, from the sizes alone; a
+ * leading dimension that is too small or K > T: -1; B == 0: 0, nothing is launched or written; a pointer that must not
+ * be NULL: -1; a scratch that is too small: -3. */
+size_t rec_sim_search_lds_bytes(int T, int C, int E, int K);
+size_t rec_esu_attn_lds_bytes(int K, int D, int H, int dk);
+size_t rec_esu_attn_scratch_bytes(int64_t B, int K, int D, int H, int dk);
+int rec_sim_search_fwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* series, int64_t B,
+                           int T, const float* q, int64_t ld_q, int64_t padding_index, int K, float* scores,
+                           float* pooled, int64_t ld_pooled, int* chosen, float* sel, int* sel_valid, int* oob_flag,
+                           void* stream);
+int rec_sim_search_bwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* series, int64_t B,
+                           int T, const float* q, int64_t ld_q, int64_t padding_index, int K, const float* scores,
+                           const float* gpooled, int64_t ld_gpooled, const int* chosen, const float* gsel, float* gkeys,
+                           float* gq, void* stream);
+int rec_esu_attn_fwd_f32(const float* q, int64_t ld_q, const float* x, const int* mask, int64_t B, int K, int D, int H,
+                         int dk, const float* Wq, const float* bq, const float* Wk, const float* bk, const float* Wv,
+                         const float* bv, const float* Wo, const float* bo, float* out, float* probs, void* scratch,
+                         size_t scratch_bytes, void* stream);
+int rec_esu_attn_bwd_f32(const float* q, int64_t ld_q, const float* x, const int* mask, int64_t B, int K, int D, int H,
+                         int dk, const float* Wq, const float* bq, const float* Wk, const float* bk, const float* Wv,
+                         const float* bv, const float* Wo, const float* gout, int64_t ld_gout, float* gq, float* gx,
+                         float* dWq, float* dbq, float* dWk, float* dbk, float* dWv, float* dbv, float* dWo, float* dbo,
+                         void* scratch, size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
