@@ -1416,6 +1416,46 @@ class EsuAttention(torch.autograd.Function):
         return (grads[0], grads[1], None) + tuple(grads[2:])
 
 
+class EtaSearch(torch.autograd.Function):
+    """ETA's SimHash search fused with the series lookup (7.SIM/CustomLayers.py:556-571; csrc/eta.hip): ``embed`` [V,E],
+    the candidate's rows ``q`` [B,D], ``series`` ids [B,T,C], the frozen projection ``Hm`` [D,m] -> (sel [B,K,D],
+    sel_valid int32 [B,K], chosen int32 [B,K], scores int32 [B,T]) with K = min(k, T); the last three carry no gradient.
+    One launch forward and none backward: ``sign`` has no gradient, so neither ``q`` nor ``Hm`` receives one, and the
+    table's is the sparse row gradient of the B K C selected ids -- the [B,T,D] series is never written.  ``sink``: a
+    GradSink of a Gather of the same table whose output feeds ``q``; the selected ids and their gradient rows are left
+    there and ride that lookup's de-duplication plan.  With no gradient arriving through ``sel`` nothing is done."""
+
+    @staticmethod
+    def forward(ctx, embed, q, series, Hm, padding_index, k, oob=None, sink=None):
+        q = q.contiguous()
+        K = min(int(k), series.shape[1])
+        scores, chosen, sel, sel_valid, sel_ids = ops.eta_search_fwd(embed, series, q, Hm.contiguous(), padding_index,
+                                                                     K, oob)
+        ctx.save_for_backward(sel_ids)
+        ctx.shape, ctx.sink = tuple(embed.shape), sink
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(sel_valid, chosen, scores)
+        return sel, sel_valid, chosen, scores
+
+    @staticmethod
+    def backward(ctx, gsel, _gvalid, _gchosen, _gscores):
+        (sel_ids,) = ctx.saved_tensors
+        V, E = ctx.shape
+        none = (None,) * 8
+        if gsel is None:
+            return none
+        rows = gsel.contiguous().reshape(-1, E)               # row (b, j, c) belongs to sel_ids[b, j, c]
+        sink = ctx.sink
+        if sink is not None:
+            buf = sink.new_buf(rows.shape[0], E, rows.device)
+            buf[sink.n_head:sink.n_head + rows.shape[0]].copy_(rows)
+            sink.ids, sink.buf = sel_ids, buf
+            return none
+        if not ctx.needs_input_grad[0]:
+            return none
+        return (_sparse_grad(ops.DedupPlan(sel_ids, V), rows, E, (V, E)),) + none[1:]
+
+
 def sim_loss(gsu_logits, esu_logits, label, alpha=0.2, beta=0.8):
     """The loss of SIM's train loop (7.SIM/ModelManager.py:173-180): tf.nn.softmax_cross_entropy_with_logits on the two
     heads' outputs -- which are softmax outputs already; the double softmax is the reference's and is kept -- weighted

@@ -2777,3 +2777,63 @@ def esu_attn_bwd(q, x, mask, weights, gout):
         _call_ws("rec_esu_attn_scratch_bytes", (B, K, D, H, dk), "rec_esu_attn_bwd_f32", dev, *args,
                  *_ptrs(weights[:7]), _ptr(gout), D, _ptr(gq), _ptr(gx), *_ptrs(grads))
     return (gq, gx) + tuple(grads)
+
+
+# ---------------------------------------------------------------------------------------------------
+# ETA (7.SIM/CustomLayers.py:518-626; csrc/eta.hip): the SimHash search of the long series.  The limits are the .hip
+# file's and show through its size query.
+# ---------------------------------------------------------------------------------------------------
+ETA_MAX_M = 32
+
+
+def eta_search_lds_bytes(T, D, m):
+    """LDS of one example of the search (include/mi355rec.h): the projection in 16 or 32 columns, the ranks, the chosen"""
+    return 4 * (D * (16 if m <= 16 else 32) + T + 16)
+
+
+def eta_check_shape(D, T=None, K=None, m=None, C=None):
+    """ValueError for sizes that describe no ETA search, NotImplementedError naming the limit for shapes the kernel does
+    not cover (the ABI would return -2): the key width D = E C, the series length T, the K selected positions, the m
+    hash bits and the C id columns of a step."""
+    given = [v for v in (D, T, K, m, C) if v is not None]
+    if min(given) < 1:
+        raise ValueError("every size of an ETA search must be positive, got D=%r, T=%r, K=%r, m=%r, C=%r"
+                         % (D, T, K, m, C))
+    if C is not None and D % C:
+        raise ValueError("the key width D = embedding_dims * series features; got D=%d with C=%d" % (D, C))
+    if D > DIN_WIDE_D * 2:
+        raise NotImplementedError("the ETA search covers a key width embedding_dims * series features <= %d; got %d"
+                                  % (DIN_WIDE_D * 2, D))
+    if K is not None and K > SIM_MAX_K:
+        raise NotImplementedError("the ETA search covers lsh_topk <= %d selected positions; got %d" % (SIM_MAX_K, K))
+    if m is not None and m > ETA_MAX_M:
+        raise NotImplementedError("the ETA search covers lsh_dim <= %d hash bits; got %d" % (ETA_MAX_M, m))
+    if T is not None and eta_search_lds_bytes(T, D, 1 if m is None else m) > _SIM_SEARCH_LDS_CAP:
+        m = 1 if m is None else m
+        raise NotImplementedError("the ETA search holds the projection and one example's ranks in LDS: 4 (D MC + T + 16) "
+                                  "<= %d bytes with MC = 16 or 32 columns; got %d at T=%d, D=%d, lsh_dim=%d"
+                                  % (_SIM_SEARCH_LDS_CAP, eta_search_lds_bytes(T, D, m), T, D, m))
+
+
+def eta_search_fwd(embed, series, q, Hm, padding_index, K, oob=None, want_scores=True):
+    """series [B,T,C] int64, q [B, C E], Hm [C E, m] -> (scores int32 [B,T] or None, chosen int32 [B,K], sel [B,K,D],
+    sel_valid int32 [B,K], sel_ids int64 [B,K,C]): the Hamming similarity of the SimHash codes of every step and of q,
+    the K best positions by it (padded steps rank as -inf, ties go to the lower index), their rows and their ids
+    (7.SIM/CustomLayers.py:556-571).  One launch."""
+    head, (V, E, B, T, Cn) = _series_head(embed, series, "the ETA search")
+    D = Cn * E
+    _expect(q, (B, D), "q", "[B, C E]")
+    if _f32(Hm, "Hm").dim() != 2 or Hm.shape[0] != D:
+        raise ValueError("Hm must be [C E, m] = [%d, m], got %s" % (D, tuple(Hm.shape)))
+    m = Hm.shape[1]
+    if not 1 <= K <= T:
+        raise ValueError("the ETA search selects 1 <= K <= T positions, got K=%d at T=%d" % (K, T))
+    eta_check_shape(D, T, K, m, Cn)
+    dev = embed.device
+    scores = _new((B, T), dev, B, torch.int32) if want_scores else None
+    chosen, sel_valid = _new((B, K), dev, B, torch.int32), _new((B, K), dev, B, torch.int32)
+    sel, sel_ids = _new((B, K, D), dev, B), _new((B, K, Cn), dev, B, torch.int64)
+    if B > 0:
+        _call("rec_eta_search_fwd_f32", *head, _ptr(q), D, _ptr(Hm), m, int(padding_index), int(K), _ptr(scores),
+              _ptr(chosen), _ptr(sel), _ptr(sel_valid), _ptr(sel_ids), _ptr(oob))
+    return scores, chosen, sel, sel_valid, sel_ids

@@ -1518,6 +1518,30 @@ int rec_esu_attn_bwd_f32(const float* q, int64_t ld_q, const float* x, const int
                          float* dWq, float* dbq, float* dWk, float* dbk, float* dWv, float* dbv, float* dWo, float* dbo,
                          void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- ETA (ETALayer, 7.SIM/CustomLayers.py:518-626; csrc/eta.hip): the SimHash search of the long behaviour series.
+ * D = E C.  key k_t = concat_c embed[series[b,t,c]], valid[b,t] = series[b,t,0] != padding_index (the first column
+ * alone).  q [B,D] is the candidate's rows, Hm [D,m] row-major the frozen projection.  The code of a row x is
+ * c(x)_j = sign(sum_d x_d Hm[d,j]) in {-1, 0, +1} as tf.sign gives it in fp32: a zero projection gives 0 (a zero row
+ * gives m of them), a NaN projection equals nothing.  A code depends on the values of its row and of Hm only -- not on
+ * t, T, the lane or ld -- so steps with the same ids get the same codes bit for bit.  scores int32 [B,T] (may be NULL) =
+ * #{ j : c(k_t)_j == c(q_b)_j } in [0, m], for every step, padded ones too.  A valid step ranks by its score, a padded
+ * one as -inf (the reference adds mask * (-inf), NaN for every valid step; the intent is kept, as rec_sim_search does).
+ * chosen int32 [B,K] = argsort(rank, DESCENDING)[:, :K], on equal ranks the lower index first; it also orders the padded
+ * steps when fewer than K are valid.  sel [B,K,D] is the key at chosen[b,j], read for padded positions too; sel_valid
+ * int32 [B,K] = valid[b, chosen[b,j]]; sel_ids int64 [B,K,C] the ids of the chosen steps as given.  An id outside [0, V)
+ * reads a zero row and sets *oob_flag (may be NULL).  One launch, one workgroup per example, a lane per step; no float
+ * atomics.  There is no backward entry point: Hm is frozen and sign has no gradient, so the gradient of sel is the sparse
+ * row gradient over sel_ids.
+ * Supported: m <= 32, K <= 16, D <= 256, V and B < 2^31, 4 (D MC + T + 16) <= 65536 bytes of LDS with MC = 16 for
+ * m <= 16 and 32 beyond (rec_eta_search_lds_bytes: that sum, 0: invalid or unsupported).
+ * Return codes, in this order: a size below 1 (B below 0): -1; a shape outside the limits: -2, from the sizes alone;
+ * ld < E, ld_q < D or K > T: -1; B == 0: 0, nothing is launched or written; a pointer that must not be NULL: -1. */
+size_t rec_eta_search_lds_bytes(int T, int C, int E, int m, int K);
+int rec_eta_search_fwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* series, int64_t B,
+                           int T, const float* q, int64_t ld_q, const float* Hm, int m, int64_t padding_index, int K,
+                           int* scores, int* chosen, float* sel, int* sel_valid, int64_t* sel_ids, int* oob_flag,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif
