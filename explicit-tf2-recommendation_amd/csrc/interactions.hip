@@ -179,31 +179,61 @@ __global__ __launch_bounds__(256) void emb_ipn_bwd_kernel(const float* __restric
 
 // Examples per workgroup.  A workgroup is load -> barrier -> compute -> store with nothing overlapped inside it, so
 // the overlap has to come from MANY resident workgroups per CU: keep the LDS of one at <= 16 KB (>= 8 per CU) and the
-// grid at >= 1024 workgroups; only a single example that needs more may take up to 64 KB.
-static int ipn_examples_per_group(int64_t B, int F, int E, bool bwd, size_t* lds) {
+// grid at >= 1024 workgroups; only a single example that needs more may take more: the forward up to 64 KB, the
+// backward (two copies of the rows' worth plus the F x F matrix) up to IPN_BWD_LDS_MAX through rec_allow_lds.
+constexpr int IPN_MAX_F = 255;                             // pair endpoints are bytes in LDS
+constexpr size_t IPN_FWD_LDS_MAX = 64 * 1024;
+
+constexpr size_t ipn_lds_bytes(int EX, int F, int64_t E, bool bwd) {
   const int P = F * (F - 1) / 2;
+  return bwd ? (size_t)EX * ((size_t)F * (E + 1) + (size_t)F * E + (size_t)F * F) * 4
+             : (size_t)EX * F * (E + 4) * 4 + (size_t)EX * F * 4 + 2 * (size_t)P + 16;
+}
+
+// what the backward of one example would need at the widest row the forward's 64 KB admits, over every F (the forward
+// formula grows by 4*F bytes per unit of E)
+constexpr size_t ipn_bwd_need() {
+  size_t need = 0;
+  for (int F = 1; F <= IPN_MAX_F; ++F) {
+    const size_t fixed = ipn_lds_bytes(1, F, 0, false);
+    if (fixed + 4 * (size_t)F > IPN_FWD_LDS_MAX) break;    // not even E = 1
+    const int64_t E = (int64_t)((IPN_FWD_LDS_MAX - fixed) / (4 * (size_t)F));
+    const size_t b = ipn_lds_bytes(1, F, E, true);
+    if (b > need) need = b;
+  }
+  return need;
+}
+// 241072 bytes (F = 244, E = 1) is more than a CU has, so the CU is the limit and the forward refuses what is beyond it
+constexpr size_t IPN_BWD_LDS_MAX = ipn_bwd_need() < REC_LDS_CU_BYTES ? ipn_bwd_need() : REC_LDS_CU_BYTES;
+
+static int ipn_examples_per_group(int64_t B, int F, int E, bool bwd, size_t* lds) {
   int EX = 8;
   while (EX > 1 && (B / EX) < 1024) EX >>= 1;
   for (;; EX >>= 1) {
-    size_t bytes = bwd ? (size_t)EX * ((size_t)F * (E + 1) + (size_t)F * E + (size_t)F * F) * 4
-                       : (size_t)EX * F * (E + 4) * 4 + (size_t)EX * F * 4 + 2 * (size_t)P + 16;
+    size_t bytes = ipn_lds_bytes(EX, F, E, bwd);
     if (bytes <= 16 * 1024 || EX == 1) {
       *lds = bytes;
-      return (bytes <= 64 * 1024) ? EX : 0;
+      return (bytes <= (bwd ? IPN_BWD_LDS_MAX : IPN_FWD_LDS_MAX)) ? EX : 0;
     }
   }
 }
 
+// ONE domain for both directions: a shape the forward takes must be trainable
+static bool ipn_shape_ok(int64_t B, int F, int E) {
+  size_t lds;
+  return ipn_examples_per_group(B, F, E, false, &lds) > 0 && ipn_examples_per_group(B, F, E, true, &lds) > 0;
+}
+
 extern "C" int rec_emb_ipn_fwd_f32(const float* table, int64_t V, int E, int64_t ld, const int64_t* X, int64_t B, int F,
                                    float* out, int64_t ld_out, int* oob_flag, void* stream) {
-  if (V <= 0 || V > INT32_MAX || E <= 0 || ld < E || B < 0 || F <= 0 || F > 255) return REC_E_ARG;
+  if (V <= 0 || V > INT32_MAX || E <= 0 || ld < E || B < 0 || F <= 0 || F > IPN_MAX_F) return REC_E_ARG;
   if (ld_out < (int64_t)F * E + (int64_t)F * (F - 1) / 2) return REC_E_ARG;
+  if (!ipn_shape_ok(B, F, E)) return REC_E_ARG;
   if (B == 0) return REC_OK;
   if (!table || !X || !out) return REC_E_ARG;
   const int vec4 = (E & 3) == 0 && (ld & 3) == 0 && rec_is_aligned16(table);
   size_t lds;
   int EX = ipn_examples_per_group(B, F, E, false, &lds);
-  if (!EX) return REC_E_ARG;
   hipLaunchKernelGGL(emb_ipn_fwd_kernel, dim3((unsigned)ceil_div64(B, EX)), dim3(256), lds, as_stream(stream), table, V,
                      E, ld, X, B, F, EX, vec4, out, ld_out, oob_flag);
   REC_LAUNCH_CHECK();
@@ -212,14 +242,15 @@ extern "C" int rec_emb_ipn_fwd_f32(const float* table, int64_t V, int E, int64_t
 
 extern "C" int rec_emb_ipn_bwd_vals_f32(const float* out, int64_t ld_out, const float* g, int64_t ld_g, int64_t B, int F,
                                         int E, float* vals, void* stream) {
-  if (E <= 0 || B < 0 || F <= 0 || F > 255) return REC_E_ARG;
+  if (E <= 0 || B < 0 || F <= 0 || F > IPN_MAX_F) return REC_E_ARG;
   const int64_t W = (int64_t)F * E + (int64_t)F * (F - 1) / 2;
   if (ld_out < W || ld_g < W) return REC_E_ARG;
+  if (!ipn_shape_ok(B, F, E)) return REC_E_ARG;
   if (B == 0) return REC_OK;
   if (!out || !g || !vals) return REC_E_ARG;
   size_t lds;
   int EX = ipn_examples_per_group(B, F, E, true, &lds);
-  if (!EX) return REC_E_ARG;
+  if (hipError_t err = rec_allow_lds<emb_ipn_bwd_kernel>(IPN_BWD_LDS_MAX)) return (int)err;
   hipLaunchKernelGGL(emb_ipn_bwd_kernel, dim3((unsigned)ceil_div64(B, EX)), dim3(256), lds, as_stream(stream), out,
                      ld_out, g, ld_g, B, F, E, EX, vals);
   REC_LAUNCH_CHECK();
@@ -607,14 +638,21 @@ __global__ __launch_bounds__(128) void ffm_bwd_rows_kernel(const float* __restri
   }
 }
 
+// ids [F], the 4 wave sums, the pair endpoints as bytes: the forward launches without the LDS opt-in, so the field limit
+// is the largest F whose request stays within the 64 KB every kernel may ask for (F = 255 would need 65806 bytes)
+constexpr size_t ffm_fwd_lds_bytes(int F) { return (size_t)F * 4 + 16 + (size_t)F * (F - 1); }
+constexpr int FFM_MAX_F = 254;
+static_assert(ffm_fwd_lds_bytes(FFM_MAX_F) <= 64 * 1024 && ffm_fwd_lds_bytes(FFM_MAX_F + 1) > 64 * 1024,
+              "FFM_MAX_F is the largest F that launches without rec_allow_lds");
+
 extern "C" int rec_ffm_fwd_f32(const float* v, int64_t ld_v, const float* w, int64_t ld_w, const float* bias, int64_t V,
                                int E, const int64_t* X, int64_t B, int F, float* z, float* prob, int* oob_flag,
                                void* stream) {
-  if (V <= 0 || V > INT32_MAX || E <= 0 || F <= 0 || F > 255 || ld_v < (int64_t)F * E || ld_w < 1 || B < 0)
+  if (V <= 0 || V > INT32_MAX || E <= 0 || F <= 0 || F > FFM_MAX_F || ld_v < (int64_t)F * E || ld_w < 1 || B < 0)
     return REC_E_ARG;
   if (B == 0) return REC_OK;
   if (!v || !w || !bias || !X || (!z && !prob)) return REC_E_ARG;
-  const size_t lds = (size_t)F * 4 + 16 + (size_t)F * (F - 1);
+  const size_t lds = ffm_fwd_lds_bytes(F);
   const bool vec = (E & 3) == 0 && (ld_v & 3) == 0 && rec_is_aligned16(v);
   if (vec)
     hipLaunchKernelGGL((ffm_fwd_kernel<true>), dim3((unsigned)B), dim3(256), lds, as_stream(stream), v, ld_v, w, ld_w,
@@ -629,7 +667,8 @@ extern "C" int rec_ffm_fwd_f32(const float* v, int64_t ld_v, const float* w, int
 extern "C" int rec_ffm_bwd_rows_f32(const float* v, int64_t ld_v, int64_t V, int E, const int64_t* X, int64_t B, int F,
                                     const float* gz, const int32_t* perm, const int32_t* seg_start,
                                     const int64_t* n_uniq, float* g_rows, void* stream) {
-  if (V <= 0 || E <= 0 || F <= 0 || ld_v < (int64_t)F * E || B < 0 || B * F > INT32_MAX) return REC_E_ARG;
+  if (V <= 0 || E <= 0 || F <= 0 || F > FFM_MAX_F || ld_v < (int64_t)F * E || B < 0 || B * F > INT32_MAX)
+    return REC_E_ARG;
   if (B == 0) return REC_OK;
   if (!v || !X || !gz || !perm || !seg_start || !n_uniq || !g_rows) return REC_E_ARG;
   const bool vec = (E & 3) == 0 && (ld_v & 3) == 0 &&

@@ -526,7 +526,8 @@ int rec_softmax_bwd_f32(const float* y, const float* gy, int64_t M, int N, float
 /* ---- PNN inner product: Embedding -> Flatten ++ IpnLayer (2.FM/CustomLayers.py:729-745, :755-792).
  * out[b, f*E + d] = table[X[b,f], d];  out[b, F*E + p(i,j)] = <e_i, e_j> for i < j in the row-major order of the
  * upper triangle (the order tf.boolean_mask keeps).  ld_out >= F*E + F*(F-1)/2: `out` IS the reference's
- * combined_vector.  F <= 255. */
+ * combined_vector.  Forward and backward accept the same shapes: F <= 255, 4*F*(E+4) + 4*F + F*(F-1) + 16 <= 65536 (the
+ * forward's LDS of one example) and 4*F*(2*E + 1 + F) <= 163840 (the backward's, one CU); REC_E_ARG beyond. */
 int rec_emb_ipn_fwd_f32(const float* table, int64_t V, int E, int64_t ld, const int64_t* X, int64_t B, int F,
                         float* out, int64_t ld_out, int* oob_flag, void* stream);
 /* IndexedSlices values of that lookup: vals[b*F+i, :] = g[b, i*E:(i+1)*E] + sum_{j != i} g[b, F*E + p(i,j)] * e_j,
@@ -556,7 +557,8 @@ int rec_ip_attn_bwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C,
 /* ---- FFM, field-aware second order (FieldAwareInteractionLayer 2.FM/CustomLayers.py:428-462; FFMRankingLayer.call
  * :398-425 computes the same numbers from F separate tables).  v [V, F, E] with row stride ld_v >= F*E floats:
  * v[id, c, :] is the vector id uses against field c (table c of the loop form, row id).
- *   z[b] = bias + sum_a w[X[b,a]] + sum_{a<c} < v[X[b,a], c, :], v[X[b,c], a, :] >,  prob = sigmoid(z). */
+ *   z[b] = bias + sum_a w[X[b,a]] + sum_{a<c} < v[X[b,a], c, :], v[X[b,c], a, :] >,  prob = sigmoid(z).
+ * F <= 254 in both directions (4*F + 16 + F*(F-1) bytes of LDS, launched without the opt-in). */
 int rec_ffm_fwd_f32(const float* v, int64_t ld_v, const float* w, int64_t ld_w, const float* bias, int64_t V, int E,
                     const int64_t* X, int64_t B, int F, float* z, float* prob, int* oob_flag, void* stream);
 /* de-duplicated gradient rows of v on the plan of rec_dedup_plan_i64 over X (n = B*F):
