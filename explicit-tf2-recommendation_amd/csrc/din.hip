@@ -20,12 +20,6 @@ constexpr float LN_EPS = 1e-3f;   // keras LayerNormalization epsilon
 
 enum { DACT_NONE = 0, DACT_RELU = 1, DACT_SIGMOID = 2, DACT_TANH = 3, DACT_DICE = 4, DACT_PRELU = 5 };
 
-__device__ __forceinline__ float wave_sum64(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // y = act(x) with per-feature parameters; also d y/d x and d y/d alpha
 __device__ __forceinline__ float feat_act(int kind, float x, float alpha, float mean, float var, float* dydx,
                                           float* dyda) {
@@ -782,7 +776,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
     v[j] = n < N ? x[row * N + n] : 0.f;
     s += v[j];
   }
-  float mu = wave_sum64(s) / (float)N;
+  float mu = group_sum<64>(s) / (float)N;
   float q = 0.f;
 #pragma unroll
   for (int j = 0; j < LN_MAXJ; ++j) {
@@ -790,7 +784,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
     float d = n < N ? v[j] - mu : 0.f;
     q += d * d;
   }
-  float r = rsqrtf(wave_sum64(q) / (float)N + LN_EPS);
+  float r = rsqrtf(group_sum<64>(q) / (float)N + LN_EPS);
 #pragma unroll
   for (int j = 0; j < LN_MAXJ; ++j) {
     int n = lane + 64 * j;
@@ -823,8 +817,8 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
     s2 += g[j] * xh[j];
     if (n < N && gg_elem) gg_elem[row * N + n] = gyv * xh[j];
   }
-  s1 = wave_sum64(s1) / (float)N;
-  s2 = wave_sum64(s2) / (float)N;
+  s1 = group_sum<64>(s1) / (float)N;
+  s2 = group_sum<64>(s2) / (float)N;
   float r = rstd[row];
 #pragma unroll
   for (int j = 0; j < LN_MAXJ; ++j) {
@@ -855,7 +849,7 @@ __global__ __launch_bounds__(256) void softmax_fwd_kernel(const float* __restric
     v[j] = n < N ? expf(v[j] - mx) : 0.f;
     s += v[j];
   }
-  s = wave_sum64(s);
+  s = group_sum<64>(s);
 #pragma unroll
   for (int j = 0; j < LN_MAXJ; ++j) {
     int n = lane + 64 * j;
@@ -870,7 +864,7 @@ __global__ __launch_bounds__(256) void softmax_bwd_kernel(const float* __restric
   if (row >= M) return;
   float s = 0.f;
   for (int n = lane; n < N; n += 64) s += y[row * N + n] * gy[row * N + n];
-  s = wave_sum64(s);
+  s = group_sum<64>(s);
   for (int n = lane; n < N; n += 64) gx[row * N + n] = y[row * N + n] * (gy[row * N + n] - s);
 }
 

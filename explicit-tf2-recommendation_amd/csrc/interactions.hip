@@ -379,13 +379,9 @@ extern "C" int rec_emb_bi_bwd_vals_f32(const float* table, int64_t V, int E, int
 // One workgroup per example, its 4 waves share the time axis; lane l owns dims l, l+64, ...; TB time steps are in
 // flight together per wave; padded steps are never read (their score and their gradient are zero by definition).
 // backward: gs_t = <gpooled, k_t>;  gq = sum_t valid*gs_t*k_t;  gkeys[b,t,:] = scores_t*gpooled + valid*gs_t*q.
+// sim_search_kernel (sim.hip) holds a copy of this body with its selection added, compiled with fp contract off; the
+// note there says why the two are not one template.  A fix to one goes into both.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float wave_sum64(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 template <int NPL, bool BWD>
 __global__ __launch_bounds__(256) void ip_attn_kernel(const float* __restrict__ embed, int64_t ld, int64_t V, int E,
                                                       int C, const int64_t* __restrict__ series, int64_t B, int T,
@@ -450,7 +446,7 @@ __global__ __launch_bounds__(256) void ip_attn_kernel(const float* __restrict__ 
         float part = 0.f;
 #pragma unroll
         for (int a = 0; a < NPL; ++a) part += (BWD ? gp[a] : qv[a]) * k[u][a];
-        dot = wave_sum64(part);
+        dot = group_sum<64>(part);
       }
       if (!BWD) {
         if (lane == 0) scores[b * T + t] = dot;
@@ -477,11 +473,6 @@ __global__ __launch_bounds__(256) void ip_attn_kernel(const float* __restrict__ 
   }
 }
 
-#define IP_ATTN_LAUNCH(NPL, BWD)                                                                                   \
-  hipLaunchKernelGGL((ip_attn_kernel<NPL, BWD>), dim3((unsigned)B), dim3(256), lds, as_stream(stream), \
-                     embed, ld, V, E, C, series, B, T, q, ld_q, padding_index, scores, pooled, ld_p, gpooled, ld_gp,   \
-                     gkeys, gq, oob_flag)
-
 static int ip_attn_launch(bool bwd, const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* series,
                           int64_t B, int T, const float* q, int64_t ld_q, int64_t padding_index, float* scores,
                           float* pooled, int64_t ld_p, const float* gpooled, int64_t ld_gp, float* gkeys, float* gq,
@@ -494,23 +485,16 @@ static int ip_attn_launch(bool bwd, const float* embed, int64_t ld, int64_t V, i
   if (B == 0) return REC_OK;
   if (!embed || !series || !q || !scores) return REC_E_ARG;
   const int npl = (D + 63) / 64;
-  if (!bwd) {
-    switch (npl) {
-      case 1: IP_ATTN_LAUNCH(1, false); break;
-      case 2: IP_ATTN_LAUNCH(2, false); break;
-      case 3: IP_ATTN_LAUNCH(3, false); break;
-      default: IP_ATTN_LAUNCH(4, false); break;
-    }
-  } else {
-    switch (npl) {
-      case 1: IP_ATTN_LAUNCH(1, true); break;
-      case 2: IP_ATTN_LAUNCH(2, true); break;
-      case 3: IP_ATTN_LAUNCH(3, true); break;
-      default: IP_ATTN_LAUNCH(4, true); break;
-    }
-  }
-  REC_LAUNCH_CHECK();
-  return REC_OK;
+  return rec_dispatch_1to4(npl, [&](auto n) {
+    auto go = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(256), lds, as_stream(stream), embed, ld, V, E, C, series, B, T,
+                         q, ld_q, padding_index, scores, pooled, ld_p, gpooled, ld_gp, gkeys, gq, oob_flag);
+    };
+    if (bwd) go(ip_attn_kernel<decltype(n)::value, true>);
+    else go(ip_attn_kernel<decltype(n)::value, false>);
+    REC_LAUNCH_CHECK();
+    return (int)REC_OK;
+  });
 }
 
 extern "C" int rec_ip_attn_fwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* series,

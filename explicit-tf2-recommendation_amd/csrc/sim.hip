@@ -2,8 +2,8 @@
 // multi-head attention of the exact search unit.
 //
 // Search (rec_sim_search_*): the body of ip_attn_kernel (interactions.hip) -- one workgroup per example, its 4 waves
-// share the time axis, lane l owns dims l, l + 64, ..., a step's score is wave_sum64 of the lane products, so it depends
-// on the values of the key and of q only and equal items tie bit for bit -- plus, in the same launch:
+// share the time axis, lane l owns dims l, l + 64, ..., a step's score is group_sum<64> of the lane products, so it
+// depends on the values of the key and of q only and equal items tie bit for bit -- plus, in the same launch:
 //   forward   rank[t] = <q, k_t> for a valid step, -inf for a padded one, kept in LDS; K rounds of a one-wave arg-max
 //             over rank (a candidate loses to an equal one with a lower index: tf.argsort(DESCENDING)[:K]); the K chosen
 //             rows are gathered again (L2-hot; a padded position's row too) into sel, with sel_valid and chosen.
@@ -44,12 +44,10 @@ __host__ __device__ inline size_t ss_lds_bytes(int T, int C, int D) {
   return (size_t)T * C * 4 + (size_t)4 * D * 4 + (size_t)T * 4 + SS_MAX_K * 4;
 }
 
-__device__ __forceinline__ float wave_sum64(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
+// The copy of ip_attn_kernel's body is kept on purpose, and a fix to one (the ids[t * C] validity test, say) goes into
+// both.  Hoisted into one __forceinline__ template over a hooks struct the two kernels kept their registers, occupancy
+// and bits, but the compiler ordered the address arithmetic of the unrolled steps differently and the backward kernels
+// ran 2.5 % (ip_attn, config G) and 3 - 4 % (this one, T = 100 and 1000) slower on the MI355X, twice in a row.
 template <int NPL, bool BWD>
 __global__ __launch_bounds__(256) void sim_search_kernel(
     const float* __restrict__ embed, int64_t ld, int64_t V, int E, int C, const int64_t* __restrict__ series, int64_t B,
@@ -124,7 +122,7 @@ __global__ __launch_bounds__(256) void sim_search_kernel(
         float part = 0.f;
 #pragma unroll
         for (int a = 0; a < NPL; ++a) part += (BWD ? gp[a] : qv[a]) * k[u][a];
-        dot = wave_sum64(part);
+        dot = group_sum<64>(part);
       }
       if (!BWD) {
         if (lane == 0) {

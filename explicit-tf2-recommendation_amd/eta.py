@@ -11,19 +11,14 @@ from .layers import (Activation, ConcatCols, Dense, Dice, Embedding, Layer, Laye
                      _initializer, _stack_ids, assemble_index, make_mlp_layer)
 
 
-def _ids_in_torch(inputs, names, device, series):
-    """the ids of ``names`` stacked on a last axis with torch alone, on any device: [B] or [B,1] features -> [B,F],
-    ``series`` features [B,T] -> [B,T,F]"""
+def _ids_in_torch(inputs, names, device):
+    """the ids of ``names`` stacked on a last axis with torch alone, on any device: [B] or [B,1] features -> [B,F]"""
     cols = []
     for name in names:
         t = torch.as_tensor(inputs[name]).to(device=device, dtype=torch.int64)
-        if not series:
-            if t.dim() not in (1, 2) or (t.dim() == 2 and t.shape[1] != 1):
-                raise ValueError("feature %r must have shape [B] or [B,1], got %s" % (name, tuple(t.shape)))
-            t = t.reshape(-1)
-        elif t.dim() != 2:
-            raise ValueError("feature %r must have shape [B,T], got %s" % (name, tuple(t.shape)))
-        cols.append(t)
+        if t.dim() not in (1, 2) or (t.dim() == 2 and t.shape[1] != 1):
+            raise ValueError("feature %r must have shape [B] or [B,1], got %s" % (name, tuple(t.shape)))
+        cols.append(t.reshape(-1))
     return torch.stack(cols, -1)
 
 
@@ -133,10 +128,11 @@ class ETALayer(Layer):
     def _forward_composed(self, inputs):
         table = self.embed.embeddings
         dev = table.device
-        X_item = _ids_in_torch(inputs, self.item_categorical_features, dev, False)
-        X_user = _ids_in_torch(inputs, self.user_and_context_categorical_features, dev, False)
-        X_short = _ids_in_torch(inputs, self.shortterm_series_features, dev, True)
-        X_long = _ids_in_torch(inputs, self.longterm_series_features, dev, True)
+        X_item = _ids_in_torch(inputs, self.item_categorical_features, dev)
+        X_user = _ids_in_torch(inputs, self.user_and_context_categorical_features, dev)
+        stack = lambda cols: torch.stack(cols, -1)         # torch alone: this path runs on any device
+        X_short = _stack_ids(inputs, self.shortterm_series_features, dev, stack)
+        X_long = _stack_ids(inputs, self.longterm_series_features, dev, stack)
         B = X_item.shape[0]
         if table.is_cuda:
             flag = ops.new_flag(dev) if self.check_ids else None

@@ -52,6 +52,39 @@ class GradSink:
         return ids, buf
 
 
+def _sink_dsts(sink, E, device, *id_tensors):
+    """First half of a fused lookup's gradient hand-off: where its backward writes the IndexedSlices values of each id
+    tensor ([B,n,C], or None for a lookup that is absent) -> (buf, a [B,n,C E] view of it per tensor), the views one
+    after the other behind the sink's head rows; without a sink (None, Nones) and the kernel wrapper allocates."""
+    if sink is None:
+        return None, [None] * len(id_tensors)
+    buf = sink.new_buf(sum(t.numel() for t in id_tensors if t is not None), E, device)
+    dsts, at = [], sink.n_head
+    for t in id_tensors:
+        dsts.append(None if t is None else buf[at:at + t.numel()].view(t.shape[0], t.shape[1], t.shape[2] * E))
+        at += 0 if t is None else t.numel()
+    return buf, dsts
+
+
+def _series_grad(ctx, ids, vals, V, E, sink=None, buf=None):
+    """Second half: the table's gradient of a fused series / item lookup.  ``ids`` and ``vals`` are one tensor each or
+    matching sequences (series first, then negatives; None entries are absent lookups), laid end to end in that order:
+    it defines the de-duplication plan.  With a sink the ids and ``buf`` (which holds the values) are left there for the
+    Gather's backward and None is returned; else sparse COO with de-duplicated rows, or None when the table needs no
+    gradient."""
+    if torch.is_tensor(ids):
+        ids, vals = (ids,), (vals,)
+    ids = [t for t in ids if t is not None]
+    ids = ids[0] if len(ids) == 1 else torch.cat([t.reshape(-1) for t in ids])
+    if sink is not None:
+        sink.ids, sink.buf = ids, buf
+        return None
+    if not ctx.needs_input_grad[0]:
+        return None
+    vals = [v.reshape(-1, E) for v in vals if v is not None]
+    return _sparse_grad(ops.DedupPlan(ids, V), vals[0] if len(vals) == 1 else torch.cat(vals), E, (V, E))
+
+
 class Gather(torch.autograd.Function):
     """Embedding(V,E)(X): K2.  Backward: sparse row gradient (K4)."""
 
@@ -353,11 +386,7 @@ class DinAttention(torch.autograd.Function):
             gpooled = torch.zeros((B, D), dtype=torch.float32, device=q.device)
         if gscores is not None:
             gscores = gscores.contiguous()
-        sink, buf, dst = ctx.sink, None, None
-        if sink is not None:                                 # values land behind the Gather's rows in one shared buffer
-            n_ser = series.numel()
-            buf = sink.new_buf(n_ser, E, embed.device)
-            dst = buf[sink.n_head:sink.n_head + n_ser].view(series.shape[0], series.shape[1], D)
+        buf, (dst,) = _sink_dsts(ctx.sink, E, embed.device, series)
         gkeys, gMext, gw2p, galphap, gb2p = ops.din_attn_bwd(embed, series, Mext, Wkd, kind, alpha, mean, var, w2, b2,
                                                              padding_index, mask_valid, scores, gpooled.contiguous(),
                                                              gkeys=dst, gscores=gscores)
@@ -371,12 +400,7 @@ class DinAttention(torch.autograd.Function):
         gW2 = ops.colsum(gw2p).reshape(H, 1)
         galpha = ops.colsum(galphap) if alpha is not None else None
         gb2 = ops.colsum(gb2p)
-        if sink is not None:
-            sink.ids, sink.buf = series, buf
-            gembed = None
-        else:
-            plan = ops.DedupPlan(series, V)
-            gembed = _sparse_grad(plan, gkeys.reshape(-1, E), E, (V, E))
+        gembed = _series_grad(ctx, series, gkeys, V, E, ctx.sink, buf)
         return gembed, gq, None, gW1, gb1, None, galpha, None, None, gW2, gb2, None, None, None, None, None
 
 
@@ -446,16 +470,9 @@ class IpAttention(torch.autograd.Function):
     def backward(ctx, gpooled, _gscores):
         embed, q, series, scores = ctx.saved_tensors
         V, E = embed.shape
-        sink, dst = ctx.sink, None
-        if sink is not None:
-            buf = sink.new_buf(series.numel(), E, embed.device)
-            dst = buf[sink.n_head:sink.n_head + series.numel()].view(series.shape[0], series.shape[1], -1)
+        buf, (dst,) = _sink_dsts(ctx.sink, E, embed.device, series)
         gkeys, gq = ops.ip_attn_bwd(embed, series, q, ctx.padding_index, scores, gpooled.contiguous(), gkeys=dst)
-        if sink is not None:
-            sink.ids, sink.buf = series, buf
-            return None, gq, None, None, None, None
-        plan = ops.DedupPlan(series, V)
-        return _sparse_grad(plan, gkeys.reshape(-1, E), E, (V, E)), gq, None, None, None, None
+        return _series_grad(ctx, series, gkeys, V, E, ctx.sink, buf), gq, None, None, None, None
 
 
 class BatchNorm(torch.autograd.Function):
@@ -911,13 +928,6 @@ class PLELevel(torch.autograd.Function):
         return (dxin, None, None, None, None) + tuple(grads)
 
 
-def _series_grad(ctx, series, gkeys, V, E):
-    """the table's gradient of a fused series / item lookup: sparse COO, rows de-duplicated"""
-    if not ctx.needs_input_grad[0]:
-        return None
-    return _sparse_grad(ops.DedupPlan(series, V), gkeys.reshape(-1, E), E, (V, E))
-
-
 class CapsuleRouting(torch.autograd.Function):
     """MultiInterestExtractorLayer.call fused with the series lookup (6.MIND/CustomLayers.py:111-138, 204-212;
     csrc/mind.hip): table, series ids [B,T,C], S [C E, Dc], the non-trainable logits B0 [K,T] -> the capsules [B,K,Dc].
@@ -1172,27 +1182,14 @@ class DmrMatch(torch.autograd.Function):
         B, D = xi.shape
         H = Wc.shape[1]
         c = lambda g: None if g is None else g.contiguous()
-        sink, buf, dk, dn = ctx.sink, None, None, None
-        n_ser, n_neg = series.numel(), negatives.numel()
-        if sink is not None:                                 # values land behind the Gather's rows in one shared buffer
-            buf = sink.new_buf(n_ser + n_neg, E, embed.device)
-            dk = buf[sink.n_head:sink.n_head + n_ser].view(B, series.shape[1], D)
-            dn = buf[sink.n_head + n_ser:sink.n_head + n_ser + n_neg].view(B, negatives.shape[1], D)
+        buf, (dk, dn) = _sink_dsts(ctx.sink, E, embed.device, series, negatives)
         gkeys, gneg, gitem, gq, dP, dWe, dz = ops.dmr_bwd(embed, series, negatives, xi, q, P, We, z, c(g_i2i), c(g_u2i),
                                                           c(g_aux), ctx.padding_index, gkeys=dk, gneg=dn)
         gxi = ops.gemm(gq, Wc, transB=True, epi=ops.EPI_ADD, e1=gitem)       # through u . xi and through q = xi Wc
         dWc = ops.gemm(xi, gq, transA=True)
         dWp = ops.gemm(pos, dP, transA=True)
         dpos = ops.gemm(dP, Wp, transB=True)
-        ids = torch.cat([series.reshape(-1), negatives.reshape(-1)])
-        if sink is not None:
-            sink.ids, sink.buf = ids, buf
-            gembed = None
-        elif ctx.needs_input_grad[0]:
-            vals = torch.cat([gkeys.reshape(-1, E), gneg.reshape(-1, E)])
-            gembed = _sparse_grad(ops.DedupPlan(ids, V), vals, E, (V, E))
-        else:
-            gembed = None
+        gembed = _series_grad(ctx, (series, negatives), (gkeys, gneg), V, E, ctx.sink, buf)
         return (gembed, gxi, None, None, dpos, dWc, dWp[:, :H], dWe[:, :H], dz[0], dWp[:, H:], dWe[:, H:], dz[1],
                 None, None, None)
 
@@ -1287,29 +1284,15 @@ class DienGru(torch.autograd.Function):
         embed, series, negatives, x, mask_ids, kernel, recurrent_kernel, bias, out = ctx.saved_tensors
         c = lambda g: None if g is None else g.contiguous()
         table = embed is not None
-        sink, buf, dk, dn = ctx.sink, None, None, None
+        buf, dk, dn = None, None, None
         if table:
             V, E = embed.shape
-            B, T, H = out.shape
-            n_ser = series.numel()
-            n_neg = negatives.numel() if negatives is not None else 0
-            if sink is not None:                             # values land behind the Gather's rows in one shared buffer
-                buf = sink.new_buf(n_ser + n_neg, E, embed.device)
-                dk = buf[sink.n_head:sink.n_head + n_ser].view(B, T, H)
-                if n_neg:
-                    dn = buf[sink.n_head + n_ser:sink.n_head + n_ser + n_neg].view(B, T, H)
+            buf, (dk, dn) = _sink_dsts(ctx.sink, E, embed.device, series, negatives)
         gaux = None if gaux is None else c(gaux).reshape(1)
         dx, dneg, dK, dU, db = ops.dien_gru_bwd(kernel, recurrent_kernel, bias, out, None if not table else c(dout),
                                                 c(dfin), gaux, embed, series, negatives, x, mask_ids,
                                                 ctx.padding_index, dx=dk, dneg=dn)
-        gembed = None
-        if table:
-            ids = series.reshape(-1) if negatives is None else torch.cat([series.reshape(-1), negatives.reshape(-1)])
-            if sink is not None:
-                sink.ids, sink.buf = ids, buf
-            elif ctx.needs_input_grad[0]:
-                vals = dx.reshape(-1, E) if negatives is None else torch.cat([dx.reshape(-1, E), dneg.reshape(-1, E)])
-                gembed = _sparse_grad(ops.DedupPlan(ids, V), vals, E, (V, E))
+        gembed = _series_grad(ctx, (series, negatives), (dx, dneg), V, E, ctx.sink, buf) if table else None
         return gembed, None, None, (None if table else dx), None, dK, dU, db, None, None, None, None
 
 
@@ -1380,18 +1363,9 @@ class SimSearch(torch.autograd.Function):
         V, E = embed.shape
         gpooled = torch.zeros_like(q) if gpooled is None else gpooled.contiguous()
         gsel = None if gsel is None else gsel.contiguous()
-        sink, dst = ctx.sink, None
-        if sink is not None:
-            buf = sink.new_buf(series.numel(), E, embed.device)
-            dst = buf[sink.n_head:sink.n_head + series.numel()].view(series.shape[0], series.shape[1], -1)
+        buf, (dst,) = _sink_dsts(ctx.sink, E, embed.device, series)
         gkeys, gq = ops.sim_search_bwd(embed, series, q, ctx.padding_index, scores, gpooled, chosen, gsel, gkeys=dst)
-        if sink is not None:
-            sink.ids, sink.buf = series, buf
-            return None, gq, None, None, None, None, None
-        gembed = None
-        if ctx.needs_input_grad[0]:
-            gembed = _sparse_grad(ops.DedupPlan(series, V), gkeys.reshape(-1, E), E, (V, E))
-        return gembed, gq, None, None, None, None, None
+        return _series_grad(ctx, series, gkeys, V, E, ctx.sink, buf), gq, None, None, None, None, None
 
 
 class EsuAttention(torch.autograd.Function):
@@ -1444,16 +1418,11 @@ class EtaSearch(torch.autograd.Function):
         none = (None,) * 8
         if gsel is None:
             return none
-        rows = gsel.contiguous().reshape(-1, E)               # row (b, j, c) belongs to sel_ids[b, j, c]
-        sink = ctx.sink
-        if sink is not None:
-            buf = sink.new_buf(rows.shape[0], E, rows.device)
-            buf[sink.n_head:sink.n_head + rows.shape[0]].copy_(rows)
-            sink.ids, sink.buf = sel_ids, buf
-            return none
-        if not ctx.needs_input_grad[0]:
-            return none
-        return (_sparse_grad(ops.DedupPlan(sel_ids, V), rows, E, (V, E)),) + none[1:]
+        gsel = gsel.contiguous()                             # row (b, j, c) of its [B K C, E] belongs to sel_ids[b, j, c]
+        buf, (dst,) = _sink_dsts(ctx.sink, E, gsel.device, sel_ids)
+        if dst is not None:
+            dst.copy_(gsel)
+        return (_series_grad(ctx, sel_ids, gsel, V, E, ctx.sink, buf),) + none[1:]
 
 
 def sim_loss(gsu_logits, esu_logits, label, alpha=0.2, beta=0.8):

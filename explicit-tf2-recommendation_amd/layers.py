@@ -1701,19 +1701,6 @@ class DINLayer(Layer):
                                   input_dim=n_profile * embedding_dims + D)
         self.padding_index = padding_index
 
-    def _series(self, inputs, device):
-        series_cols = []
-        for name in self.behavior_series_features:
-            t = inputs[name]
-            if not isinstance(t, torch.Tensor):
-                t = torch.as_tensor(t)
-            t = t.to(device=device, dtype=torch.int64).contiguous()
-            if t.dim() != 2:
-                raise ValueError("behaviour series %r must have shape [B,T]" % name)
-            series_cols.append(t)
-        B, T = series_cols[0].shape
-        return ops.index_pack(series_cols).reshape(B, T, len(series_cols))        # tf.stack(axis=2)
-
     def forward(self, inputs):
         prof_names = self.user_and_context_categorical_features + self.item_categorical_features
         X_cate = assemble_index(inputs, prof_names)
@@ -1725,7 +1712,7 @@ class DINLayer(Layer):
             # (always part of the lookup: as the smallest id it is unique 0 of owner 0 = slot 0 of the rows that come
             # back, so the attention kernel's mask `first series id == padding_index` becomes `slot == 0`); every
             # consumer then works on the local [P*cap, E] rows buffer with slots in place of ids
-            series = self._series(inputs, X_cate.device)
+            series = _stack_ids(inputs, self.behavior_series_features, X_cate.device)
             pad = torch.full((1,), self.padding_index, dtype=torch.int64, device=X_cate.device)
             n1, n2 = X_cate.numel(), series.numel()
             rows, slot = self.embed.exchange(torch.cat([X_cate.reshape(-1), series.reshape(-1), pad]), flag)
@@ -1748,7 +1735,7 @@ class DINLayer(Layer):
         profile = self.embed(X_cate, flag, sink)
         profile_output = profile.reshape(profile.shape[0], -1)
         q = profile[:, profile.shape[1] - n_item:, :].reshape(profile.shape[0], -1)
-        series = self._series(inputs, X_cate.device)
+        series = _stack_ids(inputs, self.behavior_series_features, X_cate.device)
         pooled, _ = self.din_activation_layer.attend(self.embed.embeddings, q, series, self.padding_index,
                                                      mask_valid, flag, sink)
         self._raise_if_oob(flag)
@@ -1883,23 +1870,14 @@ class GSULayer(Layer):
         sink = self.embed.grad_sink(X_item)        # the series lookups share the item lookup's de-duplication
         q = self.embed(X_item, flag, sink)
         q = q.reshape(q.shape[0], -1)
-        series_cols = []
-        for name in self.behavior_series_features:
-            t = inputs[name]
-            if not isinstance(t, torch.Tensor):
-                t = torch.as_tensor(t)
-            t = t.to(device=X_item.device, dtype=torch.int64).contiguous()
-            if t.dim() != 2:
-                raise ValueError("behaviour series %r must have shape [B,T]" % name)
-            series_cols.append(t)
-        B, T = series_cols[0].shape
-        series = ops.index_pack(series_cols).reshape(B, T, len(series_cols))      # tf.stack(axis=2)
+        series = _stack_ids(inputs, self.behavior_series_features, X_item.device)
+        B, T, C = series.shape
         pooled, _ = Fn.IpAttention.apply(self.embed.embeddings, q, series, self.padding_index, flag, sink)
         self._raise_if_oob(flag)
         X_combined = ConcatCols.apply(q, pooled)
-        result = {"output": self.mlp(X_combined), "valid_mask": series_cols[0] != self.padding_index}
+        result = {"output": self.mlp(X_combined), "valid_mask": series[:, :, 0] != self.padding_index}
         if self.return_series:
-            result["X_series"] = self.embed(series.reshape(B, T * len(series_cols))).reshape(B, T, -1)
+            result["X_series"] = self.embed(series.reshape(B, T * C)).reshape(B, T, -1)
         return result
 
 
@@ -2304,8 +2282,9 @@ class PEPNetLayer(Layer):
 # MIND: multi-interest retrieval (6.MIND/CustomLayers.py:62-285)
 # ---------------------------------------------------------------------------------------------------
 
-def _stack_ids(inputs, names, device):
-    """tf.stack(axis=2) of 2-D id features: [B,T] each -> int64 [B,T,len(names)] on ``device``."""
+def _stack_ids(inputs, names, device, pack=None):
+    """tf.stack(axis=2) of 2-D id features: [B,T] each -> int64 [B,T,len(names)] on ``device``.  ``pack``: what joins
+    the columns in place of ops.index_pack (a composed path that runs on torch alone, on any device)."""
     cols = []
     for name in names:
         t = inputs[name]
@@ -2316,7 +2295,7 @@ def _stack_ids(inputs, names, device):
             raise ValueError("feature %r must have shape [B,T], got %s" % (name, tuple(t.shape)))
         cols.append(t)
     B, T = cols[0].shape
-    return ops.index_pack(cols).reshape(B, T, len(cols))
+    return (pack or ops.index_pack)(cols).reshape(B, T, len(cols))
 
 
 def mind_capsule_count_table(max_length, capsules_num):

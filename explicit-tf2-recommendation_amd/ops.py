@@ -622,32 +622,6 @@ def emb_bi_bwd_vals(table, X, g, S):
     return vals
 
 
-def ip_attn_fwd(embed, series, q, padding_index, oob=None):
-    """series [B,T,C] int64, q [B,C*E] -> masked scores [B,T], pooled [B,C*E]  (7.SIM/CustomLayers.py:88-96)."""
-    _table(embed, "embed"); _i64(series, "series"); _f32(q, "q")
-    V, E = embed.shape
-    B, T, C = series.shape
-    D = C * E
-    scores, pooled = _new((B, T), embed.device), _new((B, D), embed.device)
-    _call("rec_ip_attn_fwd_f32", _ptr(embed), embed.stride(0), V, E, C, _ptr(series), B, T, _ptr(q), q.shape[1],
-          int(padding_index), _ptr(scores), _ptr(pooled), D, _ptr(oob))
-    return scores, pooled
-
-
-def ip_attn_bwd(embed, series, q, padding_index, scores, gpooled, gkeys=None):
-    _table(embed, "embed"); _i64(series, "series"); _f32(q, "q"); _f32(scores, "scores"); _f32(gpooled, "gpooled")
-    V, E = embed.shape
-    B, T, C = series.shape
-    D = C * E
-    if gkeys is None:
-        gkeys = _new((B, T, D), embed.device)
-    _f32(gkeys, "gkeys")
-    gq = _new((B, D), embed.device)
-    _call("rec_ip_attn_bwd_f32", _ptr(embed), embed.stride(0), V, E, C, _ptr(series), B, T, _ptr(q), q.shape[1],
-          int(padding_index), _ptr(scores), _ptr(gpooled), gpooled.shape[1], _ptr(gkeys), _ptr(gq))
-    return gkeys, gq
-
-
 def batchnorm_fwd(x, gamma, beta, moving_mean, moving_var, training, eps=1e-3, momentum=0.99, save=True):
     """Keras BatchNormalization on [B,N]; moving statistics are updated in place when training."""
     _f32(x, "x")
@@ -2687,14 +2661,43 @@ def sim_check_shape(D, T=None, K=None, H=None, dk=None, C=1):
                      "33 (max(H dk, H D) + 2 + 2 H K + H)", "K=%d, D=%d, H=%d, key_dim=%d" % (K, D, H, dk))
 
 
-def _sim_search_args(embed, series, q, padding_index, K):
-    head, (V, E, B, T, Cn) = _series_head(embed, series, "the SIM search")
+def _search_head(embed, series, q, what, K=None):
+    """What every entry point that searches a series for one query starts with: _series_head, q is [B, C E] and, where
+    K positions are selected, 1 <= K <= T.  -> the leading ABI arguments (.., q, its stride) and (V, E, B, T, C, D)."""
+    head, (V, E, B, T, Cn) = _series_head(embed, series, what)
     D = Cn * E
     _expect(q, (B, D), "q", "[B, C E]")
-    if not 1 <= K <= T:
-        raise ValueError("the SIM search selects 1 <= K <= T positions, got K=%d at T=%d" % (K, T))
-    sim_check_shape(D, T, K, C=Cn)
-    return head + [_ptr(q), D, int(padding_index), int(K)], (V, E, B, T, Cn, D)
+    if K is not None and not 1 <= K <= T:
+        raise ValueError("%s selects 1 <= K <= T positions, got K=%d at T=%d" % (what, K, T))
+    return head + [_ptr(q), D], (V, E, B, T, Cn, D)
+
+
+def ip_attn_fwd(embed, series, q, padding_index, oob=None):
+    """series [B,T,C] int64, q [B,C*E] -> masked scores [B,T], pooled [B,C*E]  (7.SIM/CustomLayers.py:88-96).  A shape
+    past the kernel's limits is the library's REC_E_ARG, a ValueError."""
+    head, (V, E, B, T, Cn, D) = _search_head(embed, series, q, "the GSU attention")
+    scores, pooled = _new((B, T), embed.device), _new((B, D), embed.device)
+    _call("rec_ip_attn_fwd_f32", *head, int(padding_index), _ptr(scores), _ptr(pooled), D, _ptr(oob))
+    return scores, pooled
+
+
+def ip_attn_bwd(embed, series, q, padding_index, scores, gpooled, gkeys=None):
+    """-> (gkeys [B,T,D]: the IndexedSlices values of the series lookup, gq [B,D]) from gpooled [B,D].  ``gkeys``:
+    optional preallocated contiguous destination."""
+    head, (V, E, B, T, Cn, D) = _search_head(embed, series, q, "the GSU attention")
+    _expect_all(((scores, (B, T), "scores"), (gpooled, (B, D), "gpooled")))
+    if gkeys is None:
+        gkeys = _new((B, T, D), embed.device)
+    _expect(gkeys, (B, T, D), "gkeys", "[B,T,D]")
+    gq = _new((B, D), embed.device)
+    _call("rec_ip_attn_bwd_f32", *head, int(padding_index), _ptr(scores), _ptr(gpooled), D, _ptr(gkeys), _ptr(gq))
+    return gkeys, gq
+
+
+def _sim_search_args(embed, series, q, padding_index, K):
+    head, dims = _search_head(embed, series, q, "the SIM search", K)
+    sim_check_shape(dims[5], dims[3], K, C=dims[4])
+    return head + [int(padding_index), int(K)], dims
 
 
 def sim_search_fwd(embed, series, q, padding_index, K, oob=None):
@@ -2820,20 +2823,16 @@ def eta_search_fwd(embed, series, q, Hm, padding_index, K, oob=None, want_scores
     sel_valid int32 [B,K], sel_ids int64 [B,K,C]): the Hamming similarity of the SimHash codes of every step and of q,
     the K best positions by it (padded steps rank as -inf, ties go to the lower index), their rows and their ids
     (7.SIM/CustomLayers.py:556-571).  One launch."""
-    head, (V, E, B, T, Cn) = _series_head(embed, series, "the ETA search")
-    D = Cn * E
-    _expect(q, (B, D), "q", "[B, C E]")
+    head, (V, E, B, T, Cn, D) = _search_head(embed, series, q, "the ETA search", K)
     if _f32(Hm, "Hm").dim() != 2 or Hm.shape[0] != D:
         raise ValueError("Hm must be [C E, m] = [%d, m], got %s" % (D, tuple(Hm.shape)))
     m = Hm.shape[1]
-    if not 1 <= K <= T:
-        raise ValueError("the ETA search selects 1 <= K <= T positions, got K=%d at T=%d" % (K, T))
     eta_check_shape(D, T, K, m, Cn)
     dev = embed.device
     scores = _new((B, T), dev, B, torch.int32) if want_scores else None
     chosen, sel_valid = _new((B, K), dev, B, torch.int32), _new((B, K), dev, B, torch.int32)
     sel, sel_ids = _new((B, K, D), dev, B), _new((B, K, Cn), dev, B, torch.int64)
     if B > 0:
-        _call("rec_eta_search_fwd_f32", *head, _ptr(q), D, _ptr(Hm), m, int(padding_index), int(K), _ptr(scores),
+        _call("rec_eta_search_fwd_f32", *head, _ptr(Hm), m, int(padding_index), int(K), _ptr(scores),
               _ptr(chosen), _ptr(sel), _ptr(sel_valid), _ptr(sel_ids), _ptr(oob))
     return scores, chosen, sel, sel_valid, sel_ids

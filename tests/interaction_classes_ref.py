@@ -366,7 +366,7 @@ def fsum(t, order, axis=-1):
 
 
 def _butterfly(part):
-    """wave_sum64 over the last axis (64 lanes): every lane ends with the same sum; lane 0's is returned"""
+    """group_sum<64> over the last axis (64 lanes): every lane ends with the same sum; lane 0's is returned"""
     lane = np.arange(64)
     for o in (32, 16, 8, 4, 2, 1):
         part = part + part[..., lane ^ o]

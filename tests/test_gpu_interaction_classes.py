@@ -21,7 +21,8 @@ the listed regimes, that the bounds leave room for a correct fp32 evaluation and
               the PNN pair products ((x0 y0 + x1 y1) + (x2 y2 + x3 y3) a float4 against a chain), the FFM z (4 products a
               lane item) nor the bi-interaction's out (fma contraction differs between the two instantiations);
   refusals    D = 257, T*C*4 + 16*D > 64 KB, FFM F = 256, a PNN shape beyond the common domain (F = 244), ld < E and
-              ld_out < W return REC_E_ARG with every output untouched; B = 0 is accepted;
+              ld_out < W return REC_E_ARG with every output untouched; ops.ip_attn_fwd / ip_attn_bwd raise ValueError for a
+              q that is not [B, C E] and launch nothing; B = 0 is accepted;
   layer       PNNLayer forward + backward at F = 80, E = 64 (the backward needs 66880 bytes of LDS and was refused before)
               against oracle/torch_ref.py in fp64, with every allocation of ops guarded.
 
@@ -388,6 +389,23 @@ def test_refusals_leave_every_output_alone(lib, E_ARG):
     }
     for what, call in calls.items():
         assert finish(call(), outs, [tab, ids, flag] + outs) == E_ARG, what
+    # the ops wrappers of the attention refuse a q of the wrong shape themselves: the kernel would read past its end
+    from explicit_tf2_recommendation_amd import ops
+    B, T, Cn, E = 2, 4, 2, 8
+    D = Cn * E
+    embed, series = torch.ones((10, E), device="cuda"), torch.ones((B, T, Cn), dtype=torch.int64, device="cuda")
+    scores, gpooled = torch.ones((B, T), device="cuda"), torch.ones((B, D), device="cuda")
+    gkeys = torch.full((B, T, D), SENT, device="cuda")
+    launched = []
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setattr(ops, "_call", lambda fn, *args: launched.append(fn))
+        for shape in ((B - 1, D), (B, D - 1)):
+            q = torch.ones(shape, device="cuda")
+            with pytest.raises(ValueError, match="q must be"):
+                ops.ip_attn_fwd(embed, series, q, 0)
+            with pytest.raises(ValueError, match="q must be"):
+                ops.ip_attn_bwd(embed, series, q, 0, scores, gpooled, gkeys=gkeys)
+    assert launched == [] and bool((gkeys == SENT).all())
 
 
 def test_an_empty_batch_is_accepted(lib):

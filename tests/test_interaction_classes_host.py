@@ -175,9 +175,14 @@ def test_thresholds_are_the_ones_in_the_source(text, common, src):
             "((reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(g_rows)) & 15) == 0;",
             "bool pad = id0 == padding_index;", "if (a == c) continue;"):
         assert line in text, "interactions.hip no longer holds: " + line
-    launches = re.findall(r"case (\d): IP_ATTN_LAUNCH\((\d), (false|true)\); break;", text)
-    assert sorted(launches) == sorted((str(n), str(n), b) for n in (1, 2, 3) for b in ("false", "true"))
-    assert re.findall(r"default: IP_ATTN_LAUNCH\((\d), (false|true)\); break;", text) == [("4", "false"), ("4", "true")]
+    # both directions launch ip_attn_kernel<npl, .> through the 1..4 dispatch of common.h: 1, 2, 3 as given, else 4
+    launch = _body(text, "static int ip_attn_launch(")
+    assert "return rec_dispatch_1to4(npl, [&](auto n) {" in launch
+    assert re.findall(r"go\(ip_attn_kernel<decltype\(n\)::value, (false|true)>\);", launch) == ["true", "false"]
+    dispatch = _body(common, "static inline int rec_dispatch_1to4(int n, Fn&& f) {")
+    assert re.findall(r"case (\d): return f\(std::integral_constant<int, (\d)>\{\}\);", dispatch) == [
+        ("1", "1"), ("2", "2"), ("3", "3")]
+    assert re.findall(r"default: return f\(std::integral_constant<int, (\d)>\{\}\);", dispatch) == ["4"]
 
 
 def test_byte_formulas_are_the_ones_in_the_source(src):
