@@ -21,15 +21,16 @@
 // product rounded before the sum (fp contract off).  So a projection depends on the values of its row and of Hm only --
 // never on t, the lane, T or the table's stride -- and steps with the same ids get the same codes bit for bit.  The
 // three instantiations by row access (16 floats in flight as four 16-byte loads, one 16-byte load, one float) run the
-// same operations in the same order.  The query's code is computed in every wave, lane j owning column j, with the same
-// operations, and leaves the wave as three ballots.  The three code planes of a step (positive, negative, NaN) are three
+// same operations in the same order (et_project of csrc/simhash.h, which csrc/sdim.hip shares).  The query's code is
+// computed in every wave, lane j owning column j, with the same operations, and leaves the wave as three ballots.
+// The three code planes of a step (positive, negative, NaN) are three
 // 32-bit words; equality is one popcount.  The rank is packed with the position as (rank + 1) << 24 | (T - 1 - t) (0 in
 // the upper part for a padded step), kept in LDS [T]; K rounds of an integer arg-max by wave 0 give chosen (the taken
 // entry is overwritten by -1), then the K rows are gathered again (cache-hot).  No float atomics, no scratch.
 //
 // Limits: m <= 32, K <= 16, D <= 256, V and B < 2^31, and 4 (D MC + T + 16) <= 65536 bytes of LDS (T = 2048 at C = 3,
 // E = 16 takes 11 KB; T = 15000 fits at D = 48).
-#include "common.h"
+#include "simhash.h"
 
 #pragma clang fp contract(off)
 
@@ -39,17 +40,8 @@ constexpr int ET_MAX_M = 32, ET_MAX_K = 16, ET_MAX_D = 256;
 constexpr int ET_TSHIFT = 24;                              // rank + 1 <= 33 above, T - 1 - t < 2^24 below
 constexpr size_t ET_LDS_CAP = 64 * 1024;
 
-__host__ __device__ inline int et_mc(int m) { return m <= 16 ? 16 : 32; }
-
 __host__ __device__ inline size_t et_lds_bytes(int T, int D, int m) {
   return sizeof(float) * ((size_t)D * et_mc(m) + (size_t)T + ET_MAX_K);
-}
-
-// acc_j += x Hm[d, j] for the MC columns of row d (hs: that row in LDS, the same address in every lane)
-template <int MC>
-__device__ __forceinline__ void et_row(float (&acc)[MC], float x, const float* hs) {
-#pragma unroll
-  for (int j = 0; j < MC; ++j) acc[j] = acc[j] + x * hs[j];
 }
 
 template <int MC, int CH>
@@ -88,29 +80,7 @@ __global__ __launch_bounds__(256) void eta_search_kernel(
     float acc[MC];
 #pragma unroll
     for (int j = 0; j < MC; ++j) acc[j] = 0.f;
-    for (int c = 0; c < C; ++c) {
-      const int64_t id = idp[c];
-      const bool ok = (uint64_t)id < (uint64_t)V;
-      bad |= !ok;
-      const float* row = embed + (ok ? id : 0) * ld;
-      const float* hs = Hs + c * E * MC;
-      for (int e = 0; e < E; e += CH) {
-        if constexpr (CH == 1) {
-          et_row<MC>(acc, ok ? row[e] : 0.f, hs + e * MC);
-        } else {
-          float4 x[CH / 4];
-#pragma unroll
-          for (int u = 0; u < CH / 4; ++u) x[u] = *reinterpret_cast<const float4*>(row + e + 4 * u);
-#pragma unroll
-          for (int u = 0; u < CH / 4; ++u) {
-            et_row<MC>(acc, ok ? x[u].x : 0.f, hs + (e + 4 * u) * MC);
-            et_row<MC>(acc, ok ? x[u].y : 0.f, hs + (e + 4 * u + 1) * MC);
-            et_row<MC>(acc, ok ? x[u].z : 0.f, hs + (e + 4 * u + 2) * MC);
-            et_row<MC>(acc, ok ? x[u].w : 0.f, hs + (e + 4 * u + 3) * MC);
-          }
-        }
-      }
-    }
+    et_project<MC, CH>(acc, bad, embed, ld, V, E, C, idp, Hs);
     uint32_t kp = 0, kn = 0, kx = 0;
 #pragma unroll
     for (int j = 0; j < MC; ++j) {

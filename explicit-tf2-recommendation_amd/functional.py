@@ -1425,6 +1425,41 @@ class EtaSearch(torch.autograd.Function):
         return (_series_grad(ctx, sel_ids, gsel, V, E, ctx.sink, buf),) + none[1:]
 
 
+class SdimInterest(torch.autograd.Function):
+    """SDIM's hash-bucket interest fused with the series lookup (8.DMR/CustomLayers.py:816-841; csrc/sdim.hip):
+    ``embed`` [V,E], the candidates' rows ``q`` [B,S,D], ``series`` ids [B,T,C], the frozen projection ``Hm`` [D,G,m]
+    -> (out [B,S,D], codes int32 [B,T], qcodes int32 [B,S], cnt int32 [B,S,G]); the last three carry no gradient.  One
+    launch each way.  ``sign`` and ``one_hot`` have no gradient, so neither ``q`` nor ``Hm`` receives one; every step
+    that collides with a candidate does, and the [B,T,D] IndexedSlices values are the only [B,T,D] tensor there ever is.
+    ``mask_mode``: 'reference' sums the padded rows and counts every step, as the reference writes it; 'valid' sums and
+    counts the valid ones.  ``sink``: a GradSink of a Gather of the same table whose output feeds ``q``; the series' ids
+    and values are left there and ride that lookup's de-duplication plan.  With no gradient arriving nothing is done."""
+
+    @staticmethod
+    def forward(ctx, embed, q, series, Hm, padding_index, mask_mode="reference", oob=None, sink=None):
+        if q.dim() == 3 and (q.stride(2) != 1 or (q.shape[1] > 1 and q.stride(0) != q.shape[1] * q.stride(1))):
+            q = q.contiguous()                               # one candidate per example: a strided view is read in place
+        out, codes, qcodes, cnt = ops.sdim_interest_fwd(embed, series, q, Hm.contiguous(), padding_index, mask_mode, oob)
+        ctx.save_for_backward(series, codes, qcodes, cnt)
+        ctx.shape, ctx.m, ctx.sink = tuple(embed.shape), Hm.shape[2], sink
+        ctx.padding_index, ctx.mask_mode = padding_index, mask_mode
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(codes, qcodes, cnt)
+        return out, codes, qcodes, cnt
+
+    @staticmethod
+    def backward(ctx, gout, _gcodes, _gqcodes, _gcnt):
+        series, codes, qcodes, cnt = ctx.saved_tensors
+        V, E = ctx.shape
+        none = (None,) * 8
+        if gout is None:
+            return none
+        buf, (dst,) = _sink_dsts(ctx.sink, E, series.device, series)
+        gkeys = ops.sdim_interest_bwd(series, E, ctx.m, ctx.padding_index, codes, qcodes, cnt, gout.contiguous(),
+                                      ctx.mask_mode, gkeys=dst)
+        return (_series_grad(ctx, series, gkeys, V, E, ctx.sink, buf),) + none[1:]
+
+
 def sim_loss(gsu_logits, esu_logits, label, alpha=0.2, beta=0.8):
     """The loss of SIM's train loop (7.SIM/ModelManager.py:173-180): tf.nn.softmax_cross_entropy_with_logits on the two
     heads' outputs -- which are softmax outputs already; the double softmax is the reference's and is kept -- weighted

@@ -2836,3 +2836,107 @@ def eta_search_fwd(embed, series, q, Hm, padding_index, K, oob=None, want_scores
         _call("rec_eta_search_fwd_f32", *head, _ptr(Hm), m, int(padding_index), int(K), _ptr(scores),
               _ptr(chosen), _ptr(sel), _ptr(sel_valid), _ptr(sel_ids), _ptr(oob))
     return scores, chosen, sel, sel_valid, sel_ids
+
+
+# ---------------------------------------------------------------------------------------------------
+# SDIM (8.DMR/CustomLayers.py:816-841; csrc/sdim.hip): the hash-bucket interest of the long series.  The limits are the
+# .hip file's and show through its size query.
+# ---------------------------------------------------------------------------------------------------
+SDIM_MAX_BITS, SDIM_MAX_S, SDIM_MAX_D, SDIM_MAX_T = 32, 16, 256, 65535        # csrc/sdim.hip's SD_MAX_*; 16-bit list entries
+_SDIM_LDS_CAP = 64 * 1024
+SDIM_MODES = {"reference": 0, "valid": 1}
+
+
+def sdim_lds_bytes(T, D, G, m):
+    """LDS of one example of the forward (include/mi355rec.h): the projection in 16 or 32 columns, the steps' codes, the
+    padding bit map, the candidates' codes and four waves' lists of matching steps (16-bit entries)"""
+    return 4 * (D * (16 if G * m <= 16 else 32) + T + 2 * ((T + 63) // 64) + 16 + 2 * (T + T % 2))
+
+
+def sdim_check_shape(D, T=None, S=None, G=None, m=None, C=None):
+    """ValueError for sizes that describe no SDIM interest, NotImplementedError naming the limit for shapes the kernels
+    do not cover (the ABI would return -2): the key width D = E C, the series length T, the S candidates, the G hash
+    groups of m bits and the C id columns of a step."""
+    given = [v for v in (D, T, S, G, m, C) if v is not None]
+    if min(given) < 1:
+        raise ValueError("every size of an SDIM interest must be positive, got D=%r, T=%r, S=%r, G=%r, m=%r, C=%r"
+                         % (D, T, S, G, m, C))
+    if C is not None and D % C:
+        raise ValueError("the key width D = embedding_dims * series features; got D=%d with C=%d" % (D, C))
+    if D > SDIM_MAX_D:
+        raise NotImplementedError("the SDIM interest covers a key width embedding_dims * series features <= %d; got %d"
+                                  % (SDIM_MAX_D, D))
+    if S is not None and S > SDIM_MAX_S:
+        raise NotImplementedError("the SDIM interest covers candidates <= %d per example; got %d" % (SDIM_MAX_S, S))
+    bits = (1 if G is None else G) * (1 if m is None else m)
+    if bits > SDIM_MAX_BITS:
+        raise NotImplementedError("the SDIM interest covers lsh_group_num * lsh_group_length <= %d hash bits; got %d"
+                                  % (SDIM_MAX_BITS, bits))
+    if T is not None:
+        G1 = 1 if G is None else G
+        need = sdim_lds_bytes(T, D, G1, bits // G1)
+        if need > _SDIM_LDS_CAP or T > SDIM_MAX_T:
+            raise NotImplementedError("the SDIM interest holds the projection and one example's codes in LDS: 4 (D MC + T "
+                                      "+ 2 ceil(T / 64) + 16 + 2 (T + T mod 2)) <= %d bytes with MC = 16 or 32 columns; got %d at "
+                                      "T=%d, D=%d, hash bits=%d" % (_SDIM_LDS_CAP, need, T, D, bits))
+
+
+def _sdim_mode(mask_mode):
+    if mask_mode not in SDIM_MODES:
+        raise ValueError("mask_mode must be 'reference' or 'valid', got %r" % (mask_mode,))
+    return SDIM_MODES[mask_mode]
+
+
+def sdim_interest_fwd(embed, series, q, Hm, padding_index, mask_mode="reference", oob=None):
+    """series [B,T,C] int64, q [B,S,C E] (the candidates' rows; a view with unit inner stride and any row stride), Hm
+    [C E, G, m] -> (out [B,S,D], codes int32 [B,T], qcodes int32 [B,S], cnt int32 [B,S,G]): the mean, per hash group, of
+    the steps whose group code equals the candidate's, averaged over the groups (8.DMR/CustomLayers.py:816-841), and
+    what the backward needs.  One launch."""
+    head, (V, E, B, T, Cn) = _series_head(embed, series, "the SDIM interest")
+    D = Cn * E
+    if not isinstance(q, torch.Tensor) or not q.is_cuda:
+        raise RuntimeError("q must be a tensor on the MI355X: the HIP path has no CPU fallback")
+    if q.dtype != torch.float32 or q.dim() != 3 or q.shape[0] != B or q.shape[2] != D:
+        raise ValueError("q must be fp32 [B, S, C E] = [%d, S, %d], got %s %s" % (B, D, q.dtype, tuple(q.shape)))
+    S = q.shape[1]
+    # row (b, s) starts at (b S + s) ld_q: a size-1 axis has no stride of its own
+    ld_q = q.stride(1) if S > 1 else (q.stride(0) if B > 1 else D)
+    if q.numel() and (q.stride(2) != 1 or ld_q < D or (S > 1 and B > 1 and q.stride(0) != S * ld_q)):
+        raise ValueError("q must have unit inner stride and one row stride >= C E over [B, S], got strides %s"
+                         % (tuple(q.stride()),))
+    if _f32(Hm, "Hm").dim() != 3 or Hm.shape[0] != D:
+        raise ValueError("Hm must be [C E, G, m] = [%d, G, m], got %s" % (D, tuple(Hm.shape)))
+    G, m = Hm.shape[1:]
+    mode = _sdim_mode(mask_mode)
+    sdim_check_shape(D, T, S, G, m, Cn)
+    dev = embed.device
+    out = _new((B, S, D), dev, B)
+    codes, qcodes = _new((B, T), dev, B, torch.int32), _new((B, S), dev, B, torch.int32)
+    cnt = _new((B, S, G), dev, B, torch.int32)
+    if B > 0:
+        _call("rec_sdim_interest_fwd_f32", *head, _ptr(q), ld_q, S, _ptr(Hm), G, m, int(padding_index), mode, _ptr(out),
+              _ptr(codes), _ptr(qcodes), _ptr(cnt), _ptr(oob))
+    return out, codes, qcodes, cnt
+
+
+def sdim_interest_bwd(series, E, m, padding_index, codes, qcodes, cnt, gout, mask_mode="reference", gkeys=None):
+    """-> gkeys [B,T,C E]: the IndexedSlices values of the series lookup, from gout [B,S,D] and the forward's codes,
+    qcodes and cnt; ``E``: the table's width, ``m``: the bits of a hash group.  ``gkeys``: optional preallocated
+    contiguous destination."""
+    if _i64(series, "series").dim() != 3 or _req(cnt, torch.int32, "cnt").dim() != 3:
+        raise ValueError("series must be [B,T,C] and cnt [B,S,G]")
+    (B, T, Cn), (S, G) = series.shape, cnt.shape[1:]
+    D = Cn * int(E)
+    mode = _sdim_mode(mask_mode)
+    sdim_check_shape(D, T, S, G, int(m), Cn)
+    _expect(codes, (B, T), "codes", "[B,T]", dtype=torch.int32)
+    _expect(qcodes, (B, S), "qcodes", "[B,S]", dtype=torch.int32)
+    _expect(cnt, (B, S, G), "cnt", "[B,S,G]", dtype=torch.int32)
+    _expect_all(((gout, (B, S, D), "gout"),))
+    if gkeys is None:
+        gkeys = _new((B, T, D), series.device, B)
+    _expect(gkeys, (B, T, D), "gkeys", "[B,T,D]")
+    if B > 0:
+        _call("rec_sdim_interest_bwd_f32", _ptr(series), int(E), Cn, B, T, G, int(m), S, int(padding_index), mode,
+              _ptr(codes), _ptr(qcodes), _ptr(cnt), _ptr(gout), D, _ptr(gkeys))
+    return gkeys

@@ -1544,6 +1544,44 @@ int rec_eta_search_fwd_f32(const float* embed, int64_t ld, int64_t V, int E, int
                            int* scores, int* chosen, float* sel, int* sel_valid, int64_t* sel_ids, int* oob_flag,
                            void* stream);
 
+/* ---- SDIM (SDIMLayer.generate_longterm_interest, once=True, 8.DMR/CustomLayers.py:816-841; csrc/sdim.hip): the
+ * hash-bucket interest of the long behaviour series.  D = E C.  key k_l = concat_c embed[series[b,l,c]], pad[b,l] =
+ * series[b,l,0] == padding_index (the first column alone).  q [B,S,D] with row stride ld_q holds the S candidates' rows,
+ * Hm [D,G,m] row-major (rec_eta_search's [D, G m]) the frozen projection.  Bit j of a row x's code is
+ * sum_d x_d Hm[d,j] > 0 (tf.where(sign == 1, 1, 0): a zero and a NaN projection give 0), the projection computed as
+ * rec_eta_search computes it -- d in order, the product rounded before the sum, dependent on the values of the row and of
+ * Hm only -- so equal ids give equal codes bit for bit; group g's code is bits [g m, (g+1) m).  An id outside [0, V)
+ * reads a zero row and sets *oob_flag (may be NULL).
+ *   match[s,l,g] = code_g(k_l) == code_g(q[b,s,:])
+ *   mode 0 ('reference', the text as written: it keeps the PADDED rows and counts every step)  w_l = pad[b,l], n_l = 1
+ *   mode 1 ('valid', the paper's intent)                                                       w_l = n_l = !pad[b,l]
+ *   Sum[s,g,d] = sum_{l: match} float(w_l) k_l[d], in increasing l from 0, every product and sum rounded to fp32
+ *   cnt[s,g]   = sum_{l: match} n_l
+ *   mean[s,g,d] = Sum / float(cnt), 0 where that is not finite (an empty bucket, a non-finite sum)
+ *   out[b,s,d]  = (mean[s,0,d] + mean[s,1,d] + .. in increasing g) / float(G)
+ * The forward writes out [B,S,D] and what makes the backward table-free: codes int32 [B,T] (the steps' packed codes),
+ * qcodes int32 [B,S] and cnt int32 [B,S,G].  The backward takes gout [B,S,D] with row stride ld_gout and writes, never
+ * adds to, gkeys [B,T,D] -- the IndexedSlices values of the one series lookup, as rec_sim_search_bwd_f32 does:
+ *   gkeys[b,l,d] = sum over s, then over g, from 0, of match[s,l,g] ((gout[b,s,d] / float(G)) / float(cnt[s,g]))
+ * for a step with w_l = 1 (cnt >= 1 wherever such a step matches) and +0 for a step with w_l = 0.  q and Hm receive no
+ * gradient (sign and one_hot carry none); the backward reads neither embed nor Hm.  For an element whose bucket sum was
+ * not finite the reference's gradient is zero; this ABI leaves that element's gradient UNDEFINED.  One launch each way,
+ * one workgroup per example, no float atomics: bit-identical run to run.
+ * Supported: G m <= 32, S <= 16, D <= 256, V and B < 2^31, 4 (D MC + T + 2 ceil(T / 64) + 16 + 2 (T + T mod 2)) <= 65536
+ * bytes of LDS with MC = 16 for G m <= 16 and 32 beyond (rec_sdim_lds_bytes: the forward's sum, 0: invalid or unsupported;
+ * the backward needs less).  T >= 65536 is refused as well (16-bit list entries); the LDS rule is the stricter one.
+ * Return codes, in this order: a size below 1 (B below 0): -1; a shape outside the limits: -2, from the sizes alone;
+ * ld < E, ld_q < D, ld_gout < D or a mode other than 0 and 1: -1; B == 0: 0, nothing is launched or written; a pointer
+ * that must not be NULL: -1. */
+size_t rec_sdim_lds_bytes(int T, int C, int E, int G, int m, int S);
+int rec_sdim_interest_fwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* series, int64_t B,
+                              int T, const float* q, int64_t ld_q, int S, const float* Hm, int G, int m,
+                              int64_t padding_index, int mode, float* out, int* codes, int* qcodes, int* cnt,
+                              int* oob_flag, void* stream);
+int rec_sdim_interest_bwd_f32(const int64_t* series, int E, int C, int64_t B, int T, int G, int m, int S,
+                              int64_t padding_index, int mode, const int* codes, const int* qcodes, const int* cnt,
+                              const float* gout, int64_t ld_gout, float* gkeys, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
