@@ -36,6 +36,9 @@ constexpr int AI_MAXG = 512;                   // workgroups (= workspace slots)
 constexpr int AI_TBMAX = 32;                   // examples per tile
 constexpr int AI_LDS_SOFT = 16384;             // floats of LDS a tile aims for (64 KiB: two workgroups per CU)
 constexpr size_t AI_LDS_MAX = REC_LDS_CU_BYTES;   // one example of the backward needs <= 128 KiB
+enum { AI_RES_NONE = REC_AUTOINT_RES_NONE, AI_RES_ADD = REC_AUTOINT_RES_ADD, AI_RES_LEARNED = REC_AUTOINT_RES_LEARNED };
+static_assert(AI_RES_NONE < AI_RES_ADD && AI_RES_ADD < AI_RES_LEARNED && AI_RES_LEARNED - AI_RES_NONE == 2,
+              "ai_shape takes the residual kinds as a range");
 
 struct AiShape {
   int64_t B;
@@ -207,9 +210,9 @@ __global__ __launch_bounds__(AI_NT) void autoint_fwd_out_kernel(AiShape s, int T
       if (c >= d) continue;
       float z = acc[c];
       if (o) o[grow + c] = z;
-      if (s.res == 1) {
+      if (s.res == AI_RES_ADD) {
         z += xr[hd + c];
-      } else if (s.res == 2) {
+      } else if (s.res == AI_RES_LEARNED) {
         float rr = 0.f;
         for (int k = 0; k < E; ++k) rr = fmaf(xr[k], Wr[k * E + hd + c], rr);
         z += rr;
@@ -278,7 +281,7 @@ __global__ __launch_bounds__(AI_NT) void autoint_bwd_stats_kernel(AiShape s, int
 
 // ------------------------------------------------------------------------------------------------------------------
 // backward pass 2: persistent grid; LDS X | Q | K | V | dZ | dQ | dK | dV, each [TB, F, E]
-// slot of workgroup g [nWE] = dWq | dWk | dWv | dWres (res == 2) | dcemb [C, E]
+// slot of workgroup g [nWE] = dWq | dWk | dWv | dWres (AI_RES_LEARNED) | dcemb [C, E]
 // ------------------------------------------------------------------------------------------------------------------
 template <int DC>
 __global__ __launch_bounds__(AI_NT) void autoint_bwd_main_kernel(AiShape s, int TB, const float* __restrict__ x,
@@ -403,9 +406,9 @@ __global__ __launch_bounds__(AI_NT) void autoint_bwd_main_kernel(AiShape s, int 
         acc = fmaf(gk[e], Wk[k * E + e], acc);
         acc = fmaf(gv[e], Wv[k * E + e], acc);
       }
-      if (s.res == 1) {
+      if (s.res == AI_RES_ADD) {
         acc += Ds[t];
-      } else if (s.res == 2) {
+      } else if (s.res == AI_RES_LEARNED) {
         const float* dz = Ds + (t - k);
         for (int e = 0; e < E; ++e) acc = fmaf(dz[e], Wr[k * E + e], acc);
       }
@@ -436,7 +439,9 @@ __global__ __launch_bounds__(AI_NT) void autoint_bwd_main_kernel(AiShape s, int 
 
 // 0 ok (B == 0 included), REC_E_ARG, REC_E_UNSUPPORTED
 static int ai_shape(int64_t B, int F, int E, int H, int C, int res, int scaling, AiShape* s) {
-  if (B < 0 || F < 0 || E < 0 || H < 0 || C < 0 || res < 0 || res > 2 || scaling < 0 || scaling > 1) return REC_E_ARG;
+  if (B < 0 || F < 0 || E < 0 || H < 0 || C < 0 || res < AI_RES_NONE || res > AI_RES_LEARNED || scaling < 0 ||
+      scaling > 1)
+    return REC_E_ARG;
   if (F < 1 || F > AI_MAXF || E < 1 || E > AI_MAXE || H < 1 || H > E || E % H != 0 || C >= F) return REC_E_UNSUPPORTED;
   if (B > 0x7fffffffLL || B > ((int64_t)1 << 40) / ((int64_t)F * E)) return REC_E_UNSUPPORTED;
   *s = AiShape{};
@@ -449,7 +454,7 @@ static int ai_shape(int64_t B, int F, int E, int H, int C, int res, int scaling,
   s->Fc = F - C;
   s->res = res;
   s->HFF = H * F * F;
-  s->nmat = res == 2 ? 4 : 3;
+  s->nmat = res == AI_RES_LEARNED ? 4 : 3;
   s->nWE = s->nmat * E * E + C * E;
   s->scale = scaling ? (float)(1.0 / sqrt((double)s->d)) : 1.f;
   return REC_OK;
@@ -517,7 +522,8 @@ extern "C" int rec_autoint_fwd_f32(const float* x, const float* x_cont, const fl
   AiShape s;
   const int rc = ai_shape(B, F, E, H, C, res, scaling, &s);
   if (rc != REC_OK || B == 0) return rc;
-  if (!x || (C > 0 && (!x_cont || !cemb)) || !Wq || !Wk || !Wv || (res == 2 && !Wres) || !y || !stats || !workspace)
+  if (!x || (C > 0 && (!x_cont || !cemb)) || !Wq || !Wk || !Wv || (res == AI_RES_LEARNED && !Wres) || !y || !stats ||
+      !workspace)
     return REC_E_ARG;
   const AiCfg k = ai_cfg(s);
   if (workspace_bytes < ai_ws_bytes(s, k)) return REC_E_WORKSPACE;
@@ -549,8 +555,8 @@ extern "C" int rec_autoint_bwd_f32(const float* x, const float* x_cont, const fl
   AiShape s;
   const int rc = ai_shape(B, F, E, H, C, res, scaling, &s);
   if (rc != REC_OK || B == 0) return rc;
-  if (!x || (C > 0 && (!x_cont || !cemb || !dcemb)) || !Wq || !Wk || !Wv || (res == 2 && (!Wres || !dWres)) || !y ||
-      !dy || !stats || !dx || !dWq || !dWk || !dWv || !workspace)
+  if (!x || (C > 0 && (!x_cont || !cemb || !dcemb)) || !Wq || !Wk || !Wv ||
+      (res == AI_RES_LEARNED && (!Wres || !dWres)) || !y || !dy || !stats || !dx || !dWq || !dWk || !dWv || !workspace)
     return REC_E_ARG;
   const AiCfg k = ai_cfg(s);
   if (workspace_bytes < ai_ws_bytes(s, k)) return REC_E_WORKSPACE;
@@ -583,6 +589,6 @@ extern "C" int rec_autoint_bwd_f32(const float* x, const float* x_cont, const fl
   if (r != REC_OK) return r;
   const int EE = E * E;
   return rec_slot_sum(REC_SLOTS_WAVE, s.nWE, k.grid[3], dws,
-                      {{dWq, dWk, dWv, res == 2 ? dWres : dcemb, dcemb},
-                       {EE, EE, EE, res == 2 ? EE : C * E, res == 2 ? C * E : 0}}, st);
+                      {{dWq, dWk, dWv, res == AI_RES_LEARNED ? dWres : dcemb, dcemb},
+                       {EE, EE, EE, res == AI_RES_LEARNED ? EE : C * E, res == AI_RES_LEARNED ? C * E : 0}}, st);
 }

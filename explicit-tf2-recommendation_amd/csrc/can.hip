@@ -17,8 +17,8 @@ namespace {
 
 constexpr int CAN_NTHR = 256;
 constexpr int CAN_MAX_W = REC_AFM_MAX_E;            // the widest layer: 64
-constexpr int CAN_MAX_L = 4;                        // layers, and orders
-constexpr size_t CAN_LDS_CAP = 150 * 1024;
+constexpr int CAN_MAX_L = REC_CAN_MAX_L;            // layers, and orders
+constexpr size_t CAN_LDS_CAP = REC_TILE_LDS_CAP;
 constexpr int CAN_GRID = 2048;                      // workgroups of a launch: beyond it a workgroup takes another example
 constexpr int CAN_TP = 4;                           // positions per thread of a forward layer
 constexpr int CAN_RED = 256;                        // floats of the pooled sum's partials
@@ -103,6 +103,8 @@ struct CanArgs {
   int T, E, act;
   CanShape s;
 };
+static_assert(sizeof(CanArgs) + 7 * sizeof(void*) <= 4096,
+              "CanArgs is passed by value: its arrays of CAN_MAX_L entries fit the 4 KiB of kernel arguments");
 
 __device__ __forceinline__ float can_act(int act, float z) {
   switch (act) {

@@ -12,10 +12,10 @@
 
 namespace {
 
-// the limits are DIN's and AFM's: the header gains no constant for these families
-constexpr int MI_MAXD = REC_DIN_MAX_D, MI_MAXK = REC_AFM_MAX_A, MI_MAXR = 8;
+// the widths and the capsules are DIN's and AFM's limits; the rounds and the launch cap are the header's own
+constexpr int MI_MAXD = REC_DIN_MAX_D, MI_MAXK = REC_AFM_MAX_A, MI_MAXR = REC_CAPSULE_MAX_R;
 constexpr int MI_NTHR = 256;
-constexpr size_t MI_LDS_CAP = 150 * 1024;
+constexpr size_t MI_LDS_CAP = REC_TILE_LDS_CAP;
 static_assert(MI_LDS_CAP <= REC_LDS_CU_BYTES, "the launch cap fits the LDS of a CU");
 
 __host__ __device__ inline int mi_odd(int n) { return n | 1; }

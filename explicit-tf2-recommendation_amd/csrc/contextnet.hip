@@ -130,7 +130,7 @@ using Tile = TileOps<MB_T, MB_LD, CN_NTHR>;
 __host__ __device__ inline size_t cn_lds_floats(int D, int bwd) {
   return (size_t)((bwd ? 2 : 1) * mb_even(D) + MB_HC) * MB_LD;
 }
-constexpr size_t CN_LDS_CAP = 156 * 1024;
+constexpr size_t CN_LDS_CAP = REC_POSO_LDS_CAP;
 static_assert(sizeof(float) * (2 * CN_MAXD + MB_HC) * MB_LD <= CN_LDS_CAP && CN_LDS_CAP <= REC_LDS_CU_BYTES,
               "the backward of the largest block fits the LDS of a CU");
 

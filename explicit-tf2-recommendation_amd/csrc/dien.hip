@@ -38,8 +38,9 @@ namespace {
 
 constexpr int DN_NTHR = 256, DN_LD = MB_LD;
 constexpr int DN_MAXSLOTS = 2048;                 // workgroups of a launch at the most: each owns a slot
-constexpr size_t DN_LDS_CAP = 150 * 1024;
-enum { DN_GRU = 0, DN_AUGRU = 1, DN_AGRU = 2 };
+constexpr size_t DN_LDS_CAP = REC_TILE_LDS_CAP;
+enum { DN_GRU = REC_DIEN_GRU, DN_AUGRU = REC_DIEN_AUGRU, DN_AGRU = REC_DIEN_AGRU };
+static_assert(DN_GRU < DN_AUGRU && DN_AUGRU < DN_AGRU && DN_AGRU - DN_GRU == 2, "dn_check takes the modes as a range");
 
 struct DnArgs {
   const float* embed;        // table mode: x_t = concat_r embed[series[b,t,r]]; NULL: dense mode, x [B,T,H]

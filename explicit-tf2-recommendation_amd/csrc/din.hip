@@ -877,7 +877,7 @@ int attn_shape_status(int H, int E, int C, int T) {
   if (D > REC_DIN_WIDE_D && H > REC_DIN_WIDE_MAX_H) return REC_E_UNSUPPORTED;
   return REC_OK;
 }
-constexpr size_t ATTN_LDS_CAP = 150 * 1024;
+constexpr size_t ATTN_LDS_CAP = REC_TILE_LDS_CAP;
 // every class attn_shape_status admits fits, the refused corner <4, 16> does not
 static_assert(sizeof(float) * AL<3, 16, true>::total <= ATTN_LDS_CAP &&
                   sizeof(float) * AL<4, 8, true>::total <= ATTN_LDS_CAP &&

@@ -28,17 +28,22 @@
 // the upper part for a padded step), kept in LDS [T]; K rounds of an integer arg-max by wave 0 give chosen (the taken
 // entry is overwritten by -1), then the K rows are gathered again (cache-hot).  No float atomics, no scratch.
 //
-// Limits: m <= 32, K <= 16, D <= 256, V and B < 2^31, and 4 (D MC + T + 16) <= 65536 bytes of LDS (T = 2048 at C = 3,
-// E = 16 takes 11 KB; T = 15000 fits at D = 48).
+// Limits, the header's: m <= REC_ETA_MAX_M, K <= REC_SEARCH_MAX_K, D <= REC_SEARCH_MAX_D, V and B < 2^31, and
+// 4 (D MC + T + REC_SEARCH_MAX_K) <= REC_SEARCH_LDS_CAP bytes of LDS (T = 2048 at C = 3, E = 16 takes 11 KB; T = 15000
+// fits at D = 48).
 #include "simhash.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int ET_MAX_M = 32, ET_MAX_K = 16, ET_MAX_D = 256;
+constexpr int ET_MAX_M = REC_ETA_MAX_M, ET_MAX_K = REC_SEARCH_MAX_K, ET_MAX_D = REC_SEARCH_MAX_D;
 constexpr int ET_TSHIFT = 24;                              // rank + 1 <= 33 above, T - 1 - t < 2^24 below
-constexpr size_t ET_LDS_CAP = 64 * 1024;
+constexpr size_t ET_LDS_CAP = REC_SEARCH_LDS_CAP;
+static_assert(ET_MAX_M <= 32 && ((int64_t)(ET_MAX_M + 1) << ET_TSHIFT) <= INT32_MAX,
+              "a code plane is one 32-bit word, and the packed rank a positive int");
+static_assert(sizeof(float) * (ET_MAX_D * 32 + ET_MAX_K) < ET_LDS_CAP,
+              "the widest key's projection in 32 columns and the ET_MAX_K chosen positions leave LDS for the steps");
 
 __host__ __device__ inline size_t et_lds_bytes(int T, int D, int m) {
   return sizeof(float) * ((size_t)D * et_mc(m) + (size_t)T + ET_MAX_K);

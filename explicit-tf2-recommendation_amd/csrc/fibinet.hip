@@ -26,6 +26,9 @@ namespace {
 
 constexpr int FB_NT = 256;                       // 4 waves
 constexpr int FB_MAXF = REC_FIBINET_MAX_F, FB_MAXE = REC_FIBINET_MAX_E, FB_MAXC = REC_FIBINET_MAX_C;
+enum { FB_ALL = REC_FIBINET_TYPE_ALL, FB_EACH = REC_FIBINET_TYPE_EACH, FB_INTERACTION = REC_FIBINET_TYPE_INTERACTION };
+static_assert(FB_ALL < FB_EACH && FB_EACH < FB_INTERACTION && FB_INTERACTION - FB_ALL == 2,
+              "fb_shape takes the types as a range");
 constexpr int FB_MAXX_BLOCKS = 1024;             // persistent grid of the dx kernel: at most 4096 dS slots
 constexpr int FB_TARGET_W_BLOCKS = 2048;         // workgroups of the dW kernel (items x chunks)
 constexpr int FB_MAX_CHUNKS = 64;
@@ -52,7 +55,7 @@ __device__ __forceinline__ int pair_index(int F, int i, int j) { return i * F - 
 
 // item -> left field i, weight w, right fields [j0, j1)
 __device__ __forceinline__ void item_of(const FbShape& s, int it, int& i, int& w, int& j0, int& j1) {
-  if (s.type == 2) {
+  if (s.type == FB_INTERACTION) {
     int p = it;
     i = 0;
     while (p >= s.F - 1 - i) {
@@ -64,7 +67,7 @@ __device__ __forceinline__ void item_of(const FbShape& s, int it, int& i, int& w
     j1 = j0 + 1;
   } else {
     i = it;
-    w = s.type == 1 ? it : 0;
+    w = s.type == FB_EACH ? it : 0;
     j0 = it + 1;
     j1 = s.F;
   }
@@ -261,7 +264,7 @@ __global__ __launch_bounds__(FB_NT) void fibinet_bwd_x_kernel(FbShape s, const f
             da[r * F + j] += as[r * F + i] * sr;
           }
         }
-        if (s.type != 2 && j + 1 < j1) continue;    // 'all' / 'each': u summed over j, one u W^T per item
+        if (s.type != FB_INTERACTION && j + 1 < j1) continue;   // 'all' / 'each': u summed over j, one u W^T per item
         // dv_i += u W^T: u to LDS in D layout, back as the A operand (row c, k = e)
 #pragma unroll
         for (int u = 0; u < NTC; ++u) {
@@ -439,7 +442,7 @@ __global__ __launch_bounds__(FB_NT) void fibinet_bwd_w_kernel(FbShape s, const f
 
 // 0 ok (B == 0 included), REC_E_ARG, REC_E_UNSUPPORTED
 static int fb_shape(int64_t B, int F, int E, int C, int mid, int type, FbShape* s) {
-  if (B < 0 || F < 0 || E < 0 || C < 0 || mid < 0 || type < 0 || type > 2) return REC_E_ARG;
+  if (B < 0 || F < 0 || E < 0 || C < 0 || mid < 0 || type < FB_ALL || type > FB_INTERACTION) return REC_E_ARG;
   if (F < 2 || F > FB_MAXF || E < 1 || E > FB_MAXE || C > FB_MAXC || mid < 1 || mid > F) return REC_E_UNSUPPORTED;
   if (B > ((int64_t)1 << 40) / 64) return REC_E_UNSUPPORTED;
   *s = FbShape{};
@@ -450,8 +453,8 @@ static int fb_shape(int64_t B, int F, int E, int C, int mid, int type, FbShape* 
   s->mid = mid;
   s->type = type;
   s->P = F * (F - 1) / 2;
-  s->nW = type == 0 ? 1 : (type == 1 ? F - 1 : s->P);
-  s->nitem = type == 2 ? s->P : F - 1;
+  s->nW = type == FB_ALL ? 1 : (type == FB_EACH ? F - 1 : s->P);
+  s->nitem = type == FB_INTERACTION ? s->P : F - 1;
   s->D = 2LL * s->P * E + C;
   return REC_OK;
 }
@@ -548,7 +551,7 @@ extern "C" int rec_fibinet_bwd_f32(const float* x_emb, const float* g, const flo
   if (r != REC_OK) return r;
   // dW: the chunks in chunk order, a slot holding the chunk's nitem = nW matrices; 'all' has one W, which takes every
   // (chunk, item) in that order
-  const int nw = s.nW * E * E, nws = (int)(type == 0 ? k.nchunk * s.nitem : k.nchunk);
+  const int nw = s.nW * E * E, nws = (int)(type == FB_ALL ? k.nchunk * s.nitem : k.nchunk);
   r = rec_slot_sum(REC_SLOTS_SERIAL, nw, nws, wsl, {{dW}, {nw}}, st);
   if (r != REC_OK) return r;
   return rec_slot_sum(REC_SLOTS_WAVE, 2 * F * mid, (int)k.nslot, dsl, {{dS0, dS1}, {F * mid, F * mid}}, st);

@@ -52,6 +52,10 @@ namespace {
 constexpr int FP_MAXF = REC_FIBINET_MAX_F, FP_MAXE = REC_FIBINET_MAX_E, FP_MAXD = REC_MASKNET_MAX_D;
 constexpr int FP_MAXO = REC_MASKNET_MAX_O, FP_MAXMID = REC_MASKNET_MAX_P;
 constexpr int FP_MAXP = FP_MAXF * (FP_MAXF - 1) / 2;
+// the bilinear type is FiBiNet's code
+enum { FP_ALL = REC_FIBINET_TYPE_ALL, FP_EACH = REC_FIBINET_TYPE_EACH, FP_INTERACTION = REC_FIBINET_TYPE_INTERACTION };
+static_assert(FP_ALL < FP_EACH && FP_EACH < FP_INTERACTION && FP_INTERACTION - FP_ALL == 2,
+              "the shape check takes the types as a range");
 constexpr float FP_EPS = 1e-3f;                  // Keras' default epsilon of both normalisations
 constexpr float FP_MOMENTUM = 0.99f;             // tf.keras.layers.BatchNormalization()
 constexpr int FP_NTHR = 256;
@@ -301,7 +305,9 @@ __device__ __forceinline__ void fp_pair_table(int* pij, int F, int P, int tid) {
   }
 }
 __device__ __forceinline__ int fp_pair_index(int i, int j, int F) { return i * (2 * F - i - 1) / 2 + j - i - 1; }
-__device__ __forceinline__ int fp_weight_of(int type, int i, int t) { return type == 0 ? 0 : (type == 1 ? i : t); }
+__device__ __forceinline__ int fp_weight_of(int type, int i, int t) {
+  return type == FP_ALL ? 0 : (type == FP_EACH ? i : t);
+}
 
 // the sum over the 16 column groups of an example, groups added in order: every thread of the example gets the same bits
 __device__ __forceinline__ float fp_rowsum(float v, float* sc, int b, int g) {
@@ -625,10 +631,10 @@ __global__ __launch_bounds__(FP_NTHR) void fibinetplus_dw_kernel(const float* __
   const int oe = own ? o / E : 0, oj = own ? o - oe * E : 0;
   const int64_t b0 = (int64_t)blockIdx.y * per, b1 = b0 + per < B ? b0 + per : B;
   int i0 = 0, i1 = F - 1, jf = -1;               // 'all': every pair
-  if (type == 1) {
+  if (type == FP_EACH) {
     i0 = wi;
     i1 = wi + 1;
-  } else if (type == 2) {
+  } else if (type == FP_INTERACTION) {
     int i = 0, rem = wi;
     while (rem >= F - 1 - i) {
       rem -= F - 1 - i;
@@ -663,13 +669,15 @@ __global__ __launch_bounds__(FP_NTHR) void fibinetplus_dw_kernel(const float* __
 static int fp_shape(int64_t B, const FpDims& d) {
   if (B < 0 || d.F < 0 || d.E < 0 || d.G < 0 || d.mid < 0 || d.O < 0) return REC_E_ARG;
   if (d.F < 2 || d.F > FP_MAXF || d.E < 1 || d.E > FP_MAXE || (int64_t)d.F * d.E > FP_MAXD || d.O < 1 ||
-      d.O > FP_MAXO || d.mid < 1 || d.mid > FP_MAXMID || d.G < 1 || d.type < 0 || d.type > 2 ||
-      B >= ((int64_t)1 << 31))
+      d.O > FP_MAXO || d.mid < 1 || d.mid > FP_MAXMID || d.G < 1 || d.type < FP_ALL ||
+      d.type > FP_INTERACTION || B >= ((int64_t)1 << 31))
     return REC_E_UNSUPPORTED;
   if (d.E % d.G) return REC_E_ARG;
   return REC_OK;
 }
-static int fp_num_weights(const FpDims& d) { return d.type == 0 ? 1 : (d.type == 1 ? d.F - 1 : fp_pairs(d.F)); }
+static int fp_num_weights(const FpDims& d) {
+  return d.type == FP_ALL ? 1 : (d.type == FP_EACH ? d.F - 1 : fp_pairs(d.F));
+}
 
 struct FpWs {
   size_t dz1, dz0, dzq, dp, slot_a, slot_b, part, gemm, total;   // offsets in floats

@@ -64,7 +64,7 @@ __host__ __device__ inline size_t mm_lds_floats(const MmDims& d, int bwd) {
                        : N1e + mm_max(mb_even(d.D), d.nO() + 2 * d.Tn() + d.H2 + d.O2 + d.T);
   return (size_t)rows * MB_LD;
 }
-constexpr size_t MM_LDS_CAP = 156 * 1024;
+constexpr size_t MM_LDS_CAP = REC_POSO_LDS_CAP;
 // n O, T n, H2, O2 <= MM_MAXO
 static_assert(sizeof(float) * (MM_MAXN1 + 5 * MM_MAXO + MM_MAXT) * MB_LD <= MM_LDS_CAP &&
                   sizeof(float) * (2 * MM_MAXO + 6 * MM_MAXO + 2 * MM_MAXT) * MB_LD <= MM_LDS_CAP &&

@@ -50,7 +50,7 @@ constexpr int PL_MAXD = REC_MASKNET_MAX_D, PL_MAXO = REC_MASKNET_MAX_O, PL_MAXT 
 constexpr int PL_MAXCH = 128 * MB_NJ;            // columns of an h chunk at most: the accumulator columns of mb_mma
 constexpr int PL_NTHR = 256;
 constexpr int PL_G = PL_NTHR / MB_T;             // column groups of the VALU stages
-constexpr size_t PL_LDS_CAP = 156 * 1024;
+constexpr size_t PL_LDS_CAP = REC_POSO_LDS_CAP;
 constexpr int PL_LDS_ROWS = (int)(PL_LDS_CAP / (sizeof(float) * MB_LD));
 
 static_assert(PL_MAXD <= 128 * MB_NJ, "accumulator blocks per wave of dxin");

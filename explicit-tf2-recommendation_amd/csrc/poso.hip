@@ -34,7 +34,7 @@ constexpr int PO_MAXT = REC_MASKNET_MAX_R, PO_MAXL = REC_MASKNET_MAX_R, PO_MAXU 
 constexpr int PO_MAXH = REC_MASKNET_MAX_P, PO_MAXD = REC_MASKNET_MAX_D;
 constexpr int PO_NTHR = 256;
 constexpr int PO_MB = 128;                       // rows of a block of a small weight gradient
-constexpr size_t PO_LDS_CAP = 156 * 1024;
+constexpr size_t PO_LDS_CAP = REC_POSO_LDS_CAP;
 
 static_assert(PO_MAXH <= 128 * MB_NJ && PO_MAXD <= 128 * MB_NJ && PO_MAXU <= 128, "accumulator blocks per wave");
 static_assert(PO_LDS_CAP <= REC_LDS_CU_BYTES, "LDS of a CU");

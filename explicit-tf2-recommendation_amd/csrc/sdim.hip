@@ -10,9 +10,9 @@
 //              product rounded before the sum, dependent on the values of the row and of Hm only, so equal ids give
 //              equal codes bit for bit.  Group g's code is bits [g m, (g+1) m).
 //   match      match[s,l,g] = code_g(k_l) == code_g(q[b,s,:])
-//   flags      mode 0 ('reference', the text as written: its mask is ids == padding_index, so it KEEPS the padded rows
-//              and counts every step): w_l = pad[b,l], n_l = 1.  mode 1 ('valid', the paper's intent): w_l = n_l =
-//              !pad[b,l].
+//   flags      mode REC_SDIM_MODE_REFERENCE (0; the text as written: its mask is ids == padding_index, so it KEEPS the
+//              padded rows and counts every step): w_l = pad[b,l], n_l = 1.  mode REC_SDIM_MODE_VALID (1; the paper's
+//              intent): w_l = n_l = !pad[b,l].
 //   sum        Sum[s,g,d] = sum_{l: match} float(w_l) k_l[d], added in INCREASING l from 0.f, each product and each sum
 //              rounded to fp32; cnt[s,g] = sum_{l: match} n_l, an integer
 //   mean       mean[s,g,d] = Sum / float(cnt), replaced by 0 where that is not finite (the empty bucket's 0 / 0 and a
@@ -39,18 +39,25 @@
 // gout / G, float(cnt) and codes are staged in LDS; a thread owns a step and four (or one) of its columns, walks s,
 // then g, and stores 16 bytes.  No float atomics, no scratch: bit-identical from run to run.
 //
-// Limits: G m <= 32, S <= 16, D <= 256, V and B < 2^31, and 4 (D MC + T + 2 ceil(T / 64) + 16 + 2 (T + T mod 2)) <= 65536
-// bytes of LDS (T = 2048 at C = 3, E = 16, G = 4, m = 3 takes 27 KB; T = 5000 fits at D = 48).  T < 65536 is checked too
-// (the lists' 16-bit entries); the LDS rule is the stricter one.
+// Limits, the header's: G m <= REC_SDIM_MAX_BITS, S <= REC_SDIM_MAX_S, D <= REC_SEARCH_MAX_D, V and B < 2^31, and
+// 4 (D MC + T + 2 ceil(T / 64) + REC_SDIM_MAX_S + 2 (T + T mod 2)) <= REC_SEARCH_LDS_CAP bytes of LDS (T = 2048 at
+// C = 3, E = 16, G = 4, m = 3 takes 27 KB; T = 5000 fits at D = 48).  T < 65536 is checked too (the lists' 16-bit
+// entries); the LDS rule is the stricter one, as the static_assert below holds it to be.
 #include "simhash.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int SD_MAX_BITS = 32, SD_MAX_S = 16, SD_MAX_D = 256, SD_THREADS = 256, SD_WAVES = SD_THREADS / 64;
+constexpr int SD_MAX_BITS = REC_SDIM_MAX_BITS, SD_MAX_S = REC_SDIM_MAX_S, SD_MAX_D = REC_SEARCH_MAX_D;
+constexpr int SD_THREADS = 256, SD_WAVES = SD_THREADS / 64;
 constexpr int SD_FLIGHT = 8;                               // steps whose rows a lane has in flight during the walk
-constexpr size_t SD_LDS_CAP = 64 * 1024;
+constexpr size_t SD_LDS_CAP = REC_SEARCH_LDS_CAP;
+static_assert(SD_MAX_BITS <= 32, "the codes of all groups are packed into one 32-bit word");
+static_assert(SD_LDS_CAP / sizeof(float) < (1 << 16),
+              "a series whose codes [T] fit the launch cap has T < 65536: a step fits a 16-bit list entry");
+static_assert(sizeof(float) * (SD_MAX_D * 32 + SD_MAX_S) < SD_LDS_CAP,
+              "the widest key's projection in 32 columns and the SD_MAX_S candidates' codes leave LDS for the steps");
 
 __host__ __device__ inline size_t sd_lds_bytes(int T, int D, int G, int m) {
   const size_t Tp = ((size_t)T + 1) & ~(size_t)1;          // a wave's list: Tp 16-bit entries
@@ -142,7 +149,7 @@ __global__ __launch_bounds__(SD_THREADS) void sdim_interest_fwd_kernel(
           const bool hit = l < T && (((code[l] ^ qx) >> sh) & gmask) == 0u;
           const uint64_t hits = __ballot(hit);
           if (hit) list[n + __popcll(hits & ((1ull << lane) - 1ull))] = (uint16_t)l;
-          counted += __popcll(__ballot(hit && (mode == 0 || !sd_pad(padw, l))));
+          counted += __popcll(__ballot(hit && (mode == REC_SDIM_MODE_REFERENCE || !sd_pad(padw, l))));
           n += __popcll(hits);
         }
         if (lane == 0) cnt[(b * S + s) * G + g] = counted;
@@ -160,7 +167,7 @@ __global__ __launch_bounds__(SD_THREADS) void sdim_interest_fwd_kernel(
             for (int u = 0; u < SD_FLIGHT; ++u) {
               const int l = list[min(i0 + u, n - 1)];               // past the end: the last step again, not added
               id[u] = ser[(int64_t)l * C + c];
-              w[u] = sd_pad(padw, l) == (mode == 0) ? 1.f : 0.f;
+              w[u] = sd_pad(padw, l) == (mode == REC_SDIM_MODE_REFERENCE) ? 1.f : 0.f;
             }
 #pragma unroll
             for (int u = 0; u < SD_FLIGHT; ++u) x[u] = (uint64_t)id[u] < (uint64_t)V ? embed[id[u] * ld + e] : 0.f;
@@ -212,7 +219,7 @@ __global__ __launch_bounds__(SD_THREADS) void sdim_interest_bwd_kernel(
     float acc[VW];
 #pragma unroll
     for (int v = 0; v < VW; ++v) acc[v] = 0.f;
-    if (pad == (mode == 0)) {
+    if (pad == (mode == REC_SDIM_MODE_REFERENCE)) {
       const uint32_t kc = (uint32_t)codes[b * T + l];
       for (int s = 0; s < S; ++s) {
         const uint32_t x = kc ^ qc[s];
@@ -239,7 +246,8 @@ int sd_check(int64_t ld, int64_t V, int E, int C, int64_t B, int T, int64_t ld_q
   if (V > INT32_MAX || B > INT32_MAX || (int64_t)C * E > SD_MAX_D || (int64_t)G * m > SD_MAX_BITS || S > SD_MAX_S ||
       T >= (1 << 16) || sd_lds_bytes(T, C * E, G, m) > SD_LDS_CAP)
     return REC_E_UNSUPPORTED;
-  if (ld < E || ld_q < (int64_t)C * E || (mode != 0 && mode != 1)) return REC_E_ARG;
+  if (ld < E || ld_q < (int64_t)C * E || (mode != REC_SDIM_MODE_REFERENCE && mode != REC_SDIM_MODE_VALID))
+    return REC_E_ARG;
   return REC_OK;
 }
 

@@ -36,9 +36,11 @@ namespace {
 // ------------------------------------------------------------------------------------------------------------------
 // search
 // ------------------------------------------------------------------------------------------------------------------
-constexpr int SS_MAX_K = 16;
-constexpr int SS_MAX_D = 256;
-constexpr size_t SS_LDS_CAP = 64 * 1024;
+constexpr int SS_MAX_K = REC_SEARCH_MAX_K;
+constexpr int SS_MAX_D = REC_SEARCH_MAX_D;
+constexpr size_t SS_LDS_CAP = REC_SEARCH_LDS_CAP;
+static_assert(sizeof(float) * (4 * SS_MAX_D + SS_MAX_K) < SS_LDS_CAP,
+              "four waves' partial rows of the widest key and the SS_MAX_K chosen positions leave LDS for the steps");
 
 __host__ __device__ inline size_t ss_lds_bytes(int T, int C, int D) {
   return (size_t)T * C * 4 + (size_t)4 * D * 4 + (size_t)T * 4 + SS_MAX_K * 4;
@@ -211,9 +213,10 @@ int ss_check(int64_t ld, int64_t V, int E, int C, int64_t B, int T, int64_t ld_q
 // ------------------------------------------------------------------------------------------------------------------
 // ESU attention
 // ------------------------------------------------------------------------------------------------------------------
-constexpr int ES_MAX_D = 64, ES_MAX_DK = 64, ES_MAX_H = 8, ES_MAX_K = 16;
+constexpr int ES_MAX_D = REC_ESU_MAX_D, ES_MAX_DK = REC_ESU_MAX_D, ES_MAX_H = REC_ESU_MAX_H;
+constexpr int ES_MAX_K = REC_SEARCH_MAX_K;               // the keys are the positions a search selected
 constexpr int ES_NTHR = 256;
-constexpr size_t ES_LDS_CAP = 150 * 1024;
+constexpr size_t ES_LDS_CAP = REC_TILE_LDS_CAP;
 using EsOps = TileOps<MB_T, MB_LD, ES_NTHR>;
 
 struct EsDims {

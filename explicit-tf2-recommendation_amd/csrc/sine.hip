@@ -27,8 +27,10 @@
 
 namespace {
 
-constexpr int SN_MAX_L = 1024;                  // concepts of the pool, at the most (the header names it)
-constexpr int SN_AUX_MAX_D = 256;               // width of a pool row of the aux kernels
+constexpr int SN_MAX_L = REC_SINE_MAX_L;        // concepts of the pool, at the most
+constexpr int SN_AUX_MAX_D = REC_SINE_AUX_MAX_D;  // width of a pool row of the aux kernels
+static_assert(sizeof(float) * (2 * SN_AUX_MAX_D + SN_MAX_L) <= 64 * 1024,
+              "mean, ci and M of the aux backward are static LDS: 64 KiB at the most");
 constexpr int SN_GRID = 1024;                   // workgroups (= slots) of the example-major backward, at the most
 constexpr int SN_SLAB_MAX = 2048;               // examples of a slab, at the most: the concept-major list holds as many
 constexpr int64_t SN_SLAB_BYTES = 64 << 20;     // and bytes of its pair-major scratch (never fewer than one example)

@@ -719,7 +719,7 @@ def cin_bwd(x0, states, g, Ws):
 
 # ---- FiBiNet SENet + bilinear interaction (csrc/fibinet.hip)
 FIBINET_MAX_F, FIBINET_MAX_E, FIBINET_MAX_C = (LIMITS["REC_FIBINET_MAX_" + d] for d in "FEC")
-FIBINET_TYPES = {"all": 0, "each": 1, "interaction": 2}
+FIBINET_TYPES = {k: ENUMS["REC_FIBINET_TYPE_" + k.upper()] for k in ("all", "each", "interaction")}
 
 
 def fibinet_num_weights(F, bilinear_type):
@@ -768,7 +768,8 @@ def fibinet_bwd(x_emb, g, A, H1, S0, S1, W, type_code):
 
 # ---- AutoInt multi-head field attention (csrc/autoint.hip)
 AUTOINT_MAX_F, AUTOINT_MAX_E = (LIMITS["REC_AUTOINT_MAX_" + d] for d in "FE")
-AUTOINT_RES = {(False, False): 0, (False, True): 0, (True, False): 1, (True, True): 2}   # (use_res, res_learnable)
+AUTOINT_RES = {key: ENUMS["REC_AUTOINT_RES_" + k] for key, k in (                       # (use_res, res_learnable)
+    ((False, False), "NONE"), ((False, True), "NONE"), ((True, False), "ADD"), ((True, True), "LEARNED"))}
 
 
 def autoint_check_shape(F, E, H, C=0):
@@ -1612,9 +1613,9 @@ def ple_cgc_bwd(xin, weights, saved, y, out, dy, dout, T, S, Sh, last=False):
 
 
 # ---- MIND: capsule routing and label-aware attention + sampled-softmax loss, one launch each way (csrc/mind.hip).  The
-# limits are DIN's key width and AFM's attention size, the rounds and the LDS fit are the header's formulas.
-MIND_MAX_ROUNDS = 8
-_MIND_LDS_CAP = 150 * 1024
+# limits are DIN's key width and AFM's attention size, the rounds and the LDS fit are the header's.
+MIND_MAX_ROUNDS = LIMITS["REC_CAPSULE_MAX_R"]
+_TILE_LDS_CAP = LIMITS["REC_TILE_LDS_CAP"]    # the launch cap of every one-example / one-tile kernel _lds_fit guards
 
 
 def _odd(n):
@@ -1633,9 +1634,9 @@ def _caps_limits(family, D, Dc, K, R, rounds):
 
 def _lds_fit(nbytes, holds, formula, at):
     """NotImplementedError where what a kernel holds in LDS (``nbytes`` = 4 (``formula``)) passes the launch cap"""
-    if nbytes > _MIND_LDS_CAP:
+    if nbytes > _TILE_LDS_CAP:
         raise NotImplementedError("%s in LDS: 4 (%s) <= %d bytes; got %d at %s"
-                                  % (holds, formula, _MIND_LDS_CAP, nbytes, at))
+                                  % (holds, formula, _TILE_LDS_CAP, nbytes, at))
 
 
 def _items_fit(family, Ns, Dc, K):
@@ -1909,7 +1910,7 @@ def comirec_select_bwd(embed, items, m, chosen, ginner=None, gloss=None, gsel=No
 
 # ---- SINE: the sparse-interest extractor with its per-example top-K of L concepts, and the auxiliary loss of the concept
 # pool (csrc/sine.hip).  Key width and K are MIND's limits, L and the LDS fit are the header's.
-SINE_MAX_L = 1024
+SINE_MAX_L = LIMITS["REC_SINE_MAX_L"]
 SINE_LN_EPS = 1e-3
 
 
@@ -2012,7 +2013,7 @@ def sine_aux_bwd(pool, gloss):
 # ---- CAN co-action: both lookups and the per-example micro-MLP in one launch each way (csrc/can.hip).  The widest layer
 # is AFM's embedding limit; layers, orders and the LDS fit are the header's.
 CAN_MAX_W = AFM_MAX_E
-CAN_MAX_LAYERS = CAN_MAX_ORDER = 4
+CAN_MAX_LAYERS = CAN_MAX_ORDER = LIMITS["REC_CAN_MAX_L"]
 
 
 def can_widths(E, coefs):
@@ -2288,7 +2289,7 @@ def dmr_bwd(embed, series, negatives, xi, q, P, We, z, g_i2i=None, g_u2i=None, g
 # way (csrc/poso.hip).  The limits are MaskNet's: a gate's hidden width is held to MAX_E, tasks and chained layers to
 # MAX_R.
 EPNET_MAX_HG, POSO_MAX_T, POSO_MAX_L = MASKNET_MAX_E, MASKNET_MAX_R, MASKNET_MAX_R
-_POSO_LDS_CAP = 156 * 1024
+_POSO_LDS_CAP = LIMITS["REC_POSO_LDS_CAP"]
 _POSO_ACTS = (ACT_NONE, ACT_RELU, ACT_SIGMOID)
 
 
@@ -2468,7 +2469,7 @@ def poso_mlp_bwd(x, g, weights, saved, dout, units, acts, m=2):
 # ---- DIEN: the masked Keras GRU of the interest extractor fused with the series / negative lookups and the auxiliary
 # loss, and the attention scores fused with the AGRU / AUGRU of the interest evolution (csrc/dien.hip).  Every width is
 # H = E C, held to DIN's wide key width; the LDS fit is the header's formula.
-DIEN_AUGRU, DIEN_AGRU = 1, 2
+DIEN_GRU, DIEN_AUGRU, DIEN_AGRU = (ENUMS["REC_DIEN_" + k] for k in ("GRU", "AUGRU", "AGRU"))
 DIEN_MODE = {"AUGRU": DIEN_AUGRU, "AGRU": DIEN_AGRU}
 
 
@@ -2618,10 +2619,12 @@ def dien_augru_bwd(gru_output, q, mask_ids, mode, Wx, Uh, bx, scores, states, dh
 
 # ---------------------------------------------------------------------------------------------------
 # SIM (7.SIM/CustomLayers.py:130-282; csrc/sim.hip): the soft search fused with the GSU pooling, and the one-query
-# multi-head attention of the exact search unit.  The limits are the .hip file's and show through its size queries.
+# multi-head attention of the exact search unit.  The limits are the header's and show through the size queries.
 # ---------------------------------------------------------------------------------------------------
-SIM_MAX_D, SIM_MAX_K, SIM_MAX_H = 64, 16, 8         # the attention's; the search alone covers a key width of 256
-_SIM_SEARCH_LDS_CAP = 64 * 1024
+# the attention's widths and heads; K is the searches' as well, and a search alone covers a key width of _SEARCH_MAX_D
+SIM_MAX_D, SIM_MAX_K, SIM_MAX_H = LIMITS["REC_ESU_MAX_D"], LIMITS["REC_SEARCH_MAX_K"], LIMITS["REC_ESU_MAX_H"]
+_SEARCH_MAX_D = LIMITS["REC_SEARCH_MAX_D"]          # SIM, ETA and SDIM alike, and so is the launch cap of their kernels
+_SEARCH_LDS_CAP = LIMITS["REC_SEARCH_LDS_CAP"]
 
 
 def sim_search_lds_bytes(T, C, D, K=1):
@@ -2642,15 +2645,15 @@ def sim_check_shape(D, T=None, K=None, H=None, dk=None, C=1):
     if min(given) < 1:
         raise ValueError("every size of a SIM body must be positive, got D=%r, T=%r, K=%r, H=%r, dk=%r"
                          % (D, T, K, H, dk))
-    if D > DIN_WIDE_D * 2:
+    if D > _SEARCH_MAX_D:
         raise NotImplementedError("the SIM search covers a key width embedding_dims * series features <= %d; got %d"
-                                  % (DIN_WIDE_D * 2, D))
+                                  % (_SEARCH_MAX_D, D))
     if K is not None and K > SIM_MAX_K:
         raise NotImplementedError("SIM kernels cover k <= %d selected positions; got %d" % (SIM_MAX_K, K))
-    if T is not None and sim_search_lds_bytes(T, C, D) > _SIM_SEARCH_LDS_CAP:
+    if T is not None and sim_search_lds_bytes(T, C, D) > _SEARCH_LDS_CAP:
         raise NotImplementedError("the SIM search holds one example's ids and scores in LDS: 4 (T C + 4 D + T + 16) <= "
                                   "%d bytes; got %d at T=%d, C=%d, D=%d"
-                                  % (_SIM_SEARCH_LDS_CAP, sim_search_lds_bytes(T, C, D), T, C, D))
+                                  % (_SEARCH_LDS_CAP, sim_search_lds_bytes(T, C, D), T, C, D))
     if H is not None:
         dk = D if dk is None else dk
         if D > SIM_MAX_D or dk > SIM_MAX_D or H > SIM_MAX_H or D % 2 or dk % 2:
@@ -2783,10 +2786,10 @@ def esu_attn_bwd(q, x, mask, weights, gout):
 
 
 # ---------------------------------------------------------------------------------------------------
-# ETA (7.SIM/CustomLayers.py:518-626; csrc/eta.hip): the SimHash search of the long series.  The limits are the .hip
-# file's and show through its size query.
+# ETA (7.SIM/CustomLayers.py:518-626; csrc/eta.hip): the SimHash search of the long series.  The limits are the
+# header's and show through its size query.
 # ---------------------------------------------------------------------------------------------------
-ETA_MAX_M = 32
+ETA_MAX_M = LIMITS["REC_ETA_MAX_M"]
 
 
 def eta_search_lds_bytes(T, D, m):
@@ -2804,18 +2807,18 @@ def eta_check_shape(D, T=None, K=None, m=None, C=None):
                          % (D, T, K, m, C))
     if C is not None and D % C:
         raise ValueError("the key width D = embedding_dims * series features; got D=%d with C=%d" % (D, C))
-    if D > DIN_WIDE_D * 2:
+    if D > _SEARCH_MAX_D:
         raise NotImplementedError("the ETA search covers a key width embedding_dims * series features <= %d; got %d"
-                                  % (DIN_WIDE_D * 2, D))
+                                  % (_SEARCH_MAX_D, D))
     if K is not None and K > SIM_MAX_K:
         raise NotImplementedError("the ETA search covers lsh_topk <= %d selected positions; got %d" % (SIM_MAX_K, K))
     if m is not None and m > ETA_MAX_M:
         raise NotImplementedError("the ETA search covers lsh_dim <= %d hash bits; got %d" % (ETA_MAX_M, m))
-    if T is not None and eta_search_lds_bytes(T, D, 1 if m is None else m) > _SIM_SEARCH_LDS_CAP:
+    if T is not None and eta_search_lds_bytes(T, D, 1 if m is None else m) > _SEARCH_LDS_CAP:
         m = 1 if m is None else m
         raise NotImplementedError("the ETA search holds the projection and one example's ranks in LDS: 4 (D MC + T + 16) "
                                   "<= %d bytes with MC = 16 or 32 columns; got %d at T=%d, D=%d, lsh_dim=%d"
-                                  % (_SIM_SEARCH_LDS_CAP, eta_search_lds_bytes(T, D, m), T, D, m))
+                                  % (_SEARCH_LDS_CAP, eta_search_lds_bytes(T, D, m), T, D, m))
 
 
 def eta_search_fwd(embed, series, q, Hm, padding_index, K, oob=None, want_scores=True):
@@ -2840,11 +2843,10 @@ def eta_search_fwd(embed, series, q, Hm, padding_index, K, oob=None, want_scores
 
 # ---------------------------------------------------------------------------------------------------
 # SDIM (8.DMR/CustomLayers.py:816-841; csrc/sdim.hip): the hash-bucket interest of the long series.  The limits are the
-# .hip file's and show through its size query.
+# header's and show through its size query.
 # ---------------------------------------------------------------------------------------------------
-SDIM_MAX_BITS, SDIM_MAX_S, SDIM_MAX_D, SDIM_MAX_T = 32, 16, 256, 65535        # csrc/sdim.hip's SD_MAX_*; 16-bit list entries
-_SDIM_LDS_CAP = 64 * 1024
-SDIM_MODES = {"reference": 0, "valid": 1}
+SDIM_MAX_BITS, SDIM_MAX_S, SDIM_MAX_D = LIMITS["REC_SDIM_MAX_BITS"], LIMITS["REC_SDIM_MAX_S"], _SEARCH_MAX_D
+SDIM_MODES = {k: ENUMS["REC_SDIM_MODE_" + k.upper()] for k in ("reference", "valid")}
 
 
 def sdim_lds_bytes(T, D, G, m):
@@ -2875,10 +2877,10 @@ def sdim_check_shape(D, T=None, S=None, G=None, m=None, C=None):
     if T is not None:
         G1 = 1 if G is None else G
         need = sdim_lds_bytes(T, D, G1, bits // G1)
-        if need > _SDIM_LDS_CAP or T > SDIM_MAX_T:
+        if need > _SEARCH_LDS_CAP:      # need > 4 T: this also keeps T inside the kernel's 16-bit list entries
             raise NotImplementedError("the SDIM interest holds the projection and one example's codes in LDS: 4 (D MC + T "
                                       "+ 2 ceil(T / 64) + 16 + 2 (T + T mod 2)) <= %d bytes with MC = 16 or 32 columns; got %d at "
-                                      "T=%d, D=%d, hash bits=%d" % (_SDIM_LDS_CAP, need, T, D, bits))
+                                      "T=%d, D=%d, hash bits=%d" % (_SEARCH_LDS_CAP, need, T, D, bits))
 
 
 def _sdim_mode(mask_mode):

@@ -10,9 +10,10 @@
  * This file is also what the Python side is generated from: explicit-tf2-recommendation_amd/_lib.py reads it at import
  * and derives the ctypes signature of every prototype `ret rec_name(args);`, the fields of struct rec_deepfm_lazy_adam
  * and the two tables of constants.  Every `#define REC_<NAME> <integer>` goes to LIMITS: the status codes and the shape
- * limits of the kernel families, which the kernel files and the guards of ops.py both take from here.  The enumerators
- * of every `enum { ... }` go to ENUMS: the operation codes (REC_ACT_*, REC_EPI_*, REC_DACT_*), which the kernels switch
- * on and ops.py binds its names to.  There is no second table to keep in step; the price is a
+ * limits and launch caps of every kernel family, which the kernel files and the guards of ops.py both take from here.
+ * The enumerators of every `enum { ... }` go to ENUMS: the operation codes (REC_ACT_*, REC_EPI_*, REC_DACT_*) and the
+ * mode codes (REC_FIBINET_TYPE_*, REC_AUTOINT_RES_*, REC_DIEN_*, REC_SDIM_MODE_*), which the kernels switch on and
+ * ops.py binds its names to.  There is no second table to keep in step; the price is a
  * closed set of type spellings, and anything else fails the import and names the declaration:
  *   int, int32_t, int64_t, float, double, size_t by value (with or without a leading const);
  *   a pointer, at any depth and constness, to one of those or to void;  const rec_deepfm_lazy_adam*.
@@ -89,9 +90,44 @@ extern "C" {
 #define REC_DIN_MAX_H 64
 #define REC_DIN_WIDE_D 128
 #define REC_DIN_WIDE_MAX_H 48
+/* capsule routing, MIND and ComiRec alike (csrc/capsule.h): routing rounds.  Their key and capsule widths are
+ * REC_DIN_MAX_D and their capsules REC_AFM_MAX_A, as SINE's and DMR's widths are */
+#define REC_CAPSULE_MAX_R 8
+/* SINE (csrc/sine.hip): concepts of the pool; width of a pool row of the aux kernels */
+#define REC_SINE_MAX_L 1024
+#define REC_SINE_AUX_MAX_D 256
+/* CAN (csrc/can.hip): layers of the micro-MLP, and orders alike (its widest layer is REC_AFM_MAX_E) */
+#define REC_CAN_MAX_L 4
+/* series search, SIM, ETA and SDIM alike (csrc/sim.hip, csrc/eta.hip, csrc/sdim.hip): key width D = E C; selected
+ * positions K, which are also the keys of the ESU attention */
+#define REC_SEARCH_MAX_D 256
+#define REC_SEARCH_MAX_K 16
+/* ESU attention (csrc/sim.hip): width of the query and key rows D and of a head dk alike, heads */
+#define REC_ESU_MAX_D 64
+#define REC_ESU_MAX_H 8
+/* ETA (csrc/eta.hip): hash bits */
+#define REC_ETA_MAX_M 32
+/* SDIM (csrc/sdim.hip): hash bits of all groups together G m, candidates of an example */
+#define REC_SDIM_MAX_BITS 32
+#define REC_SDIM_MAX_S 16
+/* Launch caps: the most dynamic LDS, in bytes, a launch of these kernels asks for; a shape whose LDS formula (given
+ * with each family below) passes it is REC_E_UNSUPPORTED.
+ * 150 KiB: the one-example and one-tile kernels of MIND, ComiRec, SINE, CAN, DMR, DIEN, the ESU and DIN attentions */
+#define REC_TILE_LDS_CAP 153600
+/* 156 KiB: the 32-example tiles of POSO-MLP, PLE, MMOE and ContextNet */
+#define REC_POSO_LDS_CAP 159744
+/* 64 KiB: the series searches of SIM, ETA and SDIM */
+#define REC_SEARCH_LDS_CAP 65536
 
 /* activation kinds shared by the dense entry points */
 enum { REC_ACT_NONE = 0, REC_ACT_RELU = 1, REC_ACT_SIGMOID = 2, REC_ACT_TANH = 3 };
+
+/* mode codes of the families that take one: `type` of rec_fibinet_* and rec_fibinetplus_*, `res` of rec_autoint_*,
+ * `mode` of rec_dien_augru_* (the GRU of rec_dien_gru_* is the same cell's mode 0) and `mode` of rec_sdim_interest_* */
+enum { REC_FIBINET_TYPE_ALL = 0, REC_FIBINET_TYPE_EACH = 1, REC_FIBINET_TYPE_INTERACTION = 2 };
+enum { REC_AUTOINT_RES_NONE = 0, REC_AUTOINT_RES_ADD = 1, REC_AUTOINT_RES_LEARNED = 2 };
+enum { REC_DIEN_GRU = 0, REC_DIEN_AUGRU = 1, REC_DIEN_AGRU = 2 };
+enum { REC_SDIM_MODE_REFERENCE = 0, REC_SDIM_MODE_VALID = 1 };
 
 /* epilogues of rec_gemm_f32 */
 enum {
@@ -489,9 +525,9 @@ int rec_din_prepare_bwd_f32(const float* gWcat, const float* gWkd, int D, int H,
  * mask_valid = 1 is the intended form.  scores [B,T] are the raw (unmasked) scores; pooled [B,D].
  * Supported, the same for the forward and the backward: 1 <= D = E C <= REC_DIN_MAX_D (256), 1 <= H <= REC_DIN_MAX_H
  * (64), and D > REC_DIN_WIDE_D (128) only with H <= REC_DIN_WIDE_MAX_H (48): at 129 <= D <= 256 with 49 <= H <= 64 the
- * backward's LDS (156 KiB) is above its 150 KiB launch cap, so both directions refuse that corner.  Outside: -2
- * (REC_E_UNSUPPORTED), answered from the sizes alone before a pointer is looked at, also with B == 0.  A size <= 0,
- * ld < E, V <= 0, an unknown act or a NULL pointer: -1. */
+ * backward's LDS (156 KiB) is above its launch cap REC_TILE_LDS_CAP (150 KiB), so both directions refuse that corner.
+ * Outside: -2 (REC_E_UNSUPPORTED), answered from the sizes alone before a pointer is looked at, also with B == 0.  A
+ * size <= 0, ld < E, V <= 0, an unknown act or a NULL pointer: -1. */
 int rec_din_attn_fwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* series, int64_t B,
                          int T, const float* Mext, const float* Wkd, int H, int act, const float* alpha,
                          const float* mean, const float* var, const float* w2, const float* b2,
@@ -597,7 +633,7 @@ int rec_cin_bwd_f32(const float* x0, const float* states, const float* g, int64_
 
 /* ---- FiBiNet SENet + bilinear interaction (FiBiNetLayer / SENetLayer / BilinearInteractionLayer,
  * 3.DCN/CustomLayers.py:888-1011; csrc/fibinet.hip).  x_emb [B, F, E], x_cont [B, C] (may be NULL when C == 0),
- * S0 [F, mid], S1 [mid, F], W [nW, E, E] packed (nW = 1 / F-1 / P for type 0 'all' / 1 'each' / 2 'interaction',
+ * S0 [F, mid], S1 [mid, F], W [nW, E, E] packed (nW = 1 / F-1 / P for type REC_FIBINET_TYPE_ALL / _EACH / _INTERACTION,
  * P = F(F-1)/2 pairs i<j in itertools.combinations order; 'each' uses W[i], 'interaction' W[pair]):
  *   Z = mean_e x_emb      H1 = relu(Z S0) [B, mid]      A = relu(H1 S1) [B, F]
  *   p_ij = (v_i W_ij) * v_j      dnn_in [B, 2PE + C] = [p (raw pairs) | A_i A_j p_ij (SENet pairs) | x_cont],
@@ -605,7 +641,7 @@ int rec_cin_bwd_f32(const float* x0, const float* states, const float* g, int64_
  * The backward reads the 2PE interaction columns of g = dLoss/d dnn_in [B, 2PE + C] and writes dx_emb [B, F, E],
  * dW [nW, E, E] (summed over the pairs sharing a W), dS0 and dS1.  No float atomics: bit-identical results run to run.
  * Supported: 2 <= F <= 32, 1 <= E <= 64, 0 <= C <= 64, 1 <= mid <= F, B >= 0 (B == 0: nothing is launched);
- * otherwise -2.  A negative size, a type outside 0..2 or a NULL pointer: -1.
+ * otherwise -2.  A negative size, a type that is none of the three or a NULL pointer: -1.
  * workspace: rec_fibinet_workspace_bytes (0: invalid or unsupported shape). */
 size_t rec_fibinet_workspace_bytes(int64_t B, int F, int E, int mid, int type);
 int rec_fibinet_fwd_f32(const float* x_emb, const float* x_cont, const float* S0, const float* S1, const float* W,
@@ -622,14 +658,15 @@ int rec_fibinet_bwd_f32(const float* x_emb, const float* g, const float* A, cons
  * H heads of width d = E / H, head h owns the columns [h d, (h+1) d):
  *   Q = X Wq, K = X Wk, V = X Wv (each [E, E])      S[h,b,i,j] = scale Q_h[b,i,:] . K_h[b,j,:], scale = 1/sqrt(d) or 1
  *   P = softmax of S over the BATCH axis b (the reference's tf.nn.softmax(axis=1) on (H, B, F, F))
- *   O[b,i,h d + c] = sum_j P[h,b,i,j] V[b,j,h d + c]      Z = O (res 0) | O + X (res 1) | O + X Wres (res 2)
+ *   O[b,i,h d + c] = sum_j P[h,b,i,j] V[b,j,h d + c]      Z = O | O + X | O + X Wres  (res REC_AUTOINT_RES_NONE | _ADD | _LEARNED)
  *   y = relu(Z) [B, F, E];  o [B, F, E] = O before the residual (may be NULL);  stats [2, H, F, F] = (max_b S, 1/sum_b
  *   exp(S - max)) for the backward.
  * The backward takes dy = dLoss/dy and writes dx [B, Fc, E] (categorical rows), dWq, dWk, dWv, dWres (res 2), dcemb
  * [C, E] (C > 0).  Every output of one call depends on the whole batch.  No float atomics: bit-identical results run
  * to run; no host synchronisation (graph-capturable).
  * Supported: 1 <= F <= 64, 1 <= E <= 64, 1 <= H <= E with E % H == 0, 0 <= C < F, 0 <= B < 2^31 (B == 0: nothing is
- * launched); otherwise -2.  A negative size, res outside 0..2, scaling outside 0..1 or a NULL pointer: -1.
+ * launched); otherwise -2.  A negative size, a res that is none of the three, scaling outside 0..1 or a NULL pointer:
+ * -1.
  * workspace: rec_autoint_workspace_bytes (0: invalid or unsupported shape), for either direction. */
 size_t rec_autoint_workspace_bytes(int64_t B, int F, int E, int H, int C, int res);
 int rec_autoint_fwd_f32(const float* x, const float* x_cont, const float* cemb, const float* Wq, const float* Wk,
@@ -1009,7 +1046,7 @@ int rec_ple_cgc_bwd_f32(const float* xin, const float* W1, const float* We2, con
  * IndexedSlices values of the series lookups as rec_din_attn_bwd_f32's, and dS [D, Dc], both written, never added to.
  * dS is reduced through one partial per workgroup of a capped grid and a slot sum in wave order.
  * Supported, the same both ways: D = E C <= REC_DIN_MAX_D (256), Dc <= REC_DIN_MAX_D, K <= REC_AFM_MAX_A (16),
- * 1 <= R <= 8, 0 <= B < 2^31 and the backward's LDS within the 150 KiB launch cap:
+ * 1 <= R <= REC_CAPSULE_MAX_R, 0 <= B < 2^31 and the backward's LDS within the launch cap REC_TILE_LDS_CAP (150 KiB):
  *   4 (T (D|1) + 2 T (Dc|1) + (R + 2) K T + 2 K (Dc|1) + T) <= 153600          (x|1: x made odd)
  * e.g. T <= 226 at D = Dc = 48, K = 4, R = 3 and T <= 35 at D = Dc = 256, K = 16, R = 3.
  * workspace (backward only): rec_mind_routing_workspace_bytes: min(B, 1024) partials of D Dc floats (at most 512 when dS
@@ -1073,7 +1110,7 @@ int rec_mind_laa_bwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C
  * products run on v_mfma_f32_32x32x2_f32 over 32-example tiles with W[k,t] read once per tile, and dW is reduced through
  * one partial per batch slice (at most 16) and a slot sum in serial order.  One wave owns a row (b, k) through the rounds.
  * Supported, the same both ways: D = E C <= REC_DIN_MAX_D (256), Dc <= REC_DIN_MAX_D, K <= REC_AFM_MAX_A (16),
- * 1 <= R <= 8, 0 <= B < 2^31 and one row's LDS within the 150 KiB launch cap:
+ * 1 <= R <= REC_CAPSULE_MAX_R, 0 <= B < 2^31 and one row's LDS within the launch cap REC_TILE_LDS_CAP:
  *   4 (T (Dc|1) + (2 R + 3) T + 2 R (Dc|1)) <= 153600                          (x|1: x made odd)
  * e.g. T <= 657 at Dc = 48, R = 3 and T <= 124 at Dc = 256, R = 8.
  * workspace (BOTH directions): rec_comirec_dr_workspace_bytes: u of a slab plus, for the backward, slices K T D Dc
@@ -1156,8 +1193,8 @@ int rec_comirec_select_bwd_f32(const float* embed, int64_t ld, int64_t V, int E,
  * One workgroup of 256 threads owns an example through all orders: the feed rows are read once, each induction row once
  * per (example, order), coalesced, into LDS (W_l rows padded to an odd stride); the products are f32 FMA chains out of
  * LDS, four positions per thread forward; dW is accumulated in registers over the positions and each gind row is
- * written once.  Supported, the same both ways: every widths[l] <= REC_AFM_MAX_E (64), 1 <= n_layers <= 4,
- * 1 <= order <= 4, T >= 1, 0 <= B < 2^31 and one example's working set within the 150 KiB launch cap:
+ * written once.  Supported, the same both ways: every widths[l] <= REC_AFM_MAX_E (64), 1 <= n_layers <= REC_CAN_MAX_L,
+ * 1 <= order <= REC_CAN_MAX_L, T >= 1, 0 <= B < 2^31 and one example's working set within REC_TILE_LDS_CAP:
  *   4 (2 T E + Pv + T sum_{l<=La} (widths[l]|1) + 2 T (wmax|1) + T + 256) <= 153600                (x|1: x made odd)
  *   Pv = sum_{l<La} (widths[l] (widths[l+1]|1) + widths[l+1]),  wmax = max_{l<=La} widths[l]
  * e.g. T <= 276 at E = 16, coefs (1,1,1), order 3 (Pv = 864) and T <= 65 at E = 64, coefs (1,1), order 2 (Pv = 8448).
@@ -1207,13 +1244,14 @@ int rec_can_bwd_f32(const float* feed, int64_t ld_f, int64_t Vf, int E, const fl
  * of dpool of every pair (b, k) to the scratch; a concept-major launch adds the pairs with chosen == l in ascending
  * (b, k) order, one thread per element (the first slab writes, later slabs add); a slot sum in wave order finishes
  * dW1 .. dW4.  Supported, the same both ways: D = E C <= REC_DIN_MAX_D (256), 1 <= K <= min(L, REC_AFM_MAX_A (16)),
- * L <= 1024 (SN_MAX_L of csrc/sine.hip), 0 <= B < 2^31 and one example's LDS within the 150 KiB launch cap:
+ * L <= REC_SINE_MAX_L, 0 <= B < 2^31 and one example's LDS within the launch cap REC_TILE_LDS_CAP:
  *   4 (4 T (D|1) + 4 K T + L + 5 K (D|1) + 6 T + 8 (D|1) + 128) <= 153600                     (x|1: x made odd)
  * e.g. T <= 164 at D = 48, K = 5, L = 100.  rec_sine_lds_bytes: the left-hand side, the dynamic LDS of a launch; 0:
  * invalid or unsupported.  scratch (backward only): rec_sine_scratch_bytes: the pairs of a slab plus the slots; 0 likewise.
  *
  * aux.  Cc = pool - mean_l(pool), M = Cc Cc^T [L, L]: loss[0] = 0.5 sum_{i != j} M_ij^2; the backward takes gloss [1] ON
- * THE DEVICE and writes dpool = gloss (2 offdiag(M) Cc), pushed back through the centring.  L <= 1024, D <= 256.
+ * THE DEVICE and writes dpool = gloss (2 offdiag(M) Cc), pushed back through the centring.  L <= REC_SINE_MAX_L,
+ * D <= REC_SINE_AUX_MAX_D.
  *
  * All entry points only enqueue (no allocation, no host synchronisation: graph-capturable) and use no float atomics:
  * bit-identical results run to run.  Return codes, answered in this order: a size below 1 (B below 0), tau <= 0 or
@@ -1313,7 +1351,7 @@ int rec_finalmlp_bwd_f32(const float* xs, const float* x1, const float* x2, cons
  * dh We^T and x^T dh run on v_mfma_f32_32x32x2_f32.  Both only enqueue (no allocation, no host synchronisation:
  * graph-capturable) and use no float atomics: bit-identical results run to run.
  * Supported, the same both ways: D = E C <= REC_DIN_MAX_D (256), H <= REC_DIN_MAX_D, 0 <= B < 2^31 and one example's
- * LDS within the 150 KiB launch cap (rec_dmr_lds_bytes; 0: invalid or unsupported):
+ * LDS within the launch cap REC_TILE_LDS_CAP (rec_dmr_lds_bytes; 0: invalid or unsupported):
  *   4 (T ((D|1) + (2H|1) + 7) + Nn ((D|1) + 3) + 8 (D|1) + 5 H + 16) <= 153600                (x|1: x made odd)
  * e.g. T <= 244 at D = H = 48, Nn = 6.  scratch (backward only): rec_dmr_scratch_bytes: min(B, 1024) slots of
  * (D + T + 1) 2H floats (at most 512 / 256 slots when dWe has more than eight / sixteen 32 x 32 blocks); 0: invalid or
@@ -1370,10 +1408,10 @@ int rec_dmr_bwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, con
  * float atomics: bit-identical results run to run.  B == 0: nothing is launched.
  * Supported: 1 <= T <= REC_MASKNET_MAX_R, 1 <= L <= REC_MASKNET_MAX_R, U_i <= REC_MASKNET_MAX_O, m U_i <= REC_MASKNET_MAX_P,
  * Dm, Dg <= REC_MASKNET_MAX_D, an activation of the three above, 0 <= B < 2^31, and the forward's tile within the LDS of
- * a CU: 132 (even(Dg) + max(even(m Umax), even(Dm)) + (L > 1 ? 2 : 1) even(Umax)) <= 159744 (every L = 1 shape inside
- * the limits does; L > 1 with Dg and max(Dm, m Umax) both near 512 does not); otherwise -2.  A size below 1 (B below 0),
- * ldx < Dm, ldg < Dg, a NULL pointer or save buffers given in part: -1.  A workspace that is too small: -3.  workspace
- * (backward only): rec_poso_mlp_scratch_bytes: 4 B (NG + 2 T sumU) bytes of per-example gradients, (B / 32) slots of
+ * a CU: 132 (even(Dg) + max(even(m Umax), even(Dm)) + (L > 1 ? 2 : 1) even(Umax)) <= REC_POSO_LDS_CAP (every L = 1
+ * shape inside the limits does; L > 1 with Dg and max(Dm, m Umax) both near 512 does not); otherwise -2.  A size below
+ * 1 (B below 0), ldx < Dm, ldg < Dg, a NULL pointer or save buffers given in part: -1.  A workspace that is too small:
+ * -3.  workspace (backward only): rec_poso_mlp_scratch_bytes: 4 B (NG + 2 T sumU) bytes of per-example gradients, (B / 32) slots of
  * NG + 2 T sumU + T L floats, at most 16 copies of W and Wg2 and at most 16 of Wg1 (0: invalid or unsupported shape). */
 size_t rec_epnet_lookup_scratch_bytes(int64_t B, int F, int P, int E, int Hg);
 int rec_epnet_lookup_fwd_f32(const float* table, int64_t V, int64_t ld, const int64_t* ids, const float* A,
@@ -1419,8 +1457,8 @@ int rec_poso_mlp_bwd_f32(const float* x, int64_t ldx, const float* g, int64_t ld
  * (each may be NULL: exact zeros), recomputes the gates and writes, never adds to: dx [B, T, H], the IndexedSlices
  * values of the series lookup (table mode) or the gradient of x; dneg [B, T, H] the values of the negative lookup (with
  * negatives; position 0 is zero); dkernel, drecurrent_kernel [H, 3H], dbias [2, 3H].
- * rec_dien_augru_*.  mode 1 = AUGRU, 2 = AGRU.  gru_output [B, T, H] is the input, q [B, H] = X_item W^T (made by the
- * caller, rec_gemm_f32), mask_ids[(b T + t) mask_stride] the mask ids.  product[b,t] = gru_output[b,t] . q[b],
+ * rec_dien_augru_*.  mode REC_DIEN_AUGRU or REC_DIEN_AGRU.  gru_output [B, T, H] is the input, q [B, H] = X_item W^T (made
+ * by the caller, rec_gemm_f32), mask_ids[(b T + t) mask_stride] the mask ids.  product[b,t] = gru_output[b,t] . q[b],
  * e = sel ? exp(product) : 0 with sel = !valid (mask_valid = 0, the reference: only PADDED positions score) or valid
  * (mask_valid = 1), scores = e / sum_t e with NaN -> 0 (a row with nothing selected scores zeros) [B, T], always
  * written; a = scores.  states [B, T, H] (every h_t; may be NULL in inference) and h_final [B, H].  The backward takes
@@ -1431,7 +1469,8 @@ int rec_poso_mlp_bwd_f32(const float* x, int64_t ldx, const float* g, int64_t ld
  * (split-K over B T, slices added in order) for dWx = X^T dpre and dUh = Hprev^T drec out of the scratch.  They only
  * enqueue (graph-capturable) and use no float atomics: bit-identical results run to run.
  * Supported, the same both ways: 1 <= H <= REC_DIN_WIDE_D (128), T >= 1, 0 <= B < 2^31 and the tile's LDS within the
- * 150 KiB launch cap (rec_dien_gru_lds_bytes, rec_dien_augru_lds_bytes; 0: invalid or unsupported), He = H made even:
+ * launch cap REC_TILE_LDS_CAP (rec_dien_gru_lds_bytes, rec_dien_augru_lds_bytes; 0: invalid or unsupported), He = H
+ * made even:
  *   GRU     132 * 8 He + 512 <= 153600                       (every H up to 128, any T)
  *   AUGRU   132 * (7 He + 2 T) + 512, AGRU 132 * (6 He + 2 T) + 512 <= 153600      (T <= 131 at H = 128, <= 243 at 96)
  * scratch: rec_dien_gru_scratch_bytes (backward = 0: the forward's aux slots; 1: the backward's) and
@@ -1477,7 +1516,8 @@ int rec_dien_augru_bwd_f32(const float* gru_output, const float* q, const int64_
  * NULL).  The backward writes, never adds to, gkeys [B,T,D] = scores_t gpooled + valid <gpooled, k_t> q, plus gsel[b,j,:]
  * (may be NULL: none) where chosen[b,j] == t -- the IndexedSlices values of the one series lookup -- and gq [B,D] as
  * rec_ip_attn_bwd_f32 does (the selection sends nothing to q).  One launch each way, one workgroup per example.
- * Supported: D <= 256, K <= 16, V and B < 2^31, 4 (T C + 4 D + T + 16) <= 65536 bytes of LDS (rec_sim_search_lds_bytes:
+ * Supported: D <= REC_SEARCH_MAX_D, K <= REC_SEARCH_MAX_K, V and B < 2^31, 4 (T C + 4 D + T + REC_SEARCH_MAX_K) <=
+ * REC_SEARCH_LDS_CAP bytes of LDS (rec_sim_search_lds_bytes:
  * that sum, 0: invalid or unsupported).
  * rec_esu_attn_*.  Keras 2.x MultiHeadAttention (value_dim = key_dim, no dropout) with one query q [B,D] over K dense
  * keys x [B,K,D], mask int32 [B,K] (non-zero = attend), Wq, Wk, Wv [D,H,dk], bq, bk, bv [H,dk], Wo [H,dk,D], bo [D]:
@@ -1492,8 +1532,9 @@ int rec_dien_augru_bwd_f32(const float* gru_output, const float* q, const int64_
  * weight gradients: one launch for the chain (a workgroup of 4 waves per 32 examples, products on
  * v_mfma_f32_32x32x2_f32), a slot sum for dbq, dbv, dbo and one launch plus a slot sum for the 5 H per-head matrices of
  * dWq, dWk, dWv, dWo, dbk over at most 16 batch slices added in order.  No float atomics: bit-identical run to run.
- * Supported: D, dk <= 64 and even, H <= 8, K <= 16, B < 2^31 and 132 (max(H dk, H D) + 2 + 2 H K + H) <= 153600 bytes
- * of LDS (rec_esu_attn_lds_bytes: that product, 0: invalid or unsupported).  scratch: rec_esu_attn_scratch_bytes,
+ * Supported: D, dk <= REC_ESU_MAX_D and even, H <= REC_ESU_MAX_H, K <= REC_SEARCH_MAX_K, B < 2^31 and
+ * 132 (max(H dk, H D) + 2 + 2 H K + H) <= REC_TILE_LDS_CAP bytes of LDS (rec_esu_attn_lds_bytes: that product, 0: invalid
+ * or unsupported; inside the other limits it is at most 102696).  scratch: rec_esu_attn_scratch_bytes,
  * what the backward needs (the forward needs less): 4 B (4 H dk + 4 H D + H) bytes of per-example operands, (B / 32)
  * slots and at most 16 copies of the weights; 0: invalid or unsupported.
  * Return codes, in this order: a size below 1 (B below 0): -1; a shape outside the limits: -2, from the sizes alone; a
@@ -1534,8 +1575,9 @@ int rec_esu_attn_bwd_f32(const float* q, int64_t ld_q, const float* x, const int
  * reads a zero row and sets *oob_flag (may be NULL).  One launch, one workgroup per example, a lane per step; no float
  * atomics.  There is no backward entry point: Hm is frozen and sign has no gradient, so the gradient of sel is the sparse
  * row gradient over sel_ids.
- * Supported: m <= 32, K <= 16, D <= 256, V and B < 2^31, 4 (D MC + T + 16) <= 65536 bytes of LDS with MC = 16 for
- * m <= 16 and 32 beyond (rec_eta_search_lds_bytes: that sum, 0: invalid or unsupported).
+ * Supported: m <= REC_ETA_MAX_M, K <= REC_SEARCH_MAX_K, D <= REC_SEARCH_MAX_D, V and B < 2^31,
+ * 4 (D MC + T + REC_SEARCH_MAX_K) <= REC_SEARCH_LDS_CAP bytes of LDS with MC = 16 for m <= 16 and 32 beyond
+ * (rec_eta_search_lds_bytes: that sum, 0: invalid or unsupported).
  * Return codes, in this order: a size below 1 (B below 0): -1; a shape outside the limits: -2, from the sizes alone;
  * ld < E, ld_q < D or K > T: -1; B == 0: 0, nothing is launched or written; a pointer that must not be NULL: -1. */
 size_t rec_eta_search_lds_bytes(int T, int C, int E, int m, int K);
@@ -1553,8 +1595,9 @@ int rec_eta_search_fwd_f32(const float* embed, int64_t ld, int64_t V, int E, int
  * Hm only -- so equal ids give equal codes bit for bit; group g's code is bits [g m, (g+1) m).  An id outside [0, V)
  * reads a zero row and sets *oob_flag (may be NULL).
  *   match[s,l,g] = code_g(k_l) == code_g(q[b,s,:])
- *   mode 0 ('reference', the text as written: it keeps the PADDED rows and counts every step)  w_l = pad[b,l], n_l = 1
- *   mode 1 ('valid', the paper's intent)                                                       w_l = n_l = !pad[b,l]
+ *   mode REC_SDIM_MODE_REFERENCE (the text as written: it keeps the PADDED rows and counts every step)
+ *                                                                                              w_l = pad[b,l], n_l = 1
+ *   mode REC_SDIM_MODE_VALID (the paper's intent)                                              w_l = n_l = !pad[b,l]
  *   Sum[s,g,d] = sum_{l: match} float(w_l) k_l[d], in increasing l from 0, every product and sum rounded to fp32
  *   cnt[s,g]   = sum_{l: match} n_l
  *   mean[s,g,d] = Sum / float(cnt), 0 where that is not finite (an empty bucket, a non-finite sum)
@@ -1567,12 +1610,13 @@ int rec_eta_search_fwd_f32(const float* embed, int64_t ld, int64_t V, int E, int
  * gradient (sign and one_hot carry none); the backward reads neither embed nor Hm.  For an element whose bucket sum was
  * not finite the reference's gradient is zero; this ABI leaves that element's gradient UNDEFINED.  One launch each way,
  * one workgroup per example, no float atomics: bit-identical run to run.
- * Supported: G m <= 32, S <= 16, D <= 256, V and B < 2^31, 4 (D MC + T + 2 ceil(T / 64) + 16 + 2 (T + T mod 2)) <= 65536
- * bytes of LDS with MC = 16 for G m <= 16 and 32 beyond (rec_sdim_lds_bytes: the forward's sum, 0: invalid or unsupported;
- * the backward needs less).  T >= 65536 is refused as well (16-bit list entries); the LDS rule is the stricter one.
+ * Supported: G m <= REC_SDIM_MAX_BITS, S <= REC_SDIM_MAX_S, D <= REC_SEARCH_MAX_D, V and B < 2^31,
+ * 4 (D MC + T + 2 ceil(T / 64) + REC_SDIM_MAX_S + 2 (T + T mod 2)) <= REC_SEARCH_LDS_CAP bytes of LDS with MC = 16 for
+ * G m <= 16 and 32 beyond (rec_sdim_lds_bytes: the forward's sum, 0: invalid or unsupported; the backward needs less).
+ * T >= 65536 is refused as well (16-bit list entries); the LDS rule is the stricter one, which csrc/sdim.hip asserts.
  * Return codes, in this order: a size below 1 (B below 0): -1; a shape outside the limits: -2, from the sizes alone;
- * ld < E, ld_q < D, ld_gout < D or a mode other than 0 and 1: -1; B == 0: 0, nothing is launched or written; a pointer
- * that must not be NULL: -1. */
+ * ld < E, ld_q < D, ld_gout < D or a mode that is neither of the two: -1; B == 0: 0, nothing is launched or written; a
+ * pointer that must not be NULL: -1. */
 size_t rec_sdim_lds_bytes(int T, int C, int E, int G, int m, int S);
 int rec_sdim_interest_fwd_f32(const float* embed, int64_t ld, int64_t V, int E, int C, const int64_t* series, int64_t B,
                               int T, const float* q, int64_t ld_q, int S, const float* Hm, int G, int m,

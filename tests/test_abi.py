@@ -121,7 +121,74 @@ def _limit_cases():
         ("REC_MASKNET_MAX_O", lambda v: blk(4, 8, 8, v, 2)),
         ("REC_MASKNET_MAX_R", lambda v: blk(4, 8, 8, 4, v)),
     ]
+    # The families after DIN answer through their LDS, workspace or scratch queries.  A limit that several families
+    # share by design gets a case per family; a series of 32 steps holds one selected position past the limit (K <= T)
+    sim, eta, sdim, esu = (lib.rec_sim_search_lds_bytes, lib.rec_eta_search_lds_bytes, lib.rec_sdim_lds_bytes,
+                           lib.rec_esu_attn_lds_bytes)
+    cases += [
+        ("REC_CAPSULE_MAX_R:mind", lambda v: lib.rec_mind_routing_workspace_bytes(4, 2, 4, 1, 4, 2, v)),
+        ("REC_CAPSULE_MAX_R:comirec", lambda v: lib.rec_comirec_dr_workspace_bytes(4, 2, 4, 1, 4, 2, v)),
+        ("REC_SINE_MAX_L", lambda v: lib.rec_sine_lds_bytes(2, 4, 1, v, 1)),
+        ("REC_CAN_MAX_L:layers", lambda v: lib.rec_can_lds_bytes(2, 4, v, _ints(*[1] * v), 1)),
+        ("REC_CAN_MAX_L:order", lambda v: lib.rec_can_lds_bytes(2, 4, 1, _ints(1), v)),
+        ("REC_SEARCH_MAX_D:sim", lambda v: sim(32, 1, v, 2)),
+        ("REC_SEARCH_MAX_D:eta", lambda v: eta(32, 1, v, 4, 2)),
+        ("REC_SEARCH_MAX_D:sdim", lambda v: sdim(32, 1, v, 2, 2, 2)),
+        ("REC_SEARCH_MAX_K:sim", lambda v: sim(32, 1, 4, v)),
+        ("REC_SEARCH_MAX_K:eta", lambda v: eta(32, 1, 4, 4, v)),
+        ("REC_SEARCH_MAX_K:esu", lambda v: esu(v, 4, 1, 4)),
+        ("REC_ESU_MAX_H", lambda v: esu(2, 4, v, 4)),
+        ("REC_ETA_MAX_M", lambda v: eta(32, 1, 4, v, 2)),
+        ("REC_SDIM_MAX_BITS:one group", lambda v: sdim(32, 1, 4, 1, v, 2)),
+        ("REC_SDIM_MAX_S", lambda v: sdim(32, 1, 4, 2, 2, v)),
+    ]
     return cases
+
+
+def _last_fit(nbytes, cap):
+    """the largest T >= 1 with nbytes(T) <= cap, for an nbytes that grows with T (by bisection)"""
+    lo, hi = 1, 2
+    assert nbytes(lo) <= cap
+    while nbytes(hi) <= cap:
+        lo, hi = hi, 2 * hi
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if nbytes(mid) <= cap else (lo, mid)
+    return lo
+
+
+def _cap_cases():
+    """(define, nbytes, query): a launch cap of the header, the Python formula of a kernel's LDS as a function of the
+    series length T (ops.py's *_lds_bytes, which the family host tests hold against the library's own answers) and the
+    family's size query at that T, every other size small enough that only the cap can refuse the shape."""
+    from explicit_tf2_recommendation_amd import ops
+    from explicit_tf2_recommendation_amd._lib import lib
+    tile, search = "REC_TILE_LDS_CAP", "REC_SEARCH_LDS_CAP"
+    return [
+        (tile + ":mind routing", lambda T: ops.mind_routing_lds_bytes(T, 48, 48, 4, 3),
+         lambda T: lib.rec_mind_routing_workspace_bytes(4, T, 48, 1, 48, 4, 3)),
+        (tile + ":mind attention", lambda Ns: ops.mind_laa_lds_bytes(Ns, 48, 4),
+         lambda Ns: lib.rec_mind_laa_lds_bytes(Ns, 48, 1, 4)),
+        (tile + ":comirec routing", lambda T: ops.comirec_dr_lds_bytes(T, 48, 3),
+         lambda T: lib.rec_comirec_dr_workspace_bytes(4, T, 48, 1, 48, 4, 3)),
+        (tile + ":comirec self-attentive", lambda T: ops.comirec_sa_lds_bytes(T, 48, 48, 4),
+         lambda T: lib.rec_comirec_sa_workspace_bytes(4, T, 48, 1, 48, 4)),
+        (tile + ":comirec hard attention", lambda Ns: ops.mind_laa_lds_bytes(Ns, 48, 4),
+         lambda Ns: lib.rec_comirec_select_lds_bytes(Ns, 48, 1, 4)),
+        (tile + ":sine", lambda T: ops.sine_lds_bytes(T, 48, 100, 5),
+         lambda T: lib.rec_sine_lds_bytes(T, 48, 1, 100, 5)),
+        (tile + ":can", lambda T: ops.can_lds_bytes(T, 16, (1, 1, 1), 3),
+         lambda T: lib.rec_can_lds_bytes(T, 16, 3, _ints(1, 1, 1), 3)),
+        (tile + ":dmr", lambda T: ops.dmr_lds_bytes(T, 48, 48, 6), lambda T: lib.rec_dmr_lds_bytes(T, 48, 1, 48, 6)),
+        (tile + ":dien", lambda T: ops.dien_lds_bytes(T, 128, ops.DIEN_AUGRU),
+         lambda T: lib.rec_dien_augru_lds_bytes(T, 128, ops.DIEN_AUGRU)),
+        (search + ":sim", lambda T: ops.sim_search_lds_bytes(T, 1, 48),
+         lambda T: lib.rec_sim_search_lds_bytes(T, 1, 48, 2)),
+        (search + ":eta", lambda T: ops.eta_search_lds_bytes(T, 48, 4),
+         lambda T: lib.rec_eta_search_lds_bytes(T, 1, 48, 4, 2)),
+        (search + ":sdim", lambda T: ops.sdim_lds_bytes(T, 48, 2, 2),
+         lambda T: lib.rec_sdim_lds_bytes(T, 1, 48, 2, 2, 2)),
+    ]
 
 
 def test_header_limits_are_the_compiled_library_s():
@@ -160,6 +227,47 @@ def test_header_limits_are_the_compiled_library_s():
     assert din(wide_d + 1, wide_h) == 0 and din(wide_d + 1, wide_h + 1) == -2 and din(max_d, max_h) == -2
     seen |= {"REC_DIN_MAX_D", "REC_DIN_MAX_H", "REC_DIN_WIDE_D", "REC_DIN_WIDE_MAX_H"}
     seen |= {"REC_FIBINET_MAX_C", "REC_FIELD_CONV_BWD_GRID"}
+    # SINE's aux kernels have no size query: with NULL pointers they answer -2 from the sizes alone, and -1 for the
+    # pointers once the sizes are inside the limits
+    max_l, aux_d = LIMITS["REC_SINE_MAX_L"], LIMITS["REC_SINE_AUX_MAX_D"]
+    for aux in (lambda L, D: lib.rec_sine_aux_fwd_f32(None, L, D, None, None),
+                lambda L, D: lib.rec_sine_aux_bwd_f32(None, L, D, None, None, None)):
+        assert aux(max_l, aux_d) == -1 and aux(max_l, aux_d + 1) == -2 and aux(max_l + 1, aux_d) == -2
+    # the ESU attention's widths are even: two past the limit is the next width only the limit refuses.  D and dk alike
+    esu, esu_d = lib.rec_esu_attn_lds_bytes, LIMITS["REC_ESU_MAX_D"]
+    assert esu(2, esu_d, 1, 4) > 0 and esu(2, esu_d + 2, 1, 4) == 0
+    assert esu(2, 4, 1, esu_d) > 0 and esu(2, 4, 1, esu_d + 2) == 0
+    # SDIM's hash bits are those of all groups together
+    bits = LIMITS["REC_SDIM_MAX_BITS"]
+    assert bits % 4 == 0 and lib.rec_sdim_lds_bytes(32, 1, 4, 4, bits // 4, 2) > 0
+    assert lib.rec_sdim_lds_bytes(32, 1, 4, 3, bits // 3 + 1, 2) == 0                     # 3 groups of 11 bits at 32
+    seen |= {"REC_SINE_AUX_MAX_D", "REC_ESU_MAX_D"}
+    # The launch caps: the longest series whose LDS, by the formula the header gives, stays within the cap is accepted
+    # and the next one refused.  (The ESU attention cannot reach its cap inside its other limits; the DIN attention's
+    # tiles are held to theirs by the static_asserts of csrc/din.hip and show above as WIDE_D / WIDE_MAX_H.)
+    for key, nbytes, query in _cap_cases():
+        name = key.split(":")[0]
+        seen.add(name)
+        T = _last_fit(nbytes, LIMITS[name])
+        assert query(T) > 0, (key, T)
+        assert query(T + 1) == 0, (key, T + 1)
+    # POSO-MLP's tile grows with the widths, not with a length: two chained layers of U units behind inputs as wide as
+    # they come.  The widest U ops.py accepts under the cap is the widest the library accepts
+    from explicit_tf2_recommendation_amd import ops
+    wide = LIMITS["REC_MASKNET_MAX_D"]
+
+    def poso(U):
+        try:
+            ops.poso_mlp_check_shape(wide, wide, 1, [U, U], 1)
+        except NotImplementedError as e:
+            assert "a tile of %d bytes of LDS" % LIMITS["REC_POSO_LDS_CAP"] in str(e)
+            return False
+        return True
+    U = max(u for u in range(1, LIMITS["REC_MASKNET_MAX_O"]) if poso(u))
+    assert not poso(U + 1) and U + 1 <= LIMITS["REC_MASKNET_MAX_O"]         # the cap refused it, no other limit
+    assert lib.rec_poso_mlp_scratch_bytes(4, wide, wide, 1, 2, _ints(U, U), 1) > 0
+    assert lib.rec_poso_mlp_scratch_bytes(4, wide, wide, 1, 2, _ints(U + 1, U + 1), 1) == 0
+    seen.add("REC_POSO_LDS_CAP")
     status = {"REC_OK", "REC_E_ARG", "REC_E_UNSUPPORTED", "REC_E_WORKSPACE", "REC_MAX_COLS"}
     assert seen == set(LIMITS) - status                                # a limit added to the header gets a case here
 
@@ -178,6 +286,51 @@ def test_ops_limits_are_the_header_s():
     with pytest.raises(NotImplementedError, match="fields <= %d" % LIMITS["REC_AFM_MAX_F"]):
         ops.afm_check_shape(LIMITS["REC_AFM_MAX_F"] + 1, 4, 2)
     ops.afm_check_shape(LIMITS["REC_AFM_MAX_F"], 4, 2)
+    for name, define in (("MIND_MAX_ROUNDS", "CAPSULE_MAX_R"), ("SINE_MAX_L", "SINE_MAX_L"), ("CAN_MAX_W", "AFM_MAX_E"),
+                         ("CAN_MAX_LAYERS", "CAN_MAX_L"), ("CAN_MAX_ORDER", "CAN_MAX_L"), ("SIM_MAX_D", "ESU_MAX_D"),
+                         ("SIM_MAX_K", "SEARCH_MAX_K"), ("SIM_MAX_H", "ESU_MAX_H"), ("ETA_MAX_M", "ETA_MAX_M"),
+                         ("SDIM_MAX_BITS", "SDIM_MAX_BITS"), ("SDIM_MAX_S", "SDIM_MAX_S"),
+                         ("SDIM_MAX_D", "SEARCH_MAX_D")):
+        assert getattr(ops, name) == LIMITS["REC_" + define], name
+    rounds, concepts, can_l = LIMITS["REC_CAPSULE_MAX_R"], LIMITS["REC_SINE_MAX_L"], LIMITS["REC_CAN_MAX_L"]
+    key, top, bits = LIMITS["REC_SEARCH_MAX_D"], LIMITS["REC_SEARCH_MAX_K"], LIMITS["REC_ETA_MAX_M"]
+    esu_d, esu_h = LIMITS["REC_ESU_MAX_D"], LIMITS["REC_ESU_MAX_H"]
+    sd_bits, sd_s = LIMITS["REC_SDIM_MAX_BITS"], LIMITS["REC_SDIM_MAX_S"]
+    # (message, check, arguments one past the limit, arguments at the limit)
+    pairs = [
+        ("routing rounds <= %d" % rounds, ops.mind_check_shape, (8, 8, 2, rounds + 1), (8, 8, 2, rounds)),
+        ("routing rounds <= %d" % rounds, ops.comirec_check_shape, (8, 8, 2, rounds + 1), (8, 8, 2, rounds)),
+        ("L <= %d" % concepts, ops.sine_check_shape, (8, concepts + 1, 2), (8, concepts, 2)),
+        ("at most %d layers" % can_l, ops.can_check_shape, (4, [1] * (can_l + 1), 1), (4, [1] * can_l, 1)),
+        ("order <= %d" % can_l, ops.can_check_shape, (4, [1], can_l + 1), (4, [1], can_l)),
+        ("coef <= %d" % LIMITS["REC_AFM_MAX_E"], ops.can_check_shape, (LIMITS["REC_AFM_MAX_E"] + 1, [1], 1),
+         (LIMITS["REC_AFM_MAX_E"], [1], 1)),
+        ("series features <= %d" % key, ops.sim_check_shape, (key + 1,), (key,)),
+        ("k <= %d selected" % top, ops.sim_check_shape, (8, 32, top + 1), (8, 32, top)),
+        ("key_dim <= %d and" % esu_d, ops.sim_check_shape, (esu_d + 2, 32, 2, 1), (esu_d, 32, 2, 1)),
+        ("key_dim <= %d and" % esu_d, ops.sim_check_shape, (8, 32, 2, 1, esu_d + 2), (8, 32, 2, 1, esu_d)),
+        ("num_heads <= %d" % esu_h, ops.sim_check_shape, (8, 32, 2, esu_h + 1), (8, 32, 2, esu_h)),
+        ("series features <= %d" % key, ops.eta_check_shape, (key + 1,), (key,)),
+        ("lsh_topk <= %d" % top, ops.eta_check_shape, (8, 32, top + 1), (8, 32, top)),
+        ("lsh_dim <= %d" % bits, ops.eta_check_shape, (8, 32, 2, bits + 1), (8, 32, 2, bits)),
+        ("series features <= %d" % key, ops.sdim_check_shape, (key + 1,), (key,)),
+        ("candidates <= %d" % sd_s, ops.sdim_check_shape, (8, 32, sd_s + 1), (8, 32, sd_s)),
+        ("<= %d hash bits" % sd_bits, ops.sdim_check_shape, (8, 32, 2, 1, sd_bits + 1), (8, 32, 2, 1, sd_bits)),
+    ]
+    # and the launch caps, one family each: the longest series the Python formula fits, and the next
+    tile, search = LIMITS["REC_TILE_LDS_CAP"], LIMITS["REC_SEARCH_LDS_CAP"]
+    T = _last_fit(lambda T: ops.can_lds_bytes(T, 16, (1, 1, 1), 3), tile)
+    pairs.append(("<= %d bytes" % tile, ops.can_check_shape, (16, (1, 1, 1), 3, T + 1), (16, (1, 1, 1), 3, T)))
+    T = _last_fit(lambda T: ops.sim_search_lds_bytes(T, 1, 48), search)
+    pairs.append(("<= %d bytes" % search, ops.sim_check_shape, (48, T + 1), (48, T)))
+    T = _last_fit(lambda T: ops.eta_search_lds_bytes(T, 48, 4), search)
+    pairs.append(("<= %d bytes" % search, ops.eta_check_shape, (48, T + 1, 2, 4), (48, T, 2, 4)))
+    T = _last_fit(lambda T: ops.sdim_lds_bytes(T, 48, 2, 2), search)
+    pairs.append(("<= %d bytes" % search, ops.sdim_check_shape, (48, T + 1, 2, 2, 2), (48, T, 2, 2, 2)))
+    for message, check_shape, past, at in pairs:
+        with pytest.raises(NotImplementedError, match=re.escape(message)):
+            check_shape(*past)
+        check_shape(*at)
 
 
 def test_ops_codes_are_the_header_s_and_the_header_s_are_frozen():
@@ -190,14 +343,24 @@ def test_ops_codes_are_the_header_s_and_the_header_s_are_frozen():
               "REC_EPI_BIAS_TANH": 4, "REC_EPI_CROSS": 5, "REC_EPI_ADD": 6,
               "REC_ACT_NONE": 0, "REC_ACT_RELU": 1, "REC_ACT_SIGMOID": 2, "REC_ACT_TANH": 3,
               "REC_DACT_NONE": 0, "REC_DACT_RELU": 1, "REC_DACT_SIGMOID": 2, "REC_DACT_TANH": 3, "REC_DACT_DICE": 4,
-              "REC_DACT_PRELU": 5}
-    codes = {k: v for k, v in ENUMS.items() if k.startswith(("REC_EPI_", "REC_ACT_", "REC_DACT_"))}
+              "REC_DACT_PRELU": 5,
+              "REC_FIBINET_TYPE_ALL": 0, "REC_FIBINET_TYPE_EACH": 1, "REC_FIBINET_TYPE_INTERACTION": 2,
+              "REC_AUTOINT_RES_NONE": 0, "REC_AUTOINT_RES_ADD": 1, "REC_AUTOINT_RES_LEARNED": 2,
+              "REC_DIEN_GRU": 0, "REC_DIEN_AUGRU": 1, "REC_DIEN_AGRU": 2,
+              "REC_SDIM_MODE_REFERENCE": 0, "REC_SDIM_MODE_VALID": 1}
+    modes = ("REC_FIBINET_TYPE_", "REC_AUTOINT_RES_", "REC_SDIM_MODE_")    # bound as the values of a dict of ops.py
+    codes = {k: v for k, v in ENUMS.items() if k.startswith(("REC_EPI_", "REC_ACT_", "REC_DACT_", "REC_DIEN_") + modes)}
     assert codes == frozen
     bound = {n: getattr(ops, n) for n in dir(ops)
-             if n.startswith(("EPI_", "ACT_", "DACT_")) and isinstance(getattr(ops, n), int)}
-    assert bound == {k[len("REC_"):]: v for k, v in frozen.items()}    # every code has its name in ops.py, and no other
-    for n, v in bound.items():
+             if n.startswith(("EPI_", "ACT_", "DACT_", "DIEN_")) and isinstance(getattr(ops, n), int)}
+    assert bound == {k[len("REC_"):]: v for k, v in frozen.items() if not k.startswith(modes)}
+    for n, v in bound.items():                                         # every code has its name in ops.py, and no other
         assert v == ENUMS["REC_" + n], n
+    assert ops.DIEN_MODE == {"AUGRU": ENUMS["REC_DIEN_AUGRU"], "AGRU": ENUMS["REC_DIEN_AGRU"]}
+    assert ops.FIBINET_TYPES == {k: ENUMS["REC_FIBINET_TYPE_" + k.upper()] for k in ("all", "each", "interaction")}
+    assert ops.SDIM_MODES == {k: ENUMS["REC_SDIM_MODE_" + k.upper()] for k in ("reference", "valid")}
+    none, add, learned = (ENUMS["REC_AUTOINT_RES_" + k] for k in ("NONE", "ADD", "LEARNED"))
+    assert ops.AUTOINT_RES == {(False, False): none, (False, True): none, (True, False): add, (True, True): learned}
     assert not [k for k in ENUMS if k.startswith("REC_MASKNET_") or re.search(r"_MAX_\w+$", k)]
     assert set(ENUMS) == set(frozen)                                   # an enumerator added to the header gets a line here
 

@@ -85,7 +85,8 @@ def test_abi_names_and_signatures():
         assert _lib.SIGNATURES[name] == sig, name
         assert hasattr(_lib.lib, name)
     assert not [n for n in _lib.SIGNATURES if n.startswith("rec_eta_") and n not in want]      # no backward kernel
-    assert not [k for k in _lib.LIMITS if "ETA" in k]
+    # the family's one limit of its own is a define of the header (key width, top-k and launch cap are the searches')
+    assert {k: v for k, v in _lib.LIMITS.items() if "ETA" in k} == {"REC_ETA_MAX_M": 32}
 
 
 def test_size_query_and_the_supported_range():
