@@ -763,8 +763,8 @@ constexpr int LN_MAXJ = 16;
 
 __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                             const float* __restrict__ beta, int64_t M, int N,
-                                                            float* __restrict__ y, float* __restrict__ xhat,
-                                                            float* __restrict__ rstd) {
+                                                            float eps, float* __restrict__ y,
+                                                            float* __restrict__ xhat, float* __restrict__ rstd) {
   int lane = threadIdx.x & 63;
   int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= M) return;
@@ -784,7 +784,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
     float d = n < N ? v[j] - mu : 0.f;
     q += d * d;
   }
-  float r = rsqrtf(group_sum<64>(q) / (float)N + LN_EPS);
+  float r = rsqrtf(group_sum<64>(q) / (float)N + eps);
 #pragma unroll
   for (int j = 0; j < LN_MAXJ; ++j) {
     int n = lane + 64 * j;
@@ -1022,16 +1022,22 @@ extern "C" int rec_feat_act_bwd_f32(int kind, const float* x, const float* gy, c
   return REC_OK;
 }
 
-extern "C" int rec_layernorm_fwd_f32(const float* x, const float* gamma, const float* beta, int64_t M, int N, float* y,
-                                     float* xhat, float* rstd, void* stream) {
-  if (M < 0 || N <= 0) return REC_E_ARG;
+// eps > 0 and finite; rec_layernorm_fwd_f32 is this with Keras' default
+extern "C" int rec_layernorm_eps_fwd_f32(const float* x, const float* gamma, const float* beta, int64_t M, int N,
+                                         float eps, float* y, float* xhat, float* rstd, void* stream) {
+  if (M < 0 || N <= 0 || !(eps > 0.f) || !(eps <= 3.402823466e38f)) return REC_E_ARG;
   if (N > 64 * LN_MAXJ) return REC_E_UNSUPPORTED;
   if (M == 0) return REC_OK;
   if (!x || !gamma || !beta || !y) return REC_E_ARG;
   hipLaunchKernelGGL(layernorm_fwd_kernel, dim3((unsigned)ceil_div64(M, 4)), dim3(256), 0, as_stream(stream), x, gamma,
-                     beta, M, N, y, xhat, rstd);
+                     beta, M, N, eps, y, xhat, rstd);
   REC_LAUNCH_CHECK();
   return REC_OK;
+}
+
+extern "C" int rec_layernorm_fwd_f32(const float* x, const float* gamma, const float* beta, int64_t M, int N, float* y,
+                                     float* xhat, float* rstd, void* stream) {
+  return rec_layernorm_eps_fwd_f32(x, gamma, beta, M, N, LN_EPS, y, xhat, rstd, stream);
 }
 
 extern "C" int rec_layernorm_bwd_f32(const float* gy, const float* xhat, const float* rstd, const float* gamma, int64_t M,

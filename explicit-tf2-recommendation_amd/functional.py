@@ -320,11 +320,11 @@ class FeatAct(torch.autograd.Function):
 
 
 class LayerNorm(torch.autograd.Function):
-    """tf.keras.layers.LayerNormalization() over the last axis, epsilon 1e-3."""
+    """tf.keras.layers.LayerNormalization(epsilon) over the last axis; ``epsilon`` None: Keras' default 1e-3."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta):
-        y, xhat, rstd = ops.layernorm_fwd(x.contiguous(), gamma, beta)
+    def forward(ctx, x, gamma, beta, epsilon=None):
+        y, xhat, rstd = ops.layernorm_fwd(x.contiguous(), gamma, beta, epsilon)
         ctx.save_for_backward(xhat, rstd, gamma)
         return y
 
@@ -333,7 +333,7 @@ class LayerNorm(torch.autograd.Function):
         xhat, rstd, gamma = ctx.saved_tensors
         gy = gy.contiguous()
         gx, gg = ops.layernorm_bwd(gy, xhat, rstd, gamma)
-        return gx, ops.colsum(gg), ops.colsum(gy)
+        return gx, ops.colsum(gg), ops.colsum(gy), None
 
 
 class Softmax(torch.autograd.Function):

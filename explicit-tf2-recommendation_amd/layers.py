@@ -1543,15 +1543,18 @@ class Activation(Layer):
 
 
 class LayerNormalization(Layer):
-    """tf.keras.layers.LayerNormalization(): last axis, epsilon 1e-3, gamma 1, beta 0."""
+    """tf.keras.layers.LayerNormalization(epsilon): last axis, gamma 1, beta 0; ``epsilon`` None is Keras' default 1e-3."""
 
-    def __init__(self, input_dim):
+    def __init__(self, input_dim, epsilon=None):
         super().__init__()
+        self.epsilon = epsilon
         self.gamma = torch.nn.Parameter(torch.ones(int(input_dim)))
         self.beta = torch.nn.Parameter(torch.zeros(int(input_dim)))
 
     def forward(self, x):
-        return Fn.LayerNorm.apply(x, self.gamma, self.beta)
+        if self.epsilon is None:
+            return Fn.LayerNorm.apply(x, self.gamma, self.beta)
+        return Fn.LayerNorm.apply(x, self.gamma, self.beta, self.epsilon)
 
 
 class SoftmaxDense(Layer):

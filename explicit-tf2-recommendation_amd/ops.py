@@ -543,11 +543,16 @@ def feat_act_bwd(kind, x, gy, alpha=None, mean=None, var=None, want_alpha=False)
     return gx, ga
 
 
-def layernorm_fwd(x, gamma, beta):
+def layernorm_fwd(x, gamma, beta, epsilon=None):
+    """``epsilon`` None: Keras' default 1e-3 through the entry point that fixes it; a given one is a positive float"""
     M, N = _f32(x, "x").shape
     _f32(gamma, "gamma"); _f32(beta, "beta")
     y, xhat, rstd = _new_like(x), _new_like(x), _new(M, x.device)
-    _call("rec_layernorm_fwd_f32", _ptr(x), _ptr(gamma), _ptr(beta), M, N, _ptr(y), _ptr(xhat), _ptr(rstd))
+    if epsilon is None:
+        _call("rec_layernorm_fwd_f32", _ptr(x), _ptr(gamma), _ptr(beta), M, N, _ptr(y), _ptr(xhat), _ptr(rstd))
+    else:
+        _call("rec_layernorm_eps_fwd_f32", _ptr(x), _ptr(gamma), _ptr(beta), M, N, float(epsilon), _ptr(y), _ptr(xhat),
+              _ptr(rstd))
     return y, xhat, rstd
 
 

@@ -552,6 +552,10 @@ int rec_feat_act_bwd_f32(int kind, const float* x, const float* gy, const float*
 /* keras LayerNormalization (epsilon 1e-3): y = xhat*gamma + beta; saves xhat [M,N] and rstd [M] */
 int rec_layernorm_fwd_f32(const float* x, const float* gamma, const float* beta, int64_t M, int N, float* y,
                           float* xhat, float* rstd, void* stream);
+/* the same with a given epsilon (finite, > 0; else -1); rec_layernorm_fwd_f32 is this at 1e-3, bit for bit.  The backward
+ * works from xhat and rstd and so serves both */
+int rec_layernorm_eps_fwd_f32(const float* x, const float* gamma, const float* beta, int64_t M, int N, float eps,
+                              float* y, float* xhat, float* rstd, void* stream);
 int rec_layernorm_bwd_f32(const float* gy, const float* xhat, const float* rstd, const float* gamma, int64_t M, int N,
                           float* gx, float* gg_elem, void* stream);
 int rec_softmax_fwd_f32(const float* x, int64_t M, int N, float* y, void* stream);
